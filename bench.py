@@ -14,14 +14,18 @@ clamp / dry mix, inputs and outputs resident in HBM.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-N = 1: the line also carries `parity` (the last timed step's output against the
-CPU oracle, same run), `roofline` (compulsory bytes of the dominant kernel /
-its event-bracketed duration), `host_io` (the same path with pinned host
-buffers in and out, PCIe-inclusive), `latency_mode` (one JACK period per call)
-and `cpu_baseline`.
+N = 1: the line also carries `roofline` (compulsory bytes of the dominant kernel /
+its event-bracketed duration, inside the timed steps); with --full also `parity`
+(the last timed step's output against the CPU oracle, same run), `host_io` (the
+same path with pinned host buffers in and out, PCIe-inclusive), `latency_mode`
+(one JACK period per call), `literal_mac` and `cpu_baseline`.  Without --full a
+run sets up, warms up, times the steps and prints the line, nothing else.
 
-N > 1 measures BOTH multi-GPU layouts in the same run (each with an untimed
-check against an unsharded engine):
+    python bench.py --full                                  (every leg named here, as the records under profiles/ were taken)
+    python bench.py --steps 20 --warmup 5 --dump-outputs D  (the last timed step's output as D/<name>.npy)
+
+N > 1 with --full measures BOTH multi-GPU layouts in the same run (each with an
+untimed check against an unsharded engine; without --full only the first):
   * output blocks sliced over the GPUs, no data-path collective (weak scaling:
     every GPU finishes --blocks blocks per step) -> `value`;
   * IR partitions sharded over the GPUs + RCCL sum-reduce of the partial wet
@@ -111,7 +115,47 @@ def parse():
     ap.add_argument("--prewarm-ms", type=float, default=300.0,
                     help="untimed: run the step back to back for this long before the --warmup steps so that the timed region "
                          "does not start on idle clocks (the driver's 20-step region is 6 ms long); reported in the line")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the same-run parity with the CPU oracle, host_io, "
+                         "latency_mode, literal_mac, cpu_baseline, the multi-pair kernel pass and, for N > 1, the north-star layouts, "
+                         "the kernels-only / collective-only times and sharded_check (the --no-* options still switch legs off). "
+                         "Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32; "
+                         "a fixed, seeded sample of the blocks where the output exceeds the size limit, with the block indices "
+                         "in DIR/<name>_blocks.npy)")
+    a = ap.parse_args()
+    if not a.full:
+        a.no_parity = a.no_host_io = a.no_latency = a.no_literal_mac = a.no_cpu_baseline = True
+        a.no_check = a.no_direct_mac = True
+        if a.layouts == "both":
+            a.layouts = "blocks"
+    return a
+
+
+DUMP_LIMIT_BYTES = 48 << 20  # (under the 64 MB a dump may take in all)
+DUMP_EDGE_BLOCKS = 64
+DUMP_SEED = 20240611
+
+
+def dump_outputs(dirname, outputs):
+    """Write {name: device tensor [2, n * 256]} as DIR/<name>.npy, float32 [2, blocks, 256].  Outputs too large for the
+    limit are sampled: the first and last DUMP_EDGE_BLOCKS blocks and a seeded choice of the rest, the same for the same
+    batch length; the block indices go to DIR/<name>_blocks.npy (float64)."""
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    per = DUMP_LIMIT_BYTES // max(len(outputs), 1) // (2 * BLOCK * 4)
+    for name, t in outputs.items():
+        nblk = t.shape[1] // BLOCK
+        v = t.reshape(2, nblk, BLOCK)
+        if nblk > per:
+            rest = np.arange(DUMP_EDGE_BLOCKS, nblk - DUMP_EDGE_BLOCKS)
+            pick = np.random.default_rng(DUMP_SEED).choice(rest, per - 2 * DUMP_EDGE_BLOCKS, replace=False)
+            idx = np.sort(np.concatenate([np.arange(DUMP_EDGE_BLOCKS), pick, np.arange(nblk - DUMP_EDGE_BLOCKS, nblk)]))
+            v = v.index_select(1, torch.from_numpy(idx).to(t.device))
+            np.save(os.path.join(dirname, name + "_blocks.npy"), idx.astype(np.float64))
+        np.save(os.path.join(dirname, name + ".npy"), v.float().cpu().numpy())
 
 
 def git_head():
@@ -522,6 +566,8 @@ def main():
             e.process_device(d_in[0, o:].data_ptr(), d_in[1, o:].data_ptr(), d_out[0].data_ptr(), d_out[1].data_ptr(), T)
 
         dt, npre = timed(step, lambda: None, a.steps, a.warmup, a.prewarm_ms)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {"output_pair0": d_out})
         calls = a.steps * T
         alg = e.algorithmic_bytes_per_block()
         traffic = 12 * a.fft_size * 8  # bytes the three kernels of a call move (header of csrc/singlefft.hip.h), cache-resident
@@ -636,6 +682,8 @@ def main():
         prewarm_s = time.perf_counter() - t_pre - dt
         ks = eng[0].kernel_stats()
         eng[0].enable_kernel_timing(False)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {f"output_pair{p}": d_out[p] for p in range(npairs)})
 
         res = {"T": T, "dt": dt, "ks": ks,
                "prewarm": {"steps": npre, "untimed_ms_before_the_timed_steps": round(prewarm_s * 1e3, 1),
@@ -703,7 +751,7 @@ def main():
                 where.append((T - 64, 64))
                 res["parity"] = oracle_parity(a, eng.irs[0], [bench_params(0), bench_params(1)], excerpt, T, got, where)
 
-        if multi:
+        if multi and a.full:
             # with the pairs on streams of their own an event bracket on one stream also spans the other pairs' kernels:
             # the dominant kernel is timed now, pair 0 alone (untimed steps, after the parity check has read its output)
             arm()
@@ -967,6 +1015,8 @@ def main():
                 retire_slices()
 
         dt, npre = timed(step, drain, a.steps, a.warmup, a.prewarm_ms)
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {f"output_pair{p}_rank{rank}": d_slices[p][(a.steps - 1) % 3] for p in range(npairs)})
         res = {"T": T, "count": count, "dt": dt, "rtf": a.steps * T * BLOCK / FS / dt, "prewarm_steps": npre}
         if not a.no_check:
             for e in eng:
@@ -1091,6 +1141,8 @@ def main():
 
         dt, npre = timed(step, drain, max(2, a.steps // 4) if direct else a.steps, min(a.warmup, 2) if direct else a.warmup, 0.0 if direct else a.prewarm_ms)
         nsteps = max(2, a.steps // 4) if direct else a.steps
+        if a.dump_outputs and not direct and a.layouts == "partitions" and (rs or rank == 0 or not root_only_):  # (the headline layout only)
+            dump_outputs(a.dump_outputs, {f"output_pair{p}_rank{rank}": d_out[p] for p in range(npairs)})
         lv = None
         n = shard_world
         sent = int(npairs * 2 * T * BLOCK * 4 * ((n - 1) / n if rs else (1.0 if root_only_ else 2.0 * (n - 1) / n)))
@@ -1098,7 +1150,7 @@ def main():
                "collective": coll, "blocks_finished_per_rank": Ts, "reduce_bytes_per_step": int(npairs * 2 * T * BLOCK * 4),
                "reduce_bytes_per_rank_per_step": sent}
         # what the first hardware run should explain by itself: the kernels alone, the collective alone, and which one binds
-        if world > 1 and a.backend == "nccl":
+        if world > 1 and a.backend == "nccl" and a.full:
             nk = max(4, min(a.steps, 20))
             dt_comp, _ = timed(lambda k: step(k, with_collective=False), drain, nk, 2)
             part, ssum = d_parts[0], (d_sums[0] if rs else None)
@@ -1269,6 +1321,8 @@ def main():
             roofline["note"] = ("streaming MAC: every block re-reads IR spectra and delay line; achieved = SURVEY 8(d) bytes x blocks / "
                                 "kernel time. With many blocks per launch the working set is served from L2 / Infinity Cache, so "
                                 "achieved can exceed the HBM peak.")
+        if not ks["launches"]:
+            roofline = {"skipped": "no kernel was timed: with several pairs the dominant kernel is timed in a pass of its own (--full)"}
         line.update({
             "value": round(rtf, 2),
             "ms_per_step": round(dt / a.steps * 1e3, 4),

@@ -10,7 +10,7 @@ for round in 1 2 3; do
     ( if [ "$v" != "default" ]; then
         if [[ "$v" == *=* ]]; then IFS=',' read -ra kv <<< "$v"; for x in "${kv[@]}"; do export "$x"; done; else export MCCONV_LIB=$PWD/$v; fi
       fi
-      python bench.py --steps 40 --warmup 5 --no-cpu-baseline --no-latency --no-host-io $EXTRA 2>/dev/null | python -c "
+      python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --no-latency --no-host-io $EXTRA 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); r=d['roofline']; print('[$v]', 'rtf', d['value'], 'ms/step', d['ms_per_step'], r['kernel'], r['kernel_avg_ms'], 'frac', r['frac'], 'parity', d['parity']['rms_err'] if d.get('parity') else None)" )
   done
 done

@@ -2,7 +2,7 @@
 # A/B of the overlap-save form against the second-level-transform path on the headline step, plus per-kernel times
 set -e
 mkdir -p gpurun_out
-F="--no-cpu-baseline --no-latency --no-host-io --steps 20 --warmup 5"
+F="--full --no-cpu-baseline --no-latency --no-host-io --steps 20 --warmup 5"
 MCCONV_OS=0 python bench.py $F > gpurun_out/os_ab_off.json 2> gpurun_out/os_ab_off.err
 python bench.py $F > gpurun_out/os_ab_on.json 2> gpurun_out/os_ab_on.err
 cd /tmp && export TMPDIR=/tmp

@@ -8,7 +8,7 @@ cd $REPO
 timeout -k 10 600 python -m pytest tests -m gpu -x -q -k "q8 or tail_drop or predelay or shipped or Q8" > $OUT/tests.log 2>&1 || { tail -30 $OUT/tests.log; exit 1; }
 tail -2 $OUT/tests.log
 cd /tmp && export TMPDIR=/tmp
-A="--steps 20 --warmup 3 --prewarm-ms 100 --no-cpu-baseline --no-latency --no-host-io --shipped-defaults $@"
+A="--full --steps 20 --warmup 3 --prewarm-ms 100 --no-cpu-baseline --no-latency --no-host-io --shipped-defaults $@"
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $REPO/bench.py $A > $OUT/bench.json 2> $OUT/bench.err || { tail -5 $OUT/bench.err; exit 1; }
 python3 - <<PY
 import csv, glob, json

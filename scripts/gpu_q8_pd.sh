@@ -4,7 +4,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/q8pd
 mkdir -p $OUT
 cd $REPO
-A="--steps 10 --warmup 2 --prewarm-ms 100 --no-cpu-baseline --no-latency --no-host-io --fft-size 131072 --taps 130048 --same-ir"
+A="--full --steps 10 --warmup 2 --prewarm-ms 100 --no-cpu-baseline --no-latency --no-host-io --fft-size 131072 --taps 130048 --same-ir"
 for pd in 1024 4160 8192; do
   for v in "MCCONV_TD_FFT=1" "MCCONV_TD_FFT=1 MCCONV_HTAIL=0" "MCCONV_TD_FFT=0"; do
     env $v timeout -k 10 200 python3 bench.py $A --predelay $pd > $OUT/o.json 2> $OUT/o.err || { tail -5 $OUT/o.err; exit 1; }

@@ -3,10 +3,10 @@
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p gpurun_out/r3
 run() { name=$1; shift; timeout -k 10 400 python bench.py "$@" > gpurun_out/r3/$name.json 2> gpurun_out/r3/$name.err || { echo "$name failed"; tail -3 gpurun_out/r3/$name.err; }; }
-run bench_cfg3 --steps 200 --warmup 20
-run shipped_defaults --shipped-defaults --steps 100 --warmup 10
+run bench_cfg3 --full --steps 200 --warmup 20
+run shipped_defaults --full --shipped-defaults --steps 100 --warmup 10
 for T in 256 1024 4096 8192 32320 129296; do
-  run sweep_T$T --blocks $T --steps 100 --warmup 10 --no-cpu-baseline --no-latency --no-host-io
+  run sweep_T$T --full --blocks $T --steps 100 --warmup 10 --no-cpu-baseline --no-latency --no-host-io
 done
 python - <<'PY'
 import json, glob

@@ -7,7 +7,8 @@ mkdir -p gpurun_out
 timeout -k 10 900 python -m pytest tests -m gpu -x -q > gpurun_out/full_suite.txt 2>&1
 rc=$?; tail -2 gpurun_out/full_suite.txt; [ $rc -eq 0 ] || exit $rc
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
-python bench.py > gpurun_out/r4_bench_cfg3.json 2> gpurun_out/r4_bench_cfg3.err; tail -c 200 gpurun_out/r4_bench_cfg3.json; echo
+RUNS=${RUNS:-runs}; mkdir -p $RUNS
+python bench.py --full > $RUNS/r4_bench_cfg3.json 2> $RUNS/r4_bench_cfg3.err; tail -c 200 $RUNS/r4_bench_cfg3.json; echo
 {
   echo "== spaced calls (500 us idle), median / p90 / mean per run of 3000, alternating libraries"
   CALLS=3000 bash scripts/gpu_jack_p50.sh default build_ab/lib_fft0.so

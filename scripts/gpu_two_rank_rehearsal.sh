@@ -1,13 +1,14 @@
 #!/bin/bash
-# bench.py's N > 1 flow end to end on ONE GPU, started the way the driver starts it (plain `python bench.py --gpus 2`: the ranks are
+# bench.py's N > 1 flow end to end on ONE GPU, started as a user starts it (`python bench.py --full --gpus 2`: the ranks are
 # its own child processes): two ranks share the card, gloo in place of RCCL (the numbers mean nothing; what counts is that all three
 # layouts run and the sharded_check entries are ~1e-8)
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p gpurun_out
-timeout -k 10 900 python bench.py --gpus 2 --backend gloo --steps 4 --warmup 2 "$@" > gpurun_out/b_2rank.json 2> gpurun_out/b_2rank.err || { tail -8 gpurun_out/b_2rank.err; exit 1; }
+export RUNS=${RUNS:-runs}; mkdir -p $RUNS
+timeout -k 10 900 python bench.py --full --gpus 2 --backend gloo --steps 4 --warmup 2 "$@" > $RUNS/b_2rank.json 2> $RUNS/b_2rank.err || { tail -8 $RUNS/b_2rank.err; exit 1; }
 python - <<'PY'
-import json
-d = json.loads(open("gpurun_out/b_2rank.json").read().strip().splitlines()[-1])
+import json, os
+d = json.loads(open(os.path.join(os.environ["RUNS"], "b_2rank.json")).read().strip().splitlines()[-1])
 print(d["n_gpus"], d["value"], d["ms_per_step"], d["scaling"], d["config"]["blocks_per_step"], d.get("sharded_check"))
 for k in ("north_star_layout", "north_star_layout_direct_mac"):
     n = d.get(k) or {}

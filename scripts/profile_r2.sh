@@ -8,8 +8,8 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/prof_r2_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="$REPO/bench.py --steps 10 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --no-latency --no-host-io --no-parity $@"
-echo "bench.py --steps 10 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --no-latency --no-host-io --no-parity $@" > $OUT/command.txt
+ARGS="$REPO/bench.py --full --steps 10 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --no-latency --no-host-io --no-parity $@"
+echo "bench.py --full --steps 10 --warmup 2 --prewarm-ms 0 --no-cpu-baseline --no-latency --no-host-io --no-parity $@" > $OUT/command.txt
 # (the duration pass with the clocks warm, like the bench itself: 100 ms of untimed steps first; the counter passes without)
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 ${ARGS/--prewarm-ms 0/--prewarm-ms 100} > $OUT/stats.log 2>&1 || { tail -5 $OUT/stats.log; exit 1; }
 pass() {  # name, counters

@@ -1,9 +1,11 @@
 """Rows f-2 / f-4 / a15 / f-1 pinned by material the reference itself holds.
 
-Container-only CPU tests: they read /root/reference (the settings file, the 153 impulse responses and the index files
-the reference ships, and - compiled host-only where they lie, by oracle/Makefile's `ref` target - its own settings.cu
-and log.cu) and are skipped wherever that directory is absent (the GPU box).  Nothing of the reference is copied into
-the repository or travels with it: the expected values are recomputed from the reference's files at test time.
+CPU tests.  The settings parser is pinned everywhere: the reference's shipped settings.txt and the answers its own
+parser (settings.cu + log.cu, compiled host-only where they lie by oracle/Makefile's `ref` target) gave are stored under
+tests/golden/reference_settings/ (tests/golden/make_reference_settings.py records them); where that binary exists the
+test asks it again and holds the stored answers to it.  The WAV and loader-loop tests read the reference's 153 impulse
+responses and index files (50 MB, too large to store) and run only where the reference tree is present.  No source of
+the reference is copied into the repository.
 
 What is pinned here and what is not: the settings grammar and typed getters (src/settings.cu:4-24, 51-55 against the
 reference's own code), the WAV decode (src/wav.cu:4-118 against an independent decode of the shipped files' bytes),
@@ -21,14 +23,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference"
 HOST = os.path.join(ROOT, "cuda_audio_amd", "host")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "src")), reason="the reference tree is not present on this machine")
+GOLD = os.path.join(ROOT, "tests", "golden", "reference_settings")
+REF_DUMP = os.path.join(ROOT, "oracle", "_ref", "ref_settings_dump")  # (built only where the reference's sources are)
+SETTINGS = os.path.join(GOLD, "settings.txt")  # the reference's shipped settings.txt, byte for byte
+needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "ir")), reason="the reference's impulse responses are not present on this machine")
 
 
 @pytest.fixture(scope="module")
 def built():
     subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s", "-B", "ref"])  # (always from the current sources: the outputs are not tracked)
     subprocess.check_call(["make", "-C", HOST, "-s", "mcconv_host_tool", "mcconv_host_stub"])
-    return dict(ref=os.path.join(ROOT, "oracle", "_ref", "ref_settings_dump"), host=os.path.join(ROOT, "oracle", "_ref", "host_settings_dump"),
+    return dict(host=os.path.join(ROOT, "oracle", "_ref", "host_settings_dump"),
                 tool=os.path.join(HOST, "mcconv_host_tool"), stub=os.path.join(HOST, "mcconv_host_stub"))
 
 
@@ -62,6 +67,44 @@ def _dump(exe, path, requests, out_path):
         return f.read()
 
 
+TYPES = ("str", "u8", "u16", "u32", "f32", "isTrue", "isFalse")
+GRAMMAR_CASES = {
+    "comments": "# a comment\n#another one\nkey.a 1 # not a comment: the next token is a key\nkey.b\t2\n#tail comment without newline",
+    "missing_value": "key.a 5\nkey.b 7\nlast.key",
+    "crlf": "key.a 1\r\nkey.b two\r\n# c\r\nkey.c 3.5\r\n",
+    "repeat": "key.a 1\nkey.a 2\nkey.b yes\nkey.c true\nkey.d no\nkey.e TRUE\n",
+    "numbers": "n.neg -1\nn.plus +7\nn.hex 0x1F\nn.exp 1e3\nn.frac 0.1\nn.trail 12abc\nn.big 70000\nn.300 300\nn.space    42   \nn.fexp 2.5e-3\nn.inf inf\n"
+               "n.huge 99999999999\nn.dot .5\nn.neg0 -0.0\n",
+    "empty": "",
+    "only_comment": "# nothing here",
+}
+
+
+def shipped_requests():
+    """main.cu's getter calls, every key of the shipped file through every getter, missing keys."""
+    with open(SETTINGS) as f:
+        keys = [ln.split()[0] for ln in f if ln.strip() and not ln.lstrip().startswith("#")]
+    requests = _main_cu_requests(2)
+    requests += [(t, k) for k in keys for t in TYPES]
+    requests += [(t, f"no.such.key.{t}") for t in TYPES] + [("u32", "conv[2].fftSize"), ("str", "conv[7].index")]
+    return keys, requests
+
+
+def case_requests(text):
+    ks = sorted({tok for tok in text.replace("\r", " ").replace("\t", " ").replace("\n", " ").split(" ") if tok and not tok[0].isdigit()})
+    return [(t, k) for k in ks if not k.startswith("#") for t in TYPES] + [("u32", "absent")]
+
+
+def reference_dump(name, path, requests, out_path):
+    """What the reference's parser answers: the stored answers (tests/golden/reference_settings/<name>.ref.txt), held to the
+    reference's own binary wherever oracle/_ref could build it."""
+    with open(os.path.join(GOLD, name + ".ref.txt")) as f:
+        stored = f.read()
+    if os.path.exists(REF_DUMP):
+        assert _dump(REF_DUMP, path, requests, out_path) == stored, f"{name}: rerun tests/golden/make_reference_settings.py"
+    return stored
+
+
 def test_settings_parser_agrees_with_the_reference_parser(built, tmp_path):
     """host/settings.cpp and the reference's settings.cu (compiled host-only, oracle/_ref) give the same answers, byte
     for byte: every key main.cu reads from the shipped settings.txt, through the typed getter main.cu uses; every key of
@@ -70,15 +113,13 @@ def test_settings_parser_agrees_with_the_reference_parser(built, tmp_path):
     leaves behind, visible in the final dump of the map); and files that stress the grammar (comments with and without
     a space, a comment as the last line without a newline, a key whose value is missing at the end of the file, CR LF
     line ends, tabs, a repeated key, numbers with signs, exponents, hex and trailing text, values that wrap u8 / u16)."""
-    shipped = os.path.join(REF, "settings.txt")
-    with open(shipped) as f:
-        keys = [ln.split()[0] for ln in f if ln.strip() and not ln.lstrip().startswith("#")]
+    shipped = SETTINGS
+    if os.path.exists(os.path.join(REF, "settings.txt")):
+        with open(os.path.join(REF, "settings.txt"), "rb") as f, open(shipped, "rb") as g:
+            assert f.read() == g.read()  # the stored copy is the shipped file
+    keys, requests = shipped_requests()
     assert len(keys) == 47 and keys[0] == "conv.count"
-    types = ("str", "u8", "u16", "u32", "f32", "isTrue", "isFalse")
-    requests = _main_cu_requests(2)
-    requests += [(t, k) for k in keys for t in types]
-    requests += [(t, f"no.such.key.{t}") for t in types] + [("u32", "conv[2].fftSize"), ("str", "conv[7].index")]
-    a = _dump(built["ref"], shipped, requests, str(tmp_path / "ref.txt"))
+    a = reference_dump("shipped", shipped, requests, str(tmp_path / "ref.txt"))
     b = _dump(built["host"], shipped, requests, str(tmp_path / "host.txt"))
     assert a == b
     lines = a.splitlines()
@@ -88,22 +129,12 @@ def test_settings_parser_agrees_with_the_reference_parser(built, tmp_path):
     assert "u8 conv[0].index ! throw" in lines  # "./ir/all.index" is not a number
     assert "entry no.such.key.u32 [] key=[]" in lines  # the failed lookup left an empty entry behind (operator[])
 
-    cases = {
-        "comments": "# a comment\n#another one\nkey.a 1 # not a comment: the next token is a key\nkey.b\t2\n#tail comment without newline",
-        "missing_value": "key.a 5\nkey.b 7\nlast.key",
-        "crlf": "key.a 1\r\nkey.b two\r\n# c\r\nkey.c 3.5\r\n",
-        "repeat": "key.a 1\nkey.a 2\nkey.b yes\nkey.c true\nkey.d no\nkey.e TRUE\n",
-        "numbers": "n.neg -1\nn.plus +7\nn.hex 0x1F\nn.exp 1e3\nn.frac 0.1\nn.trail 12abc\nn.big 70000\nn.300 300\nn.space    42   \nn.fexp 2.5e-3\nn.inf inf\n"
-                   "n.huge 99999999999\nn.dot .5\nn.neg0 -0.0\n",
-        "empty": "",
-        "only_comment": "# nothing here",
-    }
-    for name, text in cases.items():
+    assert len(GRAMMAR_CASES) == 7
+    for name, text in GRAMMAR_CASES.items():
         path = tmp_path / f"{name}.txt"
         path.write_bytes(text.encode())
-        ks = sorted({tok for tok in text.replace("\r", " ").replace("\t", " ").replace("\n", " ").split(" ") if tok and not tok[0].isdigit()})
-        req = [(t, k) for k in ks if not k.startswith("#") for t in types] + [("u32", "absent")]
-        ra = _dump(built["ref"], str(path), req, str(tmp_path / f"{name}.ref"))
+        req = case_requests(text)
+        ra = reference_dump(name, str(path), req, str(tmp_path / f"{name}.ref"))
         rb = _dump(built["host"], str(path), req, str(tmp_path / f"{name}.host"))
         assert ra == rb, name
     nums = _dump(built["host"], str(tmp_path / "numbers.txt"), [("u8", "n.300"), ("u16", "n.big"), ("u32", "n.trail"), ("u32", "n.hex"), ("f32", "n.exp")],
@@ -146,6 +177,7 @@ def _decode_like_wav_cu(raw):
                      data_size=data_size, file_size=len(raw))
 
 
+@needs_reference
 def test_wav_decode_of_every_shipped_impulse_response(built, oracle_mod, tmp_path):
     """host/wav.cpp (through host_tool wavdump) against an independent decode of the raw bytes, bit for bit, for all 153
     files under the reference's ir/ (52 x 16 bit + 101 x 24 bit): samples, numFrames, and - since wav.cpp searches the
@@ -204,6 +236,7 @@ def test_wav_decode_of_every_shipped_impulse_response(built, oracle_mod, tmp_pat
 # ---------------------------------------------------------------------------------------------------------------------
 # f-1 / f-4: the loader loop of main() on the shipped settings.txt and ir/all.index, engine replaced by a call logger
 # ---------------------------------------------------------------------------------------------------------------------
+@needs_reference
 def test_main_walks_the_shipped_settings_and_index(built, tmp_path):
     """The unmodified host (main.cpp, conv.cpp, wav.cpp, settings.cpp, jackclient.cpp + fake JACK) linked against
     tests/stub/stub_engine.cpp runs in the reference's directory on the reference's own settings.txt: one Convolution of
