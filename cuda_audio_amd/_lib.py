@@ -18,7 +18,7 @@ MC_MAX_PREDELAY = 8192
 # every symbol include/mcconv.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "mc_abi_version", "mc_last_error", "mc_default_config", "mc_default_params", "mc_create", "mc_destroy",
-    "mc_reset", "mc_set_period", "mc_load_ir", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
+    "mc_reset", "mc_set_period", "mc_load_ir", "mc_load_ir_resampled", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
     "mc_enable_kernel_timing", "mc_get_kernel_stats", "mc_algorithmic_bytes_per_block", "mc_blocks_processed", "mc_preferred_batch",
@@ -110,6 +110,7 @@ def load():
     L.mc_reset.argtypes = [vp]
     L.mc_set_period.argtypes = [vp, C.c_uint32]
     L.mc_load_ir.argtypes = [vp, u64, fp, u64, u64]
+    L.mc_load_ir_resampled.argtypes = [vp, u64, fp, u64, u64, C.c_uint32, C.c_uint32]
     L.mc_num_irs.argtypes = [vp]
     L.mc_ir_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_set_params.argtypes = [vp, C.c_int, C.POINTER(McCcValue)]

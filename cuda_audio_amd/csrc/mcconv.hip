@@ -25,6 +25,7 @@
 #include "kernels.hip.h"
 #include "ossave.hip.h"
 #include "singlefft.hip.h"
+#include "resample.hip.h"
 
 // Environment switches.  The default library reads ten - MCCONV_FORM, _OS, _FFT2, _FFT2_FUSED, _FFA_LEVELS (which form sums the
 // partitions), _TD_FFT (Q8 cut terms in the time domain), _NO_PARK, _PARK_MS, _NO_SPIN, _BAR_IO (the JACK path's waiting and I/O) -
@@ -3393,15 +3394,21 @@ int mc_set_period(mc_engine* e, uint32_t nframes) {
     return e->sf ? sf_zero(e) : zero_state(e);  // the per-call semantics change: start from the cold state
 }
 
-int mc_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes) {
+}  // extern "C"
+
+namespace {
+// mc_load_ir and mc_load_ir_resampled: rs = {IR rate, session rate} converts the frames on the device (resample.hip.h)
+// before anything else sees them; null = the frames as given (the reference)
+int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs) {
     // Convolution::prepare, conv.cu:207-253
     if (!e || !lr) return fail(MC_ERR_ARG, "null argument");
     if (idx >= (uint64_t)kMaxIrs) return fail(MC_ERR_ARG, "IR index %llu >= %d", (unsigned long long)idx, kMaxIrs);
     if (nframes >= e->cfg.n_ref) return fail(MC_ERR_ARG, "nframes >= n_ref");
     if (frames == 0) return fail(MC_ERR_ARG, "empty IR");
+    const uint64_t conv = rs ? rs_out_frames(rs_geom(rs[0], rs[1]), frames) : frames;  // frames at the session's rate
     HIP_TRY(hipSetDevice(e->device));
-    if (e->sf) return sf_load_ir(e, idx, lr, frames, nframes);
-    const uint64_t n = std::min<uint64_t>(frames, e->cfg.n_ref - nframes);  // conv.cu:239
+    if (e->sf) return sf_load_ir(e, idx, lr, frames, nframes, rs);
+    const uint64_t n = std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
     const int P = (int)((n + MC_B - 1) / MC_B);
     if (P > e->Pcap) return fail(MC_ERR_ARG, "IR needs %d partitions, engine capacity is %d", P, e->Pcap);
     IrEntry& ir = e->irs[idx];
@@ -3414,7 +3421,9 @@ int mc_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uin
     if (!ir.d_H) HIP_TRY(hipMalloc(&ir.d_H, sizeof(float4) * (size_t)MC_NB * e->Pstride));
     float* d_lr = nullptr;
     HIP_TRY(hipMalloc(&d_lr, sizeof(float) * 2 * n));
-    hipError_t er = hipMemcpy(d_lr, lr, sizeof(float) * 2 * n, hipMemcpyHostToDevice);
+    double rsum[4] = {0, 0, 0, 0};
+    hipError_t er = rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, reinterpret_cast<float2*>(d_lr), n, rsum)
+                       : hipMemcpy(d_lr, lr, sizeof(float) * 2 * n, hipMemcpyHostToDevice);
     if (er == hipSuccess) er = hipMemsetAsync(ir.d_H, 0, sizeof(float4) * (size_t)MC_NB * e->Pstride, e->stream);
     if (er == hipSuccess) {
         hipLaunchKernelGGL(k_fwd<false>, dim3((P + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, e->stream, d_lr, d_lr + 1, 2, (int64_t)n, P,
@@ -3457,13 +3466,16 @@ int mc_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uin
         HIP_TRY(hipStreamSynchronize(e->stream));
     }
     double s[4] = {0, 0, 0, 0};
-    for (uint64_t m = 0; m < n; m++) {
-        const double sg = (m & 1) ? -1.0 : 1.0;
-        s[0] += lr[2 * m];
-        s[1] += lr[2 * m + 1];
-        s[2] += sg * lr[2 * m];
-        s[3] += sg * lr[2 * m + 1];
-    }
+    if (rs)
+        std::memcpy(s, rsum, sizeof(s));  // (summed on the device: the converted taps never come to the host)
+    else
+        for (uint64_t m = 0; m < n; m++) {
+            const double sg = (m & 1) ? -1.0 : 1.0;
+            s[0] += lr[2 * m];
+            s[1] += lr[2 * m + 1];
+            s[2] += sg * lr[2 * m];
+            s[3] += sg * lr[2 * m + 1];
+        }
     std::memcpy(ir.sums, s, sizeof(s));
     ir.taps = n;
     ir.P = P;
@@ -3471,6 +3483,24 @@ int mc_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uin
     e->spec_valid = e->dspec.valid = false;
     e->uniform_valid[0] = e->uniform_valid[1] = false;
     return MC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int mc_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes) {
+    return load_ir(e, idx, lr, frames, nframes, nullptr);
+}
+
+int mc_load_ir_resampled(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
+                         uint32_t session_rate) {
+    // rates are checked before any HIP call: a refused load leaves the engine as it was
+    for (uint32_t r : {ir_rate, session_rate})
+        if (r < RS_MIN_RATE || r > RS_MAX_RATE) return fail(MC_ERR_ARG, "sample rate %u outside [%u, %u]", r, RS_MIN_RATE, RS_MAX_RATE);
+    if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
+    if (ir_rate == session_rate) return mc_load_ir(e, idx, lr, frames, nframes);
+    const uint32_t rs[2] = {ir_rate, session_rate};
+    return load_ir(e, idx, lr, frames, nframes, rs);
 }
 
 int mc_num_irs(const mc_engine* e) { return e ? e->nirs : 0; }
@@ -3738,6 +3768,7 @@ uint64_t mc_preferred_batch(const mc_engine* e, uint64_t at_most) {
 int mc_debug_read(mc_engine* e, int which, uint64_t idx, void* dst, uint64_t off, uint64_t bytes, uint64_t dims[4]) {
     if (!e) return fail(MC_ERR_ARG, "null engine");
     HIP_TRY(hipSetDevice(e->device));
+    if (e->sf && which == 17) return fail(MC_ERR_STATE, "the single-transform form keeps no taps");
     if (e->sf) {  // single-transform form: 0 = an IR's spectra [H_L | H_R] (float2, n_ref / 2 bins each, bin d + (n_ref / 512) c at [d][c]), 4 = the accumulators [2][512][n_ref / 512]
         if (dims) dims[0] = dims[1] = dims[3] = e->cfg.n_ref, dims[2] = (uint64_t)e->Tmax;
         if (!dst || !bytes) return MC_OK;
@@ -3816,6 +3847,11 @@ int mc_debug_read(mc_engine* e, int which, uint64_t idx, void* dst, uint64_t off
             if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_H) return fail(MC_ERR_ARG, "IR not loaded");
             src = (const char*)e->irs[idx].d_H;
             cap = sizeof(float4) * (uint64_t)MC_NB * e->Pstride;
+            break;
+        case 17:  // the stored time-domain taps of IR idx (float2 [taps]: converted to the session's rate by mc_load_ir_resampled)
+            if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h) return fail(MC_ERR_ARG, "IR not loaded");
+            src = (const char*)e->irs[idx].d_h;
+            cap = sizeof(float2) * e->irs[idx].taps;
             break;
         case 1: src = (const char*)e->d_fdl; cap = sizeof(float4) * (uint64_t)MC_NB * e->ring; break;
         case 2: src = (const char*)e->d_Y; cap = sizeof(float4) * (uint64_t)MC_NB * y_capacity(e); break;

@@ -53,25 +53,31 @@ inline int sf_create(mc_engine* e) {
     return sf_zero(e);
 }
 
-// Convolution::prepare, conv.cu:207-253
-inline int sf_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes) {
+// Convolution::prepare, conv.cu:207-253.  rs = {IR rate, session rate}: the frames are converted on the device straight into the
+// transform's input (resample.hip.h); null = the frames as given
+inline int sf_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs = nullptr) {
     SfState* s = e->sf;
     const uint64_t N = (uint64_t)s->N;
-    const uint64_t n = std::min<uint64_t>(frames, N - nframes);  // conv.cu:239
+    const uint64_t n = std::min<uint64_t>(rs ? rs_out_frames(rs_geom(rs[0], rs[1]), frames) : frames, N - nframes);  // conv.cu:239
     IrEntry& ir = e->irs[idx];
     HIP_TRY(hipStreamSynchronize(e->stream));
-    std::vector<float2> z(N, make_float2(0.f, 0.f));  // conv.cu:223-227, 240: L -> re, R -> im, zero padded
     double sm[4] = {0, 0, 0, 0};
-    for (uint64_t m = 0; m < n; m++) {
-        z[m] = make_float2(lr[2 * m], lr[2 * m + 1]);
-        const double sg = (m & 1) ? -1.0 : 1.0;
-        sm[0] += lr[2 * m];
-        sm[1] += lr[2 * m + 1];
-        sm[2] += sg * lr[2 * m];
-        sm[3] += sg * lr[2 * m + 1];
+    if (rs) {
+        HIP_TRY(hipMemsetAsync(s->d_W, 0, sizeof(float2) * N, e->stream));
+        HIP_TRY(rs_convert(e->stream, rs[0], rs[1], lr, frames, s->d_W, n, sm));
+    } else {
+        std::vector<float2> z(N, make_float2(0.f, 0.f));  // conv.cu:223-227, 240: L -> re, R -> im, zero padded
+        for (uint64_t m = 0; m < n; m++) {
+            z[m] = make_float2(lr[2 * m], lr[2 * m + 1]);
+            const double sg = (m & 1) ? -1.0 : 1.0;
+            sm[0] += lr[2 * m];
+            sm[1] += lr[2 * m + 1];
+            sm[2] += sg * lr[2 * m];
+            sm[3] += sg * lr[2 * m + 1];
+        }
+        HIP_TRY(hipMemcpy(s->d_W, z.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
     }
     if (!ir.d_S) HIP_TRY(hipMalloc(&ir.d_S, sizeof(float2) * N));  // [H_L | H_R], N/2 bins each, bin d + M c at [d][c]
-    HIP_TRY(hipMemcpy(s->d_W, z.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(k_sf_ir_cols, dim3(FFT_N / s->AT), dim3(256), s->lds_bytes, e->stream, s->N, s->M, s->AT, s->d_W, s->d_T);
     hipLaunchKernelGGL(k_sf_ir_rows, dim3(s->M / SF_ROWS), dim3(64 * SF_ROWS), 0, e->stream, s->M, s->d_T, s->d_Z, e->d_tw);
     hipLaunchKernelGGL(k_sf_ir_unpack, dim3((s->N / 2 + 255) / 256), dim3(256), 0, e->stream, s->N, s->M, s->d_Z, ir.d_S);

@@ -82,8 +82,9 @@ class CC:
 class Convolution:
     def __init__(self, name="Conv", fftSize=CONV_DEFAULT_FFTSIZE, *, max_batch=256, device=-1, compat=True,
                  part_begin=0, part_end=0, max_partitions=0, stream_threshold=0, precision="fp32", period=256, pipeline=False,
-                 form="partitioned"):
+                 form="partitioned", sample_rate=None):
         self.name = name
+        self.sample_rate = sample_rate  # session rate (Hz): prepare() converts IRs whose own rate differs; None = the reference's behaviour
         self._L = _lib.load()
         cfg = McConfig()
         self._L.mc_default_config(C.byref(cfg))
@@ -125,11 +126,18 @@ class Convolution:
         check(self._L.mc_set_period(self._h, nframes))
 
     # -- reference surface ----------------------------------------------------
-    def prepare(self, idx, wav, nframes=1024):
+    def prepare(self, idx, wav, nframes=1024, ir_rate=None):
         """Convolution::prepare (conv.cu:207-253).  `wav` is float32 [frames, 2]
-        (what WavFile.buffer holds) or an object with a `.buffer` of that shape."""
+        (what WavFile.buffer holds) or an object with a `.buffer` of that shape.
+        ir_rate (Hz; default: `wav.sampleRate` when it has one): when both it and the engine's sample_rate are known and
+        differ, the IR is converted to the session's rate on the device (mc_load_ir_resampled)."""
         lr = _f32(getattr(wav, "buffer", wav)).reshape(-1, 2)
-        check(self._L.mc_load_ir(self._h, idx, _fp(lr), lr.shape[0], nframes))
+        if ir_rate is None:
+            ir_rate = getattr(wav, "sampleRate", None)
+        if ir_rate is not None and self.sample_rate is not None and int(ir_rate) != int(self.sample_rate):
+            check(self._L.mc_load_ir_resampled(self._h, idx, _fp(lr), lr.shape[0], nframes, int(ir_rate), int(self.sample_rate)))
+        else:
+            check(self._L.mc_load_ir(self._h, idx, _fp(lr), lr.shape[0], nframes))
 
     def onProcess(self, in1, in2):
         """One JACK period (conv.cu:287-466): returns (L, R) float32 arrays."""
@@ -312,6 +320,11 @@ class Convolution:
         check(self._L.mc_debug_read(self._h, which, idx, a.ctypes.data_as(C.c_void_p), offset_elems * a.itemsize,
                                     a.nbytes, None))
         return a
+
+    def ir_taps(self, idx):
+        """The stored time-domain taps of IR idx, float32 [taps, 2] (mc_debug_read item 17)."""
+        n = int(self.ir_info(idx)["taps"])
+        return self.debug_read(17, idx, np.float32, 0, 2 * n).reshape(n, 2)
 
     def ir_spectra(self, idx):
         """IR spectra as complex [2 ch][partitions][256 packed bins] (diagnostics)."""

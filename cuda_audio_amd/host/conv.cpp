@@ -15,6 +15,8 @@ int mc_group_load_ir(mc_group*, uint64_t, const float*, uint64_t, uint64_t) __at
 int mc_group_set_params(mc_group*, int, const mc_cc_value*) __attribute__((weak));
 int mc_group_process_batch(mc_group*, const float*, const float*, float*, float*, uint64_t) __attribute__((weak));
 const char* mc_group_last_error(void) __attribute__((weak));
+// (weak as well: the stub host's stand-in engine has no sample-rate conversion)
+int mc_load_ir_resampled(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t) __attribute__((weak));
 }
 
 namespace {
@@ -67,6 +69,7 @@ Convolution::~Convolution() {
 }
 
 void Convolution::onStart() {
+    loadPendingIrs();  // (rate matching: the client's rate is known from here on)
     // reference conv.cu:197-204: activate first, then register 2 outputs and 2 inputs
     activate();
     playback[0] = addOutput("playback_1");
@@ -75,7 +78,38 @@ void Convolution::onStart() {
     capture[1] = addInput("capture_2");
 }
 
+void Convolution::setMatchIrRate(bool on) {
+    if (on && _group) {
+        Log::error("conv", "IR rate matching is not available with several devices (mc_group_load_ir takes no rate)");
+        std::exit(2);
+    }
+    _matchIrRate = on;
+}
+
+void Convolution::loadPendingIrs() {
+    for (const PendingIr& p : _pendingIrs) {
+        const uint64_t frames = p.lr.size() / 2;
+        if (!p.rate || p.rate == samplerate) {
+            check(mc_load_ir(_engine, p.idx, p.lr.data(), frames, p.nframes), "mc_load_ir");
+            continue;
+        }
+        if (!mc_load_ir_resampled) {
+            Log::error("conv", "the engine has no sample-rate conversion (mc_load_ir_resampled)");
+            std::exit(2);
+        }
+        Log::info(name, "IR %zu: %u Hz -> %zu Hz", p.idx, p.rate, samplerate);
+        check(mc_load_ir_resampled(_engine, p.idx, p.lr.data(), frames, p.nframes, p.rate, (uint32_t)samplerate), "mc_load_ir_resampled");
+    }
+    _pendingIrs.clear();
+}
+
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
+    if (_matchIrRate) {
+        const float* lr = &wav.buffer[0].x;
+        _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames)});
+        if (idx + 1 > _nirs) _nirs = idx + 1;
+        return;
+    }
     if (_group) {
         if (mc_group_load_ir(_group, idx, &wav.buffer[0].x, wav.numFrames, nframes) != MC_OK) {
             Log::error("conv", "mc_group_load_ir failed: %s", mc_group_last_error());

@@ -64,6 +64,11 @@ public:
     double avgRuntime() const;
 
     void prepare(size_t idx, const WavFile& wav, size_t nframes = 1024);
+    // Convert every IR prepared from now on to the JACK client's sample rate (no reference equivalent: the reference plays
+    // IR frames at whatever rate jackd runs).  The rate is known only once the client is open, so prepare() keeps the
+    // decoded frames and their rate and onStart() loads them before activate().  A WAV at the client's rate (or of unknown
+    // rate) is loaded as it is.  Single device only: with several devices this reports an error and exits.
+    void setMatchIrRate(bool on);
 
     void onMidiMessage(const RawMidi::Device* sender, const uint8_t* buffer, size_t len) override;
 
@@ -79,6 +84,14 @@ private:
     size_t _nirs = 0;
     size_t _period = 256;
     size_t _pushedVsteps[2] = {0, 0};  // cc[i].value.vsteps as last handed to the engine (see pullVsteps)
+    bool _matchIrRate = false;
+    struct PendingIr {
+        size_t idx, nframes;
+        unsigned rate;
+        std::vector<float> lr;  // interleaved L, R frames
+    };
+    std::vector<PendingIr> _pendingIrs;  // (rate matching) prepared, loaded by onStart()
+    void loadPendingIrs();
     void pushParams();
     void pullVsteps();
 };

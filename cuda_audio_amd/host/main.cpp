@@ -7,7 +7,8 @@
 // waiting on stdin - all instances AT ONCE, a driver thread per client, as jackd
 // runs them (--sequential: one after the other; --period F: frames per period;
 // --spacing US: a period clock; --dump PREFIX: every instance's input and output
-// as raw float32 files PREFIX<i>.in1 / .in2 / .outL / .outR).
+// as raw float32 files PREFIX<i>.in1 / .in2 / .outL / .outR; --rate HZ: the fake server's sample rate, 44100 unless
+// given; --match-ir-rate: every IR is converted to the client's sample rate on load, Convolution::setMatchIrRate).
 #include <cassert>
 #include <cstdlib>
 #include <cstring>
@@ -26,14 +27,19 @@ int main(int argc, char** argv) {
     const char* dump = nullptr;
     bool sequential = false;
     double spacing_us = 0.0;
+    jack_nframes_t rate = 0, period = 0;  // fake JACK server: 0 = its defaults (44100 Hz, 256 frames)
+    bool matchIrRate = false;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--periods") && i + 1 < argc) periods = strtoull(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "--settings") && i + 1 < argc) settingsPath = argv[++i];
         else if (!strcmp(argv[i], "--dump") && i + 1 < argc) dump = argv[++i];
         else if (!strcmp(argv[i], "--sequential")) sequential = true;
         else if (!strcmp(argv[i], "--spacing") && i + 1 < argc) spacing_us = atof(argv[++i]);
-        else if (!strcmp(argv[i], "--period") && i + 1 < argc) fakejack_configure(44100, (jack_nframes_t)atoi(argv[++i]));
+        else if (!strcmp(argv[i], "--period") && i + 1 < argc) period = (jack_nframes_t)atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--rate") && i + 1 < argc) rate = (jack_nframes_t)atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--match-ir-rate")) matchIrRate = true;
     }
+    if (rate || period) fakejack_configure(rate ? rate : 44100, period ? period : 256);
     selectGpu();
 
     Settings settings;
@@ -50,6 +56,7 @@ int main(int argc, char** argv) {
         assert(fs1 == fs2 && "a convolution pair needs identical fft sizes");
         auto* c = new Convolution(std::string("hipconv_") + char('1' + n), fs1);
         instances.push_back(c);
+        if (matchIrRate) c->setMatchIrRate(true);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;
             const auto deviceId = settings.str("conv[%d].cc.device", idx);

@@ -133,6 +133,13 @@ int mc_set_period(mc_engine *e, uint32_t nframes);
 /* lr: interleaved L,R float frames as WavFile holds them (already scaled, wav.cu Q5);
  * nframes: the reference's third prepare() argument (1024). Host pointer. */
 int mc_load_ir(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes);
+/* mc_load_ir for an IR recorded at ir_rate Hz in a session at session_rate Hz (both in [8000, 384000], else MC_ERR_ARG
+ * before anything is touched): the frames are converted on the device to ceil(frames * session_rate / ir_rate) taps
+ * (windowed sinc, Z = 64 zero crossings, Kaiser beta = 9, passband 0.955 of the lower Nyquist frequency, scaled by
+ * ir_rate / session_rate so that sum h and the wet level stay put), then truncated and transformed exactly as
+ * mc_load_ir's frames are.  Equal rates are mc_load_ir.  Host pointer, same rules as mc_load_ir.  No reference equivalent. */
+int mc_load_ir_resampled(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
+                         uint32_t session_rate);
 int mc_num_irs(const mc_engine *e);
 /* out[0..3] = sum h_L, sum h_R, sum h_L(-1)^m, sum h_R(-1)^m of the truncated IR; out[4] = taps, out[5] = partitions */
 int mc_ir_info(const mc_engine *e, uint64_t idx, double out[6]);
@@ -235,7 +242,8 @@ uint64_t mc_preferred_batch(const mc_engine *e, uint64_t at_most);
  * of their partition sums {fused, split second-level transform, resident MAC} (3 x uint64), 11 = overlap-save form {batches that
  * took it, builds of its spectra} (2 x uint64), 12 / 13 / 14 = its row buffer and spectra (float4), 15 = 1 when the library is the lab
  * build (-DMCCONV_LAB: measurement switches and alternative kernels), 16 = 256-frame JACK tails by the form partition 0 took
- * {frequency domain, time domain}, counted by the kernel (2 x uint32; read behind the stream).  dims[0..3] receive
+ * {frequency domain, time domain}, counted by the kernel (2 x uint32; read behind the stream), 17 = the stored time-domain
+ * taps of IR `idx` (float2 [taps], as mc_ir_info counts them; MC_ERR_STATE in the single-transform form, which keeps none).  dims[0..3] receive
  * {pstride, ring, max_batch, wet ring length} when non-null. */
 int mc_debug_read(mc_engine *e, int which, uint64_t idx, void *dst, uint64_t offset_bytes, uint64_t bytes,
                   uint64_t dims[4]);
