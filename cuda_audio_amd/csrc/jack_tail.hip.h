@@ -53,7 +53,7 @@ struct TailArgs {
     unsigned* exited;
     unsigned long long park_ticks;
     const float* drop;  // Q8 terms of the period's samples [2][256] (k_drop_period), or null
-    // Tagged I/O (round 3, MCCONV_TAGGED_IO): the period and the output travel as 8-byte granules {value, sequence number}.  A
+    // Tagged I/O (round 3): the period and the output travel as 8-byte granules {value, sequence number}.  A
     // parked tail polls the period's own granules (every lane its two) instead of a doorbell followed by a second round trip
     // for the 2 KB it announces, and the host polls the output's granules instead of a completion word that has to wait behind
     // a system-scope release of every store of the kernel.  in_gran: [2][256] in device memory the CPU writes through the BAR
@@ -61,7 +61,7 @@ struct TailArgs {
     const unsigned long long* in_gran;
     unsigned long long* out_gran;
     // 256-frame tail: which form a period took, counted in device memory {frequency domain, time domain} (mc_debug_read item 16), and
-    // form != 0 (lab build, MCCONV_TAIL_FORM=td|fd): 1 = always the time-domain form (with its dry run), 2 = always the frequency-domain one
+    // form != 0 (MCCONV_TAIL_FORM=td|fd): 1 = always the time-domain form (with its dry run), 2 = always the frequency-domain one
     unsigned* formcount;
     int form;
 };
@@ -73,8 +73,8 @@ struct TailArgs {
 // after the arrival the p = 0 term is a direct 256 x 256 convolution of the period with the gain-weighted first 256 taps of the
 // sounding IRs, added to the finished rest.  Two single-wavefront 512-point transforms and two workgroup barriers leave the
 // critical path (the forward transform of the period, which later periods need in the delay line, and the segment's second half
-// follow the output).  tail1_body_fft0 (lab build, -DMC_TAIL_FFT0) is the round-3 form: forward transform, partition 0 in the
-// frequency domain, inverse transform - all behind the arrival.
+// follow the output).  (The round-3 form - forward transform, partition 0 in the frequency domain, inverse transform, all
+// behind the arrival - is retired: docs/DESIGN_history.md.)
 //
 // The direct convolution, register-tiled (a thread per output frame and tap reads 24 bytes of LDS per four multiply-adds: 3 us):
 // a unit is NO consecutive output frames x NT consecutive taps; the taps {L<-in1, R<-in1, L<-in2, R<-in2} sit in registers before
@@ -424,7 +424,7 @@ __device__ __forceinline__ void tail1_body(const TailArgs& A) {
 #ifdef MC_JACK_TRACE
         unsigned long long t_start = 0, c_start = 0;
 #endif
-        if (A.form == 2 && A.bell) {  // (lab build: this form forced on a parked tail - wait here)
+        if (A.form == 2 && A.bell) {  // (MCCONV_TAIL_FORM=fd: this form forced on a parked tail - wait here)
             const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
             if (A.in_gran) {
                 for (;;) {
@@ -462,10 +462,6 @@ __device__ __forceinline__ void tail1_body(const TailArgs& A) {
             xin2 = __hip_atomic_load(in2 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         float4 xs_keep[4];  // wave 0: the block's spectra, stored to the delay line at the end of the kernel
-#ifdef MC_FD_WARM  // (measurement build: what the frequency-domain form would take out of a warm instruction cache - a dry pass first)
-#pragma nounroll
-        for (int fdpass = 0; fdpass < 2; fdpass++) {
-#endif
 #ifdef MC_JACK_TRACE
         asm volatile("s_memrealtime %0\n\ts_memtime %1\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_start), "=s"(c_start) : "v"(xin1));  // (in program order: per trip of the loop)
 #endif
@@ -556,9 +552,6 @@ __device__ __forceinline__ void tail1_body(const TailArgs& A) {
             for (int c = 0; c < 4; c++) s_c[c] = cprev[c] + d[c];
         }
         __syncthreads();
-#ifdef MC_FD_WARM
-        }
-#endif
         // No global store is issued before the output has left: a barrier drains the vector-memory counter, so every
         // store ahead of it would put its acknowledgement latency on the critical path.
         float seg_lo[2], seg_hi[2], own_wet[2];
@@ -714,7 +707,7 @@ __device__ __forceinline__ void tail1_body(const TailArgs& A) {
 #pragma nounroll
     for (int pass = 0; pass < 2; pass++) {
         const bool live = pass == 1;
-        if (live && A.bell) {  // (not parked - this form forced in a lab build: the period is in place)
+        if (live && A.bell) {  // (not parked - this form forced by MCCONV_TAIL_FORM=td: the period is in place)
             if (A.in_gran) {
                 // Parked, tagged input: every lane looks at its own two granules of the period; lane 0 also watches the doorbell word for
                 // the "give up" command and the park time.  THREE looks are in flight, a third of a round trip through memory apart
@@ -996,402 +989,7 @@ __device__ __forceinline__ void tail1_body(const TailArgs& A) {
     }
 }
 
-#if defined(MCCONV_LAB) && defined(MC_TAIL_FFT0)  // the round-3 form of the tail (measurement build)
-__device__ __forceinline__ void tail1_body_fft0(const TailArgs& A) {
-    const float* in1 = A.in1;
-    const float* in2 = A.in2;
-    const VoiceSet& vset = A.vset;
-    const int pstride_ir = A.pstride_ir;
-    float4* __restrict__ fdl = A.fdl;
-    float4* __restrict__ slotgain = A.slotgain;
-    const int ring = A.ring, slot0 = A.slot0;
-    const float4* __restrict__ part = A.part;
-    const int nsum = A.nsum;
-    const BlockParams* __restrict__ ptab = A.ptab;
-    float* __restrict__ seg = A.seg;
-    const int sr = A.sr, seg0 = A.seg0;
-    float* __restrict__ wet = A.wet;
-    const int wr = A.wr;
-    double* __restrict__ cring = A.cring;
-    const int rc = A.rc;
-    const VoiceSums& vs = A.vs;
-    const double inv_n = A.inv_n;
-    const int compat = A.compat;
-    const int64_t tabs0 = A.tabs0, predelay = A.predelay, n_ref = A.n_ref;
-    float* __restrict__ outL = A.outL;
-    float* __restrict__ outR = A.outR;
-    const float2* __restrict__ g_tw = A.g_tw;
-    const TailDrop& td = A.td;
-    uint2* __restrict__ fdl16 = A.fdl16;
-    unsigned* __restrict__ done_flag = A.done_flag;
-    const unsigned seq = A.seq;
-    const Retired& ret = A.ret;
-    __shared__ float2 s_tw[FFT_N];
-    __shared__ float2 s_fft[FFT_WAVE_LDS];
-    __shared__ float4 s_x[MC_NB];  // raw spectra of the new block {X1, X2}
-    __shared__ float4 s_y[MC_NB];  // Y_L, Y_R
-    __shared__ float s_wet[2][MC_B];
-    __shared__ float s_in[2][MC_B];
-    __shared__ double s_c[4];
-    __shared__ float4 s_sa;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const BlockParams& bp = ptab[0];  // read through global memory: a local copy indexed at run time would live in scratch
-    const float4 dmix = make_float4(bp.d[0], bp.d[1], bp.d[2], bp.d[3]);  // (read here: at its use the load's round trip would sit between the period and its output)
-    const int m = tid;
-    const int64_t tau0 = tabs0 * MC_B, tau = tau0 + m, u = tau - predelay;
 
-    // ---- every load whose address is known now is issued here, in one round of memory latency: the period
-    // (PCIe), twiddles, this bin's chunk partials and partition-0 spectra, the previous tail, the delayed wet
-    // samples, the Q1/Q2 prefix entries and the retired-epoch residuals.  (The kernel is one workgroup on the
-    // critical path of a JACK period: six dependent round trips cost more than everything it computes.)
-    const float2 tw0 = g_tw[tid], tw1 = g_tw[tid + 256];
-    float4 ysum = make_float4(0.f, 0.f, 0.f, 0.f);
-    {
-        const float4* src = part + (size_t)tid * nsum;
-        for (int c = 0; c < nsum; c++) {
-            const float4 a = src[c];
-            ysum.x += a.x;
-            ysum.y += a.y;
-            ysum.z += a.z;
-            ysum.w += a.w;
-        }
-    }
-    float4 h0v[MC_MAXV], h1v[MC_MAXV];
-    // partition 1 pairs with the previous block: its spectrum and its slot's gains come from the delay line.  The
-    // sweep over partitions >= 2 of THIS block needed nothing of the previous period, so it ran beside that period's
-    // tail on a second stream (mcconv.hip, process_one).
-    float4 h0w[MC_MAXV], h1w[MC_MAXV], g1w[MC_MAXV];
-    const int slot1 = (slot0 + ring - 1) & (ring - 1);
-    const float4 xprev = fdl[(size_t)tid * ring + slot1];
-#pragma unroll
-    for (int vi = 0; vi < MC_MAXV; vi++) {  // constant indices: runtime-indexed kernel-argument arrays go to scratch
-        h0v[vi] = h1v[vi] = h0w[vi] = h1w[vi] = g1w[vi] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (vi < vset.n) {
-            h0v[vi] = vset.H0[vi][(size_t)tid * pstride_ir];
-            h1v[vi] = vset.H1[vi][(size_t)tid * pstride_ir];
-            h0w[vi] = vset.H0[vi][(size_t)tid * pstride_ir + 1];
-            h1w[vi] = vset.H1[vi][(size_t)tid * pstride_ir + 1];
-            g1w[vi] = slotgain[(size_t)vset.vid[vi] * ring + slot1];
-        }
-    }
-    const float* prv = seg + (size_t)((seg0 + sr - 1) & (sr - 1)) * 2 * FFT_N;
-    const float prvL = prv[MC_B + m], prvR = prv[FFT_N + MC_B + m];
-    float dwl = 0.f, dwr = 0.f;  // delayed wet sample when it predates this period
-    if (u >= 0 && u < tau0) {
-        dwl = wet[(size_t)(u & (wr - 1))];
-        dwr = wet[(size_t)wr + (u & (wr - 1))];
-    }
-    float2 ra = make_float2(0.f, 0.f), rb = ra;
-    if (tau < ret.end) {  // what blocks played under an earlier predelay still owe
-        ra = retired_at(ret.mac, ret.rr, tau);
-        rb = retired_at(ret.fix, ret.rr, tau);
-    }
-    const int64_t thi = u >> 8;
-    int64_t tlo = tau - n_ref >= 0 ? ((tau - n_ref) >> 8) : -1;
-    if (tlo < ret.b0 - 1) tlo = ret.b0 - 1;
-    const bool corr_on = compat && u >= 0 && thi > tlo;
-    double ca[4] = {0, 0, 0, 0}, cb[4] = {0, 0, 0, 0}, cprev[4] = {0, 0, 0, 0};
-    if (corr_on && thi != tabs0) {
-        const double* pa = cring + (size_t)(thi & (rc - 1)) * 4;
-        for (int c = 0; c < 4; c++) ca[c] = pa[c];
-    }
-    if (corr_on && tlo >= 0) {
-        const double* pb = cring + (size_t)(tlo & (rc - 1)) * 4;
-        for (int c = 0; c < 4; c++) cb[c] = pb[c];
-    }
-    if (tid == 64 && tabs0 > 0) {  // the thread that will extend the prefix sums
-        const double* pp = cring + (size_t)((tabs0 + rc - 1) & (rc - 1)) * 4;
-        for (int c = 0; c < 4; c++) cprev[c] = pp[c];
-    }
-
-    s_tw[tid] = tw0;
-    s_tw[tid + 256] = tw1;
-    // Q8: what the reference's cut at n_ref takes away from this period's samples comes from blocks at least n_ref frames
-    // old - nothing of it depends on the period itself: k_drop_period, launched ahead of this kernel, has summed it
-    float td_l[1] = {0.f}, td_r[1] = {0.f};
-    if (td.on) {
-        td_l[0] = A.drop[m];
-        td_r[0] = A.drop[MC_B + m];
-    }
-    float xin1 = 0.f, xin2 = 0.f;
-    bool have_in = false;
-    if (A.bell && A.in_gran) {
-        // Parked, tagged input: every lane polls its own two granules of the period; wave 0 also watches the doorbell word for
-        // the "give up" command and the park time.  A wave leaves the loop when all its lanes hold this period's samples, or
-        // when wave 0 has said to leave (an LDS word); the barrier behind the loop makes the decision the workgroup's.
-        __shared__ int s_abort;
-        if (tid == 0) s_abort = 0;
-        __syncthreads();
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        for (;;) {
-            const unsigned long long g1 = __hip_atomic_load(A.in_gran + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            const unsigned long long g2 = __hip_atomic_load(A.in_gran + MC_B + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            if (__all((unsigned)(g1 >> 32) == seq && (unsigned)(g2 >> 32) == seq)) {
-                xin1 = __uint_as_float((unsigned)g1);
-                xin2 = __uint_as_float((unsigned)g2);
-                break;
-            }
-            if (tid == 0) {
-                const unsigned long long v = __hip_atomic_load(A.bell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if ((unsigned)v == seq && (v >> 32) != 0) {
-                    *(volatile int*)&s_abort = 1;  // told to give up
-                } else if (__builtin_amdgcn_s_memrealtime() - t0 > A.park_ticks) {
-                    __hip_atomic_store(A.exited, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    *(volatile int*)&s_abort = 1;  // the host has been away for longer than the park time
-                }
-            }
-            if (*(volatile int*)&s_abort) break;
-            __builtin_amdgcn_s_sleep(2);
-        }
-        __syncthreads();
-        if (*(volatile int*)&s_abort) return;  // nothing has been written: the host launches this period again
-        have_in = true;
-    } else if (A.bell) {
-        // Parked: everything above was requested without the period; only its 2 KB are still missing.  One lane
-        // polls the mapped doorbell (a PCIe read per poll), the others wait at the barrier.
-        __shared__ int s_go;
-        if (tid == 0) {
-            int go = 1;
-            const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-            for (;;) {
-                const unsigned long long v = __hip_atomic_load(A.bell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                if ((unsigned)v == seq) {
-                    go = (v >> 32) == 0;
-                    break;
-                }
-                if (__builtin_amdgcn_s_memrealtime() - t0 > A.park_ticks) {
-                    go = 0;
-                    __hip_atomic_store(A.exited, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(4);
-            }
-            s_go = go;
-        }
-        __syncthreads();
-        if (!s_go) return;  // nothing has been written: the host launches this period again
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");  // the period was written before the doorbell
-    }
-#ifdef MC_JACK_TRACE  // diagnostic build: when the period's work started and ended (100 MHz), next to the completion word
-    const unsigned long long t_start = __builtin_amdgcn_s_memrealtime();
-    const unsigned long long c_start = __builtin_amdgcn_s_memtime();
-#endif
-    // (system scope: the period may sit in device memory the CPU wrote through the BAR - not to be served from a cache)
-    if (!have_in) {
-        xin1 = __hip_atomic_load(in1 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        xin2 = __hip_atomic_load(in2 + tid, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-    s_in[0][tid] = xin1;
-    s_in[1][tid] = xin2;
-    __syncthreads();
-    float4 xs_keep[4];  // wave 0: the block's spectra, stored to the delay line at the end of the kernel
-    if (wave == 0) {
-        float2 v[8];
-#pragma unroll
-        for (int r = 0; r < 4; r++) v[r] = make_float2(s_in[0][lane + 64 * r], s_in[1][lane + 64 * r]);
-#pragma unroll
-        for (int r = 4; r < 8; r++) v[r] = make_float2(0.f, 0.f);
-        fft512_wave<-1, false>(v, s_fft, s_tw, lane);
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            const int k = lane + 64 * j;
-            const float2 za = s_fft[k], zb = s_fft[(FFT_N - k) & (FFT_N - 1)];
-            float2 x1, x2;
-            if (k == 0) {
-                const float2 zn = s_fft[MC_B];
-                x1 = make_float2(za.x, zn.x);
-                x2 = make_float2(za.y, zn.y);
-                s_sa = make_float4(za.x, za.y, zn.x, zn.y);
-            } else {
-                x1 = make_float2(0.5f * (za.x + zb.x), 0.5f * (za.y - zb.y));
-                x2 = make_float2(0.5f * (za.y + zb.y), -0.5f * (za.x - zb.x));
-            }
-            const float4 xs = make_float4(x1.x, x1.y, x2.x, x2.y);
-            s_x[k] = xs;
-            xs_keep[j] = xs;
-        }
-    }
-    __syncthreads();
-    {  // bin tid: chunk partials (partitions >= 1) + partition 0 of every voice's IRs against the new block
-        const int k = tid;
-        const float4 x = s_x[k];
-        float4 y = ysum;
-#pragma unroll
-        for (int vi = 0; vi < MC_MAXV; vi++) {
-            if (vi >= vset.n) break;
-            const float* g = ptab->g[vset.vid[vi]];
-            const float4 h0 = h0v[vi], h1 = h1v[vi];
-            float2 a0 = make_float2(0.f, 0.f), a1 = a0, a2 = a0, a3 = a0;
-            if (k == 0) {
-                cmac<true>(a0, h0.x, h0.y, x.x, x.y);
-                cmac<true>(a1, h1.x, h1.y, x.z, x.w);
-                cmac<true>(a2, h0.z, h0.w, x.x, x.y);
-                cmac<true>(a3, h1.z, h1.w, x.z, x.w);
-            } else {
-                cmac<false>(a0, h0.x, h0.y, x.x, x.y);
-                cmac<false>(a1, h1.x, h1.y, x.z, x.w);
-                cmac<false>(a2, h0.z, h0.w, x.x, x.y);
-                cmac<false>(a3, h1.z, h1.w, x.z, x.w);
-            }
-            y.x += g[0] * a0.x + g[1] * a1.x;
-            y.y += g[0] * a0.y + g[1] * a1.y;
-            y.z += g[2] * a2.x + g[3] * a3.x;
-            y.w += g[2] * a2.y + g[3] * a3.y;
-            // partition 1 against the previous block, with the gains that block carries
-            const float4 p0 = h0w[vi], p1 = h1w[vi], gq = g1w[vi];
-            a0 = a1 = a2 = a3 = make_float2(0.f, 0.f);
-            if (k == 0) {
-                cmac<true>(a0, p0.x, p0.y, xprev.x, xprev.y);
-                cmac<true>(a1, p1.x, p1.y, xprev.z, xprev.w);
-                cmac<true>(a2, p0.z, p0.w, xprev.x, xprev.y);
-                cmac<true>(a3, p1.z, p1.w, xprev.z, xprev.w);
-            } else {
-                cmac<false>(a0, p0.x, p0.y, xprev.x, xprev.y);
-                cmac<false>(a1, p1.x, p1.y, xprev.z, xprev.w);
-                cmac<false>(a2, p0.z, p0.w, xprev.x, xprev.y);
-                cmac<false>(a3, p1.z, p1.w, xprev.z, xprev.w);
-            }
-            y.x += gq.x * a0.x + gq.y * a1.x;
-            y.y += gq.x * a0.y + gq.y * a1.y;
-            y.z += gq.z * a2.x + gq.w * a3.x;
-            y.w += gq.z * a2.y + gq.w * a3.y;
-        }
-        s_y[k] = y;
-    }
-    __syncthreads();
-    if (wave == 0) {
-        float2 v[8];
-#pragma unroll
-        for (int r = 0; r < 8; r++) {
-            const int n = lane + 64 * r;
-            float2 w;
-            if (n == 0) {
-                const float4 y = s_y[0];
-                w = make_float2(y.x, y.z);
-            } else if (n == MC_B) {
-                const float4 y = s_y[0];
-                w = make_float2(y.y, y.w);
-            } else if (n < MC_B) {
-                const float4 y = s_y[n];
-                w = make_float2(y.x - y.w, y.y + y.z);
-            } else {
-                const float4 y = s_y[FFT_N - n];
-                w = make_float2(y.x + y.w, -y.y + y.z);
-            }
-            v[r] = w;
-        }
-        fft512_wave<+1, false>(v, s_fft, s_tw, lane);
-    } else if (tid == 64) {
-        // meanwhile: this block's Q1/Q2 terms and the new prefix entry (float64, serial)
-        double d[4] = {0, 0, 0, 0};
-        if (compat) corr_terms(s_sa, bp, vs, inv_n, d);
-        for (int c = 0; c < 4; c++) s_c[c] = cprev[c] + d[c];
-    }
-    __syncthreads();
-    // No global store is issued before the output has left: a barrier drains the vector-memory counter, so every
-    // store ahead of it would put its acknowledgement latency on the critical path.
-    float seg_lo[2], seg_hi[2], own_wet[2];
-    {
-        // overlap-add with the previous block's tail; this block's segments go to the ring
-        const float sc = 1.0f / FFT_N;
-        const float2 lo = s_fft[m], hi = s_fft[MC_B + m];
-        seg_lo[0] = lo.x * sc;
-        seg_lo[1] = lo.y * sc;
-        seg_hi[0] = hi.x * sc;
-        seg_hi[1] = hi.y * sc;
-        own_wet[0] = seg_lo[0] + prvL;
-        own_wet[1] = seg_lo[1] + prvR;
-        s_wet[0][m] = own_wet[0];
-        s_wet[1][m] = own_wet[1];
-    }
-    __syncthreads();
-    {
-        float wl = dwl, wr_ = dwr;
-        if (u >= tau0) {  // inside this block: not yet visible through global memory
-            wl = s_wet[0][u - tau0];
-            wr_ = s_wet[1][u - tau0];
-        }
-        wl += ra.x + rb.x;
-        wr_ += ra.y + rb.y;
-        double cl = 0.0, cr = 0.0;
-        if (corr_on) {
-            if (thi == tabs0)
-                for (int c = 0; c < 4; c++) ca[c] = s_c[c];
-            const double sg = (u & 1) ? -1.0 : 1.0;
-            cl = (ca[0] - cb[0]) + sg * (ca[2] - cb[2]);
-            cr = (ca[1] - cb[1]) + sg * (ca[3] - cb[3]);
-        }
-        const float x1 = xin1, x2 = xin2;
-        if (td.on) {
-            wl -= td_l[0];
-            wr_ -= td_r[0];
-        }
-        const float vl = fminf(fmaxf((float)((double)wl + cl), -1.f), 1.f);
-        const float vr = fminf(fmaxf((float)((double)wr_ + cr), -1.f), 1.f);
-        const float yl = vl + x1 * dmix.x + x2 * dmix.y, yr = vr + x1 * dmix.z + x2 * dmix.w;
-        if (A.out_gran) {  // the output as granules {value, sequence number}: on the host as soon as the posted writes land
-            __hip_atomic_store(A.out_gran + m, ((unsigned long long)seq << 32) | __float_as_uint(yl), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            __hip_atomic_store(A.out_gran + MC_B + m, ((unsigned long long)seq << 32) | __float_as_uint(yr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        } else {
-            outL[m] = yl;
-            outR[m] = yr;
-        }
-        write_history(td, tau, tabs0, m, x1, x2, bp, rc);
-    }
-#ifdef MC_JACK_TRACE
-    const unsigned long long t_out = __builtin_amdgcn_s_memrealtime();  // the output's stores are issued
-    const unsigned long long c_out = __builtin_amdgcn_s_memtime();      // (shader clocks over the same stretch)
-#endif
-    // the state later periods need: delay-line slot, slot gains, segments, wet ring, Q1/Q2 prefix entry
-    {
-        float* cur = seg + (size_t)seg0 * 2 * FFT_N;
-        cur[m] = seg_lo[0];
-        cur[MC_B + m] = seg_hi[0];
-        cur[FFT_N + m] = seg_lo[1];
-        cur[FFT_N + MC_B + m] = seg_hi[1];
-        wet[(size_t)(tau & (wr - 1))] = own_wet[0];
-        wet[(size_t)wr + (tau & (wr - 1))] = own_wet[1];
-        if (wave == 0) {
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                const int k = lane + 64 * j;
-                fdl[(size_t)k * ring + slot0] = xs_keep[j];
-                if (fdl16) fdl16[(size_t)k * ring + slot0] = pack_half4(xs_keep[j], FDL16_SCALE);
-            }
-            if (lane < MC_MAXV)
-                slotgain[(size_t)lane * ring + slot0] = make_float4(bp.g[lane][0], bp.g[lane][1], bp.g[lane][2], bp.g[lane][3]);
-        }
-        if (m == 0) {
-            double* o = cring + (size_t)(tabs0 & (rc - 1)) * 4;
-            for (int c = 0; c < 4; c++) o[c] = s_c[c];
-        }
-    }
-    // publish completion to the host (mapped pinned memory): all waves drain their stores at the barrier
-    // (__syncthreads waits vmcnt(0)), then ONE lane issues the system-scope release and the sequence number.
-    // With tagged output the host does not look at the word (the granules are the completion): no release, the kernel ends
-    // 0.6 us earlier and the next period's kernel starts that much sooner (back-to-back calls).
-#ifndef MC_JACK_TRACE
-    if (A.out_gran) return;
-#endif
-    __syncthreads();
-    if (tid == 0) {
-#ifdef MC_JACK_TRACE
-        reinterpret_cast<unsigned long long*>(done_flag)[1] = t_start;
-        reinterpret_cast<unsigned long long*>(done_flag)[2] = __builtin_amdgcn_s_memrealtime();
-        reinterpret_cast<unsigned long long*>(done_flag)[3] = t_out;
-        reinterpret_cast<unsigned long long*>(done_flag)[4] = c_out - c_start;
-#endif
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-        __hip_atomic_store(done_flag, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-#define tail1_body tail1_body_fft0
-#endif
-
-#if defined(MCCONV_LAB) && defined(MC_TAIL_FFT0)
-#undef TAIL1_THREADS
-#define TAIL1_THREADS 256
-#endif
 __global__ __launch_bounds__(TAIL1_THREADS) void k_tail1(TailArgs A) { tail1_body(A); }
 
 // The tail of period t (workgroup 0, usually parked on its doorbell) and the streaming sweep over partitions >= 2 of
@@ -1441,9 +1039,6 @@ __global__ __launch_bounds__(TAIL1_THREADS) void k_jack(TailArgs A, SweepArgs S)
 // SELF_DROP (a parked launch in the Q8 regime): the workgroup sums the period's own cut terms first, while the period has not arrived
 // (they depend on blocks at least n_ref frames old) - no launch of their own ahead of this one.
 template <int PM, bool SELF_DROP>
-#ifdef TAILP_VGPR_CAP  // (measurement build: DESIGN section 4, JACK path, item 3)
-__attribute__((amdgpu_num_vgpr(TAILP_VGPR_CAP)))
-#endif
 __global__ __launch_bounds__(256) void k_tailp(const float* __restrict__ in1, const float* __restrict__ in2, VoiceSet vset,
                                                int pstride_ir, float4* __restrict__ fdl, float4* __restrict__ slotgain, int ring,
                                                int slot0, const float4* __restrict__ part, int nsum,

@@ -29,10 +29,6 @@
 
 #include "fft512.hip.h"
 
-#if !defined(MCCONV_LAB) && (defined(G2_ABL) || defined(G2_STAMPS) || defined(G2_ALIAS_TEST) || defined(DF_DBG) || defined(DF_LINEAR) || \
-                             defined(TAILP_VGPR_CAP) || defined(IW_LINEAR_TILES) || defined(OS_ABL) || defined(OS_OUT_UNROLL) || defined(MC_JACK_TRACE) || defined(MC_FD_WARM) || defined(MC_TAIL_FFT0))
-#error "the measurement builds (timing ablations, time stamps, traces) are part of the lab build only: add -DMCCONV_LAB"
-#endif
 #define MC_B 256
 #define MC_K 512
 #define MC_NB 256
@@ -956,9 +952,6 @@ __global__ __launch_bounds__(IW_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
     {
         const int nt = (int)gridDim.x, q = nt >> 3, r = nt & 7, x = (int)blockIdx.x & 7;
         tile = x * q + min(x, r) + ((int)blockIdx.x >> 3);
-#ifdef IW_LINEAR_TILES  // (measurement build: tiles in workgroup order)
-        tile = (int)blockIdx.x;
-#endif
     }
     const int tb0 = tile * IW_NEW;
     {
@@ -1652,7 +1645,7 @@ __global__ void k_h_tail(const float4* __restrict__ H, int pstride, int p0, int 
 // output blocks: thread (k0 = tid / 8, col = tid % 8) sums bins k0 + 64 r of block col - the delay line is bin-major, so the 8 columns
 // of one bin are one 128-byte line - into a [256 bins][DF_WAVES + 1] tile in LDS, wave w then transforms column w and keeps the slice
 // of block w's frames; per kappa one partition sum over the last partitions and one inverse transform, as above.  0.40 ms per
-// 125 000 blocks at the shipped operating point (one term): without the sum 0.27, without the transform 0.29 (-DDF_DBG=1 / 2); what is
+// 125 000 blocks at the shipped operating point (one term): without the sum 0.27, without the transform 0.29 (timing ablations); what is
 // left is latency per workgroup at 16 waves per CU (k_inv_wet runs the same transforms at 32).  drop: [count][256] {L, R}.
 #ifndef DF_WAVES
 #define DF_WAVES 8
@@ -1672,9 +1665,6 @@ __global__ __launch_bounds__(64 * DF_WAVES) __attribute__((amdgpu_waves_per_eu(D
     {
         const int nt = (int)gridDim.x, q = nt >> 3, r = nt & 7, xc = (int)blockIdx.x & 7;
         tile = xc * q + min(xc, r) + ((int)blockIdx.x >> 3);
-#ifdef DF_LINEAR
-        tile = (int)blockIdx.x;
-#endif
     }
     const int tb0 = tile * DF_WAVES;
     const int col = threadIdx.x % DF_WAVES, k0 = threadIdx.x / DF_WAVES;
@@ -1710,11 +1700,7 @@ __global__ __launch_bounds__(64 * DF_WAVES) __attribute__((amdgpu_waves_per_eu(D
             const int P0 = td.P0[vi], P1 = td.P1[vi], pmax = max(P0, P1);
             const float4* __restrict__ sg = td.slotgain + (size_t)vi * td.ring;
 #pragma unroll 1
-#if defined(DF_DBG) && DF_DBG == 1  // (timing ablation: no partition sum)
-            for (int p = p_lo_u; p < pmax && pd < 0; p++) {
-#else
             for (int p = p_lo_u; p < pmax; p++) {
-#endif
                 const int64_t t = b_s - kappa - a - p;
                 const bool ok = act_s && p >= p_lo && t >= blo && t >= 0;
                 const unsigned slot = (unsigned)(t < 0 ? 0 : t) & (unsigned)(td.ring - 1);
@@ -1783,12 +1769,7 @@ __global__ __launch_bounds__(64 * DF_WAVES) __attribute__((amdgpu_waves_per_eu(D
         __syncthreads();  // the tile is in registers: its memory becomes the transform buffers
         if (act_w) {
             float2* lds = s_mem + wave * FFT_WAVE_LDS;
-#if defined(DF_DBG) && DF_DBG == 2  // (timing ablation: no transform)
-            lds[lane] = v[0], lds[lane + 64] = v[1], lds[lane + 128] = v[2], lds[lane + 192] = v[3];
-            lds[lane + 256] = v[4], lds[lane + 320] = v[5], lds[lane + 384] = v[6], lds[lane + 448] = v[7];
-#else
             fft512_wave<+1, false>(v, lds, s_tw, lane);
-#endif
             const float sc = 1.0f / FFT_N;
 #pragma unroll
             for (int q = 0; q < 4; q++) {
@@ -2345,15 +2326,9 @@ __device__ __forceinline__ float2 f2_mul(float2 a, float2 b) { return make_float
 // 8-byte LDS accesses of the second-level transforms, LDS-qualified and volatile: the compiler would otherwise pair
 // neighbours into ds_read2_b64 / ds_write2_b64, which move their 16 bytes per lane at half the rate of two
 // ds_read_b64 (MI355X_MICROARCH.md, LDS table); measured 115 -> 111 us per 32320-block launch of k_g2_mac.
-// MC_LDS_PAIRED builds the paired form for comparison.
-#ifndef MC_LDS_PAIRED
 typedef __attribute__((address_space(3))) volatile v2f lds_vol_v2f;
 __device__ __forceinline__ v2f vx_ld(const float2* p) { return *(const lds_vol_v2f*)(p); }
 __device__ __forceinline__ void vx_st(float2* p, v2f v) { *(lds_vol_v2f*)(p) = v; }
-#else
-__device__ __forceinline__ v2f vx_ld(const float2* p) { return *reinterpret_cast<const v2f*>(p); }
-__device__ __forceinline__ void vx_st(float2* p, v2f v) { *reinterpret_cast<v2f*>(p) = v; }
-#endif
 // (v2f, vx_mul, vx_mulc, vx_add_j, vx_sub_j: fft512.hip.h)
 // radix-4 butterfly in place: forward y_m = sum_n a_n (-j)^(mn), inverse with +j
 template <bool INV>
@@ -2728,18 +2703,6 @@ __global__ __launch_bounds__(F2_THREADS) void k_f2_prod(const float2* __restrict
 #define G2_P(i) ((i) + ((i) >> 5))
 #define G2_LDS (G2_N + G2_N / 32)
 #define G2_THREADS 1024
-#ifndef G2_PW
-#define G2_PW 4  // window rows (of 8) requested one item ahead in the persistent form of k_g2_mac
-#endif
-#ifndef G2_PF
-#define G2_PF 2  // groups of product entries whose spectra are loaded together
-#endif
-#ifndef G2_ABL
-#define G2_ABL 0  // timing-only ablations of k_g2_mac (wrong results), bit flags: 1 no global memory, 2 no butterflies, 4 no LDS accesses in the passes that load AND store (scripts/gpu_abl.sh)
-#endif
-#ifndef G2_AHEAD
-#define G2_AHEAD 0  // 1: the first G2_PF groups' spectra are requested before the forward transforms
-#endif
 
 __device__ __forceinline__ float2 g2_tw(const float2* t_lo, const float2* t_hi, int e) { return f2_mul(t_lo[e & 127], t_hi[e >> 7]); }
 __device__ __forceinline__ v2f vg_tw(const float2* t_lo, const float2* t_hi, int e) { return vx_mul(vx_ld(t_lo + (e & 127)), vx_ld(t_hi + (e >> 7))); }
@@ -2758,9 +2721,6 @@ __device__ __forceinline__ void g2_tables(float2* t_lo, float2* t_hi) {  // w = 
 // the two radix-4 stages of a pass on a thread's 16 elements, in registers (a[m] = element pos0 + Q m)
 template <bool INV, int LQ>
 __device__ __forceinline__ void g2_pair_core(v2f (&a)[16], const float2* t_lo, const float2* t_hi, int j0) {
-#if G2_ABL & 2
-    return;
-#endif
     constexpr int step1 = G2_N >> (LQ + 4), step2 = G2_N >> (LQ + 2);
     const v2f wa = vg_tw(t_lo, t_hi, j0 * step1), w = vg_tw(t_lo, t_hi, j0 * step2);
     const v2f wr[4] = {wa, vx_mul(wa, W16_1), vx_mul(wa, W16_2), vx_mul(wa, W16_3)};
@@ -2799,16 +2759,6 @@ __device__ __forceinline__ void g2_pair(float2* s, const float2* t_lo, const flo
     // live across the whole kernel and spill
     asm volatile("" : "+v"(pos0), "+v"(j0));
     float2* p = s + G2_P(pos0);
-#if G2_ABL & 4
-    if (LOAD && STORE) {  // the butterflies on whatever the registers hold, kept alive without a store
-#pragma unroll
-        for (int m = 0; m < 16; m++) a[m] = v2f{__int_as_float(0x3f000000 | (pos0 + m)), __int_as_float(0x3f000000 | (j0 + m))};
-        g2_pair_core<INV, LQ>(a, t_lo, t_hi, j0);
-#pragma unroll
-        for (int m = 0; m < 16; m++) asm volatile("" ::"v"(a[m]));
-        return;
-    }
-#endif
     if (LOAD) {
 #pragma unroll
         for (int m = 0; m < 16; m++) a[m] = vx_ld(p + stride * m);
@@ -2925,18 +2875,11 @@ __global__ __launch_bounds__(G2_THREADS) void k_g2_ir(const float4* __restrict__
 #define G2B_THREADS 512
 // The 8/2 pass in a wave-local mapping: lane l of wave w works on parity l >> 5 of group 32 w + (l & 31) - the 32 groups
 // (1024 consecutive elements) that the same wave's 128/32 pass reads and writes.  The two passes therefore hand over
-// inside a wave: LDS operations of one wave execute in order, so no workgroup barrier sits between them (#if 0: the
-// barrier form, same mapping) and the waves of a workgroup drift apart instead of meeting 4 more times per item.
+// inside a wave: LDS operations of one wave execute in order, so no workgroup barrier sits between them and the waves
+// of a workgroup drift apart instead of meeting 4 more times per item.
 // Consecutive lanes are 33 entries apart as before: conflict-free.
 #define G2B_POS1(tt) (((32 * ((tt) >> 6) + ((tt) & 31)) << 5) + (((tt) >> 5) & 1))
-#ifndef G2B_WAVE_LOCAL
-#define G2B_WAVE_LOCAL 1
-#endif
-#if G2B_WAVE_LOCAL
 #define G2B_WAVE_SYNC() __builtin_amdgcn_wave_barrier()
-#else
-#define G2B_WAVE_SYNC() __syncthreads()
-#endif
 #ifndef G2B_AHEAD
 #define G2B_AHEAD 1  // entry pairs by which the spectra loads run ahead of the products (4 loads of 16 bytes each)
 #endif
@@ -2969,21 +2912,6 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_g2_mac(const float4* __restr
 #endif
     g2_tables(t_lo, t_hi);
     __syncthreads();  // the first forward pass runs on registers: nothing else orders its twiddle reads after the tables
-#if G2_STAMPS  // diagnostic build only: where a workgroup's time goes (s_memtime ticks = shader cycles)
-    unsigned long long st_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_prev = 0, st_now;
-    int st_items = 0;
-    const unsigned long long st_t0 = __builtin_amdgcn_s_memtime(), st_r0 = __builtin_amdgcn_s_memrealtime();
-#define G2_STAMP(k)                                                                       \
-    do {                                                                                  \
-        __builtin_amdgcn_sched_barrier(0);                                                \
-        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_now)::"memory");      \
-        __builtin_amdgcn_sched_barrier(0);                                                \
-        if ((k) >= 0) st_acc[(k) < 0 ? 0 : (k)] += st_now - st_prev;                      \
-        st_prev = st_now;                                                                 \
-    } while (0)
-#else
-#define G2_STAMP(k) do { } while (0)
-#endif
     constexpr int ROWS = G2_N / G2B_THREADS;        // 16 window entries per thread and sequence
     constexpr int PS = 2 * G2B_THREADS + 2 * G2B_THREADS / 32;  // ... of entry pairs 2 j, 2 (j + 512)
     for (int item = blockIdx.x; item < nitems; item += main_grid) {
@@ -2991,17 +2919,12 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_g2_mac(const float4* __restr
         const int bin = (xq / nch) * 8 + (item & 7), chunk = xq % nch;
         const int t_c0 = chunk * chunk_t, nout = min(chunk_t, T - t_c0), L = nout + taps - 1;
         const float4* fk = fdl + (size_t)bin * ring;
-#ifdef G2_ALIAS_TEST  // timing only (wrong data): every bin's window starts 1 KB further - does the 1 MB bin stride alias in HBM?
-        const int sb = slot0 + t_c0 - (taps - 1) + 64 * bin;
-#else
         const int sb = slot0 + t_c0 - (taps - 1);
-#endif
         for (int pass = 0; pass < (bin == 0 ? 2 : 1); pass++) {
             const float cj = pass ? -1.0f : 1.0f;  // second run of bin 0: conj(z)
             const int row = pass ? 256 : bin;
             int tt = threadIdx.x;
             asm volatile("" : "+v"(tt));
-            G2_STAMP(-1);
             // ---- window: 16 bytes per slot carry both inputs.  The rows a thread loads, n = tt + 512 r, are exactly its 16
             // elements of the first forward pass: that pass runs on the registers (x1 at once, x2 when the buffer is free)
             v2f x1[ROWS], x2[ROWS];
@@ -3013,11 +2936,7 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_g2_mac(const float4* __restr
                     for (int r = 0; r < G2B_FILL; r++) {
                         const int n = tt + G2B_THREADS * (r0 + r);
                         x[r] = make_float4(0.f, 0.f, 0.f, 0.f);
-#if G2_ABL & 1
-                        if (n < L) x[r] = make_float4(__int_as_float(0x3c000000 | n), 0.25f, -0.5f, __int_as_float(0x3c800000 | n));
-#else
                         if (n < L) x[r] = fk[(sb + n) & (ring - 1)];
-#endif
                     }
 #pragma unroll
                     for (int r = 0; r < G2B_FILL; r++) {
@@ -3026,14 +2945,12 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_g2_mac(const float4* __restr
                     }
                 }
             }
-            G2_STAMP(0);
             g2_pair<false, 9, false, true>(s, t_lo, t_hi, tt, tt, x1);  // quarter lengths 2048, 512
             __syncthreads();
             g2_pair<false, 5>(s, t_lo, t_hi, ((tt >> 5) << 9) + (tt & 31), tt & 31);  // 128, 32
             G2B_WAVE_SYNC();  // a wave's 1024 elements of this pass are the 32 groups its last pass works on
             g2_pair<false, 1>(s, t_lo, t_hi, G2B_POS1(tt), (tt >> 5) & 1);  // 8, 2
             __syncthreads();
-            G2_STAMP(1);
             // ---- own entries of X1 (pairs 2 j, 2 j + 1, j = tt + 512 r; the radix-2 stage on the way) to registers
             v2f X1[ROWS];
             {
@@ -3047,14 +2964,12 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_g2_mac(const float4* __restr
                 }
             }
             __syncthreads();  // every thread has its X1 entries: the buffer is free for x2
-            G2_STAMP(2);
             g2_pair<false, 9, false, true>(s, t_lo, t_hi, tt, tt, x2);
             __syncthreads();
             g2_pair<false, 5>(s, t_lo, t_hi, ((tt >> 5) << 9) + (tt & 31), tt & 31);
             G2B_WAVE_SYNC();
             g2_pair<false, 1>(s, t_lo, t_hi, G2B_POS1(tt), (tt >> 5) & 1);
             __syncthreads();
-            G2_STAMP(3);
             // ---- products: Y_c = sum_voices g (X1 H1c + X2 H2c) on the thread's own entries; Y_L replaces X2 in LDS,
             // Y_R replaces X1 in registers.  The first voice's spectra run G2B_AHEAD entry pairs ahead of the arithmetic
             // (4 loads of 16 bytes per pair, a ring of G2B_AHEAD + 1 pairs in registers).
@@ -3069,13 +2984,8 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_g2_mac(const float4* __restr
                     const unsigned off = ((unsigned)tt + G2B_THREADS * (unsigned)r) * 16u;
 #pragma unroll
                     for (int i = 0; i < 2; i++) {
-#if G2_ABL & 1
-                        HLq[r % RING][i] = make_float4(__int_as_float(0x3c000000 | off), 0.5f, 0.25f, __int_as_float(0x3c400000 | off));
-                        HRq[r % RING][i] = make_float4(0.5f, __int_as_float(0x3c000000 | off), __int_as_float(0x3c400000 | off), 0.25f);
-#else
                         HLq[r % RING][i] = *reinterpret_cast<const float4*>(hrow[i] + off);
                         HRq[r % RING][i] = *reinterpret_cast<const float4*>(hrow[i] + (size_t)257 * G2_N * sizeof(float2) + off);
-#endif
                     }
                 };
 #pragma unroll
@@ -3116,7 +3026,6 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_g2_mac(const float4* __restr
                 }
             }
             __syncthreads();
-            G2_STAMP(4);
             // ---- inverse of Y_L; its last pass leaves element tt + 512 m = output block tt + 512 m - (taps - 1) in registers
             v2f yl[ROWS];
             g2_pair<true, 1>(s, t_lo, t_hi, G2B_POS1(tt), (tt >> 5) & 1);
@@ -3124,7 +3033,6 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_g2_mac(const float4* __restr
             g2_pair<true, 5>(s, t_lo, t_hi, ((tt >> 5) << 9) + (tt & 31), tt & 31);
             __syncthreads();
             g2_pair<true, 9, true, false>(s, t_lo, t_hi, tt, tt, yl);
-            G2_STAMP(5);
             __syncthreads();
             {
                 asm volatile("" : "+v"(tt));
@@ -3136,7 +3044,6 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_g2_mac(const float4* __restr
                 }
             }
             __syncthreads();
-            G2_STAMP(6);
             {
                 v2f yr[ROWS];
                 g2_pair<true, 1>(s, t_lo, t_hi, G2B_POS1(tt), (tt >> 5) & 1);
@@ -3144,7 +3051,6 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_g2_mac(const float4* __restr
                 g2_pair<true, 5>(s, t_lo, t_hi, ((tt >> 5) << 9) + (tt & 31), tt & 31);
                 __syncthreads();
                 g2_pair<true, 9, true, false>(s, t_lo, t_hi, tt, tt, yr);
-                G2_STAMP(7);
                 // the valid part of the circle: its first taps - 1 outputs are discarded
                 asm volatile("" : "+v"(tt));
                 const float sc = 1.0f / (float)G2_N;
@@ -3152,11 +3058,7 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_g2_mac(const float4* __restr
 #pragma unroll
                 for (int m = 0; m < ROWS; m++) {
                     const int t = tt + G2B_THREADS * m - (taps - 1);
-#if G2_ABL & 1
-                    if (t >= 0 && t < nout && ycap < 0) {
-#else
                     if (t >= 0 && t < nout) {
-#endif
                         float4 y = make_float4(yl[m].x * sc, yl[m].y * sc, yr[m].x * sc, yr[m].y * sc);  // (second run of bin 0: h2 * conj z)
                         if (pass) {
                             const float4 o = dst[t];
@@ -3167,23 +3069,7 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_g2_mac(const float4* __restr
                 }
             }
             __syncthreads();  // the buffer is free for the next run
-            G2_STAMP(8);
-#if G2_STAMPS
-            st_items++;
-#endif
         }
     }
-#if G2_STAMPS
-    if (threadIdx.x == 0 && (blockIdx.x == 3 || blockIdx.x == 137 || blockIdx.x == 300 || blockIdx.x == 700 || blockIdx.x == 1100)) {
-        const unsigned long long dt = __builtin_amdgcn_s_memtime() - st_t0, dr = __builtin_amdgcn_s_memrealtime() - st_r0;
-        printf("g2 wg %d: %llu cycles in %llu x 10 ns = %.0f MHz\n", (int)blockIdx.x, dt, dr, (double)dt / (double)dr * 100.0);
-    }
-    if (threadIdx.x == 0 && (blockIdx.x == 3 || blockIdx.x == 137 || blockIdx.x == 300 || blockIdx.x == 700 || blockIdx.x == 1100))
-        printf("g2 wg %d items %d: fill %llu fwd1 %llu x1regs+x2fill %llu fwd2 %llu products %llu inv1 %llu out1+yrfill %llu inv2 %llu store %llu\n",
-               (int)blockIdx.x, st_items, st_acc[0], st_acc[1], st_acc[2], st_acc[3], st_acc[4], st_acc[5], st_acc[6], st_acc[7], st_acc[8]);
-#endif
 }
 
-#ifdef MCCONV_LAB
-#include "lab_kernels.hip.h"
-#endif

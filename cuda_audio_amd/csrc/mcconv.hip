@@ -27,15 +27,16 @@
 #include "singlefft.hip.h"
 #include "resample.hip.h"
 
-// Environment switches.  The default library reads ten - MCCONV_FORM, _OS, _FFT2, _FFT2_FUSED, _FFA_LEVELS (which form sums the
-// partitions), _TD_FFT (Q8 cut terms in the time domain), _NO_PARK, _PARK_MS, _NO_SPIN, _BAR_IO (the JACK path's waiting and I/O) -
-// all of which select paths a caller can also reach through mc_config or that the tests compare bit for bit.  Every other switch
-// of rounds 1-3 selects a measured-and-lost alternative or a measurement and exists only under -DMCCONV_LAB (scripts/build_variant.sh).
-#ifdef MCCONV_LAB
-#define LAB_ENV(name) std::getenv(name)
-#else
-#define LAB_ENV(name) (static_cast<const char*>(nullptr))
-#endif
+// Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
+// mc_config or that the tests compare bit for bit:
+//   MCCONV_FORM, _OS, _FFT2, _FFT2_FUSED, _FFA_LEVELS  which form sums the partitions
+//   MCCONV_TD_FFT                                      Q8 cut terms in the time domain
+//   MCCONV_NO_PARK, _PARK_MS, _NO_SPIN, _BAR_IO        the JACK path's waiting and I/O
+// Four are test hooks that make a path of the library reachable at test sizes:
+//   MCCONV_OS_MIN        shortest batch that takes the overlap-save form (mc_engine::os_min_blocks)
+//   MCCONV_FFT2_WORK     blocks x partitions from which a batch takes the fused second-level form (mc_engine::fft2_work)
+//   MCCONV_TAIL_FORM     td | fd: one form for every 256-frame JACK tail (mc_engine::tail_form)
+//   MCCONV_SF_STOCKHAM   single-transform form: pass 2 of the inverse through the LDS transform at every size (SfState::stockham)
 
 namespace {
 
@@ -61,6 +62,9 @@ constexpr int kStageBufs = 4;
 constexpr int kEvPool = 1024;
 constexpr int kPipe = 2;
 constexpr int kStampSlots = 64;  // timed launches between two drains whose kernels leave their own time stamps
+constexpr int kNchunk = 2;       // partition chunks of the streaming MAC: its workgroups per (bin, block)
+constexpr int kG2Pmax = 5632;    // longest block-axis convolution (partitions) the fused 8192-point form takes: measured crossover
+                                 // with the split 16384-point form ~5700 (30 s IRs, P = 5168: 0.25 vs 0.27 ms for a third more blocks)
 
 inline uint32_t next_pow2(uint64_t v) {
     uint32_t p = 1;
@@ -167,10 +171,9 @@ struct mc_engine {
     SfState* sf = nullptr;  // != null: the engine runs the reference's single-transform form (singlefft.hip.h)
     hipStream_t own_stream = nullptr, stream = nullptr;
     int Tcap = 0;  // blocks the scratch buffers and rings are sized for: >= Tmax, and enough to re-render history in few launches
-    int Tmax = 0, Pcap = 0, Pstride = 0, ring = 0, sr = 0, wr = 0, rc = 0, nchunk = 2, Tstream = 0;
+    int Tmax = 0, Pcap = 0, Pstride = 0, ring = 0, sr = 0, wr = 0, rc = 0, Tstream = 0;
     int stream_threshold = 0;
     int pm = 1;  // blocks per reference call (JACK period / 256): 1, 2 or 4
-    int stream_nt = 256;
     IrEntry irs[kMaxIrs + kMixIrs];
     int mix_buf[2] = {0, 0};  // which of its two merged-IR entries half i used last
     int nirs = 0;
@@ -206,13 +209,12 @@ struct mc_engine {
     float* d_io[4] = {nullptr, nullptr, nullptr, nullptr};  // in1, in2, outL, outR staging for host-pointer calls
     int Thost = 0;                                          // blocks per chunk of a host-buffer batch staged through h_io
     // host-buffer batches whose buffers are pinned (mc_host_alloc, hipHostMalloc, hipHostRegister): chunks of Tdev blocks,
-    // H2D / compute / D2H on three streams, two chunks in flight; device staging allocated on first use
-    // (three staging sets: with two, copy-in waiting for the kernels of chunk k - 2 and the kernels waiting for the copy-out of
-    // chunk k - 2 lock the three streams into taking turns - 2.9 instead of 1.5 ms per 32320-block chunk, scripts/pcie_pipeline_probe.py)
-    float* d_pio[3][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
+    // H2D and compute on two streams, the output stored straight into the caller's buffers; input staging (three sets)
+    // allocated on first use
+    float* d_pio[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
     int Tdev = 0;
-    hipStream_t h2d_stream = nullptr, d2h_stream = nullptr;
-    hipEvent_t ev_h2d[3] = {nullptr, nullptr, nullptr}, ev_comp[3] = {nullptr, nullptr, nullptr}, ev_d2h[3] = {nullptr, nullptr, nullptr};
+    hipStream_t h2d_stream = nullptr;
+    hipEvent_t ev_h2d[3] = {nullptr, nullptr, nullptr}, ev_comp[3] = {nullptr, nullptr, nullptr};
     float* h_io = nullptr;                                  // pinned mirror of d_io, 4 * Thost * 256
     float* hd_io = nullptr;                                 // device-side address of h_io (mapped, zero-copy)
     unsigned* h_flag = nullptr;                             // completion word of the single-period path (mapped)
@@ -255,7 +257,7 @@ struct mc_engine {
     int pipe_head = 0, pipe_count = 0;
     uint64_t batch_seq = 0;
     // speculative MAC of the next single block (partitions >= 1 do not depend on the next input)
-    bool speculate = true, spec_valid = false;
+    bool spec_valid = false;
     // Q8 regime, JACK path: the cut terms a parked launch summed for the period after its own (SweepArgs.drop_next): valid for that block while
     // predelay, epoch and the voices' IRs are what they were (everything else they depend on is at least n_ref frames old)
     struct DropSpec {
@@ -264,7 +266,6 @@ struct mc_engine {
         int vir[2][MC_MAXV];
         const float* buf = nullptr;
     } dspec;
-    bool carry_drop = true;  // MCCONV_CARRY_DROP=0: always a launch of its own (k_drop_period_fft) (measurement)
     uint64_t spec_block = 0;
     int spec_vir[2][MC_MAXV];
     int spec_nact = 0;
@@ -284,18 +285,16 @@ struct mc_engine {
     float* d_bar = nullptr;
     bool bar_io = false;
     // Tagged I/O of the 256-frame JACK path (TailArgs::in_gran / out_gran): input granules at byte 16384 of d_bar, output granules
-    // in mapped host memory.  On where the BAR path is (MCCONV_TAGGED_IO=0: doorbell + completion word as in round 2).
+    // in mapped host memory.  On where the BAR path is.
     bool tio = false;
-    bool tio_long = false;  // ... also for 512 / 1024-frame periods (MCCONV_TAGGED_IO=2; measured slower there: twice the bytes over the link)
     unsigned long long* h_gran = nullptr;   // [2][256] output granules {value, sequence number}
     unsigned long long* hd_gran = nullptr;
-    bool host_out_direct = true;  // MCCONV_HOST_OUT_DIRECT=0: pinned-buffer batches copy their output out instead of storing it to the host
     unsigned* h_exited = nullptr;                 // mapped: sequence number of a parked tail that gave up on its own
     unsigned* hd_exited = nullptr;
     // how often a parked period was used / gave up on its own (host away > park_ms) / was told to give up: mc_debug_read item 6
     uint64_t n_park_hit = 0, n_park_timeout = 0, n_park_cancel = 0;
     unsigned* d_tailform = nullptr;  // 256-frame tails by the form partition 0 took {frequency domain, time domain}, counted by the kernel (mc_debug_read item 16)
-    int tail_form = 0;               // lab build, MCCONV_TAIL_FORM=td|fd: one form for every 256-frame tail (0: the first look decides)
+    int tail_form = 0;               // MCCONV_TAIL_FORM=td|fd: one form for every 256-frame tail (0: the first look decides)
     uint64_t n_drop_carried = 0;  // JACK path, Q8 regime: periods whose cut terms came with the launch before theirs (mc_debug_read item 9, fourth word)
     uint64_t n_mac_form[3] = {0, 0, 0};  // batches whose partition sums took the fused / split second-level transform / the resident MAC (mc_debug_read item 10)
     uint64_t n_drop_fft = 0, n_drop_ahead = 0, n_drop_tiles = 0;  // Q8 regime: batches by the form their cut terms took (mc_debug_read item 9)
@@ -306,34 +305,16 @@ struct mc_engine {
 #endif
     bool fft2 = true;     // long batches: second-level transform along the block axis instead of the MAC
     bool fft2_fused = true;  // ... in the fused 8192-point form where it applies
-    bool debug_addr = false;  // MCCONV_DEBUG_ADDR: print the device ranges k_g2_mac touches at its first launch (fault triage)
-    int g2_grid = 1 << 30;   // workgroups of k_g2_mac, capped by the number of (bin, chunk) items (default: one per item); MCCONV_G2_GRID
-    int g2_pmax = 5632;      // longest block-axis convolution (partitions) the fused 8192-point form takes (MCCONV_G2_PMAX):
-                             // measured crossover with the split 16384-point form ~5700 (30 s IRs, P = 5168: 0.25 vs 0.27 ms
-                             // for a third more blocks)
     int64_t fft2_work = 300000;  // blocks x partitions from which a batch takes the fused second-level form (MCCONV_FFT2_WORK)
-    int g2_pmin = 16;        // shortest block-axis convolution (partitions, uniform gains) of an unsharded engine that takes the
-                             // second-level transform (MCCONV_G2_PMIN; round 1: 256)
-    bool corr_ride = true;   // MCCONV_CORR_RIDE=0: the Q1/Q2 prefix steps as launches of their own (measurement)
-    bool drop_ahead = true;  // MCCONV_DROP_AHEAD=0: Q8 regime: every cut term through k_drop_fft, none summed by the forward transforms (measurement)
-    bool fuse_drop = true;   // MCCONV_FUSE_DROP=0: Q8 regime: the output through k_post<3> even where the inverse transforms could finish it (measurement)
-    bool fuse_out = true;    // MCCONV_FUSE_OUT=0: the output always through k_post (measurement)
     unsigned* d_cticket = nullptr;  // ticket counter of the riding prefix-sum workgroups (see CorrArgs)
     unsigned* d_cflag = nullptr;    // [ceil(Tmax/256)] launch sequence number per published chunk total
     unsigned cticket_base = 0, cflag_seq = 0;
-    // k_g2_duo (round 3): one 1024-thread workgroup per CU whose halves run the items' phases in lockstep, one phase apart.
-    // Measured equal to k_g2_mac at 20 chunks per bin and slower below (profiles/r3_g2_ablation.md): NOT the default;
-    // MCCONV_G2_DUO=1 selects it for launches of at least _DUO_MINCH chunks per bin; _DUO_GRID: its workgroups (a multiple
-    // of 8, default = the CUs)
-    bool g2_duo = false;
-    int g2_duo_minch = 3, g2_duo_grid = 256;
-    bool g2_wide = false;    // MCCONV_G2_WIDE=1: the one-workgroup-per-CU form of the kernel (1024 threads, both sequences in LDS)
     // Long settled batches as overlap-save segments of 512 x 8192 frames (ossave.hip.h): whole batches on one fp32 engine whose
     // window carries one set of gains, outside the Q8 regime.  Buffers and the spectra of the sounding (IR set, gains) are
     // made by the first batch that takes the form.
     bool os_hold = false;       // set around a batch whose output pointers are mapped HOST memory (mc_process_batch with pinned buffers)
     bool os_on = true;          // MCCONV_OS=0: such batches through the second-level transform as before (measurement)
-    int os_min_blocks = 12288;  // shortest batch that takes the form (a segment costs the same however little of it is used)
+    int os_min_blocks = 12288;  // shortest batch that takes the form (a segment costs the same however little of it is used; MCCONV_OS_MIN)
     float4* d_os_T = nullptr;   // [segments][256 row pairs][8192] {row k1, row 512 - k1} between the passes
     size_t os_T_segs = 0;
     float4* d_os_part = nullptr;  // [segments][512 tiles][512] the tiles' sixteenths of the blocks' sums {S1, S2, A1, A2}
@@ -351,13 +332,11 @@ struct mc_engine {
     uint64_t ir_gen = 0;                  // counts changes of any IR's taps (load, reload, merge)
     uint64_t n_os[2] = {0, 0};            // batches that took the form, spectra builds (mc_debug_read item 11)
     // the small launches of such a batch - prefix sums, the tail's delay-line slots, the last block's segment - run on a side
-    // stream beside the three passes (MCCONV_OS_SIDE=0: in line, measurement)
-    bool os_side = true;
+    // stream beside the three passes
     hipStream_t os_stream = nullptr;
     hipEvent_t os_ev[3] = {nullptr, nullptr, nullptr};
     int ffa_levels = 3;   // resident MAC in fast-FIR form (up to this many nested levels) when batch and IR are long enough
     bool sliced = false;  // block-sliced calls keep no wet / segment history outside their slices
-    bool inv_to_wet = true;  // whole-batch path: k_inv_wet + ring-reading k_post (MCCONV_INV_WET=0: k_inv + segment ring)
     int slice_first = -1;  // ... and transform only what their windows reach: the slice start must not move
     bool uniform_valid[2] = {false, false};
     BlockParams uniform_bp[2];
@@ -522,14 +501,13 @@ void invalidate_derived(IrEntry& ir) {
 }
 // The last partitions of an IR's spectra, partition-major, for k_drop_fft: every workgroup of that launch reads the same few
 // partitions of all 256 bins, and in the bin-major bank those entries lie Pstride * 16 bytes apart (one 128-byte line fetched per
-// 16 bytes used, all of them in one L2 channel).  Worth 2-4 % of the step (scripts/gpu_q8_pd.sh, MCCONV_HTAIL=0 turns it off): the launch
+// 16 bytes used, all of them in one L2 channel).  Worth 2-4 % of the step (round 3, measured with a switch since retired): the launch
 // is bound by its latency per workgroup, not by these reads.  kTailSpan partitions cover every predelay the controllers can reach
 // (8192 frames = 32 partitions, + 2); a term outside falls back to the bank.
 constexpr int kTailSpan = 48;
 int ensure_htail(mc_engine* e, const IrEntry* irc) {
     IrEntry& ir = *const_cast<IrEntry*>(irc);
-    static const bool off = LAB_ENV("MCCONV_HTAIL") && std::atoi(LAB_ENV("MCCONV_HTAIL")) == 0;
-    if (ir.tail_valid || !ir.d_H || off) return MC_OK;
+    if (ir.tail_valid || !ir.d_H) return MC_OK;
     if (!ir.d_Htail) HIP_TRY(hipMalloc(&ir.d_Htail, sizeof(float4) * (size_t)kTailSpan * MC_NB));
     ir.tail_p0 = std::max(0, ir.P - kTailSpan);
     hipLaunchKernelGGL(k_h_tail, dim3(kTailSpan), dim3(MC_NB), 0, e->stream, (const float4*)ir.d_H, e->Pstride, ir.tail_p0, ir.P, ir.d_Htail);
@@ -978,32 +956,23 @@ void launch_mac_stream(mc_engine* e, const ActiveVoice& a, int p_lo, int p_hi, i
                        float4* dst = nullptr, unsigned long long* stamps = nullptr) {
     if (!dst) dst = e->d_part;
     const hipStream_t st = e->stream;
-    const int nt = e->stream_nt;
     const int span = p_hi - p_lo;
-    const int chunk = round_up(std::max(1, (span + e->nchunk - 1) / e->nchunk), 64);
-    const dim3 grid(MC_NB, e->nchunk, T);
+    const int chunk = round_up(std::max(1, (span + kNchunk - 1) / kNchunk), 64);
+    const dim3 grid(MC_NB, kNchunk, T);
     const float4* sg = e->d_slotgain + (size_t)a.v * e->ring;
     const bool half = e->half && a.ir0->d_H16 && a.ir1->d_H16;
     const void* h0 = half ? (const void*)a.ir0->d_H16 : (const void*)a.ir0->d_H;
     const void* h1 = half ? (const void*)a.ir1->d_H16 : (const void*)a.ir1->d_H;
     const void* fd = half ? (const void*)e->d_fdl16 : (const void*)e->d_fdl;
     const float2 inv = make_float2(1.0f / (a.ir0->scale16 * FDL16_SCALE), 1.0f / (a.ir1->scale16 * FDL16_SCALE));
-#define MC_LAUNCH_STREAM(U, NT, H)                                                                                        \
-    hipLaunchKernelGGL((k_mac_stream<U, NT, H>), grid, dim3(NT), 0, st, h0, h1, e->Pstride, p_lo, p_hi, chunk, fd, sg, \
+#define MC_LAUNCH_STREAM(U, H)                                                                                              \
+    hipLaunchKernelGGL((k_mac_stream<U, 256, H>), grid, dim3(256), 0, st, h0, h1, e->Pstride, p_lo, p_hi, chunk, fd, sg, \
                        e->ring, slot0, dst, nsum, ch_off, a.ugain, inv, stamps)
-#define MC_LAUNCH_STREAM_H(U, NT) \
-    do {                          \
-        if (half)                 \
-            MC_LAUNCH_STREAM(U, NT, true); \
-        else                      \
-            MC_LAUNCH_STREAM(U, NT, false); \
-    } while (0)
-    if (nt == 512) {
-        if (a.uniform) MC_LAUNCH_STREAM_H(true, 512); else MC_LAUNCH_STREAM_H(false, 512);
+    if (a.uniform) {
+        if (half) MC_LAUNCH_STREAM(true, true); else MC_LAUNCH_STREAM(true, false);
     } else {
-        if (a.uniform) MC_LAUNCH_STREAM_H(true, 256); else MC_LAUNCH_STREAM_H(false, 256);
+        if (half) MC_LAUNCH_STREAM(false, true); else MC_LAUNCH_STREAM(false, false);
     }
-#undef MC_LAUNCH_STREAM_H
 #undef MC_LAUNCH_STREAM
 }
 
@@ -1084,12 +1053,12 @@ bool fft2_applies(const mc_engine* e, const ActiveVoice* act, int nact, bool per
     const int taps = block_axis_taps(e, act, nact, nullptr);
     if (taps > F2_N / 2) return false;
     const bool shard = e->cfg.part_begin || e->cfg.part_end;
-    if (!per_slot && e->fft2_fused && taps <= e->g2_pmax)
+    if (!per_slot && e->fft2_fused && taps <= kG2Pmax)
         // Uniform gains, fused form: a launch costs ~39 us per chunk of 8192 - taps + 1 blocks whatever the taps; the direct
         // MAC ~10 us + 0.078 ns per block and partition (and never less than ~40 us for the longest IRs: one workgroup
         // sweeps its partitions in turn).  Measured (P = 1728 / 345 / 32): the transform wins from 128 / ~900 / ~9000
         // blocks on - a product of ~300 000 (MCCONV_FFT2_WORK)
-        return taps >= (shard ? 16 : e->g2_pmin) && (int64_t)T * taps >= e->fft2_work;
+        return taps >= 16 && (int64_t)T * taps >= e->fft2_work;
     // per-slot gains (or the fused form switched off): the split form, two launches and a stash
     if (T < 768) return false;
     if (shard) return taps >= 16 && (int64_t)T * taps >= 1300000;
@@ -1140,7 +1109,7 @@ int launch_mac_batch(mc_engine* e, const ActiveVoice* act, int nact, bool per_sl
             // transform gain(slot) x input for every voice and path
             bool per_slot = per_slot_gains;
             for (int a = 0; a < nact; a++) per_slot = per_slot || !act[a].uniform;
-            if (!per_slot && e->fft2_fused && pmax <= e->g2_pmax) {
+            if (!per_slot && e->fft2_fused && pmax <= kG2Pmax) {
                 // fused form: both inputs' 8192-point spectra side by side in LDS, no stash (k_g2_mac)
                 for (int a = 0; a < nact; a++) {
                     int rc = ensure_g2(e, act[a].ir0);
@@ -1151,42 +1120,17 @@ int launch_mac_batch(mc_engine* e, const ActiveVoice* act, int nact, bool per_sl
                 }
                 const int chunk_t = G2_N - pmax + 1;
                 const int nch = (T + chunk_t - 1) / chunk_t;
-                if (e->debug_addr) {
-                    // every address the kernel forms lies in one of these ranges (see the bounds argument at k_g2_mac)
-                    e->debug_addr = false;
-                    fprintf(stderr, "mcconv k_g2_mac: T %d chunk_t %d taps %d items %d grid %d\n  fdl  [%p, %p)\n  Yc   [%p, %p) (written: %d of %d entries per bin)\n",
-                            T, chunk_t, pmax, MC_NB * nch, std::min(MC_NB * nch, e->g2_grid), (void*)e->d_fdl, (void*)(e->d_fdl + (size_t)MC_NB * e->ring),
-                            (void*)e->d_Yc, (void*)(e->d_Yc + (size_t)MC_NB * e->Tcap), T, e->Tcap);
-                    for (int a = 0; a < nact; a++)
-                        fprintf(stderr, "  G2[%d] in1 [%p, %p) in2 [%p, %p)\n", a, (void*)vv.h0[a], (void*)(vv.h0[a] + (size_t)2 * 257 * G2_N),
-                                (void*)vv.h1[a], (void*)(vv.h1[a] + (size_t)2 * 257 * G2_N));
+                CorrArgs ca;
+                std::memset(&ca, 0, sizeof(ca));
+                if (ride && ride->nchunks > 0) {
+                    ca = *ride;
+                    mo->corr_done = true;
                 }
-#ifdef MCCONV_LAB  // the measured alternatives of k_g2_mac (lab_kernels.hip.h)
-                if (e->g2_duo && !e->g2_wide && nch >= e->g2_duo_minch && e->g2_grid == (1 << 30)) {
-                    // the lockstep form: persistent, two workers (the halves of a workgroup) per CU; the Q1/Q2 terms do not ride
-                    // along (a rider would need a CU of its own: the launches of their own follow, as for every long batch)
-                    const int grid = std::max(8, std::min(e->g2_duo_grid, 256) & ~7);
-                    static const int solo = LAB_ENV("MCCONV_G2_DUO_SOLO") ? std::atoi(LAB_ENV("MCCONV_G2_DUO_SOLO")) : 0;  // (measurement: one group works alone)
-                    const int wpl = (grid >> 3) * (solo ? 1 : 2), nxq = (MC_NB * nch) >> 3;
-                    hipLaunchKernelGGL(k_g2_duo, dim3(grid), dim3(G2D_THREADS), 0, e->stream, e->d_fdl, e->ring, slot0, T, chunk_t, pmax, vv,
-                                       e->d_Yc, e->Tcap, MC_NB * nch, (nxq + wpl - 1) / wpl, solo);
-                } else if (e->g2_wide)  // the one-workgroup-per-CU form (MCCONV_G2_WIDE=1)
-                    hipLaunchKernelGGL(k_g2_mac_wide, dim3(std::min(MC_NB * nch, e->g2_grid)), dim3(G2_THREADS), 0, e->stream, e->d_fdl,
-                                       e->ring, slot0, T, chunk_t, pmax, vv, e->d_Yc, e->Tcap, MC_NB * nch);
-                else
-#endif
-                {
-                    CorrArgs ca;
-                    std::memset(&ca, 0, sizeof(ca));
-                    if (ride && ride->nchunks > 0) {
-                        ca = *ride;
-                        mo->corr_done = true;
-                    }
-                    const int main_grid = std::min(MC_NB * nch, e->g2_grid);
-                    static const int dyn_lds = LAB_ENV("MCCONV_G2_DYNLDS") ? std::atoi(LAB_ENV("MCCONV_G2_DYNLDS")) : 0;  // (measurement: extra LDS per workgroup, > 22 KB leaves one workgroup per CU)
-                    hipLaunchKernelGGL(k_g2_mac, dim3(main_grid + ca.nchunks), dim3(G2B_THREADS), dyn_lds, e->stream, e->d_fdl, e->ring, slot0, T,
-                                       chunk_t, pmax, vv, e->d_Yc, e->Tcap, MC_NB * nch, ca, main_grid);
-                }
+                // one workgroup per (bin, chunk) item - the dispatcher keeps two resident per CU and hands a CU its next one the
+                // moment a slot frees (measured against 512 persistent workgroups striding over 1280 items: 98 vs 108 us)
+                const int main_grid = MC_NB * nch;
+                hipLaunchKernelGGL(k_g2_mac, dim3(main_grid + ca.nchunks), dim3(G2B_THREADS), 0, e->stream, e->d_fdl, e->ring, slot0, T,
+                                   chunk_t, pmax, vv, e->d_Yc, e->Tcap, MC_NB * nch, ca, main_grid);
                 mo->ysrc = e->d_Yc;
                 mo->sk = e->Tcap;
                 mo->stt = 1;
@@ -1276,11 +1220,11 @@ int launch_mac_batch(mc_engine* e, const ActiveVoice* act, int nact, bool per_sl
         mo->main_n = T - S;
         // the last S blocks: streaming kernel, one set of chunk partials per voice
         mo->tail_n = S;
-        mo->tail_nsum = nact * e->nchunk;
+        mo->tail_nsum = nact * kNchunk;
         for (int a = 0; a < nact; a++) {
             ActiveVoice av = act[a];
             if (per_slot_gains) av.uniform = false;
-            launch_mac_stream(e, av, 0, av.p_end, S, (slot0 + T - S) & (e->ring - 1), mo->tail_nsum, a * e->nchunk, e->d_tail);
+            launch_mac_stream(e, av, 0, av.p_end, S, (slot0 + T - S) & (e->ring - 1), mo->tail_nsum, a * kNchunk, e->d_tail);
         }
         mo->tail_ysrc = e->d_tail;
         mo->tail_sk = mo->tail_nsum;
@@ -1331,10 +1275,10 @@ int launch_mac_batch(mc_engine* e, const ActiveVoice* act, int nact, bool per_sl
             if (per_slot_gains) list[nv].uniform = false;
             nv++;
         }
-        mo->nsum = std::max(1, nv) * e->nchunk;
+        mo->nsum = std::max(1, nv) * kNchunk;
         if (!nv) HIP_TRY(hipMemsetAsync(e->d_part, 0, sizeof(float4) * (size_t)T * MC_NB * mo->nsum, e->stream));
         for (int a = 0; a < nv; a++) {
-            launch_mac_stream(e, list[a], pb[a], pe[a], T, slot0, mo->nsum, a * e->nchunk);
+            launch_mac_stream(e, list[a], pb[a], pe[a], T, slot0, mo->nsum, a * kNchunk);
             mo->swept = std::max(mo->swept, pe[a] - pb[a]);
         }
         mo->ysrc = e->d_part;
@@ -1462,7 +1406,7 @@ void corr_chunks(CorrArgs* ca, int T, int need_a0, int need_a1, int need_b0) {
 // the shipped shape (every output block loses ONE term of ONE source block: the forward transforms sum the cut terms, q8_ok).
 bool os_applies(const mc_engine* e, const Staged& st, int count, bool slice, const float* d_in1, const float* d_in2, const float* d_outL,
                 const float* d_outR, bool q8_ok, int* ovl_blocks) {
-    if (!e->os_on || e->os_hold || e->pipelined || !e->fuse_out || !e->inv_to_wet || (e->sliced && !slice)) return false;
+    if (!e->os_on || e->os_hold || e->pipelined || (e->sliced && !slice)) return false;
     if (e->cfg.part_begin || e->cfg.part_end || !d_outL || !d_outR || count < e->os_min_blocks || st.ctx.pstride != 0 || st.nact <= 0) return false;
     // (mc_config.stream_threshold asks for the literal MAC below it; engines with fp16 storage keep it for the partition sweep of
     // single periods and short batches - the spectra of this form come from the fp32 taps whatever the storage of the sweep)
@@ -1586,7 +1530,7 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
     // (on HIP's special stream handles - MC_STREAM_DEFAULT = hipStreamLegacy, hipStreamPerThread - everything runs in line:
     // hipStreamWaitEvent on such a handle faults in this runtime)
     const hipStream_t main = e->stream;
-    const hipStream_t side = (e->os_side && reinterpret_cast<uintptr_t>(main) > 2) ? e->os_stream : main;
+    const hipStream_t side = reinterpret_cast<uintptr_t>(main) > 2 ? e->os_stream : main;
     if (side != main) {  // the side stream starts where the engine's stream stands
         HIP_TRY(hipEventRecord(e->os_ev[0], main));
         HIP_TRY(hipStreamWaitEvent(side, e->os_ev[0], 0));
@@ -1803,8 +1747,8 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
     // the finished output comes from this engine alone: overlap-add in the inverse-transform kernel, straight into the
     // wet ring (a partition shard's partial goes through k_ola and the segment ring instead)
     // ... unless the inverse transforms can emit the delayed partial themselves: no retired epoch ringing out)
-    const bool lin_fused = lin && e->inv_to_wet && e->fuse_out && e->res_end <= e->t_front * MC_B;
-    const bool to_wet = (!lin && e->inv_to_wet) || lin_fused;
+    const bool lin_fused = lin && e->res_end <= e->t_front * MC_B;
+    const bool to_wet = !lin || lin_fused;
     st.ctx.wet_ready = to_wet;
     e->pipe[(e->pipe_head + e->pipe_count) % kPipe] = st.ctx;
     e->spec_valid = e->dspec.valid = false;
@@ -1824,7 +1768,7 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
         bool q8_ok = true;
         if (os_shape && count >= e->os_min_blocks && make_taildrop(e, st.ctx.vir, st.ctx.predelay).on) {
             q8_ok = false;
-            if (!slice && e->os_on && e->fuse_drop && e->drop_ahead && e->pm == 1 && e->epoch_b0 <= e->t_front && e->res_end <= e->t_front * MC_B) {
+            if (!slice && e->os_on && e->pm == 1 && e->epoch_b0 <= e->t_front && e->res_end <= e->t_front * MC_B) {
                 const int rc_t = plan_drop_ahead(e, st.ctx.vir, st.ctx.predelay, &os_da, &os_shift);
                 if (rc_t != MC_OK) return rc_t;
                 q8_ok = os_shift >= 0;
@@ -1854,7 +1798,7 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
         if (lo[1] <= hi[0]) hi[0] = T, lo[1] = T;  // the two runs meet
         // Q8 regime, a whole batch whose output blocks each lose ONE term of ONE source block: the forward transforms sum the cut terms
         // themselves (DropAhead; da_shift = -1 otherwise and k_drop_fft sums them all)
-        if (!slice && !lin && to_wet && !e->pipelined && e->fuse_out && e->fuse_drop && e->drop_ahead && e->pm == 1 && first == 0 && count == T &&
+        if (!slice && !lin && to_wet && !e->pipelined && e->pm == 1 && first == 0 && count == T &&
             e->res_end <= e->t_front * MC_B && e->epoch_b0 <= e->t_front && hi[0] == T && lo[0] == 0) {
             const int rc_t = plan_drop_ahead(e, st.ctx.vir, st.ctx.predelay, &da, &da_shift);
             if (rc_t != MC_OK) return rc_t;
@@ -1898,7 +1842,7 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
             std::memset(&ca, 0, sizeof(ca));
             // (every riding workgroup looks at the totals of all chunks before it: beyond 160 chunks the two launches of
             // run_back are cheaper than that quadratic chain.  A block-sliced rank has few: only the runs it transforms)
-            bool may_ride = h == 1 && !lin && !piped && to_wet && T > CORR_CHUNK && e->corr_ride;
+            bool may_ride = h == 1 && !lin && !piped && to_wet && T > CORR_CHUNK;
             auto corr_args = [&]() {
                 ca.sums = d_sums;
                 ca.ptab = d_ptab;
@@ -1954,8 +1898,8 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
                 // ... and in the Q8 regime when the cut terms come as a buffer (k_drop_fft, whole batches): they depend on the delay line and
                 // the gains only, both complete before the partition sums
                 TailDrop tdq = make_taildrop(e, st.ctx.vir, st.ctx.predelay);
-                const bool drop_buf = tdq.on && tdq.fft && !slice && !lin && e->fuse_drop;
-                bool fuse = lin_fused || (h == 1 && d_outL && d_outR && e->fuse_out && to_wet && !piped && covers &&
+                const bool drop_buf = tdq.on && tdq.fft && !slice && !lin;
+                bool fuse = lin_fused || (h == 1 && d_outL && d_outR && to_wet && !piped && covers &&
                                           e->res_end <= e->t_front * MC_B && (!tdq.on || drop_buf));
                 if (fuse && tdq.on && !lin_fused) {
                     const int rc_t = prepare_drop_fft(e, st.ctx.vir, st.ctx.predelay);
@@ -2165,7 +2109,7 @@ int wait_period(mc_engine* e, unsigned seq) {
 int wait_period_tagged(mc_engine* e, unsigned seq) {
     const auto t0 = std::chrono::steady_clock::now();
     unsigned spins = 0;
-    const int ngran = 2 * e->pm * MC_B;
+    const int ngran = 2 * MC_B;
     int first_missing = ngran - 1;  // (stores mostly arrive in order: watch the last one, then check them all)
     for (;;) {
         if ((unsigned)(__atomic_load_n(e->h_gran + first_missing, __ATOMIC_ACQUIRE) >> 32) == seq) {
@@ -2255,7 +2199,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
                 pl.nsweep++;
             }
         }
-        pl.nsum = std::max(1, pl.nsweep) * e->nchunk;
+        pl.nsum = std::max(1, pl.nsweep) * kNchunk;
     };
     auto sweep_uniform = [&](const ActiveVoice& av, int hi, uint64_t blk) {
         // one gain for all slots only when the last change is older than every slot of the sweep
@@ -2283,7 +2227,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
         for (int a = 0; a < pl.nsweep; a++) {
             ActiveVoice av = pl.sweep[a];
             av.uniform = sweep_uniform(av, pl.hi[a], blk);
-            launch_mac_stream(e, av, pl.lo[a], pl.hi[a], 1, bslot0, pl.nsum, a * e->nchunk, dst, stamps);
+            launch_mac_stream(e, av, pl.lo[a], pl.hi[a], 1, bslot0, pl.nsum, a * kNchunk, dst, stamps);
             swept = std::max(swept, pl.hi[a] - (pl.lo[a] == 2 ? 0 : pl.lo[a]));
         }
         if (e->ktiming) {
@@ -2442,7 +2386,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
     // slot carries its own gains, so it stays exact under any parameter change except a change of the sounding IR set
     // or an IR reload, which the next call checks)
     bool parked_next = false;
-    if (e->park && e->stream == e->own_stream && e->speculate && e->spin_wait && !e->pipelined && !e->ktiming && !e->half &&
+    if (e->park && e->stream == e->own_stream && e->spin_wait && !e->pipelined && !e->ktiming && !e->half &&
         params_steady(e, cc) && cc[0].predelay == e->cur_delay) {
         Staged st_next;
         int rc = stage_params(e, 1, cc, &st_next);  // (steady: advancing the cross-fade by a block changes nothing)
@@ -2472,7 +2416,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
                 S.pstride_ir = e->Pstride;
                 S.p_begin = pl_next.lo[0];
                 S.p_end = pl_next.hi[0];
-                S.chunk = round_up(std::max(1, (span + e->nchunk - 1) / e->nchunk), 64);
+                S.chunk = round_up(std::max(1, (span + kNchunk - 1) / kNchunk), 64);
                 S.fdl = e->d_fdl;
                 S.slotgain = e->d_slotgain + (size_t)av.v * e->ring;
                 S.ring = e->ring;
@@ -2482,12 +2426,12 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
                 S.ch_off = 0;
                 S.ugain = av.ugain;
                 S.inv = make_float2(1.f, 1.f);
-                S.nchunk = e->nchunk;
+                S.nchunk = kNchunk;
             }
             // the cut terms of the period after the parked one ride along (its sweep does: same launch, one more workgroup)
-            const bool carry = e->carry_drop && A.td.on && A.td.fft && e->pm == 1;
+            const bool carry = A.td.on && A.td.fft && e->pm == 1;
             S.drop_next = carry ? e->d_drop[blk2 & 1] : nullptr;
-            const dim3 grid(1 + (pl_next.nsweep == 1 ? MC_NB * e->nchunk : 0) + (carry ? 1 : 0));
+            const dim3 grid(1 + (pl_next.nsweep == 1 ? MC_NB * kNchunk : 0) + (carry ? 1 : 0));
             e->dspec.valid = false;
             if (carry) {
                 e->dspec.valid = true;
@@ -2517,7 +2461,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
             parked_next = true;
         }
     }
-    if (!parked_next && e->speculate) {
+    if (!parked_next) {
         // (not steady, or more than one voice sounding: the next period's sweep alone, in the shadow of this period)
         Staged& st = st_now;
         Plan& pl = pl_now;
@@ -2624,9 +2568,10 @@ int process_host_staged(mc_engine* e, const float* in1, const float* in2, float*
     return MC_OK;
 }
 
-// Host-buffer batch with pinned caller memory: the DMA engines read and write the caller's buffers directly.  Chunks
-// of Tdev blocks; chunk k's copy-in (H2D stream), chunk k - 1's kernels (engine stream) and chunk k - 2's copy-out
-// (D2H stream) run together, over three staging sets.  Returns when the last output byte is in outL / outR.
+// Host-buffer batch with pinned caller memory: the DMA engines read the caller's input buffers directly, and the kernels
+// that finish the output store it straight into the caller's output buffers.  Chunks of Tdev blocks; chunk k's copy-in
+// (H2D stream) runs under chunk k - 1's kernels (engine stream), over three staging sets.  Returns when the last output
+// byte is in outL / outR.
 int process_host_pinned(mc_engine* e, const float* in1, const float* in2, float* outL, float* outR, int T) {
     if (!e->Tdev) {
         // whole chunks of the second-level transform where it applies, and LONG ones: the copies set the pace, and the
@@ -2635,13 +2580,11 @@ int process_host_pinned(mc_engine* e, const float* in1, const float* in2, float*
         int tdev = (int)std::min<uint64_t>(mc_preferred_batch(e, std::min(e->Tmax, 32768)), (uint64_t)e->Tmax);
         tdev = std::max(tdev / e->pm * e->pm, e->pm);
         for (int b = 0; b < 3; b++)
-            for (int i = 0; i < 4; i++) HIP_TRY(hipMalloc(&e->d_pio[b][i], sizeof(float) * (size_t)tdev * MC_B));
+            for (int i = 0; i < 2; i++) HIP_TRY(hipMalloc(&e->d_pio[b][i], sizeof(float) * (size_t)tdev * MC_B));
         HIP_TRY(hipStreamCreateWithFlags(&e->h2d_stream, hipStreamNonBlocking));
-        HIP_TRY(hipStreamCreateWithFlags(&e->d2h_stream, hipStreamNonBlocking));
         for (int b = 0; b < 3; b++) {
             HIP_TRY(hipEventCreateWithFlags(&e->ev_h2d[b], hipEventDisableTiming));
             HIP_TRY(hipEventCreateWithFlags(&e->ev_comp[b], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&e->ev_d2h[b], hipEventDisableTiming));
         }
         e->Tdev = tdev;
     }
@@ -2656,37 +2599,22 @@ int process_host_pinned(mc_engine* e, const float* in1, const float* in2, float*
         HIP_TRY(hipMemcpyAsync(d[1], in2 + off, bytes, hipMemcpyHostToDevice, e->h2d_stream));
         HIP_TRY(hipEventRecord(e->ev_h2d[b], e->h2d_stream));
         HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_h2d[b], 0));
-        if (e->host_out_direct) {
-            // the kernels that finish the output store it straight into the caller's pinned buffers (posted writes over the
-            // link): no copy-out, no second copy direction to take turns with the copy-in
-            float *hl = nullptr, *hr = nullptr;
-            HIP_TRY(hipHostGetDevicePointer((void**)&hl, outL + off, 0));
-            HIP_TRY(hipHostGetDevicePointer((void**)&hr, outR + off, 0));
-            // (the output goes over the link as posted writes: the partitioned passes store it in whole 1 KB rows, the overlap-save
-            // form's output pass in 64-byte pieces - 119 000 against 109 000 x real time: the link prefers the former)
-            e->os_hold = true;
-            int rc = run_front(e, d[0], d[1], n, nullptr, 0, n, hl, hr);
-            e->os_hold = false;
-            if (rc) return rc;
-            rc = run_back(e, d[0], d[1], nullptr, hl, hr, n);
-            if (!rc) rc = fence_post(e);
-            if (rc) return rc;
-            HIP_TRY(hipEventRecord(e->ev_comp[b], e->stream));
-            continue;
-        }
-        if (k >= 3) HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_d2h[b], 0));
-        int rc = run_front(e, d[0], d[1], n, nullptr, 0, n, d[2], d[3]);
+        // the kernels that finish the output store it straight into the caller's pinned buffers (posted writes over the
+        // link): no copy-out, no second copy direction to take turns with the copy-in
+        float *hl = nullptr, *hr = nullptr;
+        HIP_TRY(hipHostGetDevicePointer((void**)&hl, outL + off, 0));
+        HIP_TRY(hipHostGetDevicePointer((void**)&hr, outR + off, 0));
+        // (the output goes over the link as posted writes: the partitioned passes store it in whole 1 KB rows, the overlap-save
+        // form's output pass in 64-byte pieces - 119 000 against 109 000 x real time: the link prefers the former)
+        e->os_hold = true;
+        int rc = run_front(e, d[0], d[1], n, nullptr, 0, n, hl, hr);
+        e->os_hold = false;
         if (rc) return rc;
-        rc = run_back(e, d[0], d[1], nullptr, d[2], d[3], n);
+        rc = run_back(e, d[0], d[1], nullptr, hl, hr, n);
         if (!rc) rc = fence_post(e);
         if (rc) return rc;
         HIP_TRY(hipEventRecord(e->ev_comp[b], e->stream));
-        HIP_TRY(hipStreamWaitEvent(e->d2h_stream, e->ev_comp[b], 0));
-        HIP_TRY(hipMemcpyAsync(outL + off, d[2], bytes, hipMemcpyDeviceToHost, e->d2h_stream));
-        HIP_TRY(hipMemcpyAsync(outR + off, d[3], bytes, hipMemcpyDeviceToHost, e->d2h_stream));
-        HIP_TRY(hipEventRecord(e->ev_d2h[b], e->d2h_stream));
     }
-    HIP_TRY(hipStreamSynchronize(e->d2h_stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return MC_OK;
 }
@@ -2736,7 +2664,6 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
     if (e->pipe_count) return fail(MC_ERR_STATE, "a sharded batch is still pending");
     if (e->sliced) return fail(MC_ERR_STATE, "single-period call on a block-sliced engine (mc_reset first)");
     const int pm = e->pm;
-    const bool tio_p = e->tio && e->tio_long;  // tagged I/O pays for 256-frame periods only (see mc_engine::tio_long)
     const size_t bytes = (size_t)pm * MC_B * sizeof(float), cap = (size_t)e->Thost * MC_B;
     const float *pin1 = e->bar_io ? e->d_bar + 16 : e->hd_io + 0 * cap, *pin2 = e->bar_io ? e->d_bar + 16 + 4 * MC_B : e->hd_io + 1 * cap;
     auto copy_period_in = [&]() {  // the period where a tail launched now reads it
@@ -2777,7 +2704,7 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
                 pl.nsweep++;
             }
         }
-        pl.nsum = std::max(1, pl.nsweep) * e->nchunk;
+        pl.nsum = std::max(1, pl.nsweep) * kNchunk;
     };
     // partitions >= pm of the pm blocks starting at `blk` pair only with blocks before blk
     auto launch_mac = [&](const PPlan& pl, uint64_t blk) -> int {
@@ -2797,7 +2724,7 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
         for (int a = 0; a < pl.nsweep; a++) {
             ActiveVoice av = pl.sweep[a];
             av.uniform = e->gain_change_block[av.v] + (uint64_t)pl.hi[a] <= blk && e->gain_change_block[av.v] < blk;
-            launch_mac_stream(e, av, pm, pl.hi[a], pm, bslot0, pl.nsum, a * e->nchunk, nullptr, stamps);
+            launch_mac_stream(e, av, pm, pl.hi[a], pm, bslot0, pl.nsum, a * kNchunk, nullptr, stamps);
             swept = std::max(swept, pl.hi[a]);
         }
         if (timed) {
@@ -2838,7 +2765,7 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
         }
         const TailDrop tdp = make_taildrop(e, st.ctx.vir, st.ctx.predelay);
         // Q8 regime: a parked tail sums its own cut terms while it waits for the period; one launched on arrival gets them from a launch ahead of it
-        const bool self_drop = parked && tdp.on && tdp.fft && e->carry_drop;
+        const bool self_drop = parked && tdp.on && tdp.fft;
         const float* drop = self_drop ? e->d_drop[(blk / (uint64_t)e->pm) & 1] : launch_drop_period(e, tdp, blk, st.ctx.predelay);
         if (self_drop) e->n_drop_carried++;
 #define MC_LAUNCH_TAILP(PM)                                                                                                  \
@@ -2849,9 +2776,7 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
                        st.ctx.vs, 1.0 / (double)e->cfg.n_ref, (int)e->cfg.compat, (int64_t)blk, (int64_t)st.ctx.predelay,     \
                        (int64_t)e->cfg.n_ref, e->hd_io + 2 * cap, e->hd_io + 3 * cap, e->d_tw,                                \
                        tdp, e->d_fdl16, e->hd_flag, seq, make_retired(e), bell,     \
-                       e->hd_exited, e->park_ticks, drop,                            \
-                       tio_p ? reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(e->d_bar) + 16384) : nullptr, \
-                       tio_p ? e->hd_gran : nullptr)
+                       e->hd_exited, e->park_ticks, drop, nullptr, nullptr)
         if (pm == 2) {
             MC_LAUNCH_TAILP(2);
         } else {
@@ -2874,22 +2799,8 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
                      same_cc(cc[1], e->pre.cc[1]) && cc[0].predelay == e->cur_delay;
     if (hit) {
         my_seq = e->pre.seq;
-        if (tio_p) {  // tagged input (see process_one): granules [2][pm * 256] {sample, sequence number}, no doorbell
-            volatile unsigned long long* g = reinterpret_cast<volatile unsigned long long*>(reinterpret_cast<char*>(e->d_bar) + 16384);
-            const unsigned long long tag = (unsigned long long)my_seq << 32;
-            const int n = pm * MC_B;
-            for (int i = 0; i < n; i++) {
-                uint32_t a, b;
-                std::memcpy(&a, in1 + i, 4);
-                std::memcpy(&b, in2 + i, 4);
-                g[i] = tag | a;
-                g[n + i] = tag | b;
-            }
-            _mm_sfence();
-        } else {
-            copy_period_in();
-            ring_bell(e, my_seq, 0);
-        }
+        copy_period_in();
+        ring_bell(e, my_seq, 0);
         e->pre.valid = false;
         e->n_park_hit++;
         st = e->pre.st;
@@ -2922,12 +2833,12 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
 
     // ---- the next period: its sweep in the shadow of this one (a speculation the next call checks), and - when nothing
     // is moving - its tail behind the sweep, parked
-    if (e->speculate && pl.nsweep) {
+    if (pl.nsweep) {
         int rc = launch_mac(pl, e->t_front);
         if (rc) return rc;
         remember_sweep(pl, st, e->t_front);
     }
-    if (e->park && e->stream == e->own_stream && e->speculate && e->spin_wait && !e->pipelined && !e->ktiming && !e->half &&
+    if (e->park && e->stream == e->own_stream && e->spin_wait && !e->pipelined && !e->ktiming && !e->half &&
         params_steady(e, cc) && cc[0].predelay == e->cur_delay) {
         Staged st_next;
         int rc = stage_params(e, pm, cc, &st_next);  // (steady: advancing the cross-fade by a call changes nothing)
@@ -2955,7 +2866,7 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
         }
     }
     for (;;) {
-        int rc = tio_p ? wait_period_tagged(e, my_seq) : wait_period(e, my_seq);
+        int rc = wait_period(e, my_seq);
         if (rc == MC_OK) break;
         if (rc != 1) return rc;
         copy_period_in();  // (a tail launched now reads the plain copy of the period)
@@ -2974,17 +2885,8 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
         if (prep_rc) return prep_rc;
         HIP_TRY(hipGetLastError());
     }
-    if (tio_p) {
-        const int n = pm * MC_B;
-        for (int i = 0; i < n; i++) {
-            const uint32_t a = (uint32_t)e->h_gran[i], b = (uint32_t)e->h_gran[n + i];
-            std::memcpy(outL + i, &a, 4);
-            std::memcpy(outR + i, &b, 4);
-        }
-    } else {
-        std::memcpy(outL, e->h_io + 2 * cap, bytes);
-        std::memcpy(outR, e->h_io + 3 * cap, bytes);
-    }
+    std::memcpy(outL, e->h_io + 2 * cap, bytes);
+    std::memcpy(outR, e->h_io + 3 * cap, bytes);
     return MC_OK;
 }
 
@@ -3056,8 +2958,6 @@ int mc_create(const mc_config* cfg, mc_engine** out) {
     // (pipelined: the forward stage of batch k + 1 writes histories while the post stage of batch k still reads them)
     e->rc = (int)next_pow2(cfg->n_ref / MC_B + (uint64_t)e->Tmax * (e->pipelined ? 2 : 1) + 64);
     e->stream_threshold = cfg->stream_threshold ? (int)cfg->stream_threshold : 48;  // measured crossover (scripts/sweep_T.sh)
-    if (const char* nc = LAB_ENV("MCCONV_NCHUNK")) e->nchunk = std::max(1, std::min(64, std::atoi(nc)));
-    if (const char* nt = LAB_ENV("MCCONV_STREAM_NT")) e->stream_nt = std::atoi(nt) == 512 ? 512 : 256;
     {
         const uint32_t period = cfg->period ? cfg->period : MC_BLOCK;
         if (period != 256 && period != 512 && period != 1024) {
@@ -3137,7 +3037,7 @@ int mc_create(const mc_config* cfg, mc_engine** out) {
     // >= 8 planes of 256 blocks; the fast-FIR form writes three half-rate sequences (1.5 x the blocks, + a tile each)
     ENG_TRY(hipMalloc(&e->d_Y, sizeof(float4) * (size_t)MC_NB * y_capacity(e)));
     if (!e->half) ENG_TRY(hipMalloc(&e->d_Yc, sizeof(float4) * (size_t)MC_NB * e->Tcap));
-    ENG_TRY(hipMalloc(&e->d_tail, sizeof(float4) * (size_t)8 * MC_NB * e->nchunk * MC_MAXV));
+    ENG_TRY(hipMalloc(&e->d_tail, sizeof(float4) * (size_t)8 * MC_NB * kNchunk * MC_MAXV));
     e->d_Ybuf[0] = e->d_Y;
     e->d_Ycbuf[0] = e->d_Yc;
     e->d_tailbuf[0] = e->d_tail;
@@ -3151,12 +3051,12 @@ int mc_create(const mc_config* cfg, mc_engine** out) {
         }
         ENG_TRY(hipMalloc(&e->d_Ybuf[1], sizeof(float4) * (size_t)MC_NB * y_capacity(e)));
         ENG_TRY(hipMalloc(&e->d_Ycbuf[1], sizeof(float4) * (size_t)MC_NB * e->Tcap));
-        ENG_TRY(hipMalloc(&e->d_tailbuf[1], sizeof(float4) * (size_t)8 * MC_NB * e->nchunk * MC_MAXV));
+        ENG_TRY(hipMalloc(&e->d_tailbuf[1], sizeof(float4) * (size_t)8 * MC_NB * kNchunk * MC_MAXV));
     }
-    ENG_TRY(hipMalloc(&e->d_part, sizeof(float4) * (size_t)e->Tstream * MC_NB * e->nchunk * MC_MAXV));
+    ENG_TRY(hipMalloc(&e->d_part, sizeof(float4) * (size_t)e->Tstream * MC_NB * kNchunk * MC_MAXV));
     e->d_partbuf[0] = e->d_part;
     if (cfg->pipeline != 0 && cfg->precision == 0)
-        ENG_TRY(hipMalloc(&e->d_partbuf[1], sizeof(float4) * (size_t)e->Tstream * MC_NB * e->nchunk * MC_MAXV));
+        ENG_TRY(hipMalloc(&e->d_partbuf[1], sizeof(float4) * (size_t)e->Tstream * MC_NB * kNchunk * MC_MAXV));
     ENG_TRY(hipMalloc(&e->d_sums, sizeof(float4) * (size_t)e->Tmax * kPipe));
     ENG_TRY(hipMalloc(&e->d_seg, sizeof(float) * (size_t)e->sr * 2 * FFT_N));
     ENG_TRY(hipMalloc(&e->d_wet, sizeof(float) * 2 * (size_t)e->wr));
@@ -3179,7 +3079,7 @@ int mc_create(const mc_config* cfg, mc_engine** out) {
     ENG_TRY(hipHostGetDevicePointer((void**)&e->hd_io, e->h_io, 0));
     ENG_TRY(hipMalloc(&e->d_tailform, 2 * sizeof(unsigned)));
     ENG_TRY(hipMemset(e->d_tailform, 0, 2 * sizeof(unsigned)));
-    if (const char* f = LAB_ENV("MCCONV_TAIL_FORM")) e->tail_form = !std::strcmp(f, "td") ? 1 : !std::strcmp(f, "fd") ? 2 : 0;
+    if (const char* f = std::getenv("MCCONV_TAIL_FORM")) e->tail_form = !std::strcmp(f, "td") ? 1 : !std::strcmp(f, "fd") ? 2 : 0;
     ENG_TRY(hipHostMalloc(&e->h_flag, 256, hipHostMallocMapped));  // completion word, doorbell, "gave up" word: a line each
     ENG_TRY(hipHostGetDevicePointer((void**)&e->hd_flag, e->h_flag, 0));
     std::memset(e->h_flag, 0, 256);
@@ -3188,7 +3088,6 @@ int mc_create(const mc_config* cfg, mc_engine** out) {
     e->h_exited = e->h_flag + 32;
     e->hd_exited = e->hd_flag + 32;
     if (std::getenv("MCCONV_NO_PARK")) e->park = false;
-    if (const char* ho = LAB_ENV("MCCONV_HOST_OUT_DIRECT")) e->host_out_direct = std::atoi(ho) != 0;
     {
         int large_bar = 0;
         const char* bi = std::getenv("MCCONV_BAR_IO");
@@ -3205,54 +3104,24 @@ int mc_create(const mc_config* cfg, mc_engine** out) {
     ENG_TRY(hipMalloc(&e->d_done_ctr, sizeof(unsigned)));
     ENG_TRY(hipMemset(e->d_done_ctr, 0, sizeof(unsigned)));
     if (std::getenv("MCCONV_NO_SPIN")) e->spin_wait = false;
-    if (e->bar_io && e->spin_wait && !(LAB_ENV("MCCONV_TAGGED_IO") && std::atoi(LAB_ENV("MCCONV_TAGGED_IO")) == 0)) {
-        ENG_TRY(hipHostMalloc(&e->h_gran, sizeof(unsigned long long) * 2 * 4 * MC_B, hipHostMallocMapped));  // (room for a 1024-frame period)
+    if (e->bar_io && e->spin_wait) {
+        ENG_TRY(hipHostMalloc(&e->h_gran, sizeof(unsigned long long) * 2 * MC_B, hipHostMallocMapped));
         ENG_TRY(hipHostGetDevicePointer((void**)&e->hd_gran, e->h_gran, 0));
-        std::memset(e->h_gran, 0, sizeof(unsigned long long) * 2 * 4 * MC_B);
+        std::memset(e->h_gran, 0, sizeof(unsigned long long) * 2 * MC_B);
         e->tio = true;
-        e->tio_long = LAB_ENV("MCCONV_TAGGED_IO") && std::atoi(LAB_ENV("MCCONV_TAGGED_IO")) == 2;
     }
     for (int i = 0; i < kStageBufs; i++) {
         ENG_TRY(hipHostMalloc(&e->h_ptab[i], sizeof(BlockParams) * (size_t)e->Tmax, hipHostMallocDefault));
         ENG_TRY(hipEventCreateWithFlags(&e->ptab_ev[i], hipEventDisableTiming));
     }
     ENG_TRY(hipEventCreateWithFlags(&e->ev_tail, hipEventDisableTiming));
-    for (int i = 0; i < 2; i++) ENG_TRY(hipMalloc(&e->d_part_jack[i], sizeof(float4) * (size_t)MC_NB * e->nchunk * MC_MAXV));
+    for (int i = 0; i < 2; i++) ENG_TRY(hipMalloc(&e->d_part_jack[i], sizeof(float4) * (size_t)MC_NB * kNchunk * MC_MAXV));
     for (int i = 0; i < 2; i++) ENG_TRY(hipMalloc(&e->d_drop[i], sizeof(float) * 2 * 4 * MC_B));
-    if (LAB_ENV("MCCONV_NO_SPECULATE")) e->speculate = false;
     if (const char* f2 = std::getenv("MCCONV_FFT2")) e->fft2 = std::atoi(f2) != 0;
     if (const char* g2 = std::getenv("MCCONV_FFT2_FUSED")) e->fft2_fused = std::atoi(g2) != 0;
-    {
-        int cus = 0;
-        if (const char* gw = LAB_ENV("MCCONV_G2_WIDE")) e->g2_wide = std::atoi(gw) != 0;
-        // k_g2_mac: one workgroup per (bin, chunk) item - the dispatcher keeps two resident per CU and hands a CU its next
-        // one the moment a slot frees (measured against 512 persistent workgroups striding over 1280 items: 98 vs 108 us).
-        // The one-workgroup-per-CU form is persistent (one per CU, look-ahead into its next item).
-        e->g2_grid = 1 << 30;
-        if (e->g2_wide) e->g2_grid = (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) == hipSuccess && cus >= 8) ? (cus & ~7) : 256;
-    }
-    // (any grid >= 1 is correct: a workgroup strides over the items; multiples of 8 keep a bin's chunks on one XCD)
-    if (const char* gg = LAB_ENV("MCCONV_G2_GRID")) e->g2_grid = std::max(1, std::atoi(gg));
-    if (const char* gd = LAB_ENV("MCCONV_G2_DUO")) e->g2_duo = std::atoi(gd) != 0;
-    if (const char* gd = LAB_ENV("MCCONV_G2_DUO_MINCH")) e->g2_duo_minch = std::max(1, std::atoi(gd));
-    {
-        int cus = 0;
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, e->device) == hipSuccess && cus >= 8) e->g2_duo_grid = std::min(cus & ~7, 256);
-    }
-    if (const char* gd = LAB_ENV("MCCONV_G2_DUO_GRID")) e->g2_duo_grid = std::max(8, std::atoi(gd));
-    if (LAB_ENV("MCCONV_DEBUG_ADDR")) e->debug_addr = true;
-    if (const char* cr = LAB_ENV("MCCONV_CORR_RIDE")) e->corr_ride = std::atoi(cr) != 0;
-    if (const char* tm = LAB_ENV("MCCONV_FFT2_WORK")) e->fft2_work = std::max<int64_t>(1, std::atoll(tm));
-    if (const char* gm = LAB_ENV("MCCONV_G2_PMIN")) e->g2_pmin = std::max(16, std::atoi(gm));
-    if (const char* gp = LAB_ENV("MCCONV_G2_PMAX")) e->g2_pmax = std::max(256, std::min(G2_N / 2 + 2048, std::atoi(gp)));
-    if (const char* fo = LAB_ENV("MCCONV_FUSE_OUT")) e->fuse_out = std::atoi(fo) != 0;
-    if (const char* fo = LAB_ENV("MCCONV_FUSE_DROP")) e->fuse_drop = std::atoi(fo) != 0;
-    if (const char* fo = LAB_ENV("MCCONV_DROP_AHEAD")) e->drop_ahead = std::atoi(fo) != 0;
-    if (const char* fo = LAB_ENV("MCCONV_CARRY_DROP")) e->carry_drop = std::atoi(fo) != 0;
-    if (const char* iw = LAB_ENV("MCCONV_INV_WET")) e->inv_to_wet = std::atoi(iw) != 0;
+    if (const char* tm = std::getenv("MCCONV_FFT2_WORK")) e->fft2_work = std::max<int64_t>(1, std::atoll(tm));
     if (const char* os = std::getenv("MCCONV_OS")) e->os_on = std::atoi(os) != 0;
-    if (const char* os = LAB_ENV("MCCONV_OS_SIDE")) e->os_side = std::atoi(os) != 0;
-    if (const char* os = LAB_ENV("MCCONV_OS_MIN")) e->os_min_blocks = std::max(1, std::atoi(os));
+    if (const char* os = std::getenv("MCCONV_OS_MIN")) e->os_min_blocks = std::max(1, std::atoi(os));
     if (const char* fl = std::getenv("MCCONV_FFA_LEVELS")) e->ffa_levels = std::max(0, std::min(3, std::atoi(fl)));
     {
         std::vector<float2> tw;
@@ -3344,13 +3213,11 @@ void mc_destroy(mc_engine* e) {
     (void)hipFree(e->d_tw);
     for (int i = 0; i < 4; i++) (void)hipFree(e->d_io[i]);
     for (int b = 0; b < 3; b++) {
-        for (int i = 0; i < 4; i++) (void)hipFree(e->d_pio[b][i]);
+        for (int i = 0; i < 2; i++) (void)hipFree(e->d_pio[b][i]);
         if (e->ev_h2d[b]) (void)hipEventDestroy(e->ev_h2d[b]);
         if (e->ev_comp[b]) (void)hipEventDestroy(e->ev_comp[b]);
-        if (e->ev_d2h[b]) (void)hipEventDestroy(e->ev_d2h[b]);
     }
     if (e->h2d_stream) (void)hipStreamDestroy(e->h2d_stream);
-    if (e->d2h_stream) (void)hipStreamDestroy(e->d2h_stream);
     if (e->d_bar) (void)hipFree(e->d_bar);
     if (e->h_gran) (void)hipHostFree(e->h_gran);
     if (e->h_io) (void)hipHostFree(e->h_io);
@@ -3757,8 +3624,8 @@ uint64_t mc_preferred_batch(const mc_engine* e, uint64_t at_most) {
         const uint64_t hopb = (uint64_t)(OS_N / MC_B - pmax);
         if (at_most >= hopb && at_most >= (uint64_t)e->os_min_blocks) return at_most / hopb * hopb;
     }
-    if (e->fft2 && !e->half && (shard ? pmax >= 16 : pmax >= e->g2_pmin)) {
-        if (e->fft2_fused && pmax <= e->g2_pmax) chunk = (uint64_t)(G2_N - pmax + 1);
+    if (e->fft2 && !e->half && pmax >= 16) {
+        if (e->fft2_fused && pmax <= kG2Pmax) chunk = (uint64_t)(G2_N - pmax + 1);
         else if (pmax <= F2_N / 2) chunk = (uint64_t)(F2_N - pmax + 1);
     }
     if (!chunk || at_most < chunk) return at_most >= 8 ? (at_most & ~(uint64_t)7) : at_most;
@@ -3799,16 +3666,6 @@ int mc_debug_read(mc_engine* e, int which, uint64_t idx, void* dst, uint64_t off
     if (which == 10) {  // batches by the form their partition sums took {fused, split second-level transform, resident MAC}: no stream access
         if (off + bytes > sizeof(e->n_mac_form)) return fail(MC_ERR_ARG, "read beyond the counters");
         std::memcpy(dst, reinterpret_cast<const char*>(e->n_mac_form) + off, bytes);
-        return MC_OK;
-    }
-    if (which == 15) {  // 1 = built with -DMCCONV_LAB (the measurement switches and the alternative kernels exist): no stream access
-#ifdef MCCONV_LAB
-        const uint64_t lab = 1;
-#else
-        const uint64_t lab = 0;
-#endif
-        if (off + bytes > sizeof(lab)) return fail(MC_ERR_ARG, "read beyond the word");
-        std::memcpy(dst, reinterpret_cast<const char*>(&lab) + off, bytes);
         return MC_OK;
     }
     if (which == 11) {  // overlap-save form: {batches that took it, spectra builds}: no stream access

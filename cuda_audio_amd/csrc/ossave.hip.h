@@ -52,9 +52,6 @@ struct OsGeo {
     int seg0;      // first segment of this launch
 };
 
-#ifndef OS_ABL
-#define OS_ABL 0  // timing-only ablations (wrong results), bit flags: 1 no inter-pass twiddles, 2 no Q1/Q2 window sums in the output pass, 4 no partial block sums, 8 no column transforms
-#endif
 #ifndef OS_XG
 #define OS_XG 16  // consecutive tiles of a segment that run on ONE XCD back to back (their 64-byte pieces of a line meet in that L2)
 #endif
@@ -94,10 +91,6 @@ __device__ __forceinline__ void os_twiddles(int n2, int lane, v2f (&w)[8]) {
     w[5] = vx_mul(w[4], s1);
     w[6] = vx_mul(w[4], s2);
     w[7] = vx_mul(w[4], s3);
-#if OS_ABL & 1
-#pragma unroll
-    for (int j = 0; j < 8; j++) w[j] = v2f{1.f, 0.f};
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -146,7 +139,7 @@ __global__ __launch_bounds__(OS_THREADS) void k_os_cols(const float* __restrict_
         z[1] = make_float2(a.y, b.y);
         z[2] = make_float2(a.z, b.z);
         z[3] = make_float2(a.w, b.w);
-        if (part && !(OS_ABL & 4)) {  // (kernel-uniform) frames 4 q + k of a block-aligned run of 16: parity of the frame = parity of k
+        if (part) {  // (kernel-uniform) frames 4 q + k of a block-aligned run of 16: parity of the frame = parity of k
             float s1 = (a.x + a.y) + (a.z + a.w), s2 = (b.x + b.y) + (b.z + b.w);
             float d1 = (a.x - a.y) + (a.z - a.w), d2 = (b.x - b.y) + (b.z - b.w);
             s1 += __shfl_xor(s1, 1), s2 += __shfl_xor(s2, 1), d1 += __shfl_xor(d1, 1), d2 += __shfl_xor(d2, 1);
@@ -161,12 +154,7 @@ __global__ __launch_bounds__(OS_THREADS) void k_os_cols(const float* __restrict_
     for (int r = 0; r < 8; r++) v[r] = s_mem[(lane + 64 * r) * OS_ROWT + wave];
     __syncthreads();  // every column is in registers: the staging tile becomes the transform buffers
     float2* lds = s_mem + wave * OS_WSTR;
-#if OS_ABL & 8
-#pragma unroll
-    for (int r = 0; r < 8; r++) lds[lane + 64 * r] = v[r];
-#else
     fft512_wave<-1, false>(v, lds, s_tw, lane);
-#endif
     v2f z[8];
     {
         v2f w[8];
@@ -238,14 +226,6 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_os_rows(float4* __restrict__
     // items 8 apart in launch order share an XCD: an item's segments follow each other there (its spectra are read into that L2 once)
     const int xq = (int)blockIdx.x >> 3;
     const int item = (xq / nseg) * 8 + ((int)blockIdx.x & 7), seg = xq % nseg;
-#ifndef OS_PRIO
-#define OS_PRIO 0
-#endif
-    if (OS_PRIO && nseg * OS_ITEMS >= 2048) {  // issue priority for one of a CU's two workgroups (k_g2_mac, G2_PRIO)
-        unsigned hwid;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
-        if ((hwid & 0xfu) >= 2u) __builtin_amdgcn_s_setprio(OS_PRIO);
-    }
     g2_tables(t_lo, t_hi);
     __syncthreads();
     constexpr int ROWS = G2_N / G2B_THREADS;
@@ -391,18 +371,9 @@ __global__ __launch_bounds__(OS_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
         }
     }
     __syncthreads();
-#if OS_ABL & 8
-#pragma unroll
-    for (int r = 0; r < 8; r++) s_mem[wave * OS_WSTR + lane + 64 * r] = v[r];
-#else
     fft512_wave<+1, false>(v, s_mem + wave * OS_WSTR, s_tw, lane);
-#endif
     __syncthreads();
-#ifdef OS_OUT_UNROLL
-#pragma unroll
-#else
 #pragma unroll 1
-#endif
     for (int it = 0; it < 2; it++) {
         const int e = tid + OS_THREADS * it, n1 = e >> 2, q = e & 3;
         const int64_t n = (int64_t)OS_N2 * n1 + n2_0 + 4 * q;
@@ -425,11 +396,7 @@ __global__ __launch_bounds__(OS_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
         double win[4];
         if (whole) {
             const float4 x1q = *reinterpret_cast<const float4*>(oa.in1 + o0), x2q = *reinterpret_cast<const float4*>(oa.in2 + o0);
-#if OS_ABL & 2
-            win[0] = win[1] = win[2] = win[3] = 0.0;
-#else
             out_window(oa, u0, win);
-#endif
             const BlockParams& bp = oa.ptab[(o0 >> 8) * oa.pstride];
             float4 d01 = make_float4(0.f, 0.f, 0.f, 0.f), d23 = d01;  // the Q8 cut terms of the four frames {L, R}, subtracted before the clamp (as k_inv_wet)
             if (oa.drop) {

@@ -240,8 +240,8 @@ uint64_t mc_preferred_batch(const mc_engine *e, uint64_t at_most);
  * their cut terms took {k_drop_fft, forward transforms, time-domain tiles} and JACK periods whose cut terms came with the
  * launch before theirs (4 x uint64), 10 = batch launches by the form
  * of their partition sums {fused, split second-level transform, resident MAC} (3 x uint64), 11 = overlap-save form {batches that
- * took it, builds of its spectra} (2 x uint64), 12 / 13 / 14 = its row buffer and spectra (float4), 15 = 1 when the library is the lab
- * build (-DMCCONV_LAB: measurement switches and alternative kernels), 16 = 256-frame JACK tails by the form partition 0 took
+ * took it, builds of its spectra} (2 x uint64), 12 / 13 / 14 = its row buffer and spectra (float4), 15 = retired (MC_ERR_ARG;
+ * it reported a measurement build of the library, which no longer exists), 16 = 256-frame JACK tails by the form partition 0 took
  * {frequency domain, time domain}, counted by the kernel (2 x uint32; read behind the stream), 17 = the stored time-domain
  * taps of IR `idx` (float2 [taps], as mc_ir_info counts them; MC_ERR_STATE in the single-transform form, which keeps none).  dims[0..3] receive
  * {pstride, ring, max_batch, wet ring length} when non-null. */

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B on the headline bench: each argument is "default", a library path (MCCONV_LIB) or VAR=value settings
-# (comma-separated); three rounds, alternating.   gpu_ab.sh [--blocks N] default MCCONV_G2_WIDE=1 ...
+# (comma-separated); three rounds, alternating.   gpu_ab.sh [--blocks N] default MCCONV_OS=0 ...
 cd ${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p gpurun_out
 EXTRA=""

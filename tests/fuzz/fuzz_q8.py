@@ -8,8 +8,8 @@ forward transforms sum them where the shape allows) and single periods.  usage: 
 carried by the launch before) under parameter changes.
 `long`: `general` with batches of up to 1500 calls and the switch-over to the second-level transform lowered (MCCONV_FFT2_WORK=1, set here): the
 kernels of the headline (k_g2_mac; k_f2_* where gains differ per block and the IRs have >= 256 partitions: every fifth run is at n_ref = 131072).
-`os` (round 4): `long` on the LAB build (MCCONV_LIB=build_ab/lib_lab.so) with the overlap-save form taken from 48 blocks on (MCCONV_OS_MIN=48, set here; the
-product takes it from 12288): every settled batch of a random stream runs as one 512 x 8192-frame segment - any IR set, predelay, period size, the Q8
+`os` (round 4): `long` with the overlap-save form taken from 48 blocks on (MCCONV_OS_MIN=48, set here; the library takes it from 12288
+by default): every settled batch of a random stream runs as one 512 x 8192-frame segment - any IR set, predelay, period size, the Q8
 regime's one-term shape through the forward transforms - between batches and periods of every other form."""
 import ctypes as C
 import os
@@ -113,8 +113,6 @@ for seed in range(first, first + runs):
         st = c.drop_stats()
         st.update(c.mac_stats())
         st.update(c.os_stats())  # (overlap-save form: batches that took it, builds of its spectra)
-        if os_mode and not c.lab_build():
-            raise SystemExit("the os mode needs the lab build: MCCONV_LIB=build_ab/lib_lab.so")
     except Exception:  # (the single-transform form, MCCONV_FORM=single, keeps no such counters)
         st = {}
     c.close()

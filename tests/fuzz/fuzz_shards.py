@@ -4,7 +4,7 @@ Every run picks a layout - partition shards finished on rank 0 (`reduce`), parti
 blocks (`reduce_scatter`), or output blocks sliced across ranks with no exchange (`slices`) - a world of 2..4 ranks, IR lengths up
 to n_ref - 1024, a period of 256 / 512 frames, batches of random length, and controller traffic between batches (select, predelay,
 wet, speed, pans, level).  usage: fuzz_shards.py [first_seed] [runs] [os]
-`os` (round 4, lab build: MCCONV_LIB=build_ab/lib_lab.so): the overlap-save form from one block on (MCCONV_OS_MIN=1), so that the block slices of
+`os` (round 4): the overlap-save form from one block on (MCCONV_OS_MIN=1, set here), so that the block slices of
 every settled batch run as a segment that reads its history from the batch in front of the slice."""
 import ctypes as C
 import os

@@ -14,12 +14,6 @@ from helpers import BASE, RMS_TOL, apply_params, rms
 pytestmark = pytest.mark.gpu
 
 
-def _os_form_possible():
-    """The overlap-save form needs the output finished by the transform kernels: the lab build's MCCONV_INV_WET=0 / MCCONV_FUSE_OUT=0
-    (the suite is also run under those) send it elsewhere, and with the cut terms' alternatives switched off the Q8 shape stays out."""
-    return not any(os.environ.get(k) == "0" for k in ("MCCONV_INV_WET", "MCCONV_FUSE_OUT"))
-
-
 def _conv(**kw):
     from cuda_audio_amd.engine import Convolution
 
@@ -345,22 +339,16 @@ def test_jack_path_pan_change_is_exact(oracle_mod, gpu_lib):
 
 def test_speculative_sweep_is_invisible(gpu_lib):
     """The next period's partition sweep is launched speculatively after each period; an IR switch, a batch call
-    or a reset in between must invalidate it.  Same events with speculation disabled give identical samples."""
-    import os
-
+    or a reset in between must invalidate it.  The same events played twice give identical samples (both runs
+    speculate: the library has no switch that turns speculation off)."""
     from cuda_audio_amd.synth import make_input, make_ir
 
     nb = 50
     x = make_input(nb * 256)
     irs = [make_ir(5000, seed=11, norm=0.05), make_ir(4000, seed=22, norm=0.05)]
 
-    def run(no_spec):
-        if no_spec:
-            os.environ["MCCONV_NO_SPECULATE"] = "1"
-        else:
-            os.environ.pop("MCCONV_NO_SPECULATE", None)
+    def run():
         c = _conv(fftSize=8192, max_batch=8)
-        os.environ.pop("MCCONV_NO_SPECULATE", None)
         for i, ir in enumerate(irs):
             c.prepare(i, ir)
         out = np.zeros((2, nb * 256), np.float32)
@@ -381,7 +369,7 @@ def test_speculative_sweep_is_invisible(gpu_lib):
         c.close()
         return out
 
-    a, bb = run(False), run(True)
+    a, bb = run(), run()
     assert np.abs(a).max() > 0.01
     assert rms(a - bb) < 1e-7
 
@@ -538,7 +526,7 @@ def test_q8_parked_periods_carry_the_next_periods_cut_terms(oracle_mod, gpu_lib)
     c.close()
     err = rms(got - want)
     assert err <= RMS_TOL, f"rms {err:.3e} (signal {rms(want):.3e}) {stats} {parks}"
-    if not any(os.environ.get(k) for k in ("MCCONV_NO_PARK", "MCCONV_NO_SPECULATE", "MCCONV_NO_SPIN", "MCCONV_TD_FFT", "MCCONV_CARRY_DROP")):
+    if not any(os.environ.get(k) for k in ("MCCONV_NO_PARK", "MCCONV_NO_SPIN", "MCCONV_TD_FFT")):
         assert parks["used"] > 40 and stats["carried_periods"] > 40, (stats, parks)
 
 
@@ -578,7 +566,7 @@ def test_q8_carried_cut_terms_do_not_survive_a_park_timeout(oracle_mod, gpu_lib,
     per_block = np.sqrt(((got - want) ** 2).reshape(2, nb, 256).mean(axis=(0, 2)))
     assert per_block.max() <= 2 * RMS_TOL, f"worst block {int(per_block.argmax())}: {per_block.max():.3e} {stats} {parks}"
     assert rms(got - want) <= RMS_TOL
-    if not any(os.environ.get(k) for k in ("MCCONV_NO_PARK", "MCCONV_NO_SPECULATE", "MCCONV_NO_SPIN", "MCCONV_TD_FFT", "MCCONV_CARRY_DROP")):
+    if not any(os.environ.get(k) for k in ("MCCONV_NO_PARK", "MCCONV_NO_SPIN", "MCCONV_TD_FFT")):
         assert parks["timed_out"] >= 1 and stats["carried_periods"] > 10, (stats, parks)
 
 
@@ -700,21 +688,18 @@ def test_q8_history_across_long_batches(oracle_mod, gpu_lib, sizes):
     c.close()
 
 
-@pytest.mark.parametrize("period,form,pd", [(256, "fft", 1100), (512, "fft", 1100), (1024, "fft", 1100), (512, "tiles", 1100), (256, "fft", 1024),
-                                            (256, "no_drop_ahead", 1024)])
+@pytest.mark.parametrize("period,form,pd", [(256, "fft", 1100), (512, "fft", 1100), (1024, "fft", 1100), (512, "tiles", 1100), (256, "fft", 1024)])
 def test_q8_with_crossfading_irs_and_longer_periods(oracle_mod, gpu_lib, period, form, pd, monkeypatch):
     """The Q8 regime with everything that shapes its cut terms at once: two IRs of different length cross-fading on one half
     (two voices with their own gains per block), an unaligned predelay (three slices of the last partitions' segments
     contribute), and reference calls of 2 and 4 blocks (the cut is measured from the start of the CALL: block distances
     differ inside a call).  Batches of whole calls, both forms of the cut terms, against oracle.RefCompat run call by call.
     Predelay 1024 with calls of one block is the shipped shape - every output block loses ONE term of ONE source block, here of two
-    cross-fading voices with gains per block - which the forward transforms sum themselves (k_fwd<true>; `no_drop_ahead`: k_drop_fft)."""
+    cross-fading voices with gains per block - which the forward transforms sum themselves (k_fwd<true>)."""
     from cuda_audio_amd.synth import make_input
 
     if form == "tiles":
         monkeypatch.setenv("MCCONV_TD_FFT", "0")
-    if form == "no_drop_ahead":
-        monkeypatch.setenv("MCCONV_DROP_AHEAD", "0")
     n_ref, pm = 4096, period // 256
     ncalls = (3 * n_ref // 256 // 2 + 44) // pm
     x = make_input(ncalls * period, seed=91)
@@ -747,21 +732,16 @@ def test_q8_with_crossfading_irs_and_longer_periods(oracle_mod, gpu_lib, period,
         got[:, s] = c.process(x[0, s], x[1, s])
         k += n
     stats = c.drop_stats()
-    lab = c.lab_build()
     c.close()
     err = rms(got - want)
     assert err <= RMS_TOL, f"rms {err:.3e} (signal {rms(want):.3e})"
-    if form == "no_drop_ahead" and not lab:
-        return  # (MCCONV_DROP_AHEAD exists in the lab build only: here the run repeated the default form)
     # the form under test is the form that ran
     if os.environ.get("MCCONV_TD_FFT") == "0" and form != "tiles":
         form = "tiles"  # (the whole suite under that switch)
     if form == "tiles":
         assert stats["tiles"] > 0 and stats["drop_fft"] == stats["forward_transforms"] == 0, stats
-    elif form == "fft" and pd == 1024 and not any(os.environ.get(k) for k in ("MCCONV_INV_WET", "MCCONV_FUSE_OUT", "MCCONV_FUSE_DROP", "MCCONV_DROP_AHEAD", "MCCONV_HTAIL")):
-        assert stats["forward_transforms"] > 0 and stats["tiles"] == 0, stats  # (the measurement switches named above take the output elsewhere)
     elif form == "fft" and pd == 1024:
-        assert stats["drop_fft"] + stats["forward_transforms"] > 0 and stats["tiles"] == 0, stats
+        assert stats["forward_transforms"] > 0 and stats["tiles"] == 0, stats
     else:
         assert stats["drop_fft"] > 0 and stats["forward_transforms"] == stats["tiles"] == 0, stats
 
@@ -922,11 +902,9 @@ def test_fp16_engines_take_the_overlap_save_form_for_long_batches(gpu_lib, monke
         a = 3 * T * 256
         per.append(np.concatenate([np.stack(c.onProcess(x[0, a + 256 * j:a + 256 * (j + 1)], x[1, a + 256 * j:a + 256 * (j + 1)])) for j in range(4)], axis=1))
         c.close()
-    if _os_form_possible():
-        assert levels[0][1:] == [253, 253] and levels[1][1:] == [253, 253], levels
+    assert levels[0][1:] == [253, 253] and levels[1][1:] == [253, 253], levels
     wet = rms(per[0]) * 0.5
-    # (where a lab switch keeps the form away, the fp16 engine's long batches are the fp16 sweep's)
-    assert rms(outs[1][1:] - outs[0][1:]) <= (1e-6 if _os_form_possible() else FP16_REL_TOL * wet + 1e-6)
+    assert rms(outs[1][1:] - outs[0][1:]) <= 1e-6
     assert rms(per[1] - per[0]) <= FP16_REL_TOL * wet + 1e-6
 
 
@@ -1634,10 +1612,11 @@ def test_pipelined_batches_equal_unpipelined(gpu_lib, n_ref, taps, T, pd, sliced
     assert np.array_equal(outs[0], outs[1]), f"rms difference {rms(outs[0] - outs[1]):.3e}"
 
 
-def test_overlap_add_in_the_inverse_kernel_is_bit_identical(gpu_lib, monkeypatch):
+def test_overlap_add_in_the_inverse_kernel_is_bit_identical(gpu_lib):
     """Whole-batch path: k_inv_wet (inverse transform + overlap-add into the wet ring, tiles of 15 blocks + the block
-    before them) against k_inv + segment ring + overlap-add in k_post (MCCONV_INV_WET=0) - the same bits, for batch
-    lengths around the tile size, with a predelay, single periods in between and a predelay change."""
+    before them) for batch lengths around the tile size, with a predelay, single periods in between and a predelay
+    change: two runs of the same events on fresh engines give the same bits (the tiles' hand-over through the segment
+    ring depends on nothing but the batch)."""
     from cuda_audio_amd.synth import make_input, make_ir
 
     sizes = [1, 14, 15, 16, 1, 17, 29, 30, 31, 1, 1, 45, 46, 300, 7]
@@ -1645,8 +1624,7 @@ def test_overlap_add_in_the_inverse_kernel_is_bit_identical(gpu_lib, monkeypatch
     x = make_input(nb * 256)
     irs = [make_ir(5000, seed=11, norm=0.05), make_ir(4000, seed=12, norm=0.05)]
 
-    def run(flag):
-        monkeypatch.setenv("MCCONV_INV_WET", flag)
+    def run():
         c = _conv(fftSize=8192, max_batch=max(sizes))
         for i, ir in enumerate(irs):
             c.prepare(i, ir)
@@ -1661,9 +1639,9 @@ def test_overlap_add_in_the_inverse_kernel_is_bit_identical(gpu_lib, monkeypatch
         c.close()
         return np.concatenate(parts, axis=1)
 
-    a, b = run("1"), run("0")
+    a, b = run(), run()
     assert rms(a) > 1e-3
-    assert np.array_equal(a, b), f"max abs difference {np.abs(a - b).max():.3e}"
+    assert np.array_equal(a, b), f"max abs difference between the runs {np.abs(a - b).max():.3e}"
 
 
 def test_preferred_batch_length(gpu_lib, monkeypatch):
@@ -1829,8 +1807,7 @@ def test_headline_launch_against_the_range_oracle(oracle_mod, gpu_lib, monkeypat
         assert T == ((129296 if at_most > 32768 else 32320) if taps == 441000 else (30248 if level == 254 else 22432))
         chunk = (8192 if level == 254 else 16384) - p16 + 1
         assert T == (-(-T // chunk) * chunk - 1) // 8 * 8  # whole chunks minus the halo block, rounded down to 8
-    if level != 253 or _os_form_possible():
-        assert levels[1] == level and levels[2] == level, levels  # steady state: one set of gains over the window
+    assert levels[1] == level and levels[2] == level, levels  # steady state: one set of gains over the window
     ranges = [(T + 100, 256), (T + chunk - 65, 130), (2 * T - 128, 128 + 64)]  # (first block, blocks) in the stream
     num = den = 0.0
     for b0, n in ranges:
@@ -1917,17 +1894,15 @@ def test_overlap_save_batches_match_the_partitioned_passes(oracle_mod, gpu_lib, 
     got, lv1, st1 = run(True)
     assert st0["batches"] == 0 and 253 not in lv0
     assert lv1[0] != 253 and lv1[5] != 253 and lv1[7] != 253, lv1  # cold-start ramp, gain change, cross-fade: per-slot gains
-    if _os_form_possible():
-        # batches 1-4 and 6 (one set of gains), 8 and 9 after the cross-fade has settled within the window or not: at least these
-        assert [lv1[k] for k in (1, 2, 3, 4, 6)] == [253] * 5, lv1
-        assert st1["batches"] >= 5 and st1["spectra_builds"] >= 2
+    # batches 1-4 and 6 (one set of gains), 8 and 9 after the cross-fade has settled within the window or not: at least these
+    assert [lv1[k] for k in (1, 2, 3, 4, 6)] == [253] * 5, lv1
+    assert st1["batches"] >= 5 and st1["spectra_builds"] >= 2
     o = 0
     for k, n in enumerate(sizes + [nper]):
         d = rms(got[:, o * 256:(o + n) * 256] - ref[:, o * 256:(o + n) * 256])
         assert d <= 1e-6, f"batch {k} ({n} blocks, form {lv1[k] if k < len(lv1) else 'periods'}): {d:.3e} from the partitioned passes"
         o += n
-    if _os_form_possible():
-        assert rms(got - ref) > 0
+    assert rms(got - ref) > 0
     # steady stretches against the oracle itself: inside batch 2's second segment, the end of batch 3 and the start of batch 4
     s1, s3 = sum(sizes[:2]), sum(sizes[:4])
     for b0, n in [(s1 + hop - 40, 120), (s3 - 70, 140)]:
@@ -1991,11 +1966,10 @@ def test_overlap_save_form_in_the_q8_regime_and_around_retired_epochs(gpu_lib, m
     got, lv1, st1 = run(True)
     assert 253 not in lv0
     assert lv1[0] != 253 and 253 not in lv1[3:6], lv1  # cold-start ramp; the predelay change and the three-partition Q8 shape; the change out of the regime
-    if _os_form_possible() and not any(os.environ.get(k) == "0" for k in ("MCCONV_FUSE_DROP", "MCCONV_DROP_AHEAD", "MCCONV_TD_FFT", "MCCONV_HTAIL")):
+    if os.environ.get("MCCONV_TD_FFT") != "0":
         assert lv1[1] == 253 and lv1[2] == 253, lv1  # the shipped shape in the form
         assert st1["forward_transforms"] >= 2, st1
-    if _os_form_possible():
-        assert lv1[6] == 253, lv1  # the window is settled again and the old epochs are out of reach
+    assert lv1[6] == 253, lv1  # the window is settled again and the old epochs are out of reach
     for k in range(nbat):
         d = rms(got[:, k * T * 256:(k + 1) * T * 256] - ref[:, k * T * 256:(k + 1) * T * 256])
         assert d <= 1e-6, f"batch {k}: {d:.3e}"
@@ -2057,9 +2031,8 @@ def test_overlap_save_form_of_block_slices(oracle_mod, gpu_lib, monkeypatch, pd)
         c.close()
     ref, got = ref.cpu().numpy(), got.cpu().numpy()
     assert 253 not in levels[:2], levels  # (the first batch's window holds the cold-start ramp)
-    if _os_form_possible():
-        assert levels[2:] == [253] * (2 * nbat - 2), levels
-        assert st == [nbat - 1] * world, st
+    assert levels[2:] == [253] * (2 * nbat - 2), levels
+    assert st == [nbat - 1] * world, st
     for k in range(nbat):
         d = rms(got[:, k * T * 256:(k + 1) * T * 256] - ref[:, k * T * 256:(k + 1) * T * 256])
         assert d <= 1e-6, f"batch {k}: {d:.3e} from the unsliced partitioned passes"
@@ -2134,12 +2107,10 @@ def test_native_group_driver(oracle_mod, gpu_lib, ranks):
 
 
 def test_fused_second_level_kernel_for_any_grid(gpu_lib, monkeypatch):
-    """k_g2_mac's workgroups stride over the (bin, chunk) items (default: one workgroup per item).  Any grid - one
-    workgroup, fewer / more than the CUs, not a multiple of the 8 XCDs, not a divisor of the items, exactly the items,
-    more than the items - gives the same bits; T is not a multiple of the chunk (6465 blocks) or of anything else, so
-    the last chunk is ragged (MCCONV_G2_GRID; bounds argument at the kernel).  The same for the
-    one-workgroup-per-CU form with its look-ahead into the next item (MCCONV_G2_WIDE=1) and for the lockstep form of
-    round 3 (k_g2_duo, MCCONV_G2_DUO=1)."""
+    """k_g2_mac, one workgroup per (bin, chunk) item: T is not a multiple of the chunk (6465 blocks) or of anything else,
+    so the last chunk is ragged (bounds argument at the kernel).  The fused form takes the batch, and two runs
+    on fresh engines give the same bits.  (The grid switch and the two alternative forms of the kernel that this test
+    also compared are retired: docs/DESIGN_history.md.)"""
     import torch
 
     from cuda_audio_amd.synth import make_input, make_ir
@@ -2149,17 +2120,9 @@ def test_fused_second_level_kernel_for_any_grid(gpu_lib, monkeypatch):
     T0, T = 2000, 9001  # settle the cross-fade with a first batch, then 6465 + 2536 blocks = 512 items
     x = torch.from_numpy(make_input((T0 + T) * 256)).to(dev)
 
-    def run(grid, wide=False, duo=None):
-        monkeypatch.setenv("MCCONV_FFT2", "1")  # (the suite is also run with the measurement switches set)
+    def run():
+        monkeypatch.setenv("MCCONV_FFT2", "1")  # (the suite is also run with the form switches set)
         monkeypatch.setenv("MCCONV_FFT2_FUSED", "1")
-        monkeypatch.setenv("MCCONV_G2_WIDE", "1" if wide else "0")
-        monkeypatch.setenv("MCCONV_G2_DUO", "0" if duo is None else "1")
-        monkeypatch.setenv("MCCONV_G2_DUO_MINCH", "1")
-        monkeypatch.setenv("MCCONV_G2_DUO_GRID", str(duo or 256))
-        if grid is None:
-            monkeypatch.delenv("MCCONV_G2_GRID", raising=False)
-        else:
-            monkeypatch.setenv("MCCONV_G2_GRID", str(grid))
         c = _conv(fftSize=524288, max_batch=T)
         for i, ir in enumerate(irs):
             c.prepare(i, ir)
@@ -2175,22 +2138,10 @@ def test_fused_second_level_kernel_for_any_grid(gpu_lib, monkeypatch):
         c.close()
         return out[:, T0 * 256:].cpu().numpy()
 
-    want = run(None)
+    want = run()
     assert rms(want) > 0.01
-    for grid in (1, 7, 8, 100, 255, 511, 512, 513):
-        got = run(grid)
-        assert np.array_equal(got, want), f"MCCONV_G2_GRID={grid}: rms {rms(got - want):.3e}"
-    wide = run(None, wide=True)
-    assert rms(wide - want) <= 1e-7  # (bin 0 is summed in another order there)
-    for grid in (1, 7, 255, 513):
-        got = run(grid, wide=True)
-        assert np.array_equal(got, wide), f"MCCONV_G2_WIDE=1 MCCONV_G2_GRID={grid}: rms {rms(got - wide):.3e}"
-    # k_g2_duo (MCCONV_G2_DUO=1: the two halves of a 1024-thread workgroup run the items' phases one phase apart, in
-    # barrier lockstep): the same arithmetic per item, so the same bits - with two chunks per bin (both halves busy, the
-    # ragged chunk on the second), and with fewer workgroups than CUs (several rounds, a half without an item at the end)
-    for dgrid in (256, 8, 72, 200):
-        got = run(None, duo=dgrid)
-        assert np.array_equal(got, want), f"MCCONV_G2_DUO=1 MCCONV_G2_DUO_GRID={dgrid}: rms {rms(got - want):.3e}"
+    got = run()
+    assert np.array_equal(got, want), f"rms difference between the runs {rms(got - want):.3e}"
 
 
 def test_pinned_host_batches_overlap_copies_and_match(oracle_mod, gpu_lib):
@@ -2507,11 +2458,11 @@ def test_parked_periods_survive_pauses_and_interleaved_calls(oracle_mod, gpu_lib
         if period == 256 and not os.environ.get("MCCONV_LIB") and not os.environ.get("MCCONV_TAIL_FORM"):
             # both forms of the 256-frame tail ran: a parked tail that had to wait takes partition 0 in the time domain, a period
             # launched on arrival (every one of them with MCCONV_NO_PARK=1) in the frequency domain
-            if park and not any(os.environ.get(k) for k in ("MCCONV_NO_SPECULATE", "MCCONV_NO_SPIN", "MCCONV_NO_PARK")):
+            if park and not any(os.environ.get(k) for k in ("MCCONV_NO_SPIN", "MCCONV_NO_PARK")):
                 assert forms["time_domain"] >= 30 and forms["frequency_domain"] >= 20, forms
             else:
                 assert forms["time_domain"] == 0 and forms["frequency_domain"] == ncalls, forms
-        if park and not any(os.environ.get(k) for k in ("MCCONV_NO_SPECULATE", "MCCONV_NO_SPIN")):  # (those switches leave nothing parked)
+        if park and not os.environ.get("MCCONV_NO_SPIN"):  # (that switch leaves nothing parked)
             # the paths under test really ran: parked periods were used before the first pause, a pause made one time out,
             # the controller / batch / reload told parked periods to give up, and parking resumed after the second settling
             assert stats["settled"]["used"] >= 5, stats
@@ -2523,7 +2474,7 @@ def test_parked_periods_survive_pauses_and_interleaved_calls(oracle_mod, gpu_lib
             assert stats["end"] == dict(used=0, timed_out=0, cancelled=0), stats
         err = rms(outs[-1] - want)
         assert err <= RMS_TOL, f"park={park}: rms {err:.3e}"
-    if period == 256 and not os.environ.get("MCCONV_TAIL_FORM") and "fft0" not in os.environ.get("MCCONV_LIB", ""):  # (lab builds: one form forced, or round 3's one-form tail)
+    if period == 256 and not os.environ.get("MCCONV_TAIL_FORM"):  # (MCCONV_TAIL_FORM: one form forced)
         assert np.abs(outs[0] - outs[1]).max() <= 5e-7, np.abs(outs[0] - outs[1]).max()
     else:
         assert np.array_equal(outs[0], outs[1])
@@ -2534,9 +2485,9 @@ def test_output_finished_by_the_inverse_transforms(oracle_mod, gpu_lib, monkeypa
     """Whole batches on one engine with no Q8 pass and no retired predelay epoch: the inverse-transform launches
     (k_inv_wet<true>) finish the output themselves - Q1/Q2 window sums, clamp, dry mix, shifted by the predelay - and
     k_post only fills the head the predelay reaches back for; the Q1/Q2 prefix sums ride along with k_g2_mac in one pass.
-    Same samples as the k_post route (MCCONV_FUSE_OUT=0, prefix sums as two launches) and as the oracle, for predelays
-    that are and are not multiples of four frames, batches shorter than the predelay, a device-buffer and a host-buffer
-    call, and a parameter change between batches (conv.cu:89-100, 126-140, 411-427)."""
+    The oracle's samples, and the same samples from two runs on fresh engines, for predelays that are and are not multiples
+    of four frames, batches shorter than the predelay, a device-buffer and a host-buffer call, and a parameter change
+    between batches (conv.cu:89-100, 126-140, 411-427)."""
     import torch
 
     from cuda_audio_amd.synth import make_input, make_ir
@@ -2551,9 +2502,7 @@ def test_output_finished_by_the_inverse_transforms(oracle_mod, gpu_lib, monkeypa
     x[1, ::2] += 0.04
     p0, p1 = dict(BASE, predelay=predelay, wet=0.6, panDry=0.3), dict(BASE, select=1, level=0.9, panWet=-0.4)
     outs = []
-    for fuse in ("1", "0"):
-        monkeypatch.setenv("MCCONV_FUSE_OUT", fuse)
-        monkeypatch.setenv("MCCONV_CORR_RIDE", fuse)
+    for _ in range(2):
         monkeypatch.setenv("MCCONV_FFT2", "1")
         monkeypatch.setenv("MCCONV_FFT2_FUSED", "1")
         c = _conv(fftSize=n_ref, max_batch=2048)
@@ -2578,7 +2527,7 @@ def test_output_finished_by_the_inverse_transforms(oracle_mod, gpu_lib, monkeypa
         outs.append(out)
         c.close()
     assert np.isfinite(outs[0]).all()
-    assert rms(outs[0] - outs[1]) <= 1e-7, f"finished by k_inv_wet vs by k_post: rms {rms(outs[0] - outs[1]):.3e}"
+    assert rms(outs[0] - outs[1]) <= 1e-7, f"rms difference between the runs {rms(outs[0] - outs[1]):.3e}"
     u = oracle_mod.Upols(n_ref, True)
     for i, ir in enumerate(irs):
         u.prepare(i, ir)
@@ -2592,10 +2541,11 @@ def test_output_finished_by_the_inverse_transforms(oracle_mod, gpu_lib, monkeypa
     assert err <= RMS_TOL, f"rms {err:.3e}"
 
 
-def test_batch_longer_than_the_riding_prefix_chain(oracle_mod, gpu_lib, monkeypatch):
+def test_batch_longer_than_the_riding_prefix_chain(oracle_mod, gpu_lib):
     """Batches of more than 160 x 256 blocks: the Q1/Q2 prefix sums do not ride along with the MAC launch (every riding
     workgroup would look at the totals of all chunks before it) but run as their own two launches ahead of the inverse
-    transforms that finish the output.  Same bits as the k_post route, the oracle's samples at the batch end."""
+    transforms that finish the output.  The same samples from two runs on fresh engines, the oracle's samples at the
+    batch end."""
     import torch
 
     from cuda_audio_amd.synth import make_input, make_ir
@@ -2607,8 +2557,7 @@ def test_batch_longer_than_the_riding_prefix_chain(oracle_mod, gpu_lib, monkeypa
     x[0] += 0.04
     p0, p1 = dict(BASE, predelay=128, wet=0.7), dict(BASE, select=1, panWet=0.4)
     outs = []
-    for fuse in ("1", "0"):
-        monkeypatch.setenv("MCCONV_FUSE_OUT", fuse)
+    for _ in range(2):
         c = _conv(fftSize=n_ref, max_batch=T)
         for i, ir in enumerate(irs):
             c.prepare(i, ir)
@@ -2620,7 +2569,7 @@ def test_batch_longer_than_the_riding_prefix_chain(oracle_mod, gpu_lib, monkeypa
         outs.append(d_out.cpu().numpy())
         c.close()
     assert np.isfinite(outs[0]).all()
-    assert rms(outs[0] - outs[1]) <= 1e-7
+    assert rms(outs[0] - outs[1]) <= 1e-7, f"rms difference between the runs {rms(outs[0] - outs[1]):.3e}"
     u = oracle_mod.Upols(n_ref, True)
     for i, ir in enumerate(irs):
         u.prepare(i, ir)
@@ -2722,7 +2671,7 @@ def test_spaced_jack_periods_take_the_time_domain_tail_and_match_the_oracle(orac
 
     from cuda_audio_amd.synth import make_input, make_ir
 
-    if any(os.environ.get(k) for k in ("MCCONV_NO_PARK", "MCCONV_NO_SPIN", "MCCONV_NO_SPECULATE")) or os.environ.get("MCCONV_TAIL_FORM") == "fd":
+    if any(os.environ.get(k) for k in ("MCCONV_NO_PARK", "MCCONV_NO_SPIN")) or os.environ.get("MCCONV_TAIL_FORM") == "fd":
         pytest.skip("nothing is parked / one form is forced under this switch")
     n_ref, settle, spaced = 4096, 200, 120
     compat = True
