@@ -18,7 +18,7 @@ MC_MAX_PREDELAY = 8192
 # every symbol include/mcconv.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "mc_abi_version", "mc_last_error", "mc_default_config", "mc_default_params", "mc_create", "mc_destroy",
-    "mc_reset", "mc_set_period", "mc_load_ir", "mc_load_ir_resampled", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
+    "mc_reset", "mc_set_period", "mc_load_ir", "mc_load_ir_resampled", "mc_default_ir_shape", "mc_load_ir_shaped", "mc_ir_shape_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
     "mc_enable_kernel_timing", "mc_get_kernel_stats", "mc_algorithmic_bytes_per_block", "mc_blocks_processed", "mc_preferred_batch",
@@ -58,6 +58,27 @@ class McCcValue(C.Structure):
         ("panDry", C.c_float),
         ("panWet", C.c_float),
         ("level", C.c_float),
+    ]
+
+
+MC_SHAPE_REVERSE = 1
+MC_NORM_NONE, MC_NORM_PEAK, MC_NORM_ENERGY = 0, 1, 2
+
+
+class McIrShape(C.Structure):
+    """mc_ir_shape: what mc_load_ir_shaped does to an IR before it is truncated and transformed."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("start", C.c_uint64),
+        ("length", C.c_uint64),
+        ("decay_t60", C.c_uint64),
+        ("fade_out", C.c_uint64),
+        ("trim_db", C.c_float),
+        ("pre_roll", C.c_uint32),
+        ("normalize", C.c_uint32),
+        ("target", C.c_float),
     ]
 
 
@@ -111,6 +132,10 @@ def load():
     L.mc_set_period.argtypes = [vp, C.c_uint32]
     L.mc_load_ir.argtypes = [vp, u64, fp, u64, u64]
     L.mc_load_ir_resampled.argtypes = [vp, u64, fp, u64, u64, C.c_uint32, C.c_uint32]
+    L.mc_default_ir_shape.argtypes = [C.POINTER(McIrShape)]
+    L.mc_default_ir_shape.restype = None
+    L.mc_load_ir_shaped.argtypes = [vp, u64, fp, u64, u64, C.c_uint32, C.c_uint32, C.POINTER(McIrShape)]
+    L.mc_ir_shape_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_num_irs.argtypes = [vp]
     L.mc_ir_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_set_params.argtypes = [vp, C.c_int, C.POINTER(McCcValue)]

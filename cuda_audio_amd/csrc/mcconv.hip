@@ -26,6 +26,7 @@
 #include "ossave.hip.h"
 #include "singlefft.hip.h"
 #include "resample.hip.h"
+#include "irshape.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
 // mc_config or that the tests compare bit for bit:
@@ -94,6 +95,8 @@ struct IrEntry {
     uint64_t taps = 0;
     int P = 0;
     double sums[4] = {0, 0, 0, 0};
+    bool shaped = false;  // the last load was mc_load_ir_shaped with something on: shape_info is what mc_ir_shape_info reports
+    double shape_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 }  // namespace
@@ -3264,9 +3267,27 @@ int mc_set_period(mc_engine* e, uint32_t nframes) {
 }  // extern "C"
 
 namespace {
-// mc_load_ir and mc_load_ir_resampled: rs = {IR rate, session rate} converts the frames on the device (resample.hip.h)
-// before anything else sees them; null = the frames as given (the reference)
-int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs) {
+// The shaped load's own stage (irshape.hip.h): all `conv` frames at the session's rate on the device, shaped into a new buffer
+// of *n <= cap taps that the caller owns.  Nothing of the engine's IRs is touched here.
+int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, uint64_t cap, const uint32_t* rs, const mc_ir_shape& sh,
+                float2** d_taps, uint64_t* n, double sums[4], double info[8]) {
+    float2* d_x = nullptr;
+    HIP_TRY(hipMalloc(&d_x, sizeof(float2) * conv));
+    double unused[4];
+    hipError_t er = rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, d_x, conv, unused)
+                       : hipMemcpy(d_x, lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
+    if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, sh, d_taps, n, sums, info);
+    (void)hipFree(d_x);
+    if (er != hipSuccess) return fail(MC_ERR_HIP, "IR shaping failed: %s", hipGetErrorString(er));
+    if (!*n) return fail(MC_ERR_ARG, "the shape leaves no frame of the IR (start %llu, %llu frames at the session's rate)",
+                         (unsigned long long)sh.start, (unsigned long long)conv);
+    return MC_OK;
+}
+
+// mc_load_ir, mc_load_ir_resampled and mc_load_ir_shaped: rs = {IR rate, session rate} converts the frames on the device
+// (resample.hip.h) before anything else sees them; null = the frames as given (the reference).  sh = a shape with something
+// on, applied on the device after the conversion (irshape.hip.h); null = none
+int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs, const mc_ir_shape* sh = nullptr) {
     // Convolution::prepare, conv.cu:207-253
     if (!e || !lr) return fail(MC_ERR_ARG, "null argument");
     if (idx >= (uint64_t)kMaxIrs) return fail(MC_ERR_ARG, "IR index %llu >= %d", (unsigned long long)idx, kMaxIrs);
@@ -3274,23 +3295,47 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
     if (frames == 0) return fail(MC_ERR_ARG, "empty IR");
     const uint64_t conv = rs ? rs_out_frames(rs_geom(rs[0], rs[1]), frames) : frames;  // frames at the session's rate
     HIP_TRY(hipSetDevice(e->device));
-    if (e->sf) return sf_load_ir(e, idx, lr, frames, nframes, rs);
-    const uint64_t n = std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
+    float* d_lr = nullptr;
+    uint64_t nshaped = 0;
+    double rsum[4] = {0, 0, 0, 0}, sinfo[8];
+    if (sh) {  // (the stream must be idle and out of the JACK path before the shaping kernels go onto it)
+        int rc = e->sf ? MC_OK : drain_post(e);
+        if (!rc && !e->sf) rc = leave_jack_path(e);
+        if (rc) return rc;
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo);
+        if (rc) return rc;
+    }
+    if (e->sf) {
+        const int rc = sf_load_ir(e, idx, lr, frames, nframes, rs, reinterpret_cast<const float2*>(d_lr), nshaped, rsum);
+        if (sh) (void)hipFree(d_lr);
+        if (rc) return rc;
+        e->irs[idx].shaped = sh != nullptr;
+        if (sh) std::memcpy(e->irs[idx].shape_info, sinfo, sizeof(sinfo));
+        return MC_OK;
+    }
+    const uint64_t n = sh ? nshaped : std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
     const int P = (int)((n + MC_B - 1) / MC_B);
-    if (P > e->Pcap) return fail(MC_ERR_ARG, "IR needs %d partitions, engine capacity is %d", P, e->Pcap);
+    if (P > e->Pcap) {
+        if (sh) (void)hipFree(d_lr);
+        return fail(MC_ERR_ARG, "IR needs %d partitions, engine capacity is %d", P, e->Pcap);
+    }
     IrEntry& ir = e->irs[idx];
-    {
+    if (!sh) {
         int rc = drain_post(e);
         if (!rc) rc = leave_jack_path(e);
         if (rc) return rc;
     }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (!ir.d_H) HIP_TRY(hipMalloc(&ir.d_H, sizeof(float4) * (size_t)MC_NB * e->Pstride));
-    float* d_lr = nullptr;
-    HIP_TRY(hipMalloc(&d_lr, sizeof(float) * 2 * n));
-    double rsum[4] = {0, 0, 0, 0};
-    hipError_t er = rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, reinterpret_cast<float2*>(d_lr), n, rsum)
-                       : hipMemcpy(d_lr, lr, sizeof(float) * 2 * n, hipMemcpyHostToDevice);
+    hipError_t er = hipStreamSynchronize(e->stream);
+    if (er == hipSuccess && !ir.d_H) er = hipMalloc(&ir.d_H, sizeof(float4) * (size_t)MC_NB * e->Pstride);
+    if (er == hipSuccess && !sh) er = hipMalloc(&d_lr, sizeof(float) * 2 * n);
+    if (er != hipSuccess) {
+        (void)hipFree(d_lr);
+        return fail(MC_ERR_HIP, "IR preparation failed: %s", hipGetErrorString(er));
+    }
+    if (!sh)
+        er = rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, reinterpret_cast<float2*>(d_lr), n, rsum)
+                : hipMemcpy(d_lr, lr, sizeof(float) * 2 * n, hipMemcpyHostToDevice);
     if (er == hipSuccess) er = hipMemsetAsync(ir.d_H, 0, sizeof(float4) * (size_t)MC_NB * e->Pstride, e->stream);
     if (er == hipSuccess) {
         hipLaunchKernelGGL(k_fwd<false>, dim3((P + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, e->stream, d_lr, d_lr + 1, 2, (int64_t)n, P,
@@ -3333,8 +3378,8 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
         HIP_TRY(hipStreamSynchronize(e->stream));
     }
     double s[4] = {0, 0, 0, 0};
-    if (rs)
-        std::memcpy(s, rsum, sizeof(s));  // (summed on the device: the converted taps never come to the host)
+    if (rs || sh)
+        std::memcpy(s, rsum, sizeof(s));  // (summed on the device: the converted and the shaped taps never come to the host)
     else
         for (uint64_t m = 0; m < n; m++) {
             const double sg = (m & 1) ? -1.0 : 1.0;
@@ -3346,6 +3391,8 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
     std::memcpy(ir.sums, s, sizeof(s));
     ir.taps = n;
     ir.P = P;
+    ir.shaped = sh != nullptr;
+    if (sh) std::memcpy(ir.shape_info, sinfo, sizeof(sinfo));
     if ((int)idx + 1 > e->nirs) e->nirs = (int)idx + 1;
     e->spec_valid = e->dspec.valid = false;
     e->uniform_valid[0] = e->uniform_valid[1] = false;
@@ -3368,6 +3415,38 @@ int mc_load_ir_resampled(mc_engine* e, uint64_t idx, const float* lr, uint64_t f
     if (ir_rate == session_rate) return mc_load_ir(e, idx, lr, frames, nframes);
     const uint32_t rs[2] = {ir_rate, session_rate};
     return load_ir(e, idx, lr, frames, nframes, rs);
+}
+
+void mc_default_ir_shape(mc_ir_shape* s) {
+    if (!s) return;
+    std::memset(s, 0, sizeof(*s));
+    s->struct_size = (uint32_t)sizeof(*s);
+    s->target = 1.f;
+}
+
+int mc_load_ir_shaped(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
+                      uint32_t session_rate, const mc_ir_shape* shape) {
+    // the shape and the rates are checked before the pointers and before any HIP call: a refused load leaves the engine as it was
+    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    const bool convert = ir_rate || session_rate;  // (0, 0: the frames are at the session's rate)
+    if (convert)
+        for (int k = 0; k < 2; k++) {
+            const uint32_t r = k ? session_rate : ir_rate;
+            if (r < RS_MIN_RATE || r > RS_MAX_RATE)
+                return fail(MC_ERR_ARG, "%s %u outside [%u, %u] (both rates 0 = no conversion)", k ? "session_rate" : "ir_rate", r, RS_MIN_RATE, RS_MAX_RATE);
+        }
+    if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
+    if (ish_is_off(*shape))
+        return convert ? mc_load_ir_resampled(e, idx, lr, frames, nframes, ir_rate, session_rate) : mc_load_ir(e, idx, lr, frames, nframes);
+    const uint32_t rs[2] = {ir_rate, session_rate};
+    return load_ir(e, idx, lr, frames, nframes, convert && ir_rate != session_rate ? rs : nullptr, shape);
+}
+
+int mc_ir_shape_info(const mc_engine* e, uint64_t idx, double out[8]) {
+    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
+    if (!e->irs[idx].shaped) return fail(MC_ERR_STATE, "IR %llu was not loaded with a shape", (unsigned long long)idx);
+    for (int i = 0; i < 8; i++) out[i] = e->irs[idx].shape_info[i];
+    return MC_OK;
 }
 
 int mc_num_irs(const mc_engine* e) { return e ? e->nirs : 0; }

@@ -54,15 +54,21 @@ inline int sf_create(mc_engine* e) {
 }
 
 // Convolution::prepare, conv.cu:207-253.  rs = {IR rate, session rate}: the frames are converted on the device straight into the
-// transform's input (resample.hip.h); null = the frames as given
-inline int sf_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs = nullptr) {
+// transform's input (resample.hip.h); null = the frames as given.  d_shaped = the nshaped taps (<= N - nframes) and their sums
+// that mc_load_ir_shaped left on the device (irshape.hip.h), which then are the IR; null = none
+inline int sf_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs = nullptr,
+                      const float2* d_shaped = nullptr, uint64_t nshaped = 0, const double* shaped_sums = nullptr) {
     SfState* s = e->sf;
     const uint64_t N = (uint64_t)s->N;
-    const uint64_t n = std::min<uint64_t>(rs ? rs_out_frames(rs_geom(rs[0], rs[1]), frames) : frames, N - nframes);  // conv.cu:239
+    const uint64_t n = d_shaped ? nshaped : std::min<uint64_t>(rs ? rs_out_frames(rs_geom(rs[0], rs[1]), frames) : frames, N - nframes);  // conv.cu:239
     IrEntry& ir = e->irs[idx];
     HIP_TRY(hipStreamSynchronize(e->stream));
     double sm[4] = {0, 0, 0, 0};
-    if (rs) {
+    if (d_shaped) {
+        HIP_TRY(hipMemsetAsync(s->d_W, 0, sizeof(float2) * N, e->stream));
+        HIP_TRY(hipMemcpyAsync(s->d_W, d_shaped, sizeof(float2) * n, hipMemcpyDeviceToDevice, e->stream));
+        std::memcpy(sm, shaped_sums, sizeof(sm));
+    } else if (rs) {
         HIP_TRY(hipMemsetAsync(s->d_W, 0, sizeof(float2) * N, e->stream));
         HIP_TRY(rs_convert(e->stream, rs[0], rs[1], lr, frames, s->d_W, n, sm));
     } else {

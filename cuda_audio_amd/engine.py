@@ -9,12 +9,13 @@ returns the two playback buffers.  All arithmetic runs in libmcconv.so (HIP);
 there is no CPU path here.
 """
 import ctypes as C
+import dataclasses
 import weakref
 
 import numpy as np
 
 from . import _lib
-from ._lib import MC_BLOCK, McCcValue, McConfig, McKernelStats, check
+from ._lib import MC_BLOCK, McCcValue, McConfig, McIrShape, McKernelStats, check
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
 CONV_MAX_SPEED = 1024             # conv.h:22-24
@@ -28,6 +29,33 @@ def _f32(a):
 
 def _fp(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+@dataclasses.dataclass
+class IrShape:
+    """What prepare(shape=...) does to an IR before it is truncated and transformed (mc_ir_shape, include/mcconv.h).
+    Lengths and positions are frames at the session's rate; the defaults switch everything off."""
+
+    start: int = 0          # frames skipped unconditionally at the front
+    trim_db: float = 0.0    # [-120, 0]; < 0: the onset is the first frame within trim_db of the peak
+    pre_roll: int = 0       # frames kept before the onset
+    length: int = 0         # frames kept from there; 0 = all
+    reverse: bool = False
+    decay_t60: int = 0      # 0 = off; else a further 60 dB of exponential decay at tap decay_t60
+    fade_out: int = 0       # raised-cosine fade over the last fade_out stored taps
+    normalize: str = None   # "peak", "energy" or None
+    target: float = 1.0     # peak: max |tap|; energy: sqrt(sum (hL^2 + hR^2) / 2)
+
+    def to_c(self):
+        norm = {None: _lib.MC_NORM_NONE, "peak": _lib.MC_NORM_PEAK, "energy": _lib.MC_NORM_ENERGY}
+        if self.normalize not in norm:
+            raise ValueError(f"normalize must be 'peak', 'energy' or None, not {self.normalize!r}")
+        s = McIrShape()
+        _lib.load().mc_default_ir_shape(C.byref(s))
+        s.flags = _lib.MC_SHAPE_REVERSE if self.reverse else 0
+        s.start, s.trim_db, s.pre_roll, s.length = int(self.start), float(self.trim_db), int(self.pre_roll), int(self.length)
+        s.decay_t60, s.fade_out, s.normalize, s.target = int(self.decay_t60), int(self.fade_out), norm[self.normalize], float(self.target)
+        return s
 
 
 class _CCValueView:
@@ -126,15 +154,21 @@ class Convolution:
         check(self._L.mc_set_period(self._h, nframes))
 
     # -- reference surface ----------------------------------------------------
-    def prepare(self, idx, wav, nframes=1024, ir_rate=None):
+    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None):
         """Convolution::prepare (conv.cu:207-253).  `wav` is float32 [frames, 2]
         (what WavFile.buffer holds) or an object with a `.buffer` of that shape.
         ir_rate (Hz; default: `wav.sampleRate` when it has one): when both it and the engine's sample_rate are known and
-        differ, the IR is converted to the session's rate on the device (mc_load_ir_resampled)."""
+        differ, the IR is converted to the session's rate on the device (mc_load_ir_resampled).
+        shape (an IrShape): trim, reverse, decay, fade and normalise the IR on the device, after the conversion and before
+        the truncation (mc_load_ir_shaped); ir_shape_info(idx) then tells what was done."""
         lr = _f32(getattr(wav, "buffer", wav)).reshape(-1, 2)
         if ir_rate is None:
             ir_rate = getattr(wav, "sampleRate", None)
-        if ir_rate is not None and self.sample_rate is not None and int(ir_rate) != int(self.sample_rate):
+        convert = ir_rate is not None and self.sample_rate is not None and int(ir_rate) != int(self.sample_rate)
+        if shape is not None:
+            rates = (int(ir_rate), int(self.sample_rate)) if convert else (0, 0)
+            check(self._L.mc_load_ir_shaped(self._h, idx, _fp(lr), lr.shape[0], nframes, *rates, C.byref(shape.to_c())))
+        elif convert:
             check(self._L.mc_load_ir_resampled(self._h, idx, _fp(lr), lr.shape[0], nframes, int(ir_rate), int(self.sample_rate)))
         else:
             check(self._L.mc_load_ir(self._h, idx, _fp(lr), lr.shape[0], nframes))
@@ -241,6 +275,12 @@ class Convolution:
         out = (C.c_double * 6)()
         check(self._L.mc_ir_info(self._h, idx, out))
         return dict(sigma=(out[0], out[1]), alpha=(out[2], out[3]), taps=int(out[4]), partitions=int(out[5]))
+
+    def ir_shape_info(self, idx):
+        """What the shaped load of IR idx did (mc_ir_shape_info); McError -3 for an IR that was not loaded with a shape."""
+        out = (C.c_double * 8)()
+        check(self._L.mc_ir_shape_info(self._h, idx, out))
+        return dict(frames=int(out[0]), onset=int(out[1]), first=int(out[2]), taps=int(out[3]), gain=out[4], peak=out[5], energy=out[6])
 
     def enable_kernel_timing(self, on=True):
         check(self._L.mc_enable_kernel_timing(self._h, 1 if on else 0))

@@ -1,6 +1,7 @@
 #include "conv.h"
 
 #include <cassert>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
@@ -17,6 +18,10 @@ int mc_group_process_batch(mc_group*, const float*, const float*, float*, float*
 const char* mc_group_last_error(void) __attribute__((weak));
 // (weak as well: the stub host's stand-in engine has no sample-rate conversion)
 int mc_load_ir_resampled(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t) __attribute__((weak));
+// (and no IR shaping)
+void mc_default_ir_shape(mc_ir_shape*) __attribute__((weak));
+int mc_load_ir_shaped(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*) __attribute__((weak));
+int mc_ir_shape_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 }
 
 namespace {
@@ -86,10 +91,48 @@ void Convolution::setMatchIrRate(bool on) {
     _matchIrRate = on;
 }
 
+void Convolution::setIrShape(const IrShape& shape) {
+    if (!shape.off() && _group) {
+        Log::error("conv", "IR shaping is not available with several devices (mc_group_load_ir takes no shape)");
+        std::exit(2);
+    }
+    _irShape = shape;
+}
+
+// irRate = sessionRate = 0: the frames are loaded at the rate they have
+void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape) {
+    if (!mc_load_ir_shaped || !mc_default_ir_shape || !mc_ir_shape_info) {
+        Log::error("conv", "the engine has no IR shaping (mc_load_ir_shaped)");
+        std::exit(2);
+    }
+    mc_ir_shape s;
+    mc_default_ir_shape(&s);
+    s.flags = shape.reverse ? MC_SHAPE_REVERSE : 0;
+    s.start = shape.start;
+    s.trim_db = shape.trimDb;
+    s.pre_roll = shape.preRoll;
+    s.length = shape.length;
+    s.decay_t60 = shape.decayT60;
+    s.fade_out = shape.fadeOut;
+    s.normalize = (uint32_t)shape.normalize;
+    s.target = shape.target;
+    if (irRate) Log::info(name, "IR %zu: %u Hz -> %u Hz", idx, irRate, sessionRate);
+    check(mc_load_ir_shaped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s), "mc_load_ir_shaped");
+    double info[8];
+    check(mc_ir_shape_info(_engine, idx, info), "mc_ir_shape_info");
+    Log::info(name, "IR %zu shaped: onset %llu, first kept frame %llu, %llu taps, gain %+.2f dB", idx, (unsigned long long)info[1],
+              (unsigned long long)info[2], (unsigned long long)info[3], 20.0 * std::log10(info[4]));
+}
+
 void Convolution::loadPendingIrs() {
     for (const PendingIr& p : _pendingIrs) {
         const uint64_t frames = p.lr.size() / 2;
-        if (!p.rate || p.rate == samplerate) {
+        const bool convert = p.rate && p.rate != samplerate;
+        if (!p.shape.off()) {
+            loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : 0, convert ? (unsigned)samplerate : 0, p.shape);
+            continue;
+        }
+        if (!convert) {
             check(mc_load_ir(_engine, p.idx, p.lr.data(), frames, p.nframes), "mc_load_ir");
             continue;
         }
@@ -106,7 +149,12 @@ void Convolution::loadPendingIrs() {
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
     if (_matchIrRate) {
         const float* lr = &wav.buffer[0].x;
-        _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames)});
+        _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape});
+        if (idx + 1 > _nirs) _nirs = idx + 1;
+        return;
+    }
+    if (!_irShape.off()) {  // (never with several devices: setIrShape)
+        loadShaped(idx, &wav.buffer[0].x, wav.numFrames, nframes, 0, 0, _irShape);
         if (idx + 1 > _nirs) _nirs = idx + 1;
         return;
     }

@@ -69,6 +69,24 @@ public:
     // decoded frames and their rate and onStart() loads them before activate().  A WAV at the client's rate (or of unknown
     // rate) is loaded as it is.  Single device only: with several devices this reports an error and exits.
     void setMatchIrRate(bool on);
+    // What every IR prepared from now on goes through before it is truncated and transformed (mc_ir_shape of
+    // include/mcconv.h, field for field; no reference equivalent).  Lengths and positions are frames at the rate the IR is
+    // loaded at: the client's with setMatchIrRate, the WAV's own without.  The defaults switch everything off.
+    struct IrShape {
+        uint64_t start = 0;      // frames skipped unconditionally at the front
+        float trimDb = 0.0f;     // [-120, 0]; < 0: the onset is the first frame within trimDb of the peak
+        uint32_t preRoll = 0;    // frames kept before the onset
+        uint64_t length = 0;     // frames kept from there; 0 = all
+        bool reverse = false;
+        uint64_t decayT60 = 0;   // 0 = off; else a further 60 dB of exponential decay at tap decayT60
+        uint64_t fadeOut = 0;    // raised-cosine fade over the last fadeOut stored taps
+        enum Normalize { None = 0, Peak = 1, Energy = 2 } normalize = None;
+        float target = 1.0f;     // Peak: max |tap|; Energy: sqrt(sum (hL^2 + hR^2) / 2)
+        bool off() const { return !start && trimDb == 0.0f && !length && !reverse && !decayT60 && !fadeOut && normalize == None; }
+    };
+    // One log line per shaped IR (onset, first kept frame, stored taps, gain).  Single device only: with several devices
+    // a shape with anything on reports an error and exits.
+    void setIrShape(const IrShape& shape);
 
     void onMidiMessage(const RawMidi::Device* sender, const uint8_t* buffer, size_t len) override;
 
@@ -89,9 +107,12 @@ private:
         size_t idx, nframes;
         unsigned rate;
         std::vector<float> lr;  // interleaved L, R frames
+        IrShape shape;          // as set when the IR was prepared
     };
     std::vector<PendingIr> _pendingIrs;  // (rate matching) prepared, loaded by onStart()
     void loadPendingIrs();
+    IrShape _irShape;
+    void loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape);
     void pushParams();
     void pullVsteps();
 };

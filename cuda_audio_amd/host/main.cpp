@@ -8,7 +8,10 @@
 // runs them (--sequential: one after the other; --period F: frames per period;
 // --spacing US: a period clock; --dump PREFIX: every instance's input and output
 // as raw float32 files PREFIX<i>.in1 / .in2 / .outL / .outR; --rate HZ: the fake server's sample rate, 44100 unless
-// given; --match-ir-rate: every IR is converted to the client's sample rate on load, Convolution::setMatchIrRate).
+// given; --match-ir-rate: every IR is converted to the client's sample rate on load, Convolution::setMatchIrRate;
+// --ir-start N, --ir-trim DB[:PREROLL], --ir-length N, --ir-reverse, --ir-decay N, --ir-fade N,
+// --ir-normalize peak|energy[:TARGET]: every IR is shaped on load, Convolution::setIrShape - lengths in frames at the rate
+// the IR is loaded at).
 #include <cassert>
 #include <cstdlib>
 #include <cstring>
@@ -29,6 +32,7 @@ int main(int argc, char** argv) {
     double spacing_us = 0.0;
     jack_nframes_t rate = 0, period = 0;  // fake JACK server: 0 = its defaults (44100 Hz, 256 frames)
     bool matchIrRate = false;
+    Convolution::IrShape irShape;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--periods") && i + 1 < argc) periods = strtoull(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "--settings") && i + 1 < argc) settingsPath = argv[++i];
@@ -38,6 +42,27 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--period") && i + 1 < argc) period = (jack_nframes_t)atoi(argv[++i]);
         else if (!strcmp(argv[i], "--rate") && i + 1 < argc) rate = (jack_nframes_t)atoi(argv[++i]);
         else if (!strcmp(argv[i], "--match-ir-rate")) matchIrRate = true;
+        else if (!strcmp(argv[i], "--ir-start") && i + 1 < argc) irShape.start = strtoull(argv[++i], nullptr, 10);
+        else if (!strcmp(argv[i], "--ir-trim") && i + 1 < argc) {
+            char* end = nullptr;
+            irShape.trimDb = strtof(argv[++i], &end);
+            if (*end == ':') irShape.preRoll = (uint32_t)strtoul(end + 1, nullptr, 10);
+        } else if (!strcmp(argv[i], "--ir-length") && i + 1 < argc) irShape.length = strtoull(argv[++i], nullptr, 10);
+        else if (!strcmp(argv[i], "--ir-reverse")) irShape.reverse = true;
+        else if (!strcmp(argv[i], "--ir-decay") && i + 1 < argc) irShape.decayT60 = strtoull(argv[++i], nullptr, 10);
+        else if (!strcmp(argv[i], "--ir-fade") && i + 1 < argc) irShape.fadeOut = strtoull(argv[++i], nullptr, 10);
+        else if (!strcmp(argv[i], "--ir-normalize") && i + 1 < argc) {
+            const char* a = argv[++i];
+            const char* colon = strchr(a, ':');
+            const size_t len = colon ? (size_t)(colon - a) : strlen(a);
+            if (len == 4 && !strncmp(a, "peak", 4)) irShape.normalize = Convolution::IrShape::Peak;
+            else if (len == 6 && !strncmp(a, "energy", 6)) irShape.normalize = Convolution::IrShape::Energy;
+            else {
+                std::cerr << "--ir-normalize takes peak or energy, optionally :TARGET" << std::endl;
+                return 2;
+            }
+            if (colon) irShape.target = strtof(colon + 1, nullptr);
+        }
     }
     if (rate || period) fakejack_configure(rate ? rate : 44100, period ? period : 256);
     selectGpu();
@@ -57,6 +82,7 @@ int main(int argc, char** argv) {
         auto* c = new Convolution(std::string("hipconv_") + char('1' + n), fs1);
         instances.push_back(c);
         if (matchIrRate) c->setMatchIrRate(true);
+        c->setIrShape(irShape);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;
             const auto deviceId = settings.str("conv[%d].cc.device", idx);

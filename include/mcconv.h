@@ -140,6 +140,50 @@ int mc_load_ir(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uin
  * mc_load_ir's frames are.  Equal rates are mc_load_ir.  Host pointer, same rules as mc_load_ir.  No reference equivalent. */
 int mc_load_ir_resampled(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
                          uint32_t session_rate);
+
+/* Shaping of an IR on load: what a convolution reverb does to an impulse response before it convolves.  No reference
+ * equivalent.  The engine-group interface (mcconv_group.h) has no counterpart: shaped loads are single-engine.
+ *
+ * Order of operations (lengths and positions are frames at the session's rate):
+ *   1. the whole IR is converted to the session's rate when the rates differ (as by the resampled load); F frames;
+ *   2. s0 = min(start, F); with trim_db < 0 the onset is the first frame m after s0 whose max(|L|, |R|) reaches
+ *      peak * 10^(trim_db / 20) (float arithmetic; peak over all frames after s0); first = s0 + max(0, onset - pre_roll);
+ *   3. n = min(F - first, length or unlimited, n_ref - nframes) frames are stored (n = 0: MC_ERR_ARG, nothing changes);
+ *      every later step acts on those n, so a fade ends at the last stored tap and a normalisation measures what sounds;
+ *   4. the n frames are reversed (MC_SHAPE_REVERSE);
+ *   5. tap m is multiplied by 10^(-3 m / decay_t60);
+ *   6. the last f = min(fade_out, n) taps by (1 + cos(pi (k + 1) / (f + 1))) / 2, k = 0 .. f - 1;
+ *   7. everything by gain = target / peak or target / energy of the result (1 when that measure is 0);
+ *   8. the taps are rounded to float and transformed as the plain load's are (steps 4-7 are carried in double). */
+#define MC_SHAPE_REVERSE 1u
+enum { MC_NORM_NONE = 0, MC_NORM_PEAK = 1, MC_NORM_ENERGY = 2 };
+typedef struct {
+    uint32_t struct_size;  /* sizeof(mc_ir_shape) */
+    uint32_t flags;        /* MC_SHAPE_REVERSE; unknown bits: MC_ERR_ARG */
+    uint64_t start;        /* frames skipped unconditionally at the front */
+    uint64_t length;       /* frames kept from the first kept frame; 0 = all */
+    uint64_t decay_t60;    /* 0 = off; else a further 60 dB of exponential decay at tap decay_t60 */
+    uint64_t fade_out;     /* raised-cosine fade over the last fade_out stored taps (clamped to the stored length) */
+    float trim_db;         /* [-120, 0]; 0 = no onset search; < 0: the threshold below the peak that marks the onset */
+    uint32_t pre_roll;     /* frames kept before the onset */
+    uint32_t normalize;    /* MC_NORM_* */
+    float target;          /* PEAK: max |tap| = target; ENERGY: sqrt(sum (hL^2 + hR^2) / 2) = target; finite, > 0 */
+} mc_ir_shape;
+
+/* everything off */
+void mc_default_ir_shape(mc_ir_shape *s);
+/* The plain load (ir_rate = session_rate = 0) or the resampled load (both rates in [8000, 384000]) with `shape` applied
+ * on the device between the conversion and the truncation.  The shape's fields and the rates are checked first, the
+ * pointers after them, all before the engine or the device is touched: a refused load (MC_ERR_ARG, the message names
+ * the field) leaves the engine as it was.  A shape with everything off is the plain or the resampled load itself, bit
+ * for bit, and leaves no shape information.  The tap count, the sums and the taps the engine reports for the IR are
+ * those of the shaped taps.  Two loads of the same frames with the same shape store the same bits. */
+int mc_load_ir_shaped(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
+                      uint32_t session_rate, const mc_ir_shape *shape);
+/* out = {frames at the session's rate before shaping, onset frame (counted from `start`), first kept frame, stored taps,
+ * gain applied, peak before the gain, energy before the gain, 0}; MC_ERR_STATE for an IR whose last load was not shaped */
+int mc_ir_shape_info(const mc_engine *e, uint64_t idx, double out[8]);
+
 int mc_num_irs(const mc_engine *e);
 /* out[0..3] = sum h_L, sum h_R, sum h_L(-1)^m, sum h_R(-1)^m of the truncated IR; out[4] = taps, out[5] = partitions */
 int mc_ir_info(const mc_engine *e, uint64_t idx, double out[6]);
