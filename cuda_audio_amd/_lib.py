@@ -18,7 +18,8 @@ MC_MAX_PREDELAY = 8192
 # every symbol include/mcconv.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "mc_abi_version", "mc_last_error", "mc_default_config", "mc_default_params", "mc_create", "mc_destroy",
-    "mc_reset", "mc_set_period", "mc_load_ir", "mc_load_ir_resampled", "mc_default_ir_shape", "mc_load_ir_shaped", "mc_ir_shape_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
+    "mc_reset", "mc_set_period", "mc_load_ir", "mc_load_ir_resampled", "mc_default_ir_shape", "mc_load_ir_shaped", "mc_ir_shape_info",
+    "mc_default_ir_eq", "mc_load_ir_eq", "mc_ir_eq_response", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
     "mc_enable_kernel_timing", "mc_get_kernel_stats", "mc_algorithmic_bytes_per_block", "mc_blocks_processed", "mc_preferred_batch",
@@ -82,6 +83,31 @@ class McIrShape(C.Structure):
     ]
 
 
+MC_EQ_MAX_BANDS = 8
+MC_EQ_OFF, MC_EQ_LOWCUT, MC_EQ_HIGHCUT, MC_EQ_LOWSHELF, MC_EQ_HIGHSHELF, MC_EQ_PEAK = range(6)
+
+
+class McEqBand(C.Structure):
+    """mc_eq_band: one biquad of the EQ mc_load_ir_eq applies to an IR."""
+
+    _fields_ = [
+        ("kind", C.c_uint32),
+        ("freq_hz", C.c_float),
+        ("gain_db", C.c_float),
+        ("q", C.c_float),
+    ]
+
+
+class McIrEq(C.Structure):
+    """mc_ir_eq: up to MC_EQ_MAX_BANDS bands, applied in index order."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("band", McEqBand * MC_EQ_MAX_BANDS),
+    ]
+
+
 class McKernelStats(C.Structure):
     _fields_ = [
         ("launches", C.c_uint64),
@@ -136,6 +162,10 @@ def load():
     L.mc_default_ir_shape.restype = None
     L.mc_load_ir_shaped.argtypes = [vp, u64, fp, u64, u64, C.c_uint32, C.c_uint32, C.POINTER(McIrShape)]
     L.mc_ir_shape_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_default_ir_eq.argtypes = [C.POINTER(McIrEq)]
+    L.mc_default_ir_eq.restype = None
+    L.mc_load_ir_eq.argtypes = [vp, u64, fp, u64, u64, C.c_uint32, C.c_uint32, C.POINTER(McIrShape), C.POINTER(McIrEq)]
+    L.mc_ir_eq_response.argtypes = [C.POINTER(McIrEq), C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double)]
     L.mc_num_irs.argtypes = [vp]
     L.mc_ir_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_set_params.argtypes = [vp, C.c_int, C.POINTER(McCcValue)]

@@ -113,6 +113,25 @@ __global__ __launch_bounds__(ISH_THREADS) void k_shape_onset(const float2* __res
     if (threadIdx.x == 0) part[blockIdx.x] = at;
 }
 
+// Tap m < n of the shaped IR before the gain (steps 3 to 6 of the header's order), in double: the one expression every kernel
+// that shapes goes through (k_shape_apply here, k_eq_fill in ireq.hip.h)
+__device__ inline void ish_tap(const float2* __restrict__ x, const IshPlan& pl, uint64_t m, double& L, double& R) {
+    const float2 v = x[pl.first + (pl.reverse ? pl.n - 1 - m : m)];
+    L = (double)v.x;
+    R = (double)v.y;
+    if (pl.t60) {
+        const double d = exp2(-((double)m * ISH_DECAY_K) / (double)pl.t60);
+        L *= d;
+        R *= d;
+    }
+    if (m >= pl.n - pl.fade) {
+        const double k = (double)(m - (pl.n - pl.fade));
+        const double f = 0.5 * (1.0 + cos(M_PI * (k + 1.0) / ((double)pl.fade + 1.0)));
+        L *= f;
+        R *= f;
+    }
+}
+
 // Tap m of the shaped IR, one per thread.  WRITE = false: part[2 b] = max |tap|, part[2 b + 1] = sum (L^2 + R^2) of workgroup
 // b, before the gain.  WRITE = true: y[m] = (float)(tap * gain), part[4 b ..] = the workgroup's share of sum h_L, sum h_R,
 // sum h_L (-1)^m, sum h_R (-1)^m of what it stored.
@@ -122,22 +141,7 @@ __global__ __launch_bounds__(ISH_THREADS) void k_shape_apply(const float2* __res
     __shared__ double red[ISH_WAVES];
     const uint64_t m = (uint64_t)blockIdx.x * ISH_THREADS + threadIdx.x;
     double L = 0.0, R = 0.0;
-    if (m < pl.n) {
-        const float2 v = x[pl.first + (pl.reverse ? pl.n - 1 - m : m)];
-        L = (double)v.x;
-        R = (double)v.y;
-        if (pl.t60) {
-            const double d = exp2(-((double)m * ISH_DECAY_K) / (double)pl.t60);
-            L *= d;
-            R *= d;
-        }
-        if (m >= pl.n - pl.fade) {
-            const double k = (double)(m - (pl.n - pl.fade));
-            const double f = 0.5 * (1.0 + cos(M_PI * (k + 1.0) / ((double)pl.fade + 1.0)));
-            L *= f;
-            R *= f;
-        }
-    }
+    if (m < pl.n) ish_tap(x, pl, m, L, R);
     const auto add = [](double p, double q) { return p + q; };
     if (WRITE) {
         float2 out = make_float2(0.f, 0.f);
@@ -178,11 +182,17 @@ inline bool ish_is_off(const mc_ir_shape& s) {
     return !s.flags && !s.start && s.trim_db == 0.f && !s.length && !s.decay_t60 && !s.fade_out && s.normalize == MC_NORM_NONE;
 }
 
+// ireq.hip.h: the bands of a load with EQ and what finishes such a load once the plan stands (steps 3 to 8 with 6b)
+struct IeqCascade;
+inline hipError_t ieq_finish(hipStream_t stream, const float2* d_x, const IshPlan& pl, const mc_ir_shape& sh, const IeqCascade& eq,
+                             float2** d_out, uint64_t* n_out, double sums[4], double info[8]);
+
 // Shapes the F device frames d_x (at the session's rate) into a new device buffer of n <= cap taps, *d_out, which the caller
 // owns.  sums = the four mc_ir_info sums of the stored taps, info = what mc_ir_shape_info reports.  Synchronises the stream.
-// *n_out == 0 (and no buffer) when the shape leaves no frame.
+// *n_out == 0 (and no buffer) when the shape leaves no frame.  eq = the bands of mc_load_ir_eq (null: none): the selection is
+// this function's, everything after it ieq_finish's.
 inline hipError_t ish_shape(hipStream_t stream, const float2* d_x, uint64_t F, uint64_t cap, const mc_ir_shape& sh, float2** d_out,
-                            uint64_t* n_out, double sums[4], double info[8]) {
+                            uint64_t* n_out, double sums[4], double info[8], const IeqCascade* eq = nullptr) {
     *d_out = nullptr;
     *n_out = 0;
     IshPlan pl;
@@ -225,6 +235,7 @@ inline hipError_t ish_shape(hipStream_t stream, const float2* d_x, uint64_t F, u
     pl.reverse = (sh.flags & MC_SHAPE_REVERSE) != 0;
     pl.t60 = sh.decay_t60;
     pl.fade = std::min<uint64_t>(sh.fade_out, pl.n);
+    if (eq) return ieq_finish(stream, d_x, pl, sh, *eq, d_out, n_out, sums, info);
 
     const unsigned grid = (unsigned)((pl.n + ISH_THREADS - 1) / ISH_THREADS);
     float2* d_y = nullptr;

@@ -27,6 +27,7 @@
 #include "singlefft.hip.h"
 #include "resample.hip.h"
 #include "irshape.hip.h"
+#include "ireq.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
 // mc_config or that the tests compare bit for bit:
@@ -95,7 +96,7 @@ struct IrEntry {
     uint64_t taps = 0;
     int P = 0;
     double sums[4] = {0, 0, 0, 0};
-    bool shaped = false;  // the last load was mc_load_ir_shaped with something on: shape_info is what mc_ir_shape_info reports
+    bool shaped = false;  // the last load was mc_load_ir_shaped with something on or mc_load_ir_eq with a band on: shape_info is what mc_ir_shape_info reports
     double shape_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
@@ -3270,13 +3271,13 @@ namespace {
 // The shaped load's own stage (irshape.hip.h): all `conv` frames at the session's rate on the device, shaped into a new buffer
 // of *n <= cap taps that the caller owns.  Nothing of the engine's IRs is touched here.
 int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, uint64_t cap, const uint32_t* rs, const mc_ir_shape& sh,
-                float2** d_taps, uint64_t* n, double sums[4], double info[8]) {
+                const IeqCascade* eq, float2** d_taps, uint64_t* n, double sums[4], double info[8]) {
     float2* d_x = nullptr;
     HIP_TRY(hipMalloc(&d_x, sizeof(float2) * conv));
     double unused[4];
     hipError_t er = rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, d_x, conv, unused)
                        : hipMemcpy(d_x, lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, sh, d_taps, n, sums, info);
+    if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, sh, d_taps, n, sums, info, eq);
     (void)hipFree(d_x);
     if (er != hipSuccess) return fail(MC_ERR_HIP, "IR shaping failed: %s", hipGetErrorString(er));
     if (!*n) return fail(MC_ERR_ARG, "the shape leaves no frame of the IR (start %llu, %llu frames at the session's rate)",
@@ -3286,8 +3287,10 @@ int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, u
 
 // mc_load_ir, mc_load_ir_resampled and mc_load_ir_shaped: rs = {IR rate, session rate} converts the frames on the device
 // (resample.hip.h) before anything else sees them; null = the frames as given (the reference).  sh = a shape with something
-// on, applied on the device after the conversion (irshape.hip.h); null = none
-int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs, const mc_ir_shape* sh = nullptr) {
+// on, applied on the device after the conversion (irshape.hip.h); null = none.  eq = the bands of mc_load_ir_eq that are on
+// (ireq.hip.h; with a shape, which may have everything off); null = none
+int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs, const mc_ir_shape* sh = nullptr,
+            const IeqCascade* eq = nullptr) {
     // Convolution::prepare, conv.cu:207-253
     if (!e || !lr) return fail(MC_ERR_ARG, "null argument");
     if (idx >= (uint64_t)kMaxIrs) return fail(MC_ERR_ARG, "IR index %llu >= %d", (unsigned long long)idx, kMaxIrs);
@@ -3303,7 +3306,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
         if (!rc && !e->sf) rc = leave_jack_path(e);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(e->stream));
-        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo);
+        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, eq, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo);
         if (rc) return rc;
     }
     if (e->sf) {
@@ -3440,6 +3443,39 @@ int mc_load_ir_shaped(mc_engine* e, uint64_t idx, const float* lr, uint64_t fram
         return convert ? mc_load_ir_resampled(e, idx, lr, frames, nframes, ir_rate, session_rate) : mc_load_ir(e, idx, lr, frames, nframes);
     const uint32_t rs[2] = {ir_rate, session_rate};
     return load_ir(e, idx, lr, frames, nframes, convert && ir_rate != session_rate ? rs : nullptr, shape);
+}
+
+void mc_default_ir_eq(mc_ir_eq* eq) {
+    if (!eq) return;
+    std::memset(eq, 0, sizeof(*eq));
+    eq->struct_size = (uint32_t)sizeof(*eq);
+    for (mc_eq_band& b : eq->band) b = mc_eq_band{MC_EQ_OFF, 1000.f, 0.f, 0.70710678f};
+}
+
+int mc_load_ir_eq(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
+                  const mc_ir_shape* shape, const mc_ir_eq* eq) {
+    // as in mc_load_ir_shaped, everything is checked before the pointers and before any HIP call
+    int on = 0;
+    if (const char* bad = ieq_check(eq, ir_rate, session_rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
+    mc_ir_shape off;
+    mc_default_ir_shape(&off);
+    if (!shape) shape = &off;
+    if (!on) return mc_load_ir_shaped(e, idx, lr, frames, nframes, ir_rate, session_rate, shape);
+    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
+    const IeqCascade cs = ieq_cascade(*eq, session_rate);
+    const uint32_t rs[2] = {ir_rate, session_rate};
+    return load_ir(e, idx, lr, frames, nframes, ir_rate != session_rate ? rs : nullptr, shape, &cs);
+}
+
+int mc_ir_eq_response(const mc_ir_eq* eq, uint32_t rate, const double* hz, uint32_t n, double* db) {
+    int on = 0;
+    if (const char* bad = ieq_check(eq, rate, rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
+    if (n && (!hz || !db)) return fail(MC_ERR_ARG, "null argument");
+    if (rate < RS_MIN_RATE || rate > RS_MAX_RATE) return fail(MC_ERR_ARG, "rate %u outside [%u, %u]", rate, RS_MIN_RATE, RS_MAX_RATE);
+    const IeqCascade cs = ieq_cascade(*eq, rate);
+    for (uint32_t i = 0; i < n; i++) db[i] = ieq_response_db(cs, rate, hz[i]);
+    return MC_OK;
 }
 
 int mc_ir_shape_info(const mc_engine* e, uint64_t idx, double out[8]) {

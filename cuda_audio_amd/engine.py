@@ -15,7 +15,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import MC_BLOCK, McCcValue, McConfig, McIrShape, McKernelStats, check
+from ._lib import MC_BLOCK, McCcValue, McConfig, McIrEq, McIrShape, McKernelStats, check
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
 CONV_MAX_SPEED = 1024             # conv.h:22-24
@@ -56,6 +56,44 @@ class IrShape:
         s.start, s.trim_db, s.pre_roll, s.length = int(self.start), float(self.trim_db), int(self.pre_roll), int(self.length)
         s.decay_t60, s.fade_out, s.normalize, s.target = int(self.decay_t60), int(self.fade_out), norm[self.normalize], float(self.target)
         return s
+
+
+@dataclasses.dataclass
+class IrEq:
+    """What prepare(eq=...) filters an IR with after shaping and before the normalisation (mc_ir_eq, include/mcconv.h): up to
+    8 bands in order, each `(kind, hz[, gain_db[, q]])` with kind one of "off", "lowcut", "highcut", "lowshelf", "highshelf",
+    "peak"; gain_db defaults to 0 (the cuts ignore it), q to 0.70710678."""
+
+    bands: list = dataclasses.field(default_factory=list)
+
+    KINDS = {"off": _lib.MC_EQ_OFF, "lowcut": _lib.MC_EQ_LOWCUT, "highcut": _lib.MC_EQ_HIGHCUT, "lowshelf": _lib.MC_EQ_LOWSHELF,
+             "highshelf": _lib.MC_EQ_HIGHSHELF, "peak": _lib.MC_EQ_PEAK}
+
+    def to_c(self):
+        if len(self.bands) > _lib.MC_EQ_MAX_BANDS:
+            raise ValueError(f"{len(self.bands)} bands; at most {_lib.MC_EQ_MAX_BANDS}")
+        eq = McIrEq()
+        _lib.load().mc_default_ir_eq(C.byref(eq))
+        for b, band in zip(eq.band, self.bands):
+            kind, hz, *rest = band
+            if kind not in self.KINDS or len(rest) > 2:
+                raise ValueError(f"a band is (kind, hz[, gain_db[, q]]) with kind in {sorted(self.KINDS)}, not {band!r}")
+            b.kind, b.freq_hz = self.KINDS[kind], float(hz)
+            if len(rest) > 0:
+                b.gain_db = float(rest[0])
+            if len(rest) > 1:
+                b.q = float(rest[1])
+        return eq
+
+
+def eq_response(eq, rate, hz):
+    """|H| in dB of the bands of `eq` (an IrEq) at the frequencies hz (Hz) in a session at `rate` Hz: mc_ir_eq_response, host
+    arithmetic only."""
+    hz = np.ascontiguousarray(hz, dtype=np.float64).reshape(-1)
+    db = np.empty_like(hz)
+    dp = C.POINTER(C.c_double)
+    check(_lib.load().mc_ir_eq_response(C.byref(eq.to_c()), int(rate), hz.ctypes.data_as(dp), hz.size, db.ctypes.data_as(dp)))
+    return db
 
 
 class _CCValueView:
@@ -154,16 +192,23 @@ class Convolution:
         check(self._L.mc_set_period(self._h, nframes))
 
     # -- reference surface ----------------------------------------------------
-    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None):
+    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None):
         """Convolution::prepare (conv.cu:207-253).  `wav` is float32 [frames, 2]
         (what WavFile.buffer holds) or an object with a `.buffer` of that shape.
         ir_rate (Hz; default: `wav.sampleRate` when it has one): when both it and the engine's sample_rate are known and
         differ, the IR is converted to the session's rate on the device (mc_load_ir_resampled).
         shape (an IrShape): trim, reverse, decay, fade and normalise the IR on the device, after the conversion and before
-        the truncation (mc_load_ir_shaped); ir_shape_info(idx) then tells what was done."""
+        the truncation (mc_load_ir_shaped); ir_shape_info(idx) then tells what was done.
+        eq (an IrEq): filter the shaped taps with its bands before the normalisation (mc_load_ir_eq); the engine needs a
+        sample_rate, and ir_rate defaults to it."""
         lr = _f32(getattr(wav, "buffer", wav)).reshape(-1, 2)
         if ir_rate is None:
             ir_rate = getattr(wav, "sampleRate", None)
+        if eq is not None:
+            session = int(self.sample_rate or 0)
+            check(self._L.mc_load_ir_eq(self._h, idx, _fp(lr), lr.shape[0], nframes, session if ir_rate is None else int(ir_rate), session,
+                                        C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c())))
+            return
         convert = ir_rate is not None and self.sample_rate is not None and int(ir_rate) != int(self.sample_rate)
         if shape is not None:
             rates = (int(ir_rate), int(self.sample_rate)) if convert else (0, 0)
@@ -277,10 +322,12 @@ class Convolution:
         return dict(sigma=(out[0], out[1]), alpha=(out[2], out[3]), taps=int(out[4]), partitions=int(out[5]))
 
     def ir_shape_info(self, idx):
-        """What the shaped load of IR idx did (mc_ir_shape_info); McError -3 for an IR that was not loaded with a shape."""
+        """What the shaped load of IR idx did (mc_ir_shape_info); McError -3 for an IR that was not loaded with a shape.  After a
+        load with EQ bands gain, peak and energy are those of the equalised taps and eq_bands counts the bands."""
         out = (C.c_double * 8)()
         check(self._L.mc_ir_shape_info(self._h, idx, out))
-        return dict(frames=int(out[0]), onset=int(out[1]), first=int(out[2]), taps=int(out[3]), gain=out[4], peak=out[5], energy=out[6])
+        return dict(frames=int(out[0]), onset=int(out[1]), first=int(out[2]), taps=int(out[3]), gain=out[4], peak=out[5], energy=out[6],
+                    eq_bands=int(out[7]))
 
     def enable_kernel_timing(self, on=True):
         check(self._L.mc_enable_kernel_timing(self._h, 1 if on else 0))

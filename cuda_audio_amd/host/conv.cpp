@@ -22,6 +22,10 @@ int mc_load_ir_resampled(mc_engine*, uint64_t, const float*, uint64_t, uint64_t,
 void mc_default_ir_shape(mc_ir_shape*) __attribute__((weak));
 int mc_load_ir_shaped(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*) __attribute__((weak));
 int mc_ir_shape_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+// (... and no EQ)
+void mc_default_ir_eq(mc_ir_eq*) __attribute__((weak));
+int mc_load_ir_eq(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*) __attribute__((weak));
+int mc_ir_eq_response(const mc_ir_eq*, uint32_t, const double*, uint32_t, double*) __attribute__((weak));
 }
 
 namespace {
@@ -99,10 +103,27 @@ void Convolution::setIrShape(const IrShape& shape) {
     _irShape = shape;
 }
 
-// irRate = sessionRate = 0: the frames are loaded at the rate they have
-void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape) {
+void Convolution::setIrEq(const IrEq& eq) {
+    if (!eq.off() && _group) {
+        Log::error("conv", "IR equalisation is not available with several devices (mc_group_load_ir takes no bands)");
+        std::exit(2);
+    }
+    if (eq.bands.size() > MC_EQ_MAX_BANDS) {
+        Log::error("conv", "%zu EQ bands, at most %d", eq.bands.size(), MC_EQ_MAX_BANDS);
+        std::exit(2);
+    }
+    _irEq = eq;
+}
+
+// irRate = sessionRate = 0: the frames are loaded at the rate they have (never with a band of eq on)
+void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
+                             const IrEq& eq) {
     if (!mc_load_ir_shaped || !mc_default_ir_shape || !mc_ir_shape_info) {
         Log::error("conv", "the engine has no IR shaping (mc_load_ir_shaped)");
+        std::exit(2);
+    }
+    if (!eq.off() && (!mc_load_ir_eq || !mc_default_ir_eq || !mc_ir_eq_response)) {
+        Log::error("conv", "the engine has no IR equalisation (mc_load_ir_eq)");
         std::exit(2);
     }
     mc_ir_shape s;
@@ -116,18 +137,35 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
     s.fade_out = shape.fadeOut;
     s.normalize = (uint32_t)shape.normalize;
     s.target = shape.target;
-    if (irRate) Log::info(name, "IR %zu: %u Hz -> %u Hz", idx, irRate, sessionRate);
-    check(mc_load_ir_shaped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s), "mc_load_ir_shaped");
+    if (irRate && irRate != sessionRate) Log::info(name, "IR %zu: %u Hz -> %u Hz", idx, irRate, sessionRate);
+    mc_ir_eq q;
+    if (eq.off())
+        check(mc_load_ir_shaped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s), "mc_load_ir_shaped");
+    else {
+        mc_default_ir_eq(&q);
+        for (size_t k = 0; k < eq.bands.size(); k++) q.band[k] = mc_eq_band{(uint32_t)eq.bands[k].kind, eq.bands[k].hz, eq.bands[k].gainDb, eq.bands[k].q};
+        check(mc_load_ir_eq(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, &q), "mc_load_ir_eq");
+    }
     double info[8];
     check(mc_ir_shape_info(_engine, idx, info), "mc_ir_shape_info");
     Log::info(name, "IR %zu shaped: onset %llu, first kept frame %llu, %llu taps, gain %+.2f dB", idx, (unsigned long long)info[1],
               (unsigned long long)info[2], (unsigned long long)info[3], 20.0 * std::log10(info[4]));
+    if (!eq.off()) {
+        const double hz = 1000.0;
+        double db = 0.0;
+        check(mc_ir_eq_response(&q, sessionRate, &hz, 1, &db), "mc_ir_eq_response");
+        Log::info(name, "IR %zu equalised: %d bands, %+.2f dB at 1 kHz", idx, (int)info[7], db);
+    }
 }
 
 void Convolution::loadPendingIrs() {
     for (const PendingIr& p : _pendingIrs) {
         const uint64_t frames = p.lr.size() / 2;
-        const bool convert = p.rate && p.rate != samplerate;
+        const bool convert = p.match && p.rate && p.rate != samplerate;
+        if (!p.eq.off()) {  // (the bands are laid out at the client's rate; frames that are not converted count as being at it)
+            loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : (unsigned)samplerate, (unsigned)samplerate, p.shape, p.eq);
+            continue;
+        }
         if (!p.shape.off()) {
             loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : 0, convert ? (unsigned)samplerate : 0, p.shape);
             continue;
@@ -147,9 +185,9 @@ void Convolution::loadPendingIrs() {
 }
 
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
-    if (_matchIrRate) {
+    if (_matchIrRate || !_irEq.off()) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
-        _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape});
+        _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate});
         if (idx + 1 > _nirs) _nirs = idx + 1;
         return;
     }

@@ -87,6 +87,23 @@ public:
     // One log line per shaped IR (onset, first kept frame, stored taps, gain).  Single device only: with several devices
     // a shape with anything on reports an error and exits.
     void setIrShape(const IrShape& shape);
+    // The EQ every IR prepared from now on is filtered with on load, after its shape and before the normalisation (mc_ir_eq of
+    // include/mcconv.h; no reference equivalent): up to 8 bands in order.  The bands need the client's sample rate, so
+    // prepare() keeps the frames and onStart() loads them, as with setMatchIrRate; without it the frames count as being at the
+    // client's rate.  One more log line per IR (bands, gain at 1 kHz).  Single device only, as setIrShape.
+    struct IrEq {
+        struct Band {
+            enum Kind { Off = 0, LowCut, HighCut, LowShelf, HighShelf, Peak } kind = Off;
+            float hz = 1000.0f, gainDb = 0.0f, q = 0.70710678f;
+        };
+        std::vector<Band> bands;
+        bool off() const {
+            for (const Band& b : bands)
+                if (b.kind != Band::Off) return false;
+            return true;
+        }
+    };
+    void setIrEq(const IrEq& eq);
 
     void onMidiMessage(const RawMidi::Device* sender, const uint8_t* buffer, size_t len) override;
 
@@ -108,11 +125,15 @@ private:
         unsigned rate;
         std::vector<float> lr;  // interleaved L, R frames
         IrShape shape;          // as set when the IR was prepared
+        IrEq eq;
+        bool match;             // setMatchIrRate was on
     };
     std::vector<PendingIr> _pendingIrs;  // (rate matching) prepared, loaded by onStart()
     void loadPendingIrs();
     IrShape _irShape;
-    void loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape);
+    IrEq _irEq;
+    void loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
+                    const IrEq& eq = IrEq());
     void pushParams();
     void pullVsteps();
 };

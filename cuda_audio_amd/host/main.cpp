@@ -11,7 +11,9 @@
 // given; --match-ir-rate: every IR is converted to the client's sample rate on load, Convolution::setMatchIrRate;
 // --ir-start N, --ir-trim DB[:PREROLL], --ir-length N, --ir-reverse, --ir-decay N, --ir-fade N,
 // --ir-normalize peak|energy[:TARGET]: every IR is shaped on load, Convolution::setIrShape - lengths in frames at the rate
-// the IR is loaded at).
+// the IR is loaded at; --ir-eq KIND:HZ[:DB][:Q], up to 8 times, KIND one of lowcut, highcut, lowshelf, highshelf, peak (the cuts:
+// KIND:HZ[:Q]): every IR is equalised on load with these bands in this order, at the client's sample rate,
+// Convolution::setIrEq).
 #include <cassert>
 #include <cstdlib>
 #include <cstring>
@@ -33,6 +35,7 @@ int main(int argc, char** argv) {
     jack_nframes_t rate = 0, period = 0;  // fake JACK server: 0 = its defaults (44100 Hz, 256 frames)
     bool matchIrRate = false;
     Convolution::IrShape irShape;
+    Convolution::IrEq irEq;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--periods") && i + 1 < argc) periods = strtoull(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "--settings") && i + 1 < argc) settingsPath = argv[++i];
@@ -62,6 +65,25 @@ int main(int argc, char** argv) {
                 return 2;
             }
             if (colon) irShape.target = strtof(colon + 1, nullptr);
+        } else if (!strcmp(argv[i], "--ir-eq") && i + 1 < argc) {
+            using Band = Convolution::IrEq::Band;
+            static const struct { const char* name; Band::Kind kind; } kinds[] = {
+                {"lowcut", Band::LowCut}, {"highcut", Band::HighCut}, {"lowshelf", Band::LowShelf}, {"highshelf", Band::HighShelf}, {"peak", Band::Peak}};
+            const char* a = argv[++i];
+            const char* colon = strchr(a, ':');
+            Band b;
+            for (auto& k : kinds)
+                if (colon && strlen(k.name) == (size_t)(colon - a) && !strncmp(a, k.name, colon - a)) b.kind = k.kind;
+            if (b.kind == Band::Off || irEq.bands.size() == 8) {
+                std::cerr << "--ir-eq takes lowcut|highcut:HZ[:Q] or lowshelf|highshelf|peak:HZ[:DB][:Q], at most 8 times" << std::endl;
+                return 2;
+            }
+            char* end = nullptr;
+            b.hz = strtof(colon + 1, &end);
+            const bool cut = b.kind == Band::LowCut || b.kind == Band::HighCut;
+            if (*end == ':' && !cut) b.gainDb = strtof(end + 1, &end);
+            if (*end == ':') b.q = strtof(end + 1, &end);
+            irEq.bands.push_back(b);
         }
     }
     if (rate || period) fakejack_configure(rate ? rate : 44100, period ? period : 256);
@@ -83,6 +105,7 @@ int main(int argc, char** argv) {
         instances.push_back(c);
         if (matchIrRate) c->setMatchIrRate(true);
         c->setIrShape(irShape);
+        c->setIrEq(irEq);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;
             const auto deviceId = settings.str("conv[%d].cc.device", idx);

@@ -153,6 +153,7 @@ int mc_load_ir_resampled(mc_engine *e, uint64_t idx, const float *lr, uint64_t f
  *   4. the n frames are reversed (MC_SHAPE_REVERSE);
  *   5. tap m is multiplied by 10^(-3 m / decay_t60);
  *   6. the last f = min(fade_out, n) taps by (1 + cos(pi (k + 1) / (f + 1))) / 2, k = 0 .. f - 1;
+ *   6b. (mc_load_ir_eq only) the n taps run through the EQ bands, from rest at tap 0;
  *   7. everything by gain = target / peak or target / energy of the result (1 when that measure is 0);
  *   8. the taps are rounded to float and transformed as the plain load's are (steps 4-7 are carried in double). */
 #define MC_SHAPE_REVERSE 1u
@@ -181,8 +182,58 @@ void mc_default_ir_shape(mc_ir_shape *s);
 int mc_load_ir_shaped(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
                       uint32_t session_rate, const mc_ir_shape *shape);
 /* out = {frames at the session's rate before shaping, onset frame (counted from `start`), first kept frame, stored taps,
- * gain applied, peak before the gain, energy before the gain, 0}; MC_ERR_STATE for an IR whose last load was not shaped */
+ * gain applied, peak before the gain, energy before the gain, EQ bands applied (mc_load_ir_eq; else 0)}; MC_ERR_STATE for an IR whose last load was not shaped */
 int mc_ir_shape_info(const mc_engine *e, uint64_t idx, double out[8]);
+
+/* Equalisation of an IR on load: the EQ a convolution reverb has on its wet signal, applied to the impulse response once
+ * (the wet path is linear), so that the period and batch paths pay nothing.  No reference equivalent; single-engine, as
+ * shaping is.
+ *
+ * Up to MC_EQ_MAX_BANDS bands in index order; MC_EQ_OFF bands are skipped and their other fields ignored.  Each band is
+ * one biquad H(z) = (b0 + b1 z^-1 + b2 z^-2) / (a0 + a1 z^-1 + a2 z^-2) with the Audio-EQ-Cookbook (R. Bristow-Johnson)
+ * coefficients, computed in double from the float fields: w0 = 2 pi freq_hz / session_rate, c = cos w0,
+ * al = sin w0 / (2 q), A = 10^(gain_db / 40), r = 2 sqrt(A) al:
+ *   LOWCUT    (2nd-order high-pass)  b = {(1 + c) / 2, -(1 + c), (1 + c) / 2}          a = {1 + al, -2 c, 1 - al}
+ *   HIGHCUT   (2nd-order low-pass)   b = {(1 - c) / 2,   1 - c,  (1 - c) / 2}          a = {1 + al, -2 c, 1 - al}
+ *   LOWSHELF   b = {A ((A + 1) - (A - 1) c + r),  2 A ((A - 1) - (A + 1) c), A ((A + 1) - (A - 1) c - r)}
+ *              a = {   (A + 1) + (A - 1) c + r,    -2 ((A - 1) + (A + 1) c),    (A + 1) + (A - 1) c - r}
+ *   HIGHSHELF  b = {A ((A + 1) + (A - 1) c + r), -2 A ((A - 1) + (A + 1) c), A ((A + 1) + (A - 1) c - r)}
+ *              a = {   (A + 1) - (A - 1) c + r,     2 ((A - 1) - (A + 1) c),    (A + 1) - (A - 1) c - r}
+ *   PEAK       b = {1 + al A, -2 c, 1 - al A}                                          a = {1 + al / A, -2 c, 1 - al / A}
+ * all divided by a0.  The cuts ignore gain_db.
+ *
+ * EQ is step 6b of the order of operations above, after the fade (6) and before the normalisation (7): the peak, the
+ * energy and the gain that are measured and reported are those of the equalised taps.  The filter starts at rest at stored
+ * tap 0 and runs over the n stored taps in double through the whole cascade; its ringing past tap n - 1 is dropped (n
+ * does not change); the rounding to float is step 8's. */
+#define MC_EQ_MAX_BANDS 8
+enum { MC_EQ_OFF = 0, MC_EQ_LOWCUT, MC_EQ_HIGHCUT, MC_EQ_LOWSHELF, MC_EQ_HIGHSHELF, MC_EQ_PEAK };
+typedef struct {
+    uint32_t kind;   /* MC_EQ_*; anything above MC_EQ_PEAK: MC_ERR_ARG */
+    float freq_hz;   /* corner / centre frequency, [10, 0.45 session_rate] */
+    float gain_db;   /* shelves and peak: [-36, 24]; the cuts do not look at it */
+    float q;         /* [0.1, 32] */
+} mc_eq_band;
+typedef struct {
+    uint32_t struct_size;  /* sizeof(mc_ir_eq) */
+    uint32_t reserved;
+    mc_eq_band band[MC_EQ_MAX_BANDS];
+} mc_ir_eq;
+
+/* every band MC_EQ_OFF, freq_hz = 1000, gain_db = 0, q = 0.70710678 */
+void mc_default_ir_eq(mc_ir_eq *eq);
+/* mc_load_ir_shaped (shape = NULL: everything off) with `eq` applied as step 6b.  Everything is checked before the engine or
+ * the device is touched (MC_ERR_ARG, the message names the field, the engine stays as it was): struct_size, every kind, and
+ * with a band on session_rate and ir_rate (both in [8000, 384000]; equal rates mean no conversion, 0 / 0 is refused because
+ * the bands need the session's rate) and the on bands' freq_hz, q and gain_db; a non-null shape as by mc_load_ir_shaped.
+ * With no band on the call is mc_load_ir_shaped itself (and so, with the shape off too, the plain or the resampled load),
+ * bit for bit.  A load with a band on counts as shaped: mc_ir_shape_info reports it, out[7] holds the number of bands
+ * applied, gain, peak and energy are those of the equalised taps.  The same frames, shape and bands store the same bits. */
+int mc_load_ir_eq(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
+                  uint32_t session_rate, const mc_ir_shape *shape, const mc_ir_eq *eq);
+/* db[i] = 20 log10 |H(e^{j 2 pi hz[i] / rate})| of the cascade (0 with no band on).  Host arithmetic only: no engine, no HIP
+ * call.  `eq` is checked as by mc_load_ir_eq with session_rate = rate. */
+int mc_ir_eq_response(const mc_ir_eq *eq, uint32_t rate, const double *hz, uint32_t n, double *db);
 
 int mc_num_irs(const mc_engine *e);
 /* out[0..3] = sum h_L, sum h_R, sum h_L(-1)^m, sum h_R(-1)^m of the truncated IR; out[4] = taps, out[5] = partitions */
