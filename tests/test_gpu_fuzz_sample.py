@@ -23,11 +23,14 @@ def _run(script, *args, env=None):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("args", [(5002, 1, "general"), (5106, 1, "general"), (5143, 1, "general"), (1, 4), (5000, 6, "general"),
-                                  (70000, 2, "jack"), (80000, 1, "jack512"), (20001, 2, "long")],
-                         ids=["unequal_irs_in_a_voice", "period1024_a", "period1024_b", "q8", "general", "jack", "jack512", "long_batches"])
+                                  (70000, 2, "jack"), (80000, 1, "jack512"), (20001, 2, "long"), (40001, 2, "os")],
+                         ids=["unequal_irs_in_a_voice", "period1024_a", "period1024_b", "q8", "general", "jack", "jack512", "long_batches",
+                              "overlap_save"])
 def test_randomised_runs_against_the_oracle(gpu_lib, args):
     out = _run("fuzz_q8.py", *args)
     assert f"{args[1]} runs, 0 above" in out, out[-800:]
+    if args[2:] == ("os",):  # the form ran: the totals on the last line count the batches that took it
+        assert "'batches': 0" not in out.strip().splitlines()[-1], out[-800:]
 
 
 @pytest.mark.gpu

@@ -10,9 +10,9 @@ import numpy as np
 import pytest
 
 import ir_eq_np
-from helpers import BASE, RMS_TOL, apply_params, rms
+from helpers import BASE, RMS_TOL, _dry, apply_params, rms
 from ir_shape_np import assert_onset_margin, quiet_lead_ir, session_frames, shape
-from test_gpu_ir_shape import (COMBINED_A, FP16_REL_TOL, OS_P, P0, P1, _check_info, _check_level, _check_taps, _dry, _os_want,
+from test_gpu_ir_shape import (COMBINED_A, FP16_REL_TOL, OS_P, P0, P1, _check_info, _check_level, _check_taps, _os_want,
                                _settled_batches)
 
 pytestmark = pytest.mark.gpu

@@ -7,7 +7,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import BASE, RMS_TOL, apply_params, rms
+from helpers import BASE, RMS_TOL, _dry, apply_params, rms
 from ir_shape_np import assert_onset_margin, quiet_lead_ir, session_frames, shape
 
 pytestmark = pytest.mark.gpu
@@ -68,16 +68,6 @@ def _check_info(got, want):
         assert got[k] == want[k], k
     for k in ("gain", "peak", "energy"):
         assert abs(got[k] - want[k]) <= 1e-6 * abs(want[k]), k
-
-
-def _dry(x, p0, p1):
-    """The dry part of the reference's output (conv.cu:386-387, 440-449) for inputs x [2, n]: [2, n]."""
-    pl = lambda p: 1 - p if p >= 0 else 1.0
-    pr = lambda p: 1 + p if p <= 0 else 1.0
-    dl = [p["dry"] * pl(p["panDry"]) * p["level"] for p in (p0, p1)]
-    dr = [p["dry"] * pr(p["panDry"]) * p["level"] for p in (p0, p1)]
-    x = x.astype(np.float64)
-    return np.stack([x[0] * dl[0] + x[1] * dl[1], x[0] * dr[0] + x[1] * dr[1]])
 
 
 def _check_level(want, x, p0, p1):
