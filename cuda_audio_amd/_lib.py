@@ -19,7 +19,7 @@ MC_MAX_PREDELAY = 8192
 SYMBOLS = [
     "mc_abi_version", "mc_last_error", "mc_default_config", "mc_default_params", "mc_create", "mc_destroy",
     "mc_reset", "mc_set_period", "mc_load_ir", "mc_load_ir_resampled", "mc_default_ir_shape", "mc_load_ir_shaped", "mc_ir_shape_info",
-    "mc_default_ir_eq", "mc_load_ir_eq", "mc_ir_eq_response", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
+    "mc_default_ir_eq", "mc_load_ir_eq", "mc_ir_eq_response", "mc_default_decay_query", "mc_ir_decay", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
     "mc_enable_kernel_timing", "mc_get_kernel_stats", "mc_algorithmic_bytes_per_block", "mc_blocks_processed", "mc_preferred_batch",
@@ -108,6 +108,25 @@ class McIrEq(C.Structure):
     ]
 
 
+MC_DECAY_MAX_BANDS = 10
+MC_DECAY_MAX_CURVE = 1024
+
+
+class McDecayQuery(C.Structure):
+    """mc_decay_query: what mc_ir_decay measures of a loaded IR."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("rate", C.c_uint32),
+        ("n_bands", C.c_uint32),
+        ("curve_points", C.c_uint32),
+        ("centre_hz", C.c_float * MC_DECAY_MAX_BANDS),
+        ("q", C.c_float),
+        ("onset_db", C.c_float),
+        ("end", C.c_uint64),
+    ]
+
+
 class McKernelStats(C.Structure):
     _fields_ = [
         ("launches", C.c_uint64),
@@ -166,6 +185,9 @@ def load():
     L.mc_default_ir_eq.restype = None
     L.mc_load_ir_eq.argtypes = [vp, u64, fp, u64, u64, C.c_uint32, C.c_uint32, C.POINTER(McIrShape), C.POINTER(McIrEq)]
     L.mc_ir_eq_response.argtypes = [C.POINTER(McIrEq), C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double)]
+    L.mc_default_decay_query.argtypes = [C.POINTER(McDecayQuery)]
+    L.mc_default_decay_query.restype = None
+    L.mc_ir_decay.argtypes = [vp, u64, C.POINTER(McDecayQuery), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64)]
     L.mc_num_irs.argtypes = [vp]
     L.mc_ir_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_set_params.argtypes = [vp, C.c_int, C.POINTER(McCcValue)]

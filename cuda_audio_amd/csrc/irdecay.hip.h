@@ -1,0 +1,426 @@
+// irdecay.hip.h — the decay of a loaded impulse response, measured on the device (mc_ir_decay): energy decay curve, EDT,
+// T20, T30, C50, C80, D50 and centre time, broadband and in up to MC_DECAY_MAX_BANDS band-passed rows.  No reference
+// equivalent.  include/mcconv.h and DESIGN.md 2.9 hold the definition; tests/ir_decay_np.py states it in float64.
+//
+// The stored taps x [n] (float2, what the engine convolves with) are only read.  With N = end ? min(end, n) : n:
+//   origin  o = the onset of irshape.hip.h (k_shape_peak, k_shape_onset over taps [0, N)) or 0;
+//   per row group (broadband, then one per band):
+//     fill    buf[m] = (double) x[m], m < N (k_dec_fill);
+//     filter  a band's two identical sections run over buf in place through ireq.hip.h's chunked recurrence, unchanged:
+//             k_eq_chunk (nxt = section), k_eq_carry, k_eq_chunk (cur = nxt = section: the first section's fix-up is the
+//             second's local pass), k_eq_carry, k_eq_chunk (cur = section);
+//     sum     buf[m] = EDC[m] = sum over k in [max(m, o), N) of (yL[k]^2, yR[k]^2), the backward running sum (below);
+//     read    k_dec_pick gathers EDC at o, N - 1, k50, k80 and the curve's points; k_dec_members reduces, for the three
+//             channel sets and the three fit ranges, how many taps lie in the range and the first of them, and sum EDC[m]
+//             over m in (o, N) (= sum (m - o) e[m] by parts: the centre time without a second pass over e);
+//             k_dec_fit reduces sum x, sum y, sum x^2, sum x y over each range with x counted from the range's first tap.
+//   The host turns those into the eight numbers of a row and the curve (dec_row).
+//
+// The backward sum.  The taps are cut into chunks of IEQ_CHUNK, a function of N alone; a lane owns one (chunk, channel) and
+// walks it from its last tap to its first, one addition per tap in a fixed order.
+//   totals  k_dec_sum<false> keeps the sum of every chunk;
+//   carry   k_dec_carry replaces total c by the sum of the totals behind it, tot[c] = tot'[c + 1] + total[c + 1], one chain of
+//           additions per channel from the last chunk to the first (one workgroup, the totals staged through LDS DEC_CARRY_TILE
+//           chunks at a time, lanes 0 and 1 add);
+//   write   k_dec_sum<true> walks every chunk again and writes carry + running sum over the tap.
+// A chunk's running sum starts from zero in both walks, so the value at its first tap is carry + total exactly, which is the
+// carry of the chunk before: across a run of zero taps (a quiet lead, a band's output before the first sample) EDC stays
+// bit for bit level, chunk borders included, as a sequential sum does.  L[o] = 10 log10(EDC[o] / EDC[o]) is 0 exactly.
+//
+// Memory.  As in ireq.hip.h a workgroup (128 lanes: 64 chunks x 2 channels) stages IEQ_TILE taps of each of its chunks
+// through LDS, 16 consecutive lanes moving one chunk's 256 contiguous bytes, the next tile's loads in flight under the current
+// tile's additions; rows are padded to IEQ_ROW so that the lanes' own reads do not conflict.  The map kernels read buf one
+// double2 per lane, consecutively.
+//
+// Determinism.  Chunks, grids and the carry's order depend on N alone; no atomics; every reduction ends in one partial per
+// workgroup, combined on the host in index order.  The same query on the same taps gives the same bits.
+//
+// Scratch (double2 [N], the chunk states, the partials) is allocated by the call and freed before it returns: an engine
+// nobody asks holds nothing.
+#pragma once
+#include <limits>
+
+#include "ireq.hip.h"
+
+constexpr int DEC_CARRY_TILE = 2048;     // chunks of the carry pass in LDS at a time (x 2 channels x 8 bytes = 32 KiB)
+constexpr int DEC_CARRY_THREADS = 256;
+constexpr unsigned DEC_GRID = 512;       // workgroups of the member and fit reductions, at most
+constexpr int DEC_SETS = 3, DEC_RANGES = 3, DEC_FITS = DEC_SETS * DEC_RANGES;
+constexpr int DEC_MEMBER_PART = 2 * DEC_FITS + 2;  // per workgroup: 9 counts, 9 first taps, sum EDC_L, sum EDC_R
+constexpr int DEC_FIT_PART = 4 * DEC_FITS;         // per workgroup: sum x, sum y, sum x^2, sum x y of each fit
+constexpr int DEC_PICK_HEAD = 4;                   // k_dec_pick: EDC at o, N - 1, k50, k80, then the curve's points
+constexpr double DEC_MIN_ONSET_DB = -120.0, DEC_CURVE_FLOOR = -400.0;
+constexpr uint32_t DEC_MIN_RATE = 8000, DEC_MAX_RATE = 384000;
+// (hi, lo) dB of EDT, T20, T30
+constexpr double DEC_HI[DEC_RANGES] = {0.0, -5.0, -5.0}, DEC_LO[DEC_RANGES] = {-10.0, -25.0, -35.0};
+
+struct DecLevels {
+    double E[DEC_SETS];            // EDC[o] of L, R and L + R
+    uint64_t first[DEC_FITS];      // (k_dec_fit) the first tap of fit 3 set + range
+};
+
+// buf[m] = tap m as double
+__global__ __launch_bounds__(ISH_THREADS) void k_dec_fill(const float2* __restrict__ x, uint64_t n, double2* __restrict__ buf) {
+    const uint64_t m = (uint64_t)blockIdx.x * ISH_THREADS + threadIdx.x;
+    if (m >= n) return;
+    const float2 v = x[m];
+    buf[m] = make_double2((double)v.x, (double)v.y);
+}
+
+// One backward walk over buf [n] (the file's head), k_eq_chunk's workgroup and staging.  tot: double [gridDim.x * IEQ_THREADS],
+// entry 2 * chunk + channel.  WRITE = false: tot = the sum of y^2 over the chunk's taps in [o, n).  WRITE = true: tap m of buf
+// becomes tot + the sum of y^2 over the chunk's taps in [max(m, o), n).  Taps at and past n read as zero and are not written.
+template <bool WRITE>
+__global__ __launch_bounds__(IEQ_THREADS) void k_dec_sum(double2* __restrict__ buf, uint64_t o, uint64_t n, double* __restrict__ tot) {
+    __shared__ double2 tile[IEQ_WG_CHUNKS * IEQ_ROW];
+    constexpr int PHASES = IEQ_CHUNK / IEQ_TILE;
+    const int t = threadIdx.x, c = t >> 1, ch = t & 1;
+    const uint64_t base = (uint64_t)blockIdx.x * IEQ_SPAN;
+    const uint64_t entry = (uint64_t)blockIdx.x * IEQ_THREADS + t;
+    const uint64_t mine = base + (uint64_t)c * IEQ_CHUNK;  // the lane's chunk starts here
+    const double carry = WRITE ? tot[entry] : 0.0;
+    double s = 0.0;
+    // element j of the lane's share of a tile: chunk i / IEQ_TILE, tap i % IEQ_TILE of it, i = t + j IEQ_THREADS
+    double2 pre[IEQ_PER];
+    const auto fetch = [&](int ph) {
+#pragma unroll
+        for (int j = 0; j < IEQ_PER; j++) {
+            const int i = t + j * IEQ_THREADS;
+            const uint64_t g = base + (uint64_t)(i / IEQ_TILE) * IEQ_CHUNK + ph * IEQ_TILE + i % IEQ_TILE;
+            pre[j] = g < n ? buf[g] : make_double2(0.0, 0.0);
+        }
+    };
+    fetch(PHASES - 1);
+    for (int ph = PHASES - 1; ph >= 0; ph--) {
+#pragma unroll
+        for (int j = 0; j < IEQ_PER; j++) {
+            const int i = t + j * IEQ_THREADS;
+            tile[(i / IEQ_TILE) * IEQ_ROW + i % IEQ_TILE] = pre[j];
+        }
+        __syncthreads();
+        if (ph > 0) fetch(ph - 1);
+        double* row = reinterpret_cast<double*>(tile + c * IEQ_ROW) + ch;
+#pragma unroll
+        for (int k = IEQ_TILE - 1; k >= 0; k--) {
+            const double v = row[2 * k];
+            if (mine + (uint64_t)(ph * IEQ_TILE + k) >= o) s += v * v;
+            if (WRITE) row[2 * k] = carry + s;
+        }
+        __syncthreads();
+        if (WRITE) {
+#pragma unroll
+            for (int j = 0; j < IEQ_PER; j++) {
+                const int i = t + j * IEQ_THREADS;
+                const uint64_t g = base + (uint64_t)(i / IEQ_TILE) * IEQ_CHUNK + ph * IEQ_TILE + i % IEQ_TILE;
+                if (g < n) buf[g] = tile[(i / IEQ_TILE) * IEQ_ROW + i % IEQ_TILE];
+            }
+            __syncthreads();
+        }
+    }
+    if (!WRITE) tot[entry] = s;
+}
+
+// tot[2 c + ch], c < nchunks: in, the sum of chunk c; out, the sum of the chunks behind it, added up from the last chunk to
+// the first in one chain per channel.  One workgroup.
+__global__ __launch_bounds__(DEC_CARRY_THREADS) void k_dec_carry(double* __restrict__ tot, uint32_t nchunks) {
+    __shared__ double tile[2 * DEC_CARRY_TILE];
+    const int t = threadIdx.x;
+    double S = 0.0;  // (lanes 0 and 1: their channel's running sum)
+    for (int64_t hi = (int64_t)nchunks; hi > 0; hi -= DEC_CARRY_TILE) {
+        const int64_t lo = hi > DEC_CARRY_TILE ? hi - DEC_CARRY_TILE : 0;
+        const int cnt = 2 * (int)(hi - lo);
+        for (int i = t; i < cnt; i += DEC_CARRY_THREADS) tile[i] = tot[2 * lo + i];
+        __syncthreads();
+        if (t < 2)
+            for (int i = cnt - 2 + t; i >= 0; i -= 2) {
+                const double v = tile[i];
+                tile[i] = S;
+                S += v;
+            }
+        __syncthreads();
+        for (int i = t; i < cnt; i += DEC_CARRY_THREADS) tot[2 * lo + i] = tile[i];
+        __syncthreads();
+    }
+}
+
+// out[j] = EDC at o, n - 1, k50, k80 (j < 4; an index at or past n: zero) and at the K points of the curve,
+// o + floor(j' (n - 1 - o) / (K - 1))
+__global__ __launch_bounds__(ISH_THREADS) void k_dec_pick(const double2* __restrict__ buf, uint64_t o, uint64_t n, uint64_t k50, uint64_t k80,
+                                                          uint32_t K, double2* __restrict__ out) {
+    const uint32_t j = blockIdx.x * ISH_THREADS + threadIdx.x;
+    if (j >= DEC_PICK_HEAD + K) return;
+    uint64_t m;
+    if (j < DEC_PICK_HEAD)
+        m = j == 0 ? o : (j == 1 ? n - 1 : (j == 2 ? k50 : k80));
+    else
+        m = o + (uint64_t)(j - DEC_PICK_HEAD) * (n - 1 - o) / (uint64_t)(K - 1);
+    out[j] = m < n ? buf[m] : make_double2(0.0, 0.0);
+}
+
+// EDC of set s at a tap and its level against E in dB (NaN when E = 0, -inf when the sum has run out)
+__device__ inline double dec_edc(double2 v, int s) { return s == 0 ? v.x : (s == 1 ? v.y : v.x + v.y); }
+__device__ inline double dec_level(double edc, double E) { return 10.0 * log10(edc / E); }
+
+// part[DEC_MEMBER_PART b ..] of workgroup b over its taps in [o, n): for fit f = 3 set + range the number of taps with
+// lo <= L <= hi (part[f]) and the first of them (part[9 + f], n when there is none; both exact in double), then the sums of
+// EDC_L and EDC_R over the taps after o.
+__global__ __launch_bounds__(ISH_THREADS) void k_dec_members(const double2* __restrict__ buf, uint64_t o, uint64_t n, DecLevels lv,
+                                                             double* __restrict__ part) {
+    __shared__ double red[ISH_WAVES];
+    const uint64_t stride = (uint64_t)gridDim.x * ISH_THREADS;
+    double cnt[DEC_FITS], first[DEC_FITS], sum[2] = {0.0, 0.0};
+    for (int f = 0; f < DEC_FITS; f++) cnt[f] = 0.0, first[f] = (double)n;
+    for (uint64_t m = o + (uint64_t)blockIdx.x * ISH_THREADS + threadIdx.x; m < n; m += stride) {
+        const double2 v = buf[m];
+        if (m > o) sum[0] += v.x, sum[1] += v.y;
+#pragma unroll
+        for (int s = 0; s < DEC_SETS; s++) {
+            const double L = dec_level(dec_edc(v, s), lv.E[s]);
+#pragma unroll
+            for (int r = 0; r < DEC_RANGES; r++)
+                if (L >= DEC_LO[r] && L <= DEC_HI[r]) {
+                    cnt[3 * s + r] += 1.0;
+                    first[3 * s + r] = fmin(first[3 * s + r], (double)m);
+                }
+        }
+    }
+    double* mine = part + (uint64_t)DEC_MEMBER_PART * blockIdx.x;
+    for (int f = 0; f < DEC_FITS; f++) {
+        const double c = ish_block_reduce(cnt[f], red, [](double p, double q) { return p + q; });
+        const double a = ish_block_reduce(first[f], red, [](double p, double q) { return fmin(p, q); });
+        if (threadIdx.x == 0) mine[f] = c, mine[DEC_FITS + f] = a;
+    }
+    for (int k = 0; k < 2; k++) {
+        const double r = ish_block_reduce(sum[k], red, [](double p, double q) { return p + q; });
+        if (threadIdx.x == 0) mine[2 * DEC_FITS + k] = r;
+    }
+}
+
+// part[DEC_FIT_PART b + 4 f ..] = workgroup b's share of sum x, sum y, sum x^2, sum x y over the taps of fit f, x = m - first[f],
+// y = L[m]
+__global__ __launch_bounds__(ISH_THREADS) void k_dec_fit(const double2* __restrict__ buf, uint64_t o, uint64_t n, DecLevels lv,
+                                                         double* __restrict__ part) {
+    __shared__ double red[ISH_WAVES];
+    const uint64_t stride = (uint64_t)gridDim.x * ISH_THREADS;
+    double acc[DEC_FIT_PART];
+    for (int k = 0; k < DEC_FIT_PART; k++) acc[k] = 0.0;
+    for (uint64_t m = o + (uint64_t)blockIdx.x * ISH_THREADS + threadIdx.x; m < n; m += stride) {
+        const double2 v = buf[m];
+#pragma unroll
+        for (int s = 0; s < DEC_SETS; s++) {
+            const double L = dec_level(dec_edc(v, s), lv.E[s]);
+#pragma unroll
+            for (int r = 0; r < DEC_RANGES; r++)
+                if (L >= DEC_LO[r] && L <= DEC_HI[r]) {
+                    const int f = 3 * s + r;
+                    const double x = (double)m - (double)lv.first[f];
+                    acc[4 * f] += x;
+                    acc[4 * f + 1] += L;
+                    acc[4 * f + 2] += x * x;
+                    acc[4 * f + 3] += x * L;
+                }
+        }
+    }
+    for (int k = 0; k < DEC_FIT_PART; k++) {
+        const double r = ish_block_reduce(acc[k], red, [](double p, double q) { return p + q; });
+        if (threadIdx.x == 0) part[(uint64_t)DEC_FIT_PART * blockIdx.x + k] = r;
+    }
+}
+
+// -- host ------------------------------------------------------------------------------------------------------------
+// Every field of a query, checked without touching an engine or HIP; the message (thread-local) names the field.  Null when it
+// is good.
+inline const char* dec_check(const mc_decay_query* q) {
+    static thread_local char msg[160];
+    if (!q) return "null query";
+    if (q->struct_size != sizeof(mc_decay_query)) return "mc_decay_query struct_size mismatch";
+    if (q->rate < DEC_MIN_RATE || q->rate > DEC_MAX_RATE)
+        std::snprintf(msg, sizeof(msg), "rate %u outside [%u, %u]", q->rate, DEC_MIN_RATE, DEC_MAX_RATE);
+    else if (q->n_bands > MC_DECAY_MAX_BANDS)
+        std::snprintf(msg, sizeof(msg), "n_bands %u above %d", q->n_bands, MC_DECAY_MAX_BANDS);
+    else if (q->curve_points == 1 || q->curve_points > MC_DECAY_MAX_CURVE)
+        std::snprintf(msg, sizeof(msg), "curve_points %u is neither 0 nor in [2, %d]", q->curve_points, MC_DECAY_MAX_CURVE);
+    else {
+        const double top = IEQ_MAX_NYQ * (double)q->rate, qq = (double)q->q, on = (double)q->onset_db;
+        for (uint32_t b = 0; b < q->n_bands; b++) {
+            const double f = (double)q->centre_hz[b];
+            if (std::isfinite(f) && f >= IEQ_MIN_HZ && f <= top) continue;
+            std::snprintf(msg, sizeof(msg), "centre_hz[%u] %g outside [%g, %g]", b, f, IEQ_MIN_HZ, top);
+            return msg;
+        }
+        if (!(std::isfinite(qq) && qq >= IEQ_MIN_Q && qq <= IEQ_MAX_Q))
+            std::snprintf(msg, sizeof(msg), "q %g outside [%g, %g]", qq, IEQ_MIN_Q, IEQ_MAX_Q);
+        else if (!(on >= DEC_MIN_ONSET_DB && on <= 0.0))
+            std::snprintf(msg, sizeof(msg), "onset_db %g outside [%g, 0]", on, DEC_MIN_ONSET_DB);
+        else
+            return nullptr;
+    }
+    return msg;
+}
+
+// one section of a band: the Audio-EQ-Cookbook band-pass with 0 dB peak gain, w0, c and al as ieq_coef has them
+inline IeqCoef dec_coef(float centre_hz, float q, uint32_t rate) {
+    const double w0 = 2.0 * M_PI * (double)centre_hz / (double)rate, c = std::cos(w0), al = std::sin(w0) / (2.0 * (double)q);
+    const double a0 = 1.0 + al;
+    return IeqCoef{al / a0, 0.0, -al / a0, -2.0 * c / a0, (1.0 - al) / a0};
+}
+
+// The eight numbers of a row and its K curve points from what the kernels reduced: pick = EDC of the set at o, N - 1, k50,
+// k80 and the curve's points; cnt / first / fit = the three ranges' member counts, first taps and four sums; tsum = sum EDC
+// over (o, N).
+inline void dec_row(const double* pick, const double* cnt, const double (*fit)[4], double tsum, uint64_t o, uint64_t N, uint64_t k50,
+                    uint64_t k80, uint32_t rate, uint32_t K, double* row, double* curve) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    const double E = pick[0];
+    row[0] = E;
+    for (int k = 1; k < 8; k++) row[k] = nan;
+    for (uint32_t j = 0; j < K; j++) curve[j] = nan;
+    if (!(E > 0.0)) return;  // (an all-zero row, or taps that are not numbers)
+    const double Llast = 10.0 * std::log10(pick[1] / E);
+    for (int r = 0; r < DEC_RANGES; r++) {
+        const double n = cnt[r];
+        if (Llast > DEC_LO[r] || n < 2.0) continue;
+        const double sx = fit[r][0], sy = fit[r][1], sxx = fit[r][2], sxy = fit[r][3];
+        const double a = (n * sxy - sx * sy) / (n * sxx - sx * sx);
+        row[1 + r] = -60.0 / (a * (double)rate);
+    }
+    const uint64_t kk[2] = {k50, k80};
+    for (int k = 0; k < 2; k++) {
+        const double late = pick[2 + k];
+        if (kk[k] >= N || late == 0.0) continue;
+        row[4 + k] = 10.0 * std::log10((E - late) / late);
+        if (k == 0) row[6] = (E - late) / E;
+    }
+    row[7] = tsum / E / (double)rate;
+    for (uint32_t j = 0; j < K; j++) curve[j] = std::max(10.0 * std::log10(pick[DEC_PICK_HEAD + j] / E), DEC_CURVE_FLOOR);
+}
+
+// The whole measurement of the n stored taps d_x for a checked query.  rows, curve, info as mc_ir_decay describes them.
+// Synchronises the stream; leaves nothing allocated.
+inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n, const mc_decay_query& q, double* rows, double* curve,
+                              uint64_t info[2]) {
+    const uint64_t N = q.end ? std::min<uint64_t>(q.end, n) : n;
+    const uint32_t K = q.curve_points, npick = DEC_PICK_HEAD + K;
+    const unsigned grid = (unsigned)((N + ISH_THREADS - 1) / ISH_THREADS);                    // k_dec_fill
+    const unsigned cgrid = (unsigned)((N + IEQ_SPAN - 1) / IEQ_SPAN);                         // k_eq_chunk, k_dec_sum
+    const uint32_t nchunks = (uint32_t)((N + IEQ_CHUNK - 1) / IEQ_CHUNK), runK = (nchunks + IEQ_RUNS - 1) / IEQ_RUNS;
+    const unsigned rgrid = std::min<unsigned>(DEC_GRID, grid);                                // k_dec_members, k_dec_fit
+    const unsigned ogrid = (unsigned)std::min<uint64_t>(ISH_SCAN_GRID, (N / 2 + ISH_THREADS) / ISH_THREADS);  // the onset's walks
+    const size_t npart = std::max<size_t>({(size_t)DEC_FIT_PART * rgrid, (size_t)2 * npick, (size_t)ogrid});
+    double2 *d_buf = nullptr, *d_st = nullptr;
+    double *d_tot = nullptr, *d_part = nullptr;
+    std::vector<double> part(npart);
+    hipError_t er = hipMalloc(&d_buf, sizeof(double2) * N);
+    if (er == hipSuccess) er = hipMalloc(&d_st, sizeof(double2) * (size_t)cgrid * IEQ_THREADS);
+    if (er == hipSuccess) er = hipMalloc(&d_tot, sizeof(double) * (size_t)cgrid * IEQ_THREADS);
+    if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * npart);
+    const auto launched = [&] { er = hipGetLastError(); };
+    const auto fetch = [&](size_t count) {
+        if (er == hipSuccess) er = hipMemcpyAsync(part.data(), d_part, sizeof(double) * count, hipMemcpyDeviceToHost, stream);
+        if (er == hipSuccess) er = hipStreamSynchronize(stream);
+        return er;
+    };
+
+    // origin: the shaped load's onset over the taps that are analysed
+    uint64_t o = 0;
+    if (er == hipSuccess && q.onset_db < 0.f) {
+        hipLaunchKernelGGL(k_shape_peak, dim3(ogrid), dim3(ISH_THREADS), 0, stream, d_x, N, (float*)d_part);
+        launched();
+        std::vector<float> pk(ogrid);
+        if (er == hipSuccess) er = hipMemcpyAsync(pk.data(), d_part, sizeof(float) * ogrid, hipMemcpyDeviceToHost, stream);
+        if (er == hipSuccess) er = hipStreamSynchronize(stream);
+        if (er == hipSuccess) {
+            float peak = 0.f;
+            for (float v : pk) peak = std::max(peak, v);
+            const float t = peak * (float)std::pow(10.0, (double)q.onset_db / 20.0);
+            hipLaunchKernelGGL(k_shape_onset, dim3(ogrid), dim3(ISH_THREADS), 0, stream, d_x, N, t, (unsigned long long*)d_part);
+            launched();
+        }
+        std::vector<unsigned long long> at(ogrid);
+        if (er == hipSuccess) er = hipMemcpyAsync(at.data(), d_part, sizeof(unsigned long long) * ogrid, hipMemcpyDeviceToHost, stream);
+        if (er == hipSuccess) er = hipStreamSynchronize(stream);
+        if (er == hipSuccess) {
+            uint64_t onset = ISH_NONE;
+            for (unsigned long long v : at) onset = std::min<uint64_t>(onset, v);
+            o = onset == ISH_NONE ? 0 : onset;  // (taps that compare false with everything)
+        }
+    }
+    const uint64_t k50 = o + (uint64_t)std::floor(0.05 * (double)q.rate + 0.5), k80 = o + (uint64_t)std::floor(0.08 * (double)q.rate + 0.5);
+
+    for (uint32_t g = 0; g <= q.n_bands && er == hipSuccess; g++) {
+        hipLaunchKernelGGL(k_dec_fill, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x, N, d_buf);
+        launched();
+        if (g > 0) {  // two identical sections: the second rides as the `nxt` stage of the first's fix-up
+            IeqStage sec{}, off{};
+            sec.c = dec_coef(q.centre_hz[g - 1], q.q, q.rate), sec.on = 1;
+            const IeqMat M = ieq_matpow(IeqMat{-sec.c.a1, 1.0, -sec.c.a2, 0.0}, IEQ_CHUNK), MK = ieq_matpow(M, runK);
+            for (int pass = 0; pass < 3 && er == hipSuccess; pass++) {
+                if (pass > 0) {
+                    hipLaunchKernelGGL(k_eq_carry, dim3(1), dim3(2 * IEQ_RUNS), 0, stream, d_st, nchunks, runK, M, MK);
+                    launched();
+                }
+                if (er != hipSuccess) break;
+                hipLaunchKernelGGL(k_eq_chunk, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pass > 0 ? sec : off, pass < 2 ? sec : off, d_st);
+                launched();
+            }
+        }
+        if (er == hipSuccess) {
+            hipLaunchKernelGGL(k_dec_sum<false>, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
+            launched();
+        }
+        if (er == hipSuccess) {
+            hipLaunchKernelGGL(k_dec_carry, dim3(1), dim3(DEC_CARRY_THREADS), 0, stream, d_tot, nchunks);
+            launched();
+        }
+        if (er == hipSuccess) {
+            hipLaunchKernelGGL(k_dec_sum<true>, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
+            launched();
+        }
+        if (er == hipSuccess) {
+            hipLaunchKernelGGL(k_dec_pick, dim3((npick + ISH_THREADS - 1) / ISH_THREADS), dim3(ISH_THREADS), 0, stream, d_buf, o, N, k50, k80, K,
+                               reinterpret_cast<double2*>(d_part));
+            launched();
+        }
+        if (fetch((size_t)2 * npick) != hipSuccess) break;
+        std::vector<double> pick[DEC_SETS];
+        for (int s = 0; s < DEC_SETS; s++) {
+            pick[s].resize(npick);
+            for (uint32_t j = 0; j < npick; j++) pick[s][j] = s == 0 ? part[2 * j] : (s == 1 ? part[2 * j + 1] : part[2 * j] + part[2 * j + 1]);
+        }
+        DecLevels lv{};
+        for (int s = 0; s < DEC_SETS; s++) lv.E[s] = pick[s][0];
+        hipLaunchKernelGGL(k_dec_members, dim3(rgrid), dim3(ISH_THREADS), 0, stream, d_buf, o, N, lv, d_part);
+        launched();
+        if (fetch((size_t)DEC_MEMBER_PART * rgrid) != hipSuccess) break;
+        double cnt[DEC_FITS], tsum[DEC_SETS] = {0.0, 0.0, 0.0};
+        for (int f = 0; f < DEC_FITS; f++) cnt[f] = 0.0, lv.first[f] = N;
+        for (unsigned b = 0; b < rgrid; b++) {
+            const double* p = part.data() + (size_t)DEC_MEMBER_PART * b;
+            for (int f = 0; f < DEC_FITS; f++) {
+                cnt[f] += p[f];
+                lv.first[f] = std::min<uint64_t>(lv.first[f], (uint64_t)p[DEC_FITS + f]);
+            }
+            tsum[0] += p[2 * DEC_FITS];
+            tsum[1] += p[2 * DEC_FITS + 1];
+        }
+        tsum[2] = tsum[0] + tsum[1];
+        hipLaunchKernelGGL(k_dec_fit, dim3(rgrid), dim3(ISH_THREADS), 0, stream, d_buf, o, N, lv, d_part);
+        launched();
+        if (fetch((size_t)DEC_FIT_PART * rgrid) != hipSuccess) break;
+        double fit[DEC_FITS][4] = {};
+        for (unsigned b = 0; b < rgrid; b++)
+            for (int f = 0; f < DEC_FITS; f++)
+                for (int k = 0; k < 4; k++) fit[f][k] += part[(size_t)DEC_FIT_PART * b + 4 * f + k];
+        for (int s = 0; s < DEC_SETS; s++) {
+            const size_t r = (size_t)g * DEC_SETS + s;
+            dec_row(pick[s].data(), cnt + 3 * s, fit + 3 * s, tsum[s], o, N, k50, k80, q.rate, K, rows + 8 * r, curve ? curve + (size_t)K * r : nullptr);
+        }
+    }
+    (void)hipFree(d_part);
+    (void)hipFree(d_tot);
+    (void)hipFree(d_st);
+    (void)hipFree(d_buf);
+    info[0] = o;
+    info[1] = N;
+    return er;
+}

@@ -28,6 +28,7 @@
 #include "resample.hip.h"
 #include "irshape.hip.h"
 #include "ireq.hip.h"
+#include "irdecay.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
 // mc_config or that the tests compare bit for bit:
@@ -3475,6 +3476,34 @@ int mc_ir_eq_response(const mc_ir_eq* eq, uint32_t rate, const double* hz, uint3
     if (rate < RS_MIN_RATE || rate > RS_MAX_RATE) return fail(MC_ERR_ARG, "rate %u outside [%u, %u]", rate, RS_MIN_RATE, RS_MAX_RATE);
     const IeqCascade cs = ieq_cascade(*eq, rate);
     for (uint32_t i = 0; i < n; i++) db[i] = ieq_response_db(cs, rate, hz[i]);
+    return MC_OK;
+}
+
+void mc_default_decay_query(mc_decay_query* q) {
+    if (!q) return;
+    std::memset(q, 0, sizeof(*q));
+    q->struct_size = (uint32_t)sizeof(*q);
+    q->rate = 44100;
+    q->q = 1.41421356f;
+    q->onset_db = -20.f;
+}
+
+int mc_ir_decay(mc_engine* e, uint64_t idx, const mc_decay_query* q, double* rows, double* curve, uint64_t info[2]) {
+    // the query, the pointers and the index are checked in this order before any HIP call
+    if (const char* bad = dec_check(q)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!e) return fail(MC_ERR_ARG, "null engine");
+    if (!rows) return fail(MC_ERR_ARG, "null rows");
+    if (q->curve_points && !curve) return fail(MC_ERR_ARG, "null curve with curve_points %u", q->curve_points);
+    if (!info) return fail(MC_ERR_ARG, "null info");
+    if (e->sf) return fail(MC_ERR_STATE, "the single-transform form keeps no taps");
+    if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h || !e->irs[idx].taps) return fail(MC_ERR_ARG, "IR not loaded");
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = drain_post(e);  // (the stream must be idle and out of the JACK path before the kernels go onto it, as for a shaped load)
+    if (!rc) rc = leave_jack_path(e);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const hipError_t er = dec_measure(e->stream, e->irs[idx].d_h, e->irs[idx].taps, *q, rows, curve, info);
+    if (er != hipSuccess) return fail(MC_ERR_HIP, "decay measurement failed: %s", hipGetErrorString(er));
     return MC_OK;
 }
 

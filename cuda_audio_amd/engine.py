@@ -10,12 +10,13 @@ there is no CPU path here.
 """
 import ctypes as C
 import dataclasses
+import math
 import weakref
 
 import numpy as np
 
 from . import _lib
-from ._lib import MC_BLOCK, McCcValue, McConfig, McIrEq, McIrShape, McKernelStats, check
+from ._lib import MC_BLOCK, McCcValue, McConfig, McDecayQuery, McIrEq, McIrShape, McKernelStats, check
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
 CONV_MAX_SPEED = 1024             # conv.h:22-24
@@ -94,6 +95,47 @@ def eq_response(eq, rate, hz):
     dp = C.POINTER(C.c_double)
     check(_lib.load().mc_ir_eq_response(C.byref(eq.to_c()), int(rate), hz.ctypes.data_as(dp), hz.size, db.ctypes.data_as(dp)))
     return db
+
+
+@dataclasses.dataclass
+class DecayQuery:
+    """What ir_decay measures (mc_decay_query, include/mcconv.h): the broadband row and one row per centre frequency of `bands`
+    (two band-pass sections of quality q each), time zero at the first tap within onset_db of the peak (0: tap 0), over taps
+    [0, end) (0: all), with curve_points points of every row's decay curve."""
+
+    rate: int = 44100
+    bands: tuple = ()
+    q: float = None          # None: the library's default, sqrt 2 (one octave)
+    onset_db: float = -20.0
+    end: int = 0
+    curve_points: int = 0
+
+    def to_c(self):
+        if len(self.bands) > _lib.MC_DECAY_MAX_BANDS:
+            raise ValueError(f"{len(self.bands)} bands; at most {_lib.MC_DECAY_MAX_BANDS}")
+        d = McDecayQuery()
+        _lib.load().mc_default_decay_query(C.byref(d))
+        d.rate, d.n_bands, d.curve_points = int(self.rate), len(self.bands), int(self.curve_points)
+        for k, hz in enumerate(self.bands):
+            d.centre_hz[k] = float(hz)
+        if self.q is not None:
+            d.q = float(self.q)
+        d.onset_db, d.end = float(self.onset_db), int(self.end)
+        return d
+
+
+DECAY_SETS = ("L", "R", "LR")
+DECAY_FIELDS = ("energy", "edt", "t20", "t30", "c50", "c80", "d50", "ts")
+
+
+def decay_for_rt60(measured_s, target_s, rate):
+    """The IrShape.decay_t60 (frames) that takes an IR whose decay time is measured_s seconds to target_s seconds at `rate`
+    Hz.  The envelope 10^(-3 m / d) adds 60 rate / d dB/s to the slope, so 1 / target = 1 / measured + rate / d.  An envelope
+    can only shorten: ValueError unless 0 < target_s < measured_s, both finite."""
+    measured_s, target_s = float(measured_s), float(target_s)
+    if not (math.isfinite(measured_s) and math.isfinite(target_s) and 0.0 < target_s < measured_s):
+        raise ValueError(f"need 0 < target ({target_s}) < measured ({measured_s}), both finite")
+    return int(round(float(rate) / (1.0 / target_s - 1.0 / measured_s)))
 
 
 class _CCValueView:
@@ -328,6 +370,24 @@ class Convolution:
         check(self._L.mc_ir_shape_info(self._h, idx, out))
         return dict(frames=int(out[0]), onset=int(out[1]), first=int(out[2]), taps=int(out[3]), gain=out[4], peak=out[5], energy=out[6],
                     eq_bands=int(out[7]))
+
+    def ir_decay(self, idx, bands=(), q=None, onset_db=-20.0, end=0, curve_points=0, rate=None):
+        """The decay of the stored taps of IR idx, measured on the device (mc_ir_decay; include/mcconv.h has the definition).
+        rate defaults to the engine's sample_rate, then to 44100.  Returns {"origin", "taps", "rows", "curve"}: rows maps
+        (band, "L" | "R" | "LR") - band 0 is broadband, band b >= 1 is bands[b - 1] - to {energy, edt, t20, t30, c50, c80, d50, ts}
+        (seconds and dB; NaN where the IR does not define one); curve is float64 [1 + len(bands), 3, curve_points] in dB, or
+        None."""
+        if rate is None:
+            rate = self.sample_rate or 44100
+        d = DecayQuery(rate=rate, bands=tuple(bands), q=q, onset_db=onset_db, end=end, curve_points=curve_points).to_c()
+        groups = 1 + d.n_bands
+        rows = np.empty((groups, 3, 8), np.float64)
+        curve = np.empty((groups, 3, d.curve_points), np.float64) if d.curve_points else None
+        info = (C.c_uint64 * 2)()
+        dp = C.POINTER(C.c_double)
+        check(self._L.mc_ir_decay(self._h, idx, C.byref(d), rows.ctypes.data_as(dp), curve.ctypes.data_as(dp) if curve is not None else None, info))
+        return dict(origin=int(info[0]), taps=int(info[1]), curve=curve,
+                    rows={(b, name): dict(zip(DECAY_FIELDS, (float(v) for v in rows[b, s]))) for b in range(groups) for s, name in enumerate(DECAY_SETS)})
 
     def enable_kernel_timing(self, on=True):
         check(self._L.mc_enable_kernel_timing(self._h, 1 if on else 0))

@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <string>
 
 #include "../../include/mcconv_group.h"
 
@@ -26,6 +27,9 @@ int mc_ir_shape_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 void mc_default_ir_eq(mc_ir_eq*) __attribute__((weak));
 int mc_load_ir_eq(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*) __attribute__((weak));
 int mc_ir_eq_response(const mc_ir_eq*, uint32_t, const double*, uint32_t, double*) __attribute__((weak));
+// (... and no decay measurement)
+void mc_default_decay_query(mc_decay_query*) __attribute__((weak));
+int mc_ir_decay(mc_engine*, uint64_t, const mc_decay_query*, double*, double*, uint64_t*) __attribute__((weak));
 }
 
 namespace {
@@ -158,34 +162,145 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
     }
 }
 
+void Convolution::setIrDecayReport(bool on, const std::vector<float>& bands) {
+    if (on && _group) {
+        Log::error("conv", "the IR decay report is not available with several devices (mc_ir_decay is single-engine)");
+        std::exit(2);
+    }
+    if (bands.size() > MC_DECAY_MAX_BANDS) {
+        Log::error("conv", "%zu decay bands, at most %d", bands.size(), MC_DECAY_MAX_BANDS);
+        std::exit(2);
+    }
+    _decayReport = on;
+    _decayBands = bands;
+}
+
+void Convolution::setIrRt60(double seconds) {
+    if (seconds > 0.0 && _group) {
+        Log::error("conv", "aiming IRs at a decay time is not available with several devices (mc_ir_decay is single-engine)");
+        std::exit(2);
+    }
+    _rt60 = seconds > 0.0 ? seconds : 0.0;
+}
+
+uint64_t Convolution::decayForRt60(double measured, double target, double rate) {
+    if (!(std::isfinite(measured) && std::isfinite(target) && target > 0.0 && target < measured)) return 0;
+    return (uint64_t)std::nearbyint(rate / (1.0 / target - 1.0 / measured));
+}
+
+Convolution::Decay Convolution::irDecay(size_t idx, const DecayQuery& query) {
+    if (!mc_ir_decay || !mc_default_decay_query) {
+        Log::error("conv", "the engine has no decay measurement (mc_ir_decay)");
+        std::exit(2);
+    }
+    if (query.bands.size() > MC_DECAY_MAX_BANDS) {
+        Log::error("conv", "%zu decay bands, at most %d", query.bands.size(), MC_DECAY_MAX_BANDS);
+        std::exit(2);
+    }
+    mc_decay_query q;
+    mc_default_decay_query(&q);
+    q.rate = query.rate ? query.rate : (uint32_t)samplerate;
+    q.n_bands = (uint32_t)query.bands.size();
+    for (size_t k = 0; k < query.bands.size(); k++) q.centre_hz[k] = query.bands[k];
+    q.q = query.q;
+    q.onset_db = query.onsetDb;
+    q.end = query.end;
+    q.curve_points = query.curvePoints;
+    Decay d;
+    d.rows.resize((1 + query.bands.size()) * 3 * 8);
+    d.curve.resize((1 + query.bands.size()) * 3 * query.curvePoints);
+    uint64_t info[2] = {0, 0};
+    check(mc_ir_decay(_engine, idx, &q, d.rows.data(), d.curve.empty() ? nullptr : d.curve.data(), info), "mc_ir_decay");
+    d.origin = info[0];
+    d.taps = info[1];
+    return d;
+}
+
+namespace {
+// a number with `decimals` places, NaN as "nan" whatever its sign
+std::string places(double v, int decimals) {
+    if (std::isnan(v)) return "nan";
+    char buf[64];
+    std::snprintf(buf, sizeof(buf), "%.*f", decimals, v);
+    return buf;
+}
+}  // namespace
+
+void Convolution::reportDecay(size_t idx) {
+    DecayQuery query;
+    query.bands = _decayBands;
+    const Decay d = irDecay(idx, query);
+    for (size_t b = 0; b <= _decayBands.size(); b++) {
+        char head[64] = "";
+        if (b) std::snprintf(head, sizeof(head), " band %g Hz", (double)_decayBands[b - 1]);
+        const auto v = [&](Decay::Field f, int decimals, double scale = 1.0) { return places(scale * d.at(b, Decay::LR, f), decimals); };
+        Log::info(name, "IR %zu%s decay: origin %llu, EDT %s s, T20 %s s, T30 %s s, C50 %s dB, C80 %s dB, Ts %s ms", idx, head,
+                  (unsigned long long)d.origin, v(Decay::Edt, 4).c_str(), v(Decay::T20, 4).c_str(), v(Decay::T30, 4).c_str(), v(Decay::C50, 2).c_str(),
+                  v(Decay::C80, 2).c_str(), v(Decay::Ts, 2, 1000.0).c_str());
+    }
+}
+
+// broadband LR T30 of a loaded IR, T20 when the curve does not reach -35 dB (NaN when it does not reach -25 dB either)
+static double measuredRt(Convolution& c, size_t idx) {
+    const Convolution::Decay d = c.irDecay(idx, Convolution::DecayQuery());
+    const double t30 = d.at(0, Convolution::Decay::LR, Convolution::Decay::T30);
+    return std::isnan(t30) ? d.at(0, Convolution::Decay::LR, Convolution::Decay::T20) : t30;
+}
+
+void Convolution::aimRt60(const PendingIr& p) {
+    const double measured = measuredRt(*this, p.idx);
+    if (std::isnan(measured)) {
+        Log::warn(name, "IR %zu rt60: its decay curve does not reach -25 dB, left as it is", p.idx);
+        return;
+    }
+    const uint64_t fit = decayForRt60(measured, _rt60, (double)samplerate);
+    if (!fit) {
+        Log::info(name, "IR %zu rt60: target %.4f s is not below the measured %.4f s, left as it is", p.idx, _rt60, measured);
+        return;
+    }
+    // slopes add: 1 / d = 1 / d_user + 1 / d_fit
+    IrShape shape = p.shape;
+    shape.decayT60 = shape.decayT60 ? (uint64_t)std::nearbyint(1.0 / (1.0 / (double)shape.decayT60 + 1.0 / (double)fit)) : fit;
+    if (!shape.decayT60) shape.decayT60 = 1;
+    loadPending(p, shape);
+    Log::info(name, "IR %zu rt60: measured %.4f s, decay %llu frames, now %s s", p.idx, measured, (unsigned long long)shape.decayT60,
+              places(measuredRt(*this, p.idx), 4).c_str());
+}
+
+void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
+    const uint64_t frames = p.lr.size() / 2;
+    const bool convert = p.match && p.rate && p.rate != samplerate;
+    if (!p.eq.off()) {  // (the bands are laid out at the client's rate; frames that are not converted count as being at it)
+        loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : (unsigned)samplerate, (unsigned)samplerate, shape, p.eq);
+        return;
+    }
+    if (!shape.off()) {
+        loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : 0, convert ? (unsigned)samplerate : 0, shape);
+        return;
+    }
+    if (!convert) {
+        check(mc_load_ir(_engine, p.idx, p.lr.data(), frames, p.nframes), "mc_load_ir");
+        return;
+    }
+    if (!mc_load_ir_resampled) {
+        Log::error("conv", "the engine has no sample-rate conversion (mc_load_ir_resampled)");
+        std::exit(2);
+    }
+    Log::info(name, "IR %zu: %u Hz -> %zu Hz", p.idx, p.rate, samplerate);
+    check(mc_load_ir_resampled(_engine, p.idx, p.lr.data(), frames, p.nframes, p.rate, (uint32_t)samplerate), "mc_load_ir_resampled");
+}
+
 void Convolution::loadPendingIrs() {
     for (const PendingIr& p : _pendingIrs) {
-        const uint64_t frames = p.lr.size() / 2;
-        const bool convert = p.match && p.rate && p.rate != samplerate;
-        if (!p.eq.off()) {  // (the bands are laid out at the client's rate; frames that are not converted count as being at it)
-            loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : (unsigned)samplerate, (unsigned)samplerate, p.shape, p.eq);
-            continue;
-        }
-        if (!p.shape.off()) {
-            loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : 0, convert ? (unsigned)samplerate : 0, p.shape);
-            continue;
-        }
-        if (!convert) {
-            check(mc_load_ir(_engine, p.idx, p.lr.data(), frames, p.nframes), "mc_load_ir");
-            continue;
-        }
-        if (!mc_load_ir_resampled) {
-            Log::error("conv", "the engine has no sample-rate conversion (mc_load_ir_resampled)");
-            std::exit(2);
-        }
-        Log::info(name, "IR %zu: %u Hz -> %zu Hz", p.idx, p.rate, samplerate);
-        check(mc_load_ir_resampled(_engine, p.idx, p.lr.data(), frames, p.nframes, p.rate, (uint32_t)samplerate), "mc_load_ir_resampled");
+        loadPending(p, p.shape);
+        if (_rt60 > 0.0) aimRt60(p);
+        if (_decayReport) reportDecay(p.idx);
     }
     _pendingIrs.clear();
 }
 
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
-    if (_matchIrRate || !_irEq.off()) {  // (loaded by onStart(), once the client's rate is known)
+    if (_matchIrRate || !_irEq.off() || _decayReport || _rt60 > 0.0) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
         _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate});
         if (idx + 1 > _nirs) _nirs = idx + 1;

@@ -104,6 +104,36 @@ public:
         }
     };
     void setIrEq(const IrEq& eq);
+    // The decay of a loaded IR, measured by the engine from the taps it convolves with (mc_ir_decay of include/mcconv.h, which
+    // has the definition; no reference equivalent).  rate = 0: the client's sample rate (known from onStart() on).
+    struct DecayQuery {
+        unsigned rate = 0;
+        std::vector<float> bands;  // centre frequencies of the band-passed rows after the broadband row, at most 10
+        float q = 1.41421356f;     // per section
+        float onsetDb = -20.0f;    // 0: time zero is tap 0
+        uint64_t end = 0;          // taps [0, end) are analysed; 0 = all
+        uint32_t curvePoints = 0;
+    };
+    struct Decay {
+        uint64_t origin = 0, taps = 0;
+        std::vector<double> rows;   // [(1 + bands) * 3 * 8]: per band and channel set (L, R, LR) {E, EDT, T20, T30, C50, C80, D50, Ts}
+        std::vector<double> curve;  // [(1 + bands) * 3 * curvePoints]
+        enum Set { L = 0, R = 1, LR = 2 };
+        enum Field { Energy = 0, Edt, T20, T30, C50, C80, D50, Ts };
+        double at(size_t band, Set set, Field f) const { return rows[(band * 3 + set) * 8 + f]; }
+    };
+    Decay irDecay(size_t idx, const DecayQuery& query);
+    // The IrShape::decayT60 (frames) that takes a decay time of measured seconds to target seconds at rate Hz: the envelope
+    // 10^(-3 m / d) adds 60 rate / d dB/s to the slope.  0 unless 0 < target < measured, both finite (an envelope only shortens).
+    static uint64_t decayForRt60(double measured, double target, double rate);
+    // One log line per IR loaded from now on (origin, EDT, T20, T30, C50, C80, Ts of the broadband LR row) and one more per
+    // centre frequency of `bands`.  The times need the client's sample rate: prepare() keeps the frames and onStart() loads
+    // them, as with setMatchIrRate.  Single device only, as setIrShape.
+    void setIrDecayReport(bool on, const std::vector<float>& bands = {});
+    // Aim every IR loaded from now on at a decay time of `seconds` (0 = off): it is loaded, its broadband LR T30 (T20 when the
+    // curve does not reach -35 dB) is measured, and when the target is shorter it is loaded again with the decayT60 that
+    // takes it there, added as a slope to the shape's own decayT60.  Loaded by onStart(), single device only, as above.
+    void setIrRt60(double seconds);
 
     void onMidiMessage(const RawMidi::Device* sender, const uint8_t* buffer, size_t len) override;
 
@@ -130,6 +160,12 @@ private:
     };
     std::vector<PendingIr> _pendingIrs;  // (rate matching) prepared, loaded by onStart()
     void loadPendingIrs();
+    void loadPending(const PendingIr& p, const IrShape& shape);
+    void aimRt60(const PendingIr& p);
+    void reportDecay(size_t idx);
+    bool _decayReport = false;
+    std::vector<float> _decayBands;
+    double _rt60 = 0.0;
     IrShape _irShape;
     IrEq _irEq;
     void loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,

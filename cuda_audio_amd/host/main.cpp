@@ -13,7 +13,10 @@
 // --ir-normalize peak|energy[:TARGET]: every IR is shaped on load, Convolution::setIrShape - lengths in frames at the rate
 // the IR is loaded at; --ir-eq KIND:HZ[:DB][:Q], up to 8 times, KIND one of lowcut, highcut, lowshelf, highshelf, peak (the cuts:
 // KIND:HZ[:Q]): every IR is equalised on load with these bands in this order, at the client's sample rate,
-// Convolution::setIrEq).
+// Convolution::setIrEq; --ir-decay-report: after each IR is loaded one log line with its decay (origin, EDT, T20, T30, C50, C80, Ts
+// of the broadband LR row, measured by the engine: Convolution::setIrDecayReport), --ir-decay-bands HZ[,HZ...]: one more line per
+// centre frequency; --ir-rt60 SECONDS: every IR whose measured decay time is longer is loaded again with the further exponential
+// decay that takes it there, on top of --ir-decay, Convolution::setIrRt60).
 #include <cassert>
 #include <cstdlib>
 #include <cstring>
@@ -36,6 +39,9 @@ int main(int argc, char** argv) {
     bool matchIrRate = false;
     Convolution::IrShape irShape;
     Convolution::IrEq irEq;
+    bool irDecayReport = false;
+    std::vector<float> irDecayBands;
+    double irRt60 = 0.0;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--periods") && i + 1 < argc) periods = strtoull(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "--settings") && i + 1 < argc) settingsPath = argv[++i];
@@ -84,6 +90,24 @@ int main(int argc, char** argv) {
             if (*end == ':' && !cut) b.gainDb = strtof(end + 1, &end);
             if (*end == ':') b.q = strtof(end + 1, &end);
             irEq.bands.push_back(b);
+        } else if (!strcmp(argv[i], "--ir-decay-report")) irDecayReport = true;
+        else if (!strcmp(argv[i], "--ir-decay-bands") && i + 1 < argc) {
+            irDecayReport = true;
+            for (const char* a = argv[++i]; *a;) {
+                char* end = nullptr;
+                irDecayBands.push_back(strtof(a, &end));
+                if (end == a || (*end && *end != ',') || irDecayBands.size() > 10) {
+                    std::cerr << "--ir-decay-bands takes HZ[,HZ...], at most 10" << std::endl;
+                    return 2;
+                }
+                a = *end ? end + 1 : end;
+            }
+        } else if (!strcmp(argv[i], "--ir-rt60") && i + 1 < argc) {
+            irRt60 = atof(argv[++i]);
+            if (!(irRt60 > 0.0)) {
+                std::cerr << "--ir-rt60 takes a decay time in seconds, > 0" << std::endl;
+                return 2;
+            }
         }
     }
     if (rate || period) fakejack_configure(rate ? rate : 44100, period ? period : 256);
@@ -106,6 +130,8 @@ int main(int argc, char** argv) {
         if (matchIrRate) c->setMatchIrRate(true);
         c->setIrShape(irShape);
         c->setIrEq(irEq);
+        if (irDecayReport) c->setIrDecayReport(true, irDecayBands);
+        if (irRt60 > 0.0) c->setIrRt60(irRt60);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;
             const auto deviceId = settings.str("conv[%d].cc.device", idx);

@@ -235,6 +235,53 @@ int mc_load_ir_eq(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, 
  * call.  `eq` is checked as by mc_load_ir_eq with session_rate = rate. */
 int mc_ir_eq_response(const mc_ir_eq *eq, uint32_t rate, const double *hz, uint32_t n, double *db);
 
+/* The decay of a loaded IR, measured on the device from the taps the engine convolves with (after conversion, shaping and
+ * EQ): the readout a convolution reverb shows for the IR it has loaded, and what mc_ir_shape.decay_t60 is aimed with.  No
+ * reference equivalent; single-engine, as shaping is.  x = the n stored taps as double, N = end ? min(end, n) : n; only taps
+ * [0, N) are searched and measured.
+ *   1. origin o: with onset_db < 0 the first m whose max(|L|, |R|) reaches peak * 10^(onset_db / 20) (float arithmetic, the
+ *      shaped load's onset search); with onset_db = 0, o = 0;
+ *   2. row group 0 is broadband, y = x.  Row group b >= 1 is x[0 .. N) run from rest at tap 0 (not at o: the filter has settled
+ *      by the onset) through two identical sections in cascade, each the Audio-EQ-Cookbook band-pass with 0 dB peak gain,
+ *      b = {al, 0, -al}, a = {1 + al, -2 c, 1 - al}, all divided by a0, with w0 = 2 pi centre_hz[b - 1] / rate, c = cos w0,
+ *      al = sin w0 / (2 q), in double from the float fields (transposed direct form II);
+ *   3. channel sets s = 0, 1, 2: e[m] = yL^2, yR^2, yL^2 + yR^2 for m in [o, N);
+ *   4. EDC[m] = sum of e[k] over k in [m, N) (the Schroeder integral), E = EDC[o], L[m] = 10 log10(EDC[m] / E); with E = 0 the
+ *      row's energy is 0 and every other entry is NaN;
+ *   5. a decay time over (hi, lo) dB: S = {m : lo <= L[m] <= hi}; NaN when L[N - 1] > lo (the curve never gets there) or S has
+ *      fewer than 2 taps; else a = the least-squares slope of L over x = m - min S and T = -60 / (a rate) seconds.  EDT uses
+ *      (0, -10), T20 (-5, -25), T30 (-5, -35);
+ *   6. k50 = o + floor(0.05 rate + 0.5), k80 = o + floor(0.08 rate + 0.5); C50 = 10 log10((E - EDC[k50]) / EDC[k50]) dB, NaN
+ *      when k50 >= N or EDC[k50] = 0; C80 likewise; D50 = (E - EDC[k50]) / E with C50's NaN rule;
+ *      Ts = sum (m - o) e[m] / E / rate seconds;
+ *   7. rows[(b 3 + s) 8 ..] = {E, EDT, T20, T30, C50, C80, D50, Ts};
+ *      curve[(b 3 + s) K + j] = max(L[o + floor(j (N - 1 - o) / (K - 1))], -400), K = curve_points.
+ * The curve of a finite IR always bends down towards tap N - 1, because the integral runs out there: a time fitted over a
+ * range that reaches into that bend reads short.  `end` is the caller's tool against a noise floor or a cut; no noise-floor
+ * compensation is attempted. */
+#define MC_DECAY_MAX_BANDS 10
+#define MC_DECAY_MAX_CURVE 1024
+typedef struct {
+    uint32_t struct_size;     /* sizeof(mc_decay_query) */
+    uint32_t rate;            /* the rate the stored taps are at, [8000, 384000] */
+    uint32_t n_bands;         /* 0 .. MC_DECAY_MAX_BANDS band-passed rows after the broadband row */
+    uint32_t curve_points;    /* 0, or 2 .. MC_DECAY_MAX_CURVE points of the decay curve per row */
+    float centre_hz[MC_DECAY_MAX_BANDS]; /* [10, 0.45 rate] */
+    float q;                  /* [0.1, 32]; per section; default 1.41421356 (one octave) */
+    float onset_db;           /* [-120, 0]; 0 = time zero is tap 0; default -20 */
+    uint64_t end;             /* taps [0, end) are analysed; 0 = all stored taps */
+} mc_decay_query;
+/* rate 44100, no bands, no curve, q sqrt 2, onset -20, end 0 */
+void mc_default_decay_query(mc_decay_query *q);
+/* rows: [(1 + n_bands) * 3 * 8]; curve: [(1 + n_bands) * 3 * curve_points], NULL when curve_points = 0; info = {origin tap,
+ * taps analysed N}.  Checked in this order, all before the engine or the device is touched (MC_ERR_ARG, the message names the
+ * field): the query (struct_size, rate, n_bands, curve_points - 1 is refused -, each used centre_hz, q, onset_db), the
+ * pointers, idx (an unloaded index: "IR not loaded").  MC_ERR_STATE in the single-transform form, which keeps no taps.
+ * Threading as mc_load_ir: not concurrently with mc_process*.  Runs on the engine's stream and returns when the results are in
+ * the caller's arrays.  Nothing the engine holds changes: later outputs, the stored taps, mc_ir_info and mc_ir_shape_info are
+ * bit for bit what they would have been.  Two calls with the same query on the same IR return the same bits. */
+int mc_ir_decay(mc_engine *e, uint64_t idx, const mc_decay_query *q, double *rows, double *curve, uint64_t info[2]);
+
 int mc_num_irs(const mc_engine *e);
 /* out[0..3] = sum h_L, sum h_R, sum h_L(-1)^m, sum h_R(-1)^m of the truncated IR; out[4] = taps, out[5] = partitions */
 int mc_ir_info(const mc_engine *e, uint64_t idx, double out[6]);
