@@ -19,7 +19,8 @@ MC_MAX_PREDELAY = 8192
 SYMBOLS = [
     "mc_abi_version", "mc_last_error", "mc_default_config", "mc_default_params", "mc_create", "mc_destroy",
     "mc_reset", "mc_set_period", "mc_load_ir", "mc_load_ir_resampled", "mc_default_ir_shape", "mc_load_ir_shaped", "mc_ir_shape_info",
-    "mc_default_ir_eq", "mc_load_ir_eq", "mc_ir_eq_response", "mc_default_decay_query", "mc_ir_decay", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
+    "mc_default_ir_eq", "mc_load_ir_eq", "mc_ir_eq_response", "mc_default_ir_damp", "mc_load_ir_damped", "mc_ir_damp_info", "mc_ir_damp_response",
+    "mc_default_decay_query", "mc_ir_decay", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
     "mc_enable_kernel_timing", "mc_get_kernel_stats", "mc_algorithmic_bytes_per_block", "mc_blocks_processed", "mc_preferred_batch",
@@ -108,6 +109,22 @@ class McIrEq(C.Structure):
     ]
 
 
+MC_DAMP_MAX_XOVERS = 3
+
+
+class McIrDamp(C.Structure):
+    """mc_ir_damp: a further decay per frequency band, applied by mc_load_ir_damped between the fade and the EQ."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_xovers", C.c_uint32),
+        ("xover_hz", C.c_float * MC_DAMP_MAX_XOVERS),
+        ("reserved", C.c_uint32),
+        ("decay_t60", C.c_uint64 * (MC_DAMP_MAX_XOVERS + 1)),
+        ("origin", C.c_uint64),
+    ]
+
+
 MC_DECAY_MAX_BANDS = 10
 MC_DECAY_MAX_CURVE = 1024
 
@@ -185,6 +202,11 @@ def load():
     L.mc_default_ir_eq.restype = None
     L.mc_load_ir_eq.argtypes = [vp, u64, fp, u64, u64, C.c_uint32, C.c_uint32, C.POINTER(McIrShape), C.POINTER(McIrEq)]
     L.mc_ir_eq_response.argtypes = [C.POINTER(McIrEq), C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double)]
+    L.mc_default_ir_damp.argtypes = [C.POINTER(McIrDamp)]
+    L.mc_default_ir_damp.restype = None
+    L.mc_load_ir_damped.argtypes = [vp, u64, fp, u64, u64, C.c_uint32, C.c_uint32, C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp)]
+    L.mc_ir_damp_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_ir_damp_response.argtypes = [C.POINTER(McIrDamp), C.c_uint32, u64, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double)]
     L.mc_default_decay_query.argtypes = [C.POINTER(McDecayQuery)]
     L.mc_default_decay_query.restype = None
     L.mc_ir_decay.argtypes = [vp, u64, C.POINTER(McDecayQuery), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64)]

@@ -4,6 +4,7 @@
 // The wet path is linear, so the bands filter the IR once instead of the signal for ever.  This is step 6b of the shaped load:
 // irshape.hip.h selects the n taps (ish_shape), then ieq_finish
 //   1. materialises the shaped taps before the gain as double2 [n] (k_eq_fill: ish_tap, the expression k_shape_apply uses);
+//   1a. damps that buffer in place when the load is mc_load_ir_damped's (step 6a, damp_run of irdamp.hip.h);
 //   2. runs every band over that buffer in place, in index order, as a chunked linear recurrence (below);
 //   3. measures max |tap| and sum (L^2 + R^2) of the result (k_eq_store<false>), derives the gain, stores (float)(tap * gain)
 //      and reduces the four sums mc_ir_info reports (k_eq_store<true>).
@@ -196,6 +197,9 @@ __global__ __launch_bounds__(ISH_THREADS) void k_eq_store(const double2* __restr
 }
 
 // -- host ------------------------------------------------------------------------------------------------------------
+// irdamp.hip.h: step 6a over the buffer ieq_finish has filled
+inline hipError_t damp_run(hipStream_t stream, double2* d_buf, uint64_t n, const DampPlan& plan);
+
 // The band's coefficients (include/mcconv.h), in double from the float fields.
 inline IeqCoef ieq_coef(const mc_eq_band& b, uint32_t rate) {
     const double w0 = 2.0 * M_PI * (double)b.freq_hz / (double)rate, c = std::cos(w0), al = std::sin(w0) / (2.0 * (double)b.q);
@@ -300,8 +304,9 @@ inline IeqMat ieq_matpow(IeqMat a, uint64_t p) {
 
 // The rest of a load with EQ once ish_shape has resolved the plan (the file's head).  Same contract as ish_shape's own tail:
 // *d_out = the n stored taps (the caller's), sums and info as there, info[7] = the bands applied.  Synchronises the stream.
+// damp: the taps are damped before the bands see them (null: not).
 inline hipError_t ieq_finish(hipStream_t stream, const float2* d_x, const IshPlan& pl, const mc_ir_shape& sh, const IeqCascade& eq,
-                             float2** d_out, uint64_t* n_out, double sums[4], double info[8]) {
+                             float2** d_out, uint64_t* n_out, double sums[4], double info[8], const DampPlan* damp) {
     const uint64_t n = pl.n;
     const unsigned grid = (unsigned)((n + ISH_THREADS - 1) / ISH_THREADS);       // k_eq_fill, k_eq_store
     const unsigned cgrid = (unsigned)((n + IEQ_SPAN - 1) / IEQ_SPAN);            // k_eq_chunk
@@ -319,6 +324,7 @@ inline hipError_t ieq_finish(hipStream_t stream, const float2* d_x, const IshPla
         hipLaunchKernelGGL(k_eq_fill, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x, pl, d_buf);
         er = hipGetLastError();
     }
+    if (er == hipSuccess && damp) er = damp_run(stream, d_buf, n, *damp);
     for (int k = 0; k <= eq.bands && er == hipSuccess; k++) {
         IeqStage cur{}, nxt{};
         if (k > 0) {

@@ -183,16 +183,19 @@ inline bool ish_is_off(const mc_ir_shape& s) {
 }
 
 // ireq.hip.h: the bands of a load with EQ and what finishes such a load once the plan stands (steps 3 to 8 with 6b)
+// (damp: irdamp.hip.h, step 6a of a damped load; null = none)
 struct IeqCascade;
+struct DampPlan;
 inline hipError_t ieq_finish(hipStream_t stream, const float2* d_x, const IshPlan& pl, const mc_ir_shape& sh, const IeqCascade& eq,
-                             float2** d_out, uint64_t* n_out, double sums[4], double info[8]);
+                             float2** d_out, uint64_t* n_out, double sums[4], double info[8], const DampPlan* damp = nullptr);
 
 // Shapes the F device frames d_x (at the session's rate) into a new device buffer of n <= cap taps, *d_out, which the caller
 // owns.  sums = the four mc_ir_info sums of the stored taps, info = what mc_ir_shape_info reports.  Synchronises the stream.
 // *n_out == 0 (and no buffer) when the shape leaves no frame.  eq = the bands of mc_load_ir_eq (null: none): the selection is
-// this function's, everything after it ieq_finish's.
+// this function's, everything after it ieq_finish's.  damp = the damping of mc_load_ir_damped (null: none; needs eq, which may
+// hold no band).
 inline hipError_t ish_shape(hipStream_t stream, const float2* d_x, uint64_t F, uint64_t cap, const mc_ir_shape& sh, float2** d_out,
-                            uint64_t* n_out, double sums[4], double info[8], const IeqCascade* eq = nullptr) {
+                            uint64_t* n_out, double sums[4], double info[8], const IeqCascade* eq = nullptr, const DampPlan* damp = nullptr) {
     *d_out = nullptr;
     *n_out = 0;
     IshPlan pl;
@@ -235,7 +238,7 @@ inline hipError_t ish_shape(hipStream_t stream, const float2* d_x, uint64_t F, u
     pl.reverse = (sh.flags & MC_SHAPE_REVERSE) != 0;
     pl.t60 = sh.decay_t60;
     pl.fade = std::min<uint64_t>(sh.fade_out, pl.n);
-    if (eq) return ieq_finish(stream, d_x, pl, sh, *eq, d_out, n_out, sums, info);
+    if (eq) return ieq_finish(stream, d_x, pl, sh, *eq, d_out, n_out, sums, info, damp);
 
     const unsigned grid = (unsigned)((pl.n + ISH_THREADS - 1) / ISH_THREADS);
     float2* d_y = nullptr;

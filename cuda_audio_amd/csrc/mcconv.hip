@@ -28,6 +28,7 @@
 #include "resample.hip.h"
 #include "irshape.hip.h"
 #include "ireq.hip.h"
+#include "irdamp.hip.h"
 #include "irdecay.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
@@ -97,8 +98,10 @@ struct IrEntry {
     uint64_t taps = 0;
     int P = 0;
     double sums[4] = {0, 0, 0, 0};
-    bool shaped = false;  // the last load was mc_load_ir_shaped with something on or mc_load_ir_eq with a band on: shape_info is what mc_ir_shape_info reports
+    bool shaped = false;  // the last load was mc_load_ir_shaped with something on, mc_load_ir_eq with a band on or mc_load_ir_damped with damping on: shape_info is what mc_ir_shape_info reports
     double shape_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    bool damped = false;  // the last load was mc_load_ir_damped with damping on: damp_info is what mc_ir_damp_info reports
+    double damp_info[4] = {0, 0, 0, 0};
 };
 
 }  // namespace
@@ -3272,13 +3275,13 @@ namespace {
 // The shaped load's own stage (irshape.hip.h): all `conv` frames at the session's rate on the device, shaped into a new buffer
 // of *n <= cap taps that the caller owns.  Nothing of the engine's IRs is touched here.
 int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, uint64_t cap, const uint32_t* rs, const mc_ir_shape& sh,
-                const IeqCascade* eq, float2** d_taps, uint64_t* n, double sums[4], double info[8]) {
+                const IeqCascade* eq, const DampPlan* damp, float2** d_taps, uint64_t* n, double sums[4], double info[8]) {
     float2* d_x = nullptr;
     HIP_TRY(hipMalloc(&d_x, sizeof(float2) * conv));
     double unused[4];
     hipError_t er = rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, d_x, conv, unused)
                        : hipMemcpy(d_x, lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, sh, d_taps, n, sums, info, eq);
+    if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, sh, d_taps, n, sums, info, eq, damp);
     (void)hipFree(d_x);
     if (er != hipSuccess) return fail(MC_ERR_HIP, "IR shaping failed: %s", hipGetErrorString(er));
     if (!*n) return fail(MC_ERR_ARG, "the shape leaves no frame of the IR (start %llu, %llu frames at the session's rate)",
@@ -3289,9 +3292,10 @@ int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, u
 // mc_load_ir, mc_load_ir_resampled and mc_load_ir_shaped: rs = {IR rate, session rate} converts the frames on the device
 // (resample.hip.h) before anything else sees them; null = the frames as given (the reference).  sh = a shape with something
 // on, applied on the device after the conversion (irshape.hip.h); null = none.  eq = the bands of mc_load_ir_eq that are on
-// (ireq.hip.h; with a shape, which may have everything off); null = none
+// (ireq.hip.h; with a shape, which may have everything off); null = none.  damp = the damping of mc_load_ir_damped (irdamp.hip.h;
+// with a shape and an eq, which may hold no band); null = none
 int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs, const mc_ir_shape* sh = nullptr,
-            const IeqCascade* eq = nullptr) {
+            const IeqCascade* eq = nullptr, const DampPlan* damp = nullptr) {
     // Convolution::prepare, conv.cu:207-253
     if (!e || !lr) return fail(MC_ERR_ARG, "null argument");
     if (idx >= (uint64_t)kMaxIrs) return fail(MC_ERR_ARG, "IR index %llu >= %d", (unsigned long long)idx, kMaxIrs);
@@ -3302,12 +3306,20 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
     float* d_lr = nullptr;
     uint64_t nshaped = 0;
     double rsum[4] = {0, 0, 0, 0}, sinfo[8];
+    const auto note_damp = [&](IrEntry& ir, uint64_t taps) {  // what mc_ir_damp_info reports of this load
+        ir.damped = damp != nullptr;
+        if (!damp) return;
+        int decays = 0;
+        for (int j = 0; j <= damp->X; j++) decays += damp->t60[j] != 0;
+        const double inf[4] = {(double)damp->X, (double)std::min<uint64_t>(damp->origin, taps), (double)decays, 0.0};
+        std::copy(inf, inf + 4, ir.damp_info);
+    };
     if (sh) {  // (the stream must be idle and out of the JACK path before the shaping kernels go onto it)
         int rc = e->sf ? MC_OK : drain_post(e);
         if (!rc && !e->sf) rc = leave_jack_path(e);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(e->stream));
-        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, eq, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo);
+        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, eq, damp, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo);
         if (rc) return rc;
     }
     if (e->sf) {
@@ -3316,6 +3328,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
         if (rc) return rc;
         e->irs[idx].shaped = sh != nullptr;
         if (sh) std::memcpy(e->irs[idx].shape_info, sinfo, sizeof(sinfo));
+        note_damp(e->irs[idx], nshaped);
         return MC_OK;
     }
     const uint64_t n = sh ? nshaped : std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
@@ -3397,6 +3410,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
     ir.P = P;
     ir.shaped = sh != nullptr;
     if (sh) std::memcpy(ir.shape_info, sinfo, sizeof(sinfo));
+    note_damp(ir, n);
     if ((int)idx + 1 > e->nirs) e->nirs = (int)idx + 1;
     e->spec_valid = e->dspec.valid = false;
     e->uniform_valid[0] = e->uniform_valid[1] = false;
@@ -3476,6 +3490,55 @@ int mc_ir_eq_response(const mc_ir_eq* eq, uint32_t rate, const double* hz, uint3
     if (rate < RS_MIN_RATE || rate > RS_MAX_RATE) return fail(MC_ERR_ARG, "rate %u outside [%u, %u]", rate, RS_MIN_RATE, RS_MAX_RATE);
     const IeqCascade cs = ieq_cascade(*eq, rate);
     for (uint32_t i = 0; i < n; i++) db[i] = ieq_response_db(cs, rate, hz[i]);
+    return MC_OK;
+}
+
+void mc_default_ir_damp(mc_ir_damp* d) {
+    if (!d) return;
+    std::memset(d, 0, sizeof(*d));
+    d->struct_size = (uint32_t)sizeof(*d);
+    d->xover_hz[0] = 250.f, d->xover_hz[1] = 2000.f, d->xover_hz[2] = 8000.f;
+}
+
+int mc_load_ir_damped(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
+                      const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp) {
+    mc_ir_eq noeq;
+    mc_default_ir_eq(&noeq);
+    if (!eq) eq = &noeq;
+    if (!damp || !damp->n_xovers) return mc_load_ir_eq(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq);
+    // as in mc_load_ir_eq, everything is checked before the pointers and before any HIP call
+    if (const char* bad = damp_check(damp, ir_rate, session_rate)) return fail(MC_ERR_ARG, "%s", bad);
+    int on = 0;
+    if (const char* bad = ieq_check(eq, ir_rate, session_rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
+    mc_ir_shape off;
+    mc_default_ir_shape(&off);
+    if (!shape) shape = &off;
+    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
+    const IeqCascade cs = ieq_cascade(*eq, session_rate);  // (no band on: ieq_finish runs with none)
+    const DampPlan pl = damp_plan(*damp, session_rate);
+    const uint32_t rs[2] = {ir_rate, session_rate};
+    return load_ir(e, idx, lr, frames, nframes, ir_rate != session_rate ? rs : nullptr, shape, &cs, &pl);
+}
+
+int mc_ir_damp_info(const mc_engine* e, uint64_t idx, double out[4]) {
+    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
+    if (!e->irs[idx].damped) return fail(MC_ERR_STATE, "IR %llu was not loaded with damping", (unsigned long long)idx);
+    for (int i = 0; i < 4; i++) out[i] = e->irs[idx].damp_info[i];
+    return MC_OK;
+}
+
+int mc_ir_damp_response(const mc_ir_damp* d, uint32_t rate, uint64_t tap, const double* hz, uint32_t n, double* db) {
+    if (!d) return fail(MC_ERR_ARG, "null damp");
+    if (d->n_xovers)
+        if (const char* bad = damp_check(d, rate, rate)) return fail(MC_ERR_ARG, "%s", bad);
+    if (n && (!hz || !db)) return fail(MC_ERR_ARG, "null argument");
+    if (!d->n_xovers) {
+        for (uint32_t i = 0; i < n; i++) db[i] = 0.0;
+        return MC_OK;
+    }
+    const DampPlan pl = damp_plan(*d, rate);
+    for (uint32_t i = 0; i < n; i++) db[i] = damp_response_db(pl, rate, tap, hz[i]);
     return MC_OK;
 }
 

@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import MC_BLOCK, McCcValue, McConfig, McDecayQuery, McIrEq, McIrShape, McKernelStats, check
+from ._lib import MC_BLOCK, McCcValue, McConfig, McDecayQuery, McIrDamp, McIrEq, McIrShape, McKernelStats, check
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
 CONV_MAX_SPEED = 1024             # conv.h:22-24
@@ -98,6 +98,43 @@ def eq_response(eq, rate, hz):
 
 
 @dataclasses.dataclass
+class IrDamp:
+    """What prepare(damp=...) damps an IR with after the fade and before the EQ (mc_ir_damp, include/mcconv.h): 1 to 3 crossover
+    frequencies (Hz, ascending) and one decay per band, low to high, len(xovers) + 1 of them: a further 60 dB at `decay`
+    taps past `origin` (frames at the session's rate; 0 = that band is left alone).  No crossover switches damping off."""
+
+    xovers: tuple = (400, 1600)
+    decay: tuple = (0, 4800, 1600)
+    origin: int = 0
+
+    def to_c(self):
+        if len(self.xovers) > _lib.MC_DAMP_MAX_XOVERS:
+            raise ValueError(f"{len(self.xovers)} crossovers; at most {_lib.MC_DAMP_MAX_XOVERS}")
+        if self.xovers and len(self.decay) != len(self.xovers) + 1:
+            raise ValueError(f"{len(self.xovers)} crossovers make {len(self.xovers) + 1} bands, not {len(self.decay)} decays")
+        d = McIrDamp()
+        _lib.load().mc_default_ir_damp(C.byref(d))
+        d.n_xovers = len(self.xovers)
+        for k, hz in enumerate(self.xovers):
+            d.xover_hz[k] = float(hz)
+        if self.xovers:
+            for j, t60 in enumerate(self.decay):
+                d.decay_t60[j] = int(t60)
+        d.origin = int(self.origin)
+        return d
+
+
+def damp_response(damp, rate, tap, hz):
+    """The quasi-static response in dB of `damp` (an IrDamp) at stored tap `tap` and the frequencies hz (Hz) in a session at
+    `rate` Hz: mc_ir_damp_response, host arithmetic only."""
+    hz = np.ascontiguousarray(hz, dtype=np.float64).reshape(-1)
+    db = np.empty_like(hz)
+    dp = C.POINTER(C.c_double)
+    check(_lib.load().mc_ir_damp_response(C.byref(damp.to_c()), int(rate), int(tap), hz.ctypes.data_as(dp), hz.size, db.ctypes.data_as(dp)))
+    return db
+
+
+@dataclasses.dataclass
 class DecayQuery:
     """What ir_decay measures (mc_decay_query, include/mcconv.h): the broadband row and one row per centre frequency of `bands`
     (two band-pass sections of quality q each), time zero at the first tap within onset_db of the peak (0: tap 0), over taps
@@ -136,6 +173,21 @@ def decay_for_rt60(measured_s, target_s, rate):
     if not (math.isfinite(measured_s) and math.isfinite(target_s) and 0.0 < target_s < measured_s):
         raise ValueError(f"need 0 < target ({target_s}) < measured ({measured_s}), both finite")
     return int(round(float(rate) / (1.0 / target_s - 1.0 / measured_s)))
+
+
+def damp_for_rt60(measured_s, target_s, rate):
+    """IrDamp.decay for bands whose decay times were measured as measured_s (seconds, one per band, low to high) and are
+    wanted as target_s: decay_for_rt60 per band, and 0 (the band is left alone) where the target is None, NaN or not below
+    the measured time.  The bands overlap, so the result is a first aim to be iterated against ir_decay."""
+    if len(measured_s) != len(target_s):
+        raise ValueError(f"{len(measured_s)} measured times, {len(target_s)} targets")
+    out = []
+    for m, t in zip(measured_s, target_s):
+        if t is None or math.isnan(float(t)) or not float(t) < float(m):
+            out.append(0)
+        else:
+            out.append(decay_for_rt60(m, t, rate))
+    return tuple(out)
 
 
 class _CCValueView:
@@ -234,7 +286,7 @@ class Convolution:
         check(self._L.mc_set_period(self._h, nframes))
 
     # -- reference surface ----------------------------------------------------
-    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None):
+    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None, damp=None):
         """Convolution::prepare (conv.cu:207-253).  `wav` is float32 [frames, 2]
         (what WavFile.buffer holds) or an object with a `.buffer` of that shape.
         ir_rate (Hz; default: `wav.sampleRate` when it has one): when both it and the engine's sample_rate are known and
@@ -242,10 +294,18 @@ class Convolution:
         shape (an IrShape): trim, reverse, decay, fade and normalise the IR on the device, after the conversion and before
         the truncation (mc_load_ir_shaped); ir_shape_info(idx) then tells what was done.
         eq (an IrEq): filter the shaped taps with its bands before the normalisation (mc_load_ir_eq); the engine needs a
-        sample_rate, and ir_rate defaults to it."""
+        sample_rate, and ir_rate defaults to it.
+        damp (an IrDamp): a further decay per frequency band, after the fade and before the EQ (mc_load_ir_damped); the rates
+        as for eq; ir_damp_info(idx) then tells what was done."""
         lr = _f32(getattr(wav, "buffer", wav)).reshape(-1, 2)
         if ir_rate is None:
             ir_rate = getattr(wav, "sampleRate", None)
+        if damp is not None and damp.xovers:
+            session = int(self.sample_rate or 0)
+            check(self._L.mc_load_ir_damped(self._h, idx, _fp(lr), lr.shape[0], nframes, session if ir_rate is None else int(ir_rate), session,
+                                            C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
+                                            C.byref(damp.to_c())))
+            return
         if eq is not None:
             session = int(self.sample_rate or 0)
             check(self._L.mc_load_ir_eq(self._h, idx, _fp(lr), lr.shape[0], nframes, session if ir_rate is None else int(ir_rate), session,
@@ -370,6 +430,13 @@ class Convolution:
         check(self._L.mc_ir_shape_info(self._h, idx, out))
         return dict(frames=int(out[0]), onset=int(out[1]), first=int(out[2]), taps=int(out[3]), gain=out[4], peak=out[5], energy=out[6],
                     eq_bands=int(out[7]))
+
+    def ir_damp_info(self, idx):
+        """What the damped load of IR idx did (mc_ir_damp_info): the crossovers, the tap the envelopes started at and the
+        bands that were given a decay.  McError (MC_ERR_STATE) for an IR whose last load was not damped."""
+        out = (C.c_double * 4)()
+        check(self._L.mc_ir_damp_info(self._h, idx, out))
+        return dict(xovers=int(out[0]), origin=int(out[1]), damped_bands=int(out[2]))
 
     def ir_decay(self, idx, bands=(), q=None, onset_db=-20.0, end=0, curve_points=0, rate=None):
         """The decay of the stored taps of IR idx, measured on the device (mc_ir_decay; include/mcconv.h has the definition).

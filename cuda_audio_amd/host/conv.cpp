@@ -27,6 +27,11 @@ int mc_ir_shape_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 void mc_default_ir_eq(mc_ir_eq*) __attribute__((weak));
 int mc_load_ir_eq(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*) __attribute__((weak));
 int mc_ir_eq_response(const mc_ir_eq*, uint32_t, const double*, uint32_t, double*) __attribute__((weak));
+// (... and no damping)
+void mc_default_ir_damp(mc_ir_damp*) __attribute__((weak));
+int mc_load_ir_damped(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*)
+    __attribute__((weak));
+int mc_ir_damp_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 // (... and no decay measurement)
 void mc_default_decay_query(mc_decay_query*) __attribute__((weak));
 int mc_ir_decay(mc_engine*, uint64_t, const mc_decay_query*, double*, double*, uint64_t*) __attribute__((weak));
@@ -119,9 +124,32 @@ void Convolution::setIrEq(const IrEq& eq) {
     _irEq = eq;
 }
 
-// irRate = sessionRate = 0: the frames are loaded at the rate they have (never with a band of eq on)
+void Convolution::setIrDamp(const IrDamp& damp) {
+    if (!damp.off() && _group) {
+        Log::error("conv", "IR damping is not available with several devices (mc_group_load_ir takes no damping)");
+        std::exit(2);
+    }
+    if (damp.xovers.size() > MC_DAMP_MAX_XOVERS || (!damp.off() && damp.decaySeconds.size() != damp.xovers.size() + 1)) {
+        Log::error("conv", "%zu crossovers (at most %d) need one decay per band, %zu given", damp.xovers.size(), MC_DAMP_MAX_XOVERS,
+                   damp.decaySeconds.size());
+        std::exit(2);
+    }
+    _irDamp = damp;
+}
+
+uint64_t Convolution::dampFrames(double seconds, double rate) {
+    if (!(seconds > 0.0) || !std::isfinite(seconds)) return 0;
+    const double f = std::nearbyint(seconds * rate);
+    return f < 1.0 ? 1 : (uint64_t)f;
+}
+
+// irRate = sessionRate = 0: the frames are loaded at the rate they have (never with a band of eq on, never with damping)
 void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
-                             const IrEq& eq) {
+                             const IrEq& eq, const IrDamp& damp) {
+    if (!damp.off() && (!mc_load_ir_damped || !mc_default_ir_damp || !mc_ir_damp_info)) {
+        Log::error("conv", "the engine has no IR damping (mc_load_ir_damped)");
+        std::exit(2);
+    }
     if (!mc_load_ir_shaped || !mc_default_ir_shape || !mc_ir_shape_info) {
         Log::error("conv", "the engine has no IR shaping (mc_load_ir_shaped)");
         std::exit(2);
@@ -143,13 +171,22 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
     s.target = shape.target;
     if (irRate && irRate != sessionRate) Log::info(name, "IR %zu: %u Hz -> %u Hz", idx, irRate, sessionRate);
     mc_ir_eq q;
-    if (eq.off())
-        check(mc_load_ir_shaped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s), "mc_load_ir_shaped");
-    else {
+    mc_ir_damp d;
+    if (!eq.off()) {
         mc_default_ir_eq(&q);
         for (size_t k = 0; k < eq.bands.size(); k++) q.band[k] = mc_eq_band{(uint32_t)eq.bands[k].kind, eq.bands[k].hz, eq.bands[k].gainDb, eq.bands[k].q};
-        check(mc_load_ir_eq(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, &q), "mc_load_ir_eq");
     }
+    if (!damp.off()) {
+        mc_default_ir_damp(&d);
+        d.n_xovers = (uint32_t)damp.xovers.size();
+        for (size_t k = 0; k < damp.xovers.size(); k++) d.xover_hz[k] = damp.xovers[k];
+        for (size_t j = 0; j < damp.decaySeconds.size(); j++) d.decay_t60[j] = dampFrames(damp.decaySeconds[j], (double)sessionRate);
+        d.origin = damp.origin;
+        check(mc_load_ir_damped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, &d), "mc_load_ir_damped");
+    } else if (eq.off())
+        check(mc_load_ir_shaped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s), "mc_load_ir_shaped");
+    else
+        check(mc_load_ir_eq(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, &q), "mc_load_ir_eq");
     double info[8];
     check(mc_ir_shape_info(_engine, idx, info), "mc_ir_shape_info");
     Log::info(name, "IR %zu shaped: onset %llu, first kept frame %llu, %llu taps, gain %+.2f dB", idx, (unsigned long long)info[1],
@@ -159,6 +196,14 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         double db = 0.0;
         check(mc_ir_eq_response(&q, sessionRate, &hz, 1, &db), "mc_ir_eq_response");
         Log::info(name, "IR %zu equalised: %d bands, %+.2f dB at 1 kHz", idx, (int)info[7], db);
+    }
+    if (!damp.off()) {
+        double di[4];
+        check(mc_ir_damp_info(_engine, idx, di), "mc_ir_damp_info");
+        std::string decays;
+        for (uint32_t j = 0; j <= d.n_xovers; j++) decays += (j ? ", " : "") + std::to_string((unsigned long long)d.decay_t60[j]);
+        Log::info(name, "IR %zu damped: %d crossovers, origin %llu, %d bands with a decay (%s frames)", idx, (int)di[0], (unsigned long long)di[1],
+                  (int)di[2], decays.c_str());
     }
 }
 
@@ -270,8 +315,8 @@ void Convolution::aimRt60(const PendingIr& p) {
 void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
     const uint64_t frames = p.lr.size() / 2;
     const bool convert = p.match && p.rate && p.rate != samplerate;
-    if (!p.eq.off()) {  // (the bands are laid out at the client's rate; frames that are not converted count as being at it)
-        loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : (unsigned)samplerate, (unsigned)samplerate, shape, p.eq);
+    if (!p.eq.off() || !p.damp.off()) {  // (bands and crossovers are laid out at the client's rate; frames that are not converted count as being at it)
+        loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : (unsigned)samplerate, (unsigned)samplerate, shape, p.eq, p.damp);
         return;
     }
     if (!shape.off()) {
@@ -300,9 +345,9 @@ void Convolution::loadPendingIrs() {
 }
 
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
-    if (_matchIrRate || !_irEq.off() || _decayReport || _rt60 > 0.0) {  // (loaded by onStart(), once the client's rate is known)
+    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
-        _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate});
+        _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp});
         if (idx + 1 > _nirs) _nirs = idx + 1;
         return;
     }

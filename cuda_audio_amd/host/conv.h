@@ -104,6 +104,21 @@ public:
         }
     };
     void setIrEq(const IrEq& eq);
+    // The damping every IR prepared from now on gets on load, after its shape's fade and before the EQ (mc_ir_damp of
+    // include/mcconv.h; no reference equivalent): 1 to 3 crossover frequencies, ascending, and one further decay per band, low to
+    // high, in seconds (0 = that band is left alone), counted from stored tap `origin`.  The seconds become frames at the
+    // client's sample rate (dampFrames), so prepare() keeps the frames and onStart() loads them, as with setIrEq.  One more log
+    // line per IR.  Single device only, as setIrShape.
+    struct IrDamp {
+        std::vector<float> xovers;
+        std::vector<double> decaySeconds;  // xovers.size() + 1 of them
+        uint64_t origin;
+        IrDamp() : origin(0) {}  // (not a default member initialiser: IrDamp() is a default argument inside this class)
+        bool off() const { return xovers.empty(); }
+    };
+    void setIrDamp(const IrDamp& damp);
+    // mc_ir_damp.decay_t60 of a decay given in seconds at rate Hz: the nearest frame, at least 1 for anything above 0
+    static uint64_t dampFrames(double seconds, double rate);
     // The decay of a loaded IR, measured by the engine from the taps it convolves with (mc_ir_decay of include/mcconv.h, which
     // has the definition; no reference equivalent).  rate = 0: the client's sample rate (known from onStart() on).
     struct DecayQuery {
@@ -157,6 +172,7 @@ private:
         IrShape shape;          // as set when the IR was prepared
         IrEq eq;
         bool match;             // setMatchIrRate was on
+        IrDamp damp;
     };
     std::vector<PendingIr> _pendingIrs;  // (rate matching) prepared, loaded by onStart()
     void loadPendingIrs();
@@ -168,8 +184,9 @@ private:
     double _rt60 = 0.0;
     IrShape _irShape;
     IrEq _irEq;
+    IrDamp _irDamp;
     void loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
-                    const IrEq& eq = IrEq());
+                    const IrEq& eq = IrEq(), const IrDamp& damp = IrDamp());
     void pushParams();
     void pullVsteps();
 };

@@ -16,7 +16,9 @@
 // Convolution::setIrEq; --ir-decay-report: after each IR is loaded one log line with its decay (origin, EDT, T20, T30, C50, C80, Ts
 // of the broadband LR row, measured by the engine: Convolution::setIrDecayReport), --ir-decay-bands HZ[,HZ...]: one more line per
 // centre frequency; --ir-rt60 SECONDS: every IR whose measured decay time is longer is loaded again with the further exponential
-// decay that takes it there, on top of --ir-decay, Convolution::setIrRt60).
+// decay that takes it there, on top of --ir-decay, Convolution::setIrRt60; --ir-damp HZ[,HZ[,HZ]]:SEC[,SEC...]: every IR is damped on
+// load, 1 to 3 ascending crossover frequencies and one further decay time in seconds per band, low to high, 0 for none, turned into
+// frames at the client's sample rate, Convolution::setIrDamp; --ir-damp-origin TAP: the stored tap the damping's envelopes start at).
 #include <cassert>
 #include <cstdlib>
 #include <cstring>
@@ -42,6 +44,7 @@ int main(int argc, char** argv) {
     bool irDecayReport = false;
     std::vector<float> irDecayBands;
     double irRt60 = 0.0;
+    Convolution::IrDamp irDamp;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--periods") && i + 1 < argc) periods = strtoull(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "--settings") && i + 1 < argc) settingsPath = argv[++i];
@@ -102,6 +105,38 @@ int main(int argc, char** argv) {
                 }
                 a = *end ? end + 1 : end;
             }
+        } else if (!strcmp(argv[i], "--ir-damp") && i + 1 < argc) {
+            const char* a = argv[++i];
+            const char* colon = strchr(a, ':');
+            bool good = colon != nullptr;
+            irDamp.xovers.clear();
+            irDamp.decaySeconds.clear();
+            for (int part = 0; part < 2 && good; part++) {  // HZ[,HZ[,HZ]] up to the colon, then SEC[,SEC...]
+                const char* stop = part ? a + strlen(a) : colon;
+                for (const char* p = part ? colon + 1 : a; good;) {
+                    char* end = nullptr;
+                    const double v = strtod(p, &end);
+                    good = end != p && end <= stop && (end == stop || *end == ',') && v >= 0.0 && v < 1e9;
+                    if (!good) break;
+                    if (part) irDamp.decaySeconds.push_back(v);
+                    else irDamp.xovers.push_back((float)v);
+                    if (end == stop) break;
+                    p = end + 1;
+                }
+            }
+            if (!good || irDamp.xovers.empty() || irDamp.xovers.size() > 3 || irDamp.decaySeconds.size() != irDamp.xovers.size() + 1) {
+                std::cerr << "--ir-damp takes HZ[,HZ[,HZ]]:SEC[,SEC...]: 1 to 3 crossovers and one decay time in seconds per band (one more than crossovers), 0 for none"
+                          << std::endl;
+                return 2;
+            }
+        } else if (!strcmp(argv[i], "--ir-damp-origin") && i + 1 < argc) {
+            char* end = nullptr;
+            const char* a = argv[++i];
+            irDamp.origin = strtoull(a, &end, 10);
+            if (end == a || *end || *a == '-') {
+                std::cerr << "--ir-damp-origin takes a tap index" << std::endl;
+                return 2;
+            }
         } else if (!strcmp(argv[i], "--ir-rt60") && i + 1 < argc) {
             irRt60 = atof(argv[++i]);
             if (!(irRt60 > 0.0)) {
@@ -130,6 +165,7 @@ int main(int argc, char** argv) {
         if (matchIrRate) c->setMatchIrRate(true);
         c->setIrShape(irShape);
         c->setIrEq(irEq);
+        c->setIrDamp(irDamp);
         if (irDecayReport) c->setIrDecayReport(true, irDecayBands);
         if (irRt60 > 0.0) c->setIrRt60(irRt60);
         for (int i = 0; i < 2; i++) {

@@ -153,7 +153,8 @@ int mc_load_ir_resampled(mc_engine *e, uint64_t idx, const float *lr, uint64_t f
  *   4. the n frames are reversed (MC_SHAPE_REVERSE);
  *   5. tap m is multiplied by 10^(-3 m / decay_t60);
  *   6. the last f = min(fade_out, n) taps by (1 + cos(pi (k + 1) / (f + 1))) / 2, k = 0 .. f - 1;
- *   6b. (mc_load_ir_eq only) the n taps run through the EQ bands, from rest at tap 0;
+ *   6a. (mc_load_ir_damped only) the n taps are damped: a further decay per frequency band (mc_ir_damp below);
+ *   6b. (mc_load_ir_eq and mc_load_ir_damped) the n taps run through the EQ bands, from rest at tap 0;
  *   7. everything by gain = target / peak or target / energy of the result (1 when that measure is 0);
  *   8. the taps are rounded to float and transformed as the plain load's are (steps 4-7 are carried in double). */
 #define MC_SHAPE_REVERSE 1u
@@ -234,6 +235,57 @@ int mc_load_ir_eq(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, 
 /* db[i] = 20 log10 |H(e^{j 2 pi hz[i] / rate})| of the cascade (0 with no band on).  Host arithmetic only: no engine, no HIP
  * call.  `eq` is checked as by mc_load_ir_eq with session_rate = rate. */
 int mc_ir_eq_response(const mc_ir_eq *eq, uint32_t rate, const double *hz, uint32_t n, double *db);
+
+/* Damping of an IR on load: a decay time per frequency band, the control a convolution reverb puts next to its decay time
+ * (hi / lo damp).  mc_ir_shape.decay_t60 is one broadband envelope and an EQ band is time-invariant; damping splits the IR
+ * into up to four bands and gives each an envelope of its own.  No reference equivalent; single-engine, as shaping is.
+ *
+ * Damping is step 6a of the order of operations above: after the fade (6), before the EQ bands (6b).  The normalisation (7),
+ * mc_ir_shape_info's gain, peak and energy and mc_ir_info's sums are those of the damped taps (damped and equalised with
+ * EQ on).  n does not change: what the filters ring past tap n - 1 is dropped, as for EQ.
+ *
+ * x = the n taps after step 6, as double; X = n_xovers (1 .. 3); rate = session_rate.
+ *   Crossover filters.  For k = 1 .. X, P_k is x run from rest at tap 0 through two identical sections in cascade, each the
+ *     HIGHCUT of the table above at xover_hz[k - 1] with q = (double)0.70710678f (coefficients in double from the float
+ *     fields), in transposed direct form II, in double.  The bands are B_0 = P_1, B_j = P_(j+1) - P_j, B_X = x - P_X; they
+ *     telescope to x.
+ *   Envelopes.  o = min(origin, n), t(m) = max(m, o) - o, and for band j = 0 .. X, low to high,
+ *     g_j[m] = decay_t60[j] ? exp2(-(t(m) 3 log2(10)) / decay_t60[j]) : 1, step 5's expression counted from o.
+ *   Output.  y[m] = g_X[m] x[m] + sum over k = 1 .. X of (g_(k-1)[m] - g_k[m]) P_k[m], added in that order: sum_j g_j B_j
+ *     rearranged so that X filters and no band buffer are needed.  Hence
+ *       - equal decays give y = g x exactly (the filters drop out): the broadband envelope counted from o;
+ *       - all decays 0, or origin >= n, give y = x.
+ * Two sections per crossover, not one: with a single 12 dB / octave section an undamped low band leaks into the band above it
+ * and dominates that band's late decay.  The complement x - P_X keeps a 6 dB / octave skirt whatever the order, so a band's
+ * decay curve is bent, not straight: aiming by 1 / T = 1 / T_before + rate / decay_t60 is approximate and meant
+ * to be iterated against mc_ir_decay. */
+#define MC_DAMP_MAX_XOVERS 3
+typedef struct {
+    uint32_t struct_size;                        /* sizeof(mc_ir_damp) = 64 */
+    uint32_t n_xovers;                           /* 0 = off: every other field ignored */
+    float xover_hz[MC_DAMP_MAX_XOVERS];          /* the first n_xovers: finite, [10, 0.45 session_rate], strictly ascending */
+    uint32_t reserved;
+    uint64_t decay_t60[MC_DAMP_MAX_XOVERS + 1];  /* band j = 0 .. n_xovers, low to high: a further 60 dB at tap origin + decay_t60[j]; 0 = none */
+    uint64_t origin;                             /* stored tap the envelopes start at (clamped to n) */
+} mc_ir_damp;
+/* off; xover_hz = {250, 2000, 8000}; decays 0; origin 0 */
+void mc_default_ir_damp(mc_ir_damp *d);
+/* mc_load_ir_eq (shape, eq = NULL: everything off) with `damp` applied as step 6a.  With damp NULL or n_xovers = 0 the call is
+ * mc_load_ir_eq itself, bit for bit (and so, with shape and eq off too, the plain or the resampled load).  With damping on
+ * everything is checked before the engine or the device is touched (MC_ERR_ARG, the message names the field, the engine stays
+ * as it was), in this order: struct_size; n_xovers <= MC_DAMP_MAX_XOVERS; session_rate and ir_rate (both in [8000, 384000];
+ * equal rates mean no conversion, 0 / 0 is refused because the crossovers need the session's rate); each used xover_hz and
+ * their order; then shape and eq as by mc_load_ir_eq.  A damped load counts as shaped: mc_ir_shape_info reports it with its
+ * eight slots as they are, mc_ir_damp_info the rest.  The same frames, shape, bands and damping store the same bits. */
+int mc_load_ir_damped(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
+                      uint32_t session_rate, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp);
+/* out = {crossovers, origin used (o), bands with a decay, 0}; MC_ERR_STATE unless the IR's last load damped */
+int mc_ir_damp_info(const mc_engine *e, uint64_t idx, double out[4]);
+/* The quasi-static response at stored tap `tap` (m above, with o taken as `origin`): db[i] = 20 log10 |g_X + sum over k of
+ * (g_(k-1) - g_k) H_k(e^{j 2 pi hz[i] / rate})^2|, H_k one section of crossover k: what a slowly decaying tone of that frequency
+ * is scaled by at that time.  0 dB with damping off.  Host arithmetic only: no engine, no HIP call.  `d` is checked as by
+ * mc_load_ir_damped with ir_rate = session_rate = rate. */
+int mc_ir_damp_response(const mc_ir_damp *d, uint32_t rate, uint64_t tap, const double *hz, uint32_t n, double *db);
 
 /* The decay of a loaded IR, measured on the device from the taps the engine convolves with (after conversion, shaping and
  * EQ): the readout a convolution reverb shows for the IR it has loaded, and what mc_ir_shape.decay_t60 is aimed with.  No
