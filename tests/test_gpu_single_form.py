@@ -41,13 +41,22 @@ def _engine_stream(c, x, events, block=256):
     return out
 
 
-def test_ir_spectra_carry_the_split_quirks(oracle_mod, gpu_lib):
+# max error of the stored IR spectra against numpy's float64 transform, in units of the largest bin: 2e-6 at 8192; above, 4 x what
+# was measured on an MI355X, never above 1e-4 - a structurally wrong bin errs by the order of the scale
+# (measured: 2.08e-7 at 131072, 1.70e-7 at 262144, 1.82e-7 at 524288, 1.96e-7 at 1048576; 1.42e-7 at 8192)
+SPECTRA_BAR = {8192: 2e-6, 131072: 8.4e-7, 262144: 6.8e-7, 524288: 7.3e-7, 1048576: 7.9e-7}
+assert all(v <= 1e-4 for v in SPECTRA_BAR.values())
+
+
+@pytest.mark.parametrize("n_ref", list(SPECTRA_BAR))
+def test_ir_spectra_carry_the_split_quirks(oracle_mod, gpu_lib, n_ref):
     """Convolution::prepare (conv.cu:207-253): truncation to n_ref - nframes taps, packed transform, two-for-one split
-    whose s == 0 shortcut leaves H_L[0] = sum L + j sum R and H_R[0] = 0 (Q1); against numpy's transform."""
+    whose s == 0 shortcut leaves H_L[0] = sum L + j sum R and H_R[0] = 0 (Q1); against numpy's transform.  With
+    M = n_ref / 512 the column pass (k_sf_ir_cols) takes AT = max(1, min(8, 2048 / M)) columns per workgroup: 8, 8, 4, 2, 1
+    at these sizes."""
     from cuda_audio_amd.synth import make_ir
 
-    n_ref = 8192
-    ir = make_ir(9000, seed=3)  # longer than n_ref - 1024: truncated
+    ir = make_ir(n_ref + 808, seed=3)  # longer than n_ref - 1024: truncated
     c = _single(n_ref)
     c.prepare(0, ir)
     got = c.debug_read(0, 0, np.float32, 0, 2 * n_ref).reshape(2, n_ref // 2, 2)
@@ -61,9 +70,11 @@ def test_ir_spectra_carry_the_split_quirks(oracle_mod, gpu_lib):
     lr = np.asarray(ir, np.float64).reshape(-1, 2)[:n]
     want = [np.fft.fft(lr[:, ch], n_ref)[: n_ref // 2] for ch in range(2)]
     scale = max(np.abs(w).max() for w in want)
-    for ch in range(2):
-        assert np.abs(got[ch, 1:] - want[ch][1:]).max() <= 2e-6 * scale
-    assert abs(got[0, 0] - (lr[:, 0].sum() + 1j * lr[:, 1].sum())) <= 1e-5 * scale
+    worst = max(np.abs(got[ch, 1:] - want[ch][1:]).max() for ch in range(2)) / scale
+    dc = abs(got[0, 0] - (lr[:, 0].sum() + 1j * lr[:, 1].sum())) / scale
+    print(f"n_ref {n_ref}: max error {worst:.3e} of the largest bin ({scale:.3f}), H_L[0] {dc:.3e}")
+    assert worst <= SPECTRA_BAR[n_ref]
+    assert dc <= 1e-5
     assert got[1, 0] == 0
 
 
@@ -98,6 +109,49 @@ def test_cold_start_and_steady_state(oracle_mod, gpu_lib, monkeypatch, n_ref, ta
     assert rms(want) > 0.02
     err = rms(got - want)
     assert err <= RMS_TOL, f"rms {err:.3e} (signal {rms(want):.3e})"
+
+
+def test_ring_wraps_at_the_shipped_size(oracle_mod, gpu_lib):
+    """136 calls of 1024 frames at n_ref = 131072: the origin of the accumulator ring passes n_ref, and the last 8 calls emit
+    slots that were written, emitted and cleared once before.  IRs of stationary noise fill the accumulator to its far end;
+    they are quiet enough that nothing saturates, and there is no dry signal: the outputs are the accumulator alone."""
+    from single_form_np import flat_ir, white_input
+
+    n_ref, period, ncalls = 131072, 1024, 136
+    irs = [flat_ir(n_ref - 1024, 100, 0.0015), flat_ir(n_ref - 1024, 200, 0.0015)]
+    x = white_input(ncalls * period, 7)
+    p0 = dict(BASE, select=0, predelay=301, wet=0.6, panWet=0.3, dry=0.0)
+    p1 = dict(BASE, select=1, wet=0.4, level=0.8, panWet=-0.5, dry=0.0)
+    ev = {0: ((0, p0), (1, p1))}
+    want = _oracle_stream(oracle_mod, n_ref, irs, x, ev, block=period)
+    assert ncalls * period > n_ref + 7 * period
+    assert rms(want[:, -8 * period:]) > 0.01 and np.abs(want).max() < 0.9
+    c = _single(n_ref, period=period, max_batch=8)
+    for i, ir in enumerate(irs):
+        c.prepare(i, ir)
+    got = _engine_stream(c, x, ev, block=period)
+    c.close()
+    err, late = rms(got - want), rms(got[:, -8 * period:] - want[:, -8 * period:])
+    print(f"rms {err:.3e}, last 8 calls {late:.3e} (signal {rms(want[:, -8 * period:]):.3e})")
+    assert err <= RMS_TOL and late <= RMS_TOL, f"rms {err:.3e}, last 8 calls {late:.3e}"
+
+
+def test_sizes_above_the_largest_are_refused(oracle_mod, gpu_lib):
+    """n_ref = 2^21: a row of M = 4096 entries is beyond what the LDS transforms are laid out for; mc_create refuses, and the
+    next engine works."""
+    from cuda_audio_amd._lib import McError
+    from cuda_audio_amd.synth import make_input, make_ir
+
+    with pytest.raises(McError):
+        _single(2097152)
+    ir = make_ir(2000, seed=1, norm=0.3)
+    x = make_input(8 * 256, seed=2)
+    want = _oracle_stream(oracle_mod, 4096, [ir], x, {})
+    c = _single(4096)
+    c.prepare(0, ir)
+    got = _engine_stream(c, x, {})
+    c.close()
+    assert rms(want) > 0.01 and rms(got - want) <= RMS_TOL
 
 
 def test_ir_switches_and_controller_changes(oracle_mod, gpu_lib):
