@@ -903,6 +903,7 @@ struct OutArgs {
     int blk0;                // block of the batch this launch starts at
     int out_from;            // whole batch: blocks < out_from are left to k_post (they need wet samples of earlier calls)
     int wet_head, wet_from;  // blocks of the batch < wet_head or >= wet_from also go to the wet ring
+    const double* wring;     // != null (k_os_out, predelay a multiple of 256, pm = 1): the window sums of the batch's blocks, indexed like cring (k_out_windows)
 };
 
 // Q1/Q2 window sums {D_L, D_R, Q_L, Q_R} of the wet frame u, which sounds at tau = u + predelay (the arithmetic of k_post):
@@ -925,6 +926,18 @@ __device__ __forceinline__ void out_window(const OutArgs& A, const int64_t u, do
         win[2] -= b[2];
         win[3] -= b[3];
     }
+}
+
+// The window sums of the batch's blocks [0, T), once per block: wring[t] = out_window of block t's first frame.  With a predelay
+// and an n_ref that are multiples of 256 all frames of a block share thi and tlo, so a reader takes these four doubles
+// instead of two dependent ring entries per lane.  grid = ceil(T / 256), block = 256; ring index masked.
+__global__ __launch_bounds__(256) void k_out_windows(OutArgs A, int T, double* __restrict__ wring) {
+    const int t = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (t >= T) return;
+    double win[4];
+    out_window(A, (A.tabs0 + t) * MC_B, win);
+    double* o = wring + (size_t)((A.tabs0 + t) & (A.rc - 1)) * 4;
+    o[0] = win[0], o[1] = win[1], o[2] = win[2], o[3] = win[3];
 }
 
 __device__ __forceinline__ void out_frame(const bool odd, const float wl, const float wr, const float x1, const float x2,

@@ -202,6 +202,7 @@ struct mc_engine {
     float4 *d_fdl = nullptr, *d_slotgain = nullptr, *d_Y = nullptr, *d_part = nullptr, *d_sums = nullptr;
     float *d_seg = nullptr, *d_wet = nullptr;
     double* d_cring = nullptr;
+    double* d_wring = nullptr;  // [rc][4] window sums per block of an overlap-save batch (k_out_windows), indexed like d_cring
     double* d_ctot = nullptr;   // [ceil(Tmax/256)][4] chunk totals of the Q1/Q2 prefix sums
     // predelay epochs: what blocks played under earlier predelays still owe, by absolute output sample
     float *d_res_mac = nullptr, *d_res_fix = nullptr;  // [2][rr] each
@@ -1539,19 +1540,39 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
     // hipStreamWaitEvent on such a handle faults in this runtime)
     const hipStream_t main = e->stream;
     const hipStream_t side = reinterpret_cast<uintptr_t>(main) > 2 ? e->os_stream : main;
-    if (side != main) {  // the side stream starts where the engine's stream stands
+    // A whole batch of two segments or more outside the Q8 regime: the side stream starts behind the column pass, runs the prefix
+    // chain the output pass waits for and only then the state later calls read, beside the row pass (which leaves half a CU's
+    // wave slots free; the column pass fills them all).  The Q8 regime and block slices produce what the prefix chain or the
+    // output pass reads with k_fwd, so there the side stream starts with the call - and so it does for a single segment, whose
+    // row and output passes together (about 40 us) are shorter than the side stream's kernels in a row (about 70).
+    const bool after = side != main && !slice && q8_shift < 0 && nseg >= 2;
+    if (side != main && !after) {  // the side stream starts where the engine's stream stands
         HIP_TRY(hipEventRecord(e->os_ev[0], main));
         HIP_TRY(hipStreamWaitEvent(side, e->os_ev[0], 0));
     }
     const int hist_from = (int)std::max<int64_t>(0, (int64_t)T - (int64_t)((e->cfg.n_ref + MC_MAX_PREDELAY) / MC_B + 4));
     DropAhead da;
     std::memset(&da, 0, sizeof(da));
+    // the batch's tail: what any later window, Q8 pass or re-render of a predelay epoch can reach
+    const int from = std::max(0, T - std::max(round_up(e->Pcap, 16) + 64, (int)((e->cfg.n_ref + MC_MAX_PREDELAY) / MC_B) + 8)) & ~(FWD_TILE - 1);
+    auto state_tail = [&]() {  // delay line, slot gains and histories of the tail, no cut terms
+        hipLaunchKernelGGL(k_fwd<false>, dim3((T - from + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, side, d_in1, d_in2, 1, (int64_t)T * MC_B, T,
+                           e->d_fdl, e->ring, slot0, d_ptab, 0, (float4*)nullptr, e->d_slotgain, e->d_tw, e->d_fdl16, e->d_xhist, e->xr, e->d_gring,
+                           e->rc, (int64_t)e->t_front, 0, 0, from, hist_from, from, da, 0);
+    };
+    auto last_segment = [&]() {  // the last block's segment from the delay line
+        MacOut mo;
+        const uint64_t b = e->t_front + (uint64_t)T - 1;
+        e->stream = side;  // (the MAC and inverse-transform launchers use the engine's stream)
+        const int rc_m = launch_mac_batch(e, st.act, st.nact, false, 1, (int)(b & (uint64_t)(e->ring - 1)), &mo);
+        if (!rc_m) launch_inv(e, mo, b, side);
+        e->stream = main;
+        return rc_m;
+    };
     if (!slice) {
         // state for later calls: delay line, slot gains, input / gain histories of the last blocks (what any later window,
         // Q8 pass or re-render of a predelay epoch can reach), and the last block's segment as the partitioned passes leave it
         // (its partition sums from the delay line, one inverse transform: its second half opens the next call)
-        const int reach = std::max(round_up(e->Pcap, 16) + 64, (int)((e->cfg.n_ref + MC_MAX_PREDELAY) / MC_B) + 8);
-        const int from = std::max(0, T - reach) & ~(FWD_TILE - 1);
         if (q8_shift >= 0) {
             // Q8 regime at the shipped shape: the forward transforms of ALL blocks sum the cut terms of output block t + shift while
             // X_t is in registers (k_fwd<true>, DropAhead) - delay-line slots still only for the tail; the first `shift` output
@@ -1565,17 +1586,12 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
                                (int64_t)st.ctx.predelay, (int64_t)e->cfg.n_ref, e->pm, (int64_t)e->epoch_b0);
             (q8_shift < T ? e->n_drop_ahead : e->n_drop_fft)++;
             stored.drop_done = true;
-        } else
-            hipLaunchKernelGGL(k_fwd<false>, dim3((T - from + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, side, d_in1, d_in2, 1, (int64_t)T * MC_B, T,
-                               e->d_fdl, e->ring, slot0, d_ptab, 0, (float4*)nullptr, e->d_slotgain, e->d_tw, e->d_fdl16, e->d_xhist, e->xr, e->d_gring,
-                               e->rc, (int64_t)e->t_front, 0, 0, from, hist_from, from, da, 0);
-        MacOut mo;
-        const uint64_t b = e->t_front + (uint64_t)T - 1;
-        e->stream = side;  // (the MAC and inverse-transform launchers use the engine's stream)
-        rc = launch_mac_batch(e, st.act, st.nact, false, 1, (int)(b & (uint64_t)(e->ring - 1)), &mo);
-        if (!rc) launch_inv(e, mo, b, side);
-        e->stream = main;
-        if (rc) return rc;
+        } else if (!after)
+            state_tail();
+        if (!after) {
+            rc = last_segment();
+            if (rc) return rc;
+        }
     } else if (stored.need_b0 < T) {
         // block-sliced: the tail of the batch that the next call's windows reach back to (delay line, histories, block sums), as k_fwd leaves it
         const int from = stored.need_b0 & ~(FWD_TILE - 1);
@@ -1623,11 +1639,16 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
     G.base = (int64_t)w0 * MC_B;
     G.wet_end = (int64_t)(w0 + wn) * MC_B;
     G.seg0 = 0;
+    if (e->ktiming && e->kev_n == kEvPool) {
+        rc = drain_kernel_events(e);
+        if (rc) return rc;
+    }
     hipLaunchKernelGGL(k_os_cols, dim3(nseg * OS_TPS), dim3(OS_THREADS), 0, main, d_in1, d_in2, (const float*)e->d_xhist, e->xr, G, e->d_os_T,
                        e->cfg.compat ? e->d_os_part : (float4*)nullptr, e->d_tw);
-    if (side != main) {
-        HIP_TRY(hipEventRecord(e->os_ev[1], main));
-        HIP_TRY(hipStreamWaitEvent(side, e->os_ev[1], 0));
+    if (side != main) {  // (with kernel timing the row pass's opening event serves: one marker fewer on the engine's stream)
+        const hipEvent_t cols_done = after && e->ktiming ? e->kev[e->kev_n][0] : e->os_ev[1];
+        HIP_TRY(hipEventRecord(cols_done, main));
+        HIP_TRY(hipStreamWaitEvent(side, cols_done, 0));
     }
     {  // Q1/Q2 prefix sums of the batch from the column pass's partial sums, ahead of the output pass
         CorrArgs ca;
@@ -1652,14 +1673,21 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
         hipLaunchKernelGGL(k_corr_terms, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, side, ca);
         if (ca.nchunks > 1) hipLaunchKernelGGL(k_corr_fix, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, side, ca);
     }
+    if (after && e->cfg.compat && e->pm == 1 && !((st.ctx.predelay | e->cfg.n_ref) & (MC_B - 1))) {
+        // all frames of a block share their window: its sums once per block instead of per lane of the output pass
+        hipLaunchKernelGGL(k_out_windows, dim3((T + 255) / 256), dim3(256), 0, side, oa, T, e->d_wring);
+        oa.wring = e->d_wring;
+    }
     if (side != main) HIP_TRY(hipEventRecord(e->os_ev[2], side));
-    if (e->ktiming && e->kev_n == kEvPool) {
-        rc = drain_kernel_events(e);
+    if (after) {  // behind the prefix chain, beside the row pass: what later calls read (k_fwd writes the input history the column pass has read)
+        state_tail();
+        rc = last_segment();
         if (rc) return rc;
+        HIP_TRY(hipEventRecord(e->os_ev[0], side));
     }
     if (e->ktiming) {
         e->kev_blocks[e->kev_n] = (uint32_t)wn;
-        HIP_TRY(hipEventRecord(e->kev[e->kev_n][0], main));
+        if (!after) HIP_TRY(hipEventRecord(e->kev[e->kev_n][0], main));
     }
     hipLaunchKernelGGL(k_os_rows, dim3(nseg * OS_ITEMS), dim3(G2B_THREADS), 0, main, e->d_os_T, (const float4*)e->d_os_SP, (const float4*)e->d_os_SP0, nseg);
     if (e->ktiming) {
@@ -1669,8 +1697,9 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
         e->ks.partitions = (uint32_t)ovl_blocks;
         e->ks.fast_levels = 253u;
     }
-    if (side != main) HIP_TRY(hipStreamWaitEvent(main, e->os_ev[2], 0));  // (everything the side stream did: the output pass needs the prefix ring, later calls the rest)
+    if (side != main) HIP_TRY(hipStreamWaitEvent(main, e->os_ev[2], 0));  // (the prefix ring and the window sums; where the side stream started with the call, everything it did: the cut terms, and what later calls need)
     hipLaunchKernelGGL(k_os_out, dim3(nseg * OS_TPS), dim3(OS_THREADS), 0, main, (const float4*)e->d_os_T, G, e->d_wet, e->wr, e->d_tw, oa);
+    if (after) HIP_TRY(hipStreamWaitEvent(main, e->os_ev[0], 0));  // (later calls need the rest of what the side stream did)
     HIP_TRY(hipGetLastError());
     stored.out_from = head;
     stored.corr_done = true;
@@ -3069,6 +3098,7 @@ int mc_create(const mc_config* cfg, mc_engine** out) {
     ENG_TRY(hipMalloc(&e->d_seg, sizeof(float) * (size_t)e->sr * 2 * FFT_N));
     ENG_TRY(hipMalloc(&e->d_wet, sizeof(float) * 2 * (size_t)e->wr));
     ENG_TRY(hipMalloc(&e->d_cring, sizeof(double) * 4 * (size_t)e->rc));
+    ENG_TRY(hipMalloc(&e->d_wring, sizeof(double) * 4 * (size_t)e->rc));
     ENG_TRY(hipMalloc(&e->d_ctot, sizeof(double) * 4 * (size_t)((e->Tmax + 255) / 256 + 1)));
     ENG_TRY(hipMalloc(&e->d_cflag, sizeof(unsigned) * (size_t)((e->Tmax + 255) / 256 + 2)));
     ENG_TRY(hipMemset(e->d_cflag, 0, sizeof(unsigned) * (size_t)((e->Tmax + 255) / 256 + 2)));
@@ -3199,6 +3229,7 @@ void mc_destroy(mc_engine* e) {
     (void)hipFree(e->d_seg);
     (void)hipFree(e->d_wet);
     (void)hipFree(e->d_cring);
+    (void)hipFree(e->d_wring);
     (void)hipFree(e->d_ctot);
     (void)hipFree(e->d_cflag);
     (void)hipFree(e->d_stamps);

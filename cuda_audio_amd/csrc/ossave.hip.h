@@ -337,7 +337,7 @@ __global__ __launch_bounds__(G2B_THREADS, 4) void k_os_rows(float4* __restrict__
 // ---------------------------------------------------------------------------
 // Output pass: inverse column transforms and k_inv_wet<true>'s output stage.  grid = segments x 512, block = 1024.
 // The lane that holds four consecutive wet frames {L = Re, R = Im} of the batch finishes them: Q1/Q2 window sums from the
-// prefix ring (out_window), clamp, dry mix (out_frame), stored at the predelay offset; the frames later calls can reach
+// prefix ring (out_window, or per block from oa.wring), clamp, dry mix (out_frame), stored at the predelay offset; the frames later calls can reach
 // (blocks < wet_head or >= wet_from) also go to the wet ring.  OutArgs as for k_inv_wet (lin unused: null; drop != null in the Q8 regime: the cut terms of the batch's output frames).
 // Bounds: wet frames i0 in [base + seg hop, min(base + (seg + 1) hop, wet_end)), wet_end <= n_in; output frames tested against [out_from, out_end) blocks;
 // ring indices masked.
@@ -396,7 +396,11 @@ __global__ __launch_bounds__(OS_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8
         double win[4];
         if (whole) {
             const float4 x1q = *reinterpret_cast<const float4*>(oa.in1 + o0), x2q = *reinterpret_cast<const float4*>(oa.in2 + o0);
-            out_window(oa, u0, win);
+            if (oa.wring) {  // the block's window sums, taken once (k_out_windows)
+                const double* w = oa.wring + (size_t)((u0 >> 8) & (oa.rc - 1)) * 4;
+                win[0] = w[0], win[1] = w[1], win[2] = w[2], win[3] = w[3];
+            } else
+                out_window(oa, u0, win);
             const BlockParams& bp = oa.ptab[(o0 >> 8) * oa.pstride];
             float4 d01 = make_float4(0.f, 0.f, 0.f, 0.f), d23 = d01;  // the Q8 cut terms of the four frames {L, R}, subtracted before the clamp (as k_inv_wet)
             if (oa.drop) {
