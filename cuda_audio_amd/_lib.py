@@ -20,6 +20,7 @@ SYMBOLS = [
     "mc_abi_version", "mc_last_error", "mc_default_config", "mc_default_params", "mc_create", "mc_destroy",
     "mc_reset", "mc_set_period", "mc_load_ir", "mc_load_ir_resampled", "mc_default_ir_shape", "mc_load_ir_shaped", "mc_ir_shape_info",
     "mc_default_ir_eq", "mc_load_ir_eq", "mc_ir_eq_response", "mc_default_ir_damp", "mc_load_ir_damped", "mc_ir_damp_info", "mc_ir_damp_response",
+    "mc_default_ir_synth", "mc_synth_ir", "mc_ir_synth_info",
     "mc_default_decay_query", "mc_ir_decay", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
@@ -125,6 +126,30 @@ class McIrDamp(C.Structure):
     ]
 
 
+MC_SYNTH_MAX_EARLY = 64
+
+
+class McIrSynth(C.Structure):
+    """mc_ir_synth: the IR mc_synth_ir generates on the device from a seed."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_early", C.c_uint32),
+        ("seed", C.c_uint64),
+        ("frames", C.c_uint64),
+        ("late_start", C.c_uint64),
+        ("t60", C.c_uint64),
+        ("build_up", C.c_uint32),
+        ("late_gain", C.c_float),
+        ("direct", C.c_float),
+        ("early_gain", C.c_float),
+        ("width", C.c_float),
+        ("rate", C.c_uint32),
+        ("early_first", C.c_uint64),
+        ("early_last", C.c_uint64),
+    ]
+
+
 MC_DECAY_MAX_BANDS = 10
 MC_DECAY_MAX_CURVE = 1024
 
@@ -207,6 +232,10 @@ def load():
     L.mc_load_ir_damped.argtypes = [vp, u64, fp, u64, u64, C.c_uint32, C.c_uint32, C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp)]
     L.mc_ir_damp_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_ir_damp_response.argtypes = [C.POINTER(McIrDamp), C.c_uint32, u64, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double)]
+    L.mc_default_ir_synth.argtypes = [C.POINTER(McIrSynth)]
+    L.mc_default_ir_synth.restype = None
+    L.mc_synth_ir.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp)]
+    L.mc_ir_synth_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_default_decay_query.argtypes = [C.POINTER(McDecayQuery)]
     L.mc_default_decay_query.restype = None
     L.mc_ir_decay.argtypes = [vp, u64, C.POINTER(McDecayQuery), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64)]

@@ -30,6 +30,7 @@
 #include "ireq.hip.h"
 #include "irdamp.hip.h"
 #include "irdecay.hip.h"
+#include "irsynth.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
 // mc_config or that the tests compare bit for bit:
@@ -102,6 +103,8 @@ struct IrEntry {
     double shape_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     bool damped = false;  // the last load was mc_load_ir_damped with damping on: damp_info is what mc_ir_damp_info reports
     double damp_info[4] = {0, 0, 0, 0};
+    bool synthesised = false;  // the last load was mc_synth_ir: synth_info is what mc_ir_synth_info reports
+    double synth_info[4] = {0, 0, 0, 0};
 };
 
 }  // namespace
@@ -3304,14 +3307,17 @@ int mc_set_period(mc_engine* e, uint32_t nframes) {
 
 namespace {
 // The shaped load's own stage (irshape.hip.h): all `conv` frames at the session's rate on the device, shaped into a new buffer
-// of *n <= cap taps that the caller owns.  Nothing of the engine's IRs is touched here.
+// of *n <= cap taps that the caller owns.  Nothing of the engine's IRs is touched here.  syn = the device-side source beside
+// the host pointer (irsynth.hip.h): the conv frames are generated in place of a copy or a conversion; null = lr
 int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, uint64_t cap, const uint32_t* rs, const mc_ir_shape& sh,
-                const IeqCascade* eq, const DampPlan* damp, float2** d_taps, uint64_t* n, double sums[4], double info[8]) {
+                const IeqCascade* eq, const DampPlan* damp, float2** d_taps, uint64_t* n, double sums[4], double info[8],
+                const SynPlan* syn = nullptr) {
     float2* d_x = nullptr;
     HIP_TRY(hipMalloc(&d_x, sizeof(float2) * conv));
     double unused[4];
-    hipError_t er = rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, d_x, conv, unused)
-                       : hipMemcpy(d_x, lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
+    hipError_t er = syn  ? syn_generate(e->stream, *syn, d_x)
+                    : rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, d_x, conv, unused)
+                         : hipMemcpy(d_x, lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
     if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, sh, d_taps, n, sums, info, eq, damp);
     (void)hipFree(d_x);
     if (er != hipSuccess) return fail(MC_ERR_HIP, "IR shaping failed: %s", hipGetErrorString(er));
@@ -3324,11 +3330,12 @@ int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, u
 // (resample.hip.h) before anything else sees them; null = the frames as given (the reference).  sh = a shape with something
 // on, applied on the device after the conversion (irshape.hip.h); null = none.  eq = the bands of mc_load_ir_eq that are on
 // (ireq.hip.h; with a shape, which may have everything off); null = none.  damp = the damping of mc_load_ir_damped (irdamp.hip.h;
-// with a shape and an eq, which may hold no band); null = none
+// with a shape and an eq, which may hold no band); null = none.  syn = the source of mc_synth_ir (irsynth.hip.h; with a shape,
+// which may have everything off, lr null, frames = its F and no rs): the frames are generated on the device; null = lr
 int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs, const mc_ir_shape* sh = nullptr,
-            const IeqCascade* eq = nullptr, const DampPlan* damp = nullptr) {
+            const IeqCascade* eq = nullptr, const DampPlan* damp = nullptr, const SynPlan* syn = nullptr) {
     // Convolution::prepare, conv.cu:207-253
-    if (!e || !lr) return fail(MC_ERR_ARG, "null argument");
+    if (!e || (!lr && !syn)) return fail(MC_ERR_ARG, "null argument");
     if (idx >= (uint64_t)kMaxIrs) return fail(MC_ERR_ARG, "IR index %llu >= %d", (unsigned long long)idx, kMaxIrs);
     if (nframes >= e->cfg.n_ref) return fail(MC_ERR_ARG, "nframes >= n_ref");
     if (frames == 0) return fail(MC_ERR_ARG, "empty IR");
@@ -3345,12 +3352,18 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
         const double inf[4] = {(double)damp->X, (double)std::min<uint64_t>(damp->origin, taps), (double)decays, 0.0};
         std::copy(inf, inf + 4, ir.damp_info);
     };
+    const auto note_synth = [&](IrEntry& ir) {  // what mc_ir_synth_info reports of this load
+        ir.synthesised = syn != nullptr;
+        if (!syn) return;
+        const double inf[4] = {(double)syn->F, (double)syn->n_early, (double)std::min<uint64_t>(syn->late_start, syn->F), 0.0};
+        std::copy(inf, inf + 4, ir.synth_info);
+    };
     if (sh) {  // (the stream must be idle and out of the JACK path before the shaping kernels go onto it)
         int rc = e->sf ? MC_OK : drain_post(e);
         if (!rc && !e->sf) rc = leave_jack_path(e);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(e->stream));
-        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, eq, damp, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo);
+        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, eq, damp, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo, syn);
         if (rc) return rc;
     }
     if (e->sf) {
@@ -3360,6 +3373,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
         e->irs[idx].shaped = sh != nullptr;
         if (sh) std::memcpy(e->irs[idx].shape_info, sinfo, sizeof(sinfo));
         note_damp(e->irs[idx], nshaped);
+        note_synth(e->irs[idx]);
         return MC_OK;
     }
     const uint64_t n = sh ? nshaped : std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
@@ -3442,6 +3456,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
     ir.shaped = sh != nullptr;
     if (sh) std::memcpy(ir.shape_info, sinfo, sizeof(sinfo));
     note_damp(ir, n);
+    note_synth(ir);
     if ((int)idx + 1 > e->nirs) e->nirs = (int)idx + 1;
     e->spec_valid = e->dspec.valid = false;
     e->uniform_valid[0] = e->uniform_valid[1] = false;
@@ -3550,6 +3565,46 @@ int mc_load_ir_damped(mc_engine* e, uint64_t idx, const float* lr, uint64_t fram
     const DampPlan pl = damp_plan(*damp, session_rate);
     const uint32_t rs[2] = {ir_rate, session_rate};
     return load_ir(e, idx, lr, frames, nframes, ir_rate != session_rate ? rs : nullptr, shape, &cs, &pl);
+}
+
+void mc_default_ir_synth(mc_ir_synth* s) {
+    if (!s) return;
+    std::memset(s, 0, sizeof(*s));
+    s->struct_size = (uint32_t)sizeof(*s);
+    s->late_gain = s->early_gain = s->width = 1.f;
+}
+
+int mc_synth_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_synth* synth, const mc_ir_shape* shape, const mc_ir_eq* eq,
+                const mc_ir_damp* damp) {
+    // the struct first, then damp, eq and shape as in mc_load_ir_damped, all before the engine and before any HIP call
+    if (const char* bad = syn_check(synth)) return fail(MC_ERR_ARG, "%s", bad);
+    const uint32_t rate = synth->rate;
+    const bool damping = damp && damp->n_xovers;
+    if (damping)
+        if (const char* bad = damp_check(damp, rate, rate)) return fail(MC_ERR_ARG, "%s", bad);
+    mc_ir_eq noeq;
+    mc_default_ir_eq(&noeq);
+    if (!eq) eq = &noeq;
+    int on = 0;
+    if (const char* bad = ieq_check(eq, rate, rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
+    mc_ir_shape off;
+    mc_default_ir_shape(&off);
+    if (!shape) shape = &off;
+    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    const SynPlan syn = syn_plan(*synth);
+    IeqCascade cs;
+    cs.bands = 0;
+    DampPlan pl{};
+    if (on || damping) cs = ieq_cascade(*eq, rate);
+    if (damping) pl = damp_plan(*damp, rate);
+    return load_ir(e, idx, nullptr, synth->frames, nframes, nullptr, shape, on || damping ? &cs : nullptr, damping ? &pl : nullptr, &syn);
+}
+
+int mc_ir_synth_info(const mc_engine* e, uint64_t idx, double out[4]) {
+    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
+    if (!e->irs[idx].synthesised) return fail(MC_ERR_STATE, "IR %llu was not synthesised", (unsigned long long)idx);
+    for (int i = 0; i < 4; i++) out[i] = e->irs[idx].synth_info[i];
+    return MC_OK;
 }
 
 int mc_ir_damp_info(const mc_engine* e, uint64_t idx, double out[4]) {

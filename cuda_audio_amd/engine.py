@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import MC_BLOCK, McCcValue, McConfig, McDecayQuery, McIrDamp, McIrEq, McIrShape, McKernelStats, check
+from ._lib import MC_BLOCK, McCcValue, McConfig, McDecayQuery, McIrDamp, McIrEq, McIrShape, McIrSynth, McKernelStats, check
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
 CONV_MAX_SPEED = 1024             # conv.h:22-24
@@ -159,6 +159,38 @@ class DecayQuery:
             d.q = float(self.q)
         d.onset_db, d.end = float(self.onset_db), int(self.end)
         return d
+
+
+@dataclasses.dataclass
+class IrSynth:
+    """The IR prepare_synth generates on the device (mc_ir_synth, include/mcconv.h): `frames` stereo frames at the session's
+    rate, a pure function of the seed and these numbers.  A late field of Gaussian noise from frame late_start on, of standard
+    deviation late_gain there and 60 dB down t60 frames later (0: no decay), its echo density building up over build_up
+    frames (0: dense at once); `direct` on frame 0; n_early reflections placed in [early_first, early_last], the first of
+    gain early_gain and the later ones falling as 1 / distance, panned within `width`, which also sets how far the channels of
+    the late field differ (0: equal, 1: independent).  rate: set by prepare_synth from the engine's sample_rate."""
+
+    frames: int = 48000
+    seed: int = 0
+    late_start: int = 0
+    t60: int = 0
+    build_up: int = 0
+    late_gain: float = 1.0
+    direct: float = 0.0
+    n_early: int = 0
+    early_first: int = 0
+    early_last: int = 0
+    early_gain: float = 1.0
+    width: float = 1.0
+    rate: int = 0
+
+    def to_c(self):
+        s = McIrSynth()
+        _lib.load().mc_default_ir_synth(C.byref(s))
+        s.frames, s.seed, s.late_start, s.t60, s.build_up = int(self.frames), int(self.seed), int(self.late_start), int(self.t60), int(self.build_up)
+        s.late_gain, s.direct, s.early_gain, s.width = float(self.late_gain), float(self.direct), float(self.early_gain), float(self.width)
+        s.n_early, s.early_first, s.early_last, s.rate = int(self.n_early), int(self.early_first), int(self.early_last), int(self.rate)
+        return s
 
 
 DECAY_SETS = ("L", "R", "LR")
@@ -320,6 +352,17 @@ class Convolution:
         else:
             check(self._L.mc_load_ir(self._h, idx, _fp(lr), lr.shape[0], nframes))
 
+    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None):
+        """Generate the IR `synth` (an IrSynth) describes on the device and store it at idx (mc_synth_ir): the frames take the
+        place of a WAV's at the session's rate, and shape, eq and damp apply to them as in prepare().  A synthesised IR counts
+        as shaped: ir_shape_info(idx)["frames"] is synth.frames.  The engine's sample_rate (which eq and damp need) is passed
+        unless synth.rate is set."""
+        s = synth.to_c()
+        if not s.rate:
+            s.rate = int(self.sample_rate or 0)
+        check(self._L.mc_synth_ir(self._h, idx, nframes, C.byref(s), C.byref(shape.to_c()) if shape is not None else None,
+                                  C.byref(eq.to_c()) if eq is not None else None, C.byref(damp.to_c()) if damp is not None else None))
+
     def onProcess(self, in1, in2):
         """One JACK period (conv.cu:287-466): returns (L, R) float32 arrays."""
         in1, in2 = _f32(in1), _f32(in2)
@@ -437,6 +480,13 @@ class Convolution:
         out = (C.c_double * 4)()
         check(self._L.mc_ir_damp_info(self._h, idx, out))
         return dict(xovers=int(out[0]), origin=int(out[1]), damped_bands=int(out[2]))
+
+    def ir_synth_info(self, idx):
+        """What prepare_synth generated for IR idx (mc_ir_synth_info): the frames, the reflections kept (those placed inside
+        them) and the first frame of the late field.  McError (MC_ERR_STATE) for an IR whose last load was not synthesised."""
+        out = (C.c_double * 4)()
+        check(self._L.mc_ir_synth_info(self._h, idx, out))
+        return dict(frames=int(out[0]), reflections=int(out[1]), late_start=int(out[2]))
 
     def ir_decay(self, idx, bands=(), q=None, onset_db=-20.0, end=0, curve_points=0, rate=None):
         """The decay of the stored taps of IR idx, measured on the device (mc_ir_decay; include/mcconv.h has the definition).

@@ -1,5 +1,6 @@
 #include "conv.h"
 
+#include <algorithm>
 #include <cassert>
 #include <cmath>
 #include <cstdio>
@@ -35,6 +36,10 @@ int mc_ir_damp_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 // (... and no decay measurement)
 void mc_default_decay_query(mc_decay_query*) __attribute__((weak));
 int mc_ir_decay(mc_engine*, uint64_t, const mc_decay_query*, double*, double*, uint64_t*) __attribute__((weak));
+// (... and no synthesis)
+void mc_default_ir_synth(mc_ir_synth*) __attribute__((weak));
+int mc_synth_ir(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*) __attribute__((weak));
+int mc_ir_synth_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 }
 
 namespace {
@@ -143,9 +148,14 @@ uint64_t Convolution::dampFrames(double seconds, double rate) {
     return f < 1.0 ? 1 : (uint64_t)f;
 }
 
-// irRate = sessionRate = 0: the frames are loaded at the rate they have (never with a band of eq on, never with damping)
+// irRate = sessionRate = 0: the frames are loaded at the rate they have (never with a band of eq on, never with damping).
+// synth: the engine generates the frames (lr null; sessionRate = synth->rate)
 void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
-                             const IrEq& eq, const IrDamp& damp) {
+                             const IrEq& eq, const IrDamp& damp, const mc_ir_synth* synth) {
+    if (synth && (!mc_synth_ir || !mc_default_ir_synth || !mc_ir_synth_info)) {
+        Log::error("conv", "the engine has no IR synthesis (mc_synth_ir)");
+        std::exit(2);
+    }
     if (!damp.off() && (!mc_load_ir_damped || !mc_default_ir_damp || !mc_ir_damp_info)) {
         Log::error("conv", "the engine has no IR damping (mc_load_ir_damped)");
         std::exit(2);
@@ -182,6 +192,17 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         for (size_t k = 0; k < damp.xovers.size(); k++) d.xover_hz[k] = damp.xovers[k];
         for (size_t j = 0; j < damp.decaySeconds.size(); j++) d.decay_t60[j] = dampFrames(damp.decaySeconds[j], (double)sessionRate);
         d.origin = damp.origin;
+    }
+    if (synth) {  // (what the engine refuses of a generated IR is the index line's fault: a message and exit 2, no abort)
+        if (mc_synth_ir(_engine, idx, nframes, synth, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d) != MC_OK) {
+            Log::error("conv", "IR %zu cannot be synthesised: %s", idx, mc_last_error());
+            std::exit(2);
+        }
+        double si[4];
+        check(mc_ir_synth_info(_engine, idx, si), "mc_ir_synth_info");
+        Log::info(name, "IR %zu synthesised: %llu frames, seed %llu, %d of %u reflections kept", idx, (unsigned long long)si[0],
+                  (unsigned long long)synth->seed, (int)si[1], synth->n_early);
+    } else if (!damp.off()) {
         check(mc_load_ir_damped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, &d), "mc_load_ir_damped");
     } else if (eq.off())
         check(mc_load_ir_shaped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s), "mc_load_ir_shaped");
@@ -312,7 +333,130 @@ void Convolution::aimRt60(const PendingIr& p) {
               places(measuredRt(*this, p.idx), 4).c_str());
 }
 
+mc_ir_synth Convolution::synthFrames(const IrSynth& y, double rate) {
+    const auto frames = [&](double seconds) { return (uint64_t)std::nearbyint(seconds * rate); };
+    mc_ir_synth s;
+    mc_default_ir_synth(&s);
+    s.frames = frames(y.lengthSeconds);
+    s.t60 = frames(y.t60Seconds);
+    s.seed = y.seed;
+    s.late_start = frames(y.startSeconds);
+    s.build_up = (uint32_t)std::min<uint64_t>(frames(y.buildUpSeconds), 0xffffffffull);
+    s.late_gain = y.late;
+    s.direct = y.direct;
+    s.n_early = y.early;
+    s.early_first = frames(y.earlyFirstSeconds);
+    s.early_last = frames(y.earlyLastSeconds);
+    s.early_gain = y.earlyGain;
+    s.width = y.width;
+    s.rate = (uint32_t)rate;
+    return s;
+}
+
+bool Convolution::parseSynth(const std::string& line, IrSynth& out, std::string& why) {
+    static const char* form = "synth:LENGTH_S:T60_S[:key=value,...] with keys seed, start, buildup, late, direct, early, efirst, elast, egain, width";
+    std::vector<std::string> parts;
+    for (size_t at = 0;;) {
+        const size_t colon = line.find(':', at);
+        parts.push_back(line.substr(at, colon == std::string::npos ? colon : colon - at));
+        if (colon == std::string::npos) break;
+        at = colon + 1;
+    }
+    if (parts.size() < 3 || parts.size() > 4 || parts[0] != "synth") {
+        why = std::string("a generated IR is ") + form;
+        return false;
+    }
+    // a finite number >= 0 that fills the whole text
+    const auto number = [](const std::string& text, double& v) {
+        char* end = nullptr;
+        v = std::strtod(text.c_str(), &end);
+        return !text.empty() && end == text.c_str() + text.size() && std::isfinite(v);
+    };
+    IrSynth y;
+    if (!number(parts[1], y.lengthSeconds) || !(y.lengthSeconds > 0.0)) {
+        why = "LENGTH_S '" + parts[1] + "' is not a length in seconds, > 0";
+        return false;
+    }
+    if (!number(parts[2], y.t60Seconds) || y.t60Seconds < 0.0) {
+        why = "T60_S '" + parts[2] + "' is not a decay time in seconds, >= 0 (0 = no decay)";
+        return false;
+    }
+    const std::string list = parts.size() == 4 ? parts[3] : "";
+    if (parts.size() == 4 && list.empty()) {
+        why = std::string("nothing after the last colon: ") + form;
+        return false;
+    }
+    for (size_t at = 0; at < list.size() || (at && at == list.size());) {
+        const size_t comma = std::min(list.find(',', at), list.size());
+        const std::string item = list.substr(at, comma - at);
+        const size_t eq = item.find('=');
+        const std::string key = item.substr(0, eq), text = eq == std::string::npos ? "" : item.substr(eq + 1);
+        double v = 0.0;
+        bool good = eq != std::string::npos;
+        if (!good) {
+            why = "'" + item + "' is not key=value";
+            return false;
+        }
+        if (key == "seed") {
+            char* end = nullptr;
+            y.seed = std::strtoull(text.c_str(), &end, 0);
+            good = !text.empty() && text[0] != '-' && end == text.c_str() + text.size();
+        } else if (key == "early") {
+            good = number(text, v) && v >= 0.0 && v <= (double)MC_SYNTH_MAX_EARLY && v == std::floor(v);
+            y.early = (uint32_t)v;
+        } else if (key == "late" || key == "direct" || key == "egain" || key == "width") {
+            good = number(text, v) && (key == "direct" || key == "egain" || v >= 0.0) && (key != "width" || v <= 1.0);
+            (key == "late" ? y.late : key == "direct" ? y.direct : key == "egain" ? y.earlyGain : y.width) = (float)v;
+        } else if (key == "start" || key == "buildup" || key == "efirst" || key == "elast") {
+            good = number(text, v) && v >= 0.0;
+            (key == "start" ? y.startSeconds : key == "buildup" ? y.buildUpSeconds : key == "efirst" ? y.earlyFirstSeconds : y.earlyLastSeconds) = v;
+        } else {
+            why = "unknown key '" + key + "': " + form;
+            return false;
+        }
+        if (!good) {
+            why = "'" + text + "' is no value for " + key;
+            return false;
+        }
+        at = comma + 1;
+        if (comma == list.size()) break;
+    }
+    if (y.early && y.earlyLastSeconds < y.earlyFirstSeconds) {
+        why = "elast is before efirst";
+        return false;
+    }
+    out = y;
+    return true;
+}
+
+void Convolution::prepareSynth(size_t idx, const IrSynth& synth, size_t nframes) {
+    if (_group) {
+        Log::error("conv", "IR synthesis is not available with several devices (mc_synth_ir is single-engine)");
+        std::exit(2);
+    }
+    _pendingIrs.push_back(PendingIr{idx, nframes, 0, {}, _irShape, _irEq, false, _irDamp, true, synth});  // (generated by onStart(), once the client's rate is known)
+    if (idx + 1 > _nirs) _nirs = idx + 1;
+}
+
+void Convolution::prepareSynth(size_t idx, const mc_ir_synth& synth, size_t nframes) {
+    if (_group) {
+        Log::error("conv", "IR synthesis is not available with several devices (mc_synth_ir is single-engine)");
+        std::exit(2);
+    }
+    loadShaped(idx, nullptr, synth.frames, nframes, synth.rate, synth.rate, _irShape, _irEq, _irDamp, &synth);
+    if (idx + 1 > _nirs) _nirs = idx + 1;
+}
+
 void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
+    if (p.generated) {
+        if (!mc_default_ir_synth) {
+            Log::error("conv", "the engine has no IR synthesis (mc_synth_ir)");
+            std::exit(2);
+        }
+        const mc_ir_synth s = synthFrames(p.synth, (double)samplerate);
+        loadShaped(p.idx, nullptr, s.frames, p.nframes, s.rate, s.rate, shape, p.eq, p.damp, &s);
+        return;
+    }
     const uint64_t frames = p.lr.size() / 2;
     const bool convert = p.match && p.rate && p.rate != samplerate;
     if (!p.eq.off() || !p.damp.off()) {  // (bands and crossovers are laid out at the client's rate; frames that are not converted count as being at it)
@@ -347,7 +491,7 @@ void Convolution::loadPendingIrs() {
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
     if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
-        _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp});
+        _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth()});
         if (idx + 1 > _nirs) _nirs = idx + 1;
         return;
     }

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/mcconv.h"
 #include "gpu.h"
 #include "jackclient.h"
 #include "midi.h"
@@ -27,7 +28,6 @@
 // CONV_GRIDSIZE / CONV_BLOCKSIZE (conv.h:14-20) configured the reference's
 // grid-stride launches; launch shapes are internal to the engine here.
 
-struct mc_engine;
 struct mc_group;
 
 class Convolution : public JackClient, public RawMidi::MessageHandler {
@@ -149,6 +149,28 @@ public:
     // curve does not reach -35 dB) is measured, and when the target is shorter it is loaded again with the decayT60 that
     // takes it there, added as a slope to the shape's own decayT60.  Loaded by onStart(), single device only, as above.
     void setIrRt60(double seconds);
+    // An IR the engine generates from a seed instead of decoding a WAV (mc_ir_synth of include/mcconv.h; no reference
+    // equivalent): times in seconds, turned into frames at the client's sample rate by rint, as setIrDamp's are, so prepareSynth()
+    // keeps the numbers and onStart() generates.  What is not given is mc_default_ir_synth's.  The shape, EQ, damping, decay report
+    // and rt60 aim that are set apply to it as to a WAV.  Two log lines per IR: frames, seed and reflections kept, then the
+    // shaped load's.  Single device only, as setIrShape.
+    struct IrSynth {
+        double lengthSeconds = 1.0, t60Seconds = 0.0;  // frames, t60
+        uint64_t seed = 0;
+        double startSeconds = 0.0, buildUpSeconds = 0.0;  // late_start, build_up
+        float late = 1.0f, direct = 0.0f;                 // late_gain, direct
+        uint32_t early = 0;                               // n_early
+        double earlyFirstSeconds = 0.0, earlyLastSeconds = 0.0;
+        float earlyGain = 1.0f, width = 1.0f;
+    };
+    void prepareSynth(size_t idx, const IrSynth& synth, size_t nframes = 1024);
+    // The same from a filled mc_ir_synth (frames at synth.rate; rate 0 only without EQ and damping), generated at once.
+    void prepareSynth(size_t idx, const mc_ir_synth& synth, size_t nframes = 1024);
+    // A line of an IR index that starts with "synth:" - synth:LENGTH_S:T60_S[:key=value,...], keys seed, start, buildup, late,
+    // direct, early, efirst, elast, egain, width - as an IrSynth.  False, with the reason in `why`, for a malformed line.
+    static bool parseSynth(const std::string& line, IrSynth& out, std::string& why);
+    // mc_ir_synth of an IrSynth at rate Hz
+    static mc_ir_synth synthFrames(const IrSynth& synth, double rate);
 
     void onMidiMessage(const RawMidi::Device* sender, const uint8_t* buffer, size_t len) override;
 
@@ -173,6 +195,8 @@ private:
         IrEq eq;
         bool match;             // setMatchIrRate was on
         IrDamp damp;
+        bool generated = false;  // prepareSynth: `synth` instead of lr
+        IrSynth synth;
     };
     std::vector<PendingIr> _pendingIrs;  // (rate matching) prepared, loaded by onStart()
     void loadPendingIrs();
@@ -186,7 +210,7 @@ private:
     IrEq _irEq;
     IrDamp _irDamp;
     void loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
-                    const IrEq& eq = IrEq(), const IrDamp& damp = IrDamp());
+                    const IrEq& eq = IrEq(), const IrDamp& damp = IrDamp(), const mc_ir_synth* synth = nullptr);
     void pushParams();
     void pullVsteps();
 };

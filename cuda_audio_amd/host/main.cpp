@@ -19,6 +19,9 @@
 // decay that takes it there, on top of --ir-decay, Convolution::setIrRt60; --ir-damp HZ[,HZ[,HZ]]:SEC[,SEC...]: every IR is damped on
 // load, 1 to 3 ascending crossover frequencies and one further decay time in seconds per band, low to high, 0 for none, turned into
 // frames at the client's sample rate, Convolution::setIrDamp; --ir-damp-origin TAP: the stored tap the damping's envelopes start at).
+// A line of an IR index that starts with "synth:" is an IR the engine generates instead of a WAV path,
+// synth:LENGTH_S:T60_S[:key=value,...] with keys seed, start, buildup, late, direct, early, efirst, elast, egain, width
+// (Convolution::parseSynth; times in seconds at the client's sample rate); the --ir-* options apply to it as to a WAV.
 #include <cassert>
 #include <cstdlib>
 #include <cstring>
@@ -198,6 +201,16 @@ int main(int argc, char** argv) {
             std::string path;
             for (size_t j = 0; std::getline(index, path); j++) {
                 if (path.empty()) continue;
+                if (!path.compare(0, 6, "synth:")) {  // a generated IR instead of a WAV path
+                    Convolution::IrSynth synth;
+                    std::string why;
+                    if (!Convolution::parseSynth(path, synth, why)) {
+                        std::cerr << "index line '" << path << "': " << why << std::endl;
+                        return 2;
+                    }
+                    c->prepareSynth(j, synth);
+                    continue;
+                }
                 WavFile w(path);
                 c->prepare(j, w);
             }

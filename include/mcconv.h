@@ -334,6 +334,63 @@ void mc_default_decay_query(mc_decay_query *q);
  * bit for bit what they would have been.  Two calls with the same query on the same IR return the same bits. */
 int mc_ir_decay(mc_engine *e, uint64_t idx, const mc_decay_query *q, double *rows, double *curve, uint64_t info[2]);
 
+/* Synthesis of an IR on the device from a seed: a room from a few numbers instead of a recorded WAV.  No reference equivalent;
+ * single-engine, as shaping is.  The F = frames stereo frames are generated at the session's rate into the buffer the shaped
+ * load's steps read and never exist on the host.  Frame m is a pure function of (seed, m, this struct): the same struct gives
+ * the same bits.
+ *
+ * Random words.  W(i, s) = Philox4x32-10 (multipliers 0xD2511F53, 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85; ten rounds)
+ *   of the counter {i, 0, s, 0} under the key {seed & 0xffffffff, seed >> 32}: four 32-bit words w0 .. w3.
+ *   u(w) = (w + 0.5) / 2^32 as double (exact, inside (0, 1)).
+ * Late field.  For m >= late_start, t = m - late_start, from W(m, 0):
+ *   gA = sqrt(-2 ln u(w0)) cos(2 pi u(w1)), gB = sqrt(-2 ln u(w2)) cos(2 pi u(w3)); rho = 1 - width (double from the float);
+ *   L = gA, R = rho gA + sqrt(1 - rho^2) gB: width 0 gives R == L bit for bit, width 1 independent channels;
+ *   envelope = late_gain * (t60 ? exp2(-(t 3 log2(10)) / t60) : 1), step 5's expression counted from late_start;
+ *   echo density, with build_up = B > 0: the frame is occupied iff t + 1 >= B, or w0' < 2^28, or
+ *   (uint64) w0' B^2 < ((uint64) (t + 1)^2) << 32, w0' = w0 of W(m, 1) - integer arithmetic only, so no rounding decides
+ *   which frames sound.  The probability is p = t + 1 >= B ? 1 : max(1 / 16, ((t + 1) / B)^2); an occupied frame is scaled by
+ *   1 / sqrt(p) (at most 4), an unoccupied one is exactly 0 in both channels: the expected energy follows the envelope whatever
+ *   the density.  The late value is (L, R) * envelope * that scale.
+ * Direct sound.  `direct` is added to both channels of frame 0.
+ * Early reflections.  For j = 0 .. n_early - 1, from W(j, 2), with span = early_last - early_first + 1:
+ *   pos = early_first + (((uint64) w0 span) >> 32) (integer arithmetic); g = early_gain (w1 & 1 ? -1 : 1) (early_first + 1) /
+ *   (pos + 1); pan = width (2 u(w2) - 1); gL = g (pan >= 0 ? 1 - pan : 1), gR = g (pan <= 0 ? 1 + pan : 1) (the pan law of
+ *   panDry / panWet).  Reflections with pos >= F are dropped; those that share a frame are added in ascending j.
+ * A frame is late + direct + reflections, added in that order in double and rounded to float once. */
+#define MC_SYNTH_MAX_EARLY 64
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_ir_synth) = 80 */
+    uint32_t n_early;       /* 0 .. MC_SYNTH_MAX_EARLY */
+    uint64_t seed;
+    uint64_t frames;        /* F, 1 .. 2^24, at the session's rate */
+    uint64_t late_start;    /* >= F: no late field */
+    uint64_t t60;           /* 0 = no decay; else 60 dB down at frame late_start + t60 */
+    uint32_t build_up;      /* 0 .. 65535; 0 = dense from late_start */
+    float late_gain;        /* finite, >= 0: standard deviation of the late field at late_start */
+    float direct, early_gain; /* finite */
+    float width;            /* [0, 1] */
+    uint32_t rate;          /* the session's rate, which mc_synth_ir's eq and damp need (the WAV loads take it as a parameter;
+                               here it stands where a reserved word would): 0 = none, fine with no EQ band on and no damping;
+                               else [8000, 384000] */
+    uint64_t early_first, early_last; /* first <= last < 2^24, looked at when n_early > 0 */
+} mc_ir_synth;
+/* frames 0 (the caller's to set), seed 0, no reflections (early_gain 1, early_first = early_last = 0), late_start 0, t60 0,
+ * build_up 0, late_gain 1, direct 0, width 1, rate 0 */
+void mc_default_ir_synth(mc_ir_synth *s);
+/* Generates the IR `synth` describes and stores it at idx as mc_load_ir_damped stores converted WAV frames: the generated
+ * frames take their place at step 1 of the order of operations above, and shape, eq and damp (each may be NULL: off) apply
+ * to them.  Checked in this order, all before the engine or the device is touched (MC_ERR_ARG, the message names the field,
+ * the engine stays as it was): synth, field by field in the struct's order; damp (when on), eq and shape as by
+ * mc_load_ir_damped with ir_rate = session_rate = synth->rate; then e, idx and nframes.  The frames always pass through the
+ * shaping stage (the identity with everything off), so a synthesised IR counts as shaped: mc_ir_shape_info reports it with
+ * out[0] = F; mc_ir_info, mc_ir_decay, fp16 storage and the single-transform form see the stored taps as after any shaped
+ * load.  Threading as mc_load_ir. */
+int mc_synth_ir(mc_engine *e, uint64_t idx, uint64_t nframes, const mc_ir_synth *synth, const mc_ir_shape *shape,
+                const mc_ir_eq *eq, const mc_ir_damp *damp);
+/* out = {frames generated (F), reflections kept (pos < F), first frame of the late field (min(late_start, F)), 0};
+ * MC_ERR_STATE unless the IR's last load was mc_synth_ir */
+int mc_ir_synth_info(const mc_engine *e, uint64_t idx, double out[4]);
+
 int mc_num_irs(const mc_engine *e);
 /* out[0..3] = sum h_L, sum h_R, sum h_L(-1)^m, sum h_R(-1)^m of the truncated IR; out[4] = taps, out[5] = partitions */
 int mc_ir_info(const mc_engine *e, uint64_t idx, double out[6]);
