@@ -21,6 +21,7 @@ SYMBOLS = [
     "mc_reset", "mc_set_period", "mc_load_ir", "mc_load_ir_resampled", "mc_default_ir_shape", "mc_load_ir_shaped", "mc_ir_shape_info",
     "mc_default_ir_eq", "mc_load_ir_eq", "mc_ir_eq_response", "mc_default_ir_damp", "mc_load_ir_damped", "mc_ir_damp_info", "mc_ir_damp_response",
     "mc_default_ir_synth", "mc_synth_ir", "mc_ir_synth_info",
+    "mc_default_sweep", "mc_sweep_generate", "mc_load_ir_sweep", "mc_ir_sweep_info",
     "mc_default_decay_query", "mc_ir_decay", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
@@ -150,6 +151,22 @@ class McIrSynth(C.Structure):
     ]
 
 
+class McSweep(C.Structure):
+    """mc_sweep: the exponential sine sweep whose recording mc_load_ir_sweep deconvolves."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("rate", C.c_uint32),
+        ("frames", C.c_uint64),
+        ("f1_hz", C.c_float),
+        ("f2_hz", C.c_float),
+        ("amplitude", C.c_float),
+        ("fade_in", C.c_uint32),
+        ("fade_out", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 MC_DECAY_MAX_BANDS = 10
 MC_DECAY_MAX_CURVE = 1024
 
@@ -236,6 +253,11 @@ def load():
     L.mc_default_ir_synth.restype = None
     L.mc_synth_ir.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp)]
     L.mc_ir_synth_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_default_sweep.argtypes = [C.POINTER(McSweep)]
+    L.mc_default_sweep.restype = None
+    L.mc_sweep_generate.argtypes = [C.POINTER(McSweep), fp, u64, u64]
+    L.mc_load_ir_sweep.argtypes = [vp, u64, fp, u64, u64, C.POINTER(McSweep), C.c_int64, u64, C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp)]
+    L.mc_ir_sweep_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_default_decay_query.argtypes = [C.POINTER(McDecayQuery)]
     L.mc_default_decay_query.restype = None
     L.mc_ir_decay.argtypes = [vp, u64, C.POINTER(McDecayQuery), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64)]

@@ -31,6 +31,7 @@
 #include "irdamp.hip.h"
 #include "irdecay.hip.h"
 #include "irsynth.hip.h"
+#include "irsweep.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
 // mc_config or that the tests compare bit for bit:
@@ -105,6 +106,8 @@ struct IrEntry {
     double damp_info[4] = {0, 0, 0, 0};
     bool synthesised = false;  // the last load was mc_synth_ir: synth_info is what mc_ir_synth_info reports
     double synth_info[4] = {0, 0, 0, 0};
+    bool swept = false;  // the last load was mc_load_ir_sweep: sweep_info is what mc_ir_sweep_info reports
+    double sweep_info[4] = {0, 0, 0, 0};
 };
 
 }  // namespace
@@ -3308,18 +3311,25 @@ int mc_set_period(mc_engine* e, uint32_t nframes) {
 namespace {
 // The shaped load's own stage (irshape.hip.h): all `conv` frames at the session's rate on the device, shaped into a new buffer
 // of *n <= cap taps that the caller owns.  Nothing of the engine's IRs is touched here.  syn = the device-side source beside
-// the host pointer (irsynth.hip.h): the conv frames are generated in place of a copy or a conversion; null = lr
+// the host pointer (irsynth.hip.h): the conv frames are generated in place of a copy or a conversion; null = lr.  swp = the
+// source of mc_load_ir_sweep (irsweep.hip.h): the conv frames are deconvolved from its recording, which is uploaded to a
+// temporary buffer freed after the stage, as the weight table is
 int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, uint64_t cap, const uint32_t* rs, const mc_ir_shape& sh,
                 const IeqCascade* eq, const DampPlan* damp, float2** d_taps, uint64_t* n, double sums[4], double info[8],
-                const SynPlan* syn = nullptr) {
-    float2* d_x = nullptr;
+                const SynPlan* syn = nullptr, const SweepSource* swp = nullptr) {
+    float2 *d_x = nullptr, *d_rec = nullptr;
+    double* d_u = nullptr;
     HIP_TRY(hipMalloc(&d_x, sizeof(float2) * conv));
     double unused[4];
-    hipError_t er = syn  ? syn_generate(e->stream, *syn, d_x)
+    hipError_t er = swp  ? swp_generate(e->stream, *swp, d_x, &d_rec, &d_u)
+                    : syn ? syn_generate(e->stream, *syn, d_x)
                     : rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, d_x, conv, unused)
                          : hipMemcpy(d_x, lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
     if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, sh, d_taps, n, sums, info, eq, damp);
+    if (swp && er != hipSuccess) (void)hipStreamSynchronize(e->stream);  // (the correlation may still be reading them)
     (void)hipFree(d_x);
+    (void)hipFree(d_rec);
+    (void)hipFree(d_u);
     if (er != hipSuccess) return fail(MC_ERR_HIP, "IR shaping failed: %s", hipGetErrorString(er));
     if (!*n) return fail(MC_ERR_ARG, "the shape leaves no frame of the IR (start %llu, %llu frames at the session's rate)",
                          (unsigned long long)sh.start, (unsigned long long)conv);
@@ -3331,11 +3341,14 @@ int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, u
 // on, applied on the device after the conversion (irshape.hip.h); null = none.  eq = the bands of mc_load_ir_eq that are on
 // (ireq.hip.h; with a shape, which may have everything off); null = none.  damp = the damping of mc_load_ir_damped (irdamp.hip.h;
 // with a shape and an eq, which may hold no band); null = none.  syn = the source of mc_synth_ir (irsynth.hip.h; with a shape,
-// which may have everything off, lr null, frames = its F and no rs): the frames are generated on the device; null = lr
+// which may have everything off, lr null, frames = its F and no rs): the frames are generated on the device; null = lr.
+// swp = the source of mc_load_ir_sweep (irsweep.hip.h; as syn, frames = its F): the frames are deconvolved on the device from
+// its recording
 int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs, const mc_ir_shape* sh = nullptr,
-            const IeqCascade* eq = nullptr, const DampPlan* damp = nullptr, const SynPlan* syn = nullptr) {
+            const IeqCascade* eq = nullptr, const DampPlan* damp = nullptr, const SynPlan* syn = nullptr,
+            const SweepSource* swp = nullptr) {
     // Convolution::prepare, conv.cu:207-253
-    if (!e || (!lr && !syn)) return fail(MC_ERR_ARG, "null argument");
+    if (!e || (!lr && !syn && !swp)) return fail(MC_ERR_ARG, "null argument");
     if (idx >= (uint64_t)kMaxIrs) return fail(MC_ERR_ARG, "IR index %llu >= %d", (unsigned long long)idx, kMaxIrs);
     if (nframes >= e->cfg.n_ref) return fail(MC_ERR_ARG, "nframes >= n_ref");
     if (frames == 0) return fail(MC_ERR_ARG, "empty IR");
@@ -3358,12 +3371,18 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
         const double inf[4] = {(double)syn->F, (double)syn->n_early, (double)std::min<uint64_t>(syn->late_start, syn->F), 0.0};
         std::copy(inf, inf + 4, ir.synth_info);
     };
+    const auto note_sweep = [&](IrEntry& ir) {  // what mc_ir_sweep_info reports of this load
+        ir.swept = swp != nullptr;
+        if (!swp) return;
+        const double inf[4] = {(double)swp->plan.N, (double)swp->M, (double)swp->F, (double)swp->offset};
+        std::copy(inf, inf + 4, ir.sweep_info);
+    };
     if (sh) {  // (the stream must be idle and out of the JACK path before the shaping kernels go onto it)
         int rc = e->sf ? MC_OK : drain_post(e);
         if (!rc && !e->sf) rc = leave_jack_path(e);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(e->stream));
-        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, eq, damp, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo, syn);
+        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, eq, damp, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo, syn, swp);
         if (rc) return rc;
     }
     if (e->sf) {
@@ -3374,6 +3393,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
         if (sh) std::memcpy(e->irs[idx].shape_info, sinfo, sizeof(sinfo));
         note_damp(e->irs[idx], nshaped);
         note_synth(e->irs[idx]);
+        note_sweep(e->irs[idx]);
         return MC_OK;
     }
     const uint64_t n = sh ? nshaped : std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
@@ -3457,6 +3477,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
     if (sh) std::memcpy(ir.shape_info, sinfo, sizeof(sinfo));
     note_damp(ir, n);
     note_synth(ir);
+    note_sweep(ir);
     if ((int)idx + 1 > e->nirs) e->nirs = (int)idx + 1;
     e->spec_valid = e->dspec.valid = false;
     e->uniform_valid[0] = e->uniform_valid[1] = false;
@@ -3604,6 +3625,62 @@ int mc_ir_synth_info(const mc_engine* e, uint64_t idx, double out[4]) {
     if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
     if (!e->irs[idx].synthesised) return fail(MC_ERR_STATE, "IR %llu was not synthesised", (unsigned long long)idx);
     for (int i = 0; i < 4; i++) out[i] = e->irs[idx].synth_info[i];
+    return MC_OK;
+}
+
+void mc_default_sweep(mc_sweep* sw) {
+    if (!sw) return;
+    std::memset(sw, 0, sizeof(*sw));
+    sw->struct_size = (uint32_t)sizeof(*sw);
+    sw->rate = 44100;
+    sw->f1_hz = 20.f;
+    sw->f2_hz = 20000.f;
+    sw->amplitude = 0.5f;
+}
+
+int mc_sweep_generate(const mc_sweep* sw, float* out, uint64_t first, uint64_t count) {
+    if (const char* bad = swp_check(sw)) return fail(MC_ERR_ARG, "%s", bad);
+    if (first > sw->frames || count > sw->frames - first)
+        return fail(MC_ERR_ARG, "first %llu + count %llu above frames %llu", (unsigned long long)first, (unsigned long long)count,
+                    (unsigned long long)sw->frames);
+    if (!out) return fail(MC_ERR_ARG, "null out");
+    const SweepPlan p = swp_plan(*sw);
+    for (uint64_t i = 0; i < count; i++) out[i] = (float)swp_s64(p, first + i);
+    return MC_OK;
+}
+
+int mc_load_ir_sweep(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
+                     uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp) {
+    // the sweep first, then the lengths, then damp, eq and shape as in mc_load_ir_damped, all before the engine and before any HIP call
+    if (const char* bad = swp_check(sweep)) return fail(MC_ERR_ARG, "%s", bad);
+    if (const char* bad = swp_check_load(sweep, frames, ir_frames, offset)) return fail(MC_ERR_ARG, "%s", bad);
+    const uint32_t rate = sweep->rate;
+    const bool damping = damp && damp->n_xovers;
+    if (damping)
+        if (const char* bad = damp_check(damp, rate, rate)) return fail(MC_ERR_ARG, "%s", bad);
+    mc_ir_eq noeq;
+    mc_default_ir_eq(&noeq);
+    if (!eq) eq = &noeq;
+    int on = 0;
+    if (const char* bad = ieq_check(eq, rate, rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
+    mc_ir_shape off;
+    mc_default_ir_shape(&off);
+    if (!shape) shape = &off;
+    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!lr) return fail(MC_ERR_ARG, "null lr");
+    const SweepSource src{swp_plan(*sweep), lr, frames, ir_frames, offset};
+    IeqCascade cs;
+    cs.bands = 0;
+    DampPlan pl{};
+    if (on || damping) cs = ieq_cascade(*eq, rate);
+    if (damping) pl = damp_plan(*damp, rate);
+    return load_ir(e, idx, nullptr, ir_frames, nframes, nullptr, shape, on || damping ? &cs : nullptr, damping ? &pl : nullptr, nullptr, &src);
+}
+
+int mc_ir_sweep_info(const mc_engine* e, uint64_t idx, double out[4]) {
+    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
+    if (!e->irs[idx].swept) return fail(MC_ERR_STATE, "IR %llu was not loaded from a sweep", (unsigned long long)idx);
+    for (int i = 0; i < 4; i++) out[i] = e->irs[idx].sweep_info[i];
     return MC_OK;
 }
 

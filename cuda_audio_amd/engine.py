@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import MC_BLOCK, McCcValue, McConfig, McDecayQuery, McIrDamp, McIrEq, McIrShape, McIrSynth, McKernelStats, check
+from ._lib import MC_BLOCK, McCcValue, McConfig, McDecayQuery, McIrDamp, McIrEq, McIrShape, McIrSynth, McKernelStats, McSweep, check
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
 CONV_MAX_SPEED = 1024             # conv.h:22-24
@@ -193,6 +193,42 @@ class IrSynth:
         return s
 
 
+@dataclasses.dataclass
+class Sweep:
+    """The exponential sine sweep whose recording prepare_sweep deconvolves (mc_sweep, include/mcconv.h): `frames` frames
+    from f1_hz at frame 0 to f2_hz at the last, of peak `amplitude` (0.5 is WavFile's full scale), faded in and out over
+    fade_in and fade_out frames.  rate 0: the engine's sample_rate in prepare_sweep, the library's default (44100) in
+    sweep_frames."""
+
+    frames: int = 0
+    f1_hz: float = 20.0
+    f2_hz: float = 20000.0
+    amplitude: float = 0.5
+    fade_in: int = 0
+    fade_out: int = 0
+    rate: int = 0
+
+    def to_c(self):
+        s = McSweep()
+        _lib.load().mc_default_sweep(C.byref(s))
+        s.frames, s.fade_in, s.fade_out = int(self.frames), int(self.fade_in), int(self.fade_out)
+        s.f1_hz, s.f2_hz, s.amplitude = float(self.f1_hz), float(self.f2_hz), float(self.amplitude)
+        if self.rate:
+            s.rate = int(self.rate)
+        return s
+
+
+def sweep_frames(sweep):
+    """The sweep as float32 mono frames (mc_sweep_generate): what to play through the room."""
+    s = sweep.to_c()
+    out = np.empty(max(int(s.frames), 0), np.float32)
+    check(_lib.load().mc_sweep_generate(C.byref(s), _fp(out), 0, int(s.frames)))
+    return out
+
+
+SWEEP_MAX_FRAMES = 1 << 24  # M, F and |offset| of mc_load_ir_sweep
+SWEEP_MAX_WORK = 1 << 40    # F * N
+
 DECAY_SETS = ("L", "R", "LR")
 DECAY_FIELDS = ("energy", "edt", "t20", "t30", "c50", "c80", "d50", "ts")
 
@@ -363,6 +399,25 @@ class Convolution:
         check(self._L.mc_synth_ir(self._h, idx, nframes, C.byref(s), C.byref(shape.to_c()) if shape is not None else None,
                                   C.byref(eq.to_c()) if eq is not None else None, C.byref(damp.to_c()) if damp is not None else None))
 
+    def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None):
+        """Deconvolve `recording` (float32 [frames, 2] or an object with such a `.buffer`: what was recorded while `sweep`, a
+        Sweep, played) into an IR on the device and store it at idx (mc_load_ir_sweep): the frames take the place of a WAV's at
+        the session's rate, and shape, eq and damp apply to them as in prepare().  IR frame m is the correlation at lag
+        m + offset: a recording with no latency has its direct sound at frame -offset, and a negative offset keeps the
+        pre-roll where the harmonic-distortion images land.  ir_frames defaults to max(1, M - N + 1 - offset), what the
+        recording holds past the sweep, clamped to the library's caps.  The engine's sample_rate is passed unless sweep.rate
+        is set (the library's default, 44100, when the engine has none either)."""
+        lr = _f32(getattr(recording, "buffer", recording)).reshape(-1, 2)
+        s = sweep.to_c()
+        if not sweep.rate and self.sample_rate:
+            s.rate = int(self.sample_rate)
+        if ir_frames is None:
+            ir_frames = max(1, lr.shape[0] - int(s.frames) + 1 - int(offset))
+            ir_frames = max(1, min(ir_frames, SWEEP_MAX_FRAMES, SWEEP_MAX_WORK // max(int(s.frames), 1)))
+        check(self._L.mc_load_ir_sweep(self._h, idx, _fp(lr), lr.shape[0], nframes, C.byref(s), int(offset), int(ir_frames),
+                                       C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
+                                       C.byref(damp.to_c()) if damp is not None else None))
+
     def onProcess(self, in1, in2):
         """One JACK period (conv.cu:287-466): returns (L, R) float32 arrays."""
         in1, in2 = _f32(in1), _f32(in2)
@@ -487,6 +542,13 @@ class Convolution:
         out = (C.c_double * 4)()
         check(self._L.mc_ir_synth_info(self._h, idx, out))
         return dict(frames=int(out[0]), reflections=int(out[1]), late_start=int(out[2]))
+
+    def ir_sweep_info(self, idx):
+        """What prepare_sweep deconvolved for IR idx (mc_ir_sweep_info): the sweep's frames N, the recording's M, the frames
+        generated F and the offset.  McError (MC_ERR_STATE) for an IR whose last load was not from a sweep."""
+        out = (C.c_double * 4)()
+        check(self._L.mc_ir_sweep_info(self._h, idx, out))
+        return dict(sweep_frames=int(out[0]), recording_frames=int(out[1]), frames=int(out[2]), offset=int(out[3]))
 
     def ir_decay(self, idx, bands=(), q=None, onset_db=-20.0, end=0, curve_points=0, rate=None):
         """The decay of the stored taps of IR idx, measured on the device (mc_ir_decay; include/mcconv.h has the definition).

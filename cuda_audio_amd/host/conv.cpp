@@ -40,6 +40,12 @@ int mc_ir_decay(mc_engine*, uint64_t, const mc_decay_query*, double*, double*, u
 void mc_default_ir_synth(mc_ir_synth*) __attribute__((weak));
 int mc_synth_ir(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*) __attribute__((weak));
 int mc_ir_synth_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+// (... and no sweep capture)
+void mc_default_sweep(mc_sweep*) __attribute__((weak));
+int mc_sweep_generate(const mc_sweep*, float*, uint64_t, uint64_t) __attribute__((weak));
+int mc_load_ir_sweep(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
+                     const mc_ir_damp*) __attribute__((weak));
+int mc_ir_sweep_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 }
 
 namespace {
@@ -149,9 +155,14 @@ uint64_t Convolution::dampFrames(double seconds, double rate) {
 }
 
 // irRate = sessionRate = 0: the frames are loaded at the rate they have (never with a band of eq on, never with damping).
-// synth: the engine generates the frames (lr null; sessionRate = synth->rate)
+// synth: the engine generates the frames (lr null; sessionRate = synth->rate).  sweep: lr is the recording of a sweep, `frames`
+// frames at sessionRate = sweep->sweep.rate, which the engine deconvolves
 void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
-                             const IrEq& eq, const IrDamp& damp, const mc_ir_synth* synth) {
+                             const IrEq& eq, const IrDamp& damp, const mc_ir_synth* synth, const SweepLoad* sweep) {
+    if (sweep && (!mc_load_ir_sweep || !mc_default_sweep || !mc_ir_sweep_info)) {
+        Log::error("conv", "the engine has no sweep capture (mc_load_ir_sweep)");
+        std::exit(2);
+    }
     if (synth && (!mc_synth_ir || !mc_default_ir_synth || !mc_ir_synth_info)) {
         Log::error("conv", "the engine has no IR synthesis (mc_synth_ir)");
         std::exit(2);
@@ -202,6 +213,16 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         check(mc_ir_synth_info(_engine, idx, si), "mc_ir_synth_info");
         Log::info(name, "IR %zu synthesised: %llu frames, seed %llu, %d of %u reflections kept", idx, (unsigned long long)si[0],
                   (unsigned long long)synth->seed, (int)si[1], synth->n_early);
+    } else if (sweep) {  // (as for a generated IR: what the engine refuses is the index line's fault)
+        if (mc_load_ir_sweep(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s, eq.off() ? nullptr : &q,
+                             damp.off() ? nullptr : &d) != MC_OK) {
+            Log::error("conv", "IR %zu cannot be captured: %s", idx, mc_last_error());
+            std::exit(2);
+        }
+        double wi[4];
+        check(mc_ir_sweep_info(_engine, idx, wi), "mc_ir_sweep_info");
+        Log::info(name, "IR %zu captured: sweep %llu frames, recording %llu frames, %llu frames at offset %lld", idx, (unsigned long long)wi[0],
+                  (unsigned long long)wi[1], (unsigned long long)wi[2], (long long)wi[3]);
     } else if (!damp.off()) {
         check(mc_load_ir_damped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, &d), "mc_load_ir_damped");
     } else if (eq.off())
@@ -434,7 +455,7 @@ void Convolution::prepareSynth(size_t idx, const IrSynth& synth, size_t nframes)
         Log::error("conv", "IR synthesis is not available with several devices (mc_synth_ir is single-engine)");
         std::exit(2);
     }
-    _pendingIrs.push_back(PendingIr{idx, nframes, 0, {}, _irShape, _irEq, false, _irDamp, true, synth});  // (generated by onStart(), once the client's rate is known)
+    _pendingIrs.push_back(PendingIr{idx, nframes, 0, {}, _irShape, _irEq, false, _irDamp, true, synth, false, IrSweep()});  // (generated by onStart(), once the client's rate is known)
     if (idx + 1 > _nirs) _nirs = idx + 1;
 }
 
@@ -447,7 +468,156 @@ void Convolution::prepareSynth(size_t idx, const mc_ir_synth& synth, size_t nfra
     if (idx + 1 > _nirs) _nirs = idx + 1;
 }
 
+mc_sweep Convolution::sweepFrames(const IrSweep& w, double rate) {
+    const auto frames = [&](double seconds) { return std::nearbyint(seconds * rate); };
+    mc_sweep s;
+    mc_default_sweep(&s);
+    s.rate = (uint32_t)rate;
+    s.frames = (uint64_t)frames(w.lengthSeconds);
+    s.f1_hz = w.f1;
+    s.f2_hz = w.f2;
+    s.amplitude = w.amp;
+    s.fade_in = (uint32_t)std::min(frames(w.fadeInSeconds), 4294967295.0);
+    s.fade_out = (uint32_t)std::min(frames(w.fadeOutSeconds), 4294967295.0);
+    return s;
+}
+
+bool Convolution::parseSweep(const std::string& line, IrSweep& out, std::string& why) {
+    static const char* form = "sweep:RECORDING.wav:LENGTH_S:F1:F2[:key=value,...] with keys amp, fadein, fadeout, offset, length";
+    std::vector<std::string> parts;
+    for (size_t at = 0;;) {
+        const size_t colon = line.find(':', at);
+        parts.push_back(line.substr(at, colon == std::string::npos ? colon : colon - at));
+        if (colon == std::string::npos) break;
+        at = colon + 1;
+    }
+    if (parts.size() < 5 || parts.size() > 6 || parts[0] != "sweep") {
+        why = std::string("a captured IR is ") + form;
+        return false;
+    }
+    // a finite number that fills the whole text
+    const auto number = [](const std::string& text, double& v) {
+        char* end = nullptr;
+        v = std::strtod(text.c_str(), &end);
+        return !text.empty() && end == text.c_str() + text.size() && std::isfinite(v);
+    };
+    IrSweep w;
+    w.recording = parts[1];
+    if (w.recording.empty()) {
+        why = std::string("no file name: ") + form;
+        return false;
+    }
+    double f1 = 0.0, f2 = 0.0;
+    if (!number(parts[2], w.lengthSeconds) || !(w.lengthSeconds > 0.0)) {
+        why = "LENGTH_S '" + parts[2] + "' is not a length in seconds, > 0";
+        return false;
+    }
+    if (!number(parts[3], f1) || !(f1 >= 1.0)) {
+        why = "F1 '" + parts[3] + "' is not a frequency in Hz, >= 1";
+        return false;
+    }
+    if (!number(parts[4], f2) || !(f2 > f1)) {
+        why = "F2 '" + parts[4] + "' is not a frequency in Hz above F1";
+        return false;
+    }
+    w.f1 = (float)f1;
+    w.f2 = (float)f2;
+    const std::string list = parts.size() == 6 ? parts[5] : "";
+    if (parts.size() == 6 && list.empty()) {
+        why = std::string("nothing after the last colon: ") + form;
+        return false;
+    }
+    for (size_t at = 0; at < list.size() || (at && at == list.size());) {
+        const size_t comma = std::min(list.find(',', at), list.size());
+        const std::string item = list.substr(at, comma - at);
+        const size_t eq = item.find('=');
+        if (eq == std::string::npos) {
+            why = "'" + item + "' is not key=value";
+            return false;
+        }
+        const std::string key = item.substr(0, eq), text = item.substr(eq + 1);
+        double v = 0.0;
+        bool good = number(text, v);
+        if (key == "amp") {
+            good = good && v > 0.0;
+            w.amp = (float)v;
+        } else if (key == "fadein" || key == "fadeout" || key == "length") {
+            good = good && v >= 0.0;
+            (key == "fadein" ? w.fadeInSeconds : key == "fadeout" ? w.fadeOutSeconds : w.irLengthSeconds) = v;
+        } else if (key == "offset") {
+            w.offsetSeconds = v;
+        } else {
+            why = "unknown key '" + key + "': " + form;
+            return false;
+        }
+        if (!good) {
+            why = "'" + text + "' is no value for " + key;
+            return false;
+        }
+        at = comma + 1;
+        if (comma == list.size()) break;
+    }
+    if (w.fadeInSeconds + w.fadeOutSeconds > w.lengthSeconds) {
+        why = "fadein and fadeout are longer than the sweep";
+        return false;
+    }
+    out = w;
+    return true;
+}
+
+bool Convolution::writeSweep(const IrSweep& sweep, unsigned rate, std::string& why) {
+    if (!mc_sweep_generate || !mc_default_sweep) {
+        why = "the engine has no sweep (mc_sweep_generate)";
+        return false;
+    }
+    const mc_sweep s = sweepFrames(sweep, (double)rate);
+    std::vector<float> mono(s.frames <= (1ull << 22) ? s.frames : 0);
+    if (mc_sweep_generate(&s, mono.data(), 0, s.frames) != MC_OK) {
+        why = mc_last_error();
+        return false;
+    }
+    std::vector<float> lr(2 * mono.size());
+    for (size_t n = 0; n < mono.size(); n++) lr[2 * n] = lr[2 * n + 1] = mono[n];
+    if (!WavFile::write(sweep.recording, lr.data(), mono.size(), 24, rate)) {
+        why = "cannot write '" + sweep.recording + "'";
+        return false;
+    }
+    return true;
+}
+
+void Convolution::prepareSweep(size_t idx, const IrSweep& sweep, const WavFile& recording, size_t nframes) {
+    if (_group) {
+        Log::error("conv", "sweep capture is not available with several devices (mc_load_ir_sweep is single-engine)");
+        std::exit(2);
+    }
+    const float* lr = &recording.buffer[0].x;  // (deconvolved by onStart(), once the client's rate is known)
+    PendingIr p{idx, nframes, recording.sampleRate, std::vector<float>(lr, lr + 2 * recording.numFrames), _irShape, _irEq, false, _irDamp, false, IrSynth(), true, sweep};
+    _pendingIrs.push_back(std::move(p));
+    if (idx + 1 > _nirs) _nirs = idx + 1;
+}
+
 void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
+    if (p.swept) {
+        if (!mc_default_sweep) {
+            Log::error("conv", "the engine has no sweep capture (mc_load_ir_sweep)");
+            std::exit(2);
+        }
+        if (p.rate != samplerate) {
+            Log::error("conv", "IR %zu: the recording '%s' is at %u Hz, the client at %zu Hz (a recorded sweep is not converted)", p.idx,
+                       p.sweep.recording.c_str(), p.rate, (size_t)samplerate);
+            std::exit(2);
+        }
+        SweepLoad w;
+        w.sweep = sweepFrames(p.sweep, (double)samplerate);
+        w.offset = (int64_t)std::nearbyint(p.sweep.offsetSeconds * (double)samplerate);
+        const int64_t M = (int64_t)(p.lr.size() / 2), cap = 1ll << 24;
+        int64_t F = p.sweep.irLengthSeconds > 0.0 ? (int64_t)std::nearbyint(p.sweep.irLengthSeconds * (double)samplerate)
+                                                  : M - (int64_t)w.sweep.frames + 1 - w.offset;  // what the recording holds past the sweep
+        if (!(p.sweep.irLengthSeconds > 0.0)) F = std::min(F, std::min(cap, (int64_t)((1ull << 40) / std::max<uint64_t>(w.sweep.frames, 1))));
+        w.irFrames = (uint64_t)std::max<int64_t>(F, 1);
+        loadShaped(p.idx, p.lr.data(), (uint64_t)M, p.nframes, (unsigned)samplerate, (unsigned)samplerate, shape, p.eq, p.damp, nullptr, &w);
+        return;
+    }
     if (p.generated) {
         if (!mc_default_ir_synth) {
             Log::error("conv", "the engine has no IR synthesis (mc_synth_ir)");
@@ -491,7 +661,7 @@ void Convolution::loadPendingIrs() {
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
     if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
-        _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth()});
+        _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth(), false, IrSweep()});
         if (idx + 1 > _nirs) _nirs = idx + 1;
         return;
     }

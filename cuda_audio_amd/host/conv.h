@@ -172,6 +172,30 @@ public:
     // mc_ir_synth of an IrSynth at rate Hz
     static mc_ir_synth synthFrames(const IrSynth& synth, double rate);
 
+    // An IR the engine deconvolves from the recording of an exponential sine sweep played through a room (mc_sweep and
+    // mc_load_ir_sweep of include/mcconv.h; no reference equivalent): times in seconds, turned into frames at the client's
+    // sample rate by rint, so prepareSweep() keeps the numbers and the recording and onStart() deconvolves.  The recording
+    // must be at the client's rate (it is not converted).  irLengthSeconds 0: what the recording holds past the sweep.  The
+    // shape, EQ, damping, decay report and rt60 aim that are set apply to it as to a WAV.  Two log lines per IR: the sweep's,
+    // the recording's and the IR's frames and the offset, then the shaped load's.  Single device only, as setIrShape.
+    struct IrSweep {
+        std::string recording;  // path of the recording (index lines); file to write (--write-sweep)
+        double lengthSeconds = 1.0;
+        float f1 = 20.0f, f2 = 20000.0f, amp = 0.5f;
+        double fadeInSeconds = 0.0, fadeOutSeconds = 0.0;
+        double offsetSeconds = 0.0;    // may be negative: keeps pre-roll
+        double irLengthSeconds = 0.0;
+    };
+    void prepareSweep(size_t idx, const IrSweep& sweep, const WavFile& recording, size_t nframes = 1024);
+    // A line of an IR index that starts with "sweep:" - sweep:RECORDING.wav:LENGTH_S:F1:F2[:key=value,...], keys amp, fadein,
+    // fadeout, offset, length - as an IrSweep.  False, with the reason in `why`, for a malformed line.
+    static bool parseSweep(const std::string& line, IrSweep& out, std::string& why);
+    // mc_sweep of an IrSweep at rate Hz
+    static mc_sweep sweepFrames(const IrSweep& sweep, double rate);
+    // The sweep at rate Hz in both channels of a 24-bit WAV file at sweep.recording (mc_sweep_generate, WavFile::write).
+    // False, with the reason in `why`, when the engine has no sweep, refuses it, or the file cannot be written.
+    static bool writeSweep(const IrSweep& sweep, unsigned rate, std::string& why);
+
     void onMidiMessage(const RawMidi::Device* sender, const uint8_t* buffer, size_t len) override;
 
     // offline rendering through the same engine: nblocks * 256 frames per channel
@@ -197,6 +221,13 @@ private:
         IrDamp damp;
         bool generated = false;  // prepareSynth: `synth` instead of lr
         IrSynth synth;
+        bool swept = false;  // prepareSweep: lr is the recording of `sweep`
+        IrSweep sweep;
+    };
+    struct SweepLoad {  // the arguments of mc_load_ir_sweep beside the recording
+        mc_sweep sweep;
+        int64_t offset;
+        uint64_t irFrames;
     };
     std::vector<PendingIr> _pendingIrs;  // (rate matching) prepared, loaded by onStart()
     void loadPendingIrs();
@@ -210,7 +241,8 @@ private:
     IrEq _irEq;
     IrDamp _irDamp;
     void loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
-                    const IrEq& eq = IrEq(), const IrDamp& damp = IrDamp(), const mc_ir_synth* synth = nullptr);
+                    const IrEq& eq = IrEq(), const IrDamp& damp = IrDamp(), const mc_ir_synth* synth = nullptr,
+                    const SweepLoad* sweep = nullptr);
     void pushParams();
     void pullVsteps();
 };

@@ -22,6 +22,11 @@
 // A line of an IR index that starts with "synth:" is an IR the engine generates instead of a WAV path,
 // synth:LENGTH_S:T60_S[:key=value,...] with keys seed, start, buildup, late, direct, early, efirst, elast, egain, width
 // (Convolution::parseSynth; times in seconds at the client's sample rate); the --ir-* options apply to it as to a WAV.
+// A line that starts with "sweep:" is an IR the engine deconvolves from the recording of a sine sweep,
+// sweep:RECORDING.wav:LENGTH_S:F1:F2[:key=value,...] with keys amp, fadein, fadeout, offset, length (Convolution::parseSweep;
+// times in seconds, the recording at the client's sample rate); the --ir-* options apply to it as to a WAV.
+// --write-sweep FILE.wav:LENGTH_S:F1:F2[:key=value,...] writes that sweep (keys amp, fadein, fadeout) at --rate (44100 without)
+// to both channels of a 24-bit WAV file and exits: what to play through the room.
 #include <cassert>
 #include <cstdlib>
 #include <cstring>
@@ -48,6 +53,7 @@ int main(int argc, char** argv) {
     std::vector<float> irDecayBands;
     double irRt60 = 0.0;
     Convolution::IrDamp irDamp;
+    const char* writeSweep = nullptr;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--periods") && i + 1 < argc) periods = strtoull(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "--settings") && i + 1 < argc) settingsPath = argv[++i];
@@ -56,6 +62,7 @@ int main(int argc, char** argv) {
         else if (!strcmp(argv[i], "--spacing") && i + 1 < argc) spacing_us = atof(argv[++i]);
         else if (!strcmp(argv[i], "--period") && i + 1 < argc) period = (jack_nframes_t)atoi(argv[++i]);
         else if (!strcmp(argv[i], "--rate") && i + 1 < argc) rate = (jack_nframes_t)atoi(argv[++i]);
+        else if (!strcmp(argv[i], "--write-sweep") && i + 1 < argc) writeSweep = argv[++i];
         else if (!strcmp(argv[i], "--match-ir-rate")) matchIrRate = true;
         else if (!strcmp(argv[i], "--ir-start") && i + 1 < argc) irShape.start = strtoull(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "--ir-trim") && i + 1 < argc) {
@@ -148,6 +155,16 @@ int main(int argc, char** argv) {
             }
         }
     }
+    if (writeSweep) {  // (before any device is looked at: host arithmetic only)
+        Convolution::IrSweep sweep;
+        std::string why;
+        if (!Convolution::parseSweep(std::string("sweep:") + writeSweep, sweep, why) || !Convolution::writeSweep(sweep, rate ? rate : 44100, why)) {
+            std::cerr << "--write-sweep '" << writeSweep << "': " << why << std::endl;
+            return 2;
+        }
+        std::cout << "wrote " << sweep.recording << std::endl;
+        return 0;
+    }
     if (rate || period) fakejack_configure(rate ? rate : 44100, period ? period : 256);
     selectGpu();
 
@@ -209,6 +226,17 @@ int main(int argc, char** argv) {
                         return 2;
                     }
                     c->prepareSynth(j, synth);
+                    continue;
+                }
+                if (!path.compare(0, 6, "sweep:")) {  // an IR deconvolved from a recorded sweep
+                    Convolution::IrSweep sweep;
+                    std::string why;
+                    if (!Convolution::parseSweep(path, sweep, why)) {
+                        std::cerr << "index line '" << path << "': " << why << std::endl;
+                        return 2;
+                    }
+                    WavFile rec(sweep.recording);
+                    c->prepareSweep(j, sweep, rec);
                     continue;
                 }
                 WavFile w(path);

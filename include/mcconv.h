@@ -391,6 +391,56 @@ int mc_synth_ir(mc_engine *e, uint64_t idx, uint64_t nframes, const mc_ir_synth 
  * MC_ERR_STATE unless the IR's last load was mc_synth_ir */
 int mc_ir_synth_info(const mc_engine *e, uint64_t idx, double out[4]);
 
+/* Capture of an IR from a recorded exponential sine sweep (Farina's method): the sweep is played through a room, the
+ * recording is deconvolved on the device with the sweep's inverse filter, and the result takes the place of a WAV's frames.
+ * No reference equivalent; single-engine, as shaping is.
+ *
+ * The sweep.  N = frames; everything in double from the float fields:
+ *   Ls = (N - 1) / ln(f2 / f1), so the instantaneous frequency is f1 at frame 0 and f2 at frame N - 1;
+ *   phi(n) = (2 pi f1 Ls / rate) expm1(n / Ls);
+ *   w(n) = the product of the fade-in window (1 - cos(pi (n + 1) / (fade_in + 1))) / 2 for n < fade_in and step 6's fade-out
+ *   expression over the last fade_out frames: (1 + cos(pi (k + 1) / (fade_out + 1))) / 2, k = n - (N - fade_out);
+ *   s[n] = amplitude w(n) sin(phi(n)).
+ * The deconvolution weights.  u[j] = (4 f2 / (amplitude^2 Ls rate)) s64[j] exp(-(N - 1 - j) / Ls), s64 the unrounded sweep:
+ *   the time-reversed sweep under Farina's 6 dB/octave envelope, folded into a correlation.  The constant is the
+ *   stationary-phase value that makes |S U| = 1 inside the swept band (|S(f)|^2 ~ A^2 Ls / (4 f), f in cycles per sample), so
+ *   the recovered IR has the level of the room whatever the amplitude.
+ * The generated frames.  For c in {L, R} and m = 0 .. F - 1:
+ *   h_c[m] = sum over j = 0 .. N - 1, ascending, of u[j] (double) r_c[m + j + offset], r = 0 outside [0, M);
+ *   one double accumulator per output, updated by fma, rounded to float once.  The fixed order makes a frame a pure function
+ *   of the inputs: the same bits whatever the grid.  A sweep recorded with no latency puts its direct sound at frame -offset;
+ *   a negative offset keeps pre-roll, where the sweep's harmonic-distortion images land, for mc_ir_shape.start or the trim
+ *   to cut. */
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_sweep) = 40 */
+    uint32_t rate;          /* [8000, 384000]: the recording's rate and the session's, which eq and damp use */
+    uint64_t frames;        /* N, 2 .. 2^22 */
+    float f1_hz;            /* finite, >= 1 */
+    float f2_hz;            /* finite, f1_hz < f2_hz <= 0.5 * rate */
+    float amplitude;        /* finite, > 0 */
+    uint32_t fade_in;       /* frames */
+    uint32_t fade_out;      /* frames, fade_in + fade_out <= N */
+    uint32_t reserved;      /* must be 0 */
+} mc_sweep;
+/* rate 44100, frames 0 (the caller's to set), 20 Hz .. 20000 Hz, amplitude 0.5 (WavFile's full scale is +-0.5, quirk Q5),
+ * no fades */
+void mc_default_sweep(mc_sweep *sw);
+/* s[first .. first + count) rounded to float, mono.  Host arithmetic only: no engine and no HIP call.  MC_ERR_ARG for a bad
+ * field (the message names it), a null pointer or first + count > N. */
+int mc_sweep_generate(const mc_sweep *sw, float *out, uint64_t first, uint64_t count);
+/* Deconvolves the recording lr (M = frames interleaved L,R frames at sweep->rate, 1 .. 2^24) into F = ir_frames (1 .. 2^24)
+ * frames and stores them at idx as mc_load_ir_damped stores converted WAV frames: they take their place at step 1 of the
+ * order of operations above, and shape, eq and damp (each may be NULL: off) apply to them.  offset lies in [-2^24, 2^24];
+ * F * N <= 2^40, which bounds the one correlation launch.  Checked in this order, all before the engine or the device is
+ * touched (MC_ERR_ARG, the message names the field, the engine stays as it was): sweep, field by field in the struct's order;
+ * M, F, offset, F * N; damp (when on), eq and shape as by mc_load_ir_damped with ir_rate = session_rate = sweep->rate; then
+ * lr, e, idx and nframes.  The frames always pass through the shaping stage, so the IR counts as shaped: mc_ir_shape_info
+ * reports it with out[0] = F.  Threading as mc_load_ir. */
+int mc_load_ir_sweep(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, const mc_sweep *sweep,
+                     int64_t offset, uint64_t ir_frames, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp);
+/* out = {N, M, F, offset}; MC_ERR_STATE unless the IR's last load was mc_load_ir_sweep */
+int mc_ir_sweep_info(const mc_engine *e, uint64_t idx, double out[4]);
+
 int mc_num_irs(const mc_engine *e);
 /* out[0..3] = sum h_L, sum h_R, sum h_L(-1)^m, sum h_R(-1)^m of the truncated IR; out[4] = taps, out[5] = partitions */
 int mc_ir_info(const mc_engine *e, uint64_t idx, double out[6]);
