@@ -22,7 +22,8 @@ SYMBOLS = [
     "mc_default_ir_eq", "mc_load_ir_eq", "mc_ir_eq_response", "mc_default_ir_damp", "mc_load_ir_damped", "mc_ir_damp_info", "mc_ir_damp_response",
     "mc_default_ir_synth", "mc_synth_ir", "mc_ir_synth_info",
     "mc_default_sweep", "mc_sweep_generate", "mc_load_ir_sweep", "mc_ir_sweep_info",
-    "mc_default_decay_query", "mc_ir_decay", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
+    "mc_default_decay_query", "mc_ir_decay", "mc_default_floor_query", "mc_ir_floor", "mc_ir_tail_from_floor",
+    "mc_default_ir_tail", "mc_load_ir_tail", "mc_load_ir_sweep_tail", "mc_ir_tail_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
     "mc_enable_kernel_timing", "mc_get_kernel_stats", "mc_algorithmic_bytes_per_block", "mc_blocks_processed", "mc_preferred_batch",
@@ -186,6 +187,51 @@ class McDecayQuery(C.Structure):
     ]
 
 
+MC_FLOOR_MAX_XOVERS = 3
+
+
+class McFloorQuery(C.Structure):
+    """mc_floor_query: how mc_ir_floor searches a loaded IR for its noise floor."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("rate", C.c_uint32),
+        ("n_xovers", C.c_uint32),
+        ("window", C.c_uint32),
+        ("xover_hz", C.c_float * MC_FLOOR_MAX_XOVERS),
+        ("onset_db", C.c_float),
+        ("end", C.c_uint64),
+        ("tail_fraction", C.c_float),
+        ("margin_db", C.c_float),
+        ("span_db", C.c_float),
+        ("per_decade", C.c_uint32),
+        ("rounds", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
+MC_TAIL_OFF, MC_TAIL_CUT, MC_TAIL_EXTEND = 0, 1, 2
+MC_TAIL_LEFT_ALONE = (1 << 64) - 1  # a knee that leaves its band alone
+
+
+class McIrTail(C.Structure):
+    """mc_ir_tail: the tail step of mc_load_ir_tail and mc_load_ir_sweep_tail, a knee per frequency band."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("n_xovers", C.c_uint32),
+        ("xover_hz", C.c_float * 3),
+        ("fade", C.c_uint32),
+        ("width", C.c_float),
+        ("seed", C.c_uint64),
+        ("length", C.c_uint64),
+        ("knee", C.c_uint64 * 4),
+        ("t60", C.c_uint64 * 4),
+        ("level_db", (C.c_float * 2) * 4),
+    ]
+
+
 class McKernelStats(C.Structure):
     _fields_ = [
         ("launches", C.c_uint64),
@@ -261,6 +307,17 @@ def load():
     L.mc_default_decay_query.argtypes = [C.POINTER(McDecayQuery)]
     L.mc_default_decay_query.restype = None
     L.mc_ir_decay.argtypes = [vp, u64, C.POINTER(McDecayQuery), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64)]
+    L.mc_default_floor_query.argtypes = [C.POINTER(McFloorQuery)]
+    L.mc_default_floor_query.restype = None
+    L.mc_ir_floor.argtypes = [vp, u64, C.POINTER(McFloorQuery), C.POINTER(C.c_double), C.POINTER(u64)]
+    L.mc_ir_tail_from_floor.argtypes = [C.POINTER(McFloorQuery), C.POINTER(C.c_double), C.POINTER(u64), u64, C.POINTER(McIrTail)]
+    L.mc_default_ir_tail.argtypes = [C.POINTER(McIrTail)]
+    L.mc_default_ir_tail.restype = None
+    L.mc_load_ir_tail.argtypes = [vp, u64, fp, u64, u64, C.c_uint32, C.c_uint32, C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp),
+                                  C.POINTER(McIrTail)]
+    L.mc_load_ir_sweep_tail.argtypes = [vp, u64, fp, u64, u64, C.POINTER(McSweep), C.c_int64, u64, C.POINTER(McIrShape), C.POINTER(McIrEq),
+                                        C.POINTER(McIrDamp), C.POINTER(McIrTail)]
+    L.mc_ir_tail_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_num_irs.argtypes = [vp]
     L.mc_ir_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_set_params.argtypes = [vp, C.c_int, C.POINTER(McCcValue)]

@@ -32,6 +32,8 @@
 #include "irdecay.hip.h"
 #include "irsynth.hip.h"
 #include "irsweep.hip.h"
+#include "irfloor.hip.h"
+#include "irtail.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
 // mc_config or that the tests compare bit for bit:
@@ -108,6 +110,8 @@ struct IrEntry {
     double synth_info[4] = {0, 0, 0, 0};
     bool swept = false;  // the last load was mc_load_ir_sweep: sweep_info is what mc_ir_sweep_info reports
     double sweep_info[4] = {0, 0, 0, 0};
+    bool tailed = false;  // the last load had a tail step on (mc_load_ir_tail, mc_load_ir_sweep_tail): tail_info is what mc_ir_tail_info reports
+    double tail_info[4] = {0, 0, 0, 0};
 };
 
 }  // namespace
@@ -3309,14 +3313,21 @@ int mc_set_period(mc_engine* e, uint32_t nframes) {
 }  // extern "C"
 
 namespace {
+// the tail step of a load as load_ir and shape_stage take it: the plan over the frames at the session's rate, and the mode
+struct TailStep {
+    TailPlan plan;
+    bool extend;
+};
+
 // The shaped load's own stage (irshape.hip.h): all `conv` frames at the session's rate on the device, shaped into a new buffer
 // of *n <= cap taps that the caller owns.  Nothing of the engine's IRs is touched here.  syn = the device-side source beside
 // the host pointer (irsynth.hip.h): the conv frames are generated in place of a copy or a conversion; null = lr.  swp = the
 // source of mc_load_ir_sweep (irsweep.hip.h): the conv frames are deconvolved from its recording, which is uploaded to a
-// temporary buffer freed after the stage, as the weight table is
+// temporary buffer freed after the stage, as the weight table is.  tail = step 1a (irtail.hip.h; tail->F = conv): between the
+// source and the shaping the conv frames become tail->Fp frames in a buffer of their own
 int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, uint64_t cap, const uint32_t* rs, const mc_ir_shape& sh,
                 const IeqCascade* eq, const DampPlan* damp, float2** d_taps, uint64_t* n, double sums[4], double info[8],
-                const SynPlan* syn = nullptr, const SweepSource* swp = nullptr) {
+                const SynPlan* syn = nullptr, const SweepSource* swp = nullptr, const TailStep* tail = nullptr) {
     float2 *d_x = nullptr, *d_rec = nullptr;
     double* d_u = nullptr;
     HIP_TRY(hipMalloc(&d_x, sizeof(float2) * conv));
@@ -3325,6 +3336,19 @@ int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, u
                     : syn ? syn_generate(e->stream, *syn, d_x)
                     : rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, d_x, conv, unused)
                          : hipMemcpy(d_x, lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
+    if (er == hipSuccess && tail) {
+        float2* d_y = nullptr;
+        er = hipMalloc(&d_y, sizeof(float2) * tail->plan.Fp);
+        if (er == hipSuccess) er = tail_run(e->stream, d_x, d_y, tail->plan, tail->extend);  // (waits for the stream: d_x is free after it)
+        if (er == hipSuccess) {
+            (void)hipFree(d_x);
+            d_x = d_y;
+            conv = tail->plan.Fp;
+        } else {
+            (void)hipStreamSynchronize(e->stream);
+            (void)hipFree(d_y);
+        }
+    }
     if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, sh, d_taps, n, sums, info, eq, damp);
     if (swp && er != hipSuccess) (void)hipStreamSynchronize(e->stream);  // (the correlation may still be reading them)
     (void)hipFree(d_x);
@@ -3343,10 +3367,11 @@ int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, u
 // with a shape and an eq, which may hold no band); null = none.  syn = the source of mc_synth_ir (irsynth.hip.h; with a shape,
 // which may have everything off, lr null, frames = its F and no rs): the frames are generated on the device; null = lr.
 // swp = the source of mc_load_ir_sweep (irsweep.hip.h; as syn, frames = its F): the frames are deconvolved on the device from
-// its recording
+// its recording.  tail = the tail step of mc_load_ir_tail and mc_load_ir_sweep_tail (irtail.hip.h; with a shape, which may have
+// everything off): step 1a, between the source and the shaping; null = none
 int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs, const mc_ir_shape* sh = nullptr,
             const IeqCascade* eq = nullptr, const DampPlan* damp = nullptr, const SynPlan* syn = nullptr,
-            const SweepSource* swp = nullptr) {
+            const SweepSource* swp = nullptr, const TailStep* tail = nullptr) {
     // Convolution::prepare, conv.cu:207-253
     if (!e || (!lr && !syn && !swp)) return fail(MC_ERR_ARG, "null argument");
     if (idx >= (uint64_t)kMaxIrs) return fail(MC_ERR_ARG, "IR index %llu >= %d", (unsigned long long)idx, kMaxIrs);
@@ -3377,12 +3402,18 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
         const double inf[4] = {(double)swp->plan.N, (double)swp->M, (double)swp->F, (double)swp->offset};
         std::copy(inf, inf + 4, ir.sweep_info);
     };
+    const auto note_tail = [&](IrEntry& ir) {  // what mc_ir_tail_info reports of this load
+        ir.tailed = tail != nullptr;
+        if (!tail) return;
+        const double inf[4] = {(double)tail->plan.touched, (double)tail->plan.F, (double)tail->plan.Fp, (double)tail->plan.first};
+        std::copy(inf, inf + 4, ir.tail_info);
+    };
     if (sh) {  // (the stream must be idle and out of the JACK path before the shaping kernels go onto it)
         int rc = e->sf ? MC_OK : drain_post(e);
         if (!rc && !e->sf) rc = leave_jack_path(e);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(e->stream));
-        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, eq, damp, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo, syn, swp);
+        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, eq, damp, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo, syn, swp, tail);
         if (rc) return rc;
     }
     if (e->sf) {
@@ -3394,6 +3425,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
         note_damp(e->irs[idx], nshaped);
         note_synth(e->irs[idx]);
         note_sweep(e->irs[idx]);
+        note_tail(e->irs[idx]);
         return MC_OK;
     }
     const uint64_t n = sh ? nshaped : std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
@@ -3478,6 +3510,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
     note_damp(ir, n);
     note_synth(ir);
     note_sweep(ir);
+    note_tail(ir);
     if ((int)idx + 1 > e->nirs) e->nirs = (int)idx + 1;
     e->spec_valid = e->dspec.valid = false;
     e->uniform_valid[0] = e->uniform_valid[1] = false;
@@ -3730,6 +3763,133 @@ int mc_ir_decay(mc_engine* e, uint64_t idx, const mc_decay_query* q, double* row
     HIP_TRY(hipStreamSynchronize(e->stream));
     const hipError_t er = dec_measure(e->stream, e->irs[idx].d_h, e->irs[idx].taps, *q, rows, curve, info);
     if (er != hipSuccess) return fail(MC_ERR_HIP, "decay measurement failed: %s", hipGetErrorString(er));
+    return MC_OK;
+}
+
+void mc_default_floor_query(mc_floor_query* q) {
+    if (!q) return;
+    std::memset(q, 0, sizeof(*q));
+    q->struct_size = (uint32_t)sizeof(*q);
+    q->rate = 44100;
+    q->xover_hz[0] = 250.f, q->xover_hz[1] = 2000.f, q->xover_hz[2] = 8000.f;
+    q->onset_db = -20.f;
+    q->tail_fraction = 0.1f;
+    q->margin_db = 10.f;
+    q->span_db = 20.f;
+    q->per_decade = 5;
+    q->rounds = 5;
+}
+
+int mc_ir_floor(mc_engine* e, uint64_t idx, const mc_floor_query* q, double* rows, uint64_t info[2]) {
+    // the query, the pointers and the index are checked in this order before any HIP call
+    if (const char* bad = flr_check(q)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!e) return fail(MC_ERR_ARG, "null engine");
+    if (!rows) return fail(MC_ERR_ARG, "null rows");
+    if (!info) return fail(MC_ERR_ARG, "null info");
+    if (e->sf) return fail(MC_ERR_STATE, "the single-transform form keeps no taps");
+    if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h || !e->irs[idx].taps) return fail(MC_ERR_ARG, "IR not loaded");
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = drain_post(e);  // (as mc_ir_decay: the stream must be idle and out of the JACK path before the kernels go onto it)
+    if (!rc) rc = leave_jack_path(e);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const hipError_t er = flr_measure(e->stream, e->irs[idx].d_h, e->irs[idx].taps, *q, rows, info);
+    if (er != hipSuccess) return fail(MC_ERR_HIP, "floor measurement failed: %s", hipGetErrorString(er));
+    return MC_OK;
+}
+
+int mc_ir_tail_from_floor(const mc_floor_query* q, const double* rows, const uint64_t info[2], uint64_t first, mc_ir_tail* tail) {
+    if (const char* bad = flr_check(q)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!rows) return fail(MC_ERR_ARG, "null rows");
+    if (!info) return fail(MC_ERR_ARG, "null info");
+    if (!tail) return fail(MC_ERR_ARG, "null tail");
+    if (tail->struct_size != sizeof(mc_ir_tail)) return fail(MC_ERR_ARG, "mc_ir_tail struct_size mismatch");
+    flr_to_tail(*q, rows, info, first, tail);
+    return MC_OK;
+}
+
+void mc_default_ir_tail(mc_ir_tail* t) {
+    if (!t) return;
+    std::memset(t, 0, sizeof(*t));
+    t->struct_size = (uint32_t)sizeof(*t);
+    t->mode = MC_TAIL_OFF;
+    t->xover_hz[0] = 250.f, t->xover_hz[1] = 2000.f, t->xover_hz[2] = 8000.f;
+    t->width = 1.f;
+    for (int j = 0; j < 4; j++) t->knee[j] = ~0ull, t->t60[j] = 1;
+}
+
+int mc_load_ir_tail(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
+                    const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail) {
+    if (!tail || tail->mode == MC_TAIL_OFF) return mc_load_ir_damped(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp);
+    // the tail first, then the rates and F', then damp, eq and shape as in mc_load_ir_damped, all before the engine and before any HIP call
+    if (const char* bad = tail_check(tail, session_rate)) return fail(MC_ERR_ARG, "%s", bad);
+    for (int k = 0; k < 2; k++) {
+        const uint32_t r = k ? ir_rate : session_rate;
+        if (r < RS_MIN_RATE || r > RS_MAX_RATE)
+            return fail(MC_ERR_ARG, "%s %u outside [%u, %u] (the tail step needs the session's rate)", k ? "ir_rate" : "session_rate", r, RS_MIN_RATE, RS_MAX_RATE);
+    }
+    if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
+    const uint32_t rs[2] = {ir_rate, session_rate};
+    const uint64_t F = ir_rate != session_rate ? rs_out_frames(rs_geom(ir_rate, session_rate), frames) : frames;
+    if (const char* bad = tail_check_frames(tail, F)) return fail(MC_ERR_ARG, "%s", bad);
+    const bool damping = damp && damp->n_xovers;
+    if (damping)
+        if (const char* bad = damp_check(damp, ir_rate, session_rate)) return fail(MC_ERR_ARG, "%s", bad);
+    mc_ir_eq noeq;
+    mc_default_ir_eq(&noeq);
+    if (!eq) eq = &noeq;
+    int on = 0;
+    if (const char* bad = ieq_check(eq, ir_rate, session_rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
+    mc_ir_shape off;
+    mc_default_ir_shape(&off);
+    if (!shape) shape = &off;
+    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    IeqCascade cs;
+    cs.bands = 0;
+    DampPlan pl{};
+    if (on || damping) cs = ieq_cascade(*eq, session_rate);
+    if (damping) pl = damp_plan(*damp, session_rate);
+    const TailStep step{tail_plan(*tail, session_rate, F), tail->mode == MC_TAIL_EXTEND};
+    return load_ir(e, idx, lr, frames, nframes, ir_rate != session_rate ? rs : nullptr, shape, on || damping ? &cs : nullptr, damping ? &pl : nullptr,
+                   nullptr, nullptr, &step);
+}
+
+int mc_load_ir_sweep_tail(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
+                          uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail) {
+    if (!tail || tail->mode == MC_TAIL_OFF) return mc_load_ir_sweep(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp);
+    // the tail first, then everything mc_load_ir_sweep checks in its order, F' after F, all before the engine and before any HIP call
+    if (const char* bad = tail_check(tail, sweep ? sweep->rate : 0)) return fail(MC_ERR_ARG, "%s", bad);
+    if (const char* bad = swp_check(sweep)) return fail(MC_ERR_ARG, "%s", bad);
+    if (const char* bad = swp_check_load(sweep, frames, ir_frames, offset)) return fail(MC_ERR_ARG, "%s", bad);
+    if (const char* bad = tail_check_frames(tail, ir_frames)) return fail(MC_ERR_ARG, "%s", bad);
+    const uint32_t rate = sweep->rate;
+    const bool damping = damp && damp->n_xovers;
+    if (damping)
+        if (const char* bad = damp_check(damp, rate, rate)) return fail(MC_ERR_ARG, "%s", bad);
+    mc_ir_eq noeq;
+    mc_default_ir_eq(&noeq);
+    if (!eq) eq = &noeq;
+    int on = 0;
+    if (const char* bad = ieq_check(eq, rate, rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
+    mc_ir_shape off;
+    mc_default_ir_shape(&off);
+    if (!shape) shape = &off;
+    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!lr) return fail(MC_ERR_ARG, "null lr");
+    const SweepSource src{swp_plan(*sweep), lr, frames, ir_frames, offset};
+    IeqCascade cs;
+    cs.bands = 0;
+    DampPlan pl{};
+    if (on || damping) cs = ieq_cascade(*eq, rate);
+    if (damping) pl = damp_plan(*damp, rate);
+    const TailStep step{tail_plan(*tail, rate, ir_frames), tail->mode == MC_TAIL_EXTEND};
+    return load_ir(e, idx, nullptr, ir_frames, nframes, nullptr, shape, on || damping ? &cs : nullptr, damping ? &pl : nullptr, nullptr, &src, &step);
+}
+
+int mc_ir_tail_info(const mc_engine* e, uint64_t idx, double out[4]) {
+    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
+    if (!e->irs[idx].tailed) return fail(MC_ERR_STATE, "IR %llu was not loaded with a tail step", (unsigned long long)idx);
+    for (int i = 0; i < 4; i++) out[i] = e->irs[idx].tail_info[i];
     return MC_OK;
 }
 

@@ -16,7 +16,8 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import MC_BLOCK, McCcValue, McConfig, McDecayQuery, McIrDamp, McIrEq, McIrShape, McIrSynth, McKernelStats, McSweep, check
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McFloorQuery, McIrDamp, McIrEq, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+                   check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
 CONV_MAX_SPEED = 1024             # conv.h:22-24
@@ -162,6 +163,101 @@ class DecayQuery:
 
 
 @dataclasses.dataclass
+class FloorQuery:
+    """How ir_floor searches a loaded IR for its noise floor (mc_floor_query, include/mcconv.h has Lundeby's method as it is
+    implemented): the broadband rows and, with 1 to 3 crossover frequencies (Hz, ascending), one row group per band of
+    IrDamp's split; time zero and `end` as in DecayQuery; `window` the first averaging interval in taps (0: 30 ms);
+    tail_fraction the last share of the taps that always counts as noise; margin_db how far above the noise the decay is cut;
+    span_db the range above that which the late slope is fitted over; per_decade the intervals per 10 dB of decay; rounds the
+    iterations, which always all run."""
+
+    rate: int = 44100
+    xovers: tuple = ()
+    onset_db: float = -20.0
+    end: int = 0
+    window: int = 0
+    tail_fraction: float = 0.1
+    margin_db: float = 10.0
+    span_db: float = 20.0
+    per_decade: int = 5
+    rounds: int = 5
+
+    def to_c(self):
+        if len(self.xovers) > _lib.MC_FLOOR_MAX_XOVERS:
+            raise ValueError(f"{len(self.xovers)} crossovers; at most {_lib.MC_FLOOR_MAX_XOVERS}")
+        q = McFloorQuery()
+        _lib.load().mc_default_floor_query(C.byref(q))
+        q.rate, q.n_xovers, q.window, q.end = int(self.rate), len(self.xovers), int(self.window), int(self.end)
+        for k, hz in enumerate(self.xovers):
+            q.xover_hz[k] = float(hz)
+        q.onset_db, q.tail_fraction, q.margin_db, q.span_db = float(self.onset_db), float(self.tail_fraction), float(self.margin_db), float(self.span_db)
+        q.per_decade, q.rounds = int(self.per_decade), int(self.rounds)
+        return q
+
+
+@dataclasses.dataclass
+class IrTail:
+    """What prepare(tail=...) and prepare_sweep(tail=...) do to the tail of an IR before anything else sees it (mc_ir_tail,
+    include/mcconv.h): mode "cut" fades every band to nothing at its knee, "extend" cross-fades it there into decaying noise,
+    "off" does nothing.  0 to 3 crossover frequencies (Hz, ascending) make len(xovers) + 1 bands, low to high, each with a
+    `knee` (a frame at the session's rate; None leaves the band alone) and, to extend, a `t60` (frames in which the noise
+    falls 60 dB) and a `level_db` pair (10 log10 of the band's power per frame at the knee, left and right).  `fade` frames
+    of cross-fade end at the knee; `length` is the number of frames the step hands on (0: as many as came in); seed and width
+    are IrSynth's.  tail_from_floor fills the bands from ir_floor's result."""
+
+    mode: str = "extend"
+    xovers: tuple = ()
+    knee: tuple = (None,)
+    t60: tuple = (1,)
+    level_db: tuple = ((0.0, 0.0),)
+    fade: int = 0
+    length: int = 0
+    seed: int = 0
+    width: float = 1.0
+
+    MODES = {"off": _lib.MC_TAIL_OFF, "cut": _lib.MC_TAIL_CUT, "extend": _lib.MC_TAIL_EXTEND}
+
+    def to_c(self):
+        if self.mode not in self.MODES:
+            raise ValueError(f"mode must be one of {sorted(self.MODES)}, not {self.mode!r}")
+        if len(self.xovers) > _lib.MC_DAMP_MAX_XOVERS:
+            raise ValueError(f"{len(self.xovers)} crossovers; at most {_lib.MC_DAMP_MAX_XOVERS}")
+        bands = len(self.xovers) + 1
+        if len(self.knee) != bands:
+            raise ValueError(f"{len(self.xovers)} crossovers make {bands} bands, not {len(self.knee)} knees")
+        t = McIrTail()
+        _lib.load().mc_default_ir_tail(C.byref(t))
+        t.mode, t.n_xovers, t.fade, t.width, t.seed, t.length = self.MODES[self.mode], len(self.xovers), int(self.fade), float(self.width), int(self.seed), int(self.length)
+        for k, hz in enumerate(self.xovers):
+            t.xover_hz[k] = float(hz)
+        for j, k in enumerate(self.knee):
+            t.knee[j] = _lib.MC_TAIL_LEFT_ALONE if k is None else int(k)
+        for j, v in enumerate(self.t60[:bands]):
+            t.t60[j] = int(v)
+        for j, pair in enumerate(self.level_db[:bands]):
+            t.level_db[j][0], t.level_db[j][1] = float(pair[0]), float(pair[1])
+        return t
+
+
+def tail_from_floor(floor, first=0, mode="extend", fade=0, length=0, seed=0, width=1.0):
+    """The IrTail that repairs the tail `floor` (ir_floor's result) found: per band the knee, the decay and the two channels'
+    levels of the measured lines (mc_ir_tail_from_floor, host arithmetic only).  A band without a knee inside the analysed
+    taps is left alone.  `first` is ir_shape_info(idx)["first"] when the measured load trimmed the IR, else 0; mode, fade,
+    length, seed and width are passed on."""
+    q, groups = floor["query"].to_c(), floor["groups"]
+    rows = np.array([[[floor["rows"][(g, name)][f] for f in FLOOR_FIELDS] for name in DECAY_SETS] for g in range(groups)], np.float64)
+    info = (C.c_uint64 * 2)(int(floor["origin"]), int(floor["taps"]))
+    t = McIrTail()
+    _lib.load().mc_default_ir_tail(C.byref(t))
+    check(_lib.load().mc_ir_tail_from_floor(C.byref(q), rows.ctypes.data_as(C.POINTER(C.c_double)), info, int(first), C.byref(t)))
+    bands = t.n_xovers + 1
+    return IrTail(mode=mode, xovers=tuple(float(t.xover_hz[k]) for k in range(t.n_xovers)),
+                  knee=tuple(None if t.knee[j] == _lib.MC_TAIL_LEFT_ALONE else int(t.knee[j]) for j in range(bands)),
+                  t60=tuple(int(t.t60[j]) for j in range(bands)), level_db=tuple((float(t.level_db[j][0]), float(t.level_db[j][1])) for j in range(bands)),
+                  fade=fade, length=length, seed=seed, width=width)
+
+
+@dataclasses.dataclass
 class IrSynth:
     """The IR prepare_synth generates on the device (mc_ir_synth, include/mcconv.h): `frames` stereo frames at the session's
     rate, a pure function of the seed and these numbers.  A late field of Gaussian noise from frame late_start on, of standard
@@ -231,6 +327,7 @@ SWEEP_MAX_WORK = 1 << 40    # F * N
 
 DECAY_SETS = ("L", "R", "LR")
 DECAY_FIELDS = ("energy", "edt", "t20", "t30", "c50", "c80", "d50", "ts")
+FLOOR_FIELDS = ("energy", "noise", "knee", "t", "peak_to_noise_db", "interval", "last_change", "status")
 
 
 def decay_for_rt60(measured_s, target_s, rate):
@@ -354,7 +451,7 @@ class Convolution:
         check(self._L.mc_set_period(self._h, nframes))
 
     # -- reference surface ----------------------------------------------------
-    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None, damp=None):
+    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None, damp=None, tail=None):
         """Convolution::prepare (conv.cu:207-253).  `wav` is float32 [frames, 2]
         (what WavFile.buffer holds) or an object with a `.buffer` of that shape.
         ir_rate (Hz; default: `wav.sampleRate` when it has one): when both it and the engine's sample_rate are known and
@@ -364,10 +461,18 @@ class Convolution:
         eq (an IrEq): filter the shaped taps with its bands before the normalisation (mc_load_ir_eq); the engine needs a
         sample_rate, and ir_rate defaults to it.
         damp (an IrDamp): a further decay per frequency band, after the fade and before the EQ (mc_load_ir_damped); the rates
-        as for eq; ir_damp_info(idx) then tells what was done."""
+        as for eq; ir_damp_info(idx) then tells what was done.
+        tail (an IrTail whose mode is not "off"): cut or extend the tail of the frames band by band, after the conversion and
+        before everything else (mc_load_ir_tail); the rates as for eq; ir_tail_info(idx) then tells what was done."""
         lr = _f32(getattr(wav, "buffer", wav)).reshape(-1, 2)
         if ir_rate is None:
             ir_rate = getattr(wav, "sampleRate", None)
+        if tail is not None and tail.mode != "off":
+            session = int(self.sample_rate or 0)
+            check(self._L.mc_load_ir_tail(self._h, idx, _fp(lr), lr.shape[0], nframes, session if ir_rate is None else int(ir_rate), session,
+                                          C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
+                                          C.byref(damp.to_c()) if damp is not None else None, C.byref(tail.to_c())))
+            return
         if damp is not None and damp.xovers:
             session = int(self.sample_rate or 0)
             check(self._L.mc_load_ir_damped(self._h, idx, _fp(lr), lr.shape[0], nframes, session if ir_rate is None else int(ir_rate), session,
@@ -399,14 +504,15 @@ class Convolution:
         check(self._L.mc_synth_ir(self._h, idx, nframes, C.byref(s), C.byref(shape.to_c()) if shape is not None else None,
                                   C.byref(eq.to_c()) if eq is not None else None, C.byref(damp.to_c()) if damp is not None else None))
 
-    def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None):
+    def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None, tail=None):
         """Deconvolve `recording` (float32 [frames, 2] or an object with such a `.buffer`: what was recorded while `sweep`, a
         Sweep, played) into an IR on the device and store it at idx (mc_load_ir_sweep): the frames take the place of a WAV's at
         the session's rate, and shape, eq and damp apply to them as in prepare().  IR frame m is the correlation at lag
         m + offset: a recording with no latency has its direct sound at frame -offset, and a negative offset keeps the
         pre-roll where the harmonic-distortion images land.  ir_frames defaults to max(1, M - N + 1 - offset), what the
         recording holds past the sweep, clamped to the library's caps.  The engine's sample_rate is passed unless sweep.rate
-        is set (the library's default, 44100, when the engine has none either)."""
+        is set (the library's default, 44100, when the engine has none either).  tail (an IrTail whose mode is not "off"): the
+        tail step on the deconvolved frames (mc_load_ir_sweep_tail)."""
         lr = _f32(getattr(recording, "buffer", recording)).reshape(-1, 2)
         s = sweep.to_c()
         if not sweep.rate and self.sample_rate:
@@ -414,9 +520,13 @@ class Convolution:
         if ir_frames is None:
             ir_frames = max(1, lr.shape[0] - int(s.frames) + 1 - int(offset))
             ir_frames = max(1, min(ir_frames, SWEEP_MAX_FRAMES, SWEEP_MAX_WORK // max(int(s.frames), 1)))
-        check(self._L.mc_load_ir_sweep(self._h, idx, _fp(lr), lr.shape[0], nframes, C.byref(s), int(offset), int(ir_frames),
-                                       C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
-                                       C.byref(damp.to_c()) if damp is not None else None))
+        args = (self._h, idx, _fp(lr), lr.shape[0], nframes, C.byref(s), int(offset), int(ir_frames),
+                C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
+                C.byref(damp.to_c()) if damp is not None else None)
+        if tail is not None and tail.mode != "off":
+            check(self._L.mc_load_ir_sweep_tail(*args, C.byref(tail.to_c())))
+        else:
+            check(self._L.mc_load_ir_sweep(*args))
 
     def onProcess(self, in1, in2):
         """One JACK period (conv.cu:287-466): returns (L, R) float32 arrays."""
@@ -567,6 +677,34 @@ class Convolution:
         check(self._L.mc_ir_decay(self._h, idx, C.byref(d), rows.ctypes.data_as(dp), curve.ctypes.data_as(dp) if curve is not None else None, info))
         return dict(origin=int(info[0]), taps=int(info[1]), curve=curve,
                     rows={(b, name): dict(zip(DECAY_FIELDS, (float(v) for v in rows[b, s]))) for b in range(groups) for s, name in enumerate(DECAY_SETS)})
+
+    def ir_floor(self, idx, xovers=(), onset_db=-20.0, end=0, window=0, tail_fraction=0.1, margin_db=10.0, span_db=20.0, per_decade=5, rounds=5,
+                 rate=None):
+        """The noise floor of the stored taps of IR idx, searched for on the device (mc_ir_floor; include/mcconv.h has the
+        method).  rate defaults to the engine's sample_rate, then to 44100.  Returns {"origin", "taps", "groups", "query",
+        "rows"}: rows maps (group, "L" | "R" | "LR") - group 0 is broadband, with crossovers group j + 1 is band j of
+        IrDamp's split, low to high - to {energy, noise (power per tap), knee (tap, fractional), t (the late decay time,
+        seconds), peak_to_noise_db, interval (taps), last_change (taps), status}; status 1: too short or silent, 2: no decay
+        above the floor, 3: a silent tail, no floor (knee = taps); NaN where a row has a status.  A clean IR has a knee near
+        its end too: look at peak_to_noise_db before acting on one.  tail_from_floor turns the result into an IrTail."""
+        if rate is None:
+            rate = self.sample_rate or 44100
+        query = FloorQuery(rate=rate, xovers=tuple(xovers), onset_db=onset_db, end=end, window=window, tail_fraction=tail_fraction,
+                           margin_db=margin_db, span_db=span_db, per_decade=per_decade, rounds=rounds)
+        q = query.to_c()
+        groups = 1 + (q.n_xovers + 1 if q.n_xovers else 0)
+        rows = np.empty((groups, 3, 8), np.float64)
+        info = (C.c_uint64 * 2)()
+        check(self._L.mc_ir_floor(self._h, idx, C.byref(q), rows.ctypes.data_as(C.POINTER(C.c_double)), info))
+        return dict(origin=int(info[0]), taps=int(info[1]), groups=groups, query=query,
+                    rows={(g, name): dict(zip(FLOOR_FIELDS, (float(v) for v in rows[g, s]))) for g in range(groups) for s, name in enumerate(DECAY_SETS)})
+
+    def ir_tail_info(self, idx):
+        """What the tail step of IR idx's load did (mc_ir_tail_info): the bands it touched, the frames that came in, the frames
+        it handed on and the first frame it changed.  McError (MC_ERR_STATE) for an IR whose last load had no tail step."""
+        out = (C.c_double * 4)()
+        check(self._L.mc_ir_tail_info(self._h, idx, out))
+        return dict(bands=int(out[0]), frames=int(out[1]), length=int(out[2]), first=int(out[3]))
 
     def enable_kernel_timing(self, on=True):
         check(self._L.mc_enable_kernel_timing(self._h, 1 if on else 0))

@@ -46,6 +46,16 @@ int mc_sweep_generate(const mc_sweep*, float*, uint64_t, uint64_t) __attribute__
 int mc_load_ir_sweep(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
                      const mc_ir_damp*) __attribute__((weak));
 int mc_ir_sweep_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+// ... no floor measurement and no tail step
+void mc_default_floor_query(mc_floor_query*) __attribute__((weak));
+int mc_ir_floor(mc_engine*, uint64_t, const mc_floor_query*, double*, uint64_t*) __attribute__((weak));
+int mc_ir_tail_from_floor(const mc_floor_query*, const double*, const uint64_t*, uint64_t, mc_ir_tail*) __attribute__((weak));
+void mc_default_ir_tail(mc_ir_tail*) __attribute__((weak));
+int mc_load_ir_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
+                    const mc_ir_tail*) __attribute__((weak));
+int mc_load_ir_sweep_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
+                          const mc_ir_damp*, const mc_ir_tail*) __attribute__((weak));
+int mc_ir_tail_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 }
 
 namespace {
@@ -158,7 +168,11 @@ uint64_t Convolution::dampFrames(double seconds, double rate) {
 // synth: the engine generates the frames (lr null; sessionRate = synth->rate).  sweep: lr is the recording of a sweep, `frames`
 // frames at sessionRate = sweep->sweep.rate, which the engine deconvolves
 void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
-                             const IrEq& eq, const IrDamp& damp, const mc_ir_synth* synth, const SweepLoad* sweep) {
+                             const IrEq& eq, const IrDamp& damp, const mc_ir_synth* synth, const SweepLoad* sweep, const mc_ir_tail* tail) {
+    if (tail && (!mc_load_ir_tail || !mc_load_ir_sweep_tail || !mc_ir_tail_info)) {
+        Log::error("conv", "the engine has no tail step (mc_load_ir_tail)");
+        std::exit(2);
+    }
     if (sweep && (!mc_load_ir_sweep || !mc_default_sweep || !mc_ir_sweep_info)) {
         Log::error("conv", "the engine has no sweep capture (mc_load_ir_sweep)");
         std::exit(2);
@@ -214,8 +228,11 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         Log::info(name, "IR %zu synthesised: %llu frames, seed %llu, %d of %u reflections kept", idx, (unsigned long long)si[0],
                   (unsigned long long)synth->seed, (int)si[1], synth->n_early);
     } else if (sweep) {  // (as for a generated IR: what the engine refuses is the index line's fault)
-        if (mc_load_ir_sweep(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s, eq.off() ? nullptr : &q,
-                             damp.off() ? nullptr : &d) != MC_OK) {
+        const int rc = tail ? mc_load_ir_sweep_tail(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
+                                                    eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
+                            : mc_load_ir_sweep(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
+                                               eq.off() ? nullptr : &q, damp.off() ? nullptr : &d);
+        if (rc != MC_OK) {
             Log::error("conv", "IR %zu cannot be captured: %s", idx, mc_last_error());
             std::exit(2);
         }
@@ -223,12 +240,25 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         check(mc_ir_sweep_info(_engine, idx, wi), "mc_ir_sweep_info");
         Log::info(name, "IR %zu captured: sweep %llu frames, recording %llu frames, %llu frames at offset %lld", idx, (unsigned long long)wi[0],
                   (unsigned long long)wi[1], (unsigned long long)wi[2], (long long)wi[3]);
+    } else if (tail) {
+        check(mc_load_ir_tail(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail),
+              "mc_load_ir_tail");
     } else if (!damp.off()) {
         check(mc_load_ir_damped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, &d), "mc_load_ir_damped");
     } else if (eq.off())
         check(mc_load_ir_shaped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s), "mc_load_ir_shaped");
     else
         check(mc_load_ir_eq(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, &q), "mc_load_ir_eq");
+    if (tail) {
+        double ti[4];
+        check(mc_ir_tail_info(_engine, idx, ti), "mc_ir_tail_info");
+        std::string knees;
+        for (uint32_t j = 0; j <= tail->n_xovers; j++)
+            knees += (j ? ", " : "") + (tail->knee[j] == ~0ull ? std::string("none") : std::to_string((unsigned long long)tail->knee[j]));
+        Log::info(name, "IR %zu tail: %s, %d of %u bands at knees %s, %llu frames in, %llu out, first frame changed %llu", idx,
+                  tail->mode == MC_TAIL_CUT ? "cut" : "extended", (int)ti[0], tail->n_xovers + 1, knees.c_str(), (unsigned long long)ti[1],
+                  (unsigned long long)ti[2], (unsigned long long)ti[3]);
+    }
     double info[8];
     check(mc_ir_shape_info(_engine, idx, info), "mc_ir_shape_info");
     Log::info(name, "IR %zu shaped: onset %llu, first kept frame %llu, %llu taps, gain %+.2f dB", idx, (unsigned long long)info[1],
@@ -352,6 +382,145 @@ void Convolution::aimRt60(const PendingIr& p) {
     loadPending(p, shape);
     Log::info(name, "IR %zu rt60: measured %.4f s, decay %llu frames, now %s s", p.idx, measured, (unsigned long long)shape.decayT60,
               places(measuredRt(*this, p.idx), 4).c_str());
+}
+
+void Convolution::setIrFloorReport(bool on) {
+    if (on && _group) {
+        Log::error("conv", "the IR floor report is not available with several devices (mc_ir_floor is single-engine)");
+        std::exit(2);
+    }
+    _floorReport = on;
+}
+
+void Convolution::setIrFloorXovers(const std::vector<float>& xovers) {
+    if (xovers.size() > MC_FLOOR_MAX_XOVERS) {
+        Log::error("conv", "%zu floor crossovers, at most %d", xovers.size(), MC_FLOOR_MAX_XOVERS);
+        std::exit(2);
+    }
+    _floorXovers = xovers;
+}
+
+void Convolution::setIrTail(const IrTail& tail) {
+    if (tail.mode != IrTail::Off && _group) {
+        Log::error("conv", "the IR tail step is not available with several devices (mc_load_ir_tail is single-engine)");
+        std::exit(2);
+    }
+    _irTail = tail;
+}
+
+bool Convolution::parseTail(const std::string& arg, IrTail& out, std::string& why) {
+    const auto fail = [&](const std::string& w) {
+        why = w + " (cut|extend[:key=value,...] with keys fade, length, seed, width)";
+        return false;
+    };
+    const size_t colon = arg.find(':');
+    const std::string mode = arg.substr(0, colon);
+    IrTail t;
+    if (mode == "cut") t.mode = IrTail::Cut;
+    else if (mode == "extend") t.mode = IrTail::Extend;
+    else return fail("the mode is cut or extend, not '" + mode + "'");
+    if (colon != std::string::npos) {
+        const std::string list = arg.substr(colon + 1);
+        if (list.empty()) return fail("an empty list");
+        for (size_t at = 0; at <= list.size();) {
+            const size_t comma = std::min(list.find(',', at), list.size());
+            const std::string item = list.substr(at, comma - at);
+            at = comma + 1;
+            const size_t eqs = item.find('=');
+            if (item.empty() || eqs == std::string::npos || eqs == 0 || eqs + 1 == item.size()) return fail("'" + item + "' is not key=value");
+            const std::string key = item.substr(0, eqs), val = item.substr(eqs + 1);
+            char* end = nullptr;
+            if (key == "seed") {
+                t.seed = std::strtoull(val.c_str(), &end, 10);
+                if (*end || val[0] == '-') return fail("seed '" + val + "' is not a number >= 0");
+                continue;
+            }
+            const double v = std::strtod(val.c_str(), &end);
+            if (*end || !std::isfinite(v)) return fail("'" + val + "' of " + key + " is not a number");
+            if (key == "fade" || key == "length") {
+                if (v < 0.0 || v > 4000.0) return fail(key + " " + val + " s outside [0, 4000]");
+                (key == "fade" ? t.fadeSeconds : t.lengthSeconds) = v;
+            } else if (key == "width") {
+                if (v < 0.0 || v > 1.0) return fail("width " + val + " outside [0, 1]");
+                t.width = (float)v;
+            } else
+                return fail("no such key '" + key + "'");
+        }
+    }
+    out = t;
+    return true;
+}
+
+Convolution::Floor Convolution::irFloor(size_t idx, const std::vector<float>& xovers, unsigned rate) {
+    if (!mc_ir_floor || !mc_default_floor_query) {
+        Log::error("conv", "the engine has no floor measurement (mc_ir_floor)");
+        std::exit(2);
+    }
+    if (xovers.size() > MC_FLOOR_MAX_XOVERS) {
+        Log::error("conv", "%zu floor crossovers, at most %d", xovers.size(), MC_FLOOR_MAX_XOVERS);
+        std::exit(2);
+    }
+    Floor f;
+    mc_default_floor_query(&f.query);
+    f.query.rate = rate ? rate : (uint32_t)samplerate;
+    f.query.n_xovers = (uint32_t)xovers.size();
+    for (size_t k = 0; k < xovers.size(); k++) f.query.xover_hz[k] = xovers[k];
+    f.rows.resize((1 + (xovers.empty() ? 0 : xovers.size() + 1)) * 3 * 8);
+    uint64_t info[2] = {0, 0};
+    if (mc_ir_floor(_engine, idx, &f.query, f.rows.data(), info) != MC_OK) {  // (crossovers the rate does not allow: the command line's fault)
+        Log::error("conv", "IR %zu: the floor cannot be measured: %s", idx, mc_last_error());
+        std::exit(2);
+    }
+    f.origin = info[0];
+    f.taps = info[1];
+    return f;
+}
+
+void Convolution::reportFloor(size_t idx) {
+    const Floor f = irFloor(idx, _floorXovers);
+    for (size_t g = 0; g < f.groups(); g++) {
+        char head[32] = "";
+        if (g) std::snprintf(head, sizeof(head), " band %zu", g - 1);
+        const auto v = [&](Floor::Field fld, int decimals) { return places(f.at(g, Decay::LR, fld), decimals); };
+        const double nz = f.at(g, Decay::LR, Floor::Noise);
+        Log::info(name, "IR %zu%s floor: origin %llu, knee %s, T %s s, noise %s dB, peak to noise %s dB, interval %s, status %d", idx, head,
+                  (unsigned long long)f.origin, v(Floor::Knee, 1).c_str(), v(Floor::T, 4).c_str(), places(10.0 * std::log10(nz), 2).c_str(),
+                  v(Floor::PeakToNoise, 2).c_str(), v(Floor::Interval, 0).c_str(), (int)f.at(g, Decay::LR, Floor::Status));
+    }
+}
+
+// Loads p as it is (no shape, EQ or damping: the frames at the client's rate), measures its floor and leaves in _tailNow / _tailOn
+// the tail step its final load goes through
+void Convolution::measureTail(const PendingIr& p) {
+    _tailOn = false;
+    if (!mc_ir_tail_from_floor || !mc_default_ir_tail || !mc_load_ir_tail) {
+        Log::error("conv", "the engine has no tail step (mc_load_ir_tail)");
+        std::exit(2);
+    }
+    if (p.generated) {
+        Log::info(name, "IR %zu tail: a generated IR has no floor, left as it is", p.idx);
+        return;
+    }
+    PendingIr raw = p;
+    raw.eq = IrEq();
+    raw.damp = IrDamp();
+    loadPending(raw, IrShape());
+    const Floor f = irFloor(p.idx, _floorXovers);
+    const double need = (double)f.query.margin_db + (double)f.query.span_db, ptn = f.at(0, Decay::LR, Floor::PeakToNoise);
+    if (f.at(0, Decay::LR, Floor::Status) != 0.0 || !(ptn >= need)) {
+        Log::info(name, "IR %zu tail: peak to noise %s dB (status %d) is under %g dB, left as it is", p.idx, places(ptn, 2).c_str(),
+                  (int)f.at(0, Decay::LR, Floor::Status), need);
+        return;
+    }
+    mc_default_ir_tail(&_tailNow);
+    const uint64_t info[2] = {f.origin, f.taps};
+    check(mc_ir_tail_from_floor(&f.query, f.rows.data(), info, 0, &_tailNow), "mc_ir_tail_from_floor");
+    _tailNow.mode = _irTail.mode == IrTail::Cut ? MC_TAIL_CUT : MC_TAIL_EXTEND;
+    _tailNow.fade = (uint32_t)std::nearbyint(_irTail.fadeSeconds * (double)samplerate);
+    _tailNow.length = (uint64_t)std::nearbyint(_irTail.lengthSeconds * (double)samplerate);
+    _tailNow.seed = _irTail.seed;
+    _tailNow.width = _irTail.width;
+    _tailOn = true;
 }
 
 mc_ir_synth Convolution::synthFrames(const IrSynth& y, double rate) {
@@ -615,7 +784,8 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
                                                   : M - (int64_t)w.sweep.frames + 1 - w.offset;  // what the recording holds past the sweep
         if (!(p.sweep.irLengthSeconds > 0.0)) F = std::min(F, std::min(cap, (int64_t)((1ull << 40) / std::max<uint64_t>(w.sweep.frames, 1))));
         w.irFrames = (uint64_t)std::max<int64_t>(F, 1);
-        loadShaped(p.idx, p.lr.data(), (uint64_t)M, p.nframes, (unsigned)samplerate, (unsigned)samplerate, shape, p.eq, p.damp, nullptr, &w);
+        loadShaped(p.idx, p.lr.data(), (uint64_t)M, p.nframes, (unsigned)samplerate, (unsigned)samplerate, shape, p.eq, p.damp, nullptr, &w,
+                   _tailOn ? &_tailNow : nullptr);
         return;
     }
     if (p.generated) {
@@ -629,8 +799,9 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
     }
     const uint64_t frames = p.lr.size() / 2;
     const bool convert = p.match && p.rate && p.rate != samplerate;
-    if (!p.eq.off() || !p.damp.off()) {  // (bands and crossovers are laid out at the client's rate; frames that are not converted count as being at it)
-        loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : (unsigned)samplerate, (unsigned)samplerate, shape, p.eq, p.damp);
+    if (!p.eq.off() || !p.damp.off() || _tailOn) {  // (bands and crossovers are laid out at the client's rate; frames that are not converted count as being at it)
+        loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : (unsigned)samplerate, (unsigned)samplerate, shape, p.eq, p.damp, nullptr,
+                   nullptr, _tailOn ? &_tailNow : nullptr);
         return;
     }
     if (!shape.off()) {
@@ -651,15 +822,18 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
 
 void Convolution::loadPendingIrs() {
     for (const PendingIr& p : _pendingIrs) {
+        if (_irTail.mode != IrTail::Off) measureTail(p);
         loadPending(p, p.shape);
         if (_rt60 > 0.0) aimRt60(p);
         if (_decayReport) reportDecay(p.idx);
+        if (_floorReport) reportFloor(p.idx);
+        _tailOn = false;
     }
     _pendingIrs.clear();
 }
 
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
-    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0) {  // (loaded by onStart(), once the client's rate is known)
+    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _irTail.mode != IrTail::Off) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
         _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth(), false, IrSweep()});
         if (idx + 1 > _nirs) _nirs = idx + 1;

@@ -196,6 +196,41 @@ public:
     // False, with the reason in `why`, when the engine has no sweep, refuses it, or the file cannot be written.
     static bool writeSweep(const IrSweep& sweep, unsigned rate, std::string& why);
 
+    // The noise floor of a loaded IR, searched for by the engine in the taps it convolves with (mc_ir_floor of include/mcconv.h,
+    // which has the method; no reference equivalent): the broadband row group and, with 1 to 3 crossovers, one per band of
+    // IrDamp's split.  Everything else of the query is mc_default_floor_query's.  rate = 0: the client's sample rate.
+    struct Floor {
+        uint64_t origin = 0, taps = 0;
+        mc_floor_query query;
+        std::vector<double> rows;  // [groups * 3 * 8]: per group and channel set {E, Nz, knee, T, peak to noise dB, w, last change, status}
+        enum Field { Energy = 0, Noise, Knee, T, PeakToNoise, Interval, LastChange, Status };
+        size_t groups() const { return rows.size() / 24; }
+        double at(size_t group, Decay::Set set, Field f) const { return rows[(group * 3 + set) * 8 + f]; }
+    };
+    Floor irFloor(size_t idx, const std::vector<float>& xovers = {}, unsigned rate = 0);
+    // One log line per IR loaded from now on and row group (knee, late decay time, noise level, peak to noise, interval and
+    // status of the LR row), over the bands of setIrFloorXovers.  Loaded by onStart(), single device only, as setIrDecayReport.
+    void setIrFloorReport(bool on);
+    // The crossovers of the floor report's bands and of the tail step's (at most 3, ascending)
+    void setIrFloorXovers(const std::vector<float>& xovers);
+    // The tail step every IR loaded from now on goes through (mc_ir_tail of include/mcconv.h; no reference equivalent): the IR
+    // is loaded as it is, its floor is measured in the bands of setIrFloorXovers, and it is loaded again with every band cut at
+    // its knee (Cut) or cross-faded there into decaying noise (Extend) ahead of its shape, EQ and damping.  An IR whose
+    // broadband peak-to-noise ratio is under margin_db + span_db of the search (30 dB) is left as it is, with a log line that
+    // says so, and so is a generated one, which has no floor.  Seconds become frames at the client's rate by rint.  Loaded by
+    // onStart(), single device only.
+    struct IrTail {
+        enum Mode { Off = 0, Cut = 1, Extend = 2 } mode = Off;
+        double fadeSeconds = 0.0;    // cross-fade that ends at each knee
+        double lengthSeconds = 0.0;  // frames the step hands on; 0: as many as came in
+        uint64_t seed = 0;
+        float width = 1.0f;
+    };
+    void setIrTail(const IrTail& tail);
+    // The argument of --ir-tail, cut|extend[:key=value,...] with keys fade, length (seconds), seed and width, as an IrTail.
+    // False, with the reason in `why`, for a malformed one.
+    static bool parseTail(const std::string& arg, IrTail& out, std::string& why);
+
     void onMidiMessage(const RawMidi::Device* sender, const uint8_t* buffer, size_t len) override;
 
     // offline rendering through the same engine: nblocks * 256 frames per channel
@@ -234,6 +269,13 @@ private:
     void loadPending(const PendingIr& p, const IrShape& shape);
     void aimRt60(const PendingIr& p);
     void reportDecay(size_t idx);
+    void reportFloor(size_t idx);
+    void measureTail(const PendingIr& p);
+    bool _floorReport = false;
+    std::vector<float> _floorXovers;
+    IrTail _irTail;
+    bool _tailOn = false;  // loadPending: the IR being loaded goes through _tailNow
+    mc_ir_tail _tailNow;
     bool _decayReport = false;
     std::vector<float> _decayBands;
     double _rt60 = 0.0;
@@ -242,7 +284,7 @@ private:
     IrDamp _irDamp;
     void loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
                     const IrEq& eq = IrEq(), const IrDamp& damp = IrDamp(), const mc_ir_synth* synth = nullptr,
-                    const SweepLoad* sweep = nullptr);
+                    const SweepLoad* sweep = nullptr, const mc_ir_tail* tail = nullptr);
     void pushParams();
     void pullVsteps();
 };

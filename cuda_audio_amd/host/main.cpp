@@ -27,6 +27,11 @@
 // times in seconds, the recording at the client's sample rate); the --ir-* options apply to it as to a WAV.
 // --write-sweep FILE.wav:LENGTH_S:F1:F2[:key=value,...] writes that sweep (keys amp, fadein, fadeout) at --rate (44100 without)
 // to both channels of a 24-bit WAV file and exits: what to play through the room.
+// --ir-floor-report: after each IR is loaded one log line per row group with its noise floor (knee, late decay time, noise level,
+// peak to noise, measured by the engine: Convolution::setIrFloorReport); --ir-floor-xovers HZ[,HZ[,HZ]]: the crossovers whose bands
+// are row groups of their own, and the bands of --ir-tail; --ir-tail cut|extend[:fade=S,length=S,seed=N,width=W]: every IR is
+// loaded, its floor measured, and loaded again with every band cut at its knee or extended from there with decaying noise,
+// ahead of the other --ir-* options, Convolution::setIrTail; an IR with less than 30 dB between peak and floor is left as it is.
 #include <cassert>
 #include <cstdlib>
 #include <cstring>
@@ -54,6 +59,9 @@ int main(int argc, char** argv) {
     double irRt60 = 0.0;
     Convolution::IrDamp irDamp;
     const char* writeSweep = nullptr;
+    bool irFloorReport = false;
+    std::vector<float> irFloorXovers;
+    Convolution::IrTail irTail;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--periods") && i + 1 < argc) periods = strtoull(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "--settings") && i + 1 < argc) settingsPath = argv[++i];
@@ -147,6 +155,26 @@ int main(int argc, char** argv) {
                 std::cerr << "--ir-damp-origin takes a tap index" << std::endl;
                 return 2;
             }
+        } else if (!strcmp(argv[i], "--ir-floor-report")) irFloorReport = true;
+        else if (!strcmp(argv[i], "--ir-floor-xovers") && i + 1 < argc) {
+            irFloorXovers.clear();
+            for (const char* a = argv[++i];;) {
+                char* end = nullptr;
+                irFloorXovers.push_back(strtof(a, &end));
+                if (end == a || (*end && *end != ',') || irFloorXovers.size() > 3 || !(irFloorXovers.back() > 0.f) ||
+                    (irFloorXovers.size() > 1 && !(irFloorXovers.back() > irFloorXovers[irFloorXovers.size() - 2]))) {
+                    std::cerr << "--ir-floor-xovers takes HZ[,HZ[,HZ]]: 1 to 3 ascending crossover frequencies" << std::endl;
+                    return 2;
+                }
+                if (!*end) break;
+                a = end + 1;
+            }
+        } else if (!strcmp(argv[i], "--ir-tail") && i + 1 < argc) {
+            std::string why;
+            if (!Convolution::parseTail(argv[++i], irTail, why)) {
+                std::cerr << "--ir-tail '" << argv[i] << "': " << why << std::endl;
+                return 2;
+            }
         } else if (!strcmp(argv[i], "--ir-rt60") && i + 1 < argc) {
             irRt60 = atof(argv[++i]);
             if (!(irRt60 > 0.0)) {
@@ -188,6 +216,9 @@ int main(int argc, char** argv) {
         c->setIrDamp(irDamp);
         if (irDecayReport) c->setIrDecayReport(true, irDecayBands);
         if (irRt60 > 0.0) c->setIrRt60(irRt60);
+        c->setIrFloorXovers(irFloorXovers);
+        if (irFloorReport) c->setIrFloorReport(true);
+        c->setIrTail(irTail);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;
             const auto deviceId = settings.str("conv[%d].cc.device", idx);

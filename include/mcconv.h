@@ -146,6 +146,8 @@ int mc_load_ir_resampled(mc_engine *e, uint64_t idx, const float *lr, uint64_t f
  *
  * Order of operations (lengths and positions are frames at the session's rate):
  *   1. the whole IR is converted to the session's rate when the rates differ (as by the resampled load); F frames;
+ *   1a. (mc_load_ir_tail and mc_load_ir_sweep_tail only) every band of the F frames is cut at its knee or cross-faded there into
+ *      decaying noise (mc_ir_tail below); F' frames leave the step and take the place of the F in everything that follows;
  *   2. s0 = min(start, F); with trim_db < 0 the onset is the first frame m after s0 whose max(|L|, |R|) reaches
  *      peak * 10^(trim_db / 20) (float arithmetic; peak over all frames after s0); first = s0 + max(0, onset - pre_roll);
  *   3. n = min(F - first, length or unlimited, n_ref - nframes) frames are stored (n = 0: MC_ERR_ARG, nothing changes);
@@ -310,7 +312,8 @@ int mc_ir_damp_response(const mc_ir_damp *d, uint32_t rate, uint64_t tap, const 
  *      curve[(b 3 + s) K + j] = max(L[o + floor(j (N - 1 - o) / (K - 1))], -400), K = curve_points.
  * The curve of a finite IR always bends down towards tap N - 1, because the integral runs out there: a time fitted over a
  * range that reaches into that bend reads short.  `end` is the caller's tool against a noise floor or a cut; no noise-floor
- * compensation is attempted. */
+ * compensation is attempted here: mc_ir_floor (below) finds where the floor starts, which is what to pass as `end`, and
+ * mc_load_ir_tail removes the floor from the IR itself. */
 #define MC_DECAY_MAX_BANDS 10
 #define MC_DECAY_MAX_CURVE 1024
 typedef struct {
@@ -333,6 +336,57 @@ void mc_default_decay_query(mc_decay_query *q);
  * the caller's arrays.  Nothing the engine holds changes: later outputs, the stored taps, mc_ir_info and mc_ir_shape_info are
  * bit for bit what they would have been.  Two calls with the same query on the same IR return the same bits. */
 int mc_ir_decay(mc_engine *e, uint64_t idx, const mc_decay_query *q, double *rows, double *curve, uint64_t info[2]);
+
+/* The noise floor of a loaded IR, measured on the device: where a captured IR (mc_load_ir_sweep) stops decaying and turns
+ * into the hiss of the room and the recorder, by Lundeby's method, which ISO 3382 points to.  No reference equivalent;
+ * single-engine.  The stored taps are only read; N, the origin o, the channel sets s = L, R, L + R and e[m], EDC[m] (with
+ * EDC[N] = 0) are those of mc_ir_decay's steps 1, 3 and 4.
+ *
+ * Row groups.  Group 0 is broadband, y = x.  With X = n_xovers >= 1, group j + 1 is band B_j, j = 0 .. X, of mc_ir_damp's split
+ *   of x[0 .. N): P_k = x through crossover k's two identical HIGHCUT sections (q = (double)0.70710678f) from rest at tap 0,
+ *   B_0 = P_1, B_j = P_(j+1) - P_j, B_X = x - P_X: the bands mc_ir_tail acts on.
+ * The search, per row, in double.  n1 = N - o, cap = floor(n1 / 16), tail = max(1, floor(tail_fraction n1)).
+ *   means(w)  I = floor(n1 / w) intervals of w taps: P_i = (EDC[o + i w] - EDC[o + (i + 1) w]) / w, D_i = 10 log10 P_i,
+ *             t_i = o + i w + (w - 1) / 2;
+ *   noise(a)  Nz = EDC[a] / (N - a), V = 10 log10 Nz.  Nz = 0 (the tail is silent: there is no floor) ends the row with
+ *             status 3 and knee = N, before anything is fitted;
+ *   run(V)    ip = the first index of the largest P_i; iF = the first i >= ip with D_i < V + margin_db, or I; R = [ip, iF);
+ *   fit(S)    least squares of D_i over x_i = t_i - t_(min S), the four sums and the slope a of mc_ir_decay's step 5,
+ *             c = (sum y - a sum x) / |S|; the line meets V at t_(min S) + (V - c) / a.  Fewer than 2 intervals, or an a that
+ *             is not a finite negative number, end the row with status 2 (no decay above the floor);
+ *   status 1  (too short or silent) cap < 1 or E = EDC[o] = 0;
+ *   first     w0 = min(window or floor(0.03 rate + 0.5), cap); V = noise(N - tail); fit(run(V)) over means(w0); tc = the crossing;
+ *   interval  w = clamp(floor(-10 / (a per_decade) + 0.5), 1, cap), chosen once; means(w);
+ *   rounds    exactly `rounds` times: a_n = min(max(ceil(tc + margin_db / -a), o), N - tail); V = noise(a_n); R = run(V);
+ *             S = {i in R : D_i <= V + margin_db + span_db}, or R when that has fewer than 2 members; fit(S); tc_prev = tc,
+ *             tc = the crossing.  No convergence test: slot 6 reports the last change instead.
+ * rows[(3 g + s) 8 ..] = {E, Nz, knee tc (taps, fractional, may lie past N), T = -60 / (a rate) seconds, 10 log10(max P_i / Nz) dB,
+ *   w, |tc - tc_prev|, status}; with status != 0 the row holds E, the status and status 3's knee, every other entry is NaN.
+ * A clean exponential IR has a knee too, near its end: its last tail_fraction is noise by definition, however far down.  Look
+ * at slot 4, the peak-to-noise ratio, before acting on a knee: a floor 150 dB under the peak is the end of the file, not hiss. */
+#define MC_FLOOR_MAX_XOVERS 3
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_floor_query) = 64 */
+    uint32_t rate;          /* the rate the stored taps are at, [8000, 384000] */
+    uint32_t n_xovers;      /* X, 0 .. MC_FLOOR_MAX_XOVERS: 1 + (X ? X + 1 : 0) row groups */
+    uint32_t window;        /* first averaging interval in taps; 0 = floor(0.03 rate + 0.5) */
+    float xover_hz[MC_FLOOR_MAX_XOVERS]; /* as mc_ir_damp: finite, [10, 0.45 rate], strictly ascending */
+    float onset_db;         /* as mc_decay_query; default -20 */
+    uint64_t end;           /* as mc_decay_query */
+    float tail_fraction;    /* (0, 0.5]; default 0.1: the last share of the analysed taps that always counts as noise */
+    float margin_db;        /* [1, 30]; default 10 */
+    float span_db;          /* [5, 60]; default 20 */
+    uint32_t per_decade;    /* 1 .. 20; default 5: intervals per 10 dB of decay */
+    uint32_t rounds;        /* 1 .. 16; default 5 */
+    uint32_t reserved;      /* must be 0 */
+} mc_floor_query;
+/* rate 44100, no crossovers (xover_hz = {250, 2000, 8000}), window 0, onset -20, end 0, and the defaults above */
+void mc_default_floor_query(mc_floor_query *q);
+/* rows: [(1 + (X ? X + 1 : 0)) * 3 * 8]; info = {origin tap, taps analysed N}.  Checked in this order, all before the engine or
+ * the device is touched (MC_ERR_ARG, the message names the field): the query field by field, the pointers, idx ("IR not
+ * loaded").  MC_ERR_STATE in the single-transform form, which keeps no taps.  Threading, stream and the promise that nothing
+ * the engine holds changes are mc_ir_decay's; two calls with the same query on the same IR return the same bits. */
+int mc_ir_floor(mc_engine *e, uint64_t idx, const mc_floor_query *q, double *rows, uint64_t info[2]);
 
 /* Synthesis of an IR on the device from a seed: a room from a few numbers instead of a recorded WAV.  No reference equivalent;
  * single-engine, as shaping is.  The F = frames stereo frames are generated at the session's rate into the buffer the shaped
@@ -440,6 +494,69 @@ int mc_load_ir_sweep(mc_engine *e, uint64_t idx, const float *lr, uint64_t frame
                      int64_t offset, uint64_t ir_frames, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp);
 /* out = {N, M, F, offset}; MC_ERR_STATE unless the IR's last load was mc_load_ir_sweep */
 int mc_ir_sweep_info(const mc_engine *e, uint64_t idx, double out[4]);
+
+/* The tail step of an IR load (step 1a of the order of operations above): every frequency band of the F frames is cut at its
+ * knee, or cross-faded there into decaying noise that continues the band's own slope at the band's own level (tail
+ * extrapolation), which also lets a recording that stopped too early run out.  No reference equivalent; single-engine.  The
+ * step sits before the selection, so a fade-out ends at the new last tap and decay_t60, damping and EQ act on the new tail.
+ *
+ * x = the F frames at the session's rate as double, frames at and past F reading as 0; F' = length ? length : F; X = n_xovers;
+ * P_k(.) = crossover k's two identical HIGHCUT sections (mc_ir_damp's) from rest at frame 0 over [0, F').
+ *   Fades.  Band j with K_j = knee[j] < F' is touched: W_j = min(fade, K_j); for m < K_j - W_j fo = 1, fi = 0; for
+ *     K_j - W_j <= m < K_j theta = (pi / 2) (m - (K_j - W_j) + 1) / (W_j + 1), fo = cos theta, fi = sin theta; for m >= K_j
+ *     fo = 0, fi = 1 (power-complementary: the two signals are uncorrelated).  A band with K_j >= F' is left alone: fo = 1,
+ *     fi = 0 throughout.
+ *   Noise (MC_TAIL_EXTEND).  v_L[m] = gA, v_R[m] = rho gA + sqrt(1 - rho^2) gB, rho = 1 - width, from the words W(m, 3) as
+ *     mc_ir_synth's late field makes them from W(m, 0) (stream 3 is this step's own);
+ *     g_j[m] = exp2(-((double)((int64) m - (int64) K_j) 3 log2(10)) / t60[j]);
+ *     A_(j,c) = sqrt(10^(level_db[j][c] / 10) / beta_j), beta_j = the share of white noise band j passes: the mean over
+ *     i = 0 .. 8191 of |B_j(e^(j pi (i + 0.5) / 8192))|^2, B_0 = H_1^2, B_j = H_(j+1)^2 - H_j^2, B_X = 1 - H_X^2, H_k one section's
+ *     complex response (1 with X = 0), on the host in double; q_j[m] = fi_j A_(j,c) g_j where fi_j > 0, and 0 elsewhere.
+ *   Output, per channel c, in double, rounded to float once:
+ *     y[m] = fo_X x + sum over k = 1 .. X of (fo_(k-1) - fo_k) P_k(x) + [EXTEND] q_X v + sum over k of (q_(k-1) - q_k) P_k(v),
+ *     added in that order: damping's rearrangement, twice.  With every fo = 1 the filters cancel, so frames before the first
+ *     touched one, min over the touched bands of K_j - W_j, are the input's, bit for bit.  MC_TAIL_CUT is the same without the
+ *     noise: each band fades to nothing at its knee, and mc_ir_shape.length shortens the IR. */
+enum { MC_TAIL_OFF = 0, MC_TAIL_CUT = 1, MC_TAIL_EXTEND = 2 };
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_ir_tail) = 144 */
+    uint32_t mode;          /* MC_TAIL_*; MC_TAIL_OFF: every other field ignored */
+    uint32_t n_xovers;      /* X, 0 .. 3; 0 = one broadband band */
+    float xover_hz[3];      /* the first X: finite, [10, 0.45 session_rate], strictly ascending */
+    uint32_t fade;          /* W: cross-fade length in frames; the fade ends at the knee */
+    float width;            /* [0, 1], as mc_ir_synth.width */
+    uint64_t seed;
+    uint64_t length;        /* F' = length ? length : F; 1 .. 2^24 */
+    uint64_t knee[4];       /* K_j of band j = 0 .. X, a frame at the session's rate; >= F' leaves the band alone */
+    uint64_t t60[4];        /* EXTEND, bands 0 .. X: > 0; band j's noise is 60 dB down t60[j] frames after K_j */
+    float level_db[4][2];   /* EXTEND, bands 0 .. X: finite; 10 log10 of band j's power per frame at K_j, channel L, R */
+} mc_ir_tail;
+/* off; xover_hz = {250, 2000, 8000}; fade 0; width 1; seed 0; length 0; every knee UINT64_MAX; t60 1; levels 0 */
+void mc_default_ir_tail(mc_ir_tail *t);
+/* Fills n_xovers, xover_hz, knee, t60 and level_db of `tail` from a floor measurement (q, rows, info as mc_ir_floor took and
+ * gave them); mode, seed, width, fade and length stay the caller's.  Host arithmetic only: no engine, no HIP call.  With
+ * X >= 1 tail band j is read from row group j + 1, with X = 0 the one band from group 0: knee[j] = first + floor(tc) of the
+ * group's L + R row, t60[j] = max(1, floor(T rate + 0.5)) of that row, level_db[j][c] = channel c's own row's line at that
+ * knee, 10 log10 Nz_c + a_c (knee - first - tc_c) (from the L + R row less 10 log10 2 when the channel's row has a status).
+ * A band whose L + R row has status != 0 or whose floor(tc) >= info[1] gets knee = UINT64_MAX and is left alone.  `first` is
+ * mc_ir_shape_info's first kept frame when the measured load trimmed, else 0.  MC_ERR_ARG for a bad query or a null pointer. */
+int mc_ir_tail_from_floor(const mc_floor_query *q, const double *rows, const uint64_t info[2], uint64_t first, mc_ir_tail *tail);
+/* mc_load_ir_damped with `tail` applied as step 1a.  With tail NULL or MC_TAIL_OFF the call is mc_load_ir_damped itself, bit for
+ * bit.  With a tail on everything is checked before the engine or the device is touched (MC_ERR_ARG, the message names the
+ * field, the engine stays as it was): tail field by field in the struct's order, then session_rate and ir_rate (both in [8000,
+ * 384000]; 0 / 0 is refused because the crossovers need the session's rate) and F', then damp, eq and shape as by
+ * mc_load_ir_damped.  Such a load counts as shaped: mc_ir_shape_info's out[0] is F'.  The same frames and structs store the
+ * same bits. */
+int mc_load_ir_tail(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
+                    uint32_t session_rate, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp, const mc_ir_tail *tail);
+/* mc_load_ir_sweep with `tail` applied to the deconvolved frames; tail NULL or MC_TAIL_OFF: mc_load_ir_sweep itself, bit for
+ * bit.  With a tail on: tail field by field, then everything mc_load_ir_sweep checks, in its order, with F' after F. */
+int mc_load_ir_sweep_tail(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, const mc_sweep *sweep,
+                          int64_t offset, uint64_t ir_frames, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp,
+                          const mc_ir_tail *tail);
+/* out = {bands touched, F, F', first frame changed (F' when no band was touched)}; MC_ERR_STATE unless the IR's last load had
+ * a tail on */
+int mc_ir_tail_info(const mc_engine *e, uint64_t idx, double out[4]);
 
 int mc_num_irs(const mc_engine *e);
 /* out[0..3] = sum h_L, sum h_R, sum h_L(-1)^m, sum h_R(-1)^m of the truncated IR; out[4] = taps, out[5] = partitions */
