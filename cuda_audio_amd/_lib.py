@@ -23,7 +23,8 @@ SYMBOLS = [
     "mc_default_ir_synth", "mc_synth_ir", "mc_ir_synth_info",
     "mc_default_sweep", "mc_sweep_generate", "mc_load_ir_sweep", "mc_ir_sweep_info",
     "mc_default_decay_query", "mc_ir_decay", "mc_default_floor_query", "mc_ir_floor", "mc_ir_tail_from_floor",
-    "mc_default_ir_tail", "mc_load_ir_tail", "mc_load_ir_sweep_tail", "mc_ir_tail_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
+    "mc_default_ir_tail", "mc_load_ir_tail", "mc_load_ir_sweep_tail", "mc_ir_tail_info",
+    "mc_default_ir_room", "mc_synth_ir_room", "mc_ir_room_info", "mc_ir_room_plan", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
     "mc_enable_kernel_timing", "mc_get_kernel_stats", "mc_algorithmic_bytes_per_block", "mc_blocks_processed", "mc_preferred_batch",
@@ -232,6 +233,28 @@ class McIrTail(C.Structure):
     ]
 
 
+MC_ROOM_MAX_ORDER = 32
+
+
+class McIrRoom(C.Structure):
+    """mc_ir_room: the rectangular room whose reflections mc_synth_ir_room adds to a synthesised IR."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("order", C.c_uint32),
+        ("size_m", C.c_float * 3),
+        ("source_m", C.c_float * 3),
+        ("receiver_m", C.c_float * 3),
+        ("beta", C.c_float * 6),
+        ("spacing_m", C.c_float),
+        ("axis", C.c_uint32),
+        ("speed", C.c_float),
+        ("gain", C.c_float),
+        ("reserved", C.c_uint32),
+        ("last", C.c_uint64),
+    ]
+
+
 class McKernelStats(C.Structure):
     _fields_ = [
         ("launches", C.c_uint64),
@@ -318,6 +341,12 @@ def load():
     L.mc_load_ir_sweep_tail.argtypes = [vp, u64, fp, u64, u64, C.POINTER(McSweep), C.c_int64, u64, C.POINTER(McIrShape), C.POINTER(McIrEq),
                                         C.POINTER(McIrDamp), C.POINTER(McIrTail)]
     L.mc_ir_tail_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_default_ir_room.argtypes = [C.POINTER(McIrRoom)]
+    L.mc_default_ir_room.restype = None
+    L.mc_synth_ir_room.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrRoom), C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp),
+                                   C.POINTER(McIrTail)]
+    L.mc_ir_room_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_ir_room_plan.argtypes = [C.POINTER(McIrRoom), C.c_uint32, u64, C.POINTER(C.c_double)]
     L.mc_num_irs.argtypes = [vp]
     L.mc_ir_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_set_params.argtypes = [vp, C.c_int, C.POINTER(McCcValue)]

@@ -1,0 +1,327 @@
+// irroom.hip.h — the reflections of a rectangular room on the device (mc_synth_ir_room): Allen and Berkley's image-source
+// method, every image a Hann-windowed sinc of 32 taps at its fractional delay, summed in 64-bit integers.  No reference
+// equivalent: the reference convolves with the frames of a WAV file.
+//
+// include/mcconv.h has the definition and tests/ir_room_np.py states it in float64:
+//   images    n in [-N, N]^3, u in {0, 1}^3: p_a = ((1 - 2 u_a) s_a + 2 n_a L_a) - r_a per receiver, d = |p|,
+//             a = gain * prod_a beta_(a,0)^|n_a - u_a| beta_(a,1)^|n_a| / d, tau = d rate / c, k0 = floor(tau), f = tau - k0;
+//   taps      k = -15 .. 16, x = k - f: w_k = (k odd ? s : -s) / (pi x) * (1 + cos(pi x / 16)) / 2, s = sin(pi f); f == 0: one tap;
+//   sum       q = llrint(a w_k 2^40) added into acc[k0 + k][channel], int64: the sum does not depend on the order of arrival,
+//             so the same struct gives the same bits whatever the grid and however many images share a frame;
+//   frame     (float)(late + direct + reflections + acc 2^-40): irsynth.hip.h's three terms and this one, rounded once.
+//
+// k_room walks the lattice in one launch.  A wave takes 64 images at a time, one per lane, for the geometry: both receivers'
+// distances and k0, which prune an image before any transcendental when neither channel arrives before frame E (most of the
+// cube's corners go that way), then the amplitude (the powers of beta come from the host's table) and the one sine per channel.
+// The kept images are then scattered one per step with lane = (tap, channel): a wave instruction adds up to 64 neighbouring
+// 8-byte words (atomicAdd(unsigned long long*): one global_atomic_add_x2 per lane, no compare-and-swap loop).  The accumulator
+// holds min(E + 16, F) frames, is zeroed on the stream before the launch and freed after k_synth_room has read it; the images
+// kept per channel are counted with one add per wave and counter.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+
+#include "../../include/mcconv.h"
+#include "irsynth.hip.h"
+
+constexpr int ROOM_THREADS = 256;
+constexpr int ROOM_MAX_GRID = 2048;
+constexpr int ROOM_REACH = 16;               // taps k = -(ROOM_REACH - 1) .. ROOM_REACH: two per lane pair of a wave
+constexpr double ROOM_Q = 1099511627776.0;   // 2^40: the quantum of a contribution is 2^-40
+constexpr double ROOM_MIN_DIRECT = 0.1;      // metres
+constexpr double ROOM_MAX_SUM = 4194304.0;   // 2^22: 8 (2N + 1)^3 gain / d below it keeps the sum inside 2^62
+
+// a checked mc_ir_room as the kernels take it, everything in double from the float fields
+struct RoomPlan {
+    uint32_t N, S;      // the order used and 2N + 1
+    uint32_t total;     // 8 S^3 images
+    uint64_t E, F, A;   // images arriving at or after E are left out; A = min(E + 16, F) accumulator frames
+    uint64_t complete;  // floor(2 N min(L) rate / c)
+    double rate, speed, gain;
+    double size[3], src[3], rcv[2][3];
+    double tau[2];      // the direct sound's delay per channel, frames
+    double bpow[6][MC_ROOM_MAX_ORDER + 2];  // bpow[w][j] = pow(beta[w], j), 0^0 = 1
+};
+
+// One launch over the lattice; gridDim.x * ROOM_THREADS / 64 waves stride over it 64 images at a time.  acc: p.A frames of two
+// int64, zero; kept: two zeroed counters.
+__global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __restrict__ acc, unsigned* __restrict__ kept, RoomPlan p) {
+    const unsigned lane = threadIdx.x & 63u;
+    const uint32_t wave = (blockIdx.x * ROOM_THREADS + threadIdx.x) >> 6, nwaves = gridDim.x * (ROOM_THREADS / 64);
+    const int ch = (int)(lane & 1u), k = (int)(lane >> 1) - (ROOM_REACH - 1);
+    unsigned nkept[2] = {0u, 0u};
+    for (uint64_t base = (uint64_t)wave * 64; base < p.total; base += (uint64_t)nwaves * 64) {
+        const uint64_t i = base + lane;
+        long long k0[2] = {0, 0};
+        double f[2] = {0.0, 0.0}, s[2] = {0.0, 0.0}, a[2] = {0.0, 0.0};  // (a stays 0 for a channel that is not kept)
+        bool keep[2] = {false, false};
+        if (i < p.total) {
+            const uint32_t cell = (uint32_t)(i >> 3);
+            const int u[3] = {(int)(i & 1), (int)((i >> 1) & 1), (int)((i >> 2) & 1)};
+            const int n[3] = {(int)(cell % p.S) - (int)p.N, (int)((cell / p.S) % p.S) - (int)p.N, (int)(cell / (p.S * p.S)) - (int)p.N};
+            double q[3], b = p.gain;
+#pragma unroll
+            for (int ax = 0; ax < 3; ax++) q[ax] = (double)(1 - 2 * u[ax]) * p.src[ax] + (double)(2 * n[ax]) * p.size[ax];
+            double d[2], tau[2];
+#pragma unroll
+            for (int c = 0; c < 2; c++) {
+                const double px = q[0] - p.rcv[c][0], py = q[1] - p.rcv[c][1], pz = q[2] - p.rcv[c][2];
+                d[c] = sqrt(px * px + py * py + pz * pz);
+                tau[c] = d[c] * p.rate / p.speed;
+                const double fl = floor(tau[c]);
+                keep[c] = fl < (double)p.E;
+                k0[c] = (long long)fl;
+                f[c] = tau[c] - fl;
+            }
+            if (keep[0] || keep[1]) {
+#pragma unroll
+                for (int ax = 0; ax < 3; ax++) b *= p.bpow[2 * ax][abs(n[ax] - u[ax])] * p.bpow[2 * ax + 1][abs(n[ax])];
+#pragma unroll
+                for (int c = 0; c < 2; c++)
+                    if (keep[c]) {
+                        a[c] = b / d[c];
+                        s[c] = sin(M_PI * f[c]);
+                    }
+            }
+        }
+        nkept[0] += (unsigned)__popcll(__ballot(keep[0]));
+        nkept[1] += (unsigned)__popcll(__ballot(keep[1]));
+        unsigned long long todo = __ballot(a[0] != 0.0 || a[1] != 0.0);
+        while (todo) {  // (wave-uniform: one kept image per step, this lane's tap and channel of it)
+            const int j = __ffsll(todo) - 1;
+            todo &= todo - 1;
+            const long long k0L = __shfl(k0[0], j), k0R = __shfl(k0[1], j);
+            const double fL = __shfl(f[0], j), fR = __shfl(f[1], j), sL = __shfl(s[0], j), sR = __shfl(s[1], j);
+            const double aL = __shfl(a[0], j), aR = __shfl(a[1], j);
+            const long long kj = ch ? k0R : k0L;
+            const double fj = ch ? fR : fL, sj = ch ? sR : sL, aj = ch ? aR : aL;
+            if (aj != 0.0) {
+                double w;
+                if (fj == 0.0) {
+                    w = k == 0 ? 1.0 : 0.0;
+                } else {
+                    const double x = (double)k - fj;
+                    w = ((k & 1) ? sj : -sj) / (M_PI * x) * ((1.0 + cos(M_PI * x / 16.0)) / 2.0);
+                }
+                const long long v = llrint(aj * w * ROOM_Q), m = kj + k;
+                if (v != 0 && m >= 0 && (uint64_t)m < p.A) atomicAdd(&acc[2 * (uint64_t)m + ch], (unsigned long long)v);
+            }
+        }
+    }
+    if (lane == 0) {
+        if (nkept[0]) atomicAdd(&kept[0], nkept[0]);
+        if (nkept[1]) atomicAdd(&kept[1], nkept[1]);
+    }
+}
+
+// frame m < F with the room's term: irsynth.hip.h's three terms and acc 2^-40, added in that order in double, rounded once
+__device__ inline float2 room_frame(const SynPlan& p, uint64_t m, const long long* __restrict__ acc, uint64_t A) {
+    double2 v = syn_frame64(p, m);
+    if (m < A) {
+        v.x += (double)acc[2 * m] * (1.0 / ROOM_Q);
+        v.y += (double)acc[2 * m + 1] * (1.0 / ROOM_Q);
+    }
+    return make_float2((float)v.x, (float)v.y);
+}
+
+// k_synth with the room's term: the same walk and the same stores
+__global__ __launch_bounds__(SYN_THREADS) void k_synth_room(float2* __restrict__ x, SynPlan p, const long long* __restrict__ acc, uint64_t A) {
+    const uint64_t n = p.F;
+    const uint64_t head = ((uintptr_t)x & 8) && n ? 1 : 0, pairs = (n - head) / 2;
+    float4* __restrict__ x2 = reinterpret_cast<float4*>(x + head);
+    const uint64_t i = (uint64_t)blockIdx.x * SYN_THREADS + threadIdx.x;
+    if (i < pairs) {
+        const float2 a = room_frame(p, head + 2 * i, acc, A), b = room_frame(p, head + 2 * i + 1, acc, A);
+        x2[i] = make_float4(a.x, a.y, b.x, b.y);
+    }
+    if (i == 0) {
+        if (head) x[0] = room_frame(p, 0, acc, A);
+        if (head + 2 * pairs < n) x[n - 1] = room_frame(p, n - 1, acc, A);
+    }
+}
+
+// -- host ------------------------------------------------------------------------------------------------------------
+inline double room_min_size(const mc_ir_room& r) { return (double)std::min(r.size_m[0], std::min(r.size_m[1], r.size_m[2])); }
+
+// E of the definition
+inline uint64_t room_last(const mc_ir_room& r, uint64_t F) { return r.last ? std::min<uint64_t>(r.last, F) : F; }
+
+// the order `order` 0 stands for: the smallest N whose lattice holds every image that arrives before frame E (as a double:
+// it may lie far above MC_ROOM_MAX_ORDER)
+inline double room_auto_order(const mc_ir_room& r, uint32_t rate, uint64_t F) {
+    return std::ceil((double)room_last(r, F) * (double)r.speed / ((double)rate * 2.0 * room_min_size(r)));
+}
+
+// the receiver of channel c along axis ax
+inline double room_receiver(const mc_ir_room& r, int c, int ax) {
+    const double centre = (double)r.receiver_m[ax];
+    if ((uint32_t)ax != r.axis) return centre;
+    return c ? centre + (double)r.spacing_m / 2.0 : centre - (double)r.spacing_m / 2.0;
+}
+
+inline double room_direct(const mc_ir_room& r, int c) {
+    double sq = 0.0;
+    for (int ax = 0; ax < 3; ax++) {
+        const double p = (double)r.source_m[ax] - room_receiver(r, c, ax);
+        sq += p * p;
+    }
+    return std::sqrt(sq);
+}
+
+// Every field of a room, in the struct's order, then what follows from them and from the session's rate and F (a checked
+// synthesis's), without touching an engine or HIP; the message names the field.  Null when it is good.
+inline const char* room_check(const mc_ir_room* r, uint32_t rate, uint64_t F) {
+    static thread_local char msg[240];
+    if (!r) return "null room";
+    if (r->struct_size != sizeof(mc_ir_room)) return "mc_ir_room struct_size mismatch";
+    msg[0] = 0;
+    if (r->order > MC_ROOM_MAX_ORDER) {
+        std::snprintf(msg, sizeof(msg), "order %u above %d", r->order, MC_ROOM_MAX_ORDER);
+        return msg;
+    }
+    for (int ax = 0; ax < 3; ax++)
+        if (!(std::isfinite(r->size_m[ax]) && r->size_m[ax] >= 0.5f && r->size_m[ax] <= 200.f)) {
+            std::snprintf(msg, sizeof(msg), "size_m[%d] %g outside [0.5, 200]", ax, (double)r->size_m[ax]);
+            return msg;
+        }
+    for (int ax = 0; ax < 3; ax++)
+        if (!(r->source_m[ax] > 0.f && r->source_m[ax] < r->size_m[ax])) {
+            std::snprintf(msg, sizeof(msg), "source_m[%d] %g not strictly inside (0, %g)", ax, (double)r->source_m[ax], (double)r->size_m[ax]);
+            return msg;
+        }
+    for (int ax = 0; ax < 3; ax++)
+        if (!(r->receiver_m[ax] > 0.f && r->receiver_m[ax] < r->size_m[ax])) {
+            std::snprintf(msg, sizeof(msg), "receiver_m[%d] %g not strictly inside (0, %g)", ax, (double)r->receiver_m[ax], (double)r->size_m[ax]);
+            return msg;
+        }
+    for (int w = 0; w < 6; w++)
+        if (!(r->beta[w] >= -1.f && r->beta[w] <= 1.f)) {
+            std::snprintf(msg, sizeof(msg), "beta[%d] %g outside [-1, 1]", w, (double)r->beta[w]);
+            return msg;
+        }
+    if (!(std::isfinite(r->spacing_m) && r->spacing_m >= 0.f)) {
+        std::snprintf(msg, sizeof(msg), "spacing_m %g must be finite and >= 0", (double)r->spacing_m);
+        return msg;
+    }
+    if (r->axis > 2) {
+        std::snprintf(msg, sizeof(msg), "axis %u above 2", r->axis);
+        return msg;
+    }
+    if (!(room_receiver(*r, 0, (int)r->axis) > 0.0 && room_receiver(*r, 1, (int)r->axis) < (double)r->size_m[r->axis])) {
+        std::snprintf(msg, sizeof(msg), "spacing_m %g puts a receiver outside (0, %g) along axis %u", (double)r->spacing_m, (double)r->size_m[r->axis], r->axis);
+        return msg;
+    }
+    if (!(std::isfinite(r->speed) && r->speed >= 100.f && r->speed <= 2000.f)) {
+        std::snprintf(msg, sizeof(msg), "speed %g outside [100, 2000]", (double)r->speed);
+        return msg;
+    }
+    if (!(std::isfinite(r->gain) && r->gain > 0.f && r->gain <= 16.f)) {
+        std::snprintf(msg, sizeof(msg), "gain %g outside (0, 16]", (double)r->gain);
+        return msg;
+    }
+    if (r->reserved) {
+        std::snprintf(msg, sizeof(msg), "reserved %u must be 0", r->reserved);
+        return msg;
+    }
+    if (rate < 8000 || rate > 384000) {
+        std::snprintf(msg, sizeof(msg), "rate %u outside [8000, 384000]: the room needs the session's rate", rate);
+        return msg;
+    }
+    const double dmin = std::min(room_direct(*r, 0), room_direct(*r, 1));
+    if (!(dmin >= ROOM_MIN_DIRECT)) {
+        std::snprintf(msg, sizeof(msg), "source_m and receiver_m are %g m apart, below %g", dmin, ROOM_MIN_DIRECT);
+        return msg;
+    }
+    double N = (double)r->order;
+    if (!r->order) {
+        N = room_auto_order(*r, rate, F);
+        if (!(N <= (double)MC_ROOM_MAX_ORDER)) {
+            std::snprintf(msg, sizeof(msg), "order 0 needs order %.0f for %llu frames, above %d: set last or order", N,
+                          (unsigned long long)room_last(*r, F), MC_ROOM_MAX_ORDER);
+            return msg;
+        }
+    }
+    const double images = 8.0 * (2.0 * N + 1.0) * (2.0 * N + 1.0) * (2.0 * N + 1.0);
+    if (!(images * (double)r->gain / dmin < ROOM_MAX_SUM)) {
+        std::snprintf(msg, sizeof(msg), "gain %g: %.0f images of at most gain / %g m each may sum to 2^22 or more", (double)r->gain, images, dmin);
+        return msg;
+    }
+    return nullptr;
+}
+
+// a checked room as the kernels take it
+inline RoomPlan room_plan(const mc_ir_room& r, uint32_t rate, uint64_t F) {
+    RoomPlan p{};
+    p.N = r.order ? r.order : (uint32_t)room_auto_order(r, rate, F);
+    p.S = 2 * p.N + 1;
+    p.total = 8u * p.S * p.S * p.S;
+    p.F = F;
+    p.E = room_last(r, F);
+    p.A = std::min<uint64_t>(p.E + ROOM_REACH, F);
+    p.rate = (double)rate;
+    p.speed = (double)r.speed;
+    p.gain = (double)r.gain;
+    p.complete = (uint64_t)std::floor((double)(2 * p.N) * room_min_size(r) * p.rate / p.speed);
+    for (int ax = 0; ax < 3; ax++) {
+        p.size[ax] = (double)r.size_m[ax];
+        p.src[ax] = (double)r.source_m[ax];
+        for (int c = 0; c < 2; c++) p.rcv[c][ax] = room_receiver(r, c, ax);
+    }
+    for (int c = 0; c < 2; c++) p.tau[c] = room_direct(r, c) * p.rate / p.speed;
+    for (int w = 0; w < 6; w++)
+        for (int j = 0; j < MC_ROOM_MAX_ORDER + 2; j++) p.bpow[w][j] = std::pow((double)r.beta[w], (double)j);
+    return p;
+}
+
+// what mc_ir_room_plan reports of a checked room
+inline void room_report(const mc_ir_room& r, uint32_t rate, uint64_t F, double out[8]) {
+    const RoomPlan p = room_plan(r, rate, F);
+    const double Lx = p.size[0], Ly = p.size[1], Lz = p.size[2], V = Lx * Ly * Lz;
+    const double area[6] = {Ly * Lz, Ly * Lz, Lx * Lz, Lx * Lz, Lx * Ly, Lx * Ly};
+    double S = 0.0, A = 0.0;
+    for (int w = 0; w < 6; w++) {
+        S += area[w];
+        A += area[w] * (1.0 - (double)r.beta[w] * (double)r.beta[w]);
+    }
+    const double K = 24.0 * std::log(10.0) / p.speed;
+    out[0] = (double)p.N;
+    out[1] = (double)p.total;
+    out[2] = (double)p.complete;
+    out[3] = p.tau[0];
+    out[4] = p.tau[1];
+    out[5] = V;
+    out[6] = A > 0.0 ? K * V / A : 0.0;
+    out[7] = A > 0.0 ? K * V / (-S * std::log1p(-A / S)) : 0.0;  // (every wall fully absorbing: the logarithm is -inf and the time 0)
+}
+
+// The syn.F frames with the room's reflections into d_x (8-byte aligned), on `stream`, which is waited for: kept[c] = the
+// images of channel c that arrive before frame E.  The accumulator lives only inside this call.
+inline hipError_t room_generate(hipStream_t stream, const SynPlan& syn, const RoomPlan& room, float2* d_x, uint32_t kept[2]) {
+    unsigned long long* d_acc = nullptr;
+    const size_t acc_bytes = sizeof(unsigned long long) * 2 * room.A;
+    hipError_t er = hipMalloc(&d_acc, acc_bytes + 2 * sizeof(unsigned));
+    if (er != hipSuccess) return er;
+    unsigned* d_kept = reinterpret_cast<unsigned*>(d_acc + 2 * room.A);
+    er = hipMemsetAsync(d_acc, 0, acc_bytes + 2 * sizeof(unsigned), stream);
+    if (er == hipSuccess) {
+        const uint64_t waves = ((uint64_t)room.total + 63) / 64, per = ROOM_THREADS / 64;
+        const unsigned grid = (unsigned)std::min<uint64_t>((waves + per - 1) / per, ROOM_MAX_GRID);
+        hipLaunchKernelGGL(k_room, dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
+        er = hipGetLastError();
+    }
+    if (er == hipSuccess) {
+        const uint64_t pairs = syn.F / 2;
+        const unsigned grid = (unsigned)((std::max<uint64_t>(pairs, 1) + SYN_THREADS - 1) / SYN_THREADS);
+        hipLaunchKernelGGL(k_synth_room, dim3(grid), dim3(SYN_THREADS), 0, stream, d_x, syn, reinterpret_cast<const long long*>(d_acc), room.A);
+        er = hipGetLastError();
+    }
+    const hipError_t waited = hipStreamSynchronize(stream);  // (also after a failed launch: the memset may still be running)
+    if (er == hipSuccess) er = waited;
+    if (er == hipSuccess) er = hipMemcpy(kept, d_kept, 2 * sizeof(unsigned), hipMemcpyDeviceToHost);
+    (void)hipFree(d_acc);
+    return er;
+}

@@ -76,8 +76,8 @@ __host__ __device__ inline SynWords syn_words(const SynPlan& p, uint32_t i, uint
 
 __host__ __device__ inline double syn_u(uint32_t w) { return ((double)w + 0.5) * (1.0 / 4294967296.0); }
 
-// frame m < F
-__host__ __device__ inline float2 syn_frame(const SynPlan& p, uint64_t m) {
+// frame m < F before its rounding: late + direct + reflections in double (irroom.hip.h adds a fourth term before it rounds)
+__host__ __device__ inline double2 syn_frame64(const SynPlan& p, uint64_t m) {
     double L = 0.0, R = 0.0;
     if (m >= p.late_start) {
         const uint64_t t = m - p.late_start;
@@ -109,7 +109,13 @@ __host__ __device__ inline float2 syn_frame(const SynPlan& p, uint64_t m) {
                 L += p.gL[j];
                 R += p.gR[j];
             }
-    return make_float2((float)L, (float)R);
+    return make_double2(L, R);
+}
+
+// frame m < F
+__host__ __device__ inline float2 syn_frame(const SynPlan& p, uint64_t m) {
+    const double2 v = syn_frame64(p, m);
+    return make_float2((float)v.x, (float)v.y);
 }
 
 // x[0 .. F): two consecutive frames per thread as one 16-byte store.  x is 8-byte aligned; when it is not 16-byte aligned

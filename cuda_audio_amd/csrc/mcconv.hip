@@ -30,6 +30,7 @@
 #include "ireq.hip.h"
 #include "irdamp.hip.h"
 #include "irdecay.hip.h"
+#include "irroom.hip.h"
 #include "irsynth.hip.h"
 #include "irsweep.hip.h"
 #include "irfloor.hip.h"
@@ -112,6 +113,8 @@ struct IrEntry {
     double sweep_info[4] = {0, 0, 0, 0};
     bool tailed = false;  // the last load had a tail step on (mc_load_ir_tail, mc_load_ir_sweep_tail): tail_info is what mc_ir_tail_info reports
     double tail_info[4] = {0, 0, 0, 0};
+    bool roomed = false;  // the last load had a room (mc_synth_ir_room): room_info is what mc_ir_room_info reports
+    double room_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 }  // namespace
@@ -3319,20 +3322,28 @@ struct TailStep {
     bool extend;
 };
 
+// the room of a synthesised load as load_ir and shape_stage take it: the plan, and the images the device kept per channel
+struct RoomStep {
+    RoomPlan plan;
+    uint32_t kept[2];
+};
+
 // The shaped load's own stage (irshape.hip.h): all `conv` frames at the session's rate on the device, shaped into a new buffer
 // of *n <= cap taps that the caller owns.  Nothing of the engine's IRs is touched here.  syn = the device-side source beside
 // the host pointer (irsynth.hip.h): the conv frames are generated in place of a copy or a conversion; null = lr.  swp = the
 // source of mc_load_ir_sweep (irsweep.hip.h): the conv frames are deconvolved from its recording, which is uploaded to a
 // temporary buffer freed after the stage, as the weight table is.  tail = step 1a (irtail.hip.h; tail->F = conv): between the
-// source and the shaping the conv frames become tail->Fp frames in a buffer of their own
+// source and the shaping the conv frames become tail->Fp frames in a buffer of their own.  room = the reflections added to
+// syn's frames (irroom.hip.h); its kept counts are filled in
 int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, uint64_t cap, const uint32_t* rs, const mc_ir_shape& sh,
                 const IeqCascade* eq, const DampPlan* damp, float2** d_taps, uint64_t* n, double sums[4], double info[8],
-                const SynPlan* syn = nullptr, const SweepSource* swp = nullptr, const TailStep* tail = nullptr) {
+                const SynPlan* syn = nullptr, const SweepSource* swp = nullptr, const TailStep* tail = nullptr, RoomStep* room = nullptr) {
     float2 *d_x = nullptr, *d_rec = nullptr;
     double* d_u = nullptr;
     HIP_TRY(hipMalloc(&d_x, sizeof(float2) * conv));
     double unused[4];
     hipError_t er = swp  ? swp_generate(e->stream, *swp, d_x, &d_rec, &d_u)
+                    : syn && room ? room_generate(e->stream, *syn, room->plan, d_x, room->kept)
                     : syn ? syn_generate(e->stream, *syn, d_x)
                     : rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, d_x, conv, unused)
                          : hipMemcpy(d_x, lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
@@ -3368,10 +3379,11 @@ int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, u
 // which may have everything off, lr null, frames = its F and no rs): the frames are generated on the device; null = lr.
 // swp = the source of mc_load_ir_sweep (irsweep.hip.h; as syn, frames = its F): the frames are deconvolved on the device from
 // its recording.  tail = the tail step of mc_load_ir_tail and mc_load_ir_sweep_tail (irtail.hip.h; with a shape, which may have
-// everything off): step 1a, between the source and the shaping; null = none
+// everything off): step 1a, between the source and the shaping; null = none.  room = the room of mc_synth_ir_room
+// (irroom.hip.h; with syn): its reflections are added to the generated frames; null = none
 int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs, const mc_ir_shape* sh = nullptr,
             const IeqCascade* eq = nullptr, const DampPlan* damp = nullptr, const SynPlan* syn = nullptr,
-            const SweepSource* swp = nullptr, const TailStep* tail = nullptr) {
+            const SweepSource* swp = nullptr, const TailStep* tail = nullptr, RoomStep* room = nullptr) {
     // Convolution::prepare, conv.cu:207-253
     if (!e || (!lr && !syn && !swp)) return fail(MC_ERR_ARG, "null argument");
     if (idx >= (uint64_t)kMaxIrs) return fail(MC_ERR_ARG, "IR index %llu >= %d", (unsigned long long)idx, kMaxIrs);
@@ -3408,12 +3420,19 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
         const double inf[4] = {(double)tail->plan.touched, (double)tail->plan.F, (double)tail->plan.Fp, (double)tail->plan.first};
         std::copy(inf, inf + 4, ir.tail_info);
     };
+    const auto note_room = [&](IrEntry& ir) {  // what mc_ir_room_info reports of this load
+        ir.roomed = room != nullptr;
+        if (!room) return;
+        const RoomPlan& r = room->plan;
+        const double inf[8] = {(double)r.N, (double)room->kept[0], (double)room->kept[1], r.tau[0], r.tau[1], (double)r.E, (double)r.complete, 0.0};
+        std::copy(inf, inf + 8, ir.room_info);
+    };
     if (sh) {  // (the stream must be idle and out of the JACK path before the shaping kernels go onto it)
         int rc = e->sf ? MC_OK : drain_post(e);
         if (!rc && !e->sf) rc = leave_jack_path(e);
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(e->stream));
-        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, eq, damp, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo, syn, swp, tail);
+        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, eq, damp, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo, syn, swp, tail, room);
         if (rc) return rc;
     }
     if (e->sf) {
@@ -3426,6 +3445,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
         note_synth(e->irs[idx]);
         note_sweep(e->irs[idx]);
         note_tail(e->irs[idx]);
+        note_room(e->irs[idx]);
         return MC_OK;
     }
     const uint64_t n = sh ? nshaped : std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
@@ -3511,6 +3531,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
     note_synth(ir);
     note_sweep(ir);
     note_tail(ir);
+    note_room(ir);
     if ((int)idx + 1 > e->nirs) e->nirs = (int)idx + 1;
     e->spec_valid = e->dspec.valid = false;
     e->uniform_valid[0] = e->uniform_valid[1] = false;
@@ -3652,6 +3673,77 @@ int mc_synth_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_synth*
     if (on || damping) cs = ieq_cascade(*eq, rate);
     if (damping) pl = damp_plan(*damp, rate);
     return load_ir(e, idx, nullptr, synth->frames, nframes, nullptr, shape, on || damping ? &cs : nullptr, damping ? &pl : nullptr, &syn);
+}
+
+void mc_default_ir_room(mc_ir_room* r) {
+    if (!r) return;
+    std::memset(r, 0, sizeof(*r));
+    r->struct_size = (uint32_t)sizeof(*r);
+    r->size_m[0] = 5.f, r->size_m[1] = 4.f, r->size_m[2] = 3.f;
+    r->source_m[0] = 1.f, r->source_m[1] = 1.5f, r->source_m[2] = 1.2f;
+    r->receiver_m[0] = 3.5f, r->receiver_m[1] = 2.f, r->receiver_m[2] = 1.5f;
+    for (float& b : r->beta) b = 0.9f;
+    r->spacing_m = 0.2f;
+    r->speed = 343.f;
+    r->gain = 1.f;
+}
+
+int mc_synth_ir_room(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_synth* synth, const mc_ir_room* room, const mc_ir_shape* shape,
+                     const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail) {
+    const bool tailed = tail && tail->mode != MC_TAIL_OFF;
+    if (!room && !tailed) return mc_synth_ir(e, idx, nframes, synth, shape, eq, damp);
+    // synth, then the room, then the tail with F' after F, then damp, eq and shape as in mc_synth_ir, all before the engine and before any HIP call
+    if (const char* bad = syn_check(synth)) return fail(MC_ERR_ARG, "%s", bad);
+    const uint32_t rate = synth->rate;
+    const uint64_t F = synth->frames;
+    if (room)
+        if (const char* bad = room_check(room, rate, F)) return fail(MC_ERR_ARG, "%s", bad);
+    if (tailed) {
+        if (const char* bad = tail_check(tail, rate)) return fail(MC_ERR_ARG, "%s", bad);
+        if (rate < RS_MIN_RATE || rate > RS_MAX_RATE)
+            return fail(MC_ERR_ARG, "rate %u outside [%u, %u] (the tail step needs the session's rate)", rate, RS_MIN_RATE, RS_MAX_RATE);
+        if (const char* bad = tail_check_frames(tail, F)) return fail(MC_ERR_ARG, "%s", bad);
+    }
+    const bool damping = damp && damp->n_xovers;
+    if (damping)
+        if (const char* bad = damp_check(damp, rate, rate)) return fail(MC_ERR_ARG, "%s", bad);
+    mc_ir_eq noeq;
+    mc_default_ir_eq(&noeq);
+    if (!eq) eq = &noeq;
+    int on = 0;
+    if (const char* bad = ieq_check(eq, rate, rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
+    mc_ir_shape off;
+    mc_default_ir_shape(&off);
+    if (!shape) shape = &off;
+    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    const SynPlan syn = syn_plan(*synth);
+    IeqCascade cs;
+    cs.bands = 0;
+    DampPlan pl{};
+    if (on || damping) cs = ieq_cascade(*eq, rate);
+    if (damping) pl = damp_plan(*damp, rate);
+    TailStep step{};
+    if (tailed) step = TailStep{tail_plan(*tail, rate, F), tail->mode == MC_TAIL_EXTEND};
+    RoomStep rstep{};
+    if (room) rstep.plan = room_plan(*room, rate, F);
+    return load_ir(e, idx, nullptr, F, nframes, nullptr, shape, on || damping ? &cs : nullptr, damping ? &pl : nullptr, &syn, nullptr,
+                   tailed ? &step : nullptr, room ? &rstep : nullptr);
+}
+
+int mc_ir_room_info(const mc_engine* e, uint64_t idx, double out[8]) {
+    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
+    if (!e->irs[idx].roomed) return fail(MC_ERR_STATE, "IR %llu was not loaded with a room", (unsigned long long)idx);
+    for (int i = 0; i < 8; i++) out[i] = e->irs[idx].room_info[i];
+    return MC_OK;
+}
+
+int mc_ir_room_plan(const mc_ir_room* room, uint32_t rate, uint64_t frames, double out[8]) {
+    if (frames < 1 || frames > SYN_MAX_FRAMES)
+        return fail(MC_ERR_ARG, "frames %llu outside [1, %llu]", (unsigned long long)frames, (unsigned long long)SYN_MAX_FRAMES);
+    if (const char* bad = room_check(room, rate, frames)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!out) return fail(MC_ERR_ARG, "null out");
+    room_report(*room, rate, frames, out);
+    return MC_OK;
 }
 
 int mc_ir_synth_info(const mc_engine* e, uint64_t idx, double out[4]) {

@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McFloorQuery, McIrDamp, McIrEq, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McFloorQuery, McIrDamp, McIrEq, McIrRoom, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -290,6 +290,54 @@ class IrSynth:
 
 
 @dataclasses.dataclass
+class IrRoom:
+    """The rectangular room whose reflections prepare_synth(room=...) adds to a synthesised IR (mc_ir_room, include/mcconv.h;
+    Allen and Berkley's image-source method): `size` (Lx, Ly, Lz) in metres, the `source` and the centre of the `receiver`
+    pair inside it, and `beta`, the pressure reflection coefficient of the walls: one number for all six, or six for
+    x=0, x=Lx, y=0, y=Ly, z=0, z=Lz.  The two omnidirectional receivers (left, right) sit `spacing` metres apart along `axis`
+    (0, 1, 2 or "x", "y", "z").  `speed` is that of sound in m/s, `gain` the amplitude of an image 1 m away.  Images on the
+    lattice -order .. order per axis are rendered (0: as many as arrive before the end); those arriving at or after frame
+    `last` (0: the IR's length) are left out."""
+
+    size: tuple = (5.0, 4.0, 3.0)
+    source: tuple = (1.0, 1.5, 1.2)
+    receiver: tuple = (3.5, 2.0, 1.5)
+    beta: object = 0.9
+    spacing: float = 0.2
+    axis: object = 0
+    speed: float = 343.0
+    gain: float = 1.0
+    order: int = 0
+    last: int = 0
+
+    AXES = {"x": 0, "y": 1, "z": 2}
+
+    def to_c(self):
+        beta = tuple(self.beta) if isinstance(self.beta, (tuple, list)) else (self.beta,) * 6
+        if len(beta) != 6 or len(self.size) != 3 or len(self.source) != 3 or len(self.receiver) != 3:
+            raise ValueError("size, source and receiver take three numbers, beta one or six")
+        r = McIrRoom()
+        _lib.load().mc_default_ir_room(C.byref(r))
+        for k in range(3):
+            r.size_m[k], r.source_m[k], r.receiver_m[k] = float(self.size[k]), float(self.source[k]), float(self.receiver[k])
+        for k in range(6):
+            r.beta[k] = float(beta[k])
+        r.spacing_m, r.axis, r.speed, r.gain = float(self.spacing), int(self.AXES.get(self.axis, self.axis)), float(self.speed), float(self.gain)
+        r.order, r.last = int(self.order), int(self.last)
+        return r
+
+
+def room_plan(room, rate, frames):
+    """What a load of `frames` frames at `rate` would do with `room` (an IrRoom; mc_ir_room_plan, host arithmetic only): the
+    order used, the images in its lattice, the frames up to which the lattice is complete, the direct sound's delay per
+    channel (frames), the volume, and Sabine's and Eyring's reverberation times in seconds (0 when nothing absorbs), which
+    the method's own decay outlasts: measure the tail (ir_floor), do not compute it."""
+    out = (C.c_double * 8)()
+    check(_lib.load().mc_ir_room_plan(C.byref(room.to_c()), int(rate), int(frames), out))
+    return dict(order=int(out[0]), images=int(out[1]), complete=int(out[2]), direct=(out[3], out[4]), volume=out[5], sabine=out[6], eyring=out[7])
+
+
+@dataclasses.dataclass
 class Sweep:
     """The exponential sine sweep whose recording prepare_sweep deconvolves (mc_sweep, include/mcconv.h): `frames` frames
     from f1_hz at frame 0 to f2_hz at the last, of peak `amplitude` (0.5 is WavFile's full scale), faded in and out over
@@ -493,14 +541,22 @@ class Convolution:
         else:
             check(self._L.mc_load_ir(self._h, idx, _fp(lr), lr.shape[0], nframes))
 
-    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None):
+    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None, room=None, tail=None):
         """Generate the IR `synth` (an IrSynth) describes on the device and store it at idx (mc_synth_ir): the frames take the
         place of a WAV's at the session's rate, and shape, eq and damp apply to them as in prepare().  A synthesised IR counts
-        as shaped: ir_shape_info(idx)["frames"] is synth.frames.  The engine's sample_rate (which eq and damp need) is passed
-        unless synth.rate is set."""
+        as shaped: ir_shape_info(idx)["frames"] is synth.frames.  The engine's sample_rate (which eq, damp, room and tail
+        need) is passed unless synth.rate is set.
+        room (an IrRoom): the reflections of a rectangular room are added to the frames (mc_synth_ir_room); ir_room_info(idx)
+        then tells what was rendered.  tail (an IrTail whose mode is not "off"): the tail step on the generated frames, as
+        in prepare()."""
         s = synth.to_c()
         if not s.rate:
             s.rate = int(self.sample_rate or 0)
+        if room is not None or tail is not None:
+            check(self._L.mc_synth_ir_room(self._h, idx, nframes, C.byref(s), C.byref(room.to_c()) if room is not None else None,
+                                           C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
+                                           C.byref(damp.to_c()) if damp is not None else None, C.byref(tail.to_c()) if tail is not None else None))
+            return
         check(self._L.mc_synth_ir(self._h, idx, nframes, C.byref(s), C.byref(shape.to_c()) if shape is not None else None,
                                   C.byref(eq.to_c()) if eq is not None else None, C.byref(damp.to_c()) if damp is not None else None))
 
@@ -652,6 +708,14 @@ class Convolution:
         out = (C.c_double * 4)()
         check(self._L.mc_ir_synth_info(self._h, idx, out))
         return dict(frames=int(out[0]), reflections=int(out[1]), late_start=int(out[2]))
+
+    def ir_room_info(self, idx):
+        """What the room of IR idx's load rendered (mc_ir_room_info): the lattice order used, the images kept per channel
+        (counted on the device), the direct sound's delay per channel (frames), the frame E from which images were left out
+        and the frames up to which the lattice is complete.  McError (MC_ERR_STATE) for an IR whose last load had no room."""
+        out = (C.c_double * 8)()
+        check(self._L.mc_ir_room_info(self._h, idx, out))
+        return dict(order=int(out[0]), images=(int(out[1]), int(out[2])), direct=(out[3], out[4]), last=int(out[5]), complete=int(out[6]))
 
     def ir_sweep_info(self, idx):
         """What prepare_sweep deconvolved for IR idx (mc_ir_sweep_info): the sweep's frames N, the recording's M, the frames

@@ -56,6 +56,11 @@ int mc_load_ir_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint
 int mc_load_ir_sweep_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
                           const mc_ir_damp*, const mc_ir_tail*) __attribute__((weak));
 int mc_ir_tail_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+// ... and no room
+void mc_default_ir_room(mc_ir_room*) __attribute__((weak));
+int mc_synth_ir_room(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_room*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
+                     const mc_ir_tail*) __attribute__((weak));
+int mc_ir_room_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 }
 
 namespace {
@@ -166,9 +171,15 @@ uint64_t Convolution::dampFrames(double seconds, double rate) {
 
 // irRate = sessionRate = 0: the frames are loaded at the rate they have (never with a band of eq on, never with damping).
 // synth: the engine generates the frames (lr null; sessionRate = synth->rate).  sweep: lr is the recording of a sweep, `frames`
-// frames at sessionRate = sweep->sweep.rate, which the engine deconvolves
+// frames at sessionRate = sweep->sweep.rate, which the engine deconvolves.  room (with synth): its reflections are added to the
+// generated frames, and a tail applies to them
 void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
-                             const IrEq& eq, const IrDamp& damp, const mc_ir_synth* synth, const SweepLoad* sweep, const mc_ir_tail* tail) {
+                             const IrEq& eq, const IrDamp& damp, const mc_ir_synth* synth, const SweepLoad* sweep, const mc_ir_tail* tail,
+                             const mc_ir_room* room) {
+    if (room && (!mc_synth_ir_room || !mc_default_ir_room || !mc_ir_room_info)) {
+        Log::error("conv", "the engine has no room rendering (mc_synth_ir_room)");
+        std::exit(2);
+    }
     if (tail && (!mc_load_ir_tail || !mc_load_ir_sweep_tail || !mc_ir_tail_info)) {
         Log::error("conv", "the engine has no tail step (mc_load_ir_tail)");
         std::exit(2);
@@ -219,9 +230,18 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         d.origin = damp.origin;
     }
     if (synth) {  // (what the engine refuses of a generated IR is the index line's fault: a message and exit 2, no abort)
-        if (mc_synth_ir(_engine, idx, nframes, synth, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d) != MC_OK) {
+        const int rc = room ? mc_synth_ir_room(_engine, idx, nframes, synth, room, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
+                            : mc_synth_ir(_engine, idx, nframes, synth, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d);
+        if (rc != MC_OK) {
             Log::error("conv", "IR %zu cannot be synthesised: %s", idx, mc_last_error());
             std::exit(2);
+        }
+        if (room) {
+            double ri[8];
+            check(mc_ir_room_info(_engine, idx, ri), "mc_ir_room_info");
+            Log::info(name, "IR %zu room: order %d, %llu and %llu images before frame %llu, direct sound at %.2f and %.2f frames, complete up to frame %llu",
+                      idx, (int)ri[0], (unsigned long long)ri[1], (unsigned long long)ri[2], (unsigned long long)ri[5], ri[3], ri[4],
+                      (unsigned long long)ri[6]);
         }
         double si[4];
         check(mc_ir_synth_info(_engine, idx, si), "mc_ir_synth_info");
@@ -497,7 +517,7 @@ void Convolution::measureTail(const PendingIr& p) {
         Log::error("conv", "the engine has no tail step (mc_load_ir_tail)");
         std::exit(2);
     }
-    if (p.generated) {
+    if (p.generated && !p.roomed) {
         Log::info(name, "IR %zu tail: a generated IR has no floor, left as it is", p.idx);
         return;
     }
@@ -617,6 +637,132 @@ bool Convolution::parseSynth(const std::string& line, IrSynth& out, std::string&
     }
     out = y;
     return true;
+}
+
+mc_ir_room Convolution::roomFrames(const IrRoom& room, double rate) {
+    mc_ir_room r;
+    mc_default_ir_room(&r);
+    for (int a = 0; a < 3; a++) r.size_m[a] = room.size[a], r.source_m[a] = room.source[a], r.receiver_m[a] = room.receiver[a];
+    for (int w = 0; w < 6; w++) r.beta[w] = room.beta[w];
+    r.spacing_m = room.spacing;
+    r.axis = room.axis;
+    r.speed = room.speed;
+    r.gain = room.gain;
+    r.order = room.order;
+    r.last = (uint64_t)std::nearbyint(room.lastSeconds * rate);
+    return r;
+}
+
+bool Convolution::parseRoom(const std::string& line, IrRoom& out, std::string& why) {
+    static const char* form =
+        "room:LENGTH_S:LX,LY,LZ:SX,SY,SZ:RX,RY,RZ[:key=value,...] with keys beta (one value, or six separated by '/'), order, spacing, axis (x|y|z), "
+        "speed, gain, last, t60 and synth:'s keys";
+    std::vector<std::string> parts;
+    for (size_t at = 0;;) {
+        const size_t colon = line.find(':', at);
+        parts.push_back(line.substr(at, colon == std::string::npos ? colon : colon - at));
+        if (colon == std::string::npos) break;
+        at = colon + 1;
+    }
+    if (parts.size() < 5 || parts.size() > 6 || parts[0] != "room") {
+        why = std::string("a room is ") + form;
+        return false;
+    }
+    const auto number = [](const std::string& text, double& v) {
+        char* end = nullptr;
+        v = std::strtod(text.c_str(), &end);
+        return !text.empty() && end == text.c_str() + text.size() && std::isfinite(v);
+    };
+    // `count` numbers separated by `sep` that fill the whole text
+    const auto numbers = [&](const std::string& text, char sep, size_t count, float* v) {
+        size_t at = 0;
+        for (size_t k = 0; k < count; k++) {
+            const size_t end = k + 1 < count ? text.find(sep, at) : text.size();
+            double x;
+            if (end == std::string::npos || !number(text.substr(at, end - at), x)) return false;
+            v[k] = (float)x;
+            at = end + 1;
+        }
+        return true;
+    };
+    IrRoom room;
+    double length = 0.0;
+    if (!number(parts[1], length) || !(length > 0.0)) {
+        why = "LENGTH_S '" + parts[1] + "' is not a length in seconds, > 0";
+        return false;
+    }
+    const char* triple[3] = {"LX,LY,LZ", "SX,SY,SZ", "RX,RY,RZ"};
+    float* slot[3] = {room.size, room.source, room.receiver};
+    for (int k = 0; k < 3; k++)
+        if (!numbers(parts[2 + k], ',', 3, slot[k])) {
+            why = std::string(triple[k]) + " '" + parts[2 + k] + "' is not three numbers in metres";
+            return false;
+        }
+    const std::string list = parts.size() == 6 ? parts[5] : "";
+    if (parts.size() == 6 && list.empty()) {
+        why = std::string("nothing after the last colon: ") + form;
+        return false;
+    }
+    std::string t60 = "0", synthKeys = "late=0,direct=0";  // (the room supplies the direct sound; a later late= or direct= wins)
+    for (size_t at = 0; at < list.size() || (at && at == list.size());) {
+        const size_t comma = std::min(list.find(',', at), list.size());
+        const std::string item = list.substr(at, comma - at);
+        const size_t eq = item.find('=');
+        if (eq == std::string::npos) {
+            why = "'" + item + "' is not key=value";
+            return false;
+        }
+        const std::string key = item.substr(0, eq), text = item.substr(eq + 1);
+        double v = 0.0;
+        bool good = true;
+        if (key == "beta") {
+            good = numbers(text, '/', 6, room.beta);
+            if (!good && (good = number(text, v)))
+                for (float& b : room.beta) b = (float)v;
+        } else if (key == "order") {
+            good = number(text, v) && v >= 0.0 && v <= (double)MC_ROOM_MAX_ORDER && v == std::floor(v);
+            room.order = (uint32_t)v;
+        } else if (key == "axis") {
+            good = text == "x" || text == "y" || text == "z";
+            room.axis = good ? (uint32_t)(text[0] - 'x') : 0;
+        } else if (key == "spacing" || key == "speed" || key == "gain") {
+            good = number(text, v) && v >= 0.0;
+            (key == "spacing" ? room.spacing : key == "speed" ? room.speed : room.gain) = (float)v;
+        } else if (key == "last") {
+            good = number(text, v) && v >= 0.0;
+            room.lastSeconds = v;
+        } else if (key == "t60") {
+            good = number(text, v) && v >= 0.0;
+            t60 = text;
+        } else {
+            synthKeys += "," + item;  // (parseSynth names an unknown key)
+        }
+        if (!good) {
+            why = "'" + text + "' is no value for " + key;
+            return false;
+        }
+        at = comma + 1;
+        if (comma == list.size()) break;
+    }
+    if (!parseSynth("synth:" + parts[1] + ":" + t60 + ":" + synthKeys, room.late, why)) {
+        const size_t at = why.find("synth:LENGTH_S");
+        if (at != std::string::npos) why = why.substr(0, at) + form;
+        return false;
+    }
+    out = room;
+    return true;
+}
+
+void Convolution::prepareRoom(size_t idx, const IrRoom& room, size_t nframes) {
+    if (_group) {
+        Log::error("conv", "room rendering is not available with several devices (mc_synth_ir_room is single-engine)");
+        std::exit(2);
+    }
+    PendingIr p{idx, nframes, 0, {}, _irShape, _irEq, false, _irDamp, true, room.late, false, IrSweep()};  // (rendered by onStart(), once the client's rate is known)
+    p.roomed = true;
+    p.room = room;
+    _pendingIrs.push_back(std::move(p));
+    if (idx + 1 > _nirs) _nirs = idx + 1;
 }
 
 void Convolution::prepareSynth(size_t idx, const IrSynth& synth, size_t nframes) {
@@ -789,9 +935,19 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
         return;
     }
     if (p.generated) {
+        if (p.roomed && !mc_default_ir_room) {
+            Log::error("conv", "the engine has no room rendering (mc_synth_ir_room)");
+            std::exit(2);
+        }
         if (!mc_default_ir_synth) {
             Log::error("conv", "the engine has no IR synthesis (mc_synth_ir)");
             std::exit(2);
+        }
+        if (p.roomed) {
+            const mc_ir_synth s = synthFrames(p.room.late, (double)samplerate);
+            const mc_ir_room r = roomFrames(p.room, (double)samplerate);
+            loadShaped(p.idx, nullptr, s.frames, p.nframes, s.rate, s.rate, shape, p.eq, p.damp, &s, nullptr, _tailOn ? &_tailNow : nullptr, &r);
+            return;
         }
         const mc_ir_synth s = synthFrames(p.synth, (double)samplerate);
         loadShaped(p.idx, nullptr, s.frames, p.nframes, s.rate, s.rate, shape, p.eq, p.damp, &s);

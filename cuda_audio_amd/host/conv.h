@@ -172,6 +172,33 @@ public:
     // mc_ir_synth of an IrSynth at rate Hz
     static mc_ir_synth synthFrames(const IrSynth& synth, double rate);
 
+    // A rectangular room whose reflections the engine renders (mc_ir_room and mc_synth_ir_room of include/mcconv.h, the
+    // image-source method; no reference equivalent): metres, and seconds turned into frames at the client's sample rate by rint,
+    // so prepareRoom() keeps the numbers and onStart() renders.  `late` is an optional late field and reflections of IrSynth's
+    // under the room's (its length is the IR's; late and direct default to 0, because the room supplies the direct sound).
+    // What is not given is mc_default_ir_room's.  The shape, EQ, damping, reports and rt60 aim that are set apply as to a WAV,
+    // and so does the tail step: the floor is measured on the room alone, then the IR is rendered again with the tail, which
+    // lets a short rendering run out at its own slope.  One more log line per IR: order, images kept, the direct sound's delay.
+    // Single device only, as setIrShape.
+    struct IrRoom {
+        float size[3] = {5.0f, 4.0f, 3.0f}, source[3] = {1.0f, 1.5f, 1.2f}, receiver[3] = {3.5f, 2.0f, 1.5f};
+        float beta[6] = {0.9f, 0.9f, 0.9f, 0.9f, 0.9f, 0.9f};
+        float spacing = 0.2f;
+        uint32_t axis = 0;
+        float speed = 343.0f, gain = 1.0f;
+        uint32_t order = 0;
+        double lastSeconds = 0.0;
+        IrSynth late;
+        IrRoom() { late.late = 0.0f; }
+    };
+    void prepareRoom(size_t idx, const IrRoom& room, size_t nframes = 1024);
+    // A line of an IR index that starts with "room:" - room:LENGTH_S:LX,LY,LZ:SX,SY,SZ:RX,RY,RZ[:key=value,...], keys beta (one
+    // value, or six separated by '/'), order, spacing, axis (x|y|z), speed, gain, last (seconds), and for the late field t60 and
+    // parseSynth's keys - as an IrRoom.  False, with the reason in `why`, for a malformed line.
+    static bool parseRoom(const std::string& line, IrRoom& out, std::string& why);
+    // mc_ir_room of an IrRoom at rate Hz
+    static mc_ir_room roomFrames(const IrRoom& room, double rate);
+
     // An IR the engine deconvolves from the recording of an exponential sine sweep played through a room (mc_sweep and
     // mc_load_ir_sweep of include/mcconv.h; no reference equivalent): times in seconds, turned into frames at the client's
     // sample rate by rint, so prepareSweep() keeps the numbers and the recording and onStart() deconvolves.  The recording
@@ -217,7 +244,7 @@ public:
     // is loaded as it is, its floor is measured in the bands of setIrFloorXovers, and it is loaded again with every band cut at
     // its knee (Cut) or cross-faded there into decaying noise (Extend) ahead of its shape, EQ and damping.  An IR whose
     // broadband peak-to-noise ratio is under margin_db + span_db of the search (30 dB) is left as it is, with a log line that
-    // says so, and so is a generated one, which has no floor.  Seconds become frames at the client's rate by rint.  Loaded by
+    // says so, and so is a generated one without a room, which has no floor.  Seconds become frames at the client's rate by rint.  Loaded by
     // onStart(), single device only.
     struct IrTail {
         enum Mode { Off = 0, Cut = 1, Extend = 2 } mode = Off;
@@ -258,6 +285,8 @@ private:
         IrSynth synth;
         bool swept = false;  // prepareSweep: lr is the recording of `sweep`
         IrSweep sweep;
+        bool roomed = false;  // prepareRoom: generated, `room` with its late field in place of `synth`
+        IrRoom room = IrRoom();
     };
     struct SweepLoad {  // the arguments of mc_load_ir_sweep beside the recording
         mc_sweep sweep;
@@ -284,7 +313,7 @@ private:
     IrDamp _irDamp;
     void loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
                     const IrEq& eq = IrEq(), const IrDamp& damp = IrDamp(), const mc_ir_synth* synth = nullptr,
-                    const SweepLoad* sweep = nullptr, const mc_ir_tail* tail = nullptr);
+                    const SweepLoad* sweep = nullptr, const mc_ir_tail* tail = nullptr, const mc_ir_room* room = nullptr);
     void pushParams();
     void pullVsteps();
 };

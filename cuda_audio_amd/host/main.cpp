@@ -22,6 +22,10 @@
 // A line of an IR index that starts with "synth:" is an IR the engine generates instead of a WAV path,
 // synth:LENGTH_S:T60_S[:key=value,...] with keys seed, start, buildup, late, direct, early, efirst, elast, egain, width
 // (Convolution::parseSynth; times in seconds at the client's sample rate); the --ir-* options apply to it as to a WAV.
+// A line that starts with "room:" is a rectangular room whose reflections the engine renders (the image-source method),
+// room:LENGTH_S:LX,LY,LZ:SX,SY,SZ:RX,RY,RZ[:key=value,...] with keys beta (one value, or six separated by '/'), order, spacing,
+// axis (x|y|z), speed, gain, last (seconds), and t60 and synth:'s keys for a late field under it (Convolution::parseRoom; metres and
+// seconds); the --ir-* options apply to it as to a WAV, --ir-tail included: a short rendering runs out at its own measured slope.
 // A line that starts with "sweep:" is an IR the engine deconvolves from the recording of a sine sweep,
 // sweep:RECORDING.wav:LENGTH_S:F1:F2[:key=value,...] with keys amp, fadein, fadeout, offset, length (Convolution::parseSweep;
 // times in seconds, the recording at the client's sample rate); the --ir-* options apply to it as to a WAV.
@@ -257,6 +261,16 @@ int main(int argc, char** argv) {
                         return 2;
                     }
                     c->prepareSynth(j, synth);
+                    continue;
+                }
+                if (!path.compare(0, 5, "room:")) {  // a rendered room instead of a WAV path
+                    Convolution::IrRoom room;
+                    std::string why;
+                    if (!Convolution::parseRoom(path, room, why)) {
+                        std::cerr << "index line '" << path << "': " << why << std::endl;
+                        return 2;
+                    }
+                    c->prepareRoom(j, room);
                     continue;
                 }
                 if (!path.compare(0, 6, "sweep:")) {  // an IR deconvolved from a recorded sweep

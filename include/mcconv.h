@@ -558,6 +558,74 @@ int mc_load_ir_sweep_tail(mc_engine *e, uint64_t idx, const float *lr, uint64_t 
  * a tail on */
 int mc_ir_tail_info(const mc_engine *e, uint64_t idx, double out[4]);
 
+/* The reflections of a rectangular room (Allen and Berkley's image-source method), added on the device to the frames
+ * mc_ir_synth describes: the room itself - its size, where the source and the two receivers stand, how hard the walls are -
+ * in place of reflections at random positions.  No reference equivalent; single-engine, as shaping is.  It gives the early
+ * part of an IR; the tail step (mc_ir_floor, mc_ir_tail_from_floor, MC_TAIL_EXTEND) continues it at its own measured slope.
+ *
+ * Everything is computed in double from the float fields; rate = synth->rate, F = synth->frames, c = speed.
+ * Receivers.  r_L = receiver - spacing / 2 and r_R = receiver + spacing / 2 along `axis`, the other coordinates the centre's.
+ * Images.  For n = (n_x, n_y, n_z) in [-N, N]^3 and u in {0, 1}^3 the image lies at p_a = ((1 - 2 u_a) s_a + 2 n_a L_a) - r_a
+ *   relative to a receiver r; d = sqrt(p_x^2 + p_y^2 + p_z^2);
+ *   a = gain b_x b_y b_z / d, multiplied from the left, b_a = pow(beta_(a,0), |n_a - u_a|) pow(beta_(a,1), |n_a|), 0^0 = 1
+ *   (beta_(a,0) is the wall at 0 of axis a, beta_(a,1) the wall at L_a); an image with a = 0 adds nothing;
+ *   tau = d rate / c frames.  Each receiver (L, R) has its own p, d, a and tau.
+ * Fractional delay.  k0 = floor(tau), f = tau - k0, s = sin(pi f).  For k = -15 .. 16, with x = k - f:
+ *   w_k = (f == 0 ? (k == 0 ? 1 : 0) : (k odd ? s : -s) / (pi x)) (1 + cos(pi x / 16)) / 2, a Hann-windowed sinc over 16 zero
+ *   crossings each side at the cost of one sine per image and channel.  An image whose delay is a whole number of frames is
+ *   exactly one tap.
+ * Which images sound.  E = last ? min(last, F) : F.  Channel c of an image is kept iff k0 < E; its tap k goes to frame
+ *   m = k0 + k when 0 <= m < F, other taps are dropped.
+ * Sum.  Each contribution is q = llrint(a w_k 2^40) (to nearest, ties to even), added into a 64-bit integer per frame and
+ *   channel: integer sums do not depend on the order of arrival, so the same struct gives the same bits whatever the grid and
+ *   however many images share a frame.  8 (2N + 1)^3 gain / min(d_direct,L, d_direct,R) must stay below 2^22, which excludes
+ *   overflow: every image is farther away than the direct path, |beta| <= 1 and |w| <= 1.
+ * Frame.  (float)(late + direct + reflections + acc 2^-40), added in that order in double and rounded once; the first three
+ *   terms are mc_ir_synth's.
+ * Order 0.  N = ceil(E c / (rate 2 min(L))), refused above MC_ROOM_MAX_ORDER.  Every image with d < 2 N min(L) lies inside the
+ *   lattice, because |p_a| >= 2 (|n_a| - 1) L_a: the lattice holds every image that arrives before frame E. */
+#define MC_ROOM_MAX_ORDER 32
+typedef struct {
+    uint32_t struct_size;    /* sizeof(mc_ir_room) = 96 */
+    uint32_t order;          /* N: lattice indices -N .. N per axis, at most MC_ROOM_MAX_ORDER; 0 = the smallest N whose lattice
+                                is complete up to E */
+    float size_m[3];         /* Lx, Ly, Lz: finite, [0.5, 200] */
+    float source_m[3];       /* strictly inside the room */
+    float receiver_m[3];     /* centre of the receiver pair, strictly inside the room */
+    float beta[6];           /* pressure reflection coefficients of the walls x=0, x=Lx, y=0, y=Ly, z=0, z=Lz: [-1, 1] */
+    float spacing_m;         /* finite, >= 0: the two omnidirectional receivers sit at receiver -/+ spacing / 2 along `axis`
+                                (L, R), both strictly inside the room */
+    uint32_t axis;           /* 0, 1, 2 */
+    float speed;             /* c, m/s: finite, [100, 2000] */
+    float gain;              /* amplitude of an image 1 m away: finite, (0, 16] */
+    uint32_t reserved;       /* must be 0 */
+    uint64_t last;           /* E = last ? min(last, F) : F: images arriving at or after frame E are left out */
+} mc_ir_room;
+/* 5 x 4 x 3 m, source (1, 1.5, 1.2), receiver (3.5, 2, 1.5), every beta 0.9, spacing 0.2, axis 0, speed 343, gain 1, order 0,
+ * last 0 */
+void mc_default_ir_room(mc_ir_room *r);
+/* mc_synth_ir with the room's reflections added to the generated frames and `tail` applied to them as step 1a.  With room
+ * NULL and tail NULL or MC_TAIL_OFF the call is mc_synth_ir itself, bit for bit; tail may be used without room.  Checked in
+ * this order, all before the engine or the device is touched (MC_ERR_ARG, the message names the field, the engine stays as it
+ * was): synth as by mc_synth_ir; room, field by field in the struct's order (the spacing is refused when it puts a receiver
+ * outside the room), then synth->rate, which must be set ("the room needs the session's rate"), the two direct distances
+ * (>= 0.1 m), the automatic order and the bound on the sum; tail as by mc_load_ir_tail, with F' after F; damp, eq and shape,
+ * then e, idx and nframes as by mc_synth_ir. */
+int mc_synth_ir_room(mc_engine *e, uint64_t idx, uint64_t nframes, const mc_ir_synth *synth, const mc_ir_room *room,
+                     const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp, const mc_ir_tail *tail);
+/* out = {N used, images kept L, images kept R (counted on the device), tau of the direct sound L, R (frames, fractional), E,
+ * frames up to which the lattice is complete = floor(2 N min(L) rate / c), 0}; MC_ERR_STATE unless the IR's last load had a
+ * room */
+int mc_ir_room_info(const mc_engine *e, uint64_t idx, double out[8]);
+/* What a load of `frames` frames at `rate` would do with `room`: out = {N that would be used, images in the lattice
+ * 8 (2N + 1)^3, frames up to which it is complete, tau of the direct sound L, R, the volume (m^3), Sabine's and Eyring's
+ * reverberation times (s)}.  The times come from the mean of 1 - beta^2 over the wall areas S: T = (24 ln 10 / c) V / (S abar)
+ * and (24 ln 10 / c) V / (-S ln(1 - abar)); both are 0 when nothing absorbs.  They are estimates to compare against: the
+ * method's own decay is slower than either, which is why a tail is measured (mc_ir_floor) and not computed.  The room is
+ * checked as by mc_synth_ir_room, with rate in [8000, 384000] and frames in [1, 2^24].  Host arithmetic only: no engine and no
+ * HIP call. */
+int mc_ir_room_plan(const mc_ir_room *room, uint32_t rate, uint64_t frames, double out[8]);
+
 int mc_num_irs(const mc_engine *e);
 /* out[0..3] = sum h_L, sum h_R, sum h_L(-1)^m, sum h_R(-1)^m of the truncated IR; out[4] = taps, out[5] = partitions */
 int mc_ir_info(const mc_engine *e, uint64_t idx, double out[6]);

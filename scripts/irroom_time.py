@@ -1,0 +1,43 @@
+"""Time of one synthesised load with the reflections of a room (mc_synth_ir_room) at the largest lattice, order 32 (2.2 M
+images), F = 2^20 frames, 48 kHz, next to the same load without the room (k_synth, the shaping stage, the transforms): the
+difference is the accumulator's zeroing, k_room and k_synth_room's reads.  The engine runs on torch's current stream and HIP
+events on that stream bracket each load (the load itself ends in a stream synchronise); the host clock is printed beside them.
+Warm engine: one load of each kind that allocates, then REPS timed ones, alternating.  Prints one JSON line.  For k_room's own
+time run this under `rocprofv3 --kernel-trace --stats`, in a run of its own.  LAST=frames leaves out images from that frame on."""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from cuda_audio_amd.engine import Convolution, IrRoom, IrSynth  # noqa: E402
+
+REPS = int(os.environ.get("REPS", "5"))
+F, RATE = 1 << 20, 48000
+room = IrRoom(order=32, last=int(os.environ.get("LAST", "0")))
+synth = IrSynth(frames=F, late_gain=0.0)
+c = Convolution("room", 2 * F, max_batch=8, device=0, sample_rate=RATE)
+c.use_torch_stream()
+kinds = dict(plain=lambda: c.prepare_synth(0, synth), room=lambda: c.prepare_synth(0, synth, room=room))
+for call in kinds.values():  # (first calls allocate)
+    call()
+ev_ms, host_ms = {k: [] for k in kinds}, {k: [] for k in kinds}
+for _ in range(REPS):
+    for k, call in kinds.items():
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        a.record()
+        call()
+        b.record()
+        b.synchronize()
+        host_ms[k].append((time.perf_counter() - t0) * 1e3)
+        ev_ms[k].append(a.elapsed_time(b))
+info = c.ir_room_info(0)
+c.close()
+res = {k: dict(event_median_ms=round(float(np.median(ev_ms[k])), 3), event_min_ms=round(float(np.min(ev_ms[k])), 3),
+               host_median_ms=round(float(np.median(host_ms[k])), 3)) for k in kinds}
+print(json.dumps(dict(frames=F, order=info["order"], images_kept=info["images"], last=info["last"], reps=REPS,
+                      room_less_plain_ms=round(res["room"]["event_median_ms"] - res["plain"]["event_median_ms"], 3), **res)), flush=True)
