@@ -9,12 +9,12 @@
 // sequential float64 loops.
 //
 // EQ's pass filters in place and in cascade; here the X crossovers run in parallel from the same input, so a lane carries all
-// of them at once and x is read once, whatever X is.  Chunking, workgroup shape and LDS staging are ireq.hip.h's (a lane per
-// (chunk, channel), IEQ_TILE taps of each of 64 chunks in padded rows, the next tile's loads in flight under the arithmetic).
+// of them at once and x is read once, whatever X is.  Chunking, workgroup shape and LDS staging are chunkwalk.hip.h's chunk_walk
+// (a lane per (chunk, channel)), as for ireq.hip.h.
 // A crossover's state is four doubles, (s1, s2) of the first section and (s3, s4) of the second; over a run of taps it is
 // affine in the state before it, s' = A^len s + e, with A the 4 x 4 matrix of the cascade's updates at x = 0.
 //   local  k_damp_chunk<false> runs the X crossovers over every chunk from rest and keeps the X end states e_c;
-//   carry  k_damp_carry, one workgroup per crossover, is k_eq_carry's three-step scan over 4-vectors;
+//   carry  k_damp_carry, one workgroup per crossover, is ireq.hip.h's carry_scan over 4-vectors;
 //   fix-up k_damp_chunk<true> runs every chunk again from its true states and writes y in place.  The envelopes are evaluated
 //          per tap from the tap's own index, not as a running product: a tap's value does not depend on where its chunk starts.
 // Two launches of the chunk kernel and one of the carry for any X.  The state scratch is double2 [2 X] per lane, allocated
@@ -82,46 +82,23 @@ __device__ inline void damp_store(double2* __restrict__ st, uint64_t at, const D
 // not written.  pl.origin <= n.
 template <bool FIX>
 __global__ __launch_bounds__(IEQ_THREADS) void k_damp_chunk(double2* __restrict__ buf, uint64_t n, DampPlan pl, double2* __restrict__ st) {
-    __shared__ double2 tile[IEQ_WG_CHUNKS * IEQ_ROW];
-    const int t = threadIdx.x, c = t >> 1, ch = t & 1;
-    const uint64_t base = (uint64_t)blockIdx.x * IEQ_SPAN;
-    const uint64_t lanes = (uint64_t)gridDim.x * IEQ_THREADS, entry = (uint64_t)blockIdx.x * IEQ_THREADS + t;
+    const uint64_t lanes = (uint64_t)gridDim.x * IEQ_THREADS, entry = (uint64_t)blockIdx.x * IEQ_THREADS + threadIdx.x;
     DampState s[MC_DAMP_MAX_XOVERS];
 #pragma unroll
     for (int k = 0; k < MC_DAMP_MAX_XOVERS; k++) {
         s[k] = DampState{0.0, 0.0, 0.0, 0.0};
         if (FIX && k < pl.X) s[k] = damp_load(st, (uint64_t)k * lanes + entry);
     }
-    // element j of the lane's share of a tile: chunk i / IEQ_TILE, tap i % IEQ_TILE of it, i = t + j IEQ_THREADS
-    double2 pre[IEQ_PER];
-    const auto fetch = [&](int ph) {
-#pragma unroll
-        for (int j = 0; j < IEQ_PER; j++) {
-            const int i = t + j * IEQ_THREADS;
-            const uint64_t g = base + (uint64_t)(i / IEQ_TILE) * IEQ_CHUNK + ph * IEQ_TILE + i % IEQ_TILE;
-            pre[j] = g < n ? buf[g] : make_double2(0.0, 0.0);
-        }
-    };
-    fetch(0);
-    for (int ph = 0; ph < IEQ_CHUNK / IEQ_TILE; ph++) {
-#pragma unroll
-        for (int j = 0; j < IEQ_PER; j++) {
-            const int i = t + j * IEQ_THREADS;
-            tile[(i / IEQ_TILE) * IEQ_ROW + i % IEQ_TILE] = pre[j];
-        }
-        __syncthreads();
-        if (ph + 1 < IEQ_CHUNK / IEQ_TILE) fetch(ph + 1);
-        double* row = reinterpret_cast<double*>(tile + c * IEQ_ROW) + ch;
-        const uint64_t m0 = base + (uint64_t)c * IEQ_CHUNK + ph * IEQ_TILE;
-#pragma unroll
-        for (int k = 0; k < IEQ_TILE; k++) {
-            const double v = row[2 * k];
+    chunk_walk<false, IEQ_TILE, double2>(
+        FIX, [&](uint64_t g, double2& v) { v = g < n ? buf[g] : make_double2(0.0, 0.0); },
+        [&](double& tap, uint64_t m) {
+            const double v = tap;
             double P[MC_DAMP_MAX_XOVERS];
 #pragma unroll
             for (int x = 0; x < MC_DAMP_MAX_XOVERS; x++)
                 if (x < pl.X) P[x] = damp_step(pl.c[x], s[x], v);
             if (FIX) {
-                const uint64_t m = m0 + k, tt = (m > pl.origin ? m : pl.origin) - pl.origin;
+                const uint64_t tt = (m > pl.origin ? m : pl.origin) - pl.origin;
                 // y = g_X x + (g_0 - g_1) P_1 + .. + (g_(X-1) - g_X) P_X, added in that order: the weights first, low to high
                 double g = damp_env(pl.t60[0], tt), w[MC_DAMP_MAX_XOVERS];
 #pragma unroll
@@ -135,20 +112,12 @@ __global__ __launch_bounds__(IEQ_THREADS) void k_damp_chunk(double2* __restrict_
 #pragma unroll
                 for (int x = 0; x < MC_DAMP_MAX_XOVERS; x++)
                     if (x < pl.X) y += w[x] * P[x];
-                row[2 * k] = y;
+                tap = y;
             }
-        }
-        __syncthreads();
-        if (FIX) {
-#pragma unroll
-            for (int j = 0; j < IEQ_PER; j++) {
-                const int i = t + j * IEQ_THREADS;
-                const uint64_t g = base + (uint64_t)(i / IEQ_TILE) * IEQ_CHUNK + ph * IEQ_TILE + i % IEQ_TILE;
-                if (g < n) buf[g] = tile[(i / IEQ_TILE) * IEQ_ROW + i % IEQ_TILE];
-            }
-            __syncthreads();
-        }
-    }
+        },
+        [&](uint64_t g, double2 v) {
+            if (g < n) buf[g] = v;
+        });
     if (!FIX) {
 #pragma unroll
         for (int k = 0; k < MC_DAMP_MAX_XOVERS; k++)
@@ -156,38 +125,17 @@ __global__ __launch_bounds__(IEQ_THREADS) void k_damp_chunk(double2* __restrict_
     }
 }
 
-// Workgroup k (one per crossover) over its slice of st, entry 2 c + ch, c < nchunks: in, the state chunk c leaves when it starts
-// at rest; out, the state it starts with.  2 IEQ_RUNS lanes; lane (run, ch) owns chunks [run K, (run + 1) K).  M = A^IEQ_CHUNK,
-// MK = M^K (k_eq_carry's scan, with 4-vectors).
+// Workgroup k (one per crossover): ireq.hip.h's carry_scan over its slice of st, entry 2 c + ch, c < nchunks, with 4-vectors.
+// M = A^IEQ_CHUNK, MK = M^K.
 __global__ __launch_bounds__(2 * IEQ_RUNS) void k_damp_carry(double2* __restrict__ st, uint64_t lanes, uint32_t nchunks, uint32_t K, DampCarry cm) {
-    __shared__ DampState ends[2 * IEQ_RUNS];
-    const int t = threadIdx.x, ch = t & 1;
     const DampMat &M = cm.M[blockIdx.x], &MK = cm.MK[blockIdx.x];
     double2* my = st + 2 * (uint64_t)blockIdx.x * lanes;
-    const uint64_t r0 = (uint64_t)(t >> 1) * K, c0 = r0 < nchunks ? r0 : nchunks, c1 = c0 + K < nchunks ? c0 + K : nchunks;
-    const auto step = [](const DampMat& A, const DampState& s, const DampState& e) {
-        const DampState r = damp_mul(A, s);
-        return DampState{r.s1 + e.s1, r.s2 + e.s2, r.s3 + e.s3, r.s4 + e.s4};
-    };
-    DampState s{0.0, 0.0, 0.0, 0.0};
-    for (uint64_t c = c0; c < c1; c++) s = step(M, s, damp_load(my, 2 * c + ch));
-    ends[t] = s;
-    __syncthreads();
-    if (t < 2) {  // (a run that is short or empty is the last or lies behind the last: what follows it is not used)
-        DampState S{0.0, 0.0, 0.0, 0.0};
-        for (int g = 0; g < IEQ_RUNS; g++) {
-            const DampState e = ends[2 * g + t];
-            ends[2 * g + t] = S;
-            S = step(MK, S, e);
-        }
-    }
-    __syncthreads();
-    s = ends[t];
-    for (uint64_t c = c0; c < c1; c++) {
-        const DampState e = damp_load(my, 2 * c + ch);
-        damp_store(my, 2 * c + ch, s);
-        s = step(M, s, e);
-    }
+    carry_scan<DampState>(
+        nchunks, K, [&](uint64_t i) { return damp_load(my, i); }, [&](uint64_t i, const DampState& s) { damp_store(my, i, s); },
+        [&](bool runs, const DampState& s, const DampState& e) {
+            const DampState r = damp_mul(runs ? MK : M, s);
+            return DampState{r.s1 + e.s1, r.s2 + e.s2, r.s3 + e.s3, r.s4 + e.s4};
+        });
 }
 
 // -- host ------------------------------------------------------------------------------------------------------------
@@ -298,31 +246,35 @@ inline DampMat damp_round(const DampMatL& a) {
     return r;
 }
 
+// The carry pass's matrices for the X crossovers c, runs of K chunks
+inline DampCarry damp_carry(const IeqCoef* c, int X, uint32_t K) {
+    DampCarry cm{};
+    for (int k = 0; k < X; k++) {
+        const DampMatL M = damp_matpow(damp_widen(damp_matrix(c[k])), IEQ_CHUNK);
+        cm.M[k] = damp_round(M);
+        cm.MK[k] = damp_round(damp_matpow(M, K));
+    }
+    return cm;
+}
+
 // Step 6a over d_buf [n] in place, on the stream, after what the stream already holds.  Allocates the state scratch, waits for
 // the kernels and frees it.
 inline hipError_t damp_run(hipStream_t stream, double2* d_buf, uint64_t n, const DampPlan& plan) {
     DampPlan pl = plan;
     pl.origin = std::min<uint64_t>(pl.origin, n);
-    const unsigned cgrid = (unsigned)((n + IEQ_SPAN - 1) / IEQ_SPAN);
-    const uint64_t lanes = (uint64_t)cgrid * IEQ_THREADS;
-    const uint32_t nchunks = (uint32_t)((n + IEQ_CHUNK - 1) / IEQ_CHUNK), K = (nchunks + IEQ_RUNS - 1) / IEQ_RUNS;
-    DampCarry cm{};
-    for (int k = 0; k < pl.X; k++) {
-        const DampMatL M = damp_matpow(damp_widen(damp_matrix(pl.c[k])), IEQ_CHUNK);
-        cm.M[k] = damp_round(M);
-        cm.MK[k] = damp_round(damp_matpow(M, K));
-    }
+    const ChunkGeom cg = chunk_geom(n);
+    const DampCarry cm = damp_carry(pl.c, pl.X, cg.K);
     double2* d_st = nullptr;
-    hipError_t er = hipMalloc(&d_st, sizeof(double2) * 2 * (size_t)pl.X * lanes);
+    hipError_t er = hipMalloc(&d_st, sizeof(double2) * 2 * (size_t)pl.X * cg.lanes);
     if (er != hipSuccess) return er;
-    hipLaunchKernelGGL(k_damp_chunk<false>, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, n, pl, d_st);
+    hipLaunchKernelGGL(k_damp_chunk<false>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, n, pl, d_st);
     er = hipGetLastError();
     if (er == hipSuccess) {
-        hipLaunchKernelGGL(k_damp_carry, dim3(pl.X), dim3(2 * IEQ_RUNS), 0, stream, d_st, lanes, nchunks, K, cm);
+        hipLaunchKernelGGL(k_damp_carry, dim3(pl.X), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.lanes, cg.nchunks, cg.K, cm);
         er = hipGetLastError();
     }
     if (er == hipSuccess) {
-        hipLaunchKernelGGL(k_damp_chunk<true>, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, n, pl, d_st);
+        hipLaunchKernelGGL(k_damp_chunk<true>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, n, pl, d_st);
         er = hipGetLastError();
     }
     const hipError_t sy = hipStreamSynchronize(stream);

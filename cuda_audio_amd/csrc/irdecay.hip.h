@@ -27,10 +27,8 @@
 // carry of the chunk before: across a run of zero taps (a quiet lead, a band's output before the first sample) EDC stays
 // bit for bit level, chunk borders included, as a sequential sum does.  L[o] = 10 log10(EDC[o] / EDC[o]) is 0 exactly.
 //
-// Memory.  As in ireq.hip.h a workgroup (128 lanes: 64 chunks x 2 channels) stages IEQ_TILE taps of each of its chunks
-// through LDS, 16 consecutive lanes moving one chunk's 256 contiguous bytes, the next tile's loads in flight under the current
-// tile's additions; rows are padded to IEQ_ROW so that the lanes' own reads do not conflict.  The map kernels read buf one
-// double2 per lane, consecutively.
+// Memory.  k_dec_sum is chunkwalk.hip.h's chunk_walk, backward: its head says how the taps reach the lanes.  The map kernels read
+// buf one double2 per lane, consecutively.
 //
 // Determinism.  Chunks, grids and the carry's order depend on N alone; no atomics; every reduction ends in one partial per
 // workgroup, combined on the host in index order.  The same query on the same taps gives the same bits.
@@ -67,56 +65,24 @@ __global__ __launch_bounds__(ISH_THREADS) void k_dec_fill(const float2* __restri
     buf[m] = make_double2((double)v.x, (double)v.y);
 }
 
-// One backward walk over buf [n] (the file's head), k_eq_chunk's workgroup and staging.  tot: double [gridDim.x * IEQ_THREADS],
+// One backward walk over buf [n] (the file's head).  tot: double [gridDim.x * IEQ_THREADS],
 // entry 2 * chunk + channel.  WRITE = false: tot = the sum of y^2 over the chunk's taps in [o, n).  WRITE = true: tap m of buf
 // becomes tot + the sum of y^2 over the chunk's taps in [max(m, o), n).  Taps at and past n read as zero and are not written.
 template <bool WRITE>
 __global__ __launch_bounds__(IEQ_THREADS) void k_dec_sum(double2* __restrict__ buf, uint64_t o, uint64_t n, double* __restrict__ tot) {
-    __shared__ double2 tile[IEQ_WG_CHUNKS * IEQ_ROW];
-    constexpr int PHASES = IEQ_CHUNK / IEQ_TILE;
-    const int t = threadIdx.x, c = t >> 1, ch = t & 1;
-    const uint64_t base = (uint64_t)blockIdx.x * IEQ_SPAN;
-    const uint64_t entry = (uint64_t)blockIdx.x * IEQ_THREADS + t;
-    const uint64_t mine = base + (uint64_t)c * IEQ_CHUNK;  // the lane's chunk starts here
+    const uint64_t entry = (uint64_t)blockIdx.x * IEQ_THREADS + threadIdx.x;
     const double carry = WRITE ? tot[entry] : 0.0;
     double s = 0.0;
-    // element j of the lane's share of a tile: chunk i / IEQ_TILE, tap i % IEQ_TILE of it, i = t + j IEQ_THREADS
-    double2 pre[IEQ_PER];
-    const auto fetch = [&](int ph) {
-#pragma unroll
-        for (int j = 0; j < IEQ_PER; j++) {
-            const int i = t + j * IEQ_THREADS;
-            const uint64_t g = base + (uint64_t)(i / IEQ_TILE) * IEQ_CHUNK + ph * IEQ_TILE + i % IEQ_TILE;
-            pre[j] = g < n ? buf[g] : make_double2(0.0, 0.0);
-        }
-    };
-    fetch(PHASES - 1);
-    for (int ph = PHASES - 1; ph >= 0; ph--) {
-#pragma unroll
-        for (int j = 0; j < IEQ_PER; j++) {
-            const int i = t + j * IEQ_THREADS;
-            tile[(i / IEQ_TILE) * IEQ_ROW + i % IEQ_TILE] = pre[j];
-        }
-        __syncthreads();
-        if (ph > 0) fetch(ph - 1);
-        double* row = reinterpret_cast<double*>(tile + c * IEQ_ROW) + ch;
-#pragma unroll
-        for (int k = IEQ_TILE - 1; k >= 0; k--) {
-            const double v = row[2 * k];
-            if (mine + (uint64_t)(ph * IEQ_TILE + k) >= o) s += v * v;
-            if (WRITE) row[2 * k] = carry + s;
-        }
-        __syncthreads();
-        if (WRITE) {
-#pragma unroll
-            for (int j = 0; j < IEQ_PER; j++) {
-                const int i = t + j * IEQ_THREADS;
-                const uint64_t g = base + (uint64_t)(i / IEQ_TILE) * IEQ_CHUNK + ph * IEQ_TILE + i % IEQ_TILE;
-                if (g < n) buf[g] = tile[(i / IEQ_TILE) * IEQ_ROW + i % IEQ_TILE];
-            }
-            __syncthreads();
-        }
-    }
+    chunk_walk<true, IEQ_TILE, double2>(
+        WRITE, [&](uint64_t g, double2& v) { v = g < n ? buf[g] : make_double2(0.0, 0.0); },
+        [&](double& tap, uint64_t m) {
+            const double v = tap;
+            if (m >= o) s += v * v;
+            if (WRITE) tap = carry + s;
+        },
+        [&](uint64_t g, double2 v) {
+            if (g < n) buf[g] = v;
+        });
     if (!WRITE) tot[entry] = s;
 }
 
@@ -302,8 +268,7 @@ inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n,
     const uint64_t N = q.end ? std::min<uint64_t>(q.end, n) : n;
     const uint32_t K = q.curve_points, npick = DEC_PICK_HEAD + K;
     const unsigned grid = (unsigned)((N + ISH_THREADS - 1) / ISH_THREADS);                    // k_dec_fill
-    const unsigned cgrid = (unsigned)((N + IEQ_SPAN - 1) / IEQ_SPAN);                         // k_eq_chunk, k_dec_sum
-    const uint32_t nchunks = (uint32_t)((N + IEQ_CHUNK - 1) / IEQ_CHUNK), runK = (nchunks + IEQ_RUNS - 1) / IEQ_RUNS;
+    const ChunkGeom cg = chunk_geom(N);                                                       // k_eq_chunk, k_dec_sum and the carries
     const unsigned rgrid = std::min<unsigned>(DEC_GRID, grid);                                // k_dec_members, k_dec_fit
     const unsigned ogrid = (unsigned)std::min<uint64_t>(ISH_SCAN_GRID, (N / 2 + ISH_THREADS) / ISH_THREADS);  // the onset's walks
     const size_t npart = std::max<size_t>({(size_t)DEC_FIT_PART * rgrid, (size_t)2 * npick, (size_t)ogrid});
@@ -311,8 +276,8 @@ inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n,
     double *d_tot = nullptr, *d_part = nullptr;
     std::vector<double> part(npart);
     hipError_t er = hipMalloc(&d_buf, sizeof(double2) * N);
-    if (er == hipSuccess) er = hipMalloc(&d_st, sizeof(double2) * (size_t)cgrid * IEQ_THREADS);
-    if (er == hipSuccess) er = hipMalloc(&d_tot, sizeof(double) * (size_t)cgrid * IEQ_THREADS);
+    if (er == hipSuccess) er = hipMalloc(&d_st, sizeof(double2) * (size_t)cg.lanes);
+    if (er == hipSuccess) er = hipMalloc(&d_tot, sizeof(double) * (size_t)cg.lanes);
     if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * npart);
     const auto launched = [&] { er = hipGetLastError(); };
     const auto fetch = [&](size_t count) {
@@ -353,27 +318,27 @@ inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n,
         if (g > 0) {  // two identical sections: the second rides as the `nxt` stage of the first's fix-up
             IeqStage sec{}, off{};
             sec.c = dec_coef(q.centre_hz[g - 1], q.q, q.rate), sec.on = 1;
-            const IeqMat M = ieq_matpow(IeqMat{-sec.c.a1, 1.0, -sec.c.a2, 0.0}, IEQ_CHUNK), MK = ieq_matpow(M, runK);
+            const IeqMat M = ieq_matpow(IeqMat{-sec.c.a1, 1.0, -sec.c.a2, 0.0}, IEQ_CHUNK), MK = ieq_matpow(M, cg.K);
             for (int pass = 0; pass < 3 && er == hipSuccess; pass++) {
                 if (pass > 0) {
-                    hipLaunchKernelGGL(k_eq_carry, dim3(1), dim3(2 * IEQ_RUNS), 0, stream, d_st, nchunks, runK, M, MK);
+                    hipLaunchKernelGGL(k_eq_carry, dim3(1), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.nchunks, cg.K, M, MK);
                     launched();
                 }
                 if (er != hipSuccess) break;
-                hipLaunchKernelGGL(k_eq_chunk, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pass > 0 ? sec : off, pass < 2 ? sec : off, d_st);
+                hipLaunchKernelGGL(k_eq_chunk, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pass > 0 ? sec : off, pass < 2 ? sec : off, d_st);
                 launched();
             }
         }
         if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_dec_sum<false>, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
+            hipLaunchKernelGGL(k_dec_sum<false>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
             launched();
         }
         if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_dec_carry, dim3(1), dim3(DEC_CARRY_THREADS), 0, stream, d_tot, nchunks);
+            hipLaunchKernelGGL(k_dec_carry, dim3(1), dim3(DEC_CARRY_THREADS), 0, stream, d_tot, cg.nchunks);
             launched();
         }
         if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_dec_sum<true>, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
+            hipLaunchKernelGGL(k_dec_sum<true>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
             launched();
         }
         if (er == hipSuccess) {

@@ -25,25 +25,15 @@
 // The fix-up of band k feeds what it writes to band k + 1 from rest in the same loop, so it is band k + 1's local pass as
 // well: B bands take B + 1 launches of k_eq_chunk and B of k_eq_carry.
 //
-// Memory.  A lane walking its own chunk in global memory would put the lanes of a wave 4 KiB apart.  A workgroup (128 lanes: 64
-// chunks x 2 channels, IEQ_SPAN taps) therefore stages IEQ_TILE taps of each of its chunks through LDS: 16 consecutive lanes
-// move one chunk's 256 contiguous bytes, the next tile's loads fly under the current tile's arithmetic (registers), and the
-// lanes read their own rows with ds_read_b64.  Rows are IEQ_TILE + 1 double2 long: lane (c, ch) reads dword 68 c + 4 k + 2 ch, so
-// the 32 lanes of a half wave (c = 0 .. 15) fall on 32 different pairs of the 64 banks: no conflict.
+// Memory.  k_eq_chunk is one chunk_walk of chunkwalk.hip.h, whose head says how the taps reach the lanes (64 chunks x 2 channels
+// per workgroup, IEQ_TILE taps of every chunk staged through padded LDS rows, the next tile's loads under the arithmetic).
 //
 // Determinism.  Chunks and runs depend on n alone; no atomics; every reduction ends in one partial per workgroup, combined
 // on the host in index order (as irshape.hip.h does).  The same frames, shape and bands give the same bits.
 #pragma once
+#include "chunkwalk.hip.h"
 #include "irshape.hip.h"
 
-constexpr int IEQ_CHUNK = 256;                                 // taps one lane filters
-constexpr int IEQ_TILE = 16;                                   // taps of each chunk in LDS at a time
-constexpr int IEQ_ROW = IEQ_TILE + 1;                          // double2 per LDS row (one of padding)
-constexpr int IEQ_WG_CHUNKS = 64;                              // chunks per workgroup
-constexpr int IEQ_THREADS = 2 * IEQ_WG_CHUNKS;                 // one lane per (chunk, channel)
-constexpr int IEQ_SPAN = IEQ_WG_CHUNKS * IEQ_CHUNK;            // taps per workgroup
-constexpr int IEQ_PER = IEQ_WG_CHUNKS * IEQ_TILE / IEQ_THREADS;  // double2 a lane moves per tile
-constexpr int IEQ_RUNS = 128;                                  // runs of chunks per channel in the carry pass
 constexpr double IEQ_MIN_HZ = 10.0, IEQ_MAX_NYQ = 0.45, IEQ_MIN_Q = 0.1, IEQ_MAX_Q = 32.0, IEQ_MIN_DB = -36.0, IEQ_MAX_DB = 24.0;
 
 // one band, a0 = 1
@@ -79,93 +69,73 @@ __global__ __launch_bounds__(ISH_THREADS) void k_eq_fill(const float2* __restric
 // entry of st (read at the start, written at the end, by the same lane).  st: double2 [gridDim.x * IEQ_THREADS], entry
 // 2 * chunk + channel.  Taps at and past n read as zero and are not written.
 __global__ __launch_bounds__(IEQ_THREADS) void k_eq_chunk(double2* __restrict__ buf, uint64_t n, IeqStage cur, IeqStage nxt, double2* __restrict__ st) {
-    __shared__ double2 tile[IEQ_WG_CHUNKS * IEQ_ROW];
-    const int t = threadIdx.x, c = t >> 1, ch = t & 1;
-    const uint64_t base = (uint64_t)blockIdx.x * IEQ_SPAN;
-    const uint64_t entry = (uint64_t)blockIdx.x * IEQ_THREADS + t;
+    const uint64_t entry = (uint64_t)blockIdx.x * IEQ_THREADS + threadIdx.x;
     double s1 = 0.0, s2 = 0.0, u1 = 0.0, u2 = 0.0;
     if (cur.on) {
         const double2 s = st[entry];
         s1 = s.x;
         s2 = s.y;
     }
-    // element j of the lane's share of a tile: chunk i / IEQ_TILE, tap i % IEQ_TILE of it, i = t + j IEQ_THREADS
-    double2 pre[IEQ_PER];
-    const auto fetch = [&](int ph) {
-#pragma unroll
-        for (int j = 0; j < IEQ_PER; j++) {
-            const int i = t + j * IEQ_THREADS;
-            const uint64_t g = base + (uint64_t)(i / IEQ_TILE) * IEQ_CHUNK + ph * IEQ_TILE + i % IEQ_TILE;
-            pre[j] = g < n ? buf[g] : make_double2(0.0, 0.0);
-        }
-    };
-    fetch(0);
-    for (int ph = 0; ph < IEQ_CHUNK / IEQ_TILE; ph++) {
-#pragma unroll
-        for (int j = 0; j < IEQ_PER; j++) {
-            const int i = t + j * IEQ_THREADS;
-            tile[(i / IEQ_TILE) * IEQ_ROW + i % IEQ_TILE] = pre[j];
-        }
-        __syncthreads();
-        if (ph + 1 < IEQ_CHUNK / IEQ_TILE) fetch(ph + 1);
-        double* row = reinterpret_cast<double*>(tile + c * IEQ_ROW) + ch;
-#pragma unroll
-        for (int k = 0; k < IEQ_TILE; k++) {
-            double v = row[2 * k];
+    chunk_walk<false, IEQ_TILE, double2>(
+        cur.on, [&](uint64_t g, double2& v) { v = g < n ? buf[g] : make_double2(0.0, 0.0); },
+        [&](double& tap, uint64_t) {
+            double v = tap;
             if (cur.on) {
                 const double y = cur.c.b0 * v + s1;
                 s1 = cur.c.b1 * v - cur.c.a1 * y + s2;
                 s2 = cur.c.b2 * v - cur.c.a2 * y;
-                row[2 * k] = v = y;
+                tap = v = y;
             }
             if (nxt.on) {
                 const double y = nxt.c.b0 * v + u1;
                 u1 = nxt.c.b1 * v - nxt.c.a1 * y + u2;
                 u2 = nxt.c.b2 * v - nxt.c.a2 * y;
             }
-        }
-        __syncthreads();
-        if (cur.on) {
-#pragma unroll
-            for (int j = 0; j < IEQ_PER; j++) {
-                const int i = t + j * IEQ_THREADS;
-                const uint64_t g = base + (uint64_t)(i / IEQ_TILE) * IEQ_CHUNK + ph * IEQ_TILE + i % IEQ_TILE;
-                if (g < n) buf[g] = tile[(i / IEQ_TILE) * IEQ_ROW + i % IEQ_TILE];
-            }
-            __syncthreads();
-        }
-    }
+        },
+        [&](uint64_t g, double2 v) {
+            if (g < n) buf[g] = v;
+        });
     if (nxt.on) st[entry] = make_double2(u1, u2);
 }
 
-// st[2 c + ch], c < nchunks: in, the state chunk c leaves when it starts at rest; out, the state it starts with.  One
-// workgroup of 2 IEQ_RUNS lanes; lane (run, ch) owns chunks [run K, (run + 1) K).  M = A^IEQ_CHUNK, MK = M^K.
-__global__ __launch_bounds__(2 * IEQ_RUNS) void k_eq_carry(double2* __restrict__ st, uint32_t nchunks, uint32_t K, IeqMat M, IeqMat MK) {
-    __shared__ double2 ends[2 * IEQ_RUNS];
+// The carry pass over one channel pair's chunk states, c < nchunks: in, the state chunk c leaves when it starts at rest; out,
+// the state it starts with.  One workgroup of 2 IEQ_RUNS lanes; lane (run, ch) owns chunks [run K, (run + 1) K): it scans its
+// run, lanes 0 and 1 scan the runs' ends, and it scans its run again from its true start and writes.  load(i) / store(i, s):
+// entry i = 2 c + ch; step(runs, s, e) = A s + e with A = the matrix of a chunk, or with `runs` that of a run of K chunks.
+template <class S, class Load, class Store, class Step>
+__device__ __forceinline__ void carry_scan(uint32_t nchunks, uint32_t K, Load&& load, Store&& store, Step&& step) {
+    __shared__ S ends[2 * IEQ_RUNS];
     const int t = threadIdx.x, ch = t & 1;
     const uint64_t r0 = (uint64_t)(t >> 1) * K, c0 = r0 < nchunks ? r0 : nchunks, c1 = c0 + K < nchunks ? c0 + K : nchunks;
-    double2 s = make_double2(0.0, 0.0);
-    for (uint64_t c = c0; c < c1; c++) {
-        const double2 e = st[2 * c + ch], r = ieq_mul(M, s);
-        s = make_double2(r.x + e.x, r.y + e.y);
-    }
+    S s{};
+    for (uint64_t c = c0; c < c1; c++) s = step(false, s, load(2 * c + ch));
     ends[t] = s;
     __syncthreads();
     if (t < 2) {  // (a run that is short or empty is the last or lies behind the last: what follows it is not used)
-        double2 S = make_double2(0.0, 0.0);
+        S r{};
         for (int g = 0; g < IEQ_RUNS; g++) {
-            const double2 e = ends[2 * g + t], r = ieq_mul(MK, S);
-            ends[2 * g + t] = S;
-            S = make_double2(r.x + e.x, r.y + e.y);
+            const S e = ends[2 * g + t];
+            ends[2 * g + t] = r;
+            r = step(true, r, e);
         }
     }
     __syncthreads();
     s = ends[t];
     for (uint64_t c = c0; c < c1; c++) {
-        const double2 e = st[2 * c + ch], r = ieq_mul(M, s);
-        st[2 * c + ch] = s;
-        s = make_double2(r.x + e.x, r.y + e.y);
+        const S e = load(2 * c + ch);
+        store(2 * c + ch, s);
+        s = step(false, s, e);
     }
+}
+
+// carry_scan over st[2 c + ch].  M = A^IEQ_CHUNK, MK = M^K.
+__global__ __launch_bounds__(2 * IEQ_RUNS) void k_eq_carry(double2* __restrict__ st, uint32_t nchunks, uint32_t K, IeqMat M, IeqMat MK) {
+    carry_scan<double2>(
+        nchunks, K, [&](uint64_t i) { return st[i]; }, [&](uint64_t i, double2 s) { st[i] = s; },
+        [&](bool runs, double2 s, double2 e) {
+            const double2 r = ieq_mul(runs ? MK : M, s);
+            return make_double2(r.x + e.x, r.y + e.y);
+        });
 }
 
 // k_shape_apply's two forms over the equalised taps.  WRITE = false: part[2 b] = max |tap|, part[2 b + 1] = sum (L^2 + R^2) of
@@ -292,6 +262,19 @@ inline double ieq_response_db(const IeqCascade& cs, uint32_t rate, double hz) {
     return db;
 }
 
+// The chunk passes over n taps: workgroups of a chunk kernel, their lanes (= entries of a state array), chunks, and chunks per
+// run of the carry pass.
+struct ChunkGeom {
+    unsigned grid;
+    uint64_t lanes;
+    uint32_t nchunks, K;
+};
+inline ChunkGeom chunk_geom(uint64_t n) {
+    const unsigned grid = (unsigned)((n + IEQ_SPAN - 1) / IEQ_SPAN);
+    const uint32_t nchunks = (uint32_t)((n + IEQ_CHUNK - 1) / IEQ_CHUNK);
+    return ChunkGeom{grid, (uint64_t)grid * IEQ_THREADS, nchunks, (nchunks + IEQ_RUNS - 1) / IEQ_RUNS};
+}
+
 inline IeqMat ieq_matmul(const IeqMat& a, const IeqMat& b) {
     return IeqMat{a.m00 * b.m00 + a.m01 * b.m10, a.m00 * b.m01 + a.m01 * b.m11, a.m10 * b.m00 + a.m11 * b.m10, a.m10 * b.m01 + a.m11 * b.m11};
 }
@@ -309,17 +292,16 @@ inline hipError_t ieq_finish(hipStream_t stream, const float2* d_x, const IshPla
                              float2** d_out, uint64_t* n_out, double sums[4], double info[8], const DampPlan* damp) {
     const uint64_t n = pl.n;
     const unsigned grid = (unsigned)((n + ISH_THREADS - 1) / ISH_THREADS);       // k_eq_fill, k_eq_store
-    const unsigned cgrid = (unsigned)((n + IEQ_SPAN - 1) / IEQ_SPAN);            // k_eq_chunk
-    const uint32_t nchunks = (uint32_t)((n + IEQ_CHUNK - 1) / IEQ_CHUNK), K = (nchunks + IEQ_RUNS - 1) / IEQ_RUNS;
+    const ChunkGeom cg = chunk_geom(n);                                          // k_eq_chunk, k_eq_carry
     double2 *d_buf = nullptr, *d_st = nullptr;
     float2* d_y = nullptr;
     double* d_part = nullptr;
     std::vector<double> part(4 * (size_t)grid);
     hipError_t er = hipMalloc(&d_buf, sizeof(double2) * n);
-    if (er == hipSuccess) er = hipMalloc(&d_st, sizeof(double2) * (size_t)cgrid * IEQ_THREADS);
+    if (er == hipSuccess) er = hipMalloc(&d_st, sizeof(double2) * (size_t)cg.lanes);
     if (er == hipSuccess) er = hipMalloc(&d_y, sizeof(float2) * n);
     if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * part.size());
-    if (er == hipSuccess) er = hipMemsetAsync(d_st, 0, sizeof(double2) * (size_t)cgrid * IEQ_THREADS, stream);
+    if (er == hipSuccess) er = hipMemsetAsync(d_st, 0, sizeof(double2) * (size_t)cg.lanes, stream);
     if (er == hipSuccess) {
         hipLaunchKernelGGL(k_eq_fill, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x, pl, d_buf);
         er = hipGetLastError();
@@ -330,12 +312,12 @@ inline hipError_t ieq_finish(hipStream_t stream, const float2* d_x, const IshPla
         if (k > 0) {
             cur.c = eq.c[k - 1], cur.on = 1;
             const IeqMat M = ieq_matpow(IeqMat{-cur.c.a1, 1.0, -cur.c.a2, 0.0}, IEQ_CHUNK);
-            hipLaunchKernelGGL(k_eq_carry, dim3(1), dim3(2 * IEQ_RUNS), 0, stream, d_st, nchunks, K, M, ieq_matpow(M, K));
+            hipLaunchKernelGGL(k_eq_carry, dim3(1), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.nchunks, cg.K, M, ieq_matpow(M, cg.K));
             er = hipGetLastError();
         }
         if (k < eq.bands) nxt.c = eq.c[k], nxt.on = 1;
         if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_eq_chunk, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, n, cur, nxt, d_st);
+            hipLaunchKernelGGL(k_eq_chunk, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, n, cur, nxt, d_st);
             er = hipGetLastError();
         }
     }

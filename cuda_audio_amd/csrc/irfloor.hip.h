@@ -40,10 +40,7 @@ struct FlrGather {
 // B_j out.  The weights are damping's with g_j = 1 and every other gain 0, added in damping's order, so the band is exactly
 // P_1, P_(j+1) - P_j or x - P_X.  Taps at and past n read as zero and are not written.
 __global__ __launch_bounds__(IEQ_THREADS) void k_flr_band(double2* __restrict__ buf, uint64_t n, DampPlan pl, int band, const double2* __restrict__ st) {
-    __shared__ double2 tile[IEQ_WG_CHUNKS * IEQ_ROW];
-    const int t = threadIdx.x, c = t >> 1, ch = t & 1;
-    const uint64_t base = (uint64_t)blockIdx.x * IEQ_SPAN;
-    const uint64_t lanes = (uint64_t)gridDim.x * IEQ_THREADS, entry = (uint64_t)blockIdx.x * IEQ_THREADS + t;
+    const uint64_t lanes = (uint64_t)gridDim.x * IEQ_THREADS, entry = (uint64_t)blockIdx.x * IEQ_THREADS + threadIdx.x;
     DampState s[MC_DAMP_MAX_XOVERS];
 #pragma unroll
     for (int k = 0; k < MC_DAMP_MAX_XOVERS; k++) {
@@ -55,43 +52,19 @@ __global__ __launch_bounds__(IEQ_THREADS) void k_flr_band(double2* __restrict__ 
 #pragma unroll
     for (int k = 0; k < MC_DAMP_MAX_XOVERS; k++) w[k] = (band == k ? 1.0 : 0.0) - (band == k + 1 ? 1.0 : 0.0);
     const double gX = band == pl.X ? 1.0 : 0.0;
-    double2 pre[IEQ_PER];
-    const auto fetch = [&](int ph) {
-#pragma unroll
-        for (int j = 0; j < IEQ_PER; j++) {
-            const int i = t + j * IEQ_THREADS;
-            const uint64_t g = base + (uint64_t)(i / IEQ_TILE) * IEQ_CHUNK + ph * IEQ_TILE + i % IEQ_TILE;
-            pre[j] = g < n ? buf[g] : make_double2(0.0, 0.0);
-        }
-    };
-    fetch(0);
-    for (int ph = 0; ph < IEQ_CHUNK / IEQ_TILE; ph++) {
-#pragma unroll
-        for (int j = 0; j < IEQ_PER; j++) {
-            const int i = t + j * IEQ_THREADS;
-            tile[(i / IEQ_TILE) * IEQ_ROW + i % IEQ_TILE] = pre[j];
-        }
-        __syncthreads();
-        if (ph + 1 < IEQ_CHUNK / IEQ_TILE) fetch(ph + 1);
-        double* row = reinterpret_cast<double*>(tile + c * IEQ_ROW) + ch;
-#pragma unroll
-        for (int k = 0; k < IEQ_TILE; k++) {
-            const double v = row[2 * k];
+    chunk_walk<false, IEQ_TILE, double2>(
+        true, [&](uint64_t g, double2& v) { v = g < n ? buf[g] : make_double2(0.0, 0.0); },
+        [&](double& tap, uint64_t) {
+            const double v = tap;
             double y = gX * v;
 #pragma unroll
             for (int x = 0; x < MC_DAMP_MAX_XOVERS; x++)
                 if (x < pl.X) y += w[x] * damp_step(pl.c[x], s[x], v);
-            row[2 * k] = y;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int j = 0; j < IEQ_PER; j++) {
-            const int i = t + j * IEQ_THREADS;
-            const uint64_t g = base + (uint64_t)(i / IEQ_TILE) * IEQ_CHUNK + ph * IEQ_TILE + i % IEQ_TILE;
-            if (g < n) buf[g] = tile[(i / IEQ_TILE) * IEQ_ROW + i % IEQ_TILE];
-        }
-        __syncthreads();
-    }
+            tap = y;
+        },
+        [&](uint64_t g, double2 v) {
+            if (g < n) buf[g] = v;
+        });
 }
 
 // out[ga.at[s] + i] = EDC of set s at ga.start[s] + i ga.step[s], i < ga.count[s]; a tap at or past n: 0 (EDC[N] = 0).
@@ -299,17 +272,15 @@ inline hipError_t flr_measure(hipStream_t stream, const float2* d_x, uint64_t n,
     const uint64_t N = q.end ? std::min<uint64_t>(q.end, n) : n;
     const int X = (int)q.n_xovers;
     const unsigned grid = (unsigned)((N + ISH_THREADS - 1) / ISH_THREADS);                    // k_dec_fill
-    const unsigned cgrid = (unsigned)((N + IEQ_SPAN - 1) / IEQ_SPAN);                         // the chunk passes
-    const uint64_t lanes = (uint64_t)cgrid * IEQ_THREADS;
-    const uint32_t nchunks = (uint32_t)((N + IEQ_CHUNK - 1) / IEQ_CHUNK), runK = (nchunks + IEQ_RUNS - 1) / IEQ_RUNS;
+    const ChunkGeom cg = chunk_geom(N);                                                       // the chunk passes
     const unsigned ogrid = (unsigned)std::min<uint64_t>(ISH_SCAN_GRID, (N / 2 + ISH_THREADS) / ISH_THREADS);  // the onset's walks
     double2 *d_buf = nullptr, *d_st = nullptr;
     double *d_tot = nullptr, *d_part = nullptr;
     size_t part_cap = std::max<size_t>(ogrid, 16);
     std::vector<double> part;
     hipError_t er = hipMalloc(&d_buf, sizeof(double2) * N);
-    if (er == hipSuccess && X) er = hipMalloc(&d_st, sizeof(double2) * 2 * (size_t)X * lanes);
-    if (er == hipSuccess) er = hipMalloc(&d_tot, sizeof(double) * (size_t)cgrid * IEQ_THREADS);
+    if (er == hipSuccess && X) er = hipMalloc(&d_st, sizeof(double2) * 2 * (size_t)X * cg.lanes);
+    if (er == hipSuccess) er = hipMalloc(&d_tot, sizeof(double) * (size_t)cg.lanes);
     if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * part_cap);
     const auto launched = [&] { er = hipGetLastError(); };
 
@@ -343,20 +314,15 @@ inline hipError_t flr_measure(hipStream_t stream, const float2* d_x, uint64_t n,
     pl.X = X;
     for (int k = 0; k < X; k++) pl.c[k] = ieq_coef(mc_eq_band{MC_EQ_HIGHCUT, q.xover_hz[k], 0.f, 0.70710678f}, q.rate);
     if (er == hipSuccess && X) {
-        DampCarry cm{};
-        for (int k = 0; k < X; k++) {
-            const DampMatL M = damp_matpow(damp_widen(damp_matrix(pl.c[k])), IEQ_CHUNK);
-            cm.M[k] = damp_round(M);
-            cm.MK[k] = damp_round(damp_matpow(M, runK));
-        }
+        const DampCarry cm = damp_carry(pl.c, X, cg.K);
         hipLaunchKernelGGL(k_dec_fill, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x, N, d_buf);
         launched();
         if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_damp_chunk<false>, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pl, d_st);
+            hipLaunchKernelGGL(k_damp_chunk<false>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pl, d_st);
             launched();
         }
         if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_damp_carry, dim3(X), dim3(2 * IEQ_RUNS), 0, stream, d_st, lanes, nchunks, runK, cm);
+            hipLaunchKernelGGL(k_damp_carry, dim3(X), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.lanes, cg.nchunks, cg.K, cm);
             launched();
         }
     }
@@ -387,19 +353,19 @@ inline hipError_t flr_measure(hipStream_t stream, const float2* d_x, uint64_t n,
         hipLaunchKernelGGL(k_dec_fill, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x, N, d_buf);
         launched();
         if (er == hipSuccess && g > 0) {
-            hipLaunchKernelGGL(k_flr_band, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pl, (int)g - 1, d_st);
+            hipLaunchKernelGGL(k_flr_band, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pl, (int)g - 1, d_st);
             launched();
         }
         if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_dec_sum<false>, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
+            hipLaunchKernelGGL(k_dec_sum<false>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
             launched();
         }
         if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_dec_carry, dim3(1), dim3(DEC_CARRY_THREADS), 0, stream, d_tot, nchunks);
+            hipLaunchKernelGGL(k_dec_carry, dim3(1), dim3(DEC_CARRY_THREADS), 0, stream, d_tot, cg.nchunks);
             launched();
         }
         if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_dec_sum<true>, dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
+            hipLaunchKernelGGL(k_dec_sum<true>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
             launched();
         }
         if (er != hipSuccess) break;

@@ -10,8 +10,8 @@
 // v the Gaussian noise of irsynth.hip.h's generator on Philox stream 3.
 //
 // The kernel is irdamp.hip.h's chunked recurrence with two signals: a lane owns one (chunk, channel) and carries 2 X crossover
-// states, X for x and X for v; chunking, workgroup shape and the padded LDS rows are ireq.hip.h's.  x comes in as float2 and is
-// staged as double2; v is generated per frame in the lane (one Philox block, one Box-Muller pair in double, a second pair only
+// states, X for x and X for v; chunking, workgroup shape and the padded LDS rows are chunkwalk.hip.h's chunk_walk.  x comes in as
+// float2 and is staged as double2; v is generated per frame in the lane (one Philox block, one Box-Muller pair in double, a second pair only
 // for a right channel that is mixed from both) and never stored; y leaves as float2, rounded once.
 //   local  k_tail_chunk<false> runs the crossovers over every chunk from rest and keeps the end states of both signals;
 //   carry  k_damp_carry, unchanged, once per signal;
@@ -79,10 +79,8 @@ __device__ inline double tail_noise(const TailPlan& p, uint32_t m, int ch) {
 // st holds, y written.  NOISE: MC_TAIL_EXTEND.  Frames at and past Fp are not written.
 template <bool FIX, bool NOISE>
 __global__ __launch_bounds__(IEQ_THREADS) void k_tail_chunk(const float2* __restrict__ x, float2* __restrict__ y, TailPlan p, double2* __restrict__ st) {
-    __shared__ double2 tile[IEQ_WG_CHUNKS * IEQ_ROW];
-    const int t = threadIdx.x, c = t >> 1, ch = t & 1;
-    const uint64_t base = (uint64_t)blockIdx.x * IEQ_SPAN;
-    const uint64_t lanes = (uint64_t)gridDim.x * IEQ_THREADS, entry = (uint64_t)blockIdx.x * IEQ_THREADS + t;
+    const int ch = threadIdx.x & 1;
+    const uint64_t lanes = (uint64_t)gridDim.x * IEQ_THREADS, entry = (uint64_t)blockIdx.x * IEQ_THREADS + threadIdx.x;
     DampState sx[MC_DAMP_MAX_XOVERS], sv[MC_DAMP_MAX_XOVERS];
 #pragma unroll
     for (int k = 0; k < MC_DAMP_MAX_XOVERS; k++) {
@@ -92,31 +90,10 @@ __global__ __launch_bounds__(IEQ_THREADS) void k_tail_chunk(const float2* __rest
             if (NOISE) sv[k] = damp_load(st, (uint64_t)(p.X + k) * lanes + entry);
         }
     }
-    // element j of the lane's share of a tile: chunk i / IEQ_TILE, frame i % IEQ_TILE of it, i = t + j IEQ_THREADS
-    float2 pre[IEQ_PER];
-    const auto fetch = [&](int ph) {
-#pragma unroll
-        for (int j = 0; j < IEQ_PER; j++) {
-            const int i = t + j * IEQ_THREADS;
-            const uint64_t g = base + (uint64_t)(i / IEQ_TILE) * IEQ_CHUNK + ph * IEQ_TILE + i % IEQ_TILE;
-            pre[j] = g < p.F && g < p.Fp ? x[g] : make_float2(0.f, 0.f);
-        }
-    };
-    fetch(0);
-    for (int ph = 0; ph < IEQ_CHUNK / IEQ_TILE; ph++) {
-#pragma unroll
-        for (int j = 0; j < IEQ_PER; j++) {
-            const int i = t + j * IEQ_THREADS;
-            tile[(i / IEQ_TILE) * IEQ_ROW + i % IEQ_TILE] = make_double2((double)pre[j].x, (double)pre[j].y);
-        }
-        __syncthreads();
-        if (ph + 1 < IEQ_CHUNK / IEQ_TILE) fetch(ph + 1);
-        double* row = reinterpret_cast<double*>(tile + c * IEQ_ROW) + ch;
-        const uint64_t m0 = base + (uint64_t)c * IEQ_CHUNK + ph * IEQ_TILE;
-#pragma unroll 4
-        for (int k = 0; k < IEQ_TILE; k++) {
-            const uint64_t m = m0 + k;
-            const double vx = row[2 * k];
+    chunk_walk<false, 4, float2>(
+        FIX, [&](uint64_t g, float2& v) { v = g < p.F && g < p.Fp ? x[g] : make_float2(0.f, 0.f); },
+        [&](double& tap, uint64_t m) {
+            const double vx = tap;
             const double vn = NOISE ? tail_noise(p, (uint32_t)m, ch) : 0.0;
             double Px[MC_DAMP_MAX_XOVERS], Pv[MC_DAMP_MAX_XOVERS];
 #pragma unroll
@@ -152,21 +129,12 @@ __global__ __launch_bounds__(IEQ_THREADS) void k_tail_chunk(const float2* __rest
                             if (i < p.X) out += wq[i] * Pv[i];
                     }
                 }
-                row[2 * k] = out;
+                tap = out;
             }
-        }
-        __syncthreads();
-        if (FIX) {
-#pragma unroll
-            for (int j = 0; j < IEQ_PER; j++) {
-                const int i = t + j * IEQ_THREADS;
-                const uint64_t g = base + (uint64_t)(i / IEQ_TILE) * IEQ_CHUNK + ph * IEQ_TILE + i % IEQ_TILE;
-                const double2 v = tile[(i / IEQ_TILE) * IEQ_ROW + i % IEQ_TILE];
-                if (g < p.Fp) y[g] = make_float2((float)v.x, (float)v.y);
-            }
-            __syncthreads();
-        }
-    }
+        },
+        [&](uint64_t g, double2 v) {
+            if (g < p.Fp) y[g] = make_float2((float)v.x, (float)v.y);
+        });
     if (!FIX) {
 #pragma unroll
         for (int k = 0; k < MC_DAMP_MAX_XOVERS; k++)
@@ -294,36 +262,30 @@ inline TailPlan tail_plan(const mc_ir_tail& t, uint32_t session_rate, uint64_t F
 // Step 1a: the p.Fp frames into d_y from the p.F frames d_x, on the stream, after what the stream already holds.  Allocates
 // the state scratch, waits for the kernels and frees it.
 inline hipError_t tail_run(hipStream_t stream, const float2* d_x, float2* d_y, const TailPlan& p, bool extend) {
-    const unsigned cgrid = (unsigned)((p.Fp + IEQ_SPAN - 1) / IEQ_SPAN);
-    const uint64_t lanes = (uint64_t)cgrid * IEQ_THREADS;
-    const uint32_t nchunks = (uint32_t)((p.Fp + IEQ_CHUNK - 1) / IEQ_CHUNK), K = (nchunks + IEQ_RUNS - 1) / IEQ_RUNS;
+    const ChunkGeom cg = chunk_geom(p.Fp);
+    const uint64_t lanes = cg.lanes;
     const int signals = extend ? 2 : 1;
     double2* d_st = nullptr;
     hipError_t er = hipSuccess;
     if (p.X) {
-        DampCarry cm{};
-        for (int k = 0; k < p.X; k++) {
-            const DampMatL M = damp_matpow(damp_widen(damp_matrix(p.c[k])), IEQ_CHUNK);
-            cm.M[k] = damp_round(M);
-            cm.MK[k] = damp_round(damp_matpow(M, K));
-        }
+        const DampCarry cm = damp_carry(p.c, p.X, cg.K);
         er = hipMalloc(&d_st, sizeof(double2) * 2 * (size_t)signals * p.X * lanes);
         if (er != hipSuccess) return er;
         if (extend)
-            hipLaunchKernelGGL((k_tail_chunk<false, true>), dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_x, d_y, p, d_st);
+            hipLaunchKernelGGL((k_tail_chunk<false, true>), dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_x, d_y, p, d_st);
         else
-            hipLaunchKernelGGL((k_tail_chunk<false, false>), dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_x, d_y, p, d_st);
+            hipLaunchKernelGGL((k_tail_chunk<false, false>), dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_x, d_y, p, d_st);
         er = hipGetLastError();
         for (int s = 0; s < signals && er == hipSuccess; s++) {
-            hipLaunchKernelGGL(k_damp_carry, dim3(p.X), dim3(2 * IEQ_RUNS), 0, stream, d_st + 2 * (size_t)s * p.X * lanes, lanes, nchunks, K, cm);
+            hipLaunchKernelGGL(k_damp_carry, dim3(p.X), dim3(2 * IEQ_RUNS), 0, stream, d_st + 2 * (size_t)s * p.X * lanes, lanes, cg.nchunks, cg.K, cm);
             er = hipGetLastError();
         }
     }
     if (er == hipSuccess) {
         if (extend)
-            hipLaunchKernelGGL((k_tail_chunk<true, true>), dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_x, d_y, p, d_st);
+            hipLaunchKernelGGL((k_tail_chunk<true, true>), dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_x, d_y, p, d_st);
         else
-            hipLaunchKernelGGL((k_tail_chunk<true, false>), dim3(cgrid), dim3(IEQ_THREADS), 0, stream, d_x, d_y, p, d_st);
+            hipLaunchKernelGGL((k_tail_chunk<true, false>), dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_x, d_y, p, d_st);
         er = hipGetLastError();
     }
     const hipError_t sy = hipStreamSynchronize(stream);
