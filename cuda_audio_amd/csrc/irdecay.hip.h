@@ -318,10 +318,10 @@ inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n,
         if (g > 0) {  // two identical sections: the second rides as the `nxt` stage of the first's fix-up
             IeqStage sec{}, off{};
             sec.c = dec_coef(q.centre_hz[g - 1], q.q, q.rate), sec.on = 1;
-            const IeqMat M = ieq_matpow(IeqMat{-sec.c.a1, 1.0, -sec.c.a2, 0.0}, IEQ_CHUNK), MK = ieq_matpow(M, cg.K);
+            const IeqCarry cm = ieq_carry(sec.c, cg.K);
             for (int pass = 0; pass < 3 && er == hipSuccess; pass++) {
                 if (pass > 0) {
-                    hipLaunchKernelGGL(k_eq_carry, dim3(1), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.nchunks, cg.K, M, MK);
+                    hipLaunchKernelGGL(k_eq_carry, dim3(1), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.nchunks, cg.K, cm.M, cm.MK);
                     launched();
                 }
                 if (er != hipSuccess) break;

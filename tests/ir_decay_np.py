@@ -90,9 +90,10 @@ def row_of(e, edc, L, o, N, rate):
     return row
 
 
-def decay(taps, rate, bands=(), q=None, onset_db=-20.0, end=0, curve_points=0):
+def decay(taps, rate, bands=(), q=None, onset_db=-20.0, end=0, curve_points=0, band_filter=None):
     """taps: float32 [n, 2] as Convolution.ir_taps gives them.  Returns what Convolution.ir_decay returns, plus "levels":
-    {(band, set): L over taps origin .. N - 1} for assert_range_margin."""
+    {(band, set): L over taps origin .. N - 1} for assert_range_margin.  band_filter(x, c) -> float64 [N, 2] stands in for step 2's
+    two sequential loops (test_ir_chunk_cpu.py runs them in extended precision to check this restatement itself)."""
     taps = np.asarray(taps, np.float32).reshape(-1, 2)
     n = taps.shape[0]
     N = min(int(end), n) if end else n
@@ -106,7 +107,7 @@ def decay(taps, rate, bands=(), q=None, onset_db=-20.0, end=0, curve_points=0):
         y = x
         if b:
             c = band_coefs(bands[b - 1], q, rate)
-            y = biquad(biquad(x, c), c)
+            y = band_filter(x, c) if band_filter else biquad(biquad(x, c), c)
         e, edc, L = levels(y, o)
         for s, name in enumerate(SETS):
             rows[(b, name)] = row_of(e[s], edc[s], L[s], o, N, rate)

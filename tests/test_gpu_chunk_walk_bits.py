@@ -1,14 +1,25 @@
 """The chunked-recurrence kernels of the IR tools (csrc/chunkwalk.hip.h and the five kernels that walk through it: k_eq_chunk,
-k_damp_chunk, k_tail_chunk, k_flr_band, k_dec_sum; the carries k_eq_carry and k_damp_carry) give the bits they gave before they
-shared one walk.  tests/golden/chunk_walk_bits.json holds SHA-256 digests of what the library at the commit before the shared
-walk stored and measured for the cases below; the test computes the same with the library under test and compares.  No
-tolerance: the arithmetic and its order are meant to be untouched, so a different digest is a reordered expression.
+k_damp_chunk, k_tail_chunk, k_flr_band, k_dec_sum; the carries k_eq_carry and k_damp_carry) give the bits that are on record.
+tests/golden/chunk_walk_bits.json holds SHA-256 digests of what the library stored and measured for the cases below; the test
+computes the same with the library under test and compares.  No tolerance: a different digest is a reordered expression.
+
+What the digests pin: the arithmetic of the kernels and its order, with the carry matrices A^256 and (A^256)^K raised in long
+double and rounded once (carry_powers of csrc/ireq.hip.h).
+  "sha256"                 recorded at the commit before the five kernels shared one walk, and still what they give: eq_1, damp1_257,
+                           the three tail_* cases and floor_40000 run no matrix of k_eq_carry that matters (one chunk, or the
+                           damping's 4 x 4 ones, which were raised so from the start); the eq_* cases do, but their float32 taps
+                           round the matrices' last bits away, so they stayed as well.
+  "sha256_extended_carry"  re-recorded at the commit its "commit" field names, which raised k_eq_carry's 2 x 2 matrices in long
+                           double where they had been squared in double: damp3_eq_16385, damp3_eq_40000 and decay_40000, the
+                           three whose digests that moved.  No kernel changed there; tests/test_gpu_ir_long_carry.py has what
+                           the change is for.
 
 The lengths: 1 (below the recurrence's order), 257 (a chunk and a tap), 16385 (one workgroup's span and a tap), 32769 (129
 chunks: the carry's runs are two chunks long), 40000 (three workgroups, 157 chunks).
 
 The fixture is recorded by this module run as a program, in a process of its own, with MCCONV_LIB naming the library to record:
-    MCCONV_LIB=<the earlier build> python tests/test_gpu_chunk_walk_bits.py <output.json>
+    MCCONV_LIB=<the build to record> python tests/test_gpu_chunk_walk_bits.py <output.json>
+which writes every case under "sha256"; a digest that has to change moves by hand into a key of its own that names the commit.
 The test itself never records and never skips."""
 import hashlib
 import json
@@ -86,7 +97,10 @@ def digests():
 
 def test_the_bits_are_those_before_the_shared_walk(gpu_lib):
     with open(GOLDEN) as fh:
-        want = json.load(fh)["sha256"]
+        fixture = json.load(fh)
+    want, again = fixture["sha256"], fixture["sha256_extended_carry"]["digests"]
+    assert sorted(again) == ["damp3_eq_16385", "damp3_eq_40000", "decay_40000"] and not set(again) & set(want)
+    want = dict(want, **again)
     got = digests()
     assert sorted(got) == sorted(want)
     differ = [k for k in sorted(want) if got[k] != want[k]]

@@ -3,8 +3,8 @@ applied to the taps the engine stores (Convolution.ir_taps), and against closed 
 
 Tolerances (ir_decay_np.check_against): 1e-6 relative for energy, times, D50 and Ts, 1e-6 dB for C50, C80 and the curve, NaN where
 and only where the restatement has NaN.  The chunked recurrence of the bands is within 1.4e-9 relative RMS of the sequential one
-at worst and non-negative double sums over at most 4 M terms add 1e-9 at most; the margin over both is
-test_gpu_ir_eq.py's.  Every comparison asserts first that no level of the restatement lies within 1e-9 dB of an edge of a fit
+at this module's lengths (test_gpu_ir_long_carry.py has a 10 Hz band over 523 264 taps) and non-negative double sums
+over at most 4 M terms add 1e-9 at most; the margin over both is test_gpu_ir_eq.py's.  Every comparison asserts first that no level of the restatement lies within 1e-9 dB of an edge of a fit
 range (assert_margins)."""
 import functools
 import math
