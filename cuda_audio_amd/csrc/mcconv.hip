@@ -34,6 +34,7 @@
 #include "irsynth.hip.h"
 #include "irsweep.hip.h"
 #include "irfloor.hip.h"
+#include "irdensity.hip.h"
 #include "irtail.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
@@ -3897,6 +3898,44 @@ int mc_ir_tail_from_floor(const mc_floor_query* q, const double* rows, const uin
     if (!tail) return fail(MC_ERR_ARG, "null tail");
     if (tail->struct_size != sizeof(mc_ir_tail)) return fail(MC_ERR_ARG, "mc_ir_tail struct_size mismatch");
     flr_to_tail(*q, rows, info, first, tail);
+    return MC_OK;
+}
+
+void mc_default_density_query(mc_density_query* q) {
+    if (!q) return;
+    std::memset(q, 0, sizeof(*q));
+    q->struct_size = (uint32_t)sizeof(*q);
+    q->rate = 44100;
+    q->onset_db = -20.f;
+    q->threshold = 1.f;
+}
+
+int mc_ir_density(mc_engine* e, uint64_t idx, const mc_density_query* q, double* rows, double* profile, uint64_t info[3]) {
+    // the query, the pointers, the index and the work bounds are checked in this order before any HIP call
+    if (const char* bad = den_check(q)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!e) return fail(MC_ERR_ARG, "null engine");
+    if (!rows) return fail(MC_ERR_ARG, "null rows");
+    if (!info) return fail(MC_ERR_ARG, "null info");
+    if (e->sf) return fail(MC_ERR_STATE, "the single-transform form keeps no taps");
+    if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h || !e->irs[idx].taps) return fail(MC_ERR_ARG, "IR not loaded");
+    if (const char* bad = den_check_work(*q, e->irs[idx].taps)) return fail(MC_ERR_ARG, "%s", bad);
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = drain_post(e);  // (as mc_ir_decay: the stream must be idle and out of the JACK path before the kernels go onto it)
+    if (!rc) rc = leave_jack_path(e);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const hipError_t er = den_measure(e->stream, e->irs[idx].d_h, e->irs[idx].taps, *q, rows, profile, info);
+    if (er != hipSuccess) return fail(MC_ERR_HIP, "density measurement failed: %s", hipGetErrorString(er));
+    return MC_OK;
+}
+
+int mc_ir_tail_move_knee(mc_ir_tail* tail, uint32_t band, uint64_t frame) {
+    if (!tail) return fail(MC_ERR_ARG, "null tail");
+    if (tail->struct_size != sizeof(mc_ir_tail)) return fail(MC_ERR_ARG, "mc_ir_tail struct_size mismatch");
+    if (tail->n_xovers > 3 || band > tail->n_xovers) return fail(MC_ERR_ARG, "band %u above n_xovers %u", band, tail->n_xovers);
+    if (tail->knee[band] == FLR_LEFT_ALONE) return fail(MC_ERR_ARG, "band %u has no knee to move (it is left alone)", band);
+    if (tail->mode != MC_TAIL_EXTEND) return fail(MC_ERR_ARG, "mode %u is not MC_TAIL_EXTEND: only an extended tail has levels to slide", tail->mode);
+    den_move_knee(tail, band, frame);
     return MC_OK;
 }
 

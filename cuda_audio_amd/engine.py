@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McFloorQuery, McIrDamp, McIrEq, McIrRoom, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIrDamp, McIrEq, McIrRoom, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -196,6 +196,42 @@ class FloorQuery:
 
 
 @dataclasses.dataclass
+class DensityQuery:
+    """How ir_density measures a loaded IR's echo density (mc_density_query, include/mcconv.h has the definition): a raised-cosine
+    window of 2 half + 1 taps (0: 20 ms in all) every hop taps (0: a quarter of half); time zero and `end` as in DecayQuery;
+    the mixing time is where the density first reaches `threshold`; decay_t60 (taps per 60 dB, 0: off) is the decay undone
+    inside each window, ir_decay's t30 times the rate."""
+
+    rate: int = 44100
+    half: int = 0
+    hop: int = 0
+    onset_db: float = -20.0
+    threshold: float = 1.0
+    end: int = 0
+    decay_t60: int = 0
+
+    def to_c(self):
+        q = McDensityQuery()
+        _lib.load().mc_default_density_query(C.byref(q))
+        q.rate, q.half, q.hop, q.end, q.decay_t60 = int(self.rate), int(self.half), int(self.hop), int(self.end), int(self.decay_t60)
+        q.onset_db, q.threshold = float(self.onset_db), float(self.threshold)
+        return q
+
+
+def density_of_occupancy(p):
+    """The normalised echo density of IrSynth's late field where its occupancy is p, 0 < p <= 1:
+    p erfc(sqrt(p / 2)) / erfc(1 / sqrt 2).
+
+    A frame of the late field sounds with probability p and is then a Gaussian g scaled by 1 / sqrt p, so the field's
+    variance is p (1 / p) = 1 whatever p is and sigma = 1.  A sounding frame exceeds sigma exactly when |g| / sqrt p > 1, that is
+    |g| > sqrt p, which a Gaussian does with probability erfc(sqrt(p / 2)); a silent frame never does.  The share of frames
+    beyond sigma is therefore p erfc(sqrt(p / 2)), and the density divides it by the Gaussian share erfc(1 / sqrt 2): 1 at p = 1,
+    0.158 at the floor p = 1 / 16 where a build-up starts."""
+    p = float(p)
+    return p * math.erfc(math.sqrt(p / 2.0)) / math.erfc(math.sqrt(1.0 / 2.0))  # (the same expression at p = 1: exactly 1)
+
+
+@dataclasses.dataclass
 class IrTail:
     """What prepare(tail=...) and prepare_sweep(tail=...) do to the tail of an IR before anything else sees it (mc_ir_tail,
     include/mcconv.h): mode "cut" fades every band to nothing at its knee, "extend" cross-fades it there into decaying noise,
@@ -255,6 +291,18 @@ def tail_from_floor(floor, first=0, mode="extend", fade=0, length=0, seed=0, wid
                   knee=tuple(None if t.knee[j] == _lib.MC_TAIL_LEFT_ALONE else int(t.knee[j]) for j in range(bands)),
                   t60=tuple(int(t.t60[j]) for j in range(bands)), level_db=tuple((float(t.level_db[j][0]), float(t.level_db[j][1])) for j in range(bands)),
                   fade=fade, length=length, seed=seed, width=width)
+
+
+def tail_move_knee(tail, band, frame):
+    """`tail` (an IrTail in mode "extend") with band `band`'s knee moved to `frame` and its two levels slid along the band's own
+    line, 60 dB per t60 (mc_ir_tail_move_knee, host arithmetic only): how a rendered or synthesised IR, which has no noise
+    floor, gets its knee at the mixing tap ir_density measured.  McError for a band the tail does not have or leaves alone."""
+    t = tail.to_c()
+    check(_lib.load().mc_ir_tail_move_knee(C.byref(t), int(band), int(frame)))
+    bands = t.n_xovers + 1
+    return dataclasses.replace(tail, knee=tuple(None if t.knee[j] == _lib.MC_TAIL_LEFT_ALONE else int(t.knee[j]) for j in range(bands)),
+                               t60=tuple(int(t.t60[j]) for j in range(bands)),
+                               level_db=tuple((float(t.level_db[j][0]), float(t.level_db[j][1])) for j in range(bands)))
 
 
 @dataclasses.dataclass
@@ -376,6 +424,7 @@ SWEEP_MAX_WORK = 1 << 40    # F * N
 DECAY_SETS = ("L", "R", "LR")
 DECAY_FIELDS = ("energy", "edt", "t20", "t30", "c50", "c80", "d50", "ts")
 FLOOR_FIELDS = ("energy", "noise", "knee", "t", "peak_to_noise_db", "interval", "last_change", "status")
+DENSITY_FIELDS = ("mix", "mix_s", "first", "max", "max_tap", "mean_after", "silent", "status")
 
 
 def decay_for_rt60(measured_s, target_s, rate):
@@ -762,6 +811,34 @@ class Convolution:
         check(self._L.mc_ir_floor(self._h, idx, C.byref(q), rows.ctypes.data_as(C.POINTER(C.c_double)), info))
         return dict(origin=int(info[0]), taps=int(info[1]), groups=groups, query=query,
                     rows={(g, name): dict(zip(FLOOR_FIELDS, (float(v) for v in rows[g, s]))) for g in range(groups) for s, name in enumerate(DECAY_SETS)})
+
+    def ir_density(self, idx, half=0, hop=0, onset_db=-20.0, end=0, threshold=1.0, decay_t60=0, profile=False, rate=None):
+        """The echo density of the stored taps of IR idx, measured on the device (mc_ir_density; include/mcconv.h has the
+        definition).  rate defaults to the engine's sample_rate, then to 44100.  Returns {"origin", "taps", "centres", "hop",
+        "half", "rows", "profile"}: rows maps "L" | "R" | "LR" to {mix (the mixing tap), mix_s (seconds after the origin), first
+        (the density of the first window), max, max_tap, mean_after (the mean density from the mixing tap on), silent (windows
+        without a signal), status}; status 1: the density never reached the threshold, and mix, mix_s and mean_after are NaN.
+        profile is float64 [centres, 3], window i centred on tap origin + i hop, or None."""
+        if rate is None:
+            rate = self.sample_rate or 44100
+        q = DensityQuery(rate=rate, half=half, hop=hop, onset_db=onset_db, threshold=threshold, end=end, decay_t60=decay_t60).to_c()
+        H = q.half or int(math.floor(0.01 * q.rate + 0.5))
+        step = q.hop or max(1, H // 4)
+        rows = np.empty((3, 8), np.float64)
+        prof = None
+        if profile:
+            try:
+                taps = int(self.ir_info(idx)["taps"])
+            except _lib.McError:
+                taps = 1  # (not loaded: the call below says so, after it has checked the query)
+            n = min(q.end, taps) if q.end else taps
+            prof = np.empty((max(n - 1, 0) // step + 1, 3), np.float64)
+        info = (C.c_uint64 * 3)()
+        dp = C.POINTER(C.c_double)
+        check(self._L.mc_ir_density(self._h, idx, C.byref(q), rows.ctypes.data_as(dp), prof.ctypes.data_as(dp) if prof is not None else None, info))
+        return dict(origin=int(info[0]), taps=int(info[1]), centres=int(info[2]), hop=step, half=H,
+                    rows={name: dict(zip(DENSITY_FIELDS, (float(v) for v in rows[s]))) for s, name in enumerate(DECAY_SETS)},
+                    profile=prof[:int(info[2])].copy() if prof is not None else None)
 
     def ir_tail_info(self, idx):
         """What the tail step of IR idx's load did (mc_ir_tail_info): the bands it touched, the frames that came in, the frames

@@ -51,6 +51,10 @@ void mc_default_floor_query(mc_floor_query*) __attribute__((weak));
 int mc_ir_floor(mc_engine*, uint64_t, const mc_floor_query*, double*, uint64_t*) __attribute__((weak));
 int mc_ir_tail_from_floor(const mc_floor_query*, const double*, const uint64_t*, uint64_t, mc_ir_tail*) __attribute__((weak));
 void mc_default_ir_tail(mc_ir_tail*) __attribute__((weak));
+// ... no density measurement and no knee to move
+void mc_default_density_query(mc_density_query*) __attribute__((weak));
+int mc_ir_density(mc_engine*, uint64_t, const mc_density_query*, double*, double*, uint64_t*) __attribute__((weak));
+int mc_ir_tail_move_knee(mc_ir_tail*, uint32_t, uint64_t) __attribute__((weak));
 int mc_load_ir_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
                     const mc_ir_tail*) __attribute__((weak));
 int mc_load_ir_sweep_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
@@ -430,7 +434,7 @@ void Convolution::setIrTail(const IrTail& tail) {
 
 bool Convolution::parseTail(const std::string& arg, IrTail& out, std::string& why) {
     const auto fail = [&](const std::string& w) {
-        why = w + " (cut|extend[:key=value,...] with keys fade, length, seed, width)";
+        why = w + " (cut|extend[:key=value,...] with keys fade, length, seed, width, knee)";
         return false;
     };
     const size_t colon = arg.find(':');
@@ -450,6 +454,11 @@ bool Convolution::parseTail(const std::string& arg, IrTail& out, std::string& wh
             if (item.empty() || eqs == std::string::npos || eqs == 0 || eqs + 1 == item.size()) return fail("'" + item + "' is not key=value");
             const std::string key = item.substr(0, eqs), val = item.substr(eqs + 1);
             char* end = nullptr;
+            if (key == "knee") {
+                if (val != "floor" && val != "mix") return fail("knee is floor or mix, not '" + val + "'");
+                t.kneeAtMix = val == "mix";
+                continue;
+            }
             if (key == "seed") {
                 t.seed = std::strtoull(val.c_str(), &end, 10);
                 if (*end || val[0] == '-') return fail("seed '" + val + "' is not a number >= 0");
@@ -467,6 +476,7 @@ bool Convolution::parseTail(const std::string& arg, IrTail& out, std::string& wh
                 return fail("no such key '" + key + "'");
         }
     }
+    if (t.kneeAtMix && t.mode != IrTail::Extend) return fail("knee=mix slides the levels of an extended tail: the mode must be extend");
     out = t;
     return true;
 }
@@ -541,6 +551,80 @@ void Convolution::measureTail(const PendingIr& p) {
     _tailNow.seed = _irTail.seed;
     _tailNow.width = _irTail.width;
     _tailOn = true;
+    if (!_irTail.kneeAtMix) return;
+    if (!mc_ir_tail_move_knee) {
+        Log::error("conv", "the engine cannot move a knee (mc_ir_tail_move_knee)");
+        std::exit(2);
+    }
+    const Density d = irDensity(p.idx, _densityQuery);
+    if (d.at(Decay::LR, Density::Status) != 0.0) {
+        Log::warn(name, "IR %zu tail: the echo density never reaches 1 (largest %s), the knees stay at the floor's", p.idx,
+                  places(d.at(Decay::LR, Density::Max), 3).c_str());
+        return;
+    }
+    const uint64_t mix = (uint64_t)d.at(Decay::LR, Density::Mix);
+    for (uint32_t j = 0; j <= _tailNow.n_xovers; j++)
+        if (_tailNow.knee[j] != ~0ull) check(mc_ir_tail_move_knee(&_tailNow, j, mix), "mc_ir_tail_move_knee");
+    Log::info(name, "IR %zu tail: knees moved to the mixing tap %llu", p.idx, (unsigned long long)mix);
+}
+
+void Convolution::setIrDensityReport(bool on, const DensityQuery& query) {
+    if (on && _group) {
+        Log::error("conv", "the IR density report is not available with several devices (mc_ir_density is single-engine)");
+        std::exit(2);
+    }
+    _densityReport = on;
+    _densityQuery = query;
+}
+
+bool Convolution::parseDensity(const std::string& option, const std::string& arg, DensityQuery& out, std::string& why) {
+    if (option == "--ir-density-t60" && arg == "auto") {
+        out.autoT60 = true, out.t60Seconds = 0.0;
+        return true;
+    }
+    char* end = nullptr;
+    const double v = std::strtod(arg.c_str(), &end);
+    if (arg.empty() || *end || !std::isfinite(v) || !(v > 0.0) || v > 4000.0) {
+        why = "takes a time in seconds, > 0 and at most 4000" + std::string(option == "--ir-density-t60" ? ", or auto" : "");
+        return false;
+    }
+    if (option == "--ir-density-window") out.windowSeconds = v;
+    else if (option == "--ir-density-hop") out.hopSeconds = v;
+    else out.t60Seconds = v, out.autoT60 = false;
+    return true;
+}
+
+Convolution::Density Convolution::irDensity(size_t idx, const DensityQuery& query) {
+    if (!mc_ir_density || !mc_default_density_query) {
+        Log::error("conv", "the engine has no density measurement (mc_ir_density)");
+        std::exit(2);
+    }
+    const double rate = (double)samplerate;
+    mc_density_query q;
+    mc_default_density_query(&q);
+    q.rate = (uint32_t)samplerate;
+    if (query.windowSeconds > 0.0) q.half = (uint32_t)std::min(std::floor(query.windowSeconds * rate / 2.0 + 0.5), 4294967295.0);
+    if (query.hopSeconds > 0.0) q.hop = (uint32_t)std::min(std::max(std::nearbyint(query.hopSeconds * rate), 1.0), 4294967295.0);
+    double t60 = query.t60Seconds;
+    if (query.autoT60) t60 = irDecay(idx, DecayQuery()).at(0, Decay::LR, Decay::T30);  // (NaN: nothing is undone)
+    if (t60 > 0.0) q.decay_t60 = (uint64_t)std::max(std::nearbyint(t60 * rate), 1.0);
+    Density d;
+    uint64_t info[3] = {0, 0, 0};
+    if (mc_ir_density(_engine, idx, &q, d.rows, nullptr, info) != MC_OK) {  // (a window or a hop the engine does not take: the command line's fault)
+        Log::error("conv", "IR %zu: the density cannot be measured: %s", idx, mc_last_error());
+        std::exit(2);
+    }
+    d.origin = info[0], d.taps = info[1], d.centres = info[2];
+    return d;
+}
+
+void Convolution::reportDensity(size_t idx) {
+    const Density d = irDensity(idx, _densityQuery);
+    const auto v = [&](Density::Field f, int decimals) { return places(d.at(Decay::LR, f), decimals); };
+    Log::info(name, "IR %zu density: origin %llu, mixing %s (%s s), first %s, max %s at %s, after %s, silent %s, status %d", idx,
+              (unsigned long long)d.origin, v(Density::Mix, 0).c_str(), v(Density::MixSeconds, 4).c_str(), v(Density::First, 3).c_str(),
+              v(Density::Max, 3).c_str(), v(Density::MaxTap, 0).c_str(), v(Density::MeanAfter, 3).c_str(), v(Density::Silent, 0).c_str(),
+              (int)d.at(Decay::LR, Density::Status));
 }
 
 mc_ir_synth Convolution::synthFrames(const IrSynth& y, double rate) {
@@ -983,13 +1067,14 @@ void Convolution::loadPendingIrs() {
         if (_rt60 > 0.0) aimRt60(p);
         if (_decayReport) reportDecay(p.idx);
         if (_floorReport) reportFloor(p.idx);
+        if (_densityReport) reportDensity(p.idx);
         _tailOn = false;
     }
     _pendingIrs.clear();
 }
 
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
-    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _irTail.mode != IrTail::Off) {  // (loaded by onStart(), once the client's rate is known)
+    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _irTail.mode != IrTail::Off) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
         _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth(), false, IrSweep()});
         if (idx + 1 > _nirs) _nirs = idx + 1;

@@ -240,21 +240,47 @@ public:
     void setIrFloorReport(bool on);
     // The crossovers of the floor report's bands and of the tail step's (at most 3, ascending)
     void setIrFloorXovers(const std::vector<float>& xovers);
+    // The echo density of a loaded IR and the mixing time it gives, measured by the engine from the taps it convolves with
+    // (mc_ir_density of include/mcconv.h, which has the definition; no reference equivalent).  Seconds become taps at the client's
+    // rate: the window spans 2 H + 1 taps with H = floor(windowSeconds rate / 2 + 0.5), the hop is rint(hopSeconds rate), at least
+    // 1; 0 leaves either to the engine (20 ms, a quarter of H).  t60Seconds > 0 is the decay undone inside each window; autoT60
+    // takes the broadband LR T30 of irDecay in its place and, where that is NaN, nothing.
+    struct DensityQuery {
+        double windowSeconds = 0.0, hopSeconds = 0.0, t60Seconds = 0.0;
+        bool autoT60 = false;
+    };
+    struct Density {
+        uint64_t origin = 0, taps = 0, centres = 0;
+        double rows[24];  // per channel set (L, R, LR) {mixing tap, mixing time s, eta[0], max eta, its tap, mean eta after, silent windows, status}
+        enum Field { Mix = 0, MixSeconds, First, Max, MaxTap, MeanAfter, Silent, Status };
+        double at(Decay::Set set, Field f) const { return rows[set * 8 + f]; }
+    };
+    Density irDensity(size_t idx, const DensityQuery& query);
+    // One log line per IR loaded from now on (origin, mixing tap and time, first, largest and later density, silent windows and
+    // status of the LR row).  Loaded by onStart(), single device only, as setIrDecayReport.
+    void setIrDensityReport(bool on, const DensityQuery& query);
+    // The arguments of --ir-density-window and --ir-density-hop (seconds, > 0) and of --ir-density-t60 (seconds, > 0, or auto) into
+    // `out`.  False, with the reason in `why`, for a malformed one.
+    static bool parseDensity(const std::string& option, const std::string& arg, DensityQuery& out, std::string& why);
     // The tail step every IR loaded from now on goes through (mc_ir_tail of include/mcconv.h; no reference equivalent): the IR
     // is loaded as it is, its floor is measured in the bands of setIrFloorXovers, and it is loaded again with every band cut at
     // its knee (Cut) or cross-faded there into decaying noise (Extend) ahead of its shape, EQ and damping.  An IR whose
     // broadband peak-to-noise ratio is under margin_db + span_db of the search (30 dB) is left as it is, with a log line that
     // says so, and so is a generated one without a room, which has no floor.  Seconds become frames at the client's rate by rint.  Loaded by
-    // onStart(), single device only.
+    // onStart(), single device only.  kneeAtMix (Extend only): every band the floor search placed gets its knee moved to the
+    // mixing tap irDensity measures on the same load (the LR row, setIrDensityReport's query), its levels sliding along its own line
+    // (mc_ir_tail_move_knee): the hand-over point of a rendered room, which has no floor to find.  A density that never reaches 1
+    // leaves the floor's knees and logs a warning.
     struct IrTail {
         enum Mode { Off = 0, Cut = 1, Extend = 2 } mode = Off;
         double fadeSeconds = 0.0;    // cross-fade that ends at each knee
         double lengthSeconds = 0.0;  // frames the step hands on; 0: as many as came in
         uint64_t seed = 0;
         float width = 1.0f;
+        bool kneeAtMix = false;
     };
     void setIrTail(const IrTail& tail);
-    // The argument of --ir-tail, cut|extend[:key=value,...] with keys fade, length (seconds), seed and width, as an IrTail.
+    // The argument of --ir-tail, cut|extend[:key=value,...] with keys fade, length (seconds), seed, width and knee (floor|mix), as an IrTail.
     // False, with the reason in `why`, for a malformed one.
     static bool parseTail(const std::string& arg, IrTail& out, std::string& why);
 
@@ -299,6 +325,9 @@ private:
     void aimRt60(const PendingIr& p);
     void reportDecay(size_t idx);
     void reportFloor(size_t idx);
+    void reportDensity(size_t idx);
+    bool _densityReport = false;
+    DensityQuery _densityQuery;
     void measureTail(const PendingIr& p);
     bool _floorReport = false;
     std::vector<float> _floorXovers;

@@ -36,6 +36,11 @@
 // are row groups of their own, and the bands of --ir-tail; --ir-tail cut|extend[:fade=S,length=S,seed=N,width=W]: every IR is
 // loaded, its floor measured, and loaded again with every band cut at its knee or extended from there with decaying noise,
 // ahead of the other --ir-* options, Convolution::setIrTail; an IR with less than 30 dB between peak and floor is left as it is.
+// --ir-density-report: after each IR is loaded one log line with its echo density (origin, mixing tap and time, first, largest and
+// later density of the LR row, measured by the engine: Convolution::setIrDensityReport); --ir-density-window SECONDS: the whole
+// window (20 ms without), --ir-density-hop SECONDS: between window centres (an eighth of the window without), --ir-density-t60
+// SECONDS|auto: the decay undone inside each window, auto: the measured T30.  --ir-tail's key knee=floor|mix: with mix (extend
+// only) the knees the floor search placed are moved to that mixing tap, which is where a rendered room hands over to its tail.
 #include <cassert>
 #include <cstdlib>
 #include <cstring>
@@ -66,6 +71,8 @@ int main(int argc, char** argv) {
     bool irFloorReport = false;
     std::vector<float> irFloorXovers;
     Convolution::IrTail irTail;
+    bool irDensityReport = false;
+    Convolution::DensityQuery irDensity;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--periods") && i + 1 < argc) periods = strtoull(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "--settings") && i + 1 < argc) settingsPath = argv[++i];
@@ -179,6 +186,14 @@ int main(int argc, char** argv) {
                 std::cerr << "--ir-tail '" << argv[i] << "': " << why << std::endl;
                 return 2;
             }
+        } else if (!strcmp(argv[i], "--ir-density-report")) irDensityReport = true;
+        else if ((!strcmp(argv[i], "--ir-density-window") || !strcmp(argv[i], "--ir-density-hop") || !strcmp(argv[i], "--ir-density-t60")) && i + 1 < argc) {
+            std::string why;
+            const char* option = argv[i];
+            if (!Convolution::parseDensity(option, argv[++i], irDensity, why)) {
+                std::cerr << option << " '" << argv[i] << "': " << why << std::endl;
+                return 2;
+            }
         } else if (!strcmp(argv[i], "--ir-rt60") && i + 1 < argc) {
             irRt60 = atof(argv[++i]);
             if (!(irRt60 > 0.0)) {
@@ -222,6 +237,7 @@ int main(int argc, char** argv) {
         if (irRt60 > 0.0) c->setIrRt60(irRt60);
         c->setIrFloorXovers(irFloorXovers);
         if (irFloorReport) c->setIrFloorReport(true);
+        c->setIrDensityReport(irDensityReport, irDensity);
         c->setIrTail(irTail);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;

@@ -388,6 +388,51 @@ void mc_default_floor_query(mc_floor_query *q);
  * the engine holds changes are mc_ir_decay's; two calls with the same query on the same IR return the same bits. */
 int mc_ir_floor(mc_engine *e, uint64_t idx, const mc_floor_query *q, double *rows, uint64_t info[2]);
 
+/* The echo density of a loaded IR, measured on the device: where the IR stops being separate reflections and becomes a
+ * diffuse tail (the mixing time), by Abel and Huang's normalised echo density (AES 121, 2006).  It is what mc_ir_synth's
+ * late_start and build_up, mc_ir_room.last and the knee of a tail on a rendered IR (mc_ir_tail_move_knee) are set by.  No
+ * reference equivalent; single-engine.  The stored taps are only read; N and the origin o are those of mc_ir_decay's step 1.
+ * Everything is in double.  H = half or floor(0.01 rate + 0.5); hop = the field or max(1, floor(H / 4)).
+ *   weights   h_k = (1 + cos(pi k / (H + 1))) / 2, k = -H .. H, all positive (computed on the host into a table);
+ *   centres   t_i = o + i hop, i = 0 .. I - 1, I = floor((N - 1 - o) / hop) + 1;
+ *   window i  the taps tau in [max(t_i - H, 0), min(t_i + H, N - 1)]; taps before o belong to it;
+ *   values    v_c[tau] = (double) x_c[tau] (decay_t60 ? exp2((double)((int64) tau - (int64) t_i) 3 log2(10) / decay_t60) : 1):
+ *             the decay inside the window is undone relative to its centre.  Without that a fast decay pulls the density of
+ *             a mixed field under 1 (0.97 for 60 dB over nine window lengths); mc_ir_decay's T30 times the rate is what to pass;
+ *   sums      ws = sum of h over the window, S_c = sum of h v_c^2, sigma_L = sqrt(S_L / ws), sigma_R likewise,
+ *             sigma_LR = sqrt((S_L + S_R) / (2 ws));
+ *   counts    A_L = sum of h [|v_L| > sigma_L] (strictly greater), A_R likewise,
+ *             A_LR = (sum of h [|v_L| > sigma_LR] + sum of h [|v_R| > sigma_LR]) / 2;
+ *   density   eta_s[i] = A_s / (ws 0.31731050786291415), the constant being erfc(1 / sqrt 2), the share of Gaussian noise beyond
+ *             one standard deviation: near 0 for a few isolated reflections, 1 for a fully mixed field.  A silent window
+ *             (sigma = 0) gives 0 through the strict comparison and is counted in slot 6;
+ *   profile   profile[3 i + s] = eta_s[i], i < I; entries past I are not written;
+ *   rows      from the profile in index order, i* = the first i with eta_s[i] >= threshold:
+ *             rows[8 s ..] = {mixing tap t_(i*), mixing time (t_(i*) - o) / rate seconds, eta[0], max eta, tap of the first
+ *             maximum, mean of eta over i >= i*, silent windows, status}; status 0: the threshold was reached; status 1: it
+ *             never was, and slots 0, 1 and 5 are NaN. */
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_density_query) = 48 */
+    uint32_t rate;          /* the rate the stored taps are at, [8000, 384000] */
+    uint32_t half;          /* H: the window spans 2H + 1 taps; 0 = floor(0.01 rate + 0.5) (20 ms in all); else [4, 16384] */
+    uint32_t hop;           /* taps between window centres; 0 = max(1, H / 4); else [1, 2^20] */
+    float onset_db;         /* as mc_decay_query; default -20 */
+    float threshold;        /* finite, (0, 2]; default 1 */
+    uint64_t end;           /* as mc_decay_query */
+    uint64_t decay_t60;     /* 0 = off; else the decay that is undone inside each window, in taps per 60 dB;
+                               H 3 log2(10) / decay_t60 <= 256, so that v^2 can neither overflow nor vanish */
+    uint32_t reserved[2];   /* must be 0 */
+} mc_density_query;
+/* rate 44100, half 0, hop 0, onset -20, threshold 1, end 0, decay_t60 0 */
+void mc_default_density_query(mc_density_query *q);
+/* rows: [3 * 8]; profile: [3 * Imax] with Imax = floor((N - 1) / hop) + 1, or NULL; info = {origin tap o, taps analysed N,
+ * centres I}.  Checked in this order, all before the engine or the device is touched (MC_ERR_ARG, the message names the field):
+ * the query field by field, the pointers, idx ("IR not loaded"), then the work bounds with o taken as 0: Imax <= 2^22 and
+ * Imax (2H + 1) <= 2^34 (the message names hop).  MC_ERR_STATE in the single-transform form, which keeps no taps.  Threading,
+ * stream and the promise that nothing the engine holds changes are mc_ir_decay's; two calls with the same query on the same
+ * IR return the same bits. */
+int mc_ir_density(mc_engine *e, uint64_t idx, const mc_density_query *q, double *rows, double *profile, uint64_t info[3]);
+
 /* Synthesis of an IR on the device from a seed: a room from a few numbers instead of a recorded WAV.  No reference equivalent;
  * single-engine, as shaping is.  The F = frames stereo frames are generated at the session's rate into the buffer the shaped
  * load's steps read and never exist on the host.  Frame m is a pure function of (seed, m, this struct): the same struct gives
@@ -541,6 +586,12 @@ void mc_default_ir_tail(mc_ir_tail *t);
  * A band whose L + R row has status != 0 or whose floor(tc) >= info[1] gets knee = UINT64_MAX and is left alone.  `first` is
  * mc_ir_shape_info's first kept frame when the measured load trimmed, else 0.  MC_ERR_ARG for a bad query or a null pointer. */
 int mc_ir_tail_from_floor(const mc_floor_query *q, const double *rows, const uint64_t info[2], uint64_t first, mc_ir_tail *tail);
+/* Moves band `band`'s knee to `frame` and slides both of its levels along the band's own line:
+ * level_db[band][c] += 60 ((double) old knee - (double) frame) / t60[band], in double, rounded to float once.  It is how a
+ * rendered or synthesised IR, which has no noise floor (Lundeby's knee lands near its last tap), gets its knee at the mixing
+ * time mc_ir_density measured.  Host arithmetic only.  MC_ERR_ARG for a null tail or a struct_size mismatch, a mode other than
+ * MC_TAIL_EXTEND, a band above n_xovers, or a band whose knee is UINT64_MAX (left alone by mc_ir_tail_from_floor). */
+int mc_ir_tail_move_knee(mc_ir_tail *tail, uint32_t band, uint64_t frame);
 /* mc_load_ir_damped with `tail` applied as step 1a.  With tail NULL or MC_TAIL_OFF the call is mc_load_ir_damped itself, bit for
  * bit.  With a tail on everything is checked before the engine or the device is touched (MC_ERR_ARG, the message names the
  * field, the engine stays as it was): tail field by field in the struct's order, then session_rate and ir_rate (both in [8000,
