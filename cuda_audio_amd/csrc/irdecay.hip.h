@@ -261,6 +261,58 @@ inline void dec_row(const double* pick, const double* cnt, const double (*fit)[4
     for (uint32_t j = 0; j < K; j++) curve[j] = std::max(10.0 * std::log10(pick[DEC_PICK_HEAD + j] / E), DEC_CURVE_FLOOR);
 }
 
+// workgroups of the origin's two walks over N taps
+inline unsigned dec_origin_grid(uint64_t N) { return (unsigned)std::min<uint64_t>(ISH_SCAN_GRID, (N / 2 + ISH_THREADS) / ISH_THREADS); }
+
+// *o = the origin of taps [0, N) of d_x (mc_ir_decay's step 1): the shaped load's onset search, 0 with onset_db = 0 and for taps
+// that compare false with everything.  d_part: 8 bytes per workgroup of dec_origin_grid(N).  Synchronises the stream.
+inline hipError_t dec_origin(hipStream_t stream, const float2* d_x, uint64_t N, float onset_db, void* d_part, uint64_t* o) {
+    *o = 0;
+    if (!(onset_db < 0.f)) return hipSuccess;
+    const unsigned ogrid = dec_origin_grid(N);
+    hipLaunchKernelGGL(k_shape_peak, dim3(ogrid), dim3(ISH_THREADS), 0, stream, d_x, N, (float*)d_part);
+    hipError_t er = hipGetLastError();
+    std::vector<float> pk(ogrid);
+    if (er == hipSuccess) er = hipMemcpyAsync(pk.data(), d_part, sizeof(float) * ogrid, hipMemcpyDeviceToHost, stream);
+    if (er == hipSuccess) er = hipStreamSynchronize(stream);
+    if (er != hipSuccess) return er;
+    float peak = 0.f;
+    for (float v : pk) peak = std::max(peak, v);
+    const float t = peak * (float)std::pow(10.0, (double)onset_db / 20.0);
+    hipLaunchKernelGGL(k_shape_onset, dim3(ogrid), dim3(ISH_THREADS), 0, stream, d_x, N, t, (unsigned long long*)d_part);
+    er = hipGetLastError();
+    std::vector<unsigned long long> at(ogrid);
+    if (er == hipSuccess) er = hipMemcpyAsync(at.data(), d_part, sizeof(unsigned long long) * ogrid, hipMemcpyDeviceToHost, stream);
+    if (er == hipSuccess) er = hipStreamSynchronize(stream);
+    if (er != hipSuccess) return er;
+    uint64_t onset = ISH_NONE;
+    for (unsigned long long v : at) onset = std::min<uint64_t>(onset, v);
+    *o = onset == ISH_NONE ? 0 : onset;
+    return hipSuccess;
+}
+
+// d_buf [N] = a row group's doubles (mc_ir_decay's step 2): the taps as double and, with centre_hz, run through that band's two
+// identical sections, the second riding as the `nxt` stage of the first's fix-up.  d_st: the chunk states, double2 [cg.lanes].
+inline hipError_t dec_group(hipStream_t stream, const float2* d_x, uint64_t N, const ChunkGeom& cg, const float* centre_hz, float q, uint32_t rate,
+                            double2* d_buf, double2* d_st) {
+    hipLaunchKernelGGL(k_dec_fill, dim3((unsigned)((N + ISH_THREADS - 1) / ISH_THREADS)), dim3(ISH_THREADS), 0, stream, d_x, N, d_buf);
+    hipError_t er = hipGetLastError();
+    if (!centre_hz) return er;
+    IeqStage sec{}, off{};
+    sec.c = dec_coef(*centre_hz, q, rate), sec.on = 1;
+    const IeqCarry cm = ieq_carry(sec.c, cg.K);
+    for (int pass = 0; pass < 3 && er == hipSuccess; pass++) {
+        if (pass > 0) {
+            hipLaunchKernelGGL(k_eq_carry, dim3(1), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.nchunks, cg.K, cm.M, cm.MK);
+            er = hipGetLastError();
+        }
+        if (er != hipSuccess) break;
+        hipLaunchKernelGGL(k_eq_chunk, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pass > 0 ? sec : off, pass < 2 ? sec : off, d_st);
+        er = hipGetLastError();
+    }
+    return er;
+}
+
 // The whole measurement of the n stored taps d_x for a checked query.  rows, curve, info as mc_ir_decay describes them.
 // Synchronises the stream; leaves nothing allocated.
 inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n, const mc_decay_query& q, double* rows, double* curve,
@@ -270,7 +322,7 @@ inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n,
     const unsigned grid = (unsigned)((N + ISH_THREADS - 1) / ISH_THREADS);                    // k_dec_fill
     const ChunkGeom cg = chunk_geom(N);                                                       // k_eq_chunk, k_dec_sum and the carries
     const unsigned rgrid = std::min<unsigned>(DEC_GRID, grid);                                // k_dec_members, k_dec_fit
-    const unsigned ogrid = (unsigned)std::min<uint64_t>(ISH_SCAN_GRID, (N / 2 + ISH_THREADS) / ISH_THREADS);  // the onset's walks
+    const unsigned ogrid = dec_origin_grid(N);                                                // the onset's walks
     const size_t npart = std::max<size_t>({(size_t)DEC_FIT_PART * rgrid, (size_t)2 * npick, (size_t)ogrid});
     double2 *d_buf = nullptr, *d_st = nullptr;
     double *d_tot = nullptr, *d_part = nullptr;
@@ -288,47 +340,11 @@ inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n,
 
     // origin: the shaped load's onset over the taps that are analysed
     uint64_t o = 0;
-    if (er == hipSuccess && q.onset_db < 0.f) {
-        hipLaunchKernelGGL(k_shape_peak, dim3(ogrid), dim3(ISH_THREADS), 0, stream, d_x, N, (float*)d_part);
-        launched();
-        std::vector<float> pk(ogrid);
-        if (er == hipSuccess) er = hipMemcpyAsync(pk.data(), d_part, sizeof(float) * ogrid, hipMemcpyDeviceToHost, stream);
-        if (er == hipSuccess) er = hipStreamSynchronize(stream);
-        if (er == hipSuccess) {
-            float peak = 0.f;
-            for (float v : pk) peak = std::max(peak, v);
-            const float t = peak * (float)std::pow(10.0, (double)q.onset_db / 20.0);
-            hipLaunchKernelGGL(k_shape_onset, dim3(ogrid), dim3(ISH_THREADS), 0, stream, d_x, N, t, (unsigned long long*)d_part);
-            launched();
-        }
-        std::vector<unsigned long long> at(ogrid);
-        if (er == hipSuccess) er = hipMemcpyAsync(at.data(), d_part, sizeof(unsigned long long) * ogrid, hipMemcpyDeviceToHost, stream);
-        if (er == hipSuccess) er = hipStreamSynchronize(stream);
-        if (er == hipSuccess) {
-            uint64_t onset = ISH_NONE;
-            for (unsigned long long v : at) onset = std::min<uint64_t>(onset, v);
-            o = onset == ISH_NONE ? 0 : onset;  // (taps that compare false with everything)
-        }
-    }
+    if (er == hipSuccess) er = dec_origin(stream, d_x, N, q.onset_db, d_part, &o);
     const uint64_t k50 = o + (uint64_t)std::floor(0.05 * (double)q.rate + 0.5), k80 = o + (uint64_t)std::floor(0.08 * (double)q.rate + 0.5);
 
     for (uint32_t g = 0; g <= q.n_bands && er == hipSuccess; g++) {
-        hipLaunchKernelGGL(k_dec_fill, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x, N, d_buf);
-        launched();
-        if (g > 0) {  // two identical sections: the second rides as the `nxt` stage of the first's fix-up
-            IeqStage sec{}, off{};
-            sec.c = dec_coef(q.centre_hz[g - 1], q.q, q.rate), sec.on = 1;
-            const IeqCarry cm = ieq_carry(sec.c, cg.K);
-            for (int pass = 0; pass < 3 && er == hipSuccess; pass++) {
-                if (pass > 0) {
-                    hipLaunchKernelGGL(k_eq_carry, dim3(1), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.nchunks, cg.K, cm.M, cm.MK);
-                    launched();
-                }
-                if (er != hipSuccess) break;
-                hipLaunchKernelGGL(k_eq_chunk, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pass > 0 ? sec : off, pass < 2 ? sec : off, d_st);
-                launched();
-            }
-        }
+        er = dec_group(stream, d_x, N, cg, g ? &q.centre_hz[g - 1] : nullptr, q.q, q.rate, d_buf, d_st);
         if (er == hipSuccess) {
             hipLaunchKernelGGL(k_dec_sum<false>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
             launched();

@@ -210,7 +210,7 @@ inline hipError_t den_measure(hipStream_t stream, const float2* d_x, uint64_t n,
                               uint64_t info[3]) {
     const uint64_t N = q.end ? std::min<uint64_t>(q.end, n) : n;
     const uint32_t H = den_half(q), hop = den_hop(q);
-    const unsigned ogrid = (unsigned)std::min<uint64_t>(ISH_SCAN_GRID, (N / 2 + ISH_THREADS) / ISH_THREADS);  // the onset's walks
+    const unsigned ogrid = dec_origin_grid(N);  // the onset's walks
     const uint64_t imax = (N - 1) / hop + 1;
     const std::vector<double2> tab = den_table(H, q.decay_t60);
     double2* d_tab = nullptr;
@@ -222,30 +222,8 @@ inline hipError_t den_measure(hipStream_t stream, const float2* d_x, uint64_t n,
     if (er == hipSuccess) er = hipMemcpyAsync(d_tab, tab.data(), sizeof(double2) * tab.size(), hipMemcpyHostToDevice, stream);
     const auto launched = [&] { er = hipGetLastError(); };
 
-    // origin: irdecay.hip.h's
     uint64_t o = 0;
-    if (er == hipSuccess && q.onset_db < 0.f) {
-        hipLaunchKernelGGL(k_shape_peak, dim3(ogrid), dim3(ISH_THREADS), 0, stream, d_x, N, (float*)d_part);
-        launched();
-        std::vector<float> pk(ogrid);
-        if (er == hipSuccess) er = hipMemcpyAsync(pk.data(), d_part, sizeof(float) * ogrid, hipMemcpyDeviceToHost, stream);
-        if (er == hipSuccess) er = hipStreamSynchronize(stream);
-        if (er == hipSuccess) {
-            float peak = 0.f;
-            for (float v : pk) peak = std::max(peak, v);
-            const float t = peak * (float)std::pow(10.0, (double)q.onset_db / 20.0);
-            hipLaunchKernelGGL(k_shape_onset, dim3(ogrid), dim3(ISH_THREADS), 0, stream, d_x, N, t, (unsigned long long*)d_part);
-            launched();
-        }
-        std::vector<unsigned long long> at(ogrid);
-        if (er == hipSuccess) er = hipMemcpyAsync(at.data(), d_part, sizeof(unsigned long long) * ogrid, hipMemcpyDeviceToHost, stream);
-        if (er == hipSuccess) er = hipStreamSynchronize(stream);
-        if (er == hipSuccess) {
-            uint64_t onset = ISH_NONE;
-            for (unsigned long long v : at) onset = std::min<uint64_t>(onset, v);
-            o = onset == ISH_NONE ? 0 : onset;
-        }
-    }
+    if (er == hipSuccess) er = dec_origin(stream, d_x, N, q.onset_db, d_part, &o);
 
     DenPlan pl{};
     pl.N = N, pl.o = o, pl.I = (N - 1 - o) / hop + 1, pl.H = H, pl.hop = hop, pl.C = den_run(H, hop);

@@ -35,6 +35,7 @@
 #include "irsweep.hip.h"
 #include "irfloor.hip.h"
 #include "irdensity.hip.h"
+#include "iriacc.hip.h"
 #include "irtail.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
@@ -3936,6 +3937,43 @@ int mc_ir_tail_move_knee(mc_ir_tail* tail, uint32_t band, uint64_t frame) {
     if (tail->knee[band] == FLR_LEFT_ALONE) return fail(MC_ERR_ARG, "band %u has no knee to move (it is left alone)", band);
     if (tail->mode != MC_TAIL_EXTEND) return fail(MC_ERR_ARG, "mode %u is not MC_TAIL_EXTEND: only an extended tail has levels to slide", tail->mode);
     den_move_knee(tail, band, frame);
+    return MC_OK;
+}
+
+void mc_default_iacc_query(mc_iacc_query* q) {
+    if (!q) return;
+    std::memset(q, 0, sizeof(*q));
+    q->struct_size = (uint32_t)sizeof(*q);
+    q->rate = 44100;
+    q->max_lag = 44;
+    q->q = 1.41421356f;
+    q->onset_db = -20.f;
+}
+
+int mc_ir_iacc(mc_engine* e, uint64_t idx, const mc_iacc_query* q, double* rows, double* curve, uint64_t info[3]) {
+    // the query, the pointers, the index and the work bounds are checked in this order before any HIP call
+    if (const char* bad = iacc_check(q)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!e) return fail(MC_ERR_ARG, "null engine");
+    if (!rows) return fail(MC_ERR_ARG, "null rows");
+    if (!info) return fail(MC_ERR_ARG, "null info");
+    if (e->sf) return fail(MC_ERR_STATE, "the single-transform form keeps no taps");
+    if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h || !e->irs[idx].taps) return fail(MC_ERR_ARG, "IR not loaded");
+    if (const char* bad = iacc_check_work(*q, e->irs[idx].taps)) return fail(MC_ERR_ARG, "%s", bad);
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = drain_post(e);  // (as mc_ir_decay: the stream must be idle and out of the JACK path before the kernels go onto it)
+    if (!rc) rc = leave_jack_path(e);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    const hipError_t er = iacc_measure(e->stream, e->irs[idx].d_h, e->irs[idx].taps, *q, rows, curve, info);
+    if (er != hipSuccess) return fail(MC_ERR_HIP, "IACC measurement failed: %s", hipGetErrorString(er));
+    return MC_OK;
+}
+
+int mc_ir_tail_width_from_iacc(mc_ir_tail* tail, double rho) {
+    if (!tail) return fail(MC_ERR_ARG, "null tail");
+    if (tail->struct_size != sizeof(mc_ir_tail)) return fail(MC_ERR_ARG, "mc_ir_tail struct_size mismatch");
+    if (!std::isfinite(rho)) return fail(MC_ERR_ARG, "rho %g is not finite", rho);
+    tail->width = iacc_width(rho);
     return MC_OK;
 }
 

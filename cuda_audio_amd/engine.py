@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIrDamp, McIrEq, McIrRoom, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McIrDamp, McIrEq, McIrRoom, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -305,6 +305,18 @@ def tail_move_knee(tail, band, frame):
                                level_db=tuple((float(t.level_db[j][0]), float(t.level_db[j][1])) for j in range(bands)))
 
 
+def tail_width_from_iacc(tail, iacc_or_rho):
+    """`tail` (an IrTail) with its width set to continue an IR whose late broadband IACF(0) is rho: width = min(max(1 - rho, 0), 1)
+    (mc_ir_tail_width_from_iacc, host arithmetic only).  The tail's noise is R = rho gA + sqrt(1 - rho^2) gB, whose lag-0
+    coefficient is rho exactly; a negative rho clamps to width 1, because the tail cannot be anti-correlated.  iacc_or_rho is rho
+    or what ir_iacc returned, whose row (0, "late") is then read.  McError for a rho that is not finite, which a late window
+    of status 1 gives."""
+    rho = iacc_or_rho["rows"][(0, "late")]["iacf0"] if isinstance(iacc_or_rho, dict) else iacc_or_rho
+    t = tail.to_c()
+    check(_lib.load().mc_ir_tail_width_from_iacc(C.byref(t), float(rho)))
+    return dataclasses.replace(tail, width=float(t.width))
+
+
 @dataclasses.dataclass
 class IrSynth:
     """The IR prepare_synth generates on the device (mc_ir_synth, include/mcconv.h): `frames` stereo frames at the session's
@@ -424,6 +436,8 @@ SWEEP_MAX_WORK = 1 << 40    # F * N
 DECAY_SETS = ("L", "R", "LR")
 DECAY_FIELDS = ("energy", "edt", "t20", "t30", "c50", "c80", "d50", "ts")
 FLOOR_FIELDS = ("energy", "noise", "knee", "t", "peak_to_noise_db", "interval", "last_change", "status")
+IACC_WINDOWS = ("early", "late", "all")
+IACC_FIELDS = ("energy_l", "energy_r", "iacc", "lag", "iacf", "iacf0", "level_db", "status")
 DENSITY_FIELDS = ("mix", "mix_s", "first", "max", "max_tap", "mean_after", "silent", "status")
 
 
@@ -839,6 +853,36 @@ class Convolution:
         return dict(origin=int(info[0]), taps=int(info[1]), centres=int(info[2]), hop=step, half=H,
                     rows={name: dict(zip(DENSITY_FIELDS, (float(v) for v in rows[s]))) for s, name in enumerate(DECAY_SETS)},
                     profile=prof[:int(info[2])].copy() if prof is not None else None)
+
+    def ir_iacc(self, idx, bands=(), q=None, max_lag=None, split=0, onset_db=-20.0, end=0, curve=False, rate=None):
+        """The interaural cross-correlation of the stored taps of IR idx, measured on the device (mc_ir_iacc; include/mcconv.h
+        has the definition).  rate defaults to the engine's sample_rate, then to 44100; max_lag=None is 1 ms at that rate,
+        floor(0.001 rate + 0.5) taps; split is the early window's length in taps (0: 80 ms).  Returns {"origin", "taps", "split" (the
+        first late tap), "max_lag", "rows", "curve"}: rows maps (g, "early" | "late" | "all") - group 0 is broadband, group g >= 1 is
+        bands[g - 1] - to {energy_l, energy_r, iacc, lag (tau* in taps, positive: R is late), iacf (IACF(tau*), signed), iacf0,
+        level_db (L over R), status}; status 1: an empty window or a silent channel, and all but the energies are NaN.  curve is
+        float64 [1 + len(bands), 3, 2 max_lag + 1], IACF at lags -max_lag .. max_lag, or None."""
+        if rate is None:
+            rate = self.sample_rate or 44100
+        if len(bands) > _lib.MC_DECAY_MAX_BANDS:
+            raise ValueError(f"{len(bands)} bands; at most {_lib.MC_DECAY_MAX_BANDS}")
+        c = McIaccQuery()
+        self._L.mc_default_iacc_query(C.byref(c))
+        c.rate, c.n_bands = int(rate), len(bands)
+        c.max_lag = int(math.floor(0.001 * c.rate + 0.5)) if max_lag is None else int(max_lag)
+        for k, hz in enumerate(bands):
+            c.centre_hz[k] = float(hz)
+        if q is not None:
+            c.q = float(q)
+        c.onset_db, c.end, c.split = float(onset_db), int(end), int(split)
+        groups, lags = 1 + c.n_bands, 2 * min(c.max_lag, _lib.MC_IACC_MAX_LAG) + 1  # (a max_lag above the bound: the call says so)
+        rows = np.empty((groups, 3, 8), np.float64)
+        cv = np.empty((groups, 3, lags), np.float64) if curve else None
+        info = (C.c_uint64 * 3)()
+        dp = C.POINTER(C.c_double)
+        check(self._L.mc_ir_iacc(self._h, idx, C.byref(c), rows.ctypes.data_as(dp), cv.ctypes.data_as(dp) if cv is not None else None, info))
+        return dict(origin=int(info[0]), taps=int(info[1]), split=int(info[2]), max_lag=int(c.max_lag), curve=cv,
+                    rows={(g, name): dict(zip(IACC_FIELDS, (float(v) for v in rows[g, w]))) for g in range(groups) for w, name in enumerate(IACC_WINDOWS)})
 
     def ir_tail_info(self, idx):
         """What the tail step of IR idx's load did (mc_ir_tail_info): the bands it touched, the frames that came in, the frames

@@ -55,6 +55,10 @@ void mc_default_ir_tail(mc_ir_tail*) __attribute__((weak));
 void mc_default_density_query(mc_density_query*) __attribute__((weak));
 int mc_ir_density(mc_engine*, uint64_t, const mc_density_query*, double*, double*, uint64_t*) __attribute__((weak));
 int mc_ir_tail_move_knee(mc_ir_tail*, uint32_t, uint64_t) __attribute__((weak));
+// ... no IACC measurement and no width to take from it
+void mc_default_iacc_query(mc_iacc_query*) __attribute__((weak));
+int mc_ir_iacc(mc_engine*, uint64_t, const mc_iacc_query*, double*, double*, uint64_t*) __attribute__((weak));
+int mc_ir_tail_width_from_iacc(mc_ir_tail*, double) __attribute__((weak));
 int mc_load_ir_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
                     const mc_ir_tail*) __attribute__((weak));
 int mc_load_ir_sweep_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
@@ -464,6 +468,10 @@ bool Convolution::parseTail(const std::string& arg, IrTail& out, std::string& wh
                 if (*end || val[0] == '-') return fail("seed '" + val + "' is not a number >= 0");
                 continue;
             }
+            if (key == "width" && val == "iacc") {
+                t.widthFromIacc = true;
+                continue;
+            }
             const double v = std::strtod(val.c_str(), &end);
             if (*end || !std::isfinite(v)) return fail("'" + val + "' of " + key + " is not a number");
             if (key == "fade" || key == "length") {
@@ -472,11 +480,13 @@ bool Convolution::parseTail(const std::string& arg, IrTail& out, std::string& wh
             } else if (key == "width") {
                 if (v < 0.0 || v > 1.0) return fail("width " + val + " outside [0, 1]");
                 t.width = (float)v;
+                t.widthFromIacc = false;
             } else
                 return fail("no such key '" + key + "'");
         }
     }
     if (t.kneeAtMix && t.mode != IrTail::Extend) return fail("knee=mix slides the levels of an extended tail: the mode must be extend");
+    if (t.widthFromIacc && t.mode != IrTail::Extend) return fail("width=iacc is the width of an extended tail's noise: the mode must be extend");
     out = t;
     return true;
 }
@@ -551,6 +561,23 @@ void Convolution::measureTail(const PendingIr& p) {
     _tailNow.seed = _irTail.seed;
     _tailNow.width = _irTail.width;
     _tailOn = true;
+    if (_irTail.widthFromIacc) {
+        if (!mc_ir_tail_width_from_iacc) {
+            Log::error("conv", "the engine cannot take a width from an IACC (mc_ir_tail_width_from_iacc)");
+            std::exit(2);
+        }
+        IaccQuery broadband = _iaccQuery;  // (the lag of the command line; the width is read from the broadband group alone)
+        broadband.bands.clear();
+        const Iacc a = irIacc(p.idx, broadband);
+        const double rho = a.at(0, Iacc::Late, Iacc::Iacf0);
+        if (a.at(0, Iacc::Late, Iacc::Status) != 0.0)
+            Log::warn(name, "IR %zu tail: the late window from tap %llu has no correlation to read (status 1), the width stays %.9g", p.idx,
+                      (unsigned long long)a.split, (double)_tailNow.width);
+        else {
+            check(mc_ir_tail_width_from_iacc(&_tailNow, rho), "mc_ir_tail_width_from_iacc");
+            Log::info(name, "IR %zu tail: width %.9g from the late IACF(0) %.9f", p.idx, (double)_tailNow.width, rho);
+        }
+    }
     if (!_irTail.kneeAtMix) return;
     if (!mc_ir_tail_move_knee) {
         Log::error("conv", "the engine cannot move a knee (mc_ir_tail_move_knee)");
@@ -625,6 +652,78 @@ void Convolution::reportDensity(size_t idx) {
               (unsigned long long)d.origin, v(Density::Mix, 0).c_str(), v(Density::MixSeconds, 4).c_str(), v(Density::First, 3).c_str(),
               v(Density::Max, 3).c_str(), v(Density::MaxTap, 0).c_str(), v(Density::MeanAfter, 3).c_str(), v(Density::Silent, 0).c_str(),
               (int)d.at(Decay::LR, Density::Status));
+}
+
+void Convolution::setIrIaccReport(bool on, const IaccQuery& query) {
+    if (on && _group) {
+        Log::error("conv", "the IR IACC report is not available with several devices (mc_ir_iacc is single-engine)");
+        std::exit(2);
+    }
+    _iaccReport = on;
+    _iaccQuery = query;
+}
+
+bool Convolution::parseIacc(const std::string& option, const std::string& arg, IaccQuery& out, std::string& why) {
+    char* end = nullptr;
+    if (option == "--ir-iacc-lag") {
+        const double v = std::strtod(arg.c_str(), &end);
+        if (arg.empty() || *end || !std::isfinite(v) || v < 0.0 || v > 1.0) {
+            why = "takes a time in seconds, >= 0 and at most 1";
+            return false;
+        }
+        out.lagSeconds = v, out.lagGiven = true;
+        return true;
+    }
+    std::vector<float> bands;
+    for (const char* a = arg.c_str();; a = end + 1) {
+        const float hz = std::strtof(a, &end);
+        if (end == a || (*end && *end != ',') || !std::isfinite(hz) || !(hz > 0.f) || bands.size() >= MC_DECAY_MAX_BANDS) {
+            why = "takes HZ[,HZ...], each > 0, at most 10";
+            return false;
+        }
+        bands.push_back(hz);
+        if (!*end) break;
+    }
+    out.bands = bands;
+    return true;
+}
+
+Convolution::Iacc Convolution::irIacc(size_t idx, const IaccQuery& query) {
+    if (!mc_ir_iacc || !mc_default_iacc_query) {
+        Log::error("conv", "the engine has no IACC measurement (mc_ir_iacc)");
+        std::exit(2);
+    }
+    const double rate = (double)samplerate;
+    mc_iacc_query q;
+    mc_default_iacc_query(&q);
+    q.rate = (uint32_t)samplerate;
+    q.max_lag = (uint32_t)std::floor((query.lagGiven ? query.lagSeconds : 0.001) * rate + 0.5);
+    q.n_bands = (uint32_t)query.bands.size();
+    for (size_t k = 0; k < query.bands.size(); k++) q.centre_hz[k] = query.bands[k];
+    Iacc a;
+    a.rows.resize((1 + query.bands.size()) * 3 * 8);
+    uint64_t info[3] = {0, 0, 0};
+    if (mc_ir_iacc(_engine, idx, &q, a.rows.data(), nullptr, info) != MC_OK) {  // (a lag or a band the engine does not take: the command line's fault)
+        Log::error("conv", "IR %zu: the IACC cannot be measured: %s", idx, mc_last_error());
+        std::exit(2);
+    }
+    a.origin = info[0], a.taps = info[1], a.split = info[2], a.maxLag = q.max_lag;
+    return a;
+}
+
+void Convolution::reportIacc(size_t idx) {
+    static const char* const window[3] = {"early", "late", "all"};
+    const Iacc a = irIacc(idx, _iaccQuery);
+    for (size_t g = 0; g <= _iaccQuery.bands.size(); g++)
+        for (int w = 0; w < 3; w++) {
+            if (g && w != Iacc::All) continue;  // (a band: the whole IR only)
+            char head[64] = "";
+            if (g) std::snprintf(head, sizeof(head), " band %g Hz", (double)_iaccQuery.bands[g - 1]);
+            const auto v = [&](Iacc::Field f, int decimals, double scale = 1.0) { return places(scale * a.at(g, (Iacc::Window)w, f), decimals); };
+            Log::info(name, "IR %zu%s iacc %s: origin %llu, IACC %s at %s taps (%s ms), IACF(0) %s, level %s dB, status %d", idx, head, window[w],
+                      (unsigned long long)a.origin, v(Iacc::Peak, 4).c_str(), v(Iacc::Lag, 0).c_str(), v(Iacc::Lag, 3, 1000.0 / (double)samplerate).c_str(),
+                      v(Iacc::Iacf0, 4).c_str(), v(Iacc::LevelDb, 2).c_str(), (int)a.at(g, (Iacc::Window)w, Iacc::Status));
+        }
 }
 
 mc_ir_synth Convolution::synthFrames(const IrSynth& y, double rate) {
@@ -1068,13 +1167,14 @@ void Convolution::loadPendingIrs() {
         if (_decayReport) reportDecay(p.idx);
         if (_floorReport) reportFloor(p.idx);
         if (_densityReport) reportDensity(p.idx);
+        if (_iaccReport) reportIacc(p.idx);
         _tailOn = false;
     }
     _pendingIrs.clear();
 }
 
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
-    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _irTail.mode != IrTail::Off) {  // (loaded by onStart(), once the client's rate is known)
+    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _irTail.mode != IrTail::Off) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
         _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth(), false, IrSweep()});
         if (idx + 1 > _nirs) _nirs = idx + 1;

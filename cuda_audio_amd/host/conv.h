@@ -262,6 +262,30 @@ public:
     // The arguments of --ir-density-window and --ir-density-hop (seconds, > 0) and of --ir-density-t60 (seconds, > 0, or auto) into
     // `out`.  False, with the reason in `why`, for a malformed one.
     static bool parseDensity(const std::string& option, const std::string& arg, DensityQuery& out, std::string& why);
+    // The interaural cross-correlation of a loaded IR, measured by the engine from the taps it convolves with (mc_ir_iacc of
+    // include/mcconv.h, which has the definition; no reference equivalent): IACF over lags of +/- lagSeconds (1 ms unless given;
+    // floor(lagSeconds rate + 0.5) taps at the client's rate) and its largest magnitude, over the early (80 ms), the late and the whole
+    // IR, broadband and in one row group per band.
+    struct IaccQuery {
+        std::vector<float> bands;
+        double lagSeconds = 0.0;
+        bool lagGiven = false;
+    };
+    struct Iacc {
+        uint64_t origin = 0, taps = 0, split = 0;  // split: the first late tap
+        uint32_t maxLag = 0;
+        std::vector<double> rows;  // per group and window {E_L, E_R, IACC, tau* taps, IACF(tau*), IACF(0), L over R dB, status}
+        enum Window { Early = 0, Late, All };
+        enum Field { EnergyL = 0, EnergyR, Peak, Lag, AtLag, Iacf0, LevelDb, Status };
+        double at(size_t group, Window w, Field f) const { return rows[(group * 3 + w) * 8 + f]; }
+    };
+    Iacc irIacc(size_t idx, const IaccQuery& query);
+    // One log line per IR loaded from now on and window of the broadband group, and one per band for the whole IR (origin, IACC,
+    // tau* in taps and ms, IACF(0), level difference, status).  Loaded by onStart(), single device only, as setIrDecayReport.
+    void setIrIaccReport(bool on, const IaccQuery& query);
+    // The argument of --ir-iacc-lag (seconds, [0, 1]) or of --ir-iacc-bands (HZ[,HZ...], at most 10) into `out`.  False, with the
+    // reason in `why`, for a malformed one.
+    static bool parseIacc(const std::string& option, const std::string& arg, IaccQuery& out, std::string& why);
     // The tail step every IR loaded from now on goes through (mc_ir_tail of include/mcconv.h; no reference equivalent): the IR
     // is loaded as it is, its floor is measured in the bands of setIrFloorXovers, and it is loaded again with every band cut at
     // its knee (Cut) or cross-faded there into decaying noise (Extend) ahead of its shape, EQ and damping.  An IR whose
@@ -270,7 +294,10 @@ public:
     // onStart(), single device only.  kneeAtMix (Extend only): every band the floor search placed gets its knee moved to the
     // mixing tap irDensity measures on the same load (the LR row, setIrDensityReport's query), its levels sliding along its own line
     // (mc_ir_tail_move_knee): the hand-over point of a rendered room, which has no floor to find.  A density that never reaches 1
-    // leaves the floor's knees and logs a warning.
+    // leaves the floor's knees and logs a warning.  widthFromIacc (Extend only; width=iacc): the noise's width comes from the
+    // late broadband IACF(0) that irIacc measures on the same load (setIrIaccReport's lag), 1 - rho clamped to [0, 1]
+    // (mc_ir_tail_width_from_iacc), so that the tail is as correlated as the field it continues; a late window without a
+    // correlation (status 1) leaves `width` and logs a warning.
     struct IrTail {
         enum Mode { Off = 0, Cut = 1, Extend = 2 } mode = Off;
         double fadeSeconds = 0.0;    // cross-fade that ends at each knee
@@ -278,9 +305,10 @@ public:
         uint64_t seed = 0;
         float width = 1.0f;
         bool kneeAtMix = false;
+        bool widthFromIacc = false;
     };
     void setIrTail(const IrTail& tail);
-    // The argument of --ir-tail, cut|extend[:key=value,...] with keys fade, length (seconds), seed, width and knee (floor|mix), as an IrTail.
+    // The argument of --ir-tail, cut|extend[:key=value,...] with keys fade, length (seconds), seed, width (a number or iacc) and knee (floor|mix), as an IrTail.
     // False, with the reason in `why`, for a malformed one.
     static bool parseTail(const std::string& arg, IrTail& out, std::string& why);
 
@@ -326,6 +354,9 @@ private:
     void reportDecay(size_t idx);
     void reportFloor(size_t idx);
     void reportDensity(size_t idx);
+    void reportIacc(size_t idx);
+    bool _iaccReport = false;
+    IaccQuery _iaccQuery;
     bool _densityReport = false;
     DensityQuery _densityQuery;
     void measureTail(const PendingIr& p);

@@ -41,6 +41,10 @@
 // window (20 ms without), --ir-density-hop SECONDS: between window centres (an eighth of the window without), --ir-density-t60
 // SECONDS|auto: the decay undone inside each window, auto: the measured T30.  --ir-tail's key knee=floor|mix: with mix (extend
 // only) the knees the floor search placed are moved to that mixing tap, which is where a rendered room hands over to its tail.
+// --ir-iacc-report: after each IR is loaded one log line per window (early, late, all) with its interaural cross-correlation
+// (origin, IACC, its lag in taps and ms, IACF(0), level difference, status; measured by the engine: Convolution::setIrIaccReport);
+// --ir-iacc-bands HZ[,HZ...]: one more line per band for the whole IR; --ir-iacc-lag SECONDS: the largest lag (1 ms without).
+// --ir-tail's key width=iacc (extend only): the tail's width is 1 - the late broadband IACF(0) measured on the same load.
 #include <cassert>
 #include <cstdlib>
 #include <cstring>
@@ -73,6 +77,8 @@ int main(int argc, char** argv) {
     Convolution::IrTail irTail;
     bool irDensityReport = false;
     Convolution::DensityQuery irDensity;
+    bool irIaccReport = false;
+    Convolution::IaccQuery irIacc;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--periods") && i + 1 < argc) periods = strtoull(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "--settings") && i + 1 < argc) settingsPath = argv[++i];
@@ -194,6 +200,14 @@ int main(int argc, char** argv) {
                 std::cerr << option << " '" << argv[i] << "': " << why << std::endl;
                 return 2;
             }
+        } else if (!strcmp(argv[i], "--ir-iacc-report")) irIaccReport = true;
+        else if ((!strcmp(argv[i], "--ir-iacc-lag") || !strcmp(argv[i], "--ir-iacc-bands")) && i + 1 < argc) {
+            std::string why;
+            const char* option = argv[i];
+            if (!Convolution::parseIacc(option, argv[++i], irIacc, why)) {
+                std::cerr << option << " '" << argv[i] << "': " << why << std::endl;
+                return 2;
+            }
         } else if (!strcmp(argv[i], "--ir-rt60") && i + 1 < argc) {
             irRt60 = atof(argv[++i]);
             if (!(irRt60 > 0.0)) {
@@ -238,6 +252,7 @@ int main(int argc, char** argv) {
         c->setIrFloorXovers(irFloorXovers);
         if (irFloorReport) c->setIrFloorReport(true);
         c->setIrDensityReport(irDensityReport, irDensity);
+        c->setIrIaccReport(irIaccReport, irIacc);
         c->setIrTail(irTail);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;

@@ -433,6 +433,52 @@ void mc_default_density_query(mc_density_query *q);
  * IR return the same bits. */
 int mc_ir_density(mc_engine *e, uint64_t idx, const mc_density_query *q, double *rows, double *profile, uint64_t info[3]);
 
+/* The interaural cross-correlation of a loaded IR, measured on the device (ISO 3382-1 Annex A): how alike the two channels
+ * are, and at which lag.  It is the one readout of the relation between L and R: what mc_ir_synth.width and mc_ir_tail.width are
+ * set by (mc_ir_tail_width_from_iacc), what tells how mc_ir_room.spacing came out, and what shows a swapped, delayed or
+ * polarity-flipped channel of a captured pair.  No reference equivalent; single-engine.  The stored taps are only read.
+ * Everything is in double.
+ *   1. N and the origin o are those of mc_ir_decay's step 1; the row groups are those of its step 2: group 0 broadband,
+ *      groups 1 .. n_bands the same two-section band-pass from rest at tap 0.  y_L and y_R are the group's doubles;
+ *   2. windows: k = min(o + (split ? split : floor(0.08 rate + 0.5)), N); w = 0, 1, 2 are early [o, k), late [k, N), all [o, N);
+ *   3. lags tau = -T .. T, T = max_lag (0 .. MC_IACC_MAX_LAG; 1 ms is floor(0.001 rate + 0.5));
+ *   4. over a window [a, b): C_w(tau) = sum of y_L[m] y_R[m + tau] over the m with both m and m + tau inside [a, b);
+ *      E_L,w = sum of y_L[m]^2 over [a, b), E_R,w likewise.  Both taps of a pair stay inside the window: C_w(tau) is then the
+ *      inner product of two stretches of the window's own y_L and y_R, so |C_w(tau)| <= sqrt(E_L,w E_R,w) by Cauchy-Schwarz and
+ *      |IACF| never exceeds 1, and the early figure holds nothing of the late field.  (A sum that let m + tau leave the window
+ *      could exceed 1 for a short early window in front of a loud tail.);
+ *   5. IACF_w(tau) = C_w(tau) / sqrt(E_L,w E_R,w); IACC_w = max over tau of |IACF_w(tau)|; tau* = the first lag, ascending
+ *      from -T, that attains it.  A positive tau* means R is late: the sound came from the left;
+ *   6. rows[(3 g + w) 8 ..] = {E_L, E_R, IACC, tau* (taps, signed), IACF(tau*) (signed: a negative value is a polarity flip),
+ *      IACF(0), 10 log10(E_L / E_R) dB, status}.  Status 0: measured.  Status 1: the window is empty or E_L E_R = 0; slots 0, 1
+ *      and 7 are set and the rest are NaN;
+ *   7. curve[((3 g + w) (2T + 1)) + (tau + T)] = IACF_w(tau); a status-1 row's curve is NaN;
+ *   8. info = {o, N, k}. */
+#define MC_IACC_MAX_LAG 1024
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_iacc_query) = 88 */
+    uint32_t rate;          /* the rate the stored taps are at, [8000, 384000] */
+    uint32_t n_bands;       /* as mc_decay_query */
+    uint32_t max_lag;       /* T, 0 .. MC_IACC_MAX_LAG taps */
+    float centre_hz[MC_DECAY_MAX_BANDS]; /* as mc_decay_query */
+    float q;                /* as mc_decay_query */
+    float onset_db;         /* as mc_decay_query; default -20 */
+    uint64_t end;           /* as mc_decay_query */
+    uint64_t split;         /* taps from the origin to the late window; 0 = floor(0.08 rate + 0.5) (80 ms) */
+    uint32_t reserved[2];   /* must be 0 */
+} mc_iacc_query;
+/* rate 44100, no bands, max_lag 44 (1 ms at that rate: set it again with the rate), q sqrt 2, onset -20, end 0, split 0 */
+void mc_default_iacc_query(mc_iacc_query *q);
+/* rows: [(1 + n_bands) * 3 * 8]; curve: [(1 + n_bands) * 3 * (2 max_lag + 1)] or NULL; info = {origin tap o, taps analysed N,
+ * first late tap k}.  Checked in this order, all before the engine or the device is touched (MC_ERR_ARG, the message names the
+ * field): the query (struct_size, rate, n_bands, max_lag, each used centre_hz, q, onset_db, reserved), the pointers, idx ("IR
+ * not loaded"), then the work bounds: the lag products (1 + n_bands) N (2 max_lag + 1) <= 2^40, and the partial sums
+ * 3 ceil(N / 2304) (2 max_lag + 3) <= 2^23 doubles (64 MiB of scratch; at max_lag 1024 that is 3.1 million taps, 65 s at 48 kHz); the message
+ * names max_lag.  MC_ERR_STATE in the single-transform form, which keeps no taps.  Threading, stream and the promise that nothing
+ * the engine holds changes are mc_ir_decay's; scratch is allocated by the call and freed before it returns; two calls with the
+ * same query on the same IR return the same bits. */
+int mc_ir_iacc(mc_engine *e, uint64_t idx, const mc_iacc_query *q, double *rows, double *curve, uint64_t info[3]);
+
 /* Synthesis of an IR on the device from a seed: a room from a few numbers instead of a recorded WAV.  No reference equivalent;
  * single-engine, as shaping is.  The F = frames stereo frames are generated at the session's rate into the buffer the shaped
  * load's steps read and never exist on the host.  Frame m is a pure function of (seed, m, this struct): the same struct gives
@@ -592,6 +638,13 @@ int mc_ir_tail_from_floor(const mc_floor_query *q, const double *rows, const uin
  * time mc_ir_density measured.  Host arithmetic only.  MC_ERR_ARG for a null tail or a struct_size mismatch, a mode other than
  * MC_TAIL_EXTEND, a band above n_xovers, or a band whose knee is UINT64_MAX (left alone by mc_ir_tail_from_floor). */
 int mc_ir_tail_move_knee(mc_ir_tail *tail, uint32_t band, uint64_t frame);
+/* Sets tail->width = (float) min(max(1 - rho, 0), 1): the width that continues an IR whose late broadband IACF(0)
+ * (mc_ir_iacc's rows[(3 * 0 + 1) * 8 + 5]) is rho.  The tail's noise is v_R = rho gA + sqrt(1 - rho^2) gB with gA and gB independent
+ * of unit variance, so its lag-0 coefficient E[v_L v_R] / sqrt(E[v_L^2] E[v_R^2]) = rho / sqrt(rho^2 + 1 - rho^2) is rho exactly:
+ * a tail of width 1 - rho is as correlated as the field it takes over from.  A negative rho clamps to width 1 (independent
+ * channels): the tail cannot be anti-correlated.  Host arithmetic only.  MC_ERR_ARG for a null tail, a struct_size mismatch or
+ * a rho that is not finite; the tail is then unchanged. */
+int mc_ir_tail_width_from_iacc(mc_ir_tail *tail, double rho);
 /* mc_load_ir_damped with `tail` applied as step 1a.  With tail NULL or MC_TAIL_OFF the call is mc_load_ir_damped itself, bit for
  * bit.  With a tail on everything is checked before the engine or the device is touched (MC_ERR_ARG, the message names the
  * field, the engine stays as it was): tail field by field in the struct's order, then session_rate and ir_rate (both in [8000,
