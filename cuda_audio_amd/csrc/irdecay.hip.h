@@ -194,33 +194,48 @@ __global__ __launch_bounds__(ISH_THREADS) void k_dec_fit(const double2* __restri
 }
 
 // -- host ------------------------------------------------------------------------------------------------------------
+// What the queries of the measurements (this header, irfloor, irdensity and iriacc) have in common.  The three checks write
+// their message into the caller's buffer msg [cap] and return false; true and nothing written when the field is good.
+inline bool dec_rate_ok(uint32_t rate, char* msg, size_t cap) {
+    if (rate >= DEC_MIN_RATE && rate <= DEC_MAX_RATE) return true;
+    std::snprintf(msg, cap, "rate %u outside [%u, %u]", rate, DEC_MIN_RATE, DEC_MAX_RATE);
+    return false;
+}
+inline bool dec_onset_ok(float onset_db, char* msg, size_t cap) {
+    const double on = (double)onset_db;
+    if (on >= DEC_MIN_ONSET_DB && on <= 0.0) return true;
+    std::snprintf(msg, cap, "onset_db %g outside [%g, 0]", on, DEC_MIN_ONSET_DB);
+    return false;
+}
+// the n_bands (checked) centre frequencies at a checked rate, then the Q they share
+inline bool dec_bands_ok(const float* centre_hz, uint32_t n_bands, float q, uint32_t rate, char* msg, size_t cap) {
+    const double top = IEQ_MAX_NYQ * (double)rate, qq = (double)q;
+    for (uint32_t b = 0; b < n_bands; b++) {
+        const double f = (double)centre_hz[b];
+        if (std::isfinite(f) && f >= IEQ_MIN_HZ && f <= top) continue;
+        std::snprintf(msg, cap, "centre_hz[%u] %g outside [%g, %g]", b, f, IEQ_MIN_HZ, top);
+        return false;
+    }
+    if (std::isfinite(qq) && qq >= IEQ_MIN_Q && qq <= IEQ_MAX_Q) return true;
+    std::snprintf(msg, cap, "q %g outside [%g, %g]", qq, IEQ_MIN_Q, IEQ_MAX_Q);
+    return false;
+}
+// N, the taps a query analyses of n stored ones: all of them with end = 0
+inline uint64_t dec_span(uint64_t end, uint64_t n) { return end ? std::min<uint64_t>(end, n) : n; }
+
 // Every field of a query, checked without touching an engine or HIP; the message (thread-local) names the field.  Null when it
 // is good.
 inline const char* dec_check(const mc_decay_query* q) {
     static thread_local char msg[160];
     if (!q) return "null query";
     if (q->struct_size != sizeof(mc_decay_query)) return "mc_decay_query struct_size mismatch";
-    if (q->rate < DEC_MIN_RATE || q->rate > DEC_MAX_RATE)
-        std::snprintf(msg, sizeof(msg), "rate %u outside [%u, %u]", q->rate, DEC_MIN_RATE, DEC_MAX_RATE);
-    else if (q->n_bands > MC_DECAY_MAX_BANDS)
+    if (!dec_rate_ok(q->rate, msg, sizeof(msg))) return msg;
+    if (q->n_bands > MC_DECAY_MAX_BANDS)
         std::snprintf(msg, sizeof(msg), "n_bands %u above %d", q->n_bands, MC_DECAY_MAX_BANDS);
     else if (q->curve_points == 1 || q->curve_points > MC_DECAY_MAX_CURVE)
         std::snprintf(msg, sizeof(msg), "curve_points %u is neither 0 nor in [2, %d]", q->curve_points, MC_DECAY_MAX_CURVE);
-    else {
-        const double top = IEQ_MAX_NYQ * (double)q->rate, qq = (double)q->q, on = (double)q->onset_db;
-        for (uint32_t b = 0; b < q->n_bands; b++) {
-            const double f = (double)q->centre_hz[b];
-            if (std::isfinite(f) && f >= IEQ_MIN_HZ && f <= top) continue;
-            std::snprintf(msg, sizeof(msg), "centre_hz[%u] %g outside [%g, %g]", b, f, IEQ_MIN_HZ, top);
-            return msg;
-        }
-        if (!(std::isfinite(qq) && qq >= IEQ_MIN_Q && qq <= IEQ_MAX_Q))
-            std::snprintf(msg, sizeof(msg), "q %g outside [%g, %g]", qq, IEQ_MIN_Q, IEQ_MAX_Q);
-        else if (!(on >= DEC_MIN_ONSET_DB && on <= 0.0))
-            std::snprintf(msg, sizeof(msg), "onset_db %g outside [%g, 0]", on, DEC_MIN_ONSET_DB);
-        else
-            return nullptr;
-    }
+    else if (dec_bands_ok(q->centre_hz, q->n_bands, q->q, q->rate, msg, sizeof(msg)) && dec_onset_ok(q->onset_db, msg, sizeof(msg)))
+        return nullptr;
     return msg;
 }
 
@@ -317,7 +332,7 @@ inline hipError_t dec_group(hipStream_t stream, const float2* d_x, uint64_t N, c
 // Synchronises the stream; leaves nothing allocated.
 inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n, const mc_decay_query& q, double* rows, double* curve,
                               uint64_t info[2]) {
-    const uint64_t N = q.end ? std::min<uint64_t>(q.end, n) : n;
+    const uint64_t N = dec_span(q.end, n);
     const uint32_t K = q.curve_points, npick = DEC_PICK_HEAD + K;
     const unsigned grid = (unsigned)((N + ISH_THREADS - 1) / ISH_THREADS);                    // k_dec_fill
     const ChunkGeom cg = chunk_geom(N);                                                       // k_eq_chunk, k_dec_sum and the carries

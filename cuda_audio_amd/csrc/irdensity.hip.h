@@ -135,15 +135,14 @@ inline const char* den_check(const mc_density_query* q) {
     if (!q) return "null query";
     if (q->struct_size != sizeof(mc_density_query)) return "mc_density_query struct_size mismatch";
     msg[0] = 0;
-    const double on = (double)q->onset_db, th = (double)q->threshold;
-    if (q->rate < DEC_MIN_RATE || q->rate > DEC_MAX_RATE)
-        std::snprintf(msg, sizeof(msg), "rate %u outside [%u, %u]", q->rate, DEC_MIN_RATE, DEC_MAX_RATE);
-    else if (q->half && (q->half < DEN_MIN_HALF || q->half > DEN_MAX_HALF))
+    const double th = (double)q->threshold;
+    if (!dec_rate_ok(q->rate, msg, sizeof(msg))) return msg;
+    if (q->half && (q->half < DEN_MIN_HALF || q->half > DEN_MAX_HALF))
         std::snprintf(msg, sizeof(msg), "half %u is neither 0 nor in [%u, %u]", q->half, DEN_MIN_HALF, DEN_MAX_HALF);
     else if (q->hop > DEN_MAX_HOP)
         std::snprintf(msg, sizeof(msg), "hop %u above %u", q->hop, DEN_MAX_HOP);
-    else if (!(on >= DEC_MIN_ONSET_DB && on <= 0.0))
-        std::snprintf(msg, sizeof(msg), "onset_db %g outside [%g, 0]", on, DEC_MIN_ONSET_DB);
+    else if (!dec_onset_ok(q->onset_db, msg, sizeof(msg)))
+        return msg;
     else if (!(std::isfinite(th) && th > 0.0 && th <= 2.0))
         std::snprintf(msg, sizeof(msg), "threshold %g outside (0, 2]", th);
     else if (q->decay_t60 && (double)den_half(*q) * ISH_DECAY_K / (double)q->decay_t60 > DEN_MAX_OCTAVES)
@@ -157,7 +156,7 @@ inline const char* den_check(const mc_density_query* q) {
 // The work bounds for n stored taps, with the origin taken as 0; null when they hold
 inline const char* den_check_work(const mc_density_query& q, uint64_t n) {
     static thread_local char msg[200];
-    const uint64_t N = q.end ? std::min<uint64_t>(q.end, n) : n, hop = den_hop(q), width = 2 * (uint64_t)den_half(q) + 1;
+    const uint64_t N = dec_span(q.end, n), hop = den_hop(q), width = 2 * (uint64_t)den_half(q) + 1;
     const uint64_t imax = (N - 1) / hop + 1;
     if (imax > DEN_MAX_CENTRES)
         std::snprintf(msg, sizeof(msg), "hop %llu puts %llu windows on %llu taps, above %llu", (unsigned long long)hop, (unsigned long long)imax,
@@ -208,7 +207,7 @@ inline void den_rows(const double* out, uint64_t I, int s, uint64_t o, uint32_t 
 // mc_ir_density describes them.  Synchronises the stream; leaves nothing allocated.
 inline hipError_t den_measure(hipStream_t stream, const float2* d_x, uint64_t n, const mc_density_query& q, double* rows, double* profile,
                               uint64_t info[3]) {
-    const uint64_t N = q.end ? std::min<uint64_t>(q.end, n) : n;
+    const uint64_t N = dec_span(q.end, n);
     const uint32_t H = den_half(q), hop = den_hop(q);
     const unsigned ogrid = dec_origin_grid(N);  // the onset's walks
     const uint64_t imax = (N - 1) / hop + 1;

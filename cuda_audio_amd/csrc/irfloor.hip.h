@@ -86,10 +86,9 @@ inline const char* flr_check(const mc_floor_query* q) {
     if (!q) return "null query";
     if (q->struct_size != sizeof(mc_floor_query)) return "mc_floor_query struct_size mismatch";
     msg[0] = 0;
-    const double top = IEQ_MAX_NYQ * (double)q->rate, on = (double)q->onset_db, tf = (double)q->tail_fraction;
-    if (q->rate < DEC_MIN_RATE || q->rate > DEC_MAX_RATE)
-        std::snprintf(msg, sizeof(msg), "rate %u outside [%u, %u]", q->rate, DEC_MIN_RATE, DEC_MAX_RATE);
-    else if (q->n_xovers > MC_FLOOR_MAX_XOVERS)
+    const double top = IEQ_MAX_NYQ * (double)q->rate, tf = (double)q->tail_fraction;
+    if (!dec_rate_ok(q->rate, msg, sizeof(msg))) return msg;
+    if (q->n_xovers > MC_FLOOR_MAX_XOVERS)
         std::snprintf(msg, sizeof(msg), "n_xovers %u above %d", q->n_xovers, MC_FLOOR_MAX_XOVERS);
     if (msg[0]) return msg;
     for (uint32_t k = 0; k < q->n_xovers; k++) {
@@ -101,8 +100,8 @@ inline const char* flr_check(const mc_floor_query* q) {
                           (double)q->xover_hz[k - 1]);
         if (msg[0]) return msg;
     }
-    if (!(on >= DEC_MIN_ONSET_DB && on <= 0.0))
-        std::snprintf(msg, sizeof(msg), "onset_db %g outside [%g, 0]", on, DEC_MIN_ONSET_DB);
+    if (!dec_onset_ok(q->onset_db, msg, sizeof(msg)))
+        return msg;
     else if (!(tf > 0.0 && tf <= 0.5))
         std::snprintf(msg, sizeof(msg), "tail_fraction %g outside (0, 0.5]", tf);
     else if (!(q->margin_db >= 1.f && q->margin_db <= 30.f))
@@ -269,7 +268,7 @@ inline bool flr_search(uint64_t o, uint64_t N, const mc_floor_query& q, Gather&&
 // The whole measurement of the n stored taps d_x for a checked query.  rows, info as mc_ir_floor describes them.  Synchronises
 // the stream; leaves nothing allocated.
 inline hipError_t flr_measure(hipStream_t stream, const float2* d_x, uint64_t n, const mc_floor_query& q, double* rows, uint64_t info[2]) {
-    const uint64_t N = q.end ? std::min<uint64_t>(q.end, n) : n;
+    const uint64_t N = dec_span(q.end, n);
     const int X = (int)q.n_xovers;
     const unsigned grid = (unsigned)((N + ISH_THREADS - 1) / ISH_THREADS);                    // k_dec_fill
     const ChunkGeom cg = chunk_geom(N);                                                       // the chunk passes

@@ -115,11 +115,7 @@ inline const char* iacc_check(const mc_iacc_query* q) {
     static thread_local char msg[160];
     if (!q) return "null query";
     if (q->struct_size != sizeof(mc_iacc_query)) return "mc_iacc_query struct_size mismatch";
-    const double top = IEQ_MAX_NYQ * (double)q->rate, qq = (double)q->q, on = (double)q->onset_db;
-    if (q->rate < DEC_MIN_RATE || q->rate > DEC_MAX_RATE) {
-        std::snprintf(msg, sizeof(msg), "rate %u outside [%u, %u]", q->rate, DEC_MIN_RATE, DEC_MAX_RATE);
-        return msg;
-    }
+    if (!dec_rate_ok(q->rate, msg, sizeof(msg))) return msg;
     if (q->n_bands > MC_DECAY_MAX_BANDS) {
         std::snprintf(msg, sizeof(msg), "n_bands %u above %d", q->n_bands, MC_DECAY_MAX_BANDS);
         return msg;
@@ -128,20 +124,9 @@ inline const char* iacc_check(const mc_iacc_query* q) {
         std::snprintf(msg, sizeof(msg), "max_lag %u above %d", q->max_lag, MC_IACC_MAX_LAG);
         return msg;
     }
-    for (uint32_t b = 0; b < q->n_bands; b++) {
-        const double f = (double)q->centre_hz[b];
-        if (std::isfinite(f) && f >= IEQ_MIN_HZ && f <= top) continue;
-        std::snprintf(msg, sizeof(msg), "centre_hz[%u] %g outside [%g, %g]", b, f, IEQ_MIN_HZ, top);
-        return msg;
-    }
-    if (!(std::isfinite(qq) && qq >= IEQ_MIN_Q && qq <= IEQ_MAX_Q))
-        std::snprintf(msg, sizeof(msg), "q %g outside [%g, %g]", qq, IEQ_MIN_Q, IEQ_MAX_Q);
-    else if (!(on >= DEC_MIN_ONSET_DB && on <= 0.0))
-        std::snprintf(msg, sizeof(msg), "onset_db %g outside [%g, 0]", on, DEC_MIN_ONSET_DB);
-    else if (q->reserved[0] || q->reserved[1])
-        std::snprintf(msg, sizeof(msg), "reserved {%u, %u} must be 0", q->reserved[0], q->reserved[1]);
-    else
-        return nullptr;
+    if (!dec_bands_ok(q->centre_hz, q->n_bands, q->q, q->rate, msg, sizeof(msg)) || !dec_onset_ok(q->onset_db, msg, sizeof(msg))) return msg;
+    if (!q->reserved[0] && !q->reserved[1]) return nullptr;
+    std::snprintf(msg, sizeof(msg), "reserved {%u, %u} must be 0", q->reserved[0], q->reserved[1]);
     return msg;
 }
 
@@ -151,7 +136,7 @@ inline uint64_t iacc_part(uint64_t N, uint32_t T) { return (uint64_t)IACC_WINDOW
 // The work bounds for n stored taps; null when they hold
 inline const char* iacc_check_work(const mc_iacc_query& q, uint64_t n) {
     static thread_local char msg[200];
-    const uint64_t N = q.end ? std::min<uint64_t>(q.end, n) : n, lags = 2 * (uint64_t)q.max_lag + 1, groups = 1 + (uint64_t)q.n_bands;
+    const uint64_t N = dec_span(q.end, n), lags = 2 * (uint64_t)q.max_lag + 1, groups = 1 + (uint64_t)q.n_bands;
     if (N > IACC_MAX_WORK / (groups * lags))
         std::snprintf(msg, sizeof(msg), "max_lag %u puts %llu lags on %llu taps in %llu row groups: above %llu lag products", q.max_lag,
                       (unsigned long long)lags, (unsigned long long)N, (unsigned long long)groups, (unsigned long long)IACC_MAX_WORK);
@@ -193,7 +178,7 @@ inline void iacc_row(const double* fin, uint32_t T, bool empty, double* row, dou
 // describes them.  Synchronises the stream; leaves nothing allocated.
 inline hipError_t iacc_measure(hipStream_t stream, const float2* d_x, uint64_t n, const mc_iacc_query& q, double* rows, double* curve,
                                uint64_t info[3]) {
-    const uint64_t N = q.end ? std::min<uint64_t>(q.end, n) : n;
+    const uint64_t N = dec_span(q.end, n);
     const uint32_t T = q.max_lag, lags = 2 * T + 1, slots = lags + 2;
     const ChunkGeom cg = chunk_geom(N);
     const unsigned ogrid = dec_origin_grid(N);

@@ -87,6 +87,15 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline double pan_l(double p) { return p >= 0 ? 1 - p : 1; }  // conv.cu:386
 inline double pan_r(double p) { return p <= 0 ? 1 + p : 1; }  // conv.cu:387
 
+// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info and _room_info report of an IR's last load: one entry
+// per kind, on when that load had the step or the source (a shape with something on, an eq band or damping count as a shape, and
+// so do a synthesised, a swept and a tailed load), with the numbers the getter hands out (include/mcconv.h says what they are)
+enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_ROOM, FACT_KINDS };
+struct IrFact {
+    bool on = false;
+    double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+};
+
 struct IrEntry {
     float4* d_H = nullptr;
     float4* d_Hp[3] = {nullptr, nullptr, nullptr};  // fast-FIR components of the partition sequence: 3 / 9 / 27 arrays,
@@ -105,18 +114,7 @@ struct IrEntry {
     uint64_t taps = 0;
     int P = 0;
     double sums[4] = {0, 0, 0, 0};
-    bool shaped = false;  // the last load was mc_load_ir_shaped with something on, mc_load_ir_eq with a band on or mc_load_ir_damped with damping on: shape_info is what mc_ir_shape_info reports
-    double shape_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    bool damped = false;  // the last load was mc_load_ir_damped with damping on: damp_info is what mc_ir_damp_info reports
-    double damp_info[4] = {0, 0, 0, 0};
-    bool synthesised = false;  // the last load was mc_synth_ir: synth_info is what mc_ir_synth_info reports
-    double synth_info[4] = {0, 0, 0, 0};
-    bool swept = false;  // the last load was mc_load_ir_sweep: sweep_info is what mc_ir_sweep_info reports
-    double sweep_info[4] = {0, 0, 0, 0};
-    bool tailed = false;  // the last load had a tail step on (mc_load_ir_tail, mc_load_ir_sweep_tail): tail_info is what mc_ir_tail_info reports
-    double tail_info[4] = {0, 0, 0, 0};
-    bool roomed = false;  // the last load had a room (mc_synth_ir_room): room_info is what mc_ir_room_info reports
-    double room_info[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    IrFact facts[FACT_KINDS];  // what the last load went through (note_load), for the mc_ir_*_info getters
 };
 
 }  // namespace
@@ -3330,138 +3328,145 @@ struct RoomStep {
     uint32_t kept[2];
 };
 
-// The shaped load's own stage (irshape.hip.h): all `conv` frames at the session's rate on the device, shaped into a new buffer
-// of *n <= cap taps that the caller owns.  Nothing of the engine's IRs is touched here.  syn = the device-side source beside
-// the host pointer (irsynth.hip.h): the conv frames are generated in place of a copy or a conversion; null = lr.  swp = the
-// source of mc_load_ir_sweep (irsweep.hip.h): the conv frames are deconvolved from its recording, which is uploaded to a
-// temporary buffer freed after the stage, as the weight table is.  tail = step 1a (irtail.hip.h; tail->F = conv): between the
-// source and the shaping the conv frames become tail->Fp frames in a buffer of their own.  room = the reflections added to
-// syn's frames (irroom.hip.h); its kept counts are filled in
-int shape_stage(mc_engine* e, const float* lr, uint64_t frames, uint64_t conv, uint64_t cap, const uint32_t* rs, const mc_ir_shape& sh,
-                const IeqCascade* eq, const DampPlan* damp, float2** d_taps, uint64_t* n, double sums[4], double info[8],
-                const SynPlan* syn = nullptr, const SweepSource* swp = nullptr, const TailStep* tail = nullptr, RoomStep* room = nullptr) {
+// One load as load_ir and shape_stage take it: where the frames come from, and the steps they go through on the device.  The
+// entry points fill it in by name; a null pointer is a source that is not this load's, or a step that is off.
+struct IrLoad {
+    // -- the source: `frames` frames from exactly one of lr, syn and swp
+    const float* lr = nullptr;         // host frames, interleaved (mc_load_ir and everything built on it)
+    uint64_t frames = 0;               // of lr; with syn its F, with swp its F (the frames of the IR, not of the recording)
+    const uint32_t* rs = nullptr;      // {IR rate, session rate}: lr's frames are converted on the device (resample.hip.h) before
+                                       // anything else sees them; null = they are at the session's rate (the reference)
+    const SynPlan* syn = nullptr;      // mc_synth_ir (irsynth.hip.h): the frames are generated on the device
+    RoomStep* room = nullptr;          // mc_synth_ir_room (irroom.hip.h; with syn): its reflections are added to the generated
+                                       // frames, and the kept counts are filled in
+    const SweepSource* swp = nullptr;  // mc_load_ir_sweep (irsweep.hip.h): the frames are deconvolved on the device from its recording
+    // -- the steps, in the order they run.  Any of tail, eq, damp, syn and swp needs the shape, which may have everything off
+    const TailStep* tail = nullptr;      // step 1a, between the source and the shaping (irtail.hip.h; tail->plan.F = the frames at the session's rate)
+    const mc_ir_shape* shape = nullptr;  // applied on the device after the conversion (irshape.hip.h)
+    const IeqCascade* eq = nullptr;      // the bands of mc_load_ir_eq (ireq.hip.h); with damp it may hold no band
+    const DampPlan* damp = nullptr;      // the damping of mc_load_ir_damped (irdamp.hip.h; needs eq)
+};
+
+// what the shaping stage hands back: n taps on the device that the caller owns, mc_ir_info's sums of them and mc_ir_shape_info's numbers
+struct ShapedTaps {
+    float2* d_taps = nullptr;
+    uint64_t n = 0;
+    double sums[4] = {0, 0, 0, 0}, info[8];
+};
+
+// The stream idle and out of the JACK path, before the kernels of a load or of a measurement go onto it.  (The single-transform
+// form has no post stream and parks no period.)
+int quiesce(mc_engine* e) {
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = e->sf ? MC_OK : drain_post(e);
+    if (!rc && !e->sf) rc = leave_jack_path(e);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return MC_OK;
+}
+
+// The shaped load's own stage (irshape.hip.h): all `conv` frames of ld's source at the session's rate on the device, shaped
+// into a new buffer of out->n <= cap taps.  Nothing of the engine's IRs is touched here.  A sweep's recording is uploaded to a
+// temporary buffer freed after the stage, as its weight table is; the tail step turns the conv frames into tail->plan.Fp frames
+// in a buffer of their own.
+int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, ShapedTaps* out) {
     float2 *d_x = nullptr, *d_rec = nullptr;
     double* d_u = nullptr;
     HIP_TRY(hipMalloc(&d_x, sizeof(float2) * conv));
     double unused[4];
-    hipError_t er = swp  ? swp_generate(e->stream, *swp, d_x, &d_rec, &d_u)
-                    : syn && room ? room_generate(e->stream, *syn, room->plan, d_x, room->kept)
-                    : syn ? syn_generate(e->stream, *syn, d_x)
-                    : rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, d_x, conv, unused)
-                         : hipMemcpy(d_x, lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
-    if (er == hipSuccess && tail) {
+    hipError_t er = ld.swp  ? swp_generate(e->stream, *ld.swp, d_x, &d_rec, &d_u)
+                    : ld.syn && ld.room ? room_generate(e->stream, *ld.syn, ld.room->plan, d_x, ld.room->kept)
+                    : ld.syn ? syn_generate(e->stream, *ld.syn, d_x)
+                    : ld.rs ? rs_convert(e->stream, ld.rs[0], ld.rs[1], ld.lr, ld.frames, d_x, conv, unused)
+                            : hipMemcpy(d_x, ld.lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
+    if (er == hipSuccess && ld.tail) {
         float2* d_y = nullptr;
-        er = hipMalloc(&d_y, sizeof(float2) * tail->plan.Fp);
-        if (er == hipSuccess) er = tail_run(e->stream, d_x, d_y, tail->plan, tail->extend);  // (waits for the stream: d_x is free after it)
+        er = hipMalloc(&d_y, sizeof(float2) * ld.tail->plan.Fp);
+        if (er == hipSuccess) er = tail_run(e->stream, d_x, d_y, ld.tail->plan, ld.tail->extend);  // (waits for the stream: d_x is free after it)
         if (er == hipSuccess) {
             (void)hipFree(d_x);
             d_x = d_y;
-            conv = tail->plan.Fp;
+            conv = ld.tail->plan.Fp;
         } else {
             (void)hipStreamSynchronize(e->stream);
             (void)hipFree(d_y);
         }
     }
-    if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, sh, d_taps, n, sums, info, eq, damp);
-    if (swp && er != hipSuccess) (void)hipStreamSynchronize(e->stream);  // (the correlation may still be reading them)
+    if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, *ld.shape, &out->d_taps, &out->n, out->sums, out->info, ld.eq, ld.damp);
+    if (ld.swp && er != hipSuccess) (void)hipStreamSynchronize(e->stream);  // (the correlation may still be reading them)
     (void)hipFree(d_x);
     (void)hipFree(d_rec);
     (void)hipFree(d_u);
     if (er != hipSuccess) return fail(MC_ERR_HIP, "IR shaping failed: %s", hipGetErrorString(er));
-    if (!*n) return fail(MC_ERR_ARG, "the shape leaves no frame of the IR (start %llu, %llu frames at the session's rate)",
-                         (unsigned long long)sh.start, (unsigned long long)conv);
+    if (!out->n) return fail(MC_ERR_ARG, "the shape leaves no frame of the IR (start %llu, %llu frames at the session's rate)",
+                             (unsigned long long)ld.shape->start, (unsigned long long)conv);
     return MC_OK;
 }
 
-// mc_load_ir, mc_load_ir_resampled and mc_load_ir_shaped: rs = {IR rate, session rate} converts the frames on the device
-// (resample.hip.h) before anything else sees them; null = the frames as given (the reference).  sh = a shape with something
-// on, applied on the device after the conversion (irshape.hip.h); null = none.  eq = the bands of mc_load_ir_eq that are on
-// (ireq.hip.h; with a shape, which may have everything off); null = none.  damp = the damping of mc_load_ir_damped (irdamp.hip.h;
-// with a shape and an eq, which may hold no band); null = none.  syn = the source of mc_synth_ir (irsynth.hip.h; with a shape,
-// which may have everything off, lr null, frames = its F and no rs): the frames are generated on the device; null = lr.
-// swp = the source of mc_load_ir_sweep (irsweep.hip.h; as syn, frames = its F): the frames are deconvolved on the device from
-// its recording.  tail = the tail step of mc_load_ir_tail and mc_load_ir_sweep_tail (irtail.hip.h; with a shape, which may have
-// everything off): step 1a, between the source and the shaping; null = none.  room = the room of mc_synth_ir_room
-// (irroom.hip.h; with syn): its reflections are added to the generated frames; null = none
-int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs, const mc_ir_shape* sh = nullptr,
-            const IeqCascade* eq = nullptr, const DampPlan* damp = nullptr, const SynPlan* syn = nullptr,
-            const SweepSource* swp = nullptr, const TailStep* tail = nullptr, RoomStep* room = nullptr) {
+// What the six mc_ir_*_info getters report of the load `ld` that stored `taps` taps; sinfo = the shaping stage's numbers.
+// Every kind is written, so nothing of an earlier load onto the same index stays behind.
+void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[8]) {
+    for (IrFact& f : ir.facts) f.on = false;
+    const auto put = [&ir](IrFactKind kind, std::initializer_list<double> v) {
+        ir.facts[kind].on = true;
+        std::copy(v.begin(), v.end(), ir.facts[kind].v);
+    };
+    if (ld.shape) put(FACT_SHAPE, {sinfo[0], sinfo[1], sinfo[2], sinfo[3], sinfo[4], sinfo[5], sinfo[6], sinfo[7]});
+    if (const DampPlan* d = ld.damp) {
+        int decays = 0;
+        for (int j = 0; j <= d->X; j++) decays += d->t60[j] != 0;
+        put(FACT_DAMP, {(double)d->X, (double)std::min<uint64_t>(d->origin, taps), (double)decays, 0.0});
+    }
+    if (const SynPlan* s = ld.syn) put(FACT_SYNTH, {(double)s->F, (double)s->n_early, (double)std::min<uint64_t>(s->late_start, s->F), 0.0});
+    if (const SweepSource* s = ld.swp) put(FACT_SWEEP, {(double)s->plan.N, (double)s->M, (double)s->F, (double)s->offset});
+    if (ld.tail) {
+        const TailPlan& t = ld.tail->plan;
+        put(FACT_TAIL, {(double)t.touched, (double)t.F, (double)t.Fp, (double)t.first});
+    }
+    if (ld.room) {
+        const RoomPlan& r = ld.room->plan;
+        put(FACT_ROOM, {(double)r.N, (double)ld.room->kept[0], (double)ld.room->kept[1], r.tau[0], r.tau[1], (double)r.E, (double)r.complete, 0.0});
+    }
+}
+
+// Every load: the entry points check their arguments, describe the load (IrLoad) and come here.  nframes = the period the
+// engine's n_ref was sized for.  A load without a shape is the reference's (Convolution::prepare): lr, converted first with rs.
+int load_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const IrLoad& ld) {
     // Convolution::prepare, conv.cu:207-253
-    if (!e || (!lr && !syn && !swp)) return fail(MC_ERR_ARG, "null argument");
+    const float* const lr = ld.lr;
+    const uint64_t frames = ld.frames;
+    const uint32_t* const rs = ld.rs;
+    const bool sh = ld.shape != nullptr;
+    if (!e || (!lr && !ld.syn && !ld.swp)) return fail(MC_ERR_ARG, "null argument");
     if (idx >= (uint64_t)kMaxIrs) return fail(MC_ERR_ARG, "IR index %llu >= %d", (unsigned long long)idx, kMaxIrs);
     if (nframes >= e->cfg.n_ref) return fail(MC_ERR_ARG, "nframes >= n_ref");
     if (frames == 0) return fail(MC_ERR_ARG, "empty IR");
     const uint64_t conv = rs ? rs_out_frames(rs_geom(rs[0], rs[1]), frames) : frames;  // frames at the session's rate
     HIP_TRY(hipSetDevice(e->device));
     float* d_lr = nullptr;
-    uint64_t nshaped = 0;
-    double rsum[4] = {0, 0, 0, 0}, sinfo[8];
-    const auto note_damp = [&](IrEntry& ir, uint64_t taps) {  // what mc_ir_damp_info reports of this load
-        ir.damped = damp != nullptr;
-        if (!damp) return;
-        int decays = 0;
-        for (int j = 0; j <= damp->X; j++) decays += damp->t60[j] != 0;
-        const double inf[4] = {(double)damp->X, (double)std::min<uint64_t>(damp->origin, taps), (double)decays, 0.0};
-        std::copy(inf, inf + 4, ir.damp_info);
-    };
-    const auto note_synth = [&](IrEntry& ir) {  // what mc_ir_synth_info reports of this load
-        ir.synthesised = syn != nullptr;
-        if (!syn) return;
-        const double inf[4] = {(double)syn->F, (double)syn->n_early, (double)std::min<uint64_t>(syn->late_start, syn->F), 0.0};
-        std::copy(inf, inf + 4, ir.synth_info);
-    };
-    const auto note_sweep = [&](IrEntry& ir) {  // what mc_ir_sweep_info reports of this load
-        ir.swept = swp != nullptr;
-        if (!swp) return;
-        const double inf[4] = {(double)swp->plan.N, (double)swp->M, (double)swp->F, (double)swp->offset};
-        std::copy(inf, inf + 4, ir.sweep_info);
-    };
-    const auto note_tail = [&](IrEntry& ir) {  // what mc_ir_tail_info reports of this load
-        ir.tailed = tail != nullptr;
-        if (!tail) return;
-        const double inf[4] = {(double)tail->plan.touched, (double)tail->plan.F, (double)tail->plan.Fp, (double)tail->plan.first};
-        std::copy(inf, inf + 4, ir.tail_info);
-    };
-    const auto note_room = [&](IrEntry& ir) {  // what mc_ir_room_info reports of this load
-        ir.roomed = room != nullptr;
-        if (!room) return;
-        const RoomPlan& r = room->plan;
-        const double inf[8] = {(double)r.N, (double)room->kept[0], (double)room->kept[1], r.tau[0], r.tau[1], (double)r.E, (double)r.complete, 0.0};
-        std::copy(inf, inf + 8, ir.room_info);
-    };
-    if (sh) {  // (the stream must be idle and out of the JACK path before the shaping kernels go onto it)
-        int rc = e->sf ? MC_OK : drain_post(e);
-        if (!rc && !e->sf) rc = leave_jack_path(e);
+    ShapedTaps st;  // (without a shape, st.sums takes the sums of a conversion)
+    if (sh) {
+        int rc = quiesce(e);
+        if (!rc) rc = shape_stage(e, ld, conv, e->cfg.n_ref - nframes, &st);
         if (rc) return rc;
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        rc = shape_stage(e, lr, frames, conv, e->cfg.n_ref - nframes, rs, *sh, eq, damp, reinterpret_cast<float2**>(&d_lr), &nshaped, rsum, sinfo, syn, swp, tail, room);
-        if (rc) return rc;
+        d_lr = reinterpret_cast<float*>(st.d_taps);
     }
     if (e->sf) {
-        const int rc = sf_load_ir(e, idx, lr, frames, nframes, rs, reinterpret_cast<const float2*>(d_lr), nshaped, rsum);
+        const int rc = sf_load_ir(e, idx, lr, frames, nframes, rs, st.d_taps, st.n, st.sums);
         if (sh) (void)hipFree(d_lr);
         if (rc) return rc;
-        e->irs[idx].shaped = sh != nullptr;
-        if (sh) std::memcpy(e->irs[idx].shape_info, sinfo, sizeof(sinfo));
-        note_damp(e->irs[idx], nshaped);
-        note_synth(e->irs[idx]);
-        note_sweep(e->irs[idx]);
-        note_tail(e->irs[idx]);
-        note_room(e->irs[idx]);
+        note_load(e->irs[idx], ld, st.n, st.info);
         return MC_OK;
     }
-    const uint64_t n = sh ? nshaped : std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
+    const uint64_t n = sh ? st.n : std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
     const int P = (int)((n + MC_B - 1) / MC_B);
     if (P > e->Pcap) {
         if (sh) (void)hipFree(d_lr);
         return fail(MC_ERR_ARG, "IR needs %d partitions, engine capacity is %d", P, e->Pcap);
     }
     IrEntry& ir = e->irs[idx];
-    if (!sh) {
-        int rc = drain_post(e);
-        if (!rc) rc = leave_jack_path(e);
-        if (rc) return rc;
-    }
+    if (!sh)  // (a shaped load did this before its stage)
+        if (const int rc = quiesce(e)) return rc;
     hipError_t er = hipStreamSynchronize(e->stream);
     if (er == hipSuccess && !ir.d_H) er = hipMalloc(&ir.d_H, sizeof(float4) * (size_t)MC_NB * e->Pstride);
     if (er == hipSuccess && !sh) er = hipMalloc(&d_lr, sizeof(float) * 2 * n);
@@ -3470,7 +3475,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
         return fail(MC_ERR_HIP, "IR preparation failed: %s", hipGetErrorString(er));
     }
     if (!sh)
-        er = rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, reinterpret_cast<float2*>(d_lr), n, rsum)
+        er = rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, reinterpret_cast<float2*>(d_lr), n, st.sums)
                 : hipMemcpy(d_lr, lr, sizeof(float) * 2 * n, hipMemcpyHostToDevice);
     if (er == hipSuccess) er = hipMemsetAsync(ir.d_H, 0, sizeof(float4) * (size_t)MC_NB * e->Pstride, e->stream);
     if (er == hipSuccess) {
@@ -3515,7 +3520,7 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
     }
     double s[4] = {0, 0, 0, 0};
     if (rs || sh)
-        std::memcpy(s, rsum, sizeof(s));  // (summed on the device: the converted and the shaped taps never come to the host)
+        std::memcpy(s, st.sums, sizeof(s));  // (summed on the device: the converted and the shaped taps never come to the host)
     else
         for (uint64_t m = 0; m < n; m++) {
             const double sg = (m & 1) ? -1.0 : 1.0;
@@ -3527,24 +3532,84 @@ int load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64
     std::memcpy(ir.sums, s, sizeof(s));
     ir.taps = n;
     ir.P = P;
-    ir.shaped = sh != nullptr;
-    if (sh) std::memcpy(ir.shape_info, sinfo, sizeof(sinfo));
-    note_damp(ir, n);
-    note_synth(ir);
-    note_sweep(ir);
-    note_tail(ir);
-    note_room(ir);
+    note_load(ir, ld, n, st.info);
     if ((int)idx + 1 > e->nirs) e->nirs = (int)idx + 1;
     e->spec_valid = e->dspec.valid = false;
     e->uniform_valid[0] = e->uniform_valid[1] = false;
     return MC_OK;
 }
+
+// The damp, eq and shape arguments of a load as every entry point from mc_load_ir_damped on takes them: damping is on with a
+// crossover, a null eq is the default (no band) and a null shape the default (everything off).  The cascade and the plan are
+// for the session's rate; damping needs the cascade even with no band on (ieq_finish then runs with none).
+struct IrSteps {
+    mc_ir_shape shape;
+    IeqCascade cs;
+    DampPlan pl;
+    bool on, damping;  // an eq band is on; the damping is on
+    void into(IrLoad& ld) const {
+        ld.shape = &shape;
+        ld.eq = on || damping ? &cs : nullptr;
+        ld.damp = damping ? &pl : nullptr;
+    }
+};
+
+// Checks damp if it is on, then eq, then shape, and fills *st; the message of the first check that fails, null when all pass.
+// No engine and no HIP call.  (mc_load_ir_eq and mc_load_ir_shaped do not come here: they check the eq or the shape before the
+// rates and the frames, and with nothing on they are a plainer load whose own checks then speak.)
+const char* resolve_steps(const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, uint32_t ir_rate, uint32_t session_rate,
+                          IrSteps* st) {
+    st->damping = damp && damp->n_xovers;
+    if (st->damping)
+        if (const char* bad = damp_check(damp, ir_rate, session_rate)) return bad;
+    mc_ir_eq noeq;
+    mc_default_ir_eq(&noeq);
+    if (!eq) eq = &noeq;
+    int on = 0;
+    if (const char* bad = ieq_check(eq, ir_rate, session_rate, &on)) return bad;
+    st->on = on != 0;
+    mc_default_ir_shape(&st->shape);
+    if (shape) {
+        if (const char* bad = ish_check(shape)) return bad;
+        st->shape = *shape;
+    }
+    st->cs.bands = 0;
+    st->pl = DampPlan{};
+    if (st->on || st->damping) st->cs = ieq_cascade(*eq, session_rate);
+    if (st->damping) st->pl = damp_plan(*damp, session_rate);
+    return nullptr;
+}
+
+// The six mc_ir_*_info getters: out = the first `count` numbers of what note_load kept of that kind, or MC_ERR_STATE with
+// "IR <idx> <was_not>" when the last load had none
+int ir_fact(const mc_engine* e, uint64_t idx, IrFactKind kind, int count, const char* was_not, double* out) {
+    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
+    const IrFact& f = e->irs[idx].facts[kind];
+    if (!f.on) return fail(MC_ERR_STATE, "IR %llu %s", (unsigned long long)idx, was_not);
+    std::copy(f.v, f.v + count, out);
+    return MC_OK;
+}
+
+// The stored taps of IR idx for a measurement (mc_ir_decay, mc_ir_floor, mc_ir_density, mc_ir_iacc), once the entry point has
+// checked its query and its pointers.  No HIP call: quiesce(e) comes after the entry point's checks of the work.
+int stored_taps(const mc_engine* e, uint64_t idx, const float2** d_x, uint64_t* n) {
+    if (e->sf) return fail(MC_ERR_STATE, "the single-transform form keeps no taps");
+    if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h || !e->irs[idx].taps) return fail(MC_ERR_ARG, "IR not loaded");
+    *d_x = e->irs[idx].d_h;
+    *n = e->irs[idx].taps;
+    return MC_OK;
+}
+
+// the tail step of a checked mc_ir_tail that is on, over F frames at the session's rate
+TailStep tail_step(const mc_ir_tail& tail, uint32_t rate, uint64_t F) { return TailStep{tail_plan(tail, rate, F), tail.mode == MC_TAIL_EXTEND}; }
 }  // namespace
 
 extern "C" {
 
 int mc_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes) {
-    return load_ir(e, idx, lr, frames, nframes, nullptr);
+    IrLoad ld;
+    ld.lr = lr, ld.frames = frames;
+    return load_ir(e, idx, nframes, ld);
 }
 
 int mc_load_ir_resampled(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
@@ -3555,7 +3620,9 @@ int mc_load_ir_resampled(mc_engine* e, uint64_t idx, const float* lr, uint64_t f
     if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
     if (ir_rate == session_rate) return mc_load_ir(e, idx, lr, frames, nframes);
     const uint32_t rs[2] = {ir_rate, session_rate};
-    return load_ir(e, idx, lr, frames, nframes, rs);
+    IrLoad ld;
+    ld.lr = lr, ld.frames = frames, ld.rs = rs;
+    return load_ir(e, idx, nframes, ld);
 }
 
 void mc_default_ir_shape(mc_ir_shape* s) {
@@ -3580,7 +3647,10 @@ int mc_load_ir_shaped(mc_engine* e, uint64_t idx, const float* lr, uint64_t fram
     if (ish_is_off(*shape))
         return convert ? mc_load_ir_resampled(e, idx, lr, frames, nframes, ir_rate, session_rate) : mc_load_ir(e, idx, lr, frames, nframes);
     const uint32_t rs[2] = {ir_rate, session_rate};
-    return load_ir(e, idx, lr, frames, nframes, convert && ir_rate != session_rate ? rs : nullptr, shape);
+    IrLoad ld;
+    ld.lr = lr, ld.frames = frames, ld.rs = ir_rate != session_rate ? rs : nullptr;  // (0, 0 are equal)
+    ld.shape = shape;
+    return load_ir(e, idx, nframes, ld);
 }
 
 void mc_default_ir_eq(mc_ir_eq* eq) {
@@ -3603,7 +3673,10 @@ int mc_load_ir_eq(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, 
     if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
     const IeqCascade cs = ieq_cascade(*eq, session_rate);
     const uint32_t rs[2] = {ir_rate, session_rate};
-    return load_ir(e, idx, lr, frames, nframes, ir_rate != session_rate ? rs : nullptr, shape, &cs);
+    IrLoad ld;
+    ld.lr = lr, ld.frames = frames, ld.rs = ir_rate != session_rate ? rs : nullptr;
+    ld.shape = shape, ld.eq = &cs;
+    return load_ir(e, idx, nframes, ld);
 }
 
 int mc_ir_eq_response(const mc_ir_eq* eq, uint32_t rate, const double* hz, uint32_t n, double* db) {
@@ -3630,18 +3703,14 @@ int mc_load_ir_damped(mc_engine* e, uint64_t idx, const float* lr, uint64_t fram
     if (!eq) eq = &noeq;
     if (!damp || !damp->n_xovers) return mc_load_ir_eq(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq);
     // as in mc_load_ir_eq, everything is checked before the pointers and before any HIP call
-    if (const char* bad = damp_check(damp, ir_rate, session_rate)) return fail(MC_ERR_ARG, "%s", bad);
-    int on = 0;
-    if (const char* bad = ieq_check(eq, ir_rate, session_rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
-    mc_ir_shape off;
-    mc_default_ir_shape(&off);
-    if (!shape) shape = &off;
-    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    IrSteps steps;
+    if (const char* bad = resolve_steps(shape, eq, damp, ir_rate, session_rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
     if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
-    const IeqCascade cs = ieq_cascade(*eq, session_rate);  // (no band on: ieq_finish runs with none)
-    const DampPlan pl = damp_plan(*damp, session_rate);
     const uint32_t rs[2] = {ir_rate, session_rate};
-    return load_ir(e, idx, lr, frames, nframes, ir_rate != session_rate ? rs : nullptr, shape, &cs, &pl);
+    IrLoad ld;
+    ld.lr = lr, ld.frames = frames, ld.rs = ir_rate != session_rate ? rs : nullptr;
+    steps.into(ld);
+    return load_ir(e, idx, nframes, ld);
 }
 
 void mc_default_ir_synth(mc_ir_synth* s) {
@@ -3655,26 +3724,13 @@ int mc_synth_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_synth*
                 const mc_ir_damp* damp) {
     // the struct first, then damp, eq and shape as in mc_load_ir_damped, all before the engine and before any HIP call
     if (const char* bad = syn_check(synth)) return fail(MC_ERR_ARG, "%s", bad);
-    const uint32_t rate = synth->rate;
-    const bool damping = damp && damp->n_xovers;
-    if (damping)
-        if (const char* bad = damp_check(damp, rate, rate)) return fail(MC_ERR_ARG, "%s", bad);
-    mc_ir_eq noeq;
-    mc_default_ir_eq(&noeq);
-    if (!eq) eq = &noeq;
-    int on = 0;
-    if (const char* bad = ieq_check(eq, rate, rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
-    mc_ir_shape off;
-    mc_default_ir_shape(&off);
-    if (!shape) shape = &off;
-    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    IrSteps steps;
+    if (const char* bad = resolve_steps(shape, eq, damp, synth->rate, synth->rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
     const SynPlan syn = syn_plan(*synth);
-    IeqCascade cs;
-    cs.bands = 0;
-    DampPlan pl{};
-    if (on || damping) cs = ieq_cascade(*eq, rate);
-    if (damping) pl = damp_plan(*damp, rate);
-    return load_ir(e, idx, nullptr, synth->frames, nframes, nullptr, shape, on || damping ? &cs : nullptr, damping ? &pl : nullptr, &syn);
+    IrLoad ld;
+    ld.syn = &syn, ld.frames = synth->frames;
+    steps.into(ld);
+    return load_ir(e, idx, nframes, ld);
 }
 
 void mc_default_ir_room(mc_ir_room* r) {
@@ -3706,38 +3762,22 @@ int mc_synth_ir_room(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_s
             return fail(MC_ERR_ARG, "rate %u outside [%u, %u] (the tail step needs the session's rate)", rate, RS_MIN_RATE, RS_MAX_RATE);
         if (const char* bad = tail_check_frames(tail, F)) return fail(MC_ERR_ARG, "%s", bad);
     }
-    const bool damping = damp && damp->n_xovers;
-    if (damping)
-        if (const char* bad = damp_check(damp, rate, rate)) return fail(MC_ERR_ARG, "%s", bad);
-    mc_ir_eq noeq;
-    mc_default_ir_eq(&noeq);
-    if (!eq) eq = &noeq;
-    int on = 0;
-    if (const char* bad = ieq_check(eq, rate, rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
-    mc_ir_shape off;
-    mc_default_ir_shape(&off);
-    if (!shape) shape = &off;
-    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    IrSteps steps;
+    if (const char* bad = resolve_steps(shape, eq, damp, rate, rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
     const SynPlan syn = syn_plan(*synth);
-    IeqCascade cs;
-    cs.bands = 0;
-    DampPlan pl{};
-    if (on || damping) cs = ieq_cascade(*eq, rate);
-    if (damping) pl = damp_plan(*damp, rate);
     TailStep step{};
-    if (tailed) step = TailStep{tail_plan(*tail, rate, F), tail->mode == MC_TAIL_EXTEND};
+    if (tailed) step = tail_step(*tail, rate, F);
     RoomStep rstep{};
     if (room) rstep.plan = room_plan(*room, rate, F);
-    return load_ir(e, idx, nullptr, F, nframes, nullptr, shape, on || damping ? &cs : nullptr, damping ? &pl : nullptr, &syn, nullptr,
-                   tailed ? &step : nullptr, room ? &rstep : nullptr);
+    IrLoad ld;
+    ld.syn = &syn, ld.frames = F;
+    ld.room = room ? &rstep : nullptr;
+    ld.tail = tailed ? &step : nullptr;
+    steps.into(ld);
+    return load_ir(e, idx, nframes, ld);
 }
 
-int mc_ir_room_info(const mc_engine* e, uint64_t idx, double out[8]) {
-    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
-    if (!e->irs[idx].roomed) return fail(MC_ERR_STATE, "IR %llu was not loaded with a room", (unsigned long long)idx);
-    for (int i = 0; i < 8; i++) out[i] = e->irs[idx].room_info[i];
-    return MC_OK;
-}
+int mc_ir_room_info(const mc_engine* e, uint64_t idx, double out[8]) { return ir_fact(e, idx, FACT_ROOM, 8, "was not loaded with a room", out); }
 
 int mc_ir_room_plan(const mc_ir_room* room, uint32_t rate, uint64_t frames, double out[8]) {
     if (frames < 1 || frames > SYN_MAX_FRAMES)
@@ -3748,12 +3788,7 @@ int mc_ir_room_plan(const mc_ir_room* room, uint32_t rate, uint64_t frames, doub
     return MC_OK;
 }
 
-int mc_ir_synth_info(const mc_engine* e, uint64_t idx, double out[4]) {
-    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
-    if (!e->irs[idx].synthesised) return fail(MC_ERR_STATE, "IR %llu was not synthesised", (unsigned long long)idx);
-    for (int i = 0; i < 4; i++) out[i] = e->irs[idx].synth_info[i];
-    return MC_OK;
-}
+int mc_ir_synth_info(const mc_engine* e, uint64_t idx, double out[4]) { return ir_fact(e, idx, FACT_SYNTH, 4, "was not synthesised", out); }
 
 void mc_default_sweep(mc_sweep* sw) {
     if (!sw) return;
@@ -3781,42 +3816,19 @@ int mc_load_ir_sweep(mc_engine* e, uint64_t idx, const float* lr, uint64_t frame
     // the sweep first, then the lengths, then damp, eq and shape as in mc_load_ir_damped, all before the engine and before any HIP call
     if (const char* bad = swp_check(sweep)) return fail(MC_ERR_ARG, "%s", bad);
     if (const char* bad = swp_check_load(sweep, frames, ir_frames, offset)) return fail(MC_ERR_ARG, "%s", bad);
-    const uint32_t rate = sweep->rate;
-    const bool damping = damp && damp->n_xovers;
-    if (damping)
-        if (const char* bad = damp_check(damp, rate, rate)) return fail(MC_ERR_ARG, "%s", bad);
-    mc_ir_eq noeq;
-    mc_default_ir_eq(&noeq);
-    if (!eq) eq = &noeq;
-    int on = 0;
-    if (const char* bad = ieq_check(eq, rate, rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
-    mc_ir_shape off;
-    mc_default_ir_shape(&off);
-    if (!shape) shape = &off;
-    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    IrSteps steps;
+    if (const char* bad = resolve_steps(shape, eq, damp, sweep->rate, sweep->rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
     if (!lr) return fail(MC_ERR_ARG, "null lr");
     const SweepSource src{swp_plan(*sweep), lr, frames, ir_frames, offset};
-    IeqCascade cs;
-    cs.bands = 0;
-    DampPlan pl{};
-    if (on || damping) cs = ieq_cascade(*eq, rate);
-    if (damping) pl = damp_plan(*damp, rate);
-    return load_ir(e, idx, nullptr, ir_frames, nframes, nullptr, shape, on || damping ? &cs : nullptr, damping ? &pl : nullptr, nullptr, &src);
+    IrLoad ld;
+    ld.swp = &src, ld.frames = ir_frames;
+    steps.into(ld);
+    return load_ir(e, idx, nframes, ld);
 }
 
-int mc_ir_sweep_info(const mc_engine* e, uint64_t idx, double out[4]) {
-    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
-    if (!e->irs[idx].swept) return fail(MC_ERR_STATE, "IR %llu was not loaded from a sweep", (unsigned long long)idx);
-    for (int i = 0; i < 4; i++) out[i] = e->irs[idx].sweep_info[i];
-    return MC_OK;
-}
+int mc_ir_sweep_info(const mc_engine* e, uint64_t idx, double out[4]) { return ir_fact(e, idx, FACT_SWEEP, 4, "was not loaded from a sweep", out); }
 
-int mc_ir_damp_info(const mc_engine* e, uint64_t idx, double out[4]) {
-    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
-    if (!e->irs[idx].damped) return fail(MC_ERR_STATE, "IR %llu was not loaded with damping", (unsigned long long)idx);
-    for (int i = 0; i < 4; i++) out[i] = e->irs[idx].damp_info[i];
-    return MC_OK;
-}
+int mc_ir_damp_info(const mc_engine* e, uint64_t idx, double out[4]) { return ir_fact(e, idx, FACT_DAMP, 4, "was not loaded with damping", out); }
 
 int mc_ir_damp_response(const mc_ir_damp* d, uint32_t rate, uint64_t tap, const double* hz, uint32_t n, double* db) {
     if (!d) return fail(MC_ERR_ARG, "null damp");
@@ -3848,14 +3860,11 @@ int mc_ir_decay(mc_engine* e, uint64_t idx, const mc_decay_query* q, double* row
     if (!rows) return fail(MC_ERR_ARG, "null rows");
     if (q->curve_points && !curve) return fail(MC_ERR_ARG, "null curve with curve_points %u", q->curve_points);
     if (!info) return fail(MC_ERR_ARG, "null info");
-    if (e->sf) return fail(MC_ERR_STATE, "the single-transform form keeps no taps");
-    if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h || !e->irs[idx].taps) return fail(MC_ERR_ARG, "IR not loaded");
-    HIP_TRY(hipSetDevice(e->device));
-    int rc = drain_post(e);  // (the stream must be idle and out of the JACK path before the kernels go onto it, as for a shaped load)
-    if (!rc) rc = leave_jack_path(e);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const hipError_t er = dec_measure(e->stream, e->irs[idx].d_h, e->irs[idx].taps, *q, rows, curve, info);
+    const float2* d_x;
+    uint64_t n;
+    if (const int rc = stored_taps(e, idx, &d_x, &n)) return rc;
+    if (const int rc = quiesce(e)) return rc;
+    const hipError_t er = dec_measure(e->stream, d_x, n, *q, rows, curve, info);
     if (er != hipSuccess) return fail(MC_ERR_HIP, "decay measurement failed: %s", hipGetErrorString(er));
     return MC_OK;
 }
@@ -3880,14 +3889,11 @@ int mc_ir_floor(mc_engine* e, uint64_t idx, const mc_floor_query* q, double* row
     if (!e) return fail(MC_ERR_ARG, "null engine");
     if (!rows) return fail(MC_ERR_ARG, "null rows");
     if (!info) return fail(MC_ERR_ARG, "null info");
-    if (e->sf) return fail(MC_ERR_STATE, "the single-transform form keeps no taps");
-    if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h || !e->irs[idx].taps) return fail(MC_ERR_ARG, "IR not loaded");
-    HIP_TRY(hipSetDevice(e->device));
-    int rc = drain_post(e);  // (as mc_ir_decay: the stream must be idle and out of the JACK path before the kernels go onto it)
-    if (!rc) rc = leave_jack_path(e);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const hipError_t er = flr_measure(e->stream, e->irs[idx].d_h, e->irs[idx].taps, *q, rows, info);
+    const float2* d_x;
+    uint64_t n;
+    if (const int rc = stored_taps(e, idx, &d_x, &n)) return rc;
+    if (const int rc = quiesce(e)) return rc;
+    const hipError_t er = flr_measure(e->stream, d_x, n, *q, rows, info);
     if (er != hipSuccess) return fail(MC_ERR_HIP, "floor measurement failed: %s", hipGetErrorString(er));
     return MC_OK;
 }
@@ -3917,15 +3923,12 @@ int mc_ir_density(mc_engine* e, uint64_t idx, const mc_density_query* q, double*
     if (!e) return fail(MC_ERR_ARG, "null engine");
     if (!rows) return fail(MC_ERR_ARG, "null rows");
     if (!info) return fail(MC_ERR_ARG, "null info");
-    if (e->sf) return fail(MC_ERR_STATE, "the single-transform form keeps no taps");
-    if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h || !e->irs[idx].taps) return fail(MC_ERR_ARG, "IR not loaded");
-    if (const char* bad = den_check_work(*q, e->irs[idx].taps)) return fail(MC_ERR_ARG, "%s", bad);
-    HIP_TRY(hipSetDevice(e->device));
-    int rc = drain_post(e);  // (as mc_ir_decay: the stream must be idle and out of the JACK path before the kernels go onto it)
-    if (!rc) rc = leave_jack_path(e);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const hipError_t er = den_measure(e->stream, e->irs[idx].d_h, e->irs[idx].taps, *q, rows, profile, info);
+    const float2* d_x;
+    uint64_t n;
+    if (const int rc = stored_taps(e, idx, &d_x, &n)) return rc;
+    if (const char* bad = den_check_work(*q, n)) return fail(MC_ERR_ARG, "%s", bad);
+    if (const int rc = quiesce(e)) return rc;
+    const hipError_t er = den_measure(e->stream, d_x, n, *q, rows, profile, info);
     if (er != hipSuccess) return fail(MC_ERR_HIP, "density measurement failed: %s", hipGetErrorString(er));
     return MC_OK;
 }
@@ -3956,15 +3959,12 @@ int mc_ir_iacc(mc_engine* e, uint64_t idx, const mc_iacc_query* q, double* rows,
     if (!e) return fail(MC_ERR_ARG, "null engine");
     if (!rows) return fail(MC_ERR_ARG, "null rows");
     if (!info) return fail(MC_ERR_ARG, "null info");
-    if (e->sf) return fail(MC_ERR_STATE, "the single-transform form keeps no taps");
-    if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h || !e->irs[idx].taps) return fail(MC_ERR_ARG, "IR not loaded");
-    if (const char* bad = iacc_check_work(*q, e->irs[idx].taps)) return fail(MC_ERR_ARG, "%s", bad);
-    HIP_TRY(hipSetDevice(e->device));
-    int rc = drain_post(e);  // (as mc_ir_decay: the stream must be idle and out of the JACK path before the kernels go onto it)
-    if (!rc) rc = leave_jack_path(e);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    const hipError_t er = iacc_measure(e->stream, e->irs[idx].d_h, e->irs[idx].taps, *q, rows, curve, info);
+    const float2* d_x;
+    uint64_t n;
+    if (const int rc = stored_taps(e, idx, &d_x, &n)) return rc;
+    if (const char* bad = iacc_check_work(*q, n)) return fail(MC_ERR_ARG, "%s", bad);
+    if (const int rc = quiesce(e)) return rc;
+    const hipError_t er = iacc_measure(e->stream, d_x, n, *q, rows, curve, info);
     if (er != hipSuccess) return fail(MC_ERR_HIP, "IACC measurement failed: %s", hipGetErrorString(er));
     return MC_OK;
 }
@@ -4001,26 +4001,14 @@ int mc_load_ir_tail(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames
     const uint32_t rs[2] = {ir_rate, session_rate};
     const uint64_t F = ir_rate != session_rate ? rs_out_frames(rs_geom(ir_rate, session_rate), frames) : frames;
     if (const char* bad = tail_check_frames(tail, F)) return fail(MC_ERR_ARG, "%s", bad);
-    const bool damping = damp && damp->n_xovers;
-    if (damping)
-        if (const char* bad = damp_check(damp, ir_rate, session_rate)) return fail(MC_ERR_ARG, "%s", bad);
-    mc_ir_eq noeq;
-    mc_default_ir_eq(&noeq);
-    if (!eq) eq = &noeq;
-    int on = 0;
-    if (const char* bad = ieq_check(eq, ir_rate, session_rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
-    mc_ir_shape off;
-    mc_default_ir_shape(&off);
-    if (!shape) shape = &off;
-    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
-    IeqCascade cs;
-    cs.bands = 0;
-    DampPlan pl{};
-    if (on || damping) cs = ieq_cascade(*eq, session_rate);
-    if (damping) pl = damp_plan(*damp, session_rate);
-    const TailStep step{tail_plan(*tail, session_rate, F), tail->mode == MC_TAIL_EXTEND};
-    return load_ir(e, idx, lr, frames, nframes, ir_rate != session_rate ? rs : nullptr, shape, on || damping ? &cs : nullptr, damping ? &pl : nullptr,
-                   nullptr, nullptr, &step);
+    IrSteps steps;
+    if (const char* bad = resolve_steps(shape, eq, damp, ir_rate, session_rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
+    const TailStep step = tail_step(*tail, session_rate, F);
+    IrLoad ld;
+    ld.lr = lr, ld.frames = frames, ld.rs = ir_rate != session_rate ? rs : nullptr;
+    ld.tail = &step;
+    steps.into(ld);
+    return load_ir(e, idx, nframes, ld);
 }
 
 int mc_load_ir_sweep_tail(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
@@ -4031,43 +4019,21 @@ int mc_load_ir_sweep_tail(mc_engine* e, uint64_t idx, const float* lr, uint64_t 
     if (const char* bad = swp_check(sweep)) return fail(MC_ERR_ARG, "%s", bad);
     if (const char* bad = swp_check_load(sweep, frames, ir_frames, offset)) return fail(MC_ERR_ARG, "%s", bad);
     if (const char* bad = tail_check_frames(tail, ir_frames)) return fail(MC_ERR_ARG, "%s", bad);
-    const uint32_t rate = sweep->rate;
-    const bool damping = damp && damp->n_xovers;
-    if (damping)
-        if (const char* bad = damp_check(damp, rate, rate)) return fail(MC_ERR_ARG, "%s", bad);
-    mc_ir_eq noeq;
-    mc_default_ir_eq(&noeq);
-    if (!eq) eq = &noeq;
-    int on = 0;
-    if (const char* bad = ieq_check(eq, rate, rate, &on)) return fail(MC_ERR_ARG, "%s", bad);
-    mc_ir_shape off;
-    mc_default_ir_shape(&off);
-    if (!shape) shape = &off;
-    if (const char* bad = ish_check(shape)) return fail(MC_ERR_ARG, "%s", bad);
+    IrSteps steps;
+    if (const char* bad = resolve_steps(shape, eq, damp, sweep->rate, sweep->rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
     if (!lr) return fail(MC_ERR_ARG, "null lr");
     const SweepSource src{swp_plan(*sweep), lr, frames, ir_frames, offset};
-    IeqCascade cs;
-    cs.bands = 0;
-    DampPlan pl{};
-    if (on || damping) cs = ieq_cascade(*eq, rate);
-    if (damping) pl = damp_plan(*damp, rate);
-    const TailStep step{tail_plan(*tail, rate, ir_frames), tail->mode == MC_TAIL_EXTEND};
-    return load_ir(e, idx, nullptr, ir_frames, nframes, nullptr, shape, on || damping ? &cs : nullptr, damping ? &pl : nullptr, nullptr, &src, &step);
+    const TailStep step = tail_step(*tail, sweep->rate, ir_frames);
+    IrLoad ld;
+    ld.swp = &src, ld.frames = ir_frames;
+    ld.tail = &step;
+    steps.into(ld);
+    return load_ir(e, idx, nframes, ld);
 }
 
-int mc_ir_tail_info(const mc_engine* e, uint64_t idx, double out[4]) {
-    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
-    if (!e->irs[idx].tailed) return fail(MC_ERR_STATE, "IR %llu was not loaded with a tail step", (unsigned long long)idx);
-    for (int i = 0; i < 4; i++) out[i] = e->irs[idx].tail_info[i];
-    return MC_OK;
-}
+int mc_ir_tail_info(const mc_engine* e, uint64_t idx, double out[4]) { return ir_fact(e, idx, FACT_TAIL, 4, "was not loaded with a tail step", out); }
 
-int mc_ir_shape_info(const mc_engine* e, uint64_t idx, double out[8]) {
-    if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
-    if (!e->irs[idx].shaped) return fail(MC_ERR_STATE, "IR %llu was not loaded with a shape", (unsigned long long)idx);
-    for (int i = 0; i < 8; i++) out[i] = e->irs[idx].shape_info[i];
-    return MC_OK;
-}
+int mc_ir_shape_info(const mc_engine* e, uint64_t idx, double out[8]) { return ir_fact(e, idx, FACT_SHAPE, 8, "was not loaded with a shape", out); }
 
 int mc_num_irs(const mc_engine* e) { return e ? e->nirs : 0; }
 
