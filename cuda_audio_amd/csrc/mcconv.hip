@@ -2027,8 +2027,10 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
 }
 
 // Q1/Q2 prefix sums, predelay, clamp, dry mix of the oldest batch in flight.
-// d_outL == null: the caller does not need this engine's output (a non-root
-// rank of a reduce-to-root): nothing is launched, the batch is just retired.
+// d_outL == null: the caller does not need this engine's output (a non-root rank of a reduce-to-root): the batch is retired
+// and only its Q1/Q2 prefix sums are launched (k_corr_terms / k_corr_fix, unless they rode along with the front half) - the
+// history in d_cring has no gaps, so the next batch may be finished here (with output, or a run of it) and a retired epoch
+// (k_flush_fix) reads the right sums.  No cut terms, no k_post.
 // lin_first / lin_count >= 0 (partition shards after a reduce-scatter): lin_sum holds only blocks [lin_first, lin_first +
 // lin_count) of the summed partial, [2][lin_count * 256], and only those blocks are finished (into d_outL / d_outR, which
 // start at block lin_first); the Q1/Q2 prefix sums still run over the whole batch - every shard keeps that history.
@@ -2042,28 +2044,29 @@ int run_back(mc_engine* e, const float* d_in1, const float* d_in2, const float* 
         return fail(MC_ERR_ARG, "slice [%d, %d) of the summed partial outside the batch of %d blocks (or not whole periods)", lin_first, lin_first + lin_count, T);
     e->pipe_head = (e->pipe_head + 1) % kPipe;
     e->pipe_count--;
+    const BlockParams* d_ptab = e->d_ptab + (size_t)ctx.slot * e->Tmax;
+    // Q1/Q2 prefix sums of this batch, with or without output: run_front left the block sums and the parameter table of the
+    // whole batch in the slot on every shard
+    if (!ctx.corr_done) {  // (on the headline path they rode along with the front half's launches)
+        CorrArgs ca;
+        std::memset(&ca, 0, sizeof(ca));
+        ca.sums = e->d_sums + (size_t)ctx.slot * e->Tmax;
+        ca.ptab = d_ptab;
+        ca.pstride = ctx.pstride;
+        ca.T = T;
+        ca.vs = ctx.vs;
+        ca.inv_n = 1.0 / (double)e->cfg.n_ref;
+        ca.compat = (int)e->cfg.compat;
+        ca.cring = e->d_cring;
+        ca.rc = e->rc;
+        ca.tabs0 = (int64_t)ctx.t0;
+        ca.ctot = e->d_ctot;
+        corr_chunks(&ca, T, ctx.need_a0, ctx.need_a1, ctx.need_b0);
+        hipLaunchKernelGGL(k_corr_terms, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, e->stream, ca);
+        if (ca.nchunks > 1) hipLaunchKernelGGL(k_corr_fix, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, e->stream, ca);  // a single chunk adds its base itself
+        HIP_TRY(hipGetLastError());
+    }
     if (d_outL && d_outR) {
-        const BlockParams* d_ptab = e->d_ptab + (size_t)ctx.slot * e->Tmax;
-        const float4* d_sums = e->d_sums + (size_t)ctx.slot * e->Tmax;
-        // Q1/Q2 prefix sums of this batch (only where the output is finished: a non-root shard skips them)
-        if (!ctx.corr_done) {  // (on the headline path they rode along with the front half's launches)
-            CorrArgs ca;
-            std::memset(&ca, 0, sizeof(ca));
-            ca.sums = d_sums;
-            ca.ptab = d_ptab;
-            ca.pstride = ctx.pstride;
-            ca.T = T;
-            ca.vs = ctx.vs;
-            ca.inv_n = 1.0 / (double)e->cfg.n_ref;
-            ca.compat = (int)e->cfg.compat;
-            ca.cring = e->d_cring;
-            ca.rc = e->rc;
-            ca.tabs0 = (int64_t)ctx.t0;
-            ca.ctot = e->d_ctot;
-            corr_chunks(&ca, T, ctx.need_a0, ctx.need_a1, ctx.need_b0);
-            hipLaunchKernelGGL(k_corr_terms, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, e->stream, ca);
-            if (ca.nchunks > 1) hipLaunchKernelGGL(k_corr_fix, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, e->stream, ca);  // a single chunk adds its base itself
-        }
         {
             const int rc_t = prepare_drop_fft(e, ctx.vir, ctx.predelay);
             if (rc_t != MC_OK) return rc_t;

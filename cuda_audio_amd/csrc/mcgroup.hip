@@ -141,7 +141,7 @@ int rank_back(mc_group* g, int q, float* outL, float* outR, uint64_t T, bool sca
         rc = mc_finish_batch_slice_device(k.eng, k.d_in, k.d_in + F, k.d_sum, k.d_out, k.d_out + Fs, T, first, Ts);
     else if (q == 0)
         rc = mc_finish_batch_device(k.eng, k.d_in, k.d_in + F, k.d_sum, k.d_out, k.d_out + F, T);
-    else
+    else  // retired without output; the engine still records the batch's Q1/Q2 sums, which this rank's next runs reach back to
         rc = mc_finish_batch_device(k.eng, nullptr, nullptr, nullptr, nullptr, nullptr, T);
     if (rc) return gfail(rc, "rank %d: %s", q, mc_last_error());
     if (finishes) {
@@ -163,14 +163,22 @@ int mc_group_create(const mc_config* cfg, const int32_t* devices, uint32_t ndev,
     if (!cfg || !devices || !out || ndev < 1 || ndev > 16) return gfail(MC_ERR_ARG, "bad argument (1..16 devices)");
     if (cfg->struct_size != sizeof(mc_config)) return gfail(MC_ERR_ARG, "mc_config size mismatch");
     if (cfg->form != 0 || cfg->pipeline != 0) return gfail(MC_ERR_ARG, "a group runs partitioned, unpipelined engines");
+    // all distinct (RCCL) or all equal (virtual ranks: k_group_sum reads every rank's partial, so they must live on one device)
+    uint32_t same = 0;
+    for (uint32_t a = 0; a < ndev; a++)
+        for (uint32_t b = a + 1; b < ndev; b++)
+            if (devices[a] == devices[b]) same++;
+    if (same != 0 && same != ndev * (ndev - 1) / 2) {
+        std::string list;
+        for (uint32_t a = 0; a < ndev; a++) list += (a ? ", " : "") + std::to_string(devices[a]);
+        return gfail(MC_ERR_ARG, "device list {%s} mixes repeated and distinct devices (list each device once, or one device throughout)", list.c_str());
+    }
     mc_group* g = new (std::nothrow) mc_group();
     if (!g) return gfail(MC_ERR_NOMEM, "out of host memory");
     g->cfg = *cfg;
     g->pm = (int)((cfg->period ? cfg->period : MC_BLOCK) / MC_BLOCK);
     g->r.resize(ndev);
-    for (uint32_t a = 0; a < ndev; a++)
-        for (uint32_t b = a + 1; b < ndev; b++)
-            if (devices[a] == devices[b]) g->dup = true;
+    g->dup = same != 0;
     // partition runs in multiples of 16, as cuda_audio_amd/sharded.py shard_bounds
     const uint32_t P = cfg->max_partitions ? cfg->max_partitions : (uint32_t)((cfg->n_ref - 1024 + MC_BLOCK - 1) / MC_BLOCK);
     const uint32_t total = (P + 15) / 16 * 16, per = ((total / 16 + ndev - 1) / ndev) * 16;

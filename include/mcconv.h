@@ -779,8 +779,10 @@ int mc_process_batch_slice_device(mc_engine *e, const float *d_in1, const float 
  * Up to two batches may be between their partial and their finish (finishes
  * retire batches in order), so the reduce of batch k can overlap the MAC of
  * batch k+1.  A rank that does not need the output (non-root of a reduce)
- * passes NULL for d_wet_sum, d_outL and d_outR: the batch is retired, nothing runs (such a shard keeps no
- * Q1/Q2 history, so an engine should either always or never finish with output). */
+ * passes NULL for d_wet_sum, d_outL and d_outR: the batch is retired and only its Q1/Q2 prefix sums are
+ * recorded (two small launches; d_in1 / d_in2 may be NULL too - the sums come from the partial's front half).
+ * Every shard therefore keeps the whole Q1/Q2 history, and an engine may mix the finishes from batch to batch:
+ * without output, with output, or a run of blocks (mc_finish_batch_slice_device). */
 int mc_partial_batch_device(mc_engine *e, const float *d_in1, const float *d_in2, float *d_partial, uint64_t nblocks);
 int mc_finish_batch_device(mc_engine *e, const float *d_in1, const float *d_in2, const float *d_wet_sum,
                            float *d_outL, float *d_outR, uint64_t nblocks);
@@ -790,7 +792,8 @@ int mc_finish_batch_device(mc_engine *e, const float *d_in1, const float *d_in2,
  * (count * 256 floats each).  d_in1 / d_in2 are the whole batch's inputs, as passed to mc_partial_batch_device.  Every
  * shard then keeps the Q1/Q2 history (it transforms the whole input anyway), no rank is a root, and each link carries
  * 1/N of what a reduce to one root funnels into that root.  first and count are multiples of period/256.  Retires the
- * batch like mc_finish_batch_device; an engine should use one of the two finishes throughout.  No reference
+ * batch like mc_finish_batch_device, and may alternate with it from batch to batch (a driver falls back to a reduce for a
+ * batch that does not split into equal runs).  No reference
  * equivalent (the reference runs on one device, gpu.cu:38-90). */
 int mc_finish_batch_slice_device(mc_engine *e, const float *d_in1, const float *d_in2, const float *d_wet_sum_slice,
                                  float *d_outL, float *d_outR, uint64_t nblocks, uint64_t first, uint64_t count);

@@ -19,6 +19,10 @@
  * of whole periods (every rank finishes nblocks / n blocks; each link carries 1/n of the partials), else ncclReduce to rank 0,
  * which finishes the whole batch.  Listing one device more than once (tests on a one-GPU box: "virtual ranks") replaces
  * RCCL - which refuses duplicate devices in one communicator - by a sum kernel on that device; mc_group_exchange says which.
+ * A list that is neither all distinct nor all equal (such as {0, 0, 1}) is refused with MC_ERR_ARG before any engine is created:
+ * the sum kernel of one device would read partials that live on another.
+ * The ranks that do not finish a reduced batch retire it without output (mc_finish_batch_device with NULL buffers), which still
+ * records its Q1/Q2 sums: every rank keeps the whole history, whatever mixture of batch lengths it is fed.
  * Same error convention as mcconv.h (0 / negative mc_status, message through mc_last_error of the calling thread).
  */
 #ifndef MCCONV_GROUP_H

@@ -2047,6 +2047,9 @@ def test_overlap_save_form_of_block_slices(oracle_mod, gpu_lib, monkeypatch, pd)
     assert err <= RMS_TOL, f"rms {err:.3e} (signal {rms(want):.3e})"
 
 
+_GROUP_DRIVER_ORACLE = {}
+
+
 @pytest.mark.parametrize("ranks", [1, 2, 4, -1], ids=["one", "two_virtual", "four_virtual", "one_through_rccl"])
 def test_native_group_driver(oracle_mod, gpu_lib, ranks):
     """include/mcconv_group.h (libmcconv_rccl.so): IR partitions sharded over the listed devices by a native driver - one host
@@ -2056,7 +2059,8 @@ def test_native_group_driver(oracle_mod, gpu_lib, ranks):
     for the collective, mc_group_exchange says so) - partition runs, per-rank threads, slice finishes and host copies are the
     real ones; and one device sent through partial -> ncclReduceScatter on a communicator of one -> slice finish runs the RCCL
     calls themselves (more than one rank of them has never run: no multi-GPU node has been available).  Batches that split evenly (reduce-scatter shape) and one that does not (reduce to rank 0), against the plain engine
-    and the oracle."""
+    and the oracle, over the whole run and block by block (test_gpu_group_history.py has the small cases in which the batch after
+    the ragged one is finished by ranks >= 1 inside its Q1/Q2 window; here that window lies in rank 0's run)."""
     from cuda_audio_amd.group import ConvolutionGroup
     from cuda_audio_amd.synth import make_input, make_ir
 
@@ -2095,15 +2099,26 @@ def test_native_group_driver(oracle_mod, gpu_lib, ranks):
         assert rms(got - ref) <= 1e-6
     else:
         assert 0 < rms(got - ref) <= 1e-6, rms(got - ref)
+    # ... and block by block: one block finished from a wrong history vanishes in an RMS over 5631 of them
+    from group_history_cases import block_rms
+
+    apart = block_rms(got - ref)
+    assert apart.max() <= 1e-6, f"block {int(np.argmax(apart))}: {apart.max():.3e} from the plain engine"
+    if "want" not in _GROUP_DRIVER_ORACLE:  # the whole run, the ragged batch and the one after it included; once for all rank counts
+        u = oracle_mod.Upols(n_ref, True)
+        for i, ir in enumerate(irs):
+            u.prepare(i, ir)
+        apply_params(u, p0, p1, True)
+        want = u.process(x[0], x[1])
+        u.close()
+        want.setflags(write=False)
+        _GROUP_DRIVER_ORACLE["want"] = want
+    want = _GROUP_DRIVER_ORACLE["want"]
     nchk = 1200
-    u = oracle_mod.Upols(n_ref, True)
-    for i, ir in enumerate(irs):
-        u.prepare(i, ir)
-    apply_params(u, p0, p1, True)
-    want = u.process(x[0, : nchk * 256], x[1, : nchk * 256])
-    u.close()
-    err = rms(got[:, : nchk * 256] - want)
-    assert err <= RMS_TOL, f"rms {err:.3e} (signal {rms(want):.3e})"
+    err = rms(got[:, : nchk * 256] - want[:, : nchk * 256])
+    assert err <= RMS_TOL, f"rms {err:.3e} (signal {rms(want[:, : nchk * 256]):.3e})"
+    errs = block_rms(got - want)  # (every block within the bound: so is the RMS over the whole run)
+    assert errs.max() <= RMS_TOL, f"block {int(np.argmax(errs))} of batches {sizes}: rms {errs.max():.3e}"
 
 
 def test_fused_second_level_kernel_for_any_grid(gpu_lib, monkeypatch):
