@@ -25,6 +25,7 @@ SYMBOLS = [
     "mc_default_decay_query", "mc_ir_decay", "mc_default_floor_query", "mc_ir_floor", "mc_ir_tail_from_floor",
     "mc_default_density_query", "mc_ir_density", "mc_ir_tail_move_knee",
     "mc_default_iacc_query", "mc_ir_iacc", "mc_ir_tail_width_from_iacc",
+    "mc_default_sti_query", "mc_ir_sti",
     "mc_default_ir_tail", "mc_load_ir_tail", "mc_load_ir_sweep_tail", "mc_ir_tail_info",
     "mc_default_ir_room", "mc_synth_ir_room", "mc_ir_room_info", "mc_ir_room_plan", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
@@ -249,6 +250,32 @@ class McIaccQuery(C.Structure):
     ]
 
 
+MC_STI_MAX_BANDS = 7
+MC_STI_MAX_MOD = 16
+MC_STI_SNR = 1
+
+
+class McStiQuery(C.Structure):
+    """mc_sti_query: how mc_ir_sti measures a loaded IR's speech transmission index."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("rate", C.c_uint32),
+        ("n_bands", C.c_uint32),
+        ("n_mod", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("centre_hz", C.c_float * MC_STI_MAX_BANDS),
+        ("alpha", C.c_double * MC_STI_MAX_BANDS),
+        ("beta", C.c_double * (MC_STI_MAX_BANDS - 1)),
+        ("snr_db", C.c_float * MC_STI_MAX_BANDS),
+        ("mod_hz", C.c_float * MC_STI_MAX_MOD),
+        ("q", C.c_float),
+        ("onset_db", C.c_float),
+        ("end", C.c_uint64),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 MC_TAIL_OFF, MC_TAIL_CUT, MC_TAIL_EXTEND = 0, 1, 2
 MC_TAIL_LEFT_ALONE = (1 << 64) - 1  # a knee that leaves its band alone
 
@@ -380,6 +407,9 @@ def load():
     L.mc_default_iacc_query.restype = None
     L.mc_ir_iacc.argtypes = [vp, u64, C.POINTER(McIaccQuery), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64)]
     L.mc_ir_tail_width_from_iacc.argtypes = [C.POINTER(McIrTail), C.c_double]
+    L.mc_default_sti_query.argtypes = [C.POINTER(McStiQuery)]
+    L.mc_default_sti_query.restype = None
+    L.mc_ir_sti.argtypes = [vp, u64, C.POINTER(McStiQuery), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64)]
     L.mc_default_ir_tail.argtypes = [C.POINTER(McIrTail)]
     L.mc_default_ir_tail.restype = None
     L.mc_load_ir_tail.argtypes = [vp, u64, fp, u64, u64, C.c_uint32, C.c_uint32, C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp),

@@ -194,7 +194,7 @@ __global__ __launch_bounds__(ISH_THREADS) void k_dec_fit(const double2* __restri
 }
 
 // -- host ------------------------------------------------------------------------------------------------------------
-// What the queries of the measurements (this header, irfloor, irdensity and iriacc) have in common.  The three checks write
+// What the queries of the measurements (this header, irfloor, irdensity, iriacc and irsti) have in common.  The three checks write
 // their message into the caller's buffer msg [cap] and return false; true and nothing written when the field is good.
 inline bool dec_rate_ok(uint32_t rate, char* msg, size_t cap) {
     if (rate >= DEC_MIN_RATE && rate <= DEC_MAX_RATE) return true;

@@ -36,6 +36,7 @@
 #include "irfloor.hip.h"
 #include "irdensity.hip.h"
 #include "iriacc.hip.h"
+#include "irsti.hip.h"
 #include "irtail.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
@@ -3593,7 +3594,7 @@ int ir_fact(const mc_engine* e, uint64_t idx, IrFactKind kind, int count, const 
     return MC_OK;
 }
 
-// The stored taps of IR idx for a measurement (mc_ir_decay, mc_ir_floor, mc_ir_density, mc_ir_iacc), once the entry point has
+// The stored taps of IR idx for a measurement (mc_ir_decay, mc_ir_floor, mc_ir_density, mc_ir_iacc, mc_ir_sti), once the entry point has
 // checked its query and its pointers.  No HIP call: quiesce(e) comes after the entry point's checks of the work.
 int stored_taps(const mc_engine* e, uint64_t idx, const float2** d_x, uint64_t* n) {
     if (e->sf) return fail(MC_ERR_STATE, "the single-transform form keeps no taps");
@@ -3977,6 +3978,43 @@ int mc_ir_tail_width_from_iacc(mc_ir_tail* tail, double rho) {
     if (tail->struct_size != sizeof(mc_ir_tail)) return fail(MC_ERR_ARG, "mc_ir_tail struct_size mismatch");
     if (!std::isfinite(rho)) return fail(MC_ERR_ARG, "rho %g is not finite", rho);
     tail->width = iacc_width(rho);
+    return MC_OK;
+}
+
+void mc_default_sti_query(mc_sti_query* q) {
+    if (!q) return;
+    std::memset(q, 0, sizeof(*q));
+    q->struct_size = (uint32_t)sizeof(*q);
+    q->rate = 44100;
+    q->n_bands = MC_STI_MAX_BANDS;
+    q->n_mod = 14;
+    // the octaves, IEC 60268-16's modulation frequencies and its weights for male speech
+    const float centre[MC_STI_MAX_BANDS] = {125.f, 250.f, 500.f, 1000.f, 2000.f, 4000.f, 8000.f};
+    const double alpha[MC_STI_MAX_BANDS] = {0.085, 0.127, 0.230, 0.233, 0.309, 0.224, 0.173};
+    const double beta[MC_STI_MAX_BANDS - 1] = {0.085, 0.078, 0.065, 0.011, 0.047, 0.095};
+    const float mod[14] = {0.63f, 0.8f, 1.f, 1.25f, 1.6f, 2.f, 2.5f, 3.15f, 4.f, 5.f, 6.3f, 8.f, 10.f, 12.5f};
+    std::copy(centre, centre + MC_STI_MAX_BANDS, q->centre_hz);
+    std::copy(alpha, alpha + MC_STI_MAX_BANDS, q->alpha);
+    std::copy(beta, beta + MC_STI_MAX_BANDS - 1, q->beta);
+    std::copy(mod, mod + 14, q->mod_hz);
+    q->q = 1.41421356f;
+    q->onset_db = -20.f;
+}
+
+int mc_ir_sti(mc_engine* e, uint64_t idx, const mc_sti_query* q, double* rows, double* mtf, double sti[3], uint64_t info[2]) {
+    // the query, the pointers and the index are checked in this order before any HIP call
+    if (const char* bad = sti_check(q)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!e) return fail(MC_ERR_ARG, "null engine");
+    if (!rows) return fail(MC_ERR_ARG, "null rows");
+    if (!mtf) return fail(MC_ERR_ARG, "null mtf");
+    if (!sti) return fail(MC_ERR_ARG, "null sti");
+    if (!info) return fail(MC_ERR_ARG, "null info");
+    const float2* d_x;
+    uint64_t n;
+    if (const int rc = stored_taps(e, idx, &d_x, &n)) return rc;
+    if (const int rc = quiesce(e)) return rc;
+    const hipError_t er = sti_measure(e->stream, d_x, n, *q, rows, mtf, sti, info);
+    if (er != hipSuccess) return fail(MC_ERR_HIP, "STI measurement failed: %s", hipGetErrorString(er));
     return MC_OK;
 }
 

@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McIrDamp, McIrEq, McIrRoom, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McIrDamp, McIrEq, McIrRoom, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -439,6 +439,19 @@ FLOOR_FIELDS = ("energy", "noise", "knee", "t", "peak_to_noise_db", "interval", 
 IACC_WINDOWS = ("early", "late", "all")
 IACC_FIELDS = ("energy_l", "energy_r", "iacc", "lag", "iacf", "iacf0", "level_db", "status")
 DENSITY_FIELDS = ("mix", "mix_s", "first", "max", "max_tap", "mean_after", "silent", "status")
+STI_RATINGS = ((0.30, "bad"), (0.45, "poor"), (0.60, "fair"), (0.75, "good"))
+
+
+def sti_rating(sti):
+    """The word IEC 60268-16 puts on a speech transmission index: "bad" below 0.30, "poor" below 0.45, "fair" below 0.60,
+    "good" below 0.75, "excellent" from there on (an edge belongs to the better word).  ValueError for a NaN."""
+    sti = float(sti)
+    if math.isnan(sti):
+        raise ValueError("sti is NaN: it has no rating")
+    for edge, word in STI_RATINGS:
+        if sti < edge:
+            return word
+    return "excellent"
 
 
 def decay_for_rt60(measured_s, target_s, rate):
@@ -883,6 +896,54 @@ class Convolution:
         check(self._L.mc_ir_iacc(self._h, idx, C.byref(c), rows.ctypes.data_as(dp), cv.ctypes.data_as(dp) if cv is not None else None, info))
         return dict(origin=int(info[0]), taps=int(info[1]), split=int(info[2]), max_lag=int(c.max_lag), curve=cv,
                     rows={(g, name): dict(zip(IACC_FIELDS, (float(v) for v in rows[g, w]))) for g in range(groups) for w, name in enumerate(IACC_WINDOWS)})
+
+    def ir_sti(self, idx, bands=None, alpha=None, beta=None, mod_hz=None, snr_db=None, q=None, onset_db=-20.0, end=0, rate=None):
+        """The speech transmission index of the stored taps of IR idx, measured on the device (mc_ir_sti; include/mcconv.h has
+        the definition).  rate defaults to the engine's sample_rate, then to 44100.  bands=None means the seven octaves 125 Hz ..
+        8 kHz with IEC 60268-16's weights for male speech; bands of one's own need alpha (one weight per band) and beta (one per
+        pair of neighbours) too: ValueError without them.  mod_hz=None means the standard's 14 modulation frequencies.  snr_db, one
+        value per band, adds stationary noise at that signal-to-noise ratio.  Returns {"origin", "taps", "sti", "rows", "mtf"}: sti
+        maps "L" | "R" | "LR" to the index (NaN without bands or with a silent band: sti_rating gives the word for a number); rows
+        maps (g, "L" | "R" | "LR") - group 0 is broadband, group g >= 1 is bands[g - 1] - to {energy, mti, status}; status 1: no
+        energy, and mti is NaN.  mtf is float64 [1 + len(bands), 3, len(mod_hz)], the modulation transfer function."""
+        if rate is None:
+            rate = self.sample_rate or 44100
+        c = McStiQuery()
+        self._L.mc_default_sti_query(C.byref(c))
+        if bands is None:
+            bands = tuple(c.centre_hz)
+            alpha = tuple(c.alpha) if alpha is None else alpha
+            beta = tuple(c.beta) if beta is None else beta
+        elif alpha is None or beta is None:
+            raise ValueError("bands of one's own need alpha and beta: the default weights belong to the seven octaves")
+        mod_hz = tuple(c.mod_hz)[:c.n_mod] if mod_hz is None else tuple(mod_hz)
+        if len(bands) > _lib.MC_STI_MAX_BANDS:
+            raise ValueError(f"{len(bands)} bands; at most {_lib.MC_STI_MAX_BANDS}")
+        if len(alpha) != len(bands) or len(beta) != max(len(bands) - 1, 0):
+            raise ValueError(f"{len(bands)} bands need {len(bands)} alpha and {max(len(bands) - 1, 0)} beta; got {len(alpha)} and {len(beta)}")
+        if not 1 <= len(mod_hz) <= _lib.MC_STI_MAX_MOD:
+            raise ValueError(f"{len(mod_hz)} modulation frequencies; 1 to {_lib.MC_STI_MAX_MOD}")
+        if snr_db is not None and len(snr_db) != len(bands):
+            raise ValueError(f"{len(bands)} bands need {len(bands)} snr_db; got {len(snr_db)}")
+        c.rate, c.n_bands, c.n_mod = int(rate), len(bands), len(mod_hz)
+        c.flags = _lib.MC_STI_SNR if snr_db is not None else 0
+        for name, values in (("centre_hz", bands), ("alpha", alpha), ("beta", beta), ("snr_db", () if snr_db is None else snr_db), ("mod_hz", mod_hz)):
+            field = getattr(c, name)
+            for k in range(len(field)):
+                field[k] = float(values[k]) if k < len(values) else 0.0
+        if q is not None:
+            c.q = float(q)
+        c.onset_db, c.end = float(onset_db), int(end)
+        groups = 1 + c.n_bands
+        rows = np.empty((groups, 3, 4), np.float64)
+        mtf = np.empty((groups, 3, c.n_mod), np.float64)
+        sti = (C.c_double * 3)()
+        info = (C.c_uint64 * 2)()
+        dp = C.POINTER(C.c_double)
+        check(self._L.mc_ir_sti(self._h, idx, C.byref(c), rows.ctypes.data_as(dp), mtf.ctypes.data_as(dp), sti, info))
+        return dict(origin=int(info[0]), taps=int(info[1]), sti={name: float(sti[s]) for s, name in enumerate(DECAY_SETS)}, mtf=mtf,
+                    rows={(g, name): dict(energy=float(rows[g, s, 0]), mti=float(rows[g, s, 1]), status=int(rows[g, s, 2]))
+                          for g in range(groups) for s, name in enumerate(DECAY_SETS)})
 
     def ir_tail_info(self, idx):
         """What the tail step of IR idx's load did (mc_ir_tail_info): the bands it touched, the frames that came in, the frames

@@ -59,6 +59,9 @@ int mc_ir_tail_move_knee(mc_ir_tail*, uint32_t, uint64_t) __attribute__((weak));
 void mc_default_iacc_query(mc_iacc_query*) __attribute__((weak));
 int mc_ir_iacc(mc_engine*, uint64_t, const mc_iacc_query*, double*, double*, uint64_t*) __attribute__((weak));
 int mc_ir_tail_width_from_iacc(mc_ir_tail*, double) __attribute__((weak));
+// ... no STI measurement
+void mc_default_sti_query(mc_sti_query*) __attribute__((weak));
+int mc_ir_sti(mc_engine*, uint64_t, const mc_sti_query*, double*, double*, double*, uint64_t*) __attribute__((weak));
 int mc_load_ir_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
                     const mc_ir_tail*) __attribute__((weak));
 int mc_load_ir_sweep_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
@@ -726,6 +729,81 @@ void Convolution::reportIacc(size_t idx) {
         }
 }
 
+void Convolution::setIrStiReport(bool on, const StiQuery& query) {
+    if (on && _group) {
+        Log::error("conv", "the IR STI report is not available with several devices (mc_ir_sti is single-engine)");
+        std::exit(2);
+    }
+    _stiReport = on;
+    _stiQuery = query;
+}
+
+bool Convolution::parseSti(const std::string& arg, StiQuery& out, std::string& why) {
+    std::vector<float> snr;
+    char* end = nullptr;
+    for (const char* a = arg.c_str();; a = end + 1) {
+        const float db = std::strtof(a, &end);
+        if (end == a || (*end && *end != ',') || !std::isfinite(db) || db < -60.f || db > 120.f || snr.size() >= MC_STI_MAX_BANDS) {
+            why = "takes DB[,DB...]: one signal-to-noise ratio for all seven octaves or one per octave from 125 Hz up, each in [-60, 120]";
+            return false;
+        }
+        snr.push_back(db);
+        if (!*end) break;
+    }
+    if (snr.size() != 1 && snr.size() != MC_STI_MAX_BANDS) {
+        why = "takes one signal-to-noise ratio for all seven octaves or seven, one per octave";
+        return false;
+    }
+    snr.resize(MC_STI_MAX_BANDS, snr[0]);
+    out.snrDb = snr;
+    return true;
+}
+
+const char* Convolution::stiRating(double sti) {
+    if (std::isnan(sti)) return "none";
+    return sti < 0.30 ? "bad" : sti < 0.45 ? "poor" : sti < 0.60 ? "fair" : sti < 0.75 ? "good" : "excellent";
+}
+
+Convolution::Sti Convolution::irSti(size_t idx, const StiQuery& query) {
+    if (!mc_ir_sti || !mc_default_sti_query) {
+        Log::error("conv", "the engine has no STI measurement (mc_ir_sti)");
+        std::exit(2);
+    }
+    mc_sti_query q;
+    mc_default_sti_query(&q);  // (the seven octaves, IEC 60268-16's modulation frequencies and weights)
+    q.rate = (uint32_t)samplerate;
+    if (!query.snrDb.empty()) {
+        q.flags |= MC_STI_SNR;
+        for (size_t b = 0; b < query.snrDb.size() && b < MC_STI_MAX_BANDS; b++) q.snr_db[b] = query.snrDb[b];
+    }
+    Sti s;
+    s.bands = q.n_bands;
+    s.rows.resize((1 + (size_t)q.n_bands) * 3 * 4);
+    std::vector<double> mtf((1 + (size_t)q.n_bands) * 3 * q.n_mod);
+    uint64_t info[2] = {0, 0};
+    if (mc_ir_sti(_engine, idx, &q, s.rows.data(), mtf.data(), s.sti, info) != MC_OK) {  // (a rate that cannot hold the 8 kHz octave)
+        Log::error("conv", "IR %zu: the STI cannot be measured: %s", idx, mc_last_error());
+        std::exit(2);
+    }
+    s.origin = info[0], s.taps = info[1];
+    return s;
+}
+
+void Convolution::reportSti(size_t idx) {
+    static const char* const set[3] = {"L", "R", "LR"};
+    const Sti s = irSti(idx, _stiQuery);
+    for (int k = 0; k < 3; k++) {
+        std::string mti;
+        int status = 0;
+        for (size_t b = 1; b <= s.bands; b++) {
+            mti += " " + places(s.at(b, (Decay::Set)k, Sti::Mti), 4);
+            if (s.at(b, (Decay::Set)k, Sti::Status) != 0.0) status = 1;
+        }
+        Log::info(name, "IR %zu sti %s: origin %llu, STI %s (%s), MTI%s, status %d", idx, set[k], (unsigned long long)s.origin, places(s.sti[k], 4).c_str(),
+                  stiRating(s.sti[k]), mti.c_str(), status);
+    }
+}
+
 mc_ir_synth Convolution::synthFrames(const IrSynth& y, double rate) {
     const auto frames = [&](double seconds) { return (uint64_t)std::nearbyint(seconds * rate); };
     mc_ir_synth s;
@@ -1168,13 +1246,14 @@ void Convolution::loadPendingIrs() {
         if (_floorReport) reportFloor(p.idx);
         if (_densityReport) reportDensity(p.idx);
         if (_iaccReport) reportIacc(p.idx);
+        if (_stiReport) reportSti(p.idx);
         _tailOn = false;
     }
     _pendingIrs.clear();
 }
 
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
-    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _irTail.mode != IrTail::Off) {  // (loaded by onStart(), once the client's rate is known)
+    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _stiReport || _irTail.mode != IrTail::Off) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
         _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth(), false, IrSweep()});
         if (idx + 1 > _nirs) _nirs = idx + 1;

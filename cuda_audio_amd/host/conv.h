@@ -286,6 +286,30 @@ public:
     // The argument of --ir-iacc-lag (seconds, [0, 1]) or of --ir-iacc-bands (HZ[,HZ...], at most 10) into `out`.  False, with the
     // reason in `why`, for a malformed one.
     static bool parseIacc(const std::string& option, const std::string& arg, IaccQuery& out, std::string& why);
+    // The speech transmission index of a loaded IR, measured by the engine from the taps it convolves with (mc_ir_sti of
+    // include/mcconv.h, which has the definition; no reference equivalent): the seven octaves 125 Hz .. 8 kHz, IEC 60268-16's 14
+    // modulation frequencies and its weights for male speech, at the client's rate.  snrDb: empty, or seven signal-to-noise
+    // ratios in dB, one per octave, of stationary noise in the room.
+    struct StiQuery {
+        std::vector<float> snrDb;
+    };
+    struct Sti {
+        uint64_t origin = 0, taps = 0;
+        size_t bands = 0;
+        double sti[3] = {0.0, 0.0, 0.0};  // L, R, LR
+        std::vector<double> rows;         // per group (0 broadband, then the bands) and set {E, MTI, status, 0}
+        enum Field { Energy = 0, Mti, Status };
+        double at(size_t group, Decay::Set set, Field f) const { return rows[(group * 3 + set) * 4 + f]; }
+    };
+    Sti irSti(size_t idx, const StiQuery& query);
+    // One log line per IR loaded from now on and channel set (origin, STI and its rating, the seven bands' MTI, status: 1 when a
+    // band of the set has no energy).  Loaded by onStart(), single device only, as setIrDecayReport.
+    void setIrStiReport(bool on, const StiQuery& query);
+    // The argument of --ir-sti-snr (DB[,DB...]: one value for all seven octaves or seven, each in [-60, 120]) into `out`.  False,
+    // with the reason in `why`, for a malformed one.
+    static bool parseSti(const std::string& arg, StiQuery& out, std::string& why);
+    // "bad", "poor", "fair", "good" or "excellent" at the edges 0.30, 0.45, 0.60, 0.75; "none" for NaN
+    static const char* stiRating(double sti);
     // The tail step every IR loaded from now on goes through (mc_ir_tail of include/mcconv.h; no reference equivalent): the IR
     // is loaded as it is, its floor is measured in the bands of setIrFloorXovers, and it is loaded again with every band cut at
     // its knee (Cut) or cross-faded there into decaying noise (Extend) ahead of its shape, EQ and damping.  An IR whose
@@ -355,6 +379,9 @@ private:
     void reportFloor(size_t idx);
     void reportDensity(size_t idx);
     void reportIacc(size_t idx);
+    void reportSti(size_t idx);
+    bool _stiReport = false;
+    StiQuery _stiQuery;
     bool _iaccReport = false;
     IaccQuery _iaccQuery;
     bool _densityReport = false;

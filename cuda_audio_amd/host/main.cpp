@@ -45,6 +45,9 @@
 // (origin, IACC, its lag in taps and ms, IACF(0), level difference, status; measured by the engine: Convolution::setIrIaccReport);
 // --ir-iacc-bands HZ[,HZ...]: one more line per band for the whole IR; --ir-iacc-lag SECONDS: the largest lag (1 ms without).
 // --ir-tail's key width=iacc (extend only): the tail's width is 1 - the late broadband IACF(0) measured on the same load.
+// --ir-sti-report: after each IR is loaded one log line per channel set (L, R, LR) with its speech transmission index (origin,
+// STI and its rating, the seven octaves' MTI, status; measured by the engine: Convolution::setIrStiReport); --ir-sti-snr
+// DB[,DB...]: stationary noise at that signal-to-noise ratio, one value for all octaves or one per octave.
 #include <cassert>
 #include <cstdlib>
 #include <cstring>
@@ -79,6 +82,8 @@ int main(int argc, char** argv) {
     Convolution::DensityQuery irDensity;
     bool irIaccReport = false;
     Convolution::IaccQuery irIacc;
+    bool irStiReport = false;
+    Convolution::StiQuery irSti;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--periods") && i + 1 < argc) periods = strtoull(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "--settings") && i + 1 < argc) settingsPath = argv[++i];
@@ -208,6 +213,14 @@ int main(int argc, char** argv) {
                 std::cerr << option << " '" << argv[i] << "': " << why << std::endl;
                 return 2;
             }
+        } else if (!strcmp(argv[i], "--ir-sti-report")) irStiReport = true;
+        else if (!strcmp(argv[i], "--ir-sti-snr") && i + 1 < argc) {
+            std::string why;
+            const char* option = argv[i];
+            if (!Convolution::parseSti(argv[++i], irSti, why)) {
+                std::cerr << option << " '" << argv[i] << "': " << why << std::endl;
+                return 2;
+            }
         } else if (!strcmp(argv[i], "--ir-rt60") && i + 1 < argc) {
             irRt60 = atof(argv[++i]);
             if (!(irRt60 > 0.0)) {
@@ -253,6 +266,7 @@ int main(int argc, char** argv) {
         if (irFloorReport) c->setIrFloorReport(true);
         c->setIrDensityReport(irDensityReport, irDensity);
         c->setIrIaccReport(irIaccReport, irIacc);
+        c->setIrStiReport(irStiReport, irSti);
         c->setIrTail(irTail);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;

@@ -479,6 +479,64 @@ void mc_default_iacc_query(mc_iacc_query *q);
  * same query on the same IR return the same bits. */
 int mc_ir_iacc(mc_engine *e, uint64_t idx, const mc_iacc_query *q, double *rows, double *curve, uint64_t info[3]);
 
+/* The speech transmission index of a loaded IR, measured on the device: how well speech is understood through the room the
+ * engine convolves with, from 0 (bad) to 1 (excellent).  It is obtained from the impulse response by Schroeder's relation (the
+ * indirect method of IEC 60268-16): the modulation transfer function of the squared, octave-filtered response at n_mod
+ * modulation frequencies in n_bands bands, folded into one number with the standard's band weights.  C50 and D50 of mc_ir_decay
+ * are its coarse relatives.  No reference equivalent; single-engine.  The stored taps are only read.  Everything is in double,
+ * computed from the fields as they are (floats, but for the weights).
+ *   1. N and the origin o are those of mc_ir_decay's step 1; the row groups are those of its step 2: group 0 broadband,
+ *      groups b = 1 .. n_bands the same two-section band-pass from rest at tap 0, at centre_hz[b - 1] with q.  y_L and y_R are
+ *      the group's doubles;
+ *   2. over the taps m in [o, N), for each channel c in {L, R} and each modulation frequency F_f = (double) mod_hz[f], f < n_mod,
+ *      with theta = 2 pi F_f (m - o) / rate: C_c(f) = sum of y_c[m]^2 cos theta, S_c(f) = sum of y_c[m]^2 sin theta,
+ *      E_c = sum of y_c[m]^2.  The channel sets s = 0, 1, 2 are L, R and L + R; the third set's C, S and E are the sums of the
+ *      other two's (L + R), added after the taps have been summed: it is not walked again;
+ *   3. m_s(f) = hypot(C, S) / E, the modulation transfer function.  With flags & MC_STI_SNR, in the band groups only, m is
+ *      multiplied by 1 / (1 + 10^(-snr_db[b - 1] / 10)): stationary noise at that signal-to-noise ratio in band b.  A set with
+ *      E = 0 or an E that is not finite has status 1, and its m and everything derived from it are NaN;
+ *   4. the transmission index TI = 1 when m >= 1, 0 when m <= 0, else min(max((10 log10(m / (1 - m)) + 15) / 30, 0), 1): the
+ *      apparent signal-to-noise ratio clipped to +/- 15 dB.  MTI = (sum of TI over f, ascending) / n_mod;
+ *   5. STI_s = sum of alpha[b] MTI_b over the band groups (ascending b) less the sum of beta[b] sqrt(MTI_b MTI_(b+1)) over
+ *      b < n_bands - 1 (ascending b, subtracted one by one after the alphas).  NaN when n_bands = 0 or a band of the set has
+ *      status 1;
+ *   6. mtf[((3 g + s) n_mod) + f] = m; rows[(3 g + s) 4 ..] = {E, MTI, status, 0}; sti[s]; info = {o, N}.
+ * The standard's level-dependent auditory masking and its reception threshold need absolute sound pressure levels, which an
+ * impulse response does not have: they are left out.  The default weights are IEC 60268-16's for male speech; a caller with
+ * another set passes its own. */
+#define MC_STI_MAX_BANDS 7
+#define MC_STI_MAX_MOD 16
+#define MC_STI_SNR 1u           /* flags: apply snr_db */
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_sti_query) = 272 (4 bytes of padding before end) */
+    uint32_t rate;          /* the rate the stored taps are at, [8000, 384000] */
+    uint32_t n_bands;       /* 0 .. MC_STI_MAX_BANDS */
+    uint32_t n_mod;         /* 1 .. MC_STI_MAX_MOD */
+    uint32_t flags;         /* MC_STI_SNR or 0; any other bit is refused */
+    float centre_hz[MC_STI_MAX_BANDS];   /* as mc_decay_query: [10, 0.45 rate] */
+    double alpha[MC_STI_MAX_BANDS];      /* the bands' weights: finite, >= 0.  Doubles, so that the defaults add up to 1 */
+    double beta[MC_STI_MAX_BANDS - 1];   /* the redundancy of bands b and b + 1: finite, >= 0; the first n_bands - 1 are used */
+    float snr_db[MC_STI_MAX_BANDS];      /* with MC_STI_SNR: finite, [-60, 120]; not looked at without */
+    float mod_hz[MC_STI_MAX_MOD];        /* finite, [0.1, 50] */
+    float q;                /* as mc_decay_query */
+    float onset_db;         /* as mc_decay_query; default -20 */
+    uint64_t end;           /* as mc_decay_query */
+    uint32_t reserved[2];   /* must be 0 */
+} mc_sti_query;
+/* rate 44100, q sqrt 2, onset -20, end 0, no flag, snr_db 0; the seven octaves 125 .. 8000 Hz; the 14 modulation frequencies
+ * 0.63, 0.8, 1, 1.25, 1.6, 2, 2.5, 3.15, 4, 5, 6.3, 8, 10, 12.5 Hz; alpha = 0.085, 0.127, 0.230, 0.233, 0.309, 0.224, 0.173 and
+ * beta = 0.085, 0.078, 0.065, 0.011, 0.047, 0.095 (sum alpha - sum beta = 1).  A rate below 8000 / 0.45 Hz cannot hold the 8 kHz
+ * octave: centre_hz[6] is then refused, and the caller passes fewer bands and weights of its own. */
+void mc_default_sti_query(mc_sti_query *q);
+/* rows: [(1 + n_bands) * 3 * 4]; mtf: [(1 + n_bands) * 3 * n_mod]; sti: [3]; info = {origin tap o, taps analysed N}.  Checked
+ * in this order, all before the engine or the device is touched (MC_ERR_ARG, the message names the field): the query field by
+ * field in struct order (struct_size, rate, n_bands, n_mod, flags, each used centre_hz, alpha, beta, snr_db under the flag,
+ * mod_hz, q, onset_db, reserved), the pointers ("null rows", "null mtf", "null sti", "null info"), idx ("IR not loaded").
+ * MC_ERR_STATE in the single-transform form, which keeps no taps.  Threading, stream and the promise that nothing the engine
+ * holds changes are mc_ir_decay's; scratch is allocated by the call and freed before it returns; two calls with the same query
+ * on the same IR return the same bits. */
+int mc_ir_sti(mc_engine *e, uint64_t idx, const mc_sti_query *q, double *rows, double *mtf, double sti[3], uint64_t info[2]);
+
 /* Synthesis of an IR on the device from a seed: a room from a few numbers instead of a recorded WAV.  No reference equivalent;
  * single-engine, as shaping is.  The F = frames stereo frames are generated at the session's rate into the buffer the shaped
  * load's steps read and never exist on the host.  Frame m is a pure function of (seed, m, this struct): the same struct gives
