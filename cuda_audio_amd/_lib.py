@@ -27,7 +27,8 @@ SYMBOLS = [
     "mc_default_iacc_query", "mc_ir_iacc", "mc_ir_tail_width_from_iacc",
     "mc_default_sti_query", "mc_ir_sti",
     "mc_default_ir_tail", "mc_load_ir_tail", "mc_load_ir_sweep_tail", "mc_ir_tail_info",
-    "mc_default_ir_room", "mc_synth_ir_room", "mc_ir_room_info", "mc_ir_room_plan", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
+    "mc_default_ir_room", "mc_synth_ir_room", "mc_ir_room_info", "mc_ir_room_plan",
+    "mc_default_ir_room_mics", "mc_synth_ir_room_mics", "mc_ir_room_mics_plan", "mc_ir_room_mics_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
     "mc_enable_kernel_timing", "mc_get_kernel_stats", "mc_algorithmic_bytes_per_block", "mc_blocks_processed", "mc_preferred_batch",
@@ -320,6 +321,22 @@ class McIrRoom(C.Structure):
     ]
 
 
+class McIrRoomMics(C.Structure):
+    """mc_ir_room_mics: the patterns and aims of the two receivers and of the source in the room of mc_synth_ir_room_mics."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("mic_pattern", C.c_float * 2),
+        ("mic_az_deg", C.c_float * 2),
+        ("mic_el_deg", C.c_float * 2),
+        ("src_pattern", C.c_float),
+        ("src_az_deg", C.c_float),
+        ("src_el_deg", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class McKernelStats(C.Structure):
     _fields_ = [
         ("launches", C.c_uint64),
@@ -423,6 +440,12 @@ def load():
                                    C.POINTER(McIrTail)]
     L.mc_ir_room_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_ir_room_plan.argtypes = [C.POINTER(McIrRoom), C.c_uint32, u64, C.POINTER(C.c_double)]
+    L.mc_default_ir_room_mics.argtypes = [C.POINTER(McIrRoomMics)]
+    L.mc_default_ir_room_mics.restype = None
+    L.mc_synth_ir_room_mics.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrRoom), C.POINTER(McIrRoomMics), C.POINTER(McIrShape),
+                                        C.POINTER(McIrEq), C.POINTER(McIrDamp), C.POINTER(McIrTail)]
+    L.mc_ir_room_mics_plan.argtypes = [C.POINTER(McIrRoom), C.POINTER(McIrRoomMics), C.c_uint32, u64, C.POINTER(C.c_double)]
+    L.mc_ir_room_mics_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_num_irs.argtypes = [vp]
     L.mc_ir_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_set_params.argtypes = [vp, C.c_int, C.POINTER(McCcValue)]

@@ -17,6 +17,11 @@
 // 8-byte words (atomicAdd(unsigned long long*): one global_atomic_add_x2 per lane, no compare-and-swap loop).  The accumulator
 // holds min(E + 16, F) frames, is zeroed on the stream before the launch and freed after k_synth_room has read it; the images
 // kept per channel are counted with one add per wave and counter.
+//
+// Directional microphones and a directional source (mc_synth_ir_room_mics) are k_room's second instantiation: where a lane
+// holds one image and has its b, it multiplies b / d by gs gr, two first-order patterns of two dot products with p, the
+// source's aim mirrored with the image.  Nothing else differs: the delays, the prune, the counts and the scatter are shared,
+// and the instantiation without microphones is the kernel as it was.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -33,7 +38,14 @@ constexpr int ROOM_MAX_GRID = 2048;
 constexpr int ROOM_REACH = 16;               // taps k = -(ROOM_REACH - 1) .. ROOM_REACH: two per lane pair of a wave
 constexpr double ROOM_Q = 1099511627776.0;   // 2^40: the quantum of a contribution is 2^-40
 constexpr double ROOM_MIN_DIRECT = 0.1;      // metres
-constexpr double ROOM_MAX_SUM = 4194304.0;   // 2^22: 8 (2N + 1)^3 gain / d below it keeps the sum inside 2^62
+constexpr double ROOM_MAX_SUM = 4194304.0;   // 2^22: 8 (2N + 1)^3 gain / d below it keeps the sum inside 2^62 (with microphones
+                                             // too: |gs gr| <= 1 makes no image louder)
+
+// checked mc_ir_room_mics as the kernel takes them, fifteen doubles that room_factors knows by their place: the unit vectors
+// of the aims of receiver L, receiver R and the source, and their patterns as alpha and as 1 - alpha
+struct RoomMics {
+    double aim[3][3], alpha[3], oma[3];
+};
 
 // a checked mc_ir_room as the kernels take it, everything in double from the float fields
 struct RoomPlan {
@@ -45,15 +57,42 @@ struct RoomPlan {
     double size[3], src[3], rcv[2][3];
     double tau[2];      // the direct sound's delay per channel, frames
     double bpow[6][MC_ROOM_MAX_ORDER + 2];  // bpow[w][j] = pow(beta[w], j), 0^0 = 1
+    RoomMics m;         // mc_ir_room_mics, when `mics` is set
+    uint32_t mics;
 };
 
+// g(cos) of a first-order pattern: exactly 1 for alpha = 1 (oma = 0), whatever the cosine
+__host__ __device__ inline double room_pattern(double alpha, double oma, double cosine) { return fma(oma, cosine, alpha); }
+
+// a . p in the definition's order
+__host__ __device__ inline double room_dot(double ax, double ay, double az, double px, double py, double pz) { return fma(pz, az, fma(py, ay, px * ax)); }
+
+// {gs, gr} of channel c for the image at p (from the receiver), d = |p|, whose axes are mirrored where sx, sy, sz = 1 - 2 u_a
+// are -1; get(j) is number j of a RoomMics
+template <class Get>
+__host__ __device__ inline double2 room_factors(Get get, int c, double sx, double sy, double sz, double px, double py, double pz, double d) {
+    const double cr = room_dot(get(3 * c), get(3 * c + 1), get(3 * c + 2), px, py, pz) / d;
+    const double cs = -room_dot(sx * get(6), sy * get(7), sz * get(8), px, py, pz) / d;  // (times 1 or -1: exact)
+    return make_double2(room_pattern(get(11), get(14), cs), room_pattern(get(9 + c), get(12 + c), cr));
+}
+
 // One launch over the lattice; gridDim.x * ROOM_THREADS / 64 waves stride over it 64 images at a time.  acc: p.A frames of two
-// int64, zero; kept: two zeroed counters.
+// int64, zero; kept: two zeroed counters.  MICS: p.mics is set, and an image's amplitude takes its factor gs gr.
+template <bool MICS>
 __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __restrict__ acc, unsigned* __restrict__ kept, RoomPlan p) {
     const unsigned lane = threadIdx.x & 63u;
-    const uint32_t wave = (blockIdx.x * ROOM_THREADS + threadIdx.x) >> 6, nwaves = gridDim.x * (ROOM_THREADS / 64);
+    uint32_t wave = (blockIdx.x * ROOM_THREADS + threadIdx.x) >> 6;
+    const uint32_t nwaves = gridDim.x * (ROOM_THREADS / 64);
+    if (MICS) wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave);  // (the same in every lane: the walk below becomes scalar)
     const int ch = (int)(lane & 1u), k = (int)(lane >> 1) - (ROOM_REACH - 1);
     unsigned nkept[2] = {0u, 0u};
+    // The microphones' fifteen numbers, one per lane of a register pair, and read from there where an image needs them: the
+    // kernel without them already fills the scalar registers (102 of 102), and thirty more for the whole walk would spill.
+    // (v_readlane does not look at EXEC: the lanes that hold the numbers need not be among those that hold a kept image.)
+    const double mics = MICS && lane < 15 ? reinterpret_cast<const double*>(&p.m)[lane] : 0.0;
+    const auto mic = [mics](int j) {
+        return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(mics), j), __builtin_amdgcn_readlane(__double2loint(mics), j));
+    };
     for (uint64_t base = (uint64_t)wave * 64; base < p.total; base += (uint64_t)nwaves * 64) {
         const uint64_t i = base + lane;
         long long k0[2] = {0, 0};
@@ -85,6 +124,11 @@ __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __res
                     if (keep[c]) {
                         a[c] = b / d[c];
                         s[c] = sin(M_PI * f[c]);
+                        if (MICS) {  // (after the sine, whose constants want the scalar registers too: before it hipcc reserves scratch)
+                            const double2 g = room_factors(mic, c, (double)(1 - 2 * u[0]), (double)(1 - 2 * u[1]), (double)(1 - 2 * u[2]), q[0] - p.rcv[c][0],
+                                                           q[1] - p.rcv[c][1], q[2] - p.rcv[c][2], d[c]);
+                            a[c] *= g.x * g.y;
+                        }
                     }
             }
         }
@@ -277,6 +321,68 @@ inline RoomPlan room_plan(const mc_ir_room& r, uint32_t rate, uint64_t F) {
     return p;
 }
 
+// Every field of the microphones, in the struct's order, without touching an engine or HIP; the message names the field.
+// Null when they are good.
+inline const char* room_mics_check(const mc_ir_room_mics* m) {
+    static thread_local char msg[160];
+    if (!m) return "null mics";
+    if (m->struct_size != sizeof(mc_ir_room_mics)) return "mc_ir_room_mics struct_size mismatch";
+    msg[0] = 0;
+    const auto outside = [](const char* name, int j, float v, double lo, double hi) {
+        if (std::isfinite(v) && (double)v >= lo && (double)v <= hi) return false;
+        if (j < 0)
+            std::snprintf(msg, sizeof(msg), "%s %g outside [%g, %g]", name, (double)v, lo, hi);
+        else
+            std::snprintf(msg, sizeof(msg), "%s[%d] %g outside [%g, %g]", name, j, (double)v, lo, hi);
+        return true;
+    };
+    if (m->flags) {
+        std::snprintf(msg, sizeof(msg), "mics flags %u must be 0", m->flags);
+        return msg;
+    }
+    for (int c = 0; c < 2; c++)
+        if (outside("mic_pattern", c, m->mic_pattern[c], 0.0, 1.0)) return msg;
+    for (int c = 0; c < 2; c++)
+        if (outside("mic_az_deg", c, m->mic_az_deg[c], -360.0, 360.0)) return msg;
+    for (int c = 0; c < 2; c++)
+        if (outside("mic_el_deg", c, m->mic_el_deg[c], -90.0, 90.0)) return msg;
+    if (outside("src_pattern", -1, m->src_pattern, 0.0, 1.0)) return msg;
+    if (outside("src_az_deg", -1, m->src_az_deg, -360.0, 360.0)) return msg;
+    if (outside("src_el_deg", -1, m->src_el_deg, -90.0, 90.0)) return msg;
+    if (m->reserved) {
+        std::snprintf(msg, sizeof(msg), "mics reserved %u must be 0", m->reserved);
+        return msg;
+    }
+    return nullptr;
+}
+
+// checked microphones into a room's plan: the aims as unit vectors, the patterns as alpha and 1 - alpha
+inline void room_plan_mics(RoomPlan& p, const mc_ir_room_mics& m) {
+    const float alpha[3] = {m.mic_pattern[0], m.mic_pattern[1], m.src_pattern};
+    const float az[3] = {m.mic_az_deg[0], m.mic_az_deg[1], m.src_az_deg}, el[3] = {m.mic_el_deg[0], m.mic_el_deg[1], m.src_el_deg};
+    for (int j = 0; j < 3; j++) {
+        const double a = (double)az[j] * M_PI / 180, e = (double)el[j] * M_PI / 180;
+        p.m.aim[j][0] = std::cos(e) * std::cos(a);
+        p.m.aim[j][1] = std::cos(e) * std::sin(a);
+        p.m.aim[j][2] = std::sin(e);
+        p.m.alpha[j] = (double)alpha[j];
+        p.m.oma[j] = 1.0 - (double)alpha[j];
+    }
+    p.mics = 1;
+}
+
+// what mc_ir_room_mics_plan and mc_ir_room_mics_info report: the direct sound's gs L, R, gr L, R, gs gr L, R, 0, 0
+inline void room_mics_report(const RoomPlan& p, double out[8]) {
+    const double* numbers = &p.m.aim[0][0];
+    const auto mic = [numbers](int j) { return numbers[j]; };
+    for (int c = 0; c < 2; c++) {
+        const double px = p.src[0] - p.rcv[c][0], py = p.src[1] - p.rcv[c][1], pz = p.src[2] - p.rcv[c][2];
+        const double2 g = room_factors(mic, c, 1.0, 1.0, 1.0, px, py, pz, std::sqrt(px * px + py * py + pz * pz));
+        out[c] = g.x, out[2 + c] = g.y, out[4 + c] = g.x * g.y;
+    }
+    out[6] = out[7] = 0.0;
+}
+
 // what mc_ir_room_plan reports of a checked room
 inline void room_report(const mc_ir_room& r, uint32_t rate, uint64_t F, double out[8]) {
     const RoomPlan p = room_plan(r, rate, F);
@@ -310,7 +416,10 @@ inline hipError_t room_generate(hipStream_t stream, const SynPlan& syn, const Ro
     if (er == hipSuccess) {
         const uint64_t waves = ((uint64_t)room.total + 63) / 64, per = ROOM_THREADS / 64;
         const unsigned grid = (unsigned)std::min<uint64_t>((waves + per - 1) / per, ROOM_MAX_GRID);
-        hipLaunchKernelGGL(k_room, dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
+        if (room.mics)
+            hipLaunchKernelGGL(k_room<true>, dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
+        else
+            hipLaunchKernelGGL(k_room<false>, dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
         er = hipGetLastError();
     }
     if (er == hipSuccess) {

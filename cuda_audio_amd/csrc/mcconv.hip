@@ -88,10 +88,10 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline double pan_l(double p) { return p >= 0 ? 1 - p : 1; }  // conv.cu:386
 inline double pan_r(double p) { return p <= 0 ? 1 + p : 1; }  // conv.cu:387
 
-// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info and _room_info report of an IR's last load: one entry
-// per kind, on when that load had the step or the source (a shape with something on, an eq band or damping count as a shape, and
+// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _room_info and _room_mics_info report of an IR's last
+// load: one entry per kind, on when that load had the step or the source (a shape with something on, an eq band or damping count as a shape, and
 // so do a synthesised, a swept and a tailed load), with the numbers the getter hands out (include/mcconv.h says what they are)
-enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_ROOM, FACT_KINDS };
+enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_ROOM, FACT_ROOM_MICS, FACT_KINDS };
 struct IrFact {
     bool on = false;
     double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -3407,7 +3407,7 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
     return MC_OK;
 }
 
-// What the six mc_ir_*_info getters report of the load `ld` that stored `taps` taps; sinfo = the shaping stage's numbers.
+// What the seven mc_ir_*_info getters report of the load `ld` that stored `taps` taps; sinfo = the shaping stage's numbers.
 // Every kind is written, so nothing of an earlier load onto the same index stays behind.
 void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[8]) {
     for (IrFact& f : ir.facts) f.on = false;
@@ -3430,6 +3430,11 @@ void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[
     if (ld.room) {
         const RoomPlan& r = ld.room->plan;
         put(FACT_ROOM, {(double)r.N, (double)ld.room->kept[0], (double)ld.room->kept[1], r.tau[0], r.tau[1], (double)r.E, (double)r.complete, 0.0});
+        if (r.mics) {
+            double m[8];
+            room_mics_report(r, m);
+            put(FACT_ROOM_MICS, {m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7]});
+        }
     }
 }
 
@@ -3750,16 +3755,32 @@ void mc_default_ir_room(mc_ir_room* r) {
     r->gain = 1.f;
 }
 
+void mc_default_ir_room_mics(mc_ir_room_mics* m) {
+    if (!m) return;
+    std::memset(m, 0, sizeof(*m));
+    m->struct_size = (uint32_t)sizeof(*m);
+    m->mic_pattern[0] = m->mic_pattern[1] = m->src_pattern = 1.f;
+}
+
 int mc_synth_ir_room(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_synth* synth, const mc_ir_room* room, const mc_ir_shape* shape,
                      const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail) {
+    return mc_synth_ir_room_mics(e, idx, nframes, synth, room, nullptr, shape, eq, damp, tail);
+}
+
+int mc_synth_ir_room_mics(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_synth* synth, const mc_ir_room* room, const mc_ir_room_mics* mics,
+                          const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail) {
     const bool tailed = tail && tail->mode != MC_TAIL_OFF;
-    if (!room && !tailed) return mc_synth_ir(e, idx, nframes, synth, shape, eq, damp);
-    // synth, then the room, then the tail with F' after F, then damp, eq and shape as in mc_synth_ir, all before the engine and before any HIP call
+    if (!room && !mics && !tailed) return mc_synth_ir(e, idx, nframes, synth, shape, eq, damp);
+    // synth, then the room and its microphones, then the tail with F' after F, then damp, eq and shape as in mc_synth_ir, all before
+    // the engine and before any HIP call
     if (const char* bad = syn_check(synth)) return fail(MC_ERR_ARG, "%s", bad);
     const uint32_t rate = synth->rate;
     const uint64_t F = synth->frames;
+    if (mics && !room) return fail(MC_ERR_ARG, "the microphones need a room");
     if (room)
         if (const char* bad = room_check(room, rate, F)) return fail(MC_ERR_ARG, "%s", bad);
+    if (mics)
+        if (const char* bad = room_mics_check(mics)) return fail(MC_ERR_ARG, "%s", bad);
     if (tailed) {
         if (const char* bad = tail_check(tail, rate)) return fail(MC_ERR_ARG, "%s", bad);
         if (rate < RS_MIN_RATE || rate > RS_MAX_RATE)
@@ -3773,6 +3794,7 @@ int mc_synth_ir_room(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_s
     if (tailed) step = tail_step(*tail, rate, F);
     RoomStep rstep{};
     if (room) rstep.plan = room_plan(*room, rate, F);
+    if (mics) room_plan_mics(rstep.plan, *mics);
     IrLoad ld;
     ld.syn = &syn, ld.frames = F;
     ld.room = room ? &rstep : nullptr;
@@ -3790,6 +3812,22 @@ int mc_ir_room_plan(const mc_ir_room* room, uint32_t rate, uint64_t frames, doub
     if (!out) return fail(MC_ERR_ARG, "null out");
     room_report(*room, rate, frames, out);
     return MC_OK;
+}
+
+int mc_ir_room_mics_plan(const mc_ir_room* room, const mc_ir_room_mics* mics, uint32_t rate, uint64_t frames, double out[8]) {
+    if (frames < 1 || frames > SYN_MAX_FRAMES)
+        return fail(MC_ERR_ARG, "frames %llu outside [1, %llu]", (unsigned long long)frames, (unsigned long long)SYN_MAX_FRAMES);
+    if (const char* bad = room_check(room, rate, frames)) return fail(MC_ERR_ARG, "%s", bad);
+    if (const char* bad = room_mics_check(mics)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!out) return fail(MC_ERR_ARG, "null out");
+    RoomPlan p = room_plan(*room, rate, frames);
+    room_plan_mics(p, *mics);
+    room_mics_report(p, out);
+    return MC_OK;
+}
+
+int mc_ir_room_mics_info(const mc_engine* e, uint64_t idx, double out[8]) {
+    return ir_fact(e, idx, FACT_ROOM_MICS, 8, "was not loaded with microphones", out);
 }
 
 int mc_ir_synth_info(const mc_engine* e, uint64_t idx, double out[4]) { return ir_fact(e, idx, FACT_SYNTH, 4, "was not synthesised", out); }

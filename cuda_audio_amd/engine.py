@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McIrDamp, McIrEq, McIrRoom, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McIrDamp, McIrEq, McIrRoom, McIrRoomMics, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -398,6 +398,75 @@ def room_plan(room, rate, frames):
 
 
 @dataclasses.dataclass
+class IrRoomMics:
+    """Directional microphones and a directional source in an IrRoom (mc_ir_room_mics, include/mcconv.h): prepare_synth(room=,
+    mics=).  `pattern` is the receivers' first-order pattern, a name of PATTERNS or the number alpha of
+    g = alpha + (1 - alpha) cos (1 omni, 0.5 cardioid, 0 figure-of-eight); `az` and `el` are their aims in degrees, azimuth from
+    +x towards +y and elevation towards +z.  Each takes one value for both receivers or a pair (left, right).
+    source_pattern, source_az and source_el are the source's.  The defaults are omni everywhere: the room as it is without
+    microphones, bit for bit."""
+
+    pattern: object = "omni"
+    az: object = 0.0
+    el: object = 0.0
+    source_pattern: object = "omni"
+    source_az: float = 0.0
+    source_el: float = 0.0
+
+    PATTERNS = {"omni": 1.0, "subcardioid": 0.75, "cardioid": 0.5, "supercardioid": 0.366, "hypercardioid": 0.25, "fig8": 0.0}
+
+    @classmethod
+    def alpha(cls, pattern):
+        """The number of a pattern given by name or as a number."""
+        if isinstance(pattern, str):
+            if pattern not in cls.PATTERNS:
+                raise ValueError(f"'{pattern}' is no pattern: {', '.join(cls.PATTERNS)} or a number")
+            return cls.PATTERNS[pattern]
+        return float(pattern)
+
+    @classmethod
+    def pair(cls, facing=0.0, angle=90.0, pattern="cardioid", **kw):
+        """A pair of equal microphones that faces azimuth `facing` and opens by `angle` degrees: L aims at
+        facing + angle / 2 and R at facing - angle / 2.  Azimuth runs counter-clockwise seen from above, so the microphone
+        with the larger azimuth points to the left of someone who looks along `facing`: XY is pair(angle=90) with
+        IrRoom.spacing 0, Blumlein pair(angle=90, pattern="fig8"), ORTF pair(angle=110) with spacing 0.17.
+        IrRoom.spacing puts L at the smaller coordinate of `axis`, whatever the aims.  Someone looking along +x has their left
+        at larger y, so with the spacing along y a pair facing +x would have its left microphone on the right: a spaced
+        pair such as ORTF along y faces -x (facing=180), or swaps its aims (a negative angle).  Further keywords are
+        IrRoomMics' own (el, source_pattern, ...)."""
+        return cls(pattern=pattern, az=(float(facing) + float(angle) / 2.0, float(facing) - float(angle) / 2.0), **kw)
+
+    @staticmethod
+    def _two(v):
+        v = tuple(v) if isinstance(v, (tuple, list)) else (v, v)
+        if len(v) != 2:
+            raise ValueError("pattern, az and el take one value or two (left, right)")
+        return v
+
+    def to_c(self):
+        m = McIrRoomMics()
+        _lib.load().mc_default_ir_room_mics(C.byref(m))
+        pattern, az, el = self._two(self.pattern), self._two(self.az), self._two(self.el)
+        for k in range(2):
+            m.mic_pattern[k], m.mic_az_deg[k], m.mic_el_deg[k] = self.alpha(pattern[k]), float(az[k]), float(el[k])
+        m.src_pattern, m.src_az_deg, m.src_el_deg = self.alpha(self.source_pattern), float(self.source_az), float(self.source_el)
+        return m
+
+
+def _mics_factors(out):
+    return dict(source=(out[0], out[1]), receiver=(out[2], out[3]), factor=(out[4], out[5]))
+
+
+def room_mics_plan(room, mics, rate, frames):
+    """What `mics` (an IrRoomMics) do to the direct sound of `room` in a load of `frames` frames at `rate`
+    (mc_ir_room_mics_plan, host arithmetic only): the source's factor towards each receiver, each receiver's factor towards the
+    source, and their product, which multiplies the direct sound's gain / d; each as (left, right)."""
+    out = (C.c_double * 8)()
+    check(_lib.load().mc_ir_room_mics_plan(C.byref(room.to_c()), C.byref(mics.to_c()), int(rate), int(frames), out))
+    return _mics_factors(out)
+
+
+@dataclasses.dataclass
 class Sweep:
     """The exponential sine sweep whose recording prepare_sweep deconvolves (mc_sweep, include/mcconv.h): `frames` frames
     from f1_hz at frame 0 to f2_hz at the last, of peak `amplitude` (0.5 is WavFile's full scale), faded in and out over
@@ -617,17 +686,25 @@ class Convolution:
         else:
             check(self._L.mc_load_ir(self._h, idx, _fp(lr), lr.shape[0], nframes))
 
-    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None, room=None, tail=None):
+    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None, room=None, tail=None, mics=None):
         """Generate the IR `synth` (an IrSynth) describes on the device and store it at idx (mc_synth_ir): the frames take the
         place of a WAV's at the session's rate, and shape, eq and damp apply to them as in prepare().  A synthesised IR counts
         as shaped: ir_shape_info(idx)["frames"] is synth.frames.  The engine's sample_rate (which eq, damp, room and tail
         need) is passed unless synth.rate is set.
         room (an IrRoom): the reflections of a rectangular room are added to the frames (mc_synth_ir_room); ir_room_info(idx)
         then tells what was rendered.  tail (an IrTail whose mode is not "off"): the tail step on the generated frames, as
-        in prepare()."""
+        in prepare().  mics (an IrRoomMics, with room): the receivers and the source of the room are directional
+        (mc_synth_ir_room_mics); ir_room_mics_info(idx) then tells the direct sound's factors."""
         s = synth.to_c()
         if not s.rate:
             s.rate = int(self.sample_rate or 0)
+        if mics is not None:
+            if room is None:
+                raise ValueError("the microphones need a room")
+            check(self._L.mc_synth_ir_room_mics(self._h, idx, nframes, C.byref(s), C.byref(room.to_c()), C.byref(mics.to_c()),
+                                                C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
+                                                C.byref(damp.to_c()) if damp is not None else None, C.byref(tail.to_c()) if tail is not None else None))
+            return
         if room is not None or tail is not None:
             check(self._L.mc_synth_ir_room(self._h, idx, nframes, C.byref(s), C.byref(room.to_c()) if room is not None else None,
                                            C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
@@ -792,6 +869,13 @@ class Convolution:
         out = (C.c_double * 8)()
         check(self._L.mc_ir_room_info(self._h, idx, out))
         return dict(order=int(out[0]), images=(int(out[1]), int(out[2])), direct=(out[3], out[4]), last=int(out[5]), complete=int(out[6]))
+
+    def ir_room_mics_info(self, idx):
+        """What the microphones of IR idx's load did to the direct sound (mc_ir_room_mics_info), as room_mics_plan reports it.
+        McError (MC_ERR_STATE) for an IR whose last load had no microphones."""
+        out = (C.c_double * 8)()
+        check(self._L.mc_ir_room_mics_info(self._h, idx, out))
+        return _mics_factors(out)
 
     def ir_sweep_info(self, idx):
         """What prepare_sweep deconvolved for IR idx (mc_ir_sweep_info): the sweep's frames N, the recording's M, the frames

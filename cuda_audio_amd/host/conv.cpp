@@ -72,6 +72,11 @@ void mc_default_ir_room(mc_ir_room*) __attribute__((weak));
 int mc_synth_ir_room(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_room*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
                      const mc_ir_tail*) __attribute__((weak));
 int mc_ir_room_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+// ... or a room without directional microphones
+void mc_default_ir_room_mics(mc_ir_room_mics*) __attribute__((weak));
+int mc_synth_ir_room_mics(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_room*, const mc_ir_room_mics*, const mc_ir_shape*,
+                          const mc_ir_eq*, const mc_ir_damp*, const mc_ir_tail*) __attribute__((weak));
+int mc_ir_room_mics_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 }
 
 namespace {
@@ -183,10 +188,14 @@ uint64_t Convolution::dampFrames(double seconds, double rate) {
 // irRate = sessionRate = 0: the frames are loaded at the rate they have (never with a band of eq on, never with damping).
 // synth: the engine generates the frames (lr null; sessionRate = synth->rate).  sweep: lr is the recording of a sweep, `frames`
 // frames at sessionRate = sweep->sweep.rate, which the engine deconvolves.  room (with synth): its reflections are added to the
-// generated frames, and a tail applies to them
+// generated frames, and a tail applies to them; mics (with room): its receivers and its source are directional
 void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
                              const IrEq& eq, const IrDamp& damp, const mc_ir_synth* synth, const SweepLoad* sweep, const mc_ir_tail* tail,
-                             const mc_ir_room* room) {
+                             const mc_ir_room* room, const mc_ir_room_mics* mics) {
+    if (mics && (!mc_synth_ir_room_mics || !mc_default_ir_room_mics || !mc_ir_room_mics_info)) {
+        Log::error("conv", "the engine has no directional microphones in its rooms (mc_synth_ir_room_mics)");
+        std::exit(2);
+    }
     if (room && (!mc_synth_ir_room || !mc_default_ir_room || !mc_ir_room_info)) {
         Log::error("conv", "the engine has no room rendering (mc_synth_ir_room)");
         std::exit(2);
@@ -241,8 +250,9 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         d.origin = damp.origin;
     }
     if (synth) {  // (what the engine refuses of a generated IR is the index line's fault: a message and exit 2, no abort)
-        const int rc = room ? mc_synth_ir_room(_engine, idx, nframes, synth, room, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
-                            : mc_synth_ir(_engine, idx, nframes, synth, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d);
+        const int rc = mics   ? mc_synth_ir_room_mics(_engine, idx, nframes, synth, room, mics, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
+                       : room ? mc_synth_ir_room(_engine, idx, nframes, synth, room, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
+                              : mc_synth_ir(_engine, idx, nframes, synth, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d);
         if (rc != MC_OK) {
             Log::error("conv", "IR %zu cannot be synthesised: %s", idx, mc_last_error());
             std::exit(2);
@@ -253,6 +263,12 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
             Log::info(name, "IR %zu room: order %d, %llu and %llu images before frame %llu, direct sound at %.2f and %.2f frames, complete up to frame %llu",
                       idx, (int)ri[0], (unsigned long long)ri[1], (unsigned long long)ri[2], (unsigned long long)ri[5], ri[3], ri[4],
                       (unsigned long long)ri[6]);
+        }
+        if (mics) {
+            double mi[8];
+            check(mc_ir_room_mics_info(_engine, idx, mi), "mc_ir_room_mics_info");
+            Log::info(name, "IR %zu microphones: the direct sound leaves the source at %.4f and %.4f, is received at %.4f and %.4f, factors %.4f and %.4f",
+                      idx, mi[0], mi[1], mi[2], mi[3], mi[4], mi[5]);
         }
         double si[4];
         check(mc_ir_synth_info(_engine, idx, si), "mc_ir_synth_info");
@@ -914,10 +930,21 @@ mc_ir_room Convolution::roomFrames(const IrRoom& room, double rate) {
     return r;
 }
 
+mc_ir_room_mics Convolution::roomMics(const IrRoom& room) {
+    mc_ir_room_mics m;
+    mc_default_ir_room_mics(&m);
+    for (int c = 0; c < 2; c++) m.mic_pattern[c] = room.micPattern[c], m.mic_az_deg[c] = room.micAim[c], m.mic_el_deg[c] = room.micTilt[c];
+    m.src_pattern = room.sourcePattern;
+    m.src_az_deg = room.sourceAim;
+    m.src_el_deg = room.sourceTilt;
+    return m;
+}
+
 bool Convolution::parseRoom(const std::string& line, IrRoom& out, std::string& why) {
     static const char* form =
         "room:LENGTH_S:LX,LY,LZ:SX,SY,SZ:RX,RY,RZ[:key=value,...] with keys beta (one value, or six separated by '/'), order, spacing, axis (x|y|z), "
-        "speed, gain, last, t60 and synth:'s keys";
+        "speed, gain, last, mic (omni|subcardioid|cardioid|supercardioid|hypercardioid|fig8 or a number in [0, 1]; P or P/P), aim and tilt (degrees; "
+        "one value or L/R), src, srcaim, srctilt, t60 and synth:'s keys";
     std::vector<std::string> parts;
     for (size_t at = 0;;) {
         const size_t colon = line.find(':', at);
@@ -943,6 +970,33 @@ bool Convolution::parseRoom(const std::string& line, IrRoom& out, std::string& w
             if (end == std::string::npos || !number(text.substr(at, end - at), x)) return false;
             v[k] = (float)x;
             at = end + 1;
+        }
+        return true;
+    };
+    // a pattern by name or as alpha in [0, 1]
+    const auto pattern = [&](const std::string& text, float& v) {
+        static const struct {
+            const char* name;
+            float alpha;
+        } named[] = {{"omni", 1.0f}, {"subcardioid", 0.75f}, {"cardioid", 0.5f}, {"supercardioid", 0.366f}, {"hypercardioid", 0.25f}, {"fig8", 0.0f}};
+        for (const auto& p : named)
+            if (text == p.name) {
+                v = p.alpha;
+                return true;
+            }
+        double x;
+        if (!number(text, x) || x < 0.0 || x > 1.0) return false;
+        v = (float)x;
+        return true;
+    };
+    // one value for both receivers, or left/right; each within [-limit, limit] (a pattern with limit 0)
+    const auto pair = [&](const std::string& text, double limit, float* v) {
+        const size_t slash = text.find('/');
+        const std::string one[2] = {text.substr(0, slash), slash == std::string::npos ? text.substr(0, slash) : text.substr(slash + 1)};
+        for (int c = 0; c < 2; c++) {
+            double x;
+            if (limit == 0.0 ? !pattern(one[c], v[c]) : !number(one[c], x) || std::fabs(x) > limit) return false;
+            if (limit != 0.0) v[c] = (float)x;
         }
         return true;
     };
@@ -995,6 +1049,16 @@ bool Convolution::parseRoom(const std::string& line, IrRoom& out, std::string& w
         } else if (key == "t60") {
             good = number(text, v) && v >= 0.0;
             t60 = text;
+        } else if (key == "mic" || key == "aim" || key == "tilt") {
+            good = key == "mic" ? pair(text, 0.0, room.micPattern) : key == "aim" ? pair(text, 360.0, room.micAim) : pair(text, 90.0, room.micTilt);
+            room.directional = true;
+        } else if (key == "src") {
+            good = pattern(text, room.sourcePattern);
+            room.directional = true;
+        } else if (key == "srcaim" || key == "srctilt") {
+            good = number(text, v) && std::fabs(v) <= (key == "srcaim" ? 360.0 : 90.0);
+            (key == "srcaim" ? room.sourceAim : room.sourceTilt) = (float)v;
+            room.directional = true;
         } else {
             synthKeys += "," + item;  // (parseSynth names an unknown key)
         }
@@ -1196,6 +1260,10 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
         return;
     }
     if (p.generated) {
+        if (p.roomed && p.room.directional && !mc_default_ir_room_mics) {
+            Log::error("conv", "the engine has no directional microphones in its rooms (mc_synth_ir_room_mics)");
+            std::exit(2);
+        }
         if (p.roomed && !mc_default_ir_room) {
             Log::error("conv", "the engine has no room rendering (mc_synth_ir_room)");
             std::exit(2);
@@ -1207,7 +1275,10 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
         if (p.roomed) {
             const mc_ir_synth s = synthFrames(p.room.late, (double)samplerate);
             const mc_ir_room r = roomFrames(p.room, (double)samplerate);
-            loadShaped(p.idx, nullptr, s.frames, p.nframes, s.rate, s.rate, shape, p.eq, p.damp, &s, nullptr, _tailOn ? &_tailNow : nullptr, &r);
+            mc_ir_room_mics m;
+            if (p.room.directional) m = roomMics(p.room);
+            loadShaped(p.idx, nullptr, s.frames, p.nframes, s.rate, s.rate, shape, p.eq, p.damp, &s, nullptr, _tailOn ? &_tailNow : nullptr, &r,
+                       p.room.directional ? &m : nullptr);
             return;
         }
         const mc_ir_synth s = synthFrames(p.synth, (double)samplerate);

@@ -180,6 +180,10 @@ public:
     // and so does the tail step: the floor is measured on the room alone, then the IR is rendered again with the tail, which
     // lets a short rendering run out at its own slope.  One more log line per IR: order, images kept, the direct sound's delay.
     // Single device only, as setIrShape.
+    // Directional microphones and a directional source (mc_ir_room_mics and mc_synth_ir_room_mics): `directional` is set by any
+    // of the line's keys mic, aim, tilt, src, srcaim and srctilt, and such a room is loaded through mc_synth_ir_room_mics, in both
+    // renderings of the tail flow, with one more log line: the direct sound's factors.  Patterns are alpha of
+    // g = alpha + (1 - alpha) cos, angles degrees (azimuth from +x towards +y, tilt towards +z), left then right.
     struct IrRoom {
         float size[3] = {5.0f, 4.0f, 3.0f}, source[3] = {1.0f, 1.5f, 1.2f}, receiver[3] = {3.5f, 2.0f, 1.5f};
         float beta[6] = {0.9f, 0.9f, 0.9f, 0.9f, 0.9f, 0.9f};
@@ -188,16 +192,23 @@ public:
         float speed = 343.0f, gain = 1.0f;
         uint32_t order = 0;
         double lastSeconds = 0.0;
+        bool directional = false;
+        float micPattern[2] = {1.0f, 1.0f}, micAim[2] = {0.0f, 0.0f}, micTilt[2] = {0.0f, 0.0f};
+        float sourcePattern = 1.0f, sourceAim = 0.0f, sourceTilt = 0.0f;
         IrSynth late;
         IrRoom() { late.late = 0.0f; }
     };
     void prepareRoom(size_t idx, const IrRoom& room, size_t nframes = 1024);
     // A line of an IR index that starts with "room:" - room:LENGTH_S:LX,LY,LZ:SX,SY,SZ:RX,RY,RZ[:key=value,...], keys beta (one
-    // value, or six separated by '/'), order, spacing, axis (x|y|z), speed, gain, last (seconds), and for the late field t60 and
-    // parseSynth's keys - as an IrRoom.  False, with the reason in `why`, for a malformed line.
+    // value, or six separated by '/'), order, spacing, axis (x|y|z), speed, gain, last (seconds), mic (a pattern: omni, subcardioid,
+    // cardioid, supercardioid, hypercardioid, fig8 or a number in [0, 1]; P or P/P), aim and tilt (degrees; one value or L/R),
+    // src, srcaim and srctilt (the source's), and for the late field t60 and parseSynth's keys - as an IrRoom.  False, with the
+    // reason in `why`, for a malformed line.
     static bool parseRoom(const std::string& line, IrRoom& out, std::string& why);
     // mc_ir_room of an IrRoom at rate Hz
     static mc_ir_room roomFrames(const IrRoom& room, double rate);
+    // mc_ir_room_mics of a directional IrRoom
+    static mc_ir_room_mics roomMics(const IrRoom& room);
 
     // An IR the engine deconvolves from the recording of an exponential sine sweep played through a room (mc_sweep and
     // mc_load_ir_sweep of include/mcconv.h; no reference equivalent): times in seconds, turned into frames at the client's
@@ -400,7 +411,8 @@ private:
     IrDamp _irDamp;
     void loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
                     const IrEq& eq = IrEq(), const IrDamp& damp = IrDamp(), const mc_ir_synth* synth = nullptr,
-                    const SweepLoad* sweep = nullptr, const mc_ir_tail* tail = nullptr, const mc_ir_room* room = nullptr);
+                    const SweepLoad* sweep = nullptr, const mc_ir_tail* tail = nullptr, const mc_ir_room* room = nullptr,
+                    const mc_ir_room_mics* mics = nullptr);
     void pushParams();
     void pullVsteps();
 };

@@ -26,6 +26,9 @@
 // room:LENGTH_S:LX,LY,LZ:SX,SY,SZ:RX,RY,RZ[:key=value,...] with keys beta (one value, or six separated by '/'), order, spacing,
 // axis (x|y|z), speed, gain, last (seconds), and t60 and synth:'s keys for a late field under it (Convolution::parseRoom; metres and
 // seconds); the --ir-* options apply to it as to a WAV, --ir-tail included: a short rendering runs out at its own measured slope.
+// Directional microphones and a directional source in that room: mic=P or mic=P/P (left/right; P one of omni, subcardioid,
+// cardioid, supercardioid, hypercardioid, fig8, or alpha in [0, 1]), aim=AZ or AZ/AZ and tilt=EL or EL/EL in degrees (azimuth
+// from +x towards +y, tilt towards +z), src=P, srcaim=AZ, srctilt=EL; one more log line tells the direct sound's factors.
 // A line that starts with "sweep:" is an IR the engine deconvolves from the recording of a sine sweep,
 // sweep:RECORDING.wav:LENGTH_S:F1:F2[:key=value,...] with keys amp, fadein, fadeout, offset, length (Convolution::parseSweep;
 // times in seconds, the recording at the client's sample rate); the --ir-* options apply to it as to a WAV.

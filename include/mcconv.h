@@ -741,7 +741,8 @@ int mc_ir_tail_info(const mc_engine *e, uint64_t idx, double out[4]);
  * Sum.  Each contribution is q = llrint(a w_k 2^40) (to nearest, ties to even), added into a 64-bit integer per frame and
  *   channel: integer sums do not depend on the order of arrival, so the same struct gives the same bits whatever the grid and
  *   however many images share a frame.  8 (2N + 1)^3 gain / min(d_direct,L, d_direct,R) must stay below 2^22, which excludes
- *   overflow: every image is farther away than the direct path, |beta| <= 1 and |w| <= 1.
+ *   overflow: every image is farther away than the direct path, |beta| <= 1 and |w| <= 1 (and, with mc_ir_room_mics below,
+ *   |gs gr| <= 1).
  * Frame.  (float)(late + direct + reflections + acc 2^-40), added in that order in double and rounded once; the first three
  *   terms are mc_ir_synth's.
  * Order 0.  N = ceil(E c / (rate 2 min(L))), refused above MC_ROOM_MAX_ORDER.  Every image with d < 2 N min(L) lies inside the
@@ -787,6 +788,52 @@ int mc_ir_room_info(const mc_engine *e, uint64_t idx, double out[8]);
  * checked as by mc_synth_ir_room, with rate in [8000, 384000] and frames in [1, 2^24].  Host arithmetic only: no engine and no
  * HIP call. */
 int mc_ir_room_plan(const mc_ir_room *room, uint32_t rate, uint64_t frames, double out[8]);
+
+/* Directional microphones and a directional source in the room of mc_ir_room: first-order patterns, which the image-source
+ * method renders exactly.  An image source is the mirror of the real one, so its aim is mirrored with it; a receiver weighs
+ * an arrival by the direction it comes from.  Only the amplitude of an image changes.  No reference equivalent.
+ *
+ * Aims.  Azimuth runs from +x towards +y, elevation towards +z, both in degrees; the unit vector of an aim is
+ *   (cos el cos az, cos el sin az, sin el), computed on the host in double from the float fields: (double)deg * M_PI / 180.
+ * Patterns.  A pattern is one number alpha in [0, 1], g(cos) = alpha + (1 - alpha) cos: 1 omni, 0.75 subcardioid, 0.5 cardioid,
+ *   0.366 supercardioid, 0.25 hypercardioid, 0 figure-of-eight.  |g| <= 1, so the bound on the integer sum of mc_ir_room holds
+ *   unchanged.
+ * Receiver c sits where mc_ir_room puts it (spacing 0: a coincident pair), with its own pattern alpha_c and aim m_c.  For an
+ *   image at p (from that receiver, as above), d = |p|: cr = (m_c . p) / d, gr = alpha_c + (1 - alpha_c) cr.
+ * Source.  Pattern alpha_s, aim v.  The image (n, u) aims along v'_a = (1 - 2 u_a) v_a: mirrored on every axis it was reflected
+ *   an odd number of times; translations do not turn it.  It radiates towards the receiver along -p: cs = -(v' . p) / d,
+ *   gs = alpha_s + (1 - alpha_s) cs, per channel, since the two receivers see the image from different directions.
+ * Amplitude.  a_c = (b / d_c) (gs_c gr_c), b = gain b_x b_y b_z as above.  The order is part of the definition: a dot product
+ *   is fma(z, z', fma(y, y', x x')) and g is fma(1 - alpha, cos, alpha), which is exactly 1 for alpha = 1: omni microphones with
+ *   an omni source store the bits of a room without microphones, and mirror-symmetric setups store equal channels.
+ * Unchanged.  tau, k0, f, the keep rule k0 < E, the taps, the quantum, the one rounding, E, the accumulator and the automatic
+ *   order.  The kept counts stay a matter of geometry: an image whose factor is 0 is counted, as one with b = 0 is.  A
+ *   negative factor (the rear lobe of a figure-of-eight) is an ordinary negative contribution. */
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_ir_room_mics) = 48 */
+    uint32_t flags;         /* must be 0 */
+    float mic_pattern[2];   /* alpha of L, R: [0, 1] */
+    float mic_az_deg[2];    /* finite, [-360, 360] */
+    float mic_el_deg[2];    /* finite, [-90, 90] */
+    float src_pattern;      /* [0, 1] */
+    float src_az_deg, src_el_deg;   /* as the microphones' */
+    uint32_t reserved;      /* must be 0 */
+} mc_ir_room_mics;
+/* every pattern 1 (omni), every angle 0 */
+void mc_default_ir_room_mics(mc_ir_room_mics *m);
+/* mc_synth_ir_room with `mics` in the room.  With mics NULL the call is mc_synth_ir_room itself, bit for bit.  mics without
+ * room is MC_ERR_ARG ("the microphones need a room").  Checked in mc_synth_ir_room's order, the microphones field by field in
+ * the struct's order right after the room and before the tail; the message names the field, nothing of the engine or the
+ * device is touched before every check has passed, and the engine stays as it was on a refusal. */
+int mc_synth_ir_room_mics(mc_engine *e, uint64_t idx, uint64_t nframes, const mc_ir_synth *synth, const mc_ir_room *room,
+                          const mc_ir_room_mics *mics, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp,
+                          const mc_ir_tail *tail);
+/* What `mics` do to the direct sound of `room`: out = {gs L, gs R, gr L, gr R, gs gr L, gs gr R, 0, 0}.  The room is checked
+ * as by mc_ir_room_plan, then the microphones.  Host arithmetic only: no engine and no HIP call. */
+int mc_ir_room_mics_plan(const mc_ir_room *room, const mc_ir_room_mics *mics, uint32_t rate, uint64_t frames, double out[8]);
+/* The same eight numbers of the IR's last load; MC_ERR_STATE unless that load had microphones (mc_ir_room_info still answers
+ * for a room without them) */
+int mc_ir_room_mics_info(const mc_engine *e, uint64_t idx, double out[8]);
 
 int mc_num_irs(const mc_engine *e);
 /* out[0..3] = sum h_L, sum h_R, sum h_L(-1)^m, sum h_R(-1)^m of the truncated IR; out[4] = taps, out[5] = partitions */

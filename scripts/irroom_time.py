@@ -1,6 +1,7 @@
 """Time of one synthesised load with the reflections of a room (mc_synth_ir_room) at the largest lattice, order 32 (2.2 M
 images), F = 2^20 frames, 48 kHz, next to the same load without the room (k_synth, the shaping stage, the transforms): the
-difference is the accumulator's zeroing, k_room and k_synth_room's reads.  The engine runs on torch's current stream and HIP
+difference is the accumulator's zeroing, k_room and k_synth_room's reads; and the load with a cardioid pair in the room
+(mc_synth_ir_room_mics, k_room's other instantiation).  The engine runs on torch's current stream and HIP
 events on that stream bracket each load (the load itself ends in a stream synchronise); the host clock is printed beside them.
 Warm engine: one load of each kind that allocates, then REPS timed ones, alternating.  Prints one JSON line.  For k_room's own
 time run this under `rocprofv3 --kernel-trace --stats`, in a run of its own.  LAST=frames leaves out images from that frame on."""
@@ -13,7 +14,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from cuda_audio_amd.engine import Convolution, IrRoom, IrSynth  # noqa: E402
+from cuda_audio_amd.engine import Convolution, IrRoom, IrRoomMics, IrSynth  # noqa: E402
 
 REPS = int(os.environ.get("REPS", "5"))
 F, RATE = 1 << 20, 48000
@@ -21,7 +22,9 @@ room = IrRoom(order=32, last=int(os.environ.get("LAST", "0")))
 synth = IrSynth(frames=F, late_gain=0.0)
 c = Convolution("room", 2 * F, max_batch=8, device=0, sample_rate=RATE)
 c.use_torch_stream()
-kinds = dict(plain=lambda: c.prepare_synth(0, synth), room=lambda: c.prepare_synth(0, synth, room=room))
+mics = IrRoomMics.pair()  # XY: cardioids at +45 and -45 degrees
+kinds = dict(plain=lambda: c.prepare_synth(0, synth), mics=lambda: c.prepare_synth(0, synth, room=room, mics=mics),
+             room=lambda: c.prepare_synth(0, synth, room=room))
 for call in kinds.values():  # (first calls allocate)
     call()
 ev_ms, host_ms = {k: [] for k in kinds}, {k: [] for k in kinds}
@@ -40,4 +43,5 @@ c.close()
 res = {k: dict(event_median_ms=round(float(np.median(ev_ms[k])), 3), event_min_ms=round(float(np.min(ev_ms[k])), 3),
                host_median_ms=round(float(np.median(host_ms[k])), 3)) for k in kinds}
 print(json.dumps(dict(frames=F, order=info["order"], images_kept=info["images"], last=info["last"], reps=REPS,
-                      room_less_plain_ms=round(res["room"]["event_median_ms"] - res["plain"]["event_median_ms"], 3), **res)), flush=True)
+                      room_less_plain_ms=round(res["room"]["event_median_ms"] - res["plain"]["event_median_ms"], 3),
+                      mics_less_room_ms=round(res["mics"]["event_median_ms"] - res["room"]["event_median_ms"], 3), **res)), flush=True)
