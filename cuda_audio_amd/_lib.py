@@ -28,7 +28,8 @@ SYMBOLS = [
     "mc_default_sti_query", "mc_ir_sti",
     "mc_default_ir_tail", "mc_load_ir_tail", "mc_load_ir_sweep_tail", "mc_ir_tail_info",
     "mc_default_ir_room", "mc_synth_ir_room", "mc_ir_room_info", "mc_ir_room_plan",
-    "mc_default_ir_room_mics", "mc_synth_ir_room_mics", "mc_ir_room_mics_plan", "mc_ir_room_mics_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
+    "mc_default_ir_room_mics", "mc_synth_ir_room_mics", "mc_ir_room_mics_plan", "mc_ir_room_mics_info",
+    "mc_default_ir_room_bands", "mc_synth_ir_room_bands", "mc_ir_room_bands_plan", "mc_ir_room_bands_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
     "mc_enable_kernel_timing", "mc_get_kernel_stats", "mc_algorithmic_bytes_per_block", "mc_blocks_processed", "mc_preferred_batch",
@@ -337,6 +338,20 @@ class McIrRoomMics(C.Structure):
     ]
 
 
+class McIrRoomBands(C.Structure):
+    """mc_ir_room_bands: the walls and the air of the room of mc_synth_ir_room_bands per frequency band."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("n_xovers", C.c_uint32),
+        ("xover_hz", C.c_float * 3),
+        ("beta", (C.c_float * 6) * 4),
+        ("air_db_per_m", C.c_float * 4),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class McKernelStats(C.Structure):
     _fields_ = [
         ("launches", C.c_uint64),
@@ -446,6 +461,12 @@ def load():
                                         C.POINTER(McIrEq), C.POINTER(McIrDamp), C.POINTER(McIrTail)]
     L.mc_ir_room_mics_plan.argtypes = [C.POINTER(McIrRoom), C.POINTER(McIrRoomMics), C.c_uint32, u64, C.POINTER(C.c_double)]
     L.mc_ir_room_mics_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_default_ir_room_bands.argtypes = [C.POINTER(McIrRoomBands)]
+    L.mc_default_ir_room_bands.restype = None
+    L.mc_synth_ir_room_bands.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrRoom), C.POINTER(McIrRoomMics), C.POINTER(McIrRoomBands),
+                                         C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp), C.POINTER(McIrTail)]
+    L.mc_ir_room_bands_plan.argtypes = [C.POINTER(McIrRoom), C.POINTER(McIrRoomBands), C.c_uint32, u64, C.POINTER(C.c_double)]
+    L.mc_ir_room_bands_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_num_irs.argtypes = [vp]
     L.mc_ir_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_set_params.argtypes = [vp, C.c_int, C.POINTER(McCcValue)]

@@ -22,6 +22,19 @@
 // holds one image and has its b, it multiplies b / d by gs gr, two first-order patterns of two dot products with p, the
 // source's aim mirrored with the image.  Nothing else differs: the delays, the prune, the counts and the scatter are shared,
 // and the instantiation without microphones is the kernel as it was.
+//
+// Walls and air per frequency band (mc_synth_ir_room_bands): k_room runs once per band into that band's own accumulator, with
+// the band's table of powers and, through a second template flag, its air factor exp2(-(d k_j)) on b / d; the instantiations
+// without air are the kernels as they were.  The accumulators are joined by irdamp.hip.h's band split, written by its differences:
+// D_k = (acc_(k-1) - acc_k) 2^-40 through crossover k's two sections (damp_step) over all F frames, chunked as every recurrence
+// of the IR tools is (chunkwalk.hip.h):
+//   local  k_room_join<false>, a workgroup row per crossover, runs every chunk from rest and keeps the end states;
+//   carry  k_damp_carry, unchanged, over all X crossovers at once;
+//   fix-up k_room_join<true>, one launch per crossover low to high, runs every chunk from its true state and adds P_k into
+//          r [F]; the last one adds acc_X 2^-40 after it.  The order of the additions is the definition's.
+// k_synth_room_bands then adds r where k_synth_room adds one accumulator's term.  Chunks and runs depend on F alone and the join
+// has no atomics: the same struct stores the same bits whatever the grid.  Equal accumulators give D_k = 0, P_k = +0.0 and r the
+// unbanded term: a banded room whose bands are alike stores the unbanded room's bits.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -31,6 +44,7 @@
 #include <cstdio>
 
 #include "../../include/mcconv.h"
+#include "irdamp.hip.h"
 #include "irsynth.hip.h"
 
 constexpr int ROOM_THREADS = 256;
@@ -51,6 +65,7 @@ struct RoomMics {
 struct RoomPlan {
     uint32_t N, S;      // the order used and 2N + 1
     uint32_t total;     // 8 S^3 images
+    uint32_t mics;      // m is set (in the gap before E: with air in the place this flag had, the kernels' arguments lie where they lay)
     uint64_t E, F, A;   // images arriving at or after E are left out; A = min(E + 16, F) accumulator frames
     uint64_t complete;  // floor(2 N min(L) rate / c)
     double rate, speed, gain;
@@ -58,7 +73,7 @@ struct RoomPlan {
     double tau[2];      // the direct sound's delay per channel, frames
     double bpow[6][MC_ROOM_MAX_ORDER + 2];  // bpow[w][j] = pow(beta[w], j), 0^0 = 1
     RoomMics m;         // mc_ir_room_mics, when `mics` is set
-    uint32_t mics;
+    double air;         // k_j of a band of mc_ir_room_bands, right behind m's fifteen numbers: the sixteenth; 0 = no factor
 };
 
 // g(cos) of a first-order pattern: exactly 1 for alpha = 1 (oma = 0), whatever the cosine
@@ -77,8 +92,9 @@ __host__ __device__ inline double2 room_factors(Get get, int c, double sx, doubl
 }
 
 // One launch over the lattice; gridDim.x * ROOM_THREADS / 64 waves stride over it 64 images at a time.  acc: p.A frames of two
-// int64, zero; kept: two zeroed counters.  MICS: p.mics is set, and an image's amplitude takes its factor gs gr.
-template <bool MICS>
+// int64, zero; kept: two zeroed counters.  MICS: p.mics is set, and an image's amplitude takes its factor gs gr.  AIR: p.air is
+// not 0, and b / d takes the factor exp2(-(d p.air)) before that.
+template <bool MICS, bool AIR>
 __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __restrict__ acc, unsigned* __restrict__ kept, RoomPlan p) {
     const unsigned lane = threadIdx.x & 63u;
     uint32_t wave = (blockIdx.x * ROOM_THREADS + threadIdx.x) >> 6;
@@ -89,7 +105,11 @@ __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __res
     // The microphones' fifteen numbers, one per lane of a register pair, and read from there where an image needs them: the
     // kernel without them already fills the scalar registers (102 of 102), and thirty more for the whole walk would spill.
     // (v_readlane does not look at EXEC: the lanes that hold the numbers need not be among those that hold a kept image.)
-    const double mics = MICS && lane < 15 ? reinterpret_cast<const double*>(&p.m)[lane] : 0.0;
+    // The air constant travels the same way, as number 15, and with it the receivers' six coordinates, as numbers 16 to 21:
+    // the double exp2 wants scalar registers for its constants as the sine does, and without those twelve back hipcc spills two.
+    const double mics = AIR && lane >= 16 && lane < 22                 ? (&p.rcv[0][0])[lane - 16]
+                        : (MICS && lane < 15) || (AIR && lane == 15) ? reinterpret_cast<const double*>(&p.m)[lane]
+                                                                     : 0.0;
     const auto mic = [mics](int j) {
         return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(mics), j), __builtin_amdgcn_readlane(__double2loint(mics), j));
     };
@@ -108,7 +128,8 @@ __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __res
             double d[2], tau[2];
 #pragma unroll
             for (int c = 0; c < 2; c++) {
-                const double px = q[0] - p.rcv[c][0], py = q[1] - p.rcv[c][1], pz = q[2] - p.rcv[c][2];
+                const double px = q[0] - (AIR ? mic(16 + 3 * c) : p.rcv[c][0]), py = q[1] - (AIR ? mic(17 + 3 * c) : p.rcv[c][1]),
+                             pz = q[2] - (AIR ? mic(18 + 3 * c) : p.rcv[c][2]);
                 d[c] = sqrt(px * px + py * py + pz * pz);
                 tau[c] = d[c] * p.rate / p.speed;
                 const double fl = floor(tau[c]);
@@ -119,14 +140,22 @@ __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __res
             if (keep[0] || keep[1]) {
 #pragma unroll
                 for (int ax = 0; ax < 3; ax++) b *= p.bpow[2 * ax][abs(n[ax] - u[ax])] * p.bpow[2 * ax + 1][abs(n[ax])];
+                double air[2] = {1.0, 1.0};
+                if (AIR) {  // (for both channels, kept or not: no branch, and before the sine)
+                    const double kj = mic(15);
+#pragma unroll
+                    for (int c = 0; c < 2; c++) air[c] = exp2(-(d[c] * kj));
+                }
 #pragma unroll
                 for (int c = 0; c < 2; c++)
                     if (keep[c]) {
                         a[c] = b / d[c];
+                        if (AIR) a[c] *= air[c];
                         s[c] = sin(M_PI * f[c]);
                         if (MICS) {  // (after the sine, whose constants want the scalar registers too: before it hipcc reserves scratch)
-                            const double2 g = room_factors(mic, c, (double)(1 - 2 * u[0]), (double)(1 - 2 * u[1]), (double)(1 - 2 * u[2]), q[0] - p.rcv[c][0],
-                                                           q[1] - p.rcv[c][1], q[2] - p.rcv[c][2], d[c]);
+                            const double2 g = room_factors(mic, c, (double)(1 - 2 * u[0]), (double)(1 - 2 * u[1]), (double)(1 - 2 * u[2]),
+                                                           q[0] - (AIR ? mic(16 + 3 * c) : p.rcv[c][0]), q[1] - (AIR ? mic(17 + 3 * c) : p.rcv[c][1]),
+                                                           q[2] - (AIR ? mic(18 + 3 * c) : p.rcv[c][2]), d[c]);
                             a[c] *= g.x * g.y;
                         }
                     }
@@ -185,6 +214,83 @@ __global__ __launch_bounds__(SYN_THREADS) void k_synth_room(float2* __restrict__
     if (i == 0) {
         if (head) x[0] = room_frame(p, 0, acc, A);
         if (head + 2 * pairs < n) x[n - 1] = room_frame(p, n - 1, acc, A);
+    }
+}
+
+// the crossovers of a checked mc_ir_room_bands as the join takes them: one section of crossover k + 1 (damp_plan's)
+struct RoomJoin {
+    int X;
+    IeqCoef c[MC_DAMP_MAX_XOVERS];
+};
+
+static_assert(offsetof(RoomPlan, air) == offsetof(RoomPlan, m) + 15 * sizeof(double), "k_room reads the air constant as number 15 behind the microphones'");
+
+// One pass of the join over F frames for crossover k + 1, k = k0 + blockIdx.y: its input D[m] = (acc_k[m] - acc_(k+1)[m]) 2^-40
+// below A and 0 from there, formed where the walk loads it.  acc: [B][A] pairs of int64 (16-byte aligned).  st: double2
+// [X][gridDim.x * IEQ_THREADS][2], k_damp_chunk's layout, which k_damp_carry scans.  FIX = false: from rest, the end states to st.
+// FIX = true (gridDim.y = 1, k0 = 0 .. X - 1 in that order): from the state st holds, r[m] = P (k == 0) or r[m] + P, and the
+// last crossover adds acc_X[m] 2^-40 after it.  Frames at and past F read as zero and are not written.
+template <bool FIX>
+__global__ __launch_bounds__(IEQ_THREADS) void k_room_join(const longlong2* __restrict__ acc, uint64_t A, uint64_t F, RoomJoin pl, int k0, double2* __restrict__ st,
+                                                           double2* __restrict__ r) {
+    const int k = k0 + (int)blockIdx.y;
+    const uint64_t lanes = (uint64_t)gridDim.x * IEQ_THREADS, entry = (uint64_t)blockIdx.x * IEQ_THREADS + threadIdx.x;
+    const longlong2* __restrict__ lo = acc + A * (uint64_t)k;
+    const longlong2* __restrict__ hi = lo + A;
+    const IeqCoef c = pl.c[k];
+    DampState s{0.0, 0.0, 0.0, 0.0};
+    if (FIX) s = damp_load(st, (uint64_t)k * lanes + entry);
+    chunk_walk<false, IEQ_TILE, double2>(
+        FIX,
+        [&](uint64_t g, double2& v) {
+            v = make_double2(0.0, 0.0);
+            if (g < A) {
+                const longlong2 a = lo[g], b = hi[g];
+                v = make_double2((double)(a.x - b.x) * (1.0 / ROOM_Q), (double)(a.y - b.y) * (1.0 / ROOM_Q));
+            }
+        },
+        [&](double& tap, uint64_t) {
+            const double y = damp_step(c, s, tap);
+            if (FIX) tap = y;
+        },
+        [&](uint64_t g, double2 v) {
+            if (g < F) {
+                if (k) {
+                    const double2 sum = r[g];
+                    v = make_double2(sum.x + v.x, sum.y + v.y);
+                }
+                if (k + 1 == pl.X && g < A) {
+                    const longlong2 top = hi[g];
+                    v = make_double2(v.x + (double)top.x * (1.0 / ROOM_Q), v.y + (double)top.y * (1.0 / ROOM_Q));
+                }
+                r[g] = v;
+            }
+        });
+    if (!FIX) damp_store(st, (uint64_t)k * lanes + entry, s);
+}
+
+// frame m < F with the banded room's term r[m]
+__device__ inline float2 room_frame(const SynPlan& p, uint64_t m, const double2* __restrict__ r) {
+    double2 v = syn_frame64(p, m);
+    const double2 t = r[m];
+    v.x += t.x;
+    v.y += t.y;
+    return make_float2((float)v.x, (float)v.y);
+}
+
+// k_synth_room with the join's r [F] in place of one accumulator's term
+__global__ __launch_bounds__(SYN_THREADS) void k_synth_room_bands(float2* __restrict__ x, SynPlan p, const double2* __restrict__ r) {
+    const uint64_t n = p.F;
+    const uint64_t head = ((uintptr_t)x & 8) && n ? 1 : 0, pairs = (n - head) / 2;
+    float4* __restrict__ x2 = reinterpret_cast<float4*>(x + head);
+    const uint64_t i = (uint64_t)blockIdx.x * SYN_THREADS + threadIdx.x;
+    if (i < pairs) {
+        const float2 a = room_frame(p, head + 2 * i, r), b = room_frame(p, head + 2 * i + 1, r);
+        x2[i] = make_float4(a.x, a.y, b.x, b.y);
+    }
+    if (i == 0) {
+        if (head) x[0] = room_frame(p, 0, r);
+        if (head + 2 * pairs < n) x[n - 1] = room_frame(p, n - 1, r);
     }
 }
 
@@ -404,6 +510,162 @@ inline void room_report(const mc_ir_room& r, uint32_t rate, uint64_t F, double o
     out[7] = A > 0.0 ? K * V / (-S * std::log1p(-A / S)) : 0.0;  // (every wall fully absorbing: the logarithm is -inf and the time 0)
 }
 
+// Every field of the bands, in the struct's order (of beta and air the bands in use), against the session's rate, which
+// room_check has looked at; no engine, no HIP; the message names the field.  Null when they are good.
+inline const char* room_bands_check(const mc_ir_room_bands* b, uint32_t rate) {
+    static thread_local char msg[200];
+    if (!b) return "null bands";
+    if (b->struct_size != sizeof(mc_ir_room_bands)) return "mc_ir_room_bands struct_size mismatch";
+    msg[0] = 0;
+    if (b->n_xovers > MC_DAMP_MAX_XOVERS) {
+        std::snprintf(msg, sizeof(msg), "bands n_xovers %u above %d", b->n_xovers, MC_DAMP_MAX_XOVERS);
+        return msg;
+    }
+    const double top = IEQ_MAX_NYQ * (double)rate;
+    for (uint32_t k = 0; k < b->n_xovers; k++) {
+        const double f = (double)b->xover_hz[k];
+        if (!(std::isfinite(f) && f >= IEQ_MIN_HZ && f <= top)) {
+            std::snprintf(msg, sizeof(msg), "bands xover_hz[%u] %g outside [%g, %g]", k, f, IEQ_MIN_HZ, top);
+            return msg;
+        }
+        if (k && !(b->xover_hz[k] > b->xover_hz[k - 1])) {
+            std::snprintf(msg, sizeof(msg), "bands xover_hz[%u] %g not above xover_hz[%u] %g: the crossovers must ascend strictly", k, f, k - 1,
+                          (double)b->xover_hz[k - 1]);
+            return msg;
+        }
+    }
+    for (uint32_t j = 0; j <= b->n_xovers; j++)
+        for (int w = 0; w < 6; w++)
+            if (!(b->beta[j][w] >= -1.f && b->beta[j][w] <= 1.f)) {
+                std::snprintf(msg, sizeof(msg), "bands beta[%u][%d] %g outside [-1, 1]", j, w, (double)b->beta[j][w]);
+                return msg;
+            }
+    for (uint32_t j = 0; j <= b->n_xovers; j++)
+        if (!(std::isfinite(b->air_db_per_m[j]) && b->air_db_per_m[j] >= 0.f && b->air_db_per_m[j] <= 1.f)) {
+            std::snprintf(msg, sizeof(msg), "bands air_db_per_m[%u] %g outside [0, 1]", j, (double)b->air_db_per_m[j]);
+            return msg;
+        }
+    if (b->flags) {
+        std::snprintf(msg, sizeof(msg), "bands flags %u must be 0", b->flags);
+        return msg;
+    }
+    if (b->reserved) {
+        std::snprintf(msg, sizeof(msg), "bands reserved %u must be 0", b->reserved);
+        return msg;
+    }
+    return nullptr;
+}
+
+// checked bands as the kernels take them: the room's plan once per band (with the microphones, when it has them), each with
+// its band's powers of beta and air constant, and the crossovers
+struct RoomBands {
+    int B;
+    RoomPlan plan[MC_DAMP_MAX_XOVERS + 1];
+    RoomJoin join;
+    double report[16];  // what mc_ir_room_bands_plan and mc_ir_room_bands_info hand out
+};
+
+// what mc_ir_room_bands_plan reports of checked bands in a checked room
+inline void room_bands_report(const mc_ir_room& r, const mc_ir_room_bands& b, double out[16]) {
+    const double Lx = (double)r.size_m[0], Ly = (double)r.size_m[1], Lz = (double)r.size_m[2], V = Lx * Ly * Lz;
+    const double area[6] = {Ly * Lz, Ly * Lz, Lx * Lz, Lx * Lz, Lx * Ly, Lx * Ly};
+    const double K = 24.0 * std::log(10.0) / (double)r.speed;
+    std::fill(out, out + 16, 0.0);
+    out[0] = (double)(b.n_xovers + 1);
+    for (uint32_t k = 0; k < b.n_xovers; k++) out[1 + k] = (double)b.xover_hz[k];
+    for (uint32_t j = 0; j <= b.n_xovers; j++) {
+        double S = 0.0, A = 0.0;
+        for (int w = 0; w < 6; w++) {
+            S += area[w];
+            A += area[w] * (1.0 - (double)b.beta[j][w] * (double)b.beta[j][w]);
+        }
+        const double air = 4.0 * ((double)b.air_db_per_m[j] * std::log(10.0) / 10.0) * V;
+        const double sabine = A + air, eyring = -S * std::log1p(-A / S) + air;  // (every wall fully absorbing: inf, and the time 0)
+        out[4 + j] = sabine > 0.0 ? K * V / sabine : 0.0;
+        out[8 + j] = eyring > 0.0 ? K * V / eyring : 0.0;
+    }
+}
+
+// `base` = the room's plan, its microphones in it when it has them
+inline RoomBands room_bands_plan(const RoomPlan& base, const mc_ir_room& r, const mc_ir_room_bands& b, uint32_t rate) {
+    RoomBands rb{};
+    rb.B = (int)b.n_xovers + 1;
+    rb.join.X = (int)b.n_xovers;
+    for (int k = 0; k < rb.join.X; k++) rb.join.c[k] = ieq_coef(mc_eq_band{MC_EQ_HIGHCUT, b.xover_hz[k], 0.f, 0.70710678f}, rate);
+    for (int j = 0; j < rb.B; j++) {
+        RoomPlan& p = rb.plan[j];
+        p = base;
+        for (int w = 0; w < 6; w++)
+            for (int q = 0; q < MC_ROOM_MAX_ORDER + 2; q++) p.bpow[w][q] = std::pow((double)b.beta[j][w], (double)q);
+        p.air = (double)b.air_db_per_m[j] * std::log2(10.0) / 20.0;
+    }
+    room_bands_report(r, b, rb.report);
+    return rb;
+}
+
+// k_room over room's lattice into acc (room.A frames, zero) and kept (two zeroed counters)
+inline hipError_t room_launch(hipStream_t stream, const RoomPlan& room, unsigned long long* d_acc, unsigned* d_kept) {
+    const uint64_t waves = ((uint64_t)room.total + 63) / 64, per = ROOM_THREADS / 64;
+    const unsigned grid = (unsigned)std::min<uint64_t>((waves + per - 1) / per, ROOM_MAX_GRID);
+    const bool air = room.air != 0.0;
+    if (room.mics && air)
+        hipLaunchKernelGGL((k_room<true, true>), dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
+    else if (air)
+        hipLaunchKernelGGL((k_room<false, true>), dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
+    else if (room.mics)
+        hipLaunchKernelGGL((k_room<true, false>), dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
+    else
+        hipLaunchKernelGGL((k_room<false, false>), dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
+    return hipGetLastError();
+}
+
+// room_generate for a banded room: one k_room per band into its own accumulator, the join, k_synth_room_bands.  One allocation
+// holds the B accumulators and the counters (zeroed with one memset), r and the join's states; kept = band 0's counts (they
+// are a matter of geometry and the same in every band).  With one band there is nothing to join: k_synth_room reads its
+// accumulator.
+inline hipError_t room_generate_bands(hipStream_t stream, const SynPlan& syn, const RoomBands& rb, float2* d_x, uint32_t kept[2]) {
+    const uint64_t A = rb.plan[0].A, F = syn.F;
+    const int B = rb.B, X = rb.join.X;
+    const ChunkGeom cg = chunk_geom(F);
+    const size_t acc_bytes = sizeof(unsigned long long) * 2 * A * (size_t)B, zero_bytes = acc_bytes + 16 * (size_t)B;  // (16: two counters, padded)
+    const size_t r_bytes = X ? sizeof(double2) * F : 0, st_bytes = sizeof(double2) * 2 * (size_t)X * cg.lanes;
+    char* d_all = nullptr;
+    hipError_t er = hipMalloc(&d_all, zero_bytes + r_bytes + st_bytes);
+    if (er != hipSuccess) return er;
+    unsigned long long* d_acc = reinterpret_cast<unsigned long long*>(d_all);
+    unsigned* d_kept = reinterpret_cast<unsigned*>(d_all + acc_bytes);
+    double2* d_r = reinterpret_cast<double2*>(d_all + zero_bytes);
+    double2* d_st = reinterpret_cast<double2*>(d_all + zero_bytes + r_bytes);
+    er = hipMemsetAsync(d_all, 0, zero_bytes, stream);
+    for (int j = 0; j < B && er == hipSuccess; j++) er = room_launch(stream, rb.plan[j], d_acc + 2 * A * (size_t)j, d_kept + 4 * j);
+    const longlong2* acc2 = reinterpret_cast<const longlong2*>(d_acc);
+    if (er == hipSuccess && X) {
+        hipLaunchKernelGGL(k_room_join<false>, dim3(cg.grid, X), dim3(IEQ_THREADS), 0, stream, acc2, A, F, rb.join, 0, d_st, d_r);
+        er = hipGetLastError();
+    }
+    if (er == hipSuccess && X) {
+        hipLaunchKernelGGL(k_damp_carry, dim3(X), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.lanes, cg.nchunks, cg.K, damp_carry(rb.join.c, X, cg.K));
+        er = hipGetLastError();
+    }
+    for (int k = 0; k < X && er == hipSuccess; k++) {
+        hipLaunchKernelGGL(k_room_join<true>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, acc2, A, F, rb.join, k, d_st, d_r);
+        er = hipGetLastError();
+    }
+    if (er == hipSuccess) {
+        const unsigned grid = (unsigned)((std::max<uint64_t>(F / 2, 1) + SYN_THREADS - 1) / SYN_THREADS);
+        if (X)
+            hipLaunchKernelGGL(k_synth_room_bands, dim3(grid), dim3(SYN_THREADS), 0, stream, d_x, syn, d_r);
+        else
+            hipLaunchKernelGGL(k_synth_room, dim3(grid), dim3(SYN_THREADS), 0, stream, d_x, syn, reinterpret_cast<const long long*>(d_acc), A);
+        er = hipGetLastError();
+    }
+    const hipError_t waited = hipStreamSynchronize(stream);  // (also after a failed launch: the memset may still be running)
+    if (er == hipSuccess) er = waited;
+    if (er == hipSuccess) er = hipMemcpy(kept, d_kept, 2 * sizeof(unsigned), hipMemcpyDeviceToHost);
+    (void)hipFree(d_all);
+    return er;
+}
+
 // The syn.F frames with the room's reflections into d_x (8-byte aligned), on `stream`, which is waited for: kept[c] = the
 // images of channel c that arrive before frame E.  The accumulator lives only inside this call.
 inline hipError_t room_generate(hipStream_t stream, const SynPlan& syn, const RoomPlan& room, float2* d_x, uint32_t kept[2]) {
@@ -413,15 +675,7 @@ inline hipError_t room_generate(hipStream_t stream, const SynPlan& syn, const Ro
     if (er != hipSuccess) return er;
     unsigned* d_kept = reinterpret_cast<unsigned*>(d_acc + 2 * room.A);
     er = hipMemsetAsync(d_acc, 0, acc_bytes + 2 * sizeof(unsigned), stream);
-    if (er == hipSuccess) {
-        const uint64_t waves = ((uint64_t)room.total + 63) / 64, per = ROOM_THREADS / 64;
-        const unsigned grid = (unsigned)std::min<uint64_t>((waves + per - 1) / per, ROOM_MAX_GRID);
-        if (room.mics)
-            hipLaunchKernelGGL(k_room<true>, dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
-        else
-            hipLaunchKernelGGL(k_room<false>, dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
-        er = hipGetLastError();
-    }
+    if (er == hipSuccess) er = room_launch(stream, room, d_acc, d_kept);
     if (er == hipSuccess) {
         const uint64_t pairs = syn.F / 2;
         const unsigned grid = (unsigned)((std::max<uint64_t>(pairs, 1) + SYN_THREADS - 1) / SYN_THREADS);

@@ -88,13 +88,13 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline double pan_l(double p) { return p >= 0 ? 1 - p : 1; }  // conv.cu:386
 inline double pan_r(double p) { return p <= 0 ? 1 + p : 1; }  // conv.cu:387
 
-// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _room_info and _room_mics_info report of an IR's last
+// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _room_info, _room_mics_info and _room_bands_info report of an IR's last
 // load: one entry per kind, on when that load had the step or the source (a shape with something on, an eq band or damping count as a shape, and
 // so do a synthesised, a swept and a tailed load), with the numbers the getter hands out (include/mcconv.h says what they are)
-enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_ROOM, FACT_ROOM_MICS, FACT_KINDS };
+enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_KINDS };
 struct IrFact {
     bool on = false;
-    double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double v[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 struct IrEntry {
@@ -3326,10 +3326,13 @@ struct TailStep {
     bool extend;
 };
 
-// the room of a synthesised load as load_ir and shape_stage take it: the plan, and the images the device kept per channel
+// the room of a synthesised load as load_ir and shape_stage take it: the plan, the images the device kept per channel, and
+// with `banded` the bands of mc_ir_room_bands, which are then what is rendered
 struct RoomStep {
     RoomPlan plan;
     uint32_t kept[2];
+    bool banded;
+    RoomBands bands;
 };
 
 // One load as load_ir and shape_stage take it: where the frames come from, and the steps they go through on the device.  The
@@ -3342,7 +3345,8 @@ struct IrLoad {
                                        // anything else sees them; null = they are at the session's rate (the reference)
     const SynPlan* syn = nullptr;      // mc_synth_ir (irsynth.hip.h): the frames are generated on the device
     RoomStep* room = nullptr;          // mc_synth_ir_room (irroom.hip.h; with syn): its reflections are added to the generated
-                                       // frames, and the kept counts are filled in
+                                       // frames, and the kept counts are filled in; room->banded: once per band of
+                                       // room->bands, joined by the band split (mc_synth_ir_room_bands)
     const SweepSource* swp = nullptr;  // mc_load_ir_sweep (irsweep.hip.h): the frames are deconvolved on the device from its recording
     // -- the steps, in the order they run.  Any of tail, eq, damp, syn and swp needs the shape, which may have everything off
     const TailStep* tail = nullptr;      // step 1a, between the source and the shaping (irtail.hip.h; tail->plan.F = the frames at the session's rate)
@@ -3379,6 +3383,7 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
     HIP_TRY(hipMalloc(&d_x, sizeof(float2) * conv));
     double unused[4];
     hipError_t er = ld.swp  ? swp_generate(e->stream, *ld.swp, d_x, &d_rec, &d_u)
+                    : ld.syn && ld.room && ld.room->banded ? room_generate_bands(e->stream, *ld.syn, ld.room->bands, d_x, ld.room->kept)
                     : ld.syn && ld.room ? room_generate(e->stream, *ld.syn, ld.room->plan, d_x, ld.room->kept)
                     : ld.syn ? syn_generate(e->stream, *ld.syn, d_x)
                     : ld.rs ? rs_convert(e->stream, ld.rs[0], ld.rs[1], ld.lr, ld.frames, d_x, conv, unused)
@@ -3407,7 +3412,7 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
     return MC_OK;
 }
 
-// What the seven mc_ir_*_info getters report of the load `ld` that stored `taps` taps; sinfo = the shaping stage's numbers.
+// What the eight mc_ir_*_info getters report of the load `ld` that stored `taps` taps; sinfo = the shaping stage's numbers.
 // Every kind is written, so nothing of an earlier load onto the same index stays behind.
 void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[8]) {
     for (IrFact& f : ir.facts) f.on = false;
@@ -3434,6 +3439,10 @@ void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[
             double m[8];
             room_mics_report(r, m);
             put(FACT_ROOM_MICS, {m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7]});
+        }
+        if (ld.room->banded) {
+            const double* b = ld.room->bands.report;
+            put(FACT_ROOM_BANDS, {b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8], b[9], b[10], b[11], b[12], b[13], b[14], b[15]});
         }
     }
 }
@@ -3769,10 +3778,23 @@ int mc_synth_ir_room(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_s
 
 int mc_synth_ir_room_mics(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_synth* synth, const mc_ir_room* room, const mc_ir_room_mics* mics,
                           const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail) {
+    return mc_synth_ir_room_bands(e, idx, nframes, synth, room, mics, nullptr, shape, eq, damp, tail);
+}
+
+void mc_default_ir_room_bands(mc_ir_room_bands* b) {
+    if (!b) return;
+    std::memset(b, 0, sizeof(*b));
+    b->struct_size = (uint32_t)sizeof(*b);
+    for (auto& band : b->beta)
+        for (float& v : band) v = 0.9f;
+}
+
+int mc_synth_ir_room_bands(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_synth* synth, const mc_ir_room* room, const mc_ir_room_mics* mics,
+                           const mc_ir_room_bands* bands, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail) {
     const bool tailed = tail && tail->mode != MC_TAIL_OFF;
-    if (!room && !mics && !tailed) return mc_synth_ir(e, idx, nframes, synth, shape, eq, damp);
-    // synth, then the room and its microphones, then the tail with F' after F, then damp, eq and shape as in mc_synth_ir, all before
-    // the engine and before any HIP call
+    if (!room && !mics && !bands && !tailed) return mc_synth_ir(e, idx, nframes, synth, shape, eq, damp);
+    // synth, then the room, its microphones and its bands, then the tail with F' after F, then damp, eq and shape as in mc_synth_ir,
+    // all before the engine and before any HIP call
     if (const char* bad = syn_check(synth)) return fail(MC_ERR_ARG, "%s", bad);
     const uint32_t rate = synth->rate;
     const uint64_t F = synth->frames;
@@ -3781,6 +3803,9 @@ int mc_synth_ir_room_mics(mc_engine* e, uint64_t idx, uint64_t nframes, const mc
         if (const char* bad = room_check(room, rate, F)) return fail(MC_ERR_ARG, "%s", bad);
     if (mics)
         if (const char* bad = room_mics_check(mics)) return fail(MC_ERR_ARG, "%s", bad);
+    if (bands && !room) return fail(MC_ERR_ARG, "the bands need a room");
+    if (bands)
+        if (const char* bad = room_bands_check(bands, rate)) return fail(MC_ERR_ARG, "%s", bad);
     if (tailed) {
         if (const char* bad = tail_check(tail, rate)) return fail(MC_ERR_ARG, "%s", bad);
         if (rate < RS_MIN_RATE || rate > RS_MAX_RATE)
@@ -3795,6 +3820,7 @@ int mc_synth_ir_room_mics(mc_engine* e, uint64_t idx, uint64_t nframes, const mc
     RoomStep rstep{};
     if (room) rstep.plan = room_plan(*room, rate, F);
     if (mics) room_plan_mics(rstep.plan, *mics);
+    if (bands) rstep.bands = room_bands_plan(rstep.plan, *room, *bands, rate), rstep.banded = true;
     IrLoad ld;
     ld.syn = &syn, ld.frames = F;
     ld.room = room ? &rstep : nullptr;
@@ -3828,6 +3854,20 @@ int mc_ir_room_mics_plan(const mc_ir_room* room, const mc_ir_room_mics* mics, ui
 
 int mc_ir_room_mics_info(const mc_engine* e, uint64_t idx, double out[8]) {
     return ir_fact(e, idx, FACT_ROOM_MICS, 8, "was not loaded with microphones", out);
+}
+
+int mc_ir_room_bands_plan(const mc_ir_room* room, const mc_ir_room_bands* bands, uint32_t rate, uint64_t frames, double out[16]) {
+    if (frames < 1 || frames > SYN_MAX_FRAMES)
+        return fail(MC_ERR_ARG, "frames %llu outside [1, %llu]", (unsigned long long)frames, (unsigned long long)SYN_MAX_FRAMES);
+    if (const char* bad = room_check(room, rate, frames)) return fail(MC_ERR_ARG, "%s", bad);
+    if (const char* bad = room_bands_check(bands, rate)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!out) return fail(MC_ERR_ARG, "null out");
+    room_bands_report(*room, *bands, out);
+    return MC_OK;
+}
+
+int mc_ir_room_bands_info(const mc_engine* e, uint64_t idx, double out[16]) {
+    return ir_fact(e, idx, FACT_ROOM_BANDS, 16, "was not loaded with bands", out);
 }
 
 int mc_ir_synth_info(const mc_engine* e, uint64_t idx, double out[4]) { return ir_fact(e, idx, FACT_SYNTH, 4, "was not synthesised", out); }

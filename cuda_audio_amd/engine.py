@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McIrDamp, McIrEq, McIrRoom, McIrRoomMics, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McIrDamp, McIrEq, McIrRoom, McIrRoomBands, McIrRoomMics, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -467,6 +467,75 @@ def room_mics_plan(room, mics, rate, frames):
 
 
 @dataclasses.dataclass
+class IrRoomBands:
+    """Walls and air that differ per frequency band in an IrRoom (mc_ir_room_bands, include/mcconv.h): prepare_synth(room=,
+    bands=).  `xovers` are up to three crossover frequencies in Hz, ascending; they cut len(xovers) + 1 bands, low to high.
+    `beta` is the walls' pressure reflection coefficient: one number for every band and wall, one per band, or six per band
+    (IrRoom's order).  `air` is the air's loss in dB per metre: one number or one per band.  The room is rendered once per
+    band and the renderings are joined by IrDamp's band split; with bands, IrRoom.beta is not used for rendering.  Equal bands
+    without air store the unbanded room, bit for bit."""
+
+    xovers: tuple = ()
+    beta: object = 0.9
+    air: object = 0.0
+
+    @classmethod
+    def from_absorption(cls, xovers, alpha, air=0.0):
+        """Bands from energy absorption coefficients alpha in [0, 1], in the shapes `beta` takes: beta = sqrt(1 - alpha)."""
+        def root(a):
+            if isinstance(a, (tuple, list)):
+                return tuple(root(v) for v in a)
+            if not 0.0 <= float(a) <= 1.0:
+                raise ValueError(f"alpha {a} outside [0, 1]")
+            return math.sqrt(1.0 - float(a))
+
+        return cls(xovers=tuple(xovers), beta=root(alpha), air=air)
+
+    def _per_band(self, v, name, walls):
+        B = len(tuple(self.xovers)) + 1
+        v = tuple(v) if isinstance(v, (tuple, list)) else (v,) * B
+        if len(v) != B:
+            raise ValueError(f"{name} takes one value or one per band ({B})")
+        if not walls:
+            return tuple(float(x) for x in v)
+        rows = tuple(tuple(x) if isinstance(x, (tuple, list)) else (x,) * 6 for x in v)
+        if any(len(r) != 6 for r in rows):
+            raise ValueError("beta takes one value, one per band, or six per band")
+        return tuple(tuple(float(x) for x in r) for r in rows)
+
+    def to_c(self):
+        xovers = tuple(self.xovers)
+        if len(xovers) > 3:
+            raise ValueError("at most three crossovers")
+        b = McIrRoomBands()
+        _lib.load().mc_default_ir_room_bands(C.byref(b))
+        b.n_xovers = len(xovers)
+        for k, hz in enumerate(xovers):
+            b.xover_hz[k] = float(hz)
+        for j, row in enumerate(self._per_band(self.beta, "beta", True)):
+            for w in range(6):
+                b.beta[j][w] = row[w]
+        for j, a in enumerate(self._per_band(self.air, "air", False)):
+            b.air_db_per_m[j] = a
+        return b
+
+
+def _bands_report(out):
+    B = int(out[0])
+    return dict(bands=B, xovers=tuple(out[1 + k] for k in range(B - 1)), sabine=tuple(out[4 + j] for j in range(B)),
+                eyring=tuple(out[8 + j] for j in range(B)))
+
+
+def room_bands_plan(room, bands, rate, frames):
+    """What a load of `frames` frames at `rate` would do with `bands` (an IrRoomBands) in `room` (mc_ir_room_bands_plan, host
+    arithmetic only): the number of bands, the crossovers, and Sabine's and Eyring's reverberation times per band in seconds,
+    the air's loss included (0 when nothing absorbs)."""
+    out = (C.c_double * 16)()
+    check(_lib.load().mc_ir_room_bands_plan(C.byref(room.to_c()), C.byref(bands.to_c()), int(rate), int(frames), out))
+    return _bands_report(out)
+
+
+@dataclasses.dataclass
 class Sweep:
     """The exponential sine sweep whose recording prepare_sweep deconvolves (mc_sweep, include/mcconv.h): `frames` frames
     from f1_hz at frame 0 to f2_hz at the last, of peak `amplitude` (0.5 is WavFile's full scale), faded in and out over
@@ -686,7 +755,7 @@ class Convolution:
         else:
             check(self._L.mc_load_ir(self._h, idx, _fp(lr), lr.shape[0], nframes))
 
-    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None, room=None, tail=None, mics=None):
+    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None, room=None, tail=None, mics=None, bands=None):
         """Generate the IR `synth` (an IrSynth) describes on the device and store it at idx (mc_synth_ir): the frames take the
         place of a WAV's at the session's rate, and shape, eq and damp apply to them as in prepare().  A synthesised IR counts
         as shaped: ir_shape_info(idx)["frames"] is synth.frames.  The engine's sample_rate (which eq, damp, room and tail
@@ -694,10 +763,20 @@ class Convolution:
         room (an IrRoom): the reflections of a rectangular room are added to the frames (mc_synth_ir_room); ir_room_info(idx)
         then tells what was rendered.  tail (an IrTail whose mode is not "off"): the tail step on the generated frames, as
         in prepare().  mics (an IrRoomMics, with room): the receivers and the source of the room are directional
-        (mc_synth_ir_room_mics); ir_room_mics_info(idx) then tells the direct sound's factors."""
+        (mc_synth_ir_room_mics); ir_room_mics_info(idx) then tells the direct sound's factors.  bands (an IrRoomBands, with
+        room): the walls and the air differ per frequency band (mc_synth_ir_room_bands); ir_room_bands_info(idx) then tells
+        the bands' reverberation times."""
         s = synth.to_c()
         if not s.rate:
             s.rate = int(self.sample_rate or 0)
+        if bands is not None:
+            if room is None:
+                raise ValueError("the bands need a room")
+            check(self._L.mc_synth_ir_room_bands(self._h, idx, nframes, C.byref(s), C.byref(room.to_c()), C.byref(mics.to_c()) if mics is not None else None,
+                                                 C.byref(bands.to_c()), C.byref(shape.to_c()) if shape is not None else None,
+                                                 C.byref(eq.to_c()) if eq is not None else None, C.byref(damp.to_c()) if damp is not None else None,
+                                                 C.byref(tail.to_c()) if tail is not None else None))
+            return
         if mics is not None:
             if room is None:
                 raise ValueError("the microphones need a room")
@@ -869,6 +948,13 @@ class Convolution:
         out = (C.c_double * 8)()
         check(self._L.mc_ir_room_info(self._h, idx, out))
         return dict(order=int(out[0]), images=(int(out[1]), int(out[2])), direct=(out[3], out[4]), last=int(out[5]), complete=int(out[6]))
+
+    def ir_room_bands_info(self, idx):
+        """The bands of IR idx's load (mc_ir_room_bands_info), as room_bands_plan reports them.  McError (MC_ERR_STATE) for an
+        IR whose last load had no bands."""
+        out = (C.c_double * 16)()
+        check(self._L.mc_ir_room_bands_info(self._h, idx, out))
+        return _bands_report(out)
 
     def ir_room_mics_info(self, idx):
         """What the microphones of IR idx's load did to the direct sound (mc_ir_room_mics_info), as room_mics_plan reports it.

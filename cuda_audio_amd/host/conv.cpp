@@ -77,6 +77,11 @@ void mc_default_ir_room_mics(mc_ir_room_mics*) __attribute__((weak));
 int mc_synth_ir_room_mics(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_room*, const mc_ir_room_mics*, const mc_ir_shape*,
                           const mc_ir_eq*, const mc_ir_damp*, const mc_ir_tail*) __attribute__((weak));
 int mc_ir_room_mics_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+// ... or a room whose walls are the same at every frequency
+void mc_default_ir_room_bands(mc_ir_room_bands*) __attribute__((weak));
+int mc_synth_ir_room_bands(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_room*, const mc_ir_room_mics*, const mc_ir_room_bands*,
+                           const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*, const mc_ir_tail*) __attribute__((weak));
+int mc_ir_room_bands_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 }
 
 namespace {
@@ -188,10 +193,15 @@ uint64_t Convolution::dampFrames(double seconds, double rate) {
 // irRate = sessionRate = 0: the frames are loaded at the rate they have (never with a band of eq on, never with damping).
 // synth: the engine generates the frames (lr null; sessionRate = synth->rate).  sweep: lr is the recording of a sweep, `frames`
 // frames at sessionRate = sweep->sweep.rate, which the engine deconvolves.  room (with synth): its reflections are added to the
-// generated frames, and a tail applies to them; mics (with room): its receivers and its source are directional
+// generated frames, and a tail applies to them; mics (with room): its receivers and its source are directional; bands (with
+// room): its walls and its air differ per frequency band
 void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
                              const IrEq& eq, const IrDamp& damp, const mc_ir_synth* synth, const SweepLoad* sweep, const mc_ir_tail* tail,
-                             const mc_ir_room* room, const mc_ir_room_mics* mics) {
+                             const mc_ir_room* room, const mc_ir_room_mics* mics, const mc_ir_room_bands* bands) {
+    if (bands && (!mc_synth_ir_room_bands || !mc_default_ir_room_bands || !mc_ir_room_bands_info)) {
+        Log::error("conv", "the engine has no frequency bands in its rooms (mc_synth_ir_room_bands)");
+        std::exit(2);
+    }
     if (mics && (!mc_synth_ir_room_mics || !mc_default_ir_room_mics || !mc_ir_room_mics_info)) {
         Log::error("conv", "the engine has no directional microphones in its rooms (mc_synth_ir_room_mics)");
         std::exit(2);
@@ -250,7 +260,8 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         d.origin = damp.origin;
     }
     if (synth) {  // (what the engine refuses of a generated IR is the index line's fault: a message and exit 2, no abort)
-        const int rc = mics   ? mc_synth_ir_room_mics(_engine, idx, nframes, synth, room, mics, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
+        const int rc = bands  ? mc_synth_ir_room_bands(_engine, idx, nframes, synth, room, mics, bands, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
+                       : mics ? mc_synth_ir_room_mics(_engine, idx, nframes, synth, room, mics, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
                        : room ? mc_synth_ir_room(_engine, idx, nframes, synth, room, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
                               : mc_synth_ir(_engine, idx, nframes, synth, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d);
         if (rc != MC_OK) {
@@ -269,6 +280,19 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
             check(mc_ir_room_mics_info(_engine, idx, mi), "mc_ir_room_mics_info");
             Log::info(name, "IR %zu microphones: the direct sound leaves the source at %.4f and %.4f, is received at %.4f and %.4f, factors %.4f and %.4f",
                       idx, mi[0], mi[1], mi[2], mi[3], mi[4], mi[5]);
+        }
+        if (bands) {
+            double bi[16];
+            check(mc_ir_room_bands_info(_engine, idx, bi), "mc_ir_room_bands_info");
+            std::string sabine, eyring;
+            for (int j = 0; j < (int)bi[0]; j++) {
+                char one[32];
+                std::snprintf(one, sizeof(one), "%s%.3f", j ? " / " : "", bi[4 + j]);
+                sabine += one;
+                std::snprintf(one, sizeof(one), "%s%.3f", j ? " / " : "", bi[8 + j]);
+                eyring += one;
+            }
+            Log::info(name, "IR %zu bands: %d, low to high Sabine %s s, Eyring %s s", idx, (int)bi[0], sabine.c_str(), eyring.c_str());
         }
         double si[4];
         check(mc_ir_synth_info(_engine, idx, si), "mc_ir_synth_info");
@@ -940,11 +964,24 @@ mc_ir_room_mics Convolution::roomMics(const IrRoom& room) {
     return m;
 }
 
+mc_ir_room_bands Convolution::roomBands(const IrRoom& room) {
+    mc_ir_room_bands b;
+    mc_default_ir_room_bands(&b);
+    b.n_xovers = room.nXovers;
+    for (uint32_t k = 0; k < room.nXovers; k++) b.xover_hz[k] = room.xovers[k];
+    for (uint32_t j = 0; j <= room.nXovers; j++) {
+        for (int w = 0; w < 6; w++) b.beta[j][w] = room.nBetas ? room.betas[j] : room.beta[w];
+        b.air_db_per_m[j] = room.air[room.nAir > 1 ? j : 0];
+    }
+    return b;
+}
+
 bool Convolution::parseRoom(const std::string& line, IrRoom& out, std::string& why) {
     static const char* form =
         "room:LENGTH_S:LX,LY,LZ:SX,SY,SZ:RX,RY,RZ[:key=value,...] with keys beta (one value, or six separated by '/'), order, spacing, axis (x|y|z), "
         "speed, gain, last, mic (omni|subcardioid|cardioid|supercardioid|hypercardioid|fig8 or a number in [0, 1]; P or P/P), aim and tilt (degrees; "
-        "one value or L/R), src, srcaim, srctilt, t60 and synth:'s keys";
+        "one value or L/R), src, srcaim, srctilt, xover (HZ[/HZ[/HZ]]), betas (one value per band, separated by '/'), air (dB per metre: one value, or one "
+        "per band), t60 and synth:'s keys";
     std::vector<std::string> parts;
     for (size_t at = 0;;) {
         const size_t colon = line.find(':', at);
@@ -1000,7 +1037,18 @@ bool Convolution::parseRoom(const std::string& line, IrRoom& out, std::string& w
         }
         return true;
     };
+    // one to `most` numbers separated by '/', each within [lo, hi]
+    const auto upTo = [&](const std::string& text, size_t most, double lo, double hi, float* v, uint32_t& count) {
+        for (count = 1; count <= most; count++)
+            if (numbers(text, '/', count, v)) {
+                for (uint32_t k = 0; k < count; k++)
+                    if (!((double)v[k] >= lo && (double)v[k] <= hi)) return false;
+                return true;
+            }
+        return false;
+    };
     IrRoom room;
+    std::string betasText, airText;
     double length = 0.0;
     if (!number(parts[1], length) || !(length > 0.0)) {
         why = "LENGTH_S '" + parts[1] + "' is not a length in seconds, > 0";
@@ -1052,6 +1100,18 @@ bool Convolution::parseRoom(const std::string& line, IrRoom& out, std::string& w
         } else if (key == "mic" || key == "aim" || key == "tilt") {
             good = key == "mic" ? pair(text, 0.0, room.micPattern) : key == "aim" ? pair(text, 360.0, room.micAim) : pair(text, 90.0, room.micTilt);
             room.directional = true;
+        } else if (key == "xover") {
+            good = upTo(text, MC_DAMP_MAX_XOVERS, 10.0, 172800.0, room.xovers, room.nXovers);  // (the engine checks them against the client's rate)
+            for (uint32_t k = 1; good && k < room.nXovers; k++) good = room.xovers[k] > room.xovers[k - 1];
+            room.banded = true;
+        } else if (key == "betas") {
+            good = upTo(text, MC_DAMP_MAX_XOVERS + 1, -1.0, 1.0, room.betas, room.nBetas);
+            betasText = text;
+            room.banded = true;
+        } else if (key == "air") {
+            good = upTo(text, MC_DAMP_MAX_XOVERS + 1, 0.0, 1.0, room.air, room.nAir);
+            airText = text;
+            room.banded = true;
         } else if (key == "src") {
             good = pattern(text, room.sourcePattern);
             room.directional = true;
@@ -1068,6 +1128,15 @@ bool Convolution::parseRoom(const std::string& line, IrRoom& out, std::string& w
         }
         at = comma + 1;
         if (comma == list.size()) break;
+    }
+    // (the keys come in any order: the counts are compared once every key has been read)
+    if (room.nBetas && room.nBetas != room.nXovers + 1) {
+        why = "'" + betasText + "' is no value for betas: one value for each of the " + std::to_string(room.nXovers + 1) + " bands xover cuts";
+        return false;
+    }
+    if (room.nAir > 1 && room.nAir != room.nXovers + 1) {
+        why = "'" + airText + "' is no value for air: one value, or one for each of the " + std::to_string(room.nXovers + 1) + " bands xover cuts";
+        return false;
     }
     if (!parseSynth("synth:" + parts[1] + ":" + t60 + ":" + synthKeys, room.late, why)) {
         const size_t at = why.find("synth:LENGTH_S");
@@ -1260,6 +1329,10 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
         return;
     }
     if (p.generated) {
+        if (p.roomed && p.room.banded && !mc_default_ir_room_bands) {
+            Log::error("conv", "the engine has no frequency bands in its rooms (mc_synth_ir_room_bands)");
+            std::exit(2);
+        }
         if (p.roomed && p.room.directional && !mc_default_ir_room_mics) {
             Log::error("conv", "the engine has no directional microphones in its rooms (mc_synth_ir_room_mics)");
             std::exit(2);
@@ -1277,8 +1350,10 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
             const mc_ir_room r = roomFrames(p.room, (double)samplerate);
             mc_ir_room_mics m;
             if (p.room.directional) m = roomMics(p.room);
+            mc_ir_room_bands b;
+            if (p.room.banded) b = roomBands(p.room);
             loadShaped(p.idx, nullptr, s.frames, p.nframes, s.rate, s.rate, shape, p.eq, p.damp, &s, nullptr, _tailOn ? &_tailNow : nullptr, &r,
-                       p.room.directional ? &m : nullptr);
+                       p.room.directional ? &m : nullptr, p.room.banded ? &b : nullptr);
             return;
         }
         const mc_ir_synth s = synthFrames(p.synth, (double)samplerate);

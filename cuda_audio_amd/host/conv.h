@@ -184,6 +184,10 @@ public:
     // of the line's keys mic, aim, tilt, src, srcaim and srctilt, and such a room is loaded through mc_synth_ir_room_mics, in both
     // renderings of the tail flow, with one more log line: the direct sound's factors.  Patterns are alpha of
     // g = alpha + (1 - alpha) cos, angles degrees (azimuth from +x towards +y, tilt towards +z), left then right.
+    // Walls and air per frequency band (mc_ir_room_bands and mc_synth_ir_room_bands): `banded` is set by any of the line's keys
+    // xover, betas and air, and such a room is loaded through mc_synth_ir_room_bands, in both renderings of the tail flow, with one
+    // more log line: Sabine's and Eyring's reverberation times per band.  xover cuts nXovers + 1 bands; betas gives every band one
+    // value for its six walls (without it every band has `beta`), air one loss in dB per metre for every band or one per band.
     struct IrRoom {
         float size[3] = {5.0f, 4.0f, 3.0f}, source[3] = {1.0f, 1.5f, 1.2f}, receiver[3] = {3.5f, 2.0f, 1.5f};
         float beta[6] = {0.9f, 0.9f, 0.9f, 0.9f, 0.9f, 0.9f};
@@ -195,6 +199,10 @@ public:
         bool directional = false;
         float micPattern[2] = {1.0f, 1.0f}, micAim[2] = {0.0f, 0.0f}, micTilt[2] = {0.0f, 0.0f};
         float sourcePattern = 1.0f, sourceAim = 0.0f, sourceTilt = 0.0f;
+        bool banded = false;
+        uint32_t nXovers = 0, nBetas = 0, nAir = 0;  // values given by xover, betas and air
+        float xovers[MC_DAMP_MAX_XOVERS] = {0.0f, 0.0f, 0.0f};
+        float betas[MC_DAMP_MAX_XOVERS + 1] = {0.9f, 0.9f, 0.9f, 0.9f}, air[MC_DAMP_MAX_XOVERS + 1] = {0.0f, 0.0f, 0.0f, 0.0f};
         IrSynth late;
         IrRoom() { late.late = 0.0f; }
     };
@@ -202,13 +210,16 @@ public:
     // A line of an IR index that starts with "room:" - room:LENGTH_S:LX,LY,LZ:SX,SY,SZ:RX,RY,RZ[:key=value,...], keys beta (one
     // value, or six separated by '/'), order, spacing, axis (x|y|z), speed, gain, last (seconds), mic (a pattern: omni, subcardioid,
     // cardioid, supercardioid, hypercardioid, fig8 or a number in [0, 1]; P or P/P), aim and tilt (degrees; one value or L/R),
-    // src, srcaim and srctilt (the source's), and for the late field t60 and parseSynth's keys - as an IrRoom.  False, with the
+    // src, srcaim and srctilt (the source's), xover (HZ[/HZ[/HZ]]), betas (one value per band, separated by '/') and air (dB per
+    // metre: one value, or one per band), and for the late field t60 and parseSynth's keys - as an IrRoom.  False, with the
     // reason in `why`, for a malformed line.
     static bool parseRoom(const std::string& line, IrRoom& out, std::string& why);
     // mc_ir_room of an IrRoom at rate Hz
     static mc_ir_room roomFrames(const IrRoom& room, double rate);
     // mc_ir_room_mics of a directional IrRoom
     static mc_ir_room_mics roomMics(const IrRoom& room);
+    // mc_ir_room_bands of a banded IrRoom
+    static mc_ir_room_bands roomBands(const IrRoom& room);
 
     // An IR the engine deconvolves from the recording of an exponential sine sweep played through a room (mc_sweep and
     // mc_load_ir_sweep of include/mcconv.h; no reference equivalent): times in seconds, turned into frames at the client's
@@ -412,7 +423,7 @@ private:
     void loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
                     const IrEq& eq = IrEq(), const IrDamp& damp = IrDamp(), const mc_ir_synth* synth = nullptr,
                     const SweepLoad* sweep = nullptr, const mc_ir_tail* tail = nullptr, const mc_ir_room* room = nullptr,
-                    const mc_ir_room_mics* mics = nullptr);
+                    const mc_ir_room_mics* mics = nullptr, const mc_ir_room_bands* bands = nullptr);
     void pushParams();
     void pullVsteps();
 };

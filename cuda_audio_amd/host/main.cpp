@@ -29,6 +29,9 @@
 // Directional microphones and a directional source in that room: mic=P or mic=P/P (left/right; P one of omni, subcardioid,
 // cardioid, supercardioid, hypercardioid, fig8, or alpha in [0, 1]), aim=AZ or AZ/AZ and tilt=EL or EL/EL in degrees (azimuth
 // from +x towards +y, tilt towards +z), src=P, srcaim=AZ, srctilt=EL; one more log line tells the direct sound's factors.
+// Walls and air per frequency band in that room: xover=HZ[/HZ[/HZ]] cuts up to four bands, betas=B[/B...] gives every band one
+// reflection coefficient for its six walls, air=DB[/DB...] the air's loss in dB per metre (one value, or one per band); the room
+// is rendered once per band and joined by --ir-damp's band split, and one more log line tells the bands' reverberation times.
 // A line that starts with "sweep:" is an IR the engine deconvolves from the recording of a sine sweep,
 // sweep:RECORDING.wav:LENGTH_S:F1:F2[:key=value,...] with keys amp, fadein, fadeout, offset, length (Convolution::parseSweep;
 // times in seconds, the recording at the client's sample rate); the --ir-* options apply to it as to a WAV.

@@ -835,6 +835,58 @@ int mc_ir_room_mics_plan(const mc_ir_room *room, const mc_ir_room_mics *mics, ui
  * for a room without them) */
 int mc_ir_room_mics_info(const mc_engine *e, uint64_t idx, double out[8]);
 
+/* Walls and air that differ per frequency band in the room of mc_ir_room: carpet, curtains, glass and air take the highs
+ * faster than the lows.  The room is rendered once per band with that band's walls and air loss, and the renderings are
+ * joined by mc_ir_damp's band split, whose bands sum to their input exactly: no filter per image.  No reference equivalent.
+ *
+ * Bands.  X = n_xovers crossovers cut B = X + 1 bands, low to high; crossover k = 1 .. X is mc_ir_damp's: two identical
+ *   high-cut sections at xover_hz[k - 1], q = 0.70710678f, at rate = synth->rate.
+ * Band rendering.  Band j = 0 .. X is the room of mc_ir_room (and of mc_ir_room_mics when given) with beta[j] in place of
+ *   room->beta and with each channel's amplitude multiplied by the air factor exp2(-(d_c k_j)),
+ *   k_j = (double)air_db_per_m[j] * log2(10) / 20, made on the host: a_c = ((b / d_c) air_c) (gs_c gr_c), in that order.  Where
+ *   air_db_per_m[j] == 0 no factor is applied at all: that band's rendering is mc_ir_room's, bit for bit.  tau, k0, f, the keep
+ *   rule, the taps, the quantum 2^-40, E, A = min(E + 16, F), the automatic order and the kept counts (geometry only) are the
+ *   room's and the same in every band.  Each band has its own 64-bit accumulator acc_j[A][2]; the bound on the integer sum
+ *   holds per band, because the air factor is <= 1.
+ * The join.  For k = 1 .. X: D_k[m] = (double)(acc_(k-1)[m] - acc_k[m]) 2^-40 for m < A and 0 for A <= m < F, the difference taken
+ *   in int64 (both terms lie inside 2^62) and converted once (exact below 2^53, which every allowed room stays);
+ *   P_k = D_k through crossover k's two sections from rest at frame 0 over all F frames: the ringing past the accumulator
+ *   belongs to the IR;
+ *   r[m] = (P_1[m] + .. + P_X[m]) + (m < A ? (double)acc_X[m] 2^-40 : 0), added low to high, the accumulator's term last.
+ *   This is sum_j B_j(acc_j) over mc_ir_damp's bands B_0 = P_1, B_j = P_(j+1) - P_j, B_X = x - P_X, written by its differences.
+ * Frame.  (float)(late + direct + reflections + r), rounded once.
+ * Equal bands.  With X = 0, or with every D_k identically zero, every P_k is +0.0 and r is mc_ir_room's term: a banded room whose
+ *   bands are all alike (and without air) stores the bits of the unbanded room.
+ * With bands, room->beta is still checked as before but is not used for rendering. */
+typedef struct {
+    uint32_t struct_size;                          /* sizeof(mc_ir_room_bands) = 140 */
+    uint32_t n_xovers;                             /* X: 0 .. MC_DAMP_MAX_XOVERS */
+    float xover_hz[MC_DAMP_MAX_XOVERS];            /* the first n_xovers: finite, [10, 0.45 synth->rate], strictly ascending */
+    float beta[MC_DAMP_MAX_XOVERS + 1][6];         /* band j = 0 .. n_xovers: the six walls in mc_ir_room's order, [-1, 1] */
+    float air_db_per_m[MC_DAMP_MAX_XOVERS + 1];    /* band j: the air's loss in dB per metre, finite, [0, 1] */
+    uint32_t flags;                                /* must be 0 */
+    uint32_t reserved;                             /* must be 0 */
+} mc_ir_room_bands;
+/* n_xovers 0 (one band), every beta 0.9, no air loss */
+void mc_default_ir_room_bands(mc_ir_room_bands *b);
+/* mc_synth_ir_room_mics with `bands` in the room.  With bands NULL the call is mc_synth_ir_room_mics itself, bit for bit.
+ * bands without room is MC_ERR_ARG ("the bands need a room").  Checked in mc_synth_ir_room_mics' order, the bands field by
+ * field in the struct's order right after the microphones and before the tail (entries of the bands in use; the crossovers
+ * against synth->rate); the message names the field, nothing of the engine or the device is touched before every check has
+ * passed, and the engine stays as it was on a refusal. */
+int mc_synth_ir_room_bands(mc_engine *e, uint64_t idx, uint64_t nframes, const mc_ir_synth *synth, const mc_ir_room *room,
+                           const mc_ir_room_mics *mics, const mc_ir_room_bands *bands, const mc_ir_shape *shape, const mc_ir_eq *eq,
+                           const mc_ir_damp *damp, const mc_ir_tail *tail);
+/* What a load of `frames` frames at `rate` would do with `bands` in `room`: out[0] = B; out[1..3] = the crossovers (Hz; unused
+ * ones 0); out[4..7] = Sabine's and out[8..11] = Eyring's reverberation time per band (s; unused bands 0), mc_ir_room_plan's
+ * formulas on beta[j] with 4 m_j V added to the absorption area S abar and to -S ln(1 - abar), m_j = air_db_per_m[j] ln(10) / 10
+ * the air's energy loss in nepers per metre; a time is 0 when nothing absorbs; out[12..15] = 0.  The room is checked as by
+ * mc_ir_room_plan, then the bands.  Host arithmetic only: no engine and no HIP call. */
+int mc_ir_room_bands_plan(const mc_ir_room *room, const mc_ir_room_bands *bands, uint32_t rate, uint64_t frames, double out[16]);
+/* The same sixteen numbers of the IR's last load; MC_ERR_STATE unless that load had bands (mc_ir_room_info and
+ * mc_ir_room_mics_info still answer for such a load) */
+int mc_ir_room_bands_info(const mc_engine *e, uint64_t idx, double out[16]);
+
 int mc_num_irs(const mc_engine *e);
 /* out[0..3] = sum h_L, sum h_R, sum h_L(-1)^m, sum h_R(-1)^m of the truncated IR; out[4] = taps, out[5] = partitions */
 int mc_ir_info(const mc_engine *e, uint64_t idx, double out[6]);
