@@ -1,6 +1,7 @@
 // chunkwalk.hip.h — the walk of a workgroup over its chunks, shared by the chunked-recurrence kernels of the IR tools:
 // k_eq_chunk (ireq.hip.h), k_damp_chunk (irdamp.hip.h), k_tail_chunk (irtail.hip.h), k_flr_band (irfloor.hip.h) and k_dec_sum
-// (irdecay.hip.h).  No reference equivalent.
+// (irdecay.hip.h).  No reference equivalent.  The host side of the measurements that launch them (the scratch, the origin, the
+// order of a row group's launches) is irdecay.hip.h's Measure.
 //
 // The n taps of a buffer are cut into chunks of IEQ_CHUNK, a function of n alone; a lane owns one (chunk, channel) and runs a
 // recurrence over its chunk's taps in order, first to last or last to first.  What the recurrence is, where a tap comes from and

@@ -35,6 +35,10 @@
 //
 // Scratch (double2 [N], the chunk states, the partials) is allocated by the call and freed before it returns: an engine
 // nobody asks holds nothing.
+//
+// The host side.  N, the scratch, the origin, a row group's fill and filter, the backward sum and the fetches are the operations
+// of one struct, Measure, in the host section below (not in a header of its own: irfloor, irdensity, iriacc and irsti.hip.h include
+// this one for its kernels already).  Their *_measure functions are written on it as dec_measure is.
 #pragma once
 #include <limits>
 
@@ -306,60 +310,76 @@ inline hipError_t dec_origin(hipStream_t stream, const float2* d_x, uint64_t N, 
     return hipSuccess;
 }
 
-// d_buf [N] = a row group's doubles (mc_ir_decay's step 2): the taps as double and, with centre_hz, run through that band's two
-// identical sections, the second riding as the `nxt` stage of the first's fix-up.  d_st: the chunk states, double2 [cg.lanes].
-inline hipError_t dec_group(hipStream_t stream, const float2* d_x, uint64_t N, const ChunkGeom& cg, const float* centre_hz, float q, uint32_t rate,
-                            double2* d_buf, double2* d_st) {
-    hipLaunchKernelGGL(k_dec_fill, dim3((unsigned)((N + ISH_THREADS - 1) / ISH_THREADS)), dim3(ISH_THREADS), 0, stream, d_x, N, d_buf);
-    hipError_t er = hipGetLastError();
-    if (!centre_hz) return er;
-    IeqStage sec{}, off{};
-    sec.c = dec_coef(*centre_hz, q, rate), sec.on = 1;
-    const IeqCarry cm = ieq_carry(sec.c, cg.K);
-    for (int pass = 0; pass < 3 && er == hipSuccess; pass++) {
-        if (pass > 0) {
-            hipLaunchKernelGGL(k_eq_carry, dim3(1), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.nchunks, cg.K, cm.M, cm.MK);
-            er = hipGetLastError();
-        }
-        if (er != hipSuccess) break;
-        hipLaunchKernelGGL(k_eq_chunk, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pass > 0 ? sec : off, pass < 2 ? sec : off, d_st);
-        er = hipGetLastError();
+// The host side of a measurement: what dec_measure here and flr_measure, den_measure, iacc_measure and sti_measure (irfloor,
+// irdensity, iriacc, irsti.hip.h) do around their own kernels.  It lives in this host section, not in a header of its own, because
+// it needs this header's kernels and those four include this header already.  A *_measure constructs it (the span N and the chunk
+// geometry), opens it (the scratch and the origin o) and strings its own launches between the operations below; every one of them
+// does nothing once `er` is set, so a *_measure tests m.er where it has to stop.  The scratch goes when the struct goes: nothing
+// stays allocated on any path.
+struct Measure {
+    hipStream_t stream;
+    const float2* d_x;
+    uint64_t N, o = 0;                           // the taps analysed are [0, N); the origin among them
+    ChunkGeom cg;                                // k_eq_chunk, k_dec_sum and the carries over N taps
+    hipError_t er = hipSuccess;
+    double2 *d_buf = nullptr, *d_st = nullptr;   // a row group's doubles [N]; the chunk states
+    double *d_tot = nullptr, *d_part = nullptr, *d_fin = nullptr;  // the chunk totals [cg.lanes]; partials [part_cap]; folded sums
+    size_t part_cap = 0;
+
+    Measure(hipStream_t stream, const float2* d_x, uint64_t n, uint64_t end) : stream(stream), d_x(d_x), N(dec_span(end, n)), cg(chunk_geom(N)) {}
+    Measure(const Measure&) = delete;
+    ~Measure() {
+        for (void* p : {(void*)d_fin, (void*)d_part, (void*)d_tot, (void*)d_st, (void*)d_buf}) (void)hipFree(p);
     }
-    return er;
-}
-
-// The whole measurement of the n stored taps d_x for a checked query.  rows, curve, info as mc_ir_decay describes them.
-// Synchronises the stream; leaves nothing allocated.
-inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n, const mc_decay_query& q, double* rows, double* curve,
-                              uint64_t info[2]) {
-    const uint64_t N = dec_span(q.end, n);
-    const uint32_t K = q.curve_points, npick = DEC_PICK_HEAD + K;
-    const unsigned grid = (unsigned)((N + ISH_THREADS - 1) / ISH_THREADS);                    // k_dec_fill
-    const ChunkGeom cg = chunk_geom(N);                                                       // k_eq_chunk, k_dec_sum and the carries
-    const unsigned rgrid = std::min<unsigned>(DEC_GRID, grid);                                // k_dec_members, k_dec_fit
-    const unsigned ogrid = dec_origin_grid(N);                                                // the onset's walks
-    const size_t npart = std::max<size_t>({(size_t)DEC_FIT_PART * rgrid, (size_t)2 * npick, (size_t)ogrid});
-    double2 *d_buf = nullptr, *d_st = nullptr;
-    double *d_tot = nullptr, *d_part = nullptr;
-    std::vector<double> part(npart);
-    hipError_t er = hipMalloc(&d_buf, sizeof(double2) * N);
-    if (er == hipSuccess) er = hipMalloc(&d_st, sizeof(double2) * (size_t)cg.lanes);
-    if (er == hipSuccess) er = hipMalloc(&d_tot, sizeof(double) * (size_t)cg.lanes);
-    if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * npart);
-    const auto launched = [&] { er = hipGetLastError(); };
-    const auto fetch = [&](size_t count) {
-        if (er == hipSuccess) er = hipMemcpyAsync(part.data(), d_part, sizeof(double) * count, hipMemcpyDeviceToHost, stream);
+    template <class T>
+    void alloc(T** p, size_t count) {
+        if (er == hipSuccess && count) er = hipMalloc(p, sizeof(T) * count);
+    }
+    // The scratch, each buffer with the elements the measurement names (0: none; d_part holds the origin's partials at least),
+    // then the origin (mc_ir_decay's step 1).  Synchronises the stream when onset_db < 0.  st0: what d_st starts as, nst double2
+    // of the host that go onto the stream ahead of the origin's kernels (mc_ir_density's table); the caller keeps them until the
+    // stream has run dry.
+    void open(float onset_db, size_t nbuf, size_t nst, size_t ntot, size_t npart, size_t nfin, const double2* st0 = nullptr) {
+        part_cap = std::max<size_t>(npart, dec_origin_grid(N));
+        alloc(&d_buf, nbuf), alloc(&d_st, nst), alloc(&d_tot, ntot), alloc(&d_part, part_cap), alloc(&d_fin, nfin);
+        if (er == hipSuccess && st0) er = hipMemcpyAsync(d_st, st0, sizeof(double2) * nst, hipMemcpyHostToDevice, stream);
+        if (er == hipSuccess) er = dec_origin(stream, d_x, N, onset_db, d_part, &o);
+    }
+    // d_part [count] at least: what it held is dropped
+    void grow_part(size_t count) {
+        if (er != hipSuccess || count <= part_cap) return;
+        (void)hipFree(d_part);
+        d_part = nullptr, part_cap = count;
+        er = hipMalloc(&d_part, sizeof(double) * part_cap);
+    }
+    void launched() { er = hipGetLastError(); }
+    // dst = src [bytes] of the device, and the stream has run dry
+    void fetch(void* dst, const void* src, size_t bytes) {
+        if (er == hipSuccess) er = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, stream);
         if (er == hipSuccess) er = hipStreamSynchronize(stream);
-        return er;
-    };
-
-    // origin: the shaped load's onset over the taps that are analysed
-    uint64_t o = 0;
-    if (er == hipSuccess) er = dec_origin(stream, d_x, N, q.onset_db, d_part, &o);
-    const uint64_t k50 = o + (uint64_t)std::floor(0.05 * (double)q.rate + 0.5), k80 = o + (uint64_t)std::floor(0.08 * (double)q.rate + 0.5);
-
-    for (uint32_t g = 0; g <= q.n_bands && er == hipSuccess; g++) {
-        er = dec_group(stream, d_x, N, cg, g ? &q.centre_hz[g - 1] : nullptr, q.q, q.rate, d_buf, d_st);
+    }
+    // d_buf [N] = a row group's doubles (mc_ir_decay's step 2): the taps as double and, with centre_hz, run through that band's two
+    // identical sections, the second riding as the `nxt` stage of the first's fix-up.  d_st: double2 [cg.lanes].
+    void group(const float* centre_hz, float q, uint32_t rate) {
+        if (er != hipSuccess) return;
+        hipLaunchKernelGGL(k_dec_fill, dim3((unsigned)((N + ISH_THREADS - 1) / ISH_THREADS)), dim3(ISH_THREADS), 0, stream, d_x, N, d_buf);
+        launched();
+        if (!centre_hz) return;
+        IeqStage sec{}, off{};
+        sec.c = dec_coef(*centre_hz, q, rate), sec.on = 1;
+        const IeqCarry cm = ieq_carry(sec.c, cg.K);
+        for (int pass = 0; pass < 3 && er == hipSuccess; pass++) {
+            if (pass > 0) {
+                hipLaunchKernelGGL(k_eq_carry, dim3(1), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.nchunks, cg.K, cm.M, cm.MK);
+                launched();
+            }
+            if (er != hipSuccess) break;
+            hipLaunchKernelGGL(k_eq_chunk, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pass > 0 ? sec : off, pass < 2 ? sec : off, d_st);
+            launched();
+        }
+    }
+    // d_buf = EDC, the backward sum over [o, N) (the file's head).  d_tot: double [cg.lanes].
+    void edc() {
         if (er == hipSuccess) {
             hipLaunchKernelGGL(k_dec_sum<false>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
             launched();
@@ -372,12 +392,34 @@ inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n,
             hipLaunchKernelGGL(k_dec_sum<true>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
             launched();
         }
-        if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_dec_pick, dim3((npick + ISH_THREADS - 1) / ISH_THREADS), dim3(ISH_THREADS), 0, stream, d_buf, o, N, k50, k80, K,
-                               reinterpret_cast<double2*>(d_part));
-            launched();
+    }
+    void info(uint64_t out[2]) const { out[0] = o, out[1] = N; }
+};
+
+// The whole measurement of the n stored taps d_x for a checked query.  rows, curve, info as mc_ir_decay describes them.
+// Synchronises the stream; leaves nothing allocated.
+inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n, const mc_decay_query& q, double* rows, double* curve,
+                              uint64_t info[2]) {
+    Measure m(stream, d_x, n, q.end);
+    const uint64_t N = m.N;
+    const uint32_t K = q.curve_points, npick = DEC_PICK_HEAD + K;
+    const unsigned rgrid = std::min<unsigned>(DEC_GRID, (unsigned)((N + ISH_THREADS - 1) / ISH_THREADS));  // k_dec_members, k_dec_fit
+    // (a vector of this function's own, not a member of m: the loops over it below vectorise only while its address stays here)
+    std::vector<double> part(std::max<size_t>((size_t)DEC_FIT_PART * rgrid, (size_t)2 * npick));
+    m.open(q.onset_db, N, m.cg.lanes, m.cg.lanes, part.size(), 0);
+    const uint64_t o = m.o;
+    const uint64_t k50 = o + (uint64_t)std::floor(0.05 * (double)q.rate + 0.5), k80 = o + (uint64_t)std::floor(0.08 * (double)q.rate + 0.5);
+
+    for (uint32_t g = 0; g <= q.n_bands && m.er == hipSuccess; g++) {
+        m.group(g ? &q.centre_hz[g - 1] : nullptr, q.q, q.rate);
+        m.edc();
+        if (m.er == hipSuccess) {
+            hipLaunchKernelGGL(k_dec_pick, dim3((npick + ISH_THREADS - 1) / ISH_THREADS), dim3(ISH_THREADS), 0, stream, m.d_buf, o, N, k50, k80, K,
+                               reinterpret_cast<double2*>(m.d_part));
+            m.launched();
         }
-        if (fetch((size_t)2 * npick) != hipSuccess) break;
+        m.fetch(part.data(), m.d_part, sizeof(double) * 2 * npick);
+        if (m.er != hipSuccess) break;
         std::vector<double> pick[DEC_SETS];
         for (int s = 0; s < DEC_SETS; s++) {
             pick[s].resize(npick);
@@ -385,9 +427,10 @@ inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n,
         }
         DecLevels lv{};
         for (int s = 0; s < DEC_SETS; s++) lv.E[s] = pick[s][0];
-        hipLaunchKernelGGL(k_dec_members, dim3(rgrid), dim3(ISH_THREADS), 0, stream, d_buf, o, N, lv, d_part);
-        launched();
-        if (fetch((size_t)DEC_MEMBER_PART * rgrid) != hipSuccess) break;
+        hipLaunchKernelGGL(k_dec_members, dim3(rgrid), dim3(ISH_THREADS), 0, stream, m.d_buf, o, N, lv, m.d_part);
+        m.launched();
+        m.fetch(part.data(), m.d_part, sizeof(double) * DEC_MEMBER_PART * rgrid);
+        if (m.er != hipSuccess) break;
         double cnt[DEC_FITS], tsum[DEC_SETS] = {0.0, 0.0, 0.0};
         for (int f = 0; f < DEC_FITS; f++) cnt[f] = 0.0, lv.first[f] = N;
         for (unsigned b = 0; b < rgrid; b++) {
@@ -400,9 +443,10 @@ inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n,
             tsum[1] += p[2 * DEC_FITS + 1];
         }
         tsum[2] = tsum[0] + tsum[1];
-        hipLaunchKernelGGL(k_dec_fit, dim3(rgrid), dim3(ISH_THREADS), 0, stream, d_buf, o, N, lv, d_part);
-        launched();
-        if (fetch((size_t)DEC_FIT_PART * rgrid) != hipSuccess) break;
+        hipLaunchKernelGGL(k_dec_fit, dim3(rgrid), dim3(ISH_THREADS), 0, stream, m.d_buf, o, N, lv, m.d_part);
+        m.launched();
+        m.fetch(part.data(), m.d_part, sizeof(double) * DEC_FIT_PART * rgrid);
+        if (m.er != hipSuccess) break;
         double fit[DEC_FITS][4] = {};
         for (unsigned b = 0; b < rgrid; b++)
             for (int f = 0; f < DEC_FITS; f++)
@@ -412,11 +456,6 @@ inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n,
             dec_row(pick[s].data(), cnt + 3 * s, fit + 3 * s, tsum[s], o, N, k50, k80, q.rate, K, rows + 8 * r, curve ? curve + (size_t)K * r : nullptr);
         }
     }
-    (void)hipFree(d_part);
-    (void)hipFree(d_tot);
-    (void)hipFree(d_st);
-    (void)hipFree(d_buf);
-    info[0] = o;
-    info[1] = N;
-    return er;
+    m.info(info);
+    return m.er;
 }

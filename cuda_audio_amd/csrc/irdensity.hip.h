@@ -3,7 +3,7 @@
 // equivalent.  include/mcconv.h and DESIGN.md 2.15 hold the definition; tests/ir_density_np.py states it in float64.
 // mc_ir_tail_move_knee, host arithmetic, moves a tail band's knee to such a mixing time (den_move_knee).
 //
-// The stored taps x [n] are only read.  With N = end ? min(end, n) : n and the origin o of irdecay.hip.h, centre i sits at
+// The stored taps x [n] are only read.  With N = end ? min(end, n) : n and the origin o of irdecay.hip.h's Measure, centre i sits at
 // t_i = o + i hop, i < I = floor((N - 1 - o) / hop) + 1, and its window holds the taps t_i + k, k = -H .. H, that lie in [0, N).
 //   table   the host fills tab[k + H] = {h_k, g_k}: the window's weight and the decay compensation exp2(k 3 log2(10) / decay_t60)
 //           (1 with decay_t60 = 0).  Both depend on k alone, so no centre ever evaluates a cosine or an exp2;
@@ -207,46 +207,38 @@ inline void den_rows(const double* out, uint64_t I, int s, uint64_t o, uint32_t 
 // mc_ir_density describes them.  Synchronises the stream; leaves nothing allocated.
 inline hipError_t den_measure(hipStream_t stream, const float2* d_x, uint64_t n, const mc_density_query& q, double* rows, double* profile,
                               uint64_t info[3]) {
-    const uint64_t N = dec_span(q.end, n);
+    Measure m(stream, d_x, n, q.end);
+    const uint64_t N = m.N;
     const uint32_t H = den_half(q), hop = den_hop(q);
-    const unsigned ogrid = dec_origin_grid(N);  // the onset's walks
     const uint64_t imax = (N - 1) / hop + 1;
     const std::vector<double2> tab = den_table(H, q.decay_t60);
-    double2* d_tab = nullptr;
-    double* d_out = nullptr;
-    void* d_part = nullptr;
-    hipError_t er = hipMalloc(&d_tab, sizeof(double2) * tab.size());
-    if (er == hipSuccess) er = hipMalloc(&d_out, sizeof(double) * DEN_OUT * (size_t)imax);
-    if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(unsigned long long) * ogrid);
-    if (er == hipSuccess) er = hipMemcpyAsync(d_tab, tab.data(), sizeof(double2) * tab.size(), hipMemcpyHostToDevice, stream);
-    const auto launched = [&] { er = hipGetLastError(); };
-
-    uint64_t o = 0;
-    if (er == hipSuccess) er = dec_origin(stream, d_x, N, q.onset_db, d_part, &o);
+    // no row groups: the table rides in the states' place, the centres' outputs in the folded sums'
+    m.open(q.onset_db, 0, tab.size(), 0, 0, DEN_OUT * (size_t)imax, tab.data());
+    double2* const d_tab = m.d_st;
+    double* const d_out = m.d_fin;
+    const uint64_t o = m.o;
 
     DenPlan pl{};
     pl.N = N, pl.o = o, pl.I = (N - 1 - o) / hop + 1, pl.H = H, pl.hop = hop, pl.C = den_run(H, hop);
     std::vector<double> out(DEN_OUT * (size_t)pl.I);
-    if (er == hipSuccess) {
+    if (m.er == hipSuccess) {
         const unsigned grid = (unsigned)((pl.I + pl.C - 1) / pl.C);
         if (den_staged(H, hop))
             hipLaunchKernelGGL(k_den_window<true>, dim3(grid), dim3(DEN_THREADS), den_lds_bytes(H, hop), stream, d_x, pl, d_tab, d_out);
         else
             hipLaunchKernelGGL(k_den_window<false>, dim3(grid), dim3(DEN_THREADS), 0, stream, d_x, pl, d_tab, d_out);
-        launched();
+        m.launched();
     }
-    if (er == hipSuccess) er = hipMemcpyAsync(out.data(), d_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, stream);
-    const hipError_t sync = hipStreamSynchronize(stream);  // (the table's upload reads `tab`: wait for it on every path)
-    if (er == hipSuccess) er = sync;
-    (void)hipFree(d_part);
-    (void)hipFree(d_out);
-    (void)hipFree(d_tab);
-    if (er != hipSuccess) return er;
+    m.fetch(out.data(), d_out, sizeof(double) * out.size());
+    if (m.er != hipSuccess) {
+        (void)hipStreamSynchronize(stream);  // (the table's upload reads `tab`: wait for it on every path)
+        return m.er;
+    }
     for (int s = 0; s < DEC_SETS; s++) den_rows(out.data(), pl.I, s, o, hop, q.rate, (double)q.threshold, rows + 8 * s);
     if (profile)
         for (uint64_t i = 0; i < pl.I; i++)
             for (int s = 0; s < DEC_SETS; s++) profile[3 * i + s] = out[DEN_OUT * i + s];
-    info[0] = o, info[1] = N, info[2] = pl.I;
+    m.info(info), info[2] = pl.I;
     return hipSuccess;
 }
 

@@ -3,14 +3,14 @@
 // crossover split.  No reference equivalent.  include/mcconv.h and DESIGN.md 2.13 hold the definition; tests/ir_floor_np.py
 // states it in float64.  mc_ir_tail_from_floor, host arithmetic, turns a measurement into the tail step's struct (irtail.hip.h).
 //
-// The stored taps x [n] are only read.  With N = end ? min(end, n) : n and the origin o of irdecay.hip.h:
+// The stored taps x [n] are only read.  With N = end ? min(end, n) : n and the origin o of irdecay.hip.h's Measure:
 //   split   with X crossovers: k_dec_fill, then irdamp.hip.h's local pass and carry, unchanged (k_damp_chunk<false>,
 //           k_damp_carry), leave every chunk's true starting states; they serve all X + 1 bands;
 //   per row group (broadband, then band 0 .. X):
 //     fill    k_dec_fill: buf[m] = (double) x[m];
 //     band    k_flr_band, the fix-up pass of k_damp_chunk with the band's own combination in place of the envelopes: buf = B_j,
 //             formed as damping forms it with band j's gain 1 and the others 0 (B_0 = P_1, B_j = P_(j+1) - P_j, B_X = x - P_X);
-//     sum     k_dec_sum / k_dec_carry / k_dec_sum: buf[m] = EDC[m], irdecay.hip.h's backward sum, unchanged;
+//     sum     buf[m] = EDC[m], the backward sum (Measure::edc);
 //     search  the host walks the three channel sets' rows through the search in step.  All it ever needs of EDC are values at
 //             interval edges and at single taps: k_flr_gather fetches, per set, EDC at start + i step, i < count, in one launch per
 //             means() and one per noise().  The interval means are differences of neighbouring edges; the regressions over at most
@@ -268,61 +268,30 @@ inline bool flr_search(uint64_t o, uint64_t N, const mc_floor_query& q, Gather&&
 // The whole measurement of the n stored taps d_x for a checked query.  rows, info as mc_ir_floor describes them.  Synchronises
 // the stream; leaves nothing allocated.
 inline hipError_t flr_measure(hipStream_t stream, const float2* d_x, uint64_t n, const mc_floor_query& q, double* rows, uint64_t info[2]) {
-    const uint64_t N = dec_span(q.end, n);
+    Measure m(stream, d_x, n, q.end);
+    const uint64_t N = m.N;
     const int X = (int)q.n_xovers;
     const unsigned grid = (unsigned)((N + ISH_THREADS - 1) / ISH_THREADS);                    // k_dec_fill
-    const ChunkGeom cg = chunk_geom(N);                                                       // the chunk passes
-    const unsigned ogrid = (unsigned)std::min<uint64_t>(ISH_SCAN_GRID, (N / 2 + ISH_THREADS) / ISH_THREADS);  // the onset's walks
-    double2 *d_buf = nullptr, *d_st = nullptr;
-    double *d_tot = nullptr, *d_part = nullptr;
-    size_t part_cap = std::max<size_t>(ogrid, 16);
+    const ChunkGeom& cg = m.cg;                                                               // the chunk passes
     std::vector<double> part;
-    hipError_t er = hipMalloc(&d_buf, sizeof(double2) * N);
-    if (er == hipSuccess && X) er = hipMalloc(&d_st, sizeof(double2) * 2 * (size_t)X * cg.lanes);
-    if (er == hipSuccess) er = hipMalloc(&d_tot, sizeof(double) * (size_t)cg.lanes);
-    if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * part_cap);
-    const auto launched = [&] { er = hipGetLastError(); };
-
-    // origin: irdecay.hip.h's
-    uint64_t o = 0;
-    if (er == hipSuccess && q.onset_db < 0.f) {
-        hipLaunchKernelGGL(k_shape_peak, dim3(ogrid), dim3(ISH_THREADS), 0, stream, d_x, N, (float*)d_part);
-        launched();
-        std::vector<float> pk(ogrid);
-        if (er == hipSuccess) er = hipMemcpyAsync(pk.data(), d_part, sizeof(float) * ogrid, hipMemcpyDeviceToHost, stream);
-        if (er == hipSuccess) er = hipStreamSynchronize(stream);
-        if (er == hipSuccess) {
-            float peak = 0.f;
-            for (float v : pk) peak = std::max(peak, v);
-            const float t = peak * (float)std::pow(10.0, (double)q.onset_db / 20.0);
-            hipLaunchKernelGGL(k_shape_onset, dim3(ogrid), dim3(ISH_THREADS), 0, stream, d_x, N, t, (unsigned long long*)d_part);
-            launched();
-        }
-        std::vector<unsigned long long> at(ogrid);
-        if (er == hipSuccess) er = hipMemcpyAsync(at.data(), d_part, sizeof(unsigned long long) * ogrid, hipMemcpyDeviceToHost, stream);
-        if (er == hipSuccess) er = hipStreamSynchronize(stream);
-        if (er == hipSuccess) {
-            uint64_t onset = ISH_NONE;
-            for (unsigned long long v : at) onset = std::min<uint64_t>(onset, v);
-            o = onset == ISH_NONE ? 0 : onset;
-        }
-    }
+    m.open(q.onset_db, N, 2 * (size_t)X * cg.lanes, cg.lanes, 16, 0);
+    const uint64_t o = m.o;
 
     // the split's starting states, once for every band
     DampPlan pl{};
     pl.X = X;
     for (int k = 0; k < X; k++) pl.c[k] = ieq_coef(mc_eq_band{MC_EQ_HIGHCUT, q.xover_hz[k], 0.f, 0.70710678f}, q.rate);
-    if (er == hipSuccess && X) {
+    if (m.er == hipSuccess && X) {
         const DampCarry cm = damp_carry(pl.c, X, cg.K);
-        hipLaunchKernelGGL(k_dec_fill, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x, N, d_buf);
-        launched();
-        if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_damp_chunk<false>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pl, d_st);
-            launched();
+        hipLaunchKernelGGL(k_dec_fill, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x, N, m.d_buf);
+        m.launched();
+        if (m.er == hipSuccess) {
+            hipLaunchKernelGGL(k_damp_chunk<false>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, m.d_buf, N, pl, m.d_st);
+            m.launched();
         }
-        if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_damp_carry, dim3(X), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.lanes, cg.nchunks, cg.K, cm);
-            launched();
+        if (m.er == hipSuccess) {
+            hipLaunchKernelGGL(k_damp_carry, dim3(X), dim3(2 * IEQ_RUNS), 0, stream, m.d_st, cg.lanes, cg.nchunks, cg.K, cm);
+            m.launched();
         }
     }
 
@@ -330,54 +299,33 @@ inline hipError_t flr_measure(hipStream_t stream, const float2* d_x, uint64_t n,
     const auto gather = [&](FlrGather& ga) {
         uint64_t total = 0;
         for (int s = 0; s < FLR_SETS; s++) ga.at[s] = total, total += ga.count[s];
-        if (er != hipSuccess) return false;
+        if (m.er != hipSuccess) return false;
         if (!total) return true;
-        if (total > part_cap) {
-            (void)hipFree(d_part);
-            d_part = nullptr;
-            part_cap = (size_t)total;
-            er = hipMalloc(&d_part, sizeof(double) * part_cap);
-            if (er != hipSuccess) return false;
-        }
+        m.grow_part((size_t)total);
+        if (m.er != hipSuccess) return false;
         part.resize((size_t)total);
-        hipLaunchKernelGGL(k_flr_gather, dim3((unsigned)((total + ISH_THREADS - 1) / ISH_THREADS)), dim3(ISH_THREADS), 0, stream, d_buf, N, ga, d_part);
-        launched();
-        if (er == hipSuccess) er = hipMemcpyAsync(part.data(), d_part, sizeof(double) * (size_t)total, hipMemcpyDeviceToHost, stream);
-        if (er == hipSuccess) er = hipStreamSynchronize(stream);
-        return er == hipSuccess;
+        hipLaunchKernelGGL(k_flr_gather, dim3((unsigned)((total + ISH_THREADS - 1) / ISH_THREADS)), dim3(ISH_THREADS), 0, stream, m.d_buf, N, ga, m.d_part);
+        m.launched();
+        m.fetch(part.data(), m.d_part, sizeof(double) * (size_t)total);
+        return m.er == hipSuccess;
     };
 
+    // the band split is the damping's, not Measure::group's band-pass: its own fill and k_flr_band
     const uint32_t groups = flr_groups(q);
-    for (uint32_t g = 0; g < groups && er == hipSuccess; g++) {
-        hipLaunchKernelGGL(k_dec_fill, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x, N, d_buf);
-        launched();
-        if (er == hipSuccess && g > 0) {
-            hipLaunchKernelGGL(k_flr_band, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, N, pl, (int)g - 1, d_st);
-            launched();
+    for (uint32_t g = 0; g < groups && m.er == hipSuccess; g++) {
+        hipLaunchKernelGGL(k_dec_fill, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x, N, m.d_buf);
+        m.launched();
+        if (m.er == hipSuccess && g > 0) {
+            hipLaunchKernelGGL(k_flr_band, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, m.d_buf, N, pl, (int)g - 1, m.d_st);
+            m.launched();
         }
-        if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_dec_sum<false>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
-            launched();
-        }
-        if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_dec_carry, dim3(1), dim3(DEC_CARRY_THREADS), 0, stream, d_tot, cg.nchunks);
-            launched();
-        }
-        if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_dec_sum<true>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, o, N, d_tot);
-            launched();
-        }
-        if (er != hipSuccess) break;
+        m.edc();
+        if (m.er != hipSuccess) break;
 
         if (!flr_search(o, N, q, gather, part, rows + 8 * (size_t)g * FLR_SETS)) break;
     }
-    (void)hipFree(d_part);
-    (void)hipFree(d_tot);
-    (void)hipFree(d_st);
-    (void)hipFree(d_buf);
-    info[0] = o;
-    info[1] = N;
-    return er;
+    m.info(info);
+    return m.er;
 }
 
 // mc_ir_tail_from_floor for a checked query: fills n_xovers, xover_hz, knee, t60 and level_db of *t

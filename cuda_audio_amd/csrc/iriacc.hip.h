@@ -4,7 +4,7 @@
 // definition; tests/ir_iacc_np.py states it in float64.
 //
 // The stored taps are only read.  N, the origin o and a row group's doubles y (double2 [N]: L in x, R in y) are irdecay.hip.h's
-// (dec_origin, dec_group).  Per group the three windows [a, b) = [o, k), [k, N), [o, N) are measured as three ranges of their
+// (its Measure: open, group).  Per group the three windows [a, b) = [o, k), [k, N), [o, N) are measured as three ranges of their
 // own by one launch (blockIdx.y = window): the whole IR costs as much again as its two parts, and every window's sums are
 // folded in an order that depends on its own length alone.
 //
@@ -178,51 +178,37 @@ inline void iacc_row(const double* fin, uint32_t T, bool empty, double* row, dou
 // describes them.  Synchronises the stream; leaves nothing allocated.
 inline hipError_t iacc_measure(hipStream_t stream, const float2* d_x, uint64_t n, const mc_iacc_query& q, double* rows, double* curve,
                                uint64_t info[3]) {
-    const uint64_t N = dec_span(q.end, n);
+    Measure m(stream, d_x, n, q.end);
+    const uint64_t N = m.N;
     const uint32_t T = q.max_lag, lags = 2 * T + 1, slots = lags + 2;
-    const ChunkGeom cg = chunk_geom(N);
-    const unsigned ogrid = dec_origin_grid(N);
-    const size_t npart = std::max<size_t>({(size_t)iacc_part(N, T), (size_t)ogrid, (size_t)1});
-    double2 *d_buf = nullptr, *d_st = nullptr;
-    double *d_part = nullptr, *d_fin = nullptr;
     std::vector<double> fin((size_t)IACC_WINDOWS * slots);
-    hipError_t er = hipMalloc(&d_buf, sizeof(double2) * N);
-    if (er == hipSuccess) er = hipMalloc(&d_st, sizeof(double2) * (size_t)cg.lanes);
-    if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * npart);
-    if (er == hipSuccess) er = hipMalloc(&d_fin, sizeof(double) * fin.size());
-
-    uint64_t o = 0;
-    if (er == hipSuccess) er = dec_origin(stream, d_x, N, q.onset_db, d_part, &o);
+    m.open(q.onset_db, N, m.cg.lanes, 0, (size_t)iacc_part(N, T), fin.size());
+    const uint64_t o = m.o;
     const uint64_t k = std::min<uint64_t>(o + (q.split ? std::min<uint64_t>(q.split, N) : (uint64_t)std::floor(0.08 * (double)q.rate + 0.5)), N);
     IaccPlan pl{};
     pl.a[0] = o, pl.b[0] = k, pl.a[1] = k, pl.b[1] = N, pl.a[2] = o, pl.b[2] = N;
     pl.T = T;
     for (int w = 0; w < IACC_WINDOWS; w++) pl.maxruns = std::max(pl.maxruns, iacc_runs(pl.a[w], pl.b[w]));
 
-    for (uint32_t g = 0; g <= q.n_bands && er == hipSuccess; g++) {
-        er = dec_group(stream, d_x, N, cg, g ? &q.centre_hz[g - 1] : nullptr, q.q, q.rate, d_buf, d_st);
-        if (er == hipSuccess && pl.maxruns) {
-            hipLaunchKernelGGL(k_iacc_runs, dim3(pl.maxruns, IACC_WINDOWS), dim3(IACC_THREADS), 0, stream, d_buf, pl, d_part);
-            er = hipGetLastError();
+    for (uint32_t g = 0; g <= q.n_bands && m.er == hipSuccess; g++) {
+        m.group(g ? &q.centre_hz[g - 1] : nullptr, q.q, q.rate);
+        if (m.er == hipSuccess && pl.maxruns) {
+            hipLaunchKernelGGL(k_iacc_runs, dim3(pl.maxruns, IACC_WINDOWS), dim3(IACC_THREADS), 0, stream, m.d_buf, pl, m.d_part);
+            m.launched();
         }
-        if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_iacc_fold, dim3((slots + IACC_THREADS - 1) / IACC_THREADS, IACC_WINDOWS), dim3(IACC_THREADS), 0, stream, d_part, pl, d_fin);
-            er = hipGetLastError();
+        if (m.er == hipSuccess) {
+            hipLaunchKernelGGL(k_iacc_fold, dim3((slots + IACC_THREADS - 1) / IACC_THREADS, IACC_WINDOWS), dim3(IACC_THREADS), 0, stream, m.d_part, pl, m.d_fin);
+            m.launched();
         }
-        if (er == hipSuccess) er = hipMemcpyAsync(fin.data(), d_fin, sizeof(double) * fin.size(), hipMemcpyDeviceToHost, stream);
-        if (er == hipSuccess) er = hipStreamSynchronize(stream);
-        if (er != hipSuccess) break;
+        m.fetch(fin.data(), m.d_fin, sizeof(double) * fin.size());
+        if (m.er != hipSuccess) break;
         for (int w = 0; w < IACC_WINDOWS; w++) {
             const size_t r = (size_t)g * IACC_WINDOWS + w;
             iacc_row(fin.data() + (size_t)w * slots, T, pl.a[w] >= pl.b[w], rows + 8 * r, curve ? curve + (size_t)lags * r : nullptr);
         }
     }
-    (void)hipFree(d_fin);
-    (void)hipFree(d_part);
-    (void)hipFree(d_st);
-    (void)hipFree(d_buf);
-    info[0] = o, info[1] = N, info[2] = k;
-    return er;
+    m.info(info), info[2] = k;
+    return m.er;
 }
 
 // mc_ir_tail_width_from_iacc's arithmetic for a finite rho

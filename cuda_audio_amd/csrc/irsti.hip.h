@@ -5,7 +5,7 @@
 // tests/ir_sti_np.py states it in float64.
 //
 // The stored taps are only read.  N, the origin o and a row group's doubles y (double2 [N]: L in x, R in y) are irdecay.hip.h's
-// (dec_origin, dec_group).  Per group one launch of k_sti_runs reduces the taps [o, N) into 4 n_mod + 2 sums: C_L, S_L, C_R, S_R
+// (its Measure: open, group).  Per group one launch of k_sti_runs reduces the taps [o, N) into 4 n_mod + 2 sums: C_L, S_L, C_R, S_R
 // per modulation frequency, then E_L and E_R.  The third channel set (L + R) is the sum of the other two's folded sums, added on
 // the host: it is not walked.
 //
@@ -189,21 +189,12 @@ inline void sti_index(const mc_sti_query& q, const double* rows, double sti[3]) 
 // Synchronises the stream; leaves nothing allocated.
 inline hipError_t sti_measure(hipStream_t stream, const float2* d_x, uint64_t n, const mc_sti_query& q, double* rows, double* mtf, double sti[3],
                               uint64_t info[2]) {
-    const uint64_t N = dec_span(q.end, n);
+    Measure m(stream, d_x, n, q.end);
+    const uint64_t N = m.N;
     const uint32_t slots = sti_slots(q.n_mod);
-    const ChunkGeom cg = chunk_geom(N);
-    const unsigned ogrid = dec_origin_grid(N);
-    const size_t npart = std::max<size_t>({(size_t)sti_runs(0, N) * slots, (size_t)ogrid, (size_t)1});
-    double2 *d_buf = nullptr, *d_st = nullptr;
-    double *d_part = nullptr, *d_fin = nullptr;
     std::vector<double> fin(slots);
-    hipError_t er = hipMalloc(&d_buf, sizeof(double2) * N);
-    if (er == hipSuccess) er = hipMalloc(&d_st, sizeof(double2) * (size_t)cg.lanes);
-    if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * npart);
-    if (er == hipSuccess) er = hipMalloc(&d_fin, sizeof(double) * fin.size());
-
-    uint64_t o = 0;
-    if (er == hipSuccess) er = dec_origin(stream, d_x, N, q.onset_db, d_part, &o);
+    m.open(q.onset_db, N, m.cg.lanes, 0, (size_t)sti_runs(0, N) * slots, fin.size());
+    const uint64_t o = m.o;
     StiPlan pl{};
     pl.o = o, pl.N = N, pl.n_mod = q.n_mod, pl.runs = sti_runs(o, N), pl.rate = (double)q.rate;
     for (uint32_t f = 0; f < q.n_mod; f++) {
@@ -212,26 +203,21 @@ inline hipError_t sti_measure(hipStream_t stream, const float2* d_x, uint64_t n,
         pl.wc[f] = std::cos(w), pl.ws[f] = std::sin(w);
     }
 
-    for (uint32_t g = 0; g <= q.n_bands && er == hipSuccess; g++) {
-        er = dec_group(stream, d_x, N, cg, g ? &q.centre_hz[g - 1] : nullptr, q.q, q.rate, d_buf, d_st);
-        if (er == hipSuccess && pl.runs) {
-            hipLaunchKernelGGL(k_sti_runs, dim3(pl.runs), dim3(STI_THREADS), 0, stream, d_buf, pl, d_part);
-            er = hipGetLastError();
+    for (uint32_t g = 0; g <= q.n_bands && m.er == hipSuccess; g++) {
+        m.group(g ? &q.centre_hz[g - 1] : nullptr, q.q, q.rate);
+        if (m.er == hipSuccess && pl.runs) {
+            hipLaunchKernelGGL(k_sti_runs, dim3(pl.runs), dim3(STI_THREADS), 0, stream, m.d_buf, pl, m.d_part);
+            m.launched();
         }
-        if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_sti_fold, dim3(1), dim3(STI_THREADS), 0, stream, d_part, pl, d_fin);
-            er = hipGetLastError();
+        if (m.er == hipSuccess) {
+            hipLaunchKernelGGL(k_sti_fold, dim3(1), dim3(STI_THREADS), 0, stream, m.d_part, pl, m.d_fin);
+            m.launched();
         }
-        if (er == hipSuccess) er = hipMemcpyAsync(fin.data(), d_fin, sizeof(double) * fin.size(), hipMemcpyDeviceToHost, stream);
-        if (er == hipSuccess) er = hipStreamSynchronize(stream);
-        if (er != hipSuccess) break;
+        m.fetch(fin.data(), m.d_fin, sizeof(double) * fin.size());
+        if (m.er != hipSuccess) break;
         sti_group(fin.data(), q, g, rows + (size_t)g * STI_SETS * 4, mtf + (size_t)g * STI_SETS * q.n_mod);
     }
-    if (er == hipSuccess) sti_index(q, rows, sti);
-    (void)hipFree(d_fin);
-    (void)hipFree(d_part);
-    (void)hipFree(d_st);
-    (void)hipFree(d_buf);
-    info[0] = o, info[1] = N;
-    return er;
+    if (m.er == hipSuccess) sti_index(q, rows, sti);
+    m.info(info);
+    return m.er;
 }

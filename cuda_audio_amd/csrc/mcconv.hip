@@ -3412,7 +3412,7 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
     return MC_OK;
 }
 
-// What the eight mc_ir_*_info getters report of the load `ld` that stored `taps` taps; sinfo = the shaping stage's numbers.
+// What the mc_ir_*_info getters report of the load `ld` that stored `taps` taps; sinfo = the shaping stage's numbers.
 // Every kind is written, so nothing of an earlier load onto the same index stays behind.
 void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[8]) {
     for (IrFact& f : ir.facts) f.on = false;
@@ -3598,8 +3598,8 @@ const char* resolve_steps(const mc_ir_shape* shape, const mc_ir_eq* eq, const mc
     return nullptr;
 }
 
-// The six mc_ir_*_info getters: out = the first `count` numbers of what note_load kept of that kind, or MC_ERR_STATE with
-// "IR <idx> <was_not>" when the last load had none
+// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, room, room mics, room bands): out = the first `count` numbers of what
+// note_load kept of that kind, or MC_ERR_STATE with "IR <idx> <was_not>" when the last load had none
 int ir_fact(const mc_engine* e, uint64_t idx, IrFactKind kind, int count, const char* was_not, double* out) {
     if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
     const IrFact& f = e->irs[idx].facts[kind];
@@ -3608,14 +3608,24 @@ int ir_fact(const mc_engine* e, uint64_t idx, IrFactKind kind, int count, const 
     return MC_OK;
 }
 
-// The stored taps of IR idx for a measurement (mc_ir_decay, mc_ir_floor, mc_ir_density, mc_ir_iacc, mc_ir_sti), once the entry point has
-// checked its query and its pointers.  No HIP call: quiesce(e) comes after the entry point's checks of the work.
-int stored_taps(const mc_engine* e, uint64_t idx, const float2** d_x, uint64_t* n) {
+// What a measurement (mc_ir_decay, mc_ir_floor, mc_ir_density, mc_ir_iacc, mc_ir_sti) does once the entry point has checked its query
+// and its pointers: the stored taps of IR idx, then work(n), the query's bounds on the work that n taps make (a message, or null),
+// both without a HIP call; then the stream idle, run(d_x, n), and a failure of it under the measurement's `name`.
+template <class Work, class Run>
+int measure(mc_engine* e, uint64_t idx, const char* name, Work&& work, Run&& run) {
     if (e->sf) return fail(MC_ERR_STATE, "the single-transform form keeps no taps");
     if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h || !e->irs[idx].taps) return fail(MC_ERR_ARG, "IR not loaded");
-    *d_x = e->irs[idx].d_h;
-    *n = e->irs[idx].taps;
+    const uint64_t n = e->irs[idx].taps;
+    if (const char* bad = work(n)) return fail(MC_ERR_ARG, "%s", bad);
+    if (const int rc = quiesce(e)) return rc;
+    const hipError_t er = run(e->irs[idx].d_h, n);
+    if (er != hipSuccess) return fail(MC_ERR_HIP, "%s measurement failed: %s", name, hipGetErrorString(er));
     return MC_OK;
+}
+// (a measurement whose work has no bound)
+template <class Run>
+int measure(mc_engine* e, uint64_t idx, const char* name, Run&& run) {
+    return measure(e, idx, name, [](uint64_t) { return (const char*)nullptr; }, run);
 }
 
 // the tail step of a checked mc_ir_tail that is on, over F frames at the session's rate
@@ -3942,13 +3952,7 @@ int mc_ir_decay(mc_engine* e, uint64_t idx, const mc_decay_query* q, double* row
     if (!rows) return fail(MC_ERR_ARG, "null rows");
     if (q->curve_points && !curve) return fail(MC_ERR_ARG, "null curve with curve_points %u", q->curve_points);
     if (!info) return fail(MC_ERR_ARG, "null info");
-    const float2* d_x;
-    uint64_t n;
-    if (const int rc = stored_taps(e, idx, &d_x, &n)) return rc;
-    if (const int rc = quiesce(e)) return rc;
-    const hipError_t er = dec_measure(e->stream, d_x, n, *q, rows, curve, info);
-    if (er != hipSuccess) return fail(MC_ERR_HIP, "decay measurement failed: %s", hipGetErrorString(er));
-    return MC_OK;
+    return measure(e, idx, "decay", [&](const float2* d_x, uint64_t n) { return dec_measure(e->stream, d_x, n, *q, rows, curve, info); });
 }
 
 void mc_default_floor_query(mc_floor_query* q) {
@@ -3971,13 +3975,7 @@ int mc_ir_floor(mc_engine* e, uint64_t idx, const mc_floor_query* q, double* row
     if (!e) return fail(MC_ERR_ARG, "null engine");
     if (!rows) return fail(MC_ERR_ARG, "null rows");
     if (!info) return fail(MC_ERR_ARG, "null info");
-    const float2* d_x;
-    uint64_t n;
-    if (const int rc = stored_taps(e, idx, &d_x, &n)) return rc;
-    if (const int rc = quiesce(e)) return rc;
-    const hipError_t er = flr_measure(e->stream, d_x, n, *q, rows, info);
-    if (er != hipSuccess) return fail(MC_ERR_HIP, "floor measurement failed: %s", hipGetErrorString(er));
-    return MC_OK;
+    return measure(e, idx, "floor", [&](const float2* d_x, uint64_t n) { return flr_measure(e->stream, d_x, n, *q, rows, info); });
 }
 
 int mc_ir_tail_from_floor(const mc_floor_query* q, const double* rows, const uint64_t info[2], uint64_t first, mc_ir_tail* tail) {
@@ -4005,14 +4003,9 @@ int mc_ir_density(mc_engine* e, uint64_t idx, const mc_density_query* q, double*
     if (!e) return fail(MC_ERR_ARG, "null engine");
     if (!rows) return fail(MC_ERR_ARG, "null rows");
     if (!info) return fail(MC_ERR_ARG, "null info");
-    const float2* d_x;
-    uint64_t n;
-    if (const int rc = stored_taps(e, idx, &d_x, &n)) return rc;
-    if (const char* bad = den_check_work(*q, n)) return fail(MC_ERR_ARG, "%s", bad);
-    if (const int rc = quiesce(e)) return rc;
-    const hipError_t er = den_measure(e->stream, d_x, n, *q, rows, profile, info);
-    if (er != hipSuccess) return fail(MC_ERR_HIP, "density measurement failed: %s", hipGetErrorString(er));
-    return MC_OK;
+    return measure(
+        e, idx, "density", [&](uint64_t n) { return den_check_work(*q, n); },
+        [&](const float2* d_x, uint64_t n) { return den_measure(e->stream, d_x, n, *q, rows, profile, info); });
 }
 
 int mc_ir_tail_move_knee(mc_ir_tail* tail, uint32_t band, uint64_t frame) {
@@ -4041,14 +4034,9 @@ int mc_ir_iacc(mc_engine* e, uint64_t idx, const mc_iacc_query* q, double* rows,
     if (!e) return fail(MC_ERR_ARG, "null engine");
     if (!rows) return fail(MC_ERR_ARG, "null rows");
     if (!info) return fail(MC_ERR_ARG, "null info");
-    const float2* d_x;
-    uint64_t n;
-    if (const int rc = stored_taps(e, idx, &d_x, &n)) return rc;
-    if (const char* bad = iacc_check_work(*q, n)) return fail(MC_ERR_ARG, "%s", bad);
-    if (const int rc = quiesce(e)) return rc;
-    const hipError_t er = iacc_measure(e->stream, d_x, n, *q, rows, curve, info);
-    if (er != hipSuccess) return fail(MC_ERR_HIP, "IACC measurement failed: %s", hipGetErrorString(er));
-    return MC_OK;
+    return measure(
+        e, idx, "IACC", [&](uint64_t n) { return iacc_check_work(*q, n); },
+        [&](const float2* d_x, uint64_t n) { return iacc_measure(e->stream, d_x, n, *q, rows, curve, info); });
 }
 
 int mc_ir_tail_width_from_iacc(mc_ir_tail* tail, double rho) {
@@ -4087,13 +4075,7 @@ int mc_ir_sti(mc_engine* e, uint64_t idx, const mc_sti_query* q, double* rows, d
     if (!mtf) return fail(MC_ERR_ARG, "null mtf");
     if (!sti) return fail(MC_ERR_ARG, "null sti");
     if (!info) return fail(MC_ERR_ARG, "null info");
-    const float2* d_x;
-    uint64_t n;
-    if (const int rc = stored_taps(e, idx, &d_x, &n)) return rc;
-    if (const int rc = quiesce(e)) return rc;
-    const hipError_t er = sti_measure(e->stream, d_x, n, *q, rows, mtf, sti, info);
-    if (er != hipSuccess) return fail(MC_ERR_HIP, "STI measurement failed: %s", hipGetErrorString(er));
-    return MC_OK;
+    return measure(e, idx, "STI", [&](const float2* d_x, uint64_t n) { return sti_measure(e->stream, d_x, n, *q, rows, mtf, sti, info); });
 }
 
 void mc_default_ir_tail(mc_ir_tail* t) {
