@@ -26,6 +26,7 @@ SYMBOLS = [
     "mc_default_density_query", "mc_ir_density", "mc_ir_tail_move_knee",
     "mc_default_iacc_query", "mc_ir_iacc", "mc_ir_tail_width_from_iacc",
     "mc_default_sti_query", "mc_ir_sti",
+    "mc_default_response_query", "mc_ir_response", "mc_response_grid", "mc_response_smooth",
     "mc_default_ir_tail", "mc_load_ir_tail", "mc_load_ir_sweep_tail", "mc_ir_tail_info",
     "mc_default_ir_room", "mc_synth_ir_room", "mc_ir_room_info", "mc_ir_room_plan",
     "mc_default_ir_room_mics", "mc_synth_ir_room_mics", "mc_ir_room_mics_plan", "mc_ir_room_mics_info",
@@ -278,6 +279,31 @@ class McStiQuery(C.Structure):
     ]
 
 
+MC_RSP_MAX_FREQ = 1024
+MC_RSP_MAX_WIN = 64
+
+
+class McResponseWindow(C.Structure):
+    """mc_response_window: the taps of one window of mc_ir_response, counted from the origin, and its raised-cosine edges."""
+
+    _fields_ = [("first", C.c_uint64), ("count", C.c_uint64), ("rise", C.c_uint32), ("fall", C.c_uint32)]
+
+
+class McResponseQuery(C.Structure):
+    """mc_response_query: how mc_ir_response measures a loaded IR's frequency response."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("rate", C.c_uint32),
+        ("n_freq", C.c_uint32),
+        ("n_win", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("onset_db", C.c_float),
+        ("end", C.c_uint64),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 MC_TAIL_OFF, MC_TAIL_CUT, MC_TAIL_EXTEND = 0, 1, 2
 MC_TAIL_LEFT_ALONE = (1 << 64) - 1  # a knee that leaves its band alone
 
@@ -442,6 +468,12 @@ def load():
     L.mc_default_sti_query.argtypes = [C.POINTER(McStiQuery)]
     L.mc_default_sti_query.restype = None
     L.mc_ir_sti.argtypes = [vp, u64, C.POINTER(McStiQuery), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(u64)]
+    L.mc_default_response_query.argtypes = [C.POINTER(McResponseQuery)]
+    L.mc_default_response_query.restype = None
+    L.mc_ir_response.argtypes = [vp, u64, C.POINTER(McResponseQuery), fp, C.POINTER(McResponseWindow), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                 C.POINTER(u64), C.POINTER(u64)]
+    L.mc_response_grid.argtypes = [C.c_double, C.c_double, C.c_uint32, fp, C.c_uint32]
+    L.mc_response_smooth.argtypes = [fp, C.POINTER(C.c_double), C.c_uint32, C.c_double, C.POINTER(C.c_double)]
     L.mc_default_ir_tail.argtypes = [C.POINTER(McIrTail)]
     L.mc_default_ir_tail.restype = None
     L.mc_load_ir_tail.argtypes = [vp, u64, fp, u64, u64, C.c_uint32, C.c_uint32, C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp),

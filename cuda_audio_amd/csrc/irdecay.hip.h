@@ -37,8 +37,8 @@
 // nobody asks holds nothing.
 //
 // The host side.  N, the scratch, the origin, a row group's fill and filter, the backward sum and the fetches are the operations
-// of one struct, Measure, in the host section below (not in a header of its own: irfloor, irdensity, iriacc and irsti.hip.h include
-// this one for its kernels already).  Their *_measure functions are written on it as dec_measure is.
+// of one struct, Measure, in the host section below (not in a header of its own: irfloor, irdensity, iriacc, irsti and
+// irresponse.hip.h include this one for its kernels already).  Their *_measure functions are written on it as dec_measure is.
 #pragma once
 #include <limits>
 
@@ -198,7 +198,7 @@ __global__ __launch_bounds__(ISH_THREADS) void k_dec_fit(const double2* __restri
 }
 
 // -- host ------------------------------------------------------------------------------------------------------------
-// What the queries of the measurements (this header, irfloor, irdensity, iriacc and irsti) have in common.  The three checks write
+// What the queries of the measurements (this header, irfloor, irdensity, iriacc, irsti and irresponse) have in common.  The three checks write
 // their message into the caller's buffer msg [cap] and return false; true and nothing written when the field is good.
 inline bool dec_rate_ok(uint32_t rate, char* msg, size_t cap) {
     if (rate >= DEC_MIN_RATE && rate <= DEC_MAX_RATE) return true;
@@ -310,8 +310,8 @@ inline hipError_t dec_origin(hipStream_t stream, const float2* d_x, uint64_t N, 
     return hipSuccess;
 }
 
-// The host side of a measurement: what dec_measure here and flr_measure, den_measure, iacc_measure and sti_measure (irfloor,
-// irdensity, iriacc, irsti.hip.h) do around their own kernels.  It lives in this host section, not in a header of its own, because
+// The host side of a measurement: what dec_measure here and flr_measure, den_measure, iacc_measure, sti_measure and rsp_measure
+// (irfloor, irdensity, iriacc, irsti, irresponse.hip.h) do around their own kernels.  It lives in this host section, not in a header of its own, because
 // it needs this header's kernels and those four include this header already.  A *_measure constructs it (the span N and the chunk
 // geometry), opens it (the scratch and the origin o) and strings its own launches between the operations below; every one of them
 // does nothing once `er` is set, so a *_measure tests m.er where it has to stop.  The scratch goes when the struct goes: nothing

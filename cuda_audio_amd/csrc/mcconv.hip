@@ -37,6 +37,7 @@
 #include "irdensity.hip.h"
 #include "iriacc.hip.h"
 #include "irsti.hip.h"
+#include "irresponse.hip.h"
 #include "irtail.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
@@ -3608,7 +3609,7 @@ int ir_fact(const mc_engine* e, uint64_t idx, IrFactKind kind, int count, const 
     return MC_OK;
 }
 
-// What a measurement (mc_ir_decay, mc_ir_floor, mc_ir_density, mc_ir_iacc, mc_ir_sti) does once the entry point has checked its query
+// What a measurement (mc_ir_decay, mc_ir_floor, mc_ir_density, mc_ir_iacc, mc_ir_sti, mc_ir_response) does once the entry point has checked its query
 // and its pointers: the stored taps of IR idx, then work(n), the query's bounds on the work that n taps make (a message, or null),
 // both without a HIP call; then the stream idle, run(d_x, n), and a failure of it under the measurement's `name`.
 template <class Work, class Run>
@@ -4076,6 +4077,52 @@ int mc_ir_sti(mc_engine* e, uint64_t idx, const mc_sti_query* q, double* rows, d
     if (!sti) return fail(MC_ERR_ARG, "null sti");
     if (!info) return fail(MC_ERR_ARG, "null info");
     return measure(e, idx, "STI", [&](const float2* d_x, uint64_t n) { return sti_measure(e->stream, d_x, n, *q, rows, mtf, sti, info); });
+}
+
+void mc_default_response_query(mc_response_query* q) {
+    if (!q) return;
+    std::memset(q, 0, sizeof(*q));
+    q->struct_size = (uint32_t)sizeof(*q);
+    q->rate = 44100;
+    q->n_win = 1;
+    q->onset_db = -20.f;
+}
+
+int mc_ir_response(mc_engine* e, uint64_t idx, const mc_response_query* q, const float* hz, const mc_response_window* win, double* resp,
+                   double* rows, uint64_t* spans, uint64_t info[2]) {
+    // the query, the frequencies, the pointers and the index are checked in this order before any HIP call
+    if (const char* bad = rsp_check(q, hz)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!hz) return fail(MC_ERR_ARG, "null hz");
+    if (!win && q->n_win > 1) return fail(MC_ERR_ARG, "null win with n_win %u", q->n_win);
+    if (!resp) return fail(MC_ERR_ARG, "null resp");
+    if (!rows) return fail(MC_ERR_ARG, "null rows");
+    if (!spans) return fail(MC_ERR_ARG, "null spans");
+    if (!info) return fail(MC_ERR_ARG, "null info");
+    if (!e) return fail(MC_ERR_ARG, "null engine");
+    return measure(e, idx, "response",
+                   [&](const float2* d_x, uint64_t n) { return rsp_measure(e->stream, d_x, n, *q, hz, win, resp, rows, spans, info); });
+}
+
+int mc_response_grid(double lo_hz, double hi_hz, uint32_t per_octave, float* hz, uint32_t cap) {
+    if (!(std::isfinite(lo_hz) && std::isfinite(hi_hz) && lo_hz > 0.0 && lo_hz <= hi_hz))
+        return fail(MC_ERR_ARG, "lo_hz %g, hi_hz %g: 0 < lo_hz <= hi_hz is required", lo_hz, hi_hz);
+    if (per_octave < 1 || per_octave > 96) return fail(MC_ERR_ARG, "per_octave %u outside [1, 96]", per_octave);
+    if (!hz) return fail(MC_ERR_ARG, "null hz");
+    const int count = rsp_grid(lo_hz, hi_hz, per_octave, hz, cap);
+    if (count < 0) return fail(MC_ERR_ARG, "the grid has more than cap %u frequencies", cap);
+    return count;
+}
+
+int mc_response_smooth(const float* hz, const double* power, uint32_t n, double octaves, double* out) {
+    if (!hz) return fail(MC_ERR_ARG, "null hz");
+    if (!power) return fail(MC_ERR_ARG, "null power");
+    if (!out) return fail(MC_ERR_ARG, "null out");
+    if (!(octaves >= 0.0 && octaves <= 10.0)) return fail(MC_ERR_ARG, "octaves %g outside [0, 10]", octaves);
+    for (uint32_t f = 0; f < n; f++)
+        if (const double v = (double)hz[f]; !(std::isfinite(v) && v >= 0.0 && (f == 0 || v >= (double)hz[f - 1])))
+            return fail(MC_ERR_ARG, "hz[%u] %g: the frequencies must be finite, >= 0 and ascend", f, v);
+    rsp_smooth(hz, power, n, octaves, out);
+    return MC_OK;
 }
 
 void mc_default_ir_tail(mc_ir_tail* t) {

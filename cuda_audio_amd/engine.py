@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McIrDamp, McIrEq, McIrRoom, McIrRoomBands, McIrRoomMics, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrRoom, McIrRoomBands, McIrRoomMics, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -592,6 +592,41 @@ def sti_rating(sti):
     return "excellent"
 
 
+RESPONSE_CHANNELS = ("L", "R")
+RESPONSE_FLOOR_DB = -400.0  # db where |H| = 0 (the floor of the decay curve)
+
+
+def response_grid(lo=20, hi=20000, per_octave=24):
+    """The frequencies lo 2^(i / per_octave) <= hi as float32 (mc_response_grid, host arithmetic only): per_octave points to the
+    octave, the grid ir_response uses when it is given none."""
+    hz = np.empty(_lib.MC_RSP_MAX_FREQ * 16, np.float32)
+    n = _lib.load().mc_response_grid(float(lo), float(hi), int(per_octave), _fp(hz), hz.size)
+    if n < 0:
+        check(n)
+    return hz[:n].copy()
+
+
+def smooth_response(hz, power, octaves):
+    """Fractional-octave smoothing of a power response (|H|^2) on an ascending grid hz: each point becomes the mean of the points
+    within octaves / 2 on either side (mc_response_smooth, host arithmetic only).  octaves = 0 returns power as it is."""
+    hz = _f32(hz).reshape(-1)
+    power = np.ascontiguousarray(power, dtype=np.float64).reshape(-1)
+    if power.size != hz.size:
+        raise ValueError(f"{hz.size} frequencies and {power.size} powers")
+    out = np.empty_like(power)
+    dp = C.POINTER(C.c_double)
+    check(_lib.load().mc_response_smooth(_fp(hz), power.ctypes.data_as(dp), hz.size, float(octaves), out.ctypes.data_as(dp)))
+    return out
+
+
+def waterfall_windows(slices, hop, length, rise=0, fall=0):
+    """The windows of a waterfall for ir_response: `slices` windows of `length` taps, each `hop` taps after the one before, the
+    first at the origin, all with the same raised-cosine edges."""
+    if slices < 1 or hop < 0 or length < 1 or rise < 0 or fall < 0:
+        raise ValueError("slices and length are at least 1; hop, rise and fall are not negative")
+    return [(k * int(hop), int(length), int(rise), int(fall)) for k in range(int(slices))]
+
+
 def decay_for_rt60(measured_s, target_s, rate):
     """The IrShape.decay_t60 (frames) that takes an IR whose decay time is measured_s seconds to target_s seconds at `rate`
     Hz.  The envelope 10^(-3 m / d) adds 60 rate / d dB/s to the slope, so 1 / target = 1 / measured + rate / d.  An envelope
@@ -1114,6 +1149,48 @@ class Convolution:
         return dict(origin=int(info[0]), taps=int(info[1]), sti={name: float(sti[s]) for s, name in enumerate(DECAY_SETS)}, mtf=mtf,
                     rows={(g, name): dict(energy=float(rows[g, s, 0]), mti=float(rows[g, s, 1]), status=int(rows[g, s, 2]))
                           for g in range(groups) for s, name in enumerate(DECAY_SETS)})
+
+    def ir_response(self, idx, hz=None, windows=None, onset_db=-20.0, end=0, rate=None):
+        """The frequency response of the stored taps of IR idx, measured on the device (mc_ir_response; include/mcconv.h has the
+        definition).  rate defaults to the engine's sample_rate, then to 44100.  hz=None means response_grid() clipped to 0.45 rate;
+        at most 1024 frequencies, each in [0, rate / 2].  windows=None is the whole span from the origin; otherwise up to 64 windows,
+        each a (first, count, rise, fall) tuple in taps from the origin or None for the whole span (waterfall_windows makes a row of
+        them); a window clips to the span.  Returns {"origin", "taps", "hz", "spans", "rows", "h", "delay", "db", "phase"}: hz as
+        float32; spans int [n_win, 2], the taps [a, b) of each window; h complex128 [n_win, 2, n_freq], phase counted from the
+        origin; delay the group delay in taps from the origin (NaN where |H| = 0); db = 20 log10 |H| (-400 where |H| = 0); phase =
+        atan2(Im, Re); rows maps (w, "L" | "R") to {energy, abs_sum, status}; status 1: a window without taps or a silent one,
+        h is 0 and delay NaN."""
+        if rate is None:
+            rate = self.sample_rate or 44100
+        if hz is None:
+            hz = response_grid(20.0, min(20000.0, 0.45 * rate))
+        hz = _f32(hz).reshape(-1)
+        windows = [None] if windows is None else list(windows)
+        if not 1 <= hz.size <= _lib.MC_RSP_MAX_FREQ:
+            raise ValueError(f"{hz.size} frequencies; 1 to {_lib.MC_RSP_MAX_FREQ}")
+        if not 1 <= len(windows) <= _lib.MC_RSP_MAX_WIN:
+            raise ValueError(f"{len(windows)} windows; 1 to {_lib.MC_RSP_MAX_WIN}")
+        c = McResponseQuery()
+        self._L.mc_default_response_query(C.byref(c))
+        c.rate, c.n_freq, c.n_win, c.onset_db, c.end = int(rate), hz.size, len(windows), float(onset_db), int(end)
+        win = (McResponseWindow * len(windows))()
+        for k, w in enumerate(windows):
+            win[k].first, win[k].count, win[k].rise, win[k].fall = (0, 0, 0, 0) if w is None else (int(v) for v in w)
+        resp = np.empty((len(windows), 2, hz.size, 3), np.float64)
+        rows = np.empty((len(windows), 2, 4), np.float64)
+        spans = np.empty((len(windows), 2), np.uint64)
+        info = (C.c_uint64 * 2)()
+        dp = C.POINTER(C.c_double)
+        check(self._L.mc_ir_response(self._h, idx, C.byref(c), _fp(hz), win, resp.ctypes.data_as(dp), rows.ctypes.data_as(dp),
+                                     spans.ctypes.data_as(C.POINTER(C.c_uint64)), info))
+        h = resp[..., 0] + 1j * resp[..., 1]
+        mag = np.abs(h)
+        with np.errstate(divide="ignore"):
+            db = np.where(mag > 0.0, np.maximum(20.0 * np.log10(mag), RESPONSE_FLOOR_DB), RESPONSE_FLOOR_DB)
+        return dict(origin=int(info[0]), taps=int(info[1]), hz=hz.copy(), spans=spans.astype(np.int64), h=h, delay=resp[..., 2].copy(), db=db,
+                    phase=np.arctan2(resp[..., 1], resp[..., 0]),
+                    rows={(w, name): dict(energy=float(rows[w, s, 0]), abs_sum=float(rows[w, s, 1]), status=int(rows[w, s, 2]))
+                          for w in range(len(windows)) for s, name in enumerate(RESPONSE_CHANNELS)})
 
     def ir_tail_info(self, idx):
         """What the tail step of IR idx's load did (mc_ir_tail_info): the bands it touched, the frames that came in, the frames

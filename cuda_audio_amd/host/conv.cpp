@@ -5,6 +5,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <limits>
 #include <string>
 
 #include "../../include/mcconv_group.h"
@@ -62,6 +63,12 @@ int mc_ir_tail_width_from_iacc(mc_ir_tail*, double) __attribute__((weak));
 // ... no STI measurement
 void mc_default_sti_query(mc_sti_query*) __attribute__((weak));
 int mc_ir_sti(mc_engine*, uint64_t, const mc_sti_query*, double*, double*, double*, uint64_t*) __attribute__((weak));
+// ... no response measurement (the grid and the smoothing are the engine's host arithmetic: they come and go with it)
+void mc_default_response_query(mc_response_query*) __attribute__((weak));
+int mc_ir_response(mc_engine*, uint64_t, const mc_response_query*, const float*, const mc_response_window*, double*, double*, uint64_t*, uint64_t*)
+    __attribute__((weak));
+int mc_response_grid(double, double, uint32_t, float*, uint32_t) __attribute__((weak));
+int mc_response_smooth(const float*, const double*, uint32_t, double, double*) __attribute__((weak));
 int mc_load_ir_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
                     const mc_ir_tail*) __attribute__((weak));
 int mc_load_ir_sweep_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
@@ -844,6 +851,82 @@ void Convolution::reportSti(size_t idx) {
     }
 }
 
+void Convolution::setIrResponseReport(bool on, const ResponseQuery& query) {
+    if (on && _group) {
+        Log::error("conv", "the IR response report is not available with several devices (mc_ir_response is single-engine)");
+        std::exit(2);
+    }
+    _responseReport = on;
+    _responseQuery = query;
+}
+
+bool Convolution::parseResponse(const std::string& arg, ResponseQuery& out, std::string& why) {
+    char* end = nullptr;
+    const double octaves = std::strtod(arg.c_str(), &end);
+    if (end == arg.c_str() || *end || !std::isfinite(octaves) || octaves < 0.0 || octaves > 10.0) {
+        why = "takes OCTAVES: the width the report's levels are smoothed over, in [0, 10]";
+        return false;
+    }
+    out.smoothOctaves = octaves;
+    return true;
+}
+
+Convolution::Response Convolution::irResponse(size_t idx, const ResponseQuery& query) {
+    if (!mc_ir_response || !mc_default_response_query || !mc_response_grid || !mc_response_smooth) {
+        Log::error("conv", "the engine has no response measurement (mc_ir_response)");
+        std::exit(2);
+    }
+    const double rate = (double)samplerate;
+    Response r;
+    r.hz.resize(MC_RSP_MAX_FREQ);
+    const int n = mc_response_grid(20.0, std::min(20000.0, 0.45 * rate), 24, r.hz.data(), (uint32_t)r.hz.size());
+    mc_response_query q;
+    mc_default_response_query(&q);
+    q.rate = (uint32_t)samplerate;
+    q.n_freq = n > 0 ? (uint32_t)n : 0;
+    r.hz.resize(q.n_freq);
+    r.resp.resize((size_t)2 * q.n_freq * 3);
+    r.smoothed.resize((size_t)2 * q.n_freq);
+    uint64_t spans[2] = {0, 0}, info[2] = {0, 0};
+    if (mc_ir_response(_engine, idx, &q, r.hz.data(), nullptr, r.resp.data(), r.rows, spans, info) != MC_OK) {  // (a rate the engine does not take)
+        Log::error("conv", "IR %zu: the response cannot be measured: %s", idx, mc_last_error());
+        std::exit(2);
+    }
+    r.origin = info[0], r.taps = info[1];
+    std::vector<double> power(q.n_freq);
+    for (int c = 0; c < 2; c++) {
+        for (size_t f = 0; f < q.n_freq; f++) power[f] = r.re(c, f) * r.re(c, f) + r.im(c, f) * r.im(c, f);
+        if (mc_response_smooth(r.hz.data(), power.data(), q.n_freq, query.smoothOctaves, r.smoothed.data() + (size_t)c * q.n_freq) != MC_OK) {
+            Log::error("conv", "IR %zu: the response cannot be smoothed: %s", idx, mc_last_error());
+            std::exit(2);
+        }
+    }
+    return r;
+}
+
+size_t Convolution::Response::nearest(double f) const {
+    const long i = std::lround(24.0 * std::log2(f / 20.0));  // (the grid is 20 2^(i / 24))
+    return (size_t)std::min<long>(std::max<long>(i, 0), (long)hz.size() - 1);
+}
+
+void Convolution::reportResponse(size_t idx) {
+    static const char* const channel[2] = {"L", "R"};
+    static const double centre[10] = {31.5, 63.0, 125.0, 250.0, 500.0, 1000.0, 2000.0, 4000.0, 8000.0, 16000.0};
+    const Response r = irResponse(idx, _responseQuery);
+    const double nan = std::numeric_limits<double>::quiet_NaN(), top = 0.45 * (double)samplerate;
+    const size_t k1 = r.nearest(1000.0);
+    for (int c = 0; c < 2; c++) {
+        const bool bad = r.rows[4 * c + 2] != 0.0;
+        const auto db = [&](size_t f) { return bad ? nan : 10.0 * std::log10(r.smoothed[(size_t)c * r.hz.size() + f]); };
+        std::string levels;
+        for (double f : centre)
+            if (f < top) levels += " " + places(db(r.nearest(f)) - db(k1), 2);
+        Log::info(name, "IR %zu response %s: origin %llu, 1 kHz level %s dB, octaves%s, delay at 1 kHz %s ms, status %d", idx, channel[c],
+                  (unsigned long long)r.origin, places(db(k1), 2).c_str(), levels.c_str(), places(r.delay(c, k1) * 1000.0 / (double)samplerate, 3).c_str(),
+                  bad ? 1 : 0);
+    }
+}
+
 mc_ir_synth Convolution::synthFrames(const IrSynth& y, double rate) {
     const auto frames = [&](double seconds) { return (uint64_t)std::nearbyint(seconds * rate); };
     mc_ir_synth s;
@@ -1393,13 +1476,14 @@ void Convolution::loadPendingIrs() {
         if (_densityReport) reportDensity(p.idx);
         if (_iaccReport) reportIacc(p.idx);
         if (_stiReport) reportSti(p.idx);
+        if (_responseReport) reportResponse(p.idx);
         _tailOn = false;
     }
     _pendingIrs.clear();
 }
 
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
-    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _stiReport || _irTail.mode != IrTail::Off) {  // (loaded by onStart(), once the client's rate is known)
+    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _stiReport || _responseReport || _irTail.mode != IrTail::Off) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
         _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth(), false, IrSweep()});
         if (idx + 1 > _nirs) _nirs = idx + 1;

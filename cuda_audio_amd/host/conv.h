@@ -332,6 +332,31 @@ public:
     static bool parseSti(const std::string& arg, StiQuery& out, std::string& why);
     // "bad", "poor", "fair", "good" or "excellent" at the edges 0.30, 0.45, 0.60, 0.75; "none" for NaN
     static const char* stiRating(double sti);
+    // The frequency response of a loaded IR, measured by the engine from the taps it convolves with (mc_ir_response of
+    // include/mcconv.h, which has the definition; no reference equivalent): the whole span from the origin, on the grid of 24
+    // points per octave from 20 Hz to min(20 kHz, 0.45 rate) at the client's rate (mc_response_grid), with the power |H|^2 of each
+    // channel smoothed over smoothOctaves (mc_response_smooth).
+    struct ResponseQuery {
+        double smoothOctaves = 1.0;
+    };
+    struct Response {
+        uint64_t origin = 0, taps = 0;
+        std::vector<float> hz;
+        std::vector<double> resp;      // per channel (L, R) and frequency {Re H, Im H, group delay in taps from the origin}
+        std::vector<double> smoothed;  // per channel and frequency: |H|^2, smoothed
+        double rows[8] = {};           // per channel {E, A, status, 0}
+        double re(int c, size_t f) const { return resp[((size_t)c * hz.size() + f) * 3]; }
+        double im(int c, size_t f) const { return resp[((size_t)c * hz.size() + f) * 3 + 1]; }
+        double delay(int c, size_t f) const { return resp[((size_t)c * hz.size() + f) * 3 + 2]; }
+        size_t nearest(double f) const;  // the grid point nearest to f Hz, in octaves
+    };
+    Response irResponse(size_t idx, const ResponseQuery& query);
+    // One log line per IR loaded from now on and channel (origin, the smoothed level at 1 kHz, the levels of the octaves 31.5 Hz ..
+    // 16 kHz below 0.45 rate relative to it, the group delay at 1 kHz, status: 1 for a silent channel).  Loaded by onStart(),
+    // single device only, as setIrDecayReport.
+    void setIrResponseReport(bool on, const ResponseQuery& query);
+    // The argument of --ir-response-smooth (OCTAVES in [0, 10]) into `out`.  False, with the reason in `why`, for a malformed one.
+    static bool parseResponse(const std::string& arg, ResponseQuery& out, std::string& why);
     // The tail step every IR loaded from now on goes through (mc_ir_tail of include/mcconv.h; no reference equivalent): the IR
     // is loaded as it is, its floor is measured in the bands of setIrFloorXovers, and it is loaded again with every band cut at
     // its knee (Cut) or cross-faded there into decaying noise (Extend) ahead of its shape, EQ and damping.  An IR whose
@@ -404,6 +429,9 @@ private:
     void reportSti(size_t idx);
     bool _stiReport = false;
     StiQuery _stiQuery;
+    void reportResponse(size_t idx);
+    bool _responseReport = false;
+    ResponseQuery _responseQuery;
     bool _iaccReport = false;
     IaccQuery _iaccQuery;
     bool _densityReport = false;

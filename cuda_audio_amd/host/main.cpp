@@ -54,6 +54,9 @@
 // --ir-sti-report: after each IR is loaded one log line per channel set (L, R, LR) with its speech transmission index (origin,
 // STI and its rating, the seven octaves' MTI, status; measured by the engine: Convolution::setIrStiReport); --ir-sti-snr
 // DB[,DB...]: stationary noise at that signal-to-noise ratio, one value for all octaves or one per octave.
+// --ir-response-report: after each IR is loaded one log line per channel with its frequency response (origin, the level at
+// 1 kHz, the octaves 31.5 Hz .. 16 kHz relative to it, the group delay at 1 kHz, status; measured by the engine:
+// Convolution::setIrResponseReport); --ir-response-smooth OCTAVES: the width the levels are smoothed over (1 without).
 #include <cassert>
 #include <cstdlib>
 #include <cstring>
@@ -90,6 +93,8 @@ int main(int argc, char** argv) {
     Convolution::IaccQuery irIacc;
     bool irStiReport = false;
     Convolution::StiQuery irSti;
+    bool irResponseReport = false;
+    Convolution::ResponseQuery irResponse;
     for (int i = 1; i < argc; i++) {
         if (!strcmp(argv[i], "--periods") && i + 1 < argc) periods = strtoull(argv[++i], nullptr, 10);
         else if (!strcmp(argv[i], "--settings") && i + 1 < argc) settingsPath = argv[++i];
@@ -227,6 +232,14 @@ int main(int argc, char** argv) {
                 std::cerr << option << " '" << argv[i] << "': " << why << std::endl;
                 return 2;
             }
+        } else if (!strcmp(argv[i], "--ir-response-report")) irResponseReport = true;
+        else if (!strcmp(argv[i], "--ir-response-smooth") && i + 1 < argc) {
+            std::string why;
+            const char* option = argv[i];
+            if (!Convolution::parseResponse(argv[++i], irResponse, why)) {
+                std::cerr << option << " '" << argv[i] << "': " << why << std::endl;
+                return 2;
+            }
         } else if (!strcmp(argv[i], "--ir-rt60") && i + 1 < argc) {
             irRt60 = atof(argv[++i]);
             if (!(irRt60 > 0.0)) {
@@ -273,6 +286,7 @@ int main(int argc, char** argv) {
         c->setIrDensityReport(irDensityReport, irDensity);
         c->setIrIaccReport(irIaccReport, irIacc);
         c->setIrStiReport(irStiReport, irSti);
+        c->setIrResponseReport(irResponseReport, irResponse);
         c->setIrTail(irTail);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;

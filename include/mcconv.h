@@ -537,6 +537,66 @@ void mc_default_sti_query(mc_sti_query *q);
  * on the same IR return the same bits. */
 int mc_ir_sti(mc_engine *e, uint64_t idx, const mc_sti_query *q, double *rows, double *mtf, double sti[3], uint64_t info[2]);
 
+/* The frequency response of a loaded IR, measured on the device: the curve of the taps the engine convolves with, as every
+ * convolution reverb shows it, at frequencies of the caller's choosing and over windows of the caller's choosing (one window:
+ * the response; a row of overlapping windows: a waterfall).  mc_ir_eq_response and mc_ir_damp_response are the curves of the
+ * filters a load applied; this is the curve of what came out.  No reference equivalent; single-engine.  The stored taps are only
+ * read.  Everything is in double, computed from the fields as they are (frequencies are floats, as in every other query).
+ *   1. N and the origin o are those of mc_ir_decay's step 1, from onset_db and end;
+ *   2. window w covers the taps [a, b): a = min(o + first, N), b = count ? min(a + count, N) : N, L = b - a.  Its edges are
+ *      raised cosines of r = min(rise, L) and f = min(fall, L - r) taps, the form of mc_ir_shape's fade: the weight of tap a + k
+ *      is u = (1 - cos(pi (k + 1) / (r + 1))) / 2 for k < r, (1 + cos(pi (k' + 1) / (f + 1))) / 2 for the last f taps, k' counted
+ *      from the first of them, and 1 between.  A window cannot be wrong: it clips, down to no taps at all.  win == NULL with
+ *      n_win = 1 is the whole span, {0, 0, 0, 0};
+ *   3. per channel c in {L, R} and frequency F_f = (double) hz[f], finite and in [0, rate / 2], with theta = 2 pi F_f (m - o) / rate
+ *      and the sums over m in [a, b): H_c(f) = sum of u x_c[m] e^(-j theta), D_c(f) = sum of (m - o) u x_c[m] e^(-j theta),
+ *      E_c = sum of (u x_c[m])^2, A_c = sum of |u x_c[m]|.  The phase of H is counted from the origin, not from tap 0;
+ *   4. the group delay tau_c(f) = Re(D conj H) / |H|^2 in taps from o: exact, not a difference of phases.  NaN when |H|^2 is 0
+ *      or not finite;
+ *   5. status 1 when L = 0 or A is 0 or not finite: H = 0 and tau is NaN;
+ *   6. resp[((2 w + c) n_freq + f) 3 ..] = {Re H, Im H, tau}; rows[(2 w + c) 4 ..] = {E, A, status, 0}; spans[2 w ..] = {a, b};
+ *      info = {o, N}.
+ * There is no third channel set: a mono sum's response is H_L + H_R and a power sum is |H_L|^2 + |H_R|^2, one line each for
+ * the caller, and neither has an energy that is consistent with the other.  |delta H| <= (L + 227) 2^-53 A. */
+#define MC_RSP_MAX_FREQ 1024
+#define MC_RSP_MAX_WIN 64
+typedef struct {
+    uint64_t first;         /* the window's first tap, counted from the origin */
+    uint64_t count;         /* its taps; 0: to the end of the span */
+    uint32_t rise, fall;    /* the taps of its raised-cosine edges; clamped to the window */
+} mc_response_window;       /* sizeof = 24 */
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_response_query) = 40 */
+    uint32_t rate;          /* the rate the stored taps are at, [8000, 384000] */
+    uint32_t n_freq;        /* 1 .. MC_RSP_MAX_FREQ */
+    uint32_t n_win;         /* 1 .. MC_RSP_MAX_WIN */
+    uint32_t flags;         /* must be 0 */
+    float onset_db;         /* as mc_decay_query; default -20 */
+    uint64_t end;           /* as mc_decay_query */
+    uint32_t reserved[2];   /* must be 0 */
+} mc_response_query;
+/* rate 44100, n_freq 0 (the caller sets it with hz), n_win 1, onset -20, end 0 */
+void mc_default_response_query(mc_response_query *q);
+/* hz: [n_freq]; win: [n_win] or NULL (n_win = 1: the whole span); resp: [n_win * 2 * n_freq * 3]; rows: [n_win * 2 * 4]; spans:
+ * [n_win * 2]; info = {origin tap o, taps analysed N}.  Checked in this order, all before the engine or the device is touched
+ * (MC_ERR_ARG, the message names the field): the query field by field in struct order (struct_size, rate, n_freq - "n_freq 0
+ * outside [1, 1024]" -, n_win, flags, onset_db, reserved), every hz[f], the pointers ("null hz", "null win" when n_win > 1, "null
+ * resp", "null rows", "null spans", "null info"), idx ("IR not loaded").  MC_ERR_STATE in the single-transform form, which keeps
+ * no taps.  Threading, stream and the promise that nothing the engine holds changes are mc_ir_decay's.  Scratch is the partial
+ * sums of the largest window, ceil(L / 1024) (8 n_freq + 4) doubles, allocated by the call and freed before it returns.  Two
+ * calls with the same query on the same IR return the same bits; a frequency's three numbers do not depend on the other
+ * frequencies of the query or on its place among them, and a window's numbers do not depend on the other windows. */
+int mc_ir_response(mc_engine *e, uint64_t idx, const mc_response_query *q, const float *hz, const mc_response_window *win,
+                   double *resp, double *rows, uint64_t *spans, uint64_t info[2]);
+/* Host arithmetic only.  hz[i] = (float)(lo_hz 2^(i / per_octave)), i = 0, 1, .. while that double is <= hi_hz: a grid with
+ * per_octave points to the octave.  Returns the count; MC_ERR_ARG unless 0 < lo_hz <= hi_hz (finite), per_octave in [1, 96],
+ * hz is not null and the count fits cap. */
+int mc_response_grid(double lo_hz, double hi_hz, uint32_t per_octave, float *hz, uint32_t cap);
+/* Host arithmetic only.  out[f] = the mean of power[g] over all g with hz[g] in [hz[f] 2^(-octaves / 2), hz[f] 2^(octaves / 2)],
+ * summed in ascending g: fractional-octave smoothing of a power response (|H|^2) on any ascending grid.  hz [n]: finite, >= 0,
+ * not descending; octaves finite in [0, 10]; with 0, out is power itself, bit for bit.  out may not overlap power. */
+int mc_response_smooth(const float *hz, const double *power, uint32_t n, double octaves, double *out);
+
 /* Synthesis of an IR on the device from a seed: a room from a few numbers instead of a recorded WAV.  No reference equivalent;
  * single-engine, as shaping is.  The F = frames stereo frames are generated at the session's rate into the buffer the shaped
  * load's steps read and never exist on the host.  Frame m is a pure function of (seed, m, this struct): the same struct gives
