@@ -28,6 +28,7 @@ SYMBOLS = [
     "mc_default_sti_query", "mc_ir_sti",
     "mc_default_response_query", "mc_ir_response", "mc_response_grid", "mc_response_smooth",
     "mc_default_ir_tail", "mc_load_ir_tail", "mc_load_ir_sweep_tail", "mc_ir_tail_info",
+    "mc_default_ir_phase", "mc_ir_phase_plan", "mc_load_ir_phase", "mc_load_ir_sweep_phase", "mc_ir_phase_info",
     "mc_default_ir_room", "mc_synth_ir_room", "mc_ir_room_info", "mc_ir_room_plan",
     "mc_default_ir_room_mics", "mc_synth_ir_room_mics", "mc_ir_room_mics_plan", "mc_ir_room_mics_info",
     "mc_default_ir_room_bands", "mc_synth_ir_room_bands", "mc_ir_room_bands_plan", "mc_ir_room_bands_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
@@ -326,6 +327,20 @@ class McIrTail(C.Structure):
     ]
 
 
+MC_PHASE_OFF, MC_PHASE_MINIMUM = 0, 1
+
+
+class McIrPhase(C.Structure):
+    """mc_ir_phase: the phase step of mc_load_ir_phase and mc_load_ir_sweep_phase."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("floor_db", C.c_float),
+        ("over_log2", C.c_uint32),
+    ]
+
+
 MC_ROOM_MAX_ORDER = 32
 
 
@@ -481,6 +496,12 @@ def load():
     L.mc_load_ir_sweep_tail.argtypes = [vp, u64, fp, u64, u64, C.POINTER(McSweep), C.c_int64, u64, C.POINTER(McIrShape), C.POINTER(McIrEq),
                                         C.POINTER(McIrDamp), C.POINTER(McIrTail)]
     L.mc_ir_tail_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_default_ir_phase.argtypes = [C.POINTER(McIrPhase)]
+    L.mc_default_ir_phase.restype = None
+    L.mc_ir_phase_plan.argtypes = [C.POINTER(McIrPhase), u64, C.POINTER(C.c_double)]
+    L.mc_load_ir_phase.argtypes = L.mc_load_ir_tail.argtypes + [C.POINTER(McIrPhase)]
+    L.mc_load_ir_sweep_phase.argtypes = L.mc_load_ir_sweep_tail.argtypes + [C.POINTER(McIrPhase)]
+    L.mc_ir_phase_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_default_ir_room.argtypes = [C.POINTER(McIrRoom)]
     L.mc_default_ir_room.restype = None
     L.mc_synth_ir_room.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrRoom), C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp),

@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrRoom, McIrRoomBands, McIrRoomMics, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrRoom, McIrRoomBands, McIrRoomMics, McIrPhase, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -273,6 +273,41 @@ class IrTail:
         for j, pair in enumerate(self.level_db[:bands]):
             t.level_db[j][0], t.level_db[j][1] = float(pair[0]), float(pair[1])
         return t
+
+
+@dataclasses.dataclass
+class IrPhase:
+    """What prepare(phase=...) and prepare_sweep(phase=...) do to the phase of an IR after the conversion and the tail step and
+    before everything else (mc_ir_phase, include/mcconv.h): mode "minimum" replaces the frames by the minimum-phase IR of the
+    same magnitude response, which takes out the delay an IR carries inside it (for short IRs: cabinets, equaliser captures);
+    "off" does nothing.  floor_db (40 .. 300) bounds how far below its largest bin the spectrum is followed; oversample (a
+    power of two, 2 .. 64) is the transform's length over the IR's, rounded up to a power of two."""
+
+    mode: str = "minimum"
+    floor_db: float = 120.0
+    oversample: int = 8
+
+    MODES = {"off": _lib.MC_PHASE_OFF, "minimum": _lib.MC_PHASE_MINIMUM}
+
+    def to_c(self):
+        if self.mode not in self.MODES:
+            raise ValueError(f"mode must be one of {sorted(self.MODES)}, not {self.mode!r}")
+        over = int(self.oversample)
+        if over < 2 or over > 64 or over & (over - 1):
+            raise ValueError(f"oversample must be a power of two from 2 to 64, not {self.oversample!r}")
+        p = McIrPhase()
+        _lib.load().mc_default_ir_phase(C.byref(p))
+        p.mode, p.floor_db, p.over_log2 = self.MODES[self.mode], float(self.floor_db), over.bit_length() - 1
+        return p
+
+
+def phase_plan(phase, frames):
+    """What the phase step `phase` (an IrPhase) would do to `frames` frames at the session's rate (mc_ir_phase_plan, host
+    arithmetic only): the transform's length, its passes and the device memory the step needs while it runs.  McError for
+    frames or an oversampling beyond the step's limits (2^21 frames, a transform of 2^22 points)."""
+    out = (C.c_double * 4)()
+    check(_lib.load().mc_ir_phase_plan(C.byref(phase.to_c()), int(frames), out))
+    return dict(nfft=int(out[0]), passes=int(out[1]), device_bytes=int(out[2]))
 
 
 def tail_from_floor(floor, first=0, mode="extend", fade=0, length=0, seed=0, width=1.0):
@@ -748,7 +783,7 @@ class Convolution:
         check(self._L.mc_set_period(self._h, nframes))
 
     # -- reference surface ----------------------------------------------------
-    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None, damp=None, tail=None):
+    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None, damp=None, tail=None, phase=None):
         """Convolution::prepare (conv.cu:207-253).  `wav` is float32 [frames, 2]
         (what WavFile.buffer holds) or an object with a `.buffer` of that shape.
         ir_rate (Hz; default: `wav.sampleRate` when it has one): when both it and the engine's sample_rate are known and
@@ -760,10 +795,26 @@ class Convolution:
         damp (an IrDamp): a further decay per frequency band, after the fade and before the EQ (mc_load_ir_damped); the rates
         as for eq; ir_damp_info(idx) then tells what was done.
         tail (an IrTail whose mode is not "off"): cut or extend the tail of the frames band by band, after the conversion and
-        before everything else (mc_load_ir_tail); the rates as for eq; ir_tail_info(idx) then tells what was done."""
+        before everything else (mc_load_ir_tail); the rates as for eq; ir_tail_info(idx) then tells what was done.
+        phase (an IrPhase whose mode is not "off"): convert the frames to minimum phase, after the tail step and before
+        the shape (mc_load_ir_phase); it needs no rate; ir_phase_info(idx) then tells what was done."""
         lr = _f32(getattr(wav, "buffer", wav)).reshape(-1, 2)
         if ir_rate is None:
             ir_rate = getattr(wav, "sampleRate", None)
+        if phase is not None and phase.mode != "off":
+            tailed = tail is not None and tail.mode != "off"
+            if tailed or eq is not None or (damp is not None and damp.xovers):
+                session = int(self.sample_rate or 0)
+                rates = (session if ir_rate is None else int(ir_rate), session)
+            elif ir_rate is not None and self.sample_rate is not None and int(ir_rate) != int(self.sample_rate):
+                rates = (int(ir_rate), int(self.sample_rate))
+            else:
+                rates = (0, 0)
+            check(self._L.mc_load_ir_phase(self._h, idx, _fp(lr), lr.shape[0], nframes, *rates,
+                                           C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
+                                           C.byref(damp.to_c()) if damp is not None else None, C.byref(tail.to_c()) if tailed else None,
+                                           C.byref(phase.to_c())))
+            return
         if tail is not None and tail.mode != "off":
             session = int(self.sample_rate or 0)
             check(self._L.mc_load_ir_tail(self._h, idx, _fp(lr), lr.shape[0], nframes, session if ir_rate is None else int(ir_rate), session,
@@ -827,7 +878,7 @@ class Convolution:
         check(self._L.mc_synth_ir(self._h, idx, nframes, C.byref(s), C.byref(shape.to_c()) if shape is not None else None,
                                   C.byref(eq.to_c()) if eq is not None else None, C.byref(damp.to_c()) if damp is not None else None))
 
-    def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None, tail=None):
+    def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None, tail=None, phase=None):
         """Deconvolve `recording` (float32 [frames, 2] or an object with such a `.buffer`: what was recorded while `sweep`, a
         Sweep, played) into an IR on the device and store it at idx (mc_load_ir_sweep): the frames take the place of a WAV's at
         the session's rate, and shape, eq and damp apply to them as in prepare().  IR frame m is the correlation at lag
@@ -835,7 +886,8 @@ class Convolution:
         pre-roll where the harmonic-distortion images land.  ir_frames defaults to max(1, M - N + 1 - offset), what the
         recording holds past the sweep, clamped to the library's caps.  The engine's sample_rate is passed unless sweep.rate
         is set (the library's default, 44100, when the engine has none either).  tail (an IrTail whose mode is not "off"): the
-        tail step on the deconvolved frames (mc_load_ir_sweep_tail)."""
+        tail step on the deconvolved frames (mc_load_ir_sweep_tail).  phase (an IrPhase whose mode is not "off"): the phase step
+        after it (mc_load_ir_sweep_phase)."""
         lr = _f32(getattr(recording, "buffer", recording)).reshape(-1, 2)
         s = sweep.to_c()
         if not sweep.rate and self.sample_rate:
@@ -846,7 +898,9 @@ class Convolution:
         args = (self._h, idx, _fp(lr), lr.shape[0], nframes, C.byref(s), int(offset), int(ir_frames),
                 C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
                 C.byref(damp.to_c()) if damp is not None else None)
-        if tail is not None and tail.mode != "off":
+        if phase is not None and phase.mode != "off":
+            check(self._L.mc_load_ir_sweep_phase(*args, C.byref(tail.to_c()) if tail is not None else None, C.byref(phase.to_c())))
+        elif tail is not None and tail.mode != "off":
             check(self._L.mc_load_ir_sweep_tail(*args, C.byref(tail.to_c())))
         else:
             check(self._L.mc_load_ir_sweep(*args))
@@ -1198,6 +1252,16 @@ class Convolution:
         out = (C.c_double * 4)()
         check(self._L.mc_ir_tail_info(self._h, idx, out))
         return dict(bands=int(out[0]), frames=int(out[1]), length=int(out[2]), first=int(out[3]))
+
+    def ir_phase_info(self, idx):
+        """What the phase step of IR idx's load did (mc_ir_phase_info): the frames it took and handed on, the transform's length,
+        the energy that went in and came out (energy_out / energy_in is what the truncation to `frames` kept), the centres of
+        energy in frames (centre_in - centre_out is the delay removed) and the bins of either channel that the floor
+        clamped.  McError (MC_ERR_STATE) for an IR whose last load had no phase step."""
+        out = (C.c_double * 8)()
+        check(self._L.mc_ir_phase_info(self._h, idx, out))
+        return dict(frames=int(out[0]), nfft=int(out[1]), energy_in=float(out[2]), energy_out=float(out[3]), centre_in=float(out[4]),
+                    centre_out=float(out[5]), clamped=(int(out[6]), int(out[7])))
 
     def enable_kernel_timing(self, on=True):
         check(self._L.mc_enable_kernel_timing(self._h, 1 if on else 0))

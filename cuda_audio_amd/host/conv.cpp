@@ -74,6 +74,12 @@ int mc_load_ir_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint
 int mc_load_ir_sweep_tail(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
                           const mc_ir_damp*, const mc_ir_tail*) __attribute__((weak));
 int mc_ir_tail_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+void mc_default_ir_phase(mc_ir_phase*) __attribute__((weak));
+int mc_load_ir_phase(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
+                     const mc_ir_tail*, const mc_ir_phase*) __attribute__((weak));
+int mc_load_ir_sweep_phase(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
+                           const mc_ir_damp*, const mc_ir_tail*, const mc_ir_phase*) __attribute__((weak));
+int mc_ir_phase_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 // ... and no room
 void mc_default_ir_room(mc_ir_room*) __attribute__((weak));
 int mc_synth_ir_room(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_room*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
@@ -217,6 +223,12 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         Log::error("conv", "the engine has no room rendering (mc_synth_ir_room)");
         std::exit(2);
     }
+    const bool minimum = _irPhase.minimum && !synth;
+    if (_irPhase.minimum && synth) Log::info(name, "IR %zu is generated: it has no phase step and is loaded as it is", idx);
+    if (minimum && (!mc_default_ir_phase || !mc_load_ir_phase || !mc_load_ir_sweep_phase || !mc_ir_phase_info)) {
+        Log::error("conv", "the engine has no phase step (mc_load_ir_phase)");
+        std::exit(2);
+    }
     if (tail && (!mc_load_ir_tail || !mc_load_ir_sweep_tail || !mc_ir_tail_info)) {
         Log::error("conv", "the engine has no tail step (mc_load_ir_tail)");
         std::exit(2);
@@ -255,6 +267,13 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
     if (irRate && irRate != sessionRate) Log::info(name, "IR %zu: %u Hz -> %u Hz", idx, irRate, sessionRate);
     mc_ir_eq q;
     mc_ir_damp d;
+    mc_ir_phase ph;
+    if (minimum) {
+        mc_default_ir_phase(&ph);
+        ph.mode = MC_PHASE_MINIMUM;
+        ph.floor_db = _irPhase.floorDb;
+        ph.over_log2 = _irPhase.overLog2;
+    }
     if (!eq.off()) {
         mc_default_ir_eq(&q);
         for (size_t k = 0; k < eq.bands.size(); k++) q.band[k] = mc_eq_band{(uint32_t)eq.bands[k].kind, eq.bands[k].hz, eq.bands[k].gainDb, eq.bands[k].q};
@@ -306,7 +325,9 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         Log::info(name, "IR %zu synthesised: %llu frames, seed %llu, %d of %u reflections kept", idx, (unsigned long long)si[0],
                   (unsigned long long)synth->seed, (int)si[1], synth->n_early);
     } else if (sweep) {  // (as for a generated IR: what the engine refuses is the index line's fault)
-        const int rc = tail ? mc_load_ir_sweep_tail(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
+        const int rc = minimum ? mc_load_ir_sweep_phase(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
+                                                        eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, &ph)
+                       : tail  ? mc_load_ir_sweep_tail(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
                                                     eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
                             : mc_load_ir_sweep(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
                                                eq.off() ? nullptr : &q, damp.off() ? nullptr : &d);
@@ -318,6 +339,11 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         check(mc_ir_sweep_info(_engine, idx, wi), "mc_ir_sweep_info");
         Log::info(name, "IR %zu captured: sweep %llu frames, recording %llu frames, %llu frames at offset %lld", idx, (unsigned long long)wi[0],
                   (unsigned long long)wi[1], (unsigned long long)wi[2], (long long)wi[3]);
+    } else if (minimum) {  // (an IR too long for the step is the command line's fault: a message and exit 2, no abort)
+        if (mc_load_ir_phase(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, &ph) != MC_OK) {
+            Log::error("conv", "IR %zu cannot be converted to minimum phase: %s", idx, mc_last_error());
+            std::exit(2);
+        }
     } else if (tail) {
         check(mc_load_ir_tail(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail),
               "mc_load_ir_tail");
@@ -336,6 +362,14 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         Log::info(name, "IR %zu tail: %s, %d of %u bands at knees %s, %llu frames in, %llu out, first frame changed %llu", idx,
                   tail->mode == MC_TAIL_CUT ? "cut" : "extended", (int)ti[0], tail->n_xovers + 1, knees.c_str(), (unsigned long long)ti[1],
                   (unsigned long long)ti[2], (unsigned long long)ti[3]);
+    }
+    if (minimum) {
+        double pi[8];
+        check(mc_ir_phase_info(_engine, idx, pi), "mc_ir_phase_info");
+        const double removed = pi[4] - pi[5];
+        Log::info(name, "IR %zu minimum phase: %llu frames through a transform of %llu points, delay removed %.1f frames (%.3f ms), %.4f dB kept, %llu and %llu bins at the floor",
+                  idx, (unsigned long long)pi[0], (unsigned long long)pi[1], removed, samplerate ? 1000.0 * removed / (double)samplerate : 0.0,
+                  pi[2] > 0.0 && pi[3] > 0.0 ? 10.0 * std::log10(pi[3] / pi[2]) : 0.0, (unsigned long long)pi[6], (unsigned long long)pi[7]);
     }
     double info[8];
     check(mc_ir_shape_info(_engine, idx, info), "mc_ir_shape_info");
@@ -486,6 +520,53 @@ void Convolution::setIrTail(const IrTail& tail) {
     _irTail = tail;
 }
 
+void Convolution::setIrPhase(const IrPhase& phase) {
+    if (phase.minimum && _group) {
+        Log::error("conv", "the IR phase step is not available with several devices (mc_load_ir_phase is single-engine)");
+        std::exit(2);
+    }
+    _irPhase = phase;
+}
+
+bool Convolution::parsePhase(const std::string& arg, IrPhase& out, std::string& why) {
+    const auto fail = [&](const std::string& w) {
+        why = w + " (minimum[:key=value,...] with keys floor, over)";
+        return false;
+    };
+    const size_t colon = arg.find(':');
+    const std::string mode = arg.substr(0, colon);
+    IrPhase p;
+    if (mode != "minimum") return fail("the mode is minimum, not '" + mode + "'");
+    p.minimum = true;
+    if (colon != std::string::npos) {
+        const std::string list = arg.substr(colon + 1);
+        if (list.empty()) return fail("an empty list");
+        for (size_t at = 0; at <= list.size();) {
+            const size_t comma = std::min(list.find(',', at), list.size());
+            const std::string item = list.substr(at, comma - at);
+            at = comma + 1;
+            const size_t eqs = item.find('=');
+            if (item.empty() || eqs == std::string::npos || eqs == 0 || eqs + 1 == item.size()) return fail("'" + item + "' is not key=value");
+            const std::string key = item.substr(0, eqs), val = item.substr(eqs + 1);
+            char* end = nullptr;
+            const double v = std::strtod(val.c_str(), &end);
+            if (*end || !std::isfinite(v)) return fail("'" + val + "' of " + key + " is not a number");
+            if (key == "floor") {
+                if (v < 40.0 || v > 300.0) return fail("floor " + val + " dB outside [40, 300]");
+                p.floorDb = (float)v;
+            } else if (key == "over") {
+                unsigned lg = 0;
+                while (lg <= 6 && (double)(1u << lg) != v) lg++;
+                if (lg < 1 || lg > 6) return fail("over " + val + " is not a power of two from 2 to 64");
+                p.overLog2 = lg;
+            } else
+                return fail("no such key '" + key + "'");
+        }
+    }
+    out = p;
+    return true;
+}
+
 bool Convolution::parseTail(const std::string& arg, IrTail& out, std::string& why) {
     const auto fail = [&](const std::string& w) {
         why = w + " (cut|extend[:key=value,...] with keys fade, length, seed, width, knee)";
@@ -594,7 +675,10 @@ void Convolution::measureTail(const PendingIr& p) {
     PendingIr raw = p;
     raw.eq = IrEq();
     raw.damp = IrDamp();
+    const IrPhase phase = _irPhase;  // (the floor is that of the frames the tail step will see: before the phase step)
+    _irPhase = IrPhase();
     loadPending(raw, IrShape());
+    _irPhase = phase;
     const Floor f = irFloor(p.idx, _floorXovers);
     const double need = (double)f.query.margin_db + (double)f.query.span_db, ptn = f.at(0, Decay::LR, Floor::PeakToNoise);
     if (f.at(0, Decay::LR, Floor::Status) != 0.0 || !(ptn >= need)) {
@@ -1450,7 +1534,7 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
                    nullptr, _tailOn ? &_tailNow : nullptr);
         return;
     }
-    if (!shape.off()) {
+    if (!shape.off() || _irPhase.minimum) {
         loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : 0, convert ? (unsigned)samplerate : 0, shape);
         return;
     }
@@ -1483,7 +1567,7 @@ void Convolution::loadPendingIrs() {
 }
 
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
-    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _stiReport || _responseReport || _irTail.mode != IrTail::Off) {  // (loaded by onStart(), once the client's rate is known)
+    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _stiReport || _responseReport || _irTail.mode != IrTail::Off || _irPhase.minimum) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
         _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth(), false, IrSweep()});
         if (idx + 1 > _nirs) _nirs = idx + 1;

@@ -382,6 +382,20 @@ public:
     // The argument of --ir-tail, cut|extend[:key=value,...] with keys fade, length (seconds), seed, width (a number or iacc) and knee (floor|mix), as an IrTail.
     // False, with the reason in `why`, for a malformed one.
     static bool parseTail(const std::string& arg, IrTail& out, std::string& why);
+    // The phase step every IR loaded from now on goes through (mc_ir_phase of include/mcconv.h; no reference equivalent): the
+    // frames are replaced by the minimum-phase IR of the same magnitude response, after the conversion and the tail step and
+    // ahead of the shape, EQ and damping, which takes out the delay a short IR carries inside it.  One log line per load tells
+    // the delay removed (frames and ms at the client's rate) and what the truncation to the IR's length kept.  Loaded by
+    // onStart(), single device only.  A generated IR has no phase step and is loaded as it is, with a log line that says so.
+    struct IrPhase {
+        bool minimum = false;
+        float floorDb = 120.0f;  // [40, 300]: how far below its largest bin the spectrum is followed
+        unsigned overLog2 = 3;   // the transform is 2^overLog2 times the IR's length rounded up to a power of two; 1 .. 6
+    };
+    void setIrPhase(const IrPhase& phase);
+    // The argument of --ir-phase, minimum[:key=value,...] with keys floor (dB) and over (2, 4, .. 64), as an IrPhase.  False,
+    // with the reason in `why`, for a malformed one.
+    static bool parsePhase(const std::string& arg, IrPhase& out, std::string& why);
 
     void onMidiMessage(const RawMidi::Device* sender, const uint8_t* buffer, size_t len) override;
 
@@ -440,6 +454,7 @@ private:
     bool _floorReport = false;
     std::vector<float> _floorXovers;
     IrTail _irTail;
+    IrPhase _irPhase;
     bool _tailOn = false;  // loadPending: the IR being loaded goes through _tailNow
     mc_ir_tail _tailNow;
     bool _decayReport = false;

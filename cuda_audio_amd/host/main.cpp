@@ -42,6 +42,10 @@
 // are row groups of their own, and the bands of --ir-tail; --ir-tail cut|extend[:fade=S,length=S,seed=N,width=W]: every IR is
 // loaded, its floor measured, and loaded again with every band cut at its knee or extended from there with decaying noise,
 // ahead of the other --ir-* options, Convolution::setIrTail; an IR with less than 30 dB between peak and floor is left as it is.
+// --ir-phase minimum[:floor=DB,over=K]: every IR (a WAV or a captured sweep; a generated one is left as it is) is converted to
+// minimum phase on load, after --ir-tail's step and ahead of the other --ir-* options: the same magnitude response with the
+// delay inside the IR taken out (Convolution::setIrPhase; floor: the dynamic range of the log spectrum in dB, 120 without; over:
+// the oversampling of the transform, 2 .. 64, 8 without); one log line tells the delay removed and what the truncation kept.
 // --ir-density-report: after each IR is loaded one log line with its echo density (origin, mixing tap and time, first, largest and
 // later density of the LR row, measured by the engine: Convolution::setIrDensityReport); --ir-density-window SECONDS: the whole
 // window (20 ms without), --ir-density-hop SECONDS: between window centres (an eighth of the window without), --ir-density-t60
@@ -87,6 +91,7 @@ int main(int argc, char** argv) {
     bool irFloorReport = false;
     std::vector<float> irFloorXovers;
     Convolution::IrTail irTail;
+    Convolution::IrPhase irPhase;
     bool irDensityReport = false;
     Convolution::DensityQuery irDensity;
     bool irIaccReport = false;
@@ -208,6 +213,12 @@ int main(int argc, char** argv) {
                 std::cerr << "--ir-tail '" << argv[i] << "': " << why << std::endl;
                 return 2;
             }
+        } else if (!strcmp(argv[i], "--ir-phase") && i + 1 < argc) {
+            std::string why;
+            if (!Convolution::parsePhase(argv[++i], irPhase, why)) {
+                std::cerr << "--ir-phase '" << argv[i] << "': " << why << std::endl;
+                return 2;
+            }
         } else if (!strcmp(argv[i], "--ir-density-report")) irDensityReport = true;
         else if ((!strcmp(argv[i], "--ir-density-window") || !strcmp(argv[i], "--ir-density-hop") || !strcmp(argv[i], "--ir-density-t60")) && i + 1 < argc) {
             std::string why;
@@ -288,6 +299,7 @@ int main(int argc, char** argv) {
         c->setIrStiReport(irStiReport, irSti);
         c->setIrResponseReport(irResponseReport, irResponse);
         c->setIrTail(irTail);
+        c->setIrPhase(irPhase);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;
             const auto deviceId = settings.str("conv[%d].cc.device", idx);

@@ -148,6 +148,8 @@ int mc_load_ir_resampled(mc_engine *e, uint64_t idx, const float *lr, uint64_t f
  *   1. the whole IR is converted to the session's rate when the rates differ (as by the resampled load); F frames;
  *   1a. (mc_load_ir_tail and mc_load_ir_sweep_tail only) every band of the F frames is cut at its knee or cross-faded there into
  *      decaying noise (mc_ir_tail below); F' frames leave the step and take the place of the F in everything that follows;
+ *   1b. (mc_load_ir_phase and mc_load_ir_sweep_phase only) the F frames are replaced by the minimum-phase IR of the same
+ *      magnitude response (mc_ir_phase below); F frames leave the step, and the onset search of step 2 sees them;
  *   2. s0 = min(start, F); with trim_db < 0 the onset is the first frame m after s0 whose max(|L|, |R|) reaches
  *      peak * 10^(trim_db / 20) (float arithmetic; peak over all frames after s0); first = s0 + max(0, onset - pre_roll);
  *   3. n = min(F - first, length or unlimited, n_ref - nframes) frames are stored (n = 0: MC_ERR_ARG, nothing changes);
@@ -779,6 +781,61 @@ int mc_load_ir_sweep_tail(mc_engine *e, uint64_t idx, const float *lr, uint64_t 
 /* out = {bands touched, F, F', first frame changed (F' when no band was touched)}; MC_ERR_STATE unless the IR's last load had
  * a tail on */
 int mc_ir_tail_info(const mc_engine *e, uint64_t idx, double out[4]);
+
+/* The phase step of an IR load (step 1b of the order of operations above): the frames are replaced by the minimum-phase impulse
+ * response that has the same magnitude response.  An IR that carries acausal build-up or excess group delay adds that delay to
+ * every note; trimming removes leading silence only.  The minimum-phase IR has its energy as early as its magnitude response
+ * allows.  It is meant for short IRs (cabinets, equaliser captures); on a room it destroys the arrival times that make the room.
+ * No reference equivalent; single-engine.  DESIGN.md 2.19 has the method (homomorphic, by the real cepstrum) and the reasons.
+ *
+ * Per channel, everything in double; x = the F frames the step takes (after steps 1 and 1a):
+ *   Nfft = max(16, (smallest power of two >= F) << over_log2);
+ *   X = FFT of x zero-padded to Nfft; p[k] = Re^2 + Im^2; pm = max p.  pm = 0: the channel's output is all zeros;
+ *   p[k] = max(p[k], pm 10^(-floor_db / 10)) (the bins below it are the clamped bins); L[k] = ln(p[k]) / 2;
+ *   c = Re IFFT(L), folded: c[0] and c[Nfft / 2] kept, c[1 .. Nfft / 2 - 1] doubled, the rest zero;
+ *   C = FFT(c); Y[k] = exp(Re C) (cos Im C + i sin Im C); y = Re IFFT(Y);
+ *   the step's output is y[0 .. F), rounded to float once.
+ * The library carries both channels through one complex transform (L + i R), so a channel's bits depend on the other channel
+ * below the last place of a double.  The same frames and struct store the same bits on every run.
+ * floor_db bounds the dynamic range of the log spectrum: a deep notch would otherwise put a spike of ln(0) into it, whose
+ * cepstrum does not fit Nfft / 2 and aliases.  The oversampling (2^over_log2) gives the cepstrum room to decay; 8 is the usual choice.
+ * The output is truncated to F frames; mc_ir_phase_info tells how much energy that dropped.
+ * Synthesised loads (mc_synth_ir and the room entry points) have no phase entry point. */
+enum { MC_PHASE_OFF = 0, MC_PHASE_MINIMUM = 1 };
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_ir_phase) = 16 */
+    uint32_t mode;          /* MC_PHASE_*; MC_PHASE_OFF: every other field ignored */
+    float floor_db;         /* [40, 300]; default 120 */
+    uint32_t over_log2;     /* 1 .. 6; default 3 (8 x) */
+} mc_ir_phase;
+/* off; floor_db 120; over_log2 3 */
+void mc_default_ir_phase(mc_ir_phase *p);
+/* What the step would do to `frames` frames, host arithmetic only: out = {Nfft, passes per transform (1 or 2), bytes of device
+ * memory the step allocates while it runs, 0}.  MC_ERR_ARG for a null pointer, a field of `p` outside its range (mode
+ * MC_PHASE_OFF is accepted and planned as if it were on), frames = 0 or frames and over_log2 beyond the limits below. */
+int mc_ir_phase_plan(const mc_ir_phase *p, uint64_t frames, double out[4]);
+/* mc_load_ir_tail with `phase` applied as step 1b.  With phase NULL or MC_PHASE_OFF the call is mc_load_ir_tail itself, bit for
+ * bit, and leaves no phase information.  With the step on everything is checked before the engine or the device is touched
+ * (MC_ERR_ARG, the message names the field, the engine stays as it was): phase field by field in the struct's order, then
+ * everything mc_load_ir_tail checks, in its order; the step's limits, F <= 2^21 frames at the session's rate and Nfft <= 2^22
+ * (the message names the frames or over_log2), come as soon as F is known: after the tail's F' with a tail on, else after
+ * damp, eq, shape, the rates and the frames.  Without a tail the rates may be 0 / 0 as in mc_load_ir_shaped: the step does not
+ * need the rate.  Such a load counts as shaped: mc_ir_shape_info's out[0] is F. */
+int mc_load_ir_phase(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
+                     uint32_t session_rate, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp, const mc_ir_tail *tail,
+                     const mc_ir_phase *phase);
+/* mc_load_ir_sweep_tail with `phase` applied to the deconvolved frames after the tail step; phase NULL or MC_PHASE_OFF:
+ * mc_load_ir_sweep_tail itself, bit for bit.  With the step on: phase field by field, then everything mc_load_ir_sweep_tail
+ * checks, in its order, with the step's limits after F (after F' with a tail on). */
+int mc_load_ir_sweep_phase(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, const mc_sweep *sweep,
+                           int64_t offset, uint64_t ir_frames, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp,
+                           const mc_ir_tail *tail, const mc_ir_phase *phase);
+/* out = {F, Nfft, E_in, E_out, Ts_in, Ts_out, clamped bins L, clamped bins R}: E = the sum over both channels of the squared
+ * frames that went into and came out of the step (the output as stored, in float), Ts = sum m e[m] / sum e[m] with e[m] = L[m]^2 +
+ * R[m]^2, the centre of energy in frames (0 when E = 0).  E_out / E_in is what the truncation to F frames kept, Ts_in - Ts_out
+ * the delay removed.  The sums are made of one partial per 256 frames, added in ascending order.  MC_ERR_STATE unless the IR's
+ * last load had the step on. */
+int mc_ir_phase_info(const mc_engine *e, uint64_t idx, double out[8]);
 
 /* The reflections of a rectangular room (Allen and Berkley's image-source method), added on the device to the frames
  * mc_ir_synth describes: the room itself - its size, where the source and the two receivers stand, how hard the walls are -
