@@ -29,6 +29,7 @@ SYMBOLS = [
     "mc_default_response_query", "mc_ir_response", "mc_response_grid", "mc_response_smooth",
     "mc_default_ir_tail", "mc_load_ir_tail", "mc_load_ir_sweep_tail", "mc_ir_tail_info",
     "mc_default_ir_phase", "mc_ir_phase_plan", "mc_load_ir_phase", "mc_load_ir_sweep_phase", "mc_ir_phase_info",
+    "mc_default_ir_filter", "mc_ir_filter_plan", "mc_load_ir_filter", "mc_load_ir_sweep_filter", "mc_ir_filter_info",
     "mc_default_ir_room", "mc_synth_ir_room", "mc_ir_room_info", "mc_ir_room_plan",
     "mc_default_ir_room_mics", "mc_synth_ir_room_mics", "mc_ir_room_mics_plan", "mc_ir_room_mics_info",
     "mc_default_ir_room_bands", "mc_synth_ir_room_bands", "mc_ir_room_bands_plan", "mc_ir_room_bands_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
@@ -341,6 +342,24 @@ class McIrPhase(C.Structure):
     ]
 
 
+MC_FILTER_OFF, MC_FILTER_CONVOLVE, MC_FILTER_DECONVOLVE = 0, 1, 2
+MC_FILTER_STEREO, MC_FILTER_LEFT, MC_FILTER_MID = 0, 1, 2
+
+
+class McIrFilter(C.Structure):
+    """mc_ir_filter: the filter step of mc_load_ir_filter and mc_load_ir_sweep_filter."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("op", C.c_uint32),
+        ("channels", C.c_uint32),
+        ("rate", C.c_uint32),
+        ("reg_db", C.c_float),
+        ("reserved", C.c_uint32),
+        ("frames_out", C.c_uint64),
+    ]
+
+
 MC_ROOM_MAX_ORDER = 32
 
 
@@ -502,6 +521,12 @@ def load():
     L.mc_load_ir_phase.argtypes = L.mc_load_ir_tail.argtypes + [C.POINTER(McIrPhase)]
     L.mc_load_ir_sweep_phase.argtypes = L.mc_load_ir_sweep_tail.argtypes + [C.POINTER(McIrPhase)]
     L.mc_ir_phase_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_default_ir_filter.argtypes = [C.POINTER(McIrFilter)]
+    L.mc_default_ir_filter.restype = None
+    L.mc_ir_filter_plan.argtypes = [C.POINTER(McIrFilter), u64, u64, C.POINTER(C.c_double)]
+    L.mc_load_ir_filter.argtypes = L.mc_load_ir_phase.argtypes + [C.POINTER(McIrFilter), fp, u64]
+    L.mc_load_ir_sweep_filter.argtypes = L.mc_load_ir_sweep_phase.argtypes + [C.POINTER(McIrFilter), fp, u64]
+    L.mc_ir_filter_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_default_ir_room.argtypes = [C.POINTER(McIrRoom)]
     L.mc_default_ir_room.restype = None
     L.mc_synth_ir_room.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrRoom), C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp),

@@ -40,6 +40,7 @@
 #include "irresponse.hip.h"
 #include "irtail.hip.h"
 #include "irphase.hip.h"
+#include "irfilter.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
 // mc_config or that the tests compare bit for bit:
@@ -90,10 +91,10 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline double pan_l(double p) { return p >= 0 ? 1 - p : 1; }  // conv.cu:386
 inline double pan_r(double p) { return p <= 0 ? 1 + p : 1; }  // conv.cu:387
 
-// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _phase_info, _room_info, _room_mics_info and _room_bands_info report of an IR's last
+// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _phase_info, _filter_info, _room_info, _room_mics_info and _room_bands_info report of an IR's last
 // load: one entry per kind, on when that load had the step or the source (a shape with something on, an eq band or damping count as a shape, and
 // so do a synthesised, a swept and a tailed load), with the numbers the getter hands out (include/mcconv.h says what they are)
-enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_PHASE, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_KINDS };
+enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_PHASE, FACT_FILTER, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_KINDS };
 struct IrFact {
     bool on = false;
     double v[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -3353,6 +3354,7 @@ struct IrLoad {
     // -- the steps, in the order they run.  Any of tail, eq, damp, syn and swp needs the shape, which may have everything off
     const TailStep* tail = nullptr;      // step 1a, between the source and the shaping (irtail.hip.h; tail->plan.F = the frames at the session's rate)
     const PhaseStep* phase = nullptr;    // step 1b, after the tail step (irphase.hip.h; phase->F = the frames the tail step hands on)
+    const FilterStep* filter = nullptr;  // step 1c, after the phase step (irfilter.hip.h; filter->F = the frames the phase step hands on)
     const mc_ir_shape* shape = nullptr;  // applied on the device after the conversion (irshape.hip.h)
     const IeqCascade* eq = nullptr;      // the bands of mc_load_ir_eq (ireq.hip.h); with damp it may hold no band
     const DampPlan* damp = nullptr;      // the damping of mc_load_ir_damped (irdamp.hip.h; needs eq)
@@ -3363,7 +3365,8 @@ struct ShapedTaps {
     float2* d_taps = nullptr;
     uint64_t n = 0;
     double sums[4] = {0, 0, 0, 0}, info[8];
-    double phase[8];  // mc_ir_phase_info's numbers, with IrLoad::phase
+    double phase[8];    // mc_ir_phase_info's numbers, with IrLoad::phase
+    double filter[10];  // mc_ir_filter_info's numbers, with IrLoad::filter
 };
 
 // The stream idle and out of the JACK path, before the kernels of a load or of a measurement go onto it.  (The single-transform
@@ -3380,7 +3383,7 @@ int quiesce(mc_engine* e) {
 // The shaped load's own stage (irshape.hip.h): all `conv` frames of ld's source at the session's rate on the device, shaped
 // into a new buffer of out->n <= cap taps.  Nothing of the engine's IRs is touched here.  A sweep's recording is uploaded to a
 // temporary buffer freed after the stage, as its weight table is; the tail step turns the conv frames into tail->plan.Fp frames
-// in a buffer of their own, and the phase step those into as many frames in another.
+// in a buffer of their own, the phase step those into as many frames in another, and the filter step those into filter->Fo.
 int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, ShapedTaps* out) {
     float2 *d_x = nullptr, *d_rec = nullptr;
     double* d_u = nullptr;
@@ -3417,6 +3420,19 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
             (void)hipFree(d_y);
         }
     }
+    if (er == hipSuccess && ld.filter) {
+        float2* d_y = nullptr;
+        er = hipMalloc(&d_y, sizeof(float2) * ld.filter->Fo);
+        if (er == hipSuccess) er = filter_run(e->stream, d_x, d_y, *ld.filter, out->filter);  // (waits for the stream: d_x is free after it)
+        if (er == hipSuccess) {
+            (void)hipFree(d_x);
+            d_x = d_y;
+            conv = ld.filter->Fo;
+        } else {
+            (void)hipStreamSynchronize(e->stream);
+            (void)hipFree(d_y);
+        }
+    }
     if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, *ld.shape, &out->d_taps, &out->n, out->sums, out->info, ld.eq, ld.damp);
     if (ld.swp && er != hipSuccess) (void)hipStreamSynchronize(e->stream);  // (the correlation may still be reading them)
     (void)hipFree(d_x);
@@ -3429,9 +3445,9 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
 }
 
 // What the mc_ir_*_info getters report of the load `ld` that stored `taps` taps; sinfo = the shaping stage's numbers, pinfo
-// the phase step's (read with ld.phase).
+// the phase step's (read with ld.phase), finfo the filter step's (read with ld.filter).
 // Every kind is written, so nothing of an earlier load onto the same index stays behind.
-void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[8], const double pinfo[8]) {
+void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[8], const double pinfo[8], const double finfo[10]) {
     for (IrFact& f : ir.facts) f.on = false;
     const auto put = [&ir](IrFactKind kind, std::initializer_list<double> v) {
         ir.facts[kind].on = true;
@@ -3450,6 +3466,7 @@ void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[
         put(FACT_TAIL, {(double)t.touched, (double)t.F, (double)t.Fp, (double)t.first});
     }
     if (ld.phase) put(FACT_PHASE, {pinfo[0], pinfo[1], pinfo[2], pinfo[3], pinfo[4], pinfo[5], pinfo[6], pinfo[7]});
+    if (ld.filter) put(FACT_FILTER, {finfo[0], finfo[1], finfo[2], finfo[3], finfo[4], finfo[5], finfo[6], finfo[7], finfo[8], finfo[9]});
     if (ld.room) {
         const RoomPlan& r = ld.room->plan;
         put(FACT_ROOM, {(double)r.N, (double)ld.room->kept[0], (double)ld.room->kept[1], r.tau[0], r.tau[1], (double)r.E, (double)r.complete, 0.0});
@@ -3491,7 +3508,7 @@ int load_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const IrLoad& ld) {
         const int rc = sf_load_ir(e, idx, lr, frames, nframes, rs, st.d_taps, st.n, st.sums);
         if (sh) (void)hipFree(d_lr);
         if (rc) return rc;
-        note_load(e->irs[idx], ld, st.n, st.info, st.phase);
+        note_load(e->irs[idx], ld, st.n, st.info, st.phase, st.filter);
         return MC_OK;
     }
     const uint64_t n = sh ? st.n : std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
@@ -3568,7 +3585,7 @@ int load_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const IrLoad& ld) {
     std::memcpy(ir.sums, s, sizeof(s));
     ir.taps = n;
     ir.P = P;
-    note_load(ir, ld, n, st.info, st.phase);
+    note_load(ir, ld, n, st.info, st.phase, st.filter);
     if ((int)idx + 1 > e->nirs) e->nirs = (int)idx + 1;
     e->spec_valid = e->dspec.valid = false;
     e->uniform_valid[0] = e->uniform_valid[1] = false;
@@ -3616,7 +3633,7 @@ const char* resolve_steps(const mc_ir_shape* shape, const mc_ir_eq* eq, const mc
     return nullptr;
 }
 
-// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, phase, room, room mics, room bands): out = the first `count` numbers of what
+// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, phase, filter, room, room mics, room bands): out = the first `count` numbers of what
 // note_load kept of that kind, or MC_ERR_STATE with "IR <idx> <was_not>" when the last load had none
 int ir_fact(const mc_engine* e, uint64_t idx, IrFactKind kind, int count, const char* was_not, double* out) {
     if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
@@ -4218,11 +4235,16 @@ int mc_ir_phase_plan(const mc_ir_phase* p, uint64_t frames, double out[4]) {
     return MC_OK;
 }
 
-int mc_load_ir_phase(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
-                     const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail, const mc_ir_phase* phase) {
-    if (!phase || phase->mode == MC_PHASE_OFF) return mc_load_ir_tail(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail);
-    // the phase first, then what mc_load_ir_tail checks in its order, the step's limits once F is known, all before the engine and before any HIP call
-    if (const char* bad = phase_check(phase)) return fail(MC_ERR_ARG, "%s", bad);
+// mc_load_ir_phase and mc_load_ir_filter behind their switches: phase is on or null, filter is on or null, and one of them is on.
+static int load_phase_filter(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
+                             const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail, const mc_ir_phase* phase,
+                             const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames) {
+    // the filter first, then the phase, then what mc_load_ir_tail checks in its order, the steps' limits once F is known, all before the engine
+    // and before any HIP call
+    if (filter)
+        if (const char* bad = filter_check(filter)) return fail(MC_ERR_ARG, "%s", bad);
+    if (phase)
+        if (const char* bad = phase_check(phase)) return fail(MC_ERR_ARG, "%s", bad);
     const bool tailed = tail && tail->mode != MC_TAIL_OFF;
     const bool convert = tailed || ir_rate || session_rate;  // (0, 0 without a tail: the frames are at the session's rate)
     const auto rates = [&](const char* why) -> int {
@@ -4235,7 +4257,13 @@ int mc_load_ir_phase(mc_engine* e, uint64_t idx, const float* lr, uint64_t frame
     };
     IrSteps steps;
     TailStep tstep{};
-    uint64_t F = 0;
+    uint64_t F = 0, G = 0;
+    // the limits of the steps that are on, over the F frames that reach them
+    const auto limits = [&]() -> const char* {
+        if (phase)
+            if (const char* bad = phase_check_frames(phase, F)) return bad;
+        return filter ? filter_check_load(filter, session_rate, F, filter_frames, &G) : nullptr;
+    };
     if (tailed) {
         if (const char* bad = tail_check(tail, session_rate)) return fail(MC_ERR_ARG, "%s", bad);
         if (const int rc = rates("the tail step needs the session's rate")) return rc;
@@ -4244,7 +4272,7 @@ int mc_load_ir_phase(mc_engine* e, uint64_t idx, const float* lr, uint64_t frame
         if (const char* bad = tail_check_frames(tail, F)) return fail(MC_ERR_ARG, "%s", bad);
         tstep = tail_step(*tail, session_rate, F);
         F = tstep.plan.Fp;
-        if (const char* bad = phase_check_frames(phase, F)) return fail(MC_ERR_ARG, "%s", bad);
+        if (const char* bad = limits()) return fail(MC_ERR_ARG, "%s", bad);
         if (const char* bad = resolve_steps(shape, eq, damp, ir_rate, session_rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
     } else {
         if (const char* bad = resolve_steps(shape, eq, damp, ir_rate, session_rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
@@ -4252,25 +4280,45 @@ int mc_load_ir_phase(mc_engine* e, uint64_t idx, const float* lr, uint64_t frame
             if (const int rc = rates("both rates 0 = no conversion")) return rc;
         if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
         F = ir_rate != session_rate ? rs_out_frames(rs_geom(ir_rate, session_rate), frames) : frames;
-        if (const char* bad = phase_check_frames(phase, F)) return fail(MC_ERR_ARG, "%s", bad);
+        if (const char* bad = limits()) return fail(MC_ERR_ARG, "%s", bad);
     }
+    if (filter && !filter_lr) return fail(MC_ERR_ARG, "null filter_lr");
     const uint32_t rs[2] = {ir_rate, session_rate};
-    const PhaseStep pstep = phase_step(*phase, F);
+    const PhaseStep pstep = phase ? phase_step(*phase, F) : PhaseStep{};
+    FilterStep fstep = filter ? filter_step(*filter, F, G) : FilterStep{};
+    if (filter) fstep.lr = filter_lr, fstep.frames = filter_frames, fstep.rs[0] = filter->rate ? filter->rate : session_rate, fstep.rs[1] = session_rate;
     IrLoad ld;
     ld.lr = lr, ld.frames = frames, ld.rs = ir_rate != session_rate ? rs : nullptr;
     ld.tail = tailed ? &tstep : nullptr;
-    ld.phase = &pstep;
+    ld.phase = phase ? &pstep : nullptr;
+    ld.filter = filter ? &fstep : nullptr;
     steps.into(ld);
     return load_ir(e, idx, nframes, ld);
 }
 
-int mc_load_ir_sweep_phase(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
-                           uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail,
-                           const mc_ir_phase* phase) {
-    if (!phase || phase->mode == MC_PHASE_OFF)
-        return mc_load_ir_sweep_tail(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail);
-    // the phase first, then what mc_load_ir_sweep_tail checks in its order, the step's limits once F is known
-    if (const char* bad = phase_check(phase)) return fail(MC_ERR_ARG, "%s", bad);
+int mc_load_ir_phase(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
+                     const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail, const mc_ir_phase* phase) {
+    if (!phase || phase->mode == MC_PHASE_OFF) return mc_load_ir_tail(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail);
+    return load_phase_filter(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail, phase, nullptr, nullptr, 0);
+}
+
+int mc_load_ir_filter(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
+                      const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail, const mc_ir_phase* phase,
+                      const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames) {
+    if (!filter || filter->op == MC_FILTER_OFF) return mc_load_ir_phase(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail, phase);
+    return load_phase_filter(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail, phase && phase->mode != MC_PHASE_OFF ? phase : nullptr,
+                             filter, filter_lr, filter_frames);
+}
+
+// mc_load_ir_sweep_phase and mc_load_ir_sweep_filter behind their switches, as load_phase_filter
+static int load_sweep_phase_filter(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
+                                   uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail,
+                                   const mc_ir_phase* phase, const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames) {
+    // the filter first, then the phase, then what mc_load_ir_sweep_tail checks in its order, the steps' limits once F is known
+    if (filter)
+        if (const char* bad = filter_check(filter)) return fail(MC_ERR_ARG, "%s", bad);
+    if (phase)
+        if (const char* bad = phase_check(phase)) return fail(MC_ERR_ARG, "%s", bad);
     const bool tailed = tail && tail->mode != MC_TAIL_OFF;
     if (tailed)
         if (const char* bad = tail_check(tail, sweep ? sweep->rate : 0)) return fail(MC_ERR_ARG, "%s", bad);
@@ -4280,19 +4328,66 @@ int mc_load_ir_sweep_phase(mc_engine* e, uint64_t idx, const float* lr, uint64_t
         if (const char* bad = tail_check_frames(tail, ir_frames)) return fail(MC_ERR_ARG, "%s", bad);
     const TailStep tstep = tailed ? tail_step(*tail, sweep->rate, ir_frames) : TailStep{};
     const uint64_t F = tailed ? tstep.plan.Fp : ir_frames;
-    if (const char* bad = phase_check_frames(phase, F)) return fail(MC_ERR_ARG, "%s", bad);
+    uint64_t G = 0;
+    if (phase)
+        if (const char* bad = phase_check_frames(phase, F)) return fail(MC_ERR_ARG, "%s", bad);
+    if (filter)
+        if (const char* bad = filter_check_load(filter, sweep->rate, F, filter_frames, &G)) return fail(MC_ERR_ARG, "%s", bad);
     IrSteps steps;
     if (const char* bad = resolve_steps(shape, eq, damp, sweep->rate, sweep->rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
     if (!lr) return fail(MC_ERR_ARG, "null lr");
+    if (filter && !filter_lr) return fail(MC_ERR_ARG, "null filter_lr");
     const SweepSource src{swp_plan(*sweep), lr, frames, ir_frames, offset};
-    const PhaseStep pstep = phase_step(*phase, F);
+    const PhaseStep pstep = phase ? phase_step(*phase, F) : PhaseStep{};
+    FilterStep fstep = filter ? filter_step(*filter, F, G) : FilterStep{};
+    if (filter) fstep.lr = filter_lr, fstep.frames = filter_frames, fstep.rs[0] = filter->rate ? filter->rate : sweep->rate, fstep.rs[1] = sweep->rate;
     IrLoad ld;
     ld.swp = &src, ld.frames = ir_frames;
     ld.tail = tailed ? &tstep : nullptr;
-    ld.phase = &pstep;
+    ld.phase = phase ? &pstep : nullptr;
+    ld.filter = filter ? &fstep : nullptr;
     steps.into(ld);
     return load_ir(e, idx, nframes, ld);
 }
+
+int mc_load_ir_sweep_phase(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
+                           uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail,
+                           const mc_ir_phase* phase) {
+    if (!phase || phase->mode == MC_PHASE_OFF)
+        return mc_load_ir_sweep_tail(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail);
+    return load_sweep_phase_filter(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail, phase, nullptr, nullptr, 0);
+}
+
+int mc_load_ir_sweep_filter(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
+                            uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail,
+                            const mc_ir_phase* phase, const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames) {
+    if (!filter || filter->op == MC_FILTER_OFF)
+        return mc_load_ir_sweep_phase(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail, phase);
+    return load_sweep_phase_filter(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail,
+                                   phase && phase->mode != MC_PHASE_OFF ? phase : nullptr, filter, filter_lr, filter_frames);
+}
+
+void mc_default_ir_filter(mc_ir_filter* f) {
+    if (!f) return;
+    std::memset(f, 0, sizeof(*f));
+    f->struct_size = (uint32_t)sizeof(*f);
+    f->op = MC_FILTER_OFF;
+    f->channels = MC_FILTER_STEREO;
+    f->reg_db = 60.f;
+}
+
+int mc_ir_filter_plan(const mc_ir_filter* f, uint64_t frames, uint64_t filter_frames, double out[4]) {
+    if (!f) return fail(MC_ERR_ARG, "null filter");
+    if (const char* bad = filter_check(f)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!frames) return fail(MC_ERR_ARG, "empty IR");
+    if (const char* bad = filter_check_frames(f, frames, filter_frames)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!out) return fail(MC_ERR_ARG, "null out");
+    const FilterStep s = filter_step(*f, frames, filter_frames);
+    out[0] = (double)s.Nfft, out[1] = (double)s.fft.passes, out[2] = (double)filter_device_bytes(s), out[3] = (double)s.Fo;
+    return MC_OK;
+}
+
+int mc_ir_filter_info(const mc_engine* e, uint64_t idx, double out[10]) { return ir_fact(e, idx, FACT_FILTER, 10, "was not loaded with a filter step", out); }
 
 int mc_ir_phase_info(const mc_engine* e, uint64_t idx, double out[8]) { return ir_fact(e, idx, FACT_PHASE, 8, "was not loaded with a phase step", out); }
 

@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrRoom, McIrRoomBands, McIrRoomMics, McIrPhase, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrRoom, McIrRoomBands, McIrRoomMics, McIrFilter, McIrPhase, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -308,6 +308,60 @@ def phase_plan(phase, frames):
     out = (C.c_double * 4)()
     check(_lib.load().mc_ir_phase_plan(C.byref(phase.to_c()), int(frames), out))
     return dict(nfft=int(out[0]), passes=int(out[1]), device_bytes=int(out[2]))
+
+
+@dataclasses.dataclass
+class IrFilter:
+    """A second impulse response that prepare(filter=...) and prepare_sweep(filter=...) combine with the IR after the phase step
+    and before everything else (mc_ir_filter, include/mcconv.h).  ir: float32 [frames, 2], or an object with such a `.buffer`
+    (and a `.sampleRate`, which rate then defaults to).  op "convolve" cascades the two, so that the engine runs one IR; op
+    "deconvolve" divides the filter out of the IR (a loop-back capture out of a measurement), regularised reg_db (20 .. 200)
+    below the filter's strongest bin; "off" does nothing.  channels: "stereo" (left with left, right with right), "left" or
+    "mid" ((L + R) / 2): one filter signal for both channels.  rate (Hz; None or 0 = the session's): the filter is converted
+    to the session's rate on the device first.  frames_out: the frames the step hands on; 0 = all of a convolution, as many
+    as went in of a deconvolution."""
+
+    ir: object = None
+    op: str = "convolve"
+    channels: str = "stereo"
+    rate: object = None
+    reg_db: float = 60.0
+    frames_out: int = 0
+
+    OPS = {"off": _lib.MC_FILTER_OFF, "convolve": _lib.MC_FILTER_CONVOLVE, "deconvolve": _lib.MC_FILTER_DECONVOLVE}
+    CHANNELS = {"stereo": _lib.MC_FILTER_STEREO, "left": _lib.MC_FILTER_LEFT, "mid": _lib.MC_FILTER_MID}
+
+    def to_c(self):
+        if self.op not in self.OPS:
+            raise ValueError(f"op must be one of {sorted(self.OPS)}, not {self.op!r}")
+        if self.channels not in self.CHANNELS:
+            raise ValueError(f"channels must be one of {sorted(self.CHANNELS)}, not {self.channels!r}")
+        rate = self.rate if self.rate is not None else getattr(self.ir, "sampleRate", None)
+        f = McIrFilter()
+        _lib.load().mc_default_ir_filter(C.byref(f))
+        f.op, f.channels, f.rate, f.reg_db, f.frames_out = self.OPS[self.op], self.CHANNELS[self.channels], int(rate or 0), float(self.reg_db), int(self.frames_out)
+        return f
+
+    def frames(self):
+        """The filter's frames as the library takes them: contiguous float32 [G, 2]."""
+        if self.ir is None:
+            raise ValueError("an IrFilter needs its ir")
+        return _f32(getattr(self.ir, "buffer", self.ir)).reshape(-1, 2)
+
+
+def filter_plan(filter, frames, session_rate=None):
+    """What the filter step `filter` (an IrFilter with its ir) would do to `frames` frames at the session's rate
+    (mc_ir_filter_plan, host arithmetic only): the transform's length, its passes, the device memory the step needs while it
+    runs and the frames it hands on.  session_rate: needed when the filter has a rate of its own, for its length after the
+    conversion.  McError for lengths beyond the step's limits (a transform of 2^22 points)."""
+    f = filter.to_c()
+    G = filter.frames().shape[0]
+    if f.rate and session_rate and int(session_rate) != f.rate:
+        g = math.gcd(int(session_rate), f.rate)
+        G = -(-G * (int(session_rate) // g) // (f.rate // g))
+    out = (C.c_double * 4)()
+    check(_lib.load().mc_ir_filter_plan(C.byref(f), int(frames), G, out))
+    return dict(nfft=int(out[0]), passes=int(out[1]), device_bytes=int(out[2]), frames_out=int(out[3]))
 
 
 def tail_from_floor(floor, first=0, mode="extend", fade=0, length=0, seed=0, width=1.0):
@@ -783,7 +837,7 @@ class Convolution:
         check(self._L.mc_set_period(self._h, nframes))
 
     # -- reference surface ----------------------------------------------------
-    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None, damp=None, tail=None, phase=None):
+    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None, damp=None, tail=None, phase=None, filter=None):
         """Convolution::prepare (conv.cu:207-253).  `wav` is float32 [frames, 2]
         (what WavFile.buffer holds) or an object with a `.buffer` of that shape.
         ir_rate (Hz; default: `wav.sampleRate` when it has one): when both it and the engine's sample_rate are known and
@@ -797,23 +851,32 @@ class Convolution:
         tail (an IrTail whose mode is not "off"): cut or extend the tail of the frames band by band, after the conversion and
         before everything else (mc_load_ir_tail); the rates as for eq; ir_tail_info(idx) then tells what was done.
         phase (an IrPhase whose mode is not "off"): convert the frames to minimum phase, after the tail step and before
-        the shape (mc_load_ir_phase); it needs no rate; ir_phase_info(idx) then tells what was done."""
+        the shape (mc_load_ir_phase); it needs no rate; ir_phase_info(idx) then tells what was done.
+        filter (an IrFilter whose op is not "off"): convolve the frames with a second IR, or divide it out of them, after the
+        phase step and before the shape (mc_load_ir_filter); a filter with a rate of its own needs the engine's sample_rate;
+        ir_filter_info(idx) then tells what was done."""
         lr = _f32(getattr(wav, "buffer", wav)).reshape(-1, 2)
         if ir_rate is None:
             ir_rate = getattr(wav, "sampleRate", None)
-        if phase is not None and phase.mode != "off":
+        filtered = filter is not None and filter.op != "off"
+        if filtered or (phase is not None and phase.mode != "off"):
             tailed = tail is not None and tail.mode != "off"
-            if tailed or eq is not None or (damp is not None and damp.xovers):
+            if tailed or eq is not None or (damp is not None and damp.xovers) or (filtered and filter.to_c().rate and self.sample_rate):
                 session = int(self.sample_rate or 0)
                 rates = (session if ir_rate is None else int(ir_rate), session)
             elif ir_rate is not None and self.sample_rate is not None and int(ir_rate) != int(self.sample_rate):
                 rates = (int(ir_rate), int(self.sample_rate))
             else:
                 rates = (0, 0)
-            check(self._L.mc_load_ir_phase(self._h, idx, _fp(lr), lr.shape[0], nframes, *rates,
-                                           C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
-                                           C.byref(damp.to_c()) if damp is not None else None, C.byref(tail.to_c()) if tailed else None,
-                                           C.byref(phase.to_c())))
+            args = (self._h, idx, _fp(lr), lr.shape[0], nframes, *rates,
+                    C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
+                    C.byref(damp.to_c()) if damp is not None else None, C.byref(tail.to_c()) if tailed else None,
+                    C.byref(phase.to_c()) if phase is not None else None)
+            if filtered:
+                flr = filter.frames()
+                check(self._L.mc_load_ir_filter(*args, C.byref(filter.to_c()), _fp(flr), flr.shape[0]))
+            else:
+                check(self._L.mc_load_ir_phase(*args))
             return
         if tail is not None and tail.mode != "off":
             session = int(self.sample_rate or 0)
@@ -878,7 +941,7 @@ class Convolution:
         check(self._L.mc_synth_ir(self._h, idx, nframes, C.byref(s), C.byref(shape.to_c()) if shape is not None else None,
                                   C.byref(eq.to_c()) if eq is not None else None, C.byref(damp.to_c()) if damp is not None else None))
 
-    def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None, tail=None, phase=None):
+    def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None, tail=None, phase=None, filter=None):
         """Deconvolve `recording` (float32 [frames, 2] or an object with such a `.buffer`: what was recorded while `sweep`, a
         Sweep, played) into an IR on the device and store it at idx (mc_load_ir_sweep): the frames take the place of a WAV's at
         the session's rate, and shape, eq and damp apply to them as in prepare().  IR frame m is the correlation at lag
@@ -887,7 +950,8 @@ class Convolution:
         recording holds past the sweep, clamped to the library's caps.  The engine's sample_rate is passed unless sweep.rate
         is set (the library's default, 44100, when the engine has none either).  tail (an IrTail whose mode is not "off"): the
         tail step on the deconvolved frames (mc_load_ir_sweep_tail).  phase (an IrPhase whose mode is not "off"): the phase step
-        after it (mc_load_ir_sweep_phase)."""
+        after it (mc_load_ir_sweep_phase).  filter (an IrFilter whose op is not "off"): the filter step after that
+        (mc_load_ir_sweep_filter), the session's rate being the sweep's."""
         lr = _f32(getattr(recording, "buffer", recording)).reshape(-1, 2)
         s = sweep.to_c()
         if not sweep.rate and self.sample_rate:
@@ -898,7 +962,11 @@ class Convolution:
         args = (self._h, idx, _fp(lr), lr.shape[0], nframes, C.byref(s), int(offset), int(ir_frames),
                 C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
                 C.byref(damp.to_c()) if damp is not None else None)
-        if phase is not None and phase.mode != "off":
+        if filter is not None and filter.op != "off":
+            flr = filter.frames()
+            check(self._L.mc_load_ir_sweep_filter(*args, C.byref(tail.to_c()) if tail is not None else None, C.byref(phase.to_c()) if phase is not None else None,
+                                                  C.byref(filter.to_c()), _fp(flr), flr.shape[0]))
+        elif phase is not None and phase.mode != "off":
             check(self._L.mc_load_ir_sweep_phase(*args, C.byref(tail.to_c()) if tail is not None else None, C.byref(phase.to_c())))
         elif tail is not None and tail.mode != "off":
             check(self._L.mc_load_ir_sweep_tail(*args, C.byref(tail.to_c())))
@@ -1262,6 +1330,16 @@ class Convolution:
         check(self._L.mc_ir_phase_info(self._h, idx, out))
         return dict(frames=int(out[0]), nfft=int(out[1]), energy_in=float(out[2]), energy_out=float(out[3]), centre_in=float(out[4]),
                     centre_out=float(out[5]), clamped=(int(out[6]), int(out[7])))
+
+    def ir_filter_info(self, idx):
+        """What the filter step of IR idx's load did (mc_ir_filter_info): the frames it took, the filter's frames at the
+        session's rate, the frames it handed on, the transform's length, the energy of the frames, of the filter and of what
+        was stored, the energy left behind past frames_out, and the bins of either channel that a deconvolution
+        regularised.  McError (MC_ERR_STATE) for an IR whose last load had no filter step."""
+        out = (C.c_double * 10)()
+        check(self._L.mc_ir_filter_info(self._h, idx, out))
+        return dict(frames=int(out[0]), filter_frames=int(out[1]), frames_out=int(out[2]), nfft=int(out[3]), energy_in=float(out[4]),
+                    energy_filter=float(out[5]), energy_out=float(out[6]), energy_rest=float(out[7]), regularised=(int(out[8]), int(out[9])))
 
     def enable_kernel_timing(self, on=True):
         check(self._L.mc_enable_kernel_timing(self._h, 1 if on else 0))

@@ -80,6 +80,12 @@ int mc_load_ir_phase(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uin
 int mc_load_ir_sweep_phase(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
                            const mc_ir_damp*, const mc_ir_tail*, const mc_ir_phase*) __attribute__((weak));
 int mc_ir_phase_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+void mc_default_ir_filter(mc_ir_filter*) __attribute__((weak));
+int mc_load_ir_filter(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
+                      const mc_ir_tail*, const mc_ir_phase*, const mc_ir_filter*, const float*, uint64_t) __attribute__((weak));
+int mc_load_ir_sweep_filter(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
+                            const mc_ir_damp*, const mc_ir_tail*, const mc_ir_phase*, const mc_ir_filter*, const float*, uint64_t) __attribute__((weak));
+int mc_ir_filter_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 // ... and no room
 void mc_default_ir_room(mc_ir_room*) __attribute__((weak));
 int mc_synth_ir_room(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_room*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
@@ -229,6 +235,12 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         Log::error("conv", "the engine has no phase step (mc_load_ir_phase)");
         std::exit(2);
     }
+    const bool filtered = _irFilter.on && !synth;
+    if (_irFilter.on && synth) Log::info(name, "IR %zu is generated: it has no filter step and is loaded as it is", idx);
+    if (filtered && (!mc_default_ir_filter || !mc_load_ir_filter || !mc_load_ir_sweep_filter || !mc_ir_filter_info)) {
+        Log::error("conv", "the engine has no filter step (mc_load_ir_filter)");
+        std::exit(2);
+    }
     if (tail && (!mc_load_ir_tail || !mc_load_ir_sweep_tail || !mc_ir_tail_info)) {
         Log::error("conv", "the engine has no tail step (mc_load_ir_tail)");
         std::exit(2);
@@ -273,6 +285,19 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         ph.mode = MC_PHASE_MINIMUM;
         ph.floor_db = _irPhase.floorDb;
         ph.over_log2 = _irPhase.overLog2;
+    }
+    mc_ir_filter fl;
+    const uint64_t flFrames = _irFilter.lr.size() / 2;
+    if (filtered) {
+        // a filter at another rate needs the session's in the call: frames that are loaded at the rate they have are at the client's
+        const unsigned session = sweep ? sweep->sweep.rate : sessionRate ? sessionRate : (unsigned)samplerate;
+        mc_default_ir_filter(&fl);
+        fl.op = _irFilter.deconvolve ? MC_FILTER_DECONVOLVE : MC_FILTER_CONVOLVE;
+        fl.channels = _irFilter.channels;
+        fl.rate = _irFilter.rate && _irFilter.rate != session ? _irFilter.rate : 0;
+        fl.reg_db = _irFilter.regDb;
+        fl.frames_out = dampFrames(_irFilter.keepSeconds, (double)session);
+        if (fl.rate && !sessionRate) irRate = sessionRate = session;
     }
     if (!eq.off()) {
         mc_default_ir_eq(&q);
@@ -325,7 +350,10 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         Log::info(name, "IR %zu synthesised: %llu frames, seed %llu, %d of %u reflections kept", idx, (unsigned long long)si[0],
                   (unsigned long long)synth->seed, (int)si[1], synth->n_early);
     } else if (sweep) {  // (as for a generated IR: what the engine refuses is the index line's fault)
-        const int rc = minimum ? mc_load_ir_sweep_phase(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
+        const int rc = filtered ? mc_load_ir_sweep_filter(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
+                                                          eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, minimum ? &ph : nullptr, &fl,
+                                                          _irFilter.lr.data(), flFrames)
+                       : minimum ? mc_load_ir_sweep_phase(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
                                                         eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, &ph)
                        : tail  ? mc_load_ir_sweep_tail(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
                                                     eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
@@ -339,6 +367,12 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         check(mc_ir_sweep_info(_engine, idx, wi), "mc_ir_sweep_info");
         Log::info(name, "IR %zu captured: sweep %llu frames, recording %llu frames, %llu frames at offset %lld", idx, (unsigned long long)wi[0],
                   (unsigned long long)wi[1], (unsigned long long)wi[2], (long long)wi[3]);
+    } else if (filtered) {  // (lengths beyond the step are the command line's fault: a message and exit 2, no abort)
+        if (mc_load_ir_filter(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail,
+                              minimum ? &ph : nullptr, &fl, _irFilter.lr.data(), flFrames) != MC_OK) {
+            Log::error("conv", "IR %zu cannot be filtered with %s: %s", idx, _irFilter.path.c_str(), mc_last_error());
+            std::exit(2);
+        }
     } else if (minimum) {  // (an IR too long for the step is the command line's fault: a message and exit 2, no abort)
         if (mc_load_ir_phase(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, &ph) != MC_OK) {
             Log::error("conv", "IR %zu cannot be converted to minimum phase: %s", idx, mc_last_error());
@@ -370,6 +404,14 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         Log::info(name, "IR %zu minimum phase: %llu frames through a transform of %llu points, delay removed %.1f frames (%.3f ms), %.4f dB kept, %llu and %llu bins at the floor",
                   idx, (unsigned long long)pi[0], (unsigned long long)pi[1], removed, samplerate ? 1000.0 * removed / (double)samplerate : 0.0,
                   pi[2] > 0.0 && pi[3] > 0.0 ? 10.0 * std::log10(pi[3] / pi[2]) : 0.0, (unsigned long long)pi[6], (unsigned long long)pi[7]);
+    }
+    if (filtered) {
+        double fi[10];
+        check(mc_ir_filter_info(_engine, idx, fi), "mc_ir_filter_info");
+        Log::info(name, "IR %zu %s %s: %llu frames and %llu filter frames through a transform of %llu points, %llu frames kept, level %+.2f dB, %.2f dB left behind, %llu and %llu bins regularised",
+                  idx, _irFilter.deconvolve ? "deconvolved by" : "convolved with", _irFilter.path.c_str(), (unsigned long long)fi[0], (unsigned long long)fi[1],
+                  (unsigned long long)fi[3], (unsigned long long)fi[2], fi[4] > 0.0 && fi[6] > 0.0 ? 10.0 * std::log10(fi[6] / fi[4]) : 0.0,
+                  fi[6] > 0.0 && fi[7] > 0.0 ? std::max(-999.0, 10.0 * std::log10(fi[7] / fi[6])) : -999.0, (unsigned long long)fi[8], (unsigned long long)fi[9]);
     }
     double info[8];
     check(mc_ir_shape_info(_engine, idx, info), "mc_ir_shape_info");
@@ -528,6 +570,59 @@ void Convolution::setIrPhase(const IrPhase& phase) {
     _irPhase = phase;
 }
 
+void Convolution::setIrFilter(const IrFilter& filter) {
+    if (filter.on && _group) {
+        Log::error("conv", "the IR filter step is not available with several devices (mc_load_ir_filter is single-engine)");
+        std::exit(2);
+    }
+    _irFilter = filter;
+}
+
+bool Convolution::parseFilter(const std::string& arg, IrFilter& out, std::string& why) {
+    const auto fail = [&](const std::string& w) {
+        why = w + " (FILE.wav[:key=value,...] with keys op, channels, reg, keep)";
+        return false;
+    };
+    const size_t colon = arg.find(':');
+    IrFilter f;
+    f.path = arg.substr(0, colon);
+    if (f.path.empty()) return fail("no file");
+    f.on = true;
+    if (colon != std::string::npos) {
+        const std::string list = arg.substr(colon + 1);
+        if (list.empty()) return fail("an empty list");
+        for (size_t at = 0; at <= list.size();) {
+            const size_t comma = std::min(list.find(',', at), list.size());
+            const std::string item = list.substr(at, comma - at);
+            at = comma + 1;
+            const size_t eqs = item.find('=');
+            if (item.empty() || eqs == std::string::npos || eqs == 0 || eqs + 1 == item.size()) return fail("'" + item + "' is not key=value");
+            const std::string key = item.substr(0, eqs), val = item.substr(eqs + 1);
+            if (key == "op") {
+                if (val != "convolve" && val != "deconvolve") return fail("op is convolve or deconvolve, not '" + val + "'");
+                f.deconvolve = val == "deconvolve";
+            } else if (key == "channels") {
+                if (val != "stereo" && val != "left" && val != "mid") return fail("channels is stereo, left or mid, not '" + val + "'");
+                f.channels = val == "stereo" ? 0 : val == "left" ? 1 : 2;
+            } else if (key == "reg" || key == "keep") {
+                char* end = nullptr;
+                const double v = std::strtod(val.c_str(), &end);
+                if (*end || !std::isfinite(v)) return fail("'" + val + "' of " + key + " is not a number");
+                if (key == "reg") {
+                    if (v < 20.0 || v > 200.0) return fail("reg " + val + " dB outside [20, 200]");
+                    f.regDb = (float)v;
+                } else {
+                    if (!(v > 0.0) || v > 3600.0) return fail("keep " + val + " s outside (0, 3600]");
+                    f.keepSeconds = v;
+                }
+            } else
+                return fail("no such key '" + key + "'");
+        }
+    }
+    out = f;
+    return true;
+}
+
 bool Convolution::parsePhase(const std::string& arg, IrPhase& out, std::string& why) {
     const auto fail = [&](const std::string& w) {
         why = w + " (minimum[:key=value,...] with keys floor, over)";
@@ -675,10 +770,13 @@ void Convolution::measureTail(const PendingIr& p) {
     PendingIr raw = p;
     raw.eq = IrEq();
     raw.damp = IrDamp();
-    const IrPhase phase = _irPhase;  // (the floor is that of the frames the tail step will see: before the phase step)
+    const IrPhase phase = _irPhase;  // (the floor is that of the frames the tail step will see: before the phase and filter steps)
+    IrFilter filter;
+    std::swap(filter, _irFilter);
     _irPhase = IrPhase();
     loadPending(raw, IrShape());
     _irPhase = phase;
+    std::swap(filter, _irFilter);
     const Floor f = irFloor(p.idx, _floorXovers);
     const double need = (double)f.query.margin_db + (double)f.query.span_db, ptn = f.at(0, Decay::LR, Floor::PeakToNoise);
     if (f.at(0, Decay::LR, Floor::Status) != 0.0 || !(ptn >= need)) {
@@ -1534,7 +1632,7 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
                    nullptr, _tailOn ? &_tailNow : nullptr);
         return;
     }
-    if (!shape.off() || _irPhase.minimum) {
+    if (!shape.off() || _irPhase.minimum || _irFilter.on) {
         loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : 0, convert ? (unsigned)samplerate : 0, shape);
         return;
     }
@@ -1567,7 +1665,7 @@ void Convolution::loadPendingIrs() {
 }
 
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
-    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _stiReport || _responseReport || _irTail.mode != IrTail::Off || _irPhase.minimum) {  // (loaded by onStart(), once the client's rate is known)
+    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _stiReport || _responseReport || _irTail.mode != IrTail::Off || _irPhase.minimum || _irFilter.on) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
         _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth(), false, IrSweep()});
         if (idx + 1 > _nirs) _nirs = idx + 1;

@@ -396,6 +396,26 @@ public:
     // The argument of --ir-phase, minimum[:key=value,...] with keys floor (dB) and over (2, 4, .. 64), as an IrPhase.  False,
     // with the reason in `why`, for a malformed one.
     static bool parsePhase(const std::string& arg, IrPhase& out, std::string& why);
+    // The filter step every IR loaded from now on goes through (mc_ir_filter of include/mcconv.h; no reference equivalent): the
+    // frames are convolved with a second IR (a cabinet into a room, a correction FIR into a hall: one IR at run time), or that
+    // one is divided out of them (a loop-back capture out of a measurement), after the phase step and ahead of the shape, EQ
+    // and damping.  lr holds the filter's interleaved frames at `rate` Hz (0: the client's); the engine converts them to the
+    // client's rate.  One log line per load tells the lengths and the level.  Loaded by onStart(), single device only.  A
+    // generated IR has no filter step and is loaded as it is, with a log line that says so.
+    struct IrFilter {
+        bool on = false;
+        bool deconvolve = false;
+        unsigned channels = 0;     // 0 stereo, 1 left, 2 mid (MC_FILTER_STEREO / LEFT / MID)
+        float regDb = 60.0f;       // [20, 200]: the regularisation of a deconvolution below the filter's strongest bin
+        double keepSeconds = 0.0;  // the length the step hands on; 0 = all of a convolution, the IR's own of a deconvolution
+        std::string path;          // as given on the command line
+        unsigned rate = 0;
+        std::vector<float> lr;
+    };
+    void setIrFilter(const IrFilter& filter);
+    // The argument of --ir-filter, FILE.wav[:key=value,...] with keys op (convolve, deconvolve), channels (stereo, left, mid),
+    // reg (dB) and keep (seconds), as an IrFilter without its frames.  False, with the reason in `why`, for a malformed one.
+    static bool parseFilter(const std::string& arg, IrFilter& out, std::string& why);
 
     void onMidiMessage(const RawMidi::Device* sender, const uint8_t* buffer, size_t len) override;
 
@@ -455,6 +475,7 @@ private:
     std::vector<float> _floorXovers;
     IrTail _irTail;
     IrPhase _irPhase;
+    IrFilter _irFilter;
     bool _tailOn = false;  // loadPending: the IR being loaded goes through _tailNow
     mc_ir_tail _tailNow;
     bool _decayReport = false;

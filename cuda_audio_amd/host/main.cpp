@@ -46,6 +46,12 @@
 // minimum phase on load, after --ir-tail's step and ahead of the other --ir-* options: the same magnitude response with the
 // delay inside the IR taken out (Convolution::setIrPhase; floor: the dynamic range of the log spectrum in dB, 120 without; over:
 // the oversampling of the transform, 2 .. 64, 8 without); one log line tells the delay removed and what the truncation kept.
+// --ir-filter FILE.wav[:op=deconvolve,channels=mid,reg=DB,keep=SECONDS]: every IR (a WAV or a captured sweep; a generated one is
+// left as it is) is convolved on load with the stereo IR in FILE.wav, converted from that file's rate to the client's, after
+// --ir-phase's step and ahead of the other --ir-* options, so that the cascade of the two runs as one IR
+// (Convolution::setIrFilter); op=deconvolve divides FILE.wav out of the IR instead, reg dB (60 without) below its strongest bin;
+// channels: stereo (without), left, or mid = (L + R) / 2 for both; keep: the seconds the step hands on (all of a convolution, the
+// IR's own length of a deconvolution without); one log line tells the lengths and the level.
 // --ir-density-report: after each IR is loaded one log line with its echo density (origin, mixing tap and time, first, largest and
 // later density of the LR row, measured by the engine: Convolution::setIrDensityReport); --ir-density-window SECONDS: the whole
 // window (20 ms without), --ir-density-hop SECONDS: between window centres (an eighth of the window without), --ir-density-t60
@@ -92,6 +98,7 @@ int main(int argc, char** argv) {
     std::vector<float> irFloorXovers;
     Convolution::IrTail irTail;
     Convolution::IrPhase irPhase;
+    Convolution::IrFilter irFilter;
     bool irDensityReport = false;
     Convolution::DensityQuery irDensity;
     bool irIaccReport = false;
@@ -219,6 +226,19 @@ int main(int argc, char** argv) {
                 std::cerr << "--ir-phase '" << argv[i] << "': " << why << std::endl;
                 return 2;
             }
+        } else if (!strcmp(argv[i], "--ir-filter") && i + 1 < argc) {
+            std::string why;
+            if (!Convolution::parseFilter(argv[++i], irFilter, why)) {
+                std::cerr << "--ir-filter '" << argv[i] << "': " << why << std::endl;
+                return 2;
+            }
+            if (!std::ifstream(irFilter.path, std::ifstream::binary).good()) {
+                std::cerr << "--ir-filter '" << argv[i] << "': cannot open " << irFilter.path << std::endl;
+                return 2;
+            }
+            const WavFile wav(irFilter.path);
+            irFilter.rate = wav.sampleRate;
+            irFilter.lr.assign(&wav.buffer[0].x, &wav.buffer[0].x + 2 * wav.numFrames);
         } else if (!strcmp(argv[i], "--ir-density-report")) irDensityReport = true;
         else if ((!strcmp(argv[i], "--ir-density-window") || !strcmp(argv[i], "--ir-density-hop") || !strcmp(argv[i], "--ir-density-t60")) && i + 1 < argc) {
             std::string why;
@@ -300,6 +320,7 @@ int main(int argc, char** argv) {
         c->setIrResponseReport(irResponseReport, irResponse);
         c->setIrTail(irTail);
         c->setIrPhase(irPhase);
+        c->setIrFilter(irFilter);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;
             const auto deviceId = settings.str("conv[%d].cc.device", idx);

@@ -150,6 +150,9 @@ int mc_load_ir_resampled(mc_engine *e, uint64_t idx, const float *lr, uint64_t f
  *      decaying noise (mc_ir_tail below); F' frames leave the step and take the place of the F in everything that follows;
  *   1b. (mc_load_ir_phase and mc_load_ir_sweep_phase only) the F frames are replaced by the minimum-phase IR of the same
  *      magnitude response (mc_ir_phase below); F frames leave the step, and the onset search of step 2 sees them;
+ *   1c. (mc_load_ir_filter and mc_load_ir_sweep_filter only) the F frames are convolved with a second impulse response, or that
+ *      one is divided out of them (mc_ir_filter below); Fo frames leave the step and take the place of the F in everything
+ *      that follows;
  *   2. s0 = min(start, F); with trim_db < 0 the onset is the first frame m after s0 whose max(|L|, |R|) reaches
  *      peak * 10^(trim_db / 20) (float arithmetic; peak over all frames after s0); first = s0 + max(0, onset - pre_roll);
  *   3. n = min(F - first, length or unlimited, n_ref - nframes) frames are stored (n = 0: MC_ERR_ARG, nothing changes);
@@ -836,6 +839,73 @@ int mc_load_ir_sweep_phase(mc_engine *e, uint64_t idx, const float *lr, uint64_t
  * the delay removed.  The sums are made of one partial per 256 frames, added in ascending order.  MC_ERR_STATE unless the IR's
  * last load had the step on. */
 int mc_ir_phase_info(const mc_engine *e, uint64_t idx, double out[8]);
+
+/* The filter step of an IR load (step 1c of the order of operations above): the frames are combined with a second impulse
+ * response, the filter.  Convolution cascades the two at load time - a cabinet into a room, a correction FIR into a hall - so
+ * that the period and batch paths pay nothing for it.  Deconvolution divides the filter out of the frames: the response of the
+ * playback and recording chain, as a loop-back capture gives it, out of a measured IR (Kirkeby's regularised inverse).
+ * No reference equivalent; single-engine.  DESIGN.md 2.20 has the reasons.
+ *
+ * Per output channel c, everything in double; a_c = the F frames the step takes (after steps 1, 1a and 1b); the filter is G
+ * stereo frames b at the session's rate (given at `rate` Hz, they are converted first as step 1 converts the IR, and G is
+ * the count after that: ceil(filter_frames session / rate)):
+ *   f_c = b_c (MC_FILTER_STEREO), b_L for both channels (MC_FILTER_LEFT) or (b_L + b_R) / 2 for both (MC_FILTER_MID);
+ *   Nfft = max(16, smallest power of two >= F + G - 1); A = FFT of a_c zero-padded to Nfft, B = FFT of f_c likewise;
+ *   MC_FILTER_CONVOLVE:   Y = A B;
+ *   MC_FILTER_DECONVOLVE: p[k] = |B[k]|^2, pm = max p, eps = 10^(-reg_db / 10), Y = A conj(B) / (p + eps pm).  pm = 0: the
+ *                         channel's output is all zeros.  The bins with p < eps pm are the regularised bins;
+ *   y = Re IFFT(Y); the step's output is y[0 .. Fo), rounded to float once;
+ *   Fo = frames_out when that is set, else F + G - 1 for a convolution (all of it) and F for a deconvolution.
+ * The deconvolution is circular over Nfft points: what the inverse of the filter rings past Nfft comes back at the front.
+ * The library carries both channels through one complex transform (L + i R), so a channel's bits depend on the other channel
+ * below the last place of a double.  The same frames, filter and struct store the same bits on every run.
+ * Synthesised loads (mc_synth_ir and the room entry points) have no filter entry point. */
+enum { MC_FILTER_OFF = 0, MC_FILTER_CONVOLVE = 1, MC_FILTER_DECONVOLVE = 2 };
+enum { MC_FILTER_STEREO = 0, MC_FILTER_LEFT = 1, MC_FILTER_MID = 2 };
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_ir_filter) = 32 */
+    uint32_t op;            /* MC_FILTER_OFF / CONVOLVE / DECONVOLVE; MC_FILTER_OFF: every other field ignored */
+    uint32_t channels;      /* MC_FILTER_STEREO / LEFT / MID */
+    uint32_t rate;          /* Hz of the filter's frames, [8000, 384000]; 0 = the session's */
+    float reg_db;           /* [20, 200]; default 60; read by a deconvolution only, checked always */
+    uint32_t reserved;      /* must be 0 */
+    uint64_t frames_out;    /* Fo; 0 = F + G - 1 (convolution) or F (deconvolution) */
+} mc_ir_filter;
+/* off; stereo; rate 0; reg_db 60; frames_out 0 */
+void mc_default_ir_filter(mc_ir_filter *f);
+/* What the step would do to `frames` frames with a filter of `filter_frames` frames, both at the session's rate (`rate` is
+ * checked and not used), host arithmetic only: out = {Nfft, passes per transform (1 or 2), bytes of device memory the step
+ * allocates while it runs (the filter's frames, the transforms' buffers and the partial sums), Fo}.  MC_ERR_ARG for a null
+ * pointer, a field of `f` outside its range (MC_FILTER_OFF is planned as a convolution), frames = 0 or filter_frames = 0, or
+ * lengths and frames_out beyond the limits below. */
+int mc_ir_filter_plan(const mc_ir_filter *f, uint64_t frames, uint64_t filter_frames, double out[4]);
+/* mc_load_ir_phase with `filter` applied as step 1c to the `filter_frames` interleaved stereo frames at filter_lr.  With filter
+ * NULL or MC_FILTER_OFF the call is mc_load_ir_phase itself, bit for bit; it leaves no filter information and does not look at
+ * filter_lr.  With the step on everything is checked before the engine or the device is touched (MC_ERR_ARG, the message names
+ * the field, the engine stays as it was): filter field by field in the struct's order (frames_out apart), then everything
+ * mc_load_ir_phase checks, in its order: phase, if it is on, field by field, then the tail, the rates and F' with a tail on, else
+ * damp, eq, shape, the rates and the frames.  The step's limits come as soon as F is known, after the phase step's: a rate
+ * that differs from a session_rate of 0 (the conversion needs the session's rate), filter_frames = 0 or above 2^40, Nfft <= 2^22
+ * (the message names the frames) and frames_out, at most F + G - 1 for a convolution and Nfft for a deconvolution.  A null
+ * filter_lr comes last, before the load's own null engine.  Such a load counts as shaped: mc_ir_shape_info's out[0] is Fo. */
+int mc_load_ir_filter(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
+                      uint32_t session_rate, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp, const mc_ir_tail *tail,
+                      const mc_ir_phase *phase, const mc_ir_filter *filter, const float *filter_lr, uint64_t filter_frames);
+/* mc_load_ir_sweep_phase with `filter` applied to the deconvolved frames after the phase step; the session's rate is the
+ * sweep's.  filter NULL or MC_FILTER_OFF: mc_load_ir_sweep_phase itself, bit for bit.  With the step on: filter field by field,
+ * then everything mc_load_ir_sweep_phase checks, in its order, with the step's limits after the phase step's, and a null
+ * filter_lr after the null lr. */
+int mc_load_ir_sweep_filter(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, const mc_sweep *sweep,
+                            int64_t offset, uint64_t ir_frames, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp,
+                            const mc_ir_tail *tail, const mc_ir_phase *phase, const mc_ir_filter *filter, const float *filter_lr,
+                            uint64_t filter_frames);
+/* out = {F, G, Fo, Nfft, E_in, E_filter, E_out, E_rest, regularised bins L, regularised bins R}: E_in = the sum over both
+ * channels of the squared frames that went in, E_filter that of f_L and f_R (with LEFT and MID the one signal counts for
+ * both channels), E_out that of the Fo frames as stored, in float, and E_rest that of y[Fo .. Nfft), in double, which the step
+ * left behind: rounding noise after a whole convolution, the truncated tail or the wrapped-round ringing otherwise.  The bins
+ * are 0 for a convolution.  The sums are made of one partial per 256 frames, added in ascending order.  MC_ERR_STATE unless
+ * the IR's last load had the step on. */
+int mc_ir_filter_info(const mc_engine *e, uint64_t idx, double out[10]);
 
 /* The reflections of a rectangular room (Allen and Berkley's image-source method), added on the device to the frames
  * mc_ir_synth describes: the room itself - its size, where the source and the two receivers stand, how hard the walls are -
