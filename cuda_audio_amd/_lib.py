@@ -30,6 +30,7 @@ SYMBOLS = [
     "mc_default_ir_tail", "mc_load_ir_tail", "mc_load_ir_sweep_tail", "mc_ir_tail_info",
     "mc_default_ir_phase", "mc_ir_phase_plan", "mc_load_ir_phase", "mc_load_ir_sweep_phase", "mc_ir_phase_info",
     "mc_default_ir_filter", "mc_ir_filter_plan", "mc_load_ir_filter", "mc_load_ir_sweep_filter", "mc_ir_filter_info",
+    "mc_default_ir_match", "mc_ir_match_plan", "mc_load_ir_match", "mc_load_ir_sweep_match", "mc_ir_match_info", "mc_ir_match_curve",
     "mc_default_ir_room", "mc_synth_ir_room", "mc_ir_room_info", "mc_ir_room_plan",
     "mc_default_ir_room_mics", "mc_synth_ir_room_mics", "mc_ir_room_mics_plan", "mc_ir_room_mics_info",
     "mc_default_ir_room_bands", "mc_synth_ir_room_bands", "mc_ir_room_bands_plan", "mc_ir_room_bands_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
@@ -360,6 +361,34 @@ class McIrFilter(C.Structure):
     ]
 
 
+MC_MATCH_OFF, MC_MATCH_TARGET, MC_MATCH_FLAT = 0, 1, 2
+MC_MATCH_MINIMUM, MC_MATCH_LINEAR = 0, 1
+MC_MATCH_MAX_POINTS = 1024
+
+
+class McIrMatch(C.Structure):
+    """mc_ir_match: the match step of mc_load_ir_match and mc_load_ir_sweep_match."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("phase", C.c_uint32),
+        ("link", C.c_uint32),
+        ("rate", C.c_uint32),
+        ("per_octave", C.c_uint32),
+        ("lo_hz", C.c_double),
+        ("hi_hz", C.c_double),
+        ("octaves", C.c_double),
+        ("amount", C.c_float),
+        ("boost_db", C.c_float),
+        ("cut_db", C.c_float),
+        ("floor_db", C.c_float),
+        ("tilt_db", C.c_float),
+        ("delay", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 MC_ROOM_MAX_ORDER = 32
 
 
@@ -527,6 +556,13 @@ def load():
     L.mc_load_ir_filter.argtypes = L.mc_load_ir_phase.argtypes + [C.POINTER(McIrFilter), fp, u64]
     L.mc_load_ir_sweep_filter.argtypes = L.mc_load_ir_sweep_phase.argtypes + [C.POINTER(McIrFilter), fp, u64]
     L.mc_ir_filter_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_default_ir_match.argtypes = [C.POINTER(McIrMatch)]
+    L.mc_default_ir_match.restype = None
+    L.mc_ir_match_plan.argtypes = [C.POINTER(McIrMatch), u64, u64, C.c_uint32, C.POINTER(C.c_double)]
+    L.mc_load_ir_match.argtypes = L.mc_load_ir_filter.argtypes + [C.POINTER(McIrMatch), fp, u64]
+    L.mc_load_ir_sweep_match.argtypes = L.mc_load_ir_sweep_filter.argtypes + [C.POINTER(McIrMatch), fp, u64]
+    L.mc_ir_match_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_ir_match_curve.argtypes = [vp, u64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32]
     L.mc_default_ir_room.argtypes = [C.POINTER(McIrRoom)]
     L.mc_default_ir_room.restype = None
     L.mc_synth_ir_room.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrRoom), C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp),

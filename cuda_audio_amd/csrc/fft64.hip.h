@@ -1,5 +1,5 @@
 // fft64.hip.h — a complex FFT in double for the IR tools: power-of-two lengths N = 2^4 .. 2^22, forward and inverse, data in
-// device memory as double2.  No reference equivalent.  It is a load-time tool (irphase.hip.h is its first user, irfilter.hip.h its second): correctness
+// device memory as double2.  No reference equivalent.  It is a load-time tool (irphase.hip.h is its first user, irfilter.hip.h its second, irmatch.hip.h its third): correctness
 // and the same bits on every run come first; the engine's own float transforms (fft512.hip.h, ossave.hip.h) stay what they are.
 //
 // Four-step form.  S = 2^11: a sub-transform of up to S points runs in LDS in one workgroup.

@@ -41,6 +41,7 @@
 #include "irtail.hip.h"
 #include "irphase.hip.h"
 #include "irfilter.hip.h"
+#include "irmatch.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
 // mc_config or that the tests compare bit for bit:
@@ -91,10 +92,10 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline double pan_l(double p) { return p >= 0 ? 1 - p : 1; }  // conv.cu:386
 inline double pan_r(double p) { return p <= 0 ? 1 + p : 1; }  // conv.cu:387
 
-// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _phase_info, _filter_info, _room_info, _room_mics_info and _room_bands_info report of an IR's last
+// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _phase_info, _filter_info, _match_info, _room_info, _room_mics_info and _room_bands_info report of an IR's last
 // load: one entry per kind, on when that load had the step or the source (a shape with something on, an eq band or damping count as a shape, and
 // so do a synthesised, a swept and a tailed load), with the numbers the getter hands out (include/mcconv.h says what they are)
-enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_PHASE, FACT_FILTER, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_KINDS };
+enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_PHASE, FACT_FILTER, FACT_MATCH, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_KINDS };
 struct IrFact {
     bool on = false;
     double v[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -119,6 +120,7 @@ struct IrEntry {
     int P = 0;
     double sums[4] = {0, 0, 0, 0};
     IrFact facts[FACT_KINDS];  // what the last load went through (note_load), for the mc_ir_*_info getters
+    std::vector<double> match_curve;  // with FACT_MATCH: hz[J], (before L, R)[J], (gain L, R)[J] (mc_ir_match_curve)
 };
 
 }  // namespace
@@ -3355,6 +3357,7 @@ struct IrLoad {
     const TailStep* tail = nullptr;      // step 1a, between the source and the shaping (irtail.hip.h; tail->plan.F = the frames at the session's rate)
     const PhaseStep* phase = nullptr;    // step 1b, after the tail step (irphase.hip.h; phase->F = the frames the tail step hands on)
     const FilterStep* filter = nullptr;  // step 1c, after the phase step (irfilter.hip.h; filter->F = the frames the phase step hands on)
+    const MatchStep* match = nullptr;    // step 1d, after the filter step (irmatch.hip.h; match->F = the frames the filter step hands on)
     const mc_ir_shape* shape = nullptr;  // applied on the device after the conversion (irshape.hip.h)
     const IeqCascade* eq = nullptr;      // the bands of mc_load_ir_eq (ireq.hip.h); with damp it may hold no band
     const DampPlan* damp = nullptr;      // the damping of mc_load_ir_damped (irdamp.hip.h; needs eq)
@@ -3367,6 +3370,7 @@ struct ShapedTaps {
     double sums[4] = {0, 0, 0, 0}, info[8];
     double phase[8];    // mc_ir_phase_info's numbers, with IrLoad::phase
     double filter[10];  // mc_ir_filter_info's numbers, with IrLoad::filter
+    MatchFacts match;   // mc_ir_match_info's numbers and mc_ir_match_curve's arrays, with IrLoad::match
 };
 
 // The stream idle and out of the JACK path, before the kernels of a load or of a measurement go onto it.  (The single-transform
@@ -3383,7 +3387,7 @@ int quiesce(mc_engine* e) {
 // The shaped load's own stage (irshape.hip.h): all `conv` frames of ld's source at the session's rate on the device, shaped
 // into a new buffer of out->n <= cap taps.  Nothing of the engine's IRs is touched here.  A sweep's recording is uploaded to a
 // temporary buffer freed after the stage, as its weight table is; the tail step turns the conv frames into tail->plan.Fp frames
-// in a buffer of their own, the phase step those into as many frames in another, and the filter step those into filter->Fo.
+// in a buffer of their own, the phase step those into as many frames in another, the filter step those into filter->Fo, and the match step those into match->Fo.
 int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, ShapedTaps* out) {
     float2 *d_x = nullptr, *d_rec = nullptr;
     double* d_u = nullptr;
@@ -3433,6 +3437,19 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
             (void)hipFree(d_y);
         }
     }
+    if (er == hipSuccess && ld.match) {
+        float2* d_y = nullptr;
+        er = hipMalloc(&d_y, sizeof(float2) * ld.match->Fo);
+        if (er == hipSuccess) er = match_run(e->stream, d_x, d_y, *ld.match, &out->match);  // (waits for the stream: d_x is free after it)
+        if (er == hipSuccess) {
+            (void)hipFree(d_x);
+            d_x = d_y;
+            conv = ld.match->Fo;
+        } else {
+            (void)hipStreamSynchronize(e->stream);
+            (void)hipFree(d_y);
+        }
+    }
     if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, *ld.shape, &out->d_taps, &out->n, out->sums, out->info, ld.eq, ld.damp);
     if (ld.swp && er != hipSuccess) (void)hipStreamSynchronize(e->stream);  // (the correlation may still be reading them)
     (void)hipFree(d_x);
@@ -3445,9 +3462,9 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
 }
 
 // What the mc_ir_*_info getters report of the load `ld` that stored `taps` taps; sinfo = the shaping stage's numbers, pinfo
-// the phase step's (read with ld.phase), finfo the filter step's (read with ld.filter).
+// the phase step's (read with ld.phase), finfo the filter step's (read with ld.filter), match the match step's (read with ld.match).
 // Every kind is written, so nothing of an earlier load onto the same index stays behind.
-void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[8], const double pinfo[8], const double finfo[10]) {
+void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[8], const double pinfo[8], const double finfo[10], const MatchFacts& match) {
     for (IrFact& f : ir.facts) f.on = false;
     const auto put = [&ir](IrFactKind kind, std::initializer_list<double> v) {
         ir.facts[kind].on = true;
@@ -3467,6 +3484,12 @@ void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[
     }
     if (ld.phase) put(FACT_PHASE, {pinfo[0], pinfo[1], pinfo[2], pinfo[3], pinfo[4], pinfo[5], pinfo[6], pinfo[7]});
     if (ld.filter) put(FACT_FILTER, {finfo[0], finfo[1], finfo[2], finfo[3], finfo[4], finfo[5], finfo[6], finfo[7], finfo[8], finfo[9]});
+    ir.match_curve.clear();
+    if (ld.match) {
+        const double* m = match.info;
+        put(FACT_MATCH, {m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8], m[9], m[10], m[11]});
+        ir.match_curve = match.curve;
+    }
     if (ld.room) {
         const RoomPlan& r = ld.room->plan;
         put(FACT_ROOM, {(double)r.N, (double)ld.room->kept[0], (double)ld.room->kept[1], r.tau[0], r.tau[1], (double)r.E, (double)r.complete, 0.0});
@@ -3508,7 +3531,7 @@ int load_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const IrLoad& ld) {
         const int rc = sf_load_ir(e, idx, lr, frames, nframes, rs, st.d_taps, st.n, st.sums);
         if (sh) (void)hipFree(d_lr);
         if (rc) return rc;
-        note_load(e->irs[idx], ld, st.n, st.info, st.phase, st.filter);
+        note_load(e->irs[idx], ld, st.n, st.info, st.phase, st.filter, st.match);
         return MC_OK;
     }
     const uint64_t n = sh ? st.n : std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
@@ -3585,7 +3608,7 @@ int load_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const IrLoad& ld) {
     std::memcpy(ir.sums, s, sizeof(s));
     ir.taps = n;
     ir.P = P;
-    note_load(ir, ld, n, st.info, st.phase, st.filter);
+    note_load(ir, ld, n, st.info, st.phase, st.filter, st.match);
     if ((int)idx + 1 > e->nirs) e->nirs = (int)idx + 1;
     e->spec_valid = e->dspec.valid = false;
     e->uniform_valid[0] = e->uniform_valid[1] = false;
@@ -3633,7 +3656,7 @@ const char* resolve_steps(const mc_ir_shape* shape, const mc_ir_eq* eq, const mc
     return nullptr;
 }
 
-// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, phase, filter, room, room mics, room bands): out = the first `count` numbers of what
+// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, phase, filter, match, room, room mics, room bands): out = the first `count` numbers of what
 // note_load kept of that kind, or MC_ERR_STATE with "IR <idx> <was_not>" when the last load had none
 int ir_fact(const mc_engine* e, uint64_t idx, IrFactKind kind, int count, const char* was_not, double* out) {
     if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
@@ -4235,12 +4258,16 @@ int mc_ir_phase_plan(const mc_ir_phase* p, uint64_t frames, double out[4]) {
     return MC_OK;
 }
 
-// mc_load_ir_phase and mc_load_ir_filter behind their switches: phase is on or null, filter is on or null, and one of them is on.
+// mc_load_ir_phase, mc_load_ir_filter and mc_load_ir_match behind their switches: each of phase, filter and match is on or null, and one
+// of them is on.
 static int load_phase_filter(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
                              const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail, const mc_ir_phase* phase,
-                             const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames) {
-    // the filter first, then the phase, then what mc_load_ir_tail checks in its order, the steps' limits once F is known, all before the engine
-    // and before any HIP call
+                             const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames, const mc_ir_match* match = nullptr,
+                             const float* target_lr = nullptr, uint64_t target_frames = 0) {
+    // the match first, then the filter, then the phase, then what mc_load_ir_tail checks in its order, the steps' limits once F is known, all
+    // before the engine and before any HIP call
+    if (match)
+        if (const char* bad = match_check(match)) return fail(MC_ERR_ARG, "%s", bad);
     if (filter)
         if (const char* bad = filter_check(filter)) return fail(MC_ERR_ARG, "%s", bad);
     if (phase)
@@ -4257,12 +4284,14 @@ static int load_phase_filter(mc_engine* e, uint64_t idx, const float* lr, uint64
     };
     IrSteps steps;
     TailStep tstep{};
-    uint64_t F = 0, G = 0;
+    uint64_t F = 0, G = 0, Gm = 0;
     // the limits of the steps that are on, over the F frames that reach them
     const auto limits = [&]() -> const char* {
         if (phase)
             if (const char* bad = phase_check_frames(phase, F)) return bad;
-        return filter ? filter_check_load(filter, session_rate, F, filter_frames, &G) : nullptr;
+        if (filter)
+            if (const char* bad = filter_check_load(filter, session_rate, F, filter_frames, &G)) return bad;
+        return match ? match_check_load(match, session_rate, filter && F ? filter_step(*filter, F, G).Fo : F, target_frames, &Gm) : nullptr;
     };
     if (tailed) {
         if (const char* bad = tail_check(tail, session_rate)) return fail(MC_ERR_ARG, "%s", bad);
@@ -4283,15 +4312,19 @@ static int load_phase_filter(mc_engine* e, uint64_t idx, const float* lr, uint64
         if (const char* bad = limits()) return fail(MC_ERR_ARG, "%s", bad);
     }
     if (filter && !filter_lr) return fail(MC_ERR_ARG, "null filter_lr");
+    if (match && match->mode == MC_MATCH_TARGET && !target_lr) return fail(MC_ERR_ARG, "null target_lr");
     const uint32_t rs[2] = {ir_rate, session_rate};
     const PhaseStep pstep = phase ? phase_step(*phase, F) : PhaseStep{};
     FilterStep fstep = filter ? filter_step(*filter, F, G) : FilterStep{};
     if (filter) fstep.lr = filter_lr, fstep.frames = filter_frames, fstep.rs[0] = filter->rate ? filter->rate : session_rate, fstep.rs[1] = session_rate;
+    MatchStep mstep = match && F ? match_step(*match, session_rate, filter ? fstep.Fo : F, Gm) : MatchStep{};
+    if (match) mstep.lr = target_lr, mstep.frames = target_frames, mstep.rs[0] = match->rate ? match->rate : session_rate, mstep.rs[1] = session_rate;
     IrLoad ld;
     ld.lr = lr, ld.frames = frames, ld.rs = ir_rate != session_rate ? rs : nullptr;
     ld.tail = tailed ? &tstep : nullptr;
     ld.phase = phase ? &pstep : nullptr;
     ld.filter = filter ? &fstep : nullptr;
+    ld.match = match ? &mstep : nullptr;
     steps.into(ld);
     return load_ir(e, idx, nframes, ld);
 }
@@ -4313,8 +4346,11 @@ int mc_load_ir_filter(mc_engine* e, uint64_t idx, const float* lr, uint64_t fram
 // mc_load_ir_sweep_phase and mc_load_ir_sweep_filter behind their switches, as load_phase_filter
 static int load_sweep_phase_filter(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
                                    uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail,
-                                   const mc_ir_phase* phase, const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames) {
-    // the filter first, then the phase, then what mc_load_ir_sweep_tail checks in its order, the steps' limits once F is known
+                                   const mc_ir_phase* phase, const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames,
+                                   const mc_ir_match* match = nullptr, const float* target_lr = nullptr, uint64_t target_frames = 0) {
+    // the match first, then the filter, then the phase, then what mc_load_ir_sweep_tail checks in its order, the steps' limits once F is known
+    if (match)
+        if (const char* bad = match_check(match)) return fail(MC_ERR_ARG, "%s", bad);
     if (filter)
         if (const char* bad = filter_check(filter)) return fail(MC_ERR_ARG, "%s", bad);
     if (phase)
@@ -4328,24 +4364,31 @@ static int load_sweep_phase_filter(mc_engine* e, uint64_t idx, const float* lr, 
         if (const char* bad = tail_check_frames(tail, ir_frames)) return fail(MC_ERR_ARG, "%s", bad);
     const TailStep tstep = tailed ? tail_step(*tail, sweep->rate, ir_frames) : TailStep{};
     const uint64_t F = tailed ? tstep.plan.Fp : ir_frames;
-    uint64_t G = 0;
+    uint64_t G = 0, Gm = 0;
     if (phase)
         if (const char* bad = phase_check_frames(phase, F)) return fail(MC_ERR_ARG, "%s", bad);
     if (filter)
         if (const char* bad = filter_check_load(filter, sweep->rate, F, filter_frames, &G)) return fail(MC_ERR_ARG, "%s", bad);
+    if (match)
+        if (const char* bad = match_check_load(match, sweep->rate, filter && F ? filter_step(*filter, F, G).Fo : F, target_frames, &Gm))
+            return fail(MC_ERR_ARG, "%s", bad);
     IrSteps steps;
     if (const char* bad = resolve_steps(shape, eq, damp, sweep->rate, sweep->rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
     if (!lr) return fail(MC_ERR_ARG, "null lr");
     if (filter && !filter_lr) return fail(MC_ERR_ARG, "null filter_lr");
+    if (match && match->mode == MC_MATCH_TARGET && !target_lr) return fail(MC_ERR_ARG, "null target_lr");
     const SweepSource src{swp_plan(*sweep), lr, frames, ir_frames, offset};
     const PhaseStep pstep = phase ? phase_step(*phase, F) : PhaseStep{};
     FilterStep fstep = filter ? filter_step(*filter, F, G) : FilterStep{};
     if (filter) fstep.lr = filter_lr, fstep.frames = filter_frames, fstep.rs[0] = filter->rate ? filter->rate : sweep->rate, fstep.rs[1] = sweep->rate;
+    MatchStep mstep = match && F ? match_step(*match, sweep->rate, filter ? fstep.Fo : F, Gm) : MatchStep{};
+    if (match) mstep.lr = target_lr, mstep.frames = target_frames, mstep.rs[0] = match->rate ? match->rate : sweep->rate, mstep.rs[1] = sweep->rate;
     IrLoad ld;
     ld.swp = &src, ld.frames = ir_frames;
     ld.tail = tailed ? &tstep : nullptr;
     ld.phase = phase ? &pstep : nullptr;
     ld.filter = filter ? &fstep : nullptr;
+    ld.match = match ? &mstep : nullptr;
     steps.into(ld);
     return load_ir(e, idx, nframes, ld);
 }
@@ -4365,6 +4408,74 @@ int mc_load_ir_sweep_filter(mc_engine* e, uint64_t idx, const float* lr, uint64_
         return mc_load_ir_sweep_phase(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail, phase);
     return load_sweep_phase_filter(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail,
                                    phase && phase->mode != MC_PHASE_OFF ? phase : nullptr, filter, filter_lr, filter_frames);
+}
+
+int mc_load_ir_match(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
+                     const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail, const mc_ir_phase* phase,
+                     const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames, const mc_ir_match* match, const float* target_lr,
+                     uint64_t target_frames) {
+    if (!match || match->mode == MC_MATCH_OFF)
+        return mc_load_ir_filter(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail, phase, filter, filter_lr, filter_frames);
+    return load_phase_filter(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail, phase && phase->mode != MC_PHASE_OFF ? phase : nullptr,
+                             filter && filter->op != MC_FILTER_OFF ? filter : nullptr, filter_lr, filter_frames, match, target_lr, target_frames);
+}
+
+int mc_load_ir_sweep_match(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
+                           uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail,
+                           const mc_ir_phase* phase, const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames,
+                           const mc_ir_match* match, const float* target_lr, uint64_t target_frames) {
+    if (!match || match->mode == MC_MATCH_OFF)
+        return mc_load_ir_sweep_filter(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail, phase, filter, filter_lr, filter_frames);
+    return load_sweep_phase_filter(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail,
+                                   phase && phase->mode != MC_PHASE_OFF ? phase : nullptr, filter && filter->op != MC_FILTER_OFF ? filter : nullptr, filter_lr,
+                                   filter_frames, match, target_lr, target_frames);
+}
+
+void mc_default_ir_match(mc_ir_match* m) {
+    if (!m) return;
+    std::memset(m, 0, sizeof(*m));
+    m->struct_size = (uint32_t)sizeof(*m);
+    m->mode = MC_MATCH_OFF;
+    m->phase = MC_MATCH_MINIMUM;
+    m->link = 1;
+    m->per_octave = 12;
+    m->lo_hz = 20.0;
+    m->octaves = 1.0 / 3.0;
+    m->amount = 1.f;
+    m->boost_db = 12.f;
+    m->cut_db = 24.f;
+    m->floor_db = 120.f;
+}
+
+int mc_ir_match_plan(const mc_ir_match* m, uint64_t frames, uint64_t target_frames, uint32_t session_rate, double out[6]) {
+    if (!m) return fail(MC_ERR_ARG, "null match");
+    if (const char* bad = match_check(m)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!frames) return fail(MC_ERR_ARG, "empty IR");
+    mc_ir_match at = *m;  // (both lengths are at the session's rate already; off is planned as a target)
+    at.rate = 0;
+    if (at.mode == MC_MATCH_OFF) at.mode = MC_MATCH_TARGET;
+    uint64_t G = 0;
+    if (const char* bad = match_check_load(&at, session_rate, frames, target_frames, &G)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!out) return fail(MC_ERR_ARG, "null out");
+    const MatchStep s = match_step(at, session_rate, frames, G);
+    out[0] = (double)s.Nfft, out[1] = (double)s.fft.passes, out[2] = (double)match_device_bytes(s), out[3] = (double)s.Fo, out[4] = (double)s.J;
+    out[5] = (double)s.window_bins;
+    return MC_OK;
+}
+
+int mc_ir_match_info(const mc_engine* e, uint64_t idx, double out[12]) { return ir_fact(e, idx, FACT_MATCH, 12, "was not loaded with a match step", out); }
+
+int mc_ir_match_curve(const mc_engine* e, uint64_t idx, double* hz, double* before_db, double* gain_db, uint32_t cap) {
+    double info[12];
+    if (const int rc = ir_fact(e, idx, FACT_MATCH, 12, "was not loaded with a match step", info)) return rc;
+    const std::vector<double>& c = e->irs[idx].match_curve;
+    const size_t J = c.size() / 5;
+    if (!hz || !before_db || !gain_db) return fail(MC_ERR_ARG, "null argument");
+    if (cap < J) return fail(MC_ERR_ARG, "cap %u below the curve's %llu points", cap, (unsigned long long)J);
+    std::copy(c.begin(), c.begin() + J, hz);
+    std::copy(c.begin() + J, c.begin() + 3 * J, before_db);
+    std::copy(c.begin() + 3 * J, c.end(), gain_db);
+    return (int)J;
 }
 
 void mc_default_ir_filter(mc_ir_filter* f) {

@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrRoom, McIrRoomBands, McIrRoomMics, McIrFilter, McIrPhase, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrRoom, McIrRoomBands, McIrRoomMics, McIrFilter, McIrMatch, McIrPhase, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -362,6 +362,85 @@ def filter_plan(filter, frames, session_rate=None):
     out = (C.c_double * 4)()
     check(_lib.load().mc_ir_filter_plan(C.byref(f), int(frames), G, out))
     return dict(nfft=int(out[0]), passes=int(out[1]), device_bytes=int(out[2]), frames_out=int(out[3]))
+
+
+@dataclasses.dataclass
+class IrMatch:
+    """A match EQ that prepare(match=...) and prepare_sweep(match=...) apply to the IR after the filter step and before
+    everything else (mc_ir_match, include/mcconv.h): the IR gets the smoothed spectrum of the target `ir` (float32 [frames, 2],
+    or an object with such a `.buffer` and a `.sampleRate`, which rate then defaults to), or with ir=None of a flat line that
+    tilts by tilt_db per octave (0 whitens, -3 aims at pink).  rate (Hz; None or 0 = the session's): the target is converted
+    to the session's rate on the device first.  The spectra are compared at per_octave points per octave from lo to hi Hz
+    (hi None: min(20000, half the session's rate)), each the mean power over `octaves` octaves; the difference, less its
+    mean, times amount, is bounded to [-cut_db, boost_db] and applied as a minimum-phase correction, or with phase="linear"
+    as a linear-phase one that delays the IR by `delay` frames.  link: one curve from the sum of both channels, which keeps
+    the stereo balance; False gives each channel a curve of its own.  floor_db: how far below its largest level a smoothed
+    spectrum is floored.  mode "off" does nothing."""
+
+    ir: object = None
+    rate: object = None
+    lo: float = 20.0
+    hi: object = None
+    per_octave: int = 12
+    octaves: float = 1.0 / 3.0
+    amount: float = 1.0
+    boost_db: float = 12.0
+    cut_db: float = 24.0
+    link: bool = True
+    phase: str = "minimum"
+    delay: int = 0
+    tilt_db: float = 0.0
+    floor_db: float = 120.0
+    mode: object = None
+
+    PHASES = {"minimum": _lib.MC_MATCH_MINIMUM, "linear": _lib.MC_MATCH_LINEAR}
+    MODES = {"off": _lib.MC_MATCH_OFF, "target": _lib.MC_MATCH_TARGET, "flat": _lib.MC_MATCH_FLAT}
+
+    def on(self):
+        return self.mode != "off"
+
+    def to_c(self):
+        if self.phase not in self.PHASES:
+            raise ValueError(f"phase must be one of {sorted(self.PHASES)}, not {self.phase!r}")
+        mode = self.mode if self.mode is not None else ("flat" if self.ir is None else "target")
+        if mode not in self.MODES:
+            raise ValueError(f"mode must be one of {sorted(self.MODES)}, not {mode!r}")
+        rate = self.rate if self.rate is not None else getattr(self.ir, "sampleRate", None)
+        m = McIrMatch()
+        _lib.load().mc_default_ir_match(C.byref(m))
+        m.mode, m.phase, m.link, m.rate, m.per_octave = self.MODES[mode], self.PHASES[self.phase], int(bool(self.link)), int(rate or 0), int(self.per_octave)
+        m.lo_hz, m.hi_hz, m.octaves = float(self.lo), float(self.hi or 0.0), float(self.octaves)
+        m.amount, m.boost_db, m.cut_db, m.floor_db, m.tilt_db, m.delay = (float(self.amount), float(self.boost_db), float(self.cut_db), float(self.floor_db),
+                                                                       float(self.tilt_db), int(self.delay))
+        return m
+
+    def frames(self):
+        """The target's frames as the library takes them: contiguous float32 [G, 2]; None for a flat target."""
+        if self.ir is None:
+            return None
+        return _f32(getattr(self.ir, "buffer", self.ir)).reshape(-1, 2)
+
+    def c_args(self):
+        """(match, target_lr, target_frames) as mc_load_ir_match takes them; the frames are returned too, to keep them alive."""
+        t = self.frames()
+        return (C.byref(self.to_c()), _fp(t) if t is not None else None, t.shape[0] if t is not None else 0), t
+
+
+def match_plan(match, frames, target_frames=None, rate=48000):
+    """What the match step `match` (an IrMatch) would do to `frames` frames at the session's rate `rate` (mc_ir_match_plan,
+    host arithmetic only): the transform's length, its passes, the device memory the step needs while it runs, the frames it
+    hands on, the grid's points and the bins all windows hold together.  target_frames: the target's length at the session's
+    rate (default: that of match.ir, converted when it has a rate of its own).  McError beyond the step's limits."""
+    m = match.to_c()
+    if target_frames is None:
+        t = match.frames()
+        target_frames = 0 if t is None else t.shape[0]
+        if m.rate and int(rate) != m.rate:
+            g = math.gcd(int(rate), m.rate)
+            target_frames = -(-target_frames * (int(rate) // g) // (m.rate // g))
+    out = (C.c_double * 6)()
+    check(_lib.load().mc_ir_match_plan(C.byref(m), int(frames), int(target_frames), int(rate), out))
+    return dict(nfft=int(out[0]), passes=int(out[1]), device_bytes=int(out[2]), frames_out=int(out[3]), points=int(out[4]), window_bins=int(out[5]))
 
 
 def tail_from_floor(floor, first=0, mode="extend", fade=0, length=0, seed=0, width=1.0):
@@ -837,7 +916,7 @@ class Convolution:
         check(self._L.mc_set_period(self._h, nframes))
 
     # -- reference surface ----------------------------------------------------
-    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None, damp=None, tail=None, phase=None, filter=None):
+    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None, damp=None, tail=None, phase=None, filter=None, match=None):
         """Convolution::prepare (conv.cu:207-253).  `wav` is float32 [frames, 2]
         (what WavFile.buffer holds) or an object with a `.buffer` of that shape.
         ir_rate (Hz; default: `wav.sampleRate` when it has one): when both it and the engine's sample_rate are known and
@@ -854,14 +933,18 @@ class Convolution:
         the shape (mc_load_ir_phase); it needs no rate; ir_phase_info(idx) then tells what was done.
         filter (an IrFilter whose op is not "off"): convolve the frames with a second IR, or divide it out of them, after the
         phase step and before the shape (mc_load_ir_filter); a filter with a rate of its own needs the engine's sample_rate;
-        ir_filter_info(idx) then tells what was done."""
+        ir_filter_info(idx) then tells what was done.
+        match (an IrMatch whose mode is not "off"): give the frames the smoothed spectrum of a target IR, or a flat one, after
+        the filter step and before the shape (mc_load_ir_match); the engine needs a sample_rate; ir_match_info(idx) and
+        ir_match_curve(idx) then tell what was done."""
         lr = _f32(getattr(wav, "buffer", wav)).reshape(-1, 2)
         if ir_rate is None:
             ir_rate = getattr(wav, "sampleRate", None)
         filtered = filter is not None and filter.op != "off"
-        if filtered or (phase is not None and phase.mode != "off"):
+        matched = match is not None and match.on()
+        if matched or filtered or (phase is not None and phase.mode != "off"):
             tailed = tail is not None and tail.mode != "off"
-            if tailed or eq is not None or (damp is not None and damp.xovers) or (filtered and filter.to_c().rate and self.sample_rate):
+            if matched or tailed or eq is not None or (damp is not None and damp.xovers) or (filtered and filter.to_c().rate and self.sample_rate):
                 session = int(self.sample_rate or 0)
                 rates = (session if ir_rate is None else int(ir_rate), session)
             elif ir_rate is not None and self.sample_rate is not None and int(ir_rate) != int(self.sample_rate):
@@ -872,7 +955,12 @@ class Convolution:
                     C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
                     C.byref(damp.to_c()) if damp is not None else None, C.byref(tail.to_c()) if tailed else None,
                     C.byref(phase.to_c()) if phase is not None else None)
-            if filtered:
+            if matched:
+                flr = filter.frames() if filtered else None
+                margs, keep = match.c_args()
+                check(self._L.mc_load_ir_match(*args, C.byref(filter.to_c()) if filtered else None, _fp(flr) if filtered else None,
+                                               flr.shape[0] if filtered else 0, *margs))
+            elif filtered:
                 flr = filter.frames()
                 check(self._L.mc_load_ir_filter(*args, C.byref(filter.to_c()), _fp(flr), flr.shape[0]))
             else:
@@ -941,7 +1029,7 @@ class Convolution:
         check(self._L.mc_synth_ir(self._h, idx, nframes, C.byref(s), C.byref(shape.to_c()) if shape is not None else None,
                                   C.byref(eq.to_c()) if eq is not None else None, C.byref(damp.to_c()) if damp is not None else None))
 
-    def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None, tail=None, phase=None, filter=None):
+    def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None, tail=None, phase=None, filter=None, match=None):
         """Deconvolve `recording` (float32 [frames, 2] or an object with such a `.buffer`: what was recorded while `sweep`, a
         Sweep, played) into an IR on the device and store it at idx (mc_load_ir_sweep): the frames take the place of a WAV's at
         the session's rate, and shape, eq and damp apply to them as in prepare().  IR frame m is the correlation at lag
@@ -951,7 +1039,8 @@ class Convolution:
         is set (the library's default, 44100, when the engine has none either).  tail (an IrTail whose mode is not "off"): the
         tail step on the deconvolved frames (mc_load_ir_sweep_tail).  phase (an IrPhase whose mode is not "off"): the phase step
         after it (mc_load_ir_sweep_phase).  filter (an IrFilter whose op is not "off"): the filter step after that
-        (mc_load_ir_sweep_filter), the session's rate being the sweep's."""
+        (mc_load_ir_sweep_filter), the session's rate being the sweep's.  match (an IrMatch whose mode is not "off"): the match
+        step after that (mc_load_ir_sweep_match)."""
         lr = _f32(getattr(recording, "buffer", recording)).reshape(-1, 2)
         s = sweep.to_c()
         if not sweep.rate and self.sample_rate:
@@ -962,7 +1051,14 @@ class Convolution:
         args = (self._h, idx, _fp(lr), lr.shape[0], nframes, C.byref(s), int(offset), int(ir_frames),
                 C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
                 C.byref(damp.to_c()) if damp is not None else None)
-        if filter is not None and filter.op != "off":
+        if match is not None and match.on():
+            filtered = filter is not None and filter.op != "off"
+            flr = filter.frames() if filtered else None
+            margs, keep = match.c_args()
+            check(self._L.mc_load_ir_sweep_match(*args, C.byref(tail.to_c()) if tail is not None else None, C.byref(phase.to_c()) if phase is not None else None,
+                                                 C.byref(filter.to_c()) if filtered else None, _fp(flr) if filtered else None, flr.shape[0] if filtered else 0,
+                                                 *margs))
+        elif filter is not None and filter.op != "off":
             flr = filter.frames()
             check(self._L.mc_load_ir_sweep_filter(*args, C.byref(tail.to_c()) if tail is not None else None, C.byref(phase.to_c()) if phase is not None else None,
                                                   C.byref(filter.to_c()), _fp(flr), flr.shape[0]))
@@ -1340,6 +1436,28 @@ class Convolution:
         check(self._L.mc_ir_filter_info(self._h, idx, out))
         return dict(frames=int(out[0]), filter_frames=int(out[1]), frames_out=int(out[2]), nfft=int(out[3]), energy_in=float(out[4]),
                     energy_filter=float(out[5]), energy_out=float(out[6]), energy_rest=float(out[7]), regularised=(int(out[8]), int(out[9])))
+
+    def ir_match_info(self, idx):
+        """What the match step of IR idx's load did (mc_ir_match_info): the frames it took, the target's frames at the
+        session's rate (0 for a flat target), the frames it handed on, the transform's length, the grid's points, the energy
+        of the frames, of the target and of what was stored, the energy left behind past frames_out, the mean that was
+        taken out of either channel's curve (dB) and the points that ran into boost_db or cut_db.  McError (MC_ERR_STATE)
+        for an IR whose last load had no match step."""
+        out = (C.c_double * 12)()
+        check(self._L.mc_ir_match_info(self._h, idx, out))
+        return dict(frames=int(out[0]), target_frames=int(out[1]), frames_out=int(out[2]), nfft=int(out[3]), points=int(out[4]), energy_in=float(out[5]),
+                    energy_target=float(out[6]), energy_out=float(out[7]), energy_rest=float(out[8]), mean_db=(float(out[9]), float(out[10])),
+                    clamped=int(out[11]))
+
+    def ir_match_curve(self, idx):
+        """The curve of IR idx's match step (mc_ir_match_curve): hz [J], before_db [J, 2] (the smoothed difference to the target
+        less its mean, per channel) and gain_db [J, 2] (what was applied at those frequencies), float64."""
+        cap = _lib.MC_MATCH_MAX_POINTS
+        hz, before, gain = (C.c_double * cap)(), (C.c_double * (2 * cap))(), (C.c_double * (2 * cap))()
+        J = self._L.mc_ir_match_curve(self._h, idx, hz, before, gain, cap)
+        if J < 0:
+            check(J)
+        return dict(hz=np.array(hz[:J]), before_db=np.array(before[:2 * J]).reshape(J, 2), gain_db=np.array(gain[:2 * J]).reshape(J, 2))
 
     def enable_kernel_timing(self, on=True):
         check(self._L.mc_enable_kernel_timing(self._h, 1 if on else 0))

@@ -86,6 +86,15 @@ int mc_load_ir_filter(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, ui
 int mc_load_ir_sweep_filter(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
                             const mc_ir_damp*, const mc_ir_tail*, const mc_ir_phase*, const mc_ir_filter*, const float*, uint64_t) __attribute__((weak));
 int mc_ir_filter_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+void mc_default_ir_match(mc_ir_match*) __attribute__((weak));
+int mc_load_ir_match(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
+                     const mc_ir_tail*, const mc_ir_phase*, const mc_ir_filter*, const float*, uint64_t, const mc_ir_match*, const float*, uint64_t)
+    __attribute__((weak));
+int mc_load_ir_sweep_match(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
+                           const mc_ir_damp*, const mc_ir_tail*, const mc_ir_phase*, const mc_ir_filter*, const float*, uint64_t, const mc_ir_match*,
+                           const float*, uint64_t) __attribute__((weak));
+int mc_ir_match_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+int mc_ir_match_curve(const mc_engine*, uint64_t, double*, double*, double*, uint32_t) __attribute__((weak));
 // ... and no room
 void mc_default_ir_room(mc_ir_room*) __attribute__((weak));
 int mc_synth_ir_room(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_room*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
@@ -241,6 +250,12 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         Log::error("conv", "the engine has no filter step (mc_load_ir_filter)");
         std::exit(2);
     }
+    const bool matched = _irMatch.on && !synth;
+    if (_irMatch.on && synth) Log::info(name, "IR %zu is generated: it has no match step and is loaded as it is", idx);
+    if (matched && (!mc_default_ir_match || !mc_load_ir_match || !mc_load_ir_sweep_match || !mc_ir_match_info || !mc_ir_match_curve)) {
+        Log::error("conv", "the engine has no match step (mc_load_ir_match)");
+        std::exit(2);
+    }
     if (tail && (!mc_load_ir_tail || !mc_load_ir_sweep_tail || !mc_ir_tail_info)) {
         Log::error("conv", "the engine has no tail step (mc_load_ir_tail)");
         std::exit(2);
@@ -299,6 +314,26 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         fl.frames_out = dampFrames(_irFilter.keepSeconds, (double)session);
         if (fl.rate && !sessionRate) irRate = sessionRate = session;
     }
+    mc_ir_match mt;
+    const uint64_t mtFrames = _irMatch.lr.size() / 2;
+    if (matched) {
+        // the grid is in Hz: the call needs the session's rate, and frames that are loaded at the rate they have are at the client's
+        const unsigned session = sweep ? sweep->sweep.rate : sessionRate ? sessionRate : (unsigned)samplerate;
+        mc_default_ir_match(&mt);
+        mt.mode = _irMatch.flat ? MC_MATCH_FLAT : MC_MATCH_TARGET;
+        mt.phase = _irMatch.linear ? MC_MATCH_LINEAR : MC_MATCH_MINIMUM;
+        mt.link = _irMatch.link ? 1 : 0;
+        mt.rate = !_irMatch.flat && _irMatch.rate && _irMatch.rate != session ? _irMatch.rate : 0;
+        mt.lo_hz = _irMatch.loHz;
+        mt.hi_hz = _irMatch.hiHz;
+        mt.octaves = _irMatch.octaves;
+        mt.amount = _irMatch.amount;
+        mt.boost_db = _irMatch.boostDb;
+        mt.cut_db = _irMatch.cutDb;
+        mt.tilt_db = _irMatch.tiltDb;
+        mt.delay = (uint32_t)dampFrames(_irMatch.delaySeconds, (double)session);
+        if (!sessionRate) irRate = sessionRate = session;
+    }
     if (!eq.off()) {
         mc_default_ir_eq(&q);
         for (size_t k = 0; k < eq.bands.size(); k++) q.band[k] = mc_eq_band{(uint32_t)eq.bands[k].kind, eq.bands[k].hz, eq.bands[k].gainDb, eq.bands[k].q};
@@ -350,7 +385,10 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         Log::info(name, "IR %zu synthesised: %llu frames, seed %llu, %d of %u reflections kept", idx, (unsigned long long)si[0],
                   (unsigned long long)synth->seed, (int)si[1], synth->n_early);
     } else if (sweep) {  // (as for a generated IR: what the engine refuses is the index line's fault)
-        const int rc = filtered ? mc_load_ir_sweep_filter(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
+        const int rc = matched ? mc_load_ir_sweep_match(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
+                                                        eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, minimum ? &ph : nullptr,
+                                                        filtered ? &fl : nullptr, _irFilter.lr.data(), flFrames, &mt, _irMatch.lr.data(), mtFrames)
+                       : filtered ? mc_load_ir_sweep_filter(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
                                                           eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, minimum ? &ph : nullptr, &fl,
                                                           _irFilter.lr.data(), flFrames)
                        : minimum ? mc_load_ir_sweep_phase(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
@@ -367,6 +405,12 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         check(mc_ir_sweep_info(_engine, idx, wi), "mc_ir_sweep_info");
         Log::info(name, "IR %zu captured: sweep %llu frames, recording %llu frames, %llu frames at offset %lld", idx, (unsigned long long)wi[0],
                   (unsigned long long)wi[1], (unsigned long long)wi[2], (long long)wi[3]);
+    } else if (matched) {  // (lengths and a grid beyond the step are the command line's fault: a message and exit 2, no abort)
+        if (mc_load_ir_match(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail,
+                             minimum ? &ph : nullptr, filtered ? &fl : nullptr, _irFilter.lr.data(), flFrames, &mt, _irMatch.lr.data(), mtFrames) != MC_OK) {
+            Log::error("conv", "IR %zu cannot be matched to %s: %s", idx, _irMatch.path.c_str(), mc_last_error());
+            std::exit(2);
+        }
     } else if (filtered) {  // (lengths beyond the step are the command line's fault: a message and exit 2, no abort)
         if (mc_load_ir_filter(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail,
                               minimum ? &ph : nullptr, &fl, _irFilter.lr.data(), flFrames) != MC_OK) {
@@ -412,6 +456,22 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
                   idx, _irFilter.deconvolve ? "deconvolved by" : "convolved with", _irFilter.path.c_str(), (unsigned long long)fi[0], (unsigned long long)fi[1],
                   (unsigned long long)fi[3], (unsigned long long)fi[2], fi[4] > 0.0 && fi[6] > 0.0 ? 10.0 * std::log10(fi[6] / fi[4]) : 0.0,
                   fi[6] > 0.0 && fi[7] > 0.0 ? std::max(-999.0, 10.0 * std::log10(fi[7] / fi[6])) : -999.0, (unsigned long long)fi[8], (unsigned long long)fi[9]);
+    }
+    if (matched) {
+        double mi[12];
+        check(mc_ir_match_info(_engine, idx, mi), "mc_ir_match_info");
+        std::vector<double> hz(1024), before(2048), gain(2048);
+        const int J = mc_ir_match_curve(_engine, idx, hz.data(), before.data(), gain.data(), 1024);
+        if (J < 0) check(J, "mc_ir_match_curve");
+        double least = 0.0, most = 0.0;
+        for (int j = 0; j < 2 * J; j++) least = std::min(least, gain[j]), most = std::max(most, gain[j]);
+        Log::info(name, "IR %zu matched to %s: %llu frames and %llu target frames through a transform of %llu points, %llu frames kept, %d points, gain %+.2f .. %+.2f dB, %llu clamped, level %+.2f dB",
+                  idx, _irMatch.path.c_str(), (unsigned long long)mi[0], (unsigned long long)mi[1], (unsigned long long)mi[3], (unsigned long long)mi[2], J, least,
+                  most, (unsigned long long)mi[11], mi[5] > 0.0 && mi[7] > 0.0 ? 10.0 * std::log10(mi[7] / mi[5]) : 0.0);
+        if (_irMatchReport)
+            for (int j = 0; j < J; j++)
+                Log::info(name, "IR %zu match %.3f Hz: before %+.4f %+.4f dB, gain %+.4f %+.4f dB", idx, hz[j], before[2 * j], before[2 * j + 1], gain[2 * j],
+                          gain[2 * j + 1]);
     }
     double info[8];
     check(mc_ir_shape_info(_engine, idx, info), "mc_ir_shape_info");
@@ -576,6 +636,78 @@ void Convolution::setIrFilter(const IrFilter& filter) {
         std::exit(2);
     }
     _irFilter = filter;
+}
+
+void Convolution::setIrMatch(const IrMatch& match, bool report) {
+    if (match.on && _group) {
+        Log::error("conv", "the IR match step is not available with several devices (mc_load_ir_match is single-engine)");
+        std::exit(2);
+    }
+    _irMatch = match;
+    _irMatchReport = report;
+}
+
+bool Convolution::parseMatch(const std::string& arg, IrMatch& out, std::string& why) {
+    const auto fail = [&](const std::string& w) {
+        why = w + " (FILE.wav|flat[:key=value,...] with keys amount, boost, cut, smooth, lo, hi, link, phase, delay, tilt)";
+        return false;
+    };
+    const size_t colon = arg.find(':');
+    IrMatch m;
+    m.path = arg.substr(0, colon);
+    if (m.path.empty()) return fail("no file");
+    m.flat = m.path == "flat";
+    m.on = true;
+    if (colon != std::string::npos) {
+        const std::string list = arg.substr(colon + 1);
+        if (list.empty()) return fail("an empty list");
+        for (size_t at = 0; at <= list.size();) {
+            const size_t comma = std::min(list.find(',', at), list.size());
+            const std::string item = list.substr(at, comma - at);
+            at = comma + 1;
+            const size_t eqs = item.find('=');
+            if (item.empty() || eqs == std::string::npos || eqs == 0 || eqs + 1 == item.size()) return fail("'" + item + "' is not key=value");
+            const std::string key = item.substr(0, eqs), val = item.substr(eqs + 1);
+            if (key == "phase") {
+                if (val != "minimum" && val != "linear") return fail("phase is minimum or linear, not '" + val + "'");
+                m.linear = val == "linear";
+                continue;
+            }
+            if (key == "link") {
+                if (val != "0" && val != "1") return fail("link is 0 or 1, not '" + val + "'");
+                m.link = val == "1";
+                continue;
+            }
+            char* end = nullptr;
+            const double v = std::strtod(val.c_str(), &end);
+            const auto within = [&](double lo, double hi) { return v >= lo && v <= hi; };
+            if (key != "amount" && key != "boost" && key != "cut" && key != "smooth" && key != "lo" && key != "hi" && key != "delay" && key != "tilt")
+                return fail("no such key '" + key + "'");
+            if (*end || !std::isfinite(v)) return fail("'" + val + "' of " + key + " is not a number");
+            if (key == "amount") {
+                if (!within(0.0, 1.0)) return fail("amount " + val + " outside [0, 1]");
+                m.amount = (float)v;
+            } else if (key == "boost" || key == "cut") {
+                if (!within(0.0, 60.0)) return fail(key + " " + val + " dB outside [0, 60]");
+                (key == "boost" ? m.boostDb : m.cutDb) = (float)v;
+            } else if (key == "smooth") {
+                if (!within(1.0 / 24.0, 2.0)) return fail("smooth " + val + " octaves outside [1/24, 2]");
+                m.octaves = v;
+            } else if (key == "lo" || key == "hi") {
+                if (!within(1.0, 192000.0)) return fail(key + " " + val + " Hz outside [1, 192000]");
+                (key == "lo" ? m.loHz : m.hiHz) = v;
+            } else if (key == "delay") {
+                if (!within(0.0, 10.0)) return fail("delay " + val + " s outside [0, 10]");
+                m.delaySeconds = v;
+            } else {
+                if (!within(-12.0, 12.0)) return fail("tilt " + val + " dB per octave outside [-12, 12]");
+                m.tiltDb = (float)v;
+            }
+        }
+    }
+    if (m.hiHz != 0.0 && !(m.hiHz > m.loHz)) return fail("hi is not above lo");
+    out = m;
+    return true;
 }
 
 bool Convolution::parseFilter(const std::string& arg, IrFilter& out, std::string& why) {
@@ -772,11 +904,14 @@ void Convolution::measureTail(const PendingIr& p) {
     raw.damp = IrDamp();
     const IrPhase phase = _irPhase;  // (the floor is that of the frames the tail step will see: before the phase and filter steps)
     IrFilter filter;
+    IrMatch match;
     std::swap(filter, _irFilter);
+    std::swap(match, _irMatch);
     _irPhase = IrPhase();
     loadPending(raw, IrShape());
     _irPhase = phase;
     std::swap(filter, _irFilter);
+    std::swap(match, _irMatch);
     const Floor f = irFloor(p.idx, _floorXovers);
     const double need = (double)f.query.margin_db + (double)f.query.span_db, ptn = f.at(0, Decay::LR, Floor::PeakToNoise);
     if (f.at(0, Decay::LR, Floor::Status) != 0.0 || !(ptn >= need)) {
@@ -1632,7 +1767,7 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
                    nullptr, _tailOn ? &_tailNow : nullptr);
         return;
     }
-    if (!shape.off() || _irPhase.minimum || _irFilter.on) {
+    if (!shape.off() || _irPhase.minimum || _irFilter.on || _irMatch.on) {
         loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : 0, convert ? (unsigned)samplerate : 0, shape);
         return;
     }
@@ -1665,7 +1800,7 @@ void Convolution::loadPendingIrs() {
 }
 
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
-    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _stiReport || _responseReport || _irTail.mode != IrTail::Off || _irPhase.minimum || _irFilter.on) {  // (loaded by onStart(), once the client's rate is known)
+    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _stiReport || _responseReport || _irTail.mode != IrTail::Off || _irPhase.minimum || _irFilter.on || _irMatch.on) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
         _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth(), false, IrSweep()});
         if (idx + 1 > _nirs) _nirs = idx + 1;

@@ -416,6 +416,32 @@ public:
     // The argument of --ir-filter, FILE.wav[:key=value,...] with keys op (convolve, deconvolve), channels (stereo, left, mid),
     // reg (dB) and keep (seconds), as an IrFilter without its frames.  False, with the reason in `why`, for a malformed one.
     static bool parseFilter(const std::string& arg, IrFilter& out, std::string& why);
+    // The match step every IR loaded from now on goes through (mc_ir_match of include/mcconv.h; no reference equivalent): a match
+    // EQ that gives the frames the smoothed spectrum of a target IR, or of a flat or tilted line, after the filter step and ahead
+    // of the shape, EQ and damping.  lr holds the target's interleaved frames at `rate` Hz (0: the client's); the engine converts
+    // them to the client's rate.  One log line per load tells the lengths, the curve's range and the level; with `report` one
+    // line per grid point follows with the curve.  Loaded by onStart(), single device only.  A generated IR has no match step
+    // and is loaded as it is, with a log line that says so.
+    struct IrMatch {
+        bool on = false;
+        bool flat = false;          // no target: a line that tilts by tiltDb per octave
+        bool linear = false;        // a linear-phase correction that delays the IR by delaySeconds; else minimum phase
+        bool link = true;           // one curve from both channels; false: a curve per channel
+        float amount = 1.0f;        // [0, 1] of the difference
+        float boostDb = 12.0f, cutDb = 24.0f;  // [0, 60]: the curve's bounds
+        double octaves = 1.0 / 3.0;            // [1/24, 2]: the smoothing
+        double loHz = 20.0, hiHz = 0.0;        // the grid; hiHz 0: min(20000, half the client's rate)
+        double delaySeconds = 0.0;
+        float tiltDb = 0.0f;
+        std::string path;           // as given on the command line, or "flat"
+        unsigned rate = 0;
+        std::vector<float> lr;
+    };
+    void setIrMatch(const IrMatch& match, bool report);
+    // The argument of --ir-match, FILE.wav|flat[:key=value,...] with keys amount, boost, cut (dB), smooth (octaves), lo, hi (Hz),
+    // link (0, 1), phase (minimum, linear), delay (seconds) and tilt (dB per octave), as an IrMatch without its frames.  False,
+    // with the reason in `why`, for a malformed one.
+    static bool parseMatch(const std::string& arg, IrMatch& out, std::string& why);
 
     void onMidiMessage(const RawMidi::Device* sender, const uint8_t* buffer, size_t len) override;
 
@@ -476,6 +502,8 @@ private:
     IrTail _irTail;
     IrPhase _irPhase;
     IrFilter _irFilter;
+    IrMatch _irMatch;
+    bool _irMatchReport = false;
     bool _tailOn = false;  // loadPending: the IR being loaded goes through _tailNow
     mc_ir_tail _tailNow;
     bool _decayReport = false;

@@ -52,6 +52,14 @@
 // (Convolution::setIrFilter); op=deconvolve divides FILE.wav out of the IR instead, reg dB (60 without) below its strongest bin;
 // channels: stereo (without), left, or mid = (L + R) / 2 for both; keep: the seconds the step hands on (all of a convolution, the
 // IR's own length of a deconvolution without); one log line tells the lengths and the level.
+// --ir-match FILE.wav|flat[:amount=A,boost=DB,cut=DB,smooth=OCTAVES,lo=HZ,hi=HZ,link=0,phase=linear,delay=SECONDS,tilt=DB]: every IR (a
+// WAV or a captured sweep; a generated one is left as it is) gets on load the tonal balance of the stereo IR in FILE.wav, converted
+// from that file's rate to the client's, or with `flat` of a line that tilts by tilt dB per octave (0 whitens, -3 aims at pink),
+// after --ir-filter's step and ahead of the other --ir-* options (Convolution::setIrMatch): the third-octave-smoothed (smooth)
+// spectra are compared from lo to hi Hz (20 Hz to 20 kHz or half the rate without), amount (1 without) of the difference, less
+// its mean, is bounded to boost and cut dB (12 and 24 without) and applied as a minimum-phase correction, or with phase=linear
+// as a linear-phase one that delays the IR by delay seconds; link=0 gives each channel a curve of its own; one log line tells the
+// lengths, the curve's range and the level.  --ir-match-report: one more line per grid point with the curve.
 // --ir-density-report: after each IR is loaded one log line with its echo density (origin, mixing tap and time, first, largest and
 // later density of the LR row, measured by the engine: Convolution::setIrDensityReport); --ir-density-window SECONDS: the whole
 // window (20 ms without), --ir-density-hop SECONDS: between window centres (an eighth of the window without), --ir-density-t60
@@ -99,6 +107,8 @@ int main(int argc, char** argv) {
     Convolution::IrTail irTail;
     Convolution::IrPhase irPhase;
     Convolution::IrFilter irFilter;
+    Convolution::IrMatch irMatch;
+    bool irMatchReport = false;
     bool irDensityReport = false;
     Convolution::DensityQuery irDensity;
     bool irIaccReport = false;
@@ -239,7 +249,23 @@ int main(int argc, char** argv) {
             const WavFile wav(irFilter.path);
             irFilter.rate = wav.sampleRate;
             irFilter.lr.assign(&wav.buffer[0].x, &wav.buffer[0].x + 2 * wav.numFrames);
-        } else if (!strcmp(argv[i], "--ir-density-report")) irDensityReport = true;
+        } else if (!strcmp(argv[i], "--ir-match") && i + 1 < argc) {
+            std::string why;
+            if (!Convolution::parseMatch(argv[++i], irMatch, why)) {
+                std::cerr << "--ir-match '" << argv[i] << "': " << why << std::endl;
+                return 2;
+            }
+            if (!irMatch.flat) {
+                if (!std::ifstream(irMatch.path, std::ifstream::binary).good()) {
+                    std::cerr << "--ir-match '" << argv[i] << "': cannot open " << irMatch.path << std::endl;
+                    return 2;
+                }
+                const WavFile wav(irMatch.path);
+                irMatch.rate = wav.sampleRate;
+                irMatch.lr.assign(&wav.buffer[0].x, &wav.buffer[0].x + 2 * wav.numFrames);
+            }
+        } else if (!strcmp(argv[i], "--ir-match-report")) irMatchReport = true;
+        else if (!strcmp(argv[i], "--ir-density-report")) irDensityReport = true;
         else if ((!strcmp(argv[i], "--ir-density-window") || !strcmp(argv[i], "--ir-density-hop") || !strcmp(argv[i], "--ir-density-t60")) && i + 1 < argc) {
             std::string why;
             const char* option = argv[i];
@@ -321,6 +347,7 @@ int main(int argc, char** argv) {
         c->setIrTail(irTail);
         c->setIrPhase(irPhase);
         c->setIrFilter(irFilter);
+        c->setIrMatch(irMatch, irMatchReport);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;
             const auto deviceId = settings.str("conv[%d].cc.device", idx);

@@ -153,6 +153,8 @@ int mc_load_ir_resampled(mc_engine *e, uint64_t idx, const float *lr, uint64_t f
  *   1c. (mc_load_ir_filter and mc_load_ir_sweep_filter only) the F frames are convolved with a second impulse response, or that
  *      one is divided out of them (mc_ir_filter below); Fo frames leave the step and take the place of the F in everything
  *      that follows;
+ *   1d. (mc_load_ir_match and mc_load_ir_sweep_match only) the F frames are given the smoothed spectrum of a target impulse
+ *      response, or a flat or tilted one, by a match EQ (mc_ir_match below); Fo frames leave the step likewise;
  *   2. s0 = min(start, F); with trim_db < 0 the onset is the first frame m after s0 whose max(|L|, |R|) reaches
  *      peak * 10^(trim_db / 20) (float arithmetic; peak over all frames after s0); first = s0 + max(0, onset - pre_roll);
  *   3. n = min(F - first, length or unlimited, n_ref - nframes) frames are stored (n = 0: MC_ERR_ARG, nothing changes);
@@ -906,6 +908,99 @@ int mc_load_ir_sweep_filter(mc_engine *e, uint64_t idx, const float *lr, uint64_
  * are 0 for a convolution.  The sums are made of one partial per 256 frames, added in ascending order.  MC_ERR_STATE unless
  * the IR's last load had the step on. */
 int mc_ir_filter_info(const mc_engine *e, uint64_t idx, double out[10]);
+
+/* The match step of an IR load (step 1d of the order of operations above): a match EQ.  The frames get the tonal balance of a
+ * second impulse response, the target ("make this cabinet sound like that one"), or of a flat or tilted line.  The two
+ * fractional-octave-smoothed power spectra are compared on a logarithmic grid, the difference is bounded and applied as a
+ * short, smooth minimum-phase or linear-phase correction.  Unlike a deconvolution it leaves fine structure and phase alone,
+ * and it changes tone, not level.  No reference equivalent; single-engine.  DESIGN.md 2.21 has the reasons.
+ *
+ * Per channel c, everything in double; a_c = the F frames the step takes (after steps 1 .. 1c); the target is G stereo frames
+ * t at the session's rate `rate_s` (given at `rate` Hz, they are converted first as step 1 converts the IR, and G is the count
+ * after that):
+ *   Nfft = max(16, smallest power of two >= 2 max(F, G)); above 2^22 is refused.  A_c, T_c = the transforms of a_c and t_c
+ *   zero-padded; Pa_c[k] = |A_c[k]|^2 and Pt_c[k] = |T_c[k]|^2 for k = 0 .. Nfft / 2;
+ *   grid:    f_j = lo_hz 2^(j / per_octave) for j = 0, 1, .. while that double is <= hi_hz (mc_response_grid's rule): J points,
+ *            2 <= J <= 1024;
+ *   window:  k_lo = ceil(f_j 2^(-octaves / 2) Nfft / rate_s), k_hi = floor(f_j 2^(octaves / 2) Nfft / rate_s), both clipped to
+ *            [1, Nfft / 2]; when k_lo > k_hi both are round-to-nearest(f_j Nfft / rate_s), clipped the same way;
+ *   levels:  Sa_c[j] = the mean of Pa_c over the window, St_c[j] likewise; with MC_MATCH_FLAT there is no target and
+ *            St_c[j] = 10^(tilt_db log2(f_j / 1000) / 10): tilt_db 0 whitens, -3 aims at pink.  With link the two channels'
+ *            levels are added before anything else and one curve serves both channels, so the stereo image keeps its balance;
+ *   floor:   S = max(S, max_j S 10^(-floor_db / 10)), for Sa and St separately.  A source channel whose frames are all zero is
+ *            stored as zeros; when the source or the target of a curve is all zeros (of a linked curve: both channels) the
+ *            curve is 0 dB throughout;
+ *   curve:   raw[j] = 10 log10(St[j] / Sa[j]); m = the mean of raw, added in ascending j; d[j] = clamp(amount (raw[j] - m),
+ *            -cut_db, +boost_db); a point counts as clamped when amount (raw[j] - m) lies outside that range;
+ *   per bin, k = 0 .. Nfft / 2: u = per_octave log2(k rate_s / Nfft / lo_hz) clipped to [0, J - 1] (k = 0: u = 0),
+ *            i = min(floor(u), J - 2), dB = d[i] + (u - i) (d[i + 1] - d[i]), L[k] = dB ln 10 / 20: flat outside [lo_hz, hi_hz];
+ *   MC_MATCH_MINIMUM: the phase step's recipe on L mirrored to Nfft points: c = Re IFFT(L); c[0] and c[Nfft / 2] kept,
+ *            c[1 .. Nfft / 2) doubled, the rest zero; C = exp(FFT(c)); Fo = F;
+ *   MC_MATCH_LINEAR:  C[k] = exp(L[k]) e^(-2 pi i k D / Nfft), D = delay, the angle reduced as (k D mod Nfft) first;
+ *            Fo = F + D, and F + D <= Nfft;
+ *   Y_c = A_c C_c; y = Re IFFT(Y); the step's output is y[0 .. Fo), rounded to float once.
+ * The step is circular over Nfft points.  The library carries both channels through one complex transform (L + i R), so a
+ * channel's bits depend on the other channel below the last place of a double; every window's sum is made in an order that
+ * depends on (k_lo, k_hi) alone.  The same frames, target and struct store the same bits on every run.
+ * Synthesised loads (mc_synth_ir and the room entry points) have no match entry point. */
+enum { MC_MATCH_OFF = 0, MC_MATCH_TARGET = 1, MC_MATCH_FLAT = 2 };
+enum { MC_MATCH_MINIMUM = 0, MC_MATCH_LINEAR = 1 };
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_ir_match) = 80 */
+    uint32_t mode;          /* MC_MATCH_OFF / TARGET / FLAT; MC_MATCH_OFF: every other field ignored */
+    uint32_t phase;         /* MC_MATCH_MINIMUM / LINEAR */
+    uint32_t link;          /* 0 or 1; default 1: one curve for both channels */
+    uint32_t rate;          /* Hz of the target's frames, [8000, 384000]; 0 = the session's */
+    uint32_t per_octave;    /* [1, 96]; default 12 */
+    double lo_hz, hi_hz;    /* 1 <= lo_hz < hi_hz <= session rate / 2; default 20 and 0 = min(20000, session rate / 2) */
+    double octaves;         /* the windows' width, [1/24, 2]; default 1/3 */
+    float amount;           /* [0, 1]; default 1 */
+    float boost_db, cut_db; /* [0, 60]; default 12 and 24 */
+    float floor_db;         /* [40, 300]; default 120 */
+    float tilt_db;          /* dB per octave of MC_MATCH_FLAT's line, [-12, 12]; default 0; checked always */
+    uint32_t delay;         /* D of MC_MATCH_LINEAR in frames, <= 2^20; checked always */
+    uint32_t reserved[2];   /* must be 0 */
+} mc_ir_match;
+/* off; minimum phase; linked; rate 0; 12 per octave from 20 Hz to min(20000, session rate / 2); a third of an octave; amount 1;
+ * boost 12, cut 24, floor 120; tilt 0; delay 0 */
+void mc_default_ir_match(mc_ir_match *m);
+/* What the step would do to `frames` frames with a target of `target_frames` frames (ignored with MC_MATCH_FLAT), both at
+ * session_rate Hz (`rate` is checked and not used), host arithmetic only: out = {Nfft, passes per transform (1 or 2), bytes of
+ * device memory the step allocates while it runs, Fo, J, the sum of the J windows' widths in bins}.  MC_ERR_ARG for a null
+ * pointer, a field of `m` outside its range (MC_MATCH_OFF is planned as MC_MATCH_TARGET), frames = 0, or the limits below. */
+int mc_ir_match_plan(const mc_ir_match *m, uint64_t frames, uint64_t target_frames, uint32_t session_rate, double out[6]);
+/* mc_load_ir_filter with `match` applied as step 1d, the target being the `target_frames` interleaved stereo frames at
+ * target_lr.  With match NULL or MC_MATCH_OFF the call is mc_load_ir_filter itself, bit for bit; it leaves no match
+ * information and does not look at target_lr.  With the step on everything is checked before the engine or the device is
+ * touched (MC_ERR_ARG, the message names the field, the engine stays as it was): match field by field in the struct's order,
+ * then everything mc_load_ir_filter checks, in its order.  The step's limits come as soon as F is known, after the filter
+ * step's: a session_rate of 0 (the grid is in Hz), hi_hz above half the session's rate, J outside [2, 1024], target_frames = 0
+ * (or above 2^40) with MC_MATCH_TARGET, Nfft above 2^22 (the message names the frames), F + delay above Nfft.  A null target_lr
+ * with MC_MATCH_TARGET comes last, before the load's own null engine.  Such a load counts as shaped: mc_ir_shape_info's out[0]
+ * is Fo. */
+int mc_load_ir_match(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
+                     uint32_t session_rate, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp, const mc_ir_tail *tail,
+                     const mc_ir_phase *phase, const mc_ir_filter *filter, const float *filter_lr, uint64_t filter_frames,
+                     const mc_ir_match *match, const float *target_lr, uint64_t target_frames);
+/* mc_load_ir_sweep_filter with `match` applied to the deconvolved frames after the filter step; the session's rate is the
+ * sweep's.  match NULL or MC_MATCH_OFF: mc_load_ir_sweep_filter itself, bit for bit.  With the step on: match field by field,
+ * then everything mc_load_ir_sweep_filter checks, in its order, with the step's limits after the filter step's, and a null
+ * target_lr after the null filter_lr. */
+int mc_load_ir_sweep_match(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, const mc_sweep *sweep,
+                           int64_t offset, uint64_t ir_frames, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp,
+                           const mc_ir_tail *tail, const mc_ir_phase *phase, const mc_ir_filter *filter, const float *filter_lr,
+                           uint64_t filter_frames, const mc_ir_match *match, const float *target_lr, uint64_t target_frames);
+/* out = {F, G, Fo, Nfft, J, E_in, E_target, E_out, E_rest, mean removed L, mean removed R, clamped points}: G and E_target are
+ * 0 with MC_MATCH_FLAT; E_in = the sum over both channels of the squared frames that went in, E_target that of the target's,
+ * E_out that of the Fo frames as stored, in float, and E_rest that of y[Fo .. Nfft), in double, which the step left behind;
+ * the means are m of either channel's curve in dB (the same number when linked); the clamped points are counted over the
+ * curves there are, one when linked and two otherwise.  The sums are made of one partial per 256 frames, added in ascending
+ * order.  MC_ERR_STATE unless the IR's last load had the step on. */
+int mc_ir_match_info(const mc_engine *e, uint64_t idx, double out[12]);
+/* The curve of IR idx's last load: hz[j] = f_j, before_db[2 j + c] = raw[j] - m and gain_db[2 j + c] = d[j] of channel c
+ * (both channels hold the same numbers when linked), j < J.  Returns J; MC_ERR_ARG for a null pointer or cap < J (hz holds cap
+ * numbers, before_db and gain_db 2 cap each); MC_ERR_STATE unless the IR's last load had the step on. */
+int mc_ir_match_curve(const mc_engine *e, uint64_t idx, double *hz, double *before_db, double *gain_db, uint32_t cap);
 
 /* The reflections of a rectangular room (Allen and Berkley's image-source method), added on the device to the frames
  * mc_ir_synth describes: the room itself - its size, where the source and the two receivers stand, how hard the walls are -
