@@ -35,9 +35,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "fft64.hip.h"
-#include "irshape.hip.h"
-#include "resample.hip.h"
+#include "irspectral.hip.h"
 
 constexpr int FL_MAX_LOG2 = F64_MAX_LOG2;  // Nfft <= 2^22
 constexpr int FL_THREADS = ISH_THREADS;
@@ -48,10 +46,7 @@ struct FilterStep {
     uint32_t op, channels;
     double reg_db;
     Fft64Plan fft;
-    // where the filter's frames come from: `frames` host frames, converted on the device from rs[0] to rs[1] Hz when they differ
-    const float* lr;
-    uint64_t frames;
-    uint32_t rs[2];
+    SecondIr second;  // where the filter's frames come from
 };
 
 // z[i] = the frame x[i] as double for i < n, zero up to N; map = MC_FILTER_STEREO: (L, R), _LEFT: (L, 0), _MID: ((L + R) / 2, 0).
@@ -75,12 +70,6 @@ __global__ __launch_bounds__(FL_THREADS) void k_fl_pack(const float2* __restrict
         part[2 * (uint64_t)blockIdx.x] = s0;
         part[2 * (uint64_t)blockIdx.x + 1] = s1;
     }
-}
-
-// the two channels' bins k of Z = FFT(x_L + i x_R), x real, from a = Z[k] and b = Z[N - k]
-__device__ inline void fl_split(double2 a, double2 b, double2& l, double2& r) {
-    l = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
-    r = make_double2(0.5 * (a.y + b.y), -0.5 * (a.x - b.x));
 }
 
 __device__ inline double2 fl_mul(double2 a, double2 b) { return make_double2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x); }
@@ -236,17 +225,8 @@ inline const char* filter_check(const mc_ir_filter* f) {
     return nullptr;
 }
 
-// the filter's G frames at the session's rate, of filter_frames at f's rate (0 = the session's; filter_frames <= 2^40)
-inline uint64_t filter_frames_at(const mc_ir_filter* f, uint32_t session_rate, uint64_t filter_frames) {
-    return f->rate && f->rate != session_rate ? rs_out_frames(rs_geom(f->rate, session_rate), filter_frames) : filter_frames;
-}
-
 // log2 of the transform of F + G - 1 points
-inline int filter_log2(uint64_t F, uint64_t G) {
-    int lg = F64_MIN_LOG2;
-    while ((1ull << lg) < F + G - 1) lg++;
-    return lg;
-}
+inline int filter_log2(uint64_t F, uint64_t G) { return spec_ceil_log2(F + G - 1, F64_MIN_LOG2); }
 
 // the limits of a checked filter step over F frames and G filter frames at the session's rate: G >= 1, Nfft <= 2^22, and
 // frames_out within what the transform holds (F = 0 is the load's own "empty IR")
@@ -283,7 +263,7 @@ inline const char* filter_check_load(const mc_ir_filter* f, uint32_t session_rat
         std::snprintf(msg, sizeof(msg), "filter of %llu frames (filter_frames)", (unsigned long long)filter_frames);
         return msg;
     }
-    *G = filter_frames_at(f, session_rate, filter_frames);
+    *G = second_frames_at(f->rate, session_rate, filter_frames);
     return filter_check_frames(f, F, *G);
 }
 
@@ -292,44 +272,28 @@ inline const char* filter_check_load(const mc_ir_filter* f, uint32_t session_rat
 inline FilterStep filter_step(const mc_ir_filter& f, uint64_t F, uint64_t G) {
     const int lg = filter_log2(std::max<uint64_t>(F, 1), std::max<uint64_t>(G, 1));
     const uint64_t Fo = f.frames_out ? f.frames_out : f.op == MC_FILTER_DECONVOLVE ? F : F + G - 1;
-    return FilterStep{F, G, Fo, 1ull << lg, f.op, f.channels, (double)f.reg_db, fft64_plan(lg), nullptr, 0, {0, 0}};
+    return FilterStep{F, G, Fo, 1ull << lg, f.op, f.channels, (double)f.reg_db, fft64_plan(lg), SecondIr{}};
 }
-
-inline uint64_t filter_groups(uint64_t n) { return (n + FL_THREADS - 1) / FL_THREADS; }
 
 // what filter_run allocates on the device while it runs: the filter's G frames, two buffers of Nfft double2, a third when the
 // transform has two passes, and the partials (the resampler's own temporaries for a filter at another rate are not counted)
-inline uint64_t filter_device_bytes(const FilterStep& s) {
-    return 8 * s.G + (s.fft.passes == 2 ? 3 : 2) * 16 * s.Nfft + 16 * filter_groups(s.Nfft);
-}
+inline uint64_t filter_device_bytes(const FilterStep& s) { return 8 * s.G + spec_work_bytes(s.fft, s.Nfft); }
 
 // Step 1c: the s.Fo frames d_y from the s.F frames d_x and the filter's host frames, on the stream, after what the stream
-// already holds.  Allocates the work buffers, waits for the kernels and frees them.  info = mc_ir_filter_info's ten numbers.
+// already holds.  Allocates the work buffers (SpectralWork), waits for the kernels and frees them.  info = mc_ir_filter_info's ten numbers.
 inline hipError_t filter_run(hipStream_t stream, const float2* d_x, float2* d_y, const FilterStep& s, double info[10]) {
-    const uint64_t F = s.F, G = s.G, Fo = s.Fo, N = s.Nfft, gF = filter_groups(F), gG = filter_groups(G), gN = filter_groups(N);
-    const uint64_t gH = filter_groups(N / 2 + 1);
+    const uint64_t F = s.F, G = s.G, Fo = s.Fo, N = s.Nfft, gF = spec_groups(F), gG = spec_groups(G), gN = spec_groups(N);
+    const uint64_t gH = spec_groups(N / 2 + 1);
     const bool mono = s.channels != MC_FILTER_STEREO;
     float2* d_f = nullptr;
-    double2 *d_a = nullptr, *d_b = nullptr, *d_w = nullptr;
-    double* d_part = nullptr;
-    std::vector<double> part(2 * (size_t)gN);
+    SpectralWork wk;
     hipError_t er = hipMalloc(&d_f, sizeof(float2) * G);
-    if (er == hipSuccess) er = hipMalloc(&d_a, sizeof(double2) * N);
-    if (er == hipSuccess) er = hipMalloc(&d_b, sizeof(double2) * N);
-    if (er == hipSuccess && s.fft.passes == 2) er = hipMalloc(&d_w, sizeof(double2) * N);
-    if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * 2 * gN);
-    if (er == hipSuccess) {
-        double unused[4];
-        er = s.rs[0] != s.rs[1] ? rs_convert(stream, s.rs[0], s.rs[1], s.lr, s.frames, d_f, G, unused)
-                                : hipMemcpy(d_f, s.lr, sizeof(float2) * G, hipMemcpyHostToDevice);
-    }
-    // the first `count` partials, once the stream has run dry
-    const auto fetch = [&](uint64_t count) {
-        hipError_t e2 = hipGetLastError();
-        if (e2 == hipSuccess) e2 = hipMemcpyAsync(part.data(), d_part, sizeof(double) * count, hipMemcpyDeviceToHost, stream);
-        if (e2 == hipSuccess) e2 = hipStreamSynchronize(stream);
-        return e2;
-    };
+    if (er == hipSuccess) er = wk.alloc(s.fft, N);
+    if (er == hipSuccess) er = second_upload(stream, s.second, d_f, G);
+    double2 *const d_a = wk.d_a, *const d_b = wk.d_b, *const d_w = wk.d_w;
+    double* const d_part = wk.d_part;
+    const std::vector<double>& part = wk.part;
+    const auto fetch = [&](uint64_t count) { return wk.fetch(stream, count); };
     // A filter channel whose frames are all zero has pm = 0; the packed transform leaves rounding noise of the other channel in
     // its spectrum, so its energy before the transform decides (zero exactly when every frame is), not the maximum after it.
     double Ein = 0.0, Ef[2] = {0.0, 0.0}, Eout = 0.0, Erest = 0.0, pm[2] = {0.0, 0.0}, reg[2] = {0.0, 0.0};
@@ -393,9 +357,5 @@ inline hipError_t filter_run(hipStream_t stream, const float2* d_x, float2* d_y,
         (void)hipStreamSynchronize(stream);
     }
     (void)hipFree(d_f);
-    (void)hipFree(d_a);
-    (void)hipFree(d_b);
-    (void)hipFree(d_w);
-    (void)hipFree(d_part);
     return er;
 }

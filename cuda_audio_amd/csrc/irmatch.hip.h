@@ -42,11 +42,9 @@
 #include <cstring>
 #include <vector>
 
-#include "fft64.hip.h"
 #include "irfilter.hip.h"
 #include "irphase.hip.h"
-#include "irshape.hip.h"
-#include "resample.hip.h"
+#include "irspectral.hip.h"
 
 constexpr int MT_MAX_LOG2 = F64_MAX_LOG2;  // Nfft <= 2^22
 constexpr int MT_THREADS = ISH_THREADS;
@@ -63,10 +61,7 @@ struct MatchStep {
     std::vector<double> hz;     // f_j
     std::vector<uint32_t> win;  // k_lo, k_hi of point j at [2 j], [2 j + 1]
     uint64_t window_bins = 0;   // the sum of the windows' widths
-    // where the target's frames come from: `frames` host frames, converted on the device from rs[0] to rs[1] Hz when they differ
-    const float* lr = nullptr;
-    uint64_t frames = 0;
-    uint32_t rs[2] = {0, 0};
+    SecondIr second;            // where the target's frames come from
 };
 
 // what match_run hands back beside the taps: mc_ir_match_info's twelve numbers and mc_ir_match_curve's arrays
@@ -262,12 +257,7 @@ inline uint32_t match_grid(double lo, double hi, uint32_t per_octave, std::vecto
 }
 
 // log2 of the transform: max(16, smallest power of two >= 2 max(F, G)); above MT_MAX_LOG2 when that is too long
-inline int match_log2(uint64_t F, uint64_t G) {
-    const uint64_t n = std::max(F, G);
-    int lg = F64_MIN_LOG2;
-    while (lg <= MT_MAX_LOG2 && (1ull << lg) < 2 * n) lg++;
-    return lg;
-}
+inline int match_log2(uint64_t F, uint64_t G) { return spec_ceil_log2(2 * std::max(F, G), F64_MIN_LOG2); }
 
 // The limits of a checked match step in a load whose F frames at the session's rate are known, in the documented order: the
 // session's rate, hi_hz, the grid, the target's frames (target_frames at m's rate become *G at the session's), Nfft, delay.
@@ -297,7 +287,7 @@ inline const char* match_check_load(const mc_ir_match* m, uint32_t session_rate,
             std::snprintf(msg, sizeof(msg), "target of %llu frames (target_frames)", (unsigned long long)target_frames);
             return msg;
         }
-        *G = m->rate && m->rate != session_rate ? rs_out_frames(rs_geom(m->rate, session_rate), target_frames) : target_frames;
+        *G = second_frames_at(m->rate, session_rate, target_frames);
     }
     const int lg = match_log2(F, *G);
     if (lg > MT_MAX_LOG2) {
@@ -337,16 +327,14 @@ inline MatchStep match_step(const mc_ir_match& m, uint32_t session_rate, uint64_
     return s;
 }
 
-inline uint64_t match_groups(uint64_t n) { return (n + MT_THREADS - 1) / MT_THREADS; }
-
 // the length of one signal's stretch of powers: Nfft / 2 + 1 bins, rounded up to whole rows of 256
-inline uint64_t match_stride(const MatchStep& s) { return match_groups(s.Nfft / 2 + 1) * MT_THREADS; }
+inline uint64_t match_stride(const MatchStep& s) { return spec_groups(s.Nfft / 2 + 1) * MT_THREADS; }
 
 // what match_run allocates on the device while it runs: the target's G frames, two buffers of Nfft double2 and a third when
 // the transform has two passes, the two stretches of powers (which hold the correction's spectrum afterwards), the partials,
 // the window table, the sums and the curve (the resampler's own temporaries for a target at another rate are not counted)
 inline uint64_t match_device_bytes(const MatchStep& s) {
-    return 8 * s.G + (s.fft.passes == 2 ? 3 : 2) * 16 * s.Nfft + 2 * 16 * match_stride(s) + 16 * match_groups(s.Nfft) + 8 * s.J + 2 * 16 * s.J + 16 * s.J;
+    return 8 * s.G + spec_work_bytes(s.fft, s.Nfft) + 2 * 16 * match_stride(s) + 8 * s.J + 2 * 16 * s.J + 16 * s.J;
 }
 
 // The curve on the J points, host arithmetic in double.  S = the four sums per point as k_mt_smooth left them: (L, R) of the
@@ -398,40 +386,30 @@ inline void match_curve(const MatchStep& s, const double* S, const double Ea[2],
 }
 
 // Step 1d: the s.Fo frames d_y from the s.F frames d_x and the target's host frames, on the stream, after what the stream
-// already holds.  Allocates the work buffers, waits for the kernels and frees them.
+// already holds.  Allocates the work buffers (SpectralWork and its own), waits for the kernels and frees them.
 inline hipError_t match_run(hipStream_t stream, const float2* d_x, float2* d_y, const MatchStep& s, MatchFacts* facts) {
-    const uint64_t F = s.F, G = s.G, Fo = s.Fo, N = s.Nfft, gF = match_groups(F), gG = match_groups(G), gN = match_groups(N);
-    const uint64_t gH = match_groups(N / 2 + 1), stride = match_stride(s);
+    const uint64_t F = s.F, G = s.G, Fo = s.Fo, N = s.Nfft, gF = spec_groups(F), gG = spec_groups(G), gN = spec_groups(N);
+    const uint64_t gH = spec_groups(N / 2 + 1), stride = match_stride(s);
     const uint32_t J = s.J;
     const bool target = s.mode == MC_MATCH_TARGET;
     const int two = s.link ? 0 : 1;
     float2* d_t = nullptr;
-    double2 *d_a = nullptr, *d_b = nullptr, *d_w = nullptr, *d_P = nullptr, *d_S = nullptr, *d_d = nullptr;
+    double2 *d_P = nullptr, *d_S = nullptr, *d_d = nullptr;
     uint2* d_win = nullptr;
-    double* d_part = nullptr;
-    std::vector<double> part(2 * (size_t)gN), S(8 * (size_t)J, 0.0);
+    std::vector<double> S(8 * (size_t)J, 0.0);
+    SpectralWork wk;
     hipError_t er = target ? hipMalloc(&d_t, sizeof(float2) * G) : hipSuccess;
-    if (er == hipSuccess) er = hipMalloc(&d_a, sizeof(double2) * N);
-    if (er == hipSuccess) er = hipMalloc(&d_b, sizeof(double2) * N);
-    if (er == hipSuccess && s.fft.passes == 2) er = hipMalloc(&d_w, sizeof(double2) * N);
+    if (er == hipSuccess) er = wk.alloc(s.fft, N);
     if (er == hipSuccess) er = hipMalloc(&d_P, sizeof(double2) * 2 * stride);
-    if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * 2 * gN);
     if (er == hipSuccess) er = hipMalloc(&d_win, sizeof(uint2) * J);
     if (er == hipSuccess) er = hipMalloc(&d_S, sizeof(double2) * 2 * J);
     if (er == hipSuccess) er = hipMalloc(&d_d, sizeof(double2) * J);
     if (er == hipSuccess) er = hipMemcpy(d_win, s.win.data(), sizeof(uint2) * J, hipMemcpyHostToDevice);
-    if (er == hipSuccess && target) {
-        double unused[4];
-        er = s.rs[0] != s.rs[1] ? rs_convert(stream, s.rs[0], s.rs[1], s.lr, s.frames, d_t, G, unused)
-                                : hipMemcpy(d_t, s.lr, sizeof(float2) * G, hipMemcpyHostToDevice);
-    }
-    // the first `count` partials, once the stream has run dry
-    const auto fetch = [&](uint64_t count) {
-        hipError_t e2 = hipGetLastError();
-        if (e2 == hipSuccess) e2 = hipMemcpyAsync(part.data(), d_part, sizeof(double) * count, hipMemcpyDeviceToHost, stream);
-        if (e2 == hipSuccess) e2 = hipStreamSynchronize(stream);
-        return e2;
-    };
+    if (er == hipSuccess && target) er = second_upload(stream, s.second, d_t, G);
+    double2 *const d_a = wk.d_a, *const d_b = wk.d_b, *const d_w = wk.d_w;
+    double* const d_part = wk.d_part;
+    const std::vector<double>& part = wk.part;
+    const auto fetch = [&](uint64_t count) { return wk.fetch(stream, count); };
     // A channel whose frames are all zero is recognised from its energy before the transform: the packed transform leaves
     // rounding noise of the other channel in its spectrum (irfilter.hip.h has the same device).
     double Ea[2] = {0.0, 0.0}, Et[2] = {0.0, 0.0}, Eout = 0.0, Erest = 0.0, mean[2] = {0.0, 0.0};
@@ -509,11 +487,7 @@ inline hipError_t match_run(hipStream_t stream, const float2* d_x, float2* d_y, 
         (void)hipStreamSynchronize(stream);
     }
     (void)hipFree(d_t);
-    (void)hipFree(d_a);
-    (void)hipFree(d_b);
-    (void)hipFree(d_w);
     (void)hipFree(d_P);
-    (void)hipFree(d_part);
     (void)hipFree(d_win);
     (void)hipFree(d_S);
     (void)hipFree(d_d);

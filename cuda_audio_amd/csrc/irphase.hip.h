@@ -26,8 +26,7 @@
 #include <cstdio>
 #include <cstring>
 
-#include "fft64.hip.h"
-#include "irshape.hip.h"
+#include "irspectral.hip.h"
 
 constexpr uint64_t PH_MAX_FRAMES = 1ull << 21;
 constexpr int PH_MAX_LOG2 = F64_MAX_LOG2;  // Nfft <= 2^22
@@ -62,13 +61,6 @@ __global__ __launch_bounds__(PH_THREADS) void k_ph_pack(const float2* __restrict
     }
 }
 
-// the two channels' bins k of Z = FFT(a_L + i a_R), a real: (Z[k] + conj Z[N - k]) / 2 and (Z[k] - conj Z[N - k]) / (2 i)
-__device__ inline void ph_split(const double2* __restrict__ Z, uint64_t k, uint64_t N, double2& l, double2& r) {
-    const double2 a = Z[k], b = Z[(N - k) & (N - 1)];
-    l = make_double2(0.5 * (a.x + b.x), 0.5 * (a.y - b.y));
-    r = make_double2(0.5 * (a.y + b.y), -0.5 * (a.x - b.x));
-}
-
 // P[k] = (|X_L[k]|^2, |X_R[k]|^2); part[2 b], part[2 b + 1] = the workgroup's maxima
 __global__ __launch_bounds__(PH_THREADS) void k_ph_power(const double2* __restrict__ Z, uint64_t N, double2* __restrict__ P, double* __restrict__ part) {
     __shared__ double red[ISH_WAVES];
@@ -76,7 +68,7 @@ __global__ __launch_bounds__(PH_THREADS) void k_ph_power(const double2* __restri
     double2 p = make_double2(0.0, 0.0);
     if (k < N) {
         double2 l, r;
-        ph_split(Z, k, N, l, r);
+        fl_split(Z[k], Z[(N - k) & (N - 1)], l, r);
         p = make_double2(l.x * l.x + l.y * l.y, r.x * r.x + r.y * r.y);
         P[k] = p;
     }
@@ -128,7 +120,7 @@ __global__ __launch_bounds__(PH_THREADS) void k_ph_exp(const double2* __restrict
     const uint64_t k = (uint64_t)blockIdx.x * PH_THREADS + threadIdx.x;
     if (k >= N) return;
     double2 l, r;
-    ph_split(Z, k, N, l, r);
+    fl_split(Z[k], Z[(N - k) & (N - 1)], l, r);
     const double2 yl = ph_cexp(l), yr = ph_cexp(r);
     Y[k] = make_double2(yl.x - yr.y, yl.y + yr.x);
 }
@@ -174,13 +166,6 @@ inline const char* phase_check(const mc_ir_phase* p) {
     return nullptr;
 }
 
-// log2 of the smallest power of two >= F (F >= 1)
-inline int phase_ceil_log2(uint64_t F) {
-    int lg = 0;
-    while ((1ull << lg) < F) lg++;
-    return lg;
-}
-
 // the limits of a checked phase step over F frames: F <= 2^21 and Nfft <= 2^22 (F = 0 is the load's own "empty IR")
 inline const char* phase_check_frames(const mc_ir_phase* p, uint64_t F) {
     static thread_local char msg[200];
@@ -189,9 +174,9 @@ inline const char* phase_check_frames(const mc_ir_phase* p, uint64_t F) {
                       (unsigned long long)F);
         return msg;
     }
-    if (F && phase_ceil_log2(F) + (int)p->over_log2 > PH_MAX_LOG2) {
+    if (F && spec_ceil_log2(F) + (int)p->over_log2 > PH_MAX_LOG2) {
         std::snprintf(msg, sizeof(msg), "over_log2 %u with %llu frames needs a transform of 2^%d points, above 2^%d", p->over_log2,
-                      (unsigned long long)F, phase_ceil_log2(F) + (int)p->over_log2, PH_MAX_LOG2);
+                      (unsigned long long)F, spec_ceil_log2(F) + (int)p->over_log2, PH_MAX_LOG2);
         return msg;
     }
     return nullptr;
@@ -199,33 +184,22 @@ inline const char* phase_check_frames(const mc_ir_phase* p, uint64_t F) {
 
 // a checked phase step that is on, over F frames within the limits
 inline PhaseStep phase_step(const mc_ir_phase& p, uint64_t F) {
-    const int lg = std::max(F64_MIN_LOG2, phase_ceil_log2(std::max<uint64_t>(F, 1)) + (int)p.over_log2);
+    const int lg = std::max(F64_MIN_LOG2, spec_ceil_log2(std::max<uint64_t>(F, 1)) + (int)p.over_log2);
     return PhaseStep{F, 1ull << lg, (double)p.floor_db, fft64_plan(lg)};
 }
 
-inline uint64_t phase_groups(uint64_t n) { return (n + PH_THREADS - 1) / PH_THREADS; }
-
 // what phase_run allocates on the device: two buffers of Nfft double2, a third when the transform has two passes, and the partials
-inline uint64_t phase_device_bytes(const PhaseStep& s) { return (s.fft.passes == 2 ? 3 : 2) * 16 * s.Nfft + 16 * phase_groups(s.Nfft); }
+inline uint64_t phase_device_bytes(const PhaseStep& s) { return spec_work_bytes(s.fft, s.Nfft); }
 
 // Step 1b: the s.F frames d_y from the s.F frames d_x, on the stream, after what the stream already holds.  Allocates the work
-// buffers, waits for the kernels and frees them.  info = mc_ir_phase_info's eight numbers.
+// buffers (SpectralWork), waits for the kernels and frees them.  info = mc_ir_phase_info's eight numbers.
 inline hipError_t phase_run(hipStream_t stream, const float2* d_x, float2* d_y, const PhaseStep& s, double info[8]) {
-    const uint64_t F = s.F, N = s.Nfft, gF = phase_groups(F), gN = phase_groups(N);
-    double2 *d_a = nullptr, *d_b = nullptr, *d_w = nullptr;
-    double* d_part = nullptr;
-    std::vector<double> part(2 * (size_t)gN);
-    hipError_t er = hipMalloc(&d_a, sizeof(double2) * N);
-    if (er == hipSuccess) er = hipMalloc(&d_b, sizeof(double2) * N);
-    if (er == hipSuccess && s.fft.passes == 2) er = hipMalloc(&d_w, sizeof(double2) * N);
-    if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * 2 * gN);
-    // the partials of `groups` workgroups, once the stream has run dry
-    const auto fetch = [&](uint64_t groups) {
-        hipError_t e2 = hipGetLastError();
-        if (e2 == hipSuccess) e2 = hipMemcpyAsync(part.data(), d_part, sizeof(double) * 2 * groups, hipMemcpyDeviceToHost, stream);
-        if (e2 == hipSuccess) e2 = hipStreamSynchronize(stream);
-        return e2;
-    };
+    const uint64_t F = s.F, N = s.Nfft, gF = spec_groups(F), gN = spec_groups(N);
+    SpectralWork wk;
+    hipError_t er = wk.alloc(s.fft, N);
+    double2 *const d_a = wk.d_a, *const d_b = wk.d_b, *const d_w = wk.d_w;
+    double* const d_part = wk.d_part;
+    const std::vector<double>& part = wk.part;
     // sum e and sum m e over `groups` partial pairs, in index order
     const auto sums = [&](uint64_t groups, double& E, double& T) {
         E = T = 0.0;
@@ -235,7 +209,7 @@ inline hipError_t phase_run(hipStream_t stream, const float2* d_x, float2* d_y, 
     unsigned long long clamped[2] = {0, 0};
     if (er == hipSuccess) {
         hipLaunchKernelGGL(k_ph_pack, dim3((unsigned)gN), dim3(PH_THREADS), 0, stream, d_x, F, N, d_a, d_part);
-        er = fetch(gF);
+        er = wk.fetch(stream, 2 * gF);
     }
     if (er == hipSuccess) {
         sums(gF, Ein, Tin);
@@ -243,14 +217,14 @@ inline hipError_t phase_run(hipStream_t stream, const float2* d_x, float2* d_y, 
     }
     if (er == hipSuccess) {
         hipLaunchKernelGGL(k_ph_power, dim3((unsigned)gN), dim3(PH_THREADS), 0, stream, d_a, N, d_b, d_part);
-        er = fetch(gN);
+        er = wk.fetch(stream, 2 * gN);
     }
     if (er == hipSuccess) {
         for (uint64_t b = 0; b < gN; b++) pm[0] = std::max(pm[0], part[2 * b]), pm[1] = std::max(pm[1], part[2 * b + 1]);
         const double rel = std::pow(10.0, -s.floor_db / 10.0);
         hipLaunchKernelGGL(k_ph_log, dim3((unsigned)gN), dim3(PH_THREADS), 0, stream, d_b, N, pm[0] * rel, pm[1] * rel, (int)(pm[0] > 0.0),
                            (int)(pm[1] > 0.0), reinterpret_cast<unsigned long long*>(d_part));
-        er = fetch(gN);
+        er = wk.fetch(stream, 2 * gN);
     }
     if (er == hipSuccess) {
         for (uint64_t b = 0; b < 2 * gN; b++) {
@@ -272,7 +246,7 @@ inline hipError_t phase_run(hipStream_t stream, const float2* d_x, float2* d_y, 
     if (er == hipSuccess) er = fft64_run(stream, s.fft, d_a, d_a, d_w, true);
     if (er == hipSuccess) {
         hipLaunchKernelGGL(k_ph_unpack, dim3((unsigned)gF), dim3(PH_THREADS), 0, stream, d_a, F, (int)(pm[0] > 0.0), (int)(pm[1] > 0.0), d_y, d_part);
-        er = fetch(gF);
+        er = wk.fetch(stream, 2 * gF);
     }
     if (er == hipSuccess) {
         sums(gF, Eout, Tout);
@@ -281,9 +255,5 @@ inline hipError_t phase_run(hipStream_t stream, const float2* d_x, float2* d_y, 
     } else {
         (void)hipStreamSynchronize(stream);
     }
-    (void)hipFree(d_a);
-    (void)hipFree(d_b);
-    (void)hipFree(d_w);
-    (void)hipFree(d_part);
     return er;
 }

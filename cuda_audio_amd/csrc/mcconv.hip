@@ -3399,57 +3399,25 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
                     : ld.syn ? syn_generate(e->stream, *ld.syn, d_x)
                     : ld.rs ? rs_convert(e->stream, ld.rs[0], ld.rs[1], ld.lr, ld.frames, d_x, conv, unused)
                             : hipMemcpy(d_x, ld.lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
-    if (er == hipSuccess && ld.tail) {
+    // one step: its Fo frames into a buffer of their own, which then takes d_x's place (run waits for the stream: d_x is free after it)
+    const auto step = [&](uint64_t Fo, auto&& run) {
+        if (er != hipSuccess) return;
         float2* d_y = nullptr;
-        er = hipMalloc(&d_y, sizeof(float2) * ld.tail->plan.Fp);
-        if (er == hipSuccess) er = tail_run(e->stream, d_x, d_y, ld.tail->plan, ld.tail->extend);  // (waits for the stream: d_x is free after it)
+        er = hipMalloc(&d_y, sizeof(float2) * Fo);
+        if (er == hipSuccess) er = run(d_y);
         if (er == hipSuccess) {
             (void)hipFree(d_x);
             d_x = d_y;
-            conv = ld.tail->plan.Fp;
+            conv = Fo;
         } else {
             (void)hipStreamSynchronize(e->stream);
             (void)hipFree(d_y);
         }
-    }
-    if (er == hipSuccess && ld.phase) {
-        float2* d_y = nullptr;
-        er = hipMalloc(&d_y, sizeof(float2) * conv);
-        if (er == hipSuccess) er = phase_run(e->stream, d_x, d_y, *ld.phase, out->phase);  // (waits for the stream: d_x is free after it)
-        if (er == hipSuccess) {
-            (void)hipFree(d_x);
-            d_x = d_y;
-        } else {
-            (void)hipStreamSynchronize(e->stream);
-            (void)hipFree(d_y);
-        }
-    }
-    if (er == hipSuccess && ld.filter) {
-        float2* d_y = nullptr;
-        er = hipMalloc(&d_y, sizeof(float2) * ld.filter->Fo);
-        if (er == hipSuccess) er = filter_run(e->stream, d_x, d_y, *ld.filter, out->filter);  // (waits for the stream: d_x is free after it)
-        if (er == hipSuccess) {
-            (void)hipFree(d_x);
-            d_x = d_y;
-            conv = ld.filter->Fo;
-        } else {
-            (void)hipStreamSynchronize(e->stream);
-            (void)hipFree(d_y);
-        }
-    }
-    if (er == hipSuccess && ld.match) {
-        float2* d_y = nullptr;
-        er = hipMalloc(&d_y, sizeof(float2) * ld.match->Fo);
-        if (er == hipSuccess) er = match_run(e->stream, d_x, d_y, *ld.match, &out->match);  // (waits for the stream: d_x is free after it)
-        if (er == hipSuccess) {
-            (void)hipFree(d_x);
-            d_x = d_y;
-            conv = ld.match->Fo;
-        } else {
-            (void)hipStreamSynchronize(e->stream);
-            (void)hipFree(d_y);
-        }
-    }
+    };
+    if (ld.tail) step(ld.tail->plan.Fp, [&](float2* d_y) { return tail_run(e->stream, d_x, d_y, ld.tail->plan, ld.tail->extend); });
+    if (ld.phase) step(conv, [&](float2* d_y) { return phase_run(e->stream, d_x, d_y, *ld.phase, out->phase); });
+    if (ld.filter) step(ld.filter->Fo, [&](float2* d_y) { return filter_run(e->stream, d_x, d_y, *ld.filter, out->filter); });
+    if (ld.match) step(ld.match->Fo, [&](float2* d_y) { return match_run(e->stream, d_x, d_y, *ld.match, &out->match); });
     if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, *ld.shape, &out->d_taps, &out->n, out->sums, out->info, ld.eq, ld.damp);
     if (ld.swp && er != hipSuccess) (void)hipStreamSynchronize(e->stream);  // (the correlation may still be reading them)
     (void)hipFree(d_x);
@@ -3461,10 +3429,11 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
     return MC_OK;
 }
 
-// What the mc_ir_*_info getters report of the load `ld` that stored `taps` taps; sinfo = the shaping stage's numbers, pinfo
-// the phase step's (read with ld.phase), finfo the filter step's (read with ld.filter), match the match step's (read with ld.match).
-// Every kind is written, so nothing of an earlier load onto the same index stays behind.
-void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[8], const double pinfo[8], const double finfo[10], const MatchFacts& match) {
+// What the mc_ir_*_info getters report of the load `ld` that stored `taps` taps; st = what the shaping stage handed back, whose
+// numbers of a step are read when ld has that step.  Every kind is written, so nothing of an earlier load onto the same index
+// stays behind.
+void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const ShapedTaps& st) {
+    const double *sinfo = st.info, *pinfo = st.phase, *finfo = st.filter;
     for (IrFact& f : ir.facts) f.on = false;
     const auto put = [&ir](IrFactKind kind, std::initializer_list<double> v) {
         ir.facts[kind].on = true;
@@ -3486,9 +3455,9 @@ void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const double sinfo[
     if (ld.filter) put(FACT_FILTER, {finfo[0], finfo[1], finfo[2], finfo[3], finfo[4], finfo[5], finfo[6], finfo[7], finfo[8], finfo[9]});
     ir.match_curve.clear();
     if (ld.match) {
-        const double* m = match.info;
+        const double* m = st.match.info;
         put(FACT_MATCH, {m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8], m[9], m[10], m[11]});
-        ir.match_curve = match.curve;
+        ir.match_curve = st.match.curve;
     }
     if (ld.room) {
         const RoomPlan& r = ld.room->plan;
@@ -3531,7 +3500,7 @@ int load_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const IrLoad& ld) {
         const int rc = sf_load_ir(e, idx, lr, frames, nframes, rs, st.d_taps, st.n, st.sums);
         if (sh) (void)hipFree(d_lr);
         if (rc) return rc;
-        note_load(e->irs[idx], ld, st.n, st.info, st.phase, st.filter, st.match);
+        note_load(e->irs[idx], ld, st.n, st);
         return MC_OK;
     }
     const uint64_t n = sh ? st.n : std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
@@ -3608,7 +3577,7 @@ int load_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const IrLoad& ld) {
     std::memcpy(ir.sums, s, sizeof(s));
     ir.taps = n;
     ir.P = P;
-    note_load(ir, ld, n, st.info, st.phase, st.filter, st.match);
+    note_load(ir, ld, n, st);
     if ((int)idx + 1 > e->nirs) e->nirs = (int)idx + 1;
     e->spec_valid = e->dspec.valid = false;
     e->uniform_valid[0] = e->uniform_valid[1] = false;
@@ -3688,6 +3657,155 @@ int measure(mc_engine* e, uint64_t idx, const char* name, Run&& run) {
 
 // the tail step of a checked mc_ir_tail that is on, over F frames at the session's rate
 TailStep tail_step(const mc_ir_tail& tail, uint32_t rate, uint64_t F) { return TailStep{tail_plan(tail, rate, F), tail.mode == MC_TAIL_EXTEND}; }
+
+// The arguments of steps 1a to 1d as an entry point receives them.  An entry point fills in by name what it takes; normalise()
+// is the one place that looks at the switches: a step that is off becomes a null pointer, whatever else its struct holds.
+struct StepRequest {
+    const mc_ir_tail* tail = nullptr;
+    const mc_ir_phase* phase = nullptr;
+    const mc_ir_filter* filter = nullptr;
+    const float* filter_lr = nullptr;
+    uint64_t filter_frames = 0;
+    const mc_ir_match* match = nullptr;
+    const float* target_lr = nullptr;
+    uint64_t target_frames = 0;
+    StepRequest& normalise() {
+        if (tail && tail->mode == MC_TAIL_OFF) tail = nullptr;
+        if (phase && phase->mode == MC_PHASE_OFF) phase = nullptr;
+        if (filter && filter->op == MC_FILTER_OFF) filter = nullptr;
+        if (match && match->mode == MC_MATCH_OFF) match = nullptr;
+        return *this;
+    }
+    bool any() const { return tail || phase || filter || match; }
+};
+
+// Steps 1a to 1d of a normalised request as load_ir takes them, beside IrSteps and in its manner.  The checks return the message
+// of the first one that fails, null when all pass; no engine and no HIP call.  The tail's own checks (tail_check,
+// tail_check_frames) stay with the source, which knows where among its own they belong.
+struct StepPlan {
+    TailStep tail{};
+    PhaseStep phase{};
+    FilterStep filter{};
+    MatchStep match;
+    uint64_t G = 0, Gm = 0;  // limits(): the filter's and the target's frames at the session's rate
+    bool tailed = false, phased = false, filtered = false, matched = false;
+
+    // the structs of the match, the filter and the phase, in that order
+    static const char* check_structs(const StepRequest& rq) {
+        if (rq.match)
+            if (const char* bad = match_check(rq.match)) return bad;
+        if (rq.filter)
+            if (const char* bad = filter_check(rq.filter)) return bad;
+        return rq.phase ? phase_check(rq.phase) : nullptr;
+    }
+    // the checked tail over F frames at the session's rate; the frames it hands on
+    uint64_t plan_tail(const mc_ir_tail& t, uint32_t session_rate, uint64_t F) {
+        tail = tail_step(t, session_rate, F), tailed = true;
+        return tail.plan.Fp;
+    }
+    // the limits of the steps that are on, over the F frames that reach them: the phase's, the filter's, the match's over what the filter hands on
+    const char* limits(const StepRequest& rq, uint64_t F, uint32_t session_rate) {
+        if (rq.phase)
+            if (const char* bad = phase_check_frames(rq.phase, F)) return bad;
+        if (rq.filter)
+            if (const char* bad = filter_check_load(rq.filter, session_rate, F, rq.filter_frames, &G)) return bad;
+        return rq.match ? match_check_load(rq.match, session_rate, rq.filter && F ? filter_step(*rq.filter, F, G).Fo : F, rq.target_frames, &Gm) : nullptr;
+    }
+    // the second IRs' frames: the filter's, and the target's when the match has one
+    static const char* pointers(const StepRequest& rq) {
+        if (rq.filter && !rq.filter_lr) return "null filter_lr";
+        return rq.match && rq.match->mode == MC_MATCH_TARGET && !rq.target_lr ? "null target_lr" : nullptr;
+    }
+    // the three spectral steps over the F frames that reach them, after limits(); a second IR's rate 0 is the session's
+    void plan(const StepRequest& rq, uint64_t F, uint32_t session_rate) {
+        phased = rq.phase, filtered = rq.filter, matched = rq.match;
+        if (rq.phase) phase = phase_step(*rq.phase, F);
+        if (rq.filter) filter = filter_step(*rq.filter, F, G), filter.second = second_ir(rq.filter_lr, rq.filter_frames, rq.filter->rate, session_rate);
+        if (rq.match && F) match = match_step(*rq.match, session_rate, rq.filter ? filter.Fo : F, Gm);
+        if (rq.match) match.second = second_ir(rq.target_lr, rq.target_frames, rq.match->rate, session_rate);
+    }
+    void into(IrLoad& ld) const {
+        ld.tail = tailed ? &tail : nullptr;
+        ld.phase = phased ? &phase : nullptr;
+        ld.filter = filtered ? &filter : nullptr;
+        ld.match = matched ? &match : nullptr;
+    }
+};
+
+// mc_load_ir_tail, _phase, _filter and _match behind their switches: a file's frames through the steps of rq, of which one is on.
+// All before the engine and before any HIP call: the structs of the match, the filter and the phase; with a tail the tail, the
+// rates, the frames and F', the steps' limits over F', then damp, eq and shape; without one damp, eq and shape as in
+// mc_load_ir_damped, the rates unless both are 0, the frames and the steps' limits; then the second IRs' pointers.
+int load_file_steps(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
+                    const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const StepRequest& rq) {
+    if (const char* bad = StepPlan::check_structs(rq)) return fail(MC_ERR_ARG, "%s", bad);
+    const auto rates = [&](const char* why) -> int {
+        for (int k = 0; k < 2; k++) {
+            const uint32_t r = k ? ir_rate : session_rate;
+            if (r < RS_MIN_RATE || r > RS_MAX_RATE)
+                return fail(MC_ERR_ARG, "%s %u outside [%u, %u] (%s)", k ? "ir_rate" : "session_rate", r, RS_MIN_RATE, RS_MAX_RATE, why);
+        }
+        return MC_OK;
+    };
+    // the frames at the session's rate, once the rates and the frames are good
+    const auto converted = [&] { return ir_rate != session_rate ? rs_out_frames(rs_geom(ir_rate, session_rate), frames) : frames; };
+    IrSteps steps;
+    StepPlan plan;
+    uint64_t F = 0;
+    if (rq.tail) {
+        if (const char* bad = tail_check(rq.tail, session_rate)) return fail(MC_ERR_ARG, "%s", bad);
+        if (const int rc = rates("the tail step needs the session's rate")) return rc;
+        if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
+        F = converted();
+        if (const char* bad = tail_check_frames(rq.tail, F)) return fail(MC_ERR_ARG, "%s", bad);
+        F = plan.plan_tail(*rq.tail, session_rate, F);
+        if (const char* bad = plan.limits(rq, F, session_rate)) return fail(MC_ERR_ARG, "%s", bad);
+        if (const char* bad = resolve_steps(shape, eq, damp, ir_rate, session_rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
+    } else {
+        if (const char* bad = resolve_steps(shape, eq, damp, ir_rate, session_rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
+        if (ir_rate || session_rate)  // (0, 0 without a tail: the frames are at the session's rate)
+            if (const int rc = rates("both rates 0 = no conversion")) return rc;
+        if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
+        F = converted();
+        if (const char* bad = plan.limits(rq, F, session_rate)) return fail(MC_ERR_ARG, "%s", bad);
+    }
+    if (const char* bad = StepPlan::pointers(rq)) return fail(MC_ERR_ARG, "%s", bad);
+    plan.plan(rq, F, session_rate);
+    const uint32_t rs[2] = {ir_rate, session_rate};
+    IrLoad ld;
+    ld.lr = lr, ld.frames = frames, ld.rs = ir_rate != session_rate ? rs : nullptr;
+    plan.into(ld);
+    steps.into(ld);
+    return load_ir(e, idx, nframes, ld);
+}
+
+// mc_load_ir_sweep_tail, _phase, _filter and _match behind their switches, as load_file_steps: the structs of the match, the filter
+// and the phase, the tail, then everything mc_load_ir_sweep checks in its order with F' and the steps' limits after the lengths,
+// the recording, then the second IRs' pointers.
+int load_sweep_steps(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
+                     uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const StepRequest& rq) {
+    if (const char* bad = StepPlan::check_structs(rq)) return fail(MC_ERR_ARG, "%s", bad);
+    if (rq.tail)
+        if (const char* bad = tail_check(rq.tail, sweep ? sweep->rate : 0)) return fail(MC_ERR_ARG, "%s", bad);
+    if (const char* bad = swp_check(sweep)) return fail(MC_ERR_ARG, "%s", bad);
+    if (const char* bad = swp_check_load(sweep, frames, ir_frames, offset)) return fail(MC_ERR_ARG, "%s", bad);
+    if (rq.tail)
+        if (const char* bad = tail_check_frames(rq.tail, ir_frames)) return fail(MC_ERR_ARG, "%s", bad);
+    StepPlan plan;
+    const uint64_t F = rq.tail ? plan.plan_tail(*rq.tail, sweep->rate, ir_frames) : ir_frames;
+    if (const char* bad = plan.limits(rq, F, sweep->rate)) return fail(MC_ERR_ARG, "%s", bad);
+    IrSteps steps;
+    if (const char* bad = resolve_steps(shape, eq, damp, sweep->rate, sweep->rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!lr) return fail(MC_ERR_ARG, "null lr");
+    if (const char* bad = StepPlan::pointers(rq)) return fail(MC_ERR_ARG, "%s", bad);
+    plan.plan(rq, F, sweep->rate);
+    const SweepSource src{swp_plan(*sweep), lr, frames, ir_frames, offset};
+    IrLoad ld;
+    ld.swp = &src, ld.frames = ir_frames;
+    plan.into(ld);
+    steps.into(ld);
+    return load_ir(e, idx, nframes, ld);
+}
 }  // namespace
 
 extern "C" {
@@ -4194,46 +4312,18 @@ void mc_default_ir_tail(mc_ir_tail* t) {
 
 int mc_load_ir_tail(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
                     const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail) {
-    if (!tail || tail->mode == MC_TAIL_OFF) return mc_load_ir_damped(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp);
-    // the tail first, then the rates and F', then damp, eq and shape as in mc_load_ir_damped, all before the engine and before any HIP call
-    if (const char* bad = tail_check(tail, session_rate)) return fail(MC_ERR_ARG, "%s", bad);
-    for (int k = 0; k < 2; k++) {
-        const uint32_t r = k ? ir_rate : session_rate;
-        if (r < RS_MIN_RATE || r > RS_MAX_RATE)
-            return fail(MC_ERR_ARG, "%s %u outside [%u, %u] (the tail step needs the session's rate)", k ? "ir_rate" : "session_rate", r, RS_MIN_RATE, RS_MAX_RATE);
-    }
-    if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
-    const uint32_t rs[2] = {ir_rate, session_rate};
-    const uint64_t F = ir_rate != session_rate ? rs_out_frames(rs_geom(ir_rate, session_rate), frames) : frames;
-    if (const char* bad = tail_check_frames(tail, F)) return fail(MC_ERR_ARG, "%s", bad);
-    IrSteps steps;
-    if (const char* bad = resolve_steps(shape, eq, damp, ir_rate, session_rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
-    const TailStep step = tail_step(*tail, session_rate, F);
-    IrLoad ld;
-    ld.lr = lr, ld.frames = frames, ld.rs = ir_rate != session_rate ? rs : nullptr;
-    ld.tail = &step;
-    steps.into(ld);
-    return load_ir(e, idx, nframes, ld);
+    StepRequest rq;
+    rq.tail = tail;
+    if (!rq.normalise().any()) return mc_load_ir_damped(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp);
+    return load_file_steps(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, rq);
 }
 
 int mc_load_ir_sweep_tail(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
                           uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail) {
-    if (!tail || tail->mode == MC_TAIL_OFF) return mc_load_ir_sweep(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp);
-    // the tail first, then everything mc_load_ir_sweep checks in its order, F' after F, all before the engine and before any HIP call
-    if (const char* bad = tail_check(tail, sweep ? sweep->rate : 0)) return fail(MC_ERR_ARG, "%s", bad);
-    if (const char* bad = swp_check(sweep)) return fail(MC_ERR_ARG, "%s", bad);
-    if (const char* bad = swp_check_load(sweep, frames, ir_frames, offset)) return fail(MC_ERR_ARG, "%s", bad);
-    if (const char* bad = tail_check_frames(tail, ir_frames)) return fail(MC_ERR_ARG, "%s", bad);
-    IrSteps steps;
-    if (const char* bad = resolve_steps(shape, eq, damp, sweep->rate, sweep->rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
-    if (!lr) return fail(MC_ERR_ARG, "null lr");
-    const SweepSource src{swp_plan(*sweep), lr, frames, ir_frames, offset};
-    const TailStep step = tail_step(*tail, sweep->rate, ir_frames);
-    IrLoad ld;
-    ld.swp = &src, ld.frames = ir_frames;
-    ld.tail = &step;
-    steps.into(ld);
-    return load_ir(e, idx, nframes, ld);
+    StepRequest rq;
+    rq.tail = tail;
+    if (!rq.normalise().any()) return mc_load_ir_sweep(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp);
+    return load_sweep_steps(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, rq);
 }
 
 int mc_ir_tail_info(const mc_engine* e, uint64_t idx, double out[4]) { return ir_fact(e, idx, FACT_TAIL, 4, "was not loaded with a tail step", out); }
@@ -4258,177 +4348,61 @@ int mc_ir_phase_plan(const mc_ir_phase* p, uint64_t frames, double out[4]) {
     return MC_OK;
 }
 
-// mc_load_ir_phase, mc_load_ir_filter and mc_load_ir_match behind their switches: each of phase, filter and match is on or null, and one
-// of them is on.
-static int load_phase_filter(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
-                             const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail, const mc_ir_phase* phase,
-                             const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames, const mc_ir_match* match = nullptr,
-                             const float* target_lr = nullptr, uint64_t target_frames = 0) {
-    // the match first, then the filter, then the phase, then what mc_load_ir_tail checks in its order, the steps' limits once F is known, all
-    // before the engine and before any HIP call
-    if (match)
-        if (const char* bad = match_check(match)) return fail(MC_ERR_ARG, "%s", bad);
-    if (filter)
-        if (const char* bad = filter_check(filter)) return fail(MC_ERR_ARG, "%s", bad);
-    if (phase)
-        if (const char* bad = phase_check(phase)) return fail(MC_ERR_ARG, "%s", bad);
-    const bool tailed = tail && tail->mode != MC_TAIL_OFF;
-    const bool convert = tailed || ir_rate || session_rate;  // (0, 0 without a tail: the frames are at the session's rate)
-    const auto rates = [&](const char* why) -> int {
-        for (int k = 0; k < 2; k++) {
-            const uint32_t r = k ? ir_rate : session_rate;
-            if (r < RS_MIN_RATE || r > RS_MAX_RATE)
-                return fail(MC_ERR_ARG, "%s %u outside [%u, %u] (%s)", k ? "ir_rate" : "session_rate", r, RS_MIN_RATE, RS_MAX_RATE, why);
-        }
-        return MC_OK;
-    };
-    IrSteps steps;
-    TailStep tstep{};
-    uint64_t F = 0, G = 0, Gm = 0;
-    // the limits of the steps that are on, over the F frames that reach them
-    const auto limits = [&]() -> const char* {
-        if (phase)
-            if (const char* bad = phase_check_frames(phase, F)) return bad;
-        if (filter)
-            if (const char* bad = filter_check_load(filter, session_rate, F, filter_frames, &G)) return bad;
-        return match ? match_check_load(match, session_rate, filter && F ? filter_step(*filter, F, G).Fo : F, target_frames, &Gm) : nullptr;
-    };
-    if (tailed) {
-        if (const char* bad = tail_check(tail, session_rate)) return fail(MC_ERR_ARG, "%s", bad);
-        if (const int rc = rates("the tail step needs the session's rate")) return rc;
-        if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
-        F = ir_rate != session_rate ? rs_out_frames(rs_geom(ir_rate, session_rate), frames) : frames;
-        if (const char* bad = tail_check_frames(tail, F)) return fail(MC_ERR_ARG, "%s", bad);
-        tstep = tail_step(*tail, session_rate, F);
-        F = tstep.plan.Fp;
-        if (const char* bad = limits()) return fail(MC_ERR_ARG, "%s", bad);
-        if (const char* bad = resolve_steps(shape, eq, damp, ir_rate, session_rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
-    } else {
-        if (const char* bad = resolve_steps(shape, eq, damp, ir_rate, session_rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
-        if (convert)
-            if (const int rc = rates("both rates 0 = no conversion")) return rc;
-        if (frames > (1ull << 40)) return fail(MC_ERR_ARG, "IR of %llu frames", (unsigned long long)frames);
-        F = ir_rate != session_rate ? rs_out_frames(rs_geom(ir_rate, session_rate), frames) : frames;
-        if (const char* bad = limits()) return fail(MC_ERR_ARG, "%s", bad);
-    }
-    if (filter && !filter_lr) return fail(MC_ERR_ARG, "null filter_lr");
-    if (match && match->mode == MC_MATCH_TARGET && !target_lr) return fail(MC_ERR_ARG, "null target_lr");
-    const uint32_t rs[2] = {ir_rate, session_rate};
-    const PhaseStep pstep = phase ? phase_step(*phase, F) : PhaseStep{};
-    FilterStep fstep = filter ? filter_step(*filter, F, G) : FilterStep{};
-    if (filter) fstep.lr = filter_lr, fstep.frames = filter_frames, fstep.rs[0] = filter->rate ? filter->rate : session_rate, fstep.rs[1] = session_rate;
-    MatchStep mstep = match && F ? match_step(*match, session_rate, filter ? fstep.Fo : F, Gm) : MatchStep{};
-    if (match) mstep.lr = target_lr, mstep.frames = target_frames, mstep.rs[0] = match->rate ? match->rate : session_rate, mstep.rs[1] = session_rate;
-    IrLoad ld;
-    ld.lr = lr, ld.frames = frames, ld.rs = ir_rate != session_rate ? rs : nullptr;
-    ld.tail = tailed ? &tstep : nullptr;
-    ld.phase = phase ? &pstep : nullptr;
-    ld.filter = filter ? &fstep : nullptr;
-    ld.match = match ? &mstep : nullptr;
-    steps.into(ld);
-    return load_ir(e, idx, nframes, ld);
-}
-
 int mc_load_ir_phase(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
                      const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail, const mc_ir_phase* phase) {
-    if (!phase || phase->mode == MC_PHASE_OFF) return mc_load_ir_tail(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail);
-    return load_phase_filter(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail, phase, nullptr, nullptr, 0);
+    StepRequest rq;
+    rq.tail = tail, rq.phase = phase;
+    if (!rq.normalise().any()) return mc_load_ir_damped(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp);
+    return load_file_steps(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, rq);
 }
 
 int mc_load_ir_filter(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
                       const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail, const mc_ir_phase* phase,
                       const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames) {
-    if (!filter || filter->op == MC_FILTER_OFF) return mc_load_ir_phase(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail, phase);
-    return load_phase_filter(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail, phase && phase->mode != MC_PHASE_OFF ? phase : nullptr,
-                             filter, filter_lr, filter_frames);
-}
-
-// mc_load_ir_sweep_phase and mc_load_ir_sweep_filter behind their switches, as load_phase_filter
-static int load_sweep_phase_filter(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
-                                   uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail,
-                                   const mc_ir_phase* phase, const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames,
-                                   const mc_ir_match* match = nullptr, const float* target_lr = nullptr, uint64_t target_frames = 0) {
-    // the match first, then the filter, then the phase, then what mc_load_ir_sweep_tail checks in its order, the steps' limits once F is known
-    if (match)
-        if (const char* bad = match_check(match)) return fail(MC_ERR_ARG, "%s", bad);
-    if (filter)
-        if (const char* bad = filter_check(filter)) return fail(MC_ERR_ARG, "%s", bad);
-    if (phase)
-        if (const char* bad = phase_check(phase)) return fail(MC_ERR_ARG, "%s", bad);
-    const bool tailed = tail && tail->mode != MC_TAIL_OFF;
-    if (tailed)
-        if (const char* bad = tail_check(tail, sweep ? sweep->rate : 0)) return fail(MC_ERR_ARG, "%s", bad);
-    if (const char* bad = swp_check(sweep)) return fail(MC_ERR_ARG, "%s", bad);
-    if (const char* bad = swp_check_load(sweep, frames, ir_frames, offset)) return fail(MC_ERR_ARG, "%s", bad);
-    if (tailed)
-        if (const char* bad = tail_check_frames(tail, ir_frames)) return fail(MC_ERR_ARG, "%s", bad);
-    const TailStep tstep = tailed ? tail_step(*tail, sweep->rate, ir_frames) : TailStep{};
-    const uint64_t F = tailed ? tstep.plan.Fp : ir_frames;
-    uint64_t G = 0, Gm = 0;
-    if (phase)
-        if (const char* bad = phase_check_frames(phase, F)) return fail(MC_ERR_ARG, "%s", bad);
-    if (filter)
-        if (const char* bad = filter_check_load(filter, sweep->rate, F, filter_frames, &G)) return fail(MC_ERR_ARG, "%s", bad);
-    if (match)
-        if (const char* bad = match_check_load(match, sweep->rate, filter && F ? filter_step(*filter, F, G).Fo : F, target_frames, &Gm))
-            return fail(MC_ERR_ARG, "%s", bad);
-    IrSteps steps;
-    if (const char* bad = resolve_steps(shape, eq, damp, sweep->rate, sweep->rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
-    if (!lr) return fail(MC_ERR_ARG, "null lr");
-    if (filter && !filter_lr) return fail(MC_ERR_ARG, "null filter_lr");
-    if (match && match->mode == MC_MATCH_TARGET && !target_lr) return fail(MC_ERR_ARG, "null target_lr");
-    const SweepSource src{swp_plan(*sweep), lr, frames, ir_frames, offset};
-    const PhaseStep pstep = phase ? phase_step(*phase, F) : PhaseStep{};
-    FilterStep fstep = filter ? filter_step(*filter, F, G) : FilterStep{};
-    if (filter) fstep.lr = filter_lr, fstep.frames = filter_frames, fstep.rs[0] = filter->rate ? filter->rate : sweep->rate, fstep.rs[1] = sweep->rate;
-    MatchStep mstep = match && F ? match_step(*match, sweep->rate, filter ? fstep.Fo : F, Gm) : MatchStep{};
-    if (match) mstep.lr = target_lr, mstep.frames = target_frames, mstep.rs[0] = match->rate ? match->rate : sweep->rate, mstep.rs[1] = sweep->rate;
-    IrLoad ld;
-    ld.swp = &src, ld.frames = ir_frames;
-    ld.tail = tailed ? &tstep : nullptr;
-    ld.phase = phase ? &pstep : nullptr;
-    ld.filter = filter ? &fstep : nullptr;
-    ld.match = match ? &mstep : nullptr;
-    steps.into(ld);
-    return load_ir(e, idx, nframes, ld);
+    StepRequest rq;
+    rq.tail = tail, rq.phase = phase, rq.filter = filter, rq.filter_lr = filter_lr, rq.filter_frames = filter_frames;
+    if (!rq.normalise().any()) return mc_load_ir_damped(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp);
+    return load_file_steps(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, rq);
 }
 
 int mc_load_ir_sweep_phase(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
                            uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail,
                            const mc_ir_phase* phase) {
-    if (!phase || phase->mode == MC_PHASE_OFF)
-        return mc_load_ir_sweep_tail(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail);
-    return load_sweep_phase_filter(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail, phase, nullptr, nullptr, 0);
+    StepRequest rq;
+    rq.tail = tail, rq.phase = phase;
+    if (!rq.normalise().any()) return mc_load_ir_sweep(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp);
+    return load_sweep_steps(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, rq);
 }
 
 int mc_load_ir_sweep_filter(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
                             uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail,
                             const mc_ir_phase* phase, const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames) {
-    if (!filter || filter->op == MC_FILTER_OFF)
-        return mc_load_ir_sweep_phase(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail, phase);
-    return load_sweep_phase_filter(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail,
-                                   phase && phase->mode != MC_PHASE_OFF ? phase : nullptr, filter, filter_lr, filter_frames);
+    StepRequest rq;
+    rq.tail = tail, rq.phase = phase, rq.filter = filter, rq.filter_lr = filter_lr, rq.filter_frames = filter_frames;
+    if (!rq.normalise().any()) return mc_load_ir_sweep(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp);
+    return load_sweep_steps(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, rq);
 }
 
 int mc_load_ir_match(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
                      const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail, const mc_ir_phase* phase,
                      const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames, const mc_ir_match* match, const float* target_lr,
                      uint64_t target_frames) {
-    if (!match || match->mode == MC_MATCH_OFF)
-        return mc_load_ir_filter(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail, phase, filter, filter_lr, filter_frames);
-    return load_phase_filter(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, tail, phase && phase->mode != MC_PHASE_OFF ? phase : nullptr,
-                             filter && filter->op != MC_FILTER_OFF ? filter : nullptr, filter_lr, filter_frames, match, target_lr, target_frames);
+    StepRequest rq;
+    rq.tail = tail, rq.phase = phase, rq.filter = filter, rq.filter_lr = filter_lr, rq.filter_frames = filter_frames,
+        rq.match = match, rq.target_lr = target_lr, rq.target_frames = target_frames;
+    if (!rq.normalise().any()) return mc_load_ir_damped(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp);
+    return load_file_steps(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, rq);
 }
 
 int mc_load_ir_sweep_match(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
                            uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail,
                            const mc_ir_phase* phase, const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames,
                            const mc_ir_match* match, const float* target_lr, uint64_t target_frames) {
-    if (!match || match->mode == MC_MATCH_OFF)
-        return mc_load_ir_sweep_filter(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail, phase, filter, filter_lr, filter_frames);
-    return load_sweep_phase_filter(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, tail,
-                                   phase && phase->mode != MC_PHASE_OFF ? phase : nullptr, filter && filter->op != MC_FILTER_OFF ? filter : nullptr, filter_lr,
-                                   filter_frames, match, target_lr, target_frames);
+    StepRequest rq;
+    rq.tail = tail, rq.phase = phase, rq.filter = filter, rq.filter_lr = filter_lr, rq.filter_frames = filter_frames,
+        rq.match = match, rq.target_lr = target_lr, rq.target_frames = target_frames;
+    if (!rq.normalise().any()) return mc_load_ir_sweep(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp);
+    return load_sweep_steps(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, rq);
 }
 
 void mc_default_ir_match(mc_ir_match* m) {

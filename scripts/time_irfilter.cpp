@@ -60,7 +60,7 @@ int main(int argc, char** argv) {
     for (uint32_t op : {(uint32_t)MC_FILTER_CONVOLVE, (uint32_t)MC_FILTER_DECONVOLVE}) {
         mc_ir_filter f{(uint32_t)sizeof(mc_ir_filter), op, MC_FILTER_STEREO, 0, 60.f, 0, 0};
         FilterStep step = filter_step(f, F, G);
-        step.lr = &b[0].x, step.frames = G;
+        step.second = second_ir(&b[0].x, G, 0, 0);
         plan = step.fft;
         double info[10];
         std::vector<float2> first(step.Fo), again(step.Fo);

@@ -63,7 +63,7 @@ static int one_size(int lgN) {
         return 1;
     }
     MatchStep step = match_step(m, 48000, F, G);
-    step.lr = &t[0].x, step.frames = G, step.rs[0] = step.rs[1] = 48000;
+    step.second = second_ir(&t[0].x, G, 0, 48000);
     MatchFacts facts;
     std::vector<float2> first(step.Fo), again(step.Fo);
     std::vector<float> warm;

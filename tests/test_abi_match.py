@@ -6,6 +6,7 @@ import os
 import re
 
 import numpy as np
+import pytest
 
 HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "mcconv.h")
 NAN = float("nan")
@@ -100,6 +101,15 @@ def test_the_plan_refuses():
     assert rc == 0 and out[:2] == [256.0, 1.0] and out[3:5] == [100.0, 120.0]
     rc, msg, _ = _plan(_match(), out=False)
     assert rc == -1 and "null out" in msg
+
+
+@pytest.mark.parametrize("frames", [(1 << 22) + 1, (1 << 40) + 1, (1 << 62) + 1, (1 << 63) - 1])
+def test_the_plan_refuses_any_length_beyond_the_transform(frames):
+    """mc_ir_match_plan bounds `frames` by nothing but the transform: the search for its length must end at 2^22 whatever comes in
+    (a power of two >= 2 frames does not exist in 64 bits from 2^62 + 1 on)."""
+    rc, msg, out = _plan(_match(), frames=frames, target_frames=5)
+    assert rc == -1 and msg == f"{frames} frames and 5 target frames at the session's rate need a transform of more than 2^22 points", msg
+    assert out == [-1.0] * 6
 
 
 def _load(m, frames=100, rates=(48000, 48000), lr=True, tlr=True, G=10, tail=None, shape=None, phase=None, filt=None, flr=True, fG=10):
