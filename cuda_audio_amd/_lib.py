@@ -31,6 +31,7 @@ SYMBOLS = [
     "mc_default_ir_phase", "mc_ir_phase_plan", "mc_load_ir_phase", "mc_load_ir_sweep_phase", "mc_ir_phase_info",
     "mc_default_ir_filter", "mc_ir_filter_plan", "mc_load_ir_filter", "mc_load_ir_sweep_filter", "mc_ir_filter_info",
     "mc_default_ir_match", "mc_ir_match_plan", "mc_load_ir_match", "mc_load_ir_sweep_match", "mc_ir_match_info", "mc_ir_match_curve",
+    "mc_default_ir_parts", "mc_ir_parts_plan", "mc_ir_parts_at", "mc_load_ir_parts", "mc_load_ir_sweep_parts", "mc_ir_parts_info",
     "mc_default_ir_room", "mc_synth_ir_room", "mc_ir_room_info", "mc_ir_room_plan",
     "mc_default_ir_room_mics", "mc_synth_ir_room_mics", "mc_ir_room_mics_plan", "mc_ir_room_mics_info",
     "mc_default_ir_room_bands", "mc_synth_ir_room_bands", "mc_ir_room_bands_plan", "mc_ir_room_bands_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
@@ -389,6 +390,29 @@ class McIrMatch(C.Structure):
     ]
 
 
+MC_PARTS_OFF, MC_PARTS_ON = 0, 1
+
+
+class McIrParts(C.Structure):
+    """mc_ir_parts: the parts step of mc_load_ir_parts and mc_load_ir_sweep_parts."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("mode", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved0", C.c_uint32),
+        ("direct_end", C.c_uint64),
+        ("early_end", C.c_uint64),
+        ("xfade", C.c_uint32 * 2),
+        ("delay", C.c_int32 * 3),
+        ("gain_db", C.c_float * 3),
+        ("width", C.c_float * 3),
+        ("balance", C.c_float * 3),
+        ("frames_out", C.c_uint64),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 MC_ROOM_MAX_ORDER = 32
 
 
@@ -563,6 +587,13 @@ def load():
     L.mc_load_ir_sweep_match.argtypes = L.mc_load_ir_sweep_filter.argtypes + [C.POINTER(McIrMatch), fp, u64]
     L.mc_ir_match_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_ir_match_curve.argtypes = [vp, u64, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_uint32]
+    L.mc_default_ir_parts.argtypes = [C.POINTER(McIrParts)]
+    L.mc_default_ir_parts.restype = None
+    L.mc_ir_parts_plan.argtypes = [C.POINTER(McIrParts), u64, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mc_ir_parts_at.argtypes = [C.POINTER(McIrParts), u64, u64, u64]
+    L.mc_load_ir_parts.argtypes = L.mc_load_ir_match.argtypes + [C.POINTER(McIrParts)]
+    L.mc_load_ir_sweep_parts.argtypes = L.mc_load_ir_sweep_match.argtypes + [C.POINTER(McIrParts)]
+    L.mc_ir_parts_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_default_ir_room.argtypes = [C.POINTER(McIrRoom)]
     L.mc_default_ir_room.restype = None
     L.mc_synth_ir_room.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrRoom), C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp),

@@ -42,6 +42,7 @@
 #include "irphase.hip.h"
 #include "irfilter.hip.h"
 #include "irmatch.hip.h"
+#include "irparts.hip.h"
 
 // Environment switches, read at mc_create.  The library reads fourteen.  Ten select paths a caller can also reach through
 // mc_config or that the tests compare bit for bit:
@@ -92,10 +93,10 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline double pan_l(double p) { return p >= 0 ? 1 - p : 1; }  // conv.cu:386
 inline double pan_r(double p) { return p <= 0 ? 1 + p : 1; }  // conv.cu:387
 
-// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _phase_info, _filter_info, _match_info, _room_info, _room_mics_info and _room_bands_info report of an IR's last
+// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _phase_info, _filter_info, _match_info, _parts_info, _room_info, _room_mics_info and _room_bands_info report of an IR's last
 // load: one entry per kind, on when that load had the step or the source (a shape with something on, an eq band or damping count as a shape, and
 // so do a synthesised, a swept and a tailed load), with the numbers the getter hands out (include/mcconv.h says what they are)
-enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_PHASE, FACT_FILTER, FACT_MATCH, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_KINDS };
+enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_PHASE, FACT_FILTER, FACT_MATCH, FACT_PARTS, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_KINDS };
 struct IrFact {
     bool on = false;
     double v[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -3358,6 +3359,7 @@ struct IrLoad {
     const PhaseStep* phase = nullptr;    // step 1b, after the tail step (irphase.hip.h; phase->F = the frames the tail step hands on)
     const FilterStep* filter = nullptr;  // step 1c, after the phase step (irfilter.hip.h; filter->F = the frames the phase step hands on)
     const MatchStep* match = nullptr;    // step 1d, after the filter step (irmatch.hip.h; match->F = the frames the filter step hands on)
+    const PartsStep* parts = nullptr;    // step 1e, after the match step (irparts.hip.h; parts->F = the frames the match step hands on)
     const mc_ir_shape* shape = nullptr;  // applied on the device after the conversion (irshape.hip.h)
     const IeqCascade* eq = nullptr;      // the bands of mc_load_ir_eq (ireq.hip.h); with damp it may hold no band
     const DampPlan* damp = nullptr;      // the damping of mc_load_ir_damped (irdamp.hip.h; needs eq)
@@ -3371,6 +3373,7 @@ struct ShapedTaps {
     double phase[8];    // mc_ir_phase_info's numbers, with IrLoad::phase
     double filter[10];  // mc_ir_filter_info's numbers, with IrLoad::filter
     MatchFacts match;   // mc_ir_match_info's numbers and mc_ir_match_curve's arrays, with IrLoad::match
+    double parts[10];   // mc_ir_parts_info's numbers, with IrLoad::parts
 };
 
 // The stream idle and out of the JACK path, before the kernels of a load or of a measurement go onto it.  (The single-transform
@@ -3387,7 +3390,7 @@ int quiesce(mc_engine* e) {
 // The shaped load's own stage (irshape.hip.h): all `conv` frames of ld's source at the session's rate on the device, shaped
 // into a new buffer of out->n <= cap taps.  Nothing of the engine's IRs is touched here.  A sweep's recording is uploaded to a
 // temporary buffer freed after the stage, as its weight table is; the tail step turns the conv frames into tail->plan.Fp frames
-// in a buffer of their own, the phase step those into as many frames in another, the filter step those into filter->Fo, and the match step those into match->Fo.
+// in a buffer of their own, the phase step those into as many frames in another, the filter step those into filter->Fo, the match step those into match->Fo, and the parts step those into parts->Fo.
 int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, ShapedTaps* out) {
     float2 *d_x = nullptr, *d_rec = nullptr;
     double* d_u = nullptr;
@@ -3418,6 +3421,7 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
     if (ld.phase) step(conv, [&](float2* d_y) { return phase_run(e->stream, d_x, d_y, *ld.phase, out->phase); });
     if (ld.filter) step(ld.filter->Fo, [&](float2* d_y) { return filter_run(e->stream, d_x, d_y, *ld.filter, out->filter); });
     if (ld.match) step(ld.match->Fo, [&](float2* d_y) { return match_run(e->stream, d_x, d_y, *ld.match, &out->match); });
+    if (ld.parts) step(ld.parts->Fo, [&](float2* d_y) { return parts_run(e->stream, d_x, d_y, *ld.parts, out->parts); });
     if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, *ld.shape, &out->d_taps, &out->n, out->sums, out->info, ld.eq, ld.damp);
     if (ld.swp && er != hipSuccess) (void)hipStreamSynchronize(e->stream);  // (the correlation may still be reading them)
     (void)hipFree(d_x);
@@ -3458,6 +3462,10 @@ void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const ShapedTaps& s
         const double* m = st.match.info;
         put(FACT_MATCH, {m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7], m[8], m[9], m[10], m[11]});
         ir.match_curve = st.match.curve;
+    }
+    if (ld.parts) {
+        const double* p = st.parts;
+        put(FACT_PARTS, {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9]});
     }
     if (ld.room) {
         const RoomPlan& r = ld.room->plan;
@@ -3625,7 +3633,7 @@ const char* resolve_steps(const mc_ir_shape* shape, const mc_ir_eq* eq, const mc
     return nullptr;
 }
 
-// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, phase, filter, match, room, room mics, room bands): out = the first `count` numbers of what
+// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, phase, filter, match, parts, room, room mics, room bands): out = the first `count` numbers of what
 // note_load kept of that kind, or MC_ERR_STATE with "IR <idx> <was_not>" when the last load had none
 int ir_fact(const mc_engine* e, uint64_t idx, IrFactKind kind, int count, const char* was_not, double* out) {
     if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
@@ -3658,7 +3666,7 @@ int measure(mc_engine* e, uint64_t idx, const char* name, Run&& run) {
 // the tail step of a checked mc_ir_tail that is on, over F frames at the session's rate
 TailStep tail_step(const mc_ir_tail& tail, uint32_t rate, uint64_t F) { return TailStep{tail_plan(tail, rate, F), tail.mode == MC_TAIL_EXTEND}; }
 
-// The arguments of steps 1a to 1d as an entry point receives them.  An entry point fills in by name what it takes; normalise()
+// The arguments of steps 1a to 1e as an entry point receives them.  An entry point fills in by name what it takes; normalise()
 // is the one place that looks at the switches: a step that is off becomes a null pointer, whatever else its struct holds.
 struct StepRequest {
     const mc_ir_tail* tail = nullptr;
@@ -3669,17 +3677,19 @@ struct StepRequest {
     const mc_ir_match* match = nullptr;
     const float* target_lr = nullptr;
     uint64_t target_frames = 0;
+    const mc_ir_parts* parts = nullptr;
     StepRequest& normalise() {
         if (tail && tail->mode == MC_TAIL_OFF) tail = nullptr;
         if (phase && phase->mode == MC_PHASE_OFF) phase = nullptr;
         if (filter && filter->op == MC_FILTER_OFF) filter = nullptr;
         if (match && match->mode == MC_MATCH_OFF) match = nullptr;
+        if (parts && parts->mode == MC_PARTS_OFF) parts = nullptr;
         return *this;
     }
-    bool any() const { return tail || phase || filter || match; }
+    bool any() const { return tail || phase || filter || match || parts; }
 };
 
-// Steps 1a to 1d of a normalised request as load_ir takes them, beside IrSteps and in its manner.  The checks return the message
+// Steps 1a to 1e of a normalised request as load_ir takes them, beside IrSteps and in its manner.  The checks return the message
 // of the first one that fails, null when all pass; no engine and no HIP call.  The tail's own checks (tail_check,
 // tail_check_frames) stay with the source, which knows where among its own they belong.
 struct StepPlan {
@@ -3687,11 +3697,14 @@ struct StepPlan {
     PhaseStep phase{};
     FilterStep filter{};
     MatchStep match;
+    PartsStep parts{};
     uint64_t G = 0, Gm = 0;  // limits(): the filter's and the target's frames at the session's rate
-    bool tailed = false, phased = false, filtered = false, matched = false;
+    bool tailed = false, phased = false, filtered = false, matched = false, parted = false;
 
-    // the structs of the match, the filter and the phase, in that order
+    // the structs of the parts, the match, the filter and the phase, in that order
     static const char* check_structs(const StepRequest& rq) {
+        if (rq.parts)
+            if (const char* bad = parts_check(rq.parts)) return bad;
         if (rq.match)
             if (const char* bad = match_check(rq.match)) return bad;
         if (rq.filter)
@@ -3703,37 +3716,43 @@ struct StepPlan {
         tail = tail_step(t, session_rate, F), tailed = true;
         return tail.plan.Fp;
     }
-    // the limits of the steps that are on, over the F frames that reach them: the phase's, the filter's, the match's over what the filter hands on
+    // the limits of the steps that are on, over the F frames that reach them: the phase's, the filter's, the match's over what the
+    // filter hands on, the parts' over what the match hands on
     const char* limits(const StepRequest& rq, uint64_t F, uint32_t session_rate) {
         if (rq.phase)
             if (const char* bad = phase_check_frames(rq.phase, F)) return bad;
         if (rq.filter)
             if (const char* bad = filter_check_load(rq.filter, session_rate, F, rq.filter_frames, &G)) return bad;
-        return rq.match ? match_check_load(rq.match, session_rate, rq.filter && F ? filter_step(*rq.filter, F, G).Fo : F, rq.target_frames, &Gm) : nullptr;
+        const uint64_t Ff = rq.filter && F ? filter_step(*rq.filter, F, G).Fo : F;
+        if (rq.match)
+            if (const char* bad = match_check_load(rq.match, session_rate, Ff, rq.target_frames, &Gm)) return bad;
+        return rq.parts ? parts_check_frames(rq.parts, rq.match && F ? match_step(*rq.match, session_rate, Ff, Gm).Fo : Ff) : nullptr;
     }
     // the second IRs' frames: the filter's, and the target's when the match has one
     static const char* pointers(const StepRequest& rq) {
         if (rq.filter && !rq.filter_lr) return "null filter_lr";
         return rq.match && rq.match->mode == MC_MATCH_TARGET && !rq.target_lr ? "null target_lr" : nullptr;
     }
-    // the three spectral steps over the F frames that reach them, after limits(); a second IR's rate 0 is the session's
+    // the three spectral steps and the parts over the F frames that reach them, after limits(); a second IR's rate 0 is the session's
     void plan(const StepRequest& rq, uint64_t F, uint32_t session_rate) {
-        phased = rq.phase, filtered = rq.filter, matched = rq.match;
+        phased = rq.phase, filtered = rq.filter, matched = rq.match, parted = rq.parts;
         if (rq.phase) phase = phase_step(*rq.phase, F);
         if (rq.filter) filter = filter_step(*rq.filter, F, G), filter.second = second_ir(rq.filter_lr, rq.filter_frames, rq.filter->rate, session_rate);
         if (rq.match && F) match = match_step(*rq.match, session_rate, rq.filter ? filter.Fo : F, Gm);
         if (rq.match) match.second = second_ir(rq.target_lr, rq.target_frames, rq.match->rate, session_rate);
+        if (rq.parts && F) parts = parts_step(*rq.parts, rq.match ? match.Fo : rq.filter ? filter.Fo : F);
     }
     void into(IrLoad& ld) const {
         ld.tail = tailed ? &tail : nullptr;
         ld.phase = phased ? &phase : nullptr;
         ld.filter = filtered ? &filter : nullptr;
         ld.match = matched ? &match : nullptr;
+        ld.parts = parted ? &parts : nullptr;
     }
 };
 
-// mc_load_ir_tail, _phase, _filter and _match behind their switches: a file's frames through the steps of rq, of which one is on.
-// All before the engine and before any HIP call: the structs of the match, the filter and the phase; with a tail the tail, the
+// mc_load_ir_tail, _phase, _filter, _match and _parts behind their switches: a file's frames through the steps of rq, of which one is on.
+// All before the engine and before any HIP call: the structs of the parts, the match, the filter and the phase; with a tail the tail, the
 // rates, the frames and F', the steps' limits over F', then damp, eq and shape; without one damp, eq and shape as in
 // mc_load_ir_damped, the rates unless both are 0, the frames and the steps' limits; then the second IRs' pointers.
 int load_file_steps(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
@@ -3779,7 +3798,7 @@ int load_file_steps(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames
     return load_ir(e, idx, nframes, ld);
 }
 
-// mc_load_ir_sweep_tail, _phase, _filter and _match behind their switches, as load_file_steps: the structs of the match, the filter
+// mc_load_ir_sweep_tail, _phase, _filter, _match and _parts behind their switches, as load_file_steps: the structs of the parts, the match, the filter
 // and the phase, the tail, then everything mc_load_ir_sweep checks in its order with F' and the steps' limits after the lengths,
 // the recording, then the second IRs' pointers.
 int load_sweep_steps(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
@@ -4404,6 +4423,61 @@ int mc_load_ir_sweep_match(mc_engine* e, uint64_t idx, const float* lr, uint64_t
     if (!rq.normalise().any()) return mc_load_ir_sweep(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp);
     return load_sweep_steps(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, rq);
 }
+
+int mc_load_ir_parts(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate, uint32_t session_rate,
+                     const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail, const mc_ir_phase* phase,
+                     const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames, const mc_ir_match* match, const float* target_lr,
+                     uint64_t target_frames, const mc_ir_parts* parts) {
+    StepRequest rq;
+    rq.tail = tail, rq.phase = phase, rq.filter = filter, rq.filter_lr = filter_lr, rq.filter_frames = filter_frames,
+        rq.match = match, rq.target_lr = target_lr, rq.target_frames = target_frames, rq.parts = parts;
+    if (!rq.normalise().any()) return mc_load_ir_damped(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp);
+    return load_file_steps(e, idx, lr, frames, nframes, ir_rate, session_rate, shape, eq, damp, rq);
+}
+
+int mc_load_ir_sweep_parts(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const mc_sweep* sweep, int64_t offset,
+                           uint64_t ir_frames, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail,
+                           const mc_ir_phase* phase, const mc_ir_filter* filter, const float* filter_lr, uint64_t filter_frames,
+                           const mc_ir_match* match, const float* target_lr, uint64_t target_frames, const mc_ir_parts* parts) {
+    StepRequest rq;
+    rq.tail = tail, rq.phase = phase, rq.filter = filter, rq.filter_lr = filter_lr, rq.filter_frames = filter_frames,
+        rq.match = match, rq.target_lr = target_lr, rq.target_frames = target_frames, rq.parts = parts;
+    if (!rq.normalise().any()) return mc_load_ir_sweep(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp);
+    return load_sweep_steps(e, idx, lr, frames, nframes, sweep, offset, ir_frames, shape, eq, damp, rq);
+}
+
+void mc_default_ir_parts(mc_ir_parts* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(*p);
+    p->mode = MC_PARTS_OFF;
+    for (int k = 0; k < PT_PARTS; k++) p->width[k] = 1.f;
+}
+
+int mc_ir_parts_plan(const mc_ir_parts* p, uint64_t frames, double out[4], double coef[12]) {
+    if (!p) return fail(MC_ERR_ARG, "null parts");
+    if (const char* bad = parts_check(p)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!frames) return fail(MC_ERR_ARG, "empty IR");
+    if (const char* bad = parts_check_frames(p, frames)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!out || !coef) return fail(MC_ERR_ARG, "null out");
+    const PartsStep s = parts_step(*p, frames);
+    out[0] = (double)s.Fo, out[1] = (double)s.s[0], out[2] = (double)s.s[1], out[3] = (double)parts_device_bytes(s);
+    for (int k = 0; k < PT_PARTS; k++) std::copy(s.c[k], s.c[k] + 4, coef + 4 * k);
+    return MC_OK;
+}
+
+int mc_ir_parts_at(mc_ir_parts* parts, uint64_t onset, uint64_t direct_frames, uint64_t early_frames) {
+    if (!parts) return fail(MC_ERR_ARG, "null parts");
+    if (parts->struct_size != sizeof(mc_ir_parts)) return fail(MC_ERR_ARG, "mc_ir_parts struct_size mismatch");
+    if (early_frames < direct_frames) return fail(MC_ERR_ARG, "early_frames %llu below direct_frames %llu", (unsigned long long)early_frames, (unsigned long long)direct_frames);
+    if (onset > PT_MAX_BOUNDARY || early_frames > PT_MAX_BOUNDARY || onset + early_frames > PT_MAX_BOUNDARY)
+        return fail(MC_ERR_ARG, "the boundary at onset %llu + %llu frames lies above 2^40", (unsigned long long)onset, (unsigned long long)early_frames);
+    parts->direct_end = onset + direct_frames;
+    parts->early_end = onset + early_frames;
+    return MC_OK;
+}
+
+int mc_ir_parts_info(const mc_engine* e, uint64_t idx, double out[10]) { return ir_fact(e, idx, FACT_PARTS, 10, "was not loaded with a parts step", out); }
 
 void mc_default_ir_match(mc_ir_match* m) {
     if (!m) return;

@@ -443,6 +443,105 @@ def match_plan(match, frames, target_frames=None, rate=48000):
     return dict(nfft=int(out[0]), passes=int(out[1]), device_bytes=int(out[2]), frames_out=int(out[3]), points=int(out[4]), window_bins=int(out[5]))
 
 
+PARTS = ("direct", "early", "late")
+
+
+def _triple(v, cast):
+    """A per-part field of IrParts: a scalar for all three parts, or (direct, early, late)."""
+    if isinstance(v, (tuple, list, np.ndarray)):
+        if len(v) != 3:
+            raise ValueError(f"a per-part value is a scalar or (direct, early, late), not {v!r}")
+        return tuple(cast(x) for x in v)
+    return (cast(v),) * 3
+
+
+@dataclasses.dataclass
+class IrParts:
+    """The direct sound, the early reflections and the late tail of an IR as three parts with controls of their own, which
+    prepare(parts=...) and prepare_sweep(parts=...) apply after the match step and before everything else (mc_ir_parts,
+    include/mcconv.h).  direct_end and early_end (frames at the session's rate, of the frames that reach the step) are where
+    the direct part and the early part end; xfade: the lengths of the raised-cosine cross-fades around them.  delay (whole
+    frames), gain_db, width (0 mono, 1 as it is, 2 the side signal doubled) and balance (-1 left .. +1 right) take a scalar,
+    which applies to all three parts, or a triple (direct, early, late).  mute, swap (the part's input channels change
+    places) and invert name parts: mute=("direct",).  frames_out: the frames the step hands on, 0 = all that the parts
+    reach.  mode "off" does nothing."""
+
+    direct_end: int = 0
+    early_end: int = 0
+    xfade: object = (0, 0)
+    delay: object = 0
+    gain_db: object = 0.0
+    width: object = 1.0
+    balance: object = 0.0
+    mute: tuple = ()
+    swap: tuple = ()
+    invert: tuple = ()
+    frames_out: int = 0
+    mode: str = "on"
+
+    MODES = {"off": _lib.MC_PARTS_OFF, "on": _lib.MC_PARTS_ON}
+
+    def on(self):
+        return self.mode != "off"
+
+    def to_c(self):
+        if self.mode not in self.MODES:
+            raise ValueError(f"mode must be one of {sorted(self.MODES)}, not {self.mode!r}")
+        p = _lib.McIrParts()
+        _lib.load().mc_default_ir_parts(C.byref(p))
+        p.mode, p.direct_end, p.early_end, p.frames_out = self.MODES[self.mode], int(self.direct_end), int(self.early_end), int(self.frames_out)
+        flags = 0
+        for shift, names in ((0, self.mute), (4, self.swap), (8, self.invert)):
+            for name in (names,) if isinstance(names, str) else names:
+                if name not in PARTS:
+                    raise ValueError(f"a part is one of {PARTS}, not {name!r}")
+                flags |= 1 << (shift + PARTS.index(name))
+        p.flags = flags
+        xf = self.xfade if isinstance(self.xfade, (tuple, list)) else (self.xfade, self.xfade)
+        p.xfade[0], p.xfade[1] = int(xf[0]), int(xf[1])
+        for k in range(3):
+            p.delay[k], p.gain_db[k] = _triple(self.delay, int)[k], _triple(self.gain_db, float)[k]
+            p.width[k], p.balance[k] = _triple(self.width, float)[k], _triple(self.balance, float)[k]
+        return p
+
+
+def parts_plan(parts, frames):
+    """What the parts step `parts` (an IrParts) would do to `frames` frames at the session's rate (mc_ir_parts_plan, host
+    arithmetic only): the frames it hands on, where the two cross-fades begin, the device memory the step needs while it runs,
+    and the coefficients float64 [3, 4]: c_LL, c_LR, c_RL, c_RR of the direct, the early and the late part.  McError beyond the
+    step's limits."""
+    out, coef = (C.c_double * 4)(), (C.c_double * 12)()
+    check(_lib.load().mc_ir_parts_plan(C.byref(parts.to_c()), int(frames), out, coef))
+    return dict(frames_out=int(out[0]), fade_start=(int(out[1]), int(out[2])), device_bytes=int(out[3]), coef=np.array(coef[:12]).reshape(3, 4))
+
+
+def parts_at(parts, onset, rate, direct_s=0.0025, early_s=0.08):
+    """`parts` (an IrParts) with its boundaries put direct_s and early_s seconds after frame `onset` at `rate` Hz, rounded to
+    frames (mc_ir_parts_at, host arithmetic only): onset is ir_shape_info(idx)["onset"] of a load that searched for it, or the
+    origin a measurement reports.  Everything else of `parts` stays."""
+    p = parts.to_c()
+    check(_lib.load().mc_ir_parts_at(C.byref(p), int(onset), int(math.floor(direct_s * rate + 0.5)), int(math.floor(early_s * rate + 0.5))))
+    return dataclasses.replace(parts, direct_end=int(p.direct_end), early_end=int(p.early_end))
+
+
+def parts_from_density(parts, density, first=0, direct_s=0.0025, rate=None):
+    """`parts` (an IrParts) with early_end at the mixing tap that `density` (ir_density's result) measured for the "LR" row and
+    direct_end direct_s seconds after the measurement's origin.  `first` is ir_shape_info(idx)["first"] when the measured load
+    trimmed the IR, else 0: the taps it skipped are added to both.  rate (Hz) defaults to the one the measurement's mix and
+    mix_s imply.  ValueError when the row's status is 1: the density never reached the threshold, and there is no mixing
+    tap."""
+    row = density["rows"]["LR"]
+    if row["status"] == 1 or not math.isfinite(row["mix"]):
+        raise ValueError("the density never reached the threshold: there is no mixing tap to put early_end at")
+    mix, origin = int(row["mix"]), int(density["origin"])
+    if rate is None:
+        rate = (mix - origin) / row["mix_s"] if mix > origin and row["mix_s"] > 0 else 0.0
+    direct = min(int(math.floor(direct_s * rate + 0.5)), max(mix - origin, 0))
+    p = parts.to_c()
+    check(_lib.load().mc_ir_parts_at(C.byref(p), int(first) + origin, direct, max(mix - origin, 0)))
+    return dataclasses.replace(parts, direct_end=int(p.direct_end), early_end=int(p.early_end))
+
+
 def tail_from_floor(floor, first=0, mode="extend", fade=0, length=0, seed=0, width=1.0):
     """The IrTail that repairs the tail `floor` (ir_floor's result) found: per band the knee, the decay and the two channels'
     levels of the measured lines (mc_ir_tail_from_floor, host arithmetic only).  A band without a knee inside the analysed
@@ -916,7 +1015,7 @@ class Convolution:
         check(self._L.mc_set_period(self._h, nframes))
 
     # -- reference surface ----------------------------------------------------
-    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None, damp=None, tail=None, phase=None, filter=None, match=None):
+    def prepare(self, idx, wav, nframes=1024, ir_rate=None, shape=None, eq=None, damp=None, tail=None, phase=None, filter=None, match=None, parts=None):
         """Convolution::prepare (conv.cu:207-253).  `wav` is float32 [frames, 2]
         (what WavFile.buffer holds) or an object with a `.buffer` of that shape.
         ir_rate (Hz; default: `wav.sampleRate` when it has one): when both it and the engine's sample_rate are known and
@@ -936,13 +1035,17 @@ class Convolution:
         ir_filter_info(idx) then tells what was done.
         match (an IrMatch whose mode is not "off"): give the frames the smoothed spectrum of a target IR, or a flat one, after
         the filter step and before the shape (mc_load_ir_match); the engine needs a sample_rate; ir_match_info(idx) and
-        ir_match_curve(idx) then tell what was done."""
+        ir_match_curve(idx) then tell what was done.
+        parts (an IrParts whose mode is not "off"): the direct sound, the early reflections and the late tail get a gain, a
+        delay, a width and a balance each, after the match step and before the shape (mc_load_ir_parts); it needs no rate;
+        ir_parts_info(idx) then tells what was done."""
         lr = _f32(getattr(wav, "buffer", wav)).reshape(-1, 2)
         if ir_rate is None:
             ir_rate = getattr(wav, "sampleRate", None)
         filtered = filter is not None and filter.op != "off"
         matched = match is not None and match.on()
-        if matched or filtered or (phase is not None and phase.mode != "off"):
+        parted = parts is not None and parts.on()
+        if parted or matched or filtered or (phase is not None and phase.mode != "off"):
             tailed = tail is not None and tail.mode != "off"
             if matched or tailed or eq is not None or (damp is not None and damp.xovers) or (filtered and filter.to_c().rate and self.sample_rate):
                 session = int(self.sample_rate or 0)
@@ -955,7 +1058,12 @@ class Convolution:
                     C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
                     C.byref(damp.to_c()) if damp is not None else None, C.byref(tail.to_c()) if tailed else None,
                     C.byref(phase.to_c()) if phase is not None else None)
-            if matched:
+            if parted:
+                flr = filter.frames() if filtered else None
+                margs, keep = match.c_args() if matched else ((None, None, 0), None)
+                check(self._L.mc_load_ir_parts(*args, C.byref(filter.to_c()) if filtered else None, _fp(flr) if filtered else None,
+                                               flr.shape[0] if filtered else 0, *margs, C.byref(parts.to_c())))
+            elif matched:
                 flr = filter.frames() if filtered else None
                 margs, keep = match.c_args()
                 check(self._L.mc_load_ir_match(*args, C.byref(filter.to_c()) if filtered else None, _fp(flr) if filtered else None,
@@ -1029,7 +1137,7 @@ class Convolution:
         check(self._L.mc_synth_ir(self._h, idx, nframes, C.byref(s), C.byref(shape.to_c()) if shape is not None else None,
                                   C.byref(eq.to_c()) if eq is not None else None, C.byref(damp.to_c()) if damp is not None else None))
 
-    def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None, tail=None, phase=None, filter=None, match=None):
+    def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None, tail=None, phase=None, filter=None, match=None, parts=None):
         """Deconvolve `recording` (float32 [frames, 2] or an object with such a `.buffer`: what was recorded while `sweep`, a
         Sweep, played) into an IR on the device and store it at idx (mc_load_ir_sweep): the frames take the place of a WAV's at
         the session's rate, and shape, eq and damp apply to them as in prepare().  IR frame m is the correlation at lag
@@ -1040,7 +1148,8 @@ class Convolution:
         tail step on the deconvolved frames (mc_load_ir_sweep_tail).  phase (an IrPhase whose mode is not "off"): the phase step
         after it (mc_load_ir_sweep_phase).  filter (an IrFilter whose op is not "off"): the filter step after that
         (mc_load_ir_sweep_filter), the session's rate being the sweep's.  match (an IrMatch whose mode is not "off"): the match
-        step after that (mc_load_ir_sweep_match)."""
+        step after that (mc_load_ir_sweep_match).  parts (an IrParts whose mode is not "off"): the parts step after that
+        (mc_load_ir_sweep_parts)."""
         lr = _f32(getattr(recording, "buffer", recording)).reshape(-1, 2)
         s = sweep.to_c()
         if not sweep.rate and self.sample_rate:
@@ -1051,7 +1160,14 @@ class Convolution:
         args = (self._h, idx, _fp(lr), lr.shape[0], nframes, C.byref(s), int(offset), int(ir_frames),
                 C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
                 C.byref(damp.to_c()) if damp is not None else None)
-        if match is not None and match.on():
+        if parts is not None and parts.on():
+            filtered = filter is not None and filter.op != "off"
+            flr = filter.frames() if filtered else None
+            margs, keep = match.c_args() if match is not None and match.on() else ((None, None, 0), None)
+            check(self._L.mc_load_ir_sweep_parts(*args, C.byref(tail.to_c()) if tail is not None else None, C.byref(phase.to_c()) if phase is not None else None,
+                                                 C.byref(filter.to_c()) if filtered else None, _fp(flr) if filtered else None, flr.shape[0] if filtered else 0,
+                                                 *margs, C.byref(parts.to_c())))
+        elif match is not None and match.on():
             filtered = filter is not None and filter.op != "off"
             flr = filter.frames() if filtered else None
             margs, keep = match.c_args()
@@ -1448,6 +1564,19 @@ class Convolution:
         return dict(frames=int(out[0]), target_frames=int(out[1]), frames_out=int(out[2]), nfft=int(out[3]), points=int(out[4]), energy_in=float(out[5]),
                     energy_target=float(out[6]), energy_out=float(out[7]), energy_rest=float(out[8]), mean_db=(float(out[9]), float(out[10])),
                     clamped=int(out[11]))
+
+    def ir_parts_info(self, idx):
+        """What the parts step of IR idx's load did (mc_ir_parts_info): the frames it took and handed on, the two boundaries
+        clamped to the frames, the weighted energy of the direct, the early and the late part as they came in (muted or not),
+        drr_db = 10 log10(direct / (early + late)), the energy of what was stored, and the energy and the number of the
+        contributions that landed outside the frames handed on.  McError (MC_ERR_STATE) for an IR whose last load had no parts
+        step."""
+        out = (C.c_double * 10)()
+        check(self._L.mc_ir_parts_info(self._h, idx, out))
+        rest = float(out[5]) + float(out[6])
+        drr = 10.0 * math.log10(float(out[4]) / rest) if out[4] > 0 and rest > 0 else (math.inf if out[4] > 0 else -math.inf if rest > 0 else math.nan)
+        return dict(frames=int(out[0]), frames_out=int(out[1]), direct_end=int(out[2]), early_end=int(out[3]), energy_direct=float(out[4]),
+                    energy_early=float(out[5]), energy_late=float(out[6]), drr_db=drr, energy_out=float(out[7]), energy_lost=float(out[8]), lost=int(out[9]))
 
     def ir_match_curve(self, idx):
         """The curve of IR idx's match step (mc_ir_match_curve): hz [J], before_db [J, 2] (the smoothed difference to the target

@@ -95,6 +95,15 @@ int mc_load_ir_sweep_match(mc_engine*, uint64_t, const float*, uint64_t, uint64_
                            const float*, uint64_t) __attribute__((weak));
 int mc_ir_match_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 int mc_ir_match_curve(const mc_engine*, uint64_t, double*, double*, double*, uint32_t) __attribute__((weak));
+void mc_default_ir_parts(mc_ir_parts*) __attribute__((weak));
+int mc_load_ir_parts(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, uint32_t, uint32_t, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
+                     const mc_ir_tail*, const mc_ir_phase*, const mc_ir_filter*, const float*, uint64_t, const mc_ir_match*, const float*, uint64_t,
+                     const mc_ir_parts*) __attribute__((weak));
+int mc_load_ir_sweep_parts(mc_engine*, uint64_t, const float*, uint64_t, uint64_t, const mc_sweep*, int64_t, uint64_t, const mc_ir_shape*, const mc_ir_eq*,
+                           const mc_ir_damp*, const mc_ir_tail*, const mc_ir_phase*, const mc_ir_filter*, const float*, uint64_t, const mc_ir_match*,
+                           const float*, uint64_t, const mc_ir_parts*) __attribute__((weak));
+int mc_ir_parts_at(mc_ir_parts*, uint64_t, uint64_t, uint64_t) __attribute__((weak));
+int mc_ir_parts_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 // ... and no room
 void mc_default_ir_room(mc_ir_room*) __attribute__((weak));
 int mc_synth_ir_room(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_room*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
@@ -256,6 +265,12 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         Log::error("conv", "the engine has no match step (mc_load_ir_match)");
         std::exit(2);
     }
+    const bool parted = _irParts.on && !synth;
+    if (_irParts.on && synth) Log::info(name, "IR %zu is generated: it has no parts step and is loaded as it is", idx);
+    if (parted && (!mc_default_ir_parts || !mc_load_ir_parts || !mc_load_ir_sweep_parts || !mc_ir_parts_at || !mc_ir_parts_info)) {
+        Log::error("conv", "the engine has no parts step (mc_load_ir_parts)");
+        std::exit(2);
+    }
     if (tail && (!mc_load_ir_tail || !mc_load_ir_sweep_tail || !mc_ir_tail_info)) {
         Log::error("conv", "the engine has no tail step (mc_load_ir_tail)");
         std::exit(2);
@@ -334,6 +349,26 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         mt.delay = (uint32_t)dampFrames(_irMatch.delaySeconds, (double)session);
         if (!sessionRate) irRate = sessionRate = session;
     }
+    mc_ir_parts pt;
+    if (parted) {
+        // seconds become frames at the session's rate; frames that are loaded at the rate they have are at the client's
+        const double session = (double)(sweep ? sweep->sweep.rate : sessionRate ? sessionRate : (unsigned)samplerate);
+        mc_default_ir_parts(&pt);
+        pt.mode = MC_PARTS_ON;
+        for (int k = 0; k < 3; k++) {
+            pt.flags |= (_irParts.mute[k] ? MC_PARTS_MUTE(k) : 0u) | (_irParts.swap[k] ? MC_PARTS_SWAP(k) : 0u) | (_irParts.invert[k] ? MC_PARTS_INVERT(k) : 0u);
+            pt.delay[k] = (int32_t)std::nearbyint(_irParts.delaySeconds[k] * session);
+            pt.gain_db[k] = _irParts.gainDb[k], pt.width[k] = _irParts.width[k], pt.balance[k] = _irParts.balance[k];
+        }
+        for (int k = 0; k < 2; k++) pt.xfade[k] = (uint32_t)dampFrames(_irParts.xfadeSeconds[k], session);
+        const uint64_t onset = _partsMeasured ? _partsOnset : dampFrames(_irParts.onsetSeconds, session);
+        const uint64_t first = dampFrames(_irParts.firstSeconds, session);
+        const uint64_t split = _partsMeasured ? _partsMix - _partsOnset : dampFrames(_irParts.splitSeconds, session);
+        if (mc_ir_parts_at(&pt, onset, std::min(first, split), split) != MC_OK) {
+            Log::error("conv", "IR %zu cannot be split into parts: %s", idx, mc_last_error());
+            std::exit(2);
+        }
+    }
     if (!eq.off()) {
         mc_default_ir_eq(&q);
         for (size_t k = 0; k < eq.bands.size(); k++) q.band[k] = mc_eq_band{(uint32_t)eq.bands[k].kind, eq.bands[k].hz, eq.bands[k].gainDb, eq.bands[k].q};
@@ -385,7 +420,11 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         Log::info(name, "IR %zu synthesised: %llu frames, seed %llu, %d of %u reflections kept", idx, (unsigned long long)si[0],
                   (unsigned long long)synth->seed, (int)si[1], synth->n_early);
     } else if (sweep) {  // (as for a generated IR: what the engine refuses is the index line's fault)
-        const int rc = matched ? mc_load_ir_sweep_match(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
+        const int rc = parted ? mc_load_ir_sweep_parts(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
+                                                       eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, minimum ? &ph : nullptr,
+                                                       filtered ? &fl : nullptr, _irFilter.lr.data(), flFrames, matched ? &mt : nullptr, _irMatch.lr.data(),
+                                                       mtFrames, &pt)
+                       : matched ? mc_load_ir_sweep_match(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
                                                         eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, minimum ? &ph : nullptr,
                                                         filtered ? &fl : nullptr, _irFilter.lr.data(), flFrames, &mt, _irMatch.lr.data(), mtFrames)
                        : filtered ? mc_load_ir_sweep_filter(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
@@ -405,6 +444,13 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         check(mc_ir_sweep_info(_engine, idx, wi), "mc_ir_sweep_info");
         Log::info(name, "IR %zu captured: sweep %llu frames, recording %llu frames, %llu frames at offset %lld", idx, (unsigned long long)wi[0],
                   (unsigned long long)wi[1], (unsigned long long)wi[2], (long long)wi[3]);
+    } else if (parted) {  // (boundaries and delays that leave nothing are the command line's fault: a message and exit 2, no abort)
+        if (mc_load_ir_parts(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail,
+                             minimum ? &ph : nullptr, filtered ? &fl : nullptr, _irFilter.lr.data(), flFrames, matched ? &mt : nullptr, _irMatch.lr.data(),
+                             mtFrames, &pt) != MC_OK) {
+            Log::error("conv", "IR %zu cannot be split into parts: %s", idx, mc_last_error());
+            std::exit(2);
+        }
     } else if (matched) {  // (lengths and a grid beyond the step are the command line's fault: a message and exit 2, no abort)
         if (mc_load_ir_match(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail,
                              minimum ? &ph : nullptr, filtered ? &fl : nullptr, _irFilter.lr.data(), flFrames, &mt, _irMatch.lr.data(), mtFrames) != MC_OK) {
@@ -472,6 +518,15 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
             for (int j = 0; j < J; j++)
                 Log::info(name, "IR %zu match %.3f Hz: before %+.4f %+.4f dB, gain %+.4f %+.4f dB", idx, hz[j], before[2 * j], before[2 * j + 1], gain[2 * j],
                           gain[2 * j + 1]);
+    }
+    if (parted) {
+        double pi[10];
+        check(mc_ir_parts_info(_engine, idx, pi), "mc_ir_parts_info");
+        const double rest = pi[5] + pi[6];
+        Log::info(name, "IR %zu parts: %llu frames in, %llu out, direct to %llu, early to %llu%s, energies %.6e / %.6e / %.6e, direct to reverberant %+.2f dB, level %+.2f dB, %llu contributions lost (%.6e)",
+                  idx, (unsigned long long)pi[0], (unsigned long long)pi[1], (unsigned long long)pi[2], (unsigned long long)pi[3],
+                  _partsMeasured ? " (the mixing tap)" : "", pi[4], pi[5], pi[6], pi[4] > 0.0 && rest > 0.0 ? 10.0 * std::log10(pi[4] / rest) : 0.0,
+                  pi[4] + rest > 0.0 && pi[7] > 0.0 ? 10.0 * std::log10(pi[7] / (pi[4] + rest)) : 0.0, (unsigned long long)pi[9], pi[8]);
     }
     double info[8];
     check(mc_ir_shape_info(_engine, idx, info), "mc_ir_shape_info");
@@ -636,6 +691,122 @@ void Convolution::setIrFilter(const IrFilter& filter) {
         std::exit(2);
     }
     _irFilter = filter;
+}
+
+void Convolution::setIrParts(const IrParts& parts) {
+    if (parts.on && _group) {
+        Log::error("conv", "the IR parts step is not available with several devices (mc_load_ir_parts is single-engine)");
+        std::exit(2);
+    }
+    _irParts = parts;
+}
+
+bool Convolution::parseParts(const std::string& arg, IrParts& out, std::string& why) {
+    const auto fail = [&](const std::string& w) {
+        why = w + " (key=value,... with keys direct, early, late, split, first, onset, xfade, delay, width, balance, swap, invert)";
+        return false;
+    };
+    static const char* const names[3] = {"direct", "early", "late"};
+    if (arg.empty()) return fail("an empty list");
+    IrParts p;
+    p.on = true;
+    // `count` numbers joined by ':' (or one for all when `one`), each finite and within [lo, hi]
+    const auto numbers = [](const std::string& val, size_t count, bool one, double lo, double hi, double* v) {
+        std::vector<double> got;
+        for (size_t at = 0; at <= val.size();) {
+            const size_t colon = std::min(val.find(':', at), val.size());
+            const std::string item = val.substr(at, colon - at);
+            at = colon + 1;
+            char* end = nullptr;
+            const double x = std::strtod(item.c_str(), &end);
+            if (item.empty() || *end || !std::isfinite(x) || x < lo || x > hi) return false;
+            got.push_back(x);
+        }
+        if (got.size() != count && !(one && got.size() == 1)) return false;
+        for (size_t k = 0; k < count; k++) v[k] = got[got.size() == 1 ? 0 : k];
+        return true;
+    };
+    for (size_t at = 0; at <= arg.size();) {
+        const size_t comma = std::min(arg.find(',', at), arg.size());
+        const std::string item = arg.substr(at, comma - at);
+        at = comma + 1;
+        const size_t eqs = item.find('=');
+        if (item == "swap" || item == "invert") {  // (alone: all three parts)
+            for (int k = 0; k < 3; k++) (item == "swap" ? p.swap : p.invert)[k] = true;
+            continue;
+        }
+        if (item.empty() || eqs == std::string::npos || eqs == 0 || eqs + 1 == item.size()) return fail("'" + item + "' is not key=value");
+        const std::string key = item.substr(0, eqs), val = item.substr(eqs + 1);
+        double v[3];
+        if (key == "direct" || key == "early" || key == "late") {
+            const int k = key == "direct" ? 0 : key == "early" ? 1 : 2;
+            if (val == "off") {
+                p.mute[k] = true;
+                continue;
+            }
+            if (!numbers(val, 1, true, -120.0, 24.0, v)) return fail(key + " is a gain in dB within [-120, 24] or off, not '" + val + "'");
+            p.gainDb[k] = (float)v[0], p.mute[k] = false;
+        } else if (key == "split") {
+            p.splitAtMix = val == "mix";
+            if (!p.splitAtMix && !numbers(val, 1, true, 0.0, 100.0, &p.splitSeconds)) return fail("split is a time in seconds within [0, 100] or mix, not '" + val + "'");
+        } else if (key == "first" || key == "onset") {
+            if (!numbers(val, 1, true, 0.0, 100.0, key == "first" ? &p.firstSeconds : &p.onsetSeconds))
+                return fail(key + " is a time in seconds within [0, 100], not '" + val + "'");
+        } else if (key == "xfade") {
+            if (!numbers(val, 2, false, 0.0, 100.0, p.xfadeSeconds)) return fail("xfade is S:S, two times in seconds within [0, 100], not '" + val + "'");
+        } else if (key == "delay") {
+            if (!numbers(val, 3, false, -10.0, 10.0, p.delaySeconds)) return fail("delay is S:S:S, three times in seconds within [-10, 10], not '" + val + "'");
+        } else if (key == "width" || key == "balance") {
+            const bool w = key == "width";
+            if (!numbers(val, 3, true, w ? 0.0 : -1.0, w ? 2.0 : 1.0, v)) return fail(key + (w ? " is one number or W:W:W within [0, 2], not '" : " is one number or B:B:B within [-1, 1], not '") + val + "'");
+            for (int k = 0; k < 3; k++) (w ? p.width : p.balance)[k] = (float)v[k];
+        } else if (key == "swap" || key == "invert") {
+            for (size_t from = 0; from <= val.size();) {
+                const size_t colon = std::min(val.find(':', from), val.size());
+                const std::string part = val.substr(from, colon - from);
+                from = colon + 1;
+                int k = 0;
+                while (k < 3 && part != names[k]) k++;
+                if (k == 3) return fail(key + " names parts (direct, early, late) joined by ':', not '" + val + "'");
+                (key == "swap" ? p.swap : p.invert)[k] = true;
+            }
+        } else
+            return fail("no such key '" + key + "'");
+    }
+    if (!p.splitAtMix && p.splitSeconds < p.firstSeconds) return fail("split is before first");
+    if (p.mute[0] && p.mute[1] && p.mute[2]) return fail("every part is off");
+    out = p;
+    return true;
+}
+
+// Loads p with every step but the parts and with no shape, EQ or damping, measures its echo density and leaves in _partsOnset /
+// _partsMix / _partsMeasured the boundaries its final load goes through
+void Convolution::measureParts(const PendingIr& p) {
+    _partsMeasured = false;
+    if (!mc_default_ir_parts || !mc_load_ir_parts || !mc_load_ir_sweep_parts || !mc_ir_parts_at || !mc_ir_parts_info) {
+        Log::error("conv", "the engine has no parts step (mc_load_ir_parts)");
+        std::exit(2);
+    }
+    if (p.generated) return;  // (loadShaped says that it has no parts step)
+    PendingIr raw = p;
+    raw.eq = IrEq();
+    raw.damp = IrDamp();
+    IrParts parts;
+    std::swap(parts, _irParts);
+    loadPending(raw, IrShape());
+    std::swap(parts, _irParts);
+    const Density d = irDensity(p.idx, _densityQuery);
+    _partsOnset = d.origin;
+    if (d.at(Decay::LR, Density::Status) != 0.0) {
+        _partsMix = _partsOnset + (uint64_t)std::nearbyint(0.08 * (double)samplerate);
+        Log::warn(name, "IR %zu parts: the echo density never reaches 1 (largest %s), the early part ends 80 ms after the onset at frame %llu", p.idx,
+                  places(d.at(Decay::LR, Density::Max), 3).c_str(), (unsigned long long)_partsOnset);
+    } else {
+        _partsMix = std::max<uint64_t>((uint64_t)d.at(Decay::LR, Density::Mix), _partsOnset);
+        Log::info(name, "IR %zu parts: onset at frame %llu, the early part ends at the mixing tap %llu", p.idx, (unsigned long long)_partsOnset,
+                  (unsigned long long)_partsMix);
+    }
+    _partsMeasured = true;
 }
 
 void Convolution::setIrMatch(const IrMatch& match, bool report) {
@@ -1767,7 +1938,7 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
                    nullptr, _tailOn ? &_tailNow : nullptr);
         return;
     }
-    if (!shape.off() || _irPhase.minimum || _irFilter.on || _irMatch.on) {
+    if (!shape.off() || _irPhase.minimum || _irFilter.on || _irMatch.on || _irParts.on) {
         loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : 0, convert ? (unsigned)samplerate : 0, shape);
         return;
     }
@@ -1786,6 +1957,7 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
 void Convolution::loadPendingIrs() {
     for (const PendingIr& p : _pendingIrs) {
         if (_irTail.mode != IrTail::Off) measureTail(p);
+        if (_irParts.on && _irParts.splitAtMix) measureParts(p);
         loadPending(p, p.shape);
         if (_rt60 > 0.0) aimRt60(p);
         if (_decayReport) reportDecay(p.idx);
@@ -1795,12 +1967,13 @@ void Convolution::loadPendingIrs() {
         if (_stiReport) reportSti(p.idx);
         if (_responseReport) reportResponse(p.idx);
         _tailOn = false;
+        _partsMeasured = false;
     }
     _pendingIrs.clear();
 }
 
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
-    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _stiReport || _responseReport || _irTail.mode != IrTail::Off || _irPhase.minimum || _irFilter.on || _irMatch.on) {  // (loaded by onStart(), once the client's rate is known)
+    if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _stiReport || _responseReport || _irTail.mode != IrTail::Off || _irPhase.minimum || _irFilter.on || _irMatch.on || _irParts.on) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
         _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth(), false, IrSweep()});
         if (idx + 1 > _nirs) _nirs = idx + 1;

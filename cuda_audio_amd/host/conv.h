@@ -442,6 +442,27 @@ public:
     // link (0, 1), phase (minimum, linear), delay (seconds) and tilt (dB per octave), as an IrMatch without its frames.  False,
     // with the reason in `why`, for a malformed one.
     static bool parseMatch(const std::string& arg, IrMatch& out, std::string& why);
+    // The parts step every IR loaded from now on goes through (mc_ir_parts of include/mcconv.h; no reference equivalent): the
+    // direct sound, the early reflections and the late tail get a gain (or are muted), a delay, a width and a balance each, after
+    // the match step and ahead of the shape, EQ and damping.  The direct part ends firstSeconds and the early part splitSeconds
+    // after onsetSeconds; with splitAtMix the IR is loaded once without the step, its echo density is measured, and the onset and
+    // the early part's end are the measurement's origin and mixing tap (80 ms after the origin when the density never reaches
+    // 1).  One log line per load tells the boundaries, the parts' energies and what was lost.  Loaded by onStart(), single
+    // device only.  A generated IR has no parts step and is loaded as it is, with a log line that says so.
+    struct IrParts {
+        bool on = false;
+        bool mute[3] = {false, false, false}, swap[3] = {false, false, false}, invert[3] = {false, false, false};
+        float gainDb[3] = {0.f, 0.f, 0.f};
+        float width[3] = {1.f, 1.f, 1.f}, balance[3] = {0.f, 0.f, 0.f};
+        double delaySeconds[3] = {0.0, 0.0, 0.0}, xfadeSeconds[2] = {0.0, 0.0};
+        double onsetSeconds = 0.0, firstSeconds = 0.0025, splitSeconds = 0.08;
+        bool splitAtMix = false;
+    };
+    void setIrParts(const IrParts& parts);
+    // The argument of --ir-parts, key=value,... with keys direct, early, late (dB, or off), split (seconds, or mix), first, onset
+    // (seconds), xfade (S:S), delay (S:S:S), width and balance (one number or three) and swap, invert (part names joined by ':'), as
+    // an IrParts.  False, with the reason in `why`, for a malformed one.
+    static bool parseParts(const std::string& arg, IrParts& out, std::string& why);
 
     void onMidiMessage(const RawMidi::Device* sender, const uint8_t* buffer, size_t len) override;
 
@@ -504,6 +525,10 @@ private:
     IrFilter _irFilter;
     IrMatch _irMatch;
     bool _irMatchReport = false;
+    IrParts _irParts;
+    void measureParts(const PendingIr& p);
+    bool _partsMeasured = false;  // loadPending: the IR being loaded has its boundaries in _partsOnset and _partsMix
+    uint64_t _partsOnset = 0, _partsMix = 0;
     bool _tailOn = false;  // loadPending: the IR being loaded goes through _tailNow
     mc_ir_tail _tailNow;
     bool _decayReport = false;

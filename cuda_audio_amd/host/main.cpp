@@ -60,6 +60,16 @@
 // its mean, is bounded to boost and cut dB (12 and 24 without) and applied as a minimum-phase correction, or with phase=linear
 // as a linear-phase one that delays the IR by delay seconds; link=0 gives each channel a curve of its own; one log line tells the
 // lengths, the curve's range and the level.  --ir-match-report: one more line per grid point with the curve.
+// --ir-parts direct=DB|off,early=DB|off,late=DB|off[,split=SECONDS|mix,first=SECONDS,onset=SECONDS,xfade=S:S,delay=S:S:S,width=W[:W:W],
+// balance=B[:B:B],swap[=PARTS],invert[=PARTS]]: every IR (a WAV or a captured sweep; a generated one is left as it is) is split on
+// load into its direct sound, its early reflections and its late tail, after --ir-match's step and ahead of the other --ir-*
+// options (Convolution::setIrParts): each part gets a gain in dB or is taken out (off), a delay in seconds (negative: earlier), a
+// width (0 mono, 1 as it is, 2 the side signal doubled) and a balance (-1 left .. +1 right); the direct part ends `first` seconds
+// (2.5 ms without) and the early part `split` seconds (80 ms without) after `onset` (0 without), with cross-fades of xfade
+// seconds around the two; split=mix: the IR is loaded once without the step, and the onset and the early part's end are the
+// origin and the mixing tap of its echo density (--ir-density-window and -hop apply); swap exchanges and invert negates the
+// channels of the named parts (direct:early:late; all without names); one log line tells the boundaries, the energies and what
+// was lost.
 // --ir-density-report: after each IR is loaded one log line with its echo density (origin, mixing tap and time, first, largest and
 // later density of the LR row, measured by the engine: Convolution::setIrDensityReport); --ir-density-window SECONDS: the whole
 // window (20 ms without), --ir-density-hop SECONDS: between window centres (an eighth of the window without), --ir-density-t60
@@ -108,6 +118,7 @@ int main(int argc, char** argv) {
     Convolution::IrPhase irPhase;
     Convolution::IrFilter irFilter;
     Convolution::IrMatch irMatch;
+    Convolution::IrParts irParts;
     bool irMatchReport = false;
     bool irDensityReport = false;
     Convolution::DensityQuery irDensity;
@@ -264,6 +275,12 @@ int main(int argc, char** argv) {
                 irMatch.rate = wav.sampleRate;
                 irMatch.lr.assign(&wav.buffer[0].x, &wav.buffer[0].x + 2 * wav.numFrames);
             }
+        } else if (!strcmp(argv[i], "--ir-parts") && i + 1 < argc) {
+            std::string why;
+            if (!Convolution::parseParts(argv[++i], irParts, why)) {
+                std::cerr << "--ir-parts '" << argv[i] << "': " << why << std::endl;
+                return 2;
+            }
         } else if (!strcmp(argv[i], "--ir-match-report")) irMatchReport = true;
         else if (!strcmp(argv[i], "--ir-density-report")) irDensityReport = true;
         else if ((!strcmp(argv[i], "--ir-density-window") || !strcmp(argv[i], "--ir-density-hop") || !strcmp(argv[i], "--ir-density-t60")) && i + 1 < argc) {
@@ -348,6 +365,7 @@ int main(int argc, char** argv) {
         c->setIrPhase(irPhase);
         c->setIrFilter(irFilter);
         c->setIrMatch(irMatch, irMatchReport);
+        c->setIrParts(irParts);
         for (int i = 0; i < 2; i++) {
             const int idx = n * 2 + i;
             const auto deviceId = settings.str("conv[%d].cc.device", idx);

@@ -155,6 +155,9 @@ int mc_load_ir_resampled(mc_engine *e, uint64_t idx, const float *lr, uint64_t f
  *      that follows;
  *   1d. (mc_load_ir_match and mc_load_ir_sweep_match only) the F frames are given the smoothed spectrum of a target impulse
  *      response, or a flat or tilted one, by a match EQ (mc_ir_match below); Fo frames leave the step likewise;
+ *   1e. (mc_load_ir_parts and mc_load_ir_sweep_parts only) the F frames are split into the direct sound, the early reflections
+ *      and the late tail, each with a gain, a delay, a width and a balance of its own (mc_ir_parts below); Fo frames leave the
+ *      step likewise, and the onset search of step 2 sees them;
  *   2. s0 = min(start, F); with trim_db < 0 the onset is the first frame m after s0 whose max(|L|, |R|) reaches
  *      peak * 10^(trim_db / 20) (float arithmetic; peak over all frames after s0); first = s0 + max(0, onset - pre_roll);
  *   3. n = min(F - first, length or unlimited, n_ref - nframes) frames are stored (n = 0: MC_ERR_ARG, nothing changes);
@@ -1001,6 +1004,92 @@ int mc_ir_match_info(const mc_engine *e, uint64_t idx, double out[12]);
  * (both channels hold the same numbers when linked), j < J.  Returns J; MC_ERR_ARG for a null pointer or cap < J (hz holds cap
  * numbers, before_db and gain_db 2 cap each); MC_ERR_STATE unless the IR's last load had the step on. */
 int mc_ir_match_curve(const mc_engine *e, uint64_t idx, double *hz, double *before_db, double *gain_db, uint32_t cap);
+
+/* The parts step of an IR load (step 1e of the order of operations above): the direct sound, the early reflections and the
+ * late tail as three parts with controls of their own, as a convolution reverb offers them after "load".  The step is linear
+ * in the taps, so it happens once at load time.  No reference equivalent; single-engine.  DESIGN.md 2.22 has the reasons.
+ *
+ * Positions are frames of the F frames that reach the step (after steps 1 .. 1d).  Part p = 0 is the direct sound, frames
+ * before b_0 = direct_end; p = 1 the early reflections, from b_0 to b_1 = early_end; p = 2 the late tail, from b_1 on.  Either
+ * boundary may lie past F, and the later parts are then empty.  Boundary k has a raised-cosine cross-fade of x_k = xfade[k]
+ * frames around it that begins at s_k = b_k - floor(x_k / 2); s_0 >= 0 and s_0 + x_0 <= s_1 are required.  Weights of input
+ * frame m (the shape's fade form), in double:
+ *   u_k(m) = 0 for m < s_k, 1 for m >= s_k + x_k, else (1 - cos(pi (m - s_k + 1) / (x_k + 1))) / 2;
+ *   w_0 = 1 - u_0, w_1 = u_0 - u_1, w_2 = u_1; x_k = 0 is a hard cut at b_k.
+ * Coefficients of part p, made on the host in double from the struct's floats:
+ *   g = 10^(gain_db / 20), negated when the part is inverted; a = (1 + width) / 2, b = (1 - width) / 2;
+ *   gl = balance > 0 ? 1 - balance : 1, gr = balance < 0 ? 1 + balance : 1 (the synthesiser's pan law);
+ *   c_LL = g gl a, c_LR = g gl b, c_RL = g gr b, c_RR = g gr a; when the part's input channels are swapped c_LL and c_LR change
+ *   places, and c_RL and c_RR.
+ * Output frame n, the parts that are not muted in the order p = 0, 1, 2, in double:
+ *   m = n - delay_p, used when 0 <= m < F and w_p(m) > 0; t = w_p(m) x[m] per channel;
+ *   acc_L += fma(c_LR, t_R, c_LL t_L); acc_R += fma(c_RL, t_L, c_RR t_R); the frame is (float) acc, rounded once.
+ * Fo = frames_out when that is set, in [1, F + 2^24].  Otherwise Fo = the largest of (the end of part p's frames inside
+ * [0, F)) + delay_p over the parts that are neither muted nor empty, where part 0 ends at min(F, s_0 + x_0), part 1 holds
+ * [s_0, min(F, s_1 + x_1)) and part 2 [s_1, F).  Without such a part, or with that largest value <= 0, the load is refused.
+ * Contributions that land outside [0, Fo) are dropped and reported.  Fo takes F's place in everything after the step.
+ * Two consequences:
+ *   - unity parts store the input's values: with gains of 0 dB, width 1, balance 0, no delay and no flag the stored values are
+ *     the input's whatever the boundaries and the cross-fades (x w_0 + x w_1 + x w_2 in double lies within a few 2^-53 of the
+ *     float x and rounds back to it; compared as values, -0 being +0);
+ *   - width 0 stores equal channels bit for bit: fma(.5, R, .5 L) and fma(.5, L, .5 R) are the same rounded sum.
+ * The onset search of step 2 sees the step's output: with the direct part muted and trim_db < 0 the trim moves to the first
+ * reflection, which is then the caller's choice.  The same frames and struct store the same bits on every run.
+ * Synthesised loads (mc_synth_ir and the room entry points) have no parts entry point: they have direct, reflection and late
+ * gains of their own. */
+enum { MC_PARTS_OFF = 0, MC_PARTS_ON = 1 };
+#define MC_PARTS_MUTE(p) (1u << (p))         /* p = 0 direct, 1 early, 2 late */
+#define MC_PARTS_SWAP(p) (1u << (4 + (p)))   /* the part's input channels change places */
+#define MC_PARTS_INVERT(p) (1u << (8 + (p))) /* the part's sign */
+typedef struct {
+    uint32_t struct_size; /* sizeof(mc_ir_parts) = 104 */
+    uint32_t mode;        /* MC_PARTS_OFF / ON; MC_PARTS_OFF: every other field ignored */
+    uint32_t flags;       /* MC_PARTS_MUTE / SWAP / INVERT of p = 0, 1, 2; unknown bits: MC_ERR_ARG */
+    uint32_t reserved0;   /* must be 0 */
+    uint64_t direct_end;  /* b_0 <= 2^40 */
+    uint64_t early_end;   /* b_1, b_0 <= b_1 <= 2^40 */
+    uint32_t xfade[2];    /* x_0, x_1: b_0 >= floor(x_0 / 2) and s_0 + x_0 <= s_1 */
+    int32_t delay[3];     /* frames, [-2^24, 2^24] */
+    float gain_db[3];     /* [-120, 24] */
+    float width[3];       /* [0, 2]: 0 mono, 1 as it is, 2 the side signal doubled */
+    float balance[3];     /* [-1, 1]: -1 left only, +1 right only */
+    uint64_t frames_out;  /* 0 = automatic; checked once F is known */
+    uint32_t reserved[2]; /* must be 0 */
+} mc_ir_parts;
+/* off; no flag; both boundaries 0 (everything is the late part); no cross-fade; no delay; 0 dB; width 1; balance 0; automatic */
+void mc_default_ir_parts(mc_ir_parts *p);
+/* What the step would do to `frames` frames, host arithmetic only: out = {Fo, s_0, s_1, bytes of device memory the step
+ * allocates while it runs}, coef[4 p + j] = c_LL, c_LR, c_RL, c_RR of part p.  MC_ERR_ARG for a null pointer, a field of `p`
+ * outside its range (MC_PARTS_OFF is planned as MC_PARTS_ON), frames = 0, or the limits below. */
+int mc_ir_parts_plan(const mc_ir_parts *p, uint64_t frames, double out[4], double coef[12]);
+/* b_0 = onset + direct_frames and b_1 = onset + early_frames, everything else of `parts` left as it is: the counterpart of
+ * mc_ir_tail_move_knee for an onset that mc_ir_shape_info or a measurement found.  Host arithmetic only.  MC_ERR_ARG for a null
+ * parts, a struct_size mismatch, early_frames < direct_frames or a boundary above 2^40. */
+int mc_ir_parts_at(mc_ir_parts *parts, uint64_t onset, uint64_t direct_frames, uint64_t early_frames);
+/* mc_load_ir_match with `parts` applied as step 1e.  With parts NULL or MC_PARTS_OFF the call is mc_load_ir_match itself, bit
+ * for bit; it leaves no parts information.  With the step on everything is checked before the engine or the device is touched
+ * (MC_ERR_ARG, the message names the field, the engine stays as it was): parts field by field in the struct's order, then
+ * everything mc_load_ir_match checks, in its order.  The step's limits come as soon as F is known, after the match step's:
+ * frames_out above F + 2^24, and every part muted, empty or delayed to before frame 0.  Such a load counts as shaped:
+ * mc_ir_shape_info's out[0] is Fo. */
+int mc_load_ir_parts(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, uint32_t ir_rate,
+                     uint32_t session_rate, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp, const mc_ir_tail *tail,
+                     const mc_ir_phase *phase, const mc_ir_filter *filter, const float *filter_lr, uint64_t filter_frames,
+                     const mc_ir_match *match, const float *target_lr, uint64_t target_frames, const mc_ir_parts *parts);
+/* mc_load_ir_sweep_match with `parts` applied to the deconvolved frames after the match step.  parts NULL or MC_PARTS_OFF:
+ * mc_load_ir_sweep_match itself, bit for bit.  With the step on: parts field by field, then everything mc_load_ir_sweep_match
+ * checks, in its order, with the step's limits after the match step's. */
+int mc_load_ir_sweep_parts(mc_engine *e, uint64_t idx, const float *lr, uint64_t frames, uint64_t nframes, const mc_sweep *sweep,
+                           int64_t offset, uint64_t ir_frames, const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp,
+                           const mc_ir_tail *tail, const mc_ir_phase *phase, const mc_ir_filter *filter, const float *filter_lr,
+                           uint64_t filter_frames, const mc_ir_match *match, const float *target_lr, uint64_t target_frames,
+                           const mc_ir_parts *parts);
+/* out = {F, Fo, b_0 clamped to F, b_1 clamped to F, E_direct, E_early, E_late, E_out, E_lost, contributions lost}: E_direct,
+ * E_early and E_late = the sum over both channels of w_p(m)^2 x[m]^2 of part p, muted or not (so E_direct / (E_early + E_late)
+ * is the IR's direct-to-reverberant ratio); E_out that of the Fo frames as stored, in float; E_lost that weighted energy of the
+ * contributions of parts that are not muted which landed outside [0, Fo), and the last number how many there were.  The sums
+ * are made of one partial per 256 frames, added in ascending order.  MC_ERR_STATE unless the IR's last load had the step on. */
+int mc_ir_parts_info(const mc_engine *e, uint64_t idx, double out[10]);
 
 /* The reflections of a rectangular room (Allen and Berkley's image-source method), added on the device to the frames
  * mc_ir_synth describes: the room itself - its size, where the source and the two receivers stand, how hard the walls are -
