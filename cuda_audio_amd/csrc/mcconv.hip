@@ -80,6 +80,14 @@ constexpr int kEvPool = 1024;
 constexpr int kPipe = 2;
 constexpr int kStampSlots = 64;  // timed launches between two drains whose kernels leave their own time stamps
 constexpr int kNchunk = 2;       // partition chunks of the streaming MAC: its workgroups per (bin, block)
+// fp16 storage: the exponent of an IR's power-of-two scale16 goes no higher, so that scale16 * FDL16_SCALE (<= 2^126) and its
+// reciprocal (>= 2^-126), which the streaming MAC multiplies into the gains, stay normal floats however quiet the IR (without it
+// an IR whose largest spectrum entry is below 2^-115 got scale16 = inf and an inverse of zero).  At the limit the inverse is
+// 2^-126, so its product with any gain below 1 (mac_stream_body, g * inv) is a SUBNORMAL float: the sum of such an IR is right
+// only because this build keeps fp32 subnormals (hipcc's default for gfx9; -fgpu-flush-denormals-to-zero would silence the IR).
+// tests/test_gpu_fp16_storage.py::test_quiet_ir runs that case at a wet gain of 0.3.  A lower limit would keep the product
+// normal but push the IR's own halves into the subnormal range instead; an IR this quiet gives up precision either way
+constexpr int kScale16MaxExp = 122;
 constexpr int kG2Pmax = 5632;    // longest block-axis convolution (partitions) the fused 8192-point form takes: measured crossover
                                  // with the split 16384-point form ~5700 (30 s IRs, P = 5168: 0.25 vs 0.27 ms for a third more blocks)
 
@@ -631,7 +639,7 @@ int consolidate_voices(mc_engine* e, int i) {
     if (e->half) {
         int ex = 0;
         if (bound16 > 0.0) std::frexp(bound16, &ex);
-        M.scale16 = std::ldexp(1.0f, 13 - ex);
+        M.scale16 = std::ldexp(1.0f, std::min(13 - ex, kScale16MaxExp));
         if (!M.d_H16) HIP_TRY(hipMalloc(&M.d_H16, sizeof(uint2) * (nH / 4)));
         hipLaunchKernelGGL(k_to_half, dim3(1024), dim3(256), 0, e->stream, M.d_H, M.d_H16, nH / 4, M.scale16);
         HIP_TRY(hipGetLastError());
@@ -3565,7 +3573,7 @@ int load_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const IrLoad& ld) {
         for (float v : host) mx = std::max(mx, std::fabs(v));
         int ex = 0;
         if (mx > 0.f) std::frexp(mx, &ex);
-        ir.scale16 = std::ldexp(1.0f, 13 - ex);
+        ir.scale16 = std::ldexp(1.0f, std::min(13 - ex, kScale16MaxExp));
         if (!ir.d_H16) HIP_TRY(hipMalloc(&ir.d_H16, sizeof(uint2) * nel));
         hipLaunchKernelGGL(k_to_half, dim3(1024), dim3(256), 0, e->stream, ir.d_H, ir.d_H16, nel, ir.scale16);
         HIP_TRY(hipGetLastError());
@@ -4879,14 +4887,31 @@ int mc_debug_read(mc_engine* e, int which, uint64_t idx, void* dst, uint64_t off
         std::memcpy(dst, reinterpret_cast<const char*>(c) + off, bytes);
         return MC_OK;
     }
+    if ((which >= 18 && which <= 20) && !e->half) return fail(MC_ERR_STATE, "item %d: the engine keeps no fp16 copies (precision = fp32)", which);
     const char* src = nullptr;
     uint64_t cap = 0;
     switch (which) {
-        case 0:
-            if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_H) return fail(MC_ERR_ARG, "IR not loaded");
+        case 0:  // (items 0, 18 and 20 also read the merged-IR entries kMaxIrs .. kMaxIrs + kMixIrs - 1)
+            if (idx >= (uint64_t)(kMaxIrs + kMixIrs) || !e->irs[idx].d_H) return fail(MC_ERR_ARG, "IR not loaded");
             src = (const char*)e->irs[idx].d_H;
             cap = sizeof(float4) * (uint64_t)MC_NB * e->Pstride;
             break;
+        case 18:  // the fp16 copy of IR idx's spectra, scaled by item 20 (uint2 [256][pstride])
+            if (idx >= (uint64_t)(kMaxIrs + kMixIrs) || !e->irs[idx].d_H || !e->irs[idx].d_H16) return fail(MC_ERR_ARG, "IR not loaded");
+            src = (const char*)e->irs[idx].d_H16;
+            cap = sizeof(uint2) * (uint64_t)MC_NB * e->Pstride;
+            break;
+        case 19: src = (const char*)e->d_fdl16; cap = sizeof(uint2) * (uint64_t)MC_NB * e->ring; break;
+        case 20: {  // scale16 of IR idx (one float): a host-side word, read behind the stream like the copy it belongs to
+            if (idx >= (uint64_t)(kMaxIrs + kMixIrs) || !e->irs[idx].d_H || !e->irs[idx].d_H16) return fail(MC_ERR_ARG, "IR not loaded");
+            if (off + bytes > sizeof(float)) return fail(MC_ERR_ARG, "read beyond the scale");
+            int rc = leave_jack_path(e);
+            if (rc) return rc;
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            std::memcpy(dst, reinterpret_cast<const char*>(&e->irs[idx].scale16) + off, bytes);
+            return MC_OK;
+        }
+        case 21: src = (const char*)e->d_slotgain; cap = sizeof(float4) * (uint64_t)MC_MAXV * e->ring; break;
         case 17:  // the stored time-domain taps of IR idx (float2 [taps]: converted to the session's rate by mc_load_ir_resampled)
             if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h) return fail(MC_ERR_ARG, "IR not loaded");
             src = (const char*)e->irs[idx].d_h;

@@ -1665,6 +1665,37 @@ class Convolution:
         n = int(self.ir_info(idx)["taps"])
         return self.debug_read(17, idx, np.float32, 0, 2 * n).reshape(n, 2)
 
+    def ir_spectra16(self, idx):
+        """The fp16 copy of IR idx's spectra as stored, uint16 [256 bins][pstride][4] {L.re, L.im, R.re, R.im} (mc_debug_read
+        item 18; fp16 engines only).  idx may name a merged-IR entry (256 ..)."""
+        ps = self.debug_dims()["pstride"]
+        return self.debug_read(18, idx, np.uint16, 0, 256 * ps * 4).reshape(256, ps, 4)
+
+    def ir_spectra32(self, idx):
+        """The fp32 spectra of IR idx as stored, float32 [256 bins][pstride][4] (mc_debug_read item 0), padding included."""
+        ps = self.debug_dims()["pstride"]
+        return self.debug_read(0, idx, np.float32, 0, 256 * ps * 4).reshape(256, ps, 4)
+
+    def ir_scale16(self, idx):
+        """The power-of-two scale of IR idx's fp16 copy (mc_debug_read item 20; fp16 engines only)."""
+        return float(self.debug_read(20, idx, np.float32, 0, 1)[0])
+
+    def delay_line(self):
+        """The delay line as stored, float32 [256 bins][ring][4] {in1.re, in1.im, in2.re, in2.im} (mc_debug_read item 1)."""
+        ring = self.debug_dims()["ring"]
+        return self.debug_read(1, 0, np.float32, 0, 256 * ring * 4).reshape(256, ring, 4)
+
+    def delay_line16(self):
+        """The delay line's fp16 mirror as stored, uint16 [256 bins][ring][4] (mc_debug_read item 19; fp16 engines only)."""
+        ring = self.debug_dims()["ring"]
+        return self.debug_read(19, 0, np.uint16, 0, 256 * ring * 4).reshape(256, ring, 4)
+
+    def slot_gains(self):
+        """The gains of the delay line's slots, float32 [3 voice rows][ring][4] {L<-in1, L<-in2, R<-in1, R<-in2}
+        (mc_debug_read item 21)."""
+        ring = self.debug_dims()["ring"]
+        return self.debug_read(21, 0, np.float32, 0, 3 * ring * 4).reshape(3, ring, 4)
+
     def ir_spectra(self, idx):
         """IR spectra as complex [2 ch][partitions][256 packed bins] (diagnostics)."""
         info, dims = self.ir_info(idx), self.debug_dims()

@@ -70,7 +70,14 @@ typedef struct {
     uint32_t precision;     /* 0 = fp32 spectra; 1 = fp16 storage of IR spectra and delay line for the
                                partition sweep (fp32 products and sums; the streaming kernel: single periods and batches
                                below 12288 blocks).  Longer settled batches take the overlap-save form in either precision
-                               (its spectra are built from the fp32 taps: fp32 accuracy there) */
+                               (its spectra are built from the fp32 taps: fp32 accuracy there).
+                               The delay line's fp16 mirror holds 16 x the block's spectrum: full-scale input
+                               (|x| <= 1, |X| <= 256) reaches 4096, and input beyond 16 times full scale overflows
+                               the mirror (65504) to infinity.  Each IR's copy carries its own power-of-two scale,
+                               2^(13 - e) for a largest spectrum entry in [2^(e-1), 2^e), the exponent held to at most
+                               122 so that the scale times 16 and its reciprocal stay normal floats (at that limit, an IR
+                               whose largest spectrum entry is below 2^-109, the reciprocal times a gain below 1 is a
+                               subnormal float: exact enough only while the device keeps fp32 subnormals, as this build does) */
     uint32_t period;        /* JACK period the host will call mc_process with: 0/256, 512 or 1024 frames.  The
                                reference's per-call semantics (cross-fade step, DC/Nyquist and tail-drop windows)
                                follow this size; internally a period is 1, 2 or 4 blocks of 256.  Batch calls
@@ -1364,8 +1371,15 @@ uint64_t mc_preferred_batch(const mc_engine *e, uint64_t at_most);
  * took it, builds of its spectra} (2 x uint64), 12 / 13 / 14 = its row buffer and spectra (float4), 15 = retired (MC_ERR_ARG;
  * it reported a measurement build of the library, which no longer exists), 16 = 256-frame JACK tails by the form partition 0 took
  * {frequency domain, time domain}, counted by the kernel (2 x uint32; read behind the stream), 17 = the stored time-domain
- * taps of IR `idx` (float2 [taps], as mc_ir_info counts them; MC_ERR_STATE in the single-transform form, which keeps none).  dims[0..3] receive
- * {pstride, ring, max_batch, wet ring length} when non-null. */
+ * taps of IR `idx` (float2 [taps], as mc_ir_info counts them; MC_ERR_STATE in the single-transform form, which keeps none).
+ * fp16 storage (precision = 1; MC_ERR_STATE on an fp32 engine): 18 = the fp16 copy of IR `idx`'s spectra, four halves
+ * {L.re, L.im, R.re, R.im} per entry, each the fp32 entry of item 0 times item 20, rounded to nearest even (uint2 [256][pstride]),
+ * 19 = the fp16 mirror of the delay line, item 1 times 16 (uint2 [256][ring]), 20 = the power-of-two scale of IR `idx`'s copy
+ * (one float).  Either precision: 21 = the gains of the delay line's slots, {L<-in1, L<-in2, R<-in1, R<-in2} per voice row
+ * (float4 [3][ring]).  Items 1, 18, 19, 20 and 21 leave the JACK path and wait for the stream, as every device buffer here does.
+ * Items 0, 18 and 20 also take the merged-IR entries, idx = 256 .. 259 ([half][buffer]: what a half's IRs were summed into when
+ * more of them were cross-fading than there are voices); an entry that was never allocated answers MC_ERR_ARG, as an
+ * unloaded IR does.  dims[0..3] receive {pstride, ring, max_batch, wet ring length} when non-null. */
 int mc_debug_read(mc_engine *e, int which, uint64_t idx, void *dst, uint64_t offset_bytes, uint64_t bytes,
                   uint64_t dims[4]);
 
