@@ -420,11 +420,6 @@ class IrMatch:
             return None
         return _f32(getattr(self.ir, "buffer", self.ir)).reshape(-1, 2)
 
-    def c_args(self):
-        """(match, target_lr, target_frames) as mc_load_ir_match takes them; the frames are returned too, to keep them alive."""
-        t = self.frames()
-        return (C.byref(self.to_c()), _fp(t) if t is not None else None, t.shape[0] if t is not None else 0), t
-
 
 def match_plan(match, frames, target_frames=None, rate=48000):
     """What the match step `match` (an IrMatch) would do to `frames` frames at the session's rate `rate` (mc_ir_match_plan,
@@ -968,6 +963,35 @@ class CC:
         return (self.select, self.predelay, self.dry, self.wet, self.speed, self.panDry, self.panWet, self.level)
 
 
+def _on(step):
+    """Whether a step of a load (an IrTail, IrPhase, IrFilter, IrMatch or IrParts, or None) is asked for and switched on."""
+    return step is not None and getattr(step, "op", getattr(step, "mode", None)) != "off"
+
+
+def _file_rates(ir_rate, session, eq, damp, tail, filter, match):
+    """(ir_rate, session_rate) of a file load.  What is laid out in Hz or converts a second IR needs the session's rate in the
+    call, and frames without a rate of their own then count as being at it; otherwise the rates are passed only to convert."""
+    if _on(match) or _on(tail) or eq is not None or (damp is not None and damp.xovers) or (_on(filter) and filter.to_c().rate and session):
+        return (int(session or 0) if ir_rate is None else int(ir_rate), int(session or 0))
+    if ir_rate is not None and session is not None and int(ir_rate) != int(session):
+        return (int(ir_rate), int(session))
+    return (0, 0)
+
+
+def _c_steps(shape, eq, damp, tail, phase, filter, match, parts):
+    """The step objects as the widest entry points take them, after the source's own arguments: shape, eq, damp, tail, phase,
+    filter, filter_lr, filter_frames, match, target_lr, target_frames, parts.  None or a step that is switched off is a null
+    pointer (and no frames).  The second value holds the second IRs' arrays, which must outlive the call (the structs live in
+    their byref objects)."""
+    ref = lambda x: C.byref(x.to_c()) if x is not None else None  # noqa: E731
+    head = (ref(shape), ref(eq), ref(damp), ref(tail if _on(tail) else None), ref(phase if _on(phase) else None))
+    flr = filter.frames() if _on(filter) else None
+    tlr = match.frames() if _on(match) else None
+    m = ref(match if _on(match) else None)
+    second = lambda a: (_fp(a), a.shape[0]) if a is not None else (None, 0)  # noqa: E731
+    return (*head, ref(filter if _on(filter) else None), *second(flr), m, *second(tlr), ref(parts if _on(parts) else None)), (flr, tlr)
+
+
 class Convolution:
     def __init__(self, name="Conv", fftSize=CONV_DEFAULT_FFTSIZE, *, max_batch=256, device=-1, compat=True,
                  part_begin=0, part_end=0, max_partitions=0, stream_threshold=0, precision="fp32", period=256, pipeline=False,
@@ -1021,121 +1045,59 @@ class Convolution:
         ir_rate (Hz; default: `wav.sampleRate` when it has one): when both it and the engine's sample_rate are known and
         differ, the IR is converted to the session's rate on the device (mc_load_ir_resampled).
         shape (an IrShape): trim, reverse, decay, fade and normalise the IR on the device, after the conversion and before
-        the truncation (mc_load_ir_shaped); ir_shape_info(idx) then tells what was done.
-        eq (an IrEq): filter the shaped taps with its bands before the normalisation (mc_load_ir_eq); the engine needs a
-        sample_rate, and ir_rate defaults to it.
-        damp (an IrDamp): a further decay per frequency band, after the fade and before the EQ (mc_load_ir_damped); the rates
-        as for eq; ir_damp_info(idx) then tells what was done.
+        the truncation; ir_shape_info(idx) then tells what was done.
+        eq (an IrEq): filter the shaped taps with its bands before the normalisation; the engine needs a sample_rate, and
+        ir_rate defaults to it.
+        damp (an IrDamp): a further decay per frequency band, after the fade and before the EQ; the rates as for eq;
+        ir_damp_info(idx) then tells what was done.
         tail (an IrTail whose mode is not "off"): cut or extend the tail of the frames band by band, after the conversion and
-        before everything else (mc_load_ir_tail); the rates as for eq; ir_tail_info(idx) then tells what was done.
+        before everything else; the rates as for eq; ir_tail_info(idx) then tells what was done.
         phase (an IrPhase whose mode is not "off"): convert the frames to minimum phase, after the tail step and before
-        the shape (mc_load_ir_phase); it needs no rate; ir_phase_info(idx) then tells what was done.
+        the shape; it needs no rate; ir_phase_info(idx) then tells what was done.
         filter (an IrFilter whose op is not "off"): convolve the frames with a second IR, or divide it out of them, after the
-        phase step and before the shape (mc_load_ir_filter); a filter with a rate of its own needs the engine's sample_rate;
+        phase step and before the shape; a filter with a rate of its own needs the engine's sample_rate;
         ir_filter_info(idx) then tells what was done.
         match (an IrMatch whose mode is not "off"): give the frames the smoothed spectrum of a target IR, or a flat one, after
-        the filter step and before the shape (mc_load_ir_match); the engine needs a sample_rate; ir_match_info(idx) and
+        the filter step and before the shape; the engine needs a sample_rate; ir_match_info(idx) and
         ir_match_curve(idx) then tell what was done.
         parts (an IrParts whose mode is not "off"): the direct sound, the early reflections and the late tail get a gain, a
-        delay, a width and a balance each, after the match step and before the shape (mc_load_ir_parts); it needs no rate;
+        delay, a width and a balance each, after the match step and before the shape; it needs no rate;
         ir_parts_info(idx) then tells what was done."""
         lr = _f32(getattr(wav, "buffer", wav)).reshape(-1, 2)
         if ir_rate is None:
             ir_rate = getattr(wav, "sampleRate", None)
-        filtered = filter is not None and filter.op != "off"
-        matched = match is not None and match.on()
-        parted = parts is not None and parts.on()
-        if parted or matched or filtered or (phase is not None and phase.mode != "off"):
-            tailed = tail is not None and tail.mode != "off"
-            if matched or tailed or eq is not None or (damp is not None and damp.xovers) or (filtered and filter.to_c().rate and self.sample_rate):
-                session = int(self.sample_rate or 0)
-                rates = (session if ir_rate is None else int(ir_rate), session)
-            elif ir_rate is not None and self.sample_rate is not None and int(ir_rate) != int(self.sample_rate):
-                rates = (int(ir_rate), int(self.sample_rate))
+        if shape is None and eq is None and not (damp is not None and damp.xovers) and not any(_on(s) for s in (tail, phase, filter, match, parts)):
+            # (the reference's plain call)
+            if ir_rate is not None and self.sample_rate is not None and int(ir_rate) != int(self.sample_rate):
+                check(self._L.mc_load_ir_resampled(self._h, idx, _fp(lr), lr.shape[0], nframes, int(ir_rate), int(self.sample_rate)))
             else:
-                rates = (0, 0)
-            args = (self._h, idx, _fp(lr), lr.shape[0], nframes, *rates,
-                    C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
-                    C.byref(damp.to_c()) if damp is not None else None, C.byref(tail.to_c()) if tailed else None,
-                    C.byref(phase.to_c()) if phase is not None else None)
-            if parted:
-                flr = filter.frames() if filtered else None
-                margs, keep = match.c_args() if matched else ((None, None, 0), None)
-                check(self._L.mc_load_ir_parts(*args, C.byref(filter.to_c()) if filtered else None, _fp(flr) if filtered else None,
-                                               flr.shape[0] if filtered else 0, *margs, C.byref(parts.to_c())))
-            elif matched:
-                flr = filter.frames() if filtered else None
-                margs, keep = match.c_args()
-                check(self._L.mc_load_ir_match(*args, C.byref(filter.to_c()) if filtered else None, _fp(flr) if filtered else None,
-                                               flr.shape[0] if filtered else 0, *margs))
-            elif filtered:
-                flr = filter.frames()
-                check(self._L.mc_load_ir_filter(*args, C.byref(filter.to_c()), _fp(flr), flr.shape[0]))
-            else:
-                check(self._L.mc_load_ir_phase(*args))
+                check(self._L.mc_load_ir(self._h, idx, _fp(lr), lr.shape[0], nframes))
             return
-        if tail is not None and tail.mode != "off":
-            session = int(self.sample_rate or 0)
-            check(self._L.mc_load_ir_tail(self._h, idx, _fp(lr), lr.shape[0], nframes, session if ir_rate is None else int(ir_rate), session,
-                                          C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
-                                          C.byref(damp.to_c()) if damp is not None else None, C.byref(tail.to_c())))
-            return
-        if damp is not None and damp.xovers:
-            session = int(self.sample_rate or 0)
-            check(self._L.mc_load_ir_damped(self._h, idx, _fp(lr), lr.shape[0], nframes, session if ir_rate is None else int(ir_rate), session,
-                                            C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
-                                            C.byref(damp.to_c())))
-            return
-        if eq is not None:
-            session = int(self.sample_rate or 0)
-            check(self._L.mc_load_ir_eq(self._h, idx, _fp(lr), lr.shape[0], nframes, session if ir_rate is None else int(ir_rate), session,
-                                        C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c())))
-            return
-        convert = ir_rate is not None and self.sample_rate is not None and int(ir_rate) != int(self.sample_rate)
-        if shape is not None:
-            rates = (int(ir_rate), int(self.sample_rate)) if convert else (0, 0)
-            check(self._L.mc_load_ir_shaped(self._h, idx, _fp(lr), lr.shape[0], nframes, *rates, C.byref(shape.to_c())))
-        elif convert:
-            check(self._L.mc_load_ir_resampled(self._h, idx, _fp(lr), lr.shape[0], nframes, int(ir_rate), int(self.sample_rate)))
-        else:
-            check(self._L.mc_load_ir(self._h, idx, _fp(lr), lr.shape[0], nframes))
+        rates = _file_rates(ir_rate, self.sample_rate, eq, damp, tail, filter, match)
+        steps, keep = _c_steps(shape, eq, damp, tail, phase, filter, match, parts)
+        check(self._L.mc_load_ir_parts(self._h, idx, _fp(lr), lr.shape[0], nframes, *rates, *steps))
 
     def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None, room=None, tail=None, mics=None, bands=None):
         """Generate the IR `synth` (an IrSynth) describes on the device and store it at idx (mc_synth_ir): the frames take the
         place of a WAV's at the session's rate, and shape, eq and damp apply to them as in prepare().  A synthesised IR counts
         as shaped: ir_shape_info(idx)["frames"] is synth.frames.  The engine's sample_rate (which eq, damp, room and tail
         need) is passed unless synth.rate is set.
-        room (an IrRoom): the reflections of a rectangular room are added to the frames (mc_synth_ir_room); ir_room_info(idx)
-        then tells what was rendered.  tail (an IrTail whose mode is not "off"): the tail step on the generated frames, as
-        in prepare().  mics (an IrRoomMics, with room): the receivers and the source of the room are directional
-        (mc_synth_ir_room_mics); ir_room_mics_info(idx) then tells the direct sound's factors.  bands (an IrRoomBands, with
-        room): the walls and the air differ per frequency band (mc_synth_ir_room_bands); ir_room_bands_info(idx) then tells
-        the bands' reverberation times."""
+        room (an IrRoom): the reflections of a rectangular room are added to the frames; ir_room_info(idx) then tells what
+        was rendered.  tail (an IrTail whose mode is not "off"): the tail step on the generated frames, as in prepare().
+        mics (an IrRoomMics, with room): the receivers and the source of the room are directional; ir_room_mics_info(idx)
+        then tells the direct sound's factors.  bands (an IrRoomBands, with room): the walls and the air differ per
+        frequency band; ir_room_bands_info(idx) then tells the bands' reverberation times."""
         s = synth.to_c()
         if not s.rate:
             s.rate = int(self.sample_rate or 0)
-        if bands is not None:
-            if room is None:
-                raise ValueError("the bands need a room")
-            check(self._L.mc_synth_ir_room_bands(self._h, idx, nframes, C.byref(s), C.byref(room.to_c()), C.byref(mics.to_c()) if mics is not None else None,
-                                                 C.byref(bands.to_c()), C.byref(shape.to_c()) if shape is not None else None,
-                                                 C.byref(eq.to_c()) if eq is not None else None, C.byref(damp.to_c()) if damp is not None else None,
-                                                 C.byref(tail.to_c()) if tail is not None else None))
-            return
-        if mics is not None:
-            if room is None:
-                raise ValueError("the microphones need a room")
-            check(self._L.mc_synth_ir_room_mics(self._h, idx, nframes, C.byref(s), C.byref(room.to_c()), C.byref(mics.to_c()),
-                                                C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
-                                                C.byref(damp.to_c()) if damp is not None else None, C.byref(tail.to_c()) if tail is not None else None))
-            return
-        if room is not None or tail is not None:
-            check(self._L.mc_synth_ir_room(self._h, idx, nframes, C.byref(s), C.byref(room.to_c()) if room is not None else None,
-                                           C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
-                                           C.byref(damp.to_c()) if damp is not None else None, C.byref(tail.to_c()) if tail is not None else None))
-            return
-        check(self._L.mc_synth_ir(self._h, idx, nframes, C.byref(s), C.byref(shape.to_c()) if shape is not None else None,
-                                  C.byref(eq.to_c()) if eq is not None else None, C.byref(damp.to_c()) if damp is not None else None))
+        if bands is not None and room is None:
+            raise ValueError("the bands need a room")
+        if mics is not None and room is None:
+            raise ValueError("the microphones need a room")
+        ref = lambda x: C.byref(x.to_c()) if x is not None else None  # noqa: E731
+        source = (ref(room), ref(mics), ref(bands))
+        steps, keep = _c_steps(shape, eq, damp, tail, None, None, None, None)
+        check(self._L.mc_synth_ir_room_bands(self._h, idx, nframes, C.byref(s), *source, *steps[:4]))
 
     def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None, tail=None, phase=None, filter=None, match=None, parts=None):
         """Deconvolve `recording` (float32 [frames, 2] or an object with such a `.buffer`: what was recorded while `sweep`, a
@@ -1145,11 +1107,10 @@ class Convolution:
         pre-roll where the harmonic-distortion images land.  ir_frames defaults to max(1, M - N + 1 - offset), what the
         recording holds past the sweep, clamped to the library's caps.  The engine's sample_rate is passed unless sweep.rate
         is set (the library's default, 44100, when the engine has none either).  tail (an IrTail whose mode is not "off"): the
-        tail step on the deconvolved frames (mc_load_ir_sweep_tail).  phase (an IrPhase whose mode is not "off"): the phase step
-        after it (mc_load_ir_sweep_phase).  filter (an IrFilter whose op is not "off"): the filter step after that
-        (mc_load_ir_sweep_filter), the session's rate being the sweep's.  match (an IrMatch whose mode is not "off"): the match
-        step after that (mc_load_ir_sweep_match).  parts (an IrParts whose mode is not "off"): the parts step after that
-        (mc_load_ir_sweep_parts)."""
+        tail step on the deconvolved frames.  phase (an IrPhase whose mode is not "off"): the phase step after it.  filter
+        (an IrFilter whose op is not "off"): the filter step after that, the session's rate being the sweep's.  match (an
+        IrMatch whose mode is not "off"): the match step after that.  parts (an IrParts whose mode is not "off"): the parts
+        step after that.  The getters report each step as after prepare()."""
         lr = _f32(getattr(recording, "buffer", recording)).reshape(-1, 2)
         s = sweep.to_c()
         if not sweep.rate and self.sample_rate:
@@ -1157,33 +1118,8 @@ class Convolution:
         if ir_frames is None:
             ir_frames = max(1, lr.shape[0] - int(s.frames) + 1 - int(offset))
             ir_frames = max(1, min(ir_frames, SWEEP_MAX_FRAMES, SWEEP_MAX_WORK // max(int(s.frames), 1)))
-        args = (self._h, idx, _fp(lr), lr.shape[0], nframes, C.byref(s), int(offset), int(ir_frames),
-                C.byref(shape.to_c()) if shape is not None else None, C.byref(eq.to_c()) if eq is not None else None,
-                C.byref(damp.to_c()) if damp is not None else None)
-        if parts is not None and parts.on():
-            filtered = filter is not None and filter.op != "off"
-            flr = filter.frames() if filtered else None
-            margs, keep = match.c_args() if match is not None and match.on() else ((None, None, 0), None)
-            check(self._L.mc_load_ir_sweep_parts(*args, C.byref(tail.to_c()) if tail is not None else None, C.byref(phase.to_c()) if phase is not None else None,
-                                                 C.byref(filter.to_c()) if filtered else None, _fp(flr) if filtered else None, flr.shape[0] if filtered else 0,
-                                                 *margs, C.byref(parts.to_c())))
-        elif match is not None and match.on():
-            filtered = filter is not None and filter.op != "off"
-            flr = filter.frames() if filtered else None
-            margs, keep = match.c_args()
-            check(self._L.mc_load_ir_sweep_match(*args, C.byref(tail.to_c()) if tail is not None else None, C.byref(phase.to_c()) if phase is not None else None,
-                                                 C.byref(filter.to_c()) if filtered else None, _fp(flr) if filtered else None, flr.shape[0] if filtered else 0,
-                                                 *margs))
-        elif filter is not None and filter.op != "off":
-            flr = filter.frames()
-            check(self._L.mc_load_ir_sweep_filter(*args, C.byref(tail.to_c()) if tail is not None else None, C.byref(phase.to_c()) if phase is not None else None,
-                                                  C.byref(filter.to_c()), _fp(flr), flr.shape[0]))
-        elif phase is not None and phase.mode != "off":
-            check(self._L.mc_load_ir_sweep_phase(*args, C.byref(tail.to_c()) if tail is not None else None, C.byref(phase.to_c())))
-        elif tail is not None and tail.mode != "off":
-            check(self._L.mc_load_ir_sweep_tail(*args, C.byref(tail.to_c())))
-        else:
-            check(self._L.mc_load_ir_sweep(*args))
+        steps, keep = _c_steps(shape, eq, damp, tail, phase, filter, match, parts)
+        check(self._L.mc_load_ir_sweep_parts(self._h, idx, _fp(lr), lr.shape[0], nframes, C.byref(s), int(offset), int(ir_frames), *steps))
 
     def onProcess(self, in1, in2):
         """One JACK period (conv.cu:287-466): returns (L, R) float32 arrays."""

@@ -227,74 +227,7 @@ uint64_t Convolution::dampFrames(double seconds, double rate) {
     return f < 1.0 ? 1 : (uint64_t)f;
 }
 
-// irRate = sessionRate = 0: the frames are loaded at the rate they have (never with a band of eq on, never with damping).
-// synth: the engine generates the frames (lr null; sessionRate = synth->rate).  sweep: lr is the recording of a sweep, `frames`
-// frames at sessionRate = sweep->sweep.rate, which the engine deconvolves.  room (with synth): its reflections are added to the
-// generated frames, and a tail applies to them; mics (with room): its receivers and its source are directional; bands (with
-// room): its walls and its air differ per frequency band
-void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
-                             const IrEq& eq, const IrDamp& damp, const mc_ir_synth* synth, const SweepLoad* sweep, const mc_ir_tail* tail,
-                             const mc_ir_room* room, const mc_ir_room_mics* mics, const mc_ir_room_bands* bands) {
-    if (bands && (!mc_synth_ir_room_bands || !mc_default_ir_room_bands || !mc_ir_room_bands_info)) {
-        Log::error("conv", "the engine has no frequency bands in its rooms (mc_synth_ir_room_bands)");
-        std::exit(2);
-    }
-    if (mics && (!mc_synth_ir_room_mics || !mc_default_ir_room_mics || !mc_ir_room_mics_info)) {
-        Log::error("conv", "the engine has no directional microphones in its rooms (mc_synth_ir_room_mics)");
-        std::exit(2);
-    }
-    if (room && (!mc_synth_ir_room || !mc_default_ir_room || !mc_ir_room_info)) {
-        Log::error("conv", "the engine has no room rendering (mc_synth_ir_room)");
-        std::exit(2);
-    }
-    const bool minimum = _irPhase.minimum && !synth;
-    if (_irPhase.minimum && synth) Log::info(name, "IR %zu is generated: it has no phase step and is loaded as it is", idx);
-    if (minimum && (!mc_default_ir_phase || !mc_load_ir_phase || !mc_load_ir_sweep_phase || !mc_ir_phase_info)) {
-        Log::error("conv", "the engine has no phase step (mc_load_ir_phase)");
-        std::exit(2);
-    }
-    const bool filtered = _irFilter.on && !synth;
-    if (_irFilter.on && synth) Log::info(name, "IR %zu is generated: it has no filter step and is loaded as it is", idx);
-    if (filtered && (!mc_default_ir_filter || !mc_load_ir_filter || !mc_load_ir_sweep_filter || !mc_ir_filter_info)) {
-        Log::error("conv", "the engine has no filter step (mc_load_ir_filter)");
-        std::exit(2);
-    }
-    const bool matched = _irMatch.on && !synth;
-    if (_irMatch.on && synth) Log::info(name, "IR %zu is generated: it has no match step and is loaded as it is", idx);
-    if (matched && (!mc_default_ir_match || !mc_load_ir_match || !mc_load_ir_sweep_match || !mc_ir_match_info || !mc_ir_match_curve)) {
-        Log::error("conv", "the engine has no match step (mc_load_ir_match)");
-        std::exit(2);
-    }
-    const bool parted = _irParts.on && !synth;
-    if (_irParts.on && synth) Log::info(name, "IR %zu is generated: it has no parts step and is loaded as it is", idx);
-    if (parted && (!mc_default_ir_parts || !mc_load_ir_parts || !mc_load_ir_sweep_parts || !mc_ir_parts_at || !mc_ir_parts_info)) {
-        Log::error("conv", "the engine has no parts step (mc_load_ir_parts)");
-        std::exit(2);
-    }
-    if (tail && (!mc_load_ir_tail || !mc_load_ir_sweep_tail || !mc_ir_tail_info)) {
-        Log::error("conv", "the engine has no tail step (mc_load_ir_tail)");
-        std::exit(2);
-    }
-    if (sweep && (!mc_load_ir_sweep || !mc_default_sweep || !mc_ir_sweep_info)) {
-        Log::error("conv", "the engine has no sweep capture (mc_load_ir_sweep)");
-        std::exit(2);
-    }
-    if (synth && (!mc_synth_ir || !mc_default_ir_synth || !mc_ir_synth_info)) {
-        Log::error("conv", "the engine has no IR synthesis (mc_synth_ir)");
-        std::exit(2);
-    }
-    if (!damp.off() && (!mc_load_ir_damped || !mc_default_ir_damp || !mc_ir_damp_info)) {
-        Log::error("conv", "the engine has no IR damping (mc_load_ir_damped)");
-        std::exit(2);
-    }
-    if (!mc_load_ir_shaped || !mc_default_ir_shape || !mc_ir_shape_info) {
-        Log::error("conv", "the engine has no IR shaping (mc_load_ir_shaped)");
-        std::exit(2);
-    }
-    if (!eq.off() && (!mc_load_ir_eq || !mc_default_ir_eq || !mc_ir_eq_response)) {
-        Log::error("conv", "the engine has no IR equalisation (mc_load_ir_eq)");
-        std::exit(2);
-    }
+mc_ir_shape Convolution::shapeArg(const IrShape& shape) {
     mc_ir_shape s;
     mc_default_ir_shape(&s);
     s.flags = shape.reverse ? MC_SHAPE_REVERSE : 0;
@@ -306,188 +239,263 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
     s.fade_out = shape.fadeOut;
     s.normalize = (uint32_t)shape.normalize;
     s.target = shape.target;
-    if (irRate && irRate != sessionRate) Log::info(name, "IR %zu: %u Hz -> %u Hz", idx, irRate, sessionRate);
+    return s;
+}
+
+mc_ir_eq Convolution::eqArg(const IrEq& eq) {
     mc_ir_eq q;
+    mc_default_ir_eq(&q);
+    for (size_t k = 0; k < eq.bands.size(); k++) q.band[k] = mc_eq_band{(uint32_t)eq.bands[k].kind, eq.bands[k].hz, eq.bands[k].gainDb, eq.bands[k].q};
+    return q;
+}
+
+mc_ir_damp Convolution::dampArg(const IrDamp& damp, double session) {
     mc_ir_damp d;
+    mc_default_ir_damp(&d);
+    d.n_xovers = (uint32_t)damp.xovers.size();
+    for (size_t k = 0; k < damp.xovers.size(); k++) d.xover_hz[k] = damp.xovers[k];
+    for (size_t j = 0; j < damp.decaySeconds.size(); j++) d.decay_t60[j] = dampFrames(damp.decaySeconds[j], session);
+    d.origin = damp.origin;
+    return d;
+}
+
+mc_ir_phase Convolution::phaseArg(const IrPhase& phase) {
     mc_ir_phase ph;
-    if (minimum) {
-        mc_default_ir_phase(&ph);
-        ph.mode = MC_PHASE_MINIMUM;
-        ph.floor_db = _irPhase.floorDb;
-        ph.over_log2 = _irPhase.overLog2;
-    }
+    mc_default_ir_phase(&ph);
+    ph.mode = MC_PHASE_MINIMUM;
+    ph.floor_db = phase.floorDb;
+    ph.over_log2 = phase.overLog2;
+    return ph;
+}
+
+mc_ir_filter Convolution::filterArg(const IrFilter& filter, unsigned session) {
     mc_ir_filter fl;
-    const uint64_t flFrames = _irFilter.lr.size() / 2;
-    if (filtered) {
-        // a filter at another rate needs the session's in the call: frames that are loaded at the rate they have are at the client's
-        const unsigned session = sweep ? sweep->sweep.rate : sessionRate ? sessionRate : (unsigned)samplerate;
-        mc_default_ir_filter(&fl);
-        fl.op = _irFilter.deconvolve ? MC_FILTER_DECONVOLVE : MC_FILTER_CONVOLVE;
-        fl.channels = _irFilter.channels;
-        fl.rate = _irFilter.rate && _irFilter.rate != session ? _irFilter.rate : 0;
-        fl.reg_db = _irFilter.regDb;
-        fl.frames_out = dampFrames(_irFilter.keepSeconds, (double)session);
-        if (fl.rate && !sessionRate) irRate = sessionRate = session;
-    }
+    mc_default_ir_filter(&fl);
+    fl.op = filter.deconvolve ? MC_FILTER_DECONVOLVE : MC_FILTER_CONVOLVE;
+    fl.channels = filter.channels;
+    fl.rate = filter.rate && filter.rate != session ? filter.rate : 0;
+    fl.reg_db = filter.regDb;
+    fl.frames_out = dampFrames(filter.keepSeconds, (double)session);
+    return fl;
+}
+
+mc_ir_match Convolution::matchArg(const IrMatch& match, unsigned session) {
     mc_ir_match mt;
-    const uint64_t mtFrames = _irMatch.lr.size() / 2;
-    if (matched) {
-        // the grid is in Hz: the call needs the session's rate, and frames that are loaded at the rate they have are at the client's
-        const unsigned session = sweep ? sweep->sweep.rate : sessionRate ? sessionRate : (unsigned)samplerate;
-        mc_default_ir_match(&mt);
-        mt.mode = _irMatch.flat ? MC_MATCH_FLAT : MC_MATCH_TARGET;
-        mt.phase = _irMatch.linear ? MC_MATCH_LINEAR : MC_MATCH_MINIMUM;
-        mt.link = _irMatch.link ? 1 : 0;
-        mt.rate = !_irMatch.flat && _irMatch.rate && _irMatch.rate != session ? _irMatch.rate : 0;
-        mt.lo_hz = _irMatch.loHz;
-        mt.hi_hz = _irMatch.hiHz;
-        mt.octaves = _irMatch.octaves;
-        mt.amount = _irMatch.amount;
-        mt.boost_db = _irMatch.boostDb;
-        mt.cut_db = _irMatch.cutDb;
-        mt.tilt_db = _irMatch.tiltDb;
-        mt.delay = (uint32_t)dampFrames(_irMatch.delaySeconds, (double)session);
-        if (!sessionRate) irRate = sessionRate = session;
-    }
+    mc_default_ir_match(&mt);
+    mt.mode = match.flat ? MC_MATCH_FLAT : MC_MATCH_TARGET;
+    mt.phase = match.linear ? MC_MATCH_LINEAR : MC_MATCH_MINIMUM;
+    mt.link = match.link ? 1 : 0;
+    mt.rate = !match.flat && match.rate && match.rate != session ? match.rate : 0;
+    mt.lo_hz = match.loHz;
+    mt.hi_hz = match.hiHz;
+    mt.octaves = match.octaves;
+    mt.amount = match.amount;
+    mt.boost_db = match.boostDb;
+    mt.cut_db = match.cutDb;
+    mt.tilt_db = match.tiltDb;
+    mt.delay = (uint32_t)dampFrames(match.delaySeconds, (double)session);
+    return mt;
+}
+
+mc_ir_parts Convolution::partsArg(size_t idx, const IrParts& parts, double session, const std::optional<PartsSplit>& split) {
     mc_ir_parts pt;
-    if (parted) {
-        // seconds become frames at the session's rate; frames that are loaded at the rate they have are at the client's
-        const double session = (double)(sweep ? sweep->sweep.rate : sessionRate ? sessionRate : (unsigned)samplerate);
-        mc_default_ir_parts(&pt);
-        pt.mode = MC_PARTS_ON;
-        for (int k = 0; k < 3; k++) {
-            pt.flags |= (_irParts.mute[k] ? MC_PARTS_MUTE(k) : 0u) | (_irParts.swap[k] ? MC_PARTS_SWAP(k) : 0u) | (_irParts.invert[k] ? MC_PARTS_INVERT(k) : 0u);
-            pt.delay[k] = (int32_t)std::nearbyint(_irParts.delaySeconds[k] * session);
-            pt.gain_db[k] = _irParts.gainDb[k], pt.width[k] = _irParts.width[k], pt.balance[k] = _irParts.balance[k];
+    mc_default_ir_parts(&pt);
+    pt.mode = MC_PARTS_ON;
+    for (int k = 0; k < 3; k++) {
+        pt.flags |= (parts.mute[k] ? MC_PARTS_MUTE(k) : 0u) | (parts.swap[k] ? MC_PARTS_SWAP(k) : 0u) | (parts.invert[k] ? MC_PARTS_INVERT(k) : 0u);
+        pt.delay[k] = (int32_t)std::nearbyint(parts.delaySeconds[k] * session);
+        pt.gain_db[k] = parts.gainDb[k], pt.width[k] = parts.width[k], pt.balance[k] = parts.balance[k];
+    }
+    for (int k = 0; k < 2; k++) pt.xfade[k] = (uint32_t)dampFrames(parts.xfadeSeconds[k], session);
+    const uint64_t onset = split ? split->onset : dampFrames(parts.onsetSeconds, session);
+    const uint64_t first = dampFrames(parts.firstSeconds, session);
+    const uint64_t early = split ? split->mix - split->onset : dampFrames(parts.splitSeconds, session);
+    if (mc_ir_parts_at(&pt, onset, std::min(first, early), early) != MC_OK) {
+        Log::error("conv", "IR %zu cannot be split into parts: %s", idx, mc_last_error());
+        std::exit(2);
+    }
+    return pt;
+}
+
+// The one way an IR reaches the engine once anything but the reference's plain load is asked of it: what the engine must have,
+// the settings as its structs, the call, and the log lines of what was done.
+void Convolution::loadIr(const IrLoadRequest& r) {
+    const size_t idx = r.idx;
+    const bool generated = r.synth.has_value();
+    const bool minimum = r.phase && !generated, filtered = r.filter && !generated, matched = r.match && !generated, parted = r.parts && !generated;
+    const bool tailed = r.tail.has_value(), equalised = !r.eq.off(), damped = !r.damp.off();
+    if (!generated && !r.sweep && !tailed && !minimum && !filtered && !matched && !parted && !equalised && !damped && r.shape.off()) {  // (the reference's plain load)
+        const bool convert = r.irRate && r.irRate != r.sessionRate;
+        if (!convert) {
+            check(mc_load_ir(_engine, idx, r.lr, r.frames, r.nframes), "mc_load_ir");
+            return;
         }
-        for (int k = 0; k < 2; k++) pt.xfade[k] = (uint32_t)dampFrames(_irParts.xfadeSeconds[k], session);
-        const uint64_t onset = _partsMeasured ? _partsOnset : dampFrames(_irParts.onsetSeconds, session);
-        const uint64_t first = dampFrames(_irParts.firstSeconds, session);
-        const uint64_t split = _partsMeasured ? _partsMix - _partsOnset : dampFrames(_irParts.splitSeconds, session);
-        if (mc_ir_parts_at(&pt, onset, std::min(first, split), split) != MC_OK) {
-            Log::error("conv", "IR %zu cannot be split into parts: %s", idx, mc_last_error());
+        if (!mc_load_ir_resampled) {
+            Log::error("conv", "the engine has no sample-rate conversion (mc_load_ir_resampled)");
+            std::exit(2);
+        }
+        Log::info(name, "IR %zu: %u Hz -> %u Hz", idx, r.irRate, r.sessionRate);
+        check(mc_load_ir_resampled(_engine, idx, r.lr, r.frames, r.nframes, r.irRate, r.sessionRate), "mc_load_ir_resampled");
+        return;
+    }
+
+    // what the engine must have: the stub host's stand-in has mc_load_ir alone
+    const struct {
+        const char* dropped;  // a step that is set and that a generated IR does not go through
+        bool needed, there;
+        const char* lacks;
+    } capabilities[] = {
+        {nullptr, r.bands.has_value(), mc_synth_ir_room_bands && mc_default_ir_room_bands && mc_ir_room_bands_info, "frequency bands in its rooms (mc_synth_ir_room_bands)"},
+        {nullptr, r.mics.has_value(), mc_synth_ir_room_mics && mc_default_ir_room_mics && mc_ir_room_mics_info, "directional microphones in its rooms (mc_synth_ir_room_mics)"},
+        {nullptr, r.room.has_value(), mc_synth_ir_room && mc_default_ir_room && mc_ir_room_info, "room rendering (mc_synth_ir_room)"},
+        {r.phase && generated ? "phase" : nullptr, minimum, mc_default_ir_phase && mc_load_ir_phase && mc_load_ir_sweep_phase && mc_ir_phase_info, "phase step (mc_load_ir_phase)"},
+        {r.filter && generated ? "filter" : nullptr, filtered, mc_default_ir_filter && mc_load_ir_filter && mc_load_ir_sweep_filter && mc_ir_filter_info, "filter step (mc_load_ir_filter)"},
+        {r.match && generated ? "match" : nullptr, matched, mc_default_ir_match && mc_load_ir_match && mc_load_ir_sweep_match && mc_ir_match_info && mc_ir_match_curve, "match step (mc_load_ir_match)"},
+        {r.parts && generated ? "parts" : nullptr, parted, mc_default_ir_parts && mc_load_ir_parts && mc_load_ir_sweep_parts && mc_ir_parts_at && mc_ir_parts_info, "parts step (mc_load_ir_parts)"},
+        {nullptr, tailed, mc_load_ir_tail && mc_load_ir_sweep_tail && mc_ir_tail_info, "tail step (mc_load_ir_tail)"},
+        {nullptr, r.sweep.has_value(), mc_load_ir_sweep && mc_default_sweep && mc_ir_sweep_info, "sweep capture (mc_load_ir_sweep)"},
+        {nullptr, generated, mc_synth_ir && mc_default_ir_synth && mc_ir_synth_info, "IR synthesis (mc_synth_ir)"},
+        {nullptr, damped, mc_load_ir_damped && mc_default_ir_damp && mc_ir_damp_info, "IR damping (mc_load_ir_damped)"},
+        {nullptr, true, mc_load_ir_shaped && mc_default_ir_shape && mc_ir_shape_info, "IR shaping (mc_load_ir_shaped)"},
+        {nullptr, equalised, mc_load_ir_eq && mc_default_ir_eq && mc_ir_eq_response, "IR equalisation (mc_load_ir_eq)"},
+    };
+    for (const auto& c : capabilities) {
+        if (c.dropped) Log::info(name, "IR %zu is generated: it has no %s step and is loaded as it is", idx, c.dropped);
+        if (c.needed && !c.there) {
+            Log::error("conv", "the engine has no %s", c.lacks);
             std::exit(2);
         }
     }
-    if (!eq.off()) {
-        mc_default_ir_eq(&q);
-        for (size_t k = 0; k < eq.bands.size(); k++) q.band[k] = mc_eq_band{(uint32_t)eq.bands[k].kind, eq.bands[k].hz, eq.bands[k].gainDb, eq.bands[k].q};
-    }
-    if (!damp.off()) {
-        mc_default_ir_damp(&d);
-        d.n_xovers = (uint32_t)damp.xovers.size();
-        for (size_t k = 0; k < damp.xovers.size(); k++) d.xover_hz[k] = damp.xovers[k];
-        for (size_t j = 0; j < damp.decaySeconds.size(); j++) d.decay_t60[j] = dampFrames(damp.decaySeconds[j], (double)sessionRate);
-        d.origin = damp.origin;
-    }
-    if (synth) {  // (what the engine refuses of a generated IR is the index line's fault: a message and exit 2, no abort)
-        const int rc = bands  ? mc_synth_ir_room_bands(_engine, idx, nframes, synth, room, mics, bands, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
-                       : mics ? mc_synth_ir_room_mics(_engine, idx, nframes, synth, room, mics, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
-                       : room ? mc_synth_ir_room(_engine, idx, nframes, synth, room, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
-                              : mc_synth_ir(_engine, idx, nframes, synth, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d);
+
+    // The rates of the call.  What is laid out in Hz (bands, crossovers, the tail's and the match's bands) or converts a second IR
+    // needs the session's rate, and host frames that are not converted then count as being at it; otherwise the rates are passed
+    // only to convert.  Seconds become frames at the session's rate.
+    const unsigned session = r.sweep ? r.sweep->sweep.rate : generated ? r.synth->rate : r.sessionRate;
+    const bool needsRate = equalised || damped || tailed || matched || (filtered && r.filter->rate && r.filter->rate != session);
+    const unsigned irRate = needsRate && !r.irRate ? session : r.irRate, sessionRate = needsRate || r.irRate ? session : 0;
+    if (irRate && irRate != sessionRate) Log::info(name, "IR %zu: %u Hz -> %u Hz", idx, irRate, sessionRate);
+
+    // the settings as the engine's structs; a null pointer switches a step off
+    const mc_ir_shape s = shapeArg(r.shape);
+    mc_ir_eq eq;
+    mc_ir_damp damp;
+    mc_ir_phase phase;
+    mc_ir_filter filter;
+    mc_ir_match match;
+    mc_ir_parts parts;
+    if (minimum) phase = phaseArg(*r.phase);
+    if (filtered) filter = filterArg(*r.filter, session);
+    if (matched) match = matchArg(*r.match, session);
+    if (parted) parts = partsArg(idx, *r.parts, (double)session, r.split);
+    if (equalised) eq = eqArg(r.eq);
+    if (damped) damp = dampArg(r.damp, (double)session);
+    const mc_ir_eq* q = equalised ? &eq : nullptr;
+    const mc_ir_damp* d = damped ? &damp : nullptr;
+    const mc_ir_tail* t = tailed ? &*r.tail : nullptr;
+    const mc_ir_phase* ph = minimum ? &phase : nullptr;
+    const mc_ir_filter* fl = filtered ? &filter : nullptr;
+    const mc_ir_match* mt = matched ? &match : nullptr;
+    const mc_ir_parts* pt = parted ? &parts : nullptr;
+    const float *flLr = filtered ? r.filter->lr.data() : nullptr, *mtLr = matched ? r.match->lr.data() : nullptr;
+    const uint64_t flFrames = filtered ? r.filter->lr.size() / 2 : 0, mtFrames = matched ? r.match->lr.size() / 2 : 0;
+
+    // the call: per source kind, the narrowest entry point that takes everything that is on
+    if (generated) {  // (what the engine refuses of a generated IR is the index line's fault: a message and exit 2, no abort)
+        const mc_ir_synth* y = &*r.synth;
+        const mc_ir_room* room = r.room ? &*r.room : nullptr;
+        const mc_ir_room_mics* mics = r.mics ? &*r.mics : nullptr;
+        const mc_ir_room_bands* bands = r.bands ? &*r.bands : nullptr;
+        const int rc = bands  ? mc_synth_ir_room_bands(_engine, idx, r.nframes, y, room, mics, bands, &s, q, d, t)
+                       : mics ? mc_synth_ir_room_mics(_engine, idx, r.nframes, y, room, mics, &s, q, d, t)
+                       : room ? mc_synth_ir_room(_engine, idx, r.nframes, y, room, &s, q, d, t)
+                              : mc_synth_ir(_engine, idx, r.nframes, y, &s, q, d);
         if (rc != MC_OK) {
             Log::error("conv", "IR %zu cannot be synthesised: %s", idx, mc_last_error());
             std::exit(2);
         }
-        if (room) {
-            double ri[8];
-            check(mc_ir_room_info(_engine, idx, ri), "mc_ir_room_info");
-            Log::info(name, "IR %zu room: order %d, %llu and %llu images before frame %llu, direct sound at %.2f and %.2f frames, complete up to frame %llu",
-                      idx, (int)ri[0], (unsigned long long)ri[1], (unsigned long long)ri[2], (unsigned long long)ri[5], ri[3], ri[4],
-                      (unsigned long long)ri[6]);
-        }
-        if (mics) {
-            double mi[8];
-            check(mc_ir_room_mics_info(_engine, idx, mi), "mc_ir_room_mics_info");
-            Log::info(name, "IR %zu microphones: the direct sound leaves the source at %.4f and %.4f, is received at %.4f and %.4f, factors %.4f and %.4f",
-                      idx, mi[0], mi[1], mi[2], mi[3], mi[4], mi[5]);
-        }
-        if (bands) {
-            double bi[16];
-            check(mc_ir_room_bands_info(_engine, idx, bi), "mc_ir_room_bands_info");
-            std::string sabine, eyring;
-            for (int j = 0; j < (int)bi[0]; j++) {
-                char one[32];
-                std::snprintf(one, sizeof(one), "%s%.3f", j ? " / " : "", bi[4 + j]);
-                sabine += one;
-                std::snprintf(one, sizeof(one), "%s%.3f", j ? " / " : "", bi[8 + j]);
-                eyring += one;
-            }
-            Log::info(name, "IR %zu bands: %d, low to high Sabine %s s, Eyring %s s", idx, (int)bi[0], sabine.c_str(), eyring.c_str());
-        }
-        double si[4];
-        check(mc_ir_synth_info(_engine, idx, si), "mc_ir_synth_info");
-        Log::info(name, "IR %zu synthesised: %llu frames, seed %llu, %d of %u reflections kept", idx, (unsigned long long)si[0],
-                  (unsigned long long)synth->seed, (int)si[1], synth->n_early);
-    } else if (sweep) {  // (as for a generated IR: what the engine refuses is the index line's fault)
-        const int rc = parted ? mc_load_ir_sweep_parts(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
-                                                       eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, minimum ? &ph : nullptr,
-                                                       filtered ? &fl : nullptr, _irFilter.lr.data(), flFrames, matched ? &mt : nullptr, _irMatch.lr.data(),
-                                                       mtFrames, &pt)
-                       : matched ? mc_load_ir_sweep_match(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
-                                                        eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, minimum ? &ph : nullptr,
-                                                        filtered ? &fl : nullptr, _irFilter.lr.data(), flFrames, &mt, _irMatch.lr.data(), mtFrames)
-                       : filtered ? mc_load_ir_sweep_filter(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
-                                                          eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, minimum ? &ph : nullptr, &fl,
-                                                          _irFilter.lr.data(), flFrames)
-                       : minimum ? mc_load_ir_sweep_phase(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
-                                                        eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, &ph)
-                       : tail  ? mc_load_ir_sweep_tail(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
-                                                    eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail)
-                            : mc_load_ir_sweep(_engine, idx, lr, frames, nframes, &sweep->sweep, sweep->offset, sweep->irFrames, &s,
-                                               eq.off() ? nullptr : &q, damp.off() ? nullptr : &d);
+    } else if (r.sweep) {  // (as for a generated IR: what the engine refuses is the index line's fault)
+        const SweepLoad& w = *r.sweep;
+        const int rc = pt   ? mc_load_ir_sweep_parts(_engine, idx, r.lr, r.frames, r.nframes, &w.sweep, w.offset, w.irFrames, &s, q, d, t, ph, fl, flLr, flFrames, mt, mtLr, mtFrames, pt)
+                       : mt ? mc_load_ir_sweep_match(_engine, idx, r.lr, r.frames, r.nframes, &w.sweep, w.offset, w.irFrames, &s, q, d, t, ph, fl, flLr, flFrames, mt, mtLr, mtFrames)
+                       : fl ? mc_load_ir_sweep_filter(_engine, idx, r.lr, r.frames, r.nframes, &w.sweep, w.offset, w.irFrames, &s, q, d, t, ph, fl, flLr, flFrames)
+                       : ph ? mc_load_ir_sweep_phase(_engine, idx, r.lr, r.frames, r.nframes, &w.sweep, w.offset, w.irFrames, &s, q, d, t, ph)
+                       : t  ? mc_load_ir_sweep_tail(_engine, idx, r.lr, r.frames, r.nframes, &w.sweep, w.offset, w.irFrames, &s, q, d, t)
+                            : mc_load_ir_sweep(_engine, idx, r.lr, r.frames, r.nframes, &w.sweep, w.offset, w.irFrames, &s, q, d);
         if (rc != MC_OK) {
             Log::error("conv", "IR %zu cannot be captured: %s", idx, mc_last_error());
             std::exit(2);
         }
+    } else if (pt || mt || fl || ph) {  // (what these steps refuse is the command line's fault: a message and exit 2, no abort)
+        const int rc = pt   ? mc_load_ir_parts(_engine, idx, r.lr, r.frames, r.nframes, irRate, sessionRate, &s, q, d, t, ph, fl, flLr, flFrames, mt, mtLr, mtFrames, pt)
+                       : mt ? mc_load_ir_match(_engine, idx, r.lr, r.frames, r.nframes, irRate, sessionRate, &s, q, d, t, ph, fl, flLr, flFrames, mt, mtLr, mtFrames)
+                       : fl ? mc_load_ir_filter(_engine, idx, r.lr, r.frames, r.nframes, irRate, sessionRate, &s, q, d, t, ph, fl, flLr, flFrames)
+                            : mc_load_ir_phase(_engine, idx, r.lr, r.frames, r.nframes, irRate, sessionRate, &s, q, d, t, ph);
+        if (rc != MC_OK) {
+            if (pt) Log::error("conv", "IR %zu cannot be split into parts: %s", idx, mc_last_error());
+            else if (mt) Log::error("conv", "IR %zu cannot be matched to %s: %s", idx, r.match->path.c_str(), mc_last_error());
+            else if (fl) Log::error("conv", "IR %zu cannot be filtered with %s: %s", idx, r.filter->path.c_str(), mc_last_error());
+            else Log::error("conv", "IR %zu cannot be converted to minimum phase: %s", idx, mc_last_error());
+            std::exit(2);
+        }
+    } else if (t)
+        check(mc_load_ir_tail(_engine, idx, r.lr, r.frames, r.nframes, irRate, sessionRate, &s, q, d, t), "mc_load_ir_tail");
+    else if (d)
+        check(mc_load_ir_damped(_engine, idx, r.lr, r.frames, r.nframes, irRate, sessionRate, &s, q, d), "mc_load_ir_damped");
+    else if (q)
+        check(mc_load_ir_eq(_engine, idx, r.lr, r.frames, r.nframes, irRate, sessionRate, &s, q), "mc_load_ir_eq");
+    else
+        check(mc_load_ir_shaped(_engine, idx, r.lr, r.frames, r.nframes, irRate, sessionRate, &s), "mc_load_ir_shaped");
+
+    // what was done: the source's lines, then one per step in the order the frames went through them
+    if (r.room) {
+        double ri[8];
+        check(mc_ir_room_info(_engine, idx, ri), "mc_ir_room_info");
+        Log::info(name, "IR %zu room: order %d, %llu and %llu images before frame %llu, direct sound at %.2f and %.2f frames, complete up to frame %llu",
+                  idx, (int)ri[0], (unsigned long long)ri[1], (unsigned long long)ri[2], (unsigned long long)ri[5], ri[3], ri[4],
+                  (unsigned long long)ri[6]);
+    }
+    if (r.mics) {
+        double mi[8];
+        check(mc_ir_room_mics_info(_engine, idx, mi), "mc_ir_room_mics_info");
+        Log::info(name, "IR %zu microphones: the direct sound leaves the source at %.4f and %.4f, is received at %.4f and %.4f, factors %.4f and %.4f",
+                  idx, mi[0], mi[1], mi[2], mi[3], mi[4], mi[5]);
+    }
+    if (r.bands) {
+        double bi[16];
+        check(mc_ir_room_bands_info(_engine, idx, bi), "mc_ir_room_bands_info");
+        std::string sabine, eyring;
+        for (int j = 0; j < (int)bi[0]; j++) {
+            char one[32];
+            std::snprintf(one, sizeof(one), "%s%.3f", j ? " / " : "", bi[4 + j]);
+            sabine += one;
+            std::snprintf(one, sizeof(one), "%s%.3f", j ? " / " : "", bi[8 + j]);
+            eyring += one;
+        }
+        Log::info(name, "IR %zu bands: %d, low to high Sabine %s s, Eyring %s s", idx, (int)bi[0], sabine.c_str(), eyring.c_str());
+    }
+    if (generated) {
+        double si[4];
+        check(mc_ir_synth_info(_engine, idx, si), "mc_ir_synth_info");
+        Log::info(name, "IR %zu synthesised: %llu frames, seed %llu, %d of %u reflections kept", idx, (unsigned long long)si[0],
+                  (unsigned long long)r.synth->seed, (int)si[1], r.synth->n_early);
+    }
+    if (r.sweep) {
         double wi[4];
         check(mc_ir_sweep_info(_engine, idx, wi), "mc_ir_sweep_info");
         Log::info(name, "IR %zu captured: sweep %llu frames, recording %llu frames, %llu frames at offset %lld", idx, (unsigned long long)wi[0],
                   (unsigned long long)wi[1], (unsigned long long)wi[2], (long long)wi[3]);
-    } else if (parted) {  // (boundaries and delays that leave nothing are the command line's fault: a message and exit 2, no abort)
-        if (mc_load_ir_parts(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail,
-                             minimum ? &ph : nullptr, filtered ? &fl : nullptr, _irFilter.lr.data(), flFrames, matched ? &mt : nullptr, _irMatch.lr.data(),
-                             mtFrames, &pt) != MC_OK) {
-            Log::error("conv", "IR %zu cannot be split into parts: %s", idx, mc_last_error());
-            std::exit(2);
-        }
-    } else if (matched) {  // (lengths and a grid beyond the step are the command line's fault: a message and exit 2, no abort)
-        if (mc_load_ir_match(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail,
-                             minimum ? &ph : nullptr, filtered ? &fl : nullptr, _irFilter.lr.data(), flFrames, &mt, _irMatch.lr.data(), mtFrames) != MC_OK) {
-            Log::error("conv", "IR %zu cannot be matched to %s: %s", idx, _irMatch.path.c_str(), mc_last_error());
-            std::exit(2);
-        }
-    } else if (filtered) {  // (lengths beyond the step are the command line's fault: a message and exit 2, no abort)
-        if (mc_load_ir_filter(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail,
-                              minimum ? &ph : nullptr, &fl, _irFilter.lr.data(), flFrames) != MC_OK) {
-            Log::error("conv", "IR %zu cannot be filtered with %s: %s", idx, _irFilter.path.c_str(), mc_last_error());
-            std::exit(2);
-        }
-    } else if (minimum) {  // (an IR too long for the step is the command line's fault: a message and exit 2, no abort)
-        if (mc_load_ir_phase(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail, &ph) != MC_OK) {
-            Log::error("conv", "IR %zu cannot be converted to minimum phase: %s", idx, mc_last_error());
-            std::exit(2);
-        }
-    } else if (tail) {
-        check(mc_load_ir_tail(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, damp.off() ? nullptr : &d, tail),
-              "mc_load_ir_tail");
-    } else if (!damp.off()) {
-        check(mc_load_ir_damped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, eq.off() ? nullptr : &q, &d), "mc_load_ir_damped");
-    } else if (eq.off())
-        check(mc_load_ir_shaped(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s), "mc_load_ir_shaped");
-    else
-        check(mc_load_ir_eq(_engine, idx, lr, frames, nframes, irRate, sessionRate, &s, &q), "mc_load_ir_eq");
-    if (tail) {
+    }
+    if (t) {
         double ti[4];
         check(mc_ir_tail_info(_engine, idx, ti), "mc_ir_tail_info");
         std::string knees;
-        for (uint32_t j = 0; j <= tail->n_xovers; j++)
-            knees += (j ? ", " : "") + (tail->knee[j] == ~0ull ? std::string("none") : std::to_string((unsigned long long)tail->knee[j]));
+        for (uint32_t j = 0; j <= t->n_xovers; j++)
+            knees += (j ? ", " : "") + (t->knee[j] == ~0ull ? std::string("none") : std::to_string((unsigned long long)t->knee[j]));
         Log::info(name, "IR %zu tail: %s, %d of %u bands at knees %s, %llu frames in, %llu out, first frame changed %llu", idx,
-                  tail->mode == MC_TAIL_CUT ? "cut" : "extended", (int)ti[0], tail->n_xovers + 1, knees.c_str(), (unsigned long long)ti[1],
+                  t->mode == MC_TAIL_CUT ? "cut" : "extended", (int)ti[0], t->n_xovers + 1, knees.c_str(), (unsigned long long)ti[1],
                   (unsigned long long)ti[2], (unsigned long long)ti[3]);
     }
-    if (minimum) {
+    if (ph) {
         double pi[8];
         check(mc_ir_phase_info(_engine, idx, pi), "mc_ir_phase_info");
         const double removed = pi[4] - pi[5];
@@ -495,15 +503,15 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
                   idx, (unsigned long long)pi[0], (unsigned long long)pi[1], removed, samplerate ? 1000.0 * removed / (double)samplerate : 0.0,
                   pi[2] > 0.0 && pi[3] > 0.0 ? 10.0 * std::log10(pi[3] / pi[2]) : 0.0, (unsigned long long)pi[6], (unsigned long long)pi[7]);
     }
-    if (filtered) {
+    if (fl) {
         double fi[10];
         check(mc_ir_filter_info(_engine, idx, fi), "mc_ir_filter_info");
         Log::info(name, "IR %zu %s %s: %llu frames and %llu filter frames through a transform of %llu points, %llu frames kept, level %+.2f dB, %.2f dB left behind, %llu and %llu bins regularised",
-                  idx, _irFilter.deconvolve ? "deconvolved by" : "convolved with", _irFilter.path.c_str(), (unsigned long long)fi[0], (unsigned long long)fi[1],
+                  idx, r.filter->deconvolve ? "deconvolved by" : "convolved with", r.filter->path.c_str(), (unsigned long long)fi[0], (unsigned long long)fi[1],
                   (unsigned long long)fi[3], (unsigned long long)fi[2], fi[4] > 0.0 && fi[6] > 0.0 ? 10.0 * std::log10(fi[6] / fi[4]) : 0.0,
                   fi[6] > 0.0 && fi[7] > 0.0 ? std::max(-999.0, 10.0 * std::log10(fi[7] / fi[6])) : -999.0, (unsigned long long)fi[8], (unsigned long long)fi[9]);
     }
-    if (matched) {
+    if (mt) {
         double mi[12];
         check(mc_ir_match_info(_engine, idx, mi), "mc_ir_match_info");
         std::vector<double> hz(1024), before(2048), gain(2048);
@@ -512,37 +520,37 @@ void Convolution::loadShaped(size_t idx, const float* lr, uint64_t frames, size_
         double least = 0.0, most = 0.0;
         for (int j = 0; j < 2 * J; j++) least = std::min(least, gain[j]), most = std::max(most, gain[j]);
         Log::info(name, "IR %zu matched to %s: %llu frames and %llu target frames through a transform of %llu points, %llu frames kept, %d points, gain %+.2f .. %+.2f dB, %llu clamped, level %+.2f dB",
-                  idx, _irMatch.path.c_str(), (unsigned long long)mi[0], (unsigned long long)mi[1], (unsigned long long)mi[3], (unsigned long long)mi[2], J, least,
+                  idx, r.match->path.c_str(), (unsigned long long)mi[0], (unsigned long long)mi[1], (unsigned long long)mi[3], (unsigned long long)mi[2], J, least,
                   most, (unsigned long long)mi[11], mi[5] > 0.0 && mi[7] > 0.0 ? 10.0 * std::log10(mi[7] / mi[5]) : 0.0);
         if (_irMatchReport)
             for (int j = 0; j < J; j++)
                 Log::info(name, "IR %zu match %.3f Hz: before %+.4f %+.4f dB, gain %+.4f %+.4f dB", idx, hz[j], before[2 * j], before[2 * j + 1], gain[2 * j],
                           gain[2 * j + 1]);
     }
-    if (parted) {
+    if (pt) {
         double pi[10];
         check(mc_ir_parts_info(_engine, idx, pi), "mc_ir_parts_info");
         const double rest = pi[5] + pi[6];
         Log::info(name, "IR %zu parts: %llu frames in, %llu out, direct to %llu, early to %llu%s, energies %.6e / %.6e / %.6e, direct to reverberant %+.2f dB, level %+.2f dB, %llu contributions lost (%.6e)",
                   idx, (unsigned long long)pi[0], (unsigned long long)pi[1], (unsigned long long)pi[2], (unsigned long long)pi[3],
-                  _partsMeasured ? " (the mixing tap)" : "", pi[4], pi[5], pi[6], pi[4] > 0.0 && rest > 0.0 ? 10.0 * std::log10(pi[4] / rest) : 0.0,
+                  r.split ? " (the mixing tap)" : "", pi[4], pi[5], pi[6], pi[4] > 0.0 && rest > 0.0 ? 10.0 * std::log10(pi[4] / rest) : 0.0,
                   pi[4] + rest > 0.0 && pi[7] > 0.0 ? 10.0 * std::log10(pi[7] / (pi[4] + rest)) : 0.0, (unsigned long long)pi[9], pi[8]);
     }
     double info[8];
     check(mc_ir_shape_info(_engine, idx, info), "mc_ir_shape_info");
     Log::info(name, "IR %zu shaped: onset %llu, first kept frame %llu, %llu taps, gain %+.2f dB", idx, (unsigned long long)info[1],
               (unsigned long long)info[2], (unsigned long long)info[3], 20.0 * std::log10(info[4]));
-    if (!eq.off()) {
+    if (q) {
         const double hz = 1000.0;
         double db = 0.0;
-        check(mc_ir_eq_response(&q, sessionRate, &hz, 1, &db), "mc_ir_eq_response");
+        check(mc_ir_eq_response(q, sessionRate, &hz, 1, &db), "mc_ir_eq_response");
         Log::info(name, "IR %zu equalised: %d bands, %+.2f dB at 1 kHz", idx, (int)info[7], db);
     }
-    if (!damp.off()) {
+    if (d) {
         double di[4];
         check(mc_ir_damp_info(_engine, idx, di), "mc_ir_damp_info");
         std::string decays;
-        for (uint32_t j = 0; j <= d.n_xovers; j++) decays += (j ? ", " : "") + std::to_string((unsigned long long)d.decay_t60[j]);
+        for (uint32_t j = 0; j <= d->n_xovers; j++) decays += (j ? ", " : "") + std::to_string((unsigned long long)d->decay_t60[j]);
         Log::info(name, "IR %zu damped: %d crossovers, origin %llu, %d bands with a decay (%s frames)", idx, (int)di[0], (unsigned long long)di[1],
                   (int)di[2], decays.c_str());
     }
@@ -633,24 +641,25 @@ static double measuredRt(Convolution& c, size_t idx) {
     return std::isnan(t30) ? d.at(0, Convolution::Decay::LR, Convolution::Decay::T20) : t30;
 }
 
-void Convolution::aimRt60(const PendingIr& p) {
-    const double measured = measuredRt(*this, p.idx);
+void Convolution::aimRt60(const IrLoadRequest& loaded) {
+    const double measured = measuredRt(*this, loaded.idx);
     if (std::isnan(measured)) {
-        Log::warn(name, "IR %zu rt60: its decay curve does not reach -25 dB, left as it is", p.idx);
+        Log::warn(name, "IR %zu rt60: its decay curve does not reach -25 dB, left as it is", loaded.idx);
         return;
     }
     const uint64_t fit = decayForRt60(measured, _rt60, (double)samplerate);
     if (!fit) {
-        Log::info(name, "IR %zu rt60: target %.4f s is not below the measured %.4f s, left as it is", p.idx, _rt60, measured);
+        Log::info(name, "IR %zu rt60: target %.4f s is not below the measured %.4f s, left as it is", loaded.idx, _rt60, measured);
         return;
     }
     // slopes add: 1 / d = 1 / d_user + 1 / d_fit
-    IrShape shape = p.shape;
+    IrLoadRequest again = loaded;  // (the measured tail and split included)
+    IrShape& shape = again.shape;
     shape.decayT60 = shape.decayT60 ? (uint64_t)std::nearbyint(1.0 / (1.0 / (double)shape.decayT60 + 1.0 / (double)fit)) : fit;
     if (!shape.decayT60) shape.decayT60 = 1;
-    loadPending(p, shape);
-    Log::info(name, "IR %zu rt60: measured %.4f s, decay %llu frames, now %s s", p.idx, measured, (unsigned long long)shape.decayT60,
-              places(measuredRt(*this, p.idx), 4).c_str());
+    loadIr(again);
+    Log::info(name, "IR %zu rt60: measured %.4f s, decay %llu frames, now %s s", loaded.idx, measured, (unsigned long long)shape.decayT60,
+              places(measuredRt(*this, loaded.idx), 4).c_str());
 }
 
 void Convolution::setIrFloorReport(bool on) {
@@ -779,34 +788,31 @@ bool Convolution::parseParts(const std::string& arg, IrParts& out, std::string& 
     return true;
 }
 
-// Loads p with every step but the parts and with no shape, EQ or damping, measures its echo density and leaves in _partsOnset /
-// _partsMix / _partsMeasured the boundaries its final load goes through
-void Convolution::measureParts(const PendingIr& p) {
-    _partsMeasured = false;
+// Loads p with every step but the parts (the measured tail included) and with no shape, EQ or damping, measures its echo density
+// and returns the boundaries its final load goes through; nothing for a generated IR, which has no parts step
+std::optional<Convolution::PartsSplit> Convolution::measureParts(const PendingIr& p, const std::optional<mc_ir_tail>& tail) {
     if (!mc_default_ir_parts || !mc_load_ir_parts || !mc_load_ir_sweep_parts || !mc_ir_parts_at || !mc_ir_parts_info) {
         Log::error("conv", "the engine has no parts step (mc_load_ir_parts)");
         std::exit(2);
     }
-    if (p.generated) return;  // (loadShaped says that it has no parts step)
-    PendingIr raw = p;
-    raw.eq = IrEq();
-    raw.damp = IrDamp();
-    IrParts parts;
-    std::swap(parts, _irParts);
-    loadPending(raw, IrShape());
-    std::swap(parts, _irParts);
+    if (p.generated) return std::nullopt;  // (loadIr says that it has no parts step)
+    IrLoadRequest raw = requestFor(p);
+    raw.tail = tail;
+    raw.parts = nullptr;
+    raw.shape = IrShape(), raw.eq = IrEq(), raw.damp = IrDamp();
+    loadIr(raw);
     const Density d = irDensity(p.idx, _densityQuery);
-    _partsOnset = d.origin;
+    PartsSplit split{d.origin, 0};
     if (d.at(Decay::LR, Density::Status) != 0.0) {
-        _partsMix = _partsOnset + (uint64_t)std::nearbyint(0.08 * (double)samplerate);
+        split.mix = split.onset + (uint64_t)std::nearbyint(0.08 * (double)samplerate);
         Log::warn(name, "IR %zu parts: the echo density never reaches 1 (largest %s), the early part ends 80 ms after the onset at frame %llu", p.idx,
-                  places(d.at(Decay::LR, Density::Max), 3).c_str(), (unsigned long long)_partsOnset);
+                  places(d.at(Decay::LR, Density::Max), 3).c_str(), (unsigned long long)split.onset);
     } else {
-        _partsMix = std::max<uint64_t>((uint64_t)d.at(Decay::LR, Density::Mix), _partsOnset);
-        Log::info(name, "IR %zu parts: onset at frame %llu, the early part ends at the mixing tap %llu", p.idx, (unsigned long long)_partsOnset,
-                  (unsigned long long)_partsMix);
+        split.mix = std::max<uint64_t>((uint64_t)d.at(Decay::LR, Density::Mix), split.onset);
+        Log::info(name, "IR %zu parts: onset at frame %llu, the early part ends at the mixing tap %llu", p.idx, (unsigned long long)split.onset,
+                  (unsigned long long)split.mix);
     }
-    _partsMeasured = true;
+    return split;
 }
 
 void Convolution::setIrMatch(const IrMatch& match, bool report) {
@@ -1058,47 +1064,39 @@ void Convolution::reportFloor(size_t idx) {
     }
 }
 
-// Loads p as it is (no shape, EQ or damping: the frames at the client's rate), measures its floor and leaves in _tailNow / _tailOn
-// the tail step its final load goes through
-void Convolution::measureTail(const PendingIr& p) {
-    _tailOn = false;
+// Loads p as it is (no shape, EQ or damping: the frames at the client's rate), measures its floor and returns the tail step its
+// final load goes through; nothing for an IR that is left as it is
+std::optional<mc_ir_tail> Convolution::measureTail(const PendingIr& p) {
     if (!mc_ir_tail_from_floor || !mc_default_ir_tail || !mc_load_ir_tail) {
         Log::error("conv", "the engine has no tail step (mc_load_ir_tail)");
         std::exit(2);
     }
     if (p.generated && !p.roomed) {
         Log::info(name, "IR %zu tail: a generated IR has no floor, left as it is", p.idx);
-        return;
+        return std::nullopt;
     }
-    PendingIr raw = p;
-    raw.eq = IrEq();
-    raw.damp = IrDamp();
-    const IrPhase phase = _irPhase;  // (the floor is that of the frames the tail step will see: before the phase and filter steps)
-    IrFilter filter;
-    IrMatch match;
-    std::swap(filter, _irFilter);
-    std::swap(match, _irMatch);
-    _irPhase = IrPhase();
-    loadPending(raw, IrShape());
-    _irPhase = phase;
-    std::swap(filter, _irFilter);
-    std::swap(match, _irMatch);
+    IrLoadRequest raw = requestFor(p);
+    raw.shape = IrShape(), raw.eq = IrEq(), raw.damp = IrDamp();
+    raw.phase = nullptr, raw.filter = nullptr, raw.match = nullptr;  // (the floor is that of the frames the tail step will see: before the steps after it)
+    // A known divergence from that, and from what DESIGN.md says: raw.parts stays, so with the parts step on the floor is measured
+    // on frames that went through it, although it runs after the tail.  Kept as the host has behaved since the parts step came.
+    loadIr(raw);
     const Floor f = irFloor(p.idx, _floorXovers);
     const double need = (double)f.query.margin_db + (double)f.query.span_db, ptn = f.at(0, Decay::LR, Floor::PeakToNoise);
     if (f.at(0, Decay::LR, Floor::Status) != 0.0 || !(ptn >= need)) {
         Log::info(name, "IR %zu tail: peak to noise %s dB (status %d) is under %g dB, left as it is", p.idx, places(ptn, 2).c_str(),
                   (int)f.at(0, Decay::LR, Floor::Status), need);
-        return;
+        return std::nullopt;
     }
-    mc_default_ir_tail(&_tailNow);
+    mc_ir_tail tail;
+    mc_default_ir_tail(&tail);
     const uint64_t info[2] = {f.origin, f.taps};
-    check(mc_ir_tail_from_floor(&f.query, f.rows.data(), info, 0, &_tailNow), "mc_ir_tail_from_floor");
-    _tailNow.mode = _irTail.mode == IrTail::Cut ? MC_TAIL_CUT : MC_TAIL_EXTEND;
-    _tailNow.fade = (uint32_t)std::nearbyint(_irTail.fadeSeconds * (double)samplerate);
-    _tailNow.length = (uint64_t)std::nearbyint(_irTail.lengthSeconds * (double)samplerate);
-    _tailNow.seed = _irTail.seed;
-    _tailNow.width = _irTail.width;
-    _tailOn = true;
+    check(mc_ir_tail_from_floor(&f.query, f.rows.data(), info, 0, &tail), "mc_ir_tail_from_floor");
+    tail.mode = _irTail.mode == IrTail::Cut ? MC_TAIL_CUT : MC_TAIL_EXTEND;
+    tail.fade = (uint32_t)std::nearbyint(_irTail.fadeSeconds * (double)samplerate);
+    tail.length = (uint64_t)std::nearbyint(_irTail.lengthSeconds * (double)samplerate);
+    tail.seed = _irTail.seed;
+    tail.width = _irTail.width;
     if (_irTail.widthFromIacc) {
         if (!mc_ir_tail_width_from_iacc) {
             Log::error("conv", "the engine cannot take a width from an IACC (mc_ir_tail_width_from_iacc)");
@@ -1110,13 +1108,13 @@ void Convolution::measureTail(const PendingIr& p) {
         const double rho = a.at(0, Iacc::Late, Iacc::Iacf0);
         if (a.at(0, Iacc::Late, Iacc::Status) != 0.0)
             Log::warn(name, "IR %zu tail: the late window from tap %llu has no correlation to read (status 1), the width stays %.9g", p.idx,
-                      (unsigned long long)a.split, (double)_tailNow.width);
+                      (unsigned long long)a.split, (double)tail.width);
         else {
-            check(mc_ir_tail_width_from_iacc(&_tailNow, rho), "mc_ir_tail_width_from_iacc");
-            Log::info(name, "IR %zu tail: width %.9g from the late IACF(0) %.9f", p.idx, (double)_tailNow.width, rho);
+            check(mc_ir_tail_width_from_iacc(&tail, rho), "mc_ir_tail_width_from_iacc");
+            Log::info(name, "IR %zu tail: width %.9g from the late IACF(0) %.9f", p.idx, (double)tail.width, rho);
         }
     }
-    if (!_irTail.kneeAtMix) return;
+    if (!_irTail.kneeAtMix) return tail;
     if (!mc_ir_tail_move_knee) {
         Log::error("conv", "the engine cannot move a knee (mc_ir_tail_move_knee)");
         std::exit(2);
@@ -1125,12 +1123,13 @@ void Convolution::measureTail(const PendingIr& p) {
     if (d.at(Decay::LR, Density::Status) != 0.0) {
         Log::warn(name, "IR %zu tail: the echo density never reaches 1 (largest %s), the knees stay at the floor's", p.idx,
                   places(d.at(Decay::LR, Density::Max), 3).c_str());
-        return;
+        return tail;
     }
     const uint64_t mix = (uint64_t)d.at(Decay::LR, Density::Mix);
-    for (uint32_t j = 0; j <= _tailNow.n_xovers; j++)
-        if (_tailNow.knee[j] != ~0ull) check(mc_ir_tail_move_knee(&_tailNow, j, mix), "mc_ir_tail_move_knee");
+    for (uint32_t j = 0; j <= tail.n_xovers; j++)
+        if (tail.knee[j] != ~0ull) check(mc_ir_tail_move_knee(&tail, j, mix), "mc_ir_tail_move_knee");
     Log::info(name, "IR %zu tail: knees moved to the mixing tap %llu", p.idx, (unsigned long long)mix);
+    return tail;
 }
 
 void Convolution::setIrDensityReport(bool on, const DensityQuery& query) {
@@ -1723,11 +1722,20 @@ void Convolution::prepareRoom(size_t idx, const IrRoom& room, size_t nframes) {
         Log::error("conv", "room rendering is not available with several devices (mc_synth_ir_room is single-engine)");
         std::exit(2);
     }
-    PendingIr p{idx, nframes, 0, {}, _irShape, _irEq, false, _irDamp, true, room.late, false, IrSweep()};  // (rendered by onStart(), once the client's rate is known)
-    p.roomed = true;
+    PendingIr& p = pend(idx, nframes);  // (rendered by onStart(), once the client's rate is known)
+    p.generated = p.roomed = true;
+    p.synth = room.late;
     p.room = room;
-    _pendingIrs.push_back(std::move(p));
+}
+
+// A new entry of _pendingIrs with what every kind of IR has: its place, and the shape, EQ and damping that are set now
+Convolution::PendingIr& Convolution::pend(size_t idx, size_t nframes) {
+    _pendingIrs.emplace_back();
+    PendingIr& p = _pendingIrs.back();
+    p.idx = idx, p.nframes = nframes;
+    p.shape = _irShape, p.eq = _irEq, p.damp = _irDamp;
     if (idx + 1 > _nirs) _nirs = idx + 1;
+    return p;
 }
 
 void Convolution::prepareSynth(size_t idx, const IrSynth& synth, size_t nframes) {
@@ -1735,8 +1743,9 @@ void Convolution::prepareSynth(size_t idx, const IrSynth& synth, size_t nframes)
         Log::error("conv", "IR synthesis is not available with several devices (mc_synth_ir is single-engine)");
         std::exit(2);
     }
-    _pendingIrs.push_back(PendingIr{idx, nframes, 0, {}, _irShape, _irEq, false, _irDamp, true, synth, false, IrSweep()});  // (generated by onStart(), once the client's rate is known)
-    if (idx + 1 > _nirs) _nirs = idx + 1;
+    PendingIr& p = pend(idx, nframes);  // (generated by onStart(), once the client's rate is known)
+    p.generated = true;
+    p.synth = synth;
 }
 
 void Convolution::prepareSynth(size_t idx, const mc_ir_synth& synth, size_t nframes) {
@@ -1744,7 +1753,9 @@ void Convolution::prepareSynth(size_t idx, const mc_ir_synth& synth, size_t nfra
         Log::error("conv", "IR synthesis is not available with several devices (mc_synth_ir is single-engine)");
         std::exit(2);
     }
-    loadShaped(idx, nullptr, synth.frames, nframes, synth.rate, synth.rate, _irShape, _irEq, _irDamp, &synth);
+    IrLoadRequest r = requestNow(idx, nframes, _irShape, _irEq, _irDamp);
+    r.synth = synth;
+    loadIr(r);
     if (idx + 1 > _nirs) _nirs = idx + 1;
 }
 
@@ -1871,12 +1882,26 @@ void Convolution::prepareSweep(size_t idx, const IrSweep& sweep, const WavFile& 
         std::exit(2);
     }
     const float* lr = &recording.buffer[0].x;  // (deconvolved by onStart(), once the client's rate is known)
-    PendingIr p{idx, nframes, recording.sampleRate, std::vector<float>(lr, lr + 2 * recording.numFrames), _irShape, _irEq, false, _irDamp, false, IrSynth(), true, sweep};
-    _pendingIrs.push_back(std::move(p));
-    if (idx + 1 > _nirs) _nirs = idx + 1;
+    PendingIr& p = pend(idx, nframes);
+    p.rate = recording.sampleRate;
+    p.lr.assign(lr, lr + 2 * recording.numFrames);
+    p.swept = true;
+    p.sweep = sweep;
 }
 
-void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
+Convolution::IrLoadRequest Convolution::requestNow(size_t idx, size_t nframes, const IrShape& shape, const IrEq& eq, const IrDamp& damp) const {
+    IrLoadRequest r;
+    r.idx = idx, r.nframes = nframes;
+    r.shape = shape, r.eq = eq, r.damp = damp;
+    r.phase = _irPhase.minimum ? &_irPhase : nullptr;
+    r.filter = _irFilter.on ? &_irFilter : nullptr;
+    r.match = _irMatch.on ? &_irMatch : nullptr;
+    r.parts = _irParts.on ? &_irParts : nullptr;
+    return r;
+}
+
+Convolution::IrLoadRequest Convolution::requestFor(const PendingIr& p) {
+    IrLoadRequest r = requestNow(p.idx, p.nframes, p.shape, p.eq, p.damp);
     if (p.swept) {
         if (!mc_default_sweep) {
             Log::error("conv", "the engine has no sweep capture (mc_load_ir_sweep)");
@@ -1895,9 +1920,9 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
                                                   : M - (int64_t)w.sweep.frames + 1 - w.offset;  // what the recording holds past the sweep
         if (!(p.sweep.irLengthSeconds > 0.0)) F = std::min(F, std::min(cap, (int64_t)((1ull << 40) / std::max<uint64_t>(w.sweep.frames, 1))));
         w.irFrames = (uint64_t)std::max<int64_t>(F, 1);
-        loadShaped(p.idx, p.lr.data(), (uint64_t)M, p.nframes, (unsigned)samplerate, (unsigned)samplerate, shape, p.eq, p.damp, nullptr, &w,
-                   _tailOn ? &_tailNow : nullptr);
-        return;
+        r.lr = p.lr.data(), r.frames = (uint64_t)M;
+        r.sweep = w;
+        return r;
     }
     if (p.generated) {
         if (p.roomed && p.room.banded && !mc_default_ir_room_bands) {
@@ -1916,58 +1941,34 @@ void Convolution::loadPending(const PendingIr& p, const IrShape& shape) {
             Log::error("conv", "the engine has no IR synthesis (mc_synth_ir)");
             std::exit(2);
         }
-        if (p.roomed) {
-            const mc_ir_synth s = synthFrames(p.room.late, (double)samplerate);
-            const mc_ir_room r = roomFrames(p.room, (double)samplerate);
-            mc_ir_room_mics m;
-            if (p.room.directional) m = roomMics(p.room);
-            mc_ir_room_bands b;
-            if (p.room.banded) b = roomBands(p.room);
-            loadShaped(p.idx, nullptr, s.frames, p.nframes, s.rate, s.rate, shape, p.eq, p.damp, &s, nullptr, _tailOn ? &_tailNow : nullptr, &r,
-                       p.room.directional ? &m : nullptr, p.room.banded ? &b : nullptr);
-            return;
-        }
-        const mc_ir_synth s = synthFrames(p.synth, (double)samplerate);
-        loadShaped(p.idx, nullptr, s.frames, p.nframes, s.rate, s.rate, shape, p.eq, p.damp, &s);
-        return;
+        r.synth = synthFrames(p.roomed ? p.room.late : p.synth, (double)samplerate);
+        if (p.roomed) r.room = roomFrames(p.room, (double)samplerate);
+        if (p.roomed && p.room.directional) r.mics = roomMics(p.room);
+        if (p.roomed && p.room.banded) r.bands = roomBands(p.room);
+        return r;
     }
-    const uint64_t frames = p.lr.size() / 2;
-    const bool convert = p.match && p.rate && p.rate != samplerate;
-    if (!p.eq.off() || !p.damp.off() || _tailOn) {  // (bands and crossovers are laid out at the client's rate; frames that are not converted count as being at it)
-        loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : (unsigned)samplerate, (unsigned)samplerate, shape, p.eq, p.damp, nullptr,
-                   nullptr, _tailOn ? &_tailNow : nullptr);
-        return;
-    }
-    if (!shape.off() || _irPhase.minimum || _irFilter.on || _irMatch.on || _irParts.on) {
-        loadShaped(p.idx, p.lr.data(), frames, p.nframes, convert ? p.rate : 0, convert ? (unsigned)samplerate : 0, shape);
-        return;
-    }
-    if (!convert) {
-        check(mc_load_ir(_engine, p.idx, p.lr.data(), frames, p.nframes), "mc_load_ir");
-        return;
-    }
-    if (!mc_load_ir_resampled) {
-        Log::error("conv", "the engine has no sample-rate conversion (mc_load_ir_resampled)");
-        std::exit(2);
-    }
-    Log::info(name, "IR %zu: %u Hz -> %zu Hz", p.idx, p.rate, samplerate);
-    check(mc_load_ir_resampled(_engine, p.idx, p.lr.data(), frames, p.nframes, p.rate, (uint32_t)samplerate), "mc_load_ir_resampled");
+    r.lr = p.lr.data(), r.frames = p.lr.size() / 2;
+    r.irRate = p.match && p.rate && p.rate != samplerate ? p.rate : 0;  // (0: loaded at the rate they have)
+    r.sessionRate = (unsigned)samplerate;
+    return r;
 }
 
 void Convolution::loadPendingIrs() {
     for (const PendingIr& p : _pendingIrs) {
-        if (_irTail.mode != IrTail::Off) measureTail(p);
-        if (_irParts.on && _irParts.splitAtMix) measureParts(p);
-        loadPending(p, p.shape);
-        if (_rt60 > 0.0) aimRt60(p);
+        std::optional<mc_ir_tail> tail;
+        std::optional<PartsSplit> split;
+        if (_irTail.mode != IrTail::Off) tail = measureTail(p);
+        if (_irParts.on && _irParts.splitAtMix) split = measureParts(p, tail);
+        IrLoadRequest r = requestFor(p);
+        r.tail = tail, r.split = split;
+        loadIr(r);
+        if (_rt60 > 0.0) aimRt60(r);
         if (_decayReport) reportDecay(p.idx);
         if (_floorReport) reportFloor(p.idx);
         if (_densityReport) reportDensity(p.idx);
         if (_iaccReport) reportIacc(p.idx);
         if (_stiReport) reportSti(p.idx);
         if (_responseReport) reportResponse(p.idx);
-        _tailOn = false;
-        _partsMeasured = false;
     }
     _pendingIrs.clear();
 }
@@ -1975,12 +1976,16 @@ void Convolution::loadPendingIrs() {
 void Convolution::prepare(size_t idx, const WavFile& wav, size_t nframes) {
     if (_matchIrRate || !_irEq.off() || !_irDamp.off() || _decayReport || _rt60 > 0.0 || _floorReport || _densityReport || _iaccReport || _stiReport || _responseReport || _irTail.mode != IrTail::Off || _irPhase.minimum || _irFilter.on || _irMatch.on || _irParts.on) {  // (loaded by onStart(), once the client's rate is known)
         const float* lr = &wav.buffer[0].x;
-        _pendingIrs.push_back(PendingIr{idx, nframes, wav.sampleRate, std::vector<float>(lr, lr + 2 * wav.numFrames), _irShape, _irEq, _matchIrRate, _irDamp, false, IrSynth(), false, IrSweep()});
-        if (idx + 1 > _nirs) _nirs = idx + 1;
+        PendingIr& p = pend(idx, nframes);
+        p.rate = wav.sampleRate;
+        p.lr.assign(lr, lr + 2 * wav.numFrames);
+        p.match = _matchIrRate;
         return;
     }
     if (!_irShape.off()) {  // (never with several devices: setIrShape)
-        loadShaped(idx, &wav.buffer[0].x, wav.numFrames, nframes, 0, 0, _irShape);
+        IrLoadRequest r = requestNow(idx, nframes, _irShape, IrEq(), IrDamp());  // (no rates: the frames are loaded at the rate they have)
+        r.lr = &wav.buffer[0].x, r.frames = wav.numFrames;
+        loadIr(r);
         if (idx + 1 > _nirs) _nirs = idx + 1;
         return;
     }

@@ -7,6 +7,7 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <optional>
 #include <string>
 #include <vector>
 
@@ -112,8 +113,7 @@ public:
     struct IrDamp {
         std::vector<float> xovers;
         std::vector<double> decaySeconds;  // xovers.size() + 1 of them
-        uint64_t origin;
-        IrDamp() : origin(0) {}  // (not a default member initialiser: IrDamp() is a default argument inside this class)
+        uint64_t origin = 0;
         bool off() const { return xovers.empty(); }
     };
     void setIrDamp(const IrDamp& damp);
@@ -480,12 +480,12 @@ private:
     size_t _pushedVsteps[2] = {0, 0};  // cc[i].value.vsteps as last handed to the engine (see pullVsteps)
     bool _matchIrRate = false;
     struct PendingIr {
-        size_t idx, nframes;
-        unsigned rate;
+        size_t idx = 0, nframes = 1024;
+        unsigned rate = 0;
         std::vector<float> lr;  // interleaved L, R frames
         IrShape shape;          // as set when the IR was prepared
         IrEq eq;
-        bool match;             // setMatchIrRate was on
+        bool match = false;     // setMatchIrRate was on
         IrDamp damp;
         bool generated = false;  // prepareSynth: `synth` instead of lr
         IrSynth synth;
@@ -499,10 +499,55 @@ private:
         int64_t offset;
         uint64_t irFrames;
     };
+    struct PartsSplit {  // measureParts: the frames of the onset and of the mixing tap
+        uint64_t onset, mix;
+    };
+    // One load of one IR: where its frames come from and every step they go through.  loadIr() reads nothing else that describes
+    // the load, so a load without some of the steps is a copy of this with those fields cleared.
+    struct IrLoadRequest {
+        size_t idx = 0, nframes = 1024;
+        // The source, exactly one of three.  Host frames: lr, `frames` of them at irRate Hz (0: at the rate they have, not
+        // converted) in a session at sessionRate Hz (0: not known).  synth: the engine generates the frames at synth->rate, with the
+        // reflections of `room`, its microphones directional with `mics`, its walls and air per frequency band with `bands`.  sweep:
+        // lr is the recording of a sweep, `frames` frames at sweep->sweep.rate, which the engine deconvolves.
+        const float* lr = nullptr;
+        uint64_t frames = 0;
+        unsigned irRate = 0, sessionRate = 0;
+        std::optional<mc_ir_synth> synth;
+        std::optional<mc_ir_room> room;
+        std::optional<mc_ir_room_mics> mics;
+        std::optional<mc_ir_room_bands> bands;
+        std::optional<SweepLoad> sweep;
+        // The steps, in the order the frames go through them: tail, phase, filter, match, parts (null = off; they point at the
+        // object's settings, whose second IRs are not copied), then shape, damp, eq.  A generated IR goes through the tail (with a
+        // room), shape, damp and eq alone.  split: the parts' boundaries as measured, in place of the settings' seconds.
+        std::optional<mc_ir_tail> tail;
+        const IrPhase* phase = nullptr;
+        const IrFilter* filter = nullptr;
+        const IrMatch* match = nullptr;
+        const IrParts* parts = nullptr;
+        std::optional<PartsSplit> split;
+        IrShape shape;
+        IrEq eq;
+        IrDamp damp;
+    };
     std::vector<PendingIr> _pendingIrs;  // (rate matching) prepared, loaded by onStart()
+    PendingIr& pend(size_t idx, size_t nframes);
     void loadPendingIrs();
-    void loadPending(const PendingIr& p, const IrShape& shape);
-    void aimRt60(const PendingIr& p);
+    IrLoadRequest requestNow(size_t idx, size_t nframes, const IrShape& shape, const IrEq& eq, const IrDamp& damp) const;  // no source yet; the steps that are set
+    IrLoadRequest requestFor(const PendingIr& p);  // p's source at the client's rate and every step that is set; no tail, no split
+    void loadIr(const IrLoadRequest& r);
+    std::optional<mc_ir_tail> measureTail(const PendingIr& p);
+    std::optional<PartsSplit> measureParts(const PendingIr& p, const std::optional<mc_ir_tail>& tail);
+    void aimRt60(const IrLoadRequest& loaded);
+    // the host's settings as the engine's structs; seconds become frames at `session` Hz
+    static mc_ir_shape shapeArg(const IrShape& shape);
+    static mc_ir_eq eqArg(const IrEq& eq);
+    static mc_ir_damp dampArg(const IrDamp& damp, double session);
+    static mc_ir_phase phaseArg(const IrPhase& phase);
+    static mc_ir_filter filterArg(const IrFilter& filter, unsigned session);
+    static mc_ir_match matchArg(const IrMatch& match, unsigned session);
+    static mc_ir_parts partsArg(size_t idx, const IrParts& parts, double session, const std::optional<PartsSplit>& split);
     void reportDecay(size_t idx);
     void reportFloor(size_t idx);
     void reportDensity(size_t idx);
@@ -517,7 +562,6 @@ private:
     IaccQuery _iaccQuery;
     bool _densityReport = false;
     DensityQuery _densityQuery;
-    void measureTail(const PendingIr& p);
     bool _floorReport = false;
     std::vector<float> _floorXovers;
     IrTail _irTail;
@@ -526,21 +570,12 @@ private:
     IrMatch _irMatch;
     bool _irMatchReport = false;
     IrParts _irParts;
-    void measureParts(const PendingIr& p);
-    bool _partsMeasured = false;  // loadPending: the IR being loaded has its boundaries in _partsOnset and _partsMix
-    uint64_t _partsOnset = 0, _partsMix = 0;
-    bool _tailOn = false;  // loadPending: the IR being loaded goes through _tailNow
-    mc_ir_tail _tailNow;
     bool _decayReport = false;
     std::vector<float> _decayBands;
     double _rt60 = 0.0;
     IrShape _irShape;
     IrEq _irEq;
     IrDamp _irDamp;
-    void loadShaped(size_t idx, const float* lr, uint64_t frames, size_t nframes, unsigned irRate, unsigned sessionRate, const IrShape& shape,
-                    const IrEq& eq = IrEq(), const IrDamp& damp = IrDamp(), const mc_ir_synth* synth = nullptr,
-                    const SweepLoad* sweep = nullptr, const mc_ir_tail* tail = nullptr, const mc_ir_room* room = nullptr,
-                    const mc_ir_room_mics* mics = nullptr, const mc_ir_room_bands* bands = nullptr);
     void pushParams();
     void pullVsteps();
 };

@@ -22,9 +22,17 @@ exists).  A step's knobs are asked for on that step's cases only:
   prepare_synth with a tail, and with a room and a tail
   a stepped load and then a plain prepare() on the same index
 
-The fixture is recorded by this module run as a program, in a process of its own, with MCCONV_LIB naming the library to record:
+tests/golden/ir_load_bits_parts.json is a second fixture by the same mechanism for the parts step (step 1e), which the first
+one's commit predates, under the package and the library of the commit it names: the last one at which prepare() and
+prepare_sweep() chose among the entry points themselves.  Its digests cover ir_parts_info too.  Frames 200 and 5000: the parts
+step alone, all five steps, all five with the IR at 44100 Hz; prepare_sweep with the parts alone and with all five; a five-step
+load and then a plain prepare() on the same index.  No tolerance here either: only the callers of the library moved.
+
+A fixture is recorded by this module run as a program, in a process of its own, with MCCONV_LIB naming the library to record,
+or MCCONV_TREE the built checkout whose package and library are recorded; a third argument `parts` records the second fixture:
     MCCONV_LIB=<the build to record> python tests/test_gpu_ir_load_bits.py <output.json> <the commit that build is of>
-The test itself never records and never skips."""
+    MCCONV_TREE=<a built checkout of the commit> python tests/test_gpu_ir_load_bits.py <output.json> <that commit> parts
+The tests themselves never record and never skip."""
 import hashlib
 import json
 import os
@@ -39,7 +47,9 @@ pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ir_load_bits.json")
 RATE = 48000
 N_REF = 65536
+GOLDEN_PARTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ir_load_bits_parts.json")
 FRAMES = (1, 200, 5000)
+PARTS_FRAMES = (200, 5000)
 GETTERS = ("shape", "damp", "synth", "room", "room_bands", "room_mics", "sweep", "tail", "phase", "filter", "match")
 
 
@@ -77,10 +87,10 @@ def _or_error(call):
         return f"error {e.code}: {e}"
 
 
-def _stored(c, idx):
+def _stored(c, idx, getters=GETTERS):
     """everything the engine tells of IR idx"""
     got = dict(taps=_or_error(lambda: c.ir_taps(idx)), info=_or_error(lambda: c.ir_info(idx)), curve=_or_error(lambda: c.ir_match_curve(idx)))
-    for name in GETTERS:
+    for name in getters:
         got[name] = _or_error(lambda: getattr(c, f"ir_{name}_info")(idx))
     return got
 
@@ -161,28 +171,83 @@ def digests(verbose=False):
     return out
 
 
-def test_the_bits_are_those_before_the_step_plan(gpu_lib):
-    with open(GOLDEN) as fh:
+def parts_digests(verbose=False):
+    """{case: SHA-256} of the library and the package that are loaded, for the cases with the parts step."""
+    from cuda_audio_amd.engine import Convolution, IrFilter, IrMatch, IrParts, IrPhase, IrTail, Sweep
+    from cuda_audio_amd.synth import make_ir
+
+    out = {}
+    c = Convolution("bitsparts", N_REF, sample_rate=RATE, stream_threshold=8, max_batch=8)
+
+    def put(case, load):
+        assert case not in out, case
+        refused = _or_error(lambda: load(0))
+        got = refused if refused is not None else _stored(c, 0, GETTERS + ("parts",))
+        h = hashlib.sha256()
+        _feed(h, got)
+        out[case] = h.hexdigest()
+        if verbose:
+            print(case, refused if refused is not None else {k: v for k, v in got.items() if isinstance(v, str)}, flush=True)
+
+    second = make_ir(300, seed=23, norm=0.3)
+
+    def parts(F):  # (boundaries inside the shortest thing that reaches the step, every knob of the step moved)
+        return IrParts(direct_end=F // 20, early_end=F // 3, xfade=(F // 50, F // 10), delay=(0, 8, -16), gain_db=(-3.0, -4.0, 2.0), width=(1.0, 0.3, 1.7),
+                       balance=0.25, swap=("early",), invert=("late",))
+
+    def five(F):
+        return dict(tail=IrTail(mode="extend", knee=(F // 2,), t60=(2000,), level_db=((-60.0, -50.0),), fade=min(40, F // 4), length=F + 300, seed=9),
+                    phase=IrPhase(), filter=IrFilter(ir=second), match=IrMatch(ir=second), parts=parts(F))
+
+    for F in PARTS_FRAMES:
+        ir = make_ir(F, seed=61 + F % 7, norm=0.05)
+        put(f"parts_{F}", lambda idx: c.prepare(idx, ir, parts=parts(F)))
+        put(f"all_five_{F}", lambda idx: c.prepare(idx, ir, **five(F)))
+        put(f"all_five_ir_at_44100_{F}", lambda idx: c.prepare(idx, ir, ir_rate=44100, **five(F)))
+    sweep, rec = Sweep(frames=4096, f1_hz=100.0, f2_hz=20000.0, rate=RATE), make_ir(5000, seed=41, norm=0.5)
+    F = 5000 - 4096 + 1
+    put("sweep_parts", lambda idx: c.prepare_sweep(idx, rec, sweep, parts=parts(F)))
+    put("sweep_all_five", lambda idx: c.prepare_sweep(idx, rec, sweep, **five(F)))
+
+    def stepped_then_plain(idx):
+        c.prepare(idx, make_ir(200, seed=61, norm=0.05), **five(200))
+        c.prepare(idx, make_ir(257, seed=62, norm=0.05))
+
+    put("all_five_then_plain", stepped_then_plain)
+    c.close()
+    return out
+
+
+def _compare(golden, got):
+    with open(golden) as fh:
         fixture = json.load(fh)
     want = fixture["sha256"]
     assert fixture["commit"]
-    got = digests()
     assert sorted(got) == sorted(want)
     differ = [k for k in sorted(want) if got[k] != want[k]]
     assert not differ, differ
 
 
+def test_the_bits_are_those_before_the_step_plan(gpu_lib):
+    _compare(GOLDEN, digests())
+
+
+def test_the_bits_with_the_parts_step_are_those_before_the_one_call_per_source(gpu_lib):
+    _compare(GOLDEN_PARTS, parts_digests())
+
+
 if __name__ == "__main__":
     import subprocess
 
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    sys.path.insert(0, os.environ.get("MCCONV_TREE") or os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     try:
         from cuda_audio_amd.build import hipcc as find_hipcc
 
         hipcc = next(l for l in subprocess.run([find_hipcc(), "--version"], capture_output=True, text=True).stdout.splitlines() if "HIP version" in l)
     except (OSError, RuntimeError, StopIteration):
         hipcc = "unknown"
+    record = parts_digests if "parts" in sys.argv[3:] else digests
     with open(sys.argv[1], "w") as fh:
-        json.dump(dict(commit=sys.argv[2], hipcc=hipcc.strip(), sha256=digests(verbose=True)), fh, indent=1, sort_keys=True)
+        json.dump(dict(commit=sys.argv[2], hipcc=hipcc.strip(), sha256=record(verbose=True)), fh, indent=1, sort_keys=True)
         fh.write("\n")
     print("recorded", sys.argv[1], "from", os.environ.get("MCCONV_LIB", "the tree's library"))
