@@ -333,7 +333,7 @@ struct mc_engine {
     unsigned* d_tailform = nullptr;  // 256-frame tails by the form partition 0 took {frequency domain, time domain}, counted by the kernel (mc_debug_read item 16)
     int tail_form = 0;               // MCCONV_TAIL_FORM=td|fd: one form for every 256-frame tail (0: the first look decides)
     uint64_t n_drop_carried = 0;  // JACK path, Q8 regime: periods whose cut terms came with the launch before theirs (mc_debug_read item 9, fourth word)
-    uint64_t n_mac_form[3] = {0, 0, 0};  // batches whose partition sums took the fused / split second-level transform / the resident MAC (mc_debug_read item 10)
+    uint64_t n_mac_form[3] = {0, 0, 0};  // batches whose partition sums took the fused / split second-level transform / the resident MAC (form_counter; mc_debug_read item 10)
     uint64_t n_drop_fft = 0, n_drop_ahead = 0, n_drop_tiles = 0;  // Q8 regime: batches by the form their cut terms took (mc_debug_read item 9)
 #ifdef MC_JACK_TRACE
     double tr_launch = 0, tr_flag = 0, tr_total = 0, tr_kernel = 0, tr_gap = 0, tr_out = 0, tr_clk = 0, tr_c[3] = {0, 0, 0};
@@ -557,36 +557,36 @@ bool hp_possible(const mc_engine* e, int lvl) {
     return !e->half && e->Pstride >= 128 && (e->Pstride >> lvl) >= 32;  // the fp16 MAC streams; small engines never use the fast form
 }
 // fast-FIR components of an IR's spectra (level lvl) for the resident MAC, built on first use
-int ensure_hp(mc_engine* e, const IrEntry* irc, int lvl) {
+int ensure_hp(mc_engine* e, hipStream_t st, const IrEntry* irc, int lvl) {
     IrEntry& ir = *const_cast<IrEntry*>(irc);
     if (ir.hp_valid[lvl - 1]) return MC_OK;
     const size_t n = (size_t)(lvl == 1 ? 3 : (lvl == 2 ? 9 : 27)) * MC_NB * (e->Pstride >> lvl);
     if (!ir.d_Hp[lvl - 1]) HIP_TRY(hipMalloc(&ir.d_Hp[lvl - 1], sizeof(float4) * n));
-    hipLaunchKernelGGL(k_polyphase, dim3(2048), dim3(256), 0, e->stream, ir.d_H, ir.d_Hp[lvl - 1], e->Pstride, lvl);
+    hipLaunchKernelGGL(k_polyphase, dim3(2048), dim3(256), 0, st, ir.d_H, ir.d_Hp[lvl - 1], e->Pstride, lvl);
     HIP_TRY(hipGetLastError());
     ir.hp_valid[lvl - 1] = true;
     return MC_OK;
 }
 
 // second-level spectra of an IR (transform of its partition sequence along the block axis), built on first use
-int ensure_fft2(mc_engine* e, const IrEntry* irc) {
+int ensure_fft2(mc_engine* e, hipStream_t st, const IrEntry* irc) {
     IrEntry& ir = *const_cast<IrEntry*>(irc);
     if (ir.h2_valid) return MC_OK;
     if (!ir.d_H2) HIP_TRY(hipMalloc(&ir.d_H2, sizeof(float2) * (size_t)2 * 257 * F2_N));
     // a partition shard transforms its own run of the partition sequence, H[pb .. pe)
     const int pb = std::min<int>((int)e->cfg.part_begin, ir.P), pe = e->cfg.part_end ? std::min<int>((int)e->cfg.part_end, ir.P) : ir.P;
-    hipLaunchKernelGGL(k_fft2_ir, dim3(257, 2), dim3(F2_THREADS), 0, e->stream, ir.d_H + pb, e->Pstride, std::min(std::max(pe - pb, 0), F2_N), ir.d_H2);
+    hipLaunchKernelGGL(k_fft2_ir, dim3(257, 2), dim3(F2_THREADS), 0, st, ir.d_H + pb, e->Pstride, std::min(std::max(pe - pb, 0), F2_N), ir.d_H2);
     HIP_TRY(hipGetLastError());
     ir.h2_valid = true;
     return MC_OK;
 }
 
-int ensure_g2(mc_engine* e, const IrEntry* irc) {
+int ensure_g2(mc_engine* e, hipStream_t st, const IrEntry* irc) {
     IrEntry& ir = *const_cast<IrEntry*>(irc);
     if (ir.g2_valid) return MC_OK;
     if (!ir.d_G2) HIP_TRY(hipMalloc(&ir.d_G2, sizeof(float2) * (size_t)2 * 257 * G2_N));
     const int pb = std::min<int>((int)e->cfg.part_begin, ir.P), pe = e->cfg.part_end ? std::min<int>((int)e->cfg.part_end, ir.P) : ir.P;
-    hipLaunchKernelGGL(k_g2_ir, dim3(257), dim3(G2_THREADS), 0, e->stream, ir.d_H + pb, e->Pstride, std::min(std::max(pe - pb, 0), G2_N), ir.d_G2);
+    hipLaunchKernelGGL(k_g2_ir, dim3(257), dim3(G2_THREADS), 0, st, ir.d_H + pb, e->Pstride, std::min(std::max(pe - pb, 0), G2_N), ir.d_G2);
     HIP_TRY(hipGetLastError());
     ir.g2_valid = true;
     return MC_OK;
@@ -989,10 +989,9 @@ void partition_range(const mc_engine* e, int p_hi, int* p_begin, int* p_end) {
     *p_end = pe;
 }
 
-void launch_mac_stream(mc_engine* e, const ActiveVoice& a, int p_lo, int p_hi, int T, int slot0, int nsum, int ch_off,
+void launch_mac_stream(mc_engine* e, hipStream_t st, const ActiveVoice& a, int p_lo, int p_hi, int T, int slot0, int nsum, int ch_off,
                        float4* dst = nullptr, unsigned long long* stamps = nullptr) {
     if (!dst) dst = e->d_part;
-    const hipStream_t st = e->stream;
     const int span = p_hi - p_lo;
     const int chunk = round_up(std::max(1, (span + kNchunk - 1) / kNchunk), 64);
     const dim3 grid(MC_NB, kNchunk, T);
@@ -1013,14 +1012,42 @@ void launch_mac_stream(mc_engine* e, const ActiveVoice& a, int p_lo, int p_hi, i
 #undef MC_LAUNCH_STREAM
 }
 
+// The forms a batch's partition sums take (choose_form and os_applies decide; DESIGN.md §2.5c has the table)
+enum class MacForm { Stream, Resident, FastFir, Split, Fused, OverlapSave };
+
+bool second_level(MacForm f) { return f == MacForm::Split || f == MacForm::Fused; }  // the forms that have no 256-block tiles
+
+// mc_kernel_stats.fast_levels of a form: the fast-FIR level 1..3, 0 for the direct forms, 255 / 254 / 253 for the split and the fused
+// second-level transform and the overlap-save passes.  Tests and bench.py read these codes.
+uint32_t form_code(MacForm f, int level) {
+    switch (f) {
+        case MacForm::FastFir: return (uint32_t)level;
+        case MacForm::Split: return 255u;
+        case MacForm::Fused: return 254u;
+        case MacForm::OverlapSave: return 253u;
+        default: return 0u;
+    }
+}
+
+// the form's counter in mc_engine::n_mac_form (mc_debug_read item 10), -1: none (the overlap-save passes count in n_os)
+int form_counter(MacForm f) {
+    switch (f) {
+        case MacForm::Fused: return 0;
+        case MacForm::Split: return 1;
+        case MacForm::FastFir:
+        case MacForm::Resident: return 2;
+        default: return -1;
+    }
+}
+
 // Where k_inv finds the partition sums of a batch
 struct MacOut {
+    MacForm form;
+    int lvl;  // fast-FIR levels of the main part (FastFir only)
     const float4* ysrc;
     int64_t sk, stt, sc;
     int nsum;
     int swept;
-    bool resident;
-    int lvl;            // fast-FIR levels of the main part (0 = direct form)
     int64_t ffa_plane;  // elements between the component sequences (k_inv combines them)
     int main_n;         // blocks described by the fields above; the remaining tail_n blocks of the batch come from
     int tail_n;         // the streaming kernel:
@@ -1028,6 +1055,23 @@ struct MacOut {
     int64_t tail_sk, tail_stt;
     int tail_nsum;
     bool corr_done;  // the Q1/Q2 prefix sums rode along with the launch (k_g2_mac) and are final when it ends
+
+    // n blocks as nsum planes Y[plane][bin][block], sk elements per bin and sc per plane (all forms but the streaming one)
+    static MacOut planes(MacForm form, const float4* y, int64_t sk, int nsum, int64_t sc, int n, int swept) {
+        MacOut mo = {};
+        mo.form = form, mo.ysrc = y, mo.sk = sk, mo.stt = 1, mo.nsum = nsum, mo.sc = sc, mo.main_n = n, mo.swept = swept;
+        return mo;
+    }
+    // n blocks as the streaming kernel leaves them: nsum chunk partials per (block, bin), side by side
+    static MacOut partials(const float4* y, int nsum, int n, int swept) {
+        MacOut mo = {};
+        mo.form = MacForm::Stream, mo.ysrc = y, mo.sk = nsum, mo.stt = (int64_t)MC_NB * nsum, mo.nsum = nsum, mo.sc = 1, mo.main_n = n, mo.swept = swept;
+        return mo;
+    }
+    // ... and the last n blocks of a fast-FIR batch, which come from the streaming kernel
+    void add_tail(const float4* y, int nsum, int n) {
+        main_n -= n, tail_n = n, tail_ysrc = y, tail_nsum = nsum, tail_sk = nsum, tail_stt = (int64_t)MC_NB * nsum;
+    }
 };
 
 // inverse transforms of the blocks whose partition sums `mo` describes, into the segment ring from block `b0` -
@@ -1039,28 +1083,21 @@ void launch_inv(mc_engine* e, const MacOut& mo, uint64_t b0, hipStream_t st, boo
         if (to_wet) {
             OutArgs oa;
             std::memset(&oa, 0, sizeof(oa));
-            const dim3 grid((n + IW_NEW - 1) / IW_NEW);
             if (out) {
                 oa = *out;
                 oa.blk0 = (int)((int64_t)b - out->tabs0);
-                hipLaunchKernelGGL(k_inv_wet<true>, grid, dim3(IW_THREADS), 0, st, y, sk, stt, nsum, sc, n, e->d_seg, e->sr, seg0, e->d_wet,
-                                   e->wr, (int64_t)b * MC_B, e->d_tw, oa);
-            } else
-                hipLaunchKernelGGL(k_inv_wet<false>, grid, dim3(IW_THREADS), 0, st, y, sk, stt, nsum, sc, n, e->d_seg, e->sr, seg0, e->d_wet,
-                                   e->wr, (int64_t)b * MC_B, e->d_tw, oa);
+            }
+            hipLaunchKernelGGL(out ? k_inv_wet<true> : k_inv_wet<false>, dim3((n + IW_NEW - 1) / IW_NEW), dim3(IW_THREADS), 0, st, y, sk, stt, nsum, sc, n,
+                               e->d_seg, e->sr, seg0, e->d_wet, e->wr, (int64_t)b * MC_B, e->d_tw, oa);
         } else
             hipLaunchKernelGGL(k_inv, dim3((n + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, st, y, sk, stt, nsum, sc, n, e->d_seg, e->sr,
                                seg0, e->d_tw);
     };
-    if (mo.main_n > 0 && mo.lvl > 0) {
+    if (mo.main_n > 0 && mo.form == MacForm::FastFir) {
         const int S = 1 << mo.lvl;
         const dim3 cgrid(((mo.main_n + S - 1) / S + 255) / 256, MC_NB);
-        if (mo.lvl == 1)
-            hipLaunchKernelGGL(k_ffa_combine<1>, cgrid, dim3(256), 0, st, mo.ysrc, mo.ffa_plane, (int)mo.sk, mo.main_n, e->d_Yc, e->Tcap);
-        else if (mo.lvl == 2)
-            hipLaunchKernelGGL(k_ffa_combine<2>, cgrid, dim3(256), 0, st, mo.ysrc, mo.ffa_plane, (int)mo.sk, mo.main_n, e->d_Yc, e->Tcap);
-        else
-            hipLaunchKernelGGL(k_ffa_combine<3>, cgrid, dim3(256), 0, st, mo.ysrc, mo.ffa_plane, (int)mo.sk, mo.main_n, e->d_Yc, e->Tcap);
+        hipLaunchKernelGGL(mo.lvl < 3 ? (mo.lvl == 1 ? k_ffa_combine<1> : k_ffa_combine<2>) : k_ffa_combine<3>, cgrid, dim3(256), 0, st, mo.ysrc,
+                           mo.ffa_plane, (int)mo.sk, mo.main_n, e->d_Yc, e->Tcap);
         inv(e->d_Yc, (int64_t)e->Tcap, (int64_t)1, 1, (int64_t)0, mo.main_n, b0);
     } else if (mo.main_n > 0) {
         inv(mo.ysrc, mo.sk, mo.stt, mo.nsum, mo.sc, mo.main_n, b0);
@@ -1081,249 +1118,226 @@ int block_axis_taps(const mc_engine* e, const ActiveVoice* act, int nact, int* p
     return taps;
 }
 
-// Will launch_mac_batch take the second-level transform for this batch?
-bool fft2_applies(const mc_engine* e, const ActiveVoice* act, int nact, bool per_slot_gains, int T) {
-    // both gain layouts are handled (uniform: 2 sequences per bin, fused form; per slot: 4 per voice, split form)
-    bool per_slot = per_slot_gains;
-    for (int a = 0; a < nact; a++) per_slot = per_slot || !act[a].uniform;
-    if (!(T >= e->stream_threshold && !e->half) || !e->fft2 || nact <= 0) return false;
-    const int taps = block_axis_taps(e, act, nact, nullptr);
-    if (taps > F2_N / 2) return false;
+// What choose_form decides
+struct FormChoice {
+    MacForm form;
+    int lvl;        // FastFir: the levels
+    int taps, pb0;  // the second-level forms: the taps of this engine's (shard of the) convolution and where its window starts (block_axis_taps)
+    bool per_slot;  // the window does not carry one set of gains: the caller said so, or some voice's gains moved inside it
+};
+
+// The form the partition sums of T blocks take, for launch_mac_batch and for run_front, which keeps a sliced window in one launch
+// where a second-level form takes it.  (Whether a whole batch goes through the overlap-save passes instead is os_applies' decision,
+// further down: it needs the call's pointers and the epoch's state.)
+FormChoice choose_form(const mc_engine* e, const ActiveVoice* act, int nact, bool per_slot_gains, int T) {
+    FormChoice c = {MacForm::Stream, 0, 0, 0, per_slot_gains};
+    for (int a = 0; a < nact; a++) c.per_slot = c.per_slot || !act[a].uniform;
+    if (!(T >= e->stream_threshold && !e->half)) return c;
+    c.form = MacForm::Resident;
+    if (nact <= 0) return c;
     const bool shard = e->cfg.part_begin || e->cfg.part_end;
-    if (!per_slot && e->fft2_fused && taps <= kG2Pmax)
-        // Uniform gains, fused form: a launch costs ~39 us per chunk of 8192 - taps + 1 blocks whatever the taps; the direct
-        // MAC ~10 us + 0.078 ns per block and partition (and never less than ~40 us for the longest IRs: one workgroup
-        // sweeps its partitions in turn).  Measured (P = 1728 / 345 / 32): the transform wins from 128 / ~900 / ~9000
-        // blocks on - a product of ~300 000 (MCCONV_FFT2_WORK)
-        return taps >= 16 && (int64_t)T * taps >= e->fft2_work;
-    // per-slot gains (or the fused form switched off): the split form, two launches and a stash
-    if (T < 768) return false;
-    if (shard) return taps >= 16 && (int64_t)T * taps >= 1300000;
-    return taps >= 256;
+    c.taps = block_axis_taps(e, act, nact, &c.pb0);
+    // both gain layouts are handled (uniform: 2 sequences per bin, fused form; per slot: 4 per voice, split form)
+    if (e->fft2 && c.taps <= F2_N / 2) {
+        if (!c.per_slot && e->fft2_fused && c.taps <= kG2Pmax) {
+            // Uniform gains, fused form: a launch costs ~39 us per chunk of 8192 - taps + 1 blocks whatever the taps; the direct
+            // MAC ~10 us + 0.078 ns per block and partition (and never less than ~40 us for the longest IRs: one workgroup
+            // sweeps its partitions in turn).  Measured (P = 1728 / 345 / 32): the transform wins from 128 / ~900 / ~9000
+            // blocks on - a product of ~300 000 (MCCONV_FFT2_WORK)
+            if (c.taps >= 16 && (int64_t)T * c.taps >= e->fft2_work) c.form = MacForm::Fused;
+        } else if (T >= 768 && (shard ? c.taps >= 16 && (int64_t)T * c.taps >= 1300000 : c.taps >= 256)) {
+            // per-slot gains (or the fused form switched off): the split form, two launches and a stash
+            c.form = MacForm::Split;
+        }
+        if (c.form != MacForm::Resident) return c;
+    }
+    if (e->ffa_levels > 0 && !shard && hp_possible(e, 1)) {
+        int pmin = 1 << 30;
+        for (int a = 0; a < nact; a++) pmin = std::min(pmin, act[a].p_end);
+        if (e->ffa_levels >= 3 && T >= 8192 && T % 8 == 0 && pmin >= 1024 && hp_possible(e, 3)) c.lvl = 3;
+        else if (e->ffa_levels >= 2 && T >= 4096 && T % 4 == 0 && pmin >= 512 && hp_possible(e, 2)) c.lvl = 2;
+        else if (T >= 2048 && T % 2 == 0 && pmin >= 256) c.lvl = 1;
+        if (c.lvl) c.form = MacForm::FastFir;
+    }
+    return c;
 }
 
-// Partition x bin MAC of T blocks starting at delay-line slot `slot0` for the given voices.
-// per_slot_gains: the batch's blocks (or the window) do not share one set of gains.
-// ride != null: the Q1/Q2 prefix sums may ride along with the launch (mo->corr_done says whether they did)
-int launch_mac_batch(mc_engine* e, const ActiveVoice* act, int nact, bool per_slot_gains, int T, int slot0, MacOut* mo,
-                     const CorrArgs* ride = nullptr) {
-    mo->corr_done = false;
-    mo->resident = T >= e->stream_threshold && !e->half;
-    mo->swept = 0;
-    mo->sc = 1;
-    mo->lvl = 0;
-    mo->ffa_plane = 0;
-    mo->main_n = T;
-    mo->tail_n = 0;
-    // Fast-FIR form of the convolution along the block axis.  With the polyphase components Xe[n] = X[2n],
-    // Xo[n] = X[2n+1], He[q] = H[2q], Ho[q] = H[2q+1] (indices relative to the batch start):
-    //   Y[2n] = (He*Xe)[n] + (Ho*Xo)[n-1],   Y[2n+1] = ((He+Ho)*(Xe+Xo))[n] - (He*Xe)[n] - (Ho*Xo)[n]
-    // - three convolutions with half the taps and half the outputs: 3/4 of the multiply-adds; applied to each of
-    // the three again (level 2): nine convolutions at a quarter of the rate, 9/16.  One launch of the resident
-    // kernel covers all components; k_inv combines them.  Every component is computed for sequence indices
-    // -1 .. T/2^L - 2, which covers the first T - 2^L blocks of the batch; the last 2^L blocks go through the
-    // streaming kernel, so that no tile is spent on one extra output.
-    // Long batches whose window carries one set of gains: the convolution along the block axis as a circular
-    // convolution per (bin, chunk of blocks) with a second-level transform of length F2_N (k_f2_fwd, k_f2_prod); the IRs'
-    // partition sequences are transformed once (k_fft2_ir).  O(log) instead of O(P) work per output block.
-    if (fft2_applies(e, act, nact, per_slot_gains, T)) {
-        int pb0 = 0;
-        const int pmax = block_axis_taps(e, act, nact, &pb0);  // taps of this engine's (shard of the) convolution
-        slot0 = (slot0 - pb0) & (e->ring - 1);                  // a shard's window starts pb slots earlier
-        {
-            Fft2Voices vv;
-            std::memset(&vv, 0, sizeof(vv));
-            for (int a = 0; a < nact; a++) {
-                int rc = ensure_fft2(e, act[a].ir0);
-                if (!rc) rc = ensure_fft2(e, act[a].ir1);
-                if (rc) return rc;
-                vv.h0[a] = act[a].ir0->d_H2;
-                vv.h1[a] = act[a].ir1->d_H2;
-                vv.g[a] = act[a].ugain;
-            }
-            vv.n = nact;
-            // one set of gains over the whole window: transform the two inputs and weight the products; otherwise
-            // transform gain(slot) x input for every voice and path
-            bool per_slot = per_slot_gains;
-            for (int a = 0; a < nact; a++) per_slot = per_slot || !act[a].uniform;
-            if (!per_slot && e->fft2_fused && pmax <= kG2Pmax) {
-                // fused form: both inputs' 8192-point spectra side by side in LDS, no stash (k_g2_mac)
-                for (int a = 0; a < nact; a++) {
-                    int rc = ensure_g2(e, act[a].ir0);
-                    if (!rc) rc = ensure_g2(e, act[a].ir1);
-                    if (rc) return rc;
-                    vv.h0[a] = act[a].ir0->d_G2;
-                    vv.h1[a] = act[a].ir1->d_G2;
-                }
-                const int chunk_t = G2_N - pmax + 1;
-                const int nch = (T + chunk_t - 1) / chunk_t;
-                CorrArgs ca;
-                std::memset(&ca, 0, sizeof(ca));
-                if (ride && ride->nchunks > 0) {
-                    ca = *ride;
-                    mo->corr_done = true;
-                }
-                // one workgroup per (bin, chunk) item - the dispatcher keeps two resident per CU and hands a CU its next one the
-                // moment a slot frees (measured against 512 persistent workgroups striding over 1280 items: 98 vs 108 us)
-                const int main_grid = MC_NB * nch;
-                hipLaunchKernelGGL(k_g2_mac, dim3(main_grid + ca.nchunks), dim3(G2B_THREADS), 0, e->stream, e->d_fdl, e->ring, slot0, T,
-                                   chunk_t, pmax, vv, e->d_Yc, e->Tcap, MC_NB * nch, ca, main_grid);
-                mo->ysrc = e->d_Yc;
-                mo->sk = e->Tcap;
-                mo->stt = 1;
-                mo->nsum = 1;
-                mo->sc = 0;
-                mo->swept = pmax;
-                mo->lvl = -2;  // second-level transform, fused form
-                e->n_mac_form[0]++;
-                return MC_OK;
-            }
-            const int nseq = per_slot ? 4 * nact : 2;
-            Fft2Gains gg;
-            std::memset(&gg, 0, sizeof(gg));
-            if (per_slot)
-                for (int a = 0; a < nact; a++) gg.row[a] = e->d_slotgain + (size_t)act[a].v * e->ring;
-            const int chunk_t = F2_N - pmax + 1;
-            const dim3 grid(MC_NB, (T + chunk_t - 1) / chunk_t);
-            const size_t need = (size_t)grid.y * nseq;
-            if (e->stash_chunks < need) {
-                HIP_TRY(hipStreamSynchronize(e->stream));
-                if (e->d_stash) (void)hipFree(e->d_stash);
-                e->d_stash = nullptr;
-                HIP_TRY(hipMalloc(&e->d_stash, sizeof(float2) * need * MC_NB * F2_N));
-                e->stash_chunks = need;
-            }
-            hipLaunchKernelGGL(k_f2_fwd, dim3(grid.x * grid.y * nseq), dim3(F2_THREADS), 0, e->stream, e->d_fdl, e->ring, slot0, T,
-                               chunk_t, pmax, e->d_stash, nseq, gg);
-            hipLaunchKernelGGL(k_f2_prod, dim3(grid.x * grid.y * 2), dim3(F2_THREADS), 0, e->stream, e->d_stash, T, chunk_t, pmax, vv,
-                               e->d_Yc, e->Tcap, nseq);
-            mo->ysrc = e->d_Yc;
-            mo->sk = e->Tcap;
-            mo->stt = 1;
-            mo->nsum = 1;
-            mo->sc = 0;
-            mo->swept = pmax;
-            mo->lvl = -1;  // marks the second-level transform in the kernel statistics
-            e->n_mac_form[1]++;
-            return MC_OK;
-        }
+// The voices' second-level spectra (transforms of their partition sequences along the block axis), built on the first batch that
+// takes the form: the split form's, or the fused form's
+int fft2_voices(mc_engine* e, hipStream_t st, const ActiveVoice* act, int nact, bool fused, Fft2Voices* vv) {
+    std::memset(vv, 0, sizeof(*vv));
+    for (int a = 0; a < nact; a++) {
+        int rc = ensure_fft2(e, st, act[a].ir0);
+        if (!rc) rc = ensure_fft2(e, st, act[a].ir1);
+        if (!rc && fused) rc = ensure_g2(e, st, act[a].ir0);
+        if (!rc && fused) rc = ensure_g2(e, st, act[a].ir1);
+        if (rc) return rc;
+        vv->h0[a] = fused ? act[a].ir0->d_G2 : act[a].ir0->d_H2;
+        vv->h1[a] = fused ? act[a].ir1->d_G2 : act[a].ir1->d_H2;
+        vv->g[a] = act[a].ugain;
     }
-    int lvl = 0;
-    if (mo->resident && e->ffa_levels > 0 && e->cfg.part_begin == 0 && e->cfg.part_end == 0 && nact > 0) {
-        int pmin = 1 << 30;
-        const bool have = hp_possible(e, 1);
-        for (int a = 0; a < nact; a++) pmin = std::min(pmin, act[a].p_end);
-        auto ready = [&](int l) { return hp_possible(e, l); };
-        if (have && e->ffa_levels >= 3 && T >= 8192 && T % 8 == 0 && pmin >= 1024 && ready(3)) lvl = 3;
-        else if (have && e->ffa_levels >= 2 && T >= 4096 && T % 4 == 0 && pmin >= 512 && ready(2)) lvl = 2;
-        else if (have && T >= 2048 && T % 2 == 0 && pmin >= 256) lvl = 1;
-    }
-    if (lvl) {
-        for (int a = 0; a < nact; a++) {  // the components of this level, built on the first batch that takes it
-            int rc = ensure_hp(e, act[a].ir0, lvl);
-            if (!rc) rc = ensure_hp(e, act[a].ir1, lvl);
-            if (rc) return rc;
-        }
-        const int S = 1 << lvl, ncomp = lvl == 1 ? 3 : (lvl == 2 ? 9 : 27);
-        const int nh = T / S, ph = e->Pstride >> lvl;
-        const int tiles = (nh + 255) / 256;
-        const int tcap = tiles * 256;
-        const size_t plane = (size_t)MC_NB * tcap;
-        int launched = 0;
-        for (int a = 0; a < nact; a++) {
-            const ActiveVoice& av = act[a];
-            const int q_end = round_up((av.p_end + S - 1) / S, 16);
-            const float4* sg = e->d_slotgain + (size_t)av.v * e->ring;
-            const dim3 grid(MC_NB * tiles * ncomp);
-            if (av.uniform && !per_slot_gains)
-                hipLaunchKernelGGL(k_mac_resident<false>, grid, dim3(256), 0, e->stream, av.ir0->d_Hp[lvl - 1], av.ir1->d_Hp[lvl - 1],
-                                   ph, 0, q_end, e->d_fdl, e->ring, slot0, nh, av.ugain, sg, e->d_Y, tcap, launched ? 1 : 0, 1, q_end,
-                                   lvl, tiles, (int64_t)plane);
-            else
-                hipLaunchKernelGGL(k_mac_resident<true>, grid, dim3(256), 0, e->stream, av.ir0->d_Hp[lvl - 1], av.ir1->d_Hp[lvl - 1],
-                                   ph, 0, q_end, e->d_fdl, e->ring, slot0, nh, av.ugain, sg, e->d_Y, tcap, launched ? 1 : 0, 1, q_end,
-                                   lvl, tiles, (int64_t)plane);
-            launched++;
-            mo->swept = std::max(mo->swept, av.p_end);
-        }
-        mo->ysrc = e->d_Y;
-        mo->sk = tcap;
-        mo->stt = 1;
-        mo->nsum = 1;
-        mo->sc = 0;
-        mo->lvl = lvl;
-        e->n_mac_form[2]++;
-        mo->ffa_plane = (int64_t)plane;
-        mo->main_n = T - S;
-        // the last S blocks: streaming kernel, one set of chunk partials per voice
-        mo->tail_n = S;
-        mo->tail_nsum = nact * kNchunk;
-        for (int a = 0; a < nact; a++) {
-            ActiveVoice av = act[a];
-            if (per_slot_gains) av.uniform = false;
-            launch_mac_stream(e, av, 0, av.p_end, S, (slot0 + T - S) & (e->ring - 1), mo->tail_nsum, a * kNchunk, e->d_tail);
-        }
-        mo->tail_ysrc = e->d_tail;
-        mo->tail_sk = mo->tail_nsum;
-        mo->tail_stt = (int64_t)MC_NB * mo->tail_nsum;
-        return MC_OK;
-    }
-    if (mo->resident) {
-        e->n_mac_form[2]++;
-        // short batches: split the partition range so that the launch has ~2048 workgroups
-        const int tiles = (T + 255) / 256;
-        const int psplit = std::max(1, std::min(8, 8 / tiles));
-        const int tcap = psplit > 1 ? tiles * 256 : e->Tcap;  // plane stride of Y (planes summed by k_inv)
-        int launched = 0;
-        for (int a = 0; a < nact; a++) {
-            const ActiveVoice& av = act[a];
-            int p_begin, p_end;
-            partition_range(e, av.p_end, &p_begin, &p_end);
-            if (p_end <= p_begin) continue;
-            const int pchunk = round_up((p_end - p_begin + psplit - 1) / psplit, 16);
-            const dim3 grid(MC_NB * tiles * psplit);
-            const float4* sg = e->d_slotgain + (size_t)av.v * e->ring;
-            if (av.uniform && !per_slot_gains)
-                hipLaunchKernelGGL(k_mac_resident<false>, grid, dim3(256), 0, e->stream, av.ir0->d_H, av.ir1->d_H, e->Pstride,
-                                   p_begin, p_end, e->d_fdl, e->ring, slot0, T, av.ugain, sg, e->d_Y, tcap, launched ? 1 : 0,
-                                   psplit, pchunk, 0, tiles, (int64_t)0);
-            else
-                hipLaunchKernelGGL(k_mac_resident<true>, grid, dim3(256), 0, e->stream, av.ir0->d_H, av.ir1->d_H, e->Pstride,
-                                   p_begin, p_end, e->d_fdl, e->ring, slot0, T, av.ugain, sg, e->d_Y, tcap, launched ? 1 : 0,
-                                   psplit, pchunk, 0, tiles, (int64_t)0);
-            launched++;
-            mo->swept = std::max(mo->swept, p_end - p_begin);
-        }
-        if (!launched) HIP_TRY(hipMemsetAsync(e->d_Y, 0, sizeof(float4) * (size_t)MC_NB * tcap * psplit, e->stream));
-        mo->ysrc = e->d_Y;
-        mo->sk = tcap;
-        mo->stt = 1;
-        mo->nsum = psplit;
-        mo->sc = (int64_t)MC_NB * tcap;
-    } else {
-        // streaming: one set of chunk partials per sounding voice, all added by k_inv
-        int nv = 0;
-        ActiveVoice list[MC_MAXV];
-        int pb[MC_MAXV], pe[MC_MAXV];
-        for (int a = 0; a < nact; a++) {
-            partition_range(e, act[a].p_end, &pb[nv], &pe[nv]);
-            if (pe[nv] <= pb[nv]) continue;
-            list[nv] = act[a];
-            if (per_slot_gains) list[nv].uniform = false;
-            nv++;
-        }
-        mo->nsum = std::max(1, nv) * kNchunk;
-        if (!nv) HIP_TRY(hipMemsetAsync(e->d_part, 0, sizeof(float4) * (size_t)T * MC_NB * mo->nsum, e->stream));
-        for (int a = 0; a < nv; a++) {
-            launch_mac_stream(e, list[a], pb[a], pe[a], T, slot0, mo->nsum, a * kNchunk);
-            mo->swept = std::max(mo->swept, pe[a] - pb[a]);
-        }
-        mo->ysrc = e->d_part;
-        mo->sk = mo->nsum;
-        mo->stt = (int64_t)MC_NB * mo->nsum;
-    }
+    vv->n = nact;
     return MC_OK;
 }
+
+// Long batches whose window carries one set of gains: the convolution along the block axis as a circular convolution per
+// (bin, chunk of blocks) with a second-level transform; the IRs' partition sequences are transformed once.  O(log) instead of
+// O(P) work per output block.  Fused form: both inputs' 8192-point spectra side by side in LDS, no stash (k_g2_mac).
+// ride != null: the Q1/Q2 prefix sums ride along with the launch (mo->corr_done)
+int mac_fused(mc_engine* e, hipStream_t st, const FormChoice& fc, const ActiveVoice* act, int nact, int T, int slot0, const CorrArgs* ride, MacOut* mo) {
+    Fft2Voices vv;
+    const int rc = fft2_voices(e, st, act, nact, true, &vv);
+    if (rc) return rc;
+    const int chunk_t = G2_N - fc.taps + 1;
+    const int nch = (T + chunk_t - 1) / chunk_t;
+    const bool rides = ride && ride->nchunks > 0;
+    CorrArgs ca;
+    std::memset(&ca, 0, sizeof(ca));
+    if (rides) ca = *ride;
+    // one workgroup per (bin, chunk) item - the dispatcher keeps two resident per CU and hands a CU its next one the
+    // moment a slot frees (measured against 512 persistent workgroups striding over 1280 items: 98 vs 108 us)
+    const int main_grid = MC_NB * nch;
+    hipLaunchKernelGGL(k_g2_mac, dim3(main_grid + ca.nchunks), dim3(G2B_THREADS), 0, st, e->d_fdl, e->ring, slot0, T, chunk_t, fc.taps, vv,
+                       e->d_Yc, e->Tcap, MC_NB * nch, ca, main_grid);
+    *mo = MacOut::planes(MacForm::Fused, e->d_Yc, e->Tcap, 1, 0, T, fc.taps);
+    mo->corr_done = rides;
+    return MC_OK;
+}
+
+// Split form of the second-level transform (length F2_N; k_f2_fwd, a stash, k_f2_prod).  One set of gains over the whole window:
+// transform the two inputs and weight the products; otherwise transform gain(slot) x input for every voice and path
+int mac_split(mc_engine* e, hipStream_t st, const FormChoice& fc, const ActiveVoice* act, int nact, int T, int slot0, MacOut* mo) {
+    Fft2Voices vv;
+    const int rc = fft2_voices(e, st, act, nact, false, &vv);
+    if (rc) return rc;
+    const int nseq = fc.per_slot ? 4 * nact : 2;
+    Fft2Gains gg;
+    std::memset(&gg, 0, sizeof(gg));
+    if (fc.per_slot)
+        for (int a = 0; a < nact; a++) gg.row[a] = e->d_slotgain + (size_t)act[a].v * e->ring;
+    const int chunk_t = F2_N - fc.taps + 1;
+    const dim3 grid(MC_NB, (T + chunk_t - 1) / chunk_t);
+    const size_t need = (size_t)grid.y * nseq;
+    if (e->stash_chunks < need) {
+        HIP_TRY(hipStreamSynchronize(st));
+        if (e->d_stash) (void)hipFree(e->d_stash);
+        e->d_stash = nullptr;
+        HIP_TRY(hipMalloc(&e->d_stash, sizeof(float2) * need * MC_NB * F2_N));
+        e->stash_chunks = need;
+    }
+    hipLaunchKernelGGL(k_f2_fwd, dim3(grid.x * grid.y * nseq), dim3(F2_THREADS), 0, st, e->d_fdl, e->ring, slot0, T, chunk_t, fc.taps, e->d_stash,
+                       nseq, gg);
+    hipLaunchKernelGGL(k_f2_prod, dim3(grid.x * grid.y * 2), dim3(F2_THREADS), 0, st, e->d_stash, T, chunk_t, fc.taps, vv, e->d_Yc, e->Tcap, nseq);
+    *mo = MacOut::planes(MacForm::Split, e->d_Yc, e->Tcap, 1, 0, T, fc.taps);
+    return MC_OK;
+}
+
+// Fast-FIR form of the convolution along the block axis.  With the polyphase components Xe[n] = X[2n],
+// Xo[n] = X[2n+1], He[q] = H[2q], Ho[q] = H[2q+1] (indices relative to the batch start):
+//   Y[2n] = (He*Xe)[n] + (Ho*Xo)[n-1],   Y[2n+1] = ((He+Ho)*(Xe+Xo))[n] - (He*Xe)[n] - (Ho*Xo)[n]
+// - three convolutions with half the taps and half the outputs: 3/4 of the multiply-adds; applied to each of
+// the three again (level 2): nine convolutions at a quarter of the rate, 9/16.  One launch of the resident
+// kernel covers all components; k_inv combines them.  Every component is computed for sequence indices
+// -1 .. T/2^L - 2, which covers the first T - 2^L blocks of the batch; the last 2^L blocks go through the
+// streaming kernel, so that no tile is spent on one extra output.
+int mac_fast_fir(mc_engine* e, hipStream_t st, int lvl, const ActiveVoice* act, int nact, bool per_slot_gains, int T, int slot0, MacOut* mo) {
+    for (int a = 0; a < nact; a++) {  // the components of this level, built on the first batch that takes it
+        int rc = ensure_hp(e, st, act[a].ir0, lvl);
+        if (!rc) rc = ensure_hp(e, st, act[a].ir1, lvl);
+        if (rc) return rc;
+    }
+    const int S = 1 << lvl, ncomp = lvl == 1 ? 3 : (lvl == 2 ? 9 : 27);
+    const int nh = T / S, ph = e->Pstride >> lvl;
+    const int tiles = (nh + 255) / 256;
+    const int tcap = tiles * 256;
+    const size_t plane = (size_t)MC_NB * tcap;
+    const int tail_nsum = nact * kNchunk;  // the last S blocks: streaming kernel, one set of chunk partials per voice
+    int swept = 0;
+    for (int a = 0; a < nact; a++) {
+        const ActiveVoice& av = act[a];
+        const int q_end = round_up((av.p_end + S - 1) / S, 16);
+        hipLaunchKernelGGL(av.uniform && !per_slot_gains ? k_mac_resident<false> : k_mac_resident<true>, dim3(MC_NB * tiles * ncomp), dim3(256), 0, st,
+                           av.ir0->d_Hp[lvl - 1], av.ir1->d_Hp[lvl - 1], ph, 0, q_end, e->d_fdl, e->ring, slot0, nh, av.ugain,
+                           e->d_slotgain + (size_t)av.v * e->ring, e->d_Y, tcap, a ? 1 : 0, 1, q_end, lvl, tiles, (int64_t)plane);
+        swept = std::max(swept, av.p_end);
+    }
+    for (int a = 0; a < nact; a++) {
+        ActiveVoice av = act[a];
+        if (per_slot_gains) av.uniform = false;
+        launch_mac_stream(e, st, av, 0, av.p_end, S, (slot0 + T - S) & (e->ring - 1), tail_nsum, a * kNchunk, e->d_tail);
+    }
+    *mo = MacOut::planes(MacForm::FastFir, e->d_Y, tcap, 1, 0, T, swept);
+    mo->lvl = lvl;
+    mo->ffa_plane = (int64_t)plane;
+    mo->add_tail(e->d_tail, tail_nsum, S);
+    return MC_OK;
+}
+
+// Resident MAC, direct form, over this engine's (shard of the) partitions
+int mac_resident(mc_engine* e, hipStream_t st, const ActiveVoice* act, int nact, bool per_slot_gains, int T, int slot0, MacOut* mo) {
+    // short batches: split the partition range so that the launch has ~2048 workgroups
+    const int tiles = (T + 255) / 256;
+    const int psplit = std::max(1, std::min(8, 8 / tiles));
+    const int tcap = psplit > 1 ? tiles * 256 : e->Tcap;  // plane stride of Y (planes summed by k_inv)
+    int launched = 0, swept = 0;
+    for (int a = 0; a < nact; a++) {
+        const ActiveVoice& av = act[a];
+        int p_begin, p_end;
+        partition_range(e, av.p_end, &p_begin, &p_end);
+        if (p_end <= p_begin) continue;
+        const int pchunk = round_up((p_end - p_begin + psplit - 1) / psplit, 16);
+        hipLaunchKernelGGL(av.uniform && !per_slot_gains ? k_mac_resident<false> : k_mac_resident<true>, dim3(MC_NB * tiles * psplit), dim3(256), 0, st,
+                           av.ir0->d_H, av.ir1->d_H, e->Pstride, p_begin, p_end, e->d_fdl, e->ring, slot0, T, av.ugain,
+                           e->d_slotgain + (size_t)av.v * e->ring, e->d_Y, tcap, launched ? 1 : 0, psplit, pchunk, 0, tiles, (int64_t)0);
+        launched++;
+        swept = std::max(swept, p_end - p_begin);
+    }
+    if (!launched) HIP_TRY(hipMemsetAsync(e->d_Y, 0, sizeof(float4) * (size_t)MC_NB * tcap * psplit, st));
+    *mo = MacOut::planes(MacForm::Resident, e->d_Y, tcap, psplit, (int64_t)MC_NB * tcap, T, swept);
+    return MC_OK;
+}
+
+// streaming MAC: one set of chunk partials per sounding voice, all added by k_inv
+int mac_stream(mc_engine* e, hipStream_t st, const ActiveVoice* act, int nact, bool per_slot_gains, int T, int slot0, MacOut* mo) {
+    int nv = 0, swept = 0;
+    ActiveVoice list[MC_MAXV];
+    int pb[MC_MAXV], pe[MC_MAXV];
+    for (int a = 0; a < nact; a++) {
+        partition_range(e, act[a].p_end, &pb[nv], &pe[nv]);
+        if (pe[nv] <= pb[nv]) continue;
+        list[nv] = act[a];
+        if (per_slot_gains) list[nv].uniform = false;
+        nv++;
+    }
+    const int nsum = std::max(1, nv) * kNchunk;
+    if (!nv) HIP_TRY(hipMemsetAsync(e->d_part, 0, sizeof(float4) * (size_t)T * MC_NB * nsum, st));
+    for (int a = 0; a < nv; a++) {
+        launch_mac_stream(e, st, list[a], pb[a], pe[a], T, slot0, nsum, a * kNchunk);
+        swept = std::max(swept, pe[a] - pb[a]);
+    }
+    *mo = MacOut::partials(e->d_part, nsum, T, swept);
+    return MC_OK;
+}
+
+// Partition x bin MAC of T blocks starting at delay-line slot `slot0` for the given voices, on stream `st`.
+// per_slot_gains: the batch's blocks (or the window) do not share one set of gains.
+// ride != null: the Q1/Q2 prefix sums may ride along with the launch (mo->corr_done says whether they did)
+int launch_mac_batch(mc_engine* e, hipStream_t st, const ActiveVoice* act, int nact, bool per_slot_gains, int T, int slot0, MacOut* mo,
+                     const CorrArgs* ride = nullptr) {
+    const FormChoice fc = choose_form(e, act, nact, per_slot_gains, T);
+    const int slot2 = (slot0 - fc.pb0) & (e->ring - 1);  // the second-level forms: a shard's window starts pb slots earlier
+    int rc;
+    switch (fc.form) {
+        case MacForm::Fused: rc = mac_fused(e, st, fc, act, nact, T, slot2, ride, mo); break;
+        case MacForm::Split: rc = mac_split(e, st, fc, act, nact, T, slot2, mo); break;
+        case MacForm::FastFir: rc = mac_fast_fir(e, st, fc.lvl, act, nact, per_slot_gains, T, slot0, mo); break;
+        case MacForm::Resident: rc = mac_resident(e, st, act, nact, per_slot_gains, T, slot0, mo); break;
+        default: rc = mac_stream(e, st, act, nact, per_slot_gains, T, slot0, mo); break;
+    }
+    if (!rc && form_counter(fc.form) >= 0) e->n_mac_form[form_counter(fc.form)]++;
+    return rc;
+}
+
 
 Retired make_retired(const mc_engine* e) {
     Retired r;
@@ -1346,6 +1360,17 @@ int zero_ring_range(mc_engine* e, float* ring, uint64_t from, uint64_t to) {
         if (n > n1) HIP_TRY(hipMemsetAsync(ring + (size_t)c * rr, 0, sizeof(float) * (n - n1), e->stream));
     }
     return MC_OK;
+}
+
+// K1 over blocks [t_base, t_end) of a batch of T blocks that starts at delay-line slot `slot0` (k_fwd has the parameters' meaning).
+// in1 == null: silent blocks into the delay line and nothing else (the inputs are never read); da != null: k_fwd<true>, DropAhead
+void launch_fwd(mc_engine* e, hipStream_t st, const float* in1, const float* in2, int T, int slot0, const BlockParams* ptab, int pstride, float4* sums,
+                int need_a0, int need_a1, int need_b0, int hist_from, int t_base, int t_end, const DropAhead* da = nullptr, int store_from = 0) {
+    const bool live = in1 != nullptr;
+    hipLaunchKernelGGL(!da ? k_fwd<false> : k_fwd<true>, dim3((t_end - t_base + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, st, in1, in2, 1,
+                       live ? (int64_t)T * MC_B : (int64_t)0, T, e->d_fdl, e->ring, slot0, ptab, pstride, sums, live ? e->d_slotgain : (float4*)nullptr, e->d_tw,
+                       e->d_fdl16, live ? e->d_xhist : (float*)nullptr, live ? e->xr : 0, live ? e->d_gring : (float4*)nullptr, live ? e->rc : 0,
+                       live ? (int64_t)e->t_front : (int64_t)0, need_a0, need_a1, need_b0, hist_from, t_base, da ? *da : DropAhead(), store_from);
 }
 
 // The predelay of the next call differs from the live epoch's.  The reference shifts every call's contribution
@@ -1388,13 +1413,9 @@ int retire_epoch(mc_engine* e, uint64_t new_delay, bool force = false) {
         int Tc = std::min(F, e->Tcap);
         if (!(Tc >= e->stream_threshold && !e->half)) Tc = std::min(Tc, e->Tstream);
         const int slot0 = (int)(tv & (uint64_t)(e->ring - 1));
-        // silent blocks into the delay line (n_frames = 0: the inputs are never read)
-        hipLaunchKernelGGL(k_fwd<false>, dim3((Tc + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, e->stream, (const float*)nullptr,
-                           (const float*)nullptr, 1, (int64_t)0, Tc, e->d_fdl, e->ring, slot0, (const BlockParams*)nullptr, 0,
-                           (float4*)nullptr, (float4*)nullptr, e->d_tw, e->d_fdl16, (float*)nullptr, 0, (float4*)nullptr, 0,
-                           (int64_t)0, 0, Tc, Tc, 0, 0, DropAhead(), 0);
+        launch_fwd(e, e->stream, nullptr, nullptr, Tc, slot0, nullptr, 0, nullptr, 0, Tc, Tc, 0, 0, Tc);  // silent blocks into the delay line
         MacOut mo;
-        rc = launch_mac_batch(e, act, nact, true, Tc, slot0, &mo);
+        rc = launch_mac_batch(e, e->stream, act, nact, true, Tc, slot0, &mo);
         if (rc) return rc;
         launch_inv(e, mo, tv, e->stream);
         hipLaunchKernelGGL(k_flush_ola, dim3(Tc), dim3(256), 0, e->stream, e->d_seg, e->sr, (int64_t)tv, (int64_t)d_old,
@@ -1433,6 +1454,66 @@ void corr_chunks(CorrArgs* ca, int T, int need_a0, int need_a1, int need_b0) {
     ca->run1 = std::max(std::min(need_b0, T - 1) & ~(CORR_CHUNK - 1), end0);
     const int nrun1 = T > ca->run1 ? (T - ca->run1 + CORR_CHUNK - 1) / CORR_CHUNK : 0;
     ca->nchunks = ca->nrun0 + nrun1;
+}
+
+// Arguments of the Q1/Q2 prefix sums of the batch `ctx` describes: its block sums and its parameter table lie in its slot
+CorrArgs corr_args(const mc_engine* e, const BatchCtx& ctx) {
+    CorrArgs ca;
+    std::memset(&ca, 0, sizeof(ca));
+    ca.sums = e->d_sums + (size_t)ctx.slot * e->Tmax;
+    ca.ptab = e->d_ptab + (size_t)ctx.slot * e->Tmax;
+    ca.pstride = ctx.pstride;
+    ca.T = ctx.T;
+    ca.vs = ctx.vs;
+    ca.inv_n = 1.0 / (double)e->cfg.n_ref;
+    ca.compat = (int)e->cfg.compat;
+    ca.cring = e->d_cring;
+    ca.rc = e->rc;
+    ca.tabs0 = (int64_t)ctx.t0;
+    ca.ctot = e->d_ctot;
+    corr_chunks(&ca, ctx.T, ctx.need_a0, ctx.need_a1, ctx.need_b0);
+    return ca;
+}
+
+// ... as launches of their own (a single chunk adds its base itself)
+void launch_corr(hipStream_t st, const CorrArgs& ca) {
+    hipLaunchKernelGGL(k_corr_terms, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, st, ca);
+    if (ca.nchunks > 1) hipLaunchKernelGGL(k_corr_fix, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, st, ca);
+}
+
+// What the launches that finish output themselves (k_inv_wet<true>, k_os_out) need of the batch `ctx` describes: the slice
+// ctx.first / ctx.count of a block-sliced engine, or the whole batch from the first block the predelay does not fill from the
+// previous call (out_from = wet_head).  lin and drop are the caller's.
+OutArgs out_args(const mc_engine* e, const BatchCtx& ctx, bool slice, const float* d_in1, const float* d_in2, float* d_outL, float* d_outR) {
+    OutArgs oa;
+    std::memset(&oa, 0, sizeof(oa));
+    oa.in1 = d_in1;
+    oa.in2 = d_in2;
+    oa.outL = d_outL;
+    oa.outR = d_outR;
+    oa.ptab = e->d_ptab + (size_t)ctx.slot * e->Tmax;
+    oa.pstride = ctx.pstride;
+    oa.cring = e->d_cring;
+    oa.rc = e->rc;
+    oa.tabs0 = (int64_t)ctx.t0;
+    oa.predelay = (int64_t)ctx.predelay;
+    oa.n_ref = (int64_t)e->cfg.n_ref;
+    oa.b0 = make_retired(e).b0;
+    oa.compat = (int)e->cfg.compat;
+    oa.pm = e->pm;
+    if (slice) {  // the slice [first, first + count), nothing else; a sliced engine keeps no wet history
+        oa.out_from = ctx.first;
+        oa.out_end = ctx.first + ctx.count;
+        oa.out_blk0 = ctx.first;
+        oa.wet_head = 0;
+        oa.wet_from = 1 << 30;
+    } else {
+        oa.out_from = oa.wet_head = (int)std::min<uint64_t>((uint64_t)ctx.T, (ctx.predelay + MC_B - 1) / MC_B);
+        oa.out_end = ctx.T;
+        oa.out_blk0 = 0;
+        oa.wet_from = std::max(0, ctx.T - (MC_MAX_PREDELAY / MC_B + 8));  // what later calls and a predelay change can reach
+    }
+    return oa;
 }
 
 // ---------------------------------------------------------------------------
@@ -1579,22 +1660,16 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
         HIP_TRY(hipStreamWaitEvent(side, e->os_ev[0], 0));
     }
     const int hist_from = (int)std::max<int64_t>(0, (int64_t)T - (int64_t)((e->cfg.n_ref + MC_MAX_PREDELAY) / MC_B + 4));
-    DropAhead da;
-    std::memset(&da, 0, sizeof(da));
     // the batch's tail: what any later window, Q8 pass or re-render of a predelay epoch can reach
     const int from = std::max(0, T - std::max(round_up(e->Pcap, 16) + 64, (int)((e->cfg.n_ref + MC_MAX_PREDELAY) / MC_B) + 8)) & ~(FWD_TILE - 1);
     auto state_tail = [&]() {  // delay line, slot gains and histories of the tail, no cut terms
-        hipLaunchKernelGGL(k_fwd<false>, dim3((T - from + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, side, d_in1, d_in2, 1, (int64_t)T * MC_B, T,
-                           e->d_fdl, e->ring, slot0, d_ptab, 0, (float4*)nullptr, e->d_slotgain, e->d_tw, e->d_fdl16, e->d_xhist, e->xr, e->d_gring,
-                           e->rc, (int64_t)e->t_front, 0, 0, from, hist_from, from, da, 0);
+        launch_fwd(e, side, d_in1, d_in2, T, slot0, d_ptab, 0, nullptr, 0, 0, from, hist_from, from, T);
     };
     auto last_segment = [&]() {  // the last block's segment from the delay line
         MacOut mo;
         const uint64_t b = e->t_front + (uint64_t)T - 1;
-        e->stream = side;  // (the MAC and inverse-transform launchers use the engine's stream)
-        const int rc_m = launch_mac_batch(e, st.act, st.nact, false, 1, (int)(b & (uint64_t)(e->ring - 1)), &mo);
+        const int rc_m = launch_mac_batch(e, side, st.act, st.nact, false, 1, (int)(b & (uint64_t)(e->ring - 1)), &mo);
         if (!rc_m) launch_inv(e, mo, b, side);
-        e->stream = main;
         return rc_m;
     };
     if (!slice) {
@@ -1605,9 +1680,7 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
             // Q8 regime at the shipped shape: the forward transforms of ALL blocks sum the cut terms of output block t + shift while
             // X_t is in registers (k_fwd<true>, DropAhead) - delay-line slots still only for the tail; the first `shift` output
             // blocks, whose source lies before the batch, through k_drop_fft from the slots the previous call left
-            hipLaunchKernelGGL(k_fwd<true>, dim3((T + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, side, d_in1, d_in2, 1, (int64_t)T * MC_B, T,
-                               e->d_fdl, e->ring, slot0, d_ptab, 0, (float4*)nullptr, e->d_slotgain, e->d_tw, e->d_fdl16, e->d_xhist, e->xr, e->d_gring,
-                               e->rc, (int64_t)e->t_front, 0, T, T, hist_from, 0, *q8_da, from);
+            launch_fwd(e, side, d_in1, d_in2, T, slot0, d_ptab, 0, nullptr, 0, T, T, hist_from, 0, T, q8_da, from);
             const TailDrop tdq = make_taildrop(e, st.ctx.vir, st.ctx.predelay);
             const int nd = std::min(T, q8_shift);
             hipLaunchKernelGGL(k_drop_fft, dim3((nd + DF_WAVES - 1) / DF_WAVES), dim3(64 * DF_WAVES), 0, side, tdq, e->d_dropbuf, (int64_t)st.ctx.t0, 0, nd,
@@ -1622,43 +1695,10 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
         }
     } else if (stored.need_b0 < T) {
         // block-sliced: the tail of the batch that the next call's windows reach back to (delay line, histories, block sums), as k_fwd leaves it
-        const int from = stored.need_b0 & ~(FWD_TILE - 1);
-        hipLaunchKernelGGL(k_fwd<false>, dim3((T - from + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, side, d_in1, d_in2, 1, (int64_t)T * MC_B, T,
-                           e->d_fdl, e->ring, slot0, d_ptab, 0, st.d_sums, e->d_slotgain, e->d_tw, e->d_fdl16, e->d_xhist, e->xr, e->d_gring,
-                           e->rc, (int64_t)e->t_front, 0, 0, stored.need_b0, hist_from, from, da, 0);
+        launch_fwd(e, side, d_in1, d_in2, T, slot0, d_ptab, 0, st.d_sums, 0, 0, stored.need_b0, hist_from, stored.need_b0 & ~(FWD_TILE - 1), T);
     }
-    const int head = slice ? 0 : (int)std::min<uint64_t>((uint64_t)T, (st.ctx.predelay + MC_B - 1) / MC_B);
-    OutArgs oa;
-    std::memset(&oa, 0, sizeof(oa));
-    oa.in1 = d_in1;
-    oa.in2 = d_in2;
-    oa.outL = d_outL;
-    oa.outR = d_outR;
-    oa.ptab = d_ptab;
-    oa.pstride = 0;
-    oa.cring = e->d_cring;
-    oa.rc = e->rc;
-    oa.tabs0 = (int64_t)st.ctx.t0;
-    oa.predelay = (int64_t)st.ctx.predelay;
-    oa.n_ref = (int64_t)e->cfg.n_ref;
-    oa.b0 = make_retired(e).b0;
-    oa.compat = (int)e->cfg.compat;
-    oa.pm = e->pm;
-    oa.blk0 = 0;
+    OutArgs oa = out_args(e, st.ctx, slice, d_in1, d_in2, d_outL, d_outR);
     oa.drop = (!slice && q8_shift >= 0) ? e->d_dropbuf : nullptr;
-    if (slice) {  // the slice [first, first + count), nothing else; a sliced engine keeps no wet history
-        oa.out_from = first;
-        oa.out_end = first + count;
-        oa.out_blk0 = first;
-        oa.wet_head = 0;
-        oa.wet_from = 1 << 30;
-    } else {
-        oa.out_from = head;
-        oa.out_end = T;
-        oa.out_blk0 = 0;
-        oa.wet_head = head;
-        oa.wet_from = std::max(0, T - (MC_MAX_PREDELAY / MC_B + 8));
-    }
     OsGeo G;
     G.hop = hop;
     G.ovl = ovl;
@@ -1679,27 +1719,13 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
         HIP_TRY(hipStreamWaitEvent(side, cols_done, 0));
     }
     {  // Q1/Q2 prefix sums of the batch from the column pass's partial sums, ahead of the output pass
-        CorrArgs ca;
-        std::memset(&ca, 0, sizeof(ca));
-        ca.sums = st.d_sums;
+        CorrArgs ca = corr_args(e, st.ctx);
         ca.parts = e->d_os_part;
         ca.parts_hop = hop_blocks;
         ca.parts_ovl = ovl_blocks;
         ca.parts_t0 = w0;
         ca.parts_end = w0 + wn;
-        ca.ptab = d_ptab;
-        ca.pstride = 0;
-        ca.T = T;
-        ca.vs = st.ctx.vs;
-        ca.inv_n = 1.0 / (double)e->cfg.n_ref;
-        ca.compat = (int)e->cfg.compat;
-        ca.cring = e->d_cring;
-        ca.rc = e->rc;
-        ca.tabs0 = (int64_t)st.ctx.t0;
-        ca.ctot = e->d_ctot;
-        corr_chunks(&ca, T, stored.need_a0, stored.need_a1, stored.need_b0);
-        hipLaunchKernelGGL(k_corr_terms, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, side, ca);
-        if (ca.nchunks > 1) hipLaunchKernelGGL(k_corr_fix, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, side, ca);
+        launch_corr(side, ca);
     }
     if (after && e->cfg.compat && e->pm == 1 && !((st.ctx.predelay | e->cfg.n_ref) & (MC_B - 1))) {
         // all frames of a block share their window: its sums once per block instead of per lane of the output pass
@@ -1723,13 +1749,13 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
         e->kev_n++;
         e->ks.resident = 1;
         e->ks.partitions = (uint32_t)ovl_blocks;
-        e->ks.fast_levels = 253u;
+        e->ks.fast_levels = form_code(MacForm::OverlapSave, 0);
     }
     if (side != main) HIP_TRY(hipStreamWaitEvent(main, e->os_ev[2], 0));  // (the prefix ring and the window sums; where the side stream started with the call, everything it did: the cut terms, and what later calls need)
     hipLaunchKernelGGL(k_os_out, dim3(nseg * OS_TPS), dim3(OS_THREADS), 0, main, (const float4*)e->d_os_T, G, e->d_wet, e->wr, e->d_tw, oa);
     if (after) HIP_TRY(hipStreamWaitEvent(main, e->os_ev[0], 0));  // (later calls need the rest of what the side stream did)
     HIP_TRY(hipGetLastError());
-    stored.out_from = head;
+    stored.out_from = oa.wet_head;
     stored.corr_done = true;
     e->n_os[0]++;
     return MC_OK;
@@ -1870,10 +1896,8 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
         }
         for (int r = 0; r < 2; r++)
             if (hi[r] > lo[r])
-                hipLaunchKernelGGL(da_shift >= 0 ? k_fwd<true> : k_fwd<false>, dim3((hi[r] - lo[r] + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, e->stream, d_in1, d_in2, 1,
-                                   (int64_t)T * MC_B, T, e->d_fdl, e->ring, slot0, d_ptab, pstride, d_sums, e->d_slotgain, e->d_tw,
-                                   e->d_fdl16, e->d_xhist, e->xr, e->d_gring, e->rc, (int64_t)e->t_front, need_a0, need_a1, need_b0,
-                                   hist_from, lo[r], da, 0);
+                launch_fwd(e, e->stream, d_in1, d_in2, T, slot0, d_ptab, pstride, d_sums, need_a0, need_a1, need_b0, hist_from, lo[r], hi[r],
+                           da_shift >= 0 ? &da : nullptr);
     }
     if (e->ktiming && e->kev_n == kEvPool) {
         int rc = drain_kernel_events(e);
@@ -1889,7 +1913,7 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
         // K2 + K3.  The reach-back blocks run as their own short launch (for <= 33 blocks the streaming kernel), so
         // that the slice itself fills whole 256-block tiles of the resident kernel - unless the second-level
         // transform takes the batch, which has no tiles: then the window is one launch.
-        const bool whole = halo > 0 && fft2_applies(e, st.act, st.nact, per_slot, halo + count);
+        const bool whole = halo > 0 && second_level(choose_form(e, st.act, st.nact, per_slot, halo + count).form);
         const int parts[2][2] = {{0, whole ? 0 : halo}, {whole ? 0 : halo, whole ? halo + count : count}};
         for (int h = 0; h < 2; h++) {
             const int off = parts[h][0], n = parts[h][1];
@@ -1903,29 +1927,10 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
             MacOut mo;
             // the Q1/Q2 prefix sums of the batch ride along with this launch and the inverse transforms' (fused form only;
             // they read nothing but the block sums k_fwd left and are needed first by k_post)
-            CorrArgs ca;
-            std::memset(&ca, 0, sizeof(ca));
+            CorrArgs ca = corr_args(e, st.ctx);
             // (every riding workgroup looks at the totals of all chunks before it: beyond 160 chunks the two launches of
             // run_back are cheaper than that quadratic chain.  A block-sliced rank has few: only the runs it transforms)
-            bool may_ride = h == 1 && !lin && !piped && to_wet && T > CORR_CHUNK;
-            auto corr_args = [&]() {
-                ca.sums = d_sums;
-                ca.ptab = d_ptab;
-                ca.pstride = pstride;
-                ca.T = T;
-                ca.vs = st.ctx.vs;
-                ca.inv_n = 1.0 / (double)e->cfg.n_ref;
-                ca.compat = (int)e->cfg.compat;
-                ca.cring = e->d_cring;
-                ca.rc = e->rc;
-                ca.tabs0 = (int64_t)st.ctx.t0;
-                ca.ctot = e->d_ctot;
-                corr_chunks(&ca, T, need_a0, need_a1, need_b0);
-            };
-            if (may_ride) {
-                corr_args();
-                may_ride = ca.nchunks > 1 && ca.nchunks <= 160;
-            }
+            const bool may_ride = h == 1 && !lin && !piped && to_wet && T > CORR_CHUNK && ca.nchunks > 1 && ca.nchunks <= 160;
             if (may_ride) {
                 ca.chain = 1;
                 ca.ticket = e->d_cticket;
@@ -1933,7 +1938,7 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
                 ca.flags = e->d_cflag;
                 ca.seq = e->cflag_seq + 1;
             }
-            int rc = launch_mac_batch(e, st.act, st.nact, per_slot, n, (int)(b & (uint64_t)(e->ring - 1)), &mo, may_ride ? &ca : nullptr);
+            int rc = launch_mac_batch(e, e->stream, st.act, st.nact, per_slot, n, (int)(b & (uint64_t)(e->ring - 1)), &mo, may_ride ? &ca : nullptr);
             if (rc) return rc;
             if (mo.corr_done) {  // the riding workgroups took their tickets
                 e->cticket_base += (unsigned)ca.nchunks;
@@ -1942,9 +1947,9 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
             if (timed) {
                 HIP_TRY(hipEventRecord(e->kev[e->kev_n][1], e->stream));
                 e->kev_n++;
-                e->ks.resident = mo.resident ? 1 : 0;
+                e->ks.resident = mo.form != MacForm::Stream ? 1 : 0;
                 e->ks.partitions = (uint32_t)mo.swept;
-                e->ks.fast_levels = mo.lvl == -2 ? 254u : (mo.lvl < 0 ? 255u : (uint32_t)mo.lvl);  // 255 / 254 = second-level transform
+                e->ks.fast_levels = form_code(mo.form, mo.lvl);
             }
             if (piped) {  // the inverse transforms wait for this MAC on the post stream; the engine's stream moves on
                 HIP_TRY(hipEventRecord(e->ev_mac[par][h], e->stream));
@@ -1978,44 +1983,15 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
                 }
                 if (fuse) {
                     if (!mo.corr_done && !lin) {  // the prefix sums as launches of their own, ahead of their reader
-                        corr_args();
                         ca.chain = 0;
-                        hipLaunchKernelGGL(k_corr_terms, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, inv_stream, ca);
-                        if (ca.nchunks > 1) hipLaunchKernelGGL(k_corr_fix, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, inv_stream, ca);
+                        launch_corr(inv_stream, ca);
                         mo.corr_done = true;
                     }
-                    const int head = slice ? 0 : (int)std::min<uint64_t>((uint64_t)T, (st.ctx.predelay + MC_B - 1) / MC_B);
-                    oa.in1 = d_in1;
-                    oa.in2 = d_in2;
-                    oa.outL = d_outL;
-                    oa.outR = d_outR;
+                    oa = out_args(e, st.ctx, slice, d_in1, d_in2, d_outL, d_outR);
                     oa.lin = lin;
                     oa.drop = stored.drop_done ? e->d_dropbuf : nullptr;
-                    oa.ptab = d_ptab;
-                    oa.pstride = pstride;
-                    oa.cring = e->d_cring;
-                    oa.rc = e->rc;
-                    oa.tabs0 = (int64_t)st.ctx.t0;
-                    oa.predelay = (int64_t)st.ctx.predelay;
-                    oa.n_ref = (int64_t)e->cfg.n_ref;
-                    oa.b0 = make_retired(e).b0;
-                    oa.compat = (int)e->cfg.compat;
-                    oa.pm = e->pm;
-                    if (slice) {  // the slice [first, first + count), nothing else; a sliced engine keeps no wet history
-                        oa.out_from = first;
-                        oa.out_end = first + count;
-                        oa.out_blk0 = first;
-                        oa.wet_head = 0;
-                        oa.wet_from = 1 << 30;
-                    } else {
-                        oa.out_from = head;
-                        oa.out_end = T;
-                        oa.out_blk0 = 0;
-                        oa.wet_head = head;
-                        oa.wet_from = std::max(0, T - (MC_MAX_PREDELAY / MC_B + 8));  // what later calls and a predelay change can reach
-                    }
-                    if (!lin) stored.out_from = head;
-                    lin_head = head;
+                    if (!lin) stored.out_from = oa.wet_head;
+                    lin_head = oa.wet_head;
                 }
                 launch_inv(e, mo, b, inv_stream, to_wet, fuse ? &oa : nullptr);
                 if (mo.corr_done) stored.corr_done = true;
@@ -2063,22 +2039,7 @@ int run_back(mc_engine* e, const float* d_in1, const float* d_in2, const float* 
     // Q1/Q2 prefix sums of this batch, with or without output: run_front left the block sums and the parameter table of the
     // whole batch in the slot on every shard
     if (!ctx.corr_done) {  // (on the headline path they rode along with the front half's launches)
-        CorrArgs ca;
-        std::memset(&ca, 0, sizeof(ca));
-        ca.sums = e->d_sums + (size_t)ctx.slot * e->Tmax;
-        ca.ptab = d_ptab;
-        ca.pstride = ctx.pstride;
-        ca.T = T;
-        ca.vs = ctx.vs;
-        ca.inv_n = 1.0 / (double)e->cfg.n_ref;
-        ca.compat = (int)e->cfg.compat;
-        ca.cring = e->d_cring;
-        ca.rc = e->rc;
-        ca.tabs0 = (int64_t)ctx.t0;
-        ca.ctot = e->d_ctot;
-        corr_chunks(&ca, T, ctx.need_a0, ctx.need_a1, ctx.need_b0);
-        hipLaunchKernelGGL(k_corr_terms, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, e->stream, ca);
-        if (ca.nchunks > 1) hipLaunchKernelGGL(k_corr_fix, dim3(ca.nchunks), dim3(CORR_CHUNK), 0, e->stream, ca);  // a single chunk adds its base itself
+        launch_corr(e->stream, corr_args(e, ctx));
         HIP_TRY(hipGetLastError());
     }
     if (d_outL && d_outR) {
@@ -2295,7 +2256,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
         for (int a = 0; a < pl.nsweep; a++) {
             ActiveVoice av = pl.sweep[a];
             av.uniform = sweep_uniform(av, pl.hi[a], blk);
-            launch_mac_stream(e, av, pl.lo[a], pl.hi[a], 1, bslot0, pl.nsum, a * kNchunk, dst, stamps);
+            launch_mac_stream(e, e->stream, av, pl.lo[a], pl.hi[a], 1, bslot0, pl.nsum, a * kNchunk, dst, stamps);
             swept = std::max(swept, pl.hi[a] - (pl.lo[a] == 2 ? 0 : pl.lo[a]));
         }
         if (e->ktiming) {
@@ -2792,7 +2753,7 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
         for (int a = 0; a < pl.nsweep; a++) {
             ActiveVoice av = pl.sweep[a];
             av.uniform = e->gain_change_block[av.v] + (uint64_t)pl.hi[a] <= blk && e->gain_change_block[av.v] < blk;
-            launch_mac_stream(e, av, pm, pl.hi[a], pm, bslot0, pl.nsum, a * kNchunk, nullptr, stamps);
+            launch_mac_stream(e, e->stream, av, pm, pl.hi[a], pm, bslot0, pl.nsum, a * kNchunk, nullptr, stamps);
             swept = std::max(swept, pl.hi[a]);
         }
         if (timed) {

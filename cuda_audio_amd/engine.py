@@ -1528,6 +1528,9 @@ class Convolution:
         check(self._L.mc_enable_kernel_timing(self._h, 1 if on else 0))
 
     def kernel_stats(self, reset=False):
+        """Timing of the launches that finish a call's own blocks (enable_kernel_timing) and the form the last of them took:
+        `resident`, `partitions` swept and `fast_levels`, the form's code - 0 direct, 1..3 fast-FIR levels, 255 / 254 split / fused
+        second-level transform, 253 overlap-save (the table in DESIGN.md §2.5c)."""
         ks = McKernelStats()
         check(self._L.mc_get_kernel_stats(self._h, C.byref(ks), 1 if reset else 0))
         return dict(launches=ks.launches, blocks=ks.blocks, total_ms=ks.total_ms, last_ms=ks.last_ms,
@@ -1566,7 +1569,9 @@ class Convolution:
         return dict(drop_fft=int(a[0]), forward_transforms=int(a[1]), tiles=int(a[2]), carried_periods=int(a[3]))
 
     def mac_stats(self):
-        """Batch launches by the form their partition sums took (mc_debug_read item 10; host-side counters)."""
+        """Batch launches by the form their partition sums took (mc_debug_read item 10; host-side counters): `resident` counts the
+        direct and the fast-FIR form, the streaming MAC has no counter, the overlap-save passes count in os_stats() (the table in
+        DESIGN.md §2.5c)."""
         a = np.zeros(3, np.uint64)
         check(self._L.mc_debug_read(self._h, 10, 0, a.ctypes.data_as(C.c_void_p), 0, a.nbytes, None))
         return dict(fused=int(a[0]), split=int(a[1]), resident=int(a[2]))
