@@ -34,7 +34,8 @@ SYMBOLS = [
     "mc_default_ir_parts", "mc_ir_parts_plan", "mc_ir_parts_at", "mc_load_ir_parts", "mc_load_ir_sweep_parts", "mc_ir_parts_info",
     "mc_default_ir_room", "mc_synth_ir_room", "mc_ir_room_info", "mc_ir_room_plan",
     "mc_default_ir_room_mics", "mc_synth_ir_room_mics", "mc_ir_room_mics_plan", "mc_ir_room_mics_info",
-    "mc_default_ir_room_bands", "mc_synth_ir_room_bands", "mc_ir_room_bands_plan", "mc_ir_room_bands_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
+    "mc_default_ir_room_bands", "mc_synth_ir_room_bands", "mc_ir_room_bands_plan", "mc_ir_room_bands_info",
+    "mc_default_ir_plate", "mc_synth_ir_plate", "mc_ir_plate_plan", "mc_ir_plate_modes", "mc_ir_plate_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
     "mc_enable_kernel_timing", "mc_get_kernel_stats", "mc_algorithmic_bytes_per_block", "mc_blocks_processed", "mc_preferred_batch",
@@ -465,6 +466,34 @@ class McIrRoomBands(C.Structure):
     ]
 
 
+MC_PLATE_MAX_MODES = 1 << 18
+MC_PLATE_GROUP = 32
+MC_PLATE_SLAB = 256
+MC_PLATE_MAX_PAIRS = 1 << 36
+
+
+class McIrPlate(C.Structure):
+    """mc_ir_plate: the plate whose modes mc_synth_ir_plate adds to a synthesised IR."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("size_m", C.c_float * 2),
+        ("thickness_mm", C.c_float),
+        ("young_gpa", C.c_float),
+        ("density", C.c_float),
+        ("poisson", C.c_float),
+        ("driver_m", C.c_float * 2),
+        ("pickup_m", (C.c_float * 2) * 2),
+        ("low_hz", C.c_float),
+        ("high_hz", C.c_float),
+        ("t60_s", C.c_float * 2),
+        ("damp_hz", C.c_float),
+        ("gain", C.c_float),
+        ("reserved", C.c_uint32),
+        ("last", C.c_uint64),
+    ]
+
+
 class McKernelStats(C.Structure):
     _fields_ = [
         ("launches", C.c_uint64),
@@ -612,6 +641,13 @@ def load():
                                          C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp), C.POINTER(McIrTail)]
     L.mc_ir_room_bands_plan.argtypes = [C.POINTER(McIrRoom), C.POINTER(McIrRoomBands), C.c_uint32, u64, C.POINTER(C.c_double)]
     L.mc_ir_room_bands_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_default_ir_plate.argtypes = [C.POINTER(McIrPlate)]
+    L.mc_default_ir_plate.restype = None
+    L.mc_synth_ir_plate.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrPlate), C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp),
+                                    C.POINTER(McIrTail)]
+    L.mc_ir_plate_plan.argtypes = [C.POINTER(McIrPlate), C.c_uint32, u64, C.POINTER(C.c_double)]
+    L.mc_ir_plate_modes.argtypes = [C.POINTER(McIrPlate), C.c_uint32, u64, u64, C.POINTER(C.c_double)]
+    L.mc_ir_plate_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_num_irs.argtypes = [vp]
     L.mc_ir_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_set_params.argtypes = [vp, C.c_int, C.POINTER(McCcValue)]

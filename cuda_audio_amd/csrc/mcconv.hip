@@ -30,6 +30,7 @@
 #include "ireq.hip.h"
 #include "irdamp.hip.h"
 #include "irdecay.hip.h"
+#include "irplate.hip.h"
 #include "irroom.hip.h"
 #include "irsynth.hip.h"
 #include "irsweep.hip.h"
@@ -101,10 +102,10 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline double pan_l(double p) { return p >= 0 ? 1 - p : 1; }  // conv.cu:386
 inline double pan_r(double p) { return p <= 0 ? 1 + p : 1; }  // conv.cu:387
 
-// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _phase_info, _filter_info, _match_info, _parts_info, _room_info, _room_mics_info and _room_bands_info report of an IR's last
+// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _phase_info, _filter_info, _match_info, _parts_info, _room_info, _room_mics_info, _room_bands_info and _plate_info report of an IR's last
 // load: one entry per kind, on when that load had the step or the source (a shape with something on, an eq band or damping count as a shape, and
 // so do a synthesised, a swept and a tailed load), with the numbers the getter hands out (include/mcconv.h says what they are)
-enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_PHASE, FACT_FILTER, FACT_MATCH, FACT_PARTS, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_KINDS };
+enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_PHASE, FACT_FILTER, FACT_MATCH, FACT_PARTS, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_PLATE, FACT_KINDS };
 struct IrFact {
     bool on = false;
     double v[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -3310,6 +3311,11 @@ struct RoomStep {
     RoomBands bands;
 };
 
+// the plate of a synthesised load as load_ir and shape_stage take it: the checked plate with its table (irplate.hip.h)
+struct PlateStep {
+    PlatePlan plan;
+};
+
 // One load as load_ir and shape_stage take it: where the frames come from, and the steps they go through on the device.  The
 // entry points fill it in by name; a null pointer is a source that is not this load's, or a step that is off.
 struct IrLoad {
@@ -3322,6 +3328,8 @@ struct IrLoad {
     RoomStep* room = nullptr;          // mc_synth_ir_room (irroom.hip.h; with syn): its reflections are added to the generated
                                        // frames, and the kept counts are filled in; room->banded: once per band of
                                        // room->bands, joined by the band split (mc_synth_ir_room_bands)
+    const PlateStep* plate = nullptr;  // mc_synth_ir_plate (irplate.hip.h; with syn and without room): the sum of its modes is added
+                                       // to the generated frames
     const SweepSource* swp = nullptr;  // mc_load_ir_sweep (irsweep.hip.h): the frames are deconvolved on the device from its recording
     // -- the steps, in the order they run.  Any of tail, eq, damp, syn and swp needs the shape, which may have everything off
     const TailStep* tail = nullptr;      // step 1a, between the source and the shaping (irtail.hip.h; tail->plan.F = the frames at the session's rate)
@@ -3368,6 +3376,7 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
     hipError_t er = ld.swp  ? swp_generate(e->stream, *ld.swp, d_x, &d_rec, &d_u)
                     : ld.syn && ld.room && ld.room->banded ? room_generate_bands(e->stream, *ld.syn, ld.room->bands, d_x, ld.room->kept)
                     : ld.syn && ld.room ? room_generate(e->stream, *ld.syn, ld.room->plan, d_x, ld.room->kept)
+                    : ld.syn && ld.plate ? plate_generate(e->stream, *ld.syn, ld.plate->plan, d_x)
                     : ld.syn ? syn_generate(e->stream, *ld.syn, d_x)
                     : ld.rs ? rs_convert(e->stream, ld.rs[0], ld.rs[1], ld.lr, ld.frames, d_x, conv, unused)
                             : hipMemcpy(d_x, ld.lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
@@ -3448,6 +3457,10 @@ void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const ShapedTaps& s
             const double* b = ld.room->bands.report;
             put(FACT_ROOM_BANDS, {b[0], b[1], b[2], b[3], b[4], b[5], b[6], b[7], b[8], b[9], b[10], b[11], b[12], b[13], b[14], b[15]});
         }
+    }
+    if (ld.plate) {
+        const PlatePlan& p = ld.plate->plan;
+        put(FACT_PLATE, {(double)p.M, (double)p.nonzero[0], (double)p.nonzero[1], (double)p.E, p.lo, p.hi, p.kappa, 0.0});
     }
 }
 
@@ -3602,7 +3615,7 @@ const char* resolve_steps(const mc_ir_shape* shape, const mc_ir_eq* eq, const mc
     return nullptr;
 }
 
-// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, phase, filter, match, parts, room, room mics, room bands): out = the first `count` numbers of what
+// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, phase, filter, match, parts, room, room mics, room bands, plate): out = the first `count` numbers of what
 // note_load kept of that kind, or MC_ERR_STATE with "IR <idx> <was_not>" when the last load had none
 int ir_fact(const mc_engine* e, uint64_t idx, IrFactKind kind, int count, const char* was_not, double* out) {
     if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
@@ -4043,6 +4056,74 @@ int mc_ir_room_bands_plan(const mc_ir_room* room, const mc_ir_room_bands* bands,
 int mc_ir_room_bands_info(const mc_engine* e, uint64_t idx, double out[16]) {
     return ir_fact(e, idx, FACT_ROOM_BANDS, 16, "was not loaded with bands", out);
 }
+
+void mc_default_ir_plate(mc_ir_plate* p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_size = (uint32_t)sizeof(*p);
+    p->size_m[0] = 2.04f, p->size_m[1] = 0.97f;
+    p->thickness_mm = 0.5f;
+    p->young_gpa = 200.f, p->density = 7850.f, p->poisson = 0.3f;
+    p->driver_m[0] = 0.83f, p->driver_m[1] = 0.41f;
+    p->pickup_m[0][0] = 0.31f, p->pickup_m[0][1] = 0.67f;
+    p->pickup_m[1][0] = 1.57f, p->pickup_m[1][1] = 0.29f;
+    p->low_hz = 20.f;
+    p->t60_s[0] = 4.f, p->t60_s[1] = 1.f;
+    p->damp_hz = 10000.f;
+    p->gain = 1.f;
+}
+
+int mc_synth_ir_plate(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_synth* synth, const mc_ir_plate* plate, const mc_ir_shape* shape,
+                      const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail) {
+    if (!plate) return mc_synth_ir_room(e, idx, nframes, synth, nullptr, shape, eq, damp, tail);
+    // synth, then the plate, then the tail with F' after F, then damp, eq and shape as in mc_synth_ir_room, all before the engine
+    // and before any HIP call
+    if (const char* bad = syn_check(synth)) return fail(MC_ERR_ARG, "%s", bad);
+    const uint32_t rate = synth->rate;
+    const uint64_t F = synth->frames;
+    PlateStep pstep;
+    if (const char* bad = plate_check(plate, rate, F, &pstep.plan)) return fail(MC_ERR_ARG, "%s", bad);
+    const bool tailed = tail && tail->mode != MC_TAIL_OFF;
+    if (tailed) {
+        if (const char* bad = tail_check(tail, rate)) return fail(MC_ERR_ARG, "%s", bad);
+        if (const char* bad = tail_check_frames(tail, F)) return fail(MC_ERR_ARG, "%s", bad);
+    }
+    IrSteps steps;
+    if (const char* bad = resolve_steps(shape, eq, damp, rate, rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
+    const SynPlan syn = syn_plan(*synth);
+    TailStep step{};
+    if (tailed) step = tail_step(*tail, rate, F);
+    IrLoad ld;
+    ld.syn = &syn, ld.frames = F;
+    ld.plate = &pstep;
+    ld.tail = tailed ? &step : nullptr;
+    steps.into(ld);
+    return load_ir(e, idx, nframes, ld);
+}
+
+int mc_ir_plate_plan(const mc_ir_plate* plate, uint32_t rate, uint64_t frames, double out[8]) {
+    if (frames < 1 || frames > SYN_MAX_FRAMES)
+        return fail(MC_ERR_ARG, "frames %llu outside [1, %llu]", (unsigned long long)frames, (unsigned long long)SYN_MAX_FRAMES);
+    PlatePlan p;
+    if (const char* bad = plate_check(plate, rate, frames, &p)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!out) return fail(MC_ERR_ARG, "null out");
+    const double v[8] = {(double)p.M, p.lo, p.hi, p.kappa, p.density, p.t60_lo, p.t60_hi, (double)p.E * (double)p.M};
+    std::copy(v, v + 8, out);
+    return MC_OK;
+}
+
+int mc_ir_plate_modes(const mc_ir_plate* plate, uint32_t rate, uint64_t first, uint64_t count, double* rows) {
+    PlatePlan p;
+    if (const char* bad = plate_check(plate, rate, 0, &p)) return fail(MC_ERR_ARG, "%s", bad);
+    if (first > p.M || count > p.M - first)
+        return fail(MC_ERR_ARG, "rows %llu to %llu of a table of %llu", (unsigned long long)first, (unsigned long long)(first + count), (unsigned long long)p.M);
+    if (count && !rows) return fail(MC_ERR_ARG, "null rows");
+    static_assert(sizeof(PlateMode) == 6 * sizeof(double), "a row of the mode table is six doubles");
+    if (count) std::memcpy(rows, p.modes.data() + first, sizeof(PlateMode) * count);
+    return MC_OK;
+}
+
+int mc_ir_plate_info(const mc_engine* e, uint64_t idx, double out[8]) { return ir_fact(e, idx, FACT_PLATE, 8, "was not loaded with a plate", out); }
 
 int mc_ir_synth_info(const mc_engine* e, uint64_t idx, double out[4]) { return ir_fact(e, idx, FACT_SYNTH, 4, "was not synthesised", out); }
 

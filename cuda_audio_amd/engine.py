@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrRoom, McIrRoomBands, McIrRoomMics, McIrFilter, McIrMatch, McIrPhase, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrPlate, McIrRoom, McIrRoomBands, McIrRoomMics, McIrFilter, McIrMatch, McIrPhase, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -660,6 +660,74 @@ def room_plan(room, rate, frames):
 
 
 @dataclasses.dataclass
+class IrPlate:
+    """The plate reverberator whose modes prepare_synth(plate=...) adds to a synthesised IR (mc_ir_plate, include/mcconv.h): a
+    thin simply supported rectangular sheet of `size` (Lx, Ly) metres and `thickness_mm`, of `material` "steel" or (Young's
+    modulus in GPa, density in kg/m^3, Poisson's ratio), driven at `driver` (x, y) and picked up at `pickups` ((x, y) left,
+    (x, y) right).  The modes between low_hz and high_hz (0: min(20000, 0.45 rate)) sound; `t60` = (seconds towards 0 Hz,
+    seconds at damp_hz), 0 for no loss at that end; `gain` is the RMS of the first milliseconds; frames at and after `last`
+    (0: the IR's length) get nothing from the plate."""
+
+    size: tuple = (2.04, 0.97)
+    thickness_mm: float = 0.5
+    material: object = "steel"
+    driver: tuple = (0.83, 0.41)
+    pickups: tuple = ((0.31, 0.67), (1.57, 0.29))
+    low_hz: float = 20.0
+    high_hz: float = 0.0
+    t60: tuple = (4.0, 1.0)
+    damp_hz: float = 10000.0
+    gain: float = 1.0
+    last: int = 0
+
+    MATERIALS = {"steel": (200.0, 7850.0, 0.3)}
+
+    def to_c(self):
+        if isinstance(self.material, str):
+            if self.material not in self.MATERIALS:
+                raise ValueError(f"material {self.material!r}: one of {sorted(self.MATERIALS)} or (E in GPa, density, Poisson's ratio)")
+            material = self.MATERIALS[self.material]
+        else:
+            material = tuple(self.material)
+        if len(self.size) != 2 or len(self.driver) != 2 or len(self.pickups) != 2 or any(len(q) != 2 for q in self.pickups) or len(self.t60) != 2 \
+                or len(material) != 3:
+            raise ValueError("size, driver and t60 take two numbers, pickups two pairs, material a name or three numbers")
+        p = McIrPlate()
+        _lib.load().mc_default_ir_plate(C.byref(p))
+        for k in range(2):
+            p.size_m[k], p.driver_m[k], p.t60_s[k] = float(self.size[k]), float(self.driver[k]), float(self.t60[k])
+            for a in range(2):
+                p.pickup_m[k][a] = float(self.pickups[k][a])
+        p.thickness_mm = float(self.thickness_mm)
+        p.young_gpa, p.density, p.poisson = (float(v) for v in material)
+        p.low_hz, p.high_hz, p.damp_hz, p.gain, p.last = float(self.low_hz), float(self.high_hz), float(self.damp_hz), float(self.gain), int(self.last)
+        return p
+
+
+def plate_plan(plate, rate, frames):
+    """What a load of `frames` frames at `rate` would do with `plate` (an IrPlate; mc_ir_plate_plan, host arithmetic only): the
+    modes kept, the lowest and the highest of them in Hz, the stiffness kappa, Weyl's modal density in modes per Hz, the decay
+    times at low_hz and at the highest mode in seconds (0: no loss), and the (mode, frame) pairs the device would sum."""
+    out = (C.c_double * 8)()
+    check(_lib.load().mc_ir_plate_plan(C.byref(plate.to_c()), int(rate), int(frames), out))
+    return dict(modes=int(out[0]), lowest=out[1], highest=out[2], kappa=out[3], density=out[4], t60=(out[5], out[6]), pairs=int(out[7]))
+
+
+def plate_modes(plate, rate, first=0, count=None):
+    """Rows first .. first + count of the mode table of `plate` at `rate` (mc_ir_plate_modes, host arithmetic only; count None:
+    to the end) as float64 [count, 6]: m, n, f (Hz), sigma (1/s), a_L, a_R: the table a load uploads."""
+    L = _lib.load()
+    p = plate.to_c()
+    if count is None:
+        out = (C.c_double * 8)()
+        check(L.mc_ir_plate_plan(C.byref(p), int(rate), 1, out))
+        count = int(out[0]) - int(first)
+    rows = np.zeros((max(int(count), 0), 6), np.float64)
+    check(L.mc_ir_plate_modes(C.byref(p), int(rate), int(first), int(count), rows.ctypes.data_as(C.POINTER(C.c_double))))
+    return rows
+
+
+@dataclasses.dataclass
 class IrRoomMics:
     """Directional microphones and a directional source in an IrRoom (mc_ir_room_mics, include/mcconv.h): prepare_synth(room=,
     mics=).  `pattern` is the receivers' first-order pattern, a name of PATTERNS or the number alpha of
@@ -1077,7 +1145,7 @@ class Convolution:
         steps, keep = _c_steps(shape, eq, damp, tail, phase, filter, match, parts)
         check(self._L.mc_load_ir_parts(self._h, idx, _fp(lr), lr.shape[0], nframes, *rates, *steps))
 
-    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None, room=None, tail=None, mics=None, bands=None):
+    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None, room=None, tail=None, mics=None, bands=None, plate=None):
         """Generate the IR `synth` (an IrSynth) describes on the device and store it at idx (mc_synth_ir): the frames take the
         place of a WAV's at the session's rate, and shape, eq and damp apply to them as in prepare().  A synthesised IR counts
         as shaped: ir_shape_info(idx)["frames"] is synth.frames.  The engine's sample_rate (which eq, damp, room and tail
@@ -1086,10 +1154,18 @@ class Convolution:
         was rendered.  tail (an IrTail whose mode is not "off"): the tail step on the generated frames, as in prepare().
         mics (an IrRoomMics, with room): the receivers and the source of the room are directional; ir_room_mics_info(idx)
         then tells the direct sound's factors.  bands (an IrRoomBands, with room): the walls and the air differ per
-        frequency band; ir_room_bands_info(idx) then tells the bands' reverberation times."""
+        frequency band; ir_room_bands_info(idx) then tells the bands' reverberation times.
+        plate (an IrPlate, without room, mics and bands): the modes of a plate reverberator are added to the frames
+        (mc_synth_ir_plate); ir_plate_info(idx) then tells what was summed."""
         s = synth.to_c()
         if not s.rate:
             s.rate = int(self.sample_rate or 0)
+        if plate is not None:
+            if room is not None or mics is not None or bands is not None:
+                raise ValueError("a plate and a room (room, mics, bands) in one load are not offered")
+            steps, keep = _c_steps(shape, eq, damp, tail, None, None, None, None)
+            check(self._L.mc_synth_ir_plate(self._h, idx, nframes, C.byref(s), C.byref(plate.to_c()), *steps[:4]))
+            return
         if bands is not None and room is None:
             raise ValueError("the bands need a room")
         if mics is not None and room is None:
@@ -1253,6 +1329,14 @@ class Convolution:
         out = (C.c_double * 8)()
         check(self._L.mc_ir_room_info(self._h, idx, out))
         return dict(order=int(out[0]), images=(int(out[1]), int(out[2])), direct=(out[3], out[4]), last=int(out[5]), complete=int(out[6]))
+
+    def ir_plate_info(self, idx):
+        """What the plate of IR idx's load summed (mc_ir_plate_info): the modes kept, those with a non-zero amplitude per
+        channel, the frame E from which the plate adds nothing, the lowest and the highest kept mode in Hz and the stiffness
+        kappa.  McError (MC_ERR_STATE) for an IR whose last load had no plate."""
+        out = (C.c_double * 8)()
+        check(self._L.mc_ir_plate_info(self._h, idx, out))
+        return dict(modes=int(out[0]), sounding=(int(out[1]), int(out[2])), last=int(out[3]), lowest=out[4], highest=out[5], kappa=out[6])
 
     def ir_room_bands_info(self, idx):
         """The bands of IR idx's load (mc_ir_room_bands_info), as room_bands_plan reports them.  McError (MC_ERR_STATE) for an

@@ -119,6 +119,11 @@ void mc_default_ir_room_bands(mc_ir_room_bands*) __attribute__((weak));
 int mc_synth_ir_room_bands(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_room*, const mc_ir_room_mics*, const mc_ir_room_bands*,
                            const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*, const mc_ir_tail*) __attribute__((weak));
 int mc_ir_room_bands_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+// ... or no plate
+void mc_default_ir_plate(mc_ir_plate*) __attribute__((weak));
+int mc_synth_ir_plate(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_plate*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
+                      const mc_ir_tail*) __attribute__((weak));
+int mc_ir_plate_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 }
 
 namespace {
@@ -348,6 +353,7 @@ void Convolution::loadIr(const IrLoadRequest& r) {
         {nullptr, r.bands.has_value(), mc_synth_ir_room_bands && mc_default_ir_room_bands && mc_ir_room_bands_info, "frequency bands in its rooms (mc_synth_ir_room_bands)"},
         {nullptr, r.mics.has_value(), mc_synth_ir_room_mics && mc_default_ir_room_mics && mc_ir_room_mics_info, "directional microphones in its rooms (mc_synth_ir_room_mics)"},
         {nullptr, r.room.has_value(), mc_synth_ir_room && mc_default_ir_room && mc_ir_room_info, "room rendering (mc_synth_ir_room)"},
+        {nullptr, r.plate.has_value(), mc_synth_ir_plate && mc_default_ir_plate && mc_ir_plate_info, "plate synthesis (mc_synth_ir_plate)"},
         {r.phase && generated ? "phase" : nullptr, minimum, mc_default_ir_phase && mc_load_ir_phase && mc_load_ir_sweep_phase && mc_ir_phase_info, "phase step (mc_load_ir_phase)"},
         {r.filter && generated ? "filter" : nullptr, filtered, mc_default_ir_filter && mc_load_ir_filter && mc_load_ir_sweep_filter && mc_ir_filter_info, "filter step (mc_load_ir_filter)"},
         {r.match && generated ? "match" : nullptr, matched, mc_default_ir_match && mc_load_ir_match && mc_load_ir_sweep_match && mc_ir_match_info && mc_ir_match_curve, "match step (mc_load_ir_match)"},
@@ -408,6 +414,7 @@ void Convolution::loadIr(const IrLoadRequest& r) {
         const int rc = bands  ? mc_synth_ir_room_bands(_engine, idx, r.nframes, y, room, mics, bands, &s, q, d, t)
                        : mics ? mc_synth_ir_room_mics(_engine, idx, r.nframes, y, room, mics, &s, q, d, t)
                        : room ? mc_synth_ir_room(_engine, idx, r.nframes, y, room, &s, q, d, t)
+                       : r.plate ? mc_synth_ir_plate(_engine, idx, r.nframes, y, &*r.plate, &s, q, d, t)
                               : mc_synth_ir(_engine, idx, r.nframes, y, &s, q, d);
         if (rc != MC_OK) {
             Log::error("conv", "IR %zu cannot be synthesised: %s", idx, mc_last_error());
@@ -447,6 +454,12 @@ void Convolution::loadIr(const IrLoadRequest& r) {
         check(mc_load_ir_shaped(_engine, idx, r.lr, r.frames, r.nframes, irRate, sessionRate, &s), "mc_load_ir_shaped");
 
     // what was done: the source's lines, then one per step in the order the frames went through them
+    if (r.plate) {
+        double pi[8];
+        check(mc_ir_plate_info(_engine, idx, pi), "mc_ir_plate_info");
+        Log::info(name, "IR %zu plate: %llu modes from %.2f to %.2f Hz, %llu and %llu sounding, before frame %llu, kappa %.4f m^2/s", idx,
+                  (unsigned long long)pi[0], pi[4], pi[5], (unsigned long long)pi[1], (unsigned long long)pi[2], (unsigned long long)pi[3], pi[6]);
+    }
     if (r.room) {
         double ri[8];
         check(mc_ir_room_info(_engine, idx, ri), "mc_ir_room_info");
@@ -1071,7 +1084,7 @@ std::optional<mc_ir_tail> Convolution::measureTail(const PendingIr& p) {
         Log::error("conv", "the engine has no tail step (mc_load_ir_tail)");
         std::exit(2);
     }
-    if (p.generated && !p.roomed) {
+    if (p.generated && !p.roomed && !p.plated) {
         Log::info(name, "IR %zu tail: a generated IR has no floor, left as it is", p.idx);
         return std::nullopt;
     }
@@ -1728,6 +1741,132 @@ void Convolution::prepareRoom(size_t idx, const IrRoom& room, size_t nframes) {
     p.room = room;
 }
 
+mc_ir_plate Convolution::plateFrames(const IrPlate& plate, double rate) {
+    mc_ir_plate p;
+    mc_default_ir_plate(&p);
+    for (int a = 0; a < 2; a++) {
+        p.size_m[a] = plate.size[a], p.driver_m[a] = plate.driver[a], p.t60_s[a] = plate.t60[a];
+        for (int c = 0; c < 2; c++) p.pickup_m[c][a] = plate.pickup[c][a];
+    }
+    p.thickness_mm = plate.thickness;
+    p.young_gpa = plate.material[0], p.density = plate.material[1], p.poisson = plate.material[2];
+    p.low_hz = plate.low, p.high_hz = plate.high;
+    p.damp_hz = plate.damp;
+    p.gain = plate.gain;
+    p.last = (uint64_t)std::nearbyint(plate.lastSeconds * rate);
+    return p;
+}
+
+bool Convolution::parsePlate(const std::string& line, IrPlate& out, std::string& why) {
+    static const char* form =
+        "plate:LENGTH_S[:key=value,...] with keys size=LX,LY (metres), thick=MM, material=steel|E/RHO/NU (GPa, kg/m^3, Poisson's ratio), drive=X,Y, "
+        "pick=X,Y/X,Y (left/right), low=HZ, high=HZ, t60=LO/HI (seconds towards 0 Hz and at damp; 0 = no loss), damp=HZ, gain, last=S";
+    std::vector<std::string> parts;
+    for (size_t at = 0;;) {
+        const size_t colon = line.find(':', at);
+        parts.push_back(line.substr(at, colon == std::string::npos ? colon : colon - at));
+        if (colon == std::string::npos) break;
+        at = colon + 1;
+    }
+    if (parts.size() < 2 || parts.size() > 3 || parts[0] != "plate") {
+        why = std::string("a plate is ") + form;
+        return false;
+    }
+    const auto number = [](const std::string& text, double& v) {
+        char* end = nullptr;
+        v = std::strtod(text.c_str(), &end);
+        return !text.empty() && end == text.c_str() + text.size() && std::isfinite(v);
+    };
+    // `count` numbers >= lo separated by `sep` that fill the whole text
+    const auto numbers = [&](const std::string& text, char sep, size_t count, double lo, float* v) {
+        size_t at = 0;
+        for (size_t k = 0; k < count; k++) {
+            const size_t end = k + 1 < count ? text.find(sep, at) : text.size();
+            double x;
+            if (end == std::string::npos || !number(text.substr(at, end - at), x) || x < lo) return false;
+            v[k] = (float)x;
+            at = end + 1;
+        }
+        return true;
+    };
+    IrPlate plate;
+    if (!number(parts[1], plate.lengthSeconds) || !(plate.lengthSeconds > 0.0)) {
+        why = "LENGTH_S '" + parts[1] + "' is not a length in seconds, > 0";
+        return false;
+    }
+    const std::string list = parts.size() == 3 ? parts[2] : "";
+    if (parts.size() == 3 && list.empty()) {
+        why = std::string("nothing after the last colon: ") + form;
+        return false;
+    }
+    // the items: a comma starts a new one when key= follows it, and belongs to the value before it otherwise (size=LX,LY)
+    std::vector<std::string> items;
+    for (size_t at = 0; at < list.size() || (at && at == list.size());) {
+        const size_t comma = std::min(list.find(',', at), list.size());
+        const std::string piece = list.substr(at, comma - at);
+        if (piece.find('=') != std::string::npos || items.empty() || piece.empty())
+            items.push_back(piece);
+        else
+            items.back() += "," + piece;
+        at = comma + 1;
+        if (comma == list.size()) break;
+    }
+    for (const std::string& item : items) {
+        const size_t eq = item.find('=');
+        if (eq == std::string::npos) {
+            why = "'" + item + "' is not key=value";
+            return false;
+        }
+        const std::string key = item.substr(0, eq), text = item.substr(eq + 1);
+        double v = 0.0;
+        bool good = true;
+        if (key == "size") {
+            good = numbers(text, ',', 2, 0.0, plate.size);
+        } else if (key == "drive") {
+            good = numbers(text, ',', 2, 0.0, plate.driver);
+        } else if (key == "pick") {
+            const size_t slash = text.find('/');
+            good = slash != std::string::npos && numbers(text.substr(0, slash), ',', 2, 0.0, plate.pickup[0]) &&
+                   numbers(text.substr(slash + 1), ',', 2, 0.0, plate.pickup[1]);
+        } else if (key == "material") {
+            if (text == "steel")
+                plate.material[0] = 200.0f, plate.material[1] = 7850.0f, plate.material[2] = 0.3f;
+            else
+                good = numbers(text, '/', 3, 0.0, plate.material);
+        } else if (key == "t60") {
+            good = numbers(text, '/', 2, 0.0, plate.t60);
+        } else if (key == "thick" || key == "low" || key == "high" || key == "damp" || key == "gain") {
+            good = number(text, v) && v >= 0.0;
+            (key == "thick" ? plate.thickness : key == "low" ? plate.low : key == "high" ? plate.high : key == "damp" ? plate.damp : plate.gain) = (float)v;
+        } else if (key == "last") {
+            good = number(text, v) && v >= 0.0;
+            plate.lastSeconds = v;
+        } else {
+            why = "unknown key '" + key + "': " + form;
+            return false;
+        }
+        if (!good) {
+            why = "'" + text + "' is no value for " + key;
+            return false;
+        }
+    }
+    out = plate;
+    return true;
+}
+
+void Convolution::preparePlate(size_t idx, const IrPlate& plate, size_t nframes) {
+    if (_group) {
+        Log::error("conv", "plate synthesis is not available with several devices (mc_synth_ir_plate is single-engine)");
+        std::exit(2);
+    }
+    PendingIr& p = pend(idx, nframes);  // (generated by onStart(), once the client's rate is known)
+    p.generated = p.plated = true;
+    p.synth = IrSynth();
+    p.synth.lengthSeconds = plate.lengthSeconds;
+    p.synth.late = 0.0f;  // (the plate alone: no late field under it)
+    p.plate = plate;
+}
+
 // A new entry of _pendingIrs with what every kind of IR has: its place, and the shape, EQ and damping that are set now
 Convolution::PendingIr& Convolution::pend(size_t idx, size_t nframes) {
     _pendingIrs.emplace_back();
@@ -1937,11 +2076,16 @@ Convolution::IrLoadRequest Convolution::requestFor(const PendingIr& p) {
             Log::error("conv", "the engine has no room rendering (mc_synth_ir_room)");
             std::exit(2);
         }
+        if (p.plated && !mc_default_ir_plate) {
+            Log::error("conv", "the engine has no plate synthesis (mc_synth_ir_plate)");
+            std::exit(2);
+        }
         if (!mc_default_ir_synth) {
             Log::error("conv", "the engine has no IR synthesis (mc_synth_ir)");
             std::exit(2);
         }
         r.synth = synthFrames(p.roomed ? p.room.late : p.synth, (double)samplerate);
+        if (p.plated) r.plate = plateFrames(p.plate, (double)samplerate);
         if (p.roomed) r.room = roomFrames(p.room, (double)samplerate);
         if (p.roomed && p.room.directional) r.mics = roomMics(p.room);
         if (p.roomed && p.room.banded) r.bands = roomBands(p.room);

@@ -221,6 +221,31 @@ public:
     // mc_ir_room_bands of a banded IrRoom
     static mc_ir_room_bands roomBands(const IrRoom& room);
 
+    // A plate reverberator whose modes the engine sums (mc_ir_plate and mc_synth_ir_plate of include/mcconv.h; no reference
+    // equivalent): metres, millimetres, Hz and seconds, the length and `last` turned into frames at the client's sample rate by
+    // rint, so preparePlate() keeps the numbers and onStart() generates.  What is not given is mc_default_ir_plate's.  The shape,
+    // EQ, damping, tail, reports and rt60 aim that are set apply as to a WAV.  One more log line per IR: the modes kept, those
+    // that sound per channel, their range and the stiffness.  Single device only, as setIrShape.
+    struct IrPlate {
+        double lengthSeconds = 1.0;
+        float size[2] = {2.04f, 0.97f};
+        float thickness = 0.5f;                         // mm
+        float material[3] = {200.0f, 7850.0f, 0.3f};    // GPa, kg/m^3, Poisson's ratio: steel
+        float driver[2] = {0.83f, 0.41f};
+        float pickup[2][2] = {{0.31f, 0.67f}, {1.57f, 0.29f}};
+        float low = 20.0f, high = 0.0f;
+        float t60[2] = {4.0f, 1.0f};
+        float damp = 10000.0f, gain = 1.0f;
+        double lastSeconds = 0.0;
+    };
+    void preparePlate(size_t idx, const IrPlate& plate, size_t nframes = 1024);
+    // A line of an IR index that starts with "plate:" - plate:LENGTH_S[:key=value,...], keys size=LX,LY, thick=MM,
+    // material=steel|E/RHO/NU, drive=X,Y, pick=X,Y/X,Y, low=HZ, high=HZ, t60=LO/HI, damp=HZ, gain and last=S - as an IrPlate.  False,
+    // with the reason in `why`, for a malformed line.
+    static bool parsePlate(const std::string& line, IrPlate& out, std::string& why);
+    // mc_ir_plate of an IrPlate at rate Hz
+    static mc_ir_plate plateFrames(const IrPlate& plate, double rate);
+
     // An IR the engine deconvolves from the recording of an exponential sine sweep played through a room (mc_sweep and
     // mc_load_ir_sweep of include/mcconv.h; no reference equivalent): times in seconds, turned into frames at the client's
     // sample rate by rint, so prepareSweep() keeps the numbers and the recording and onStart() deconvolves.  The recording
@@ -493,6 +518,8 @@ private:
         IrSweep sweep;
         bool roomed = false;  // prepareRoom: generated, `room` with its late field in place of `synth`
         IrRoom room = IrRoom();
+        bool plated = false;  // preparePlate: generated, `plate` and nothing of `synth` but its length
+        IrPlate plate = IrPlate();
     };
     struct SweepLoad {  // the arguments of mc_load_ir_sweep beside the recording
         mc_sweep sweep;
@@ -517,6 +544,7 @@ private:
         std::optional<mc_ir_room> room;
         std::optional<mc_ir_room_mics> mics;
         std::optional<mc_ir_room_bands> bands;
+        std::optional<mc_ir_plate> plate;  // with synth and without room: the modes of a plate are added (mc_synth_ir_plate)
         std::optional<SweepLoad> sweep;
         // The steps, in the order the frames go through them: tail, phase, filter, match, parts (null = off; they point at the
         // object's settings, whose second IRs are not copied), then shape, damp, eq.  A generated IR goes through the tail (with a

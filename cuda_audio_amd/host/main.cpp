@@ -32,6 +32,10 @@
 // Walls and air per frequency band in that room: xover=HZ[/HZ[/HZ]] cuts up to four bands, betas=B[/B...] gives every band one
 // reflection coefficient for its six walls, air=DB[/DB...] the air's loss in dB per metre (one value, or one per band); the room
 // is rendered once per band and joined by --ir-damp's band split, and one more log line tells the bands' reverberation times.
+// A line that starts with "plate:" is a plate reverberator whose modes the engine sums, plate:LENGTH_S[:key=value,...] with keys
+// size=LX,LY, thick=MM, material=steel|E/RHO/NU, drive=X,Y, pick=X,Y/X,Y, low=HZ, high=HZ, t60=LO/HI, damp=HZ, gain, last=S
+// (Convolution::parsePlate; metres, millimetres and seconds); the --ir-* options apply to it as to a WAV, and one more log line
+// tells the modes kept.
 // A line that starts with "sweep:" is an IR the engine deconvolves from the recording of a sine sweep,
 // sweep:RECORDING.wav:LENGTH_S:F1:F2[:key=value,...] with keys amp, fadein, fadeout, offset, length (Convolution::parseSweep;
 // times in seconds, the recording at the client's sample rate); the --ir-* options apply to it as to a WAV.
@@ -414,6 +418,16 @@ int main(int argc, char** argv) {
                         return 2;
                     }
                     c->prepareRoom(j, room);
+                    continue;
+                }
+                if (!path.compare(0, 6, "plate:")) {  // a plate reverberator instead of a WAV path
+                    Convolution::IrPlate plate;
+                    std::string why;
+                    if (!Convolution::parsePlate(path, plate, why)) {
+                        std::cerr << "index line '" << path << "': " << why << std::endl;
+                        return 2;
+                    }
+                    c->preparePlate(j, plate);
                     continue;
                 }
                 if (!path.compare(0, 6, "sweep:")) {  // an IR deconvolved from a recorded sweep

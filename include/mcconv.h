@@ -1265,6 +1265,84 @@ int mc_ir_room_bands_plan(const mc_ir_room *room, const mc_ir_room_bands *bands,
  * mc_ir_room_mics_info still answer for such a load) */
 int mc_ir_room_bands_info(const mc_engine *e, uint64_t idx, double out[16]);
 
+/* A plate reverberator (a thin steel sheet, a driver and two pickups: the EMT 140), added on the device to the frames
+ * mc_ir_synth describes as the sum of the modes of a simply supported rectangular plate.  A plate is not a room: its modal
+ * density is constant over frequency, so it is dense from the first millisecond, it is dispersive, and its decay falls with
+ * frequency.  No reference equivalent; single-engine and load-time only, as shaping is.
+ *
+ * Everything is computed in double from the float fields; rate = synth->rate, F = synth->frames.
+ * Plate.  Sides Lx, Ly = size_m (metres), thickness h = thickness_mm / 1000, Young's modulus E = young_gpa 10^9, density rho,
+ *   Poisson's ratio nu.  Stiffness kappa = sqrt(E h^2 / (12 rho (1 - nu^2))) in m^2/s.
+ * Modes.  For m, n >= 1 mode (m, n) has f_mn = (pi kappa / 2) ((m / Lx)^2 + (n / Ly)^2) Hz and the shape
+ *   Phi_mn(x, y) = sin(m pi x / Lx) sin(n pi y / Ly).  Those with low_hz <= f_mn <= high_hz are kept, enumerated with m ascending
+ *   and n ascending within each m: the row order of the mode table.  M is the number kept; M = 0 and M above
+ *   MC_PLATE_MAX_MODES are refused.  high_hz must lie below rate / 2; 0 stands for min(20000, 0.45 rate).
+ * Loss.  s_i = t60_s[i] ? 3 ln 10 / t60_s[i] : 0 per second: t60_s[0] is the decay time towards 0 Hz, t60_s[1] the one at
+ *   damp_hz, 0 is no loss at that end.  sigma(f) = s_0 + (s_1 - s_0) f / damp_hz: Bilbao's two-parameter loss
+ *   sigma_0 + sigma_1 k^2, which is linear in f because omega = kappa k^2.  s_1 >= s_0 is required (the highs decay no slower
+ *   than the lows).  The damped frequency is taken as f_mn; low_hz >= 1 keeps sigma far below omega.
+ * Amplitudes.  The driver sits at driver_m, pickup c = L, R at pickup_m[c], all strictly inside the plate:
+ *   a_jc = gain 4 sqrt(2 / M) Phi_j(driver) Phi_j(pickup c).  The mean square of Phi Phi is 1/16 and M cosines of random
+ *   phase add in power, so the expected RMS of the first milliseconds is `gain`.
+ * Term.  With E = last ? min(last, F) : F, for frames t < E
+ *   y_c[t] = sum_j a_jc exp(-sigma_j t / rate) cos(2 pi frac(nu_j t)), nu_j = f_j / rate,
+ *   the phase reduced in turns, not in radians.
+ * Evaluation.  exp cos at (j, t) is a pure function of row j of the table and t, whatever the launch, F and M: frames come in
+ *   groups of MC_PLATE_GROUP aligned to multiples of it.  At a group's first frame t0 the value is z = exp(-(sigma_j / rate) t0)
+ *   (cos, sin)(2 pi (nu_j t0 - rint(nu_j t0))), the difference made with one fused multiply-add; each later frame of the group
+ *   is the one before times r_j = exp(-sigma_j / rate) (cos, sin)(2 pi nu_j) as complex numbers, and exp cos is the real part.
+ * Sum.  mc_ir_room's rule: each contribution is q = llrint(a_jc exp cos 2^40) (to nearest, ties to even), added into a 64-bit
+ *   integer per frame and channel, so the same struct stores the same bits whatever the grid.  gain 4 sqrt(2 M) must stay
+ *   below 2^22, which excludes overflow.
+ * Frame.  (float)(late + direct + reflections + acc 2^-40), added in that order in double and rounded once; the first three
+ *   terms are mc_ir_synth's.
+ * Work.  E M, the (mode, frame) pairs, may not exceed MC_PLATE_MAX_PAIRS. */
+#define MC_PLATE_MAX_MODES 262144       /* 2^18 */
+#define MC_PLATE_GROUP 32               /* K: frames per aligned group of the evaluation rule */
+#define MC_PLATE_SLAB 256               /* rows of the mode table a workgroup stages at a time */
+#define MC_PLATE_MAX_PAIRS 68719476736  /* 2^36 */
+typedef struct {
+    uint32_t struct_size;    /* sizeof(mc_ir_plate) = 88 */
+    float size_m[2];         /* Lx, Ly: finite, [0.05, 10] */
+    float thickness_mm;      /* finite, [0.05, 50] */
+    float young_gpa;         /* finite, [0.1, 2000] */
+    float density;           /* kg/m^3: finite, [100, 30000] */
+    float poisson;           /* [0, 0.499] */
+    float driver_m[2];       /* strictly inside the plate */
+    float pickup_m[2][2];    /* pickup L (x, y), pickup R (x, y): strictly inside the plate */
+    float low_hz;            /* finite, [1, 100000] */
+    float high_hz;           /* 0 = min(20000, 0.45 rate); else finite, above low_hz and below rate / 2 */
+    float t60_s[2];          /* seconds towards 0 Hz and at damp_hz: 0 (no loss) or finite in [0.001, 1000]; s_1 >= s_0 */
+    float damp_hz;           /* finite, [10, 1000000] */
+    float gain;              /* finite, (0, 16] */
+    uint32_t reserved;       /* must be 0 */
+    uint64_t last;           /* E = last ? min(last, F) : F: frames at and after E get nothing from the plate */
+} mc_ir_plate;
+/* steel (200 GPa, 7850 kg/m^3, 0.3), 0.5 mm, 2.04 x 0.97 m (sides whose squares are in no rational ratio: exactly 2 x 1 m makes
+ * many modes coincide; commensurate sides stay legal), driver (0.83, 0.41), pickups (0.31, 0.67) and (1.57, 0.29), off every
+ * low-order nodal line, low_hz 20, high_hz 0, t60 4 s at 0 Hz and 1 s at damp_hz 10000, gain 1, last 0 */
+void mc_default_ir_plate(mc_ir_plate *p);
+/* mc_synth_ir_room(..., room = NULL, ...) with the plate's term added to the generated frames; with plate NULL it is that call
+ * bit for bit.  A plate and a room in one load are not offered.  Checked in this order, all before the engine or the device is
+ * touched (MC_ERR_ARG, the message names the field, the engine stays as it was): synth as by mc_synth_ir; the plate field by
+ * field in the struct's order; then synth->rate, which must be set ("the plate needs the session's rate"), high_hz below
+ * rate / 2, M, the bound on the sum and the work cap (the message says by how much it is exceeded); tail as by mc_load_ir_tail,
+ * with F' after F; damp, eq and shape, then e, idx and nframes as by mc_synth_ir_room. */
+int mc_synth_ir_plate(mc_engine *e, uint64_t idx, uint64_t nframes, const mc_ir_synth *synth, const mc_ir_plate *plate,
+                      const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp, const mc_ir_tail *tail);
+/* What a load of `frames` frames at `rate` would do with `plate`: out = {M, the lowest and the highest kept mode (Hz), kappa
+ * (m^2/s), Weyl's modal density Lx Ly / (2 kappa) (modes per Hz), T60 = 3 ln 10 / sigma at low_hz and at the highest kept mode
+ * (s; 0 = no loss), the pairs E M}.  The plate is checked as by mc_synth_ir_plate, with rate in [8000, 384000] and frames in
+ * [1, 2^24].  Host arithmetic only: no engine and no HIP call. */
+int mc_ir_plate_plan(const mc_ir_plate *plate, uint32_t rate, uint64_t frames, double out[8]);
+/* Rows first .. first + count - 1 of the mode table as {m, n, f (Hz), sigma (1/s), a_L, a_R} in double, six numbers a row: the
+ * table a load uploads, made by the one function that makes it there.  first + count may not exceed M.  The plate is checked
+ * as by mc_ir_plate_plan (the work cap aside: no frames are involved).  Host arithmetic only. */
+int mc_ir_plate_modes(const mc_ir_plate *plate, uint32_t rate, uint64_t first, uint64_t count, double *rows);
+/* out = {M, modes with a non-zero amplitude in L, in R, E, the lowest and the highest kept mode (Hz), kappa, 0}; MC_ERR_STATE
+ * unless the IR's last load had a plate */
+int mc_ir_plate_info(const mc_engine *e, uint64_t idx, double out[8]);
+
 int mc_num_irs(const mc_engine *e);
 /* out[0..3] = sum h_L, sum h_R, sum h_L(-1)^m, sum h_R(-1)^m of the truncated IR; out[4] = taps, out[5] = partitions */
 int mc_ir_info(const mc_engine *e, uint64_t idx, double out[6]);
