@@ -37,10 +37,21 @@ def unpack(z):
     return L, R
 
 
+def split(z):
+    """The true two-for-one split: the spectra of the real and of the imaginary part of the transformed signal, every bin
+    included (no Q1, no Q2)."""
+    zr = np.conj(np.roll(z[::-1], 1))  # conj(z[(n - k) % n])
+    return 0.5 * (z + zr), -0.5j * (z - zr)
+
+
 class RefCompatNp:
-    def __init__(self, fft_size, three_mult=True):
+    def __init__(self, fft_size, three_mult=True, linear=False):
+        """linear: plain linear convolution - `split` in place of `unpack` (the engine's compat = 0 without the Q8 cut, which
+        the caller keeps out of reach with taps + 255 + predelay <= fft_size)."""
         self.N = N = fft_size
         self.three_mult = three_mult
+        self.linear = linear
+        self.unpack = split if linear else unpack
         self.cc = [
             dict(select=0, predelay=0, speed=100, vsteps=0, dry=np.float32(0.5), wet=np.float32(0.5),
                  panDry=np.float32(0), panWet=np.float32(0), level=np.float32(1))
@@ -55,7 +66,7 @@ class RefCompatNp:
         n = min(len(lr), self.N - nframes)
         z = np.zeros(self.N, np.complex128)
         z[:n] = lr[:n, 0].astype(np.float64) + 1j * lr[:n, 1].astype(np.float64)
-        self.ir[idx] = unpack(np.fft.fft(z))
+        self.ir[idx] = self.unpack(np.fft.fft(z))
 
     def _interp(self, half):
         cc = self.cc[half]
@@ -64,6 +75,9 @@ class RefCompatNp:
         div = float(cc["vsteps"] + 5)
         for c in range(2):
             a = self.irfft[half][c]
+            if self.linear:  # every bin, the Nyquist bin included
+                a += (H[c] * float(cc["wet"]) - a) / div
+                continue
             s = np.arange(0, N // 2)
             vv = a[s] + (H[c][s] * float(cc["wet"]) - a[s]) / div
             a[s] = vv
@@ -86,7 +100,7 @@ class RefCompatNp:
         z[:n] = np.asarray(in1, np.float64) + 1j * np.asarray(in2, np.float64)
         self._interp(0)
         self._interp(1)
-        X1, X2 = unpack(np.fft.fft(z))
+        X1, X2 = self.unpack(np.fft.fft(z))
         gl = [pan_l(float(c0["panWet"])) * float(c0["level"]) / N, pan_l(float(c1["panWet"])) * float(c1["level"]) / N]
         gr = [pan_r(float(c0["panWet"])) * float(c0["level"]) / N, pan_r(float(c1["panWet"])) * float(c1["level"]) / N]
         out = []

@@ -13,119 +13,20 @@ whose RMS is about U; 1e-4 lies between.  Measured: DESIGN.md §2.5b.
 Every stream runs on past the end of the last response, and its last call starts where no window of any form reaches an
 impulse any more (a transform of silence is silence; a transform that holds an impulse leaves rounding noise where the exact
 result is zero): the last two blocks of that call must be exact zeros."""
-import os
-
 import numpy as np
 import pytest
 
 import tap_probe as tp
 from tap_probe import BLOCK, WARM
+from tap_probe_device import FUSED, OS, SPLIT, STREAM
+from tap_probe_device import engine as _engine
+from tap_probe_device import forms_or_skip as _forms_or_skip
+from tap_probe_device import irs as _irs
+from tap_probe_device import judge as _judge
+from tap_probe_device import layout as _layout
+from tap_probe_device import run_device as _run_device
 
 pytestmark = pytest.mark.gpu
-
-WORST_BAR = 1e-4
-# switches that CI legs set for the whole suite and that put another form (or another library) under every test
-SUITE_WIDE = [k for k in ("MCCONV_LIB", "MCCONV_FORM", "MCCONV_NO_PARK", "MCCONV_NO_SPIN", "MCCONV_TD_FFT") if os.environ.get(k)]
-STREAM, FUSED, SPLIT, OS = 0, 254, 255, 253
-
-
-def _irs(P, full=False):
-    """Two IRs of P partitions, the last one partial (and differently so) unless `full`."""
-    return [tp.probe_ir(BLOCK * P - (0 if full else 77), 1000 + 2 * P), tp.probe_ir(BLOCK * P - (0 if full else 130), 1001 + 2 * P)]
-
-
-def _layout(P, predelay, sizes, tail, *, lead=(), ramp=0, warm=None, extra=None, limit=8, seed=0, settle=True):
-    """The calls of a stream and its impulses.  lead: calls before anything else (an odd start); ramp: a call of that many blocks
-    inside the cold-start ramp with impulses of its own (forms that take per-slot gains); then silence in calls of `warm` blocks
-    until block WARM + P, so that every window after it carries one set of gains; then the calls `sizes` with impulses around
-    the last of them (tap_probe.place_impulses; extra(bounds) names further blocks); then calls of `tail` blocks until one
-    starts beyond the reach of the last impulse.  Returns (calls, impulses, the indices of `sizes` in calls)."""
-    pdb = -(-predelay // BLOCK)
-    calls, imp, pos = list(lead), [], sum(lead)
-    if ramp:
-        imp += tp.place_impulses([pos, pos + ramp], seed + 1, batch=0, extra=[pos + k for k in (1, 2, 5) if k < ramp - 1])
-        calls.append(ramp)
-        pos += ramp
-    if settle:
-        end = max(WARM + P, (max(n for _, n, _ in imp) // BLOCK + P + pdb + 2) if imp else 0)
-        while pos < end:
-            calls.append(warm or tail)
-            pos += calls[-1]
-    first = len(calls)
-    bounds = [pos]
-    for n in sizes:
-        bounds.append(bounds[-1] + n)
-    imp += tp.place_impulses(bounds, seed, first=pos, extra=extra(bounds) if extra else (), limit=limit)
-    calls += list(sizes)
-    pos = bounds[-1]
-    quiet = max(n for _, n, _ in imp) // BLOCK + P + pdb + 10  # (10: the fast-FIR forms reach up to 2^3 blocks further)
-    while True:
-        calls.append(tail)
-        pos += tail
-        if pos - tail >= quiet:
-            break
-    return calls, imp, list(range(first, first + len(sizes)))
-
-
-def _params(c, predelay):
-    for h in (0, 1):
-        c.cc[h].value.update(select=h, predelay=predelay, dry=0.0, wet=1.0, level=1.0, panWet=0.0, panDry=0.0, vsteps=0)
-
-
-def _engine(monkeypatch, env, n_ref, irs, predelay, max_batch, whole=True, **kw):
-    from cuda_audio_amd.engine import Convolution
-
-    for k in ("MCCONV_OS_MIN", "MCCONV_FFT2_WORK", "MCCONV_TAIL_FORM"):
-        monkeypatch.delenv(k, raising=False)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
-    kw.setdefault("stream_threshold", 8)
-    c = Convolution("tap", n_ref, max_batch=max_batch, compat=False, **kw)
-    for i, ir in enumerate(irs):
-        c.prepare(i, ir)
-        assert not whole or c.ir_info(i)["partitions"] == -(-ir.shape[0] // BLOCK)
-    _params(c, predelay)
-    return c
-
-
-def _run_device(monkeypatch, env, n_ref, irs, predelay, calls, x):
-    """The stream through process_device on 16-byte-aligned device buffers, call by call: the output, the form each call took
-    (kernel_stats' fast_levels, resident) and the overlap-save counters."""
-    import torch
-
-    c = _engine(monkeypatch, env, n_ref, irs, predelay, max(calls))
-    d_in = torch.from_numpy(x).to("cuda:0")
-    d_out = torch.full((2, x.shape[1]), 7.0, device="cuda:0")  # (not zeros: the trailing blocks have to be written)
-    torch.cuda.synchronize()
-    c.enable_kernel_timing(True)
-    forms, o = [], 0
-    for n in calls:
-        c.process_device(d_in[0, o * BLOCK:].data_ptr(), d_in[1, o * BLOCK:].data_ptr(), d_out[0, o * BLOCK:].data_ptr(), d_out[1, o * BLOCK:].data_ptr(), n)
-        c.sync()
-        ks = c.kernel_stats()
-        forms.append((ks["fast_levels"], ks["resident"]))
-        o += n
-    st = c.os_stats()
-    c.close()
-    return d_out.cpu().numpy(), forms, st
-
-
-def _forms_or_skip(ok, what):
-    if not ok:
-        if SUITE_WIDE:
-            pytest.skip(f"{SUITE_WIDE} puts another form under this case: {what}")
-        raise AssertionError(what)
-
-
-def _judge(tag, got, irs, imp, predelay, peak=0.4):
-    w = tp.want(irs, imp, got.shape[1], predelay)
-    r = tp.compare(got, w, irs, imp, predelay)
-    print(f"{tag}: {tp.describe(r)}; {len(imp)} impulses, peak {np.abs(w).max():.3f}, {got.shape[1] // BLOCK} blocks")
-    assert np.abs(w).max() < peak
-    assert np.abs(w[:, -2 * BLOCK:]).max() == 0
-    assert r["worst"] <= WORST_BAR, f"{tag}: {tp.describe(r)}"
-    assert not got[:, -2 * BLOCK:].any(), f"{tag}: the trailing blocks are not silent: {np.abs(got[:, -2 * BLOCK:]).max():.3e}"
-    return r
 
 
 def _device_case(monkeypatch, tag, env, n_ref, irs, predelay, calls, imp, probed, expect, peak=0.4):
