@@ -430,10 +430,6 @@ void unpark(mc_engine* e) {
         e->n_park_cancel++;
     }
 }
-int leave_jack_path(mc_engine* e) {
-    unpark(e);
-    return MC_OK;
-}
 
 hipError_t reset_stamps(mc_engine* e) {
     return hipMemset(e->d_stamps, 0, sizeof(unsigned long long) * 2 * MC_STAMP_WGS * kStampSlots);
@@ -491,10 +487,7 @@ int fence_post(mc_engine* e) {
 }
 
 int zero_state(mc_engine* e) {
-    {
-        int rc = leave_jack_path(e);
-        if (rc) return rc;
-    }
+        unpark(e);
     {
         int rc = drain_post(e);
         if (rc) return rc;
@@ -1388,7 +1381,7 @@ int retire_epoch(mc_engine* e, uint64_t new_delay, bool force = false) {
     if (e->sliced) return fail(MC_ERR_STATE, "predelay change / voice merge on a block-sliced engine (mc_reset first)");
     {
         int rc = drain_post(e);  // the rings below are rewritten
-        if (!rc) rc = leave_jack_path(e);
+        if (!rc) unpark(e);
         if (rc) return rc;
     }
     const uint64_t b0 = e->t_front, bs = e->epoch_b0, d_old = e->cur_delay;
@@ -1774,10 +1767,7 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
     if (T <= 0 || T > e->Tmax) return fail(MC_ERR_ARG, "nblocks %d outside [1, %d]", T, e->Tmax);
     if (e->pipe_count >= kPipe) return fail(MC_ERR_STATE, "%d batches already await mc_finish_batch_device", kPipe);
     if (T % e->pm) return fail(MC_ERR_ARG, "nblocks %d is not a multiple of the period (%d blocks)", T, e->pm);
-    {
-        int rc = leave_jack_path(e);
-        if (rc) return rc;
-    }
+        unpark(e);
     const bool slice = !(first == 0 && count == T);
     if (first < 0 || count <= 0 || first + count > T) return fail(MC_ERR_ARG, "slice [%d, %d) outside the batch of %d", first, first + count, T);
     if (slice && lin) return fail(MC_ERR_ARG, "a partition shard cannot be block-sliced");
@@ -2087,9 +2077,6 @@ int run_back(mc_engine* e, const float* d_in1, const float* d_in2, const float* 
 }
 
 
-// One JACK period with host buffers (Convolution::onProcess, conv.cu:287-466):
-// zero-copy I/O through mapped pinned memory, the streaming MAC over partitions
-// >= 1 (independent of the new block) and the fused k_tail1.
 // The cross-fade has converged and nothing is ramping: staging the next block's parameters now or at the next call
 // gives the same table entry (what lets a period be launched one call ahead, see process_one)
 bool params_steady(const mc_engine* e, const mc_cc_value (&cc)[2]) {
@@ -2111,54 +2098,178 @@ bool params_steady(const mc_engine* e, const mc_cc_value (&cc)[2]) {
     return true;
 }
 
-// The output of the period is on the host once its last kernel has published the sequence number: spin on the
-// mapped word (a JACK callback blocks here anyway; the reference blocks in cudaEventSynchronize, conv.cu:455);
-// fall back to a stream sync if it does not arrive in time.  Returns 1 when a parked tail says it gave up on its own.
+// ---- The parked-period protocol: what the period calls share (process_one for 256 frames, process_period_fused for 512 and
+// 1024, process_period for shards).  A tail kernel launched one call ahead parks on a doorbell; the next call rings it, tells it
+// to give up, or finds that it timed out and launches the period again.  Each piece is defined here once; the plans, the sweep's
+// destination, the tail launches and the order of the steps are the paths' own and stay in their functions.
+
+bool same_cc(const mc_cc_value& a, const mc_cc_value& b) {  // (field by field: the struct has padding)
+    return a.select == b.select && a.predelay == b.predelay && a.speed == b.speed && a.vsteps == b.vsteps && a.dry == b.dry &&
+           a.wet == b.wet && a.panDry == b.panDry && a.panWet == b.panWet && a.level == b.level;
+}
+
+// A period of `blocks` blocks into and out of the mapped host buffers (k_fwd / the tails read hd_io, the last kernel writes it)
+void period_to_mapped(mc_engine* e, const float* in1, const float* in2, int blocks) {
+    const size_t bytes = sizeof(float) * (size_t)blocks * MC_B, cap = (size_t)e->Thost * MC_B;
+    std::memcpy(e->h_io + 0 * cap, in1, bytes);
+    std::memcpy(e->h_io + 1 * cap, in2, bytes);
+}
+void copy_period_out(const mc_engine* e, float* outL, float* outR, int blocks) {
+    const size_t bytes = sizeof(float) * (size_t)blocks * MC_B, cap = (size_t)e->Thost * MC_B;
+    std::memcpy(outL, e->h_io + 2 * cap, bytes);
+    std::memcpy(outR, e->h_io + 3 * cap, bytes);
+}
+// The period where a tail launched now reads it: straight into device memory through the BAR (see mc_engine::d_bar), else mapped memory
+void copy_period_in(mc_engine* e, const float* in1, const float* in2, int blocks) {
+    if (!e->bar_io) return period_to_mapped(e, in1, in2, blocks);
+    const size_t bytes = sizeof(float) * (size_t)blocks * MC_B;
+    std::memcpy(e->d_bar + 16, in1, bytes);
+    std::memcpy(e->d_bar + 16 + 4 * MC_B, in2, bytes);
+    _mm_sfence();  // (write-combined stores: out of the buffers before a doorbell or a launch can refer to them)
+}
+
+// The sweep speculation: the sweep of block `blk` is summed in the shadow of the period before it, for the voices the plan of
+// that moment sweeps; the call that brings `blk` uses it if its own plan sweeps the same IR pairs (`vir`: the staged block's)
+void remember_sweep(mc_engine* e, const ActiveVoice* sweep, int nsweep, const int (&vir)[2][MC_MAXV], uint64_t blk) {
+    e->spec_valid = true;
+    e->spec_block = blk;
+    e->spec_nact = nsweep;
+    for (int a = 0; a < nsweep; a++) {
+        e->spec_vir[0][a] = vir[0][sweep[a].v];
+        e->spec_vir[1][a] = vir[1][sweep[a].v];
+    }
+}
+bool sweep_matches(const mc_engine* e, const ActiveVoice* sweep, int nsweep, const int (&vir)[2][MC_MAXV], uint64_t blk) {
+    bool ok = e->spec_valid && e->spec_block == blk && e->spec_nact == nsweep;
+    for (int a = 0; a < nsweep && ok; a++) ok = e->spec_vir[0][a] == vir[0][sweep[a].v] && e->spec_vir[1][a] == vir[1][sweep[a].v];
+    return ok;
+}
+
+// A period's sweep between two events and with in-kernel time stamps when kernel timing is on (the kernel the latency-mode
+// roofline is quoted on).  `launch(stamps)` makes the path's launches and returns the span of partitions they swept.
+template <class Launch>
+int stamped_sweep(mc_engine* e, int blocks, Launch&& launch) {
+    const bool timed = e->ktiming;
+    if (timed) {
+        if (e->kev_n >= kStampSlots) {
+            int rc = drain_kernel_events(e);
+            if (rc) return rc;
+        }
+        e->kev_blocks[e->kev_n] = (uint32_t)blocks;
+        e->kev_stamped[e->kev_n] = true;
+        HIP_TRY(hipEventRecord(e->kev[e->kev_n][0], e->stream));
+    }
+    const int swept = launch(timed ? e->d_stamps + (size_t)2 * MC_STAMP_WGS * e->kev_n : nullptr);
+    if (timed) {
+        HIP_TRY(hipEventRecord(e->kev[e->kev_n][1], e->stream));
+        e->kev_n++;
+        e->ks.resident = 0;
+        e->ks.partitions = (uint32_t)swept;
+    }
+    return MC_OK;
+}
+
+// This call's period of `pm` blocks was parked one call ahead, staged with the parameters this call sampled
+bool parked_hit(const mc_engine* e, const mc_cc_value (&cc)[2], int pm) {
+    return e->pre.valid && e->pre.pm == pm && e->pre.block == e->t_front && same_cc(cc[0], e->pre.cc[0]) && same_cc(cc[1], e->pre.cc[1]) &&
+           cc[0].predelay == e->cur_delay;
+}
+// The next period may be parked: the engine's own stream, a host that spins, and nothing moving
+bool may_park(const mc_engine* e, const mc_cc_value (&cc)[2]) {
+    return e->park && e->stream == e->own_stream && e->spin_wait && !e->pipelined && !e->ktiming && !e->half && params_steady(e, cc) &&
+           cc[0].predelay == e->cur_delay;
+}
+// The period starting at t_front has been launched with doorbell value `seq` (process_one adds what its kernel carries)
+void note_parked(mc_engine* e, const mc_cc_value (&cc)[2], int pm, unsigned seq, const Staged& st) {
+    e->pre.valid = true;
+    e->pre.pm = pm;
+    e->pre.block = e->t_front;
+    e->pre.seq = seq;
+    e->pre.cc[0] = cc[0];
+    e->pre.cc[1] = cc[1];
+    e->pre.st = st;
+    e->pre.carries_sweep = false;
+}
+
+// The output of the period is on the host once `arrived()` says so: spin on it (a JACK callback blocks here anyway; the
+// reference blocks in cudaEventSynchronize, conv.cu:455); fall back to a stream sync and `all_there()` if it does not arrive
+// in time.  Returns 1 when a parked tail says it gave up on its own.
+template <class Arrived, class AllThere>
+int spin_for_period(mc_engine* e, unsigned seq, Arrived&& arrived, AllThere&& all_there) {
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned spins = 0;
+    for (;;) {
+        if (arrived()) return MC_OK;
+        if (__atomic_load_n(e->h_exited, __ATOMIC_ACQUIRE) == seq) return 1;
+        if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(300)) {
+            unpark(e);  // (a kernel parked for the NEXT period would hold the stream until its own timeout)
+            HIP_TRY(hipStreamSynchronize(e->stream));
+            return all_there() ? MC_OK : fail(MC_ERR_HIP, "period did not complete");
+        }
+        __builtin_ia32_pause();
+    }
+}
+
+// The period's last kernel publishes its sequence number in a mapped word
 int wait_period(mc_engine* e, unsigned seq) {
     if (!e->spin_wait) {
         HIP_TRY(hipEventSynchronize(e->ev_tail));
         return MC_OK;
     }
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (__atomic_load_n(e->h_flag, __ATOMIC_ACQUIRE) != seq) {
-        if (__atomic_load_n(e->h_exited, __ATOMIC_ACQUIRE) == seq) return 1;
-        if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(300)) {
-            unpark(e);  // (a kernel parked for the NEXT period would hold the stream until its own timeout)
-            HIP_TRY(hipStreamSynchronize(e->stream));
-            if (__atomic_load_n(e->h_flag, __ATOMIC_ACQUIRE) != seq) return fail(MC_ERR_HIP, "period did not complete");
-            break;
-        }
-        __builtin_ia32_pause();
-    }
-    return MC_OK;
+    auto published = [&] { return __atomic_load_n(e->h_flag, __ATOMIC_ACQUIRE) == seq; };
+    return spin_for_period(e, seq, published, published);
 }
 
 // Tagged output (mc_engine::tio): the period's 512 output granules carry its sequence number; they are on the host when every
 // tag matches.  Same return values as wait_period.
 int wait_period_tagged(mc_engine* e, unsigned seq) {
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
     const int ngran = 2 * MC_B;
+    auto tagged = [&](int i) { return (unsigned)(__atomic_load_n(e->h_gran + i, __ATOMIC_ACQUIRE) >> 32) == seq; };
+    auto count_tagged = [&] {
+        int i = 0;
+        while (i < ngran && tagged(i)) i++;
+        return i;
+    };
     int first_missing = ngran - 1;  // (stores mostly arrive in order: watch the last one, then check them all)
-    for (;;) {
-        if ((unsigned)(__atomic_load_n(e->h_gran + first_missing, __ATOMIC_ACQUIRE) >> 32) == seq) {
-            int i = 0;
-            while (i < ngran && (unsigned)(__atomic_load_n(e->h_gran + i, __ATOMIC_ACQUIRE) >> 32) == seq) i++;
-            if (i == ngran) return MC_OK;
+    auto arrived = [&] {
+        while (tagged(first_missing)) {
+            const int i = count_tagged();
+            if (i == ngran) return true;
             first_missing = i;
-            continue;
         }
-        if (__atomic_load_n(e->h_exited, __ATOMIC_ACQUIRE) == seq) return 1;
-        if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(300)) {
-            unpark(e);
-            HIP_TRY(hipStreamSynchronize(e->stream));
-            for (int i = 0; i < ngran; i++)
-                if ((unsigned)(__atomic_load_n(e->h_gran + i, __ATOMIC_ACQUIRE) >> 32) != seq) return fail(MC_ERR_HIP, "period did not complete");
-            return MC_OK;
-        }
-        __builtin_ia32_pause();
+        return false;
+    };
+    return spin_for_period(e, seq, arrived, [&] { return count_tagged() == ngran; });
+}
+
+// The end of a period call: wait for period `seq`; when its parked tail gave up on its own (the host was away for more than
+// park_ms) the same period is launched the ordinary way, once, behind whatever is queued.  `relaunch(&seq)` is the path's own
+// step - unpark, copy, sweep and tail launch in the path's order - and leaves the new sequence number.
+template <class Relaunch>
+int await_period(mc_engine* e, int (*wait)(mc_engine*, unsigned), unsigned seq, bool relaunch_ok, Relaunch&& relaunch) {
+    for (;;) {
+        int rc = wait(e, seq);
+        if (rc == MC_OK) return MC_OK;
+        if (rc != 1) return rc;
+        if (!relaunch_ok) return fail(MC_ERR_HIP, "period did not complete");
+        relaunch_ok = false;
+        e->n_park_timeout++;
+        rc = relaunch(&seq);
+        if (rc) return rc;
     }
+}
+
+// The fused tail of a 512 / 1024-frame period (PM blocks): one workgroup, behind the sweep that filled d_part
+template <int PM, bool SELF_DROP>
+void launch_tailp(mc_engine* e, const Staged& st, const VoiceSet& vset, int nsum, uint64_t blk, unsigned seq, const TailDrop& tdp,
+                  const unsigned long long* bell, const float* drop) {
+    const size_t cap = (size_t)e->Thost * MC_B;
+    const float *pin1 = e->bar_io ? e->d_bar + 16 : e->hd_io + 0 * cap, *pin2 = e->bar_io ? e->d_bar + 16 + 4 * MC_B : e->hd_io + 1 * cap;
+    hipLaunchKernelGGL((k_tailp<PM, SELF_DROP>), dim3(1), dim3(256), 0, e->stream, pin1, pin2, vset, e->Pstride, e->d_fdl, e->d_slotgain,
+                       e->ring, (int)(blk & (uint64_t)(e->ring - 1)), e->d_part, nsum, st.d_ptab, e->d_seg, e->sr, e->d_wet, e->wr, e->d_cring,
+                       e->rc, st.ctx.vs, 1.0 / (double)e->cfg.n_ref, (int)e->cfg.compat, (int64_t)blk, (int64_t)st.ctx.predelay,
+                       (int64_t)e->cfg.n_ref, e->hd_io + 2 * cap, e->hd_io + 3 * cap, e->d_tw, tdp, e->d_fdl16, e->hd_flag, seq,
+                       make_retired(e), bell, e->hd_exited, e->park_ticks, drop, nullptr, nullptr);
 }
 
 // One JACK period with host buffers (Convolution::onProcess, conv.cu:287-466): zero-copy I/O through mapped pinned
@@ -2186,16 +2297,6 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
     const auto tr0 = std::chrono::steady_clock::now();
 #endif
     const size_t cap = (size_t)e->Thost * MC_B;
-    auto copy_period_in = [&]() {  // the period where a tail launched now reads it
-        if (e->bar_io) {
-            std::memcpy(e->d_bar + 16, in1, sizeof(float) * MC_B);
-            std::memcpy(e->d_bar + 16 + 4 * MC_B, in2, sizeof(float) * MC_B);
-            _mm_sfence();  // (write-combined stores: out of the buffers before a doorbell or a launch can refer to them)
-        } else {
-            std::memcpy(e->h_io + 0 * cap, in1, sizeof(float) * MC_B);
-            std::memcpy(e->h_io + 1 * cap, in2, sizeof(float) * MC_B);
-        }
-    };
     mc_cc_value cc[2];
     {
         int rc = sample_params(e, cc);
@@ -2242,46 +2343,17 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
             HIP_TRY(hipMemsetAsync(dst, 0, sizeof(float4) * (size_t)MC_NB * pl.nsum, e->stream));
             return MC_OK;
         }
-        if (e->ktiming) {
-            if (e->kev_n >= kStampSlots) {
-                int rc = drain_kernel_events(e);
-                if (rc) return rc;
+        return stamped_sweep(e, 1, [&](unsigned long long* stamps) {
+            const int bslot0 = (int)(blk & (uint64_t)(e->ring - 1));
+            int swept = 0;
+            for (int a = 0; a < pl.nsweep; a++) {
+                ActiveVoice av = pl.sweep[a];
+                av.uniform = sweep_uniform(av, pl.hi[a], blk);
+                launch_mac_stream(e, e->stream, av, pl.lo[a], pl.hi[a], 1, bslot0, pl.nsum, a * kNchunk, dst, stamps);
+                swept = std::max(swept, pl.hi[a] - (pl.lo[a] == 2 ? 0 : pl.lo[a]));
             }
-            e->kev_blocks[e->kev_n] = 1;
-            e->kev_stamped[e->kev_n] = true;
-            HIP_TRY(hipEventRecord(e->kev[e->kev_n][0], e->stream));
-        }
-        unsigned long long* stamps = e->ktiming ? e->d_stamps + (size_t)2 * MC_STAMP_WGS * e->kev_n : nullptr;
-        const int bslot0 = (int)(blk & (uint64_t)(e->ring - 1));
-        int swept = 0;
-        for (int a = 0; a < pl.nsweep; a++) {
-            ActiveVoice av = pl.sweep[a];
-            av.uniform = sweep_uniform(av, pl.hi[a], blk);
-            launch_mac_stream(e, e->stream, av, pl.lo[a], pl.hi[a], 1, bslot0, pl.nsum, a * kNchunk, dst, stamps);
-            swept = std::max(swept, pl.hi[a] - (pl.lo[a] == 2 ? 0 : pl.lo[a]));
-        }
-        if (e->ktiming) {
-            HIP_TRY(hipEventRecord(e->kev[e->kev_n][1], e->stream));
-            e->kev_n++;
-            e->ks.resident = 0;
-            e->ks.partitions = (uint32_t)swept;
-        }
-        return MC_OK;
-    };
-    auto remember_sweep = [&](const Plan& pl, const Staged& st, uint64_t blk) {
-        e->spec_valid = true;
-        e->spec_block = blk;
-        e->spec_nact = pl.nsweep;
-        for (int a = 0; a < pl.nsweep; a++) {
-            e->spec_vir[0][a] = st.ctx.vir[0][pl.sweep[a].v];
-            e->spec_vir[1][a] = st.ctx.vir[1][pl.sweep[a].v];
-        }
-    };
-    auto sweep_matches = [&](const Plan& pl, const Staged& st, uint64_t blk) {
-        bool ok = e->spec_valid && e->spec_block == blk && e->spec_nact == pl.nsweep;
-        for (int a = 0; a < pl.nsweep && ok; a++)
-            ok = e->spec_vir[0][a] == st.ctx.vir[0][pl.sweep[a].v] && e->spec_vir[1][a] == st.ctx.vir[1][pl.sweep[a].v];
-        return ok;
+            return swept;
+        });
     };
     int prep_rc = MC_OK;  // first failure of prepare_drop_fft inside tail_args (checked behind every launch that used it)
     auto tail_args = [&](const Staged& st, const Plan& pl, uint64_t blk, unsigned seq, bool parked) {
@@ -2347,13 +2419,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
     bool relaunch_ok = false;  // (a parked period that gave up on its own can be launched again as it was staged)
     Staged st_now;
     Plan pl_now;
-    auto same_cc = [](const mc_cc_value& a, const mc_cc_value& b) {  // (field by field: the struct has padding)
-        return a.select == b.select && a.predelay == b.predelay && a.speed == b.speed && a.vsteps == b.vsteps && a.dry == b.dry &&
-               a.wet == b.wet && a.panDry == b.panDry && a.panWet == b.panWet && a.level == b.level;
-    };
-    const bool hit = e->pre.valid && e->pre.pm == 1 && e->pre.block == e->t_front && same_cc(cc[0], e->pre.cc[0]) &&
-                     same_cc(cc[1], e->pre.cc[1]) && cc[0].predelay == e->cur_delay;
-    if (hit) {
+    if (parked_hit(e, cc, 1)) {
         my_seq = e->pre.seq;
         if (e->tio) {
             // tagged input: the period as granules {sample, sequence number} straight into device memory - every lane of the
@@ -2369,7 +2435,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
             }
             _mm_sfence();
         } else {
-            copy_period_in();
+            copy_period_in(e, in1, in2, 1);
             ring_bell(e, my_seq, 0);
         }
         e->pre.valid = false;
@@ -2389,7 +2455,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
         }
     } else {
         unpark(e);
-        copy_period_in();
+        copy_period_in(e, in1, in2, 1);
         {
             int rc = drain_post(e);
             if (!rc) rc = retire_epoch(e, cc[0].predelay);
@@ -2397,7 +2463,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
             if (rc) return rc;
         }
         make_plan(st_now, pl_now);
-        if (!sweep_matches(pl_now, st_now, e->t_front)) {
+        if (!sweep_matches(e, pl_now.sweep, pl_now.nsweep, st_now.ctx.vir, e->t_front)) {
             int rc = launch_sweep(pl_now, e->t_front);
             if (rc) return rc;
         }
@@ -2416,8 +2482,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
     // slot carries its own gains, so it stays exact under any parameter change except a change of the sounding IR set
     // or an IR reload, which the next call checks)
     bool parked_next = false;
-    if (e->park && e->stream == e->own_stream && e->spin_wait && !e->pipelined && !e->ktiming && !e->half &&
-        params_steady(e, cc) && cc[0].predelay == e->cur_delay) {
+    if (may_park(e, cc)) {
         Staged st_next;
         int rc = stage_params(e, 1, cc, &st_next);  // (steady: advancing the cross-fade by a block changes nothing)
         if (rc) return rc;
@@ -2425,10 +2490,10 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
         make_plan(st_next, pl_next);
         if (st_next.ctx.pstride == 0 && pl_next.nsweep <= 1 && std::memcmp(&st_next.first, &st_now.first, sizeof(BlockParams)) == 0) {
             // the sweep of the period about to be parked, unless the kernel ahead of it already carries it
-            if (!sweep_matches(pl_next, st_next, e->t_front)) {
+            if (!sweep_matches(e, pl_next.sweep, pl_next.nsweep, st_next.ctx.vir, e->t_front)) {
                 rc = launch_sweep(pl_next, e->t_front);
                 if (rc) return rc;
-                remember_sweep(pl_next, st_next, e->t_front);
+                remember_sweep(e, pl_next.sweep, pl_next.nsweep, st_next.ctx.vir, e->t_front);
             }
             const unsigned seq = ++e->flag_seq;
             TailArgs A = tail_args(st_next, pl_next, e->t_front, seq, true);
@@ -2476,13 +2541,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
             else
                 hipLaunchKernelGGL(k_jack<false>, grid, dim3(TAIL1_THREADS), 0, e->stream, A, S);
             HIP_TRY(hipGetLastError());
-            e->pre.valid = true;
-            e->pre.pm = 1;
-            e->pre.block = e->t_front;
-            e->pre.seq = seq;
-            e->pre.cc[0] = cc[0];
-            e->pre.cc[1] = cc[1];
-            e->pre.st = st_next;
+            note_parked(e, cc, 1, seq, st_next);
             e->pre.carries_sweep = pl_next.nsweep == 1;
             if (pl_next.nsweep == 1) {
                 e->pre.carried_vir[0] = st_next.ctx.vir[0][pl_next.sweep[0].v];
@@ -2498,37 +2557,32 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
         if (pl.nsweep && !(e->spec_valid && e->spec_block == e->t_front)) {
             int rc = launch_sweep(pl, e->t_front);
             if (rc) return rc;
-            remember_sweep(pl, st, e->t_front);
+            remember_sweep(e, pl.sweep, pl.nsweep, st.ctx.vir, e->t_front);
         }
     }
 #ifdef MC_JACK_TRACE
     const auto tr1 = std::chrono::steady_clock::now();
 #endif
-    // the output of THIS block is on the host once its tail has published its sequence number.  Spin on the mapped word
-    // (a JACK callback blocks here anyway; the reference blocks in cudaEventSynchronize, conv.cu:455).
-    for (;;) {
-        int rc = e->tio ? wait_period_tagged(e, my_seq) : wait_period(e, my_seq);
-        if (rc == MC_OK) break;
-        if (rc != 1) return rc;
-        // the parked tail gave up on its own (the host was away for more than park_ms): the same period, launched the
-        // ordinary way behind whatever is queued
-        if (!relaunch_ok) return fail(MC_ERR_HIP, "period did not complete");
-        relaunch_ok = false;
-        e->n_park_timeout++;
+    // the output of THIS block is on the host once its tail has published its sequence number (await_period).  When the
+    // parked tail gave up on its own, the same period is launched the ordinary way behind whatever is queued:
+    auto relaunch = [&](unsigned* seq) -> int {
         unpark(e);  // (the kernel parked for the period after this one must not run before it)
-        copy_period_in();  // (a tail launched now reads the plain copy of the period)
+        copy_period_in(e, in1, in2, 1);  // (a tail launched now reads the plain copy of the period)
         // That kernel (launched above, behind a tail that had already left the stream) ran at once: the sweep it carries - the
         // one of the period after next - went into the partial-sum buffer of THIS period (same parity) and read a delay line
         // without this period's block.  unpark() has forgotten it; this period's own partial sums are summed again, on the
         // same stream behind the stray sweep.
-        {
-            int rc2 = launch_sweep(pl_now, e->t_front - 1);
-            if (rc2) return rc2;
-        }
-        my_seq = ++e->flag_seq;
-        hipLaunchKernelGGL(k_tail1, dim3(1), dim3(TAIL1_THREADS), 0, e->stream, tail_args(st_now, pl_now, e->t_front - 1, my_seq, false));
+        int rc = launch_sweep(pl_now, e->t_front - 1);
+        if (rc) return rc;
+        *seq = ++e->flag_seq;
+        hipLaunchKernelGGL(k_tail1, dim3(1), dim3(TAIL1_THREADS), 0, e->stream, tail_args(st_now, pl_now, e->t_front - 1, *seq, false));
         if (prep_rc) return prep_rc;
         HIP_TRY(hipGetLastError());
+        return MC_OK;
+    };
+    {
+        int rc = await_period(e, e->tio ? wait_period_tagged : wait_period, my_seq, relaunch_ok, relaunch);
+        if (rc) return rc;
     }
 #ifdef MC_JACK_TRACE
     const auto tr2 = std::chrono::steady_clock::now();
@@ -2540,8 +2594,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
             std::memcpy(outR + i, &b, 4);
         }
     } else {
-        std::memcpy(outL, e->h_io + 2 * cap, sizeof(float) * MC_B);
-        std::memcpy(outR, e->h_io + 3 * cap, sizeof(float) * MC_B);
+        copy_period_out(e, outL, outR, 1);
     }
 #ifdef MC_JACK_TRACE
     {
@@ -2668,9 +2721,8 @@ int process_period(mc_engine* e, const float* in1, const float* in2, float* outL
         if (rc) return rc;
     }
     const int T = e->pm;
-    const size_t bytes = (size_t)T * MC_B * sizeof(float), cap = (size_t)e->Thost * MC_B;
-    std::memcpy(e->h_io + 0 * cap, in1, bytes);
-    std::memcpy(e->h_io + 1 * cap, in2, bytes);
+    const size_t cap = (size_t)e->Thost * MC_B;
+    period_to_mapped(e, in1, in2, T);
     const bool was_piped = e->pipelined;
     e->pipelined = false;  // a period is finished inside this call
     int rc = run_front(e, e->hd_io + 0 * cap, e->hd_io + 1 * cap, T, nullptr, 0, T);
@@ -2680,8 +2732,7 @@ int process_period(mc_engine* e, const float* in1, const float* in2, float* outL
     if (!e->spin_wait) HIP_TRY(hipEventRecord(e->ev_tail, e->stream));
     rc = wait_period(e, e->flag_seq);
     if (rc) return rc;
-    std::memcpy(outL, e->h_io + 2 * cap, bytes);
-    std::memcpy(outR, e->h_io + 3 * cap, bytes);
+    copy_period_out(e, outL, outR, T);
     return MC_OK;
 }
 
@@ -2694,18 +2745,6 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
     if (e->pipe_count) return fail(MC_ERR_STATE, "a sharded batch is still pending");
     if (e->sliced) return fail(MC_ERR_STATE, "single-period call on a block-sliced engine (mc_reset first)");
     const int pm = e->pm;
-    const size_t bytes = (size_t)pm * MC_B * sizeof(float), cap = (size_t)e->Thost * MC_B;
-    const float *pin1 = e->bar_io ? e->d_bar + 16 : e->hd_io + 0 * cap, *pin2 = e->bar_io ? e->d_bar + 16 + 4 * MC_B : e->hd_io + 1 * cap;
-    auto copy_period_in = [&]() {  // the period where a tail launched now reads it
-        if (e->bar_io) {  // straight into device memory through the BAR (see mc_engine::d_bar)
-            std::memcpy(e->d_bar + 16, in1, bytes);
-            std::memcpy(e->d_bar + 16 + 4 * MC_B, in2, bytes);
-            _mm_sfence();
-        } else {
-            std::memcpy(e->h_io + 0 * cap, in1, bytes);
-            std::memcpy(e->h_io + 1 * cap, in2, bytes);
-        }
-    };
     mc_cc_value cc[2];
     {
         int rc = sample_params(e, cc);
@@ -2738,56 +2777,25 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
     };
     // partitions >= pm of the pm blocks starting at `blk` pair only with blocks before blk
     auto launch_mac = [&](const PPlan& pl, uint64_t blk) -> int {
-        const bool timed = e->ktiming;
-        if (timed) {
-            if (e->kev_n >= kStampSlots) {
-                int rc = drain_kernel_events(e);
-                if (rc) return rc;
+        return stamped_sweep(e, pm, [&](unsigned long long* stamps) {
+            const int bslot0 = (int)(blk & (uint64_t)(e->ring - 1));
+            int swept = 0;
+            for (int a = 0; a < pl.nsweep; a++) {
+                ActiveVoice av = pl.sweep[a];
+                av.uniform = e->gain_change_block[av.v] + (uint64_t)pl.hi[a] <= blk && e->gain_change_block[av.v] < blk;
+                launch_mac_stream(e, e->stream, av, pm, pl.hi[a], pm, bslot0, pl.nsum, a * kNchunk, nullptr, stamps);
+                swept = std::max(swept, pl.hi[a]);
             }
-            e->kev_blocks[e->kev_n] = (uint32_t)pm;
-            e->kev_stamped[e->kev_n] = true;
-            HIP_TRY(hipEventRecord(e->kev[e->kev_n][0], e->stream));
-        }
-        unsigned long long* stamps = timed ? e->d_stamps + (size_t)2 * MC_STAMP_WGS * e->kev_n : nullptr;
-        const int bslot0 = (int)(blk & (uint64_t)(e->ring - 1));
-        int swept = 0;
-        for (int a = 0; a < pl.nsweep; a++) {
-            ActiveVoice av = pl.sweep[a];
-            av.uniform = e->gain_change_block[av.v] + (uint64_t)pl.hi[a] <= blk && e->gain_change_block[av.v] < blk;
-            launch_mac_stream(e, e->stream, av, pm, pl.hi[a], pm, bslot0, pl.nsum, a * kNchunk, nullptr, stamps);
-            swept = std::max(swept, pl.hi[a]);
-        }
-        if (timed) {
-            HIP_TRY(hipEventRecord(e->kev[e->kev_n][1], e->stream));
-            e->kev_n++;
-            e->ks.resident = 0;
-            e->ks.partitions = (uint32_t)swept;
-        }
-        return MC_OK;
+            return swept;
+        });
     };
     auto sweep_or_zero = [&](const PPlan& pl, uint64_t blk) -> int {
         if (pl.nsweep) return launch_mac(pl, blk);
         HIP_TRY(hipMemsetAsync(e->d_part, 0, sizeof(float4) * (size_t)pm * MC_NB * pl.nsum, e->stream));
         return MC_OK;
     };
-    auto remember_sweep = [&](const PPlan& pl, const Staged& st, uint64_t blk) {
-        e->spec_valid = true;
-        e->spec_block = blk;
-        e->spec_nact = pl.nsweep;
-        for (int a = 0; a < pl.nsweep; a++) {
-            e->spec_vir[0][a] = st.ctx.vir[0][pl.sweep[a].v];
-            e->spec_vir[1][a] = st.ctx.vir[1][pl.sweep[a].v];
-        }
-    };
-    auto sweep_matches = [&](const PPlan& pl, const Staged& st, uint64_t blk) {
-        bool ok = e->spec_valid && e->spec_block == blk && e->spec_nact == pl.nsweep;
-        for (int a = 0; a < pl.nsweep && ok; a++)
-            ok = e->spec_vir[0][a] == st.ctx.vir[0][pl.sweep[a].v] && e->spec_vir[1][a] == st.ctx.vir[1][pl.sweep[a].v];
-        return ok;
-    };
     int prep_rc = MC_OK;  // first failure of prepare_drop_fft inside launch_tail (checked behind every call)
     auto launch_tail = [&](const Staged& st, const PPlan& pl, uint64_t blk, unsigned seq, bool parked) {
-        const int slot0 = (int)(blk & (uint64_t)(e->ring - 1));
         const unsigned long long* bell = parked ? (e->bar_io ? reinterpret_cast<unsigned long long*>(e->d_bar) : e->hd_bell) : nullptr;
         {
             const int r = prepare_drop_fft(e, st.ctx.vir, st.ctx.predelay);
@@ -2798,26 +2806,9 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
         const bool self_drop = parked && tdp.on && tdp.fft;
         const float* drop = self_drop ? e->d_drop[(blk / (uint64_t)e->pm) & 1] : launch_drop_period(e, tdp, blk, st.ctx.predelay);
         if (self_drop) e->n_drop_carried++;
-#define MC_LAUNCH_TAILP(PM)                                                                                                  \
-    if (self_drop) MC_LAUNCH_TAILP_(PM, true); else MC_LAUNCH_TAILP_(PM, false)
-#define MC_LAUNCH_TAILP_(PM, SD)                                                                                                  \
-    hipLaunchKernelGGL((k_tailp<PM, SD>), dim3(1), dim3(256), 0, e->stream, pin1, pin2, pl.vset, e->Pstride, e->d_fdl, e->d_slotgain, \
-                       e->ring, slot0, e->d_part, pl.nsum, st.d_ptab, e->d_seg, e->sr, e->d_wet, e->wr, e->d_cring, e->rc,    \
-                       st.ctx.vs, 1.0 / (double)e->cfg.n_ref, (int)e->cfg.compat, (int64_t)blk, (int64_t)st.ctx.predelay,     \
-                       (int64_t)e->cfg.n_ref, e->hd_io + 2 * cap, e->hd_io + 3 * cap, e->d_tw,                                \
-                       tdp, e->d_fdl16, e->hd_flag, seq, make_retired(e), bell,     \
-                       e->hd_exited, e->park_ticks, drop, nullptr, nullptr)
-        if (pm == 2) {
-            MC_LAUNCH_TAILP(2);
-        } else {
-            MC_LAUNCH_TAILP(4);
-        }
-#undef MC_LAUNCH_TAILP
-#undef MC_LAUNCH_TAILP_
-    };
-    auto same_cc = [](const mc_cc_value& a, const mc_cc_value& b) {  // (field by field: the struct has padding)
-        return a.select == b.select && a.predelay == b.predelay && a.speed == b.speed && a.vsteps == b.vsteps && a.dry == b.dry &&
-               a.wet == b.wet && a.panDry == b.panDry && a.panWet == b.panWet && a.level == b.level;
+        auto* launch = pm == 2 ? (self_drop ? launch_tailp<2, true> : launch_tailp<2, false>)
+                               : (self_drop ? launch_tailp<4, true> : launch_tailp<4, false>);
+        launch(e, st, pl.vset, pl.nsum, blk, seq, tdp, bell, drop);
     };
 
     // ---- this period: a parked tail staged with the same parameters, or the ordinary launches
@@ -2825,11 +2816,9 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
     PPlan pl;
     unsigned my_seq = 0;
     bool relaunch_ok = false;
-    const bool hit = e->pre.valid && e->pre.pm == pm && e->pre.block == e->t_front && same_cc(cc[0], e->pre.cc[0]) &&
-                     same_cc(cc[1], e->pre.cc[1]) && cc[0].predelay == e->cur_delay;
-    if (hit) {
+    if (parked_hit(e, cc, pm)) {
         my_seq = e->pre.seq;
-        copy_period_in();
+        copy_period_in(e, in1, in2, pm);
         ring_bell(e, my_seq, 0);
         e->pre.valid = false;
         e->n_park_hit++;
@@ -2839,14 +2828,14 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
         e->spec_valid = false;  // (its sweep has been consumed)
     } else {
         int rc = drain_post(e);
-        if (!rc) rc = leave_jack_path(e);
-        copy_period_in();
+        if (!rc) unpark(e);
+        copy_period_in(e, in1, in2, pm);
         if (!rc) rc = retire_epoch(e, cc[0].predelay);
         if (!rc) rc = stage_params(e, pm, cc, &st);
         if (rc) return rc;
         if (st.ctx.pstride != 0) return fail(MC_ERR_STATE, "the blocks of one period must share their parameters");
         make_pplan(st, pl);
-        if (!sweep_matches(pl, st, e->t_front)) {
+        if (!sweep_matches(e, pl.sweep, pl.nsweep, st.ctx.vir, e->t_front)) {
             rc = sweep_or_zero(pl, e->t_front);
             if (rc) return rc;
         }
@@ -2866,17 +2855,16 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
     if (pl.nsweep) {
         int rc = launch_mac(pl, e->t_front);
         if (rc) return rc;
-        remember_sweep(pl, st, e->t_front);
+        remember_sweep(e, pl.sweep, pl.nsweep, st.ctx.vir, e->t_front);
     }
-    if (e->park && e->stream == e->own_stream && e->spin_wait && !e->pipelined && !e->ktiming && !e->half &&
-        params_steady(e, cc) && cc[0].predelay == e->cur_delay) {
+    if (may_park(e, cc)) {
         Staged st_next;
         int rc = stage_params(e, pm, cc, &st_next);  // (steady: advancing the cross-fade by a call changes nothing)
         if (rc) return rc;
         PPlan pl_next;
         make_pplan(st_next, pl_next);
         if (st_next.ctx.pstride == 0 && std::memcmp(&st_next.first, &st.first, sizeof(BlockParams)) == 0 &&
-            (pl_next.nsweep == 0 || sweep_matches(pl_next, st_next, e->t_front))) {
+            (pl_next.nsweep == 0 || sweep_matches(e, pl_next.sweep, pl_next.nsweep, st_next.ctx.vir, e->t_front))) {
             if (!pl_next.nsweep) {
                 rc = sweep_or_zero(pl_next, e->t_front);
                 if (rc) return rc;
@@ -2885,38 +2873,29 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
             launch_tail(st_next, pl_next, e->t_front, seq, true);
             if (prep_rc) return prep_rc;
             HIP_TRY(hipGetLastError());
-            e->pre.valid = true;
-            e->pre.pm = pm;
-            e->pre.block = e->t_front;
-            e->pre.seq = seq;
-            e->pre.cc[0] = cc[0];
-            e->pre.cc[1] = cc[1];
-            e->pre.st = st_next;
-            e->pre.carries_sweep = false;
+            note_parked(e, cc, pm, seq, st_next);
         }
     }
-    for (;;) {
-        int rc = wait_period(e, my_seq);
-        if (rc == MC_OK) break;
-        if (rc != 1) return rc;
-        copy_period_in();  // (a tail launched now reads the plain copy of the period)
-        // the parked tail gave up on its own (the host was away for more than park_ms): the same period the ordinary way.
-        // What was queued behind it worked on a delay line without this period: the next period's parked tail is told to
-        // give up, its sweep is forgotten, and this period's own partial sums are summed again (the sweep behind overwrote them)
-        if (!relaunch_ok) return fail(MC_ERR_HIP, "period did not complete");
-        relaunch_ok = false;
-        e->n_park_timeout++;
+    // When the parked tail gave up on its own, the same period is launched the ordinary way.  What was queued behind it worked
+    // on a delay line without this period: the next period's parked tail is told to give up, its sweep is forgotten, and this
+    // period's own partial sums are summed again (the sweep behind overwrote them)
+    auto relaunch = [&](unsigned* seq) -> int {
+        copy_period_in(e, in1, in2, pm);  // (a tail launched now reads the plain copy of the period)
         unpark(e);
         e->spec_valid = false;
-        rc = sweep_or_zero(pl, e->t_front - (uint64_t)pm);
+        int rc = sweep_or_zero(pl, e->t_front - (uint64_t)pm);
         if (rc) return rc;
-        my_seq = ++e->flag_seq;
-        launch_tail(st, pl, e->t_front - (uint64_t)pm, my_seq, false);
+        *seq = ++e->flag_seq;
+        launch_tail(st, pl, e->t_front - (uint64_t)pm, *seq, false);
         if (prep_rc) return prep_rc;
         HIP_TRY(hipGetLastError());
+        return MC_OK;
+    };
+    {
+        int rc = await_period(e, wait_period, my_seq, relaunch_ok, relaunch);
+        if (rc) return rc;
     }
-    std::memcpy(outL, e->h_io + 2 * cap, bytes);
-    std::memcpy(outR, e->h_io + 3 * cap, bytes);
+    copy_period_out(e, outL, outR, pm);
     return MC_OK;
 }
 
@@ -3358,7 +3337,7 @@ struct ShapedTaps {
 int quiesce(mc_engine* e) {
     HIP_TRY(hipSetDevice(e->device));
     int rc = e->sf ? MC_OK : drain_post(e);
-    if (!rc && !e->sf) rc = leave_jack_path(e);
+    if (!rc && !e->sf) unpark(e);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     return MC_OK;
@@ -4747,7 +4726,7 @@ int mc_sync(mc_engine* e) {
     if (!e) return fail(MC_ERR_ARG, "null engine");
     HIP_TRY(hipSetDevice(e->device));
     int rc = drain_post(e);
-    if (!rc) rc = leave_jack_path(e);
+    if (!rc) unpark(e);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(e->stream));
     return MC_OK;
@@ -4773,7 +4752,7 @@ int mc_set_stream(mc_engine* e, void* s) {
     HIP_TRY(hipSetDevice(e->device));
     {
         int rc = drain_post(e);
-        if (!rc) rc = leave_jack_path(e);
+        if (!rc) unpark(e);
         if (rc) return rc;
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
@@ -4915,8 +4894,7 @@ int mc_debug_read(mc_engine* e, int which, uint64_t idx, void* dst, uint64_t off
         unsigned c[2] = {0, 0};
         if (off + bytes > sizeof(c)) return fail(MC_ERR_ARG, "read beyond the counters");
         if (e->d_tailform) {
-            int rc = leave_jack_path(e);
-            if (rc) return rc;
+            unpark(e);
             HIP_TRY(hipStreamSynchronize(e->stream));
             HIP_TRY(hipMemcpy(c, e->d_tailform, sizeof(c), hipMemcpyDeviceToHost));
         }
@@ -4947,8 +4925,7 @@ int mc_debug_read(mc_engine* e, int which, uint64_t idx, void* dst, uint64_t off
         case 20: {  // scale16 of IR idx (one float): a host-side word, read behind the stream like the copy it belongs to
             if (idx >= (uint64_t)(kMaxIrs + kMixIrs) || !e->irs[idx].d_H || !e->irs[idx].d_H16) return fail(MC_ERR_ARG, "IR not loaded");
             if (off + bytes > sizeof(float)) return fail(MC_ERR_ARG, "read beyond the scale");
-            int rc = leave_jack_path(e);
-            if (rc) return rc;
+            unpark(e);
             HIP_TRY(hipStreamSynchronize(e->stream));
             std::memcpy(dst, reinterpret_cast<const char*>(&e->irs[idx].scale16) + off, bytes);
             return MC_OK;
@@ -4970,10 +4947,7 @@ int mc_debug_read(mc_engine* e, int which, uint64_t idx, void* dst, uint64_t off
         default: return fail(MC_ERR_ARG, "unknown buffer %d", which);
     }
     if (off + bytes > cap) return fail(MC_ERR_ARG, "read beyond buffer (%llu + %llu > %llu)", (unsigned long long)off, (unsigned long long)bytes, (unsigned long long)cap);
-    {
-        int rc = leave_jack_path(e);
-        if (rc) return rc;
-    }
+        unpark(e);
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipMemcpy(dst, src + off, bytes, hipMemcpyDeviceToHost));
     return MC_OK;
