@@ -35,6 +35,7 @@ SYMBOLS = [
     "mc_default_ir_room", "mc_synth_ir_room", "mc_ir_room_info", "mc_ir_room_plan",
     "mc_default_ir_room_mics", "mc_synth_ir_room_mics", "mc_ir_room_mics_plan", "mc_ir_room_mics_info",
     "mc_default_ir_room_bands", "mc_synth_ir_room_bands", "mc_ir_room_bands_plan", "mc_ir_room_bands_info",
+    "mc_default_ir_room_head", "mc_synth_ir_room_head", "mc_ir_room_head_plan", "mc_ir_room_head_info",
     "mc_default_ir_plate", "mc_synth_ir_plate", "mc_ir_plate_plan", "mc_ir_plate_modes", "mc_ir_plate_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
@@ -466,6 +467,20 @@ class McIrRoomBands(C.Structure):
     ]
 
 
+class McIrRoomHead(C.Structure):
+    """mc_ir_room_head: the rigid-sphere listener that mc_synth_ir_room_head puts in the room in place of the receiver pair."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("radius_m", C.c_float),
+        ("facing_az_deg", C.c_float),
+        ("ear_deg", C.c_float),
+        ("shadow", C.c_float),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
 MC_PLATE_MAX_MODES = 1 << 18
 MC_PLATE_GROUP = 32
 MC_PLATE_SLAB = 256
@@ -641,6 +656,12 @@ def load():
                                          C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp), C.POINTER(McIrTail)]
     L.mc_ir_room_bands_plan.argtypes = [C.POINTER(McIrRoom), C.POINTER(McIrRoomBands), C.c_uint32, u64, C.POINTER(C.c_double)]
     L.mc_ir_room_bands_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_default_ir_room_head.argtypes = [C.POINTER(McIrRoomHead)]
+    L.mc_default_ir_room_head.restype = None
+    L.mc_synth_ir_room_head.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrRoom), C.POINTER(McIrRoomMics), C.POINTER(McIrRoomBands),
+                                        C.POINTER(McIrRoomHead), C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp), C.POINTER(McIrTail)]
+    L.mc_ir_room_head_plan.argtypes = [C.POINTER(McIrRoom), C.POINTER(McIrRoomHead), C.c_uint32, u64, C.POINTER(C.c_double)]
+    L.mc_ir_room_head_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_default_ir_plate.argtypes = [C.POINTER(McIrPlate)]
     L.mc_default_ir_plate.restype = None
     L.mc_synth_ir_plate.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrPlate), C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp),

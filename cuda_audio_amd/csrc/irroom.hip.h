@@ -74,6 +74,9 @@ struct RoomPlan {
     double bpow[6][MC_ROOM_MAX_ORDER + 2];  // bpow[w][j] = pow(beta[w], j), 0^0 = 1
     RoomMics m;         // mc_ir_room_mics, when `mics` is set
     double air;         // k_j of a band of mc_ir_room_bands, right behind m's fifteen numbers: the sixteenth; 0 = no factor
+    double head[8];     // mc_ir_room_head, when `headed` is set: the ear axes e_L, e_R, a and shadow (behind everything the
+    uint64_t shadow_at; // kernels without a head read); the shadow accumulator lies shadow_at words behind the plain one
+    uint32_t headed;
 };
 
 // g(cos) of a first-order pattern: exactly 1 for alpha = 1 (oma = 0), whatever the cosine
@@ -91,10 +94,22 @@ __host__ __device__ inline double2 room_factors(Get get, int c, double sx, doubl
     return make_double2(room_pattern(get(11), get(14), cs), room_pattern(get(9 + c), get(12 + c), cr));
 }
 
+// {g, th} of an ear whose axis is e for an arrival from p, d = |p|: the angle th between them and the path's excess over d in
+// units of the radius
+__host__ __device__ inline double2 room_ear(double ex, double ey, double ez, double px, double py, double pz, double d) {
+    const double cs = fmin(1.0, fmax(-1.0, room_dot(ex, ey, ez, px, py, pz) / d));
+    const double th = acos(cs);
+    return make_double2(cs >= 0.0 ? -cs : th - M_PI / 2, th);
+}
+
+// h = alpha - 1 of Brown and Duda's shelf at the angle th from the ear's axis
+__host__ __device__ inline double room_shadow(double shadow, double th) { return shadow * fma(0.95, cos(1.2 * th), 0.05); }
+
 // One launch over the lattice; gridDim.x * ROOM_THREADS / 64 waves stride over it 64 images at a time.  acc: p.A frames of two
 // int64, zero; kept: two zeroed counters.  MICS: p.mics is set, and an image's amplitude takes its factor gs gr.  AIR: p.air is
-// not 0, and b / d takes the factor exp2(-(d p.air)) before that.
-template <bool MICS, bool AIR>
+// not 0, and b / d takes the factor exp2(-(d p.air)) before that.  HEAD: p.headed is set, both receivers are the head's centre,
+// each ear has its own delay and shadow factor, and acc + p.shadow_at is a second accumulator as large as the first, zero too.
+template <bool MICS, bool AIR, bool HEAD = false>
 __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __restrict__ acc, unsigned* __restrict__ kept, RoomPlan p) {
     const unsigned lane = threadIdx.x & 63u;
     uint32_t wave = (blockIdx.x * ROOM_THREADS + threadIdx.x) >> 6;
@@ -107,7 +122,9 @@ __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __res
     // (v_readlane does not look at EXEC: the lanes that hold the numbers need not be among those that hold a kept image.)
     // The air constant travels the same way, as number 15, and with it the receivers' six coordinates, as numbers 16 to 21:
     // the double exp2 wants scalar registers for its constants as the sine does, and without those twelve back hipcc spills two.
-    const double mics = AIR && lane >= 16 && lane < 22                 ? (&p.rcv[0][0])[lane - 16]
+    // The head's eight numbers are numbers 22 to 29, and a head takes the receivers' coordinates from the lanes as the air does.
+    const double mics = HEAD && lane >= 22 && lane < 30                ? p.head[lane - 22]
+                        : (AIR || HEAD) && lane >= 16 && lane < 22     ? (&p.rcv[0][0])[lane - 16]
                         : (MICS && lane < 15) || (AIR && lane == 15) ? reinterpret_cast<const double*>(&p.m)[lane]
                                                                      : 0.0;
     const auto mic = [mics](int j) {
@@ -117,6 +134,7 @@ __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __res
         const uint64_t i = base + lane;
         long long k0[2] = {0, 0};
         double f[2] = {0.0, 0.0}, s[2] = {0.0, 0.0}, a[2] = {0.0, 0.0};  // (a stays 0 for a channel that is not kept)
+        double sh[2] = {0.0, 0.0};                                       // HEAD: a h, the shadow accumulator's amplitude
         bool keep[2] = {false, false};
         if (i < p.total) {
             const uint32_t cell = (uint32_t)(i >> 3);
@@ -125,17 +143,36 @@ __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __res
             double q[3], b = p.gain;
 #pragma unroll
             for (int ax = 0; ax < 3; ax++) q[ax] = (double)(1 - 2 * u[ax]) * p.src[ax] + (double)(2 * n[ax]) * p.size[ax];
-            double d[2], tau[2];
+            double d[2], tau[2], th[2] = {0.0, 0.0};
+            if (HEAD) {
+                const double px = q[0] - mic(16), py = q[1] - mic(17), pz = q[2] - mic(18);
+                d[0] = d[1] = sqrt(px * px + py * py + pz * pz);
+                // An ear's path is at most the radius shorter than d: an image that even so arrives a frame or more past E is
+                // kept by neither ear, and is pruned before any arc cosine.
+                if ((d[0] - mic(28)) * p.rate / p.speed < (double)p.E + 1.0) {
 #pragma unroll
-            for (int c = 0; c < 2; c++) {
-                const double px = q[0] - (AIR ? mic(16 + 3 * c) : p.rcv[c][0]), py = q[1] - (AIR ? mic(17 + 3 * c) : p.rcv[c][1]),
-                             pz = q[2] - (AIR ? mic(18 + 3 * c) : p.rcv[c][2]);
-                d[c] = sqrt(px * px + py * py + pz * pz);
-                tau[c] = d[c] * p.rate / p.speed;
-                const double fl = floor(tau[c]);
-                keep[c] = fl < (double)p.E;
-                k0[c] = (long long)fl;
-                f[c] = tau[c] - fl;
+                    for (int c = 0; c < 2; c++) {
+                        const double2 e = room_ear(mic(22 + 3 * c), mic(23 + 3 * c), mic(24 + 3 * c), px, py, pz, d[c]);
+                        th[c] = e.y;
+                        tau[c] = fma(mic(28), e.x, d[c]) * p.rate / p.speed;
+                        const double fl = floor(tau[c]);
+                        keep[c] = fl < (double)p.E;
+                        k0[c] = (long long)fl;
+                        f[c] = tau[c] - fl;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int c = 0; c < 2; c++) {
+                    const double px = q[0] - (AIR ? mic(16 + 3 * c) : p.rcv[c][0]), py = q[1] - (AIR ? mic(17 + 3 * c) : p.rcv[c][1]),
+                                 pz = q[2] - (AIR ? mic(18 + 3 * c) : p.rcv[c][2]);
+                    d[c] = sqrt(px * px + py * py + pz * pz);
+                    tau[c] = d[c] * p.rate / p.speed;
+                    const double fl = floor(tau[c]);
+                    keep[c] = fl < (double)p.E;
+                    k0[c] = (long long)fl;
+                    f[c] = tau[c] - fl;
+                }
             }
             if (keep[0] || keep[1]) {
 #pragma unroll
@@ -154,10 +191,11 @@ __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __res
                         s[c] = sin(M_PI * f[c]);
                         if (MICS) {  // (after the sine, whose constants want the scalar registers too: before it hipcc reserves scratch)
                             const double2 g = room_factors(mic, c, (double)(1 - 2 * u[0]), (double)(1 - 2 * u[1]), (double)(1 - 2 * u[2]),
-                                                           q[0] - (AIR ? mic(16 + 3 * c) : p.rcv[c][0]), q[1] - (AIR ? mic(17 + 3 * c) : p.rcv[c][1]),
-                                                           q[2] - (AIR ? mic(18 + 3 * c) : p.rcv[c][2]), d[c]);
+                                                           q[0] - (AIR || HEAD ? mic(16 + 3 * c) : p.rcv[c][0]), q[1] - (AIR || HEAD ? mic(17 + 3 * c) : p.rcv[c][1]),
+                                                           q[2] - (AIR || HEAD ? mic(18 + 3 * c) : p.rcv[c][2]), d[c]);
                             a[c] *= g.x * g.y;
                         }
+                        if (HEAD) sh[c] = a[c] * room_shadow(mic(29), th[c]);
                     }
             }
         }
@@ -172,6 +210,11 @@ __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __res
             const double aL = __shfl(a[0], j), aR = __shfl(a[1], j);
             const long long kj = ch ? k0R : k0L;
             const double fj = ch ? fR : fL, sj = ch ? sR : sL, aj = ch ? aR : aL;
+            double hj = 0.0;
+            if (HEAD) {
+                const double hL = __shfl(sh[0], j), hR = __shfl(sh[1], j);
+                hj = ch ? hR : hL;
+            }
             if (aj != 0.0) {
                 double w;
                 if (fj == 0.0) {
@@ -182,6 +225,10 @@ __global__ __launch_bounds__(ROOM_THREADS) void k_room(unsigned long long* __res
                 }
                 const long long v = llrint(aj * w * ROOM_Q), m = kj + k;
                 if (v != 0 && m >= 0 && (uint64_t)m < p.A) atomicAdd(&acc[2 * (uint64_t)m + ch], (unsigned long long)v);
+                if (HEAD && hj != 0.0) {  // (a h is 0 only where a is or the shadow is: the same taps of the same image)
+                    const long long vs = llrint(hj * w * ROOM_Q);
+                    if (vs != 0 && m >= 0 && (uint64_t)m < p.A) atomicAdd(&acc[p.shadow_at + 2 * (uint64_t)m + ch], (unsigned long long)vs);
+                }
             }
         }
     }
@@ -292,6 +339,52 @@ __global__ __launch_bounds__(SYN_THREADS) void k_synth_room_bands(float2* __rest
         if (head) x[0] = room_frame(p, 0, r);
         if (head + 2 * pairs < n) x[n - 1] = room_frame(p, n - 1, r);
     }
+}
+
+// the fixed high-pass of the head's shelf: K = tan(c / (a rate)), y = b0 v + s, s' = b1 v - a1 y
+struct RoomShelf {
+    double K, b0, b1, a1;
+};
+
+// One pass of the head's high-pass over F frames.  Its input is accS[m] 2^-40 below A (accS: A pairs of int64, 16-byte aligned)
+// or, with rS, rS[m] (the join of the bands' shadow accumulators), and 0 from A or F on.  st: double2 [gridDim.x * IEQ_THREADS],
+// k_eq_chunk's layout, which k_eq_carry scans: (s, 0).  FIX = false: from rest, the end states to st.  FIX = true: from the state
+// st holds, r[m] = S[m] + (m < A ? accP[m] 2^-40 : 0) or, with accP null, S[m] + r[m] (the join of the plain accumulators, in
+// place).  Frames at and past F read as zero and are not written.
+template <bool FIX>
+__global__ __launch_bounds__(IEQ_THREADS) void k_room_head(const longlong2* __restrict__ accS, const double2* __restrict__ rS, const longlong2* __restrict__ accP,
+                                                           uint64_t A, uint64_t F, RoomShelf c, double2* __restrict__ st, double2* r) {
+    const uint64_t entry = (uint64_t)blockIdx.x * IEQ_THREADS + threadIdx.x;
+    double s = FIX ? st[entry].x : 0.0;
+    chunk_walk<false, IEQ_TILE, double2>(
+        FIX,
+        [&](uint64_t g, double2& v) {
+            v = make_double2(0.0, 0.0);
+            if (rS) {
+                if (g < F) v = rS[g];
+            } else if (g < A) {
+                const longlong2 a = accS[g];
+                v = make_double2((double)a.x * (1.0 / ROOM_Q), (double)a.y * (1.0 / ROOM_Q));
+            }
+        },
+        [&](double& tap, uint64_t) {
+            const double v = tap, y = c.b0 * v + s;
+            s = c.b1 * v - c.a1 * y;
+            if (FIX) tap = y;
+        },
+        [&](uint64_t g, double2 v) {
+            if (g < F) {
+                double2 plain = make_double2(0.0, 0.0);
+                if (!accP) {
+                    plain = r[g];
+                } else if (g < A) {
+                    const longlong2 a = accP[g];
+                    plain = make_double2((double)a.x * (1.0 / ROOM_Q), (double)a.y * (1.0 / ROOM_Q));
+                }
+                r[g] = make_double2(v.x + plain.x, v.y + plain.y);
+            }
+        });
+    if (!FIX) st[entry] = make_double2(s, 0.0);
 }
 
 // -- host ------------------------------------------------------------------------------------------------------------
@@ -603,12 +696,142 @@ inline RoomBands room_bands_plan(const RoomPlan& base, const mc_ir_room& r, cons
     return rb;
 }
 
+// frames up to which the lattice of order N is complete for a head of radius a: an image outside it is at least 2 N min(L) away
+// and its sound reaches an ear at most a / c before d / c
+inline double room_head_complete(const mc_ir_room& r, double a, uint32_t rate, double N) {
+    return std::floor((2.0 * N * room_min_size(r) - a) * (double)rate / (double)r.speed);
+}
+
+// the order `order` 0 stands for with a head: the smallest N whose lattice is complete up to E (as a double: it may lie above
+// MC_ROOM_MAX_ORDER)
+inline double room_head_auto_order(const mc_ir_room& r, double a, uint32_t rate, uint64_t F) {
+    double N = std::max(1.0, room_auto_order(r, rate, F));  // (the room's own is never too large, and at most one too small)
+    while (room_head_complete(r, a, rate, N) < (double)room_last(r, F)) N += 1.0;
+    return N;
+}
+
+// the head's centre to the source
+inline double room_head_direct(const mc_ir_room& r) {
+    double sq = 0.0;
+    for (int ax = 0; ax < 3; ax++) {
+        const double p = (double)r.source_m[ax] - (double)r.receiver_m[ax];
+        sq += p * p;
+    }
+    return std::sqrt(sq);
+}
+
+// Every field of the head, then what follows from it in a room that room_check has passed, at the session's rate and F, and
+// with the microphones (or null) that room_mics_check has passed; no engine, no HIP; the message names the field.  Null when
+// it is good.
+inline const char* room_head_check(const mc_ir_room_head* h, const mc_ir_room& r, const mc_ir_room_mics* mics, uint32_t rate, uint64_t F) {
+    static thread_local char msg[240];
+    if (!h) return "null head";
+    if (h->struct_size != sizeof(mc_ir_room_head)) return "mc_ir_room_head struct_size mismatch";
+    msg[0] = 0;
+    const auto outside = [](const char* name, float v, double lo, double hi) {
+        if (std::isfinite(v) && v >= (float)lo && v <= (float)hi) return false;  // (as floats: 0.05f and 0.15f are in)
+        std::snprintf(msg, sizeof(msg), "head %s %g outside [%g, %g]", name, (double)v, lo, hi);
+        return true;
+    };
+    if (outside("radius_m", h->radius_m, 0.05, 0.15)) return msg;
+    if (outside("facing_az_deg", h->facing_az_deg, -360.0, 360.0)) return msg;
+    if (outside("ear_deg", h->ear_deg, 60.0, 120.0)) return msg;
+    if (outside("shadow", h->shadow, 0.0, 1.0)) return msg;
+    if (h->flags) {
+        std::snprintf(msg, sizeof(msg), "head flags %u must be 0", h->flags);
+        return msg;
+    }
+    for (int k = 0; k < 2; k++)
+        if (h->reserved[k]) {
+            std::snprintf(msg, sizeof(msg), "head reserved[%d] %u must be 0", k, h->reserved[k]);
+            return msg;
+        }
+    const double a = (double)h->radius_m, x = (double)r.speed / (a * (double)rate);
+    if (!(x < 1.5)) {
+        std::snprintf(msg, sizeof(msg), "head radius_m %g at rate %u: the head's corner lies above the rate (c / (a rate) = %g, not below 1.5)", a, rate, x);
+        return msg;
+    }
+    const double direct = room_head_direct(r);
+    if (!(direct >= a + ROOM_MIN_DIRECT)) {
+        std::snprintf(msg, sizeof(msg), "source_m is %g m from the head's centre, below radius_m + %g = %g", direct, ROOM_MIN_DIRECT, a + ROOM_MIN_DIRECT);
+        return msg;
+    }
+    double N = (double)r.order;
+    if (!r.order) {
+        N = room_head_auto_order(r, a, rate, F);
+        if (!(N <= (double)MC_ROOM_MAX_ORDER)) {
+            std::snprintf(msg, sizeof(msg), "order 0 needs order %.0f for %llu frames with a head, above %d: set last or order", N,
+                          (unsigned long long)room_last(r, F), MC_ROOM_MAX_ORDER);
+            return msg;
+        }
+    }
+    const double images = 8.0 * (2.0 * N + 1.0) * (2.0 * N + 1.0) * (2.0 * N + 1.0);
+    if (!(images * (double)r.gain / direct < ROOM_MAX_SUM)) {
+        std::snprintf(msg, sizeof(msg), "gain %g: %.0f images of at most gain / %g m each may sum to 2^22 or more", (double)r.gain, images, direct);
+        return msg;
+    }
+    if (mics)
+        for (int c = 0; c < 2; c++)
+            if (mics->mic_pattern[c] != 1.f) {
+                std::snprintf(msg, sizeof(msg), "mic_pattern[%d] %g must be 1 with a head: ears are not microphones", c, (double)mics->mic_pattern[c]);
+                return msg;
+            }
+    return nullptr;
+}
+
+// the head's high-pass at the session's rate
+inline RoomShelf room_shelf(double a, double speed, double rate) {
+    const double K = std::tan(speed / (a * rate)), b0 = 1.0 / (1.0 + K);
+    return RoomShelf{K, b0, -b0, -(1.0 - K) / (1.0 + K)};
+}
+
+// A checked head into the plan of its room, before the microphones and the bands: both receivers at the centre, the ear axes,
+// the order, the completeness and the ears' direct delays by the head's rules.  report = what mc_ir_room_head_plan and
+// mc_ir_room_head_info hand out.
+inline void room_plan_head(RoomPlan& p, const mc_ir_room& r, const mc_ir_room_head& h, double report[12]) {
+    const double a = (double)h.radius_m, az = (double)h.facing_az_deg * M_PI / 180, ear = (double)h.ear_deg * M_PI / 180;
+    p.N = r.order ? r.order : (uint32_t)room_head_auto_order(r, a, (uint32_t)p.rate, p.F);
+    p.S = 2 * p.N + 1;
+    p.total = 8u * p.S * p.S * p.S;
+    p.complete = (uint64_t)room_head_complete(r, a, (uint32_t)p.rate, (double)p.N);
+    for (int c = 0; c < 2; c++) {
+        const double at = c ? az - ear : az + ear;
+        p.head[3 * c] = std::cos(at), p.head[3 * c + 1] = std::sin(at), p.head[3 * c + 2] = 0.0;
+        for (int ax = 0; ax < 3; ax++) p.rcv[c][ax] = (double)r.receiver_m[ax];
+    }
+    p.head[6] = a;
+    p.head[7] = (double)h.shadow;
+    p.headed = 1;
+    const double px = p.src[0] - p.rcv[0][0], py = p.src[1] - p.rcv[0][1], pz = p.src[2] - p.rcv[0][2], d = std::sqrt(px * px + py * py + pz * pz);
+    std::fill(report, report + 12, 0.0);
+    for (int c = 0; c < 2; c++) {
+        const double2 e = room_ear(p.head[3 * c], p.head[3 * c + 1], p.head[3 * c + 2], px, py, pz, d);
+        p.tau[c] = std::fma(a, e.x, d) * p.rate / p.speed;
+        report[2 + c] = p.tau[c];
+        report[5 + c] = e.y * 180 / M_PI;
+        report[7 + c] = room_shadow(p.head[7], e.y);
+    }
+    report[0] = (double)p.N;
+    report[1] = (double)p.complete;
+    report[4] = (p.tau[1] - p.tau[0]) / p.rate;
+    report[9] = p.speed / (M_PI * a);
+    report[10] = room_shelf(a, p.speed, p.rate).K;
+}
+
 // k_room over room's lattice into acc (room.A frames, zero) and kept (two zeroed counters)
 inline hipError_t room_launch(hipStream_t stream, const RoomPlan& room, unsigned long long* d_acc, unsigned* d_kept) {
     const uint64_t waves = ((uint64_t)room.total + 63) / 64, per = ROOM_THREADS / 64;
     const unsigned grid = (unsigned)std::min<uint64_t>((waves + per - 1) / per, ROOM_MAX_GRID);
     const bool air = room.air != 0.0;
-    if (room.mics && air)
+    if (room.headed && room.mics && air)
+        hipLaunchKernelGGL((k_room<true, true, true>), dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
+    else if (room.headed && air)
+        hipLaunchKernelGGL((k_room<false, true, true>), dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
+    else if (room.headed && room.mics)
+        hipLaunchKernelGGL((k_room<true, false, true>), dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
+    else if (room.headed)
+        hipLaunchKernelGGL((k_room<false, false, true>), dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
+    else if (room.mics && air)
         hipLaunchKernelGGL((k_room<true, true>), dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
     else if (air)
         hipLaunchKernelGGL((k_room<false, true>), dim3(grid), dim3(ROOM_THREADS), 0, stream, d_acc, d_kept, room);
@@ -619,11 +842,86 @@ inline hipError_t room_launch(hipStream_t stream, const RoomPlan& room, unsigned
     return hipGetLastError();
 }
 
+// The join of the X + 1 accumulators at acc2 ([X + 1][A] pairs of int64) into d_r [F], X >= 1: the local pass, the carry and one
+// fix-up per crossover, low to high.  d_st: 2 X cg.lanes double2, cg = chunk_geom(F).
+inline hipError_t room_join(hipStream_t stream, const longlong2* acc2, uint64_t A, uint64_t F, const RoomJoin& join, const ChunkGeom& cg, double2* d_st,
+                            double2* d_r) {
+    const int X = join.X;
+    hipLaunchKernelGGL(k_room_join<false>, dim3(cg.grid, X), dim3(IEQ_THREADS), 0, stream, acc2, A, F, join, 0, d_st, d_r);
+    hipError_t er = hipGetLastError();
+    if (er == hipSuccess) {
+        hipLaunchKernelGGL(k_damp_carry, dim3(X), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.lanes, cg.nchunks, cg.K, damp_carry(join.c, X, cg.K));
+        er = hipGetLastError();
+    }
+    for (int k = 0; k < X && er == hipSuccess; k++) {
+        hipLaunchKernelGGL(k_room_join<true>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, acc2, A, F, join, k, d_st, d_r);
+        er = hipGetLastError();
+    }
+    return er;
+}
+
+// room_generate and room_generate_bands for a room with a head: plans = the B band plans (B = 1 and X = 0 without bands), each
+// headed.  One k_room per band into its own pair of accumulators, the plain ones [B][A] and behind them the shadow ones [B][A];
+// with X crossovers the join of each block (rP into r, rS); the head's pass over the shadow accumulator or rS, which leaves
+// r = S + the plain term; k_synth_room_bands.  One allocation holds the accumulators and the counters (zeroed with one memset),
+// r, rS and the states, and is freed after the synth kernel.
+inline hipError_t room_generate_head(hipStream_t stream, const SynPlan& syn, const RoomPlan* plans, int B, const RoomJoin* join, float2* d_x, uint32_t kept[2]) {
+    const uint64_t A = plans[0].A, F = syn.F;
+    const int X = join ? join->X : 0;
+    const ChunkGeom cg = chunk_geom(F);
+    const RoomShelf shelf = room_shelf(plans[0].head[6], plans[0].speed, plans[0].rate);
+    const size_t block_bytes = sizeof(unsigned long long) * 2 * A * (size_t)B, zero_bytes = 2 * block_bytes + 16 * (size_t)B;  // (16: two counters, padded)
+    const size_t r_bytes = sizeof(double2) * F * (X ? 2 : 1), st_bytes = sizeof(double2) * (size_t)std::max(2 * X, 1) * cg.lanes;
+    char* d_all = nullptr;
+    hipError_t er = hipMalloc(&d_all, zero_bytes + r_bytes + st_bytes);
+    if (er != hipSuccess) return er;
+    unsigned long long* d_acc = reinterpret_cast<unsigned long long*>(d_all);
+    unsigned* d_kept = reinterpret_cast<unsigned*>(d_all + 2 * block_bytes);
+    double2* d_r = reinterpret_cast<double2*>(d_all + zero_bytes);
+    double2* d_rs = X ? d_r + F : nullptr;
+    double2* d_st = reinterpret_cast<double2*>(d_all + zero_bytes + r_bytes);
+    er = hipMemsetAsync(d_all, 0, zero_bytes, stream);
+    for (int j = 0; j < B && er == hipSuccess; j++) {
+        RoomPlan p = plans[j];
+        p.shadow_at = 2 * A * (uint64_t)B;  // (from band j's plain accumulator to band j's shadow accumulator)
+        er = room_launch(stream, p, d_acc + 2 * A * (size_t)j, d_kept + 4 * j);
+    }
+    const longlong2* plain = reinterpret_cast<const longlong2*>(d_acc);
+    const longlong2* shadow = plain + A * (size_t)B;
+    if (er == hipSuccess && X) er = room_join(stream, plain, A, F, *join, cg, d_st, d_r);
+    if (er == hipSuccess && X) er = room_join(stream, shadow, A, F, *join, cg, d_st, d_rs);
+    const longlong2 *in = X ? nullptr : shadow, *add = X ? nullptr : plain;
+    if (er == hipSuccess) {
+        hipLaunchKernelGGL(k_room_head<false>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, in, d_rs, add, A, F, shelf, d_st, d_r);
+        er = hipGetLastError();
+    }
+    if (er == hipSuccess) {
+        const IeqCarry cm = ieq_carry(IeqCoef{shelf.b0, shelf.b1, 0.0, shelf.a1, 0.0}, cg.K);  // (a tap's matrix is the scalar -a1)
+        hipLaunchKernelGGL(k_eq_carry, dim3(1), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.nchunks, cg.K, cm.M, cm.MK);
+        er = hipGetLastError();
+    }
+    if (er == hipSuccess) {
+        hipLaunchKernelGGL(k_room_head<true>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, in, d_rs, add, A, F, shelf, d_st, d_r);
+        er = hipGetLastError();
+    }
+    if (er == hipSuccess) {
+        const unsigned grid = (unsigned)((std::max<uint64_t>(F / 2, 1) + SYN_THREADS - 1) / SYN_THREADS);
+        hipLaunchKernelGGL(k_synth_room_bands, dim3(grid), dim3(SYN_THREADS), 0, stream, d_x, syn, d_r);
+        er = hipGetLastError();
+    }
+    const hipError_t waited = hipStreamSynchronize(stream);  // (also after a failed launch: the memset may still be running)
+    if (er == hipSuccess) er = waited;
+    if (er == hipSuccess) er = hipMemcpy(kept, d_kept, 2 * sizeof(unsigned), hipMemcpyDeviceToHost);
+    (void)hipFree(d_all);
+    return er;
+}
+
 // room_generate for a banded room: one k_room per band into its own accumulator, the join, k_synth_room_bands.  One allocation
 // holds the B accumulators and the counters (zeroed with one memset), r and the join's states; kept = band 0's counts (they
 // are a matter of geometry and the same in every band).  With one band there is nothing to join: k_synth_room reads its
-// accumulator.
+// accumulator.  With a head: room_generate_head.
 inline hipError_t room_generate_bands(hipStream_t stream, const SynPlan& syn, const RoomBands& rb, float2* d_x, uint32_t kept[2]) {
+    if (rb.plan[0].headed) return room_generate_head(stream, syn, rb.plan, rb.B, &rb.join, d_x, kept);
     const uint64_t A = rb.plan[0].A, F = syn.F;
     const int B = rb.B, X = rb.join.X;
     const ChunkGeom cg = chunk_geom(F);
@@ -638,19 +936,7 @@ inline hipError_t room_generate_bands(hipStream_t stream, const SynPlan& syn, co
     double2* d_st = reinterpret_cast<double2*>(d_all + zero_bytes + r_bytes);
     er = hipMemsetAsync(d_all, 0, zero_bytes, stream);
     for (int j = 0; j < B && er == hipSuccess; j++) er = room_launch(stream, rb.plan[j], d_acc + 2 * A * (size_t)j, d_kept + 4 * j);
-    const longlong2* acc2 = reinterpret_cast<const longlong2*>(d_acc);
-    if (er == hipSuccess && X) {
-        hipLaunchKernelGGL(k_room_join<false>, dim3(cg.grid, X), dim3(IEQ_THREADS), 0, stream, acc2, A, F, rb.join, 0, d_st, d_r);
-        er = hipGetLastError();
-    }
-    if (er == hipSuccess && X) {
-        hipLaunchKernelGGL(k_damp_carry, dim3(X), dim3(2 * IEQ_RUNS), 0, stream, d_st, cg.lanes, cg.nchunks, cg.K, damp_carry(rb.join.c, X, cg.K));
-        er = hipGetLastError();
-    }
-    for (int k = 0; k < X && er == hipSuccess; k++) {
-        hipLaunchKernelGGL(k_room_join<true>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, acc2, A, F, rb.join, k, d_st, d_r);
-        er = hipGetLastError();
-    }
+    if (er == hipSuccess && X) er = room_join(stream, reinterpret_cast<const longlong2*>(d_acc), A, F, rb.join, cg, d_st, d_r);
     if (er == hipSuccess) {
         const unsigned grid = (unsigned)((std::max<uint64_t>(F / 2, 1) + SYN_THREADS - 1) / SYN_THREADS);
         if (X)
@@ -667,8 +953,9 @@ inline hipError_t room_generate_bands(hipStream_t stream, const SynPlan& syn, co
 }
 
 // The syn.F frames with the room's reflections into d_x (8-byte aligned), on `stream`, which is waited for: kept[c] = the
-// images of channel c that arrive before frame E.  The accumulator lives only inside this call.
+// images of channel c that arrive before frame E.  The accumulator lives only inside this call.  With a head: room_generate_head.
 inline hipError_t room_generate(hipStream_t stream, const SynPlan& syn, const RoomPlan& room, float2* d_x, uint32_t kept[2]) {
+    if (room.headed) return room_generate_head(stream, syn, &room, 1, nullptr, d_x, kept);
     unsigned long long* d_acc = nullptr;
     const size_t acc_bytes = sizeof(unsigned long long) * 2 * room.A;
     hipError_t er = hipMalloc(&d_acc, acc_bytes + 2 * sizeof(unsigned));

@@ -102,10 +102,10 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline double pan_l(double p) { return p >= 0 ? 1 - p : 1; }  // conv.cu:386
 inline double pan_r(double p) { return p <= 0 ? 1 + p : 1; }  // conv.cu:387
 
-// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _phase_info, _filter_info, _match_info, _parts_info, _room_info, _room_mics_info, _room_bands_info and _plate_info report of an IR's last
+// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _phase_info, _filter_info, _match_info, _parts_info, _room_info, _room_mics_info, _room_bands_info, _room_head_info and _plate_info report of an IR's last
 // load: one entry per kind, on when that load had the step or the source (a shape with something on, an eq band or damping count as a shape, and
 // so do a synthesised, a swept and a tailed load), with the numbers the getter hands out (include/mcconv.h says what they are)
-enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_PHASE, FACT_FILTER, FACT_MATCH, FACT_PARTS, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_PLATE, FACT_KINDS };
+enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_PHASE, FACT_FILTER, FACT_MATCH, FACT_PARTS, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_ROOM_HEAD, FACT_PLATE, FACT_KINDS };
 struct IrFact {
     bool on = false;
     double v[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -3282,12 +3282,14 @@ struct TailStep {
 };
 
 // the room of a synthesised load as load_ir and shape_stage take it: the plan, the images the device kept per channel, and
-// with `banded` the bands of mc_ir_room_bands, which are then what is rendered
+// with `banded` the bands of mc_ir_room_bands, which are then what is rendered; with plan.headed the twelve numbers of
+// mc_ir_room_head_info
 struct RoomStep {
     RoomPlan plan;
     uint32_t kept[2];
     bool banded;
     RoomBands bands;
+    double head[12];
 };
 
 // the plate of a synthesised load as load_ir and shape_stage take it: the checked plate with its table (irplate.hip.h)
@@ -3431,6 +3433,10 @@ void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const ShapedTaps& s
             double m[8];
             room_mics_report(r, m);
             put(FACT_ROOM_MICS, {m[0], m[1], m[2], m[3], m[4], m[5], m[6], m[7]});
+        }
+        if (r.headed) {
+            const double* h = ld.room->head;
+            put(FACT_ROOM_HEAD, {h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11]});
         }
         if (ld.room->banded) {
             const double* b = ld.room->bands.report;
@@ -3594,7 +3600,7 @@ const char* resolve_steps(const mc_ir_shape* shape, const mc_ir_eq* eq, const mc
     return nullptr;
 }
 
-// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, phase, filter, match, parts, room, room mics, room bands, plate): out = the first `count` numbers of what
+// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, phase, filter, match, parts, room, room mics, room bands, room head, plate): out = the first `count` numbers of what
 // note_load kept of that kind, or MC_ERR_STATE with "IR <idx> <was_not>" when the last load had none
 int ir_fact(const mc_engine* e, uint64_t idx, IrFactKind kind, int count, const char* was_not, double* out) {
     if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
@@ -3957,10 +3963,25 @@ void mc_default_ir_room_bands(mc_ir_room_bands* b) {
 
 int mc_synth_ir_room_bands(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_synth* synth, const mc_ir_room* room, const mc_ir_room_mics* mics,
                            const mc_ir_room_bands* bands, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail) {
+    return mc_synth_ir_room_head(e, idx, nframes, synth, room, mics, bands, nullptr, shape, eq, damp, tail);
+}
+
+void mc_default_ir_room_head(mc_ir_room_head* h) {
+    if (!h) return;
+    std::memset(h, 0, sizeof(*h));
+    h->struct_size = (uint32_t)sizeof(*h);
+    h->radius_m = 0.0875f;
+    h->ear_deg = 90.f;
+    h->shadow = 1.f;
+}
+
+int mc_synth_ir_room_head(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_synth* synth, const mc_ir_room* room, const mc_ir_room_mics* mics,
+                          const mc_ir_room_bands* bands, const mc_ir_room_head* head, const mc_ir_shape* shape, const mc_ir_eq* eq, const mc_ir_damp* damp,
+                          const mc_ir_tail* tail) {
     const bool tailed = tail && tail->mode != MC_TAIL_OFF;
-    if (!room && !mics && !bands && !tailed) return mc_synth_ir(e, idx, nframes, synth, shape, eq, damp);
-    // synth, then the room, its microphones and its bands, then the tail with F' after F, then damp, eq and shape as in mc_synth_ir,
-    // all before the engine and before any HIP call
+    if (!room && !mics && !bands && !head && !tailed) return mc_synth_ir(e, idx, nframes, synth, shape, eq, damp);
+    // synth, then the room, its microphones, its bands and its head, then the tail with F' after F, then damp, eq and shape as in
+    // mc_synth_ir, all before the engine and before any HIP call
     if (const char* bad = syn_check(synth)) return fail(MC_ERR_ARG, "%s", bad);
     const uint32_t rate = synth->rate;
     const uint64_t F = synth->frames;
@@ -3972,6 +3993,9 @@ int mc_synth_ir_room_bands(mc_engine* e, uint64_t idx, uint64_t nframes, const m
     if (bands && !room) return fail(MC_ERR_ARG, "the bands need a room");
     if (bands)
         if (const char* bad = room_bands_check(bands, rate)) return fail(MC_ERR_ARG, "%s", bad);
+    if (head && !room) return fail(MC_ERR_ARG, "the head needs a room");
+    if (head)
+        if (const char* bad = room_head_check(head, *room, mics, rate, F)) return fail(MC_ERR_ARG, "%s", bad);
     if (tailed) {
         if (const char* bad = tail_check(tail, rate)) return fail(MC_ERR_ARG, "%s", bad);
         if (rate < RS_MIN_RATE || rate > RS_MAX_RATE)
@@ -3985,6 +4009,7 @@ int mc_synth_ir_room_bands(mc_engine* e, uint64_t idx, uint64_t nframes, const m
     if (tailed) step = tail_step(*tail, rate, F);
     RoomStep rstep{};
     if (room) rstep.plan = room_plan(*room, rate, F);
+    if (head) room_plan_head(rstep.plan, *room, *head, rstep.head);
     if (mics) room_plan_mics(rstep.plan, *mics);
     if (bands) rstep.bands = room_bands_plan(rstep.plan, *room, *bands, rate), rstep.banded = true;
     IrLoad ld;
@@ -4034,6 +4059,21 @@ int mc_ir_room_bands_plan(const mc_ir_room* room, const mc_ir_room_bands* bands,
 
 int mc_ir_room_bands_info(const mc_engine* e, uint64_t idx, double out[16]) {
     return ir_fact(e, idx, FACT_ROOM_BANDS, 16, "was not loaded with bands", out);
+}
+
+int mc_ir_room_head_plan(const mc_ir_room* room, const mc_ir_room_head* head, uint32_t rate, uint64_t frames, double out[12]) {
+    if (frames < 1 || frames > SYN_MAX_FRAMES)
+        return fail(MC_ERR_ARG, "frames %llu outside [1, %llu]", (unsigned long long)frames, (unsigned long long)SYN_MAX_FRAMES);
+    if (const char* bad = room_check(room, rate, frames)) return fail(MC_ERR_ARG, "%s", bad);
+    if (const char* bad = room_head_check(head, *room, nullptr, rate, frames)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!out) return fail(MC_ERR_ARG, "null out");
+    RoomPlan p = room_plan(*room, rate, frames);
+    room_plan_head(p, *room, *head, out);
+    return MC_OK;
+}
+
+int mc_ir_room_head_info(const mc_engine* e, uint64_t idx, double out[12]) {
+    return ir_fact(e, idx, FACT_ROOM_HEAD, 12, "was not loaded with a head", out);
 }
 
 void mc_default_ir_plate(mc_ir_plate* p) {

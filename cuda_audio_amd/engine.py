@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrPlate, McIrRoom, McIrRoomBands, McIrRoomMics, McIrFilter, McIrMatch, McIrPhase, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrPlate, McIrRoom, McIrRoomBands, McIrRoomHead, McIrRoomMics, McIrFilter, McIrMatch, McIrPhase, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -866,6 +866,44 @@ def room_bands_plan(room, bands, rate, frames):
 
 
 @dataclasses.dataclass
+class IrRoomHead:
+    """A binaural listener in an IrRoom (mc_ir_room_head, include/mcconv.h): prepare_synth(room=, head=).  A rigid sphere of
+    `radius` metres (Brown and Duda's structural model) takes the place of the receiver pair at IrRoom.receiver: each ear
+    hears an arrival with a delay that depends on its direction and through a head-shadow shelf, up to +6 dB towards the ear
+    and down to about -20 dB behind the head at high frequencies.  `facing` is the azimuth the listener looks along, in
+    degrees from +x towards +y; `ear` is the ears' angle from it (90: on the axis through the head; Brown and Duda place them
+    at 100, a little behind it); the left ear is channel 0.  `shadow` in [0, 1] scales the shelf: 0 leaves the delays alone.
+    IrRoom.spacing and axis are not used with a head.  A far-field model of an upright head: no pinna, no torso, no
+    elevation cue."""
+
+    radius: float = 0.0875
+    facing: float = 0.0
+    ear: float = 90.0
+    shadow: float = 1.0
+
+    def to_c(self):
+        h = McIrRoomHead()
+        _lib.load().mc_default_ir_room_head(C.byref(h))
+        h.radius_m, h.facing_az_deg, h.ear_deg, h.shadow = float(self.radius), float(self.facing), float(self.ear), float(self.shadow)
+        return h
+
+
+def _head_report(out):
+    return dict(order=int(out[0]), complete=int(out[1]), direct=(out[2], out[3]), itd=out[4], angle=(out[5], out[6]), shadow=(out[7], out[8]),
+                corner=out[9], k=out[10])
+
+
+def room_head_plan(room, head, rate, frames):
+    """What a load of `frames` frames at `rate` would do with `head` (an IrRoomHead) in `room` (mc_ir_room_head_plan, host
+    arithmetic only): the lattice order and the frames up to which it is complete, the direct sound's delay at each ear
+    (frames) and their difference right minus left in seconds (`itd`), its angle from each ear's axis (degrees), each ear's
+    shadow factor h = alpha - 1, the shelf's corner in Hz and its prewarped constant K; pairs are (left, right)."""
+    out = (C.c_double * 12)()
+    check(_lib.load().mc_ir_room_head_plan(C.byref(room.to_c()), C.byref(head.to_c()), int(rate), int(frames), out))
+    return _head_report(out)
+
+
+@dataclasses.dataclass
 class Sweep:
     """The exponential sine sweep whose recording prepare_sweep deconvolves (mc_sweep, include/mcconv.h): `frames` frames
     from f1_hz at frame 0 to f2_hz at the last, of peak `amplitude` (0.5 is WavFile's full scale), faded in and out over
@@ -1145,7 +1183,7 @@ class Convolution:
         steps, keep = _c_steps(shape, eq, damp, tail, phase, filter, match, parts)
         check(self._L.mc_load_ir_parts(self._h, idx, _fp(lr), lr.shape[0], nframes, *rates, *steps))
 
-    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None, room=None, tail=None, mics=None, bands=None, plate=None):
+    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None, room=None, tail=None, mics=None, bands=None, plate=None, head=None):
         """Generate the IR `synth` (an IrSynth) describes on the device and store it at idx (mc_synth_ir): the frames take the
         place of a WAV's at the session's rate, and shape, eq and damp apply to them as in prepare().  A synthesised IR counts
         as shaped: ir_shape_info(idx)["frames"] is synth.frames.  The engine's sample_rate (which eq, damp, room and tail
@@ -1154,15 +1192,17 @@ class Convolution:
         was rendered.  tail (an IrTail whose mode is not "off"): the tail step on the generated frames, as in prepare().
         mics (an IrRoomMics, with room): the receivers and the source of the room are directional; ir_room_mics_info(idx)
         then tells the direct sound's factors.  bands (an IrRoomBands, with room): the walls and the air differ per
-        frequency band; ir_room_bands_info(idx) then tells the bands' reverberation times.
+        frequency band; ir_room_bands_info(idx) then tells the bands' reverberation times.  head (an IrRoomHead, with
+        room): a rigid-sphere listener takes the receiver pair's place and the IR is binaural; ir_room_head_info(idx) then
+        tells the ears' delays and shadow factors.
         plate (an IrPlate, without room, mics and bands): the modes of a plate reverberator are added to the frames
         (mc_synth_ir_plate); ir_plate_info(idx) then tells what was summed."""
         s = synth.to_c()
         if not s.rate:
             s.rate = int(self.sample_rate or 0)
         if plate is not None:
-            if room is not None or mics is not None or bands is not None:
-                raise ValueError("a plate and a room (room, mics, bands) in one load are not offered")
+            if room is not None or mics is not None or bands is not None or head is not None:
+                raise ValueError("a plate and a room (room, mics, bands, head) in one load are not offered")
             steps, keep = _c_steps(shape, eq, damp, tail, None, None, None, None)
             check(self._L.mc_synth_ir_plate(self._h, idx, nframes, C.byref(s), C.byref(plate.to_c()), *steps[:4]))
             return
@@ -1170,9 +1210,14 @@ class Convolution:
             raise ValueError("the bands need a room")
         if mics is not None and room is None:
             raise ValueError("the microphones need a room")
+        if head is not None and room is None:
+            raise ValueError("the head needs a room")
         ref = lambda x: C.byref(x.to_c()) if x is not None else None  # noqa: E731
         source = (ref(room), ref(mics), ref(bands))
         steps, keep = _c_steps(shape, eq, damp, tail, None, None, None, None)
+        if head is not None:
+            check(self._L.mc_synth_ir_room_head(self._h, idx, nframes, C.byref(s), *source, ref(head), *steps[:4]))
+            return
         check(self._L.mc_synth_ir_room_bands(self._h, idx, nframes, C.byref(s), *source, *steps[:4]))
 
     def prepare_sweep(self, idx, recording, sweep, offset=0, ir_frames=None, nframes=1024, shape=None, eq=None, damp=None, tail=None, phase=None, filter=None, match=None, parts=None):
@@ -1344,6 +1389,13 @@ class Convolution:
         out = (C.c_double * 16)()
         check(self._L.mc_ir_room_bands_info(self._h, idx, out))
         return _bands_report(out)
+
+    def ir_room_head_info(self, idx):
+        """The head of IR idx's load (mc_ir_room_head_info), as room_head_plan reports it.  McError (MC_ERR_STATE) for an IR
+        whose last load had no head."""
+        out = (C.c_double * 12)()
+        check(self._L.mc_ir_room_head_info(self._h, idx, out))
+        return _head_report(out)
 
     def ir_room_mics_info(self, idx):
         """What the microphones of IR idx's load did to the direct sound (mc_ir_room_mics_info), as room_mics_plan reports it.

@@ -119,6 +119,11 @@ void mc_default_ir_room_bands(mc_ir_room_bands*) __attribute__((weak));
 int mc_synth_ir_room_bands(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_room*, const mc_ir_room_mics*, const mc_ir_room_bands*,
                            const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*, const mc_ir_tail*) __attribute__((weak));
 int mc_ir_room_bands_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+// ... or a room without a binaural listener
+void mc_default_ir_room_head(mc_ir_room_head*) __attribute__((weak));
+int mc_synth_ir_room_head(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_room*, const mc_ir_room_mics*, const mc_ir_room_bands*,
+                          const mc_ir_room_head*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*, const mc_ir_tail*) __attribute__((weak));
+int mc_ir_room_head_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 // ... or no plate
 void mc_default_ir_plate(mc_ir_plate*) __attribute__((weak));
 int mc_synth_ir_plate(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_plate*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
@@ -350,6 +355,7 @@ void Convolution::loadIr(const IrLoadRequest& r) {
         bool needed, there;
         const char* lacks;
     } capabilities[] = {
+        {nullptr, r.head.has_value(), mc_synth_ir_room_head && mc_default_ir_room_head && mc_ir_room_head_info, "a binaural listener in its rooms (mc_synth_ir_room_head)"},
         {nullptr, r.bands.has_value(), mc_synth_ir_room_bands && mc_default_ir_room_bands && mc_ir_room_bands_info, "frequency bands in its rooms (mc_synth_ir_room_bands)"},
         {nullptr, r.mics.has_value(), mc_synth_ir_room_mics && mc_default_ir_room_mics && mc_ir_room_mics_info, "directional microphones in its rooms (mc_synth_ir_room_mics)"},
         {nullptr, r.room.has_value(), mc_synth_ir_room && mc_default_ir_room && mc_ir_room_info, "room rendering (mc_synth_ir_room)"},
@@ -411,7 +417,9 @@ void Convolution::loadIr(const IrLoadRequest& r) {
         const mc_ir_room* room = r.room ? &*r.room : nullptr;
         const mc_ir_room_mics* mics = r.mics ? &*r.mics : nullptr;
         const mc_ir_room_bands* bands = r.bands ? &*r.bands : nullptr;
-        const int rc = bands  ? mc_synth_ir_room_bands(_engine, idx, r.nframes, y, room, mics, bands, &s, q, d, t)
+        const mc_ir_room_head* head = r.head ? &*r.head : nullptr;
+        const int rc = head   ? mc_synth_ir_room_head(_engine, idx, r.nframes, y, room, mics, bands, head, &s, q, d, t)
+                       : bands ? mc_synth_ir_room_bands(_engine, idx, r.nframes, y, room, mics, bands, &s, q, d, t)
                        : mics ? mc_synth_ir_room_mics(_engine, idx, r.nframes, y, room, mics, &s, q, d, t)
                        : room ? mc_synth_ir_room(_engine, idx, r.nframes, y, room, &s, q, d, t)
                        : r.plate ? mc_synth_ir_plate(_engine, idx, r.nframes, y, &*r.plate, &s, q, d, t)
@@ -485,6 +493,13 @@ void Convolution::loadIr(const IrLoadRequest& r) {
             eyring += one;
         }
         Log::info(name, "IR %zu bands: %d, low to high Sabine %s s, Eyring %s s", idx, (int)bi[0], sabine.c_str(), eyring.c_str());
+    }
+    if (r.head) {
+        double hi[12];
+        check(mc_ir_room_head_info(_engine, idx, hi), "mc_ir_room_head_info");
+        Log::info(name, "IR %zu head: the direct sound reaches the ears at %.2f and %.2f frames (right minus left %+.4f ms), %.1f and %.1f degrees off their "
+                        "axes, shadow factors %+.4f and %+.4f, shelf corner %.0f Hz",
+                  idx, hi[2], hi[3], hi[4] * 1e3, hi[5], hi[6], hi[7], hi[8], hi[9]);
     }
     if (generated) {
         double si[4];
@@ -1559,12 +1574,23 @@ mc_ir_room_bands Convolution::roomBands(const IrRoom& room) {
     return b;
 }
 
+mc_ir_room_head Convolution::roomHead(const IrRoom& room) {
+    mc_ir_room_head h;
+    mc_default_ir_room_head(&h);
+    h.radius_m = room.headRadius;
+    h.facing_az_deg = room.headFacing;
+    h.ear_deg = room.headEars;
+    h.shadow = room.headShadow;
+    return h;
+}
+
 bool Convolution::parseRoom(const std::string& line, IrRoom& out, std::string& why) {
     static const char* form =
         "room:LENGTH_S:LX,LY,LZ:SX,SY,SZ:RX,RY,RZ[:key=value,...] with keys beta (one value, or six separated by '/'), order, spacing, axis (x|y|z), "
         "speed, gain, last, mic (omni|subcardioid|cardioid|supercardioid|hypercardioid|fig8 or a number in [0, 1]; P or P/P), aim and tilt (degrees; "
         "one value or L/R), src, srcaim, srctilt, xover (HZ[/HZ[/HZ]]), betas (one value per band, separated by '/'), air (dB per metre: one value, or one "
-        "per band), t60 and synth:'s keys";
+        "per band), head (the azimuth the listener faces, degrees), headradius (metres), ears (degrees from the facing direction), shadow ([0, 1]), "
+        "t60 and synth:'s keys";
     std::vector<std::string> parts;
     for (size_t at = 0;;) {
         const size_t colon = line.find(':', at);
@@ -1695,6 +1721,12 @@ bool Convolution::parseRoom(const std::string& line, IrRoom& out, std::string& w
             good = upTo(text, MC_DAMP_MAX_XOVERS + 1, 0.0, 1.0, room.air, room.nAir);
             airText = text;
             room.banded = true;
+        } else if (key == "head" || key == "headradius" || key == "ears" || key == "shadow") {
+            const double lo = key == "head" ? -360.0 : key == "headradius" ? 0.05 : key == "ears" ? 60.0 : 0.0;
+            const double hi = key == "head" ? 360.0 : key == "headradius" ? 0.15 : key == "ears" ? 120.0 : 1.0;
+            good = number(text, v) && v >= lo && v <= hi;
+            (key == "head" ? room.headFacing : key == "headradius" ? room.headRadius : key == "ears" ? room.headEars : room.headShadow) = (float)v;
+            room.headed = true;
         } else if (key == "src") {
             good = pattern(text, room.sourcePattern);
             room.directional = true;
@@ -2064,6 +2096,10 @@ Convolution::IrLoadRequest Convolution::requestFor(const PendingIr& p) {
         return r;
     }
     if (p.generated) {
+        if (p.roomed && p.room.headed && !mc_default_ir_room_head) {
+            Log::error("conv", "the engine has no binaural listener in its rooms (mc_synth_ir_room_head)");
+            std::exit(2);
+        }
         if (p.roomed && p.room.banded && !mc_default_ir_room_bands) {
             Log::error("conv", "the engine has no frequency bands in its rooms (mc_synth_ir_room_bands)");
             std::exit(2);
@@ -2089,6 +2125,7 @@ Convolution::IrLoadRequest Convolution::requestFor(const PendingIr& p) {
         if (p.roomed) r.room = roomFrames(p.room, (double)samplerate);
         if (p.roomed && p.room.directional) r.mics = roomMics(p.room);
         if (p.roomed && p.room.banded) r.bands = roomBands(p.room);
+        if (p.roomed && p.room.headed) r.head = roomHead(p.room);
         return r;
     }
     r.lr = p.lr.data(), r.frames = p.lr.size() / 2;

@@ -188,6 +188,12 @@ public:
     // xover, betas and air, and such a room is loaded through mc_synth_ir_room_bands, in both renderings of the tail flow, with one
     // more log line: Sabine's and Eyring's reverberation times per band.  xover cuts nXovers + 1 bands; betas gives every band one
     // value for its six walls (without it every band has `beta`), air one loss in dB per metre for every band or one per band.
+    // A binaural listener (mc_ir_room_head and mc_synth_ir_room_head): `headed` is set by any of the line's keys head (the azimuth
+    // the listener faces, degrees), headradius (metres), ears (their angle from the facing direction, degrees) and shadow (the
+    // depth of the head-shadow shelf, [0, 1]), and such a room is loaded through mc_synth_ir_room_head, in both renderings of the
+    // tail flow, with one more log line: the ears' delays, their difference and their shadow factors.  A rigid sphere at
+    // `receiver` takes the receiver pair's place (spacing and axis are not used): a far-field model of an upright head, without
+    // pinna, torso or elevation cues.
     struct IrRoom {
         float size[3] = {5.0f, 4.0f, 3.0f}, source[3] = {1.0f, 1.5f, 1.2f}, receiver[3] = {3.5f, 2.0f, 1.5f};
         float beta[6] = {0.9f, 0.9f, 0.9f, 0.9f, 0.9f, 0.9f};
@@ -203,6 +209,8 @@ public:
         uint32_t nXovers = 0, nBetas = 0, nAir = 0;  // values given by xover, betas and air
         float xovers[MC_DAMP_MAX_XOVERS] = {0.0f, 0.0f, 0.0f};
         float betas[MC_DAMP_MAX_XOVERS + 1] = {0.9f, 0.9f, 0.9f, 0.9f}, air[MC_DAMP_MAX_XOVERS + 1] = {0.0f, 0.0f, 0.0f, 0.0f};
+        bool headed = false;
+        float headFacing = 0.0f, headRadius = 0.0875f, headEars = 90.0f, headShadow = 1.0f;
         IrSynth late;
         IrRoom() { late.late = 0.0f; }
     };
@@ -211,7 +219,8 @@ public:
     // value, or six separated by '/'), order, spacing, axis (x|y|z), speed, gain, last (seconds), mic (a pattern: omni, subcardioid,
     // cardioid, supercardioid, hypercardioid, fig8 or a number in [0, 1]; P or P/P), aim and tilt (degrees; one value or L/R),
     // src, srcaim and srctilt (the source's), xover (HZ[/HZ[/HZ]]), betas (one value per band, separated by '/') and air (dB per
-    // metre: one value, or one per band), and for the late field t60 and parseSynth's keys - as an IrRoom.  False, with the
+    // metre: one value, or one per band), head (degrees), headradius (metres), ears (degrees) and shadow ([0, 1]), and for the
+    // late field t60 and parseSynth's keys - as an IrRoom.  False, with the
     // reason in `why`, for a malformed line.
     static bool parseRoom(const std::string& line, IrRoom& out, std::string& why);
     // mc_ir_room of an IrRoom at rate Hz
@@ -220,6 +229,8 @@ public:
     static mc_ir_room_mics roomMics(const IrRoom& room);
     // mc_ir_room_bands of a banded IrRoom
     static mc_ir_room_bands roomBands(const IrRoom& room);
+    // mc_ir_room_head of a headed IrRoom
+    static mc_ir_room_head roomHead(const IrRoom& room);
 
     // A plate reverberator whose modes the engine sums (mc_ir_plate and mc_synth_ir_plate of include/mcconv.h; no reference
     // equivalent): metres, millimetres, Hz and seconds, the length and `last` turned into frames at the client's sample rate by
@@ -544,6 +555,7 @@ private:
         std::optional<mc_ir_room> room;
         std::optional<mc_ir_room_mics> mics;
         std::optional<mc_ir_room_bands> bands;
+        std::optional<mc_ir_room_head> head;
         std::optional<mc_ir_plate> plate;  // with synth and without room: the modes of a plate are added (mc_synth_ir_plate)
         std::optional<SweepLoad> sweep;
         // The steps, in the order the frames go through them: tail, phase, filter, match, parts (null = off; they point at the

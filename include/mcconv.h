@@ -1265,6 +1265,73 @@ int mc_ir_room_bands_plan(const mc_ir_room *room, const mc_ir_room_bands *bands,
  * mc_ir_room_mics_info still answer for such a load) */
 int mc_ir_room_bands_info(const mc_engine *e, uint64_t idx, double out[16]);
 
+/* A binaural listener in the room of mc_ir_room: a rigid sphere in place of the receiver pair, by Brown and Duda's structural
+ * model (IEEE Trans. Speech Audio Proc. 6(5), 1998).  Each ear hears an arrival with a delay that depends on its direction
+ * (Woodworth's path around the sphere) and through a first-order head-shadow shelf: up to +6 dB towards the ear, down to about
+ * -20 dB behind the head at high frequencies, unity at DC.  The shelf is
+ * H(s, theta) = (1 + alpha(theta) s / wc) / (1 + s / wc) = 1 + (alpha(theta) - 1) HP(s) with HP one fixed first-order
+ * high-pass: no filter per image, but two accumulators, a plain one and one that goes through HP once.  No reference equivalent.
+ * Limits: a far-field model (no dependence on range), no pinna, no torso and no elevation cue beyond the cone of confusion the
+ * sphere leaves, and the head is upright.
+ *
+ * Everything is computed in double from the float fields; rate = synth->rate, c = room->speed, a = radius_m.
+ * Head.  The centre is room->receiver_m, and both ears are rendered from the centre; room->spacing_m and axis are checked as
+ *   before but not used, as room->beta is with bands.  The head is upright: az = facing_az_deg and ear = ear_deg, both
+ *   (double)deg * M_PI / 180, azimuth from +x towards +y as for the microphones; the ear axes, made on the host, are
+ *   e_L = (cos(az + ear), sin(az + ear), 0) and e_R = (cos(az - ear), sin(az - ear), 0).
+ * Per image and ear c.  p is the image's position relative to the centre as in mc_ir_room, d = |p|, once for both ears;
+ *   cs_c = min(1, max(-1, (e_c . p) / d)), the dot product fma(z, z', fma(y, y', x x')) as for the microphones; th_c = acos(cs_c).
+ * Delay.  g_c = cs_c >= 0 ? -cs_c : th_c - pi / 2: the plane wave's path to a point on a sphere, shorter by up to a on the near
+ *   side, around the sphere on the far side, continuous at 90 degrees.  tau_c = fma(a, g_c, d) * rate / c.  k0, f, the 32 taps and
+ *   the keep rule k0 < E are the room's, per ear.
+ * Shadow.  h_c = shadow * fma(0.95, cos(1.2 * th_c), 0.05): Brown and Duda's alpha - 1 with alpha_min = 0.1 and theta_min = 150
+ *   degrees, in [-0.9, 1] times shadow.
+ * Amplitude.  a_c is the room's: b / d, times the band's air factor, times the source's factor gs_c when mics is given (with a
+ *   head mics->mic_pattern[] must both be 1: ears are not microphones; the source's pattern and aim apply as before).  The
+ *   shadow amplitude is s_c = a_c h_c.
+ * Sums.  qP = llrint(a_c w_k 2^40) goes into accP[k0 + k][c] and qS = llrint(s_c w_k 2^40) into accS[k0 + k][c], both int64 [A][2],
+ *   A = min(E + 16, F).  The room's bound on the sum covers both, because |h| <= 1.
+ * The shelf's fixed part.  K = tan(c / (a rate)): the corner wc = 2 c / a rad/s, prewarped.  b0 = 1 / (1 + K), b1 = -b0,
+ *   a1 = -(1 - K) / (1 + K); y = b0 v + s, s' = b1 v - a1 y: the first section of mc_ir_damp's crossover step with b2 = a2 = 0, one
+ *   state per channel, from rest at frame 0 over all F frames on v[m] = accS[m] 2^-40 for m < A (converted once) and 0 from
+ *   there.  The ringing past A belongs to the IR.
+ * Term.  r[m] = S[m] + (m < A ? accP[m] 2^-40 : 0), the shelf's output S first.
+ * Frame.  (float)(late + direct + reflections + r), rounded once.
+ * With bands.  Each band renders its own accP_j and accS_j; mc_ir_room_bands' join is applied to the accP_j, giving rP [F], and
+ *   separately to the accS_j, giving rS [F] (with X = 0 the join is the one accumulator's values); r = HP(rS) + rP in the order
+ *   above.  Equal bands without air store the bits of the unbanded room with the same head.
+ * Order and completeness.  An image outside the lattice has d >= 2 N min(L) and can arrive up to a / c earlier than d / c: with
+ *   a head, complete = floor((2 N min(L) - a) rate / c), and order 0 picks the smallest N with complete >= E.  mc_ir_room_info
+ *   reports these and the ears' direct delays for such a load.
+ * shadow 0 leaves the pure delays: accS stays zero, S is +0.0 everywhere and r is accP's term. */
+typedef struct {
+    uint32_t struct_size;   /* sizeof(mc_ir_room_head) = 32 */
+    uint32_t flags;         /* must be 0 */
+    float radius_m;         /* a: finite, [0.05, 0.15] */
+    float facing_az_deg;    /* finite, [-360, 360] */
+    float ear_deg;          /* the ears' angle from the facing direction: finite, [60, 120]; Brown and Duda place them at 100 */
+    float shadow;           /* [0, 1]: the depth of the shelf, 0 = delays only */
+    uint32_t reserved[2];   /* must be 0 */
+} mc_ir_room_head;
+/* radius 0.0875 m, facing 0, ears at 90 degrees, shadow 1 */
+void mc_default_ir_room_head(mc_ir_room_head *h);
+/* mc_synth_ir_room_bands with `head` as the room's receiver.  With head NULL the call is mc_synth_ir_room_bands itself, bit for
+ * bit.  head without room is MC_ERR_ARG ("the head needs a room").  Checked in mc_synth_ir_room_bands' order, the head right
+ * after the bands and before the tail: radius_m, facing_az_deg, ear_deg, shadow, flags, reserved; then c / (a rate) < 1.5 ("the
+ * head's corner lies above the rate"), the direct distance from the centre (>= a + 0.1 m), the automatic order and the bound on
+ * the sum with the head's order, and mics->mic_pattern[], which must both be 1.  The message names the field, nothing of the
+ * engine or the device is touched before every check has passed, and the engine stays as it was on a refusal. */
+int mc_synth_ir_room_head(mc_engine *e, uint64_t idx, uint64_t nframes, const mc_ir_synth *synth, const mc_ir_room *room,
+                          const mc_ir_room_mics *mics, const mc_ir_room_bands *bands, const mc_ir_room_head *head,
+                          const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp, const mc_ir_tail *tail);
+/* What a load of `frames` frames at `rate` would do with `head` in `room`: out = {N, complete, tau L, tau R of the direct sound
+ * (frames), ITD = (tau R - tau L) / rate (s), theta L, theta R of the direct sound (degrees), h L, h R, the shelf's corner
+ * c / (pi a) (Hz), K, 0}.  The room is checked as by mc_ir_room_plan, then the head.  Host arithmetic only: no engine and no HIP
+ * call. */
+int mc_ir_room_head_plan(const mc_ir_room *room, const mc_ir_room_head *head, uint32_t rate, uint64_t frames, double out[12]);
+/* The same twelve numbers of the IR's last load; MC_ERR_STATE unless that load had a head */
+int mc_ir_room_head_info(const mc_engine *e, uint64_t idx, double out[12]);
+
 /* A plate reverberator (a thin steel sheet, a driver and two pickups: the EMT 140), added on the device to the frames
  * mc_ir_synth describes as the sum of the modes of a simply supported rectangular plate.  A plate is not a room: its modal
  * density is constant over frequency, so it is dense from the first millisecond, it is dispersive, and its decay falls with
