@@ -36,7 +36,8 @@ SYMBOLS = [
     "mc_default_ir_room_mics", "mc_synth_ir_room_mics", "mc_ir_room_mics_plan", "mc_ir_room_mics_info",
     "mc_default_ir_room_bands", "mc_synth_ir_room_bands", "mc_ir_room_bands_plan", "mc_ir_room_bands_info",
     "mc_default_ir_room_head", "mc_synth_ir_room_head", "mc_ir_room_head_plan", "mc_ir_room_head_info",
-    "mc_default_ir_plate", "mc_synth_ir_plate", "mc_ir_plate_plan", "mc_ir_plate_modes", "mc_ir_plate_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
+    "mc_default_ir_plate", "mc_synth_ir_plate", "mc_ir_plate_plan", "mc_ir_plate_modes", "mc_ir_plate_info",
+    "mc_default_ir_spring", "mc_synth_ir_spring", "mc_ir_spring_plan", "mc_ir_spring_response", "mc_ir_spring_info", "mc_num_irs", "mc_ir_info", "mc_set_params", "mc_get_params", "mc_handle_cc",
     "mc_process", "mc_process_batch", "mc_process_batch_device", "mc_partial_batch_device",
     "mc_finish_batch_device", "mc_finish_batch_slice_device", "mc_process_batch_slice_device", "mc_sync", "mc_fence", "mc_fence_older", "mc_set_stream", "mc_get_stream", "mc_avg_runtime_ms",
     "mc_enable_kernel_timing", "mc_get_kernel_stats", "mc_algorithmic_bytes_per_block", "mc_blocks_processed", "mc_preferred_batch",
@@ -509,6 +510,36 @@ class McIrPlate(C.Structure):
     ]
 
 
+MC_SPRING_MAX = 3
+MC_SPRING_MAX_STRETCH = 64
+MC_SPRING_RADIUS = 1e8
+MC_SPRING_MAX_LOG2 = 22
+
+
+class McIrSpring(C.Structure):
+    """mc_ir_spring: the spring tank whose response mc_synth_ir_spring adds to a synthesised IR."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("sections", C.c_uint32),
+        ("transition_hz", C.c_float),
+        ("dispersion", C.c_float),
+        ("delay_ms", C.c_float * 3),
+        ("t60_s", C.c_float),
+        ("damping", C.c_float),
+        ("lowpass_order", C.c_uint32),
+        ("high_gain", C.c_float),
+        ("high_sections", C.c_uint32),
+        ("high_dispersion", C.c_float),
+        ("high_delay", C.c_float),
+        ("high_t60_s", C.c_float),
+        ("stereo", C.c_float),
+        ("gain", C.c_float),
+        ("log2_points", C.c_uint32),
+        ("last", C.c_uint64),
+    ]
+
+
 class McKernelStats(C.Structure):
     _fields_ = [
         ("launches", C.c_uint64),
@@ -669,6 +700,13 @@ def load():
     L.mc_ir_plate_plan.argtypes = [C.POINTER(McIrPlate), C.c_uint32, u64, C.POINTER(C.c_double)]
     L.mc_ir_plate_modes.argtypes = [C.POINTER(McIrPlate), C.c_uint32, u64, u64, C.POINTER(C.c_double)]
     L.mc_ir_plate_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
+    L.mc_default_ir_spring.argtypes = [C.POINTER(McIrSpring)]
+    L.mc_default_ir_spring.restype = None
+    L.mc_synth_ir_spring.argtypes = [vp, u64, u64, C.POINTER(McIrSynth), C.POINTER(McIrSpring), C.POINTER(McIrShape), C.POINTER(McIrEq), C.POINTER(McIrDamp),
+                                     C.POINTER(McIrTail)]
+    L.mc_ir_spring_plan.argtypes = [C.POINTER(McIrSpring), C.c_uint32, u64, C.POINTER(C.c_double)]
+    L.mc_ir_spring_response.argtypes = [C.POINTER(McIrSpring), C.c_uint32, C.POINTER(C.c_double), C.c_uint32, C.POINTER(C.c_double)]
+    L.mc_ir_spring_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_num_irs.argtypes = [vp]
     L.mc_ir_info.argtypes = [vp, u64, C.POINTER(C.c_double)]
     L.mc_set_params.argtypes = [vp, C.c_int, C.POINTER(McCcValue)]

@@ -31,6 +31,7 @@
 #include "irdamp.hip.h"
 #include "irdecay.hip.h"
 #include "irplate.hip.h"
+#include "irspring.hip.h"
 #include "irroom.hip.h"
 #include "irsynth.hip.h"
 #include "irsweep.hip.h"
@@ -102,13 +103,13 @@ inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline double pan_l(double p) { return p >= 0 ? 1 - p : 1; }  // conv.cu:386
 inline double pan_r(double p) { return p <= 0 ? 1 + p : 1; }  // conv.cu:387
 
-// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _phase_info, _filter_info, _match_info, _parts_info, _room_info, _room_mics_info, _room_bands_info, _room_head_info and _plate_info report of an IR's last
+// What mc_ir_shape_info, _damp_info, _synth_info, _sweep_info, _tail_info, _phase_info, _filter_info, _match_info, _parts_info, _room_info, _room_mics_info, _room_bands_info, _room_head_info, _plate_info and _spring_info report of an IR's last
 // load: one entry per kind, on when that load had the step or the source (a shape with something on, an eq band or damping count as a shape, and
 // so do a synthesised, a swept and a tailed load), with the numbers the getter hands out (include/mcconv.h says what they are)
-enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_PHASE, FACT_FILTER, FACT_MATCH, FACT_PARTS, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_ROOM_HEAD, FACT_PLATE, FACT_KINDS };
+enum IrFactKind { FACT_SHAPE, FACT_DAMP, FACT_SYNTH, FACT_SWEEP, FACT_TAIL, FACT_PHASE, FACT_FILTER, FACT_MATCH, FACT_PARTS, FACT_ROOM, FACT_ROOM_MICS, FACT_ROOM_BANDS, FACT_ROOM_HEAD, FACT_PLATE, FACT_SPRING, FACT_KINDS };
 struct IrFact {
     bool on = false;
-    double v[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    double v[24] = {};
 };
 
 struct IrEntry {
@@ -3297,6 +3298,11 @@ struct PlateStep {
     PlatePlan plan;
 };
 
+// the spring tank of a synthesised load as load_ir and shape_stage take it: the checked spring with its constants (irspring.hip.h)
+struct SpringStep {
+    SpringPlan plan;
+};
+
 // One load as load_ir and shape_stage take it: where the frames come from, and the steps they go through on the device.  The
 // entry points fill it in by name; a null pointer is a source that is not this load's, or a step that is off.
 struct IrLoad {
@@ -3311,6 +3317,8 @@ struct IrLoad {
                                        // room->bands, joined by the band split (mc_synth_ir_room_bands)
     const PlateStep* plate = nullptr;  // mc_synth_ir_plate (irplate.hip.h; with syn and without room): the sum of its modes is added
                                        // to the generated frames
+    const SpringStep* spring = nullptr;  // mc_synth_ir_spring (irspring.hip.h; with syn and without room and plate): the tank's
+                                         // response is added to the generated frames
     const SweepSource* swp = nullptr;  // mc_load_ir_sweep (irsweep.hip.h): the frames are deconvolved on the device from its recording
     // -- the steps, in the order they run.  Any of tail, eq, damp, syn and swp needs the shape, which may have everything off
     const TailStep* tail = nullptr;      // step 1a, between the source and the shaping (irtail.hip.h; tail->plan.F = the frames at the session's rate)
@@ -3358,6 +3366,7 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
                     : ld.syn && ld.room && ld.room->banded ? room_generate_bands(e->stream, *ld.syn, ld.room->bands, d_x, ld.room->kept)
                     : ld.syn && ld.room ? room_generate(e->stream, *ld.syn, ld.room->plan, d_x, ld.room->kept)
                     : ld.syn && ld.plate ? plate_generate(e->stream, *ld.syn, ld.plate->plan, d_x)
+                    : ld.syn && ld.spring ? spring_generate(e->stream, *ld.syn, ld.spring->plan, d_x)
                     : ld.syn ? syn_generate(e->stream, *ld.syn, d_x)
                     : ld.rs ? rs_convert(e->stream, ld.rs[0], ld.rs[1], ld.lr, ld.frames, d_x, conv, unused)
                             : hipMemcpy(d_x, ld.lr, sizeof(float2) * conv, hipMemcpyHostToDevice);
@@ -3446,6 +3455,10 @@ void note_load(IrEntry& ir, const IrLoad& ld, uint64_t taps, const ShapedTaps& s
     if (ld.plate) {
         const PlatePlan& p = ld.plate->plan;
         put(FACT_PLATE, {(double)p.M, (double)p.nonzero[0], (double)p.nonzero[1], (double)p.E, p.lo, p.hi, p.kappa, 0.0});
+    }
+    if (ld.spring) {
+        ir.facts[FACT_SPRING].on = true;
+        spring_numbers(ld.spring->plan, ir.facts[FACT_SPRING].v);
     }
 }
 
@@ -3600,7 +3613,7 @@ const char* resolve_steps(const mc_ir_shape* shape, const mc_ir_eq* eq, const mc
     return nullptr;
 }
 
-// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, phase, filter, match, parts, room, room mics, room bands, room head, plate): out = the first `count` numbers of what
+// The mc_ir_*_info getters (shape, damp, synth, sweep, tail, phase, filter, match, parts, room, room mics, room bands, room head, plate, spring): out = the first `count` numbers of what
 // note_load kept of that kind, or MC_ERR_STATE with "IR <idx> <was_not>" when the last load had none
 int ir_fact(const mc_engine* e, uint64_t idx, IrFactKind kind, int count, const char* was_not, double* out) {
     if (!e || !out || idx >= (uint64_t)kMaxIrs || !(e->irs[idx].d_H || e->irs[idx].d_S)) return fail(MC_ERR_ARG, "IR %llu not loaded", (unsigned long long)idx);
@@ -4143,6 +4156,77 @@ int mc_ir_plate_modes(const mc_ir_plate* plate, uint32_t rate, uint64_t first, u
 }
 
 int mc_ir_plate_info(const mc_engine* e, uint64_t idx, double out[8]) { return ir_fact(e, idx, FACT_PLATE, 8, "was not loaded with a plate", out); }
+
+void mc_default_ir_spring(mc_ir_spring* s) {
+    if (!s) return;
+    std::memset(s, 0, sizeof(*s));
+    s->struct_size = (uint32_t)sizeof(*s);
+    s->sections = 100;
+    s->transition_hz = 4300.f;
+    s->dispersion = 0.62f;
+    s->delay_ms[0] = 66.f, s->delay_ms[1] = 82.f;
+    s->t60_s = 2.5f;
+    s->damping = 0.2f;
+    s->lowpass_order = 8;
+    s->high_gain = 0.1f;
+    s->high_sections = 200;
+    s->high_dispersion = -0.6f;
+    s->high_delay = 0.5f;
+    s->high_t60_s = 1.f;
+    s->stereo = 0.03f;
+    s->gain = 1.f;
+}
+
+int mc_synth_ir_spring(mc_engine* e, uint64_t idx, uint64_t nframes, const mc_ir_synth* synth, const mc_ir_spring* spring, const mc_ir_shape* shape,
+                       const mc_ir_eq* eq, const mc_ir_damp* damp, const mc_ir_tail* tail) {
+    if (!spring) return mc_synth_ir_room(e, idx, nframes, synth, nullptr, shape, eq, damp, tail);
+    // synth, then the spring, then the tail with F' after F, then damp, eq and shape as in mc_synth_ir_plate, all before the engine
+    // and before any HIP call
+    if (const char* bad = syn_check(synth)) return fail(MC_ERR_ARG, "%s", bad);
+    const uint32_t rate = synth->rate;
+    const uint64_t F = synth->frames;
+    SpringStep sstep;
+    if (const char* bad = spring_check(spring, rate, F, &sstep.plan)) return fail(MC_ERR_ARG, "%s", bad);
+    const bool tailed = tail && tail->mode != MC_TAIL_OFF;
+    if (tailed) {
+        if (const char* bad = tail_check(tail, rate)) return fail(MC_ERR_ARG, "%s", bad);
+        if (const char* bad = tail_check_frames(tail, F)) return fail(MC_ERR_ARG, "%s", bad);
+    }
+    IrSteps steps;
+    if (const char* bad = resolve_steps(shape, eq, damp, rate, rate, &steps)) return fail(MC_ERR_ARG, "%s", bad);
+    const SynPlan syn = syn_plan(*synth);
+    TailStep step{};
+    if (tailed) step = tail_step(*tail, rate, F);
+    IrLoad ld;
+    ld.syn = &syn, ld.frames = F;
+    ld.spring = &sstep;
+    ld.tail = tailed ? &step : nullptr;
+    steps.into(ld);
+    return load_ir(e, idx, nframes, ld);
+}
+
+int mc_ir_spring_plan(const mc_ir_spring* spring, uint32_t rate, uint64_t frames, double out[24]) {
+    if (frames < 1 || frames > SYN_MAX_FRAMES)
+        return fail(MC_ERR_ARG, "frames %llu outside [1, %llu]", (unsigned long long)frames, (unsigned long long)SYN_MAX_FRAMES);
+    SpringPlan p;
+    if (const char* bad = spring_check(spring, rate, frames, &p)) return fail(MC_ERR_ARG, "%s", bad);
+    if (!out) return fail(MC_ERR_ARG, "null out");
+    spring_numbers(p, out);
+    return MC_OK;
+}
+
+int mc_ir_spring_response(const mc_ir_spring* spring, uint32_t rate, const double* hz, uint32_t n, double* out_re_im) {
+    SpringPlan p;
+    if (const char* bad = spring_check(spring, rate, 0, &p)) return fail(MC_ERR_ARG, "%s", bad);
+    if (n && (!hz || !out_re_im)) return fail(MC_ERR_ARG, "null hz or out_re_im");
+    for (uint32_t i = 0; i < n; i++) {
+        if (!std::isfinite(hz[i])) return fail(MC_ERR_ARG, "hz[%u] is not finite", i);
+        spring_response(p.k, rate, hz[i], out_re_im + 4 * (size_t)i);
+    }
+    return MC_OK;
+}
+
+int mc_ir_spring_info(const mc_engine* e, uint64_t idx, double out[24]) { return ir_fact(e, idx, FACT_SPRING, 24, "was not loaded with a spring", out); }
 
 int mc_ir_synth_info(const mc_engine* e, uint64_t idx, double out[4]) { return ir_fact(e, idx, FACT_SYNTH, 4, "was not synthesised", out); }
 

@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _lib
-from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrPlate, McIrRoom, McIrRoomBands, McIrRoomHead, McIrRoomMics, McIrFilter, McIrMatch, McIrPhase, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
+from ._lib import (MC_BLOCK, McCcValue, McConfig, McDecayQuery, McDensityQuery, McFloorQuery, McIaccQuery, McStiQuery, McResponseQuery, McResponseWindow, McIrDamp, McIrEq, McIrPlate, McIrSpring, McIrRoom, McIrRoomBands, McIrRoomHead, McIrRoomMics, McIrFilter, McIrMatch, McIrPhase, McIrShape, McIrSynth, McIrTail, McKernelStats, McSweep,
                    check)
 
 CONV_DEFAULT_FFTSIZE = 512 * 256  # conv.h:10-12
@@ -660,6 +660,76 @@ def room_plan(room, rate, frames):
 
 
 @dataclasses.dataclass
+class IrSpring:
+    """The spring tank whose response prepare_synth(spring=...) adds to a synthesised IR (mc_ir_spring, include/mcconv.h): up
+    to three springs of round-trip times `delay_ms`, each a loop of `sections` all-pass sections of coefficient `dispersion`
+    stretched so that the chirps end at `transition_hz`, a one-pole `damping` and the gain that `t60` seconds make; a
+    Butterworth low-pass of `lowpass_order` at the transition; a second, weaker family of chirps above it (`high_gain`, 0:
+    off, `high_sections`, `high_dispersion`, `high_delay` as a part of the period, `high_t60`); channel R's periods are
+    (1 + stereo) times channel L's.  `log2_points` (0: by the length) fixes the transform's size; frames at and after `last`
+    (0: the IR's length) get nothing from the spring."""
+
+    sections: int = 100
+    transition_hz: float = 4300.0
+    dispersion: float = 0.62
+    delay_ms: tuple = (66.0, 82.0)
+    t60: float = 2.5
+    damping: float = 0.2
+    lowpass_order: int = 8
+    high_gain: float = 0.1
+    high_sections: int = 200
+    high_dispersion: float = -0.6
+    high_delay: float = 0.5
+    high_t60: float = 1.0
+    stereo: float = 0.03
+    gain: float = 1.0
+    log2_points: int = 0
+    last: int = 0
+
+    def to_c(self):
+        delays = tuple(self.delay_ms) if isinstance(self.delay_ms, (tuple, list)) else (self.delay_ms,)
+        if not 1 <= len(delays) <= 3:
+            raise ValueError("delay_ms takes one to three numbers")
+        p = McIrSpring()
+        _lib.load().mc_default_ir_spring(C.byref(p))
+        for k in range(3):
+            p.delay_ms[k] = float(delays[k]) if k < len(delays) else 0.0
+        p.sections, p.lowpass_order, p.high_sections, p.log2_points, p.last = (int(self.sections), int(self.lowpass_order), int(self.high_sections),
+                                                                               int(self.log2_points), int(self.last))
+        p.transition_hz, p.dispersion, p.t60_s, p.damping = float(self.transition_hz), float(self.dispersion), float(self.t60), float(self.damping)
+        p.high_gain, p.high_dispersion, p.high_delay, p.high_t60_s = float(self.high_gain), float(self.high_dispersion), float(self.high_delay), float(self.high_t60)
+        p.stereo, p.gain = float(self.stereo), float(self.gain)
+        return p
+
+
+def _spring_numbers(out):
+    springs = int(out[3])
+    return dict(points=int(out[0]), stretch=int(out[1]), transition=out[2], springs=springs, sections=int(out[4]), lowpass=bool(out[5]), last=int(out[6]),
+                alias_db=out[7], delay=[(int(out[8 + 2 * s]), int(out[9 + 2 * s])) for s in range(springs)],
+                loop_gain=[(out[14 + 2 * s], out[15 + 2 * s]) for s in range(springs)])
+
+
+def spring_plan(spring, rate, frames):
+    """What a load of `frames` frames at `rate` would do with `spring` (an IrSpring; mc_ir_spring_plan, host arithmetic only):
+    the transform's points N, the stretch K, the effective transition rate / (2 K) in Hz, the springs, the sections, whether
+    the low-pass is in, the frame E from which the spring adds nothing, the bound in dB on what wraps around relative to the
+    first echo, and per spring (L, R) the loop's delay in frames and its gain."""
+    out = (C.c_double * 24)()
+    check(_lib.load().mc_ir_spring_plan(C.byref(spring.to_c()), int(rate), int(frames), out))
+    return _spring_numbers(out)
+
+
+def spring_response(spring, rate, hz):
+    """H_L and H_R of `spring` at `rate` on the unit circle at the frequencies hz (mc_ir_spring_response, host arithmetic
+    through the functions that make the kernel's constants) as complex128 [len(hz), 2]."""
+    hz = np.ascontiguousarray(hz, np.float64).reshape(-1)
+    out = np.zeros((hz.shape[0], 4), np.float64)
+    dp = C.POINTER(C.c_double)
+    check(_lib.load().mc_ir_spring_response(C.byref(spring.to_c()), int(rate), hz.ctypes.data_as(dp), hz.shape[0], out.ctypes.data_as(dp)))
+    return np.stack([out[:, 0] + 1j * out[:, 1], out[:, 2] + 1j * out[:, 3]], axis=1)
+
+
+@dataclasses.dataclass
 class IrPlate:
     """The plate reverberator whose modes prepare_synth(plate=...) adds to a synthesised IR (mc_ir_plate, include/mcconv.h): a
     thin simply supported rectangular sheet of `size` (Lx, Ly) metres and `thickness_mm`, of `material` "steel" or (Young's
@@ -1183,7 +1253,7 @@ class Convolution:
         steps, keep = _c_steps(shape, eq, damp, tail, phase, filter, match, parts)
         check(self._L.mc_load_ir_parts(self._h, idx, _fp(lr), lr.shape[0], nframes, *rates, *steps))
 
-    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None, room=None, tail=None, mics=None, bands=None, plate=None, head=None):
+    def prepare_synth(self, idx, synth, nframes=1024, shape=None, eq=None, damp=None, room=None, tail=None, mics=None, bands=None, plate=None, head=None, spring=None):
         """Generate the IR `synth` (an IrSynth) describes on the device and store it at idx (mc_synth_ir): the frames take the
         place of a WAV's at the session's rate, and shape, eq and damp apply to them as in prepare().  A synthesised IR counts
         as shaped: ir_shape_info(idx)["frames"] is synth.frames.  The engine's sample_rate (which eq, damp, room and tail
@@ -1196,10 +1266,18 @@ class Convolution:
         room): a rigid-sphere listener takes the receiver pair's place and the IR is binaural; ir_room_head_info(idx) then
         tells the ears' delays and shadow factors.
         plate (an IrPlate, without room, mics and bands): the modes of a plate reverberator are added to the frames
-        (mc_synth_ir_plate); ir_plate_info(idx) then tells what was summed."""
+        (mc_synth_ir_plate); ir_plate_info(idx) then tells what was summed.
+        spring (an IrSpring, without room, mics, bands, head and plate): the response of a spring tank is added to the
+        frames (mc_synth_ir_spring); ir_spring_info(idx) then tells the plan it was rendered by."""
+        if spring is not None and any(v is not None for v in (room, mics, bands, head, plate)):
+            raise ValueError("a spring together with a room (room, mics, bands, head) or a plate in one load is not offered")
         s = synth.to_c()
         if not s.rate:
             s.rate = int(self.sample_rate or 0)
+        if spring is not None:
+            steps, keep = _c_steps(shape, eq, damp, tail, None, None, None, None)
+            check(self._L.mc_synth_ir_spring(self._h, idx, nframes, C.byref(s), C.byref(spring.to_c()), *steps[:4]))
+            return
         if plate is not None:
             if room is not None or mics is not None or bands is not None or head is not None:
                 raise ValueError("a plate and a room (room, mics, bands, head) in one load are not offered")
@@ -1374,6 +1452,13 @@ class Convolution:
         out = (C.c_double * 8)()
         check(self._L.mc_ir_room_info(self._h, idx, out))
         return dict(order=int(out[0]), images=(int(out[1]), int(out[2])), direct=(out[3], out[4]), last=int(out[5]), complete=int(out[6]))
+
+    def ir_spring_info(self, idx):
+        """The plan the spring of IR idx's load was rendered by (mc_ir_spring_info), as spring_plan reports it.  McError
+        (MC_ERR_STATE) for an IR whose last load had no spring."""
+        out = (C.c_double * 24)()
+        check(self._L.mc_ir_spring_info(self._h, idx, out))
+        return _spring_numbers(out)
 
     def ir_plate_info(self, idx):
         """What the plate of IR idx's load summed (mc_ir_plate_info): the modes kept, those with a non-zero amplitude per

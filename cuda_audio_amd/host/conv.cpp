@@ -129,6 +129,11 @@ void mc_default_ir_plate(mc_ir_plate*) __attribute__((weak));
 int mc_synth_ir_plate(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_plate*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
                       const mc_ir_tail*) __attribute__((weak));
 int mc_ir_plate_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
+// ... or no spring
+void mc_default_ir_spring(mc_ir_spring*) __attribute__((weak));
+int mc_synth_ir_spring(mc_engine*, uint64_t, uint64_t, const mc_ir_synth*, const mc_ir_spring*, const mc_ir_shape*, const mc_ir_eq*, const mc_ir_damp*,
+                       const mc_ir_tail*) __attribute__((weak));
+int mc_ir_spring_info(const mc_engine*, uint64_t, double*) __attribute__((weak));
 }
 
 namespace {
@@ -360,6 +365,7 @@ void Convolution::loadIr(const IrLoadRequest& r) {
         {nullptr, r.mics.has_value(), mc_synth_ir_room_mics && mc_default_ir_room_mics && mc_ir_room_mics_info, "directional microphones in its rooms (mc_synth_ir_room_mics)"},
         {nullptr, r.room.has_value(), mc_synth_ir_room && mc_default_ir_room && mc_ir_room_info, "room rendering (mc_synth_ir_room)"},
         {nullptr, r.plate.has_value(), mc_synth_ir_plate && mc_default_ir_plate && mc_ir_plate_info, "plate synthesis (mc_synth_ir_plate)"},
+        {nullptr, r.spring.has_value(), mc_synth_ir_spring && mc_default_ir_spring && mc_ir_spring_info, "spring synthesis (mc_synth_ir_spring)"},
         {r.phase && generated ? "phase" : nullptr, minimum, mc_default_ir_phase && mc_load_ir_phase && mc_load_ir_sweep_phase && mc_ir_phase_info, "phase step (mc_load_ir_phase)"},
         {r.filter && generated ? "filter" : nullptr, filtered, mc_default_ir_filter && mc_load_ir_filter && mc_load_ir_sweep_filter && mc_ir_filter_info, "filter step (mc_load_ir_filter)"},
         {r.match && generated ? "match" : nullptr, matched, mc_default_ir_match && mc_load_ir_match && mc_load_ir_sweep_match && mc_ir_match_info && mc_ir_match_curve, "match step (mc_load_ir_match)"},
@@ -423,6 +429,7 @@ void Convolution::loadIr(const IrLoadRequest& r) {
                        : mics ? mc_synth_ir_room_mics(_engine, idx, r.nframes, y, room, mics, &s, q, d, t)
                        : room ? mc_synth_ir_room(_engine, idx, r.nframes, y, room, &s, q, d, t)
                        : r.plate ? mc_synth_ir_plate(_engine, idx, r.nframes, y, &*r.plate, &s, q, d, t)
+                       : r.spring ? mc_synth_ir_spring(_engine, idx, r.nframes, y, &*r.spring, &s, q, d, t)
                               : mc_synth_ir(_engine, idx, r.nframes, y, &s, q, d);
         if (rc != MC_OK) {
             Log::error("conv", "IR %zu cannot be synthesised: %s", idx, mc_last_error());
@@ -467,6 +474,19 @@ void Convolution::loadIr(const IrLoadRequest& r) {
         check(mc_ir_plate_info(_engine, idx, pi), "mc_ir_plate_info");
         Log::info(name, "IR %zu plate: %llu modes from %.2f to %.2f Hz, %llu and %llu sounding, before frame %llu, kappa %.4f m^2/s", idx,
                   (unsigned long long)pi[0], pi[4], pi[5], (unsigned long long)pi[1], (unsigned long long)pi[2], (unsigned long long)pi[3], pi[6]);
+    }
+    if (r.spring) {
+        double si[24];
+        check(mc_ir_spring_info(_engine, idx, si), "mc_ir_spring_info");
+        std::string delays;
+        for (int k = 0; k < (int)si[3]; k++) {
+            char one[64];
+            std::snprintf(one, sizeof(one), "%s%llu/%llu", k ? ", " : "", (unsigned long long)si[8 + 2 * k], (unsigned long long)si[9 + 2 * k]);
+            delays += one;
+        }
+        Log::info(name, "IR %zu spring: %llu points, K %llu (transition %.1f Hz), %llu sections, low-pass %s, %llu springs with delays %s frames (L/R), before frame %llu, alias bound %.1f dB",
+                  idx, (unsigned long long)si[0], (unsigned long long)si[1], si[2], (unsigned long long)si[4], si[5] != 0.0 ? "in" : "out", (unsigned long long)si[3],
+                  delays.c_str(), (unsigned long long)si[6], si[7]);
     }
     if (r.room) {
         double ri[8];
@@ -1099,7 +1119,7 @@ std::optional<mc_ir_tail> Convolution::measureTail(const PendingIr& p) {
         Log::error("conv", "the engine has no tail step (mc_load_ir_tail)");
         std::exit(2);
     }
-    if (p.generated && !p.roomed && !p.plated) {
+    if (p.generated && !p.roomed && !p.plated && !p.sprung) {
         Log::info(name, "IR %zu tail: a generated IR has no floor, left as it is", p.idx);
         return std::nullopt;
     }
@@ -1899,6 +1919,143 @@ void Convolution::preparePlate(size_t idx, const IrPlate& plate, size_t nframes)
     p.plate = plate;
 }
 
+mc_ir_spring Convolution::springFrames(const IrSpring& spring, double rate) {
+    mc_ir_spring s;
+    mc_default_ir_spring(&s);
+    s.sections = spring.sections;
+    s.transition_hz = spring.transition, s.dispersion = spring.dispersion;
+    for (int k = 0; k < 3; k++) s.delay_ms[k] = spring.delayMs[k];
+    s.t60_s = spring.t60, s.damping = spring.damping;
+    s.lowpass_order = spring.lowpass;
+    s.high_gain = spring.high, s.high_sections = spring.highSections;
+    s.high_dispersion = spring.highDispersion, s.high_delay = spring.highDelay, s.high_t60_s = spring.highT60;
+    s.stereo = spring.stereo, s.gain = spring.gain;
+    s.log2_points = spring.points;
+    s.last = (uint64_t)std::nearbyint(spring.lastSeconds * rate);
+    return s;
+}
+
+bool Convolution::parseSpring(const std::string& line, IrSpring& out, std::string& why) {
+    static const char* form =
+        "spring:LENGTH_S[:key=value,...] with keys sections, fc=HZ (the transition), a (the dispersion), delay=MS[,MS[,MS]] (one per spring), t60=S, damping, "
+        "lowpass=ORDER, high (the high chirps' gain), highsections, higha, highdelay (a part of the period), hight60=S, stereo, gain, points (log2 of the "
+        "transform's size), last=S";
+    std::vector<std::string> parts;
+    for (size_t at = 0;;) {
+        const size_t colon = line.find(':', at);
+        parts.push_back(line.substr(at, colon == std::string::npos ? colon : colon - at));
+        if (colon == std::string::npos) break;
+        at = colon + 1;
+    }
+    if (parts.size() < 2 || parts.size() > 3 || parts[0] != "spring") {
+        why = std::string("a spring is ") + form;
+        return false;
+    }
+    const auto number = [](const std::string& text, double& v) {
+        char* end = nullptr;
+        v = std::strtod(text.c_str(), &end);
+        return !text.empty() && end == text.c_str() + text.size() && std::isfinite(v);
+    };
+    // a whole number that fills the text
+    const auto count = [&](const std::string& text, unsigned& v) {
+        double x;
+        if (!number(text, x) || x < 0.0 || x > 1e6 || x != std::floor(x)) return false;
+        v = (unsigned)x;
+        return true;
+    };
+    IrSpring spring;
+    if (!number(parts[1], spring.lengthSeconds) || !(spring.lengthSeconds > 0.0)) {
+        why = "LENGTH_S '" + parts[1] + "' is not a length in seconds, > 0";
+        return false;
+    }
+    const std::string list = parts.size() == 3 ? parts[2] : "";
+    if (parts.size() == 3 && list.empty()) {
+        why = std::string("nothing after the last colon: ") + form;
+        return false;
+    }
+    // the items: a comma starts a new one when key= follows it, and belongs to the value before it otherwise (delay=MS,MS)
+    std::vector<std::string> items;
+    for (size_t at = 0; at < list.size() || (at && at == list.size());) {
+        const size_t comma = std::min(list.find(',', at), list.size());
+        const std::string piece = list.substr(at, comma - at);
+        if (piece.find('=') != std::string::npos || items.empty() || piece.empty())
+            items.push_back(piece);
+        else
+            items.back() += "," + piece;
+        at = comma + 1;
+        if (comma == list.size()) break;
+    }
+    for (const std::string& item : items) {
+        const size_t eq = item.find('=');
+        if (eq == std::string::npos) {
+            why = "'" + item + "' is not key=value";
+            return false;
+        }
+        const std::string key = item.substr(0, eq), text = item.substr(eq + 1);
+        double v = 0.0;
+        bool good = true;
+        if (key == "delay") {  // one to three periods in milliseconds, > 0; the springs not named are absent
+            size_t at = 0;
+            int k = 0;
+            for (; good && at <= text.size(); k++) {
+                const size_t end = std::min(text.find(',', at), text.size());
+                good = k < 3 && number(text.substr(at, end - at), v) && v > 0.0;
+                if (good) spring.delayMs[k] = (float)v;
+                at = end + 1;
+            }
+            for (; good && k < 3; k++) spring.delayMs[k] = 0.0f;
+        } else if (key == "sections") {
+            good = count(text, spring.sections);
+        } else if (key == "lowpass") {
+            good = count(text, spring.lowpass);
+        } else if (key == "highsections") {
+            good = count(text, spring.highSections);
+        } else if (key == "points") {
+            good = count(text, spring.points);
+        } else if (key == "higha") {  // (the one key whose value is at most 0)
+            good = number(text, v) && v <= 0.0;
+            spring.highDispersion = (float)v;
+        } else if (key == "fc" || key == "a" || key == "t60" || key == "damping" || key == "high" || key == "highdelay" || key == "hight60" || key == "stereo" ||
+                   key == "gain") {
+            good = number(text, v) && v >= 0.0;
+            (key == "fc"          ? spring.transition
+             : key == "a"         ? spring.dispersion
+             : key == "t60"       ? spring.t60
+             : key == "damping"   ? spring.damping
+             : key == "high"      ? spring.high
+             : key == "highdelay" ? spring.highDelay
+             : key == "hight60"   ? spring.highT60
+             : key == "stereo"    ? spring.stereo
+                                  : spring.gain) = (float)v;
+        } else if (key == "last") {
+            good = number(text, v) && v >= 0.0;
+            spring.lastSeconds = v;
+        } else {
+            why = "unknown key '" + key + "': " + form;
+            return false;
+        }
+        if (!good) {
+            why = "'" + text + "' is no value for " + key;
+            return false;
+        }
+    }
+    out = spring;
+    return true;
+}
+
+void Convolution::prepareSpring(size_t idx, const IrSpring& spring, size_t nframes) {
+    if (_group) {
+        Log::error("conv", "spring synthesis is not available with several devices (mc_synth_ir_spring is single-engine)");
+        std::exit(2);
+    }
+    PendingIr& p = pend(idx, nframes);  // (generated by onStart(), once the client's rate is known)
+    p.generated = p.sprung = true;
+    p.synth = IrSynth();
+    p.synth.lengthSeconds = spring.lengthSeconds;
+    p.synth.late = 0.0f;  // (the spring alone: no late field under it)
+    p.spring = spring;
+}
+
 // A new entry of _pendingIrs with what every kind of IR has: its place, and the shape, EQ and damping that are set now
 Convolution::PendingIr& Convolution::pend(size_t idx, size_t nframes) {
     _pendingIrs.emplace_back();
@@ -2116,12 +2273,17 @@ Convolution::IrLoadRequest Convolution::requestFor(const PendingIr& p) {
             Log::error("conv", "the engine has no plate synthesis (mc_synth_ir_plate)");
             std::exit(2);
         }
+        if (p.sprung && !mc_default_ir_spring) {
+            Log::error("conv", "the engine has no spring synthesis (mc_synth_ir_spring)");
+            std::exit(2);
+        }
         if (!mc_default_ir_synth) {
             Log::error("conv", "the engine has no IR synthesis (mc_synth_ir)");
             std::exit(2);
         }
         r.synth = synthFrames(p.roomed ? p.room.late : p.synth, (double)samplerate);
         if (p.plated) r.plate = plateFrames(p.plate, (double)samplerate);
+        if (p.sprung) r.spring = springFrames(p.spring, (double)samplerate);
         if (p.roomed) r.room = roomFrames(p.room, (double)samplerate);
         if (p.roomed && p.room.directional) r.mics = roomMics(p.room);
         if (p.roomed && p.room.banded) r.bands = roomBands(p.room);

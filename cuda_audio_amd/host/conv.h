@@ -257,6 +257,34 @@ public:
     // mc_ir_plate of an IrPlate at rate Hz
     static mc_ir_plate plateFrames(const IrPlate& plate, double rate);
 
+    // A spring reverberation tank whose response the engine evaluates bin by bin (mc_ir_spring and mc_synth_ir_spring of
+    // include/mcconv.h; no reference equivalent): Hz, milliseconds and seconds, the length and `last` turned into frames at the
+    // client's sample rate by rint, so prepareSpring() keeps the numbers and onStart() generates.  What is not given is
+    // mc_default_ir_spring's.  The shape, EQ, damping, tail, reports and rt60 aim that are set apply as to a WAV.  One more log
+    // line per IR: the transform's size, the stretch and the transition, the springs' delays and the alias bound.  Single device
+    // only, as setIrShape.
+    struct IrSpring {
+        double lengthSeconds = 1.0;
+        unsigned sections = 100;
+        float transition = 4300.0f, dispersion = 0.62f;
+        float delayMs[3] = {66.0f, 82.0f, 0.0f};
+        float t60 = 2.5f, damping = 0.2f;
+        unsigned lowpass = 8;
+        float high = 0.1f;
+        unsigned highSections = 200;
+        float highDispersion = -0.6f, highDelay = 0.5f, highT60 = 1.0f;
+        float stereo = 0.03f, gain = 1.0f;
+        unsigned points = 0;  // log2 of the transform's size, 0 = by the length
+        double lastSeconds = 0.0;
+    };
+    void prepareSpring(size_t idx, const IrSpring& spring, size_t nframes = 1024);
+    // A line of an IR index that starts with "spring:" - spring:LENGTH_S[:key=value,...], keys sections, fc=HZ, a,
+    // delay=MS[,MS[,MS]], t60=S, damping, lowpass=ORDER, high, highsections, higha, highdelay, hight60=S, stereo, gain, points and
+    // last=S - as an IrSpring.  False, with the reason in `why`, for a malformed line.
+    static bool parseSpring(const std::string& line, IrSpring& out, std::string& why);
+    // mc_ir_spring of an IrSpring at rate Hz
+    static mc_ir_spring springFrames(const IrSpring& spring, double rate);
+
     // An IR the engine deconvolves from the recording of an exponential sine sweep played through a room (mc_sweep and
     // mc_load_ir_sweep of include/mcconv.h; no reference equivalent): times in seconds, turned into frames at the client's
     // sample rate by rint, so prepareSweep() keeps the numbers and the recording and onStart() deconvolves.  The recording
@@ -531,6 +559,8 @@ private:
         IrRoom room = IrRoom();
         bool plated = false;  // preparePlate: generated, `plate` and nothing of `synth` but its length
         IrPlate plate = IrPlate();
+        bool sprung = false;  // prepareSpring: generated, `spring` and nothing of `synth` but its length
+        IrSpring spring = IrSpring();
     };
     struct SweepLoad {  // the arguments of mc_load_ir_sweep beside the recording
         mc_sweep sweep;
@@ -557,6 +587,7 @@ private:
         std::optional<mc_ir_room_bands> bands;
         std::optional<mc_ir_room_head> head;
         std::optional<mc_ir_plate> plate;  // with synth and without room: the modes of a plate are added (mc_synth_ir_plate)
+        std::optional<mc_ir_spring> spring;  // with synth and without room and plate: a spring tank's response is added (mc_synth_ir_spring)
         std::optional<SweepLoad> sweep;
         // The steps, in the order the frames go through them: tail, phase, filter, match, parts (null = off; they point at the
         // object's settings, whose second IRs are not copied), then shape, damp, eq.  A generated IR goes through the tail (with a

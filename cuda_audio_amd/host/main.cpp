@@ -36,6 +36,10 @@
 // size=LX,LY, thick=MM, material=steel|E/RHO/NU, drive=X,Y, pick=X,Y/X,Y, low=HZ, high=HZ, t60=LO/HI, damp=HZ, gain, last=S
 // (Convolution::parsePlate; metres, millimetres and seconds); the --ir-* options apply to it as to a WAV, and one more log line
 // tells the modes kept.
+// A line that starts with "spring:" is a spring reverberation tank whose response the engine evaluates bin by bin,
+// spring:LENGTH_S[:key=value,...] with keys sections, fc=HZ, a, delay=MS[,MS[,MS]], t60=S, damping, lowpass=ORDER, high, highsections,
+// higha, highdelay, hight60=S, stereo, gain, points, last=S (Convolution::parseSpring; Hz, milliseconds and seconds); the --ir-*
+// options apply to it as to a WAV, and one more log line tells the transform's size, the delays and the alias bound.
 // A line that starts with "sweep:" is an IR the engine deconvolves from the recording of a sine sweep,
 // sweep:RECORDING.wav:LENGTH_S:F1:F2[:key=value,...] with keys amp, fadein, fadeout, offset, length (Convolution::parseSweep;
 // times in seconds, the recording at the client's sample rate); the --ir-* options apply to it as to a WAV.
@@ -428,6 +432,16 @@ int main(int argc, char** argv) {
                         return 2;
                     }
                     c->preparePlate(j, plate);
+                    continue;
+                }
+                if (!path.compare(0, 7, "spring:")) {  // a spring tank instead of a WAV path
+                    Convolution::IrSpring spring;
+                    std::string why;
+                    if (!Convolution::parseSpring(path, spring, why)) {
+                        std::cerr << "index line '" << path << "': " << why << std::endl;
+                        return 2;
+                    }
+                    c->prepareSpring(j, spring);
                     continue;
                 }
                 if (!path.compare(0, 6, "sweep:")) {  // an IR deconvolved from a recorded sweep

@@ -1410,6 +1410,98 @@ int mc_ir_plate_modes(const mc_ir_plate *plate, uint32_t rate, uint64_t first, u
  * unless the IR's last load had a plate */
 int mc_ir_plate_info(const mc_engine *e, uint64_t idx, double out[8]);
 
+/* A spring reverberation tank (up to three helical springs between a driver and a pickup), added on the device to the frames
+ * mc_ir_synth describes.  A spring is neither a room nor a plate: the helix is strongly dispersive, so every echo is a chirp
+ * (below a transition frequency of a few kHz the lows arrive first and the highs tens of milliseconds later; a much weaker
+ * second family of chirps lies above it), and the echoes repeat at the spring's round-trip time.  The model is the parametric
+ * one of Valimaki, Parker and Abel (JAES 2010): a cascade of stretched all-pass sections in a feedback loop with a delay.  In
+ * time that recursion is serial; as a transfer function it is closed form at every z, so the device evaluates it bin by bin,
+ * transforms once and undoes a radius.  No reference equivalent; single-engine and load-time only, as shaping is.
+ *
+ * Everything is computed in double from the float fields; rate = synth->rate, F = synth->frames; round is to nearest, ties to
+ * even.
+ * Springs.  Spring s is present when delay_ms[s] != 0; the present ones come first, at least one is present, S is their count.
+ *   Channel L uses the period T_s = delay_ms[s] / 1000, channel R T_s (1 + stereo).
+ * Low chirps.  K = max(1, round(rate / (2 transition_hz))), at most MC_SPRING_MAX_STRETCH; f_t = rate / (2 K).
+ *   A(z) = (a + z^-K) / (1 + a z^-K), a = dispersion; C = A^M, M = sections (M = 0: C = 1).
+ *   P(z) = (1 - c) / (1 - c z^-1), c = damping.
+ *   L = round(T rate) - round(M K (1 - a) / (1 + a)): the period less the cascade's delay at 0 Hz; L < 1 is refused.
+ *   g = -10^(-3 T / t60_s) (reflections invert); t60_s = 0: g = 0, a single pass.  |g| above 0.9999 is refused.
+ *   U = C P z^-L, H_low = U / (1 - g U).
+ *   B(z): a Butterworth low-pass of even order lowpass_order at f_t, outside the loop, as order / 2 biquads.  With
+ *   W = tan(pi / (2 K)) and, for section i < order / 2, q = 2 sin(pi (2 i + 1) / (2 order)) W:  a0 = (1 + q) + W W,
+ *   b0 = b2 = (W W) / a0, b1 = 2 b0, a1 = (2 (W W - 1)) / a0, a2 = ((1 - q) + W W) / a0;
+ *   section(z) = (b0 + b1 z^-1 + b2 z^-2) / (1 + a1 z^-1 + a2 z^-2).  Order 0, or K = 1, leaves B out.
+ * High chirps (off when high_gain = 0, and then not evaluated).  A_h(z) = (a_h + z^-1) / (1 + a_h z^-1), a_h =
+ *   high_dispersion; L_h = max(1, round(high_delay T rate)); g_h from high_t60_s as g from t60_s;
+ *   U_h = A_h^M_h z^-L_h, M_h = high_sections; H_high = U_h / (1 - g_h U_h).
+ * Sum.  H_c(z) = gain / sqrt(S) sum over s ascending of (B H_low + high_gain H_high), c = L, R.  |U| <= 1 on and outside the
+ *   unit circle and |g| < 1: no denominator comes near 0.
+ * Powers.  A^M and A_h^M_h by square-and-multiply on the complex value from M's highest bit down: r = A; for every lower bit
+ *   r = r r, and r = r A when the bit is set.
+ * Frames.  E = last ? min(last, F) : F.  N = 2^log2_points when set, else the smallest power of two >= max(1024, 2 E);
+ *   E > N / 2 and N > 2^22 are refused.  R = MC_SPRING_RADIUS = 1e8, rho = R^(1/N).  For bin k: z_k^-1 = rho^-1
+ *   e^(-2 pi i k / N) (z^-q has the magnitude exp(-q ln(R) / N) and the angle -((k q) mod N) / N turns, reduced in integers),
+ *   X[k] = H_L(z_k) + i H_R(z_k), x = the inverse N-point transform of X, and for t < E
+ *     y_L[t] = Re x[t] rho^t,  y_R[t] = Im x[t] rho^t.
+ *   By construction y[t] = sum over m >= 0 of h[t + m N] R^-m, where h is the recursion's own impulse response: the endless
+ *   tail that a transform of N points wraps around comes back R times weaker per wrap.  With |h| <= 1 per echo, what remains
+ *   is at most max |g|^floor((N - E) / (L + M K (1 + a) / (1 - a))) / R of the first echo (the loop's longest round trip in
+ *   the divisor): mc_ir_spring_plan reports it.  rho^t = exp(t ln(R) / N) <= 1e4 for t < N / 2.
+ * Store.  llrint(y 2^40) (to nearest, ties to even) into the 64-bit accumulator of mc_ir_room's rule, written once per frame
+ *   and channel: no atomics and no sums in arrival order.  Frame = (float)(late + direct + reflections + acc 2^-40).  Frame
+ *   t is a function of (struct, rate, N, t) alone: the same struct stores the same bits in any slot on any run, and with
+ *   log2_points set so do loads of different F on the frames both have.
+ *   |y| < 2^23, so the rounded value fits: gain <= 16, sqrt(3) for three springs, echoes of at most 1 each that all overlap
+ *   sum to 1 / (1 - 0.9999), the low-pass's taps sum to about 2 in magnitude and high_gain <= 16: 16 sqrt(3) (2 + 16) 1e4 = 5e6. */
+#define MC_SPRING_MAX 3             /* springs */
+#define MC_SPRING_MAX_STRETCH 64    /* K */
+#define MC_SPRING_RADIUS 1e8        /* R */
+#define MC_SPRING_MAX_LOG2 22       /* N <= 2^22, E <= 2^21 */
+typedef struct {
+    uint32_t struct_size;     /* sizeof(mc_ir_spring) = 80 */
+    uint32_t sections;        /* M: 0 .. 512 */
+    float transition_hz;      /* finite, (0, rate / 2] */
+    float dispersion;         /* a: [0, 0.95] */
+    float delay_ms[3];        /* finite, 0 (absent) or (0, 10000]; the present springs first, at least one */
+    float t60_s;              /* 0 (one pass) or finite in [0.001, 1000] */
+    float damping;            /* c: [0, 0.95] */
+    uint32_t lowpass_order;   /* 0, or even 2 .. 12 */
+    float high_gain;          /* [0, 16]; 0 = no high chirps */
+    uint32_t high_sections;   /* M_h: 0 .. 1024 */
+    float high_dispersion;    /* a_h: [-0.95, 0] */
+    float high_delay;         /* (0, 1]: the high loop's delay as a part of the period */
+    float high_t60_s;         /* as t60_s */
+    float stereo;             /* [0, 0.25]: channel R's periods are (1 + stereo) times channel L's */
+    float gain;               /* finite, (0, 16] */
+    uint32_t log2_points;     /* 0 = by E, or 10 .. 22 */
+    uint64_t last;            /* E = last ? min(last, F) : F: frames at and after E get nothing from the spring */
+} mc_ir_spring;
+/* 100 sections, transition 4300 Hz, a 0.62, springs of 66 and 82 ms, t60 2.5 s, damping 0.2, low-pass order 8, high chirps at
+ * 0.1 with 200 sections, a_h -0.6, half the period, 1 s; stereo 0.03, gain 1, log2_points 0, last 0 */
+void mc_default_ir_spring(mc_ir_spring *s);
+/* mc_synth_ir_room(..., room = NULL, ...) with the spring's term added to the generated frames; with spring NULL it is that
+ * call bit for bit.  A spring together with a room or a plate is not offered.  Checked in this order, all before the engine or
+ * the device is touched (MC_ERR_ARG, the message names the field, the engine stays as it was): synth as by mc_synth_ir; the
+ * spring field by field in the struct's order; then synth->rate, which must be set ("the spring needs the session's rate");
+ * then transition_hz against rate / 2, K, L per spring and channel ("delay_ms[s] is shorter than the dispersion's own
+ * delay"), |g|, and E against N (the message says to set last); tail as by mc_load_ir_tail, with F' after F; damp, eq and
+ * shape, then e, idx and nframes as by mc_synth_ir_room. */
+int mc_synth_ir_spring(mc_engine *e, uint64_t idx, uint64_t nframes, const mc_ir_synth *synth, const mc_ir_spring *spring,
+                       const mc_ir_shape *shape, const mc_ir_eq *eq, const mc_ir_damp *damp, const mc_ir_tail *tail);
+/* What a load of `frames` frames at `rate` would do with `spring`: out = {N, K, f_t (Hz), S, M, 1 when B is in, E, the alias
+ * bound in dB (20 log10 of the bound under Frames, over the low loops and, when on, the high ones; -400 when it is 0); then
+ * at 8 + 2 s + c the delay L and at 14 + 2 s + c the loop gain g of spring s < 3 in channel c (0 for an absent spring);
+ * 20 .. 23 are 0}.  The spring is checked as by mc_synth_ir_spring, with rate in [8000, 384000] and frames in [1, 2^24].
+ * Host arithmetic only: no engine and no HIP call. */
+int mc_ir_spring_plan(const mc_ir_spring *spring, uint32_t rate, uint64_t frames, double out[24]);
+/* out_re_im[4 i .. 4 i + 3] = Re H_L, Im H_L, Re H_R, Im H_R at z = e^(2 pi i hz[i] / rate), on the unit circle, by the
+ * functions that make the kernel's constants and in the kernel's order of operations.  The spring is checked as by
+ * mc_ir_spring_plan (no frames are involved).  Host arithmetic only. */
+int mc_ir_spring_response(const mc_ir_spring *spring, uint32_t rate, const double *hz, uint32_t n, double *out_re_im);
+/* The plan's twenty-four numbers of the IR's last load; MC_ERR_STATE unless that load had a spring */
+int mc_ir_spring_info(const mc_engine *e, uint64_t idx, double out[24]);
+
 int mc_num_irs(const mc_engine *e);
 /* out[0..3] = sum h_L, sum h_R, sum h_L(-1)^m, sum h_R(-1)^m of the truncated IR; out[4] = taps, out[5] = partitions */
 int mc_ir_info(const mc_engine *e, uint64_t idx, double out[6]);
