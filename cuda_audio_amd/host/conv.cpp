@@ -758,84 +758,6 @@ void Convolution::setIrParts(const IrParts& parts) {
     _irParts = parts;
 }
 
-bool Convolution::parseParts(const std::string& arg, IrParts& out, std::string& why) {
-    const auto fail = [&](const std::string& w) {
-        why = w + " (key=value,... with keys direct, early, late, split, first, onset, xfade, delay, width, balance, swap, invert)";
-        return false;
-    };
-    static const char* const names[3] = {"direct", "early", "late"};
-    if (arg.empty()) return fail("an empty list");
-    IrParts p;
-    p.on = true;
-    // `count` numbers joined by ':' (or one for all when `one`), each finite and within [lo, hi]
-    const auto numbers = [](const std::string& val, size_t count, bool one, double lo, double hi, double* v) {
-        std::vector<double> got;
-        for (size_t at = 0; at <= val.size();) {
-            const size_t colon = std::min(val.find(':', at), val.size());
-            const std::string item = val.substr(at, colon - at);
-            at = colon + 1;
-            char* end = nullptr;
-            const double x = std::strtod(item.c_str(), &end);
-            if (item.empty() || *end || !std::isfinite(x) || x < lo || x > hi) return false;
-            got.push_back(x);
-        }
-        if (got.size() != count && !(one && got.size() == 1)) return false;
-        for (size_t k = 0; k < count; k++) v[k] = got[got.size() == 1 ? 0 : k];
-        return true;
-    };
-    for (size_t at = 0; at <= arg.size();) {
-        const size_t comma = std::min(arg.find(',', at), arg.size());
-        const std::string item = arg.substr(at, comma - at);
-        at = comma + 1;
-        const size_t eqs = item.find('=');
-        if (item == "swap" || item == "invert") {  // (alone: all three parts)
-            for (int k = 0; k < 3; k++) (item == "swap" ? p.swap : p.invert)[k] = true;
-            continue;
-        }
-        if (item.empty() || eqs == std::string::npos || eqs == 0 || eqs + 1 == item.size()) return fail("'" + item + "' is not key=value");
-        const std::string key = item.substr(0, eqs), val = item.substr(eqs + 1);
-        double v[3];
-        if (key == "direct" || key == "early" || key == "late") {
-            const int k = key == "direct" ? 0 : key == "early" ? 1 : 2;
-            if (val == "off") {
-                p.mute[k] = true;
-                continue;
-            }
-            if (!numbers(val, 1, true, -120.0, 24.0, v)) return fail(key + " is a gain in dB within [-120, 24] or off, not '" + val + "'");
-            p.gainDb[k] = (float)v[0], p.mute[k] = false;
-        } else if (key == "split") {
-            p.splitAtMix = val == "mix";
-            if (!p.splitAtMix && !numbers(val, 1, true, 0.0, 100.0, &p.splitSeconds)) return fail("split is a time in seconds within [0, 100] or mix, not '" + val + "'");
-        } else if (key == "first" || key == "onset") {
-            if (!numbers(val, 1, true, 0.0, 100.0, key == "first" ? &p.firstSeconds : &p.onsetSeconds))
-                return fail(key + " is a time in seconds within [0, 100], not '" + val + "'");
-        } else if (key == "xfade") {
-            if (!numbers(val, 2, false, 0.0, 100.0, p.xfadeSeconds)) return fail("xfade is S:S, two times in seconds within [0, 100], not '" + val + "'");
-        } else if (key == "delay") {
-            if (!numbers(val, 3, false, -10.0, 10.0, p.delaySeconds)) return fail("delay is S:S:S, three times in seconds within [-10, 10], not '" + val + "'");
-        } else if (key == "width" || key == "balance") {
-            const bool w = key == "width";
-            if (!numbers(val, 3, true, w ? 0.0 : -1.0, w ? 2.0 : 1.0, v)) return fail(key + (w ? " is one number or W:W:W within [0, 2], not '" : " is one number or B:B:B within [-1, 1], not '") + val + "'");
-            for (int k = 0; k < 3; k++) (w ? p.width : p.balance)[k] = (float)v[k];
-        } else if (key == "swap" || key == "invert") {
-            for (size_t from = 0; from <= val.size();) {
-                const size_t colon = std::min(val.find(':', from), val.size());
-                const std::string part = val.substr(from, colon - from);
-                from = colon + 1;
-                int k = 0;
-                while (k < 3 && part != names[k]) k++;
-                if (k == 3) return fail(key + " names parts (direct, early, late) joined by ':', not '" + val + "'");
-                (key == "swap" ? p.swap : p.invert)[k] = true;
-            }
-        } else
-            return fail("no such key '" + key + "'");
-    }
-    if (!p.splitAtMix && p.splitSeconds < p.firstSeconds) return fail("split is before first");
-    if (p.mute[0] && p.mute[1] && p.mute[2]) return fail("every part is off");
-    out = p;
-    return true;
-}
-
 // Loads p with every step but the parts (the measured tail included) and with no shape, EQ or damping, measures its echo density
 // and returns the boundaries its final load goes through; nothing for a generated IR, which has no parts step
 std::optional<Convolution::PartsSplit> Convolution::measureParts(const PendingIr& p, const std::optional<mc_ir_tail>& tail) {
@@ -870,208 +792,6 @@ void Convolution::setIrMatch(const IrMatch& match, bool report) {
     }
     _irMatch = match;
     _irMatchReport = report;
-}
-
-bool Convolution::parseMatch(const std::string& arg, IrMatch& out, std::string& why) {
-    const auto fail = [&](const std::string& w) {
-        why = w + " (FILE.wav|flat[:key=value,...] with keys amount, boost, cut, smooth, lo, hi, link, phase, delay, tilt)";
-        return false;
-    };
-    const size_t colon = arg.find(':');
-    IrMatch m;
-    m.path = arg.substr(0, colon);
-    if (m.path.empty()) return fail("no file");
-    m.flat = m.path == "flat";
-    m.on = true;
-    if (colon != std::string::npos) {
-        const std::string list = arg.substr(colon + 1);
-        if (list.empty()) return fail("an empty list");
-        for (size_t at = 0; at <= list.size();) {
-            const size_t comma = std::min(list.find(',', at), list.size());
-            const std::string item = list.substr(at, comma - at);
-            at = comma + 1;
-            const size_t eqs = item.find('=');
-            if (item.empty() || eqs == std::string::npos || eqs == 0 || eqs + 1 == item.size()) return fail("'" + item + "' is not key=value");
-            const std::string key = item.substr(0, eqs), val = item.substr(eqs + 1);
-            if (key == "phase") {
-                if (val != "minimum" && val != "linear") return fail("phase is minimum or linear, not '" + val + "'");
-                m.linear = val == "linear";
-                continue;
-            }
-            if (key == "link") {
-                if (val != "0" && val != "1") return fail("link is 0 or 1, not '" + val + "'");
-                m.link = val == "1";
-                continue;
-            }
-            char* end = nullptr;
-            const double v = std::strtod(val.c_str(), &end);
-            const auto within = [&](double lo, double hi) { return v >= lo && v <= hi; };
-            if (key != "amount" && key != "boost" && key != "cut" && key != "smooth" && key != "lo" && key != "hi" && key != "delay" && key != "tilt")
-                return fail("no such key '" + key + "'");
-            if (*end || !std::isfinite(v)) return fail("'" + val + "' of " + key + " is not a number");
-            if (key == "amount") {
-                if (!within(0.0, 1.0)) return fail("amount " + val + " outside [0, 1]");
-                m.amount = (float)v;
-            } else if (key == "boost" || key == "cut") {
-                if (!within(0.0, 60.0)) return fail(key + " " + val + " dB outside [0, 60]");
-                (key == "boost" ? m.boostDb : m.cutDb) = (float)v;
-            } else if (key == "smooth") {
-                if (!within(1.0 / 24.0, 2.0)) return fail("smooth " + val + " octaves outside [1/24, 2]");
-                m.octaves = v;
-            } else if (key == "lo" || key == "hi") {
-                if (!within(1.0, 192000.0)) return fail(key + " " + val + " Hz outside [1, 192000]");
-                (key == "lo" ? m.loHz : m.hiHz) = v;
-            } else if (key == "delay") {
-                if (!within(0.0, 10.0)) return fail("delay " + val + " s outside [0, 10]");
-                m.delaySeconds = v;
-            } else {
-                if (!within(-12.0, 12.0)) return fail("tilt " + val + " dB per octave outside [-12, 12]");
-                m.tiltDb = (float)v;
-            }
-        }
-    }
-    if (m.hiHz != 0.0 && !(m.hiHz > m.loHz)) return fail("hi is not above lo");
-    out = m;
-    return true;
-}
-
-bool Convolution::parseFilter(const std::string& arg, IrFilter& out, std::string& why) {
-    const auto fail = [&](const std::string& w) {
-        why = w + " (FILE.wav[:key=value,...] with keys op, channels, reg, keep)";
-        return false;
-    };
-    const size_t colon = arg.find(':');
-    IrFilter f;
-    f.path = arg.substr(0, colon);
-    if (f.path.empty()) return fail("no file");
-    f.on = true;
-    if (colon != std::string::npos) {
-        const std::string list = arg.substr(colon + 1);
-        if (list.empty()) return fail("an empty list");
-        for (size_t at = 0; at <= list.size();) {
-            const size_t comma = std::min(list.find(',', at), list.size());
-            const std::string item = list.substr(at, comma - at);
-            at = comma + 1;
-            const size_t eqs = item.find('=');
-            if (item.empty() || eqs == std::string::npos || eqs == 0 || eqs + 1 == item.size()) return fail("'" + item + "' is not key=value");
-            const std::string key = item.substr(0, eqs), val = item.substr(eqs + 1);
-            if (key == "op") {
-                if (val != "convolve" && val != "deconvolve") return fail("op is convolve or deconvolve, not '" + val + "'");
-                f.deconvolve = val == "deconvolve";
-            } else if (key == "channels") {
-                if (val != "stereo" && val != "left" && val != "mid") return fail("channels is stereo, left or mid, not '" + val + "'");
-                f.channels = val == "stereo" ? 0 : val == "left" ? 1 : 2;
-            } else if (key == "reg" || key == "keep") {
-                char* end = nullptr;
-                const double v = std::strtod(val.c_str(), &end);
-                if (*end || !std::isfinite(v)) return fail("'" + val + "' of " + key + " is not a number");
-                if (key == "reg") {
-                    if (v < 20.0 || v > 200.0) return fail("reg " + val + " dB outside [20, 200]");
-                    f.regDb = (float)v;
-                } else {
-                    if (!(v > 0.0) || v > 3600.0) return fail("keep " + val + " s outside (0, 3600]");
-                    f.keepSeconds = v;
-                }
-            } else
-                return fail("no such key '" + key + "'");
-        }
-    }
-    out = f;
-    return true;
-}
-
-bool Convolution::parsePhase(const std::string& arg, IrPhase& out, std::string& why) {
-    const auto fail = [&](const std::string& w) {
-        why = w + " (minimum[:key=value,...] with keys floor, over)";
-        return false;
-    };
-    const size_t colon = arg.find(':');
-    const std::string mode = arg.substr(0, colon);
-    IrPhase p;
-    if (mode != "minimum") return fail("the mode is minimum, not '" + mode + "'");
-    p.minimum = true;
-    if (colon != std::string::npos) {
-        const std::string list = arg.substr(colon + 1);
-        if (list.empty()) return fail("an empty list");
-        for (size_t at = 0; at <= list.size();) {
-            const size_t comma = std::min(list.find(',', at), list.size());
-            const std::string item = list.substr(at, comma - at);
-            at = comma + 1;
-            const size_t eqs = item.find('=');
-            if (item.empty() || eqs == std::string::npos || eqs == 0 || eqs + 1 == item.size()) return fail("'" + item + "' is not key=value");
-            const std::string key = item.substr(0, eqs), val = item.substr(eqs + 1);
-            char* end = nullptr;
-            const double v = std::strtod(val.c_str(), &end);
-            if (*end || !std::isfinite(v)) return fail("'" + val + "' of " + key + " is not a number");
-            if (key == "floor") {
-                if (v < 40.0 || v > 300.0) return fail("floor " + val + " dB outside [40, 300]");
-                p.floorDb = (float)v;
-            } else if (key == "over") {
-                unsigned lg = 0;
-                while (lg <= 6 && (double)(1u << lg) != v) lg++;
-                if (lg < 1 || lg > 6) return fail("over " + val + " is not a power of two from 2 to 64");
-                p.overLog2 = lg;
-            } else
-                return fail("no such key '" + key + "'");
-        }
-    }
-    out = p;
-    return true;
-}
-
-bool Convolution::parseTail(const std::string& arg, IrTail& out, std::string& why) {
-    const auto fail = [&](const std::string& w) {
-        why = w + " (cut|extend[:key=value,...] with keys fade, length, seed, width, knee)";
-        return false;
-    };
-    const size_t colon = arg.find(':');
-    const std::string mode = arg.substr(0, colon);
-    IrTail t;
-    if (mode == "cut") t.mode = IrTail::Cut;
-    else if (mode == "extend") t.mode = IrTail::Extend;
-    else return fail("the mode is cut or extend, not '" + mode + "'");
-    if (colon != std::string::npos) {
-        const std::string list = arg.substr(colon + 1);
-        if (list.empty()) return fail("an empty list");
-        for (size_t at = 0; at <= list.size();) {
-            const size_t comma = std::min(list.find(',', at), list.size());
-            const std::string item = list.substr(at, comma - at);
-            at = comma + 1;
-            const size_t eqs = item.find('=');
-            if (item.empty() || eqs == std::string::npos || eqs == 0 || eqs + 1 == item.size()) return fail("'" + item + "' is not key=value");
-            const std::string key = item.substr(0, eqs), val = item.substr(eqs + 1);
-            char* end = nullptr;
-            if (key == "knee") {
-                if (val != "floor" && val != "mix") return fail("knee is floor or mix, not '" + val + "'");
-                t.kneeAtMix = val == "mix";
-                continue;
-            }
-            if (key == "seed") {
-                t.seed = std::strtoull(val.c_str(), &end, 10);
-                if (*end || val[0] == '-') return fail("seed '" + val + "' is not a number >= 0");
-                continue;
-            }
-            if (key == "width" && val == "iacc") {
-                t.widthFromIacc = true;
-                continue;
-            }
-            const double v = std::strtod(val.c_str(), &end);
-            if (*end || !std::isfinite(v)) return fail("'" + val + "' of " + key + " is not a number");
-            if (key == "fade" || key == "length") {
-                if (v < 0.0 || v > 4000.0) return fail(key + " " + val + " s outside [0, 4000]");
-                (key == "fade" ? t.fadeSeconds : t.lengthSeconds) = v;
-            } else if (key == "width") {
-                if (v < 0.0 || v > 1.0) return fail("width " + val + " outside [0, 1]");
-                t.width = (float)v;
-                t.widthFromIacc = false;
-            } else
-                return fail("no such key '" + key + "'");
-        }
-    }
-    if (t.kneeAtMix && t.mode != IrTail::Extend) return fail("knee=mix slides the levels of an extended tail: the mode must be extend");
-    if (t.widthFromIacc && t.mode != IrTail::Extend) return fail("width=iacc is the width of an extended tail's noise: the mode must be extend");
-    out = t;
-    return true;
 }
 
 Convolution::Floor Convolution::irFloor(size_t idx, const std::vector<float>& xovers, unsigned rate) {
@@ -1189,23 +909,6 @@ void Convolution::setIrDensityReport(bool on, const DensityQuery& query) {
     _densityQuery = query;
 }
 
-bool Convolution::parseDensity(const std::string& option, const std::string& arg, DensityQuery& out, std::string& why) {
-    if (option == "--ir-density-t60" && arg == "auto") {
-        out.autoT60 = true, out.t60Seconds = 0.0;
-        return true;
-    }
-    char* end = nullptr;
-    const double v = std::strtod(arg.c_str(), &end);
-    if (arg.empty() || *end || !std::isfinite(v) || !(v > 0.0) || v > 4000.0) {
-        why = "takes a time in seconds, > 0 and at most 4000" + std::string(option == "--ir-density-t60" ? ", or auto" : "");
-        return false;
-    }
-    if (option == "--ir-density-window") out.windowSeconds = v;
-    else if (option == "--ir-density-hop") out.hopSeconds = v;
-    else out.t60Seconds = v, out.autoT60 = false;
-    return true;
-}
-
 Convolution::Density Convolution::irDensity(size_t idx, const DensityQuery& query) {
     if (!mc_ir_density || !mc_default_density_query) {
         Log::error("conv", "the engine has no density measurement (mc_ir_density)");
@@ -1246,31 +949,6 @@ void Convolution::setIrIaccReport(bool on, const IaccQuery& query) {
     }
     _iaccReport = on;
     _iaccQuery = query;
-}
-
-bool Convolution::parseIacc(const std::string& option, const std::string& arg, IaccQuery& out, std::string& why) {
-    char* end = nullptr;
-    if (option == "--ir-iacc-lag") {
-        const double v = std::strtod(arg.c_str(), &end);
-        if (arg.empty() || *end || !std::isfinite(v) || v < 0.0 || v > 1.0) {
-            why = "takes a time in seconds, >= 0 and at most 1";
-            return false;
-        }
-        out.lagSeconds = v, out.lagGiven = true;
-        return true;
-    }
-    std::vector<float> bands;
-    for (const char* a = arg.c_str();; a = end + 1) {
-        const float hz = std::strtof(a, &end);
-        if (end == a || (*end && *end != ',') || !std::isfinite(hz) || !(hz > 0.f) || bands.size() >= MC_DECAY_MAX_BANDS) {
-            why = "takes HZ[,HZ...], each > 0, at most 10";
-            return false;
-        }
-        bands.push_back(hz);
-        if (!*end) break;
-    }
-    out.bands = bands;
-    return true;
 }
 
 Convolution::Iacc Convolution::irIacc(size_t idx, const IaccQuery& query) {
@@ -1320,32 +998,6 @@ void Convolution::setIrStiReport(bool on, const StiQuery& query) {
     _stiQuery = query;
 }
 
-bool Convolution::parseSti(const std::string& arg, StiQuery& out, std::string& why) {
-    std::vector<float> snr;
-    char* end = nullptr;
-    for (const char* a = arg.c_str();; a = end + 1) {
-        const float db = std::strtof(a, &end);
-        if (end == a || (*end && *end != ',') || !std::isfinite(db) || db < -60.f || db > 120.f || snr.size() >= MC_STI_MAX_BANDS) {
-            why = "takes DB[,DB...]: one signal-to-noise ratio for all seven octaves or one per octave from 125 Hz up, each in [-60, 120]";
-            return false;
-        }
-        snr.push_back(db);
-        if (!*end) break;
-    }
-    if (snr.size() != 1 && snr.size() != MC_STI_MAX_BANDS) {
-        why = "takes one signal-to-noise ratio for all seven octaves or seven, one per octave";
-        return false;
-    }
-    snr.resize(MC_STI_MAX_BANDS, snr[0]);
-    out.snrDb = snr;
-    return true;
-}
-
-const char* Convolution::stiRating(double sti) {
-    if (std::isnan(sti)) return "none";
-    return sti < 0.30 ? "bad" : sti < 0.45 ? "poor" : sti < 0.60 ? "fair" : sti < 0.75 ? "good" : "excellent";
-}
-
 Convolution::Sti Convolution::irSti(size_t idx, const StiQuery& query) {
     if (!mc_ir_sti || !mc_default_sti_query) {
         Log::error("conv", "the engine has no STI measurement (mc_ir_sti)");
@@ -1393,17 +1045,6 @@ void Convolution::setIrResponseReport(bool on, const ResponseQuery& query) {
     }
     _responseReport = on;
     _responseQuery = query;
-}
-
-bool Convolution::parseResponse(const std::string& arg, ResponseQuery& out, std::string& why) {
-    char* end = nullptr;
-    const double octaves = std::strtod(arg.c_str(), &end);
-    if (end == arg.c_str() || *end || !std::isfinite(octaves) || octaves < 0.0 || octaves > 10.0) {
-        why = "takes OCTAVES: the width the report's levels are smoothed over, in [0, 10]";
-        return false;
-    }
-    out.smoothOctaves = octaves;
-    return true;
 }
 
 Convolution::Response Convolution::irResponse(size_t idx, const ResponseQuery& query) {
@@ -1482,82 +1123,6 @@ mc_ir_synth Convolution::synthFrames(const IrSynth& y, double rate) {
     return s;
 }
 
-bool Convolution::parseSynth(const std::string& line, IrSynth& out, std::string& why) {
-    static const char* form = "synth:LENGTH_S:T60_S[:key=value,...] with keys seed, start, buildup, late, direct, early, efirst, elast, egain, width";
-    std::vector<std::string> parts;
-    for (size_t at = 0;;) {
-        const size_t colon = line.find(':', at);
-        parts.push_back(line.substr(at, colon == std::string::npos ? colon : colon - at));
-        if (colon == std::string::npos) break;
-        at = colon + 1;
-    }
-    if (parts.size() < 3 || parts.size() > 4 || parts[0] != "synth") {
-        why = std::string("a generated IR is ") + form;
-        return false;
-    }
-    // a finite number >= 0 that fills the whole text
-    const auto number = [](const std::string& text, double& v) {
-        char* end = nullptr;
-        v = std::strtod(text.c_str(), &end);
-        return !text.empty() && end == text.c_str() + text.size() && std::isfinite(v);
-    };
-    IrSynth y;
-    if (!number(parts[1], y.lengthSeconds) || !(y.lengthSeconds > 0.0)) {
-        why = "LENGTH_S '" + parts[1] + "' is not a length in seconds, > 0";
-        return false;
-    }
-    if (!number(parts[2], y.t60Seconds) || y.t60Seconds < 0.0) {
-        why = "T60_S '" + parts[2] + "' is not a decay time in seconds, >= 0 (0 = no decay)";
-        return false;
-    }
-    const std::string list = parts.size() == 4 ? parts[3] : "";
-    if (parts.size() == 4 && list.empty()) {
-        why = std::string("nothing after the last colon: ") + form;
-        return false;
-    }
-    for (size_t at = 0; at < list.size() || (at && at == list.size());) {
-        const size_t comma = std::min(list.find(',', at), list.size());
-        const std::string item = list.substr(at, comma - at);
-        const size_t eq = item.find('=');
-        const std::string key = item.substr(0, eq), text = eq == std::string::npos ? "" : item.substr(eq + 1);
-        double v = 0.0;
-        bool good = eq != std::string::npos;
-        if (!good) {
-            why = "'" + item + "' is not key=value";
-            return false;
-        }
-        if (key == "seed") {
-            char* end = nullptr;
-            y.seed = std::strtoull(text.c_str(), &end, 0);
-            good = !text.empty() && text[0] != '-' && end == text.c_str() + text.size();
-        } else if (key == "early") {
-            good = number(text, v) && v >= 0.0 && v <= (double)MC_SYNTH_MAX_EARLY && v == std::floor(v);
-            y.early = (uint32_t)v;
-        } else if (key == "late" || key == "direct" || key == "egain" || key == "width") {
-            good = number(text, v) && (key == "direct" || key == "egain" || v >= 0.0) && (key != "width" || v <= 1.0);
-            (key == "late" ? y.late : key == "direct" ? y.direct : key == "egain" ? y.earlyGain : y.width) = (float)v;
-        } else if (key == "start" || key == "buildup" || key == "efirst" || key == "elast") {
-            good = number(text, v) && v >= 0.0;
-            (key == "start" ? y.startSeconds : key == "buildup" ? y.buildUpSeconds : key == "efirst" ? y.earlyFirstSeconds : y.earlyLastSeconds) = v;
-        } else {
-            why = "unknown key '" + key + "': " + form;
-            return false;
-        }
-        if (!good) {
-            why = "'" + text + "' is no value for " + key;
-            return false;
-        }
-        at = comma + 1;
-        if (comma == list.size()) break;
-    }
-    if (y.early && y.earlyLastSeconds < y.earlyFirstSeconds) {
-        why = "elast is before efirst";
-        return false;
-    }
-    out = y;
-    return true;
-}
-
 mc_ir_room Convolution::roomFrames(const IrRoom& room, double rate) {
     mc_ir_room r;
     mc_default_ir_room(&r);
@@ -1604,184 +1169,6 @@ mc_ir_room_head Convolution::roomHead(const IrRoom& room) {
     return h;
 }
 
-bool Convolution::parseRoom(const std::string& line, IrRoom& out, std::string& why) {
-    static const char* form =
-        "room:LENGTH_S:LX,LY,LZ:SX,SY,SZ:RX,RY,RZ[:key=value,...] with keys beta (one value, or six separated by '/'), order, spacing, axis (x|y|z), "
-        "speed, gain, last, mic (omni|subcardioid|cardioid|supercardioid|hypercardioid|fig8 or a number in [0, 1]; P or P/P), aim and tilt (degrees; "
-        "one value or L/R), src, srcaim, srctilt, xover (HZ[/HZ[/HZ]]), betas (one value per band, separated by '/'), air (dB per metre: one value, or one "
-        "per band), head (the azimuth the listener faces, degrees), headradius (metres), ears (degrees from the facing direction), shadow ([0, 1]), "
-        "t60 and synth:'s keys";
-    std::vector<std::string> parts;
-    for (size_t at = 0;;) {
-        const size_t colon = line.find(':', at);
-        parts.push_back(line.substr(at, colon == std::string::npos ? colon : colon - at));
-        if (colon == std::string::npos) break;
-        at = colon + 1;
-    }
-    if (parts.size() < 5 || parts.size() > 6 || parts[0] != "room") {
-        why = std::string("a room is ") + form;
-        return false;
-    }
-    const auto number = [](const std::string& text, double& v) {
-        char* end = nullptr;
-        v = std::strtod(text.c_str(), &end);
-        return !text.empty() && end == text.c_str() + text.size() && std::isfinite(v);
-    };
-    // `count` numbers separated by `sep` that fill the whole text
-    const auto numbers = [&](const std::string& text, char sep, size_t count, float* v) {
-        size_t at = 0;
-        for (size_t k = 0; k < count; k++) {
-            const size_t end = k + 1 < count ? text.find(sep, at) : text.size();
-            double x;
-            if (end == std::string::npos || !number(text.substr(at, end - at), x)) return false;
-            v[k] = (float)x;
-            at = end + 1;
-        }
-        return true;
-    };
-    // a pattern by name or as alpha in [0, 1]
-    const auto pattern = [&](const std::string& text, float& v) {
-        static const struct {
-            const char* name;
-            float alpha;
-        } named[] = {{"omni", 1.0f}, {"subcardioid", 0.75f}, {"cardioid", 0.5f}, {"supercardioid", 0.366f}, {"hypercardioid", 0.25f}, {"fig8", 0.0f}};
-        for (const auto& p : named)
-            if (text == p.name) {
-                v = p.alpha;
-                return true;
-            }
-        double x;
-        if (!number(text, x) || x < 0.0 || x > 1.0) return false;
-        v = (float)x;
-        return true;
-    };
-    // one value for both receivers, or left/right; each within [-limit, limit] (a pattern with limit 0)
-    const auto pair = [&](const std::string& text, double limit, float* v) {
-        const size_t slash = text.find('/');
-        const std::string one[2] = {text.substr(0, slash), slash == std::string::npos ? text.substr(0, slash) : text.substr(slash + 1)};
-        for (int c = 0; c < 2; c++) {
-            double x;
-            if (limit == 0.0 ? !pattern(one[c], v[c]) : !number(one[c], x) || std::fabs(x) > limit) return false;
-            if (limit != 0.0) v[c] = (float)x;
-        }
-        return true;
-    };
-    // one to `most` numbers separated by '/', each within [lo, hi]
-    const auto upTo = [&](const std::string& text, size_t most, double lo, double hi, float* v, uint32_t& count) {
-        for (count = 1; count <= most; count++)
-            if (numbers(text, '/', count, v)) {
-                for (uint32_t k = 0; k < count; k++)
-                    if (!((double)v[k] >= lo && (double)v[k] <= hi)) return false;
-                return true;
-            }
-        return false;
-    };
-    IrRoom room;
-    std::string betasText, airText;
-    double length = 0.0;
-    if (!number(parts[1], length) || !(length > 0.0)) {
-        why = "LENGTH_S '" + parts[1] + "' is not a length in seconds, > 0";
-        return false;
-    }
-    const char* triple[3] = {"LX,LY,LZ", "SX,SY,SZ", "RX,RY,RZ"};
-    float* slot[3] = {room.size, room.source, room.receiver};
-    for (int k = 0; k < 3; k++)
-        if (!numbers(parts[2 + k], ',', 3, slot[k])) {
-            why = std::string(triple[k]) + " '" + parts[2 + k] + "' is not three numbers in metres";
-            return false;
-        }
-    const std::string list = parts.size() == 6 ? parts[5] : "";
-    if (parts.size() == 6 && list.empty()) {
-        why = std::string("nothing after the last colon: ") + form;
-        return false;
-    }
-    std::string t60 = "0", synthKeys = "late=0,direct=0";  // (the room supplies the direct sound; a later late= or direct= wins)
-    for (size_t at = 0; at < list.size() || (at && at == list.size());) {
-        const size_t comma = std::min(list.find(',', at), list.size());
-        const std::string item = list.substr(at, comma - at);
-        const size_t eq = item.find('=');
-        if (eq == std::string::npos) {
-            why = "'" + item + "' is not key=value";
-            return false;
-        }
-        const std::string key = item.substr(0, eq), text = item.substr(eq + 1);
-        double v = 0.0;
-        bool good = true;
-        if (key == "beta") {
-            good = numbers(text, '/', 6, room.beta);
-            if (!good && (good = number(text, v)))
-                for (float& b : room.beta) b = (float)v;
-        } else if (key == "order") {
-            good = number(text, v) && v >= 0.0 && v <= (double)MC_ROOM_MAX_ORDER && v == std::floor(v);
-            room.order = (uint32_t)v;
-        } else if (key == "axis") {
-            good = text == "x" || text == "y" || text == "z";
-            room.axis = good ? (uint32_t)(text[0] - 'x') : 0;
-        } else if (key == "spacing" || key == "speed" || key == "gain") {
-            good = number(text, v) && v >= 0.0;
-            (key == "spacing" ? room.spacing : key == "speed" ? room.speed : room.gain) = (float)v;
-        } else if (key == "last") {
-            good = number(text, v) && v >= 0.0;
-            room.lastSeconds = v;
-        } else if (key == "t60") {
-            good = number(text, v) && v >= 0.0;
-            t60 = text;
-        } else if (key == "mic" || key == "aim" || key == "tilt") {
-            good = key == "mic" ? pair(text, 0.0, room.micPattern) : key == "aim" ? pair(text, 360.0, room.micAim) : pair(text, 90.0, room.micTilt);
-            room.directional = true;
-        } else if (key == "xover") {
-            good = upTo(text, MC_DAMP_MAX_XOVERS, 10.0, 172800.0, room.xovers, room.nXovers);  // (the engine checks them against the client's rate)
-            for (uint32_t k = 1; good && k < room.nXovers; k++) good = room.xovers[k] > room.xovers[k - 1];
-            room.banded = true;
-        } else if (key == "betas") {
-            good = upTo(text, MC_DAMP_MAX_XOVERS + 1, -1.0, 1.0, room.betas, room.nBetas);
-            betasText = text;
-            room.banded = true;
-        } else if (key == "air") {
-            good = upTo(text, MC_DAMP_MAX_XOVERS + 1, 0.0, 1.0, room.air, room.nAir);
-            airText = text;
-            room.banded = true;
-        } else if (key == "head" || key == "headradius" || key == "ears" || key == "shadow") {
-            const double lo = key == "head" ? -360.0 : key == "headradius" ? 0.05 : key == "ears" ? 60.0 : 0.0;
-            const double hi = key == "head" ? 360.0 : key == "headradius" ? 0.15 : key == "ears" ? 120.0 : 1.0;
-            good = number(text, v) && v >= lo && v <= hi;
-            (key == "head" ? room.headFacing : key == "headradius" ? room.headRadius : key == "ears" ? room.headEars : room.headShadow) = (float)v;
-            room.headed = true;
-        } else if (key == "src") {
-            good = pattern(text, room.sourcePattern);
-            room.directional = true;
-        } else if (key == "srcaim" || key == "srctilt") {
-            good = number(text, v) && std::fabs(v) <= (key == "srcaim" ? 360.0 : 90.0);
-            (key == "srcaim" ? room.sourceAim : room.sourceTilt) = (float)v;
-            room.directional = true;
-        } else {
-            synthKeys += "," + item;  // (parseSynth names an unknown key)
-        }
-        if (!good) {
-            why = "'" + text + "' is no value for " + key;
-            return false;
-        }
-        at = comma + 1;
-        if (comma == list.size()) break;
-    }
-    // (the keys come in any order: the counts are compared once every key has been read)
-    if (room.nBetas && room.nBetas != room.nXovers + 1) {
-        why = "'" + betasText + "' is no value for betas: one value for each of the " + std::to_string(room.nXovers + 1) + " bands xover cuts";
-        return false;
-    }
-    if (room.nAir > 1 && room.nAir != room.nXovers + 1) {
-        why = "'" + airText + "' is no value for air: one value, or one for each of the " + std::to_string(room.nXovers + 1) + " bands xover cuts";
-        return false;
-    }
-    if (!parseSynth("synth:" + parts[1] + ":" + t60 + ":" + synthKeys, room.late, why)) {
-        const size_t at = why.find("synth:LENGTH_S");
-        if (at != std::string::npos) why = why.substr(0, at) + form;
-        return false;
-    }
-    out = room;
-    return true;
-}
-
 void Convolution::prepareRoom(size_t idx, const IrRoom& room, size_t nframes) {
     if (_group) {
         Log::error("conv", "room rendering is not available with several devices (mc_synth_ir_room is single-engine)");
@@ -1807,103 +1194,6 @@ mc_ir_plate Convolution::plateFrames(const IrPlate& plate, double rate) {
     p.gain = plate.gain;
     p.last = (uint64_t)std::nearbyint(plate.lastSeconds * rate);
     return p;
-}
-
-bool Convolution::parsePlate(const std::string& line, IrPlate& out, std::string& why) {
-    static const char* form =
-        "plate:LENGTH_S[:key=value,...] with keys size=LX,LY (metres), thick=MM, material=steel|E/RHO/NU (GPa, kg/m^3, Poisson's ratio), drive=X,Y, "
-        "pick=X,Y/X,Y (left/right), low=HZ, high=HZ, t60=LO/HI (seconds towards 0 Hz and at damp; 0 = no loss), damp=HZ, gain, last=S";
-    std::vector<std::string> parts;
-    for (size_t at = 0;;) {
-        const size_t colon = line.find(':', at);
-        parts.push_back(line.substr(at, colon == std::string::npos ? colon : colon - at));
-        if (colon == std::string::npos) break;
-        at = colon + 1;
-    }
-    if (parts.size() < 2 || parts.size() > 3 || parts[0] != "plate") {
-        why = std::string("a plate is ") + form;
-        return false;
-    }
-    const auto number = [](const std::string& text, double& v) {
-        char* end = nullptr;
-        v = std::strtod(text.c_str(), &end);
-        return !text.empty() && end == text.c_str() + text.size() && std::isfinite(v);
-    };
-    // `count` numbers >= lo separated by `sep` that fill the whole text
-    const auto numbers = [&](const std::string& text, char sep, size_t count, double lo, float* v) {
-        size_t at = 0;
-        for (size_t k = 0; k < count; k++) {
-            const size_t end = k + 1 < count ? text.find(sep, at) : text.size();
-            double x;
-            if (end == std::string::npos || !number(text.substr(at, end - at), x) || x < lo) return false;
-            v[k] = (float)x;
-            at = end + 1;
-        }
-        return true;
-    };
-    IrPlate plate;
-    if (!number(parts[1], plate.lengthSeconds) || !(plate.lengthSeconds > 0.0)) {
-        why = "LENGTH_S '" + parts[1] + "' is not a length in seconds, > 0";
-        return false;
-    }
-    const std::string list = parts.size() == 3 ? parts[2] : "";
-    if (parts.size() == 3 && list.empty()) {
-        why = std::string("nothing after the last colon: ") + form;
-        return false;
-    }
-    // the items: a comma starts a new one when key= follows it, and belongs to the value before it otherwise (size=LX,LY)
-    std::vector<std::string> items;
-    for (size_t at = 0; at < list.size() || (at && at == list.size());) {
-        const size_t comma = std::min(list.find(',', at), list.size());
-        const std::string piece = list.substr(at, comma - at);
-        if (piece.find('=') != std::string::npos || items.empty() || piece.empty())
-            items.push_back(piece);
-        else
-            items.back() += "," + piece;
-        at = comma + 1;
-        if (comma == list.size()) break;
-    }
-    for (const std::string& item : items) {
-        const size_t eq = item.find('=');
-        if (eq == std::string::npos) {
-            why = "'" + item + "' is not key=value";
-            return false;
-        }
-        const std::string key = item.substr(0, eq), text = item.substr(eq + 1);
-        double v = 0.0;
-        bool good = true;
-        if (key == "size") {
-            good = numbers(text, ',', 2, 0.0, plate.size);
-        } else if (key == "drive") {
-            good = numbers(text, ',', 2, 0.0, plate.driver);
-        } else if (key == "pick") {
-            const size_t slash = text.find('/');
-            good = slash != std::string::npos && numbers(text.substr(0, slash), ',', 2, 0.0, plate.pickup[0]) &&
-                   numbers(text.substr(slash + 1), ',', 2, 0.0, plate.pickup[1]);
-        } else if (key == "material") {
-            if (text == "steel")
-                plate.material[0] = 200.0f, plate.material[1] = 7850.0f, plate.material[2] = 0.3f;
-            else
-                good = numbers(text, '/', 3, 0.0, plate.material);
-        } else if (key == "t60") {
-            good = numbers(text, '/', 2, 0.0, plate.t60);
-        } else if (key == "thick" || key == "low" || key == "high" || key == "damp" || key == "gain") {
-            good = number(text, v) && v >= 0.0;
-            (key == "thick" ? plate.thickness : key == "low" ? plate.low : key == "high" ? plate.high : key == "damp" ? plate.damp : plate.gain) = (float)v;
-        } else if (key == "last") {
-            good = number(text, v) && v >= 0.0;
-            plate.lastSeconds = v;
-        } else {
-            why = "unknown key '" + key + "': " + form;
-            return false;
-        }
-        if (!good) {
-            why = "'" + text + "' is no value for " + key;
-            return false;
-        }
-    }
-    out = plate;
-    return true;
 }
 
 void Convolution::preparePlate(size_t idx, const IrPlate& plate, size_t nframes) {
@@ -1933,114 +1223,6 @@ mc_ir_spring Convolution::springFrames(const IrSpring& spring, double rate) {
     s.log2_points = spring.points;
     s.last = (uint64_t)std::nearbyint(spring.lastSeconds * rate);
     return s;
-}
-
-bool Convolution::parseSpring(const std::string& line, IrSpring& out, std::string& why) {
-    static const char* form =
-        "spring:LENGTH_S[:key=value,...] with keys sections, fc=HZ (the transition), a (the dispersion), delay=MS[,MS[,MS]] (one per spring), t60=S, damping, "
-        "lowpass=ORDER, high (the high chirps' gain), highsections, higha, highdelay (a part of the period), hight60=S, stereo, gain, points (log2 of the "
-        "transform's size), last=S";
-    std::vector<std::string> parts;
-    for (size_t at = 0;;) {
-        const size_t colon = line.find(':', at);
-        parts.push_back(line.substr(at, colon == std::string::npos ? colon : colon - at));
-        if (colon == std::string::npos) break;
-        at = colon + 1;
-    }
-    if (parts.size() < 2 || parts.size() > 3 || parts[0] != "spring") {
-        why = std::string("a spring is ") + form;
-        return false;
-    }
-    const auto number = [](const std::string& text, double& v) {
-        char* end = nullptr;
-        v = std::strtod(text.c_str(), &end);
-        return !text.empty() && end == text.c_str() + text.size() && std::isfinite(v);
-    };
-    // a whole number that fills the text
-    const auto count = [&](const std::string& text, unsigned& v) {
-        double x;
-        if (!number(text, x) || x < 0.0 || x > 1e6 || x != std::floor(x)) return false;
-        v = (unsigned)x;
-        return true;
-    };
-    IrSpring spring;
-    if (!number(parts[1], spring.lengthSeconds) || !(spring.lengthSeconds > 0.0)) {
-        why = "LENGTH_S '" + parts[1] + "' is not a length in seconds, > 0";
-        return false;
-    }
-    const std::string list = parts.size() == 3 ? parts[2] : "";
-    if (parts.size() == 3 && list.empty()) {
-        why = std::string("nothing after the last colon: ") + form;
-        return false;
-    }
-    // the items: a comma starts a new one when key= follows it, and belongs to the value before it otherwise (delay=MS,MS)
-    std::vector<std::string> items;
-    for (size_t at = 0; at < list.size() || (at && at == list.size());) {
-        const size_t comma = std::min(list.find(',', at), list.size());
-        const std::string piece = list.substr(at, comma - at);
-        if (piece.find('=') != std::string::npos || items.empty() || piece.empty())
-            items.push_back(piece);
-        else
-            items.back() += "," + piece;
-        at = comma + 1;
-        if (comma == list.size()) break;
-    }
-    for (const std::string& item : items) {
-        const size_t eq = item.find('=');
-        if (eq == std::string::npos) {
-            why = "'" + item + "' is not key=value";
-            return false;
-        }
-        const std::string key = item.substr(0, eq), text = item.substr(eq + 1);
-        double v = 0.0;
-        bool good = true;
-        if (key == "delay") {  // one to three periods in milliseconds, > 0; the springs not named are absent
-            size_t at = 0;
-            int k = 0;
-            for (; good && at <= text.size(); k++) {
-                const size_t end = std::min(text.find(',', at), text.size());
-                good = k < 3 && number(text.substr(at, end - at), v) && v > 0.0;
-                if (good) spring.delayMs[k] = (float)v;
-                at = end + 1;
-            }
-            for (; good && k < 3; k++) spring.delayMs[k] = 0.0f;
-        } else if (key == "sections") {
-            good = count(text, spring.sections);
-        } else if (key == "lowpass") {
-            good = count(text, spring.lowpass);
-        } else if (key == "highsections") {
-            good = count(text, spring.highSections);
-        } else if (key == "points") {
-            good = count(text, spring.points);
-        } else if (key == "higha") {  // (the one key whose value is at most 0)
-            good = number(text, v) && v <= 0.0;
-            spring.highDispersion = (float)v;
-        } else if (key == "fc" || key == "a" || key == "t60" || key == "damping" || key == "high" || key == "highdelay" || key == "hight60" || key == "stereo" ||
-                   key == "gain") {
-            good = number(text, v) && v >= 0.0;
-            (key == "fc"          ? spring.transition
-             : key == "a"         ? spring.dispersion
-             : key == "t60"       ? spring.t60
-             : key == "damping"   ? spring.damping
-             : key == "high"      ? spring.high
-             : key == "highdelay" ? spring.highDelay
-             : key == "hight60"   ? spring.highT60
-             : key == "stereo"    ? spring.stereo
-                                  : spring.gain) = (float)v;
-        } else if (key == "last") {
-            good = number(text, v) && v >= 0.0;
-            spring.lastSeconds = v;
-        } else {
-            why = "unknown key '" + key + "': " + form;
-            return false;
-        }
-        if (!good) {
-            why = "'" + text + "' is no value for " + key;
-            return false;
-        }
-    }
-    out = spring;
-    return true;
 }
 
 void Convolution::prepareSpring(size_t idx, const IrSpring& spring, size_t nframes) {
@@ -2099,89 +1281,6 @@ mc_sweep Convolution::sweepFrames(const IrSweep& w, double rate) {
     s.fade_in = (uint32_t)std::min(frames(w.fadeInSeconds), 4294967295.0);
     s.fade_out = (uint32_t)std::min(frames(w.fadeOutSeconds), 4294967295.0);
     return s;
-}
-
-bool Convolution::parseSweep(const std::string& line, IrSweep& out, std::string& why) {
-    static const char* form = "sweep:RECORDING.wav:LENGTH_S:F1:F2[:key=value,...] with keys amp, fadein, fadeout, offset, length";
-    std::vector<std::string> parts;
-    for (size_t at = 0;;) {
-        const size_t colon = line.find(':', at);
-        parts.push_back(line.substr(at, colon == std::string::npos ? colon : colon - at));
-        if (colon == std::string::npos) break;
-        at = colon + 1;
-    }
-    if (parts.size() < 5 || parts.size() > 6 || parts[0] != "sweep") {
-        why = std::string("a captured IR is ") + form;
-        return false;
-    }
-    // a finite number that fills the whole text
-    const auto number = [](const std::string& text, double& v) {
-        char* end = nullptr;
-        v = std::strtod(text.c_str(), &end);
-        return !text.empty() && end == text.c_str() + text.size() && std::isfinite(v);
-    };
-    IrSweep w;
-    w.recording = parts[1];
-    if (w.recording.empty()) {
-        why = std::string("no file name: ") + form;
-        return false;
-    }
-    double f1 = 0.0, f2 = 0.0;
-    if (!number(parts[2], w.lengthSeconds) || !(w.lengthSeconds > 0.0)) {
-        why = "LENGTH_S '" + parts[2] + "' is not a length in seconds, > 0";
-        return false;
-    }
-    if (!number(parts[3], f1) || !(f1 >= 1.0)) {
-        why = "F1 '" + parts[3] + "' is not a frequency in Hz, >= 1";
-        return false;
-    }
-    if (!number(parts[4], f2) || !(f2 > f1)) {
-        why = "F2 '" + parts[4] + "' is not a frequency in Hz above F1";
-        return false;
-    }
-    w.f1 = (float)f1;
-    w.f2 = (float)f2;
-    const std::string list = parts.size() == 6 ? parts[5] : "";
-    if (parts.size() == 6 && list.empty()) {
-        why = std::string("nothing after the last colon: ") + form;
-        return false;
-    }
-    for (size_t at = 0; at < list.size() || (at && at == list.size());) {
-        const size_t comma = std::min(list.find(',', at), list.size());
-        const std::string item = list.substr(at, comma - at);
-        const size_t eq = item.find('=');
-        if (eq == std::string::npos) {
-            why = "'" + item + "' is not key=value";
-            return false;
-        }
-        const std::string key = item.substr(0, eq), text = item.substr(eq + 1);
-        double v = 0.0;
-        bool good = number(text, v);
-        if (key == "amp") {
-            good = good && v > 0.0;
-            w.amp = (float)v;
-        } else if (key == "fadein" || key == "fadeout" || key == "length") {
-            good = good && v >= 0.0;
-            (key == "fadein" ? w.fadeInSeconds : key == "fadeout" ? w.fadeOutSeconds : w.irLengthSeconds) = v;
-        } else if (key == "offset") {
-            w.offsetSeconds = v;
-        } else {
-            why = "unknown key '" + key + "': " + form;
-            return false;
-        }
-        if (!good) {
-            why = "'" + text + "' is no value for " + key;
-            return false;
-        }
-        at = comma + 1;
-        if (comma == list.size()) break;
-    }
-    if (w.fadeInSeconds + w.fadeOutSeconds > w.lengthSeconds) {
-        why = "fadein and fadeout are longer than the sweep";
-        return false;
-    }
-    out = w;
-    return true;
 }
 
 bool Convolution::writeSweep(const IrSweep& sweep, unsigned rate, std::string& why) {

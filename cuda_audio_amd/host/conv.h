@@ -166,8 +166,8 @@ public:
     void prepareSynth(size_t idx, const IrSynth& synth, size_t nframes = 1024);
     // The same from a filled mc_ir_synth (frames at synth.rate; rate 0 only without EQ and damping), generated at once.
     void prepareSynth(size_t idx, const mc_ir_synth& synth, size_t nframes = 1024);
-    // A line of an IR index that starts with "synth:" - synth:LENGTH_S:T60_S[:key=value,...], keys seed, start, buildup, late,
-    // direct, early, efirst, elast, egain, width - as an IrSynth.  False, with the reason in `why`, for a malformed line.
+    // A line of an IR index that starts with "synth:" - synth:LENGTH_S:T60_S[:key=value,...] - as an IrSynth; irargs.cpp has the
+    // grammar and the keys.  False, with the reason in `why`, for a malformed line.
     static bool parseSynth(const std::string& line, IrSynth& out, std::string& why);
     // mc_ir_synth of an IrSynth at rate Hz
     static mc_ir_synth synthFrames(const IrSynth& synth, double rate);
@@ -215,13 +215,9 @@ public:
         IrRoom() { late.late = 0.0f; }
     };
     void prepareRoom(size_t idx, const IrRoom& room, size_t nframes = 1024);
-    // A line of an IR index that starts with "room:" - room:LENGTH_S:LX,LY,LZ:SX,SY,SZ:RX,RY,RZ[:key=value,...], keys beta (one
-    // value, or six separated by '/'), order, spacing, axis (x|y|z), speed, gain, last (seconds), mic (a pattern: omni, subcardioid,
-    // cardioid, supercardioid, hypercardioid, fig8 or a number in [0, 1]; P or P/P), aim and tilt (degrees; one value or L/R),
-    // src, srcaim and srctilt (the source's), xover (HZ[/HZ[/HZ]]), betas (one value per band, separated by '/') and air (dB per
-    // metre: one value, or one per band), head (degrees), headradius (metres), ears (degrees) and shadow ([0, 1]), and for the
-    // late field t60 and parseSynth's keys - as an IrRoom.  False, with the
-    // reason in `why`, for a malformed line.
+    // A line of an IR index that starts with "room:" - room:LENGTH_S:LX,LY,LZ:SX,SY,SZ:RX,RY,RZ[:key=value,...], with t60 and
+    // parseSynth's keys for the late field - as an IrRoom; irargs.cpp has the grammar and the keys.  False, with the reason in
+    // `why`, for a malformed line.
     static bool parseRoom(const std::string& line, IrRoom& out, std::string& why);
     // mc_ir_room of an IrRoom at rate Hz
     static mc_ir_room roomFrames(const IrRoom& room, double rate);
@@ -250,9 +246,8 @@ public:
         double lastSeconds = 0.0;
     };
     void preparePlate(size_t idx, const IrPlate& plate, size_t nframes = 1024);
-    // A line of an IR index that starts with "plate:" - plate:LENGTH_S[:key=value,...], keys size=LX,LY, thick=MM,
-    // material=steel|E/RHO/NU, drive=X,Y, pick=X,Y/X,Y, low=HZ, high=HZ, t60=LO/HI, damp=HZ, gain and last=S - as an IrPlate.  False,
-    // with the reason in `why`, for a malformed line.
+    // A line of an IR index that starts with "plate:" - plate:LENGTH_S[:key=value,...] - as an IrPlate; irargs.cpp has the grammar
+    // and the keys.  False, with the reason in `why`, for a malformed line.
     static bool parsePlate(const std::string& line, IrPlate& out, std::string& why);
     // mc_ir_plate of an IrPlate at rate Hz
     static mc_ir_plate plateFrames(const IrPlate& plate, double rate);
@@ -278,9 +273,8 @@ public:
         double lastSeconds = 0.0;
     };
     void prepareSpring(size_t idx, const IrSpring& spring, size_t nframes = 1024);
-    // A line of an IR index that starts with "spring:" - spring:LENGTH_S[:key=value,...], keys sections, fc=HZ, a,
-    // delay=MS[,MS[,MS]], t60=S, damping, lowpass=ORDER, high, highsections, higha, highdelay, hight60=S, stereo, gain, points and
-    // last=S - as an IrSpring.  False, with the reason in `why`, for a malformed line.
+    // A line of an IR index that starts with "spring:" - spring:LENGTH_S[:key=value,...] - as an IrSpring; irargs.cpp has the
+    // grammar and the keys.  False, with the reason in `why`, for a malformed line.
     static bool parseSpring(const std::string& line, IrSpring& out, std::string& why);
     // mc_ir_spring of an IrSpring at rate Hz
     static mc_ir_spring springFrames(const IrSpring& spring, double rate);
@@ -300,8 +294,8 @@ public:
         double irLengthSeconds = 0.0;
     };
     void prepareSweep(size_t idx, const IrSweep& sweep, const WavFile& recording, size_t nframes = 1024);
-    // A line of an IR index that starts with "sweep:" - sweep:RECORDING.wav:LENGTH_S:F1:F2[:key=value,...], keys amp, fadein,
-    // fadeout, offset, length - as an IrSweep.  False, with the reason in `why`, for a malformed line.
+    // A line of an IR index that starts with "sweep:" - sweep:RECORDING.wav:LENGTH_S:F1:F2[:key=value,...] - as an IrSweep;
+    // irargs.cpp has the grammar and the keys.  False, with the reason in `why`, for a malformed line.
     static bool parseSweep(const std::string& line, IrSweep& out, std::string& why);
     // mc_sweep of an IrSweep at rate Hz
     static mc_sweep sweepFrames(const IrSweep& sweep, double rate);
@@ -443,8 +437,8 @@ public:
         bool widthFromIacc = false;
     };
     void setIrTail(const IrTail& tail);
-    // The argument of --ir-tail, cut|extend[:key=value,...] with keys fade, length (seconds), seed, width (a number or iacc) and knee (floor|mix), as an IrTail.
-    // False, with the reason in `why`, for a malformed one.
+    // The argument of --ir-tail, cut|extend[:key=value,...], as an IrTail; irargs.cpp has the grammar and the keys.  False, with the
+    // reason in `why`, for a malformed one.
     static bool parseTail(const std::string& arg, IrTail& out, std::string& why);
     // The phase step every IR loaded from now on goes through (mc_ir_phase of include/mcconv.h; no reference equivalent): the
     // frames are replaced by the minimum-phase IR of the same magnitude response, after the conversion and the tail step and
@@ -457,8 +451,8 @@ public:
         unsigned overLog2 = 3;   // the transform is 2^overLog2 times the IR's length rounded up to a power of two; 1 .. 6
     };
     void setIrPhase(const IrPhase& phase);
-    // The argument of --ir-phase, minimum[:key=value,...] with keys floor (dB) and over (2, 4, .. 64), as an IrPhase.  False,
-    // with the reason in `why`, for a malformed one.
+    // The argument of --ir-phase, minimum[:key=value,...], as an IrPhase; irargs.cpp has the grammar and the keys.  False, with the
+    // reason in `why`, for a malformed one.
     static bool parsePhase(const std::string& arg, IrPhase& out, std::string& why);
     // The filter step every IR loaded from now on goes through (mc_ir_filter of include/mcconv.h; no reference equivalent): the
     // frames are convolved with a second IR (a cabinet into a room, a correction FIR into a hall: one IR at run time), or that
@@ -477,8 +471,8 @@ public:
         std::vector<float> lr;
     };
     void setIrFilter(const IrFilter& filter);
-    // The argument of --ir-filter, FILE.wav[:key=value,...] with keys op (convolve, deconvolve), channels (stereo, left, mid),
-    // reg (dB) and keep (seconds), as an IrFilter without its frames.  False, with the reason in `why`, for a malformed one.
+    // The argument of --ir-filter, FILE.wav[:key=value,...], as an IrFilter without its frames; irargs.cpp has the grammar and the
+    // keys.  False, with the reason in `why`, for a malformed one.
     static bool parseFilter(const std::string& arg, IrFilter& out, std::string& why);
     // The match step every IR loaded from now on goes through (mc_ir_match of include/mcconv.h; no reference equivalent): a match
     // EQ that gives the frames the smoothed spectrum of a target IR, or of a flat or tilted line, after the filter step and ahead
@@ -502,9 +496,8 @@ public:
         std::vector<float> lr;
     };
     void setIrMatch(const IrMatch& match, bool report);
-    // The argument of --ir-match, FILE.wav|flat[:key=value,...] with keys amount, boost, cut (dB), smooth (octaves), lo, hi (Hz),
-    // link (0, 1), phase (minimum, linear), delay (seconds) and tilt (dB per octave), as an IrMatch without its frames.  False,
-    // with the reason in `why`, for a malformed one.
+    // The argument of --ir-match, FILE.wav|flat[:key=value,...], as an IrMatch without its frames; irargs.cpp has the grammar and
+    // the keys.  False, with the reason in `why`, for a malformed one.
     static bool parseMatch(const std::string& arg, IrMatch& out, std::string& why);
     // The parts step every IR loaded from now on goes through (mc_ir_parts of include/mcconv.h; no reference equivalent): the
     // direct sound, the early reflections and the late tail get a gain (or are muted), a delay, a width and a balance each, after
@@ -523,9 +516,8 @@ public:
         bool splitAtMix = false;
     };
     void setIrParts(const IrParts& parts);
-    // The argument of --ir-parts, key=value,... with keys direct, early, late (dB, or off), split (seconds, or mix), first, onset
-    // (seconds), xfade (S:S), delay (S:S:S), width and balance (one number or three) and swap, invert (part names joined by ':'), as
-    // an IrParts.  False, with the reason in `why`, for a malformed one.
+    // The argument of --ir-parts, key=value,..., as an IrParts; irargs.cpp has the grammar and the keys.  False, with the reason in
+    // `why`, for a malformed one.
     static bool parseParts(const std::string& arg, IrParts& out, std::string& why);
 
     void onMidiMessage(const RawMidi::Device* sender, const uint8_t* buffer, size_t len) override;

@@ -105,6 +105,24 @@
 #include "conv.h"
 #include "settings.h"
 
+// text through one of Convolution's argument parsers into out; false, with "<what> '<text>': <the parser's reason>" on stderr, for
+// a text the parser refuses (what: the option, or "index line")
+template <typename T>
+static bool parsed(const char* what, const std::string& text, T& out, bool (*parse)(const std::string&, T&, std::string&)) {
+    std::string why;
+    if (parse(text, out, why)) return true;
+    std::cerr << what << " '" << text << "': " << why << std::endl;
+    return false;
+}
+// (the parsers of several options take the option first)
+template <typename T>
+static bool parsed(const char* option, const std::string& text, T& out, bool (*parse)(const std::string&, const std::string&, T&, std::string&)) {
+    std::string why;
+    if (parse(option, text, out, why)) return true;
+    std::cerr << option << " '" << text << "': " << why << std::endl;
+    return false;
+}
+
 int main(int argc, char** argv) {
     uint64_t periods = 0;
     const char* settingsPath = "settings.txt";
@@ -244,23 +262,11 @@ int main(int argc, char** argv) {
                 a = end + 1;
             }
         } else if (!strcmp(argv[i], "--ir-tail") && i + 1 < argc) {
-            std::string why;
-            if (!Convolution::parseTail(argv[++i], irTail, why)) {
-                std::cerr << "--ir-tail '" << argv[i] << "': " << why << std::endl;
-                return 2;
-            }
+            if (!parsed("--ir-tail", argv[++i], irTail, Convolution::parseTail)) return 2;
         } else if (!strcmp(argv[i], "--ir-phase") && i + 1 < argc) {
-            std::string why;
-            if (!Convolution::parsePhase(argv[++i], irPhase, why)) {
-                std::cerr << "--ir-phase '" << argv[i] << "': " << why << std::endl;
-                return 2;
-            }
+            if (!parsed("--ir-phase", argv[++i], irPhase, Convolution::parsePhase)) return 2;
         } else if (!strcmp(argv[i], "--ir-filter") && i + 1 < argc) {
-            std::string why;
-            if (!Convolution::parseFilter(argv[++i], irFilter, why)) {
-                std::cerr << "--ir-filter '" << argv[i] << "': " << why << std::endl;
-                return 2;
-            }
+            if (!parsed("--ir-filter", argv[++i], irFilter, Convolution::parseFilter)) return 2;
             if (!std::ifstream(irFilter.path, std::ifstream::binary).good()) {
                 std::cerr << "--ir-filter '" << argv[i] << "': cannot open " << irFilter.path << std::endl;
                 return 2;
@@ -269,11 +275,7 @@ int main(int argc, char** argv) {
             irFilter.rate = wav.sampleRate;
             irFilter.lr.assign(&wav.buffer[0].x, &wav.buffer[0].x + 2 * wav.numFrames);
         } else if (!strcmp(argv[i], "--ir-match") && i + 1 < argc) {
-            std::string why;
-            if (!Convolution::parseMatch(argv[++i], irMatch, why)) {
-                std::cerr << "--ir-match '" << argv[i] << "': " << why << std::endl;
-                return 2;
-            }
+            if (!parsed("--ir-match", argv[++i], irMatch, Convolution::parseMatch)) return 2;
             if (!irMatch.flat) {
                 if (!std::ifstream(irMatch.path, std::ifstream::binary).good()) {
                     std::cerr << "--ir-match '" << argv[i] << "': cannot open " << irMatch.path << std::endl;
@@ -284,44 +286,22 @@ int main(int argc, char** argv) {
                 irMatch.lr.assign(&wav.buffer[0].x, &wav.buffer[0].x + 2 * wav.numFrames);
             }
         } else if (!strcmp(argv[i], "--ir-parts") && i + 1 < argc) {
-            std::string why;
-            if (!Convolution::parseParts(argv[++i], irParts, why)) {
-                std::cerr << "--ir-parts '" << argv[i] << "': " << why << std::endl;
-                return 2;
-            }
+            if (!parsed("--ir-parts", argv[++i], irParts, Convolution::parseParts)) return 2;
         } else if (!strcmp(argv[i], "--ir-match-report")) irMatchReport = true;
         else if (!strcmp(argv[i], "--ir-density-report")) irDensityReport = true;
         else if ((!strcmp(argv[i], "--ir-density-window") || !strcmp(argv[i], "--ir-density-hop") || !strcmp(argv[i], "--ir-density-t60")) && i + 1 < argc) {
-            std::string why;
             const char* option = argv[i];
-            if (!Convolution::parseDensity(option, argv[++i], irDensity, why)) {
-                std::cerr << option << " '" << argv[i] << "': " << why << std::endl;
-                return 2;
-            }
+            if (!parsed(option, argv[++i], irDensity, Convolution::parseDensity)) return 2;
         } else if (!strcmp(argv[i], "--ir-iacc-report")) irIaccReport = true;
         else if ((!strcmp(argv[i], "--ir-iacc-lag") || !strcmp(argv[i], "--ir-iacc-bands")) && i + 1 < argc) {
-            std::string why;
             const char* option = argv[i];
-            if (!Convolution::parseIacc(option, argv[++i], irIacc, why)) {
-                std::cerr << option << " '" << argv[i] << "': " << why << std::endl;
-                return 2;
-            }
+            if (!parsed(option, argv[++i], irIacc, Convolution::parseIacc)) return 2;
         } else if (!strcmp(argv[i], "--ir-sti-report")) irStiReport = true;
         else if (!strcmp(argv[i], "--ir-sti-snr") && i + 1 < argc) {
-            std::string why;
-            const char* option = argv[i];
-            if (!Convolution::parseSti(argv[++i], irSti, why)) {
-                std::cerr << option << " '" << argv[i] << "': " << why << std::endl;
-                return 2;
-            }
+            if (!parsed("--ir-sti-snr", argv[++i], irSti, Convolution::parseSti)) return 2;
         } else if (!strcmp(argv[i], "--ir-response-report")) irResponseReport = true;
         else if (!strcmp(argv[i], "--ir-response-smooth") && i + 1 < argc) {
-            std::string why;
-            const char* option = argv[i];
-            if (!Convolution::parseResponse(argv[++i], irResponse, why)) {
-                std::cerr << option << " '" << argv[i] << "': " << why << std::endl;
-                return 2;
-            }
+            if (!parsed("--ir-response-smooth", argv[++i], irResponse, Convolution::parseResponse)) return 2;
         } else if (!strcmp(argv[i], "--ir-rt60") && i + 1 < argc) {
             irRt60 = atof(argv[++i]);
             if (!(irRt60 > 0.0)) {
@@ -406,51 +386,31 @@ int main(int argc, char** argv) {
                 if (path.empty()) continue;
                 if (!path.compare(0, 6, "synth:")) {  // a generated IR instead of a WAV path
                     Convolution::IrSynth synth;
-                    std::string why;
-                    if (!Convolution::parseSynth(path, synth, why)) {
-                        std::cerr << "index line '" << path << "': " << why << std::endl;
-                        return 2;
-                    }
+                    if (!parsed("index line", path, synth, Convolution::parseSynth)) return 2;
                     c->prepareSynth(j, synth);
                     continue;
                 }
                 if (!path.compare(0, 5, "room:")) {  // a rendered room instead of a WAV path
                     Convolution::IrRoom room;
-                    std::string why;
-                    if (!Convolution::parseRoom(path, room, why)) {
-                        std::cerr << "index line '" << path << "': " << why << std::endl;
-                        return 2;
-                    }
+                    if (!parsed("index line", path, room, Convolution::parseRoom)) return 2;
                     c->prepareRoom(j, room);
                     continue;
                 }
                 if (!path.compare(0, 6, "plate:")) {  // a plate reverberator instead of a WAV path
                     Convolution::IrPlate plate;
-                    std::string why;
-                    if (!Convolution::parsePlate(path, plate, why)) {
-                        std::cerr << "index line '" << path << "': " << why << std::endl;
-                        return 2;
-                    }
+                    if (!parsed("index line", path, plate, Convolution::parsePlate)) return 2;
                     c->preparePlate(j, plate);
                     continue;
                 }
                 if (!path.compare(0, 7, "spring:")) {  // a spring tank instead of a WAV path
                     Convolution::IrSpring spring;
-                    std::string why;
-                    if (!Convolution::parseSpring(path, spring, why)) {
-                        std::cerr << "index line '" << path << "': " << why << std::endl;
-                        return 2;
-                    }
+                    if (!parsed("index line", path, spring, Convolution::parseSpring)) return 2;
                     c->prepareSpring(j, spring);
                     continue;
                 }
                 if (!path.compare(0, 6, "sweep:")) {  // an IR deconvolved from a recorded sweep
                     Convolution::IrSweep sweep;
-                    std::string why;
-                    if (!Convolution::parseSweep(path, sweep, why)) {
-                        std::cerr << "index line '" << path << "': " << why << std::endl;
-                        return 2;
-                    }
+                    if (!parsed("index line", path, sweep, Convolution::parseSweep)) return 2;
                     WavFile rec(sweep.recording);
                     c->prepareSweep(j, sweep, rec);
                     continue;
