@@ -10,7 +10,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "mcconv.hip")
-DEPS = [SRC] + [os.path.join(HERE, "csrc", h) for h in ("kernels.hip.h", "jack_tail.hip.h", "fft512.hip.h", "ossave.hip.h", "singlefft.hip.h", "singlefft_host.hip.h", "resample.hip.h", "irshape.hip.h", "chunkwalk.hip.h", "ireq.hip.h", "irdamp.hip.h", "irdecay.hip.h", "irsynth.hip.h", "irroom.hip.h", "irplate.hip.h", "irspring.hip.h", "irsweep.hip.h", "irfloor.hip.h", "irdensity.hip.h", "iriacc.hip.h", "irsti.hip.h", "irresponse.hip.h", "irtail.hip.h", "fft64.hip.h", "irspectral.hip.h", "irphase.hip.h", "irfilter.hip.h", "irmatch.hip.h", "irparts.hip.h", "params_handoff.h")] + [
+DEPS = [SRC] + [os.path.join(HERE, "csrc", h) for h in ("kernels.hip.h", "jack_tail.hip.h", "fft512.hip.h", "ossave.hip.h", "singlefft.hip.h", "singlefft_host.hip.h", "resample.hip.h", "irshape.hip.h", "chunkwalk.hip.h", "ireq.hip.h", "irdamp.hip.h", "irdecay.hip.h", "irsynth.hip.h", "irroom.hip.h", "irplate.hip.h", "irspring.hip.h", "irsweep.hip.h", "irfloor.hip.h", "irdensity.hip.h", "iriacc.hip.h", "irsti.hip.h", "irresponse.hip.h", "irtail.hip.h", "fft64.hip.h", "irspectral.hip.h", "irphase.hip.h", "irfilter.hip.h", "irmatch.hip.h", "irparts.hip.h", "params_handoff.h", "owned.h")] + [
     os.path.join(os.path.dirname(HERE), "include", "mcconv.h")]
 OUT = os.path.join(HERE, "libmcconv.so")
 FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-shared", "-fPIC", "-Wall", "-Wno-unused-function"]
@@ -26,7 +26,7 @@ def hipcc():
 # the multi-GPU driver (include/mcconv_group.h): links the engine library and RCCL
 GROUP_SRC = os.path.join(HERE, "csrc", "mcgroup.hip")
 GROUP_OUT = os.path.join(HERE, "libmcconv_rccl.so")
-GROUP_DEPS = [GROUP_SRC, os.path.join(os.path.dirname(HERE), "include", "mcconv_group.h"), os.path.join(os.path.dirname(HERE), "include", "mcconv.h")]
+GROUP_DEPS = [GROUP_SRC, os.path.join(HERE, "csrc", "owned.h"), os.path.join(HERE, "csrc", "mcgroup_staging.h"), os.path.join(os.path.dirname(HERE), "include", "mcconv_group.h"), os.path.join(os.path.dirname(HERE), "include", "mcconv.h")]
 
 
 def build_group(force=False, verbose=False):

@@ -225,8 +225,8 @@ inline hipError_t damp_run(hipStream_t stream, double2* d_buf, uint64_t n, const
     pl.origin = std::min<uint64_t>(pl.origin, n);
     const ChunkGeom cg = chunk_geom(n);
     const DampCarry cm = damp_carry(pl.c, pl.X, cg.K);
-    double2* d_st = nullptr;
-    hipError_t er = hipMalloc(&d_st, sizeof(double2) * 2 * (size_t)pl.X * cg.lanes);
+    DevArray<double2> d_st;
+    hipError_t er = d_st.alloc(2 * (size_t)pl.X * cg.lanes);
     if (er != hipSuccess) return er;
     hipLaunchKernelGGL(k_damp_chunk<false>, dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_buf, n, pl, d_st);
     er = hipGetLastError();
@@ -239,6 +239,5 @@ inline hipError_t damp_run(hipStream_t stream, double2* d_buf, uint64_t n, const
         er = hipGetLastError();
     }
     const hipError_t sy = hipStreamSynchronize(stream);
-    (void)hipFree(d_st);
     return er != hipSuccess ? er : sy;
 }

@@ -322,35 +322,26 @@ struct Measure {
     uint64_t N, o = 0;                           // the taps analysed are [0, N); the origin among them
     ChunkGeom cg;                                // k_eq_chunk, k_dec_sum and the carries over N taps
     hipError_t er = hipSuccess;
-    double2 *d_buf = nullptr, *d_st = nullptr;   // a row group's doubles [N]; the chunk states
-    double *d_tot = nullptr, *d_part = nullptr, *d_fin = nullptr;  // the chunk totals [cg.lanes]; partials [part_cap]; folded sums
-    size_t part_cap = 0;
+    DevArray<double2> d_buf, d_st;         // a row group's doubles [N]; the chunk states
+    DevArray<double> d_tot, d_part, d_fin;  // the chunk totals [cg.lanes]; partials; folded sums
 
     Measure(hipStream_t stream, const float2* d_x, uint64_t n, uint64_t end) : stream(stream), d_x(d_x), N(dec_span(end, n)), cg(chunk_geom(N)) {}
-    Measure(const Measure&) = delete;
-    ~Measure() {
-        for (void* p : {(void*)d_fin, (void*)d_part, (void*)d_tot, (void*)d_st, (void*)d_buf}) (void)hipFree(p);
-    }
     template <class T>
-    void alloc(T** p, size_t count) {
-        if (er == hipSuccess && count) er = hipMalloc(p, sizeof(T) * count);
+    void alloc(DevArray<T>& a, size_t count) {
+        if (er == hipSuccess && count) er = a.alloc(count);
     }
     // The scratch, each buffer with the elements the measurement names (0: none; d_part holds the origin's partials at least),
     // then the origin (mc_ir_decay's step 1).  Synchronises the stream when onset_db < 0.  st0: what d_st starts as, nst double2
     // of the host that go onto the stream ahead of the origin's kernels (mc_ir_density's table); the caller keeps them until the
     // stream has run dry.
     void open(float onset_db, size_t nbuf, size_t nst, size_t ntot, size_t npart, size_t nfin, const double2* st0 = nullptr) {
-        part_cap = std::max<size_t>(npart, dec_origin_grid(N));
-        alloc(&d_buf, nbuf), alloc(&d_st, nst), alloc(&d_tot, ntot), alloc(&d_part, part_cap), alloc(&d_fin, nfin);
+        alloc(d_buf, nbuf), alloc(d_st, nst), alloc(d_tot, ntot), alloc(d_part, std::max<size_t>(npart, dec_origin_grid(N))), alloc(d_fin, nfin);
         if (er == hipSuccess && st0) er = hipMemcpyAsync(d_st, st0, sizeof(double2) * nst, hipMemcpyHostToDevice, stream);
         if (er == hipSuccess) er = dec_origin(stream, d_x, N, onset_db, d_part, &o);
     }
-    // d_part [count] at least: what it held is dropped
+    // d_part [count] at least: what it held is dropped (grow waits for the stream before it frees: the wait hipFree implied, now said)
     void grow_part(size_t count) {
-        if (er != hipSuccess || count <= part_cap) return;
-        (void)hipFree(d_part);
-        d_part = nullptr, part_cap = count;
-        er = hipMalloc(&d_part, sizeof(double) * part_cap);
+        if (er == hipSuccess) er = d_part.grow(count, stream);
     }
     void launched() { er = hipGetLastError(); }
     // dst = src [bytes] of the device, and the stream has run dry
@@ -415,7 +406,7 @@ inline hipError_t dec_measure(hipStream_t stream, const float2* d_x, uint64_t n,
         m.edc();
         if (m.er == hipSuccess) {
             hipLaunchKernelGGL(k_dec_pick, dim3((npick + ISH_THREADS - 1) / ISH_THREADS), dim3(ISH_THREADS), 0, stream, m.d_buf, o, N, k50, k80, K,
-                               reinterpret_cast<double2*>(m.d_part));
+                               reinterpret_cast<double2*>(m.d_part.get()));
             m.launched();
         }
         m.fetch(part.data(), m.d_part, sizeof(double) * 2 * npick);

@@ -332,15 +332,15 @@ inline hipError_t ieq_finish(hipStream_t stream, const float2* d_x, const IshPla
     const uint64_t n = pl.n;
     const unsigned grid = (unsigned)((n + ISH_THREADS - 1) / ISH_THREADS);       // k_eq_fill, k_eq_store
     const ChunkGeom cg = chunk_geom(n);                                          // k_eq_chunk, k_eq_carry
-    double2 *d_buf = nullptr, *d_st = nullptr;
-    float2* d_y = nullptr;
-    double* d_part = nullptr;
+    DevArray<double2> d_buf, d_st;
+    DevArray<float2> d_y;
+    DevArray<double> d_part;
     std::vector<double> part(4 * (size_t)grid);
-    hipError_t er = hipMalloc(&d_buf, sizeof(double2) * n);
-    if (er == hipSuccess) er = hipMalloc(&d_st, sizeof(double2) * (size_t)cg.lanes);
-    if (er == hipSuccess) er = hipMalloc(&d_y, sizeof(float2) * n);
-    if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * part.size());
-    if (er == hipSuccess) er = hipMemsetAsync(d_st, 0, sizeof(double2) * (size_t)cg.lanes, stream);
+    hipError_t er = d_buf.alloc(n);
+    if (er == hipSuccess) er = d_st.alloc((size_t)cg.lanes);
+    if (er == hipSuccess) er = d_y.alloc(n);
+    if (er == hipSuccess) er = d_part.alloc(part.size());
+    if (er == hipSuccess) er = d_st.zero(stream);
     if (er == hipSuccess) {
         hipLaunchKernelGGL(k_eq_fill, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x, pl, d_buf);
         er = hipGetLastError();
@@ -382,17 +382,11 @@ inline hipError_t ieq_finish(hipStream_t stream, const float2* d_x, const IshPla
     }
     if (er == hipSuccess) er = hipMemcpyAsync(part.data(), d_part, sizeof(double) * 4 * grid, hipMemcpyDeviceToHost, stream);
     if (er == hipSuccess) er = hipStreamSynchronize(stream);
-    (void)hipFree(d_part);
-    (void)hipFree(d_st);
-    (void)hipFree(d_buf);
-    if (er != hipSuccess) {
-        (void)hipFree(d_y);
-        return er;
-    }
+    if (er != hipSuccess) return er;
     for (int k = 0; k < 4; k++) sums[k] = 0.0;
     for (unsigned b = 0; b < grid; b++)
         for (int k = 0; k < 4; k++) sums[k] += part[4 * (size_t)b + k];
-    *d_out = d_y;
+    *d_out = d_y.release();  // (as ish_shape hands its taps out)
     *n_out = n;
     return hipSuccess;
 }

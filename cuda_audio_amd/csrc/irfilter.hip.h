@@ -285,9 +285,9 @@ inline hipError_t filter_run(hipStream_t stream, const float2* d_x, float2* d_y,
     const uint64_t F = s.F, G = s.G, Fo = s.Fo, N = s.Nfft, gF = spec_groups(F), gG = spec_groups(G), gN = spec_groups(N);
     const uint64_t gH = spec_groups(N / 2 + 1);
     const bool mono = s.channels != MC_FILTER_STEREO;
-    float2* d_f = nullptr;
+    DevArray<float2> d_f;
     SpectralWork wk;
-    hipError_t er = hipMalloc(&d_f, sizeof(float2) * G);
+    hipError_t er = d_f.alloc(G);
     if (er == hipSuccess) er = wk.alloc(s.fft, N);
     if (er == hipSuccess) er = second_upload(stream, s.second, d_f, G);
     double2 *const d_a = wk.d_a, *const d_b = wk.d_b, *const d_w = wk.d_w;
@@ -356,6 +356,5 @@ inline hipError_t filter_run(hipStream_t stream, const float2* d_x, float2* d_y,
     } else {
         (void)hipStreamSynchronize(stream);
     }
-    (void)hipFree(d_f);
     return er;
 }

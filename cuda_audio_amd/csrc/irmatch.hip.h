@@ -393,17 +393,17 @@ inline hipError_t match_run(hipStream_t stream, const float2* d_x, float2* d_y, 
     const uint32_t J = s.J;
     const bool target = s.mode == MC_MATCH_TARGET;
     const int two = s.link ? 0 : 1;
-    float2* d_t = nullptr;
-    double2 *d_P = nullptr, *d_S = nullptr, *d_d = nullptr;
-    uint2* d_win = nullptr;
+    DevArray<float2> d_t;
+    DevArray<double2> d_P, d_S, d_d;
+    DevArray<uint2> d_win;
     std::vector<double> S(8 * (size_t)J, 0.0);
     SpectralWork wk;
-    hipError_t er = target ? hipMalloc(&d_t, sizeof(float2) * G) : hipSuccess;
+    hipError_t er = target ? d_t.alloc(G) : hipSuccess;
     if (er == hipSuccess) er = wk.alloc(s.fft, N);
-    if (er == hipSuccess) er = hipMalloc(&d_P, sizeof(double2) * 2 * stride);
-    if (er == hipSuccess) er = hipMalloc(&d_win, sizeof(uint2) * J);
-    if (er == hipSuccess) er = hipMalloc(&d_S, sizeof(double2) * 2 * J);
-    if (er == hipSuccess) er = hipMalloc(&d_d, sizeof(double2) * J);
+    if (er == hipSuccess) er = d_P.alloc(2 * stride);
+    if (er == hipSuccess) er = d_win.alloc(J);
+    if (er == hipSuccess) er = d_S.alloc(2 * (size_t)J);
+    if (er == hipSuccess) er = d_d.alloc(J);
     if (er == hipSuccess) er = hipMemcpy(d_win, s.win.data(), sizeof(uint2) * J, hipMemcpyHostToDevice);
     if (er == hipSuccess && target) er = second_upload(stream, s.second, d_t, G);
     double2 *const d_a = wk.d_a, *const d_b = wk.d_b, *const d_w = wk.d_w;
@@ -486,10 +486,5 @@ inline hipError_t match_run(hipStream_t stream, const float2* d_x, float2* d_y, 
     } else {
         (void)hipStreamSynchronize(stream);
     }
-    (void)hipFree(d_t);
-    (void)hipFree(d_P);
-    (void)hipFree(d_win);
-    (void)hipFree(d_S);
-    (void)hipFree(d_d);
     return er;
 }

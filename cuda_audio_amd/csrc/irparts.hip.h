@@ -226,9 +226,9 @@ inline uint64_t parts_device_bytes(const PartsStep& s) { return 8 * std::max(spe
 // partials, waits for the kernels and frees them.  info = mc_ir_parts_info's ten numbers.
 inline hipError_t parts_run(hipStream_t stream, const float2* d_x, float2* d_y, const PartsStep& s, double info[10]) {
     const uint64_t gF = spec_groups(s.F), gO = spec_groups(s.Fo), count = std::max(gO, 5 * gF);
-    double* d_part = nullptr;
+    DevArray<double> d_part;
     std::vector<double> part(count);
-    hipError_t er = hipMalloc(&d_part, sizeof(double) * count);
+    hipError_t er = d_part.alloc(count);
     const auto fetch = [&](uint64_t n) {
         hipError_t e2 = hipGetLastError();
         if (e2 == hipSuccess) e2 = hipMemcpyAsync(part.data(), d_part, sizeof(double) * n, hipMemcpyDeviceToHost, stream);
@@ -252,6 +252,5 @@ inline hipError_t parts_run(hipStream_t stream, const float2* d_x, float2* d_y, 
     } else {
         (void)hipStreamSynchronize(stream);
     }
-    (void)hipFree(d_part);
     return er;
 }

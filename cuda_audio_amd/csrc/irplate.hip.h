@@ -297,10 +297,10 @@ inline const char* plate_check(const mc_ir_plate* p, uint32_t rate, uint64_t F, 
 inline hipError_t plate_generate(hipStream_t stream, const SynPlan& syn, const PlatePlan& plan, float2* d_x) {
     const uint64_t E = plan.E, M = plan.M;
     const size_t acc_bytes = sizeof(unsigned long long) * 2 * E, row_bytes = sizeof(PlateRow) * M;
-    char* d_all = nullptr;
-    hipError_t er = hipMalloc(&d_all, acc_bytes + row_bytes);  // (acc_bytes is a multiple of 16: the rows are aligned)
+    DevArray<char> d_all;
+    hipError_t er = d_all.alloc(acc_bytes + row_bytes);  // (acc_bytes is a multiple of 16: the rows are aligned)
     if (er != hipSuccess) return er;
-    unsigned long long* d_acc = reinterpret_cast<unsigned long long*>(d_all);
+    unsigned long long* d_acc = reinterpret_cast<unsigned long long*>(d_all.get());
     PlateRow* d_rows = reinterpret_cast<PlateRow*>(d_all + acc_bytes);
     er = hipMemsetAsync(d_acc, 0, acc_bytes, stream);
     if (er == hipSuccess) er = hipMemcpyAsync(d_rows, plan.rows.data(), row_bytes, hipMemcpyHostToDevice, stream);
@@ -318,6 +318,5 @@ inline hipError_t plate_generate(hipStream_t stream, const SynPlan& syn, const P
     }
     const hipError_t waited = hipStreamSynchronize(stream);  // (also after a failed launch: the copies may still be running)
     if (er == hipSuccess) er = waited;
-    (void)hipFree(d_all);
     return er;
 }

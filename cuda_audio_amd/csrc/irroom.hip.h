@@ -872,9 +872,10 @@ inline hipError_t room_generate_head(hipStream_t stream, const SynPlan& syn, con
     const RoomShelf shelf = room_shelf(plans[0].head[6], plans[0].speed, plans[0].rate);
     const size_t block_bytes = sizeof(unsigned long long) * 2 * A * (size_t)B, zero_bytes = 2 * block_bytes + 16 * (size_t)B;  // (16: two counters, padded)
     const size_t r_bytes = sizeof(double2) * F * (X ? 2 : 1), st_bytes = sizeof(double2) * (size_t)std::max(2 * X, 1) * cg.lanes;
-    char* d_all = nullptr;
-    hipError_t er = hipMalloc(&d_all, zero_bytes + r_bytes + st_bytes);
+    DevArray<char> d_buf;
+    hipError_t er = d_buf.alloc(zero_bytes + r_bytes + st_bytes);
     if (er != hipSuccess) return er;
+    char* const d_all = d_buf;  // view
     unsigned long long* d_acc = reinterpret_cast<unsigned long long*>(d_all);
     unsigned* d_kept = reinterpret_cast<unsigned*>(d_all + 2 * block_bytes);
     double2* d_r = reinterpret_cast<double2*>(d_all + zero_bytes);
@@ -912,7 +913,6 @@ inline hipError_t room_generate_head(hipStream_t stream, const SynPlan& syn, con
     const hipError_t waited = hipStreamSynchronize(stream);  // (also after a failed launch: the memset may still be running)
     if (er == hipSuccess) er = waited;
     if (er == hipSuccess) er = hipMemcpy(kept, d_kept, 2 * sizeof(unsigned), hipMemcpyDeviceToHost);
-    (void)hipFree(d_all);
     return er;
 }
 
@@ -927,9 +927,10 @@ inline hipError_t room_generate_bands(hipStream_t stream, const SynPlan& syn, co
     const ChunkGeom cg = chunk_geom(F);
     const size_t acc_bytes = sizeof(unsigned long long) * 2 * A * (size_t)B, zero_bytes = acc_bytes + 16 * (size_t)B;  // (16: two counters, padded)
     const size_t r_bytes = X ? sizeof(double2) * F : 0, st_bytes = sizeof(double2) * 2 * (size_t)X * cg.lanes;
-    char* d_all = nullptr;
-    hipError_t er = hipMalloc(&d_all, zero_bytes + r_bytes + st_bytes);
+    DevArray<char> d_buf;
+    hipError_t er = d_buf.alloc(zero_bytes + r_bytes + st_bytes);
     if (er != hipSuccess) return er;
+    char* const d_all = d_buf;  // view
     unsigned long long* d_acc = reinterpret_cast<unsigned long long*>(d_all);
     unsigned* d_kept = reinterpret_cast<unsigned*>(d_all + acc_bytes);
     double2* d_r = reinterpret_cast<double2*>(d_all + zero_bytes);
@@ -948,7 +949,6 @@ inline hipError_t room_generate_bands(hipStream_t stream, const SynPlan& syn, co
     const hipError_t waited = hipStreamSynchronize(stream);  // (also after a failed launch: the memset may still be running)
     if (er == hipSuccess) er = waited;
     if (er == hipSuccess) er = hipMemcpy(kept, d_kept, 2 * sizeof(unsigned), hipMemcpyDeviceToHost);
-    (void)hipFree(d_all);
     return er;
 }
 
@@ -956,10 +956,11 @@ inline hipError_t room_generate_bands(hipStream_t stream, const SynPlan& syn, co
 // images of channel c that arrive before frame E.  The accumulator lives only inside this call.  With a head: room_generate_head.
 inline hipError_t room_generate(hipStream_t stream, const SynPlan& syn, const RoomPlan& room, float2* d_x, uint32_t kept[2]) {
     if (room.headed) return room_generate_head(stream, syn, &room, 1, nullptr, d_x, kept);
-    unsigned long long* d_acc = nullptr;
+    DevArray<unsigned long long> d_buf;  // the accumulators, then the two counts (a word of 8 bytes)
     const size_t acc_bytes = sizeof(unsigned long long) * 2 * room.A;
-    hipError_t er = hipMalloc(&d_acc, acc_bytes + 2 * sizeof(unsigned));
+    hipError_t er = d_buf.alloc(2 * room.A + 1);
     if (er != hipSuccess) return er;
+    unsigned long long* const d_acc = d_buf;  // view
     unsigned* d_kept = reinterpret_cast<unsigned*>(d_acc + 2 * room.A);
     er = hipMemsetAsync(d_acc, 0, acc_bytes + 2 * sizeof(unsigned), stream);
     if (er == hipSuccess) er = room_launch(stream, room, d_acc, d_kept);
@@ -972,6 +973,5 @@ inline hipError_t room_generate(hipStream_t stream, const SynPlan& syn, const Ro
     const hipError_t waited = hipStreamSynchronize(stream);  // (also after a failed launch: the memset may still be running)
     if (er == hipSuccess) er = waited;
     if (er == hipSuccess) er = hipMemcpy(kept, d_kept, 2 * sizeof(unsigned), hipMemcpyDeviceToHost);
-    (void)hipFree(d_acc);
     return er;
 }

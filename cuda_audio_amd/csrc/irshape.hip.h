@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/mcconv.h"
+#include "owned.h"
 
 constexpr int ISH_THREADS = 256;
 constexpr int ISH_WAVES = ISH_THREADS / 64;
@@ -206,12 +207,12 @@ inline hipError_t ish_shape(hipStream_t stream, const float2* d_x, uint64_t F, u
     hipError_t er = hipSuccess;
     if (sh.trim_db < 0.f && rest) {
         const unsigned grid = (unsigned)std::min<uint64_t>(ISH_SCAN_GRID, (rest / 2 + ISH_THREADS) / ISH_THREADS);
-        void* d_part = nullptr;
-        er = hipMalloc(&d_part, sizeof(unsigned long long) * grid);
+        DevArray<unsigned long long> d_part;  // (the peaks as floats first, then the positions)
+        er = d_part.alloc(grid);
         std::vector<float> pk(grid);
         std::vector<unsigned long long> at(grid);
         if (er == hipSuccess) {
-            hipLaunchKernelGGL(k_shape_peak, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x + pl.s0, rest, (float*)d_part);
+            hipLaunchKernelGGL(k_shape_peak, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x + pl.s0, rest, reinterpret_cast<float*>(d_part.get()));
             er = hipGetLastError();
         }
         if (er == hipSuccess) er = hipMemcpyAsync(pk.data(), d_part, sizeof(float) * grid, hipMemcpyDeviceToHost, stream);
@@ -225,7 +226,6 @@ inline hipError_t ish_shape(hipStream_t stream, const float2* d_x, uint64_t F, u
         }
         if (er == hipSuccess) er = hipMemcpyAsync(at.data(), d_part, sizeof(unsigned long long) * grid, hipMemcpyDeviceToHost, stream);
         if (er == hipSuccess) er = hipStreamSynchronize(stream);
-        (void)hipFree(d_part);
         if (er != hipSuccess) return er;
         uint64_t onset = ISH_NONE;
         for (unsigned long long v : at) onset = std::min<uint64_t>(onset, v);
@@ -241,11 +241,11 @@ inline hipError_t ish_shape(hipStream_t stream, const float2* d_x, uint64_t F, u
     if (eq) return ieq_finish(stream, d_x, pl, sh, *eq, d_out, n_out, sums, info, damp);
 
     const unsigned grid = (unsigned)((pl.n + ISH_THREADS - 1) / ISH_THREADS);
-    float2* d_y = nullptr;
-    double* d_part = nullptr;
+    DevArray<float2> d_y;
+    DevArray<double> d_part;
     std::vector<double> part(4 * (size_t)grid);
-    er = hipMalloc(&d_y, sizeof(float2) * pl.n);
-    if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * part.size());
+    er = d_y.alloc(pl.n);
+    if (er == hipSuccess) er = d_part.alloc(part.size());
     if (er == hipSuccess) {
         hipLaunchKernelGGL(k_shape_apply<false>, dim3(grid), dim3(ISH_THREADS), 0, stream, d_x, pl, 1.0, (float2*)nullptr, d_part);
         er = hipGetLastError();
@@ -268,15 +268,11 @@ inline hipError_t ish_shape(hipStream_t stream, const float2* d_x, uint64_t F, u
     }
     if (er == hipSuccess) er = hipMemcpyAsync(part.data(), d_part, sizeof(double) * 4 * grid, hipMemcpyDeviceToHost, stream);
     if (er == hipSuccess) er = hipStreamSynchronize(stream);
-    (void)hipFree(d_part);
-    if (er != hipSuccess) {
-        (void)hipFree(d_y);
-        return er;
-    }
+    if (er != hipSuccess) return er;
     for (int k = 0; k < 4; k++) sums[k] = 0.0;
     for (unsigned b = 0; b < grid; b++)
         for (int k = 0; k < 4; k++) sums[k] += part[4 * (size_t)b + k];
-    *d_out = d_y;
+    *d_out = d_y.release();  // the caller owns the taps from here (load_ir adopts them)
     *n_out = pl.n;
     return hipSuccess;
 }

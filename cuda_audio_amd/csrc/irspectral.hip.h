@@ -54,24 +54,15 @@ inline hipError_t second_upload(hipStream_t stream, const SecondIr& s, float2* d
 // when it has two passes, and a pair of partials per workgroup of N with their host copy.  Freed with the owner; a run that
 // failed waits for the stream before it returns, so nothing is freed under a kernel.
 struct SpectralWork {
-    double2 *d_a = nullptr, *d_b = nullptr, *d_w = nullptr;
-    double* d_part = nullptr;
+    DevArray<double2> d_a, d_b, d_w;
+    DevArray<double> d_part;
     std::vector<double> part;
-    SpectralWork() = default;
-    SpectralWork(const SpectralWork&) = delete;
-    SpectralWork& operator=(const SpectralWork&) = delete;
-    ~SpectralWork() {
-        (void)hipFree(d_a);
-        (void)hipFree(d_b);
-        (void)hipFree(d_w);
-        (void)hipFree(d_part);
-    }
     hipError_t alloc(const Fft64Plan& fft, uint64_t N) {
         part.resize(2 * (size_t)spec_groups(N));
-        hipError_t er = hipMalloc(&d_a, sizeof(double2) * N);
-        if (er == hipSuccess) er = hipMalloc(&d_b, sizeof(double2) * N);
-        if (er == hipSuccess && fft.passes == 2) er = hipMalloc(&d_w, sizeof(double2) * N);
-        if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * part.size());
+        hipError_t er = d_a.alloc(N);
+        if (er == hipSuccess) er = d_b.alloc(N);
+        if (er == hipSuccess && fft.passes == 2) er = d_w.alloc(N);
+        if (er == hipSuccess) er = d_part.alloc(part.size());
         return er;
     }
     // the first `count` partials, once the stream has run dry

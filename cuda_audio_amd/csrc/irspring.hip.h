@@ -333,10 +333,10 @@ inline void spring_response(const SpringConst& k, uint32_t rate, double hz, doub
 inline hipError_t spring_generate(hipStream_t stream, const SynPlan& syn, const SpringPlan& plan, float2* d_x) {
     const uint64_t N = plan.N, E = plan.E;
     const size_t pts = sizeof(double2) * N, acc_bytes = sizeof(long long) * 2 * E;
-    char* d_all = nullptr;
-    hipError_t er = hipMalloc(&d_all, 2 * pts + acc_bytes);
+    DevArray<char> d_all;
+    hipError_t er = d_all.alloc(2 * pts + acc_bytes);
     if (er != hipSuccess) return er;
-    double2* d_X = reinterpret_cast<double2*>(d_all);
+    double2* d_X = reinterpret_cast<double2*>(d_all.get());
     double2* d_w = reinterpret_cast<double2*>(d_all + pts);
     long long* d_acc = reinterpret_cast<long long*>(d_all + 2 * pts);
     {
@@ -357,6 +357,5 @@ inline hipError_t spring_generate(hipStream_t stream, const SynPlan& syn, const 
     }
     const hipError_t waited = hipStreamSynchronize(stream);  // (also after a failed launch: earlier kernels may still be running)
     if (er == hipSuccess) er = waited;
-    (void)hipFree(d_all);
     return er;
 }

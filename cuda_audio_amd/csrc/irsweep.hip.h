@@ -31,6 +31,7 @@
 #include <cstdio>
 
 #include "../../include/mcconv.h"
+#include "owned.h"
 
 constexpr int SWP_THREADS = 256;
 constexpr int SWP_R = 8;                                // consecutive outputs per thread
@@ -182,16 +183,14 @@ struct SweepSource {
 };
 
 // The F frames of the deconvolved IR into d_x (8-byte aligned, F float2), on `stream`.  The recording and the weight table
-// live in two temporary buffers that the caller frees once the stream has finished with them (*d_rec, *d_u; set even on failure).
-inline hipError_t swp_generate(hipStream_t stream, const SweepSource& s, float2* d_x, float2** d_rec, double** d_u) {
-    *d_rec = nullptr;
-    *d_u = nullptr;
-    hipError_t er = hipMalloc(d_rec, sizeof(float2) * s.M);
-    if (er == hipSuccess) er = hipMalloc(d_u, sizeof(double) * s.plan.N);
-    if (er == hipSuccess) er = hipMemcpy(*d_rec, s.lr, sizeof(float2) * s.M, hipMemcpyHostToDevice);
+// live in two temporary buffers that the caller frees once the stream has finished with them (d_rec, d_u).
+inline hipError_t swp_generate(hipStream_t stream, const SweepSource& s, float2* d_x, DevArray<float2>& d_rec, DevArray<double>& d_u) {
+    hipError_t er = d_rec.alloc(s.M);
+    if (er == hipSuccess) er = d_u.alloc(s.plan.N);
+    if (er == hipSuccess) er = hipMemcpy(d_rec, s.lr, sizeof(float2) * s.M, hipMemcpyHostToDevice);
     if (er != hipSuccess) return er;
-    hipLaunchKernelGGL(k_sweep_weights, dim3((unsigned)((s.plan.N + SWP_THREADS - 1) / SWP_THREADS)), dim3(SWP_THREADS), 0, stream, *d_u, s.plan);
-    hipLaunchKernelGGL(k_sweep_corr, dim3((unsigned)((s.F + SWP_T - 1) / SWP_T)), dim3(SWP_THREADS), 0, stream, *d_rec, s.M, *d_u, s.plan.N, s.offset,
+    hipLaunchKernelGGL(k_sweep_weights, dim3((unsigned)((s.plan.N + SWP_THREADS - 1) / SWP_THREADS)), dim3(SWP_THREADS), 0, stream, d_u, s.plan);
+    hipLaunchKernelGGL(k_sweep_corr, dim3((unsigned)((s.F + SWP_T - 1) / SWP_T)), dim3(SWP_THREADS), 0, stream, d_rec, s.M, d_u, s.plan.N, s.offset,
                        d_x, s.F);
     return hipGetLastError();
 }

@@ -265,11 +265,11 @@ inline hipError_t tail_run(hipStream_t stream, const float2* d_x, float2* d_y, c
     const ChunkGeom cg = chunk_geom(p.Fp);
     const uint64_t lanes = cg.lanes;
     const int signals = extend ? 2 : 1;
-    double2* d_st = nullptr;
+    DevArray<double2> d_st;
     hipError_t er = hipSuccess;
     if (p.X) {
         const DampCarry cm = damp_carry(p.c, p.X, cg.K);
-        er = hipMalloc(&d_st, sizeof(double2) * 2 * (size_t)signals * p.X * lanes);
+        er = d_st.alloc(2 * (size_t)signals * p.X * lanes);
         if (er != hipSuccess) return er;
         if (extend)
             hipLaunchKernelGGL((k_tail_chunk<false, true>), dim3(cg.grid), dim3(IEQ_THREADS), 0, stream, d_x, d_y, p, d_st);
@@ -289,6 +289,5 @@ inline hipError_t tail_run(hipStream_t stream, const float2* d_x, float2* d_y, c
         er = hipGetLastError();
     }
     const hipError_t sy = hipStreamSynchronize(stream);
-    (void)hipFree(d_st);
     return er != hipSuccess ? er : sy;
 }

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/mcconv.h"
+#include "owned.h"
 #include "params_handoff.h"
 #include "kernels.hip.h"
 #include "ossave.hip.h"
@@ -78,7 +79,7 @@ int fail(int code, const char* fmt, ...) {
 constexpr int kMaxIrs = 256;
 constexpr int kMixIrs = 4;  // merged spectra of deselected IRs: [half][buffer], table entries kMaxIrs ..
 constexpr int kStageBufs = 4;
-constexpr int kEvPool = 1024;
+constexpr int kEvPool = KernelTiming::kPool;
 constexpr int kPipe = 2;
 constexpr int kStampSlots = 64;  // timed launches between two drains whose kernels leave their own time stamps
 constexpr int kNchunk = 2;       // partition chunks of the streaming MAC: its workgroups per (bin, block)
@@ -113,19 +114,19 @@ struct IrFact {
 };
 
 struct IrEntry {
-    float4* d_H = nullptr;
-    float4* d_Hp[3] = {nullptr, nullptr, nullptr};  // fast-FIR components of the partition sequence: 3 / 9 / 27 arrays,
+    DevArray<float4> d_H;
+    DevArray<float4> d_Hp[3];                       // fast-FIR components of the partition sequence: 3 / 9 / 27 arrays,
     bool hp_valid[3] = {false, false, false};       // built on the first batch that selects that level (ensure_hp)
-    float2* d_H2 = nullptr;  // second-level spectra [2 ch][257 rows][F2_N], built on first use (k_fft2_ir)
+    DevArray<float2> d_H2;  // second-level spectra [2 ch][257 rows][F2_N], built on first use (k_fft2_ir)
     bool h2_valid = false;
-    float2* d_G2 = nullptr;  // second-level spectra for the fused 8192-point form [2 ch][257 rows][G2_N]
+    DevArray<float2> d_G2;  // second-level spectra for the fused 8192-point form [2 ch][257 rows][G2_N]
     bool g2_valid = false;
-    float2* d_h = nullptr;  // time-domain taps {L, R} (Q8 pass)
-    float4* d_Htail = nullptr;  // Q8 pass, frequency-domain form: the last partitions' spectra partition-major [P - tail_p0][256] (ensure_htail)
+    DevArray<float2> d_h;  // time-domain taps {L, R} (Q8 pass)
+    DevArray<float4> d_Htail;  // Q8 pass, frequency-domain form: the last partitions' spectra partition-major [P - tail_p0][256] (ensure_htail)
     int tail_p0 = 0;
     bool tail_valid = false;
-    float2* d_S = nullptr;   // single-transform form (mc_config.form = 1): [H_L | H_R], n_ref / 2 bins each
-    uint2* d_H16 = nullptr;  // fp16 copy of the spectra, scaled by scale16 (precision = fp16)
+    DevArray<float2> d_S;   // single-transform form (mc_config.form = 1): [H_L | H_R], n_ref / 2 bins each
+    DevArray<uint2> d_H16;  // fp16 copy of the spectra, scaled by scale16 (precision = fp16)
     float scale16 = 1.f;
     uint64_t taps = 0;
     int P = 0;
@@ -167,8 +168,8 @@ struct ActiveVoice {
 // batch of T blocks starting at block t_front, and describe the batch in `ctx`.
 struct Staged {
     BatchCtx ctx;
-    BlockParams* d_ptab;
-    float4* d_sums;
+    BlockParams* d_ptab;  // view: this batch's half of mc_engine::d_ptab
+    float4* d_sums;       // view: this batch's half of mc_engine::d_sums
     BlockParams first;  // host copy of the first block's parameters
     ActiveVoice act[MC_MAXV];
     int nact = 0;
@@ -190,15 +191,14 @@ struct JackPre {
 // state of the single-transform form (singlefft.hip.h / singlefft_host.hip.h)
 struct SfState {
     int N = 0, M = 0, AT = 1;
-    float2* d_live = nullptr;  // [half][ch][N/2] live IR spectra (the reference's irFFT, conv.h:72); bin d + M c at [d][c]
-    float2* d_W = nullptr;     // [M][512] packed output spectrum
-    float2* d_T = nullptr;     // [512][M] between the inverse passes; IR preparation: the packed taps, then U
-    float2* d_Z = nullptr;     // [N] IR preparation
-    float* d_acc = nullptr;    // [ch][N] accumulators (conv.h:74 residual): a ring, `base` = slot of the next output frame
-    unsigned* d_ctr = nullptr;
+    DevArray<float2> d_live;  // [half][ch][N/2] live IR spectra (the reference's irFFT, conv.h:72); bin d + M c at [d][c]
+    DevArray<float2> d_W;     // [M][512] packed output spectrum
+    DevArray<float2> d_T;     // [512][M] between the inverse passes; IR preparation: the packed taps, then U
+    DevArray<float2> d_Z;     // [N] IR preparation
+    DevArray<float> d_acc;    // [ch][N] accumulators (conv.h:74 residual): a ring, `base` = slot of the next output frame
+    DevArray<unsigned> d_ctr;
     unsigned base = 0;
-    float* d_io[4] = {nullptr, nullptr, nullptr, nullptr};  // staging of host-buffer batches, io_cap frames each
-    size_t io_cap = 0;
+    DevArray<float> d_io[4];  // staging of host-buffer batches, Tmax blocks each
     size_t lds_bytes = 0;
     bool stockham = false;  // MCCONV_SF_STOCKHAM: pass 2 of the inverse through the LDS transform whatever the size
 };
@@ -206,8 +206,9 @@ struct SfState {
 struct mc_engine {
     mc_config cfg;
     int device = 0;
-    SfState* sf = nullptr;  // != null: the engine runs the reference's single-transform form (singlefft.hip.h)
-    hipStream_t own_stream = nullptr, stream = nullptr;
+    std::unique_ptr<SfState> sf;  // != null: the engine runs the reference's single-transform form (singlefft.hip.h)
+    Stream own_stream;
+    hipStream_t stream = nullptr;  // view: own_stream, or the caller's (mc_set_stream)
     int Tcap = 0;  // blocks the scratch buffers and rings are sized for: >= Tmax, and enough to re-render history in few launches
     int Tmax = 0, Pcap = 0, Pstride = 0, ring = 0, sr = 0, wr = 0, rc = 0, Tstream = 0;
     int stream_threshold = 0;
@@ -216,53 +217,49 @@ struct mc_engine {
     int mix_buf[2] = {0, 0};  // which of its two merged-IR entries half i used last
     int nirs = 0;
 
-    uint2* d_fdl16 = nullptr;  // fp16 mirror of the delay line (precision = fp16)
+    DevArray<uint2> d_fdl16;  // fp16 mirror of the delay line (precision = fp16)
     bool half = false;
-    float4* d_Yc = nullptr;  // [256][Tcap] partition sums combined from the fast-FIR components
-    float2* d_stash = nullptr;  // second-level transform: spectra parked between the transforms and the products
-    size_t stash_chunks = 0;  // capacity of d_stash in sequences per bin (chunks x sequences per chunk)
+    float4* d_Yc = nullptr;  // view of d_Ycbuf[0], pipelined: of the batch parity's: [256][Tcap] partition sums combined from the fast-FIR components
+    DevArray<float2> d_stash;  // second-level transform: spectra parked between the transforms and the products
     // Pipelined batches (mc_config.pipeline): the inverse transforms and the post stage of batch k run on a second
     // stream under the MAC of batch k + 1.  Scratch that both touch is double-buffered by batch parity.
     bool pipelined = false;
-    hipStream_t post_stream = nullptr;
-    hipEvent_t ev_mac[2][2], ev_corr[2], ev_post[2];
+    Stream post_stream;
+    Event ev_mac[2][2], ev_corr[2], ev_post[2];
     bool post_pending[2] = {false, false};
-    float4 *d_Ybuf[2] = {nullptr, nullptr}, *d_Ycbuf[2] = {nullptr, nullptr}, *d_partbuf[2] = {nullptr, nullptr};
-    float4 *d_tail = nullptr, *d_tailbuf[2] = {nullptr, nullptr};  // chunk partials of the last 2^levels blocks (fast-FIR form)
-    float4 *d_fdl = nullptr, *d_slotgain = nullptr, *d_Y = nullptr, *d_part = nullptr, *d_sums = nullptr;
-    float *d_seg = nullptr, *d_wet = nullptr;
-    double* d_cring = nullptr;
-    double* d_wring = nullptr;  // [rc][4] window sums per block of an overlap-save batch (k_out_windows), indexed like d_cring
-    double* d_ctot = nullptr;   // [ceil(Tmax/256)][4] chunk totals of the Q1/Q2 prefix sums
+    DevArray<float4> d_Ybuf[2], d_Ycbuf[2], d_partbuf[2];
+    DevArray<float4> d_tailbuf[2];  // chunk partials of the last 2^levels blocks (fast-FIR form)
+    float4 *d_Y = nullptr, *d_tail = nullptr, *d_part = nullptr;  // views of d_Ybuf[0], d_tailbuf[0], d_partbuf[0] (pipelined: of the batch parity's)
+    DevArray<float4> d_fdl, d_slotgain, d_sums;
+    DevArray<float> d_seg, d_wet;
+    DevArray<double> d_cring;
+    DevArray<double> d_wring;  // [rc][4] window sums per block of an overlap-save batch (k_out_windows), indexed like d_cring
+    DevArray<double> d_ctot;   // [ceil(Tmax/256)][4] chunk totals of the Q1/Q2 prefix sums
     // predelay epochs: what blocks played under earlier predelays still owe, by absolute output sample
-    float *d_res_mac = nullptr, *d_res_fix = nullptr;  // [2][rr] each
+    DevArray<float> d_res_mac, d_res_fix;  // [2][rr] each
     int rr = 0;
     uint64_t res_end = 0;     // the rings hold output samples < res_end
     uint64_t epoch_b0 = 0;    // first block of the live epoch
     uint64_t cur_delay = 0;   // its predelay
-    float* d_xhist = nullptr;   // [2][xr] input history (Q8 pass)
-    float4* d_gring = nullptr;  // [MC_MAXV][rc] wet gains of past blocks (Q8 pass)
+    DevArray<float> d_xhist;   // [2][xr] input history (Q8 pass)
+    DevArray<float4> d_gring;  // [MC_MAXV][rc] wet gains of past blocks (Q8 pass)
     int xr = 0;
-    BlockParams* d_ptab = nullptr;
-    float2* d_tw = nullptr;
-    float* d_io[4] = {nullptr, nullptr, nullptr, nullptr};  // in1, in2, outL, outR staging for host-pointer calls
+    DevArray<BlockParams> d_ptab;
+    DevArray<float2> d_tw;
+    DevArray<float> d_io[4];  // in1, in2, outL, outR staging for host-pointer calls
     int Thost = 0;                                          // blocks per chunk of a host-buffer batch staged through h_io
     // host-buffer batches whose buffers are pinned (mc_host_alloc, hipHostMalloc, hipHostRegister): chunks of Tdev blocks,
     // H2D and compute on two streams, the output stored straight into the caller's buffers; input staging (three sets)
-    // allocated on first use
-    float* d_pio[3][2] = {{nullptr, nullptr}, {nullptr, nullptr}, {nullptr, nullptr}};
+    // made by the first such batch
+    std::unique_ptr<PinnedStaging> pinned;
     int Tdev = 0;
-    hipStream_t h2d_stream = nullptr;
-    hipEvent_t ev_h2d[3] = {nullptr, nullptr, nullptr}, ev_comp[3] = {nullptr, nullptr, nullptr};
-    float* h_io = nullptr;                                  // pinned mirror of d_io, 4 * Thost * 256
-    float* hd_io = nullptr;                                 // device-side address of h_io (mapped, zero-copy)
-    unsigned* h_flag = nullptr;                             // completion word of the single-period path (mapped)
-    unsigned* hd_flag = nullptr;
+    PinnedArray<float> h_io;       // pinned mirror of d_io, 4 * Thost * 256 (mapped, zero-copy: h_io.dev())
+    PinnedArray<unsigned> h_flag;  // completion word of the single-period path (mapped)
     unsigned flag_seq = 0;
-    unsigned* d_done_ctr = nullptr;  // workgroups of the period's last kernel that have finished
+    DevArray<unsigned> d_done_ctr;  // workgroups of the period's last kernel that have finished
     bool spin_wait = true;
-    BlockParams* h_ptab[kStageBufs] = {nullptr, nullptr, nullptr, nullptr};
-    hipEvent_t ptab_ev[kStageBufs];
+    PinnedArray<BlockParams> h_ptab[kStageBufs];
+    Event ptab_ev[kStageBufs];
     bool ptab_ev_used[kStageBufs] = {false, false, false, false};
     int ptab_next = 0;
 
@@ -303,36 +300,35 @@ struct mc_engine {
         bool valid = false;
         uint64_t block = 0, predelay = 0, epoch_b0 = 0;
         int vir[2][MC_MAXV];
-        const float* buf = nullptr;
+        const float* buf = nullptr;  // view: the d_drop buffer that launch wrote
     } dspec;
     uint64_t spec_block = 0;
     int spec_vir[2][MC_MAXV];
     int spec_nact = 0;
-    hipEvent_t ev_tail = nullptr;
-    float4* d_part_jack[2] = {nullptr, nullptr};  // JACK path: the sweep's partials, double-buffered by block parity
+    Event ev_tail;
+    DevArray<float4> d_part_jack[2];  // JACK path: the sweep's partials, double-buffered by block parity
     bool td_fft = true;                           // Q8 regime, batches: the cut terms in the frequency domain (MCCONV_TD_FFT=0: time-domain tiles)
-    float2* d_dropbuf = nullptr;                  // batches, Q8 regime: the cut terms of a batch's blocks [Tmax][256] {L, R} (k_drop_fft), allocated by the first such batch
-    float* d_drop[2] = {nullptr, nullptr};        // JACK path, Q8 regime: a period's tail-drop terms [2][1024] (k_drop_period), by period parity
+    DevArray<float2> d_dropbuf;                   // batches, Q8 regime: the cut terms of a batch's blocks [Tmax][256] {L, R} (k_drop_fft), allocated by the first such batch
+    DevArray<float> d_drop[2];                    // JACK path, Q8 regime: a period's tail-drop terms [2][1024] (k_drop_period), by period parity
     JackPre pre;                     // the period parked one call ahead
     bool park = true;                // MCCONV_NO_PARK=1: every period launched when it arrives
     unsigned long long park_ticks = 10000000ull;  // a parked tail gives up after this many 100 MHz ticks (100 ms; MCCONV_PARK_MS)
-    unsigned long long* h_bell = nullptr;         // mapped: {sequence number, command} the parked tail polls
-    unsigned long long* hd_bell = nullptr;
+    unsigned long long* h_bell = nullptr;         // view into h_flag: {sequence number, command} the parked tail polls
+    unsigned long long* hd_bell = nullptr;        // view into h_flag.dev(): the same words as the device sees them
     // JACK path on a large-BAR system: doorbell and period input live in fine-grained DEVICE memory that the CPU writes
     // straight through the BAR (posted writes), so the parked tail polls and reads locally instead of over PCIe
     // (MCCONV_BAR_IO=0: mapped host memory as before).  16 floats = the doorbell's line, then in1, in2 (room for 1024 frames each).
-    float* d_bar = nullptr;
+    DevArray<float> d_bar;
     bool bar_io = false;
     // Tagged I/O of the 256-frame JACK path (TailArgs::in_gran / out_gran): input granules at byte 16384 of d_bar, output granules
     // in mapped host memory.  On where the BAR path is.
     bool tio = false;
-    unsigned long long* h_gran = nullptr;   // [2][256] output granules {value, sequence number}
-    unsigned long long* hd_gran = nullptr;
-    unsigned* h_exited = nullptr;                 // mapped: sequence number of a parked tail that gave up on its own
-    unsigned* hd_exited = nullptr;
+    PinnedArray<unsigned long long> h_gran;   // [2][256] output granules {value, sequence number}
+    unsigned* h_exited = nullptr;                 // view into h_flag: sequence number of a parked tail that gave up on its own
+    unsigned* hd_exited = nullptr;                // view into h_flag.dev()
     // how often a parked period was used / gave up on its own (host away > park_ms) / was told to give up: mc_debug_read item 6
     uint64_t n_park_hit = 0, n_park_timeout = 0, n_park_cancel = 0;
-    unsigned* d_tailform = nullptr;  // 256-frame tails by the form partition 0 took {frequency domain, time domain}, counted by the kernel (mc_debug_read item 16)
+    DevArray<unsigned> d_tailform;  // 256-frame tails by the form partition 0 took {frequency domain, time domain}, counted by the kernel (mc_debug_read item 16)
     int tail_form = 0;               // MCCONV_TAIL_FORM=td|fd: one form for every 256-frame tail (0: the first look decides)
     uint64_t n_drop_carried = 0;  // JACK path, Q8 regime: periods whose cut terms came with the launch before theirs (mc_debug_read item 9, fourth word)
     uint64_t n_mac_form[3] = {0, 0, 0};  // batches whose partition sums took the fused / split second-level transform / the resident MAC (form_counter; mc_debug_read item 10)
@@ -345,8 +341,8 @@ struct mc_engine {
     bool fft2 = true;     // long batches: second-level transform along the block axis instead of the MAC
     bool fft2_fused = true;  // ... in the fused 8192-point form where it applies
     int64_t fft2_work = 300000;  // blocks x partitions from which a batch takes the fused second-level form (MCCONV_FFT2_WORK)
-    unsigned* d_cticket = nullptr;  // ticket counter of the riding prefix-sum workgroups (see CorrArgs)
-    unsigned* d_cflag = nullptr;    // [ceil(Tmax/256)] launch sequence number per published chunk total
+    unsigned* d_cticket = nullptr;  // view, the last word of d_cflag: ticket counter of the riding prefix-sum workgroups (see CorrArgs)
+    DevArray<unsigned> d_cflag;     // [ceil(Tmax/256)] launch sequence number per published chunk total
     unsigned cticket_base = 0, cflag_seq = 0;
     // Long settled batches as overlap-save segments of 512 x 8192 frames (ossave.hip.h): whole batches on one fp32 engine whose
     // window carries one set of gains, outside the Q8 regime.  Buffers and the spectra of the sounding (IR set, gains) are
@@ -354,13 +350,10 @@ struct mc_engine {
     bool os_hold = false;       // set around a batch whose output pointers are mapped HOST memory (mc_process_batch with pinned buffers)
     bool os_on = true;          // MCCONV_OS=0: such batches through the second-level transform as before (measurement)
     int os_min_blocks = 12288;  // shortest batch that takes the form (a segment costs the same however little of it is used; MCCONV_OS_MIN)
-    float4* d_os_T = nullptr;   // [segments][256 row pairs][8192] {row k1, row 512 - k1} between the passes
-    size_t os_T_segs = 0;
-    float4* d_os_part = nullptr;  // [segments][512 tiles][512] the tiles' sixteenths of the blocks' sums {S1, S2, A1, A2}
-    size_t os_part_segs = 0;
-    float4 *d_os_SP = nullptr, *d_os_SP0 = nullptr;  // spectra A, B of the cached key, in the row pass's order
-    float* d_os_planes = nullptr;  // gain-weighted taps, four planes of os_planes_n floats
-    size_t os_planes_n = 0;
+    DevArray<float4> d_os_T;     // [segments][256 row pairs][8192] {row k1, row 512 - k1} between the passes
+    DevArray<float4> d_os_part;  // [segments][512 tiles][512] the tiles' sixteenths of the blocks' sums {S1, S2, A1, A2}
+    DevArray<float4> d_os_SP, d_os_SP0;  // spectra A, B of the cached key, in the row pass's order
+    DevArray<float> d_os_planes;  // gain-weighted taps, four planes
     struct OsKey {
         bool valid = false;
         int n = 0;
@@ -371,9 +364,8 @@ struct mc_engine {
     uint64_t ir_gen = 0;                  // counts changes of any IR's taps (load, reload, merge)
     uint64_t n_os[2] = {0, 0};            // batches that took the form, spectra builds (mc_debug_read item 11)
     // the small launches of such a batch - prefix sums, the tail's delay-line slots, the last block's segment - run on a side
-    // stream beside the three passes
-    hipStream_t os_stream = nullptr;
-    hipEvent_t os_ev[3] = {nullptr, nullptr, nullptr};
+    // stream beside the three passes, made by the first such batch
+    std::unique_ptr<OsSide> os_side;
     int ffa_levels = 3;   // resident MAC in fast-FIR form (up to this many nested levels) when batch and IR are long enough
     bool sliced = false;  // block-sliced calls keep no wet / segment history outside their slices
     int slice_first = -1;  // ... and transform only what their windows reach: the slice start must not move
@@ -386,12 +378,10 @@ struct mc_engine {
 
     // kernel timing
     bool ktiming = false;
-    hipEvent_t kev[kEvPool][2];
+    std::unique_ptr<KernelTiming> kt;  // made by the first mc_enable_kernel_timing(on)
     uint32_t kev_blocks[kEvPool];
     bool kev_stamped[kEvPool];            // the launch carries in-kernel time stamps (a single period's sweep)
-    unsigned long long* d_stamps = nullptr;  // [kStampSlots][MC_STAMP_WGS][2] {start, end} per workgroup in 100 MHz ticks
-    int kev_n = 0;
-    bool kev_created = false;
+    int kev_n = 0;  // (KernelTiming::d_stamps: [kStampSlots][MC_STAMP_WGS][2] {start, end} per workgroup in 100 MHz ticks)
     mc_kernel_stats ks;
 };
 
@@ -411,7 +401,7 @@ void ring_bell(mc_engine* e, unsigned seq, unsigned command) {
     // the period was written before: release order makes it visible to the tail that acquires the doorbell
     if (e->bar_io) {
         _mm_sfence();  // the period's write-combined stores leave before the doorbell's
-        __atomic_store_n(reinterpret_cast<unsigned long long*>(e->d_bar), ((unsigned long long)command << 32) | seq, __ATOMIC_RELEASE);
+        __atomic_store_n(reinterpret_cast<unsigned long long*>(e->d_bar.get()), ((unsigned long long)command << 32) | seq, __ATOMIC_RELEASE);
         _mm_sfence();  // ... and the doorbell does not wait in the write-combining buffer
         return;
     }
@@ -433,7 +423,7 @@ void unpark(mc_engine* e) {
 }
 
 hipError_t reset_stamps(mc_engine* e) {
-    return hipMemset(e->d_stamps, 0, sizeof(unsigned long long) * 2 * MC_STAMP_WGS * kStampSlots);
+    return hipMemset(e->kt->d_stamps, 0, sizeof(unsigned long long) * e->kt->d_stamps.size());
 }
 
 int drain_kernel_events(mc_engine* e) {
@@ -443,14 +433,14 @@ int drain_kernel_events(mc_engine* e) {
     std::vector<unsigned long long> stamps;
     bool any_stamped = false;
     for (int i = 0; i < e->kev_n; i++) any_stamped = any_stamped || e->kev_stamped[i];
-    if (any_stamped && e->d_stamps) {
+    if (any_stamped) {
         stamps.resize((size_t)2 * MC_STAMP_WGS * kStampSlots);
-        HIP_TRY(hipMemcpy(stamps.data(), e->d_stamps, sizeof(unsigned long long) * stamps.size(), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(stamps.data(), e->kt->d_stamps, sizeof(unsigned long long) * stamps.size(), hipMemcpyDeviceToHost));
         HIP_TRY(reset_stamps(e));
     }
     for (int i = 0; i < e->kev_n; i++) {
         float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, e->kev[i][0], e->kev[i][1]));
+        HIP_TRY(hipEventElapsedTime(&ms, e->kt->ev[i][0], e->kt->ev[i][1]));
         if (e->kev_stamped[i] && !stamps.empty() && i < kStampSlots) {
             unsigned long long lo = ~0ull, hi = 0;
             const unsigned long long* sp = stamps.data() + (size_t)2 * MC_STAMP_WGS * i;
@@ -493,16 +483,16 @@ int zero_state(mc_engine* e) {
         int rc = drain_post(e);
         if (rc) return rc;
     }
-    HIP_TRY(hipMemsetAsync(e->d_fdl, 0, sizeof(float4) * (size_t)MC_NB * e->ring, e->stream));
-    if (e->d_fdl16) HIP_TRY(hipMemsetAsync(e->d_fdl16, 0, sizeof(uint2) * (size_t)MC_NB * e->ring, e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_slotgain, 0, sizeof(float4) * (size_t)MC_MAXV * e->ring, e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_seg, 0, sizeof(float) * (size_t)e->sr * 2 * FFT_N, e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_wet, 0, sizeof(float) * 2 * (size_t)e->wr, e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_cring, 0, sizeof(double) * 4 * (size_t)e->rc, e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_xhist, 0, sizeof(float) * 2 * (size_t)e->xr, e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_gring, 0, sizeof(float4) * (size_t)MC_MAXV * e->rc, e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_res_mac, 0, sizeof(float) * 2 * (size_t)e->rr, e->stream));
-    HIP_TRY(hipMemsetAsync(e->d_res_fix, 0, sizeof(float) * 2 * (size_t)e->rr, e->stream));
+    HIP_TRY(e->d_fdl.zero(e->stream));
+    HIP_TRY(e->d_fdl16.zero(e->stream));  // (empty unless precision = fp16)
+    HIP_TRY(e->d_slotgain.zero(e->stream));
+    HIP_TRY(e->d_seg.zero(e->stream));
+    HIP_TRY(e->d_wet.zero(e->stream));
+    HIP_TRY(e->d_cring.zero(e->stream));
+    HIP_TRY(e->d_xhist.zero(e->stream));
+    HIP_TRY(e->d_gring.zero(e->stream));
+    HIP_TRY(e->d_res_mac.zero(e->stream));
+    HIP_TRY(e->d_res_fix.zero(e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     e->res_end = e->epoch_b0 = e->cur_delay = 0;
     e->sliced = false;
@@ -540,7 +530,7 @@ constexpr int kTailSpan = 48;
 int ensure_htail(mc_engine* e, const IrEntry* irc) {
     IrEntry& ir = *const_cast<IrEntry*>(irc);
     if (ir.tail_valid || !ir.d_H) return MC_OK;
-    if (!ir.d_Htail) HIP_TRY(hipMalloc(&ir.d_Htail, sizeof(float4) * (size_t)kTailSpan * MC_NB));
+    if (!ir.d_Htail) HIP_TRY(ir.d_Htail.alloc((size_t)kTailSpan * MC_NB));
     ir.tail_p0 = std::max(0, ir.P - kTailSpan);
     hipLaunchKernelGGL(k_h_tail, dim3(kTailSpan), dim3(MC_NB), 0, e->stream, (const float4*)ir.d_H, e->Pstride, ir.tail_p0, ir.P, ir.d_Htail);
     HIP_TRY(hipGetLastError());
@@ -556,7 +546,7 @@ int ensure_hp(mc_engine* e, hipStream_t st, const IrEntry* irc, int lvl) {
     IrEntry& ir = *const_cast<IrEntry*>(irc);
     if (ir.hp_valid[lvl - 1]) return MC_OK;
     const size_t n = (size_t)(lvl == 1 ? 3 : (lvl == 2 ? 9 : 27)) * MC_NB * (e->Pstride >> lvl);
-    if (!ir.d_Hp[lvl - 1]) HIP_TRY(hipMalloc(&ir.d_Hp[lvl - 1], sizeof(float4) * n));
+    if (!ir.d_Hp[lvl - 1]) HIP_TRY(ir.d_Hp[lvl - 1].alloc(n));
     hipLaunchKernelGGL(k_polyphase, dim3(2048), dim3(256), 0, st, ir.d_H, ir.d_Hp[lvl - 1], e->Pstride, lvl);
     HIP_TRY(hipGetLastError());
     ir.hp_valid[lvl - 1] = true;
@@ -567,7 +557,7 @@ int ensure_hp(mc_engine* e, hipStream_t st, const IrEntry* irc, int lvl) {
 int ensure_fft2(mc_engine* e, hipStream_t st, const IrEntry* irc) {
     IrEntry& ir = *const_cast<IrEntry*>(irc);
     if (ir.h2_valid) return MC_OK;
-    if (!ir.d_H2) HIP_TRY(hipMalloc(&ir.d_H2, sizeof(float2) * (size_t)2 * 257 * F2_N));
+    if (!ir.d_H2) HIP_TRY(ir.d_H2.alloc((size_t)2 * 257 * F2_N));
     // a partition shard transforms its own run of the partition sequence, H[pb .. pe)
     const int pb = std::min<int>((int)e->cfg.part_begin, ir.P), pe = e->cfg.part_end ? std::min<int>((int)e->cfg.part_end, ir.P) : ir.P;
     hipLaunchKernelGGL(k_fft2_ir, dim3(257, 2), dim3(F2_THREADS), 0, st, ir.d_H + pb, e->Pstride, std::min(std::max(pe - pb, 0), F2_N), ir.d_H2);
@@ -579,7 +569,7 @@ int ensure_fft2(mc_engine* e, hipStream_t st, const IrEntry* irc) {
 int ensure_g2(mc_engine* e, hipStream_t st, const IrEntry* irc) {
     IrEntry& ir = *const_cast<IrEntry*>(irc);
     if (ir.g2_valid) return MC_OK;
-    if (!ir.d_G2) HIP_TRY(hipMalloc(&ir.d_G2, sizeof(float2) * (size_t)2 * 257 * G2_N));
+    if (!ir.d_G2) HIP_TRY(ir.d_G2.alloc((size_t)2 * 257 * G2_N));
     const int pb = std::min<int>((int)e->cfg.part_begin, ir.P), pe = e->cfg.part_end ? std::min<int>((int)e->cfg.part_end, ir.P) : ir.P;
     hipLaunchKernelGGL(k_g2_ir, dim3(257), dim3(G2_THREADS), 0, st, ir.d_H + pb, e->Pstride, std::min(std::max(pe - pb, 0), G2_N), ir.d_G2);
     HIP_TRY(hipGetLastError());
@@ -601,8 +591,8 @@ int consolidate_voices(mc_engine* e, int i) {
     const int midx = kMaxIrs + i * 2 + buf;
     IrEntry& M = e->irs[midx];
     const size_t nH = (size_t)MC_NB * e->Pstride * 4, nh_cap = (size_t)e->cfg.n_ref * 2;
-    if (!M.d_H) HIP_TRY(hipMalloc(&M.d_H, sizeof(float) * nH));
-    if (!M.d_h) HIP_TRY(hipMalloc(&M.d_h, sizeof(float) * nh_cap));
+    if (!M.d_H) HIP_TRY(M.d_H.alloc(nH / 4));
+    if (!M.d_h) HIP_TRY(M.d_h.alloc(nh_cap / 2));
     MixSrc sH, sh;
     std::memset(&sH, 0, sizeof(sH));
     std::memset(&sh, 0, sizeof(sh));
@@ -612,10 +602,10 @@ int consolidate_voices(mc_engine* e, int i) {
     for (int v = 0; v < MC_MAXV; v++) {
         if (vs[v].ir < 0 || vs[v].coef == 0.0 || !e->irs[vs[v].ir].d_H) continue;
         const IrEntry& src = e->irs[vs[v].ir];
-        sH.p[v] = reinterpret_cast<const float*>(src.d_H);
+        sH.p[v] = reinterpret_cast<const float*>(src.d_H.get());
         sH.n[v] = nH;
         sH.c[v] = (float)vs[v].coef;
-        sh.p[v] = reinterpret_cast<const float*>(src.d_h);
+        sh.p[v] = reinterpret_cast<const float*>(src.d_h.get());
         sh.n[v] = (size_t)src.taps * 2;
         sh.c[v] = (float)vs[v].coef;
         for (int c = 0; c < 4; c++) sums[c] += vs[v].coef * src.sums[c];
@@ -623,8 +613,8 @@ int consolidate_voices(mc_engine* e, int i) {
         P = std::max(P, src.P);
         bound16 += std::fabs(vs[v].coef) * 16384.0 / (double)src.scale16;  // |H_j| < 2^14 / scale16_j
     }
-    hipLaunchKernelGGL(k_mix, dim3(2048), dim3(256), 0, e->stream, reinterpret_cast<float*>(M.d_H), nH, sH);
-    hipLaunchKernelGGL(k_mix, dim3(256), dim3(256), 0, e->stream, reinterpret_cast<float*>(M.d_h), (size_t)taps * 2, sh);
+    hipLaunchKernelGGL(k_mix, dim3(2048), dim3(256), 0, e->stream, reinterpret_cast<float*>(M.d_H.get()), nH, sH);
+    hipLaunchKernelGGL(k_mix, dim3(256), dim3(256), 0, e->stream, reinterpret_cast<float*>(M.d_h.get()), (size_t)taps * 2, sh);
     HIP_TRY(hipGetLastError());
     invalidate_derived(M);
     e->ir_gen++;
@@ -635,7 +625,7 @@ int consolidate_voices(mc_engine* e, int i) {
         int ex = 0;
         if (bound16 > 0.0) std::frexp(bound16, &ex);
         M.scale16 = std::ldexp(1.0f, std::min(13 - ex, kScale16MaxExp));
-        if (!M.d_H16) HIP_TRY(hipMalloc(&M.d_H16, sizeof(uint2) * (nH / 4)));
+        if (!M.d_H16) HIP_TRY(M.d_H16.alloc(nH / 4));
         hipLaunchKernelGGL(k_to_half, dim3(1024), dim3(256), 0, e->stream, M.d_H, M.d_H16, nH / 4, M.scale16);
         HIP_TRY(hipGetLastError());
     }
@@ -914,7 +904,7 @@ int prepare_drop_fft(mc_engine* e, const int (&vir)[2][MC_MAXV], uint64_t predel
                 const int rc_t = ensure_htail(e, &e->irs[vir[h][v]]);
                 if (rc_t != MC_OK) return rc_t;
             }
-    if (!e->d_dropbuf) HIP_TRY(hipMalloc(&e->d_dropbuf, sizeof(float2) * (size_t)e->Tmax * MC_B));
+    if (!e->d_dropbuf) HIP_TRY(e->d_dropbuf.alloc((size_t)e->Tmax * MC_B));
     return MC_OK;
 }
 
@@ -1213,13 +1203,7 @@ int mac_split(mc_engine* e, hipStream_t st, const FormChoice& fc, const ActiveVo
     const int chunk_t = F2_N - fc.taps + 1;
     const dim3 grid(MC_NB, (T + chunk_t - 1) / chunk_t);
     const size_t need = (size_t)grid.y * nseq;
-    if (e->stash_chunks < need) {
-        HIP_TRY(hipStreamSynchronize(st));
-        if (e->d_stash) (void)hipFree(e->d_stash);
-        e->d_stash = nullptr;
-        HIP_TRY(hipMalloc(&e->d_stash, sizeof(float2) * need * MC_NB * F2_N));
-        e->stash_chunks = need;
-    }
+    HIP_TRY(e->d_stash.grow(need * MC_NB * F2_N, st));
     hipLaunchKernelGGL(k_f2_fwd, dim3(grid.x * grid.y * nseq), dim3(F2_THREADS), 0, st, e->d_fdl, e->ring, slot0, T, chunk_t, fc.taps, e->d_stash,
                        nseq, gg);
     hipLaunchKernelGGL(k_f2_prod, dim3(grid.x * grid.y * 2), dim3(F2_THREADS), 0, st, e->d_stash, T, chunk_t, fc.taps, vv, e->d_Yc, e->Tcap, nseq);
@@ -1544,28 +1528,11 @@ bool os_applies(const mc_engine* e, const Staged& st, int count, bool slice, con
 int ensure_os(mc_engine* e, const Staged& st, int nseg) {
     const size_t seg_el = (size_t)OS_ITEMS * OS_N2;
     const size_t want = (size_t)std::max(nseg, 2);  // (the spectra are built in two segments' worth of it)
-    if (e->os_T_segs < want) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        if (e->d_os_T) (void)hipFree(e->d_os_T);
-        e->d_os_T = nullptr;
-        e->os_T_segs = 0;
-        HIP_TRY(hipMalloc(&e->d_os_T, sizeof(float4) * seg_el * want));
-        e->os_T_segs = want;
-    }
-    if (e->os_part_segs < (size_t)nseg) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        if (e->d_os_part) (void)hipFree(e->d_os_part);
-        e->d_os_part = nullptr;
-        e->os_part_segs = 0;
-        HIP_TRY(hipMalloc(&e->d_os_part, sizeof(float4) * (size_t)OS_TPS * OS_N1 * (size_t)nseg));
-        e->os_part_segs = (size_t)nseg;
-    }
-    if (!e->os_stream) {
-        HIP_TRY(hipStreamCreateWithFlags(&e->os_stream, hipStreamNonBlocking));
-        for (int i = 0; i < 3; i++) HIP_TRY(hipEventCreateWithFlags(&e->os_ev[i], hipEventDisableTiming));
-    }
-    if (!e->d_os_SP) HIP_TRY(hipMalloc(&e->d_os_SP, sizeof(float4) * seg_el * 2));
-    if (!e->d_os_SP0) HIP_TRY(hipMalloc(&e->d_os_SP0, sizeof(float4) * 2 * OS_N2));
+    HIP_TRY(e->d_os_T.grow(seg_el * want, e->stream));
+    HIP_TRY(e->d_os_part.grow((size_t)OS_TPS * OS_N1 * (size_t)nseg, e->stream));
+    if (!e->os_side) HIP_TRY(make_group(e->os_side));
+    if (!e->d_os_SP) HIP_TRY(e->d_os_SP.alloc(seg_el * 2));
+    if (!e->d_os_SP0) HIP_TRY(e->d_os_SP0.alloc((size_t)2 * OS_N2));
     mc_engine::OsKey key;
     OsMix mix;
     std::memset(&mix, 0, sizeof(mix));
@@ -1594,14 +1561,7 @@ int ensure_os(mc_engine* e, const Staged& st, int nseg) {
         !std::memcmp(k0.ir1, key.ir1, sizeof(key.ir1)) && !std::memcmp(k0.g, key.g, sizeof(key.g)))
         return MC_OK;
     const int64_t np = (lmax + 3) & ~(int64_t)3;
-    if (e->os_planes_n < (size_t)np) {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        if (e->d_os_planes) (void)hipFree(e->d_os_planes);
-        e->d_os_planes = nullptr;
-        e->os_planes_n = 0;
-        HIP_TRY(hipMalloc(&e->d_os_planes, sizeof(float) * 4 * (size_t)np));
-        e->os_planes_n = (size_t)np;
-    }
+    HIP_TRY(e->d_os_planes.grow(4 * (size_t)np, e->stream));
     e->os_key.valid = false;
     hipLaunchKernelGGL(k_os_ir_mix, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, e->stream, mix, e->d_os_planes, np);
     OsGeo G;
@@ -1643,7 +1603,7 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
     // (on HIP's special stream handles - MC_STREAM_DEFAULT = hipStreamLegacy, hipStreamPerThread - everything runs in line:
     // hipStreamWaitEvent on such a handle faults in this runtime)
     const hipStream_t main = e->stream;
-    const hipStream_t side = reinterpret_cast<uintptr_t>(main) > 2 ? e->os_stream : main;
+    const hipStream_t side = reinterpret_cast<uintptr_t>(main) > 2 ? (hipStream_t)e->os_side->stream : main;
     // A whole batch of two segments or more outside the Q8 regime: the side stream starts behind the column pass, runs the prefix
     // chain the output pass waits for and only then the state later calls read, beside the row pass (which leaves half a CU's
     // wave slots free; the column pass fills them all).  The Q8 regime and block slices produce what the prefix chain or the
@@ -1651,8 +1611,8 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
     // row and output passes together (about 40 us) are shorter than the side stream's kernels in a row (about 70).
     const bool after = side != main && !slice && q8_shift < 0 && nseg >= 2;
     if (side != main && !after) {  // the side stream starts where the engine's stream stands
-        HIP_TRY(hipEventRecord(e->os_ev[0], main));
-        HIP_TRY(hipStreamWaitEvent(side, e->os_ev[0], 0));
+        HIP_TRY(hipEventRecord(e->os_side->ev[0], main));
+        HIP_TRY(hipStreamWaitEvent(side, e->os_side->ev[0], 0));
     }
     const int hist_from = (int)std::max<int64_t>(0, (int64_t)T - (int64_t)((e->cfg.n_ref + MC_MAX_PREDELAY) / MC_B + 4));
     // the batch's tail: what any later window, Q8 pass or re-render of a predelay epoch can reach
@@ -1709,7 +1669,7 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
     hipLaunchKernelGGL(k_os_cols, dim3(nseg * OS_TPS), dim3(OS_THREADS), 0, main, d_in1, d_in2, (const float*)e->d_xhist, e->xr, G, e->d_os_T,
                        e->cfg.compat ? e->d_os_part : (float4*)nullptr, e->d_tw);
     if (side != main) {  // (with kernel timing the row pass's opening event serves: one marker fewer on the engine's stream)
-        const hipEvent_t cols_done = after && e->ktiming ? e->kev[e->kev_n][0] : e->os_ev[1];
+        const hipEvent_t cols_done = after && e->ktiming ? e->kt->ev[e->kev_n][0] : e->os_side->ev[1];
         HIP_TRY(hipEventRecord(cols_done, main));
         HIP_TRY(hipStreamWaitEvent(side, cols_done, 0));
     }
@@ -1727,28 +1687,28 @@ int run_os(mc_engine* e, const Staged& st, mc_engine::BatchCtx& stored, const fl
         hipLaunchKernelGGL(k_out_windows, dim3((T + 255) / 256), dim3(256), 0, side, oa, T, e->d_wring);
         oa.wring = e->d_wring;
     }
-    if (side != main) HIP_TRY(hipEventRecord(e->os_ev[2], side));
+    if (side != main) HIP_TRY(hipEventRecord(e->os_side->ev[2], side));
     if (after) {  // behind the prefix chain, beside the row pass: what later calls read (k_fwd writes the input history the column pass has read)
         state_tail();
         rc = last_segment();
         if (rc) return rc;
-        HIP_TRY(hipEventRecord(e->os_ev[0], side));
+        HIP_TRY(hipEventRecord(e->os_side->ev[0], side));
     }
     if (e->ktiming) {
         e->kev_blocks[e->kev_n] = (uint32_t)wn;
-        if (!after) HIP_TRY(hipEventRecord(e->kev[e->kev_n][0], main));
+        if (!after) HIP_TRY(hipEventRecord(e->kt->ev[e->kev_n][0], main));
     }
     hipLaunchKernelGGL(k_os_rows, dim3(nseg * OS_ITEMS), dim3(G2B_THREADS), 0, main, e->d_os_T, (const float4*)e->d_os_SP, (const float4*)e->d_os_SP0, nseg);
     if (e->ktiming) {
-        HIP_TRY(hipEventRecord(e->kev[e->kev_n][1], main));
+        HIP_TRY(hipEventRecord(e->kt->ev[e->kev_n][1], main));
         e->kev_n++;
         e->ks.resident = 1;
         e->ks.partitions = (uint32_t)ovl_blocks;
         e->ks.fast_levels = form_code(MacForm::OverlapSave, 0);
     }
-    if (side != main) HIP_TRY(hipStreamWaitEvent(main, e->os_ev[2], 0));  // (the prefix ring and the window sums; where the side stream started with the call, everything it did: the cut terms, and what later calls need)
+    if (side != main) HIP_TRY(hipStreamWaitEvent(main, e->os_side->ev[2], 0));  // (the prefix ring and the window sums; where the side stream started with the call, everything it did: the cut terms, and what later calls need)
     hipLaunchKernelGGL(k_os_out, dim3(nseg * OS_TPS), dim3(OS_THREADS), 0, main, (const float4*)e->d_os_T, G, e->d_wet, e->wr, e->d_tw, oa);
-    if (after) HIP_TRY(hipStreamWaitEvent(main, e->os_ev[0], 0));  // (later calls need the rest of what the side stream did)
+    if (after) HIP_TRY(hipStreamWaitEvent(main, e->os_side->ev[0], 0));  // (later calls need the rest of what the side stream did)
     HIP_TRY(hipGetLastError());
     stored.out_from = oa.wet_head;
     stored.corr_done = true;
@@ -1914,7 +1874,7 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
             const bool timed = e->ktiming && h == 1;  // the MAC of the blocks this engine finishes: the roofline kernel
             if (timed) {
                 e->kev_blocks[e->kev_n] = (uint32_t)n;
-                HIP_TRY(hipEventRecord(e->kev[e->kev_n][0], e->stream));
+                HIP_TRY(hipEventRecord(e->kt->ev[e->kev_n][0], e->stream));
             }
             MacOut mo;
             // the Q1/Q2 prefix sums of the batch ride along with this launch and the inverse transforms' (fused form only;
@@ -1937,7 +1897,7 @@ int run_front(mc_engine* e, const float* d_in1, const float* d_in2, int T, float
                 e->cflag_seq++;
             }
             if (timed) {
-                HIP_TRY(hipEventRecord(e->kev[e->kev_n][1], e->stream));
+                HIP_TRY(hipEventRecord(e->kt->ev[e->kev_n][1], e->stream));
                 e->kev_n++;
                 e->ks.resident = mo.form != MacForm::Stream ? 1 : 0;
                 e->ks.partitions = (uint32_t)mo.swept;
@@ -2064,7 +2024,7 @@ int run_back(mc_engine* e, const float* d_in1, const float* d_in2, const float* 
                            lin_sum, e->d_wet, e->wr, e->d_cring,
                            e->rc, d_ptab, ctx.pstride, d_in1, d_in2, d_outL, d_outR, T, (int64_t)ctx.t0, post_first, post_count,
                            ctx.wet_ready ? INT64_MAX : (int64_t)ctx.win0, (int64_t)ctx.predelay, (int64_t)e->cfg.n_ref, (int)e->cfg.compat,
-                           td, e->pm, make_retired(e), publish ? e->hd_flag : (unsigned*)nullptr,
+                           td, e->pm, make_retired(e), publish ? e->h_flag.dev() : (unsigned*)nullptr,
                            publish ? ++e->flag_seq : 0u, e->d_done_ctr, lin_slice ? (int64_t)lin_count * MC_B : (int64_t)T * MC_B,
                            lin_slice ? lin_first : 0);
         HIP_TRY(hipGetLastError());
@@ -2158,11 +2118,11 @@ int stamped_sweep(mc_engine* e, int blocks, Launch&& launch) {
         }
         e->kev_blocks[e->kev_n] = (uint32_t)blocks;
         e->kev_stamped[e->kev_n] = true;
-        HIP_TRY(hipEventRecord(e->kev[e->kev_n][0], e->stream));
+        HIP_TRY(hipEventRecord(e->kt->ev[e->kev_n][0], e->stream));
     }
-    const int swept = launch(timed ? e->d_stamps + (size_t)2 * MC_STAMP_WGS * e->kev_n : nullptr);
+    const int swept = launch(timed ? e->kt->d_stamps + (size_t)2 * MC_STAMP_WGS * e->kev_n : nullptr);
     if (timed) {
-        HIP_TRY(hipEventRecord(e->kev[e->kev_n][1], e->stream));
+        HIP_TRY(hipEventRecord(e->kt->ev[e->kev_n][1], e->stream));
         e->kev_n++;
         e->ks.resident = 0;
         e->ks.partitions = (uint32_t)swept;
@@ -2217,7 +2177,7 @@ int wait_period(mc_engine* e, unsigned seq) {
         HIP_TRY(hipEventSynchronize(e->ev_tail));
         return MC_OK;
     }
-    auto published = [&] { return __atomic_load_n(e->h_flag, __ATOMIC_ACQUIRE) == seq; };
+    auto published = [&] { return __atomic_load_n(e->h_flag.get(), __ATOMIC_ACQUIRE) == seq; };
     return spin_for_period(e, seq, published, published);
 }
 
@@ -2265,11 +2225,11 @@ template <int PM, bool SELF_DROP>
 void launch_tailp(mc_engine* e, const Staged& st, const VoiceSet& vset, int nsum, uint64_t blk, unsigned seq, const TailDrop& tdp,
                   const unsigned long long* bell, const float* drop) {
     const size_t cap = (size_t)e->Thost * MC_B;
-    const float *pin1 = e->bar_io ? e->d_bar + 16 : e->hd_io + 0 * cap, *pin2 = e->bar_io ? e->d_bar + 16 + 4 * MC_B : e->hd_io + 1 * cap;
+    const float *pin1 = e->bar_io ? e->d_bar + 16 : e->h_io.dev() + 0 * cap, *pin2 = e->bar_io ? e->d_bar + 16 + 4 * MC_B : e->h_io.dev() + 1 * cap;
     hipLaunchKernelGGL((k_tailp<PM, SELF_DROP>), dim3(1), dim3(256), 0, e->stream, pin1, pin2, vset, e->Pstride, e->d_fdl, e->d_slotgain,
                        e->ring, (int)(blk & (uint64_t)(e->ring - 1)), e->d_part, nsum, st.d_ptab, e->d_seg, e->sr, e->d_wet, e->wr, e->d_cring,
                        e->rc, st.ctx.vs, 1.0 / (double)e->cfg.n_ref, (int)e->cfg.compat, (int64_t)blk, (int64_t)st.ctx.predelay,
-                       (int64_t)e->cfg.n_ref, e->hd_io + 2 * cap, e->hd_io + 3 * cap, e->d_tw, tdp, e->d_fdl16, e->hd_flag, seq,
+                       (int64_t)e->cfg.n_ref, e->h_io.dev() + 2 * cap, e->h_io.dev() + 3 * cap, e->d_tw, tdp, e->d_fdl16, e->h_flag.dev(), seq,
                        make_retired(e), bell, e->hd_exited, e->park_ticks, drop, nullptr, nullptr);
 }
 
@@ -2360,8 +2320,8 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
     auto tail_args = [&](const Staged& st, const Plan& pl, uint64_t blk, unsigned seq, bool parked) {
         TailArgs A;
         std::memset(&A, 0, sizeof(A));
-        A.in1 = e->bar_io ? e->d_bar + 16 : e->hd_io + 0 * cap;
-        A.in2 = e->bar_io ? e->d_bar + 16 + 4 * MC_B : e->hd_io + 1 * cap;
+        A.in1 = e->bar_io ? e->d_bar + 16 : e->h_io.dev() + 0 * cap;
+        A.in2 = e->bar_io ? e->d_bar + 16 + 4 * MC_B : e->h_io.dev() + 1 * cap;
         A.vset = pl.vset;
         A.pstride_ir = e->Pstride;
         A.fdl = e->d_fdl;
@@ -2384,8 +2344,8 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
         A.tabs0 = (int64_t)blk;
         A.predelay = (int64_t)st.ctx.predelay;
         A.n_ref = (int64_t)e->cfg.n_ref;
-        A.outL = e->hd_io + 2 * cap;
-        A.outR = e->hd_io + 3 * cap;
+        A.outL = e->h_io.dev() + 2 * cap;
+        A.outR = e->h_io.dev() + 3 * cap;
         A.g_tw = e->d_tw;
         {  // (Q8 regime: the last partitions partition-major and the buffer of the cut terms)
             const int r = prepare_drop_fft(e, st.ctx.vir, st.ctx.predelay);
@@ -2393,10 +2353,10 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
         }
         A.td = make_taildrop(e, st.ctx.vir, st.ctx.predelay);
         A.fdl16 = e->d_fdl16;
-        A.done_flag = e->hd_flag;
+        A.done_flag = e->h_flag.dev();
         A.seq = seq;
         A.ret = make_retired(e);
-        A.bell = parked ? (e->bar_io ? reinterpret_cast<unsigned long long*>(e->d_bar) : e->hd_bell) : nullptr;
+        A.bell = parked ? (e->bar_io ? reinterpret_cast<unsigned long long*>(e->d_bar.get()) : e->hd_bell) : nullptr;
         A.exited = e->hd_exited;
         A.park_ticks = e->park_ticks;
         {
@@ -2410,8 +2370,8 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
         }
         A.formcount = e->d_tailform;
         A.form = e->tail_form;
-        A.in_gran = e->tio ? reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(e->d_bar) + 16384) : nullptr;
-        A.out_gran = e->tio ? e->hd_gran : nullptr;
+        A.in_gran = e->tio ? reinterpret_cast<const unsigned long long*>(reinterpret_cast<const char*>(e->d_bar.get()) + 16384) : nullptr;
+        A.out_gran = e->tio ? e->h_gran.dev() : nullptr;
         return A;
     };
 
@@ -2425,7 +2385,7 @@ int process_one(mc_engine* e, const float* in1, const float* in2, float* outL, f
         if (e->tio) {
             // tagged input: the period as granules {sample, sequence number} straight into device memory - every lane of the
             // parked tail is polling its own two; no doorbell, no second round trip for the data it would announce
-            volatile unsigned long long* g = reinterpret_cast<volatile unsigned long long*>(reinterpret_cast<char*>(e->d_bar) + 16384);
+            volatile unsigned long long* g = reinterpret_cast<volatile unsigned long long*>(reinterpret_cast<char*>(e->d_bar.get()) + 16384);
             const unsigned long long tag = (unsigned long long)my_seq << 32;
             for (int i = 0; i < MC_B; i++) {
                 uint32_t a, b;
@@ -2657,32 +2617,27 @@ int process_host_staged(mc_engine* e, const float* in1, const float* in2, float*
 // (H2D stream) runs under chunk k - 1's kernels (engine stream), over three staging sets.  Returns when the last output
 // byte is in outL / outR.
 int process_host_pinned(mc_engine* e, const float* in1, const float* in2, float* outL, float* outR, int T) {
-    if (!e->Tdev) {
+    if (!e->pinned) {
         // whole chunks of the second-level transform where it applies, and LONG ones: the copies set the pace, and the
         // link carries 45-48 GB/s each way at once in copies of >= 33 MB but only 26 GB/s in 6.6 MB ones
         // (scripts/pcie_probe.py; 53-57 GB/s one way at a time)
         int tdev = (int)std::min<uint64_t>(mc_preferred_batch(e, std::min(e->Tmax, 32768)), (uint64_t)e->Tmax);
         tdev = std::max(tdev / e->pm * e->pm, e->pm);
-        for (int b = 0; b < 3; b++)
-            for (int i = 0; i < 2; i++) HIP_TRY(hipMalloc(&e->d_pio[b][i], sizeof(float) * (size_t)tdev * MC_B));
-        HIP_TRY(hipStreamCreateWithFlags(&e->h2d_stream, hipStreamNonBlocking));
-        for (int b = 0; b < 3; b++) {
-            HIP_TRY(hipEventCreateWithFlags(&e->ev_h2d[b], hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&e->ev_comp[b], hipEventDisableTiming));
-        }
+        HIP_TRY(make_group(e->pinned, (size_t)tdev * MC_B));
         e->Tdev = tdev;
     }
+    PinnedStaging& ps = *e->pinned;
     int k = 0;
     for (int o = 0; o < T; o += e->Tdev, k++) {
         const int n = std::min(e->Tdev, T - o), b = k % 3;
         const size_t bytes = (size_t)n * MC_B * sizeof(float), off = (size_t)o * MC_B;
-        float* const* d = e->d_pio[b];
+        const DevArray<float>* d = ps.d_in[b];
         // the staging set is free once chunk k - 3 has been computed (inputs) and copied out (outputs)
-        if (k >= 3) HIP_TRY(hipStreamWaitEvent(e->h2d_stream, e->ev_comp[b], 0));
-        HIP_TRY(hipMemcpyAsync(d[0], in1 + off, bytes, hipMemcpyHostToDevice, e->h2d_stream));
-        HIP_TRY(hipMemcpyAsync(d[1], in2 + off, bytes, hipMemcpyHostToDevice, e->h2d_stream));
-        HIP_TRY(hipEventRecord(e->ev_h2d[b], e->h2d_stream));
-        HIP_TRY(hipStreamWaitEvent(e->stream, e->ev_h2d[b], 0));
+        if (k >= 3) HIP_TRY(hipStreamWaitEvent(ps.h2d, ps.ev_comp[b], 0));
+        HIP_TRY(hipMemcpyAsync(d[0], in1 + off, bytes, hipMemcpyHostToDevice, ps.h2d));
+        HIP_TRY(hipMemcpyAsync(d[1], in2 + off, bytes, hipMemcpyHostToDevice, ps.h2d));
+        HIP_TRY(hipEventRecord(ps.ev_h2d[b], ps.h2d));
+        HIP_TRY(hipStreamWaitEvent(e->stream, ps.ev_h2d[b], 0));
         // the kernels that finish the output store it straight into the caller's pinned buffers (posted writes over the
         // link): no copy-out, no second copy direction to take turns with the copy-in
         float *hl = nullptr, *hr = nullptr;
@@ -2697,7 +2652,7 @@ int process_host_pinned(mc_engine* e, const float* in1, const float* in2, float*
         rc = run_back(e, d[0], d[1], nullptr, hl, hr, n);
         if (!rc) rc = fence_post(e);
         if (rc) return rc;
-        HIP_TRY(hipEventRecord(e->ev_comp[b], e->stream));
+        HIP_TRY(hipEventRecord(ps.ev_comp[b], e->stream));
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     return MC_OK;
@@ -2726,8 +2681,8 @@ int process_period(mc_engine* e, const float* in1, const float* in2, float* outL
     period_to_mapped(e, in1, in2, T);
     const bool was_piped = e->pipelined;
     e->pipelined = false;  // a period is finished inside this call
-    int rc = run_front(e, e->hd_io + 0 * cap, e->hd_io + 1 * cap, T, nullptr, 0, T);
-    if (!rc) rc = run_back(e, e->hd_io + 0 * cap, e->hd_io + 1 * cap, nullptr, e->hd_io + 2 * cap, e->hd_io + 3 * cap, T, true);
+    int rc = run_front(e, e->h_io.dev() + 0 * cap, e->h_io.dev() + 1 * cap, T, nullptr, 0, T);
+    if (!rc) rc = run_back(e, e->h_io.dev() + 0 * cap, e->h_io.dev() + 1 * cap, nullptr, e->h_io.dev() + 2 * cap, e->h_io.dev() + 3 * cap, T, true);
     e->pipelined = was_piped;
     if (rc) return rc;
     if (!e->spin_wait) HIP_TRY(hipEventRecord(e->ev_tail, e->stream));
@@ -2797,7 +2752,7 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
     };
     int prep_rc = MC_OK;  // first failure of prepare_drop_fft inside launch_tail (checked behind every call)
     auto launch_tail = [&](const Staged& st, const PPlan& pl, uint64_t blk, unsigned seq, bool parked) {
-        const unsigned long long* bell = parked ? (e->bar_io ? reinterpret_cast<unsigned long long*>(e->d_bar) : e->hd_bell) : nullptr;
+        const unsigned long long* bell = parked ? (e->bar_io ? reinterpret_cast<unsigned long long*>(e->d_bar.get()) : e->hd_bell) : nullptr;
         {
             const int r = prepare_drop_fft(e, st.ctx.vir, st.ctx.predelay);
             if (r != MC_OK && prep_rc == MC_OK) prep_rc = r;
@@ -2904,6 +2859,151 @@ int process_period_fused(mc_engine* e, const float* in1, const float* in2, float
 
 #include "singlefft_host.hip.h"
 
+namespace {
+
+// The mapped I/O buffer of the period calls (4 * Thost blocks), the mapped line of their flags, and the BAR page where the CPU can
+// write device memory (see mc_engine::d_bar)
+int create_period_io(mc_engine* e) {
+    HIP_TRY(e->h_io.alloc(4 * (size_t)e->Thost * MC_B, hipHostMallocMapped));
+    HIP_TRY(e->h_flag.alloc(64, hipHostMallocMapped));  // completion word, doorbell, "gave up" word: a line each
+    std::memset(e->h_flag, 0, 256);
+    if (std::getenv("MCCONV_NO_SPIN")) e->spin_wait = false;
+    int large_bar = 0;
+    const char* bi = std::getenv("MCCONV_BAR_IO");
+    if ((!bi || std::atoi(bi) != 0) && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, e->device) == hipSuccess && large_bar &&
+        e->d_bar.alloc_finegrained(8192) == hipSuccess) {
+        HIP_TRY(hipMemset(e->d_bar, 0, 32768));
+        e->bar_io = true;
+    } else {
+        (void)hipGetLastError();
+    }
+    return MC_OK;
+}
+
+int create_engine(mc_engine* e) {
+    const mc_config* cfg = &e->cfg;
+    e->ph.update([](mc_cc_value (&cc)[2]) {
+        mc_default_params(&cc[0]);
+        mc_default_params(&cc[1]);
+    });
+    std::memset(&e->ks, 0, sizeof(e->ks));
+    e->Tmax = (int)cfg->max_batch;
+    e->Tcap = std::max(e->Tmax, 256);
+    e->Pcap = cfg->max_partitions ? (int)cfg->max_partitions : (int)((cfg->n_ref - 1024 + MC_B - 1) / MC_B);
+    e->Pstride = (int)next_pow2((uint64_t)round_up(e->Pcap, 16));
+    e->ring = (int)next_pow2((uint64_t)e->Pstride + (uint64_t)e->Tcap + 64);  // + reach-back of a block slice (<= 33)
+    e->sr = (int)next_pow2((uint64_t)e->Tcap + 4);  // power of two: ring indices are masks in the kernels; a slice + reach-back <= Tmax
+    e->wr = (int)next_pow2((uint64_t)MC_MAX_PREDELAY + (uint64_t)e->Tmax * MC_B + 2 * MC_B);
+    e->pipelined = cfg->pipeline != 0 && cfg->precision == 0;
+    // (pipelined: the forward stage of batch k + 1 writes histories while the post stage of batch k still reads them)
+    e->rc = (int)next_pow2(cfg->n_ref / MC_B + (uint64_t)e->Tmax * (e->pipelined ? 2 : 1) + 64);
+    e->stream_threshold = cfg->stream_threshold ? (int)cfg->stream_threshold : 48;  // measured crossover (scripts/sweep_T.sh)
+    e->half = cfg->precision == 1;
+    if (e->half) e->stream_threshold = e->Tmax + 1;  // the fp16 MAC is the streaming sweep
+    // (at least 8 blocks: the fast-FIR form sends the last 2^levels blocks of a batch through the streaming kernel)
+    e->Tstream = std::min(e->half ? e->Tmax : e->Tcap, std::max(8, e->stream_threshold - 1));
+
+    if (const char* v = std::getenv("MCCONV_TD_FFT")) e->td_fft = std::atoi(v) != 0;
+    HIP_TRY(e->own_stream.create(hipStreamNonBlocking));
+    e->stream = e->own_stream;
+    if (e->cfg.form == 1) {  // the reference's own shape: none of the partitioned engine's state
+        HIP_TRY(e->d_tw.alloc(FFT_N));
+        {
+            std::vector<float2> tw;
+            host_twiddles(tw);
+            HIP_TRY(hipMemcpy(e->d_tw, tw.data(), sizeof(float2) * FFT_N, hipMemcpyHostToDevice));
+        }
+        e->Thost = 4;  // the mapped buffer holds one period
+        const int rc = create_period_io(e);
+        return rc ? rc : sf_create(e);
+    }
+    HIP_TRY(e->d_fdl.alloc((size_t)MC_NB * e->ring));
+    if (e->half) HIP_TRY(e->d_fdl16.alloc((size_t)MC_NB * e->ring));
+    HIP_TRY(e->d_slotgain.alloc((size_t)MC_MAXV * e->ring));
+    // >= 8 planes of 256 blocks; the fast-FIR form writes three half-rate sequences (1.5 x the blocks, + a tile each)
+    HIP_TRY(e->d_Ybuf[0].alloc((size_t)MC_NB * y_capacity(e)));
+    if (!e->half) HIP_TRY(e->d_Ycbuf[0].alloc((size_t)MC_NB * e->Tcap));
+    HIP_TRY(e->d_tailbuf[0].alloc((size_t)8 * MC_NB * kNchunk * MC_MAXV));
+    e->d_Y = e->d_Ybuf[0];
+    e->d_Yc = e->d_Ycbuf[0];
+    e->d_tail = e->d_tailbuf[0];
+    if (e->pipelined) {
+        HIP_TRY(e->post_stream.create(hipStreamNonBlocking));
+        for (int i = 0; i < 2; i++) {
+            HIP_TRY(e->ev_mac[i][0].create(hipEventDisableTiming));
+            HIP_TRY(e->ev_mac[i][1].create(hipEventDisableTiming));
+            HIP_TRY(e->ev_corr[i].create(hipEventDisableTiming));
+            HIP_TRY(e->ev_post[i].create(hipEventDisableTiming));
+        }
+        HIP_TRY(e->d_Ybuf[1].alloc((size_t)MC_NB * y_capacity(e)));
+        HIP_TRY(e->d_Ycbuf[1].alloc((size_t)MC_NB * e->Tcap));
+        HIP_TRY(e->d_tailbuf[1].alloc((size_t)8 * MC_NB * kNchunk * MC_MAXV));
+    }
+    HIP_TRY(e->d_partbuf[0].alloc((size_t)e->Tstream * MC_NB * kNchunk * MC_MAXV));
+    e->d_part = e->d_partbuf[0];
+    if (cfg->pipeline != 0 && cfg->precision == 0)
+        HIP_TRY(e->d_partbuf[1].alloc((size_t)e->Tstream * MC_NB * kNchunk * MC_MAXV));
+    HIP_TRY(e->d_sums.alloc((size_t)e->Tmax * kPipe));
+    HIP_TRY(e->d_seg.alloc((size_t)e->sr * 2 * FFT_N));
+    HIP_TRY(e->d_wet.alloc(2 * (size_t)e->wr));
+    HIP_TRY(e->d_cring.alloc(4 * (size_t)e->rc));
+    HIP_TRY(e->d_wring.alloc(4 * (size_t)e->rc));
+    HIP_TRY(e->d_ctot.alloc(4 * (size_t)((e->Tmax + 255) / 256 + 1)));
+    HIP_TRY(e->d_cflag.alloc((size_t)((e->Tmax + 255) / 256 + 2)));
+    HIP_TRY(hipMemset(e->d_cflag, 0, sizeof(unsigned) * e->d_cflag.size()));
+    e->d_cticket = e->d_cflag + e->d_cflag.size() - 1;
+    e->rr = (int)next_pow2(cfg->n_ref);
+    HIP_TRY(e->d_res_mac.alloc(2 * (size_t)e->rr));
+    HIP_TRY(e->d_res_fix.alloc(2 * (size_t)e->rr));
+    e->xr = (int)next_pow2(cfg->n_ref + (uint64_t)e->Tmax * MC_B * (e->pipelined ? 2 : 1) + MC_MAX_PREDELAY + 1024);
+    HIP_TRY(e->d_xhist.alloc(2 * (size_t)e->xr));
+    HIP_TRY(e->d_gring.alloc((size_t)MC_MAXV * e->rc));
+    HIP_TRY(e->d_ptab.alloc((size_t)e->Tmax * kPipe));
+    HIP_TRY(e->d_tw.alloc(FFT_N));
+    e->Thost = std::min(e->Tmax, 16384);  // host-buffer calls with pageable buffers stage through pinned memory in chunks of this
+    for (int i = 0; i < 4; i++) HIP_TRY(e->d_io[i].alloc((size_t)e->Thost * MC_B));
+    HIP_TRY(e->d_tailform.alloc(2));
+    HIP_TRY(hipMemset(e->d_tailform, 0, 2 * sizeof(unsigned)));
+    if (const char* f = std::getenv("MCCONV_TAIL_FORM")) e->tail_form = !std::strcmp(f, "td") ? 1 : !std::strcmp(f, "fd") ? 2 : 0;
+    {
+        const int rc = create_period_io(e);
+        if (rc) return rc;
+    }
+    e->h_bell = reinterpret_cast<unsigned long long*>(e->h_flag + 16);
+    e->hd_bell = reinterpret_cast<unsigned long long*>(e->h_flag.dev() + 16);
+    e->h_exited = e->h_flag + 32;
+    e->hd_exited = e->h_flag.dev() + 32;
+    if (std::getenv("MCCONV_NO_PARK")) e->park = false;
+    if (const char* pm = std::getenv("MCCONV_PARK_MS")) e->park_ticks = (unsigned long long)std::max(1, std::atoi(pm)) * 100000ull;
+    HIP_TRY(e->d_done_ctr.alloc(1));
+    HIP_TRY(hipMemset(e->d_done_ctr, 0, sizeof(unsigned)));
+    if (e->bar_io && e->spin_wait) {
+        HIP_TRY(e->h_gran.alloc(2 * MC_B, hipHostMallocMapped));
+        std::memset(e->h_gran, 0, sizeof(unsigned long long) * 2 * MC_B);
+        e->tio = true;
+    }
+    for (int i = 0; i < kStageBufs; i++) {
+        HIP_TRY(e->h_ptab[i].alloc((size_t)e->Tmax, hipHostMallocDefault));
+        HIP_TRY(e->ptab_ev[i].create(hipEventDisableTiming));
+    }
+    HIP_TRY(e->ev_tail.create(hipEventDisableTiming));
+    for (int i = 0; i < 2; i++) HIP_TRY(e->d_part_jack[i].alloc((size_t)MC_NB * kNchunk * MC_MAXV));
+    for (int i = 0; i < 2; i++) HIP_TRY(e->d_drop[i].alloc(2 * 4 * MC_B));
+    if (const char* f2 = std::getenv("MCCONV_FFT2")) e->fft2 = std::atoi(f2) != 0;
+    if (const char* g2 = std::getenv("MCCONV_FFT2_FUSED")) e->fft2_fused = std::atoi(g2) != 0;
+    if (const char* tm = std::getenv("MCCONV_FFT2_WORK")) e->fft2_work = std::max<int64_t>(1, std::atoll(tm));
+    if (const char* os = std::getenv("MCCONV_OS")) e->os_on = std::atoi(os) != 0;
+    if (const char* os = std::getenv("MCCONV_OS_MIN")) e->os_min_blocks = std::max(1, std::atoi(os));
+    if (const char* fl = std::getenv("MCCONV_FFA_LEVELS")) e->ffa_levels = std::max(0, std::min(3, std::atoi(fl)));
+    {
+        std::vector<float2> tw;
+        host_twiddles(tw);
+        HIP_TRY(hipMemcpy(e->d_tw, tw.data(), sizeof(float2) * FFT_N, hipMemcpyHostToDevice));
+    }
+    return zero_state(e);
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -2947,206 +3047,29 @@ int mc_create(const mc_config* cfg, mc_engine** out) {
     if (dev < 0) HIP_TRY(hipGetDevice(&dev));
     if (dev >= ndev) return fail(MC_ERR_ARG, "device %d out of range (%d devices)", dev, ndev);
     HIP_TRY(hipSetDevice(dev));
+    const uint32_t period = cfg->period ? cfg->period : MC_BLOCK;
+    if (period != 256 && period != 512 && period != 1024) return fail(MC_ERR_ARG, "period must be 256, 512 or 1024 frames");
+    if (cfg->max_batch % (period / MC_BLOCK)) return fail(MC_ERR_ARG, "max_batch must be a multiple of period / 256");
+    uint32_t form = cfg->form;
+    {
+        const char* fm = std::getenv("MCCONV_FORM");  // lets an unmodified host pick the form: "single" / "partitioned"
+        if (fm && !std::strcmp(fm, "single")) form = 1;
+        else if (fm && !std::strcmp(fm, "partitioned")) form = 0;
+    }
+    if (form > 1) return fail(MC_ERR_ARG, "mc_config.form must be 0 (partitioned) or 1 (single transform)");
 
+    // everything the engine holds is an owner (owned.h): whatever create_engine had made when it failed goes with the engine
     mc_engine* e = new (std::nothrow) mc_engine();
     if (!e) return fail(MC_ERR_NOMEM, "out of host memory");
     e->cfg = *cfg;
+    e->cfg.form = form;
     e->device = dev;
-    e->ph.update([](mc_cc_value (&cc)[2]) {
-        mc_default_params(&cc[0]);
-        mc_default_params(&cc[1]);
-    });
-    std::memset(&e->ks, 0, sizeof(e->ks));
-    e->Tmax = (int)cfg->max_batch;
-    e->Tcap = std::max(e->Tmax, 256);
-    e->Pcap = cfg->max_partitions ? (int)cfg->max_partitions : (int)((cfg->n_ref - 1024 + MC_B - 1) / MC_B);
-    e->Pstride = (int)next_pow2((uint64_t)round_up(e->Pcap, 16));
-    e->ring = (int)next_pow2((uint64_t)e->Pstride + (uint64_t)e->Tcap + 64);  // + reach-back of a block slice (<= 33)
-    e->sr = (int)next_pow2((uint64_t)e->Tcap + 4);  // power of two: ring indices are masks in the kernels; a slice + reach-back <= Tmax
-    e->wr = (int)next_pow2((uint64_t)MC_MAX_PREDELAY + (uint64_t)e->Tmax * MC_B + 2 * MC_B);
-    e->pipelined = cfg->pipeline != 0 && cfg->precision == 0;
-    // (pipelined: the forward stage of batch k + 1 writes histories while the post stage of batch k still reads them)
-    e->rc = (int)next_pow2(cfg->n_ref / MC_B + (uint64_t)e->Tmax * (e->pipelined ? 2 : 1) + 64);
-    e->stream_threshold = cfg->stream_threshold ? (int)cfg->stream_threshold : 48;  // measured crossover (scripts/sweep_T.sh)
-    {
-        const uint32_t period = cfg->period ? cfg->period : MC_BLOCK;
-        if (period != 256 && period != 512 && period != 1024) {
-            delete e;
-            return fail(MC_ERR_ARG, "period must be 256, 512 or 1024 frames");
-        }
-        e->pm = (int)(period / MC_BLOCK);
-        if (e->Tmax % e->pm) {
-            delete e;
-            return fail(MC_ERR_ARG, "max_batch must be a multiple of period / 256");
-        }
-    }
-    e->half = cfg->precision == 1;
-    if (e->half) e->stream_threshold = e->Tmax + 1;  // the fp16 MAC is the streaming sweep
-    // (at least 8 blocks: the fast-FIR form sends the last 2^levels blocks of a batch through the streaming kernel)
-    e->Tstream = std::min(e->half ? e->Tmax : e->Tcap, std::max(8, e->stream_threshold - 1));
-
-#define ENG_TRY(expr)                                                                                     \
-    do {                                                                                                  \
-        hipError_t _e = (expr);                                                                           \
-        if (_e != hipSuccess) {                                                                           \
-            int _rc = fail(MC_ERR_HIP, "%s -> %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-            mc_destroy(e);                                                                                \
-            return _rc;                                                                                   \
-        }                                                                                                 \
-    } while (0)
-
-    if (const char* v = std::getenv("MCCONV_TD_FFT")) e->td_fft = std::atoi(v) != 0;
-    ENG_TRY(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
-    e->stream = e->own_stream;
-    {
-        const char* fm = std::getenv("MCCONV_FORM");  // lets an unmodified host pick the form: "single" / "partitioned"
-        if (fm && !std::strcmp(fm, "single")) e->cfg.form = 1;
-        else if (fm && !std::strcmp(fm, "partitioned")) e->cfg.form = 0;
-    }
-    if (e->cfg.form > 1) {
+    e->pm = (int)(period / MC_BLOCK);
+    const int rc = create_engine(e);
+    if (rc) {
         mc_destroy(e);
-        return fail(MC_ERR_ARG, "mc_config.form must be 0 (partitioned) or 1 (single transform)");
+        return rc;
     }
-    if (e->cfg.form == 1) {  // the reference's own shape: none of the partitioned engine's state
-        ENG_TRY(hipMalloc(&e->d_tw, sizeof(float2) * FFT_N));
-        {
-            std::vector<float2> tw;
-            host_twiddles(tw);
-            ENG_TRY(hipMemcpy(e->d_tw, tw.data(), sizeof(float2) * FFT_N, hipMemcpyHostToDevice));
-        }
-        e->Thost = 4;  // the mapped buffer holds one period
-        ENG_TRY(hipHostMalloc(&e->h_io, sizeof(float) * 4 * (size_t)e->Thost * MC_B, hipHostMallocMapped));
-        ENG_TRY(hipHostGetDevicePointer((void**)&e->hd_io, e->h_io, 0));
-        ENG_TRY(hipHostMalloc(&e->h_flag, 256, hipHostMallocMapped));  // completion word of mc_process
-        ENG_TRY(hipHostGetDevicePointer((void**)&e->hd_flag, e->h_flag, 0));
-        std::memset(e->h_flag, 0, 256);
-        if (std::getenv("MCCONV_NO_SPIN")) e->spin_wait = false;
-        {  // the period through the BAR where the CPU can write device memory (see mc_engine::d_bar)
-            int large_bar = 0;
-            const char* bi = std::getenv("MCCONV_BAR_IO");
-            if ((!bi || std::atoi(bi) != 0) && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev) == hipSuccess && large_bar &&
-                hipExtMallocWithFlags((void**)&e->d_bar, 32768, hipDeviceMallocFinegrained) == hipSuccess) {
-                ENG_TRY(hipMemset(e->d_bar, 0, 32768));
-                e->bar_io = true;
-            } else {
-                (void)hipGetLastError();
-                e->d_bar = nullptr;
-            }
-        }
-        int rc = sf_create(e);
-        if (rc) {
-            mc_destroy(e);
-            return rc;
-        }
-        *out = e;
-        return MC_OK;
-    }
-    ENG_TRY(hipMalloc(&e->d_fdl, sizeof(float4) * (size_t)MC_NB * e->ring));
-    if (e->half) ENG_TRY(hipMalloc(&e->d_fdl16, sizeof(uint2) * (size_t)MC_NB * e->ring));
-    ENG_TRY(hipMalloc(&e->d_slotgain, sizeof(float4) * (size_t)MC_MAXV * e->ring));
-    // >= 8 planes of 256 blocks; the fast-FIR form writes three half-rate sequences (1.5 x the blocks, + a tile each)
-    ENG_TRY(hipMalloc(&e->d_Y, sizeof(float4) * (size_t)MC_NB * y_capacity(e)));
-    if (!e->half) ENG_TRY(hipMalloc(&e->d_Yc, sizeof(float4) * (size_t)MC_NB * e->Tcap));
-    ENG_TRY(hipMalloc(&e->d_tail, sizeof(float4) * (size_t)8 * MC_NB * kNchunk * MC_MAXV));
-    e->d_Ybuf[0] = e->d_Y;
-    e->d_Ycbuf[0] = e->d_Yc;
-    e->d_tailbuf[0] = e->d_tail;
-    if (e->pipelined) {
-        ENG_TRY(hipStreamCreateWithFlags(&e->post_stream, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) {
-            ENG_TRY(hipEventCreateWithFlags(&e->ev_mac[i][0], hipEventDisableTiming));
-            ENG_TRY(hipEventCreateWithFlags(&e->ev_mac[i][1], hipEventDisableTiming));
-            ENG_TRY(hipEventCreateWithFlags(&e->ev_corr[i], hipEventDisableTiming));
-            ENG_TRY(hipEventCreateWithFlags(&e->ev_post[i], hipEventDisableTiming));
-        }
-        ENG_TRY(hipMalloc(&e->d_Ybuf[1], sizeof(float4) * (size_t)MC_NB * y_capacity(e)));
-        ENG_TRY(hipMalloc(&e->d_Ycbuf[1], sizeof(float4) * (size_t)MC_NB * e->Tcap));
-        ENG_TRY(hipMalloc(&e->d_tailbuf[1], sizeof(float4) * (size_t)8 * MC_NB * kNchunk * MC_MAXV));
-    }
-    ENG_TRY(hipMalloc(&e->d_part, sizeof(float4) * (size_t)e->Tstream * MC_NB * kNchunk * MC_MAXV));
-    e->d_partbuf[0] = e->d_part;
-    if (cfg->pipeline != 0 && cfg->precision == 0)
-        ENG_TRY(hipMalloc(&e->d_partbuf[1], sizeof(float4) * (size_t)e->Tstream * MC_NB * kNchunk * MC_MAXV));
-    ENG_TRY(hipMalloc(&e->d_sums, sizeof(float4) * (size_t)e->Tmax * kPipe));
-    ENG_TRY(hipMalloc(&e->d_seg, sizeof(float) * (size_t)e->sr * 2 * FFT_N));
-    ENG_TRY(hipMalloc(&e->d_wet, sizeof(float) * 2 * (size_t)e->wr));
-    ENG_TRY(hipMalloc(&e->d_cring, sizeof(double) * 4 * (size_t)e->rc));
-    ENG_TRY(hipMalloc(&e->d_wring, sizeof(double) * 4 * (size_t)e->rc));
-    ENG_TRY(hipMalloc(&e->d_ctot, sizeof(double) * 4 * (size_t)((e->Tmax + 255) / 256 + 1)));
-    ENG_TRY(hipMalloc(&e->d_cflag, sizeof(unsigned) * (size_t)((e->Tmax + 255) / 256 + 2)));
-    ENG_TRY(hipMemset(e->d_cflag, 0, sizeof(unsigned) * (size_t)((e->Tmax + 255) / 256 + 2)));
-    e->d_cticket = e->d_cflag + (e->Tmax + 255) / 256 + 1;
-    e->rr = (int)next_pow2(cfg->n_ref);
-    ENG_TRY(hipMalloc(&e->d_res_mac, sizeof(float) * 2 * (size_t)e->rr));
-    ENG_TRY(hipMalloc(&e->d_res_fix, sizeof(float) * 2 * (size_t)e->rr));
-    e->xr = (int)next_pow2(cfg->n_ref + (uint64_t)e->Tmax * MC_B * (e->pipelined ? 2 : 1) + MC_MAX_PREDELAY + 1024);
-    ENG_TRY(hipMalloc(&e->d_xhist, sizeof(float) * 2 * (size_t)e->xr));
-    ENG_TRY(hipMalloc(&e->d_gring, sizeof(float4) * (size_t)MC_MAXV * e->rc));
-    ENG_TRY(hipMalloc(&e->d_ptab, sizeof(BlockParams) * (size_t)e->Tmax * kPipe));
-    ENG_TRY(hipMalloc(&e->d_tw, sizeof(float2) * FFT_N));
-    e->Thost = std::min(e->Tmax, 16384);  // host-buffer calls with pageable buffers stage through pinned memory in chunks of this
-    for (int i = 0; i < 4; i++) ENG_TRY(hipMalloc(&e->d_io[i], sizeof(float) * (size_t)e->Thost * MC_B));
-    ENG_TRY(hipHostMalloc(&e->h_io, sizeof(float) * 4 * (size_t)e->Thost * MC_B, hipHostMallocMapped));
-    ENG_TRY(hipHostGetDevicePointer((void**)&e->hd_io, e->h_io, 0));
-    ENG_TRY(hipMalloc(&e->d_tailform, 2 * sizeof(unsigned)));
-    ENG_TRY(hipMemset(e->d_tailform, 0, 2 * sizeof(unsigned)));
-    if (const char* f = std::getenv("MCCONV_TAIL_FORM")) e->tail_form = !std::strcmp(f, "td") ? 1 : !std::strcmp(f, "fd") ? 2 : 0;
-    ENG_TRY(hipHostMalloc(&e->h_flag, 256, hipHostMallocMapped));  // completion word, doorbell, "gave up" word: a line each
-    ENG_TRY(hipHostGetDevicePointer((void**)&e->hd_flag, e->h_flag, 0));
-    std::memset(e->h_flag, 0, 256);
-    e->h_bell = reinterpret_cast<unsigned long long*>(e->h_flag + 16);
-    e->hd_bell = reinterpret_cast<unsigned long long*>(e->hd_flag + 16);
-    e->h_exited = e->h_flag + 32;
-    e->hd_exited = e->hd_flag + 32;
-    if (std::getenv("MCCONV_NO_PARK")) e->park = false;
-    {
-        int large_bar = 0;
-        const char* bi = std::getenv("MCCONV_BAR_IO");
-        if ((!bi || std::atoi(bi) != 0) && hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, dev) == hipSuccess && large_bar &&
-            hipExtMallocWithFlags((void**)&e->d_bar, 32768, hipDeviceMallocFinegrained) == hipSuccess) {
-            ENG_TRY(hipMemset(e->d_bar, 0, 32768));
-            e->bar_io = true;
-        } else {
-            (void)hipGetLastError();
-            e->d_bar = nullptr;
-        }
-    }
-    if (const char* pm = std::getenv("MCCONV_PARK_MS")) e->park_ticks = (unsigned long long)std::max(1, std::atoi(pm)) * 100000ull;
-    ENG_TRY(hipMalloc(&e->d_done_ctr, sizeof(unsigned)));
-    ENG_TRY(hipMemset(e->d_done_ctr, 0, sizeof(unsigned)));
-    if (std::getenv("MCCONV_NO_SPIN")) e->spin_wait = false;
-    if (e->bar_io && e->spin_wait) {
-        ENG_TRY(hipHostMalloc(&e->h_gran, sizeof(unsigned long long) * 2 * MC_B, hipHostMallocMapped));
-        ENG_TRY(hipHostGetDevicePointer((void**)&e->hd_gran, e->h_gran, 0));
-        std::memset(e->h_gran, 0, sizeof(unsigned long long) * 2 * MC_B);
-        e->tio = true;
-    }
-    for (int i = 0; i < kStageBufs; i++) {
-        ENG_TRY(hipHostMalloc(&e->h_ptab[i], sizeof(BlockParams) * (size_t)e->Tmax, hipHostMallocDefault));
-        ENG_TRY(hipEventCreateWithFlags(&e->ptab_ev[i], hipEventDisableTiming));
-    }
-    ENG_TRY(hipEventCreateWithFlags(&e->ev_tail, hipEventDisableTiming));
-    for (int i = 0; i < 2; i++) ENG_TRY(hipMalloc(&e->d_part_jack[i], sizeof(float4) * (size_t)MC_NB * kNchunk * MC_MAXV));
-    for (int i = 0; i < 2; i++) ENG_TRY(hipMalloc(&e->d_drop[i], sizeof(float) * 2 * 4 * MC_B));
-    if (const char* f2 = std::getenv("MCCONV_FFT2")) e->fft2 = std::atoi(f2) != 0;
-    if (const char* g2 = std::getenv("MCCONV_FFT2_FUSED")) e->fft2_fused = std::atoi(g2) != 0;
-    if (const char* tm = std::getenv("MCCONV_FFT2_WORK")) e->fft2_work = std::max<int64_t>(1, std::atoll(tm));
-    if (const char* os = std::getenv("MCCONV_OS")) e->os_on = std::atoi(os) != 0;
-    if (const char* os = std::getenv("MCCONV_OS_MIN")) e->os_min_blocks = std::max(1, std::atoi(os));
-    if (const char* fl = std::getenv("MCCONV_FFA_LEVELS")) e->ffa_levels = std::max(0, std::min(3, std::atoi(fl)));
-    {
-        std::vector<float2> tw;
-        host_twiddles(tw);
-        ENG_TRY(hipMemcpy(e->d_tw, tw.data(), sizeof(float2) * FFT_N, hipMemcpyHostToDevice));
-    }
-    {
-        int rc = zero_state(e);
-        if (rc) {
-            mc_destroy(e);
-            return rc;
-        }
-    }
-#undef ENG_TRY
     *out = e;
     return MC_OK;
 }
@@ -3162,97 +3085,12 @@ void mc_destroy(mc_engine* e) {
 #endif
     (void)hipSetDevice(e->device);
     unpark(e);
+    // nothing the engine issued is still running when its owners (owned.h) let go
     if (e->stream) (void)hipStreamSynchronize(e->stream);
-    sf_free(e);
-    for (int i = 0; i < kMaxIrs + kMixIrs; i++)
-        if (e->irs[i].d_H) (void)hipFree(e->irs[i].d_H);
-    for (int i = 0; i < kMaxIrs + kMixIrs; i++)
-        for (int l = 0; l < 3; l++)
-            if (e->irs[i].d_Hp[l]) (void)hipFree(e->irs[i].d_Hp[l]);
-    for (int i = 0; i < kMaxIrs + kMixIrs; i++)
-        if (e->irs[i].d_H2) (void)hipFree(e->irs[i].d_H2);
-    for (int i = 0; i < kMaxIrs + kMixIrs; i++)
-        if (e->irs[i].d_G2) (void)hipFree(e->irs[i].d_G2);
-    for (int i = 0; i < kMaxIrs + kMixIrs; i++)
-        if (e->irs[i].d_Htail) (void)hipFree(e->irs[i].d_Htail);
-    for (int i = 0; i < kMaxIrs + kMixIrs; i++)
-        if (e->irs[i].d_h) (void)hipFree(e->irs[i].d_h);
-    for (int i = 0; i < kMaxIrs + kMixIrs; i++)
-        if (e->irs[i].d_H16) (void)hipFree(e->irs[i].d_H16);
-    (void)hipFree(e->d_fdl);
-    (void)hipFree(e->d_slotgain);
-    (void)hipFree(e->d_fdl16);
-    (void)hipFree(e->d_stash);
-    if (e->post_stream) (void)hipStreamSynchronize(e->post_stream);
-    for (int i = 0; i < 2; i++) {
-        (void)hipFree(e->d_Ybuf[i]);
-        (void)hipFree(e->d_Ycbuf[i]);
-        (void)hipFree(e->d_tailbuf[i]);
-        if (e->post_stream) {
-            (void)hipEventDestroy(e->ev_mac[i][0]);
-            (void)hipEventDestroy(e->ev_mac[i][1]);
-            (void)hipEventDestroy(e->ev_corr[i]);
-            (void)hipEventDestroy(e->ev_post[i]);
-        }
-    }
-    if (e->post_stream) (void)hipStreamDestroy(e->post_stream);
-    (void)hipFree(e->d_partbuf[0]);
-    (void)hipFree(e->d_partbuf[1]);
-    (void)hipFree(e->d_sums);
-    (void)hipFree(e->d_seg);
-    (void)hipFree(e->d_wet);
-    (void)hipFree(e->d_cring);
-    (void)hipFree(e->d_wring);
-    (void)hipFree(e->d_ctot);
-    (void)hipFree(e->d_cflag);
-    (void)hipFree(e->d_stamps);
-    (void)hipFree(e->d_done_ctr);
-    (void)hipFree(e->d_res_mac);
-    (void)hipFree(e->d_res_fix);
-    (void)hipFree(e->d_xhist);
-    (void)hipFree(e->d_os_T);
-    (void)hipFree(e->d_os_part);
-    (void)hipFree(e->d_os_SP);
-    (void)hipFree(e->d_os_SP0);
-    (void)hipFree(e->d_os_planes);
-    if (e->os_stream) {
-        (void)hipStreamSynchronize(e->os_stream);
-        for (int i = 0; i < 3; i++) (void)hipEventDestroy(e->os_ev[i]);
-        (void)hipStreamDestroy(e->os_stream);
-    }
-    (void)hipFree(e->d_gring);
-    (void)hipFree(e->d_ptab);
-    (void)hipFree(e->d_tw);
-    for (int i = 0; i < 4; i++) (void)hipFree(e->d_io[i]);
-    for (int b = 0; b < 3; b++) {
-        for (int i = 0; i < 2; i++) (void)hipFree(e->d_pio[b][i]);
-        if (e->ev_h2d[b]) (void)hipEventDestroy(e->ev_h2d[b]);
-        if (e->ev_comp[b]) (void)hipEventDestroy(e->ev_comp[b]);
-    }
-    if (e->h2d_stream) (void)hipStreamDestroy(e->h2d_stream);
-    if (e->d_bar) (void)hipFree(e->d_bar);
-    if (e->h_gran) (void)hipHostFree(e->h_gran);
-    if (e->h_io) (void)hipHostFree(e->h_io);
-    if (e->d_tailform) (void)hipFree(e->d_tailform);
-    if (e->h_flag) (void)hipHostFree(e->h_flag);
-    for (int i = 0; i < kStageBufs; i++) {
-        if (e->h_ptab[i]) {
-            (void)hipHostFree(e->h_ptab[i]);
-            (void)hipEventDestroy(e->ptab_ev[i]);
-        }
-    }
-    if (e->ev_tail) (void)hipEventDestroy(e->ev_tail);
-    (void)hipFree(e->d_part_jack[0]);
-    (void)hipFree(e->d_part_jack[1]);
-    (void)hipFree(e->d_dropbuf);
-    (void)hipFree(e->d_drop[0]);
-    (void)hipFree(e->d_drop[1]);
-    if (e->kev_created)
-        for (int i = 0; i < kEvPool; i++) {
-            (void)hipEventDestroy(e->kev[i][0]);
-            (void)hipEventDestroy(e->kev[i][1]);
-        }
-    if (e->own_stream) (void)hipStreamDestroy(e->own_stream);
+    (void)e->own_stream.sync();
+    (void)e->post_stream.sync();
+    if (e->os_side) (void)e->os_side->stream.sync();
+    if (e->pinned) (void)e->pinned->h2d.sync();
     delete e;
 }
 
@@ -3358,11 +3196,11 @@ int quiesce(mc_engine* e) {
 // temporary buffer freed after the stage, as its weight table is; the tail step turns the conv frames into tail->plan.Fp frames
 // in a buffer of their own, the phase step those into as many frames in another, the filter step those into filter->Fo, the match step those into match->Fo, and the parts step those into parts->Fo.
 int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, ShapedTaps* out) {
-    float2 *d_x = nullptr, *d_rec = nullptr;
-    double* d_u = nullptr;
-    HIP_TRY(hipMalloc(&d_x, sizeof(float2) * conv));
+    DevArray<float2> d_x, d_rec;
+    DevArray<double> d_u;
+    HIP_TRY(d_x.alloc(conv));
     double unused[4];
-    hipError_t er = ld.swp  ? swp_generate(e->stream, *ld.swp, d_x, &d_rec, &d_u)
+    hipError_t er = ld.swp  ? swp_generate(e->stream, *ld.swp, d_x, d_rec, d_u)
                     : ld.syn && ld.room && ld.room->banded ? room_generate_bands(e->stream, *ld.syn, ld.room->bands, d_x, ld.room->kept)
                     : ld.syn && ld.room ? room_generate(e->stream, *ld.syn, ld.room->plan, d_x, ld.room->kept)
                     : ld.syn && ld.plate ? plate_generate(e->stream, *ld.syn, ld.plate->plan, d_x)
@@ -3373,16 +3211,14 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
     // one step: its Fo frames into a buffer of their own, which then takes d_x's place (run waits for the stream: d_x is free after it)
     const auto step = [&](uint64_t Fo, auto&& run) {
         if (er != hipSuccess) return;
-        float2* d_y = nullptr;
-        er = hipMalloc(&d_y, sizeof(float2) * Fo);
+        DevArray<float2> d_y;
+        er = d_y.alloc(Fo);
         if (er == hipSuccess) er = run(d_y);
         if (er == hipSuccess) {
-            (void)hipFree(d_x);
-            d_x = d_y;
+            d_x = std::move(d_y);
             conv = Fo;
         } else {
             (void)hipStreamSynchronize(e->stream);
-            (void)hipFree(d_y);
         }
     };
     if (ld.tail) step(ld.tail->plan.Fp, [&](float2* d_y) { return tail_run(e->stream, d_x, d_y, ld.tail->plan, ld.tail->extend); });
@@ -3392,9 +3228,6 @@ int shape_stage(mc_engine* e, const IrLoad& ld, uint64_t conv, uint64_t cap, Sha
     if (ld.parts) step(ld.parts->Fo, [&](float2* d_y) { return parts_run(e->stream, d_x, d_y, *ld.parts, out->parts); });
     if (er == hipSuccess) er = ish_shape(e->stream, d_x, conv, cap, *ld.shape, &out->d_taps, &out->n, out->sums, out->info, ld.eq, ld.damp);
     if (ld.swp && er != hipSuccess) (void)hipStreamSynchronize(e->stream);  // (the correlation may still be reading them)
-    (void)hipFree(d_x);
-    (void)hipFree(d_rec);
-    (void)hipFree(d_u);
     if (er != hipSuccess) return fail(MC_ERR_HIP, "IR shaping failed: %s", hipGetErrorString(er));
     if (!out->n) return fail(MC_ERR_ARG, "the shape leaves no frame of the IR (start %llu, %llu frames at the session's rate)",
                              (unsigned long long)ld.shape->start, (unsigned long long)conv);
@@ -3476,65 +3309,48 @@ int load_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const IrLoad& ld) {
     if (frames == 0) return fail(MC_ERR_ARG, "empty IR");
     const uint64_t conv = rs ? rs_out_frames(rs_geom(rs[0], rs[1]), frames) : frames;  // frames at the session's rate
     HIP_TRY(hipSetDevice(e->device));
-    float* d_lr = nullptr;
+    DevArray<float2> d_lr;  // the taps {L, R}
     ShapedTaps st;  // (without a shape, st.sums takes the sums of a conversion)
     if (sh) {
         int rc = quiesce(e);
         if (!rc) rc = shape_stage(e, ld, conv, e->cfg.n_ref - nframes, &st);
         if (rc) return rc;
-        d_lr = reinterpret_cast<float*>(st.d_taps);
+        d_lr.adopt(st.d_taps, st.n);
     }
     if (e->sf) {
         const int rc = sf_load_ir(e, idx, lr, frames, nframes, rs, st.d_taps, st.n, st.sums);
-        if (sh) (void)hipFree(d_lr);
         if (rc) return rc;
         note_load(e->irs[idx], ld, st.n, st);
         return MC_OK;
     }
     const uint64_t n = sh ? st.n : std::min<uint64_t>(conv, e->cfg.n_ref - nframes);  // conv.cu:239
     const int P = (int)((n + MC_B - 1) / MC_B);
-    if (P > e->Pcap) {
-        if (sh) (void)hipFree(d_lr);
-        return fail(MC_ERR_ARG, "IR needs %d partitions, engine capacity is %d", P, e->Pcap);
-    }
+    if (P > e->Pcap) return fail(MC_ERR_ARG, "IR needs %d partitions, engine capacity is %d", P, e->Pcap);
     IrEntry& ir = e->irs[idx];
     if (!sh)  // (a shaped load did this before its stage)
         if (const int rc = quiesce(e)) return rc;
     hipError_t er = hipStreamSynchronize(e->stream);
-    if (er == hipSuccess && !ir.d_H) er = hipMalloc(&ir.d_H, sizeof(float4) * (size_t)MC_NB * e->Pstride);
-    if (er == hipSuccess && !sh) er = hipMalloc(&d_lr, sizeof(float) * 2 * n);
-    if (er != hipSuccess) {
-        (void)hipFree(d_lr);
-        return fail(MC_ERR_HIP, "IR preparation failed: %s", hipGetErrorString(er));
-    }
+    if (er == hipSuccess && !ir.d_H) er = ir.d_H.alloc((size_t)MC_NB * e->Pstride);
+    if (er == hipSuccess && !sh) er = d_lr.alloc(n);
+    if (er != hipSuccess) return fail(MC_ERR_HIP, "IR preparation failed: %s", hipGetErrorString(er));
     if (!sh)
-        er = rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, reinterpret_cast<float2*>(d_lr), n, st.sums)
+        er = rs ? rs_convert(e->stream, rs[0], rs[1], lr, frames, d_lr, n, st.sums)
                 : hipMemcpy(d_lr, lr, sizeof(float) * 2 * n, hipMemcpyHostToDevice);
-    if (er == hipSuccess) er = hipMemsetAsync(ir.d_H, 0, sizeof(float4) * (size_t)MC_NB * e->Pstride, e->stream);
+    if (er == hipSuccess) er = ir.d_H.zero(e->stream);
     if (er == hipSuccess) {
-        hipLaunchKernelGGL(k_fwd<false>, dim3((P + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, e->stream, d_lr, d_lr + 1, 2, (int64_t)n, P,
+        const float* const taps = reinterpret_cast<const float*>(d_lr.get());
+        hipLaunchKernelGGL(k_fwd<false>, dim3((P + FWD_TILE - 1) / FWD_TILE), dim3(XF_THREADS), 0, e->stream, taps, taps + 1, 2, (int64_t)n, P,
                            ir.d_H, e->Pstride, 0, (const BlockParams*)nullptr, 0, (float4*)nullptr, (float4*)nullptr, e->d_tw,
                            (uint2*)nullptr, (float*)nullptr, 0, (float4*)nullptr, 0, (int64_t)0, 0, P, P, 0, 0, DropAhead(), 0);
         er = hipGetLastError();
     }
     if (er == hipSuccess) er = hipStreamSynchronize(e->stream);
-    if (er != hipSuccess) {
-        (void)hipFree(d_lr);
-        return fail(MC_ERR_HIP, "IR preparation failed: %s", hipGetErrorString(er));
-    }
-    if (ir.d_h) (void)hipFree(ir.d_h);
-    if (ir.d_Htail) {
-        (void)hipFree(ir.d_Htail);
-        ir.d_Htail = nullptr;
-    }
-    ir.d_h = reinterpret_cast<float2*>(d_lr);  // the truncated taps stay on the device for the Q8 pass
+    if (er != hipSuccess) return fail(MC_ERR_HIP, "IR preparation failed: %s", hipGetErrorString(er));
+    ir.d_Htail.reset();
+    ir.d_h = std::move(d_lr);  // the truncated taps stay on the device for the Q8 pass
     invalidate_derived(ir);
     e->ir_gen++;
-    for (int l = 0; l < 3; l++)  // (a reloaded IR gives its fast-FIR components back; the stream is idle here)
-        if (ir.d_Hp[l]) {
-            (void)hipFree(ir.d_Hp[l]);
-            ir.d_Hp[l] = nullptr;
-        }
+    for (int l = 0; l < 3; l++) ir.d_Hp[l].reset();  // (a reloaded IR gives its fast-FIR components back; the stream is idle here)
     if (e->half) {
         // scaled fp16 copy: one power-of-two scale per IR puts the largest bin near 2^13 (half max 65504);
         // a 60 dB decay then still sits ~2^3 above the smallest normal half
@@ -3546,7 +3362,7 @@ int load_ir(mc_engine* e, uint64_t idx, uint64_t nframes, const IrLoad& ld) {
         int ex = 0;
         if (mx > 0.f) std::frexp(mx, &ex);
         ir.scale16 = std::ldexp(1.0f, std::min(13 - ex, kScale16MaxExp));
-        if (!ir.d_H16) HIP_TRY(hipMalloc(&ir.d_H16, sizeof(uint2) * nel));
+        if (!ir.d_H16) HIP_TRY(ir.d_H16.alloc(nel));
         hipLaunchKernelGGL(k_to_half, dim3(1024), dim3(256), 0, e->stream, ir.d_H, ir.d_H16, nel, ir.scale16);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(e->stream));
@@ -4880,7 +4696,7 @@ int mc_set_stream(mc_engine* e, void* s) {
         if (rc) return rc;
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
-    e->stream = s ? (hipStream_t)s : e->own_stream;
+    e->stream = s ? (hipStream_t)s : (hipStream_t)e->own_stream;
     return MC_OK;
 }
 
@@ -4891,15 +4707,9 @@ double mc_avg_runtime_ms(const mc_engine* e) { return (e && e->nruns > 0) ? e->r
 int mc_enable_kernel_timing(mc_engine* e, int on) {
     if (!e) return fail(MC_ERR_ARG, "null engine");
     HIP_TRY(hipSetDevice(e->device));
-    if (on && !e->kev_created) {
-        for (int i = 0; i < kEvPool; i++) {
-            HIP_TRY(hipEventCreate(&e->kev[i][0]));
-            HIP_TRY(hipEventCreate(&e->kev[i][1]));
-            e->kev_stamped[i] = false;
-        }
-        HIP_TRY(hipMalloc(&e->d_stamps, sizeof(unsigned long long) * 2 * MC_STAMP_WGS * kStampSlots));
-        HIP_TRY(reset_stamps(e));
-        e->kev_created = true;
+    if (on && !e->kt) {
+        HIP_TRY(make_group(e->kt, (size_t)2 * MC_STAMP_WGS * kStampSlots));
+        for (int i = 0; i < kEvPool; i++) e->kev_stamped[i] = false;
     }
     if (!on) {
         int rc = drain_kernel_events(e);
@@ -4976,8 +4786,8 @@ int mc_debug_read(mc_engine* e, int which, uint64_t idx, void* dst, uint64_t off
         if (!dst || !bytes) return MC_OK;
         const char* src = nullptr;
         uint64_t cap = 0;
-        if (which == 0 && idx < (uint64_t)kMaxIrs && e->irs[idx].d_S) src = (const char*)e->irs[idx].d_S, cap = sizeof(float2) * e->cfg.n_ref;
-        else if (which == 4) src = (const char*)e->sf->d_acc, cap = sizeof(float) * 2 * e->cfg.n_ref;
+        if (which == 0 && idx < (uint64_t)kMaxIrs && e->irs[idx].d_S) src = (const char*)e->irs[idx].d_S.get(), cap = sizeof(float2) * e->cfg.n_ref;
+        else if (which == 4) src = (const char*)e->sf->d_acc.get(), cap = sizeof(float) * 2 * e->cfg.n_ref;
         else return fail(MC_ERR_ARG, "nothing to read for item %d in the single-transform form", which);
         if (off > cap || bytes > cap - off) return fail(MC_ERR_ARG, "read outside the buffer");
         HIP_TRY(hipStreamSynchronize(e->stream));
@@ -5037,15 +4847,15 @@ int mc_debug_read(mc_engine* e, int which, uint64_t idx, void* dst, uint64_t off
     switch (which) {
         case 0:  // (items 0, 18 and 20 also read the merged-IR entries kMaxIrs .. kMaxIrs + kMixIrs - 1)
             if (idx >= (uint64_t)(kMaxIrs + kMixIrs) || !e->irs[idx].d_H) return fail(MC_ERR_ARG, "IR not loaded");
-            src = (const char*)e->irs[idx].d_H;
+            src = (const char*)e->irs[idx].d_H.get();
             cap = sizeof(float4) * (uint64_t)MC_NB * e->Pstride;
             break;
         case 18:  // the fp16 copy of IR idx's spectra, scaled by item 20 (uint2 [256][pstride])
             if (idx >= (uint64_t)(kMaxIrs + kMixIrs) || !e->irs[idx].d_H || !e->irs[idx].d_H16) return fail(MC_ERR_ARG, "IR not loaded");
-            src = (const char*)e->irs[idx].d_H16;
+            src = (const char*)e->irs[idx].d_H16.get();
             cap = sizeof(uint2) * (uint64_t)MC_NB * e->Pstride;
             break;
-        case 19: src = (const char*)e->d_fdl16; cap = sizeof(uint2) * (uint64_t)MC_NB * e->ring; break;
+        case 19: src = (const char*)e->d_fdl16.get(); cap = sizeof(uint2) * (uint64_t)MC_NB * e->ring; break;
         case 20: {  // scale16 of IR idx (one float): a host-side word, read behind the stream like the copy it belongs to
             if (idx >= (uint64_t)(kMaxIrs + kMixIrs) || !e->irs[idx].d_H || !e->irs[idx].d_H16) return fail(MC_ERR_ARG, "IR not loaded");
             if (off + bytes > sizeof(float)) return fail(MC_ERR_ARG, "read beyond the scale");
@@ -5054,20 +4864,20 @@ int mc_debug_read(mc_engine* e, int which, uint64_t idx, void* dst, uint64_t off
             std::memcpy(dst, reinterpret_cast<const char*>(&e->irs[idx].scale16) + off, bytes);
             return MC_OK;
         }
-        case 21: src = (const char*)e->d_slotgain; cap = sizeof(float4) * (uint64_t)MC_MAXV * e->ring; break;
+        case 21: src = (const char*)e->d_slotgain.get(); cap = sizeof(float4) * (uint64_t)MC_MAXV * e->ring; break;
         case 17:  // the stored time-domain taps of IR idx (float2 [taps]: converted to the session's rate by mc_load_ir_resampled)
             if (idx >= (uint64_t)kMaxIrs || !e->irs[idx].d_h) return fail(MC_ERR_ARG, "IR not loaded");
-            src = (const char*)e->irs[idx].d_h;
+            src = (const char*)e->irs[idx].d_h.get();
             cap = sizeof(float2) * e->irs[idx].taps;
             break;
-        case 1: src = (const char*)e->d_fdl; cap = sizeof(float4) * (uint64_t)MC_NB * e->ring; break;
+        case 1: src = (const char*)e->d_fdl.get(); cap = sizeof(float4) * (uint64_t)MC_NB * e->ring; break;
         case 2: src = (const char*)e->d_Y; cap = sizeof(float4) * (uint64_t)MC_NB * y_capacity(e); break;
-        case 3: src = (const char*)e->d_seg; cap = sizeof(float) * (uint64_t)e->sr * 2 * FFT_N; break;
-        case 4: src = (const char*)e->d_wet; cap = sizeof(float) * 2 * (uint64_t)e->wr; break;
-        case 5: src = (const char*)e->d_cring; cap = sizeof(double) * 4 * (uint64_t)e->rc; break;
-        case 12: src = (const char*)e->d_os_T; cap = sizeof(float4) * (uint64_t)OS_ITEMS * OS_N2 * e->os_T_segs; break;
-        case 13: src = (const char*)e->d_os_SP; cap = e->d_os_SP ? sizeof(float4) * (uint64_t)OS_ITEMS * OS_N2 * 2 : 0; break;
-        case 14: src = (const char*)e->d_os_SP0; cap = e->d_os_SP0 ? sizeof(float4) * 2 * (uint64_t)OS_N2 : 0; break;
+        case 3: src = (const char*)e->d_seg.get(); cap = sizeof(float) * (uint64_t)e->sr * 2 * FFT_N; break;
+        case 4: src = (const char*)e->d_wet.get(); cap = sizeof(float) * 2 * (uint64_t)e->wr; break;
+        case 5: src = (const char*)e->d_cring.get(); cap = sizeof(double) * 4 * (uint64_t)e->rc; break;
+        case 12: src = (const char*)e->d_os_T.get(); cap = sizeof(float4) * e->d_os_T.size(); break;
+        case 13: src = (const char*)e->d_os_SP.get(); cap = e->d_os_SP ? sizeof(float4) * (uint64_t)OS_ITEMS * OS_N2 * 2 : 0; break;
+        case 14: src = (const char*)e->d_os_SP0.get(); cap = e->d_os_SP0 ? sizeof(float4) * 2 * (uint64_t)OS_N2 : 0; break;
         default: return fail(MC_ERR_ARG, "unknown buffer %d", which);
     }
     if (off + bytes > cap) return fail(MC_ERR_ARG, "read beyond buffer (%llu + %llu > %llu)", (unsigned long long)off, (unsigned long long)bytes, (unsigned long long)cap);

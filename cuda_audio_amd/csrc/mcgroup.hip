@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/mcconv_group.h"
+#include "mcgroup_staging.h"
 
 namespace {
 
@@ -29,14 +30,11 @@ int gfail(int code, const char* fmt, ...) {
     return code;
 }
 
-struct Rank {
-    int device = 0;
+struct Rank : RankStaging {  // (device, stream and the staging buffers d_in, d_part, d_sum, d_out: mcgroup_staging.h)
     mc_engine* eng = nullptr;
-    hipStream_t stream = nullptr;
     ncclComm_t comm = nullptr;
     uint32_t pb = 0, pe = 0;
-    float *d_in = nullptr, *d_part = nullptr, *d_sum = nullptr, *d_out = nullptr;  // [2][cap], [2][cap], [2][cap], [2][cap] frames
-    hipEvent_t ev_part = nullptr, ev_done = nullptr;
+    Event ev_part, ev_done;
     int rc = 0;
     std::string err;
 };
@@ -73,21 +71,6 @@ namespace {
         hipError_t _e = (expr);                                                                            \
         if (_e != hipSuccess) return gfail(MC_ERR_HIP, "%s -> %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
     } while (0)
-
-int ensure_buffers(mc_group* g, uint64_t frames) {
-    if (g->cap >= frames) return MC_OK;
-    for (Rank& k : g->r) {
-        G_HIP(hipSetDevice(k.device));
-        G_HIP(hipStreamSynchronize(k.stream));
-        for (float** p : {&k.d_in, &k.d_part, &k.d_sum, &k.d_out}) {
-            if (*p) (void)hipFree(*p);
-            *p = nullptr;
-            G_HIP(hipMalloc(p, sizeof(float) * 2 * frames));
-        }
-    }
-    g->cap = frames;
-    return MC_OK;
-}
 
 // one rank's share of a batch; `phase` barriers are the caller's (threads meet between partial and exchange only where
 // ranks share a device)
@@ -202,8 +185,8 @@ int mc_group_create(const mc_config* cfg, const int32_t* devices, uint32_t ndev,
             return rc;
         }
         k.stream = (hipStream_t)mc_get_stream(k.eng);
-        if (hipSetDevice(k.device) != hipSuccess || hipEventCreateWithFlags(&k.ev_part, hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&k.ev_done, hipEventDisableTiming) != hipSuccess) {
+        if (hipSetDevice(k.device) != hipSuccess || k.ev_part.create(hipEventDisableTiming) != hipSuccess ||
+            k.ev_done.create(hipEventDisableTiming) != hipSuccess) {
             mc_group_destroy(g);
             return gfail(MC_ERR_HIP, "rank %u: event creation failed", q);
         }
@@ -230,13 +213,9 @@ void mc_group_destroy(mc_group* g) {
         (void)hipSetDevice(k.device);
         if (k.stream) (void)hipStreamSynchronize(k.stream);
         if (k.comm) (void)ncclCommDestroy(k.comm);
-        for (float* p : {k.d_in, k.d_part, k.d_sum, k.d_out})
-            if (p) (void)hipFree(p);
-        if (k.ev_part) (void)hipEventDestroy(k.ev_part);
-        if (k.ev_done) (void)hipEventDestroy(k.ev_done);
         if (k.eng) mc_destroy(k.eng);
     }
-    delete g;
+    delete g;  // (the ranks' buffers and events go with it)
 }
 
 uint32_t mc_group_size(const mc_group* g) { return g ? (uint32_t)g->r.size() : 0; }
@@ -277,8 +256,7 @@ int mc_group_process_batch(mc_group* g, const float* in1, const float* in2, floa
     if (!g || !in1 || !in2 || !outL || !outR) return gfail(MC_ERR_ARG, "null argument");
     if (nblocks < 1 || nblocks > g->cfg.max_batch) return gfail(MC_ERR_ARG, "nblocks %llu outside [1, %u]", (unsigned long long)nblocks, g->cfg.max_batch);
     if (nblocks % (uint64_t)g->pm) return gfail(MC_ERR_ARG, "nblocks is not a multiple of the period");
-    int rc = ensure_buffers(g, nblocks * MC_BLOCK);
-    if (rc) return rc;
+    G_HIP(ensure_staging(g->r, g->cap, nblocks * MC_BLOCK));  // (cap reads 0 after a growth that failed: mcgroup_staging.h)
     const int n = (int)g->r.size();
     // equal runs of whole periods -> every rank finishes its run after a reduce-scatter; else rank 0 finishes all after a reduce
     const bool scatter = (n > 1 || g->solo_exchange) && nblocks % ((uint64_t)n * g->pm) == 0;

@@ -23,6 +23,8 @@
 #include <numeric>
 #include <vector>
 
+#include "owned.h"
+
 constexpr int RS_Z = 64;                  // zero crossings of the sinc on each side (at s = 1)
 constexpr double RS_BETA = 9.0;           // Kaiser window
 constexpr double RS_RHO = 0.955;          // passband fraction of the new Nyquist frequency
@@ -150,14 +152,14 @@ inline hipError_t rs_convert(hipStream_t stream, uint32_t src, uint32_t dst, con
     // input frames any of the n outputs reads: through n0(n - 1) + Wi
     const uint64_t need = std::min<uint64_t>(frames, (n - 1) * g.q / g.p + (uint64_t)g.Wi + 1);
     const bool table = g.p <= n && g.p * (uint64_t)g.L <= RS_TABLE_MAX;
-    float2* d_in = nullptr;
+    DevArray<float2> d_in;
     const unsigned grid = (unsigned)((n + RS_THREADS - 1) / RS_THREADS);
-    float* d_tab = nullptr;
-    double* d_part = nullptr;
+    DevArray<float> d_tab;
+    DevArray<double> d_part;
     std::vector<double> part(4 * (size_t)grid);
-    hipError_t er = hipMalloc(&d_in, sizeof(float2) * need);
-    if (er == hipSuccess) er = hipMalloc(&d_part, sizeof(double) * part.size());
-    if (er == hipSuccess && table) er = hipMalloc(&d_tab, sizeof(float) * g.p * (uint64_t)g.L);
+    hipError_t er = d_in.alloc(need);
+    if (er == hipSuccess) er = d_part.alloc(part.size());
+    if (er == hipSuccess && table) er = d_tab.alloc(g.p * (uint64_t)g.L);
     if (er == hipSuccess) er = hipMemcpy(d_in, lr, sizeof(float2) * need, hipMemcpyHostToDevice);
     if (er == hipSuccess) {
         if (table) {
@@ -170,9 +172,6 @@ inline hipError_t rs_convert(hipStream_t stream, uint32_t src, uint32_t dst, con
     }
     if (er == hipSuccess) er = hipMemcpyAsync(part.data(), d_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, stream);
     if (er == hipSuccess) er = hipStreamSynchronize(stream);
-    (void)hipFree(d_in);
-    (void)hipFree(d_tab);
-    (void)hipFree(d_part);
     for (int k = 0; k < 4; k++) sums[k] = 0.0;
     for (unsigned b = 0; b < grid; b++)
         for (int k = 0; k < 4; k++) sums[k] += part[4 * (size_t)b + k];

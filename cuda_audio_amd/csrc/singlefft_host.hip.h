@@ -1,26 +1,10 @@
 // singlefft_host.hip.h — host side of the single-transform form (kernels and the algorithm: singlefft.hip.h).
 // Included by mcconv.hip after its helpers (fail, HIP_TRY, pan_l ...); SfState itself is declared next to mc_engine.
-inline void sf_free(mc_engine* e) {
-    SfState* s = e->sf;
-    if (!s) return;
-    (void)hipFree(s->d_live);
-    (void)hipFree(s->d_W);
-    (void)hipFree(s->d_T);
-    (void)hipFree(s->d_Z);
-    (void)hipFree(s->d_acc);
-    (void)hipFree(s->d_ctr);
-    for (int i = 0; i < 4; i++) (void)hipFree(s->d_io[i]);
-    for (int i = 0; i < kMaxIrs; i++)
-        if (e->irs[i].d_S) (void)hipFree(e->irs[i].d_S);
-    delete s;
-    e->sf = nullptr;
-}
-
 inline int sf_zero(mc_engine* e) {
-    SfState* s = e->sf;
-    HIP_TRY(hipMemsetAsync(s->d_live, 0, sizeof(float2) * 4 * (size_t)(s->N / 2), e->stream));
-    HIP_TRY(hipMemsetAsync(s->d_acc, 0, sizeof(float) * 2 * (size_t)s->N, e->stream));
-    HIP_TRY(hipMemsetAsync(s->d_ctr, 0, sizeof(unsigned), e->stream));
+    SfState* s = e->sf.get();
+    HIP_TRY(s->d_live.zero(e->stream));
+    HIP_TRY(s->d_acc.zero(e->stream));
+    HIP_TRY(s->d_ctr.zero(e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     s->base = 0;
     e->t_abs = 0;
@@ -34,22 +18,21 @@ inline int sf_create(mc_engine* e) {
     if (e->cfg.part_begin || e->cfg.part_end || e->cfg.precision || e->cfg.pipeline)
         return fail(MC_ERR_ARG, "the single-transform form has no partitions to shard, no fp16 storage and no pipelined batches");
     if (!e->cfg.compat) return fail(MC_ERR_ARG, "the single-transform form is the reference's algorithm: compat = 1 only");
-    SfState* s = new (std::nothrow) SfState();
+    e->sf.reset(new (std::nothrow) SfState());
+    SfState* s = e->sf.get();
     if (!s) return fail(MC_ERR_NOMEM, "out of host memory");
-    e->sf = s;
     s->N = (int)N;
     s->M = (int)(N / FFT_N);
     s->AT = std::max(1, std::min(8, 2048 / s->M));
     s->lds_bytes = sizeof(float2) * (size_t)(2 * s->AT * s->M + s->M / 2);
     s->stockham = std::getenv("MCCONV_SF_STOCKHAM") != nullptr;  // (tests: the LDS transform of the long sizes at a short one)
-    HIP_TRY(hipMalloc(&s->d_live, sizeof(float2) * 4 * (size_t)(N / 2)));
-    HIP_TRY(hipMalloc(&s->d_W, sizeof(float2) * N));
-    HIP_TRY(hipMalloc(&s->d_T, sizeof(float2) * N));
-    HIP_TRY(hipMalloc(&s->d_Z, sizeof(float2) * N));
-    HIP_TRY(hipMalloc(&s->d_acc, sizeof(float) * 2 * N));
-    HIP_TRY(hipMalloc(&s->d_ctr, sizeof(unsigned)));
-    s->io_cap = (size_t)e->Tmax * MC_B;
-    for (int i = 0; i < 4; i++) HIP_TRY(hipMalloc(&s->d_io[i], sizeof(float) * s->io_cap));
+    HIP_TRY(s->d_live.alloc(4 * (size_t)(N / 2)));
+    HIP_TRY(s->d_W.alloc(N));
+    HIP_TRY(s->d_T.alloc(N));
+    HIP_TRY(s->d_Z.alloc(N));
+    HIP_TRY(s->d_acc.alloc(2 * N));
+    HIP_TRY(s->d_ctr.alloc(1));
+    for (int i = 0; i < 4; i++) HIP_TRY(s->d_io[i].alloc((size_t)e->Tmax * MC_B));
     return sf_zero(e);
 }
 
@@ -58,7 +41,7 @@ inline int sf_create(mc_engine* e) {
 // that mc_load_ir_shaped left on the device (irshape.hip.h), which then are the IR; null = none
 inline int sf_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t frames, uint64_t nframes, const uint32_t* rs = nullptr,
                       const float2* d_shaped = nullptr, uint64_t nshaped = 0, const double* shaped_sums = nullptr) {
-    SfState* s = e->sf;
+    SfState* s = e->sf.get();
     const uint64_t N = (uint64_t)s->N;
     const uint64_t n = d_shaped ? nshaped : std::min<uint64_t>(rs ? rs_out_frames(rs_geom(rs[0], rs[1]), frames) : frames, N - nframes);  // conv.cu:239
     IrEntry& ir = e->irs[idx];
@@ -83,7 +66,7 @@ inline int sf_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t fram
         }
         HIP_TRY(hipMemcpy(s->d_W, z.data(), sizeof(float2) * N, hipMemcpyHostToDevice));
     }
-    if (!ir.d_S) HIP_TRY(hipMalloc(&ir.d_S, sizeof(float2) * N));  // [H_L | H_R], N/2 bins each, bin d + M c at [d][c]
+    if (!ir.d_S) HIP_TRY(ir.d_S.alloc(N));  // [H_L | H_R], N/2 bins each, bin d + M c at [d][c]
     hipLaunchKernelGGL(k_sf_ir_cols, dim3(FFT_N / s->AT), dim3(256), s->lds_bytes, e->stream, s->N, s->M, s->AT, s->d_W, s->d_T);
     hipLaunchKernelGGL(k_sf_ir_rows, dim3(s->M / SF_ROWS), dim3(64 * SF_ROWS), 0, e->stream, s->M, s->d_T, s->d_Z, e->d_tw);
     hipLaunchKernelGGL(k_sf_ir_unpack, dim3((s->N / 2 + 255) / 256), dim3(256), 0, e->stream, s->N, s->M, s->d_Z, ir.d_S);
@@ -99,7 +82,7 @@ inline int sf_load_ir(mc_engine* e, uint64_t idx, const float* lr, uint64_t fram
 // One call of the reference's onProcess on buffers the device can read and write.  The parameters are sampled and the
 // cross-fade counters stepped (compare-exchange, no lock), as onProcess does with its public members (conv.cu:339-353).
 inline int sf_call(mc_engine* e, const float* in1, const float* in2, float* outL, float* outR, int nframes, bool publish = false) {
-    SfState* s = e->sf;
+    SfState* s = e->sf.get();
     mc_cc_value cc[2];
     e->last_gen = e->ph.sample(cc);  // (lock-free: params_handoff.h)
     for (int i = 0; i < 2; i++) e->ph.count_down(i, cc[i].vsteps, cc[i].vsteps > 0 ? 1 : 0);
@@ -117,7 +100,7 @@ inline int sf_call(mc_engine* e, const float* in1, const float* in2, float* outL
     C.pd = (int)cc[0].predelay;
     C.base = s->base;
     if (publish) {
-        C.done_flag = e->hd_flag;
+        C.done_flag = e->h_flag.dev();
         C.seq = ++e->flag_seq;
     }
     for (int i = 0; i < 2; i++) {
@@ -156,7 +139,7 @@ inline int sf_batch_device(mc_engine* e, const float* d_in1, const float* d_in2,
 
 // host buffers, any length: chunks of max_batch blocks through the staging buffers
 inline int sf_batch_host(mc_engine* e, const float* in1, const float* in2, float* outL, float* outR, int T) {
-    SfState* s = e->sf;
+    SfState* s = e->sf.get();
     if (T <= 0) return fail(MC_ERR_ARG, "nblocks must be positive");
     if (T % e->pm) return fail(MC_ERR_ARG, "nblocks %d is not a multiple of the period (%d blocks)", T, e->pm);
     for (int o = 0; o < T;) {
@@ -179,7 +162,7 @@ inline int sf_batch_host(mc_engine* e, const float* in1, const float* in2, float
 inline int sf_process(mc_engine* e, const float* in1, const float* in2, float* outL, float* outR) {
     const int nf = e->pm * MC_B;
     const size_t cap = (size_t)e->Thost * MC_B;
-    const float *pin1 = e->hd_io + 0 * cap, *pin2 = e->hd_io + 1 * cap;
+    const float *pin1 = e->h_io.dev() + 0 * cap, *pin2 = e->h_io.dev() + 1 * cap;
     if (e->bar_io) {  // straight into device memory through the BAR (write-combined: fenced before the launches)
         std::memcpy(e->d_bar + 16, in1, sizeof(float) * nf);
         std::memcpy(e->d_bar + 16 + 4 * MC_B, in2, sizeof(float) * nf);
@@ -190,17 +173,17 @@ inline int sf_process(mc_engine* e, const float* in1, const float* in2, float* o
         std::memcpy(e->h_io + 0 * cap, in1, sizeof(float) * nf);
         std::memcpy(e->h_io + 1 * cap, in2, sizeof(float) * nf);
     }
-    int rc = sf_call(e, pin1, pin2, e->hd_io + 2 * cap, e->hd_io + 3 * cap, nf, e->spin_wait);
+    int rc = sf_call(e, pin1, pin2, e->h_io.dev() + 2 * cap, e->h_io.dev() + 3 * cap, nf, e->spin_wait);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
     if (e->spin_wait) {  // the last workgroup publishes the sequence number once the period is in h_io
         const unsigned seq = e->flag_seq;
         const auto t0 = std::chrono::steady_clock::now();
         unsigned spins = 0;
-        while (__atomic_load_n(e->h_flag, __ATOMIC_ACQUIRE) != seq)
+        while (__atomic_load_n(e->h_flag.get(), __ATOMIC_ACQUIRE) != seq)
             if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(300)) {
                 HIP_TRY(hipStreamSynchronize(e->stream));
-                if (__atomic_load_n(e->h_flag, __ATOMIC_ACQUIRE) != seq) return fail(MC_ERR_HIP, "period did not complete");
+                if (__atomic_load_n(e->h_flag.get(), __ATOMIC_ACQUIRE) != seq) return fail(MC_ERR_HIP, "period did not complete");
             }
     } else {
         HIP_TRY(hipStreamSynchronize(e->stream));
